@@ -8,6 +8,7 @@ value = unordered pairs aligned per second (whole job, all ranks).
 
   python bench.py                         # N = 1: phage-100k = 100 000 x 40 kb (the configuration the metric is quoted on)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py --steps K --warmup W --dump-outputs DIR   # + the last timed step's arrays as DIR/<name>.npy (float64)
 
 Default workload: `phage-100k` of SURVEY.md 8(d) (BASELINE configs[3]: 10 000 families x 10 members x 40 kb,
 seed 3), which fits one MI355X.  N > 1: the SAME set (strong scaling; `--scaling weak` multiplies the families
@@ -350,6 +351,59 @@ def out_aln_leg(gs, tasks, plain_parse_ms):
     return res
 
 
+DUMP_BUDGET = 64_000_000      # bytes of all --dump-outputs files together, .npy headers included
+NPY_HEADER = 128              # bytes numpy writes before the data of a 1-D array
+
+
+def step_outputs(sizes, cand, tasks, stats):
+    """What one step returned, grouped for dump_outputs.  The task list and its rows come in the canonical order
+    (vg_lz_align_pairs_sharded) and the set sizes by genome; the candidate pairs come in whatever order the single-GPU
+    prefilter emitted them (an unordered set, include/vclust_gpu.h), so they are put in ascending (a, b) order -- the order
+    the sharded prefilter returns -- for runs and builds to be comparable row by row."""
+    cand = cand[np.lexsort((cand['b'], cand['a']))]
+    return {
+        'genomes': {'kmer_set_sizes': sizes},
+        'pairs': {'pair_a': cand['a'], 'pair_b': cand['b'], 'pair_shared': cand['shared']},
+        'tasks': {'task_q': tasks['q'], 'task_r': tasks['r'],
+                  'n_match': stats['n_match'], 'aln_len': stats['aln_len'], 'n_regions': stats['n_regions']},
+    }
+
+
+def dump_outputs(out_dir, groups, budget=DUMP_BUDGET, seed=0):
+    """Write the arrays of the last timed step as <out_dir>/<name>.npy, float64 (every field is an integer below 2**53:
+    exact).  `groups` = {group: {name: 1-D array}}; the arrays of a group share their rows.  When everything would take
+    more than `budget` bytes, every group keeps the same fraction of its rows, drawn with a fixed seed and kept in
+    ascending order; the row numbers go to <group>_rows.npy.  Same arrays in, same files out.  Returns {name: rows written}."""
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rows = {g: len(next(iter(a.values()))) for g, a in groups.items()}
+    for g, arrs in groups.items():
+        assert all(len(a) == rows[g] for a in arrs.values()), f'arrays of {g} differ in length'
+    n_files = sum(len(a) for a in groups.values())
+    full = sum(rows[g] * 8 * len(a) for g, a in groups.items()) + NPY_HEADER * n_files
+    keep = {}
+    if full > budget:
+        # (+1 column per group: its row numbers)
+        per_frac = sum(rows[g] * 8 * (len(a) + 1) for g, a in groups.items())
+        frac = (budget - NPY_HEADER * (n_files + len(groups))) / per_frac
+        rng = np.random.default_rng(seed)
+        for g in groups:
+            keep[g] = np.sort(rng.choice(rows[g], size=int(rows[g] * frac), replace=False))
+    written = {}
+    for g, arrs in groups.items():
+        idx = keep.get(g)
+        if idx is not None:
+            np.save(out_dir / f'{g}_rows.npy', idx.astype(np.float64))
+            written[f'{g}_rows'] = len(idx)
+        else:
+            (out_dir / f'{g}_rows.npy').unlink(missing_ok=True)      # (left by an earlier, sampled dump)
+        for name, a in arrs.items():
+            a = np.asarray(a)
+            np.save(out_dir / f'{name}.npy', (a if idx is None else a[idx]).astype(np.float64))
+            written[name] = len(a) if idx is None else len(idx)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -370,7 +424,14 @@ def main():
     ap.add_argument('--no-other-workloads', action='store_true', help='skip configs[1] / [2] (phage-1k, imgvr-10k) behind the headline step')
     ap.add_argument('--no-out-aln', action='store_true', help='skip the --out-aln leg (rows + regions from one parse)')
     ap.add_argument('--placement-trials', type=int, default=4, help='placements of the prefilter workspace the first pass may try (vg_set_placement_trials; 1 = none)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (k-mer set sizes, candidate pairs in (a, b) '
+                         'order, tasks and their rows) as DIR/<name>.npy in float64, at most 64 MB in all (a seeded row sample beyond)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -437,7 +498,7 @@ def main():
         #    index build and parse at once; the canonical task list of the whole set is assembled on the host beside the
         #    kernels and places the rows (gathered over RCCL when there is more than one rank)
         tasks, stats = D.align_pairs(gs, cand, comm)
-        state.update(n_pairs=len(tasks) // 2, stats=stats, tasks=tasks)
+        state.update(n_pairs=len(tasks) // 2, stats=stats, tasks=tasks, sizes=sizes, cand=cand)
 
     api.profile_enable(False)
     for _ in range(args.warmup):
@@ -492,6 +553,10 @@ def main():
         stage_bytes, b_pre, b_aln = stage_bytes_of(lens, tk, n_pairs, args.k)
         roofline = roofline_of(prof, args.steps, step_s, stage_bytes, b_pre, b_aln, world,
                                args.workload if args.count is None else f'{args.workload}/{args.count}')
+        dumped = None
+        if args.dump_outputs:
+            dumped = dict(dir=str(args.dump_outputs), rows=dump_outputs(
+                args.dump_outputs, step_outputs(state['sizes'], state['cand'], tk, state['stats'])))
         # -- behind the timed region (nothing below touches `value`): --out-aln from one parse at this size, then configs[1] / [2]
         out_aln = None
         if world == 1 and not args.no_out_aln:
@@ -539,6 +604,7 @@ def main():
             'out_aln': out_aln,
             'other_workloads': others,
             'placement_trials': trials,
+            'dump_outputs': dumped,
             'comm': dict(kind=comm.kind, rccl_ranks=comm.rccl_ranks, strict=(kind == 'rccl-strict'), rccl_failure=rccl_failure,
                          backend=(dist.get_backend() if dist is not None else None)) if world > 1 else None,
             'per_rank': per_rank if world > 1 else None,

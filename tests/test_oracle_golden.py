@@ -175,7 +175,7 @@ def test_oracle_under_sanitizers(tmp_path, golden_dir):
     r = subprocess.run(['make', '-C', str(orc.ORACLE_DIR), 'asan'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-2000:]
     asan = orc.ORACLE_DIR / '_build' / 'oracle_cli_asan'
-    env = dict(**__import__('os').environ, ASAN_OPTIONS='detect_leaks=0:abort_on_error=1', UBSAN_OPTIONS='halt_on_error=1', OMP_NUM_THREADS='2')
+    env = dict(__import__('os').environ, ASAN_OPTIONS='detect_leaks=0:abort_on_error=1', UBSAN_OPTIONS='halt_on_error=1', OMP_NUM_THREADS='2')
     ragged = tmp_path / 'ragged.fna'
     ragged.write_text('>a\nACGTNNNNACGTACGTACGTTTGACCAGTAGGCATGCATGCATCGATCGATTTAGC\n>b desc\nACG\n>c\n\n>d\n' + 'ACGTTGCA' * 40 + '\n')
     for fasta, name in ((golden_dir / 'multifasta.fna', 'ex'), (ragged, 'rg')):
