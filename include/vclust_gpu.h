@@ -10,6 +10,8 @@
  *                        (vclust.py:1005-1017) + distance ani-shorter (vclust.py:1045-1055),
  *                        i.e. the whole body of handle_prefilter (vclust.py:1433-1471)
  *   vg_align          <- lz-ani all2all (vclust.py:1142-1181, run at vclust.py:1521)
+ *   vg_cluster        <- clusty (cmd_clusty, vclust.py:1184-1278, run at vclust.py:1557) for single, cd-hit,
+ *                        uclust and set-cover
  *   vg_version        <- `kmer-db -version` / `lz-ani --version` (vclust.py:1323-1331)
  *
  * The finer-grained functions (genome sets, integer kernels, writers) are what the two
@@ -267,6 +269,39 @@ int vg_prefilter_sharded(const char* const* fasta_paths, int n_paths, const char
                          const vg_prefilter_params* p, const vg_comm* c);
 int vg_align_sharded(const char* const* fasta_paths, int n_paths, const char* out_path,
                      const vg_align_params* p, const vg_comm* c);
+
+/* ------------------------------------------------------------------ cluster ----------- */
+/* The third stage: ani.tsv + ids file -> clusters.tsv, in place of Clusty (cmd_clusty, vclust.py:1184-1278, run at
+ * vclust.py:1539-1557) for the four algorithms with a deterministic definition; DESIGN.md section 9 is the contract.
+ * Objects are the rows of the ids file (index = row number from 0, i.e. the align stage's length order).  A row of ani.tsv
+ * passes when every minimum > 0 holds (column >= value), num_alns <= max_num_alns when that is > 0, and qidx != ridx; it
+ * links {qidx, ridx} with the metric value as weight (the maximum over duplicate and reverse rows). */
+enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3 };
+typedef struct {            /* mirrors the cluster sub-parser, vclust.py:423 ff. */
+    int algorithm;                                            /* VG_CLUSTER_* */
+    const char* metric;                                       /* "tani" | "gani" | "ani": the edge weight */
+    double min_tani, min_gani, min_ani, min_qcov, min_rcov, min_len_ratio;     /* 0 = off */
+    int max_num_alns;                                         /* 0 = off */
+    int representatives;                                      /* second column: the representative's id, not a number */
+    int num_threads; int verbosity;
+} vg_cluster_params;
+typedef struct {
+    int64_t rounds;             /* parallel rounds launched (single: hooking rounds) */
+    int64_t sweep_objects;      /* objects decided by the one-workgroup tail sweep */
+    int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
+} vg_cluster_stats;
+/* The whole stage, file to file: columns are found by header name (any --outfmt); a missing column, an index outside the
+ * ids file or a malformed number is VG_EINVAL naming the file and line, reported before any device use.  Output: header
+ * `object<TAB>cluster`, one line per object in ids-file order; clusters of >= 2 members are numbered 0, 1, ... by their
+ * earliest member, then singletons in ids-file order; with `representatives` the second column is the id of the cluster's
+ * earliest member. */
+int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p);
+/* The array-level stage: rows (q[i], r[i], w[i]) over n_objects objects, read as above (self rows dropped, duplicates
+ * merged to the maximum weight; NaN weights and indices >= n_objects are VG_EINVAL, n_objects >= 2^31 VG_EOVERFLOW).
+ * label[n_objects]: the output file's numbering; representative[n_objects]: the index of the cluster's earliest member.
+ * stats may be NULL. */
+int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_edges,
+                     int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats);
 
 /* ------------------------------------------------------------------ synthetic input --- */
 /* Workload generator of SURVEY.md 8(d) (bench / test input; no reference call site: the reference ships no

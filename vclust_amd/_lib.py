@@ -57,6 +57,21 @@ class AlignParams(C.Structure):
                 ('num_threads', C.c_int), ('verbosity', C.c_int), ('is_multifasta', C.c_int)]
 
 
+class ClusterParams(C.Structure):
+    _fields_ = [('algorithm', C.c_int), ('metric', C.c_char_p),
+                ('min_tani', C.c_double), ('min_gani', C.c_double), ('min_ani', C.c_double),
+                ('min_qcov', C.c_double), ('min_rcov', C.c_double), ('min_len_ratio', C.c_double),
+                ('max_num_alns', C.c_int), ('representatives', C.c_int), ('num_threads', C.c_int), ('verbosity', C.c_int)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [('rounds', C.c_int64), ('sweep_objects', C.c_int64), ('n_edges', C.c_int64)]
+
+
+# --algorithm values the library clusters itself (VG_CLUSTER_*); complete / leiden stay with Clusty
+CLUSTER_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2, 'set-cover': 3}
+
+
 class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('total_ms', C.c_double), ('launches', C.c_int64),
                 ('bytes', C.c_double)]
@@ -123,6 +138,9 @@ SYMBOLS = {
     'vg_lz_align_sharded': (C.c_int, [C.c_void_p, P(Task), C.c_int64, P(LzParams), C.c_void_p, P(PairStat), P(P(Region)), P(C.c_int64)]),
     'vg_prefilter_sharded': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(PrefilterParams), C.c_void_p]),
     'vg_align_sharded': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(AlignParams), C.c_void_p]),
+    'vg_cluster': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams)]),
+    'vg_cluster_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_int,
+                                   P(C.c_int32), P(C.c_int32), P(ClusterStats)]),
     'vg_synth_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_double, C.c_double, C.c_int,
                                 C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int64)]),
     'vg_profile_enable': (None, [C.c_int]),

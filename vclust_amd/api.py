@@ -9,8 +9,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (AlignParams, KernelTime, LzParams, PairCount, PairStat, PrefilterParams, Region,
-                   Task, check)
+from ._lib import (CLUSTER_ALGORITHMS, AlignParams, ClusterStats, KernelTime, LzParams, PairCount, PairStat,
+                   PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
                 'num_alns', 'len_ratio', 'qlen', 'rlen', 'nt_match', 'nt_mismatch']
@@ -229,7 +229,29 @@ class GenomeSet:
 
 
 # ---------------------------------------------------------------- whole-stage calls (vclust_amd/stages.py: no numpy)
-from .stages import align, align_params, prefilter  # noqa: E402,F401
+from .stages import align, align_params, cluster, prefilter  # noqa: E402,F401
+
+
+def cluster_graph(n_objects, q, r, w, algorithm='single'):
+    """Cluster n_objects objects linked by the rows (q[i], r[i]) of weight w[i] (vg_cluster_graph): self rows are dropped,
+    duplicate and reverse rows merged to the maximum weight.  -> (label int32[n], representative int32[n], stats dict):
+    label is the numbering of clusters.tsv, representative the index of each cluster's earliest member."""
+    if algorithm not in CLUSTER_ALGORITHMS:
+        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(CLUSTER_ALGORITHMS)})')
+    q = np.ascontiguousarray(q, dtype=np.uint32)
+    r = np.ascontiguousarray(r, dtype=np.uint32)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not len(q) == len(r) == len(w):
+        raise ValueError('q, r and w must have the same length')
+    n = int(n_objects)
+    label = np.zeros(max(n, 1), dtype=np.int32)
+    rep = np.zeros(max(n, 1), dtype=np.int32)
+    st = ClusterStats()
+    P = C.POINTER
+    check(_lib.load().vg_cluster_graph(n, q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)),
+                                       w.ctypes.data_as(P(C.c_double)), len(q), CLUSTER_ALGORITHMS[algorithm],
+                                       label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
 
 
 def set_lz_fit(weak_seed_ratio=3, anchor_margin=-1, seed_choice=3):

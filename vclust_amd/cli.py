@@ -2,9 +2,11 @@
 
 `prefilter` and `align` keep the reference's options, defaults, messages, exit codes and
 output files (vclust.py:178-421, 1380-1521) but call libvclust_gpu.so (HIP, MI355X) through
-ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster`,
-`deduplicate` and `info` stay what they are in the reference: thin wrappers over the CPU tools
-bin/clusty and bin/mfasta-tool (out of scope of the GPU path), used if those binaries exist.
+ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster` passes its
+arguments on to bin/clusty where that binary exists, as the reference does; without it, the
+single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster).  `deduplicate` and
+`info` stay what they are in the reference: thin wrappers over the CPU tools (out of scope of the
+GPU path), used if those binaries exist.
 
 Multi-GPU: start one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 vclust.py align -i x.fna -o ani.tsv ...
@@ -153,7 +155,7 @@ def get_parser() -> argparse.ArgumentParser:
         al.add_argument(f'--{name}', metavar='<int>', type=int, default=default, help=f'{text} [%(default)s]')
     common(al)
 
-    # cluster (CPU tool wrapper)
+    # cluster (bin/clusty if present, else vg_cluster for single / cd-hit / uclust / set-cover)
     cl = sub.add_parser('cluster', help='Cluster genomes based on ANI thresholds', formatter_class=fmt, add_help=False)
     clr = io_args(cl, 'Input file with ANI metrics (tsv)')
     clr.add_argument('--ids', metavar='<file>', type=_existing_path, dest='ids_path', required=True,
@@ -327,7 +329,28 @@ def handle_align(args, parser, logger):
     run_native(desc, work, args.verbosity_level, logger)
 
 
+def cluster_call(args):
+    """What the front-end hands to vg_cluster for validated cluster arguments -- the counterpart of cmd_clusty
+    (vclust.py:1184-1278): a minimum only for values > 0, the num_alns maximum only for values > 0."""
+    mins = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio') if getattr(args, k) > 0}
+    return dict(ani_path=args.input_path, ids_path=args.ids_path, out_path=args.output_path, algorithm=args.algorithm,
+                metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives, **mins)
+
+
 def handle_cluster(args, parser, logger):
+    from ._lib import CLUSTER_ALGORITHMS
+    if not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS:
+        # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster, DESIGN.md section 9)
+        if not vars(args).get(args.metric, 0):
+            parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+        from . import stages
+        call = cluster_call(args)
+        desc = (f'libvclust_gpu cluster --algorithm {args.algorithm} --metric {args.metric}'
+                + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
+                + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
+                + f' [1 GPU] -> {args.output_path}')
+        run_native(desc, lambda: stages.cluster(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
+        return
     _require_binary(BIN_CLUSTY)
     threshold = vars(args).get(args.metric, 0)
     if not threshold:

@@ -1,6 +1,7 @@
 // vg_api.cpp — the two whole-stage entry points the reference's front-end needs:
 //   vg_prefilter  replaces kmer-db build + all2all + distance (vclust.py:1433-1471)
 //   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521)
+//   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557)
 // Both are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
 #include "vg_common.h"
 #include <stdlib.h>
@@ -24,16 +25,18 @@ struct defer_scope { defer_scope() { vg_defer_mode(true); } ~defer_scope() { vg_
 // It also pays the other one-time costs of the first device operations there: the runtime's fill kernel (the first
 // hipMemsetAsync of a process loads it: 50-90 ms were seen in front of the first kernel of vg_kmer_shared) and the code
 // object of the stage's own kernels.
+enum warm_stage { WARM_PREFILTER, WARM_ALIGN, WARM_CLUSTER };
 struct device_warmup {
     std::thread th;
-    explicit device_warmup(bool align_stage) {
+    explicit device_warmup(warm_stage stage) {
         try {
-            th = std::thread([align_stage] {
+            th = std::thread([stage] {
                 try {
                     vg_require_device(); hipStream_t s = vg_stream(); (void)hipFree(nullptr);
                     void* p = vg_dev_alloc(4096);
                     (void)hipMemsetAsync(p, 0, 4096, s);
-                    if (align_stage) vg_warm_align(s); else { vg_warm_prefilter(s); (void)vg_side_stream(); }     // (a second queue costs 8-20 ms to create)
+                    if (stage == WARM_ALIGN) vg_warm_align(s);
+                    else if (stage == WARM_PREFILTER) { vg_warm_prefilter(s); (void)vg_side_stream(); }     // (a second queue costs 8-20 ms to create)
                     (void)hipStreamSynchronize(s);
                     vg_dev_free(p);
                     vg_host_mark("device warm");
@@ -67,7 +70,7 @@ extern "C" int vg_prefilter(const char* const* fasta_paths, int n_paths, const c
     vg_host_mark("vg_prefilter: enter");
     vg_one_shot_scope one_shot;
     defer_scope parked;
-    device_warmup warm(false);
+    device_warmup warm(WARM_PREFILTER);
     genomes_guard gg;
     check(vg_genomes_load_resident(fasta_paths, n_paths, p->is_multifasta, p->num_threads, &gg.g));
     warm.join();
@@ -97,7 +100,7 @@ extern "C" int vg_align(const char* const* fasta_paths, int n_paths, const char*
     vg_host_mark("vg_align: enter");
     vg_one_shot_scope one_shot;
     defer_scope parked;
-    device_warmup warm(true);
+    device_warmup warm(WARM_ALIGN);
     genomes_guard gg;
     check(vg_genomes_load_resident(fasta_paths, n_paths, p->is_multifasta, p->num_threads, &gg.g));
     warm.join();
@@ -115,5 +118,32 @@ extern "C" int vg_align(const char* const* fasta_paths, int n_paths, const char*
         check(vg_write_ani(gg.g, (const vg_task*)tasks.p, stats.data(), nt, (const vg_region*)regions.p, nr, out_path, p));
     }
     vg_host_mark("ani.tsv written");
+    VG_API_END
+}
+
+extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p) {
+    VG_API_BEGIN
+    if (!ani_path || !ids_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster: null argument");
+    if (p->algorithm < VG_CLUSTER_SINGLE || p->algorithm > VG_CLUSTER_SET_COVER) throw vg_error(VG_EINVAL, "vg_cluster: unknown algorithm");
+    if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
+        throw vg_error(VG_EINVAL, std::string("vg_cluster: metric must be tani, gani or ani, not ") + p->metric);
+    vg_host_mark("vg_cluster: enter");
+    device_warmup warm(WARM_CLUSTER);         // (the HIP context is created beside the parse)
+    std::vector<std::string> ids;
+    vg_cluster_read_ids(ids_path, ids);
+    if ((int64_t)ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
+    std::vector<uint32_t> q, r; std::vector<double> w;
+    vg_cluster_read_rows(ani_path, (int64_t)ids.size(), p, q, r, w);
+    vg_host_mark("ani.tsv parsed");
+    warm.join();
+    const int64_t n = (int64_t)ids.size();
+    std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
+    vg_cluster_stats st{};
+    check(vg_cluster_graph(n, q.data(), r.data(), w.data(), (int64_t)q.size(), p->algorithm, label.data(), rep.data(), &st));
+    vg_host_mark("clusters computed");
+    vg_cluster_write(out_path, ids, label.data(), rep.data(), p->representatives != 0);
+    if (p->verbosity >= 2)
+        fprintf(stderr, "vg_cluster: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld objects by the tail sweep\n",
+                (long long)n, (long long)q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
     VG_API_END
 }

@@ -1,0 +1,497 @@
+// vg_cluster.hip — the cluster stage on the GPU: single linkage, cd-hit, uclust and greedy set cover over the edge graph
+// of ani.tsv (in place of Clusty, cmd_clusty, vclust.py:1184-1278).  DESIGN.md section 9 states the contract and the design.
+//   edges     rows -> both directions -> radix sort on (src, dst) -> duplicates merged to the max weight -> CSR (int64 offsets)
+//   single    hook (atomicMin on the parent array) + pointer jumping, one launch each per round: label = min member
+//   cd-hit /  parallel rounds over UNDECIDED -> REP | MEMBER(rep) using edges to earlier objects, then a one-workgroup
+//   uclust    sweep in index order once a round decides too little
+//   set-cover rounds of 2-hop local maxima of (unassigned-neighbour count, -index), then a one-workgroup greedy sweep
+//   labels    min member per cluster, multi-member clusters numbered by earliest member, then singletons
+// Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
+// only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
+// their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
+#include "vg_common.h"
+#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+namespace {
+constexpr int32_t UND = -1;             // an undecided / unassigned object (state arrays are cleared with 0xff bytes)
+constexpr int TPB = 256;
+constexpr int SWEEP_TPB = 256;          // cd-hit / uclust sweep: 4 waves, two barriers per object
+constexpr int SC_TPB = 1024;            // set-cover sweep: one key block per thread block of the argmax index
+constexpr int SC_BLK = 1024;            // objects per block of the set-cover argmax index
+constexpr int SC_DIRTY_CAP = 2048;      // dirty blocks listed per pick (more: every block is recomputed)
+
+int grid_of(int64_t n, int cap = 8192) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
+
+__device__ __forceinline__ int32_t ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint64_t ld64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st64(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// one workgroup: every store / atomic this thread issued has completed before any thread of the workgroup goes on
+__device__ __forceinline__ void drain_sync() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
+
+__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// per-thread decision counts of a grid-stride kernel -> one atomic per wave (every lane reaches this point)
+__device__ __forceinline__ void add_count(unsigned long long* counter, int c) {
+    c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(counter, (unsigned long long)c);
+}
+#define GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
+// ---------------------------------------------------------------- edge graph
+// both directions of every row; a self row becomes two sentinel keys (src = n) that sort behind every edge
+__global__ void k_emit(const uint32_t* q, const uint32_t* r, const double* w, int64_t rows, uint32_t n, uint64_t* keys, double* vals) {
+    GRID_STRIDE(k, rows) {
+        const uint64_t a = q[k], b = r[k];
+        const bool self = a == b;
+        keys[2 * k] = self ? (uint64_t)n << 32 : a << 32 | b;
+        keys[2 * k + 1] = self ? (uint64_t)n << 32 : b << 32 | a;
+        vals[2 * k] = vals[2 * k + 1] = w[k];
+    }
+}
+// CSR of the sorted unique keys: off[s] = first edge of source s (off[n] = m), adj = destinations (ascending per row)
+__global__ void k_csr(const uint64_t* keys, int64_t m, int64_t n, int64_t* off, int32_t* adj) {
+    GRID_STRIDE(e, m + 1) {
+        const int64_t prev = e > 0 ? (int64_t)(keys[e - 1] >> 32) : -1;
+        const int64_t cur = e < m ? (int64_t)(keys[e] >> 32) : n;
+        for (int64_t s = prev + 1; s <= cur; ++s) off[s] = e;
+        if (e < m) adj[e] = (int32_t)(uint32_t)keys[e];
+    }
+}
+__global__ void k_iota(int32_t* a, int64_t n) { GRID_STRIDE(i, n) a[i] = (int32_t)i; }
+__global__ void k_fill(int32_t* a, int64_t n, int32_t v) { GRID_STRIDE(i, n) a[i] = v; }
+
+// ---------------------------------------------------------------- single linkage
+// every undirected edge once (dst < src): hook the larger of the two roots under the smaller; parent[x] <= x always
+__global__ void k_hook(const uint64_t* keys, int64_t m, int32_t* parent, int32_t* changed) {
+    int c = 0;
+    GRID_STRIDE(e, m) {
+        const int32_t s = (int32_t)(keys[e] >> 32), d = (int32_t)(uint32_t)keys[e];
+        if (d >= s) continue;
+        const int32_t ps = ld(parent + s), pd = ld(parent + d);
+        if (ps != pd) { atomicMin(parent + (ps > pd ? ps : pd), ps < pd ? ps : pd); c = 1; }
+    }
+    if (c) st(changed, 1);
+}
+// pointer jumping to the root (roots do not move inside this kernel; a stale read is an older ancestor)
+__global__ void k_compress(int32_t* parent, int64_t n) {
+    GRID_STRIDE(i, n) {
+        int32_t x = ld(parent + i);
+        for (;;) { const int32_t y = ld(parent + x); if (y == x) break; x = y; }
+        st(parent + i, x);
+    }
+}
+
+// ---------------------------------------------------------------- cd-hit / uclust
+// state[i]: UND, i (REP) or j < i (MEMBER of REP j).  Object i looks at its earlier neighbours only (the row prefix < i).
+//   cd-hit: the first REP in index order, provided every earlier neighbour before it is decided; REP when all are MEMBERs
+//   uclust: the REP of highest weight (ties: earliest), provided no undecided neighbour could outrank it
+__device__ __forceinline__ bool outranks(double w1, int32_t j1, double w2, int32_t j2) { return w1 > w2 || (w1 == w2 && j1 < j2); }
+
+template <bool UCLUST>
+__global__ void k_greedy_round(int64_t n, const int64_t* off, const int32_t* adj, const double* wts, int32_t* state,
+                               unsigned long long* decided) {
+    int c = 0;
+    GRID_STRIDE(i64, n) {
+        const int32_t i = (int32_t)i64;
+        if (ld(state + i) != UND) continue;
+        int32_t rep = -1, und = -1; double wrep = 0, wund = 0; bool wait = false;
+        for (int64_t k = off[i], e = off[i + 1]; k < e; ++k) {
+            const int32_t j = adj[k];
+            if (j >= i) break;
+            const int32_t s = ld(state + j);
+            if (!UCLUST) {
+                if (s == UND) { wait = true; break; }
+                if (s == j) { rep = j; break; }
+            } else {
+                const double wj = wts[k];
+                if (s == j) { if (rep < 0 || outranks(wj, j, wrep, rep)) { rep = j; wrep = wj; } }
+                else if (s == UND) { if (und < 0 || outranks(wj, j, wund, und)) { und = j; wund = wj; } }
+            }
+        }
+        if (UCLUST) wait = und >= 0 && (rep < 0 || outranks(wund, und, wrep, rep));
+        if (wait) continue;
+        st(state + i, rep >= 0 ? rep : i);
+        ++c;
+    }
+    add_count(decided, c);
+}
+
+template <bool UCLUST>
+__device__ __forceinline__ void wave_best(double& w, int32_t& j) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double w2 = __shfl_xor(w, o); const int32_t j2 = __shfl_xor(j, o);
+        if (UCLUST) { if (j2 >= 0 && (j < 0 || outranks(w2, j2, w, j))) { w = w2; j = j2; } }
+        else if (j2 >= 0 && (j < 0 || j2 < j)) j = j2;
+    }
+}
+// The tail: the remaining undecided objects in index order, one at a time (every earlier object is decided by then), each
+// neighbour list scanned by the whole workgroup.  One workgroup, launched once.
+template <bool UCLUST>
+__global__ void __launch_bounds__(SWEEP_TPB) k_greedy_sweep(int64_t n, const int64_t* off, const int32_t* adj, const double* wts,
+                                                            int32_t* state, int64_t first) {
+    __shared__ uint64_t und_mask[SWEEP_TPB / 64];
+    __shared__ double red_w[SWEEP_TPB / 64];
+    __shared__ int32_t red_j[SWEEP_TPB / 64];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    for (int64_t base = first; base < n; base += SWEEP_TPB) {
+        const int64_t mine = base + t;
+        const bool u = mine < n && ld(state + mine) == UND;
+        const uint64_t bal = __ballot(u);
+        if (lane == 0) und_mask[wv] = bal;
+        __syncthreads();
+        for (int w = 0; w < SWEEP_TPB / 64; ++w) {
+            for (uint64_t bits = und_mask[w]; bits; bits &= bits - 1) {
+                const int32_t i = (int32_t)(base + w * 64 + __builtin_ctzll(bits));
+                double bw = 0; int32_t bj = -1;
+                for (int64_t k = off[i] + t, e = off[i + 1]; k < e; k += SWEEP_TPB) {
+                    const int32_t j = adj[k];
+                    if (j >= i) break;
+                    if (ld(state + j) != j) continue;
+                    if (UCLUST) { const double wj = wts[k]; if (bj < 0 || outranks(wj, j, bw, bj)) { bw = wj; bj = j; } }
+                    else if (bj < 0) bj = j;        // (ascending: this thread's first REP is its smallest)
+                }
+                wave_best<UCLUST>(bw, bj);
+                if (lane == 0) { red_w[wv] = bw; red_j[wv] = bj; }
+                __syncthreads();
+                if (t == 0) {
+                    for (int x = 1; x < SWEEP_TPB / 64; ++x) {
+                        const int32_t j2 = red_j[x]; const double w2 = red_w[x];
+                        if (UCLUST) { if (j2 >= 0 && (bj < 0 || outranks(w2, j2, bw, bj))) { bw = w2; bj = j2; } }
+                        else if (j2 >= 0 && (bj < 0 || j2 < bj)) bj = j2;
+                    }
+                    st(state + i, bj >= 0 ? bj : i);
+                }
+                drain_sync();
+            }
+        }
+        __syncthreads();      // (und_mask is rewritten by the next chunk)
+    }
+}
+
+// ---------------------------------------------------------------- set cover
+// key of an unassigned object: (unassigned-neighbour count, -index), packed so that a larger key wins; assigned: 0
+__device__ __forceinline__ uint64_t sc_key(uint32_t cnt, int64_t i) { return (uint64_t)cnt << 32 | (uint64_t)(0xffffffffu - (uint32_t)i); }
+
+__global__ void k_sc_key(int64_t n, const int64_t* off, const int32_t* adj, const int32_t* asg, uint64_t* key) {
+    GRID_STRIDE(i, n) {
+        uint64_t kv = 0;
+        if (asg[i] == UND) {
+            uint32_t cnt = 0;
+            for (int64_t k = off[i], e = off[i + 1]; k < e; ++k) cnt += asg[adj[k]] == UND;
+            kv = sc_key(cnt, i);
+        }
+        key[i] = kv;
+    }
+}
+// out[i] = max over i and its neighbours (assigned objects too: 2-hop paths may pass through them)
+__global__ void k_sc_max(int64_t n, const int64_t* off, const int32_t* adj, const uint64_t* in, uint64_t* out) {
+    GRID_STRIDE(i, n) {
+        uint64_t v = in[i];
+        for (int64_t k = off[i], e = off[i + 1]; k < e; ++k) v = umax64(v, in[adj[k]]);
+        out[i] = v;
+    }
+}
+// an unassigned object whose key is the maximum within 2 hops is picked (asg = itself)
+__global__ void k_sc_pick(int64_t n, const int64_t* off, const int32_t* adj, const uint64_t* key, const uint64_t* m1, int32_t* asg,
+                          unsigned long long* decided) {
+    int c = 0;
+    GRID_STRIDE(i, n) {
+        if (asg[i] != UND) continue;
+        uint64_t v = m1[i];
+        for (int64_t k = off[i], e = off[i + 1]; k < e; ++k) v = umax64(v, m1[adj[k]]);
+        if (key[i] == v) { asg[i] = (int32_t)i; ++c; }
+    }
+    add_count(decided, c);
+}
+// an unassigned object next to a REP joins it: a REP of an earlier round has claimed all its neighbours already, and two picks
+// of one round are > 2 hops apart, so at most one neighbour qualifies
+__global__ void k_sc_claim(int64_t n, const int64_t* off, const int32_t* adj, int32_t* asg, unsigned long long* decided) {
+    int c = 0;
+    GRID_STRIDE(i, n) {
+        if (ld(asg + i) != UND) continue;
+        for (int64_t k = off[i], e = off[i + 1]; k < e; ++k) {
+            const int32_t j = adj[k];
+            if (ld(asg + j) == j) { st(asg + i, j); ++c; break; }
+        }
+    }
+    add_count(decided, c);
+}
+// the argmax index of the sweep: bmax[b] = max key of objects [b * SC_BLK, (b + 1) * SC_BLK)
+__device__ __forceinline__ uint64_t block_max(uint64_t v, uint64_t* red) {
+    for (int o = 32; o > 0; o >>= 1) v = umax64(v, (uint64_t)__shfl_xor((unsigned long long)v, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = 0;
+    for (int x = 0; x < (int)(blockDim.x >> 6); ++x) v = umax64(v, red[x]);
+    __syncthreads();
+    return v;
+}
+__global__ void __launch_bounds__(SC_TPB) k_sc_block_max(int64_t n, const uint64_t* key, uint64_t* bmax) {
+    __shared__ uint64_t red[SC_TPB / 64];
+    const int64_t i = (int64_t)blockIdx.x * SC_BLK + threadIdx.x;
+    const uint64_t v = block_max(i < n ? key[i] : 0, red);
+    if (threadIdx.x == 0) bmax[blockIdx.x] = v;
+}
+// The tail: the sequential greedy itself.  Each step takes the global maximum key (argmax over bmax), assigns the pick and its
+// unassigned neighbours, lowers the keys of their unassigned neighbours (one count each) and recomputes the blocks it touched.
+__global__ void __launch_bounds__(SC_TPB) k_sc_sweep(int64_t n, int64_t nb, const int64_t* off, const int32_t* adj, int32_t* asg,
+                                                     uint64_t* key, uint64_t* bmax, int32_t* dirty) {
+    __shared__ uint64_t red[SC_TPB / 64];
+    __shared__ int32_t dlist[SC_DIRTY_CAP];
+    __shared__ int32_t dcount;
+    const int t = threadIdx.x;
+    auto mark = [&](int64_t obj) {
+        const int32_t b = (int32_t)(obj / SC_BLK);
+        if (atomicExch(dirty + b, 1) == 0) { const int32_t s = atomicAdd(&dcount, 1); if (s < SC_DIRTY_CAP) dlist[s] = b; }
+    };
+    for (;;) {
+        uint64_t v = 0;
+        for (int64_t b = t; b < nb; b += SC_TPB) v = umax64(v, ld64(bmax + b));
+        const uint64_t best = block_max(v, red);
+        if (best == 0) break;                                    // every object is assigned
+        const int32_t p = (int32_t)(0xffffffffu - (uint32_t)best);
+        if (t == 0) dcount = 0;
+        __syncthreads();
+        const int64_t p0 = off[p], p1 = off[p + 1];
+        for (int64_t k = p0 + t; k < p1; k += SC_TPB) {
+            const int32_t j = adj[k];
+            if (ld(asg + j) == UND) { st(asg + j, p); st64(key + j, 0); mark(j); }
+        }
+        if (t == 0) { st(asg + p, p); st64(key + p, 0); mark(p); }
+        drain_sync();
+        for (int64_t k = p0 + t; k < p1; k += SC_TPB) {
+            const int32_t x = adj[k];
+            if (ld(asg + x) != p) continue;                      // (assigned before this step)
+            for (int64_t kk = off[x], e = off[x + 1]; kk < e; ++kk) {
+                const int32_t y = adj[kk];
+                if (ld(asg + y) == UND) { atomicSub((unsigned long long*)(key + y), 1ull << 32); mark(y); }
+            }
+        }
+        drain_sync();
+        const int32_t nd = dcount;
+        const bool all = nd > SC_DIRTY_CAP;
+        for (int64_t d = 0, e = all ? nb : nd; d < e; ++d) {
+            const int64_t b = all ? d : dlist[d];
+            const int64_t i = b * SC_BLK + t;                    // (SC_BLK == SC_TPB: one key per thread)
+            const uint64_t m = block_max(i < n ? ld64(key + i) : 0, red);
+            if (t == 0) { st64(bmax + b, m); st(dirty + b, 0); }
+        }
+        drain_sync();
+    }
+}
+
+// ---------------------------------------------------------------- labels
+// every object must carry a cluster id in [0, n) before the label kernels index with it
+__global__ void k_check_roots(const int32_t* root, int64_t n, int32_t* bad) { GRID_STRIDE(i, n) if ((uint32_t)root[i] >= (uint64_t)n) st(bad, 1); }
+__global__ void k_min_member(const int32_t* root, int64_t n, int32_t* minm) { GRID_STRIDE(i, n) atomicMin(minm + root[i], (int32_t)i); }
+__global__ void k_rep_size(const int32_t* root, const int32_t* minm, int64_t n, int32_t* rep, int32_t* size) {
+    GRID_STRIDE(i, n) { const int32_t r = minm[root[i]]; rep[i] = r; atomicAdd(size + r, 1); }
+}
+__global__ void k_flags(const int32_t* rep, const int32_t* size, int64_t n, int32_t* fm, int32_t* fs) {
+    GRID_STRIDE(i, n) { const bool head = rep[i] == (int32_t)i; fm[i] = head && size[i] >= 2; fs[i] = head && size[i] == 1; }
+}
+// label of a cluster head: multi-member clusters 0.. by earliest member, then singletons in object order
+__global__ void k_head_labels(const int32_t* fm, const int32_t* fs, const int32_t* sm, const int32_t* ss, int64_t n, int32_t* lab) {
+    const int32_t n_multi = sm[n - 1] + fm[n - 1];
+    GRID_STRIDE(i, n) { if (fm[i]) lab[i] = sm[i]; else if (fs[i]) lab[i] = n_multi + ss[i]; }
+}
+__global__ void k_gather(const int32_t* rep, const int32_t* lab, int64_t n, int32_t* label) { GRID_STRIDE(i, n) label[i] = lab[rep[i]]; }
+
+// a round that decides fewer objects than this (and < 1 % of those left) hands the rest to the one-workgroup sweep
+constexpr int64_t LOW_PROGRESS = 4096;
+bool low_progress(int64_t decided, int64_t left) { return decided < LOW_PROGRESS && decided * 100 < left; }
+
+int64_t read_counter(dbuf<unsigned long long>& c, hipStream_t s) {
+    unsigned long long v = 0;
+    c.download(&v, 1, s);
+    VG_HIP(hipStreamSynchronize(s));
+    return (int64_t)v;
+}
+
+void exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, hipStream_t s) {
+    size_t tb = 0;
+    VG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s));
+    dbuf<char> tmp(std::max<size_t>(tb, 1));
+    VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s));
+}
+}  // namespace
+
+extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats) {
+    VG_API_BEGIN
+    if (n_objects < 0 || n_rows < 0) throw vg_error(VG_EINVAL, "vg_cluster_graph: negative size");
+    if (n_objects >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_cluster_graph: 2^31 or more objects (object indices are int32)");
+    if (n_rows && (!q || !r || !w)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null rows");
+    if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null output");
+    if (algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_SET_COVER) throw vg_error(VG_EINVAL, "vg_cluster_graph: unknown algorithm");
+    {
+        std::vector<int64_t> bad((size_t)std::max(1, vg_host_threads()), -1);
+        vg_parallel_chunks(n_rows, vg_host_threads(), [&](int64_t lo, int64_t hi, int t) {
+            for (int64_t k = lo; k < hi; ++k)
+                if (q[k] >= (uint64_t)n_objects || r[k] >= (uint64_t)n_objects || std::isnan(w[k])) { bad[(size_t)t] = k; return; }
+        });
+        for (int64_t k : bad) if (k >= 0)
+            throw vg_error(VG_EINVAL, "vg_cluster_graph: row " + std::to_string(k) + ": " +
+                           (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
+    }
+    vg_cluster_stats st_local{}; vg_cluster_stats& sts = stats ? *stats : st_local;
+    sts = vg_cluster_stats{};
+    if (n_objects == 0) return VG_OK;
+    vg_require_device();
+    hipStream_t s = vg_stream();
+    const int64_t n = n_objects;
+    int bits = 1; while ((1LL << bits) <= n) ++bits;            // the sentinel source n must fit as well
+
+    // ---- edges: sort both directions by (src, dst), merge duplicates to the max weight, CSR
+    dbuf<uint64_t> ukeys; dbuf<double> uvals; int64_t m = 0;
+    if (n_rows) {
+        const int64_t nd = 2 * n_rows;
+        dbuf<uint64_t> keys((size_t)nd), keys2((size_t)nd); dbuf<double> vals((size_t)nd), vals2((size_t)nd);
+        {
+            dbuf<uint32_t> dq((size_t)n_rows), dr((size_t)n_rows); dbuf<double> dw((size_t)n_rows);
+            dq.upload(q, (size_t)n_rows, s); dr.upload(r, (size_t)n_rows, s); dw.upload(w, (size_t)n_rows, s);
+            vg_prof_scope ps("cluster_edges_emit", (double)n_rows * 48.0);
+            hipLaunchKernelGGL(k_emit, dim3(grid_of(n_rows)), dim3(TPB), 0, s, dq.p, dr.p, dw.p, n_rows, (uint32_t)n, keys.p, vals.p);
+        }
+        {
+            vg_prof_scope ps("cluster_edges_sort", (double)nd * 32.0 * 2.0);
+            size_t tb = 0;
+            VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)nd, 0u, 32u + (unsigned)bits, s));
+            dbuf<char> tmp(std::max<size_t>(tb, 1));
+            VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)nd, 0u, 32u + (unsigned)bits, s));
+        }
+        keys.release(); vals.release();
+        ukeys.alloc((size_t)nd); uvals.alloc((size_t)nd);
+        dbuf<unsigned long long> d_cnt(1);
+        {
+            vg_prof_scope ps("cluster_edges_merge", (double)nd * 32.0);
+            size_t tb = 0;
+            VG_HIP(rocprim::reduce_by_key(nullptr, tb, keys2.p, vals2.p, (size_t)nd, ukeys.p, uvals.p, d_cnt.p, rocprim::maximum<double>(),
+                                          rocprim::equal_to<uint64_t>(), s));
+            dbuf<char> tmp(std::max<size_t>(tb, 1));
+            VG_HIP(rocprim::reduce_by_key((void*)tmp.p, tb, keys2.p, vals2.p, (size_t)nd, ukeys.p, uvals.p, d_cnt.p, rocprim::maximum<double>(),
+                                          rocprim::equal_to<uint64_t>(), s));
+        }
+        m = read_counter(d_cnt, s);
+        if (m > 0) {                                             // the self-row sentinel, if any, is the last unique key
+            uint64_t last = 0;
+            vg_download_bytes(&last, ukeys.p + (m - 1), sizeof last, s);
+            VG_HIP(hipStreamSynchronize(s));
+            if ((int64_t)(last >> 32) == n) --m;
+        }
+    }
+    sts.n_edges = m / 2;
+    dbuf<int64_t> off((size_t)n + 1); dbuf<int32_t> adj((size_t)std::max<int64_t>(m, 1));
+    {
+        vg_prof_scope ps("cluster_csr", (double)m * 12.0 + (double)n * 8.0);
+        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)ukeys.p, m, n, off.p, adj.p);
+    }
+    dbuf<int32_t> root((size_t)n);
+    dbuf<unsigned long long> d_dec(1);
+
+    if (algorithm == VG_CLUSTER_SINGLE) {
+        hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n);
+        dbuf<int32_t> changed(1);
+        for (;;) {
+            for (int k = 0; k < 4; ++k) {                         // the changed word is read back every 4 rounds (of the last)
+                if (k == 3) changed.zero(s);
+                { vg_prof_scope ps("cluster_hook", (double)m * 8.0); hipLaunchKernelGGL(k_hook, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)ukeys.p, m, root.p, changed.p); }
+                { vg_prof_scope ps("cluster_compress", (double)n * 8.0); hipLaunchKernelGGL(k_compress, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n); }
+                ++sts.rounds;
+            }
+            int32_t c = 0;
+            changed.download(&c, 1, s);
+            VG_HIP(hipStreamSynchronize(s));
+            if (!c) break;
+        }
+    } else if (algorithm == VG_CLUSTER_CDHIT || algorithm == VG_CLUSTER_UCLUST) {
+        const bool uc = algorithm == VG_CLUSTER_UCLUST;
+        VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
+        int64_t left = n;
+        while (left > 0) {
+            d_dec.zero(s);
+            {
+                vg_prof_scope ps(uc ? "cluster_uclust_round" : "cluster_cdhit_round", (double)m * 12.0 + (double)n * 12.0);
+                if (uc) hipLaunchKernelGGL(k_greedy_round<true>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, d_dec.p);
+                else hipLaunchKernelGGL(k_greedy_round<false>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, d_dec.p);
+            }
+            ++sts.rounds;
+            const int64_t dec = read_counter(d_dec, s);
+            left -= dec;
+            if (left > 0 && low_progress(dec, left + dec)) {
+                // every object before the first undecided one is decided: the sweep may start at the lowest undecided index,
+                // which the host does not know -- it starts at 0 and skips decided chunks 256 at a time
+                vg_prof_scope ps(uc ? "cluster_uclust_sweep" : "cluster_cdhit_sweep", (double)m * 12.0);
+                if (uc) hipLaunchKernelGGL(k_greedy_sweep<true>, dim3(1), dim3(SWEEP_TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, (int64_t)0);
+                else hipLaunchKernelGGL(k_greedy_sweep<false>, dim3(1), dim3(SWEEP_TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, (int64_t)0);
+                sts.sweep_objects = left;
+                left = 0;
+            }
+        }
+    } else {
+        VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
+        dbuf<uint64_t> key((size_t)n), m1((size_t)n);
+        int64_t left = n;
+        while (left > 0) {
+            d_dec.zero(s);
+            {
+                vg_prof_scope ps("cluster_setcover_round", (double)m * 4.0 * 12.0);
+                hipLaunchKernelGGL(k_sc_key, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const int32_t*)root.p, key.p);
+                hipLaunchKernelGGL(k_sc_max, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const uint64_t*)key.p, m1.p);
+                hipLaunchKernelGGL(k_sc_pick, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const uint64_t*)key.p, (const uint64_t*)m1.p, root.p, d_dec.p);
+                hipLaunchKernelGGL(k_sc_claim, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, root.p, d_dec.p);
+            }
+            ++sts.rounds;
+            const int64_t dec = read_counter(d_dec, s);
+            left -= dec;
+            if (left > 0 && low_progress(dec, left + dec)) {
+                const int64_t nb = (n + SC_BLK - 1) / SC_BLK;
+                dbuf<uint64_t> bmax((size_t)nb); dbuf<int32_t> dirty((size_t)nb);
+                dirty.zero(s);
+                vg_prof_scope ps("cluster_setcover_sweep", (double)m * 12.0);
+                hipLaunchKernelGGL(k_sc_key, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const int32_t*)root.p, key.p);
+                hipLaunchKernelGGL(k_sc_block_max, dim3((unsigned)nb), dim3(SC_TPB), 0, s, n, (const uint64_t*)key.p, bmax.p);
+                hipLaunchKernelGGL(k_sc_sweep, dim3(1), dim3(SC_TPB), 0, s, n, nb, (const int64_t*)off.p, (const int32_t*)adj.p, root.p, key.p, bmax.p, dirty.p);
+                sts.sweep_objects = left;
+                left = 0;
+            }
+        }
+    }
+    VG_HIP(hipGetLastError());
+    {
+        dbuf<int32_t> bad(1); bad.zero(s);
+        hipLaunchKernelGGL(k_check_roots, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, n, bad.p);
+        int32_t b = 0; bad.download(&b, 1, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (b) throw vg_error(VG_EHIP, "vg_cluster_graph: an object was left without a cluster (internal error)");
+    }
+
+    // ---- labels: cluster id -> earliest member -> numbering
+    dbuf<int32_t> minm((size_t)n), rep((size_t)n), size((size_t)n), fm((size_t)n), fs((size_t)n), sm((size_t)n), ss((size_t)n), lab((size_t)n);
+    {
+        vg_prof_scope ps("cluster_labels", (double)n * 4.0 * 14.0);
+        size.zero(s);
+        if (algorithm == VG_CLUSTER_SET_COVER) {       // (a pick need not be its cluster's earliest member; the other ids are)
+            hipLaunchKernelGGL(k_fill, dim3(grid_of(n)), dim3(TPB), 0, s, minm.p, n, INT32_MAX);
+            hipLaunchKernelGGL(k_min_member, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, n, minm.p);
+        } else hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, minm.p, n);
+        hipLaunchKernelGGL(k_rep_size, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)minm.p, n, rep.p, size.p);
+        hipLaunchKernelGGL(k_flags, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)size.p, n, fm.p, fs.p);
+        exclusive_scan_i32(fm.p, sm.p, n, s);
+        exclusive_scan_i32(fs.p, ss.p, n, s);
+        hipLaunchKernelGGL(k_head_labels, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)fm.p, (const int32_t*)fs.p, (const int32_t*)sm.p, (const int32_t*)ss.p, n, lab.p);
+        hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)lab.p, n, minm.p);
+    }
+    VG_HIP(hipGetLastError());
+    minm.download(label, (size_t)n, s);
+    rep.download(representative, (size_t)n, s);
+    VG_HIP(hipStreamSynchronize(s));
+    VG_API_END
+}

@@ -176,6 +176,12 @@ int vg_choose_align_shift(int64_t total_len, int64_t n);
 int  vg_fmt_num(double x, char* buf);                 // LZ-ANI number format
 int  vg_fmt_len_ratio(int64_t a, int64_t b, char* buf);
 double vg_ani_shorter(int64_t shared, int64_t na, int64_t nb, int k);
+// cluster stage (vg_io.cpp): the first column of the ids file; the passing rows of ani.tsv (VG_EINVAL with file:line on a
+// missing column, an index outside the ids file or a malformed number); clusters.tsv
+void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);
+void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
+                          std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w);
+void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives);
 
 template <class F> void vg_parallel_chunks(int64_t n, int n_thr, F fn) {
     if (n_thr < 1) n_thr = 1;

@@ -4,6 +4,7 @@
 //   fltr.txt            layout of example/output/fltr.txt        
 //   ani.tsv, ids.tsv    layout of example/output/ani{,.ids}.tsv  
 //   ani.aln.tsv         layout of example/output/ani.aln.tsv     
+//   cluster stage       ids file + ani.tsv rows in, clusters.tsv out
 #include "vg_common.h"
 #include <cmath>
 #include <math.h>
@@ -16,6 +17,11 @@
 #include <numeric>
 #include <atomic>
 #include <thread>
+#include <charconv>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 // ---------------------------------------------------------------- numbers
 double vg_ani_shorter(int64_t shared, int64_t na, int64_t nb, int k) {
@@ -521,4 +527,164 @@ extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_
         if (fclose(fa)) throw vg_error(VG_EIO, std::string("write error on ") + p->out_aln_path);
     }
     VG_API_END
+}
+
+// ---------------------------------------------------------------- cluster stage: ids file, ani.tsv rows, clusters.tsv
+namespace {
+struct mapped_text {            // a whole text file, read-only mapped (empty file: n == 0)
+    const char* p = nullptr; size_t n = 0; void* m = MAP_FAILED;
+    explicit mapped_text(const char* path) {
+        const int fd = open(path, O_RDONLY);
+        if (fd < 0) throw vg_error(VG_EIO, std::string("cannot open ") + path);
+        struct stat sb;
+        if (fstat(fd, &sb) != 0) { close(fd); throw vg_error(VG_EIO, std::string("cannot stat ") + path); }
+        n = (size_t)sb.st_size;
+        if (n) {
+            m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) { close(fd); throw vg_error(VG_EIO, std::string("cannot map ") + path); }
+            (void)madvise(m, n, MADV_WILLNEED);
+            p = (const char*)m;
+        }
+        close(fd);
+    }
+    ~mapped_text() { if (m != MAP_FAILED) munmap(m, n); }
+    mapped_text(const mapped_text&) = delete; mapped_text& operator=(const mapped_text&) = delete;
+    const char* line_end(const char* a) const { const char* e = (const char*)memchr(a, '\n', (size_t)(p + n - a)); return e ? e : p + n; }
+    int64_t line_of(const char* at) const {          // 1-based line number of a position (errors only)
+        int64_t l = 1;
+        for (const char* x = p; (x = (const char*)memchr(x, '\n', (size_t)(at - x))) != nullptr; ++x) ++l;
+        return l;
+    }
+};
+[[noreturn]] void row_error(const char* path, int64_t line, const std::string& what) {
+    throw vg_error(VG_EINVAL, std::string(path) + ":" + std::to_string(line) + ": " + what);
+}
+bool parse_double(const char* a, const char* b, double& v) {
+    auto r = std::from_chars(a, b, v);
+    return r.ec == std::errc() && r.ptr == b && a != b;
+}
+}  // namespace
+
+void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids) {
+    mapped_text f(path);
+    ids.clear();
+    const char* end = f.p + f.n;
+    const char* a = f.n ? f.line_end(f.p) : end;         // (the header line)
+    while (a < end) {
+        ++a;
+        if (a >= end) break;
+        const char* e = f.line_end(a);
+        if (e > a) {
+            const char* t = (const char*)memchr(a, '\t', (size_t)(e - a));
+            ids.emplace_back(a, t ? t : e);
+        }
+        a = e;
+    }
+}
+
+void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
+                          std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w) {
+    mapped_text f(path);
+    if (!f.n) row_error(path, 1, "empty file (no header)");
+    const char* end = f.p + f.n;
+    const char* hdr_end = f.line_end(f.p);
+    std::vector<std::string> names;
+    for (const char* a = f.p; a <= hdr_end;) {
+        const char* t = (const char*)memchr(a, '\t', (size_t)(hdr_end - a));
+        const char* e = t ? t : hdr_end;
+        names.emplace_back(a, e);
+        a = e + 1;
+    }
+    auto col_of = [&](const char* name) {
+        for (size_t c = 0; c < names.size(); ++c) if (names[c] == name) return (int)c;
+        row_error(path, 1, std::string("missing column ") + name);
+    };
+    // columns: 0 qidx, 1 ridx, 2 the metric, then the active minimums and num_alns
+    std::vector<int> cols = { col_of("qidx"), col_of("ridx"), col_of(p->metric) };
+    std::vector<double> mins;
+    const std::pair<const char*, double> filters[] = { { "tani", p->min_tani }, { "gani", p->min_gani }, { "ani", p->min_ani },
+                                                       { "qcov", p->min_qcov }, { "rcov", p->min_rcov }, { "len_ratio", p->min_len_ratio } };
+    for (auto& fl : filters) if (fl.second > 0) { cols.push_back(col_of(fl.first)); mins.push_back(fl.second); }
+    const int na_slot = p->max_num_alns > 0 ? (int)cols.size() : -1;
+    if (na_slot >= 0) cols.push_back(col_of("num_alns"));
+    const int max_col = *std::max_element(cols.begin(), cols.end());
+
+    // the body cut into chunks at line starts, one per thread; each chunk keeps its passing rows and its first error
+    const char* body = hdr_end < end ? hdr_end + 1 : end;
+    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(p->num_threads > 0 ? p->num_threads : vg_host_threads(),
+                                                                 (int64_t)((end - body) >> 20) + 1));
+    std::vector<const char*> cut((size_t)nthr + 1, end);
+    cut[0] = body;
+    for (int t = 1; t < nthr; ++t) {
+        const char* x = body + (end - body) * t / nthr;
+        x = std::max(x, cut[(size_t)t - 1]);
+        cut[(size_t)t] = x < end ? std::min(end, f.line_end(x) + 1) : end;
+    }
+    struct part { std::vector<uint32_t> q, r; std::vector<double> w; const char* err_at = nullptr; std::string err; };
+    std::vector<part> parts((size_t)nthr);
+    auto work = [&](int t) {
+        part& pt = parts[(size_t)t];
+        std::vector<const char*> fb((size_t)max_col + 1), fe((size_t)max_col + 1);
+        std::vector<double> v(cols.size());
+        for (const char* a = cut[(size_t)t]; a < cut[(size_t)t + 1];) {
+            const char* e = f.line_end(a);
+            if (e == a) { a = e + 1; continue; }                // (blank line)
+            int nf = 0;
+            for (const char* x = a; nf <= max_col;) {
+                const char* tb = (const char*)memchr(x, '\t', (size_t)(e - x));
+                fb[(size_t)nf] = x; fe[(size_t)nf] = tb ? tb : e; ++nf;
+                if (!tb) break;
+                x = tb + 1;
+            }
+            if (nf <= max_col) { pt.err_at = a; pt.err = "expected " + std::to_string(names.size()) + " columns, found " + std::to_string(nf); return; }
+            uint64_t idx[2];
+            for (int k = 0; k < 2; ++k) {
+                const char* x = fb[(size_t)cols[(size_t)k]]; const char* y = fe[(size_t)cols[(size_t)k]];
+                auto rr = std::from_chars(x, y, idx[k]);
+                if (rr.ec != std::errc() || rr.ptr != y || x == y) { pt.err_at = a; pt.err = "malformed " + names[(size_t)cols[(size_t)k]] + " '" + std::string(x, y) + "'"; return; }
+                if (idx[k] >= (uint64_t)n_objects) {
+                    pt.err_at = a; pt.err = names[(size_t)cols[(size_t)k]] + " " + std::to_string(idx[k]) + " outside the ids file (" + std::to_string(n_objects) + " objects)"; return;
+                }
+            }
+            for (size_t k = 2; k < cols.size(); ++k) {
+                const char* x = fb[(size_t)cols[k]]; const char* y = fe[(size_t)cols[k]];
+                if (!parse_double(x, y, v[k])) { pt.err_at = a; pt.err = "malformed " + names[(size_t)cols[k]] + " '" + std::string(x, y) + "'"; return; }
+            }
+            bool pass = idx[0] != idx[1];
+            for (size_t k = 0; k < mins.size() && pass; ++k) pass = v[3 + k] >= mins[k];
+            if (pass && na_slot >= 0) pass = v[(size_t)na_slot] <= (double)p->max_num_alns;
+            if (pass) { pt.q.push_back((uint32_t)idx[0]); pt.r.push_back((uint32_t)idx[1]); pt.w.push_back(v[2]); }
+            a = e + 1;
+        }
+    };
+    {
+        std::vector<std::thread> th;
+        for (int t = 1; t < nthr; ++t) th.emplace_back(work, t);
+        work(0);
+        for (auto& x : th) x.join();
+    }
+    size_t total = 0;
+    for (auto& pt : parts) {
+        if (pt.err_at) row_error(path, f.line_of(pt.err_at), pt.err);
+        total += pt.q.size();
+    }
+    q.clear(); r.clear(); w.clear();
+    q.reserve(total); r.reserve(total); w.reserve(total);
+    for (auto& pt : parts) {
+        q.insert(q.end(), pt.q.begin(), pt.q.end()); r.insert(r.end(), pt.r.begin(), pt.r.end()); w.insert(w.end(), pt.w.begin(), pt.w.end());
+    }
+}
+
+void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives) {
+    std::string o = "object\tcluster\n";
+    o.reserve(ids.size() * 24 + 16);
+    for (size_t i = 0; i < ids.size(); ++i) {
+        o += ids[i]; o.push_back('\t');
+        if (representatives) o += ids[(size_t)rep[i]]; else o += std::to_string(label[i]);
+        o.push_back('\n');
+    }
+    FILE* f = fopen(path, "w");
+    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + path);
+    if (fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
+    if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + path);
 }

@@ -1,11 +1,12 @@
-"""The two whole-stage calls of the drop-in CLI (vg_prefilter, vg_align: FASTA on disk -> fltr.txt / ani.tsv on disk) as
-thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align` process is one of these calls, and importing numpy
-costs it 60-180 ms of its ~1 s.  vclust_amd.api re-exports them beside the array-level API."""
+"""The whole-stage calls of the drop-in CLI (vg_prefilter, vg_align: FASTA on disk -> fltr.txt / ani.tsv on disk; vg_cluster:
+ani.tsv + ids file -> clusters.tsv) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster` process is
+one of these calls, and importing numpy costs it 60-180 ms of its ~1 s.  vclust_amd.api re-exports them beside the
+array-level API."""
 import ctypes as C
 import os
 
 from . import _lib
-from ._lib import AlignParams, LzParams, PrefilterParams, check
+from ._lib import CLUSTER_ALGORITHMS, AlignParams, ClusterParams, LzParams, PrefilterParams, check
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -45,3 +46,22 @@ def align(paths, out_path, is_multifasta, columns, filter_path=None, filter_thre
     arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
     p = align_params(columns, filter_path, filter_threshold, out_aln, lz, out_filters, num_threads, verbosity, is_multifasta)
     check(lib.vg_align(arr, len(paths), os.fsencode(str(out_path)), C.byref(p)))
+
+
+CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
+
+
+def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num_alns=0, representatives=False,
+            num_threads=0, verbosity=0, **mins):
+    """clusters.tsv from ani.tsv + its ids file (vg_cluster).  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio= (0 = off);
+    num_alns: max. number of local alignments of a passing row (0 = off)."""
+    unknown = set(mins) - set(CLUSTER_FILTERS)
+    if unknown:
+        raise TypeError(f'unknown filter(s): {sorted(unknown)}')
+    if algorithm not in CLUSTER_ALGORITHMS:
+        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(CLUSTER_ALGORITHMS)})')
+    p = ClusterParams(algorithm=CLUSTER_ALGORITHMS[algorithm], metric=metric.encode(), max_num_alns=int(num_alns),
+                      representatives=int(bool(representatives)), num_threads=int(num_threads), verbosity=int(verbosity))
+    for name, val in mins.items():
+        setattr(p, f'min_{name}', float(val))
+    check(_lib.load().vg_cluster(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)), C.byref(p)))
