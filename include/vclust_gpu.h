@@ -12,6 +12,7 @@
  *   vg_align          <- lz-ani all2all (vclust.py:1142-1181, run at vclust.py:1521)
  *   vg_cluster        <- clusty (cmd_clusty, vclust.py:1184-1278, run at vclust.py:1557) for single, cd-hit,
  *                        uclust and set-cover
+ *   vg_deduplicate    <- mfasta-tool mrds (cmd_mfasta_deduplicate, vclust.py:810-866, run at vclust.py:1351)
  *   vg_version        <- `kmer-db -version` / `lz-ani --version` (vclust.py:1323-1331)
  *
  * The finer-grained functions (genome sets, integer kernels, writers) are what the two
@@ -302,6 +303,41 @@ int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path,
  * stats may be NULL. */
 int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_edges,
                      int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats);
+
+/* ------------------------------------------------------------------ deduplicate ------- */
+/* The first stage: FASTA files -> one FASTA of the distinct sequences + a duplicates list, in place of mfasta-tool
+ * (cmd_mfasta_deduplicate, vclust.py:810-866, run at vclust.py:1351); DESIGN.md section 10 is the contract.  A record's sequence is its lines
+ * without white space (space, tab, CR, LF), over the IUPAC codes ACGTRYSWKMBDHVN and '-', case-insensitive.  Two records
+ * are duplicates when the sequences are equal or one is the reverse complement of the other; the earliest record of a
+ * group is kept. */
+typedef struct {
+    int gzip_level;             /* 0 = plain output; 1..9 = gzip members compressed at that level */
+    int num_threads;            /* host threads (0 = the library's default) */
+    int verbosity;              /* >= 1: one summary line on stderr */
+} vg_dedup_params;
+typedef struct {
+    int64_t records;            /* records read */
+    int64_t unique;             /* records kept */
+    int64_t removed;            /* records - unique */
+    int64_t reverse;            /* removed records equal to the reverse complement of the kept one only */
+    int64_t rounds;             /* verification rounds on the device */
+    int64_t collisions;         /* candidate members that differed from their candidate head (hash collisions) */
+} vg_dedup_stats;
+/* The whole stage, file to file.  prefixes: NULL or n_paths strings put in front of every header of that file's records.
+ * A byte outside the alphabet is VG_EINVAL `<file>:<line>: '<c>' is not an IUPAC nucleotide code`, reported before any
+ * kernel runs; 2^31 or more records is VG_EOVERFLOW.  out_path gets the kept records in input order (header line
+ * prefixed, sequence lines verbatim); dup_path the header `representative<TAB>duplicate<TAB>strand` and one line per
+ * removed record. */
+int vg_deduplicate(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                   const char* dup_path, const vg_dedup_params* p);
+/* The array-level stage: n sequences, sequence i = ascii[offsets[i] .. offsets[i + 1]) (white space skipped).
+ * representative[i]: the index of the earliest record equal to i or to its reverse complement (i for a kept record);
+ * strand[i]: 0 if record i equals its representative, 1 if it equals only the representative's reverse complement.
+ * stats may be NULL. */
+int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
+                  vg_dedup_stats* stats);
+/* test knob: keep only the low `bits` (0..128) bits of the sequence hash (forces collisions); 128 = the default */
+void vg_dedup_set_hash_bits(int bits);
 
 /* ------------------------------------------------------------------ synthetic input --- */
 /* Workload generator of SURVEY.md 8(d) (bench / test input; no reference call site: the reference ships no

@@ -72,6 +72,15 @@ class ClusterStats(C.Structure):
 CLUSTER_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2, 'set-cover': 3}
 
 
+class DedupParams(C.Structure):
+    _fields_ = [('gzip_level', C.c_int), ('num_threads', C.c_int), ('verbosity', C.c_int)]
+
+
+class DedupStats(C.Structure):
+    _fields_ = [('records', C.c_int64), ('unique', C.c_int64), ('removed', C.c_int64), ('reverse', C.c_int64),
+                ('rounds', C.c_int64), ('collisions', C.c_int64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('total_ms', C.c_double), ('launches', C.c_int64),
                 ('bytes', C.c_double)]
@@ -141,6 +150,9 @@ SYMBOLS = {
     'vg_cluster': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams)]),
     'vg_cluster_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_int,
                                    P(C.c_int32), P(C.c_int32), P(ClusterStats)]),
+    'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
+    'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),
+    'vg_dedup_set_hash_bits': (None, [C.c_int]),
     'vg_synth_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_double, C.c_double, C.c_int,
                                 C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int64)]),
     'vg_profile_enable': (None, [C.c_int]),

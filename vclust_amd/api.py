@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, AlignParams, ClusterStats, KernelTime, LzParams, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, AlignParams, ClusterStats, DedupStats, KernelTime, LzParams, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -229,7 +229,7 @@ class GenomeSet:
 
 
 # ---------------------------------------------------------------- whole-stage calls (vclust_amd/stages.py: no numpy)
-from .stages import align, align_params, cluster, prefilter  # noqa: E402,F401
+from .stages import align, align_params, cluster, deduplicate as deduplicate_files, prefilter  # noqa: E402,F401
 
 
 def cluster_graph(n_objects, q, r, w, algorithm='single'):
@@ -252,6 +252,30 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
                                        w.ctypes.data_as(P(C.c_double)), len(q), CLUSTER_ALGORITHMS[algorithm],
                                        label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
+
+
+def deduplicate(seqs):
+    """Group the sequences `seqs` (str or bytes each; white space is skipped, case ignored) by equality up to reverse
+    complement (vg_dedup_seqs).  -> (representative int32[n], strand int8[n], stats dict): representative[i] is the index of
+    the earliest sequence of i's group, strand[i] is 1 when i equals only that sequence's reverse complement, else 0."""
+    bufs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    n = len(bufs)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        offsets[1:] = np.cumsum([len(b) for b in bufs])
+    ascii = b''.join(bufs)
+    rep = np.zeros(max(n, 1), dtype=np.int32)
+    strand = np.zeros(max(n, 1), dtype=np.int8)
+    st = DedupStats()
+    P = C.POINTER
+    check(_lib.load().vg_dedup_seqs(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, rep.ctypes.data_as(P(C.c_int32)),
+                                    strand.ctypes.data_as(P(C.c_int8)), C.byref(st)))
+    return rep[:n], strand[:n], {k: getattr(st, k) for k, _ in DedupStats._fields_}
+
+
+def dedup_set_hash_bits(bits=128):
+    """Test knob (vg_dedup_set_hash_bits): keep only the low `bits` bits of the sequence hash; 128 = the default."""
+    _lib.load().vg_dedup_set_hash_bits(int(bits))
 
 
 def set_lz_fit(weak_seed_ratio=3, anchor_margin=-1, seed_choice=3):

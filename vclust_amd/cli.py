@@ -4,9 +4,9 @@
 output files (vclust.py:178-421, 1380-1521) but call libvclust_gpu.so (HIP, MI355X) through
 ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster` passes its
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
-single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster).  `deduplicate` and
-`info` stay what they are in the reference: thin wrappers over the CPU tools (out of scope of the
-GPU path), used if those binaries exist.
+single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster).  `deduplicate` does
+the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
+without it.  `info` reports the library and the optional CPU tools.
 
 Multi-GPU: start one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 vclust.py align -i x.fna -o ani.tsv ...
@@ -96,7 +96,7 @@ def get_parser() -> argparse.ArgumentParser:
     parser.add_argument('-h', '--help', action='help', help='Show this help message and exit')
     sub = parser.add_subparsers(dest='command')
 
-    # deduplicate (CPU tool wrapper, out of scope of the GPU path)
+    # deduplicate (bin/mfasta-tool if present, else vg_deduplicate)
     dd = sub.add_parser('deduplicate', help='Deduplicate and merge genome sequences from multiple FASTA files',
                         formatter_class=fmt, add_help=False)
     ddr = dd.add_argument_group('required arguments')
@@ -371,7 +371,48 @@ def handle_cluster(args, parser, logger):
     run_subprocess(cmd, args.verbosity_level, logger)
 
 
+def validate_args_deduplicate(args, parser):
+    """The reference's checks and defaults (validate_args_deduplicate, vclust.py:705-728): one prefix per file and no
+    comma in any, a bare --add-prefixes means `<file stem before the first '.'>|`, a gzip level in 1..9, `.gz` added to
+    the output name under --gzip-output, and the duplicates file `<output>.duplicates.txt`.  Directories are not FASTA
+    files here."""
+    for f in args.input_path:
+        if f.is_dir():
+            parser.error(f'{f} is a directory; deduplicate takes FASTA files')
+    if args.add_prefixes:
+        if len(args.add_prefixes) != len(args.input_path):
+            parser.error('Number of prefixes must match the number of input files.')
+        if any(',' in prefix for prefix in args.add_prefixes):
+            parser.error('Prefixes cannot contain commas.')
+    elif args.add_prefixes == []:
+        args.add_prefixes = [f'{f.stem.split(".")[0]}|' for f in args.input_path]
+    if not (1 <= args.gzip_level <= 9):
+        parser.error('Compression level must be between 1 and 9.')
+    if args.gzip_output and not args.output_path.suffix == '.gz':
+        args.output_path = pathlib.Path(f'{args.output_path}.gz')
+    args.output_duplicates_path = pathlib.Path(f'{args.output_path}.duplicates.txt')
+    return args
+
+
+def deduplicate_call(args):
+    """What the front-end hands to vg_deduplicate for validated deduplicate arguments."""
+    return dict(paths=args.input_path, out_path=args.output_path, dup_path=args.output_duplicates_path,
+                prefixes=args.add_prefixes or None, gzip_level=args.gzip_level if args.gzip_output else 0,
+                num_threads=args.num_threads)
+
+
 def handle_deduplicate(args, parser, logger):
+    if not BIN_MFASTA.exists():
+        # no mfasta-tool: the GPU (vg_deduplicate, DESIGN.md section 10)
+        args = validate_args_deduplicate(args, parser)
+        from . import stages
+        call = deduplicate_call(args)
+        desc = (f'libvclust_gpu deduplicate -i {" ".join(str(f) for f in args.input_path)}'
+                + (f' --add-prefixes {" ".join(args.add_prefixes)}' if args.add_prefixes else '')
+                + (f' --gzip-level {args.gzip_level}' if args.gzip_output else '')
+                + f' [1 GPU] -> {args.output_path}, {args.output_duplicates_path}')
+        run_native(desc, lambda: stages.deduplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
+        return
     _require_binary(BIN_MFASTA)
     out_dup = pathlib.Path(f'{args.output_path}.duplicates.txt')
     cmd = [str(BIN_MFASTA), 'mrds', '-i', ','.join(str(f) for f in args.input_path), '-o', str(args.output_path),

@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <thread>
 #include <exception>
+#include <memory>
 #include "../../include/vclust_gpu.h"
 
 // ---------------------------------------------------------------- errors
@@ -182,6 +183,16 @@ void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);
 void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
                           std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w);
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives);
+
+// deduplicate stage (vg_genomes.cpp): the input files whole in memory (plain files mapped, gzip / BGZF inflated) and every
+// record in command-line and file order; a record is its header line [hdr, hdr_end) without '>' and its sequence lines [seq, end)
+struct vg_fasta_rec { const char* hdr; const char* hdr_end; const char* seq; const char* end; int file; };
+struct vg_fasta_text {
+    std::shared_ptr<void> bufs;                 // owns the mappings / inflated text
+    std::vector<const char*> file_data; std::vector<size_t> file_len;
+    std::vector<vg_fasta_rec> recs;
+};
+void vg_fasta_read(const char* const* paths, int n_paths, int n_threads, vg_fasta_text& out);
 
 template <class F> void vg_parallel_chunks(int64_t n, int n_thr, F fn) {
     if (n_thr < 1) n_thr = 1;

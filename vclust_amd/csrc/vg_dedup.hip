@@ -1,0 +1,562 @@
+// vg_dedup.hip — the deduplicate stage on the GPU (in place of mfasta-tool, cmd_mfasta_deduplicate, vclust.py:810-866).
+// DESIGN.md section 10 states the contract and the design.
+//   pack      host threads, one record at a time: every symbol -> 4 bits, its set of bases (A=1 C=2 G=4 T=8, '-'=0), eight
+//             per uint32 word, records starting on 4-word boundaries; the alphabet is checked in the same pass; stretches of
+//             records travel to the HBM while later ones are packed
+//   hash      one wave per (record, chunk of HASH_CHUNK words): 16-byte loads, a 128-bit sum of mixed (word index, word) terms
+//             of the forward strand and of the reverse complement (complement = bit reversal of a nibble, so
+//             v_bfrev_b32 of an 8-symbol word is its reverse complement; v_alignbit_b32 re-frames the words when the length
+//             is not a multiple of 8); the sums are added with 64-bit atomics, so the result does not depend on the order
+//   sort      key (length, min(fw, rc)): LSD radix passes (rocPRIM) over the two hash halves and the length; the
+//             orientation bit says which strand gave the minimum
+//   verify    rounds over the unresolved records in key order: the earliest record of every run of equal keys is the
+//             candidate head, every other member is compared in full with it (one wave per (member, chunk)) in the
+//             orientation the two bits imply; members that differ (hash collisions) stay for the next round
+//   labels    representative (int32) and strand (int8) per record, the only arrays that come back
+#include "vg_common.h"
+#include <rocprim/rocprim.hpp>
+#include <zlib.h>
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <cstdio>
+#include <mutex>
+#include <sys/stat.h>
+
+namespace {
+constexpr int TPB = 256;
+constexpr int WAVES = TPB / 64;
+constexpr int64_t HASH_CHUNK = 2048;        // words (16 Ki symbols) per hash task: 8 trips of 64 lanes x 16 bytes
+constexpr int64_t VERIFY_CHUNK = 2048;      // words per verification task
+constexpr int64_t STRETCH_WORDS = 8 << 20;  // 32 MiB of packed symbols: the unit of the overlapped upload
+constexpr size_t GZ_BLOCK = 4u << 20;       // uncompressed bytes per gzip member of the output
+
+std::atomic<int> g_hash_bits(128);
+
+// ---------------------------------------------------------------- host: packing
+// byte -> 4-bit set of bases; 0x10 = white space (skipped), 0x20 = not in the alphabet
+struct nib_lut {
+    uint8_t t[256];
+    nib_lut() {
+        for (int i = 0; i < 256; ++i) t[i] = 0x20;
+        t[(int)' '] = t[(int)'\t'] = t[(int)'\r'] = t[(int)'\n'] = 0x10;
+        const char* sym = "-ACMGRSVTWYHKDBN";          // index = the set of bases (A=1, C=2, G=4, T=8)
+        for (int v = 0; v < 16; ++v) { t[(unsigned char)sym[v]] = (uint8_t)v; t[(unsigned char)(sym[v] | 0x20)] = (uint8_t)v; }
+    }
+};
+const nib_lut NLUT;
+
+// The symbols of [q, end) into out[0 ..], eight per word, the first in the low bits; the words up to out_end are written
+// (the last symbol word with zero nibbles behind the sequence, then zero words).  Eight bytes per trip while they are all
+// symbols; line ends and anything unusual go byte by byte.  Returns the first byte outside the alphabet, or nullptr.
+const char* pack_nibbles(const char* q, const char* end, uint32_t* out, uint32_t* out_end, int64_t* n_sym) {
+    uint64_t acc = 0; int nb = 0; int64_t n = 0; uint32_t* o = out;
+    while (q < end) {
+        if (end - q >= 8) {
+            uint32_t w = 0, f = 0;
+            for (int j = 0; j < 8; ++j) { const uint32_t c = NLUT.t[(unsigned char)q[j]]; w |= (c & 15u) << (4 * j); f |= c; }
+            if (f < 16) { acc |= (uint64_t)w << nb; *o++ = (uint32_t)acc; acc >>= 32; n += 8; q += 8; continue; }
+        }
+        const uint32_t c = NLUT.t[(unsigned char)*q];
+        if (c & 0x20) { *n_sym = n; return q; }
+        ++q;
+        if (c & 0x10) continue;
+        acc |= (uint64_t)c << nb; nb += 4; ++n;
+        if (nb == 32) { *o++ = (uint32_t)acc; acc = 0; nb = 0; }
+    }
+    if (nb > 0) *o++ = (uint32_t)acc;
+    while (o < out_end) *o++ = 0;
+    *n_sym = n;
+    return nullptr;
+}
+
+template <class F> void parallel_for(int64_t n, int n_threads, F fn) {
+    std::atomic<int64_t> next(0);
+    std::vector<std::exception_ptr> err((size_t)std::max(1, n_threads));
+    auto work = [&](int t) {
+        try { for (;;) { const int64_t i = next.fetch_add(1); if (i >= n) break; fn(i); } }
+        catch (...) { err[(size_t)t] = std::current_exception(); next.store(n); }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < std::min<int64_t>(n_threads, n); ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+    for (auto& e : err) if (e) std::rethrow_exception(e);
+}
+
+// the packed records, host and device
+struct packed_set {
+    int64_t n = 0;
+    std::vector<int64_t> woff, len;                               // word offset (a multiple of 4) and symbols per record
+    std::vector<uint32_t, no_init_alloc<uint32_t>> words;
+    dbuf<uint32_t> d_words;
+    int64_t bad_rec = -1; const char* bad_at = nullptr;          // the earliest record holding a byte outside the alphabet
+};
+
+// Packs seq[i] = [first, second) for every record.  The device copy is made while the packing goes on; when there is no
+// device, or the upload fails, the packing still ends (a byte outside the alphabet is the error the caller reports first)
+// and the device error is thrown after it.
+void pack_and_upload(const std::vector<std::pair<const char*, const char*>>& seq, int n_threads, packed_set& ps) {
+    const int64_t n = (int64_t)seq.size();
+    ps.n = n;
+    ps.woff.assign((size_t)n + 1, 0); ps.len.assign((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) {           // an upper bound of the symbols: the bytes of the sequence lines
+        const int64_t ub = (int64_t)(seq[(size_t)i].second - seq[(size_t)i].first);
+        ps.woff[(size_t)i + 1] = ps.woff[(size_t)i] + ((ub + 31) >> 5 << 2);
+    }
+    const int64_t total = ps.woff[(size_t)n];
+    ps.words.resize((size_t)total + 4);
+    ps.words[(size_t)total] = ps.words[(size_t)total + 1] = ps.words[(size_t)total + 2] = ps.words[(size_t)total + 3] = 0;
+    // stretches of records: the unit of the upload
+    std::vector<int64_t> st_first{ 0 };
+    for (int64_t i = 0; i < n; ++i)
+        if (ps.woff[(size_t)i + 1] - ps.woff[(size_t)st_first.back()] >= STRETCH_WORDS && i + 1 < n) st_first.push_back(i + 1);
+    st_first.push_back(n);
+    const int64_t n_st = (int64_t)st_first.size() - 1;
+    std::vector<int32_t> st_of((size_t)n);
+    for (int64_t c = 0; c < n_st; ++c) for (int64_t i = st_first[(size_t)c]; i < st_first[(size_t)c + 1]; ++i) st_of[(size_t)i] = (int32_t)c;
+    std::unique_ptr<std::atomic<int64_t>[]> st_left(new std::atomic<int64_t>[(size_t)std::max<int64_t>(n_st, 1)]);
+    for (int64_t c = 0; c < n_st; ++c) st_left[(size_t)c].store(st_first[(size_t)c + 1] - st_first[(size_t)c]);
+
+    std::mutex mu; std::condition_variable cv; std::vector<int64_t> queue; bool done = false;
+    int dev_code = VG_OK; std::string dev_err;
+    std::thread uploader([&]() {
+        hipStream_t st = nullptr;
+        try {
+            vg_require_device();
+            ps.d_words.alloc((size_t)total + 4);
+            VG_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        } catch (const vg_error& e) { std::lock_guard<std::mutex> lk(mu); dev_code = e.code; dev_err = e.what(); }
+        catch (const std::exception& e) { std::lock_guard<std::mutex> lk(mu); dev_code = VG_EHIP; dev_err = e.what(); }
+        for (;;) {
+            int64_t c;
+            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !queue.empty() || done; }); if (queue.empty()) break; c = queue.back(); queue.pop_back(); }
+            if (dev_code != VG_OK) continue;          // (no device: the packing goes on, the error is reported after it)
+            const int64_t w0 = ps.woff[(size_t)st_first[(size_t)c]], w1 = ps.woff[(size_t)st_first[(size_t)c + 1]];
+            const hipError_t e = hipMemcpyAsync(ps.d_words.p + w0, ps.words.data() + w0, (size_t)(w1 - w0) * 4, hipMemcpyHostToDevice, st);
+            const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(st) : e;
+            if (e2 != hipSuccess) { std::lock_guard<std::mutex> lk(mu); dev_code = VG_EHIP; dev_err = std::string("upload of the packed records: ") + hipGetErrorString(e2); }
+        }
+        if (st) (void)hipStreamDestroy(st);
+    });
+    struct join_guard { std::thread& t; std::mutex& m; std::condition_variable& cv; bool& done;
+                        ~join_guard() { { std::lock_guard<std::mutex> lk(m); done = true; } cv.notify_all(); if (t.joinable()) t.join(); } } jg{ uploader, mu, cv, done };
+    std::vector<const char*> bad((size_t)n, nullptr);
+    parallel_for(n, n_threads, [&](int64_t i) {
+        int64_t ns = 0;
+        uint32_t* o = ps.words.data() + ps.woff[(size_t)i];
+        bad[(size_t)i] = pack_nibbles(seq[(size_t)i].first, seq[(size_t)i].second, o, ps.words.data() + ps.woff[(size_t)i + 1], &ns);
+        ps.len[(size_t)i] = ns;
+        if (st_left[(size_t)st_of[(size_t)i]].fetch_sub(1) == 1) {
+            { std::lock_guard<std::mutex> lk(mu); queue.push_back(st_of[(size_t)i]); }
+            cv.notify_one();
+        }
+    });
+    { std::lock_guard<std::mutex> lk(mu); done = true; }
+    cv.notify_all(); uploader.join();
+    vg_host_mark("dedup: packed");
+    for (int64_t i = 0; i < n; ++i) if (bad[(size_t)i]) { ps.bad_rec = i; ps.bad_at = bad[(size_t)i]; break; }
+    if (ps.bad_rec >= 0) return;
+    if (dev_code != VG_OK) throw vg_error(dev_code, dev_err);
+    if (n) {    // (the zero words behind the last record)
+        hipStream_t s = vg_stream();
+        VG_HIP(hipMemcpyAsync(ps.d_words.p + total, ps.words.data() + total, 16, hipMemcpyHostToDevice, s));
+    }
+}
+
+std::string quote_byte(char ch) {
+    char b[8];
+    if ((unsigned char)ch >= 0x20 && (unsigned char)ch < 0x7f) snprintf(b, sizeof b, "%c", ch);
+    else snprintf(b, sizeof b, "\\x%02x", (unsigned char)ch);
+    return b;
+}
+
+// ---------------------------------------------------------------- device: hash
+__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return k;
+}
+// the term of symbol word x at word index w of a strand: two 64-bit sums
+__device__ __forceinline__ void term(uint64_t w, uint32_t x, uint64_t& lo, uint64_t& hi) {
+    const uint64_t a = fmix64(((w + 1) * 0x9e3779b97f4a7c15ull) ^ (uint64_t)x);
+    lo += a;
+    hi += (a ^ (a >> 29)) * 0xbf58476d1ce4e5b9ull;
+}
+// reverse-complement word of the 8 forward symbols starting at symbol 8k + r (hi = word k + 1, lo = word k)
+__device__ __forceinline__ uint32_t rc_word(uint32_t hi, uint32_t lo, int r) {
+    return __builtin_bitreverse32(__builtin_amdgcn_alignbit(hi, lo, (uint32_t)(4 * r)));
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
+    return v;
+}
+// the last i in [0, n) with beg[i] <= t (beg ascending, beg[0] = 0)
+__device__ __forceinline__ int64_t owner_of(const int64_t* beg, int64_t n, int64_t t) {
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (beg[mid] <= t) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// Record i, L symbols, nw = ceil(L / 8) words, q = L / 8, r = L % 8.  Reverse-complement word w holds the complements of
+// forward symbols L-1-8w down to L-8-8w, i.e. the forward window starting at 8k + r with k = q - 1 - w (k = -1 for the
+// last one when r > 0: its missing symbols are zero, the complement of '-' padding, as in the forward strand's last word).
+// A lane loads forward words j .. j+3 (16 bytes; records start on 4-word boundaries) and word j + 4 when it needs it.
+__global__ void __launch_bounds__(TPB) k_hash(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                              const int64_t* __restrict__ cbeg, int64_t n, int64_t n_tasks, unsigned long long* h) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t i = owner_of(cbeg, n, t), c = t - cbeg[i];
+        const int64_t L = len[i], nw = (L + 7) >> 3, q = L >> 3;
+        const int r = (int)(L & 7);
+        const uint32_t* R = W + woff[i];
+        uint64_t flo = 0, fhi = 0, rlo = 0, rhi = 0;
+        const int64_t j1 = min(nw, (c + 1) * HASH_CHUNK);
+        for (int64_t j = c * HASH_CHUNK + 4 * lane; j < j1; j += 256) {
+            const uint4 v = *(const uint4*)(R + j);
+            const uint32_t x[5] = { v.x, v.y, v.z, v.w, (r && j + 4 <= q) ? R[j + 4] : 0u };
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t k = j + u;
+                if (k < nw) term((uint64_t)k, x[u], flo, fhi);
+                if (k < q) term((uint64_t)(q - 1 - k), rc_word(x[u + 1], x[u], r), rlo, rhi);
+            }
+            if (j == 0 && r) term((uint64_t)q, rc_word(x[0], 0u, r), rlo, rhi);
+        }
+        flo = wave_sum64(flo); fhi = wave_sum64(fhi); rlo = wave_sum64(rlo); rhi = wave_sum64(rhi);
+        if (lane == 0) {
+            atomicAdd(h + 4 * i, (unsigned long long)flo); atomicAdd(h + 4 * i + 1, (unsigned long long)fhi);
+            atomicAdd(h + 4 * i + 2, (unsigned long long)rlo); atomicAdd(h + 4 * i + 3, (unsigned long long)rhi);
+        }
+    }
+}
+
+// key of record i: (length, min(fw, rc)) with the hash cut to its low `bits` bits; ori[i] = 1 when rc < fw
+__global__ void k_keys(const unsigned long long* h, const int64_t* len, int64_t n, int bits, uint64_t* klo, uint64_t* khi,
+                       uint64_t* klen, uint8_t* ori, int32_t* idx) {
+    const uint64_t mlo = bits >= 64 ? ~0ull : (1ull << bits) - 1, mhi = bits >= 128 ? ~0ull : bits <= 64 ? 0ull : (1ull << (bits - 64)) - 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t flo = h[4 * i], fhi = h[4 * i + 1], rlo = h[4 * i + 2], rhi = h[4 * i + 3];
+        const bool o = rhi < fhi || (rhi == fhi && rlo < flo);
+        klo[i] = (o ? rlo : flo) & mlo; khi[i] = (o ? rhi : fhi) & mhi; klen[i] = (uint64_t)len[i];
+        ori[i] = o ? 1 : 0; idx[i] = (int32_t)i;
+    }
+}
+__global__ void k_gather(const uint64_t* key, const int32_t* perm, int64_t n, uint64_t* out) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) out[p] = key[perm[p]];
+}
+
+// ---------------------------------------------------------------- device: verification rounds
+__device__ __forceinline__ bool same_key(const uint64_t* klo, const uint64_t* khi, const uint64_t* klen, int32_t a, int32_t b) {
+    return klo[a] == klo[b] && khi[a] == khi[b] && klen[a] == klen[b];
+}
+// hp[p] = p at the start of a run of equal keys, else 0 (an inclusive max-scan then gives every position its run's head)
+__global__ void k_runs(const int32_t* A, int64_t na, const uint64_t* klo, const uint64_t* khi, const uint64_t* klen, int64_t* hp) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < na; p += (int64_t)gridDim.x * blockDim.x)
+        hp[p] = (p == 0 || !same_key(klo, khi, klen, A[p], A[p - 1])) ? p : 0;
+}
+// verification tasks per position: ceil(words / VERIFY_CHUNK) for a member, 0 for a head; cnt[na] = 0 (the total's slot)
+__global__ void k_tasks(const int32_t* A, int64_t na, const int64_t* hp, const int64_t* len, int64_t* cnt, uint8_t* diff) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= na; p += (int64_t)gridDim.x * blockDim.x) {
+        if (p == na) { cnt[p] = 0; continue; }
+        const int64_t nw = (len[A[p]] + 7) >> 3;
+        cnt[p] = hp[p] == p ? 0 : (nw + VERIFY_CHUNK - 1) / VERIFY_CHUNK;
+        diff[p] = 0;
+    }
+}
+// one wave per (member, chunk): the member's words against the head's, forward or reverse-complement as the orientation
+// bits say (equal bits: the member equals the head itself; different bits: the head's reverse complement)
+__global__ void __launch_bounds__(TPB) k_verify(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                                const uint8_t* __restrict__ ori, const int32_t* __restrict__ A, int64_t na,
+                                                const int64_t* __restrict__ hp, const int64_t* __restrict__ tbeg, int64_t n_tasks, uint8_t* diff) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t p = owner_of(tbeg, na, t), c = t - tbeg[p];
+        const int32_t m = A[p], hd = A[hp[p]];
+        const int64_t L = len[m], nw = (L + 7) >> 3, q = L >> 3;
+        const int r = (int)(L & 7);
+        const uint32_t* M = W + woff[m]; const uint32_t* H = W + woff[hd];
+        const bool fw = ori[m] == ori[hd];
+        bool bad = false;
+        for (int64_t k = c * VERIFY_CHUNK + lane, k1 = min(nw, (c + 1) * VERIFY_CHUNK); k < k1; k += 64) {
+            uint32_t b;
+            if (fw) b = H[k];
+            else if (k < q) { const int64_t s = q - 1 - k; b = rc_word(r ? H[s + 1] : 0u, H[s], r); }
+            else b = rc_word(H[0], 0u, r);                   // (k == q, r > 0)
+            bad |= M[k] != b;
+        }
+        if (__ballot(bad) && lane == 0) diff[p] = 1;
+    }
+}
+// heads keep themselves, equal members join their head, differing members stay (keep[p] = 1)
+__global__ void k_resolve(const int32_t* A, int64_t na, const int64_t* hp, const uint8_t* diff, const uint8_t* ori,
+                          int32_t* rep, int8_t* strand, int32_t* keep, unsigned long long* n_diff) {
+    int c = 0;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < na; p += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t i = A[p], hd = A[hp[p]];
+        int32_t k = 0;
+        if (hp[p] == p) { rep[i] = i; strand[i] = 0; }
+        else if (!diff[p]) { rep[i] = hd; strand[i] = ori[i] != ori[hd] ? 1 : 0; }
+        else { k = 1; ++c; }
+        keep[p] = k;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_diff, (unsigned long long)c);
+}
+__global__ void k_compact(const int32_t* A, int64_t na, const int32_t* keep, const int32_t* at, int32_t* out) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < na; p += (int64_t)gridDim.x * blockDim.x)
+        if (keep[p]) out[at[p]] = A[p];
+}
+
+int grid_of(int64_t n, int per_block = TPB, int cap = 16384) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, cap));
+}
+
+template <class K, class V>
+void sort_pairs(dbuf<K>& keys, dbuf<K>& keys2, dbuf<V>& vals, dbuf<V>& vals2, int64_t n, unsigned bits, hipStream_t s) {
+    size_t tb = 0;
+    VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)n, 0u, bits, s));
+    dbuf<char> tmp(std::max<size_t>(tb, 1));
+    VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)n, 0u, bits, s));
+    std::swap(keys.p, keys2.p); std::swap(vals.p, vals2.p);
+}
+template <class T, class Op>
+void scan(const T* in, T* out, int64_t n, bool inclusive, Op op, hipStream_t s) {
+    size_t tb = 0;
+    if (inclusive) VG_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, op, s));
+    else VG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, (T)0, (size_t)n, op, s));
+    dbuf<char> tmp(std::max<size_t>(tb, 1));
+    if (inclusive) VG_HIP(rocprim::inclusive_scan((void*)tmp.p, tb, in, out, (size_t)n, op, s));
+    else VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, in, out, (T)0, (size_t)n, op, s));
+}
+
+// the device part: packed records (resident) -> representative / strand on the host
+void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, vg_dedup_stats& st) {
+    const int64_t n = ps.n;
+    if (n == 0) return;
+    hipStream_t s = vg_stream();
+    const int bits = g_hash_bits.load();
+    int64_t total_words = 0, max_len = 0;
+    std::vector<int64_t> cbeg((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t nw = (ps.len[(size_t)i] + 7) >> 3;
+        cbeg[(size_t)i + 1] = cbeg[(size_t)i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
+        total_words += nw; max_len = std::max(max_len, ps.len[(size_t)i]);
+    }
+    const int64_t n_tasks = cbeg[(size_t)n];
+    dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1);
+    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
+    dbuf<unsigned long long> d_h((size_t)n * 4);
+    d_h.zero(s);
+    {
+        vg_prof_scope ps_("dedup_hash", (double)total_words * 4.0);
+        hipLaunchKernelGGL(k_hash, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, d_h.p);
+    }
+    d_cbeg.release();
+    dbuf<uint64_t> klo((size_t)n), khi((size_t)n), klen((size_t)n), kg((size_t)n), ks((size_t)n);
+    dbuf<uint8_t> ori((size_t)n);
+    dbuf<int32_t> A((size_t)n), A2((size_t)n);
+    {
+        vg_prof_scope ps_("dedup_keys", (double)n * 66.0);
+        hipLaunchKernelGGL(k_keys, dim3(grid_of(n)), dim3(TPB), 0, s, d_h.p, d_len.p, n, bits, klo.p, khi.p, klen.p, ori.p, A.p);
+    }
+    d_h.release();
+    {   // LSD: the low hash half, the high half, the length (stable passes: equal keys stay in index order)
+        vg_prof_scope ps_("dedup_sort", (double)n * 48.0);
+        unsigned len_bits = 0; while (len_bits < 64 && (max_len >> len_bits)) ++len_bits;
+        const unsigned pass_bits[3] = { (unsigned)std::min(bits, 64), (unsigned)std::max(bits - 64, 0), len_bits };
+        const uint64_t* src[3] = { klo.p, khi.p, klen.p };
+        for (int pass = 0; pass < 3; ++pass) {
+            if (!pass_bits[pass]) continue;
+            hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, src[pass], A.p, n, kg.p);
+            sort_pairs(kg, ks, A, A2, n, pass_bits[pass], s);
+        }
+    }
+    dbuf<int32_t> d_rep((size_t)n), keep((size_t)n), at((size_t)n);
+    dbuf<int8_t> d_strand((size_t)n);
+    dbuf<int64_t> hp((size_t)n), hp2((size_t)n), cnt((size_t)n + 1), tbeg((size_t)n + 1);
+    dbuf<uint8_t> diff((size_t)n);
+    dbuf<unsigned long long> d_ndiff(1);
+    int64_t na = n;
+    while (na > 0) {
+        ++st.rounds;
+        d_ndiff.zero(s);
+        {
+            vg_prof_scope ps_("dedup_runs", (double)na * 60.0);
+            hipLaunchKernelGGL(k_runs, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, klo.p, khi.p, klen.p, hp2.p);
+            scan(hp2.p, hp.p, na, true, rocprim::maximum<int64_t>(), s);
+            hipLaunchKernelGGL(k_tasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A.p, na, hp.p, d_len.p, cnt.p, diff.p);
+            scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+        }
+        int64_t n_vt = 0;
+        vg_download_bytes(&n_vt, tbeg.p + na, sizeof n_vt, s);          // (the element at na: the total)
+        VG_HIP(hipStreamSynchronize(s));
+        if (n_vt > 0) {
+            vg_prof_scope ps_("dedup_verify", (double)n_vt * VERIFY_CHUNK * 8.0);
+            hipLaunchKernelGGL(k_verify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, ori.p, A.p, na,
+                               hp.p, tbeg.p, n_vt, diff.p);
+        }
+        {
+            vg_prof_scope ps_("dedup_labels", (double)na * 24.0);
+            hipLaunchKernelGGL(k_resolve, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, hp.p, diff.p, ori.p, d_rep.p, d_strand.p, keep.p, d_ndiff.p);
+        }
+        unsigned long long nd = 0;
+        d_ndiff.download(&nd, 1, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (nd == 0) break;
+        st.collisions += (int64_t)nd;
+        {
+            vg_prof_scope ps_("dedup_compact", (double)na * 12.0);
+            scan(keep.p, at.p, na, false, rocprim::plus<int32_t>(), s);
+            hipLaunchKernelGGL(k_compact, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, keep.p, at.p, A2.p);
+        }
+        std::swap(A.p, A2.p);
+        na = (int64_t)nd;
+    }
+    d_rep.download(rep_out, (size_t)n, s);
+    d_strand.download(strand_out, (size_t)n, s);
+    VG_HIP(hipStreamSynchronize(s));
+}
+
+void finish_stats(int64_t n, const int32_t* rep, const int8_t* strand, vg_dedup_stats& st) {
+    st.records = n; st.unique = 0; st.reverse = 0;
+    for (int64_t i = 0; i < n; ++i) { st.unique += rep[i] == (int32_t)i; st.reverse += rep[i] != (int32_t)i && strand[i]; }
+    st.removed = n - st.unique;
+}
+
+// ---------------------------------------------------------------- host: the writer
+std::string first_token(const char* b, const char* e) {
+    const char* q = b; while (q < e && *q != ' ' && *q != '\t' && *q != '\r') ++q;
+    return std::string(b, q);
+}
+void write_all(const char* path, const std::vector<std::pair<const char*, size_t>>& parts) {
+    FILE* f = fopen(path, "wb");
+    if (!f) throw vg_error(VG_EIO, std::string("cannot create ") + path);
+    for (auto& p : parts) if (p.second && fwrite(p.first, 1, p.second, f) != p.second) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
+    if (fclose(f) != 0) throw vg_error(VG_EIO, std::string("write error on ") + path);
+}
+// the output FASTA: the kept records in input order, assembled in memory by all threads, then written plain or as gzip members
+// of GZ_BLOCK uncompressed bytes each (compressed in parallel: the bytes do not depend on the thread count)
+void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, int level, int T) {
+    const int64_t n = (int64_t)in.recs.size();
+    std::vector<int64_t> kept;
+    for (int64_t i = 0; i < n; ++i) if (rep[i] == (int32_t)i) kept.push_back(i);
+    auto size_of = [&](const vg_fasta_rec& r) {
+        const int64_t sl = r.end - r.seq;
+        return (int64_t)(1 + prefix[(size_t)r.file].size() + (r.hdr_end - r.hdr) + 1 + sl + (sl > 0 && r.end[-1] != '\n'));
+    };
+    std::vector<int64_t> at(kept.size() + 1, 0);
+    for (size_t k = 0; k < kept.size(); ++k) at[k + 1] = at[k] + size_of(in.recs[(size_t)kept[k]]);
+    std::vector<char, no_init_alloc<char>> buf((size_t)at.back());
+    parallel_for((int64_t)kept.size(), T, [&](int64_t k) {
+        const vg_fasta_rec& r = in.recs[(size_t)kept[(size_t)k]];
+        char* o = buf.data() + at[(size_t)k];
+        const std::string& pf = prefix[(size_t)r.file];
+        *o++ = '>'; memcpy(o, pf.data(), pf.size()); o += pf.size();
+        memcpy(o, r.hdr, (size_t)(r.hdr_end - r.hdr)); o += r.hdr_end - r.hdr; *o++ = '\n';
+        memcpy(o, r.seq, (size_t)(r.end - r.seq)); o += r.end - r.seq;
+        if (r.end > r.seq && r.end[-1] != '\n') *o++ = '\n';
+    });
+    if (level <= 0) { write_all(path, { { buf.data(), buf.size() } }); return; }
+    const int64_t nb = std::max<int64_t>(1, ((int64_t)buf.size() + (int64_t)GZ_BLOCK - 1) / (int64_t)GZ_BLOCK);
+    std::vector<std::vector<unsigned char>> member((size_t)nb);
+    parallel_for(nb, T, [&](int64_t b) {
+        const size_t lo = (size_t)b * GZ_BLOCK, len = std::min(GZ_BLOCK, buf.size() - std::min(buf.size(), lo));
+        z_stream zs; memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw vg_error(VG_ENOMEM, "deflateInit2 failed");
+        std::vector<unsigned char>& out = member[(size_t)b];
+        out.resize(deflateBound(&zs, (uLong)len) + 32);
+        zs.next_in = (Bytef*)(buf.data() + lo); zs.avail_in = (uInt)len;
+        zs.next_out = out.data(); zs.avail_out = (uInt)out.size();
+        const int rc = deflate(&zs, Z_FINISH);
+        out.resize(out.size() - zs.avail_out);
+        deflateEnd(&zs);
+        if (rc != Z_STREAM_END) throw vg_error(VG_EIO, "gzip compression failed");
+    });
+    std::vector<std::pair<const char*, size_t>> parts;
+    for (auto& m : member) parts.emplace_back((const char*)m.data(), m.size());
+    write_all(path, parts);
+}
+void write_duplicates(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, const int8_t* strand) {
+    const int64_t n = (int64_t)in.recs.size();
+    auto id = [&](int64_t i) { const vg_fasta_rec& r = in.recs[(size_t)i]; return prefix[(size_t)r.file] + first_token(r.hdr, r.hdr_end); };
+    std::string out = "representative\tduplicate\tstrand\n";
+    for (int64_t i = 0; i < n; ++i) {
+        if (rep[i] == (int32_t)i) continue;
+        out += id(rep[i]); out += '\t'; out += id(i); out += '\t'; out += strand[i] ? '-' : '+'; out += '\n';
+    }
+    write_all(path, { { out.data(), out.size() } });
+}
+}  // namespace
+
+extern "C" void vg_dedup_set_hash_bits(int bits) { g_hash_bits.store(std::max(0, std::min(bits, 128))); }
+
+extern "C" int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
+                             vg_dedup_stats* stats) {
+    VG_API_BEGIN
+    if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_seqs: negative count");
+    if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_dedup_seqs: 2^31 or more records (record indices are int32)");
+    if (n && (!offsets || !representative || !strand)) throw vg_error(VG_EINVAL, "vg_dedup_seqs: null argument");
+    if (n && offsets[n] > offsets[0] && !ascii) throw vg_error(VG_EINVAL, "vg_dedup_seqs: null sequence buffer");
+    for (int64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) throw vg_error(VG_EINVAL, "vg_dedup_seqs: offsets must not decrease");
+    vg_dedup_stats st_local{}; vg_dedup_stats& st = stats ? *stats : st_local;
+    st = vg_dedup_stats{};
+    if (n == 0) return VG_OK;
+    std::vector<std::pair<const char*, const char*>> seq((size_t)n);
+    for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
+    packed_set ps;
+    pack_and_upload(seq, vg_host_threads(), ps);
+    if (ps.bad_rec >= 0)
+        throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
+    dedup_device(ps, representative, strand, st);
+    finish_stats(n, representative, strand, st);
+    VG_API_END
+}
+
+extern "C" int vg_deduplicate(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                              const char* dup_path, const vg_dedup_params* p) {
+    VG_API_BEGIN
+    if (!paths || n_paths <= 0 || !out_path || !dup_path || !p) throw vg_error(VG_EINVAL, "vg_deduplicate: null argument");
+    if (p->gzip_level < 0 || p->gzip_level > 9) throw vg_error(VG_EINVAL, "vg_deduplicate: gzip_level must be 0 (plain) or 1..9");
+    for (int i = 0; i < n_paths; ++i) {
+        struct stat sb;
+        if (!paths[i]) throw vg_error(VG_EINVAL, "vg_deduplicate: null path");
+        if (stat(paths[i], &sb) == 0 && S_ISDIR(sb.st_mode)) throw vg_error(VG_EINVAL, std::string(paths[i]) + " is a directory, not a FASTA file");
+    }
+    const int T = p->num_threads > 0 ? p->num_threads : vg_host_threads();
+    std::vector<std::string> prefix((size_t)n_paths);
+    if (prefixes) for (int i = 0; i < n_paths; ++i) prefix[(size_t)i] = prefixes[i] ? prefixes[i] : "";
+    vg_host_mark("vg_deduplicate: enter");
+    vg_fasta_text in;
+    vg_fasta_read(paths, n_paths, T, in);
+    const int64_t n = (int64_t)in.recs.size();
+    if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_deduplicate: 2^31 or more records (record indices are int32)");
+    vg_host_mark("dedup: records found");
+    std::vector<std::pair<const char*, const char*>> seq((size_t)n);
+    for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { in.recs[(size_t)i].seq, in.recs[(size_t)i].end };
+    packed_set ps;
+    pack_and_upload(seq, T, ps);
+    if (ps.bad_rec >= 0) {
+        const vg_fasta_rec& r = in.recs[(size_t)ps.bad_rec];
+        const char* f0 = in.file_data[(size_t)r.file];
+        const int64_t line = 1 + (int64_t)std::count(f0, ps.bad_at, '\n');
+        throw vg_error(VG_EINVAL, std::string(paths[r.file]) + ":" + std::to_string(line) + ": '" + quote_byte(*ps.bad_at) +
+                                  "' is not an IUPAC nucleotide code");
+    }
+    vg_require_device();
+    std::vector<int32_t> rep((size_t)std::max<int64_t>(n, 1));
+    std::vector<int8_t> strand((size_t)std::max<int64_t>(n, 1));
+    vg_dedup_stats st{};
+    dedup_device(ps, rep.data(), strand.data(), st);
+    finish_stats(n, rep.data(), strand.data(), st);
+    ps.d_words.release();
+    vg_host_mark("dedup: groups computed");
+    write_fasta(out_path, in, prefix, rep.data(), p->gzip_level, T);
+    write_duplicates(dup_path, in, prefix, rep.data(), strand.data());
+    vg_host_mark("dedup: written");
+    if (p->verbosity >= 1)
+        fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds\n",
+                (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
+                (long long)st.rounds);
+    VG_API_END
+}

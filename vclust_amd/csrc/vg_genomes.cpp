@@ -608,3 +608,28 @@ extern "C" int vg_genomes_to_device(vg_genomes* g) {
     vg_host_mark("genomes uploaded");
     VG_API_END
 }
+
+// the deduplicate stage's input (vg_dedup.hip): every file whole in memory, every record in file order
+void vg_fasta_read(const char* const* paths, int n_paths, int n_threads, vg_fasta_text& out) {
+    const int T = std::max(1, n_threads);
+    auto* bufs = new std::vector<filebuf>((size_t)std::max(n_paths, 0));
+    out.bufs = std::shared_ptr<void>(bufs, [](void* p) { delete (std::vector<filebuf>*)p; });
+    {
+        std::string first_err; std::atomic<bool> failed(false);
+        parallel_for(n_paths, T, [&](int64_t i) {
+            if (failed.load()) return;
+            try { slurp(paths[i], (*bufs)[(size_t)i], std::max(1, T / (int)std::min<int64_t>(n_paths, T))); }
+            catch (const std::exception& e) { if (!failed.exchange(true)) first_err = e.what(); }
+        });
+        if (failed.load()) throw vg_error(VG_EIO, first_err);
+    }
+    out.file_data.clear(); out.file_len.clear(); out.recs.clear();
+    std::vector<record> rv;
+    for (int i = 0; i < n_paths; ++i) {
+        const filebuf& fb = (*bufs)[(size_t)i];
+        out.file_data.push_back(fb.data()); out.file_len.push_back(fb.size());
+        rv.clear();
+        find_records(fb, rv, T);
+        for (const record& r : rv) out.recs.push_back({ r.hdr, r.hdr_end, r.seq, r.end, i });
+    }
+}

@@ -1,12 +1,12 @@
 """The whole-stage calls of the drop-in CLI (vg_prefilter, vg_align: FASTA on disk -> fltr.txt / ani.tsv on disk; vg_cluster:
-ani.tsv + ids file -> clusters.tsv) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster` process is
+ani.tsv + ids file -> clusters.tsv; vg_deduplicate: FASTA files -> distinct records + duplicates list) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster|deduplicate` process is
 one of these calls, and importing numpy costs it 60-180 ms of its ~1 s.  vclust_amd.api re-exports them beside the
 array-level API."""
 import ctypes as C
 import os
 
 from . import _lib
-from ._lib import CLUSTER_ALGORITHMS, AlignParams, ClusterParams, LzParams, PrefilterParams, check
+from ._lib import CLUSTER_ALGORITHMS, AlignParams, ClusterParams, DedupParams, LzParams, PrefilterParams, check
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -65,3 +65,14 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     for name, val in mins.items():
         setattr(p, f'min_{name}', float(val))
     check(_lib.load().vg_cluster(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)), C.byref(p)))
+
+
+def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0):
+    """The distinct records of the FASTA files `paths` -> out_path, the removed ones -> dup_path (vg_deduplicate).
+    prefixes: None or one string per path, put in front of every header of that file; gzip_level 0 = plain output."""
+    if prefixes is not None and len(prefixes) != len(paths):
+        raise ValueError('one prefix per input file')
+    arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
+    pre = (C.c_char_p * len(paths))(*[str(x).encode() for x in prefixes]) if prefixes is not None else None
+    prm = DedupParams(gzip_level=int(gzip_level), num_threads=int(num_threads), verbosity=int(verbosity))
+    check(_lib.load().vg_deduplicate(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm)))
