@@ -36,7 +36,7 @@ def _stale(target: pathlib.Path, deps) -> bool:
 def build_lib(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """Compile every HIP/C++ source into vclust_amd/libvclust_gpu.so for gfx950."""
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / 'vg_common.h', ROOT / 'include' / 'vclust_gpu.h']
+    deps = srcs + [CSRC / 'vg_common.h', CSRC / 'vg_window.h', ROOT / 'include' / 'vclust_gpu.h']
     if not force and not _stale(LIB_PATH, deps):
         return LIB_PATH
     obj_dir = PKG_DIR / '_obj'
@@ -53,7 +53,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> pathlib.Path:
     for s in srcs:
         o = obj_dir / (s.name + '.o')
         objs.append(o)
-        if force or _stale(o, [s, CSRC / 'vg_common.h', ROOT / 'include' / 'vclust_gpu.h']):
+        if force or _stale(o, [s, CSRC / 'vg_common.h', CSRC / 'vg_window.h', ROOT / 'include' / 'vclust_gpu.h']):
             cmd = [hipcc, *flags, '-x', 'hip', '-c', str(s), '-o', str(o)]
             if verbose:
                 print(' '.join(cmd), file=sys.stderr)

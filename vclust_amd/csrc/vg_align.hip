@@ -21,6 +21,7 @@
 // no MFMA, the levers are occupancy and L2 locality of the reference (tasks are grouped by
 // reference and dealt to workgroups XCD-aware).
 #include "vg_common.h"
+#include "vg_window.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <numeric>
@@ -180,11 +181,30 @@ __device__ __forceinline__ int wave_sum(int v) {
 // the two phases, and the whole thing is the window automaton run over the mismatch mask from
 // e = 0, with the exact run as a lower bound of the result.  Bit-parallel: 32 bases per lane
 // (one word of mismatch bits), 2 048 per round; only mismatch positions can start a violation.
-// mismatch mask of round 0 of extend(), split out so that a caller can issue the loads of several
-// extensions back to back (one memory round trip instead of one per extension)
-__device__ __forceinline__ uint32_t extend_mask0(const pair_ctx& c, int qp, int rp, int dir, int bound, int lane, int rlo, int rhi) {
+// Mismatch mask of the round of extend() that starts at position `base` (lane l: positions base + 32 l ..).
+// UNI (N-free sets): a round that lies wholly inside the query, inside [rlo, rhi) and below `bound` -- the
+// wave decides that once, on scalars -- needs none of mism32's per-lane bounds.  Its lanes then share the
+// shift of both loads (e0 = base + 32 lane), so the row address and the shift stay in SGPRs and a lane adds
+// only its constant byte offset.  Rounds at a sequence or strand end take the per-lane path.
+template <bool UNI>
+__device__ __forceinline__ uint32_t extend_mask(const pair_ctx& c, int qp, int rp, int dir, int base, int bound, int lane, int rlo, int rhi) {
+    if (UNI && base + 2048 <= bound) {
+        // first position of the round on each side (forward), or 2 048 before the round's last one (backward)
+        const int q0 = dir > 0 ? qp + base : qp - base - 2048, r0 = dir > 0 ? rp + base : rp - base - 2048;
+        if (q0 >= 0 && q0 + 2048 <= c.qlen && r0 >= rlo && r0 + 2048 <= rhi) {
+            // forward: lane l reads word pair (q0 >> 5) + l; backward: the chunk of positions q0 + 2016 - 32 l, i.e.
+            // word pair (q0 >> 5) + 63 - l (slot j <-> position e0 + j after the bit reversal)
+            const uint32_t off = (uint32_t)(dir > 0 ? lane : 63 - lane) * 8u;
+            const char* qrow = (const char*)c.qpl + (size_t)(q0 >> 5) * 8; const char* rrow = (const char*)c.rpl + (size_t)(r0 >> 5) * 8;
+            const uint32_t qsh = (uint32_t)q0 & 31u, rsh = (uint32_t)r0 & 31u;
+            uint4 vq, vr; __builtin_memcpy(&vq, qrow + off, 16); __builtin_memcpy(&vr, rrow + off, 16);
+            const uint32_t mm = (__builtin_amdgcn_alignbit(vq.z, vq.x, qsh) ^ __builtin_amdgcn_alignbit(vr.z, vr.x, rsh)) |
+                                (__builtin_amdgcn_alignbit(vq.w, vq.y, qsh) ^ __builtin_amdgcn_alignbit(vr.w, vr.y, rsh));
+            return dir > 0 ? mm : __brev(mm);
+        }
+    }
     uint32_t mm = ~0u;
-    const int e0 = 32 * lane;
+    const int e0 = base + 32 * lane;
     if (e0 < bound) {
         if (dir > 0) mm = mism32(c, qp + e0, rp + e0, rlo, rhi);
         else mm = __brev(mism32(c, qp - e0 - 32, rp - e0 - 32, rlo, rhi));        // slot j <-> position e0 + j
@@ -192,7 +212,16 @@ __device__ __forceinline__ uint32_t extend_mask0(const pair_ctx& c, int qp, int 
     }
     return mm;
 }
+// mismatch mask of round 0 of extend(), split out so that a caller can issue the loads of several
+// extensions back to back (one memory round trip instead of one per extension)
+template <bool UNI>
+__device__ __forceinline__ uint32_t extend_mask0(const pair_ctx& c, int qp, int rp, int dir, int bound, int lane, int rlo, int rhi) {
+    return extend_mask<UNI>(c, qp, rp, dir, 0, bound, lane, rlo, rhi);
+}
 
+// FAST: the set has no N and (aw, am) = (15, 7) (the FAST parse kernels): rounds inside both sequences take the uniform
+// path of extend_mask, and the window rule is the branch-free count of vg_window.h instead of the serial loop below
+template <bool FAST>
 __device__ __forceinline__ int extend(const pair_ctx& c, const lz_dev_params& P, int qp, int rp, int dir, int bound,
                                       int lane, int* n_match, uint32_t mm_first, int rlo, int rhi) {
     int accepted = 0, matches_total = 0;
@@ -205,15 +234,7 @@ __device__ __forceinline__ int extend(const pair_ctx& c, const lz_dev_params& P,
     if (bound <= 0) { *n_match = 0; return 0; }
     for (;;) {
         uint32_t mm = mm_first;
-        if (base > 0) {
-            mm = ~0u;
-            const int e0 = base + 32 * lane;
-            if (e0 < bound) {
-                if (dir > 0) mm = mism32(c, qp + e0, rp + e0, rlo, rhi);
-                else mm = __brev(mism32(c, qp - e0 - 32, rp - e0 - 32, rlo, rhi));    // slot j <-> position e0 + j
-                const int rem = bound - e0; if (rem < 32) mm |= ~slots(0, rem);
-            }
-        }
+        if (base > 0) mm = extend_mask<FAST>(c, qp, rp, dir, base, bound, lane, rlo, rhi);
         const unsigned long long anyb = __ballot(mm != 0);
         if (first_mm < 0 && anyb) {
             const int fl = __builtin_ctzll(anyb);
@@ -225,7 +246,9 @@ __device__ __forceinline__ int extend(const pair_ctx& c, const lz_dev_params& P,
         int viol = 32;
         {
             const uint32_t tail = (P.aw > 1) ? (prev_mm >> (32 - (P.aw - 1))) : 0u;
-            if ((int)(__popc(mm) + __popc(tail)) > P.am) {
+            if ((int)(__popc(mm) + __popc(tail)) > P.am && FAST) {
+                viol = vg_first_violation_15_7(mm, prev_mm);       // (aw, am) = (15, 7): a fixed carry-save count
+            } else if ((int)(__popc(mm) + __popc(tail)) > P.am) {
                 uint32_t bits = mm;
                 // a window holds the mismatches of the tail plus those up to the tested one: the first
                 // am - |tail| mismatches of this chunk cannot push any window over am
@@ -1293,21 +1316,21 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
         // (closing the open region may move kept_end: use the value it will have)
         const int kept_after = (in_region && r_qend - r_qstart + 1 >= P.reg) ? r_qend + 1 : kept_end;
         const int bwd_bound = ev_close ? 0 : i - kept_after;
-        const uint32_t mm_b = (!ev_close && !(ABL & 2)) ? extend_mask0(c, i, ev_pos, -1, bwd_bound, lane, rlo, rhi) : ~0u;
-        const uint32_t mm_f = extend_mask0(c, i, ev_pos, +1, 1 << 30, lane, rlo, rhi);
+        const uint32_t mm_b = (!ev_close && !(ABL & 2)) ? extend_mask0<FAST>(c, i, ev_pos, -1, bwd_bound, lane, rlo, rhi) : ~0u;
+        const uint32_t mm_f = extend_mask0<FAST>(c, i, ev_pos, +1, 1 << 30, lane, rlo, rhi);
         PROF_MARK(1);
         if (!ev_close) {
             // R5: new region, extended to the left (exact, then approximate), not into the last kept region
             close_region();
             int bm = 0;
-            const int b = (ABL & 2) ? 0 : extend(c, P, i, ev_pos, -1, bwd_bound, lane, &bm, mm_b, rlo, rhi);
+            const int b = (ABL & 2) ? 0 : extend<FAST>(c, P, i, ev_pos, -1, bwd_bound, lane, &bm, mm_b, rlo, rhi);
             r_qstart = i - b; r_rstart = ev_pos - b; r_match = bm; r_rend = -1;
             in_region = true;
         }
         PROF_MARK(2);
         int fe, fm = 0;
         {   // the match itself and R4, one pass
-            fe = (ABL & 4) ? P.mal : extend(c, P, i, ev_pos, +1, 1 << 30, lane, &fm, mm_f, rlo, rhi);
+            fe = (ABL & 4) ? P.mal : extend<FAST>(c, P, i, ev_pos, +1, 1 << 30, lane, &fm, mm_f, rlo, rhi);
             r_match += fm;
         }
         if (ev_close) {
