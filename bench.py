@@ -17,6 +17,11 @@ is sharded by k-mer range -- every rank scans 1/N of the bases and an RCCL all-t
 range; the pairs' keys and counts are all-gathered and summed on the device --, the align tasks are dealt by reference
 range (each rank indexes 1/N of the genomes), and the per-pair integer rows are all-gathered.  N > 1 creates the library's
 RCCL communicator strictly (no fall-back to host all-gathers); the line says which communicator ran (`comm`).  Other workloads: --workload phage-1k | imgvr-10k | contigs-1M (+ --count).
+
+A plain run does only what its headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the line (with the
+roofline priced on the timed steps' own scopes).  `--full` adds the legs beside it, each of which a --no-* option still skips:
+the end-to-end CLI (`cli_wall`), --out-aln at the headline's size (`out_aln`), phage-1k and imgvr-10k (`other_workloads`), the
+CPU baseline (`cpu_baseline`, `vs_cpu_baseline`) and the sha256 of the set (`config.sha256`); in a plain run these are null.
 """
 import argparse
 import json
@@ -404,7 +409,19 @@ def dump_outputs(out_dir, groups, budget=DUMP_BUDGET, seed=0):
     return written
 
 
-def main():
+def full_legs(args, world, kind):
+    """The legs this run adds beside the headline step: none without --full; with it, every leg that applies to the
+    run (the CLI, --out-aln, other workloads and CPU baseline need one process; the other workloads belong to the default
+    set, the CPU baseline to a family set) and that its --no-* option does not skip."""
+    one = args.full and world == 1
+    return dict(cli_wall=one and not args.no_cli_wall,
+                out_aln=one and not args.no_out_aln,
+                other_workloads=one and not args.no_other_workloads and args.workload == 'phage-100k' and args.count is None,
+                cpu_baseline=one and not args.no_cpu_baseline and kind == 'families',
+                sha256=args.full)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
@@ -419,20 +436,27 @@ def main():
     ap.add_argument('--cpu-sample-families', type=int, default=2000, help='families of the set the CPU baseline runs on (2 000 = 20 000 genomes: a fifth of phage-100k)')
     ap.add_argument('--cpu-threads', type=int, default=0, help='OpenMP threads of the CPU baseline (default: what the process may use: affinity and cgroup quota)')
     ap.add_argument('--cpu-reps', type=int, default=3, help='repetitions of the CPU baseline (value = the median run)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-cli-wall', action='store_true')
-    ap.add_argument('--no-other-workloads', action='store_true', help='skip configs[1] / [2] (phage-1k, imgvr-10k) behind the headline step')
-    ap.add_argument('--no-out-aln', action='store_true', help='skip the --out-aln leg (rows + regions from one parse)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs the headline figure does not need: end-to-end CLI, --out-aln, other workloads, '
+                         'CPU baseline, sha256 of the set (each skipped by its --no-* option)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-cli-wall', action='store_true', help='--full: skip the end-to-end CLI leg')
+    ap.add_argument('--no-other-workloads', action='store_true', help='--full: skip configs[1] / [2] (phage-1k, imgvr-10k) behind the headline step')
+    ap.add_argument('--no-out-aln', action='store_true', help='--full: skip the --out-aln leg (rows + regions from one parse)')
     ap.add_argument('--placement-trials', type=int, default=4, help='placements of the prefilter workspace the first pass may try (vg_set_placement_trials; 1 = none)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one returned (k-mer set sizes, candidate pairs in (a, b) '
                          'order, tasks and their rows) as DIR/<name>.npy in float64, at most 64 MB in all (a seeded row sample beyond)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
     if args.warmup < 0:
         ap.error('--warmup must not be negative')
+    return args
 
+
+def main():
+    args = parse_args()
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -469,11 +493,12 @@ def main():
     n_units = base_n * (world if args.scaling == 'weak' else 1)
     codes, offsets, names, desc = synth.make_workload(args.workload, n_units)
     min_kmers = args.min_kmers if args.min_kmers is not None else (30 if args.workload == 'contigs-1M' else 20)
-    # End-to-end CLI leg FIRST, while this process has not touched the HBM yet: the driver scrubs device memory
+    legs = full_legs(args, world, wl['kind'])
+    # (--full) End-to-end CLI leg FIRST, while this process has not touched the HBM yet: the driver scrubs device memory
     # that moves between processes, so CLI processes started right after this process has used ~150 GB measure
     # the scrub (observed for the same work: 2.7 s on a quiet device, 6.7-8.4 s right after the timed loop)
     e2e = None; cli_td = None; cli_ani = None
-    if world == 1 and rank == 0 and not args.no_cli_wall:
+    if legs['cli_wall'] and rank == 0:
         try:
             e2e, cli_td, cli_ani = cli_wall(codes, offsets, names, None)
         except Exception as exc:      # the device-resident figure stands on its own
@@ -557,16 +582,16 @@ def main():
         if args.dump_outputs:
             dumped = dict(dir=str(args.dump_outputs), rows=dump_outputs(
                 args.dump_outputs, step_outputs(state['sizes'], state['cand'], tk, state['stats'])))
-        # -- behind the timed region (nothing below touches `value`): --out-aln from one parse at this size, then configs[1] / [2]
+        # -- behind the timed region, --full only (nothing below touches `value`): --out-aln from one parse at this size, then configs[1] / [2]
         out_aln = None
-        if world == 1 and not args.no_out_aln:
+        if legs['out_aln']:
             try:
                 plain = next((e['total_ms'] / args.steps for e in prof if e['name'] == 'lz_parse'), 0.0)
                 out_aln = out_aln_leg(gs, tk, plain)
             except Exception as exc:
                 out_aln = dict(error=str(exc))
         others = None
-        if world == 1 and not args.no_other_workloads and args.workload == 'phage-100k' and args.count is None:
+        if legs['other_workloads']:
             others = {}
             for name in ('phage-1k', 'imgvr-10k'):
                 try:
@@ -574,7 +599,7 @@ def main():
                 except Exception as exc:
                     others[name] = dict(error=str(exc))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and wl['kind'] == 'families':
+        if legs['cpu_baseline']:
             hc = host_cpus()
             cpu = cpu_baseline(min(args.cpu_sample_families, n_units), wl['members'], wl['length'], wl['seed'],
                                args.cpu_threads or hc['threads'], args.k, min_kmers, args.min_ident, n_units, reps=args.cpu_reps)
@@ -595,7 +620,7 @@ def main():
             'config': {
                 'workload': f'{desc}, k={args.k}, min-kmers={min_kmers}, min-ident={args.min_ident}, lz defaults',
                 'genomes': int(len(gs)), 'pairs_per_step': int(n_pairs), 'total_bases': int(lens.sum()),
-                'sha256': synth.sha256(codes, offsets) if len(codes) <= (1 << 33) else None,      # (the headline set: pinned in tests/golden/synth_sha256.json)
+                'sha256': synth.sha256(codes, offsets) if legs['sha256'] and len(codes) <= (1 << 33) else None,      # (the headline set: pinned in tests/golden/synth_sha256.json)
                 'parallelism': f'kmer-range x{world} prefilter (bases scanned in {world} slices, kept masks all-to-all), reference-range x{world} align',
             },
             'roofline': roofline,
@@ -604,6 +629,7 @@ def main():
             'out_aln': out_aln,
             'other_workloads': others,
             'placement_trials': trials,
+            'full': args.full,
             'dump_outputs': dumped,
             'comm': dict(kind=comm.kind, rccl_ranks=comm.rccl_ranks, strict=(kind == 'rccl-strict'), rccl_failure=rccl_failure,
                          backend=(dist.get_backend() if dist is not None else None)) if world > 1 else None,

@@ -523,6 +523,34 @@ def test_bench_two_ranks_smoke():
     assert d['n_gpus'] == 2 and d['config']['pairs_per_step'] == 6 * 45 and d['value'] > 0 and d['scaling'] == 'strong'
 
 
+def test_bench_plain_run_and_full(tmp_path):
+    """One GPU, six families: a plain run prints the headline line with every leg of --full null; --full adds the CLI,
+    --out-aln and CPU-baseline legs and the set's sha256 (the other workloads belong to the default set only)."""
+    import json
+    from vclust_amd import synth
+
+    def line(*extra):
+        p = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1',
+                            '--workload', 'phage-1k', '--count', '6', *extra], cwd=tmp_path,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        return json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])
+
+    plain = line()
+    assert plain['n_gpus'] == 1 and plain['config']['pairs_per_step'] == 6 * 45 and plain['value'] > 0 and plain['ms_per_step'] > 0
+    assert plain['full'] is False and plain['roofline'] is not None
+    assert all(plain[k] is None for k in ('cli_wall', 'out_aln', 'other_workloads', 'cpu_baseline')) and plain['config']['sha256'] is None
+    assert 'vs_cpu_baseline' not in plain
+    full = line('--full', '--cpu-reps', '1')
+    assert full['full'] is True and full['config']['pairs_per_step'] == 6 * 45 and full['value'] > 0
+    assert full['cli_wall']['cli_rows_equal_step'] is True and full['cli_wall']['rows'] > 0
+    assert full['out_aln']['regions'] > 0 and 'error' not in full['out_aln']
+    assert full['cpu_baseline']['value'] > 0 and full['vs_cpu_baseline']['device_resident'] > 0
+    assert full['other_workloads'] is None
+    codes, offsets, _, _ = synth.make_workload('phage-1k', 6)
+    assert full['config']['sha256'] == synth.sha256(codes, offsets)
+
+
 def test_rccl_two_ranks_when_two_gpus_are_visible():
     """The built-in RCCL communicator with two ranks on two GPUs (skipped on a one-GPU box; runs unattended
     wherever the suite sees >= 2 devices): sharded results equal the single-process ones on every rank."""

@@ -3,7 +3,7 @@
 set -u
 OUT=gpurun_out/r06f; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/tests_full.log 2>&1; echo "rc $?" >> $OUT/tests_full.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.json 2> $OUT/bench_driver_cmd.err
 bash tools/collect_profiles.sh r06 phage-100k "" 3 > $OUT/prof_100k.log 2>&1
 bash tools/collect_profiles.sh r06 phage-1k "" 10 > $OUT/prof_1k.log 2>&1
 bash tools/collect_profiles.sh r06 imgvr-10k "" 5 > $OUT/prof_imgvr.log 2>&1

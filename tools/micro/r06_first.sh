@@ -10,7 +10,7 @@ hipcc --offload-arch=gfx950 -O3 tools/micro/pool_sweep.hip -o /tmp/pool_sweep &&
 for v in default fused default fused; do
   VG_DEV_SWITCHES=1 VG_LZ_INDEX=$v timeout 300 python tools/micro/parse_ab.py >> $OUT/parse_ab.txt 2>&1
 done
-timeout 900 python bench.py --steps 5 --warmup 2 --cpu-reps 2 > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --steps 5 --warmup 2 --full --cpu-reps 2 > $OUT/bench.json 2> $OUT/bench.err
 timeout 900 python tools/strong_scaling_sim.py > $OUT/scaling.txt 2>&1
 tail -3 $OUT/tests.log; cat $OUT/pool_sweep.txt; cat $OUT/parse_ab.txt; grep "^==" $OUT/scaling.txt; python -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
