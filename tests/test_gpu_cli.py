@@ -184,7 +184,7 @@ def test_kernel_variants_write_the_same_files(tmp_path):
                      # the cold CLI's bounded footprint at a budget that bites here: eight RANGE sub-shards of the prefilter
                      # (k_part_scatter_range; then the all-positions scatter it replaces), many small index batches
                      ('subshards', dict(VG_WORKSPACE_GB='0.6')), ('subshards_dense', dict(VG_WORKSPACE_GB='1.5', VG_RANGE_SCATTER='dense')),
-                     ('index_batches', dict(VG_ONESHOT_INDEX_GB='0.25')), ('vmm_blocks', dict(VG_ALLOC='vmm', VG_WORKSPACE_GB='100', VG_ONESHOT_INDEX_GB='24'))):
+                     ('index_batches', dict(VG_ONESHOT_INDEX_GB='0.25'))):
         other = go(tag, **env)
         assert filecmp.cmp(base[0], other[0], shallow=False) and filecmp.cmp(base[1], other[1], shallow=False), tag
 
@@ -414,7 +414,7 @@ def test_four_processes_write_the_files_of_one(tmp_path):
 
 def test_ranks_that_plan_differently_are_stopped_before_the_exchange(tmp_path):
     """How a rank cuts its shard (sliced scan or not, RANGE or HASH shards) follows from PROCESS-LOCAL knobs (vg_set_subshards,
-    VG_RANGE_SCAN, VG_INDEX_PATH).  Two ranks on a set that takes the sliced scan; rank 1 forces sub-shards, which switches ITS
+    VG_INDEX_PATH).  Two ranks on a set that takes the sliced scan; rank 1 forces sub-shards, which switches ITS
     sliced scan off: without the agreement in front of the exchange rank 0 would wait inside the all-to-all for a peer that
     never comes.  Both ranks must return the same error, naming the cause, and the communicator must still work afterwards."""
     script = tmp_path / 'plan_mismatch.py'

@@ -273,12 +273,11 @@ def test_index_budget_batches_do_not_change_results():
     assert sorted(map(key, regions)) == sorted(map(key, ref_regions))
 
 
-@pytest.mark.parametrize('mode', ['vmm', 'malloc'])
+@pytest.mark.parametrize('mode', ['malloc'])
 def test_allocator_cycles_1_to_64_gib(mode):
-    """The device allocator under both of its paths (VG_ALLOC=vmm: reserved range + 2 GiB physical chunks, the path
-    behind round 3's unexplained aborts, now opt-in only; malloc: the default): three rounds of 1 + 4 + 17 + 64 GiB
-    blocks -- a size that is not a multiple of the chunk among them -- written and read back at both ends, released
-    and returned to the driver, in a process of its own (the mode is read once per process)."""
+    """The device allocator (hipMalloc blocks): three rounds of 1 + 4 + 17 + 64 GiB blocks -- a size that is not a
+    multiple of 2 MiB among them -- written and read back at both ends, released and returned to the driver, in a
+    process of its own."""
     import os
     import subprocess
     import pathlib
@@ -292,10 +291,10 @@ def test_allocator_cycles_1_to_64_gib(mode):
             'rc = lib.vg_alloc_selftest(sizes, 4, 3)\n'
             'assert rc == 0, lib.vg_last_error()\n'
             'print("ok")\n') % str(ROOT)
-    p = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, VG_DEV_SWITCHES='1', VG_ALLOC=mode, VG_ALLOC_TRACE='1'),
+    p = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, VG_ALLOC_TRACE='1'),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0 and p.stdout.strip().endswith('ok'), p.stderr[-3000:]
-    assert (' vmm of ' in p.stderr) == (mode == 'vmm')
+    assert ' hipMalloc of ' in p.stderr
 
 
 def test_prepared_indexes_do_not_change_the_rows():

@@ -46,8 +46,6 @@ def build_lib(force: bool = False, verbose: bool = False) -> pathlib.Path:
              '-Wno-unused-result', f'-I{ROOT / "include"}']
     if os.environ.get('VG_LINES') == '1':        # developer build: line tables for rocprofv3's PC sampling
         flags.append('-gline-tables-only')
-    if os.environ.get('VG_DEV') == '1':          # developer build: the instrumented parse kernel (tools/micro/lz_stats.py)
-        flags.append('-DVG_DEV_KERNELS')
     objs = []
     procs = []
     for s in srcs:

@@ -47,11 +47,11 @@ struct ref_desc {
     int32_t tag_bits;  // tag = the first tag_bits / 2 bases behind the msl-mer (<= mal - msl bases, <= 14 bits, <= 32 - pos_bits)
 };
 
-// ablate: developer timing experiments only; pw_*: probe widths; weak_ratio, margin, seed_choice: the constants of the
+// pw_*: probe widths; weak_ratio, margin, seed_choice: the constants of the
 // restatement that a handful of events of the reference's example hold (vg_lz_fit, include/vclust_gpu.h): R3's weak-seed
 // ratio (3; 0 = the rule is off), the symbols a far anchor must be longer than the seed by, minus one (msl - 1), and the
 // tie-break of seeds (3 = longest, then closest to the prediction; 1 = closest, then longest)
-struct lz_dev_params { int mal, msl, mrd, mqd, reg, aw, am, ar; int ablate; int pw_after, pw_miss; int weak_ratio; int margin; int seed_choice; };
+struct lz_dev_params { int mal, msl, mrd, mqd, reg, aw, am, ar; int pw_after, pw_miss; int weak_ratio; int margin; int seed_choice; };
 
 // ------------------------------------------------------------------ bit helpers
 // Two layouts of a sequence.  (1) The genome set's 2-bit codes, 16 bases per word (vg_common.h): what the prefilter and
@@ -1056,7 +1056,6 @@ struct seg_rec { int i_ev, ev_pos; uint32_t VM, VA, VN; };     // VN: bit 31 = o
 // known.  The unused tail of a wave's last chunk is marked.  A cursor beyond the arena's capacity = nothing was written
 // there: the host repeats the batch with an arena of exactly the size the cursor reports (the count of chunks a parse
 // takes is a function of its rows).
-constexpr int FUSED_SLOTS = 16384;         // EXPERIMENT (VG_LZ_INDEX=fused): 4^msl slots of eight words per reference (msl = 7)
 constexpr int RCHUNK = 8;
 struct region_rec { uint32_t task; int32_t qstart, qend, rstart, rend, n_match; uint32_t k, t; };     // 32 bytes; task = ~0u: unused slot
 static_assert(sizeof(region_rec) == 32, "arena record");
@@ -1068,18 +1067,16 @@ static_assert(sizeof(region_rec) == 32, "arena record");
     const uint32_t* __restrict__ rr_pool, const uint32_t* __restrict__ mask_pool, \
     const uint32_t* __restrict__ stab_pool, const uint32_t* __restrict__ sent_pool, \
     lz_dev_params P, vg_pair_stat* __restrict__ stats, \
-    region_rec* __restrict__ arena, unsigned long long* __restrict__ arena_cursor, unsigned long long arena_cap, \
-    const uint32_t* __restrict__ fslots
+    region_rec* __restrict__ arena, unsigned long long* __restrict__ arena_cursor, unsigned long long arena_cap
 #define PARSE_ARG_NAMES tasks, n_tasks, refs, planes, nmask, base_off, glen, g_has_n, rr_pool, mask_pool, \
-    stab_pool, sent_pool, P, stats, arena, arena_cursor, arena_cap, fslots
+    stab_pool, sent_pool, P, stats, arena, arena_cursor, arena_cap
 
 // FAST: the default LZ-ANI parameters and a set without N as compile-time constants (shift counts, loop bounds
 // and the mask paths fold away); the host launches it when both hold.
-template <int S, bool DEV, bool FAST = false, bool REG = false, bool FUSED = false>
+template <int S, bool FAST = false, bool REG = false>
 __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
     static_assert(!REG || S == 1, "regions are emitted by the one-wave parse (query order)");
-    if (FAST) { P.mal = 11; P.msl = 7; P.mrd = 40; P.mqd = 40; P.reg = 35; P.aw = 15; P.am = 7; P.ar = 3; P.ablate = 0; P.weak_ratio = 3; P.margin = 6; P.seed_choice = 3; }
-    const int ABL = DEV ? P.ablate : 0;           // developer timing knobs: compiled out of the production kernels
+    if (FAST) { P.mal = 11; P.msl = 7; P.mrd = 40; P.mqd = 40; P.reg = 35; P.aw = 15; P.am = 7; P.ar = 3; P.weak_ratio = 3; P.margin = 6; P.seed_choice = 3; }
     __shared__ seg_rec s_log[S > 1 ? S * SEG_LOG_CAP : 1];
     __shared__ int s_cnt[4], s_sync_v[4], s_sync_idx[4];
     __shared__ uint32_t s_end[4][3];
@@ -1099,19 +1096,15 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
     c.rpl = rr_pool + rd.rr_w; c.rmk = mask_pool + rd.mask_w; c.n_rr = rd.n_rr; c.L = rd.L; c.r_has_n = rd.has_n;
     const uint32_t* stab = stab_pool + rd.stab; const uint32_t* sent = sent_pool + rd.sent;
 
-    const long long t_start = (ABL & (32 | 1024)) ? (long long)wall_clock64() : 0;
     const int lim = c.qlen - P.mal;
     // segments: only worth it for queries of a few thousand bases
     const int seg_len = (S > 1 && lim >= S * 2048) ? ((((lim + S - 1) / S) + 63) & ~63) : (lim > 0 ? lim : 1);
     const int seg_start = (S > 1) ? min(w * seg_len, lim > 0 ? lim : 0) : 0;
     int phase_end = (S > 1 && w < S - 1) ? min((w + 1) * seg_len, lim) : lim;
     int i = seg_start, lit = 0, pred = 0; bool alive = false;
-    int n_events = 0, n_iter = 0, n_ab = 0, n_sb = 0;
+    int n_events = 0;
     int pw = 64;                 // lanes (query positions) probed per trip
     bool synced = false; int sync_v = -1, sync_idx = 0, log_n = 0, look_v = -1, look_cur = 0;
-    const bool prof = (ABL & 128) != 0; const int psel = (ABL >> 8) & 7;
-    long long pc[6] = {0, 0, 0, 0, 0, 0}; long long tp = prof ? (long long)clock64() : 0;
-#define PROF_MARK(k) do { if (DEV && prof) { long long tn_ = (long long)clock64(); pc[k] += tn_ - tp; tp = tn_; } } while (0)
     bool in_region = false; int r_qstart = 0, r_rstart = 0, r_qend = 0, r_rend = -1, r_match = 0, vend = 0;
     int kept_end = seg_start;
     uint32_t M = 0, A = 0, NR = 0;
@@ -1164,20 +1157,14 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
             // near the prediction) read ONE bucket: the entries of the query's msl-mer, four per trip.  An
             // entry is an anchor candidate when its tag (the bases behind the msl-mer) equals the query's, a
             // seed candidate when it lies in the prediction's window; a candidate is verified once.
-            const bool do_a = q_ok_a && !(ABL & 16);
-            const bool do_s = alive_l && q_ok_s && !(ABL & 1);
+            const bool do_a = q_ok_a;
+            const bool do_s = alive_l && q_ok_s;
             uint32_t s_u = 0, s_e = 0;
             const uint32_t posmask = (rd.pos_bits >= 32) ? 0xffffffffu : ((1u << rd.pos_bits) - 1u);
             const uint32_t qtag = tag_of(xq.lo, xq.hi, P.msl, rd.tag_bits);
             const bool probing = (do_a || do_s) && q_ok_s;
             const uint32_t b = bucket_of(xq.lo, xq.hi, P.msl);
-            uint4 f0 = make_uint4(~0u, ~0u, ~0u, ~0u), f1 = f0;
-            if (FUSED) {
-                // EXPERIMENT (VG_LZ_INDEX=fused): the bucket's first entries sit in a fixed 32-byte slot -- no bounds word in
-                // front of them, ONE line per probing lane; a word with bit 31 set ends the list (all ones) or, as the slot's
-                // last word, points at the bucket's remaining entries in the ordinary entry array
-                if (probing) { const uint32_t* sl = fslots + ((size_t)tk.r_slot * FUSED_SLOTS + b) * 8; __builtin_memcpy(&f0, sl, 16); __builtin_memcpy(&f1, sl + 4, 16); }
-            } else if (probing) {
+            if (probing) {
                 // bucket bounds = two neighbouring table words: one 8-byte load
                 uint2 bb; __builtin_memcpy(&bb, stab + (b ? b - 1 : 0u), 8);
                 s_u = b ? bb.x : 0u; s_e = b ? bb.y : bb.x;
@@ -1240,24 +1227,7 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
                     }
                 }
             };
-            if (FUSED) {
-                if (DEV) { ++n_ab; }
-                // (a slot's words with bit 31 set are not entries: padding or the pointer)
-                const unsigned vm0 = (unsigned)(!(f0.x >> 31)) | ((unsigned)(!(f0.y >> 31)) << 1) | ((unsigned)(!(f0.z >> 31)) << 2) | ((unsigned)(!(f0.w >> 31)) << 3);
-                const unsigned vm1 = (unsigned)(!(f1.x >> 31)) | ((unsigned)(!(f1.y >> 31)) << 1) | ((unsigned)(!(f1.z >> 31)) << 2) | ((unsigned)(!(f1.w >> 31)) << 3);
-                if (vm0) scan4(f0, vm0);
-                if (vm1) scan4(f1, vm1);
-                if ((f1.w >> 31) && f1.w != ~0u) {
-                    // the rest of a bucket of more than eight entries: count << 23 | first entry; count 255 = ask the bounds table
-                    s_u = f1.w & 0x7fffffu; const uint32_t cnt = (f1.w >> 23) & 0xffu;
-                    if (cnt == 255u) { uint2 bb; __builtin_memcpy(&bb, stab + (b ? b - 1 : 0u), 8); s_e = b ? bb.y : bb.x; }
-                    else s_e = s_u + cnt;
-                }
-                const unsigned long long hit0 = __ballot(best_len > 0 || sbest_len > 0);
-                if (hit0 && lane > __builtin_ctzll(hit0)) s_u = s_e;
-            }
             while (s_u < s_e) {
-                if (DEV) { ++n_ab; }
                 // four consecutive entries = one 16-byte load (the pool carries four entries of slack; entries past
                 // the bucket end are ignored below)
                 uint4 v; __builtin_memcpy(&v, sent + s_u, 16);
@@ -1283,8 +1253,6 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
             } else if (sbest_len > 0) { best_len = sbest_len; best_pos = sbest_pos; hit_close = true; }
         }
         const unsigned long long hb = __ballot(best_len > 0);
-        if (DEV) ++n_iter;
-        PROF_MARK(0);
         if (!hb) {
             // pw literals (or the tail); widen the next probe: a stretch without matches is scanned 64 at a time
             const int n = min(pw, lim - i);
@@ -1296,12 +1264,10 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
         pw = P.pw_after;            // the next match usually starts within a few positions of the end of this one
         // Pairs that need many events are the tail of the launch: a wave raises its own issue priority
         // as its event count grows, so the heavy pairs overtake the light ones sharing their SIMD.
-        if (!(ABL & 64)) {
-            ++n_events;
-            if (n_events == 24) __builtin_amdgcn_s_setprio(1);
-            else if (n_events == 64) __builtin_amdgcn_s_setprio(2);
-            else if (n_events == 160) __builtin_amdgcn_s_setprio(3);
-        }
+        ++n_events;
+        if (n_events == 24) __builtin_amdgcn_s_setprio(1);
+        else if (n_events == 64) __builtin_amdgcn_s_setprio(2);
+        else if (n_events == 160) __builtin_amdgcn_s_setprio(3);
         const int ev_pos = (int)lane32((uint32_t)best_pos, f);
         const bool ev_close = lane32((uint32_t)hit_close, f) != 0;
         // literals in front of the event
@@ -1316,27 +1282,25 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
         // (closing the open region may move kept_end: use the value it will have)
         const int kept_after = (in_region && r_qend - r_qstart + 1 >= P.reg) ? r_qend + 1 : kept_end;
         const int bwd_bound = ev_close ? 0 : i - kept_after;
-        const uint32_t mm_b = (!ev_close && !(ABL & 2)) ? extend_mask0<FAST>(c, i, ev_pos, -1, bwd_bound, lane, rlo, rhi) : ~0u;
+        const uint32_t mm_b = !ev_close ? extend_mask0<FAST>(c, i, ev_pos, -1, bwd_bound, lane, rlo, rhi) : ~0u;
         const uint32_t mm_f = extend_mask0<FAST>(c, i, ev_pos, +1, 1 << 30, lane, rlo, rhi);
-        PROF_MARK(1);
         if (!ev_close) {
             // R5: new region, extended to the left (exact, then approximate), not into the last kept region
             close_region();
             int bm = 0;
-            const int b = (ABL & 2) ? 0 : extend<FAST>(c, P, i, ev_pos, -1, bwd_bound, lane, &bm, mm_b, rlo, rhi);
+            const int b = extend<FAST>(c, P, i, ev_pos, -1, bwd_bound, lane, &bm, mm_b, rlo, rhi);
             r_qstart = i - b; r_rstart = ev_pos - b; r_match = bm; r_rend = -1;
             in_region = true;
         }
-        PROF_MARK(2);
         int fe, fm = 0;
         {   // the match itself and R4, one pass
-            fe = (ABL & 4) ? P.mal : extend<FAST>(c, P, i, ev_pos, +1, 1 << 30, lane, &fm, mm_f, rlo, rhi);
+            fe = extend<FAST>(c, P, i, ev_pos, +1, 1 << 30, lane, &fm, mm_f, rlo, rhi);
             r_match += fm;
         }
         if (ev_close) {
             // R7: the literal run in front of a chained match, laid against [pred0, end of the exact match)
             int pm = 0, sm = 0;
-            if (lit > 0 && !(ABL & 8)) {
+            if (lit > 0) {
                 // exact length of the match = position of the first mismatch of the forward pass
                 int xl = ev_len;
                 if (xl >= 32) {
@@ -1355,7 +1319,6 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
         }
         i += fe; pred = ev_pos + fe; lit = 0; alive = true;
         if (!ev_close) { r_rend = pred - 1; vend = pred; }
-        PROF_MARK(3);
         r_qend = i - 1;
         if (S > 1) {
             // After an event at (ev_i, ev_pos) the scan state is (i, pred, lit = 0, alive): a function of the
@@ -1410,14 +1373,6 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
         }
         return;
     }
-    if (prof) { M = (uint32_t)(pc[psel] >> 4); A = (uint32_t)n_events; }
-    if (ABL & 1024) {
-        // wave-level trip counts of the bucket loops = max over lanes
-        int mab = n_ab, msb = n_sb;
-        for (int o = 32; o; o >>= 1) { mab = max(mab, __shfl_xor(mab, o)); msb = max(msb, __shfl_xor(msb, o)); }
-        M = (uint32_t)n_iter; A = (uint32_t)n_events; if (ABL & 2048) { M = (uint32_t)mab; A = (uint32_t)msb; }
-    }
-    if (ABL & (32 | 1024)) NR = (uint32_t)((long long)wall_clock64() - t_start);        // developer timing: 100 MHz ticks
     if (REG && (NR & (RCHUNK - 1)) != 0) {
         // the unused tail of the last chunk: marked, one slot per lane
         const uint32_t used = NR & (RCHUNK - 1);
@@ -1429,39 +1384,15 @@ __device__ __forceinline__ void lz_parse_body(PARSE_ARGS) {
 
 // The parse is bound by dependent memory round trips, so resident waves are throughput: the
 // register budget is capped for the occupancy named in each kernel (waves per SIMD).
-#define PARSE_KERNEL(NAME, S, DEV, WAVES, FAST, REG, ...) \
+#define PARSE_KERNEL(NAME, S, WAVES, FAST, REG) \
     __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) NAME(PARSE_ARGS) { \
-        lz_parse_body<S, DEV, FAST, REG, ##__VA_ARGS__>(PARSE_ARG_NAMES); }
-PARSE_KERNEL(k_lz_parse, 1, false, 8, false, false)
-PARSE_KERNEL(k_lz_parse_fast, 1, false, 8, true, false)
-PARSE_KERNEL(k_lz_parse_seg, 4, false, 8, false, false)
-PARSE_KERNEL(k_lz_parse_seg_fast, 4, false, 8, true, false)
-PARSE_KERNEL(k_lz_parse_regions, 1, false, 8, false, true)            // --out-aln: rows AND regions from one parse
-PARSE_KERNEL(k_lz_parse_fast_regions, 1, false, 8, true, true)
-PARSE_KERNEL(k_lz_parse_fast_fused, 1, false, 8, true, false, true)     // EXPERIMENT: probes read fused bucket slots (VG_LZ_INDEX=fused)
-// EXPERIMENT: the fused slots of a batch's references made FROM the ordinary index (a conversion pass, so that the probe
-// side can be measured before a build kernel writes this layout itself): one workgroup per reference, a thread per bucket
-__global__ void __launch_bounds__(256)
-k_index_fuse(const ref_desc* __restrict__ refs, int first_ref, int n_refs, const uint32_t* __restrict__ stab_pool, const uint32_t* __restrict__ sent_pool,
-             uint32_t* __restrict__ fslots) {
-    for (int r = blockIdx.x; r < n_refs; r += gridDim.x) {
-        const ref_desc rd = refs[first_ref + r];
-        const uint32_t* stab = stab_pool + rd.stab; const uint32_t* sent = sent_pool + rd.sent;
-        uint32_t* out = fslots + (size_t)(first_ref + r) * FUSED_SLOTS * 8;
-        for (int b = threadIdx.x; b < FUSED_SLOTS; b += blockDim.x) {
-            const uint32_t lo = b ? stab[b - 1] : 0u, hi = stab[b], n = hi - lo;
-            uint32_t w[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) w[j] = (uint32_t)j < n ? sent[lo + j] : ~0u;
-            if (n > 8) w[7] = 0x80000000u | (((n - 7) < 255u ? (n - 7) : 255u) << 23) | (lo + 7);
-            uint4 a = make_uint4(w[0], w[1], w[2], w[3]), c2 = make_uint4(w[4], w[5], w[6], w[7]);
-            __builtin_memcpy(out + (size_t)b * 8, &a, 16); __builtin_memcpy(out + (size_t)b * 8 + 4, &c2, 16);
-        }
-    }
-}
-#ifdef VG_DEV_KERNELS      // developer build only (VG_DEV=1 python -m vclust_amd.build --force): timing knobs and counters
-PARSE_KERNEL(k_lz_parse_dev, 1, true, 3, false, false)
-#endif
+        lz_parse_body<S, FAST, REG>(PARSE_ARG_NAMES); }
+PARSE_KERNEL(k_lz_parse, 1, 8, false, false)
+PARSE_KERNEL(k_lz_parse_fast, 1, 8, true, false)
+PARSE_KERNEL(k_lz_parse_seg, 4, 8, false, false)
+PARSE_KERNEL(k_lz_parse_seg_fast, 4, 8, true, false)
+PARSE_KERNEL(k_lz_parse_regions, 1, 8, false, true)            // --out-aln: rows AND regions from one parse
+PARSE_KERNEL(k_lz_parse_fast_regions, 1, 8, true, true)
 
 // --out-aln, behind the parse: region counts of a batch's tasks in sorted-list order (the scan of them = every task's first
 // slot), and the move of every arena record to slot first[t] + k
@@ -1579,8 +1510,6 @@ struct lz_plan {
     lz_slot slot;
     int64_t budget = 0; int mal = 0, msl = 0; const vg_genomes* g = nullptr; int n_genomes = 0;
     bool batch0_built = false;
-    hipEvent_t built_ev = nullptr;            // batch 0 was queued on another queue than the library's: vg_lz_align waits for it
-    ~lz_plan() { if (built_ev) { (void)hipEventSynchronize(built_ev); (void)hipEventDestroy(built_ev); } }
 };
 int64_t lz_batch_budget(const vg_genomes* g, const vg_lz_params* p, const std::vector<uint32_t>& ref_ids);
 void lz_plan_references(const vg_genomes* g, const vg_lz_params* p, lz_plan& P);
@@ -1605,15 +1534,13 @@ void lz_keep_plan_host_side(std::unique_ptr<lz_plan>& plan) {
     if (!plan || vg_one_shot()) return;
     plan->slot = lz_slot(); plan->d_refs.release();            // (the pools go back to the allocator: nothing of the device is pinned)
     plan->batch0_built = false;
-    if (plan->built_ev) { (void)hipEventSynchronize(plan->built_ev); (void)hipEventDestroy(plan->built_ev); plan->built_ev = nullptr; }
     std::lock_guard<std::mutex> lk(g_prep_mu);
     g_plan_cache = std::move(plan);
 }
 }
 void vg_lz_drop_prepared(const vg_genomes* g) {
     std::lock_guard<std::mutex> lk(g_prep_mu);
-    // (a build deferred to the next SpGEMM -- developer experiment -- holds a raw pointer to the plan: it goes with it)
-    if (g_prepared && (!g || g_prepared->g == g)) { vg_set_spgemm_hook(nullptr); (void)hipStreamSynchronize(vg_stream()); g_prepared.reset(); }
+    if (g_prepared && (!g || g_prepared->g == g)) { (void)hipStreamSynchronize(vg_stream()); g_prepared.reset(); }
     if (g_plan_cache && (!g || g_plan_cache->g == g)) g_plan_cache.reset();
 }
 
@@ -1632,9 +1559,9 @@ k_genome_planes(const uint32_t* __restrict__ packed, int64_t n_pairs, uint32_t* 
 static std::mutex g_planes_mu;
 const uint32_t* vg_genome_planes(const vg_genomes* g, hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_planes_mu);
-    // The planes are always MADE on the library's stream; a caller on another queue (the developer experiments that build
-    // indexes on a queue of their own) waits for that stream's work up to here, whether this call launched the kernel or an
-    // earlier one did -- a pointer returned to a second queue never names planes that are still being written.
+    // The planes are always MADE on the library's stream; a caller on another queue waits for that stream's work up to
+    // here, whether this call launched the kernel or an earlier one did -- a pointer returned to a second queue never names
+    // planes that are still being written.
     hipStream_t lib = vg_stream();
     if (g->d_planes.n != g->d_packed.n || !g->d_planes.p) {
         const size_t words = g->d_packed.n & ~(size_t)1;
@@ -1713,28 +1640,21 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
         VG_HIP(hipStreamSynchronize(s));                      // the scratch buffers go out of scope
     }
     vg_host_mark("lz: tasks grouped");
-#ifdef VG_DEV_KERNELS
-    const char* abl = vg_dev_getenv("VG_LZ_ABLATE");
-#else
-    const char* abl = nullptr;                                // (the product library has no timing knobs)
-#endif
     // probe widths (speculation only: results do not depend on them): positions probed right after an event, and after a
     // first miss, before the scan goes to 64 per trip
-    static const int pw_after = [] { const char* e = vg_dev_getenv("VG_LZ_PW"); const int v = e ? atoi(e) : PW_AFTER_EVENT; return std::max(1, std::min(v, 64)); }();
-    static const int pw_miss = [] { const char* e = vg_dev_getenv("VG_LZ_PW2"); const int v = e ? atoi(e) : 64; return std::max(1, std::min(v, 64)); }();
+    const int pw_after = PW_AFTER_EVENT, pw_miss = 64;
     // R3's weak-seed ratio (a single-event fit): 3 unless VG_LZ_WEAK_SEED says otherwise (0 = off)
     const vg_lz_fit fit = lz_fit_now();
     const int weak_ratio = std::max(0, std::min(fit.weak_seed_ratio, 1000));
     const int margin = fit.anchor_margin >= 0 ? std::min(fit.anchor_margin, 1000) : p->msl - 1;
     const int seed_choice = fit.seed_choice == 1 ? 1 : 3;
-    const lz_dev_params P{ p->mal, p->msl, p->mrd, p->mqd, p->reg, p->aw, p->am, p->ar, abl ? atoi(abl) : 0, pw_after, pw_miss, weak_ratio, margin, seed_choice };
+    const lz_dev_params P{ p->mal, p->msl, p->mrd, p->mqd, p->reg, p->aw, p->am, p->ar, pw_after, pw_miss, weak_ratio, margin, seed_choice };
     // default parameters on a set without N: the kernel with those as compile-time constants (VG_LZ_KERNEL=general: never)
     static const bool no_fast = [] { const char* e = vg_dev_getenv("VG_LZ_KERNEL"); return e && !strcmp(e, "general"); }();
-    bool fast_params = !no_fast && !abl && weak_ratio == 3 && margin == 6 && seed_choice == 3 && p->mal == 11 && p->msl == 7 && p->mrd == 40 && p->mqd == 40 && p->reg == 35 && p->aw == 15 && p->am == 7 && p->ar == 3;
+    bool fast_params = !no_fast && weak_ratio == 3 && margin == 6 && seed_choice == 3 && p->mal == 11 && p->msl == 7 && p->mrd == 40 && p->mqd == 40 && p->reg == 35 && p->aw == 15 && p->am == 7 && p->ar == 3;
     for (int i = 0; fast_params && i < g->n; ++i) if (g->has_n[(size_t)i] || g->len[(size_t)i] >= (1 << 22)) fast_params = false;   // (tag: 8 bits beside <= 24 position bits)
 
     dbuf<vg_pair_stat> d_stats((size_t)n_tasks);
-    dbuf<uint32_t> fused_pool;                        // EXPERIMENT VG_LZ_INDEX=fused: 32-byte bucket slots of all references of the call
     const bool want_regions = regions != nullptr;
     std::vector<vg_region> h_regions;                 // all kept regions, batch after batch
     std::vector<vg_pair_stat> h_stats;                // host copy of the rows (sizes the region buffer)
@@ -1750,7 +1670,6 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
     {
         std::lock_guard<std::mutex> lk(g_prep_mu);
         if (g_prepared) {
-            vg_set_spgemm_hook(nullptr);                          // (a deferred build that has not run yet never will: the plan changes hands or goes)
             lz_plan& Q = *g_prepared;
             if (Q.g == g && Q.mal == p->mal && Q.msl == p->msl && Q.ref_ids == ref_ids && Q.budget == lz_batch_budget(g, p, ref_ids)) plan = std::move(g_prepared);
             else g_prepared.reset();                             // (its pools go back to the allocator: one stream, in order)
@@ -1765,7 +1684,6 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
             lz_plan_references(g, p, *plan);
         }
     }
-    if (plan->built_ev) VG_HIP(hipStreamWaitEvent(s, plan->built_ev, 0));
     std::vector<lz_batch>& batches = plan->batches;
     dbuf<ref_desc>& d_refs = plan->d_refs;
     lz_slot& slot = plan->slot;
@@ -1817,10 +1735,10 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
                     if (!ps) ps.emplace("lz_parse", B.bytes_alg);
                     if (fast_params) hipLaunchKernelGGL(k_lz_parse_fast_regions, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                        g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                       L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap, (const uint32_t*)nullptr);
+                                       L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap);
                     else hipLaunchKernelGGL(k_lz_parse_regions, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                        g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                       L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap, (const uint32_t*)nullptr);
+                                       L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap);
                     ps.reset();                                   // (the scope times the parse; what follows is the placing pass)
                     std::optional<vg_prof_scope> ps2; ps2.emplace("lz_regions_place", 0);      // (its kernels, not the downloads)
                     hipLaunchKernelGGL(k_region_counts, dim3(grid_for(nt + 1)), dim3(256), 0, s, (const task_dev*)(d_tasks.p + B.pos), nt, (const vg_pair_stat*)d_stats.p, d_first.p);
@@ -1854,50 +1772,24 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
                 }
                 continue;
             }
-            if (segments && P.ablate == 0 && nt < (1LL << 31)) {
+            if (segments && nt < (1LL << 31)) {
                 const int64_t nblk = (nt + 7) / 8 * 8;
                 if (fast_params) hipLaunchKernelGGL(k_lz_parse_seg_fast, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                    g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL, (const uint32_t*)nullptr);
+                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
                 else hipLaunchKernelGGL(k_lz_parse_seg, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                    g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL, (const uint32_t*)nullptr);
+                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
             } else {
                 const int64_t nblk = ((nt + 3) / 4 + 7) / 8 * 8;
-#ifdef VG_DEV_KERNELS
-                if (P.ablate) {
-                    hipLaunchKernelGGL(k_lz_parse_dev, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL, (const uint32_t*)nullptr);
-                } else
-#endif
-                static const bool fused_index = [] { const char* e = vg_dev_getenv("VG_LZ_INDEX"); return e && !strcmp(e, "fused"); }();      // EXPERIMENT
-                if (fast_params && fused_index && p->msl == 7) {
-                    // EXPERIMENT (profiles/r06_parse_fused_slots.md): the probes read fixed 32-byte bucket slots made from the
-                    // ordinary index by a conversion pass of its own scope -- the probe side of a layout measured before any
-                    // build kernel writes it
-                    ps.reset();
-                    if (!fused_pool.p) fused_pool.alloc((size_t)plan->all_refs.size() * FUSED_SLOTS * 8 + 8);
-                    {
-                        vg_prof_scope pf("lz_index_fuse", (double)B.n_refs * FUSED_SLOTS * 32.0);
-                        hipLaunchKernelGGL(k_index_fuse, dim3((unsigned)std::min(B.n_refs, 256 * 16)), dim3(256), 0, s, (const ref_desc*)d_refs.p, B.first_ref, B.n_refs,
-                                           (const uint32_t*)L.stab_pool.p, (const uint32_t*)L.sent_pool.p, fused_pool.p);
-                    }
-                    ps.emplace("lz_parse", B.bytes_alg);
-                    hipLaunchKernelGGL(k_lz_parse_fast_fused, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL, (const uint32_t*)fused_pool.p);
-                } else
                 if (fast_params) {
-                    // (developer experiment: VG_LZ_OCC_KB reserves that much unused LDS per workgroup, i.e. caps the resident waves)
-                    static const size_t occ_lds = [] { const char* e = vg_dev_getenv("VG_LZ_OCC_KB"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();
-                    hipLaunchKernelGGL(k_lz_parse_fast, dim3((unsigned)nblk), dim3(256), occ_lds, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
+                    hipLaunchKernelGGL(k_lz_parse_fast, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                    g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL, (const uint32_t*)nullptr);
+                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
                 } else {
                     hipLaunchKernelGGL(k_lz_parse, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                    g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL, (const uint32_t*)nullptr);
+                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
                 }
             }
             if (want_regions) {
@@ -1926,7 +1818,7 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
                     const int64_t nblk = ((nt + 3) / 4 + 7) / 8 * 8;
                     hipLaunchKernelGGL(k_lz_parse_regions, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
                                    g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap, (const uint32_t*)nullptr);
+                                   L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap);
                     hipLaunchKernelGGL(k_regions_place, dim3(grid_for((int64_t)cap)), dim3(256), 0, s, (const region_rec*)d_arena.p, cap,
                                        (const unsigned long long*)d_off.p, nr, d_regions.p, d_bad.p);
                     unsigned int bad = 0; d_bad.download(&bad, 1, s);
@@ -2167,39 +2059,6 @@ extern "C" int vg_lz_prepare(vg_genomes* g, const vg_pair_count* pairs, int64_t 
         lz_plan_references(g, p, *plan);
         vg_host_mark("lz prepare: planned");
     }
-    // (developer experiment VG_LZ_PREPARE_QUEUE=own: the build runs on a queue of its own, beside whatever the caller
-    // launches next on the library's queue -- a prefilter pass, if the references are known before it)
-    static const bool own_queue = [] { const char* e = vg_dev_getenv("VG_LZ_PREPARE_QUEUE"); return e && !strcmp(e, "own"); }();
-    static const bool at_spgemm = [] { const char* e = vg_dev_getenv("VG_LZ_PREPARE_QUEUE"); return e && !strcmp(e, "spgemm"); }();
-    if (at_spgemm) {
-        // the build is queued (own queue) when the next prefilter pass reaches its SpGEMM: random reads beside LDS-staged writes
-        lz_plan* raw = plan.get(); const vg_lz_params pp = *p;
-        VG_HIP(hipEventCreateWithFlags(&plan->built_ev, hipEventDisableTiming));
-        VG_HIP(hipEventRecord(plan->built_ev, vg_stream()));                   // (a pass that never comes: the event is complete anyway)
-        raw->batch0_built = false;
-        vg_set_spgemm_hook([g, pp, raw] {
-            static hipStream_t q = nullptr;
-            if (!q && hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return;
-            hipEvent_t e0 = nullptr; if (hipEventCreateWithFlags(&e0, hipEventDisableTiming) != hipSuccess) return;
-            (void)hipEventRecord(e0, vg_stream()); (void)hipStreamWaitEvent(q, e0, 0); (void)hipEventDestroy(e0);
-            lz_build_batch(g, &pp, *raw, 0, q);
-            (void)hipEventRecord(raw->built_ev, q);
-            raw->batch0_built = true;
-        });
-        vg_host_mark("lz: first batch of indexes deferred to the SpGEMM");
-        std::lock_guard<std::mutex> lk(g_prep_mu);
-        g_prepared = std::move(plan);
-        return VG_OK;
-    }
-    if (own_queue) {
-        static hipStream_t q = nullptr;
-        if (!q) VG_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-        hipEvent_t e0 = nullptr; VG_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-        VG_HIP(hipEventRecord(e0, vg_stream())); VG_HIP(hipStreamWaitEvent(q, e0, 0)); (void)hipEventDestroy(e0);      // (the pools may have work of the library queue pending)
-        lz_build_batch(g, p, *plan, 0, q);
-        VG_HIP(hipEventCreateWithFlags(&plan->built_ev, hipEventDisableTiming));
-        VG_HIP(hipEventRecord(plan->built_ev, q));
-    } else
     lz_build_batch(g, p, *plan, 0, vg_stream());
     plan->batch0_built = true;
     vg_host_mark("lz: first batch of indexes queued");

@@ -150,7 +150,6 @@ struct vg_slice_exchange {
     bool agreed = false;        // the agreement in front of the exchange has taken place (the failure handling of the caller pairs it otherwise)
 };
 // whether a shard pass of (g, k, fraction) over `world` ranks takes the sliced scan: a pure function of its arguments
-void vg_set_spgemm_hook(std::function<void()> fn);      // developer experiment: run once right before the next SpGEMM launch
 bool vg_slice_exchange_applies(const vg_genomes* g, int k, double fraction, int world);
 int vg_kmer_shard_mode(const vg_genomes* g, double fraction, int n_shards);      // 1 = RANGE shards, 2 = HASH shards (what a rank of an n_shards-way call would do)
 // one k-mer range shard of vg_kmer_shared with the (a, b, shared) records left in HBM (vg_prefilter.hip; used by vg_dist.hip)

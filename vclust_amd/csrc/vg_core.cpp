@@ -174,7 +174,7 @@ hipStream_t vg_side_stream() {
     return g_side_stream;
 }
 
-// time this process has spent inside the driver's allocation calls (hipMalloc / hipMemCreate + hipMemMap), all threads
+// time this process has spent inside the driver's allocation calls (hipMalloc), all threads
 static std::atomic<int64_t> g_alloc_wait_us{0};
 double vg_alloc_wait_ms() { return (double)g_alloc_wait_us.load() / 1e3; }
 
@@ -219,6 +219,12 @@ constexpr size_t ALLOC_GRAN = 1 << 12;
 const bool g_alloc_trace = [] { const char* e = getenv("VG_ALLOC_TRACE"); return e && *e && *e != '0'; }();
 }
 
+// one-shot mode: set by the whole-stage calls (vg_prefilter / vg_align) for their duration
+static std::atomic<int> g_one_shot{0};
+void vg_one_shot_begin() { ++g_one_shot; }
+void vg_one_shot_end() { --g_one_shot; }
+bool vg_one_shot() { return g_one_shot.load() > 0; }
+
 // Device blocks come from plain hipMalloc.  What an allocation costs on this platform is not a property of the call but
 // of the memory it lands on (tools/micro/first_touch.hip, profiles/r04_first_touch.txt): memory the driver holds clean
 // is handed out in well under a millisecond per 8 GiB, memory it still has to wipe -- what the PREVIOUS process on the
@@ -226,91 +232,17 @@ const bool g_alloc_trace = [] { const char* e = getenv("VG_ALLOC_TRACE"); return
 // call (up to 6 s were seen when a 240 GiB process had just gone).  Nothing in the process can shorten that, so the
 // cold one-shot calls of the CLI keep their footprint small instead (vg_one_shot: k-mer sub-shards under a workspace
 // budget in the prefilter, small index batches in the align stage): the exposure is ~10 GB, not ~100 GB.
-// The virtual memory management path (one reserved range, 2 GiB physical chunks: hipMemCreate / hipMemMap) remains behind
-// VG_ALLOC=vmm for experiments: round 3 used it for the CLI's large blocks and took its speed on clean memory for a
-// property of the API; two aborts inside a long test process were seen with it on for everything and never explained.
-static int g_vmm_mode = [] { const char* e = vg_dev_getenv("VG_ALLOC"); return !e ? 0 : !strcmp(e, "vmm") ? 1 : !strcmp(e, "malloc") ? -1 : 0; }();
-static bool g_vmm_alloc = g_vmm_mode > 0;
-// one-shot mode: set by the whole-stage calls (vg_prefilter / vg_align) for their duration
-static std::atomic<int> g_one_shot{0};
-void vg_one_shot_begin() { ++g_one_shot; }
-void vg_one_shot_end() { --g_one_shot; }
-bool vg_one_shot() { return g_one_shot.load() > 0; }
-namespace {
-struct vmm_block { std::vector<hipMemGenericAllocationHandle_t> handles; size_t total; };
-std::map<void*, vmm_block> g_vmm_blocks;
-std::mutex g_vmm_mu;
-constexpr size_t VMM_MIN = 1ull << 30, VMM_CHUNK = 2ull << 30;
-}
-static void vmm_release(void* va, vmm_block& b, size_t mapped_chunks) {
-    if (mapped_chunks) (void)hipMemUnmap(va, std::min(b.total, mapped_chunks * VMM_CHUNK));
-    for (auto& h : b.handles) (void)hipMemRelease(h);
-    (void)hipMemAddressFree(va, b.total);
-}
-static hipError_t vmm_alloc(void** p, size_t bytes) {
-    hipMemAllocationProp prop = {}; prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = g_device;
-    size_t gran = 0;
-    hipError_t e = hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended);
-    if (e != hipSuccess) return e;
-    if (gran < (2u << 20)) gran = 2u << 20;
-    vmm_block b; b.total = (bytes + gran - 1) / gran * gran;
-    void* va = nullptr;
-    e = hipMemAddressReserve(&va, b.total, 0, nullptr, 0);
-    if (e != hipSuccess) return e;
-    size_t mapped = 0;
-    for (size_t off = 0; off < b.total; off += VMM_CHUNK) {
-        const size_t n = std::min(VMM_CHUNK, b.total - off);
-        hipMemGenericAllocationHandle_t h;
-        e = hipMemCreate(&h, n, &prop, 0);
-        if (e != hipSuccess) break;
-        b.handles.push_back(h);
-        e = hipMemMap((char*)va + off, n, 0, h, 0);
-        if (e != hipSuccess) break;
-        ++mapped;
-    }
-    if (e == hipSuccess) {
-        hipMemAccessDesc acc = {}; acc.location = prop.location; acc.flags = hipMemAccessFlagsProtReadWrite;
-        e = hipMemSetAccess(va, b.total, &acc, 1);
-    }
-    if (e != hipSuccess) { vmm_release(va, b, mapped); return e; }
-    std::lock_guard<std::mutex> lk(g_vmm_mu);
-    g_vmm_blocks[va] = std::move(b);
-    *p = va;
-    return hipSuccess;
-}
-static hipError_t raw_alloc_untimed(void** p, size_t bytes, const char** path) {
-    if (g_vmm_alloc && bytes >= VMM_MIN) {
-        *path = "vmm";
-        const hipError_t e = vmm_alloc(p, bytes);
-        if (e == hipSuccess || e == hipErrorOutOfMemory) return e;
-        (void)hipGetLastError();                      // the API is not usable here: plain allocation
-    }
-    *path = "hipMalloc";
-    return hipMalloc(p, bytes);
-}
 static hipError_t raw_alloc(void** p, size_t bytes) {
     const auto t0 = std::chrono::steady_clock::now();
-    const char* path = "";
-    const hipError_t e = raw_alloc_untimed(p, bytes, &path);
+    const hipError_t e = hipMalloc(p, bytes);
     const int64_t us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     g_alloc_wait_us += us;
     if (g_alloc_trace && bytes >= (256u << 20))
-        fprintf(stderr, "[vg alloc] %s of %.2f GiB took %.1f ms (%.1f ms per GiB)%s\n", path, bytes / 1073741824.0, us / 1e3,
+        fprintf(stderr, "[vg alloc] hipMalloc of %.2f GiB took %.1f ms (%.1f ms per GiB)%s\n", bytes / 1073741824.0, us / 1e3,
                 us / 1e3 / (bytes / 1073741824.0), e == hipSuccess ? "" : " -- FAILED");
     return e;
 }
-static void raw_free(void* p) {
-    {
-        std::unique_lock<std::mutex> lk(g_vmm_mu);
-        auto it = g_vmm_blocks.find(p);
-        if (it != g_vmm_blocks.end()) {
-            vmm_block b = std::move(it->second); g_vmm_blocks.erase(it); lk.unlock();
-            vmm_release(p, b, b.handles.size());
-            return;
-        }
-    }
-    (void)hipFree(p);
-}
+static void raw_free(void* p) { (void)hipFree(p); }
 
 // allocations that are only an optimisation (a second set of scan buffers, pre-zeroed row pointers) must neither wait for
 // another process's memory nor trim the cache: vg_dev_try_scope makes every allocation of its thread fail fast
@@ -419,9 +351,9 @@ extern "C" void vg_release_device_memory(void) {
     catch (...) { (void)hipGetLastError(); }
 }
 
-// allocator self-test: `cycles` times allocate blocks of the given sizes from the library's allocator (whichever path
-// VG_ALLOC selects), write a pattern into the first and last MiB of each with a copy from the host, read it back,
-// release the blocks and return the cache to the driver.  (tests/test_gpu_parity.py runs it under VG_ALLOC=vmm.)
+// allocator self-test: `cycles` times allocate blocks of the given sizes from the library's allocator, write a pattern
+// into the first and last MiB of each with a copy from the host, read it back, release the blocks and return the cache
+// to the driver.  (tests/test_gpu_parity.py runs it.)
 extern "C" int vg_alloc_selftest(const int64_t* sizes, int n_sizes, int cycles) {
     VG_API_BEGIN
     if (!sizes || n_sizes <= 0 || cycles <= 0) throw vg_error(VG_EINVAL, "vg_alloc_selftest: bad argument");

@@ -424,10 +424,10 @@ extern "C" int vg_kmer_shared_sharded(vg_genomes* g, int k, double fraction, uin
     const bool sliced = W > 1 && vg_slice_exchange_applies(g, k, fraction, W);
     // EVERY rank of a world > 1 goes through ONE "prefilter scan" agreement in front of its shard's exchanges, sliced or
     // not, and the agreement carries how the rank is about to work: (sliced scan?, RANGE / HASH cut).  Both are decided from
-    // process-local knobs (vg_set_subshards, VG_RANGE_SCAN, VG_INDEX_PATH); a rank that decided differently would otherwise
+    // process-local knobs (vg_set_subshards, VG_INDEX_PATH); a rank that decided differently would otherwise
     // skip or add a collective and leave its peers inside grouped ncclSend / ncclRecv.  A mismatch throws on every rank.
     const uint32_t my_plan = W > 1 ? (uint32_t)(sliced ? 1 : 0) | ((uint32_t)vg_kmer_shard_mode(g, fraction, W) << 1) : 0u;
-    const char* plan_mismatch = "plan the prefilter shard differently (sliced scan / RANGE against HASH shards: do the ranks differ in vg_set_subshards, VG_RANGE_SCAN or VG_INDEX_PATH?)";
+    const char* plan_mismatch = "plan the prefilter shard differently (sliced scan / RANGE against HASH shards: do the ranks differ in vg_set_subshards or VG_INDEX_PATH?)";
     xs.alltoallv = [&](int status, const vg_xpart* parts, int n_parts) {
         xs.agreed = true;
         agree_exchange(c, status, my_plan, parts, n_parts, "prefilter scan", plan_mismatch);

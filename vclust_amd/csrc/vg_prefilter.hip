@@ -2293,14 +2293,11 @@ static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, i
 
 // partition digits of the bucket pipeline for n_expect elements: false = the pipeline declines (buckets beyond the LDS sorts)
 static bool bucket_digits(int64_t n_expect, int* total_bits_out, int* B1_out, int* B2_out) {
-    static const int tb_env = [] { const char* e = vg_dev_getenv("VG_TOTAL_BITS"); return e ? atoi(e) : 0; }();     // developer experiments
     int total_bits = 0; while ((n_expect >> total_bits) > 1024 && total_bits < 22) ++total_bits;
-    if (tb_env > 0 && tb_env < total_bits) total_bits = tb_env;
     if ((n_expect >> total_bits) > 4096) return false;
-    static const char* b2_env = vg_dev_getenv("VG_B2");          // developer experiments: level-2 bits
     // level 1 takes 11 bits whenever there are two levels: its segment length does not depend on the digit (tiles of
     // 32 768), level 2's grows as its digit shrinks, and 2k - 11 key bits fit the short records up to k = 25
-    const int B2 = total_bits > 11 ? (b2_env ? atoi(b2_env) : total_bits - 11) : 0;
+    const int B2 = total_bits > 11 ? total_bits - 11 : 0;
     *total_bits_out = total_bits; *B2_out = B2; *B1_out = total_bits - B2;
     return true;
 }
@@ -2314,8 +2311,7 @@ static bool index_path_buckets() {
 static int g_range_scan_mode = 0;
 bool vg_slice_exchange_applies(const vg_genomes* g, int k, double fraction, int world) {
     (void)k;
-    static const bool replicated = [] { const char* e = vg_dev_getenv("VG_RANGE_SCAN"); return e && !strcmp(e, "replicated"); }();      // developer A/B
-    if (replicated || world < 2 || world > SX_MAX_WORLD || g_force_subshards > 1 || !range_shards(g, fraction, world)) return false;
+    if (world < 2 || world > SX_MAX_WORLD || g_force_subshards > 1 || !range_shards(g, fraction, world)) return false;
     const int64_t P = g->padded_total();
     if (!index_path_buckets() || P < (1 << 16) || P >= (1LL << 32)) return false;
     int total_bits = 0, B1 = 0, B2 = 0;
@@ -2385,8 +2381,6 @@ static void sliced_count(int k, const part_src& S, vg_slice_exchange* xs, int st
 // set by the sub-shard loop (kmer_shared_subshards): the k-mer scan of the NEXT sub-shard, started on the second queue at
 // a point where the library queue is idle
 static std::function<void()> g_after_extract;
-static std::function<void()> g_spgemm_hook;
-void vg_set_spgemm_hook(std::function<void()> fn) { g_spgemm_hook = std::move(fn); }
 static void run_scan_hook() { if (g_after_extract) { auto hook = std::move(g_after_extract); g_after_extract = nullptr; hook(); } }
 // A RANGE shard of the dense source (A.dig_n < 2^11): `ri` receives the kept masks, the row bases and the row -> genome
 // map of the pass, n_rows_info becomes the number of kept k-mers, and the row pointers are indexed by row number.
@@ -2430,8 +2424,7 @@ static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_arg
     struct ev_guard { hipEvent_t& e; hipStream_t st; ~ev_guard() { if (e) { (void)hipStreamWaitEvent(st, e, 0); (void)hipEventDestroy(e); } } } ev_g{ ev_rows_zero, s };
     // (dense single-pass sets only, whose whole workspace is a fraction of the HBM: with sub-shards of 10^6 contigs the
     // extra 14 GB block pushed the caching allocator into trims and fresh hipMallocs -- 8.2 s per pass instead of 2.7)
-    static const bool no_prezero = [] { const char* e = vg_dev_getenv("VG_ROWS_PREZERO"); return e && *e == '0'; }();      // developer A/B
-    if (levels == 2 && dense && !no_prezero && !range) {
+    if (levels == 2 && dense && !range) {
         // (the device's total memory: asked once -- hipMemGetInfo is a driver round trip on every pass otherwise)
         static const size_t tot = [] { size_t fr0 = 0, t0 = 0; return hipMemGetInfo(&fr0, &t0) == hipSuccess ? t0 : (size_t)0; }();
         if (tot && (size_t)n_rows_info * 4 * 8 <= tot / 2) try {
@@ -2537,9 +2530,8 @@ static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_arg
         a_rec.alloc(levels == 2 ? std::max((short_rec ? 2 : 3) * n_cap + 8, rows_cap + n_cap + 16) : 3 * n_cap + 8);
         const int grid_s = (int)std::min<int64_t>(n_st, 256);
         static const bool range_dense = [] { const char* e = vg_dev_getenv("VG_RANGE_SCATTER"); return e && !strcmp(e, "dense"); }();      // developer A/B
-        static const bool range_32k = [] { const char* e = vg_dev_getenv("VG_RANGE_TILE"); return e && !strcmp(e, "32k"); }();      // developer A/B
         // (two tiles at a time when the shard keeps a sixth of the positions or less: their kept k-mers fit one list)
-        const bool tile64k = st_tiles % 8 == 0 && !range_32k && (uint64_t)A.dig_n * 6 <= (1u << DIG_BITS);
+        const bool tile64k = st_tiles % 8 == 0 && (uint64_t)A.dig_n * 6 <= (1u << DIG_BITS);
         if (tile32k && range && nb1 <= RG_MAXBINS && !range_dense) {
             const int tsh = short_rec ? L2.kr : 0;
             if (tile64k) {
@@ -2598,9 +2590,7 @@ static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_arg
         // (the library queue is idle here too.  Starting the scan of the next HASH sub-shard HERE, beside the bucket kernel,
         // instead of in front of the SpGEMM was measured at 10^6 contigs once the SpGEMM had dropped to 16 ms and no longer
         // covered the 52 ms scan: 2 502 against 2 458 ms per step -- the bucket kernel takes 86 ms instead of 55 beside it;
-        // the scan's arithmetic is additive wherever it runs.  VG_SUBSHARD_SCAN=early selects it.)
-        static const bool early_scan = [] { const char* e = vg_dev_getenv("VG_SUBSHARD_SCAN"); return e && !strcmp(e, "early"); }();
-        if (early_scan) run_scan_hook();
+        // the scan's arithmetic is additive wherever it runs: it starts in front of the SpGEMM.)
         vg_deferred_start();                                  // (the bucket kernel and the SpGEMM are the long waits of the call)
         f_rec = b_rec.p; f_stride = narrow ? 2 : 3;
         arena = std::move(a_rec);
@@ -2759,7 +2749,6 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
     // k-mer scan of the NEXT sub-shard on the second queue, beside this sub-shard's SpGEMM: arithmetic beside random
     // reads.  Started earlier, beside the partition kernels, the scan only took their CUs: 2.70 against 2.74 s.)
     run_scan_hook();
-    if (g_spgemm_hook) { auto hook = std::move(g_spgemm_hook); g_spgemm_hook = nullptr; hook(); }      // (developer experiment: work queued beside the SpGEMM)
     // SpGEMM with a growing output buffer
     dbuf<unsigned long long> d_cursor(1);
     dbuf<uint32_t> d_over((size_t)n), d_nover(1);
@@ -2918,7 +2907,6 @@ static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int sha
     for (int i = 0; i < n; ++i) set_sizes[i] = 0;
     std::vector<dbuf<vg_pair_count>> parts((size_t)sub); std::vector<unsigned long long> counts((size_t)sub, 0ULL);
     std::vector<vg_pair_count> none;
-    static const bool no_overlap = [] { const char* e = vg_dev_getenv("VG_SUBSHARD_OVERLAP"); return e && *e == '0'; }();      // developer A/B
     struct hook_guard { ~hook_guard() { g_after_extract = nullptr; g_precount.drop(); g_pass_mask = pass_mask(); } } hg;
     // HASH sub-shards: ONE scan of the bases leaves the kept masks of all passes (k_multi_mask); a pass then computes the
     // k-mers of its kept positions only.  (sub x P / 8 bytes of masks -- 22 GB at 10^6 contigs -- replace two sets of
@@ -2942,7 +2930,7 @@ static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int sha
         g_after_extract = nullptr;
         g_pass_mask = pass_mask();
         if (multi) { g_pass_mask.g = g; g_pass_mask.k = k; g_pass_mask.shard = shard * sub + t; g_pass_mask.n_shards = n_shards * sub; g_pass_mask.mask = all_masks.p + (size_t)t * (size_t)Wm; }
-        if (!multi && t + 1 < sub && !(fraction < 1.0) && !no_overlap && !range_shards(g, fraction, n_shards * sub))      // (HASH shards: the compact source scans first)
+        if (!multi && t + 1 < sub && !(fraction < 1.0) && !range_shards(g, fraction, n_shards * sub))      // (HASH shards: the compact source scans first)
             g_after_extract = [=] {
                 // (an optimisation only: without room for the second set of scan buffers the next sub-shard scans in line)
                 try { vg_dev_try_scope opportunistic; launch_precount(g, k, shard * sub + t + 1, n_shards * sub); } catch (...) { (void)hipGetLastError(); g_precount.drop(); }
@@ -3070,7 +3058,7 @@ extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, 
 
 // how a rank of an n_shards-way call cuts the k-mers (1 = RANGE, 2 = HASH): the two do not tile the key space together, so
 // the ranks of a sharded call compare notes BEFORE anything is exchanged (a per-process knob -- vg_set_subshards,
-// VG_RANGE_SCAN, VG_INDEX_PATH -- can differ between processes).  A pure function of the set and the process's knobs.
+// VG_INDEX_PATH -- can differ between processes).  A pure function of the set and the process's knobs.
 int vg_kmer_shard_mode(const vg_genomes* g, double fraction, int n_shards) {
     const int64_t P = g->padded_total();
     int64_t real_bases = 0; for (int i = 0; i < g->n; ++i) real_bases += g->len[(size_t)i];
