@@ -177,6 +177,12 @@ int vg_read_filter(const vg_genomes* g, const char* path, double thr,
  * (q = b, r = a), (q = a, r = b), couples ascending in (a, b).  ids are input-order ids. */
 int vg_align_tasks(const vg_genomes* g, const vg_pair_count* pairs, int64_t n_pairs,
                    vg_task** tasks, int64_t* n_tasks);
+/* parity tests: the index vg_lz_align would build for genome `idx` under p (no reference call site).  bucket_end: 4^msl
+ * words, the END of each bucket in `entries`; entries: *n_entries words, pos | tag << pos_bits; path: the build that made
+ * it, 0..5 the register build of 24, 20, 16, 12, 8, 4 trips, 6 mid, 7 lds, 8 global.  Both arrays: vg_free(). */
+int vg_lz_index_dump(vg_genomes* g, int idx, const vg_lz_params* p,
+                     uint32_t** bucket_end, uint32_t** entries, int64_t* n_entries,
+                     int* pos_bits, int* tag_bits, int* path);
 /* HBM budget (bytes) for the per-reference indexes of one vg_lz_align batch (default 24 GiB; without a call a set whose
  * indexes all fit in twice the default is built as one batch) */
 void vg_set_index_budget(int64_t bytes);

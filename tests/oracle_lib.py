@@ -31,6 +31,17 @@ class PairStat(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ('q', 'r', 'n_match', 'aln_len', 'n_regions')]
 
 
+class LzVariant(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('sep_len', 'anchor_while_predicting', 'bwd_bound_kept', 'bwd_exact_first', 'seed_window',
+                                       'seed_back', 'seed_fwd', 'seed_choice', 'lit_reset_ge', 'gap_mode', 'fwd_after_close',
+                                       'loop_le', 'anchor_tie', 'reg_on_span', 'rend_mode', 'trace', 'anchor_margin',
+                                       'weak_seed_ratio')]
+
+
+class OracleRegion(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('qstart', 'qend', 'rstart', 'rend', 'n_match', 'n_mismatch')]
+
+
 class PairCount(C.Structure):
     _fields_ = [('a', C.c_uint32), ('b', C.c_uint32), ('shared', C.c_uint32)]
 
@@ -62,6 +73,15 @@ def lib():
         L.vo_lz_pair_stat.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(LzParams),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.vo_lz_pair_stat.restype = C.c_int
+        L.vo_lz_default_variant.argtypes = [C.POINTER(LzVariant)]
+        L.vo_lz_default_variant.restype = None
+        L.vo_lz_build_index.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LzParams), C.POINTER(LzVariant)]
+        L.vo_lz_build_index.restype = C.c_void_p
+        L.vo_lz_free_index.argtypes = [C.c_void_p]
+        L.vo_lz_free_index.restype = None
+        L.vo_lz_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LzParams), C.POINTER(LzVariant),
+                                  C.POINTER(C.POINTER(OracleRegion)), C.POINTER(C.c_int)]
+        L.vo_lz_parse.restype = C.c_int
         L.vo_path_rows.argtypes = [C.POINTER(GenomeSet), C.c_int, C.c_int, C.c_double, C.POINTER(LzParams),
                                    C.POINTER(C.POINTER(PairStat)), C.POINTER(C.c_int64)]
         L.vo_path_rows.restype = C.c_int
@@ -155,6 +175,37 @@ def lz_pair_stat(q, r, lz=None):
     lib().vo_lz_pair_stat(q.ctypes.data_as(C.c_void_p), len(q), r.ctypes.data_as(C.c_void_p), len(r),
                           C.byref(prm), C.byref(m), C.byref(a), C.byref(n))
     return m.value, a.value, n.value
+
+
+REGION5_DTYPE = np.dtype([('qstart', '<i4'), ('qend', '<i4'), ('rstart', '<i4'), ('rend', '<i4'), ('n_match', '<i4')])
+
+
+def lz_regions(q, r, lz=None):
+    """The oracle's kept regions of query q against reference r, in parse (= query) order: a structured array
+    (qstart, qend, rstart, rend, n_match), 0-based inclusive, r* in the space fwd | N | rc -- vg_region's coordinates."""
+    prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    r = np.ascontiguousarray(r, dtype=np.uint8)
+    L = lib()
+    v = LzVariant()
+    L.vo_lz_default_variant(C.byref(v))
+    ix = L.vo_lz_build_index(r.ctypes.data_as(C.c_void_p), len(r), C.byref(prm), C.byref(v))
+    if not ix:
+        raise MemoryError('vo_lz_build_index')
+    regs = C.POINTER(OracleRegion)()
+    n = C.c_int()
+    try:
+        L.vo_lz_parse(ix, q.ctypes.data_as(C.c_void_p), len(q), C.byref(prm), C.byref(v), C.byref(regs), C.byref(n))
+        out = np.zeros(n.value, dtype=REGION5_DTYPE)
+        if n.value:
+            raw = np.ctypeslib.as_array(C.cast(regs, C.POINTER(C.c_int32)), shape=(n.value, 6))
+            for j, name in enumerate(REGION5_DTYPE.names):
+                out[name] = raw[:, j]
+    finally:
+        if regs:
+            L.free(C.cast(regs, C.c_void_p))
+        L.vo_lz_free_index(ix)
+    return out
 
 
 def path_rows(codes, offsets, k=25, min_kmers=20, min_ident=0.7, lz=None, threads=None):

@@ -4,6 +4,7 @@ bench-sized set (BASELINE.json configs[1])."""
 import numpy as np
 import pytest
 
+import lz_checks as lc
 import oracle_lib as orc
 from vclust_amd import api, synth
 
@@ -19,14 +20,13 @@ def _check_prefilter(codes, offsets, gs, k, fraction=1.0):
 
 
 def _check_lz(codes, offsets, gs, tasks, lz=None):
+    """rows of the rows-only call, then rows and regions of the one-parse call: every task against orc.lz_pair_stat and
+    orc.lz_regions (lz_checks.assert_rows_and_regions)"""
     stats = gs.lz_align(tasks, lz=lz)
-    bad = []
-    for t, s in zip(tasks, stats):
-        q, r = int(t['q']), int(t['r'])
-        ref = orc.lz_pair_stat(codes[offsets[q]:offsets[q + 1]], codes[offsets[r]:offsets[r + 1]], lz=lz)
-        if ref != (int(s['n_match']), int(s['aln_len']), int(s['n_regions'])):
-            bad.append((q, r, ref, tuple(int(x) for x in s)))
-    assert not bad, bad[:5]
+    cache = {}
+    lc.assert_rows_and_regions(orc, codes, offsets, tasks, stats, None, lz=lz, cache=cache, what='rows only')
+    stats2, regions = gs.lz_align(tasks, lz=lz, want_regions=True)
+    lc.assert_rows_and_regions(orc, codes, offsets, tasks, stats2, regions, lz=lz, cache=cache, what='rows and regions')
 
 
 def _sprinkle_n(codes, rng, n_runs):

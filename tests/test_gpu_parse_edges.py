@@ -7,7 +7,9 @@ branch-free window rule ((aw, am) = (15, 7)).
   * windows holding exactly am and am + 1 mismatches, straddling a 32-base chunk boundary;
   * buckets whose candidates all need verification (tandem repeats: one msl-mer, many entries with the query's tag).
 Every ordered pair of the set is parsed in separate processes (developer switches are read once per process): the
-one-wave FAST kernel, the four-wave one, the one that also writes regions, and the general kernel."""
+one-wave FAST kernel, the four-wave one, the one that also writes regions, the general kernel and the general kernel
+that writes regions.  The region-writing variants hand their regions back: every task's regions equal orc.lz_regions as
+an ordered list (lz_checks.assert_rows_and_regions)."""
 import os
 import pathlib
 import subprocess
@@ -16,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+import lz_checks as lc
 import oracle_lib as orc
 
 pytestmark = pytest.mark.gpu
@@ -93,7 +96,9 @@ if sys.argv[3] == 'regions':
     stats, regions = gs.lz_align(tasks, want_regions=True)
 else:
     stats = gs.lz_align(tasks)
-np.savez(sys.argv[2], tasks=tasks, stats=stats)
+    np.savez(sys.argv[2], tasks=tasks, stats=stats)
+if sys.argv[3] == 'regions':
+    np.savez(sys.argv[2], tasks=tasks, stats=stats, regions=regions)
 """ % str(ROOT)
 
 
@@ -104,12 +109,10 @@ def edge_set(tmp_path_factory):
     f = d / 'set.npz'
     np.savez(f, codes=codes, offsets=offsets)
     n = len(offsets) - 1
-    ref = {}
-    for q in range(n):
-        for r in range(n):
-            if q != r:
-                ref[(q, r)] = orc.lz_pair_stat(codes[offsets[q]:offsets[q + 1]], codes[offsets[r]:offsets[r + 1]])
-    return f, ref
+    tasks = np.array([(q, r) for q in range(n) for r in range(n) if q != r], dtype=[('q', '<u4'), ('r', '<u4')])
+    cache = lc.oracle_of(orc, codes, offsets, tasks)              # (q, r) -> (row, regions)
+    ref = {k: v[0] for k, v in cache.items()}
+    return f, ref, (codes, offsets, cache)
 
 
 @pytest.mark.parametrize('variant,env,mode', [
@@ -117,9 +120,10 @@ def edge_set(tmp_path_factory):
     ('fast_segments', dict(VG_LZ_SEGMENTS='4'), 'stats'),
     ('fast_regions', {}, 'regions'),
     ('general', dict(VG_LZ_KERNEL='general', VG_LZ_SEGMENTS='1'), 'stats'),
+    ('general_regions', dict(VG_LZ_KERNEL='general'), 'regions'),
 ])
 def test_edge_pairs_match_the_oracle(edge_set, tmp_path, variant, env, mode):
-    f, ref = edge_set
+    f, ref, (codes, offsets, cache) = edge_set
     out = tmp_path / f'{variant}.npz'
     p = subprocess.run([sys.executable, '-c', RUN, str(f), str(out), mode], env=dict(os.environ, VG_DEV_SWITCHES='1', **env),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -131,5 +135,7 @@ def test_edge_pairs_match_the_oracle(edge_set, tmp_path, variant, env, mode):
         if got != ref[(int(t['q']), int(t['r']))]:
             bad.append((int(t['q']), int(t['r']), ref[(int(t['q']), int(t['r']))], got))
     assert not bad, (len(bad), bad[:5])
+    if mode == 'regions':
+        lc.assert_rows_and_regions(orc, codes, offsets, d['tasks'], d['stats'], d['regions'], cache=cache, what=variant)
     # the set does reach long extensions: some rows cover more than two rounds of 2 048
     assert int(d['stats']['n_match'].max()) > 4096

@@ -155,6 +155,42 @@ def test_identical_and_shuffled_genome(example):
     assert orc.lz_pair_stat(b, a) == (45636, 45636, 3)       # example/output/ani.tsv:78-79
 
 
+def _regions_hold_the_row(q, r, lz=None):
+    regs = orc.lz_regions(q, r, lz)
+    row = orc.lz_pair_stat(q, r, lz)
+    span = regs['qend'].astype(np.int64) - regs['qstart'] + 1
+    assert (int(regs['n_match'].sum()), int(span.sum()), len(regs)) == row
+    assert np.all(regs['qstart'] >= 0) and np.all(regs['qend'] < len(q)) and np.all(span >= 1)
+    assert np.all(regs['n_match'] >= 0) and np.all(regs['n_match'] <= span)
+    assert np.all(regs['qstart'][1:] > regs['qend'][:-1])        # query order, no overlap
+    assert np.all(regs['rstart'] >= 0) and np.all(regs['rstart'] <= 2 * len(r)) and np.all(regs['rstart'] != len(r))
+    return regs
+
+
+def test_lz_regions_add_up_to_the_rows(example):
+    """orc.lz_regions (what the GPU's regions are held to) against orc.lz_pair_stat: on every ordered pair of the golden
+    example that shares an alignment family, and on an N-carrying synthetic pair."""
+    codes, offsets, names = example
+    n_regions = 0
+    for q in range(len(names)):
+        for r in range(len(names)):
+            if q != r and names[q].split('.')[0] == names[r].split('.')[0]:
+                n_regions += len(_regions_hold_the_row(codes[offsets[q]:offsets[q + 1]], codes[offsets[r]:offsets[r + 1]]))
+    assert n_regions > 100
+    rng = np.random.default_rng(7)
+    ref = rng.integers(0, 4, 20000).astype(np.uint8)
+    qry = ref.copy()
+    at = np.flatnonzero(rng.random(len(ref)) < 0.05)
+    qry[at] = (qry[at] + 1) % 4
+    qry = np.concatenate([qry[:12000], (3 - ref[12000:18000])[::-1]])
+    ref[:5] = 4; ref[10000:10007] = 4; ref[-10:] = 4
+    qry[3000:3004] = 4
+    regs = _regions_hold_the_row(qry, ref)
+    assert len(regs) >= 2 and int(regs["rstart"].min()) < len(ref) < int(regs["rstart"].max())       # both strands are hit
+    regs = _regions_hold_the_row(qry, ref, dict(mal=14, msl=7, mrd=60, mqd=70, reg=50, aw=25, am=12, ar=4))
+    assert len(regs) >= 2
+
+
 def test_edge_inputs():
     rng = np.random.default_rng(0)
     a = rng.integers(0, 4, size=500, dtype=np.uint8)

@@ -103,6 +103,14 @@ for case in range(n_cases):
         ok = ok and bool(np.all(tk[1:] >= tk[:-1]) or True) and bool(np.all(rg['qstart'][1:][same] > rg['qend'][:-1][same]))
     if not ok:
         bad += 1; print('REGIONS MISMATCH case', case, 'seed', seed0 + case, lz, fit, flush=True)
+    # ... and equal the oracle's, task by task, as ordered lists of (qstart, qend, rstart, rend, n_match)
+    order = np.argsort(rg['task'], kind='stable'); rs = rg[order]; first = np.searchsorted(rs['task'], np.arange(len(tasks) + 1))
+    for i, t in enumerate(tasks):
+        q, r = int(t['q']), int(t['r'])
+        want = orc.lz_regions(codes[offsets[q]:offsets[q + 1]], codes[offsets[r]:offsets[r + 1]], lz=lz)
+        mine = rs[first[i]:first[i + 1]]
+        if len(mine) != len(want) or any(not np.array_equal(mine[f], want[f]) for f in want.dtype.names):
+            bad += 1; print('REGION LIST MISMATCH case', case, 'seed', seed0 + case, (q, r), lz, fit, flush=True); break
     for t, s in zip(tasks, stats):
         q, r = int(t['q']), int(t['r'])
         ref = orc.lz_pair_stat(codes[offsets[q]:offsets[q + 1]], codes[offsets[r]:offsets[r + 1]], lz=lz)

@@ -124,6 +124,8 @@ SYMBOLS = {
     'vg_read_filter': (C.c_int, [C.c_void_p, C.c_char_p, C.c_double, P(P(PairCount)), P(C.c_int64)]),
     'vg_align_tasks': (C.c_int, [C.c_void_p, P(PairCount), C.c_int64, P(P(Task)), P(C.c_int64)]),
     'vg_lz_prepare': (C.c_int, [C.c_void_p, P(PairCount), C.c_int64, P(LzParams)]),
+    'vg_lz_index_dump': (C.c_int, [C.c_void_p, C.c_int, P(LzParams), P(P(C.c_uint32)), P(P(C.c_uint32)), P(C.c_int64),
+                                   P(C.c_int), P(C.c_int), P(C.c_int)]),
     'vg_set_index_budget': (None, [C.c_int64]),
     'vg_set_subshards': (None, [C.c_int]),
     'vg_set_range_scan': (None, [C.c_int]),

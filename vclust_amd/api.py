@@ -206,6 +206,18 @@ class GenomeSet:
             return stats, _take(rp, nr.value, REGION_DTYPE)
         return stats
 
+    def lz_index_dump(self, idx, lz=None):
+        """The index lz_align would build for genome idx (parity tests) -> dict(bucket_end uint32[4^msl], entries uint32[n],
+        pos_bits, tag_bits, path: 0..5 register build of 24..4 trips, 6 mid, 7 lds, 8 global)."""
+        prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+        tb, en = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        n, pb, tg, path = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
+        check(self._lib.vg_lz_index_dump(self._h, int(idx), C.byref(prm), C.byref(tb), C.byref(en), C.byref(n),
+                                         C.byref(pb), C.byref(tg), C.byref(path)))
+        u4 = np.dtype('<u4')
+        return dict(bucket_end=_take(tb, 1 << (2 * prm.msl), u4), entries=_take(en, n.value, u4),
+                    pos_bits=pb.value, tag_bits=tg.value, path=path.value)
+
     def write_ani(self, out_path, tasks, stats, regions=None, columns=None, out_aln=None, lz=None,
                   out_filters=None):
         tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)

@@ -2067,6 +2067,43 @@ extern "C" int vg_lz_prepare(vg_genomes* g, const vg_pair_count* pairs, int64_t 
     VG_API_END
 }
 
+// Parity tests: the index vg_lz_align would build for genome `idx` under p, planned and built by the product's own
+// lz_plan_references + lz_build_batch as a one-reference call (a plan of its own: g_prepared / g_plan_cache are not touched).
+extern "C" int vg_lz_index_dump(vg_genomes* g, int idx, const vg_lz_params* p, uint32_t** bucket_end, uint32_t** entries,
+                                int64_t* n_entries, int* pos_bits, int* tag_bits, int* path) {
+    VG_API_BEGIN
+    if (!g || !p || !bucket_end || !entries || !n_entries || !pos_bits || !tag_bits || !path) throw vg_error(VG_EINVAL, "vg_lz_index_dump: null argument");
+    *bucket_end = nullptr; *entries = nullptr; *n_entries = 0;
+    if (p->mal < 8 || p->mal > 31 || p->msl < 4 || p->msl > 12 || p->msl > p->mal) throw vg_error(VG_EINVAL, "mal must be 8..31, msl 4..12 and <= mal");
+    vg_require_device();
+    int rc = vg_genomes_to_device(g); if (rc) return rc;
+    if (idx < 0 || idx >= g->n) throw vg_error(VG_EINVAL, "genome id out of range");
+    if (g->len[idx] > (1 << 29)) throw vg_error(VG_EOVERFLOW, "genome longer than 2^29 bases");
+    hipStream_t s = vg_stream();
+    lz_plan plan;
+    plan.g = g; plan.ref_ids.assign(1, (uint32_t)idx);
+    lz_plan_references(g, p, plan);
+    lz_build_batch(g, p, plan, 0, s);
+    const lz_batch& B = plan.batches.at(0);
+    const ref_desc& rd = plan.all_refs.at(0);
+    const size_t stab_n = (size_t)1 << (2 * p->msl);
+    std::vector<uint32_t> tab(stab_n);
+    plan.slot.stab_pool.download(tab.data(), stab_n, s);
+    VG_HIP(hipStreamSynchronize(s));
+    VG_HIP(hipGetLastError());
+    const int64_t n = (int64_t)tab[stab_n - 1];               // the table holds the END of each bucket
+    if (n > (int64_t)rd.n_rr) throw vg_error(VG_EHIP, "internal error: the bucket table ends behind the reference's entry pool");
+    uint32_t* tb = (uint32_t*)malloc(sizeof(uint32_t) * stab_n);
+    uint32_t* en = (uint32_t*)malloc(sizeof(uint32_t) * std::max<size_t>(1, (size_t)n));
+    if (!tb || !en) { free(tb); free(en); throw vg_error(VG_ENOMEM, "out of host memory"); }
+    memcpy(tb, tab.data(), sizeof(uint32_t) * stab_n);
+    if (n) { vg_download_bytes(en, plan.slot.sent_pool.p + rd.sent, (size_t)n * sizeof(uint32_t), s); (void)hipStreamSynchronize(s); }
+    *bucket_end = tb; *entries = en; *n_entries = n; *pos_bits = rd.pos_bits; *tag_bits = rd.tag_bits;
+    if (!B.reg_list.empty()) { int c = 0; while (c < 5 && B.reg_class_end[c] == 0) ++c; *path = c; }
+    else *path = !B.mid_list.empty() ? 6 : !B.small_list.empty() ? 7 : 8;
+    VG_API_END
+}
+
 extern "C" void vg_set_index_budget(int64_t bytes) { if (bytes > (64 << 20)) { g_index_budget_bytes = bytes; g_index_budget_set = true; } }
 
 // (see vg_warm_prefilter)
