@@ -342,6 +342,20 @@ int vg_deduplicate(const char* const* paths, int n_paths, const char* const* pre
  * stats may be NULL. */
 int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
                   vg_dedup_stats* stats);
+/* Circular mode: with circular != 0, two records of the same length are also duplicates when one
+ * is a rotation of the other or of the other's reverse complement, rot(X, s)[i] = X[(i + s) mod L].  strand is then 0 when
+ * the record equals some rotation of its representative, 1 when it equals only rotations of the representative's reverse
+ * complement; offset is the smallest s with record == rot(Y, s), Y the representative (strand 0) or its reverse complement
+ * (strand 1).  The duplicates file gains a fourth column: `representative<TAB>duplicate<TAB>strand<TAB>offset`. */
+typedef struct {
+    int circular;               /* 0 = equal or reverse complement only; != 0 = up to rotation as well */
+} vg_dedup_options;
+/* vg_deduplicate / vg_dedup_seqs with options.  options == NULL or circular == 0: exactly the calls above (three-column
+ * duplicates file), and offset (may then be NULL) is filled with 0.  In circular mode offset[n] is required. */
+int vg_deduplicate_ex(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                      const char* dup_path, const vg_dedup_params* p, const vg_dedup_options* options);
+int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64_t n, const vg_dedup_options* options,
+                     int32_t* representative, int8_t* strand, int64_t* offset, vg_dedup_stats* stats);
 /* test knob: keep only the low `bits` (0..128) bits of the sequence hash (forces collisions); 128 = the default */
 void vg_dedup_set_hash_bits(int bits);
 

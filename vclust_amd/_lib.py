@@ -81,6 +81,10 @@ class DedupStats(C.Structure):
                 ('rounds', C.c_int64), ('collisions', C.c_int64)]
 
 
+class DedupOptions(C.Structure):
+    _fields_ = [('circular', C.c_int)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('total_ms', C.c_double), ('launches', C.c_int64),
                 ('bytes', C.c_double)]
@@ -154,6 +158,9 @@ SYMBOLS = {
                                    P(C.c_int32), P(C.c_int32), P(ClusterStats)]),
     'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),
+    'vg_deduplicate_ex': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams), P(DedupOptions)]),
+    'vg_dedup_seqs_ex': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(DedupOptions), P(C.c_int32), P(C.c_int8), P(C.c_int64),
+                                   P(DedupStats)]),
     'vg_dedup_set_hash_bits': (None, [C.c_int]),
     'vg_synth_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_double, C.c_double, C.c_int,
                                 C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int64)]),

@@ -266,10 +266,13 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
 
 
-def deduplicate(seqs):
+def deduplicate(seqs, circular=False):
     """Group the sequences `seqs` (str or bytes each; white space is skipped, case ignored) by equality up to reverse
     complement (vg_dedup_seqs).  -> (representative int32[n], strand int8[n], stats dict): representative[i] is the index of
-    the earliest sequence of i's group, strand[i] is 1 when i equals only that sequence's reverse complement, else 0."""
+    the earliest sequence of i's group, strand[i] is 1 when i equals only that sequence's reverse complement, else 0.
+    circular=True (vg_dedup_seqs_ex): rotations of a sequence and of its reverse complement are equal too; strand[i] is 1
+    when i equals only rotations of the reverse complement, and the result is (representative, strand, offset int64[n],
+    stats) with offset[i] the smallest s for which i == rot(representative or its reverse complement, s)."""
     bufs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
     n = len(bufs)
     offsets = np.zeros(n + 1, dtype=np.int64)
@@ -280,6 +283,12 @@ def deduplicate(seqs):
     strand = np.zeros(max(n, 1), dtype=np.int8)
     st = DedupStats()
     P = C.POINTER
+    if circular:
+        off = np.zeros(max(n, 1), dtype=np.int64)
+        opt = _lib.DedupOptions(circular=1)
+        check(_lib.load().vg_dedup_seqs_ex(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, C.byref(opt), rep.ctypes.data_as(P(C.c_int32)),
+                                           strand.ctypes.data_as(P(C.c_int8)), off.ctypes.data_as(P(C.c_int64)), C.byref(st)))
+        return rep[:n], strand[:n], off[:n], {k: getattr(st, k) for k, _ in DedupStats._fields_}
     check(_lib.load().vg_dedup_seqs(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, rep.ctypes.data_as(P(C.c_int32)),
                                     strand.ctypes.data_as(P(C.c_int8)), C.byref(st)))
     return rep[:n], strand[:n], {k: getattr(st, k) for k, _ in DedupStats._fields_}

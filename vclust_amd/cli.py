@@ -108,6 +108,8 @@ def get_parser() -> argparse.ArgumentParser:
                     help='Add prefixes to sequence IDs [%(default)s]')
     dd.add_argument('--gzip-output', action='store_true', help='Compress the output FASTA file with gzip')
     dd.add_argument('--gzip-level', metavar='<int>', type=int, default=4, help='Compression level (1-9) [%(default)s]')
+    dd.add_argument('--circular', action='store_true',
+                    help='Circular genomes: rotations of a sequence and of its reverse complement are duplicates too')
     common(dd)
 
     # prefilter
@@ -402,15 +404,19 @@ def deduplicate_call(args):
 
 
 def handle_deduplicate(args, parser, logger):
-    if not BIN_MFASTA.exists():
-        # no mfasta-tool: the GPU (vg_deduplicate)
+    circular = getattr(args, 'circular', False)
+    if circular or not BIN_MFASTA.exists():
+        # no mfasta-tool, or --circular (which mfasta-tool does not have): the GPU (vg_deduplicate)
         args = validate_args_deduplicate(args, parser)
         from . import stages
         call = deduplicate_call(args)
         desc = (f'libvclust_gpu deduplicate -i {" ".join(str(f) for f in args.input_path)}'
                 + (f' --add-prefixes {" ".join(args.add_prefixes)}' if args.add_prefixes else '')
                 + (f' --gzip-level {args.gzip_level}' if args.gzip_output else '')
+                + (' --circular' if circular else '')
                 + f' [1 GPU] -> {args.output_path}, {args.output_duplicates_path}')
+        if circular:
+            call['circular'] = True
         run_native(desc, lambda: stages.deduplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
         return
     _require_binary(BIN_MFASTA)

@@ -13,6 +13,15 @@
 //             candidate head, every other member is compared in full with it (one wave per (member, chunk)) in the
 //             orientation the two bits imply; members that differ (hash collisions) stay for the next round
 //   labels    representative (int32) and strand (int8) per record, the only arrays that come back
+// Circular mode (vg_dedup_options.circular): duplicates up to rotation and strand.
+//   chash     one wave per (record, chunk): every cyclic window of 16 symbols is one 64-bit value, its reverse complement the
+//             bit reversal of it; mixed terms of min(window, reverse complement) are summed, so the 128-bit sum depends
+//             neither on where the circle was opened nor on the strand
+//   ccand     per (member, chunk): the positions of the head's strands whose window equals the member's first window are
+//             the candidate offsets (ballots, a per-member counter, a list that grows when it overflows), sorted per member
+//   cverify   per (member, candidate, chunk): the member against the head rotated by the candidate (v_alignbit_b32 re-frames
+//             by offset mod 8, the word index wraps); candidates are tried in increasing order, in batches of 1, 2, 4, ...
+//             per member, and the smallest equal one is the answer
 #include "vg_common.h"
 #include <rocprim/rocprim.hpp>
 #include <zlib.h>
@@ -307,6 +316,220 @@ __global__ void k_compact(const int32_t* A, int64_t na, const int32_t* keep, con
         if (keep[p]) out[at[p]] = A[p];
 }
 
+// ---------------------------------------------------------------- device: circular mode
+__device__ __forceinline__ uint32_t sym_at(const uint32_t* R, int64_t pos) { return (R[pos >> 3] >> (4 * (int)(pos & 7))) & 15u; }
+// n (<= 16) cyclic symbols of a record of L >= 1 symbols starting at b < L, one by one (the wrap point and short records)
+__device__ __forceinline__ uint64_t gather(const uint32_t* R, int64_t L, int64_t b, int n) {
+    uint64_t w = 0;
+    for (int j = 0; j < n; ++j) { w |= (uint64_t)sym_at(R, b) << (4 * j); if (++b == L) b = 0; }
+    return w;
+}
+// word k >= q of the record continued behind its end by its own start (q = L / 8, r = L % 8, L >= 16)
+__device__ __forceinline__ uint32_t ext_word(const uint32_t* R, int64_t q, int r, int64_t k) {
+    const int64_t m = k - q;
+    if (r == 0) return R[m];
+    if (m == 0) return R[q] | (R[0] << (4 * r));
+    return __builtin_amdgcn_alignbit(R[m], R[m - 1], (uint32_t)(32 - 4 * r));
+}
+// f(valid, i, window) for every start i of chunk c of a record of L >= 1 symbols, window = the 16 cyclic symbols from i (the
+// first in the low bits).  Every lane makes the same calls (f may hold ballots); valid says whether i < L.  A lane takes
+// the 32 starts of its 16-byte load and needs the two words behind it; behind the record's end these are its first words,
+// re-framed by L % 8.  Below 16 symbols a window wraps more than once: lane i gathers window i.
+template <class F>
+__device__ __forceinline__ void for_windows(const uint32_t* R, int64_t L, int64_t c, int lane, F&& f) {
+    if (L < 16) {
+        const bool valid = lane < L;
+        f(valid, (int64_t)lane, valid ? gather(R, L, lane, 16) : 0ull);
+        return;
+    }
+    const int64_t nw = (L + 7) >> 3, q = L >> 3;
+    const int r = (int)(L & 7);
+    for (int64_t base = c * HASH_CHUNK, j1 = min(nw, (c + 1) * HASH_CHUNK); base < j1; base += 256) {
+        const int64_t j = base + 4 * lane;
+        uint32_t x[6] = { 0u, 0u, 0u, 0u, 0u, 0u };
+        if (j < nw) {
+            const uint4 v = *(const uint4*)(R + j);
+            const uint32_t own[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+                const int64_t k = j + u;
+                x[u] = k < q ? (u < 4 ? own[u & 3] : R[k]) : k <= nw + 1 ? ext_word(R, q, r, k) : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const int64_t i = 8 * (j + u) + t;
+                const uint32_t lo = __builtin_amdgcn_alignbit(x[u + 1], x[u], (uint32_t)(4 * t));
+                const uint32_t hi = __builtin_amdgcn_alignbit(x[u + 2], x[u + 1], (uint32_t)(4 * t));
+                f(i < L, i, (uint64_t)lo | ((uint64_t)hi << 32));
+            }
+    }
+}
+// the reverse complement of a window of 16 symbols
+__device__ __forceinline__ uint64_t rc_window(uint64_t w) { return __builtin_bitreverse64(w); }
+
+// h[2 i], h[2 i + 1]: the sums of the two mixes of min(window, reverse complement) over all cyclic windows of record i
+__global__ void __launch_bounds__(TPB) k_chash(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                               const int64_t* __restrict__ cbeg, int64_t n, int64_t n_tasks, unsigned long long* h) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t i = owner_of(cbeg, n, t), c = t - cbeg[i];
+        const int64_t L = len[i];
+        if (L == 0) continue;
+        uint64_t lo = 0, hi = 0;
+        for_windows(W + woff[i], L, c, lane, [&](bool valid, int64_t, uint64_t w) {
+            const uint64_t rc = rc_window(w);
+            const uint64_t a = fmix64((w < rc ? w : rc) ^ 0x9e3779b97f4a7c15ull);
+            lo += valid ? a : 0ull;
+            hi += valid ? (a ^ (a >> 29)) * 0xbf58476d1ce4e5b9ull : 0ull;
+        });
+        lo = wave_sum64(lo); hi = wave_sum64(hi);
+        if (lane == 0) { atomicAdd(h + 2 * i, (unsigned long long)lo); atomicAdd(h + 2 * i + 1, (unsigned long long)hi); }
+    }
+}
+// key of record i: (length, the sum cut to its low `bits` bits); no orientation
+__global__ void k_ckeys(const unsigned long long* h, const int64_t* len, int64_t n, int bits, uint64_t* klo, uint64_t* khi,
+                        uint64_t* klen, int32_t* idx) {
+    const uint64_t mlo = bits >= 64 ? ~0ull : (1ull << bits) - 1, mhi = bits >= 128 ? ~0ull : bits <= 64 ? 0ull : (1ull << (bits - 64)) - 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        klo[i] = h[2 * i] & mlo; khi[i] = h[2 * i + 1] & mhi; klen[i] = (uint64_t)len[i]; idx[i] = (int32_t)i;
+    }
+}
+static_assert(HASH_CHUNK == VERIFY_CHUNK, "the candidate pass cuts a record as for_windows does");
+__device__ __forceinline__ int64_t chunks_of(int64_t L) { return max((int64_t)1, (((L + 7) >> 3) + VERIFY_CHUNK - 1) / VERIFY_CHUNK); }
+constexpr unsigned long long NO_OFFSET = ~0ull;
+// candidate tasks per position: the chunks of a member (one for an empty record), 0 for a head; res[p] = no offset yet
+__global__ void k_ctasks(const int32_t* A, int64_t na, const int64_t* hp, const int64_t* len, int64_t* cnt, unsigned long long* res) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= na; p += (int64_t)gridDim.x * blockDim.x) {
+        if (p == na) { cnt[p] = 0; continue; }
+        cnt[p] = hp[p] == p ? 0 : chunks_of(len[A[p]]);
+        res[p] = NO_OFFSET;
+    }
+}
+// One wave per (member, chunk of the head).  removed == rot(Y, s) needs Y's window at s to equal the member's window at 0.
+// Y = head: s = u for every u whose window equals it.  Y = revcomp(head): Y's window at s is the reverse complement of the
+// head's window at (L - 16 - s) mod L, so s = (L - 16 - u) mod L for every u whose window equals the reverse complement of
+// the member's.  Code of a candidate: strand << sbits | s.  Slots are handed out by a global counter; what lies past `cap` is
+// counted and not written (the caller grows the list and repeats).
+__global__ void __launch_bounds__(TPB) k_ccand(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                               const int32_t* __restrict__ A, int64_t na, const int64_t* __restrict__ hp,
+                                               const int64_t* __restrict__ tbeg, int64_t n_tasks, int sbits, unsigned long long cap,
+                                               uint64_t* cand_p, uint64_t* cand_code, unsigned long long* ccnt, unsigned long long* total) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t below = (1ull << lane) - 1;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t p = owner_of(tbeg, na, t), c = t - tbeg[p];
+        const int32_t m = A[p], hd = A[hp[p]];
+        const int64_t L = len[m];
+        const uint32_t* M = W + woff[m];
+        if (L == 0) {          // (all empty records are equal: offset 0 on the forward strand)
+            if (lane == 0) {
+                const unsigned long long at = atomicAdd(total, 1ull);
+                atomicAdd(ccnt + p, 1ull);
+                if (at < cap) { cand_p[at] = (uint64_t)p; cand_code[at] = 0; }
+            }
+            continue;
+        }
+        const uint64_t m0 = L < 16 ? gather(M, L, 0, 16) : ((uint64_t)M[0] | ((uint64_t)M[1] << 32)), r0 = rc_window(m0);
+        for_windows(W + woff[hd], L, c, lane, [&](bool valid, int64_t u, uint64_t w) {
+            const bool mf = valid && w == m0, mr = valid && w == r0;
+            const uint64_t bf = __ballot(mf), br = __ballot(mr);
+            if (bf | br) {
+                const unsigned long long nf = (unsigned long long)__popcll(bf), nr = (unsigned long long)__popcll(br);
+                unsigned long long at = 0;
+                if (lane == 0) { at = atomicAdd(total, nf + nr); atomicAdd(ccnt + p, nf + nr); }
+                at = __shfl(at, 0);
+                if (mf) {
+                    const unsigned long long slot = at + (unsigned long long)__popcll(bf & below);
+                    if (slot < cap) { cand_p[slot] = (uint64_t)p; cand_code[slot] = (uint64_t)u; }
+                }
+                if (mr) {
+                    const unsigned long long slot = at + nf + (unsigned long long)__popcll(br & below);
+                    const int64_t s = (L - (16 + u) % L) % L;
+                    if (slot < cap) { cand_p[slot] = (uint64_t)p; cand_code[slot] = (1ull << sbits) | (uint64_t)s; }
+                }
+            }
+        });
+    }
+}
+// compare tasks of a batch per position: (the member's candidates of rank lo .. hi - 1) x chunks; none for heads and for
+// members that have their offset
+__global__ void k_cbatch(const int32_t* A, int64_t na, const int64_t* hp, const int64_t* len, const unsigned long long* res,
+                         const int64_t* ccnt, int64_t lo, int64_t hi, int64_t* cnt) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= na; p += (int64_t)gridDim.x * blockDim.x) {
+        if (p == na) { cnt[p] = 0; continue; }
+        const bool open = hp[p] != p && res[p] == NO_OFFSET;
+        cnt[p] = open ? max((int64_t)0, min(ccnt[p], hi) - lo) * chunks_of(len[A[p]]) : 0;
+    }
+}
+// 8 cyclic symbols of a record from b < L: one re-framed pair of words, or symbol by symbol across the wrap point
+__device__ __forceinline__ uint32_t cyc8(const uint32_t* R, int64_t L, int64_t b) {
+    if (b + 8 <= L) { const int64_t w = b >> 3; return __builtin_amdgcn_alignbit(R[w + 1], R[w], (uint32_t)(4 * (b & 7))); }
+    return (uint32_t)gather(R, L, b, 8);
+}
+// One wave per (member, candidate, chunk): member word k against the 8 symbols of Y from (8 k + s) mod L; for
+// Y = revcomp(head) these are the bit reversal of the head's 8 symbols from (L - 8 - pos) mod L.  A mismatch sets the
+// candidate's flag; a set flag ends the other chunks of that candidate early.
+__global__ void __launch_bounds__(TPB) k_ccompare(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                                  const int32_t* __restrict__ A, int64_t na, const int64_t* __restrict__ hp,
+                                                  const int64_t* __restrict__ tbeg, int64_t n_tasks, const int64_t* __restrict__ cbeg, int64_t lo,
+                                                  const uint64_t* __restrict__ cand_code, int sbits, uint8_t* bad) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t p = owner_of(tbeg, na, t), local = t - tbeg[p];
+        const int32_t m = A[p], hd = A[hp[p]];
+        const int64_t L = len[m], nw = (L + 7) >> 3, nch = chunks_of(L);
+        const int64_t g = cbeg[p] + lo + local / nch, c = local % nch;
+        if (bad[g]) continue;
+        const uint64_t code = cand_code[g];
+        const bool rcs = (code >> sbits) != 0;
+        const int64_t s = (int64_t)(code & ((1ull << sbits) - 1));
+        const uint32_t* M = W + woff[m]; const uint32_t* H = W + woff[hd];
+        bool diff = false;
+        for (int64_t base = c * VERIFY_CHUNK, k1 = min(nw, (c + 1) * VERIFY_CHUNK); base < k1; base += 64) {
+            const int64_t k = base + lane;
+            if (k < k1) {
+                int64_t pos = 8 * k + s; if (pos >= L) pos -= L;
+                uint32_t y;
+                if (rcs) { int64_t b = (L - 8 - pos) % L; if (b < 0) b += L; y = __builtin_bitreverse32(cyc8(H, L, b)); }
+                else y = cyc8(H, L, pos);
+                const int64_t nv = min((int64_t)8, L - 8 * k);
+                const uint32_t mask = nv == 8 ? ~0u : (1u << (4 * nv)) - 1;
+                diff = ((M[k] ^ y) & mask) != 0;
+            }
+            if (__ballot(diff)) break;
+        }
+        if (__ballot(diff) && lane == 0) bad[g] = 1;
+    }
+}
+// the smallest candidate of the batch without a mismatch is the member's (strand, offset)
+__global__ void k_cpick(const int32_t* A, int64_t na, const int64_t* len, const int64_t* tbeg, int64_t n_tasks, const int64_t* cbeg, int64_t lo,
+                        const uint64_t* cand_code, const uint8_t* bad, unsigned long long* res) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tasks; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = owner_of(tbeg, na, t), local = t - tbeg[p], nch = chunks_of(len[A[p]]);
+        if (local % nch) continue;
+        const int64_t g = cbeg[p] + lo + local / nch;
+        if (!bad[g]) atomicMin(res + p, (unsigned long long)cand_code[g]);
+    }
+}
+// heads keep themselves, members with an offset join their head, the others stay (keep[p] = 1)
+__global__ void k_cresolve(const int32_t* A, int64_t na, const int64_t* hp, const unsigned long long* res, int sbits,
+                           int32_t* rep, int8_t* strand, int64_t* off, int32_t* keep, unsigned long long* n_diff) {
+    int c = 0;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < na; p += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t i = A[p];
+        int32_t k = 0;
+        if (hp[p] == p) { rep[i] = i; strand[i] = 0; off[i] = 0; }
+        else if (res[p] != NO_OFFSET) { rep[i] = A[hp[p]]; strand[i] = (int8_t)(res[p] >> sbits); off[i] = (int64_t)(res[p] & ((1ull << sbits) - 1)); }
+        else { k = 1; ++c; }
+        keep[p] = k;
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_diff, (unsigned long long)c);
+}
+
 int grid_of(int64_t n, int per_block = TPB, int cap = 16384) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, cap));
 }
@@ -329,10 +552,79 @@ void scan(const T* in, T* out, int64_t n, bool inclusive, Op op, hipStream_t s) 
     else VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, in, out, (T)0, (size_t)n, op, s));
 }
 
-// the device part: packed records (resident) -> representative / strand on the host
-void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, vg_dedup_stats& st) {
+// the three stable passes over the keys (low hash half, high half, length): equal keys end up adjacent, in index order
+void sort_by_key(dbuf<uint64_t>& klo, dbuf<uint64_t>& khi, dbuf<uint64_t>& klen, dbuf<int32_t>& A, dbuf<int32_t>& A2, int64_t n, int bits,
+                 unsigned len_bits, hipStream_t s) {
+    vg_prof_scope ps_("dedup_sort", (double)n * 48.0);
+    dbuf<uint64_t> kg((size_t)n), ks((size_t)n);
+    const unsigned pass_bits[3] = { (unsigned)std::min(bits, 64), (unsigned)std::max(bits - 64, 0), len_bits };
+    const uint64_t* src[3] = { klo.p, khi.p, klen.p };
+    for (int pass = 0; pass < 3; ++pass) {
+        if (!pass_bits[pass]) continue;
+        hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, src[pass], A.p, n, kg.p);
+        sort_pairs(kg, ks, A, A2, n, pass_bits[pass], s);
+    }
+}
+
+// the candidate offsets of every member of a round, sorted by (position, strand, offset), and their flags
+struct cand_list {
+    dbuf<uint64_t> pos, code, pos2, code2;
+    dbuf<uint8_t> bad;
+    dbuf<int64_t> cnt, beg;                  // per position (na + 1): the member's candidates and where they start
+    dbuf<unsigned long long> total;
+};
+
+// One round of the circular verification: res[p] = strand << sbits | offset of every member equal to its head in some
+// rotation of one of the head's strands, NO_OFFSET for the others.
+void circular_round(const packed_set& ps, const int64_t* d_woff, const int64_t* d_len, const int32_t* A, int64_t na, const int64_t* hp,
+                    dbuf<int64_t>& cnt, dbuf<int64_t>& tbeg, cand_list& cl, int sbits, unsigned long long* res, hipStream_t s) {
+    int64_t n_ct = 0;
+    unsigned long long n_cand = 0;
+    {
+        vg_prof_scope ps_("dedup_ccand", (double)na * 16.0);
+        hipLaunchKernelGGL(k_ctasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A, na, hp, d_len, cnt.p, res);
+        scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+        vg_download_bytes(&n_ct, tbeg.p + na, sizeof n_ct, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (n_ct == 0) return;               // (heads only)
+        for (size_t cap = std::max(cl.pos.n, (size_t)(4 * na + 1024));; cap = (size_t)n_cand) {
+            if (cl.pos.n < cap) { cl.pos.alloc(cap); cl.code.alloc(cap); cl.pos2.alloc(cap); cl.code2.alloc(cap); cl.bad.alloc(cap); }
+            VG_HIP(hipMemsetAsync(cl.cnt.p, 0, (size_t)(na + 1) * sizeof(int64_t), s));
+            cl.total.zero(s);
+            hipLaunchKernelGGL(k_ccand, dim3(grid_of(n_ct, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff, d_len, A, na, hp, tbeg.p, n_ct,
+                               sbits, (unsigned long long)cl.pos.n, cl.pos.p, cl.code.p, (unsigned long long*)cl.cnt.p, cl.total.p);
+            cl.total.download(&n_cand, 1, s);
+            VG_HIP(hipStreamSynchronize(s));
+            if (n_cand <= cl.pos.n) break;   // (else: the list was too short; nothing of it is used)
+        }
+        if (n_cand == 0) return;
+        unsigned pos_bits = 1; while (pos_bits < 64 && ((uint64_t)na >> pos_bits)) ++pos_bits;
+        sort_pairs(cl.code, cl.code2, cl.pos, cl.pos2, (int64_t)n_cand, (unsigned)sbits + 1, s);
+        sort_pairs(cl.pos, cl.pos2, cl.code, cl.code2, (int64_t)n_cand, pos_bits, s);
+        scan(cl.cnt.p, cl.beg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+        VG_HIP(hipMemsetAsync(cl.bad.p, 0, (size_t)n_cand, s));
+    }
+    // candidates of rank [lo, lo + width) of every member still without an offset; the width doubles
+    for (int64_t lo = 0, width = 1;; lo += width, width *= 2) {
+        vg_prof_scope ps_("dedup_cverify", 0.0);
+        int64_t n_vt = 0;
+        hipLaunchKernelGGL(k_cbatch, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A, na, hp, d_len, res, cl.cnt.p, lo, lo + width, cnt.p);
+        scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+        vg_download_bytes(&n_vt, tbeg.p + na, sizeof n_vt, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (n_vt == 0) break;
+        hipLaunchKernelGGL(k_ccompare, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff, d_len, A, na, hp, tbeg.p, n_vt,
+                           cl.beg.p, lo, cl.code.p, sbits, cl.bad.p);
+        hipLaunchKernelGGL(k_cpick, dim3(grid_of(n_vt)), dim3(TPB), 0, s, A, na, d_len, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res);
+    }
+}
+
+// the device part: packed records (resident) -> representative / strand on the host; off_out != nullptr: circular mode,
+// which also fills the offsets
+void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, int64_t* off_out, vg_dedup_stats& st) {
     const int64_t n = ps.n;
     if (n == 0) return;
+    const bool circular = off_out != nullptr;
     hipStream_t s = vg_stream();
     const int bits = g_hash_bits.load();
     int64_t total_words = 0, max_len = 0;
@@ -342,40 +634,40 @@ void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, vg
         cbeg[(size_t)i + 1] = cbeg[(size_t)i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
         total_words += nw; max_len = std::max(max_len, ps.len[(size_t)i]);
     }
+    unsigned len_bits = 0; while (len_bits < 64 && (max_len >> len_bits)) ++len_bits;
+    const int sbits = (int)std::max(1u, len_bits);       // circular mode: an offset is below the length
     const int64_t n_tasks = cbeg[(size_t)n];
     dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1);
     d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
     dbuf<unsigned long long> d_h((size_t)n * 4);
     d_h.zero(s);
-    {
+    if (circular) {
+        vg_prof_scope ps_("dedup_chash", (double)total_words * 4.0);
+        hipLaunchKernelGGL(k_chash, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, d_h.p);
+    } else {
         vg_prof_scope ps_("dedup_hash", (double)total_words * 4.0);
         hipLaunchKernelGGL(k_hash, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, d_h.p);
     }
     d_cbeg.release();
-    dbuf<uint64_t> klo((size_t)n), khi((size_t)n), klen((size_t)n), kg((size_t)n), ks((size_t)n);
+    dbuf<uint64_t> klo((size_t)n), khi((size_t)n), klen((size_t)n);
     dbuf<uint8_t> ori((size_t)n);
     dbuf<int32_t> A((size_t)n), A2((size_t)n);
     {
         vg_prof_scope ps_("dedup_keys", (double)n * 66.0);
-        hipLaunchKernelGGL(k_keys, dim3(grid_of(n)), dim3(TPB), 0, s, d_h.p, d_len.p, n, bits, klo.p, khi.p, klen.p, ori.p, A.p);
+        if (circular) hipLaunchKernelGGL(k_ckeys, dim3(grid_of(n)), dim3(TPB), 0, s, d_h.p, d_len.p, n, bits, klo.p, khi.p, klen.p, A.p);
+        else hipLaunchKernelGGL(k_keys, dim3(grid_of(n)), dim3(TPB), 0, s, d_h.p, d_len.p, n, bits, klo.p, khi.p, klen.p, ori.p, A.p);
     }
     d_h.release();
-    {   // LSD: the low hash half, the high half, the length (stable passes: equal keys stay in index order)
-        vg_prof_scope ps_("dedup_sort", (double)n * 48.0);
-        unsigned len_bits = 0; while (len_bits < 64 && (max_len >> len_bits)) ++len_bits;
-        const unsigned pass_bits[3] = { (unsigned)std::min(bits, 64), (unsigned)std::max(bits - 64, 0), len_bits };
-        const uint64_t* src[3] = { klo.p, khi.p, klen.p };
-        for (int pass = 0; pass < 3; ++pass) {
-            if (!pass_bits[pass]) continue;
-            hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, src[pass], A.p, n, kg.p);
-            sort_pairs(kg, ks, A, A2, n, pass_bits[pass], s);
-        }
-    }
+    sort_by_key(klo, khi, klen, A, A2, n, bits, len_bits, s);
     dbuf<int32_t> d_rep((size_t)n), keep((size_t)n), at((size_t)n);
     dbuf<int8_t> d_strand((size_t)n);
     dbuf<int64_t> hp((size_t)n), hp2((size_t)n), cnt((size_t)n + 1), tbeg((size_t)n + 1);
     dbuf<uint8_t> diff((size_t)n);
     dbuf<unsigned long long> d_ndiff(1);
+    dbuf<int64_t> d_off;
+    dbuf<unsigned long long> res;
+    cand_list cl;
+    if (circular) { d_off.alloc((size_t)n); res.alloc((size_t)n); cl.cnt.alloc((size_t)n + 1); cl.beg.alloc((size_t)n + 1); cl.total.alloc(1); }
     int64_t na = n;
     while (na > 0) {
         ++st.rounds;
@@ -384,18 +676,24 @@ void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, vg
             vg_prof_scope ps_("dedup_runs", (double)na * 60.0);
             hipLaunchKernelGGL(k_runs, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, klo.p, khi.p, klen.p, hp2.p);
             scan(hp2.p, hp.p, na, true, rocprim::maximum<int64_t>(), s);
-            hipLaunchKernelGGL(k_tasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A.p, na, hp.p, d_len.p, cnt.p, diff.p);
-            scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+            if (!circular) {
+                hipLaunchKernelGGL(k_tasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A.p, na, hp.p, d_len.p, cnt.p, diff.p);
+                scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+            }
         }
-        int64_t n_vt = 0;
-        vg_download_bytes(&n_vt, tbeg.p + na, sizeof n_vt, s);          // (the element at na: the total)
-        VG_HIP(hipStreamSynchronize(s));
-        if (n_vt > 0) {
-            vg_prof_scope ps_("dedup_verify", (double)n_vt * VERIFY_CHUNK * 8.0);
-            hipLaunchKernelGGL(k_verify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, ori.p, A.p, na,
-                               hp.p, tbeg.p, n_vt, diff.p);
-        }
-        {
+        if (circular) {
+            circular_round(ps, d_woff.p, d_len.p, A.p, na, hp.p, cnt, tbeg, cl, sbits, res.p, s);
+            vg_prof_scope ps_("dedup_labels", (double)na * 32.0);
+            hipLaunchKernelGGL(k_cresolve, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, hp.p, res.p, sbits, d_rep.p, d_strand.p, d_off.p, keep.p, d_ndiff.p);
+        } else {
+            int64_t n_vt = 0;
+            vg_download_bytes(&n_vt, tbeg.p + na, sizeof n_vt, s);          // (the element at na: the total)
+            VG_HIP(hipStreamSynchronize(s));
+            if (n_vt > 0) {
+                vg_prof_scope ps_("dedup_verify", (double)n_vt * VERIFY_CHUNK * 8.0);
+                hipLaunchKernelGGL(k_verify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, ori.p, A.p, na,
+                                   hp.p, tbeg.p, n_vt, diff.p);
+            }
             vg_prof_scope ps_("dedup_labels", (double)na * 24.0);
             hipLaunchKernelGGL(k_resolve, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, hp.p, diff.p, ori.p, d_rep.p, d_strand.p, keep.p, d_ndiff.p);
         }
@@ -414,6 +712,7 @@ void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, vg
     }
     d_rep.download(rep_out, (size_t)n, s);
     d_strand.download(strand_out, (size_t)n, s);
+    if (circular) d_off.download(off_out, (size_t)n, s);
     VG_HIP(hipStreamSynchronize(s));
 }
 
@@ -476,13 +775,17 @@ void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<st
     for (auto& m : member) parts.emplace_back((const char*)m.data(), m.size());
     write_all(path, parts);
 }
-void write_duplicates(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, const int8_t* strand) {
+// offset: nullptr, or (circular mode) the fourth column
+void write_duplicates(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, const int8_t* strand,
+                      const int64_t* offset) {
     const int64_t n = (int64_t)in.recs.size();
     auto id = [&](int64_t i) { const vg_fasta_rec& r = in.recs[(size_t)i]; return prefix[(size_t)r.file] + first_token(r.hdr, r.hdr_end); };
-    std::string out = "representative\tduplicate\tstrand\n";
+    std::string out = offset ? "representative\tduplicate\tstrand\toffset\n" : "representative\tduplicate\tstrand\n";
     for (int64_t i = 0; i < n; ++i) {
         if (rep[i] == (int32_t)i) continue;
-        out += id(rep[i]); out += '\t'; out += id(i); out += '\t'; out += strand[i] ? '-' : '+'; out += '\n';
+        out += id(rep[i]); out += '\t'; out += id(i); out += '\t'; out += strand[i] ? '-' : '+';
+        if (offset) { out += '\t'; out += std::to_string(offset[i]); }
+        out += '\n';
     }
     write_all(path, { { out.data(), out.size() } });
 }
@@ -490,9 +793,11 @@ void write_duplicates(const char* path, const vg_fasta_text& in, const std::vect
 
 extern "C" void vg_dedup_set_hash_bits(int bits) { g_hash_bits.store(std::max(0, std::min(bits, 128))); }
 
-extern "C" int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
-                             vg_dedup_stats* stats) {
+extern "C" int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64_t n, const vg_dedup_options* options,
+                                int32_t* representative, int8_t* strand, int64_t* offset, vg_dedup_stats* stats) {
     VG_API_BEGIN
+    const bool circular = options && options->circular;
+    if (n > 0 && circular && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_ex: circular mode needs the offset array");
     if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_seqs: negative count");
     if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_dedup_seqs: 2^31 or more records (record indices are int32)");
     if (n && (!offsets || !representative || !strand)) throw vg_error(VG_EINVAL, "vg_dedup_seqs: null argument");
@@ -508,14 +813,21 @@ extern "C" int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t 
     pack_and_upload(seq, vg_host_threads(), ps);
     if (ps.bad_rec >= 0)
         throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
-    dedup_device(ps, representative, strand, st);
+    if (offset) std::fill(offset, offset + n, (int64_t)0);
+    dedup_device(ps, representative, strand, circular ? offset : nullptr, st);
     finish_stats(n, representative, strand, st);
     VG_API_END
 }
 
-extern "C" int vg_deduplicate(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
-                              const char* dup_path, const vg_dedup_params* p) {
+extern "C" int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
+                             vg_dedup_stats* stats) {
+    return vg_dedup_seqs_ex(ascii, offsets, n, nullptr, representative, strand, nullptr, stats);
+}
+
+extern "C" int vg_deduplicate_ex(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                                 const char* dup_path, const vg_dedup_params* p, const vg_dedup_options* options) {
     VG_API_BEGIN
+    const bool circular = options && options->circular;
     if (!paths || n_paths <= 0 || !out_path || !dup_path || !p) throw vg_error(VG_EINVAL, "vg_deduplicate: null argument");
     if (p->gzip_level < 0 || p->gzip_level > 9) throw vg_error(VG_EINVAL, "vg_deduplicate: gzip_level must be 0 (plain) or 1..9");
     for (int i = 0; i < n_paths; ++i) {
@@ -546,17 +858,23 @@ extern "C" int vg_deduplicate(const char* const* paths, int n_paths, const char*
     vg_require_device();
     std::vector<int32_t> rep((size_t)std::max<int64_t>(n, 1));
     std::vector<int8_t> strand((size_t)std::max<int64_t>(n, 1));
+    std::vector<int64_t> offset(circular ? (size_t)std::max<int64_t>(n, 1) : 0);
     vg_dedup_stats st{};
-    dedup_device(ps, rep.data(), strand.data(), st);
+    dedup_device(ps, rep.data(), strand.data(), circular ? offset.data() : nullptr, st);
     finish_stats(n, rep.data(), strand.data(), st);
     ps.d_words.release();
     vg_host_mark("dedup: groups computed");
     write_fasta(out_path, in, prefix, rep.data(), p->gzip_level, T);
-    write_duplicates(dup_path, in, prefix, rep.data(), strand.data());
+    write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), circular ? offset.data() : nullptr);
     vg_host_mark("dedup: written");
     if (p->verbosity >= 1)
         fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds\n",
                 (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
                 (long long)st.rounds);
     VG_API_END
+}
+
+extern "C" int vg_deduplicate(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                              const char* dup_path, const vg_dedup_params* p) {
+    return vg_deduplicate_ex(paths, n_paths, prefixes, out_path, dup_path, p, nullptr);
 }

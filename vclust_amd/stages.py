@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import CLUSTER_ALGORITHMS, AlignParams, ClusterParams, DedupParams, LzParams, PrefilterParams, check
+from ._lib import CLUSTER_ALGORITHMS, AlignParams, ClusterParams, DedupOptions, DedupParams, LzParams, PrefilterParams, check
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -67,12 +67,19 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     check(_lib.load().vg_cluster(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)), C.byref(p)))
 
 
-def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0):
+def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False):
     """The distinct records of the FASTA files `paths` -> out_path, the removed ones -> dup_path (vg_deduplicate).
-    prefixes: None or one string per path, put in front of every header of that file; gzip_level 0 = plain output."""
+    prefixes: None or one string per path, put in front of every header of that file; gzip_level 0 = plain output.
+    circular: rotations of a record and of its reverse complement are duplicates too, and dup_path gets an offset column
+    (vg_deduplicate_ex)."""
     if prefixes is not None and len(prefixes) != len(paths):
         raise ValueError('one prefix per input file')
     arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
     pre = (C.c_char_p * len(paths))(*[str(x).encode() for x in prefixes]) if prefixes is not None else None
     prm = DedupParams(gzip_level=int(gzip_level), num_threads=int(num_threads), verbosity=int(verbosity))
+    if circular:
+        opt = DedupOptions(circular=1)
+        check(_lib.load().vg_deduplicate_ex(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm),
+                                            C.byref(opt)))
+        return
     check(_lib.load().vg_deduplicate(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm)))
