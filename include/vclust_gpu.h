@@ -358,6 +358,31 @@ int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64_t n, const
                      int32_t* representative, int8_t* strand, int64_t* offset, vg_dedup_stats* stats);
 /* test knob: keep only the low `bits` (0..128) bits of the sequence hash (forces collisions); 128 = the default */
 void vg_dedup_set_hash_bits(int bits);
+/* Contained mode: X is contained in Y when len X <= len Y and X is a contiguous substring of Y or
+ * of revcomp(Y) (linear, no wrap-around; symbols compare literally).  A non-empty record is removed when a longer record
+ * contains it, or an earlier record of the same length equals it or its reverse complement.  Its representative is the
+ * longest kept record that contains it, the earliest of several; strand is 0 when it occurs in the representative, 1 when
+ * only in the representative's reverse complement; offset is the smallest s with Y[s .. s + len) == record, Y the
+ * representative (strand 0) or its reverse complement (strand 1).  Empty records are contained in nothing and form one
+ * group.  The duplicates file has the four columns of the circular mode.  Errors are those of vg_deduplicate /
+ * vg_dedup_seqs; offset[n] is required. */
+typedef struct {
+    int64_t passes;             /* index passes (container positions are indexed in bounded passes) */
+    int64_t positions;          /* container positions indexed, all passes */
+    int64_t hits;               /* indexed windows that start with a record's anchor, both strands */
+    int64_t candidates;         /* hits that leave room for the record in a longer (or equal, earlier) record: compared in full */
+    int64_t verified;           /* candidates that were equal */
+    int64_t slices;             /* candidate launches (the hits are cut into slices of bounded size) */
+} vg_dedup_contained_stats;
+int vg_deduplicate_contained(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                             const char* dup_path, const vg_dedup_params* p);
+/* stats and contained_stats may be NULL; stats->rounds = passes, stats->collisions = candidates - verified */
+int vg_dedup_seqs_contained(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
+                            int64_t* offset, vg_dedup_stats* stats, vg_dedup_contained_stats* contained_stats);
+/* test knobs of the contained mode: symbols of a record's anchor (1..16, default 16; short anchors flood the compare with
+ * false candidates), and the most container positions indexed per pass (0 = the default, sized from the free HBM) */
+void vg_dedup_set_anchor_symbols(int w);
+void vg_dedup_set_index_positions(int64_t n);
 
 /* ------------------------------------------------------------------ synthetic input --- */
 /* Workload generator of SURVEY.md 8(d) (bench / test input; no reference call site: the reference ships no

@@ -85,6 +85,11 @@ class DedupOptions(C.Structure):
     _fields_ = [('circular', C.c_int)]
 
 
+class DedupContainedStats(C.Structure):
+    _fields_ = [('passes', C.c_int64), ('positions', C.c_int64), ('hits', C.c_int64), ('candidates', C.c_int64),
+                ('verified', C.c_int64), ('slices', C.c_int64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('total_ms', C.c_double), ('launches', C.c_int64),
                 ('bytes', C.c_double)]
@@ -162,6 +167,11 @@ SYMBOLS = {
     'vg_dedup_seqs_ex': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(DedupOptions), P(C.c_int32), P(C.c_int8), P(C.c_int64),
                                    P(DedupStats)]),
     'vg_dedup_set_hash_bits': (None, [C.c_int]),
+    'vg_deduplicate_contained': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
+    'vg_dedup_seqs_contained': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(C.c_int64), P(DedupStats),
+                                          P(DedupContainedStats)]),
+    'vg_dedup_set_anchor_symbols': (None, [C.c_int]),
+    'vg_dedup_set_index_positions': (None, [C.c_int64]),
     'vg_synth_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_double, C.c_double, C.c_int,
                                 C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int64)]),
     'vg_profile_enable': (None, [C.c_int]),

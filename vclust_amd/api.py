@@ -266,13 +266,20 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
 
 
-def deduplicate(seqs, circular=False):
+def deduplicate(seqs, circular=False, contained=False):
     """Group the sequences `seqs` (str or bytes each; white space is skipped, case ignored) by equality up to reverse
     complement (vg_dedup_seqs).  -> (representative int32[n], strand int8[n], stats dict): representative[i] is the index of
     the earliest sequence of i's group, strand[i] is 1 when i equals only that sequence's reverse complement, else 0.
     circular=True (vg_dedup_seqs_ex): rotations of a sequence and of its reverse complement are equal too; strand[i] is 1
     when i equals only rotations of the reverse complement, and the result is (representative, strand, offset int64[n],
-    stats) with offset[i] the smallest s for which i == rot(representative or its reverse complement, s)."""
+    stats) with offset[i] the smallest s for which i == rot(representative or its reverse complement, s).
+    contained=True (vg_dedup_seqs_contained): a sequence that is a substring of a longer one, or of its reverse complement,
+    is removed too; representative[i] is the longest kept sequence that contains i (the earliest of several), strand[i] is 1
+    when i occurs only in its reverse complement, and the result is (representative, strand, offset int64[n], stats) with
+    offset[i] the smallest position of i in the representative (strand 0) or its reverse complement (strand 1); stats also
+    holds the counters of vg_dedup_contained_stats.  circular and contained together raise ValueError."""
+    if circular and contained:
+        raise ValueError('circular and contained exclude each other')
     bufs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
     n = len(bufs)
     offsets = np.zeros(n + 1, dtype=np.int64)
@@ -283,6 +290,14 @@ def deduplicate(seqs, circular=False):
     strand = np.zeros(max(n, 1), dtype=np.int8)
     st = DedupStats()
     P = C.POINTER
+    if contained:
+        off = np.zeros(max(n, 1), dtype=np.int64)
+        cst = _lib.DedupContainedStats()
+        check(_lib.load().vg_dedup_seqs_contained(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, rep.ctypes.data_as(P(C.c_int32)),
+                                                  strand.ctypes.data_as(P(C.c_int8)), off.ctypes.data_as(P(C.c_int64)), C.byref(st), C.byref(cst)))
+        stats = {k: getattr(st, k) for k, _ in DedupStats._fields_}
+        stats.update({k: getattr(cst, k) for k, _ in _lib.DedupContainedStats._fields_})
+        return rep[:n], strand[:n], off[:n], stats
     if circular:
         off = np.zeros(max(n, 1), dtype=np.int64)
         opt = _lib.DedupOptions(circular=1)
@@ -297,6 +312,16 @@ def deduplicate(seqs, circular=False):
 def dedup_set_hash_bits(bits=128):
     """Test knob (vg_dedup_set_hash_bits): keep only the low `bits` bits of the sequence hash; 128 = the default."""
     _lib.load().vg_dedup_set_hash_bits(int(bits))
+
+
+def dedup_set_anchor_symbols(w=16):
+    """Test knob (vg_dedup_set_anchor_symbols): symbols of an anchor in the contained mode, 1..16; 16 = the default."""
+    _lib.load().vg_dedup_set_anchor_symbols(int(w))
+
+
+def dedup_set_index_positions(n=0):
+    """Test knob (vg_dedup_set_index_positions): container positions indexed per pass in the contained mode; 0 = the default."""
+    _lib.load().vg_dedup_set_index_positions(int(n))
 
 
 def set_lz_fit(weak_seed_ratio=3, anchor_margin=-1, seed_choice=3):

@@ -110,6 +110,8 @@ def get_parser() -> argparse.ArgumentParser:
     dd.add_argument('--gzip-level', metavar='<int>', type=int, default=4, help='Compression level (1-9) [%(default)s]')
     dd.add_argument('--circular', action='store_true',
                     help='Circular genomes: rotations of a sequence and of its reverse complement are duplicates too')
+    dd.add_argument('--contained', action='store_true',
+                    help='Fragments: a sequence that is a contiguous substring of a longer sequence or of its reverse complement is removed too')
     common(dd)
 
     # prefilter
@@ -405,8 +407,11 @@ def deduplicate_call(args):
 
 def handle_deduplicate(args, parser, logger):
     circular = getattr(args, 'circular', False)
-    if circular or not BIN_MFASTA.exists():
-        # no mfasta-tool, or --circular (which mfasta-tool does not have): the GPU (vg_deduplicate)
+    contained = getattr(args, 'contained', False)
+    if circular and contained:
+        parser.error('--contained and --circular exclude each other.')
+    if circular or contained or not BIN_MFASTA.exists():
+        # no mfasta-tool, or --circular / --contained (which mfasta-tool does not have): the GPU (vg_deduplicate)
         args = validate_args_deduplicate(args, parser)
         from . import stages
         call = deduplicate_call(args)
@@ -414,9 +419,12 @@ def handle_deduplicate(args, parser, logger):
                 + (f' --add-prefixes {" ".join(args.add_prefixes)}' if args.add_prefixes else '')
                 + (f' --gzip-level {args.gzip_level}' if args.gzip_output else '')
                 + (' --circular' if circular else '')
+                + (' --contained' if contained else '')
                 + f' [1 GPU] -> {args.output_path}, {args.output_duplicates_path}')
         if circular:
             call['circular'] = True
+        if contained:
+            call['contained'] = True
         run_native(desc, lambda: stages.deduplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
         return
     _require_binary(BIN_MFASTA)

@@ -22,6 +22,17 @@
 //   cverify   per (member, candidate, chunk): the member against the head rotated by the candidate (v_alignbit_b32 re-frames
 //             by offset mod 8, the word index wraps); candidates are tried in increasing order, in batches of 1, 2, 4, ...
 //             per member, and the smallest equal one is the answer
+// Contained mode (vg_deduplicate_contained): a record that is a substring of a longer record, or of its reverse complement,
+// is removed as well.
+//   windows   one thread per symbol position of a pass: the 16 symbols from it as one 64-bit key, the first symbol in the
+//             top bits (the bit reversal of the packed window, so a symbol's code is its complement's: still one code per symbol)
+//   sort      rocPRIM radix sort of (key, position)
+//   lookup    per (record, strand): the anchor (the first min(anchor, L) symbols of X or of revcomp(X)) is a key range of
+//             the sorted windows, found by two binary searches; the hits are cut into slices, and a hit in a longer record
+//             that leaves room for the whole record (or at 0 in an earlier record of the same length) is a candidate
+//   verify    one wave per (candidate, chunk): X, or revcomp(X) made by v_bfrev_b32, against the container re-framed by
+//             v_alignbit_b32; a mismatch sets the candidate's flag (32-bit atomic) and ends its other chunks early
+//   pick      64-bit atomicMax per record of (container's rank by length and index, strand, offset) over the equal candidates
 #include "vg_common.h"
 #include <rocprim/rocprim.hpp>
 #include <zlib.h>
@@ -41,6 +52,11 @@ constexpr int64_t STRETCH_WORDS = 8 << 20;  // 32 MiB of packed symbols: the uni
 constexpr size_t GZ_BLOCK = 4u << 20;       // uncompressed bytes per gzip member of the output
 
 std::atomic<int> g_hash_bits(128);
+std::atomic<int> g_anchor_symbols(16);      // contained mode: symbols of an anchor (test knob)
+std::atomic<int64_t> g_index_positions(0);  // contained mode: container positions indexed per pass, 0 = from the free HBM (test knob)
+constexpr int64_t CAND_SLICE = 1 << 20;     // contained mode: anchor hits per candidate launch (the candidate queue's size)
+constexpr int64_t INDEX_BYTES = 48;         // contained mode: HBM per indexed position (key, value, the sort's second pair and scratch)
+constexpr int64_t MAX_PASS_POSITIONS = 1LL << 30;
 
 // ---------------------------------------------------------------- host: packing
 // byte -> 4-bit set of bases; 0x10 = white space (skipped), 0x20 = not in the alphabet
@@ -530,6 +546,133 @@ __global__ void k_cresolve(const int32_t* A, int64_t na, const int64_t* hp, cons
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_diff, (unsigned long long)c);
 }
 
+// ---------------------------------------------------------------- device: contained mode
+// the 16 symbols of a record of L symbols from b < L, the first in the low bits; zero behind the record's end (three words
+// are read: the packed buffer ends with four zero words)
+__device__ __forceinline__ uint64_t window_at(const uint32_t* R, int64_t L, int64_t b) {
+    const int64_t k = b >> 3;
+    const uint32_t sh = (uint32_t)(4 * (b & 7)), x0 = R[k], x1 = R[k + 1], x2 = R[k + 2];
+    const uint64_t w = (uint64_t)__builtin_amdgcn_alignbit(x1, x0, sh) | ((uint64_t)__builtin_amdgcn_alignbit(x2, x1, sh) << 32);
+    const int64_t nv = L - b;
+    return nv >= 16 ? w : w & ((1ull << (4 * nv)) - 1);
+}
+// Index entry t of a pass: position pos0 + t of the concatenated records (pbeg = the records' first positions).  The key is
+// the bit reversal of the window: symbol k of the window sits in nibble 15 - k as its complement's code, so keys that share
+// their top 4 w bits are the windows that share their first w symbols.
+__global__ void k_cwindows(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                           const int64_t* __restrict__ pbeg, int64_t n, int64_t pos0, int64_t np, uint64_t* key, int64_t* val) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < np; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t g = pos0 + t, j = owner_of(pbeg, n, g);
+        key[t] = __builtin_bitreverse64(window_at(W + woff[j], len[j], g - pbeg[j]));
+        val[t] = g;
+    }
+}
+// Query q = 2 i + strand: the sorted keys that start with the anchor, hlo[q] .. hlo[q] + hcnt[q] - 1.  Forward anchor: the
+// first w = min(anchor, L) symbols of X.  Reverse anchor: the first w symbols of revcomp(X), whose key is X's last w symbols
+// as they are packed, moved to the top bits (revcomp(X) lies in Y exactly when X lies in revcomp(Y)).  hcnt[2 n] = 0.
+__global__ void k_clookup(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len, int64_t n,
+                          int anchor, const uint64_t* __restrict__ key, int64_t np, int64_t* hlo, int64_t* hcnt) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q <= 2 * n; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = q >> 1, L = q < 2 * n ? len[i] : 0;
+        if (L == 0) { hlo[q] = 0; hcnt[q] = 0; continue; }
+        const int w = (int)min((int64_t)anchor, L);
+        const uint64_t rest = w == 16 ? 0ull : (1ull << (64 - 4 * w)) - 1;
+        const uint32_t* R = W + woff[i];
+        const uint64_t a = ((q & 1) ? window_at(R, L, L - w) << (64 - 4 * w) : __builtin_bitreverse64(window_at(R, L, 0))) & ~rest;
+        int64_t lo = 0, hi = np;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (key[mid] < a) lo = mid + 1; else hi = mid; }
+        const int64_t first = lo;
+        hi = np;
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (key[mid] <= (a | rest)) lo = mid + 1; else hi = mid; }
+        hlo[q] = first; hcnt[q] = lo - first;
+    }
+}
+// Hits h0 .. h1 - 1 of the pass (hoff = the queries' first hits): hit (i, strand) at position s of record j is a candidate
+// when j is longer and holds the whole record from s, or j is an earlier record of the same length and s = 0.  The queue has
+// room for every hit of the slice.
+__global__ void __launch_bounds__(TPB) k_ccands(const int64_t* __restrict__ len, const int64_t* __restrict__ pbeg, int64_t n,
+                                                const int64_t* __restrict__ hoff, const int64_t* __restrict__ hlo, const int64_t* __restrict__ val,
+                                                int64_t h0, int64_t h1, uint32_t* cq, int32_t* cj, int64_t* cs, unsigned long long* n_cand) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t below = (1ull << lane) - 1;
+    for (int64_t h = h0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;; h += (int64_t)gridDim.x * blockDim.x) {
+        if (!__ballot(h < h1)) break;
+        bool ok = false;
+        int64_t q = 0, j = 0, s = 0;
+        if (h < h1) {
+            q = owner_of(hoff, 2 * n, h);
+            const int64_t g = val[hlo[q] + (h - hoff[q])], i = q >> 1;
+            j = owner_of(pbeg, n, g); s = g - pbeg[j];
+            const int64_t Li = len[i], Lj = len[j];
+            ok = (Lj > Li && s + Li <= Lj) || (Lj == Li && s == 0 && j < i);
+        }
+        const uint64_t b = __ballot(ok);
+        if (!b) continue;
+        unsigned long long at = 0;
+        if (lane == 0) at = atomicAdd(n_cand, (unsigned long long)__popcll(b));
+        at = __shfl(at, 0) + (unsigned long long)__popcll(b & below);
+        if (ok) { cq[at] = (uint32_t)q; cj[at] = (int32_t)j; cs[at] = s; }
+    }
+}
+// verification tasks per candidate: the chunks of the record; bad[c] = 0; cnt[nc] = 0 (the total's slot)
+__global__ void k_cvtasks(const uint32_t* cq, int64_t nc, const int64_t* len, int64_t* cnt, uint32_t* bad) {
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= nc; c += (int64_t)gridDim.x * blockDim.x) {
+        if (c == nc) { cnt[c] = 0; continue; }
+        cnt[c] = chunks_of(len[cq[c] >> 1]);
+        bad[c] = 0;
+    }
+}
+// One wave per (candidate, chunk): word k of X (forward) or of revcomp(X) (reverse: only the record is reversed) against
+// the 8 symbols of the container from s + 8 k, two neighbouring words re-framed by s mod 8 symbols.  The padding of the last
+// word is masked.  A mismatch sets the candidate's flag; a set flag ends the candidate's other chunks early.
+__global__ void __launch_bounds__(TPB) k_cverify(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                                 const uint32_t* __restrict__ cq, const int32_t* __restrict__ cj, const int64_t* __restrict__ cs,
+                                                 int64_t nc, const int64_t* __restrict__ tbeg, int64_t n_tasks, uint32_t* bad) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t c = owner_of(tbeg, nc, t), ch = t - tbeg[c];
+        if (bad[c]) continue;
+        const int64_t i = cq[c] >> 1, s = cs[c];
+        const bool rcs = (cq[c] & 1u) != 0;
+        const int64_t L = len[i], nw = (L + 7) >> 3, qd = L >> 3;
+        const int r = (int)(L & 7);
+        const uint32_t sh = (uint32_t)(4 * (s & 7));
+        const uint32_t* M = W + woff[i]; const uint32_t* H = W + woff[cj[c]] + (s >> 3);
+        bool diff = false;
+        for (int64_t base = ch * VERIFY_CHUNK, k1 = min(nw, (ch + 1) * VERIFY_CHUNK); base < k1; base += 64) {
+            const int64_t k = base + lane;
+            if (k < k1) {
+                uint32_t x;
+                if (!rcs) x = M[k];
+                else if (k < qd) { const int64_t f = qd - 1 - k; x = rc_word(r ? M[f + 1] : 0u, M[f], r); }
+                else x = rc_word(M[0], 0u, r);                   // (k == qd, r > 0)
+                const uint32_t y = __builtin_amdgcn_alignbit(H[k + 1], H[k], sh);
+                const int64_t nv = min((int64_t)8, L - 8 * k);
+                const uint32_t mask = nv == 8 ? ~0u : (1u << (4 * nv)) - 1;
+                diff = ((x ^ y) & mask) != 0;
+            }
+            if (__ballot(diff)) break;
+        }
+        if (__ballot(diff) && lane == 0) atomicOr(bad + c, 1u);
+    }
+}
+// best[i] = the largest key over the candidates without a flag: the container's rank from the end of the order (length
+// descending, index ascending), then '+' before '-', then the smallest offset.  The offset of a reverse hit is counted in
+// revcomp(container): revcomp(X) at s of Y is X at L_Y - L_X - s of revcomp(Y).  Keys are above 0 (an offset is below 2^sbits - 1).
+__global__ void k_cpick(const int64_t* len, const int32_t* rnk, int64_t n, const uint32_t* cq, const int32_t* cj, const int64_t* cs, int64_t nc,
+                        const uint32_t* bad, int sbits, unsigned long long* best, unsigned long long* n_equal) {
+    int e = 0;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
+        if (bad[c]) continue;
+        const int64_t i = cq[c] >> 1, j = cj[c];
+        const uint64_t rcs = cq[c] & 1u, off = (uint64_t)(rcs ? len[j] - len[i] - cs[c] : cs[c]), m = (1ull << sbits) - 1;
+        atomicMax(best + i, (unsigned long long)(((uint64_t)(n - 1 - rnk[j]) << (sbits + 1)) | ((rcs ^ 1u) << sbits) | (m - off)));
+        ++e;
+    }
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+    if ((threadIdx.x & 63) == 0 && e) atomicAdd(n_equal, (unsigned long long)e);
+}
+
 int grid_of(int64_t n, int per_block = TPB, int cap = 16384) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, cap));
 }
@@ -716,6 +859,122 @@ void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, in
     VG_HIP(hipStreamSynchronize(s));
 }
 
+// Contained mode on the device: packed records (resident) -> representative / strand / offset on the host.  Every equal
+// candidate is a container of its record, and the largest key among them names a kept record: were the longest, earliest
+// container removed, its own container (longer, or equal and earlier) would contain the record too and have a larger key.
+// So one reduction over all candidates of all passes gives the representative; no second phase over the kept records.
+void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, int64_t* off_out, vg_dedup_stats& st,
+                      vg_dedup_contained_stats& cst) {
+    const int64_t n = ps.n;
+    if (n == 0) return;
+    hipStream_t s = vg_stream();
+    std::vector<int64_t> pbeg((size_t)n + 1, 0);
+    int64_t max_len = 0;
+    for (int64_t i = 0; i < n; ++i) { pbeg[(size_t)i + 1] = pbeg[(size_t)i] + ps.len[(size_t)i]; max_len = std::max(max_len, ps.len[(size_t)i]); }
+    const int64_t total_pos = pbeg[(size_t)n];
+    int sbits = 1; while (sbits < 63 && (max_len >> sbits)) ++sbits;
+    int rbits = 1; while (rbits < 32 && ((n - 1) >> rbits)) ++rbits;
+    if (rbits + 1 + sbits > 64)
+        throw vg_error(VG_EOVERFLOW, "vg_deduplicate_contained: record count and longest record together exceed the 64-bit result key");
+    std::vector<int32_t> order((size_t)n), rnk((size_t)n);      // by (length descending, index ascending)
+    for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (int32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ps.len[(size_t)a] > ps.len[(size_t)b]; });
+    for (int64_t r = 0; r < n; ++r) rnk[(size_t)order[(size_t)r]] = (int32_t)r;
+    std::vector<unsigned long long> best((size_t)n, 0ull);
+    if (total_pos > 0) {
+        const int anchor = g_anchor_symbols.load();
+        int64_t per_pass = g_index_positions.load();
+        if (per_pass <= 0) {
+            size_t fr = 0, tot = 0;
+            VG_HIP(hipMemGetInfo(&fr, &tot));
+            per_pass = std::max<int64_t>(1 << 20, (int64_t)(fr / 2) / INDEX_BYTES);
+        }
+        per_pass = std::min(std::min(per_pass, total_pos), MAX_PASS_POSITIONS);
+        dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_pbeg((size_t)n + 1);
+        dbuf<int32_t> d_rnk((size_t)n);
+        dbuf<unsigned long long> d_best((size_t)n), d_count(2);          // [0] candidates of a slice, [1] equal candidates
+        d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_pbeg.upload(pbeg.data(), (size_t)n + 1, s);
+        d_rnk.upload(rnk.data(), (size_t)n, s);
+        d_best.zero(s); d_count.zero(s);
+        const int64_t nq = 2 * n;
+        dbuf<int64_t> hlo((size_t)nq + 1), hcnt((size_t)nq + 1), hoff((size_t)nq + 1);
+        dbuf<uint32_t> cq((size_t)CAND_SLICE), bad((size_t)CAND_SLICE);
+        dbuf<int32_t> cj((size_t)CAND_SLICE);
+        dbuf<int64_t> cs((size_t)CAND_SLICE), cnt((size_t)CAND_SLICE + 1), tbeg((size_t)CAND_SLICE + 1);
+        for (int64_t pos0 = 0; pos0 < total_pos; pos0 += per_pass) {
+            const int64_t np = std::min(per_pass, total_pos - pos0);
+            ++cst.passes; cst.positions += np;
+            dbuf<uint64_t> key((size_t)np);
+            dbuf<int64_t> val((size_t)np);
+            {
+                vg_prof_scope ps_("dedupc_windows", (double)np * 16.5);
+                hipLaunchKernelGGL(k_cwindows, dim3(grid_of(np, TPB, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_pbeg.p, n, pos0, np,
+                                   key.p, val.p);
+            }
+            {
+                vg_prof_scope ps_("dedupc_sort", (double)np * 64.0);
+                dbuf<uint64_t> key2((size_t)np);
+                dbuf<int64_t> val2((size_t)np);
+                sort_pairs(key, key2, val, val2, np, 64u, s);
+            }
+            int64_t n_hits = 0;
+            {
+                vg_prof_scope ps_("dedupc_lookup", (double)nq * 40.0);
+                hipLaunchKernelGGL(k_clookup, dim3(grid_of(nq + 1)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, n, anchor, key.p, np, hlo.p, hcnt.p);
+                scan(hcnt.p, hoff.p, nq + 1, false, rocprim::plus<int64_t>(), s);
+                vg_download_bytes(&n_hits, hoff.p + nq, sizeof n_hits, s);
+                VG_HIP(hipStreamSynchronize(s));
+            }
+            cst.hits += n_hits;
+            for (int64_t h0 = 0; h0 < n_hits; h0 += CAND_SLICE) {
+                const int64_t h1 = std::min(n_hits, h0 + CAND_SLICE);
+                unsigned long long nc = 0;
+                ++cst.slices;
+                {
+                    vg_prof_scope ps_("dedupc_lookup", (double)(h1 - h0) * 32.0);
+                    VG_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), s));
+                    hipLaunchKernelGGL(k_ccands, dim3(grid_of(h1 - h0)), dim3(TPB), 0, s, d_len.p, d_pbeg.p, n, hoff.p, hlo.p, val.p, h0, h1,
+                                       cq.p, cj.p, cs.p, d_count.p);
+                    d_count.download(&nc, 1, s);
+                    VG_HIP(hipStreamSynchronize(s));
+                }
+                if (nc == 0) continue;
+                cst.candidates += (int64_t)nc;
+                {
+                    vg_prof_scope ps_("dedupc_verify", 0.0);
+                    int64_t n_vt = 0;
+                    hipLaunchKernelGGL(k_cvtasks, dim3(grid_of((int64_t)nc + 1)), dim3(TPB), 0, s, cq.p, (int64_t)nc, d_len.p, cnt.p, bad.p);
+                    scan(cnt.p, tbeg.p, (int64_t)nc + 1, false, rocprim::plus<int64_t>(), s);
+                    vg_download_bytes(&n_vt, tbeg.p + nc, sizeof n_vt, s);
+                    VG_HIP(hipStreamSynchronize(s));
+                    hipLaunchKernelGGL(k_cverify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, cq.p, cj.p, cs.p,
+                                       (int64_t)nc, tbeg.p, n_vt, bad.p);
+                }
+                vg_prof_scope ps_("dedupc_pick", (double)nc * 24.0);
+                hipLaunchKernelGGL(k_cpick, dim3(grid_of((int64_t)nc)), dim3(TPB), 0, s, d_len.p, d_rnk.p, n, cq.p, cj.p, cs.p, (int64_t)nc, bad.p, sbits,
+                                   d_best.p, d_count.p + 1);
+            }
+        }
+        unsigned long long n_equal = 0;
+        d_best.download(best.data(), (size_t)n, s);
+        vg_download_bytes(&n_equal, d_count.p + 1, sizeof n_equal, s);
+        VG_HIP(hipStreamSynchronize(s));
+        cst.verified = (int64_t)n_equal;
+    }
+    st.rounds = cst.passes; st.collisions = cst.candidates - cst.verified;
+    int64_t first_empty = -1;
+    const unsigned long long m = (1ull << sbits) - 1;
+    for (int64_t i = 0; i < n; ++i) {
+        rep_out[i] = (int32_t)i; strand_out[i] = 0; off_out[i] = 0;
+        if (ps.len[(size_t)i] == 0) { if (first_empty < 0) first_empty = i; else rep_out[i] = (int32_t)first_empty; continue; }
+        const unsigned long long b = best[(size_t)i];
+        if (!b) continue;
+        rep_out[i] = order[(size_t)(n - 1 - (int64_t)(b >> (sbits + 1)))];
+        strand_out[i] = ((b >> sbits) & 1ull) ? 0 : 1;
+        off_out[i] = (int64_t)(m - (b & m));
+    }
+}
+
 void finish_stats(int64_t n, const int32_t* rep, const int8_t* strand, vg_dedup_stats& st) {
     st.records = n; st.unique = 0; st.reverse = 0;
     for (int64_t i = 0; i < n; ++i) { st.unique += rep[i] == (int32_t)i; st.reverse += rep[i] != (int32_t)i && strand[i]; }
@@ -789,15 +1048,13 @@ void write_duplicates(const char* path, const vg_fasta_text& in, const std::vect
     }
     write_all(path, { { out.data(), out.size() } });
 }
-}  // namespace
+enum dedup_mode { MODE_PLAIN, MODE_CIRCULAR, MODE_CONTAINED };
 
-extern "C" void vg_dedup_set_hash_bits(int bits) { g_hash_bits.store(std::max(0, std::min(bits, 128))); }
-
-extern "C" int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64_t n, const vg_dedup_options* options,
-                                int32_t* representative, int8_t* strand, int64_t* offset, vg_dedup_stats* stats) {
+int dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, dedup_mode mode, int32_t* representative, int8_t* strand, int64_t* offset,
+               vg_dedup_stats* stats, vg_dedup_contained_stats* cstats) {
     VG_API_BEGIN
-    const bool circular = options && options->circular;
-    if (n > 0 && circular && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_ex: circular mode needs the offset array");
+    if (n > 0 && mode == MODE_CIRCULAR && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_ex: circular mode needs the offset array");
+    if (n > 0 && mode == MODE_CONTAINED && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_contained: the offset array is required");
     if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_seqs: negative count");
     if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_dedup_seqs: 2^31 or more records (record indices are int32)");
     if (n && (!offsets || !representative || !strand)) throw vg_error(VG_EINVAL, "vg_dedup_seqs: null argument");
@@ -806,6 +1063,8 @@ extern "C" int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64
         if (offsets[i + 1] < offsets[i]) throw vg_error(VG_EINVAL, "vg_dedup_seqs: offsets must not decrease");
     vg_dedup_stats st_local{}; vg_dedup_stats& st = stats ? *stats : st_local;
     st = vg_dedup_stats{};
+    vg_dedup_contained_stats cst_local{}; vg_dedup_contained_stats& cst = cstats ? *cstats : cst_local;
+    cst = vg_dedup_contained_stats{};
     if (n == 0) return VG_OK;
     std::vector<std::pair<const char*, const char*>> seq((size_t)n);
     for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
@@ -814,20 +1073,15 @@ extern "C" int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64
     if (ps.bad_rec >= 0)
         throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
     if (offset) std::fill(offset, offset + n, (int64_t)0);
-    dedup_device(ps, representative, strand, circular ? offset : nullptr, st);
+    if (mode == MODE_CONTAINED) contained_device(ps, representative, strand, offset, st, cst);
+    else dedup_device(ps, representative, strand, mode == MODE_CIRCULAR ? offset : nullptr, st);
     finish_stats(n, representative, strand, st);
     VG_API_END
 }
 
-extern "C" int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
-                             vg_dedup_stats* stats) {
-    return vg_dedup_seqs_ex(ascii, offsets, n, nullptr, representative, strand, nullptr, stats);
-}
-
-extern "C" int vg_deduplicate_ex(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
-                                 const char* dup_path, const vg_dedup_params* p, const vg_dedup_options* options) {
+int deduplicate_files(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path, const char* dup_path,
+                      const vg_dedup_params* p, dedup_mode mode) {
     VG_API_BEGIN
-    const bool circular = options && options->circular;
     if (!paths || n_paths <= 0 || !out_path || !dup_path || !p) throw vg_error(VG_EINVAL, "vg_deduplicate: null argument");
     if (p->gzip_level < 0 || p->gzip_level > 9) throw vg_error(VG_EINVAL, "vg_deduplicate: gzip_level must be 0 (plain) or 1..9");
     for (int i = 0; i < n_paths; ++i) {
@@ -856,25 +1110,63 @@ extern "C" int vg_deduplicate_ex(const char* const* paths, int n_paths, const ch
                                   "' is not an IUPAC nucleotide code");
     }
     vg_require_device();
+    const bool with_offset = mode != MODE_PLAIN;
     std::vector<int32_t> rep((size_t)std::max<int64_t>(n, 1));
     std::vector<int8_t> strand((size_t)std::max<int64_t>(n, 1));
-    std::vector<int64_t> offset(circular ? (size_t)std::max<int64_t>(n, 1) : 0);
+    std::vector<int64_t> offset(with_offset ? (size_t)std::max<int64_t>(n, 1) : 0);
     vg_dedup_stats st{};
-    dedup_device(ps, rep.data(), strand.data(), circular ? offset.data() : nullptr, st);
+    vg_dedup_contained_stats cst{};
+    if (mode == MODE_CONTAINED) contained_device(ps, rep.data(), strand.data(), offset.data(), st, cst);
+    else dedup_device(ps, rep.data(), strand.data(), with_offset ? offset.data() : nullptr, st);
     finish_stats(n, rep.data(), strand.data(), st);
     ps.d_words.release();
     vg_host_mark("dedup: groups computed");
     write_fasta(out_path, in, prefix, rep.data(), p->gzip_level, T);
-    write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), circular ? offset.data() : nullptr);
+    write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), with_offset ? offset.data() : nullptr);
     vg_host_mark("dedup: written");
-    if (p->verbosity >= 1)
+    if (p->verbosity >= 1 && mode == MODE_CONTAINED)
+        fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld on the reverse strand), %lld anchor hits, %lld candidates, "
+                        "%lld of them equal, %lld index passes\n",
+                (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)cst.hits,
+                (long long)cst.candidates, (long long)cst.verified, (long long)cst.passes);
+    else if (p->verbosity >= 1)
         fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds\n",
                 (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
                 (long long)st.rounds);
     VG_API_END
 }
+}  // namespace
+
+extern "C" void vg_dedup_set_hash_bits(int bits) { g_hash_bits.store(std::max(0, std::min(bits, 128))); }
+extern "C" void vg_dedup_set_anchor_symbols(int w) { g_anchor_symbols.store(std::max(1, std::min(w, 16))); }
+extern "C" void vg_dedup_set_index_positions(int64_t n) { g_index_positions.store(std::max<int64_t>(0, n)); }
+
+extern "C" int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64_t n, const vg_dedup_options* options,
+                                int32_t* representative, int8_t* strand, int64_t* offset, vg_dedup_stats* stats) {
+    return dedup_seqs(ascii, offsets, n, options && options->circular ? MODE_CIRCULAR : MODE_PLAIN, representative, strand, offset, stats, nullptr);
+}
+
+extern "C" int vg_dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
+                             vg_dedup_stats* stats) {
+    return dedup_seqs(ascii, offsets, n, MODE_PLAIN, representative, strand, nullptr, stats, nullptr);
+}
+
+extern "C" int vg_dedup_seqs_contained(const char* ascii, const int64_t* offsets, int64_t n, int32_t* representative, int8_t* strand,
+                                       int64_t* offset, vg_dedup_stats* stats, vg_dedup_contained_stats* contained_stats) {
+    return dedup_seqs(ascii, offsets, n, MODE_CONTAINED, representative, strand, offset, stats, contained_stats);
+}
+
+extern "C" int vg_deduplicate_ex(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                                 const char* dup_path, const vg_dedup_params* p, const vg_dedup_options* options) {
+    return deduplicate_files(paths, n_paths, prefixes, out_path, dup_path, p, options && options->circular ? MODE_CIRCULAR : MODE_PLAIN);
+}
 
 extern "C" int vg_deduplicate(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
                               const char* dup_path, const vg_dedup_params* p) {
-    return vg_deduplicate_ex(paths, n_paths, prefixes, out_path, dup_path, p, nullptr);
+    return deduplicate_files(paths, n_paths, prefixes, out_path, dup_path, p, MODE_PLAIN);
+}
+
+extern "C" int vg_deduplicate_contained(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                                        const char* dup_path, const vg_dedup_params* p) {
+    return deduplicate_files(paths, n_paths, prefixes, out_path, dup_path, p, MODE_CONTAINED);
 }
