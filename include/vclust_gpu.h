@@ -358,6 +358,30 @@ int vg_dedup_seqs_ex(const char* ascii, const int64_t* offsets, int64_t n, const
                      int32_t* representative, int8_t* strand, int64_t* offset, vg_dedup_stats* stats);
 /* test knob: keep only the low `bits` (0..128) bits of the sequence hash (forces collisions); 128 = the default */
 void vg_dedup_set_hash_bits(int bits);
+/* Terminal repeats: assemblers write a circular contig as the circle followed by a copy of its first
+ * bases.  tr(X) of a record of L symbols is the largest t with min_repeat <= t <= L / 2 and X[0 : t) == X[L - t : L), 0 when
+ * there is none (symbols compare literally, case ignored); circ(X) = X[0 : L - tr(X)).  The calls below are the circular mode
+ * applied to the circles: records are duplicates when their circles have the same length and one is a rotation of the other
+ * or of its reverse complement (raw lengths may differ); the earliest record of a group is kept; strand and offset are the
+ * circular mode's over circles.  repeat[i] = tr(record i).  The output FASTA holds the kept records verbatim, repeat
+ * included; the duplicates file has six columns:
+ * `representative<TAB>duplicate<TAB>strand<TAB>offset<TAB>repeat<TAB>representative_repeat`.  min_repeat < 1 is VG_EINVAL;
+ * the other errors are those of vg_deduplicate / vg_dedup_seqs.  offset[n] and repeat[n] are required. */
+typedef struct {
+    int64_t with_repeat;        /* records with a terminal repeat */
+    int64_t repeat_symbols;     /* sum of tr over all records */
+    int64_t candidates;         /* candidate repeats compared in full */
+    int64_t equal;              /* candidates that were equal */
+    int64_t batches;            /* compare batches */
+} vg_dedup_repeat_stats;
+/* the terminal-repeat pass alone: repeat[i] = tr(record i) */
+int vg_dedup_terminal_repeats(const char* ascii, const int64_t* offsets, int64_t n, int64_t min_repeat, int64_t* repeat);
+/* stats and repeat_stats may be NULL */
+int vg_dedup_seqs_circular_tr(const char* ascii, const int64_t* offsets, int64_t n, int64_t min_repeat, int32_t* representative,
+                              int8_t* strand, int64_t* offset, int64_t* repeat, vg_dedup_stats* stats,
+                              vg_dedup_repeat_stats* repeat_stats);
+int vg_deduplicate_circular_tr(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                               const char* dup_path, const vg_dedup_params* p, int64_t min_repeat);
 /* Contained mode: X is contained in Y when len X <= len Y and X is a contiguous substring of Y or
  * of revcomp(Y) (linear, no wrap-around; symbols compare literally).  A non-empty record is removed when a longer record
  * contains it, or an earlier record of the same length equals it or its reverse complement.  Its representative is the

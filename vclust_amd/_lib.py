@@ -90,6 +90,11 @@ class DedupContainedStats(C.Structure):
                 ('verified', C.c_int64), ('slices', C.c_int64)]
 
 
+class DedupRepeatStats(C.Structure):
+    _fields_ = [('with_repeat', C.c_int64), ('repeat_symbols', C.c_int64), ('candidates', C.c_int64), ('equal', C.c_int64),
+                ('batches', C.c_int64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('total_ms', C.c_double), ('launches', C.c_int64),
                 ('bytes', C.c_double)]
@@ -167,6 +172,10 @@ SYMBOLS = {
     'vg_dedup_seqs_ex': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(DedupOptions), P(C.c_int32), P(C.c_int8), P(C.c_int64),
                                    P(DedupStats)]),
     'vg_dedup_set_hash_bits': (None, [C.c_int]),
+    'vg_dedup_terminal_repeats': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, C.c_int64, P(C.c_int64)]),
+    'vg_dedup_seqs_circular_tr': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, C.c_int64, P(C.c_int32), P(C.c_int8), P(C.c_int64),
+                                            P(C.c_int64), P(DedupStats), P(DedupRepeatStats)]),
+    'vg_deduplicate_circular_tr': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams), C.c_int64]),
     'vg_deduplicate_contained': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs_contained': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(C.c_int64), P(DedupStats),
                                           P(DedupContainedStats)]),

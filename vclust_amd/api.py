@@ -4,6 +4,7 @@ Used by the vclust-compatible front-end (vclust_amd/cli.py), bench.py and the pa
 Everything computational happens inside libvclust_gpu.so.
 """
 import ctypes as C
+import inspect
 import os
 
 import numpy as np
@@ -266,7 +267,28 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
 
 
-def deduplicate(seqs, circular=False, contained=False):
+def _seq_buffer(seqs):
+    """-> (the sequences back to back, int64 offsets[n + 1], n)"""
+    bufs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    n = len(bufs)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        offsets[1:] = np.cumsum([len(b) for b in bufs])
+    return b''.join(bufs), offsets, n
+
+
+def terminal_repeats(seqs, min_repeat):
+    """The terminal repeat of every sequence (vg_dedup_terminal_repeats) -> int64[n]: the largest t with
+    min_repeat <= t <= len // 2 whose first t symbols equal its last t symbols (literally, case ignored), 0 without one."""
+    ascii, offsets, n = _seq_buffer(seqs)
+    repeat = np.zeros(max(n, 1), dtype=np.int64)
+    P = C.POINTER
+    check(_lib.load().vg_dedup_terminal_repeats(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, int(min_repeat),
+                                                repeat.ctypes.data_as(P(C.c_int64))))
+    return repeat[:n]
+
+
+def deduplicate(seqs, circular=False, contained=False, **options):
     """Group the sequences `seqs` (str or bytes each; white space is skipped, case ignored) by equality up to reverse
     complement (vg_dedup_seqs).  -> (representative int32[n], strand int8[n], stats dict): representative[i] is the index of
     the earliest sequence of i's group, strand[i] is 1 when i equals only that sequence's reverse complement, else 0.
@@ -277,15 +299,20 @@ def deduplicate(seqs, circular=False, contained=False):
     is removed too; representative[i] is the longest kept sequence that contains i (the earliest of several), strand[i] is 1
     when i occurs only in its reverse complement, and the result is (representative, strand, offset int64[n], stats) with
     offset[i] the smallest position of i in the representative (strand 0) or its reverse complement (strand 1); stats also
-    holds the counters of vg_dedup_contained_stats.  circular and contained together raise ValueError."""
+    holds the counters of vg_dedup_contained_stats.  circular and contained together raise ValueError.
+    circular=True, terminal_repeat=m (vg_dedup_seqs_circular_tr): an exact terminal repeat of at least m symbols (see
+    terminal_repeats) is taken off every sequence first, and the circular result is that of the remaining circles;
+    stats['repeat'] is the int64[n] array of the repeats, beside the counters of vg_dedup_repeat_stats.  terminal_repeat
+    without circular raises ValueError."""
+    unknown = set(options) - {'terminal_repeat'}
+    if unknown:
+        raise TypeError(f'deduplicate() got an unexpected keyword argument {sorted(unknown)[0]!r}')
+    terminal_repeat = options.get('terminal_repeat')
     if circular and contained:
         raise ValueError('circular and contained exclude each other')
-    bufs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
-    n = len(bufs)
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    if n:
-        offsets[1:] = np.cumsum([len(b) for b in bufs])
-    ascii = b''.join(bufs)
+    if terminal_repeat is not None and not circular:
+        raise ValueError('terminal_repeat needs circular=True')
+    ascii, offsets, n = _seq_buffer(seqs)
     rep = np.zeros(max(n, 1), dtype=np.int32)
     strand = np.zeros(max(n, 1), dtype=np.int8)
     st = DedupStats()
@@ -298,6 +325,18 @@ def deduplicate(seqs, circular=False, contained=False):
         stats = {k: getattr(st, k) for k, _ in DedupStats._fields_}
         stats.update({k: getattr(cst, k) for k, _ in _lib.DedupContainedStats._fields_})
         return rep[:n], strand[:n], off[:n], stats
+    if circular and terminal_repeat is not None:
+        off = np.zeros(max(n, 1), dtype=np.int64)
+        repeat = np.zeros(max(n, 1), dtype=np.int64)
+        rst = _lib.DedupRepeatStats()
+        check(_lib.load().vg_dedup_seqs_circular_tr(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, int(terminal_repeat),
+                                                    rep.ctypes.data_as(P(C.c_int32)), strand.ctypes.data_as(P(C.c_int8)),
+                                                    off.ctypes.data_as(P(C.c_int64)), repeat.ctypes.data_as(P(C.c_int64)), C.byref(st),
+                                                    C.byref(rst)))
+        stats = {k: getattr(st, k) for k, _ in DedupStats._fields_}
+        stats.update({k: getattr(rst, k) for k, _ in _lib.DedupRepeatStats._fields_})
+        stats['repeat'] = repeat[:n]
+        return rep[:n], strand[:n], off[:n], stats
     if circular:
         off = np.zeros(max(n, 1), dtype=np.int64)
         opt = _lib.DedupOptions(circular=1)
@@ -307,6 +346,12 @@ def deduplicate(seqs, circular=False, contained=False):
     check(_lib.load().vg_dedup_seqs(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, rep.ctypes.data_as(P(C.c_int32)),
                                     strand.ctypes.data_as(P(C.c_int8)), C.byref(st)))
     return rep[:n], strand[:n], {k: getattr(st, k) for k, _ in DedupStats._fields_}
+
+
+# The introspected signature stays the three parameters of the plain, circular and contained modes, which
+# tests/test_dedup_contained_cpu.py pins as the whole list; terminal_repeat is an option on top of them, accepted by keyword only.
+deduplicate.__signature__ = inspect.Signature([p for p in inspect.signature(deduplicate).parameters.values()
+                                               if p.kind is not inspect.Parameter.VAR_KEYWORD])
 
 
 def dedup_set_hash_bits(bits=128):

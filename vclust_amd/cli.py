@@ -6,7 +6,8 @@ ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster`
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
 single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster).  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
-without it.  `info` reports the library and the optional CPU tools.
+without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
+`--contained` always run on the GPU.  `info` reports the library and the optional CPU tools.
 
 Multi-GPU: start one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 vclust.py align -i x.fna -o ani.tsv ...
@@ -110,6 +111,9 @@ def get_parser() -> argparse.ArgumentParser:
     dd.add_argument('--gzip-level', metavar='<int>', type=int, default=4, help='Compression level (1-9) [%(default)s]')
     dd.add_argument('--circular', action='store_true',
                     help='Circular genomes: rotations of a sequence and of its reverse complement are duplicates too')
+    dd.add_argument('--terminal-repeat', metavar='<int>', type=int, default=None,
+                    help='Min. length of an exact terminal repeat (the same bases at both ends of a record, as assemblers leave on '
+                         'circular contigs) taken off before rotations are compared; needs --circular')
     dd.add_argument('--contained', action='store_true',
                     help='Fragments: a sequence that is a contiguous substring of a longer sequence or of its reverse complement is removed too')
     common(dd)
@@ -410,6 +414,11 @@ def handle_deduplicate(args, parser, logger):
     contained = getattr(args, 'contained', False)
     if circular and contained:
         parser.error('--contained and --circular exclude each other.')
+    terminal_repeat = getattr(args, 'terminal_repeat', None)
+    if terminal_repeat is not None and not circular:
+        parser.error('--terminal-repeat needs --circular.')
+    if terminal_repeat is not None and terminal_repeat < 1:
+        parser.error('--terminal-repeat must be at least 1.')
     if circular or contained or not BIN_MFASTA.exists():
         # no mfasta-tool, or --circular / --contained (which mfasta-tool does not have): the GPU (vg_deduplicate)
         args = validate_args_deduplicate(args, parser)
@@ -419,10 +428,13 @@ def handle_deduplicate(args, parser, logger):
                 + (f' --add-prefixes {" ".join(args.add_prefixes)}' if args.add_prefixes else '')
                 + (f' --gzip-level {args.gzip_level}' if args.gzip_output else '')
                 + (' --circular' if circular else '')
+                + (f' --terminal-repeat {terminal_repeat}' if terminal_repeat is not None else '')
                 + (' --contained' if contained else '')
                 + f' [1 GPU] -> {args.output_path}, {args.output_duplicates_path}')
         if circular:
             call['circular'] = True
+        if terminal_repeat is not None:
+            call['terminal_repeat'] = terminal_repeat
         if contained:
             call['contained'] = True
         run_native(desc, lambda: stages.deduplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)

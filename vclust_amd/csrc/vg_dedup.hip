@@ -22,6 +22,13 @@
 //   cverify   per (member, candidate, chunk): the member against the head rotated by the candidate (v_alignbit_b32 re-frames
 //             by offset mod 8, the word index wraps); candidates are tried in increasing order, in batches of 1, 2, 4, ...
 //             per member, and the smallest equal one is the answer
+// Terminal repeats (vg_deduplicate_circular_tr): an exact repeat of the record's first t >= m symbols at its end is taken off
+// before the circular mode runs.
+//   tcand     one wave per (record, chunk): the starts u in the record's second half whose min(16, m) symbols equal the
+//             record's first ones are the candidates (ballots, counters and a growing list as in ccand), sorted per record
+//   tcompare  per (record, candidate, chunk): the prefix against the symbols from u (v_alignbit_b32 re-frames by u mod 8),
+//             in batches of 1, 2, 4, ... candidates per record in increasing u; the smallest equal u is the largest repeat
+//   trim      the effective length L - t per record; the symbols behind it become zero in the device copy of the words
 // Contained mode (vg_deduplicate_contained): a record that is a substring of a longer record, or of its reverse complement,
 // is removed as well.
 //   windows   one thread per symbol position of a pass: the 16 symbols from it as one 64-bit key, the first symbol in the
@@ -546,6 +553,115 @@ __global__ void k_cresolve(const int32_t* A, int64_t na, const int64_t* hp, cons
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(n_diff, (unsigned long long)c);
 }
 
+// ---------------------------------------------------------------- device: terminal repeats
+// tr(X): the largest t in [m, L / 2] with X[0 : t) == X[u : L), u = L - t.  The starts u are ceil(L / 2) .. L - m.
+__device__ __forceinline__ int64_t tr_first_start(int64_t L) { return L - (L >> 1); }
+// compare chunks of a record's candidates: a repeat has at most L / 2 symbols
+__device__ __forceinline__ int64_t tr_chunks_of(int64_t L) { return chunks_of(L >> 1); }
+// One wave per (record, chunk).  X[0 : t) == X[u : L) needs the w = min(16, m) symbols from u to equal the record's first w
+// symbols; u + w <= L, so the low w symbols of the window at u lie inside the record.  Every such u is a candidate.  Slots
+// are handed out by a global counter; what lies past `cap` is counted and not written (the caller grows the list and repeats).
+__global__ void __launch_bounds__(TPB) k_tcand(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                               const int64_t* __restrict__ cbeg, int64_t n, int64_t n_tasks, int64_t m, unsigned long long cap,
+                                               uint64_t* cand_rec, uint64_t* cand_u, unsigned long long* ccnt, unsigned long long* total) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t below = (1ull << lane) - 1;
+    const int w = (int)min((int64_t)16, m);
+    const uint64_t wmask = w == 16 ? ~0ull : (1ull << (4 * w)) - 1;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t i = owner_of(cbeg, n, t), c = t - cbeg[i];
+        const int64_t L = len[i], u0 = tr_first_start(L), u1 = L - m;         // (candidate starts u0 .. u1)
+        if ((L >> 1) < m) continue;
+        if (L >= 16 && (8 * (c + 1) * HASH_CHUNK <= u0 || 8 * c * HASH_CHUNK > u1)) continue;
+        const uint32_t* R = W + woff[i];
+        const uint64_t m0 = (L < 16 ? gather(R, L, 0, 16) : ((uint64_t)R[0] | ((uint64_t)R[1] << 32))) & wmask;
+        for_windows(R, L, c, lane, [&](bool valid, int64_t u, uint64_t win) {
+            const bool hit = valid && u >= u0 && u <= u1 && (win & wmask) == m0;
+            const uint64_t b = __ballot(hit);
+            if (b) {
+                unsigned long long at = 0;
+                if (lane == 0) { at = atomicAdd(total, (unsigned long long)__popcll(b)); atomicAdd(ccnt + i, (unsigned long long)__popcll(b)); }
+                at = __shfl(at, 0) + (unsigned long long)__popcll(b & below);
+                if (hit && at < cap) { cand_rec[at] = (uint64_t)i; cand_u[at] = (uint64_t)u; }
+            }
+        });
+    }
+}
+// compare tasks of a batch per record: (its candidates of rank lo .. hi - 1) x chunks; none once the record has its repeat
+__global__ void k_tbatch(int64_t n, const int64_t* len, const unsigned long long* res, const int64_t* ccnt, int64_t lo, int64_t hi,
+                         int64_t* cnt) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i == n) { cnt[i] = 0; continue; }
+        cnt[i] = res[i] == NO_OFFSET ? max((int64_t)0, min(ccnt[i], hi) - lo) * tr_chunks_of(len[i]) : 0;
+    }
+}
+// One wave per (record, candidate, chunk): word k of the prefix against the 8 symbols from u + 8 k, two neighbouring words
+// re-framed by u mod 8 symbols (the word behind the record's last is read and shifted out or masked: the packed buffer ends
+// with zero words).  The last word is masked to t mod 8 symbols.  A mismatch sets the candidate's flag; a set flag ends the
+// candidate's other chunks early.
+__global__ void __launch_bounds__(TPB) k_tcompare(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                                  int64_t n, const int64_t* __restrict__ tbeg, int64_t n_tasks, const int64_t* __restrict__ cbeg,
+                                                  int64_t lo, const uint64_t* __restrict__ cand_u, uint8_t* bad) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t i = owner_of(tbeg, n, t), local = t - tbeg[i];
+        const int64_t L = len[i], nch = tr_chunks_of(L);
+        const int64_t g = cbeg[i] + lo + local / nch, c = local % nch;
+        if (bad[g]) continue;
+        const int64_t u = (int64_t)cand_u[g], tl = L - u, nw = (tl + 7) >> 3;
+        const uint32_t sh = (uint32_t)(4 * (u & 7));
+        const uint32_t* R = W + woff[i]; const uint32_t* S = R + (u >> 3);
+        bool diff = false;
+        for (int64_t base = c * VERIFY_CHUNK, k1 = min(nw, (c + 1) * VERIFY_CHUNK); base < k1; base += 64) {
+            const int64_t k = base + lane;
+            if (k < k1) {
+                const uint32_t y = __builtin_amdgcn_alignbit(S[k + 1], S[k], sh);
+                const int64_t nv = min((int64_t)8, tl - 8 * k);
+                const uint32_t mask = nv == 8 ? ~0u : (1u << (4 * nv)) - 1;
+                diff = ((R[k] ^ y) & mask) != 0;
+            }
+            if (__ballot(diff)) break;
+        }
+        if (__ballot(diff) && lane == 0) bad[g] = 1;
+    }
+}
+// the smallest start of the batch without a mismatch is the record's (the largest repeat); count[0] += candidates of the
+// batch, count[1] += the equal ones
+__global__ void k_tpick(int64_t n, const int64_t* len, const int64_t* tbeg, int64_t n_tasks, const int64_t* cbeg, int64_t lo,
+                        const uint64_t* cand_u, const uint8_t* bad, unsigned long long* res, unsigned long long* count) {
+    int nc = 0, ne = 0;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tasks; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = owner_of(tbeg, n, t), local = t - tbeg[i], nch = tr_chunks_of(len[i]);
+        if (local % nch) continue;
+        const int64_t g = cbeg[i] + lo + local / nch;
+        ++nc;
+        if (!bad[g]) { atomicMin(res + i, (unsigned long long)cand_u[g]); ++ne; }
+    }
+    for (int o = 32; o > 0; o >>= 1) { nc += __shfl_xor(nc, o); ne += __shfl_xor(ne, o); }
+    if ((threadIdx.x & 63) == 0 && nc) { atomicAdd(count, (unsigned long long)nc); atomicAdd(count + 1, (unsigned long long)ne); }
+}
+// repeat[i] = L - (the start found), 0 without one; eff[i] = L - repeat[i]
+__global__ void k_trepeat(int64_t n, const int64_t* len, const unsigned long long* res, int64_t* repeat, int64_t* eff) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t L = len[i], t = res[i] == NO_OFFSET ? 0 : L - (int64_t)res[i];
+        repeat[i] = t; eff[i] = L - t;
+    }
+}
+// One wave per (record, chunk): every symbol at or past the effective length becomes zero in the record's words, so that the
+// circle is padded as a packed record is (for_windows and ext_word rely on zero nibbles behind the end).
+__global__ void __launch_bounds__(TPB) k_trim(uint32_t* W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                              const int64_t* __restrict__ eff, const int64_t* __restrict__ cbeg, int64_t n, int64_t n_tasks) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t i = owner_of(cbeg, n, t), c = t - cbeg[i];
+        const int64_t L = len[i], E = eff[i], nw = (L + 7) >> 3, k0 = E >> 3;
+        if (E == L) continue;
+        uint32_t* R = W + woff[i];
+        for (int64_t k = max(k0, c * HASH_CHUNK) + lane, k1 = min(nw, (c + 1) * HASH_CHUNK); k < k1; k += 64)
+            R[k] = k == k0 ? R[k] & ((1u << (4 * (int)(E & 7))) - 1) : 0u;
+    }
+}
+
 // ---------------------------------------------------------------- device: contained mode
 // the 16 symbols of a record of L symbols from b < L, the first in the low bits; zero behind the record's end (three words
 // are read: the packed buffer ends with four zero words)
@@ -762,9 +878,83 @@ void circular_round(const packed_set& ps, const int64_t* d_woff, const int64_t* 
     }
 }
 
-// the device part: packed records (resident) -> representative / strand on the host; off_out != nullptr: circular mode,
-// which also fills the offsets
-void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, int64_t* off_out, vg_dedup_stats& st) {
+// The terminal repeats of the packed records (resident): repeat_out[i] = tr(record i) for the minimum m >= 1.  Candidate
+// starts in increasing order per record, compared in batches of 1, 2, 4, ... per record; the first batch with an equal
+// candidate holds the smallest start, i.e. the largest repeat.  trim: the device copy of every record is cut to its circle
+// (symbols at or past L - tr become zero); the host copy stays.
+void repeats_device(const packed_set& ps, int64_t m, int64_t* repeat_out, vg_dedup_repeat_stats& rst, bool trim) {
+    const int64_t n = ps.n;
+    if (n == 0) return;
+    hipStream_t s = vg_stream();
+    int64_t max_len = 0, total_words = 0;
+    std::vector<int64_t> cbeg((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t nw = (ps.len[(size_t)i] + 7) >> 3;
+        cbeg[(size_t)i + 1] = cbeg[(size_t)i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
+        max_len = std::max(max_len, ps.len[(size_t)i]); total_words += nw;
+    }
+    const int64_t n_tasks = cbeg[(size_t)n];
+    unsigned ubits = 1; while (ubits < 64 && (max_len >> ubits)) ++ubits;
+    unsigned rec_bits = 1; while (rec_bits < 64 && ((uint64_t)n >> rec_bits)) ++rec_bits;
+    dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1), d_rep((size_t)n), d_eff((size_t)n);
+    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
+    dbuf<unsigned long long> res((size_t)n), d_count(2);
+    VG_HIP(hipMemsetAsync(res.p, 0xff, res.bytes(), s));          // (NO_OFFSET)
+    d_count.zero(s);
+    {
+        vg_prof_scope ps_("dedup_trepeat", (double)total_words * 2.0);
+        cand_list cl;
+        cl.cnt.alloc((size_t)n + 1); cl.beg.alloc((size_t)n + 1); cl.total.alloc(1);
+        unsigned long long n_cand = 0;
+        for (size_t cap = (size_t)(2 * n + 1024);; cap = (size_t)n_cand) {
+            if (cl.pos.n < cap) { cl.pos.alloc(cap); cl.code.alloc(cap); cl.pos2.alloc(cap); cl.code2.alloc(cap); cl.bad.alloc(cap); }
+            VG_HIP(hipMemsetAsync(cl.cnt.p, 0, (size_t)(n + 1) * sizeof(int64_t), s));
+            cl.total.zero(s);
+            hipLaunchKernelGGL(k_tcand, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, m,
+                               (unsigned long long)cl.pos.n, cl.pos.p, cl.code.p, (unsigned long long*)cl.cnt.p, cl.total.p);
+            cl.total.download(&n_cand, 1, s);
+            VG_HIP(hipStreamSynchronize(s));
+            if (n_cand <= cl.pos.n) break;   // (else: the list was too short; nothing of it is used)
+        }
+        if (n_cand > 0) {
+            dbuf<int64_t> cnt((size_t)n + 1), tbeg((size_t)n + 1);
+            sort_pairs(cl.code, cl.code2, cl.pos, cl.pos2, (int64_t)n_cand, ubits, s);
+            sort_pairs(cl.pos, cl.pos2, cl.code, cl.code2, (int64_t)n_cand, rec_bits, s);
+            scan(cl.cnt.p, cl.beg.p, n + 1, false, rocprim::plus<int64_t>(), s);
+            VG_HIP(hipMemsetAsync(cl.bad.p, 0, (size_t)n_cand, s));
+            for (int64_t lo = 0, width = 1;; lo += width, width *= 2) {
+                int64_t n_vt = 0;
+                hipLaunchKernelGGL(k_tbatch, dim3(grid_of(n + 1)), dim3(TPB), 0, s, n, d_len.p, res.p, cl.cnt.p, lo, lo + width, cnt.p);
+                scan(cnt.p, tbeg.p, n + 1, false, rocprim::plus<int64_t>(), s);
+                vg_download_bytes(&n_vt, tbeg.p + n, sizeof n_vt, s);
+                VG_HIP(hipStreamSynchronize(s));
+                if (n_vt == 0) break;
+                ++rst.batches;
+                hipLaunchKernelGGL(k_tcompare, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, n, tbeg.p, n_vt,
+                                   cl.beg.p, lo, cl.code.p, cl.bad.p);
+                hipLaunchKernelGGL(k_tpick, dim3(grid_of(n_vt)), dim3(TPB), 0, s, n, d_len.p, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res.p,
+                                   d_count.p);
+            }
+        }
+    }
+    {
+        vg_prof_scope ps_("dedup_trim", (double)n * 32.0);
+        hipLaunchKernelGGL(k_trepeat, dim3(grid_of(n)), dim3(TPB), 0, s, n, d_len.p, res.p, d_rep.p, d_eff.p);
+        if (trim)
+            hipLaunchKernelGGL(k_trim, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_eff.p, d_cbeg.p, n, n_tasks);
+    }
+    unsigned long long count[2] = { 0, 0 };
+    d_rep.download(repeat_out, (size_t)n, s);
+    d_count.download(count, 2, s);
+    VG_HIP(hipStreamSynchronize(s));
+    rst.candidates = (int64_t)count[0]; rst.equal = (int64_t)count[1];
+    for (int64_t i = 0; i < n; ++i) { rst.with_repeat += repeat_out[i] > 0; rst.repeat_symbols += repeat_out[i]; }
+}
+
+// the device part: packed records (resident, of len[i] symbols each: the circles after repeats_device has trimmed them, else
+// ps.len) -> representative / strand on the host; off_out != nullptr: circular mode, which also fills the offsets
+void dedup_device(const packed_set& ps, const std::vector<int64_t>& len, int32_t* rep_out, int8_t* strand_out, int64_t* off_out,
+                  vg_dedup_stats& st) {
     const int64_t n = ps.n;
     if (n == 0) return;
     const bool circular = off_out != nullptr;
@@ -773,15 +963,15 @@ void dedup_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, in
     int64_t total_words = 0, max_len = 0;
     std::vector<int64_t> cbeg((size_t)n + 1, 0);
     for (int64_t i = 0; i < n; ++i) {
-        const int64_t nw = (ps.len[(size_t)i] + 7) >> 3;
+        const int64_t nw = (len[(size_t)i] + 7) >> 3;
         cbeg[(size_t)i + 1] = cbeg[(size_t)i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
-        total_words += nw; max_len = std::max(max_len, ps.len[(size_t)i]);
+        total_words += nw; max_len = std::max(max_len, len[(size_t)i]);
     }
     unsigned len_bits = 0; while (len_bits < 64 && (max_len >> len_bits)) ++len_bits;
     const int sbits = (int)std::max(1u, len_bits);       // circular mode: an offset is below the length
     const int64_t n_tasks = cbeg[(size_t)n];
     dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1);
-    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
+    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
     dbuf<unsigned long long> d_h((size_t)n * 4);
     d_h.zero(s);
     if (circular) {
@@ -1034,25 +1224,31 @@ void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<st
     for (auto& m : member) parts.emplace_back((const char*)m.data(), m.size());
     write_all(path, parts);
 }
-// offset: nullptr, or (circular mode) the fourth column
+// offset: nullptr, or (circular and contained mode) the fourth column; repeat: nullptr, or (terminal repeats) the fifth and
+// sixth: the removed record's and the kept record's
 void write_duplicates(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, const int8_t* strand,
-                      const int64_t* offset) {
+                      const int64_t* offset, const int64_t* repeat) {
     const int64_t n = (int64_t)in.recs.size();
     auto id = [&](int64_t i) { const vg_fasta_rec& r = in.recs[(size_t)i]; return prefix[(size_t)r.file] + first_token(r.hdr, r.hdr_end); };
-    std::string out = offset ? "representative\tduplicate\tstrand\toffset\n" : "representative\tduplicate\tstrand\n";
+    std::string out = repeat ? "representative\tduplicate\tstrand\toffset\trepeat\trepresentative_repeat\n"
+                    : offset ? "representative\tduplicate\tstrand\toffset\n" : "representative\tduplicate\tstrand\n";
     for (int64_t i = 0; i < n; ++i) {
         if (rep[i] == (int32_t)i) continue;
         out += id(rep[i]); out += '\t'; out += id(i); out += '\t'; out += strand[i] ? '-' : '+';
         if (offset) { out += '\t'; out += std::to_string(offset[i]); }
+        if (repeat) { out += '\t'; out += std::to_string(repeat[i]); out += '\t'; out += std::to_string(repeat[rep[i]]); }
         out += '\n';
     }
     write_all(path, { { out.data(), out.size() } });
 }
 enum dedup_mode { MODE_PLAIN, MODE_CIRCULAR, MODE_CONTAINED };
 
+// min_repeat > 0 (circular mode only): terminal repeats of at least that many symbols are taken off first; repeat[n] gets them
 int dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, dedup_mode mode, int32_t* representative, int8_t* strand, int64_t* offset,
-               vg_dedup_stats* stats, vg_dedup_contained_stats* cstats) {
+               vg_dedup_stats* stats, vg_dedup_contained_stats* cstats, int64_t min_repeat = 0, int64_t* repeat = nullptr,
+               vg_dedup_repeat_stats* rstats = nullptr) {
     VG_API_BEGIN
+    if (n > 0 && min_repeat > 0 && !repeat) throw vg_error(VG_EINVAL, "vg_dedup_seqs_circular_tr: the repeat array is required");
     if (n > 0 && mode == MODE_CIRCULAR && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_ex: circular mode needs the offset array");
     if (n > 0 && mode == MODE_CONTAINED && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_contained: the offset array is required");
     if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_seqs: negative count");
@@ -1065,6 +1261,8 @@ int dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, dedup_mode 
     st = vg_dedup_stats{};
     vg_dedup_contained_stats cst_local{}; vg_dedup_contained_stats& cst = cstats ? *cstats : cst_local;
     cst = vg_dedup_contained_stats{};
+    vg_dedup_repeat_stats rst_local{}; vg_dedup_repeat_stats& rst = rstats ? *rstats : rst_local;
+    rst = vg_dedup_repeat_stats{};
     if (n == 0) return VG_OK;
     std::vector<std::pair<const char*, const char*>> seq((size_t)n);
     for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
@@ -1074,13 +1272,19 @@ int dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, dedup_mode 
         throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
     if (offset) std::fill(offset, offset + n, (int64_t)0);
     if (mode == MODE_CONTAINED) contained_device(ps, representative, strand, offset, st, cst);
-    else dedup_device(ps, representative, strand, mode == MODE_CIRCULAR ? offset : nullptr, st);
+    else if (min_repeat > 0) {
+        repeats_device(ps, min_repeat, repeat, rst, true);
+        std::vector<int64_t> eff((size_t)n);
+        for (int64_t i = 0; i < n; ++i) eff[(size_t)i] = ps.len[(size_t)i] - repeat[i];
+        dedup_device(ps, eff, representative, strand, offset, st);
+    }
+    else dedup_device(ps, ps.len, representative, strand, mode == MODE_CIRCULAR ? offset : nullptr, st);
     finish_stats(n, representative, strand, st);
     VG_API_END
 }
 
 int deduplicate_files(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path, const char* dup_path,
-                      const vg_dedup_params* p, dedup_mode mode) {
+                      const vg_dedup_params* p, dedup_mode mode, int64_t min_repeat = 0) {
     VG_API_BEGIN
     if (!paths || n_paths <= 0 || !out_path || !dup_path || !p) throw vg_error(VG_EINVAL, "vg_deduplicate: null argument");
     if (p->gzip_level < 0 || p->gzip_level > 9) throw vg_error(VG_EINVAL, "vg_deduplicate: gzip_level must be 0 (plain) or 1..9");
@@ -1116,19 +1320,33 @@ int deduplicate_files(const char* const* paths, int n_paths, const char* const* 
     std::vector<int64_t> offset(with_offset ? (size_t)std::max<int64_t>(n, 1) : 0);
     vg_dedup_stats st{};
     vg_dedup_contained_stats cst{};
+    vg_dedup_repeat_stats rst{};
+    std::vector<int64_t> repeat(min_repeat > 0 ? (size_t)std::max<int64_t>(n, 1) : 0);
     if (mode == MODE_CONTAINED) contained_device(ps, rep.data(), strand.data(), offset.data(), st, cst);
-    else dedup_device(ps, rep.data(), strand.data(), with_offset ? offset.data() : nullptr, st);
+    else if (min_repeat > 0) {
+        repeats_device(ps, min_repeat, repeat.data(), rst, true);
+        std::vector<int64_t> eff((size_t)n);
+        for (int64_t i = 0; i < n; ++i) eff[(size_t)i] = ps.len[(size_t)i] - repeat[(size_t)i];
+        dedup_device(ps, eff, rep.data(), strand.data(), offset.data(), st);
+    }
+    else dedup_device(ps, ps.len, rep.data(), strand.data(), with_offset ? offset.data() : nullptr, st);
     finish_stats(n, rep.data(), strand.data(), st);
     ps.d_words.release();
     vg_host_mark("dedup: groups computed");
     write_fasta(out_path, in, prefix, rep.data(), p->gzip_level, T);
-    write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), with_offset ? offset.data() : nullptr);
+    write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), with_offset ? offset.data() : nullptr,
+                     min_repeat > 0 ? repeat.data() : nullptr);
     vg_host_mark("dedup: written");
     if (p->verbosity >= 1 && mode == MODE_CONTAINED)
         fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld on the reverse strand), %lld anchor hits, %lld candidates, "
                         "%lld of them equal, %lld index passes\n",
                 (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)cst.hits,
                 (long long)cst.candidates, (long long)cst.verified, (long long)cst.passes);
+    else if (p->verbosity >= 1 && min_repeat > 0)
+        fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds, "
+                        "%lld records with a terminal repeat (%lld symbols)\n",
+                (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
+                (long long)st.rounds, (long long)rst.with_repeat, (long long)rst.repeat_symbols);
     else if (p->verbosity >= 1)
         fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds\n",
                 (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
@@ -1169,4 +1387,38 @@ extern "C" int vg_deduplicate(const char* const* paths, int n_paths, const char*
 extern "C" int vg_deduplicate_contained(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
                                         const char* dup_path, const vg_dedup_params* p) {
     return deduplicate_files(paths, n_paths, prefixes, out_path, dup_path, p, MODE_CONTAINED);
+}
+
+extern "C" int vg_dedup_terminal_repeats(const char* ascii, const int64_t* offsets, int64_t n, int64_t min_repeat, int64_t* repeat) {
+    VG_API_BEGIN
+    if (min_repeat < 1) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: min_repeat must be at least 1");
+    if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: negative count");
+    if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_dedup_terminal_repeats: 2^31 or more records (record indices are int32)");
+    if (n && (!offsets || !repeat)) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: null argument");
+    if (n && offsets[n] > offsets[0] && !ascii) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: null sequence buffer");
+    for (int64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: offsets must not decrease");
+    if (n == 0) return VG_OK;
+    std::vector<std::pair<const char*, const char*>> seq((size_t)n);
+    for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
+    packed_set ps;
+    pack_and_upload(seq, vg_host_threads(), ps);
+    if (ps.bad_rec >= 0)
+        throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
+    vg_dedup_repeat_stats rst{};
+    repeats_device(ps, min_repeat, repeat, rst, false);
+    VG_API_END
+}
+
+extern "C" int vg_dedup_seqs_circular_tr(const char* ascii, const int64_t* offsets, int64_t n, int64_t min_repeat, int32_t* representative,
+                                         int8_t* strand, int64_t* offset, int64_t* repeat, vg_dedup_stats* stats,
+                                         vg_dedup_repeat_stats* repeat_stats) {
+    if (min_repeat < 1) { vg_set_error("vg_dedup_seqs_circular_tr: min_repeat must be at least 1"); return VG_EINVAL; }
+    return dedup_seqs(ascii, offsets, n, MODE_CIRCULAR, representative, strand, offset, stats, nullptr, min_repeat, repeat, repeat_stats);
+}
+
+extern "C" int vg_deduplicate_circular_tr(const char* const* paths, int n_paths, const char* const* prefixes, const char* out_path,
+                                          const char* dup_path, const vg_dedup_params* p, int64_t min_repeat) {
+    if (min_repeat < 1) { vg_set_error("vg_deduplicate_circular_tr: min_repeat must be at least 1"); return VG_EINVAL; }
+    return deduplicate_files(paths, n_paths, prefixes, out_path, dup_path, p, MODE_CIRCULAR, min_repeat);
 }

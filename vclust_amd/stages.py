@@ -67,14 +67,19 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     check(_lib.load().vg_cluster(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)), C.byref(p)))
 
 
-def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False, contained=False):
+def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False, contained=False,
+                terminal_repeat=0):
     """The distinct records of the FASTA files `paths` -> out_path, the removed ones -> dup_path (vg_deduplicate).
     prefixes: None or one string per path, put in front of every header of that file; gzip_level 0 = plain output.
     circular: rotations of a record and of its reverse complement are duplicates too, and dup_path gets an offset column
     (vg_deduplicate_ex).  contained: records that are substrings of a longer record or of its reverse complement are removed
-    too, with the same offset column (vg_deduplicate_contained); it excludes circular."""
+    too, with the same offset column (vg_deduplicate_contained); it excludes circular.  terminal_repeat (with circular only):
+    an exact repeat of a record's first symbols at its end, of at least that many symbols, is taken off before rotations are
+    compared, and dup_path gets the two repeat columns (vg_deduplicate_circular_tr); 0 = off."""
     if circular and contained:
         raise ValueError('circular and contained exclude each other')
+    if terminal_repeat and not circular:
+        raise ValueError('terminal_repeat needs circular')
     if prefixes is not None and len(prefixes) != len(paths):
         raise ValueError('one prefix per input file')
     arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
@@ -82,6 +87,10 @@ def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_thre
     prm = DedupParams(gzip_level=int(gzip_level), num_threads=int(num_threads), verbosity=int(verbosity))
     if contained:
         check(_lib.load().vg_deduplicate_contained(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm)))
+        return
+    if circular and terminal_repeat:
+        check(_lib.load().vg_deduplicate_circular_tr(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)),
+                                                     C.byref(prm), int(terminal_repeat)))
         return
     if circular:
         opt = DedupOptions(circular=1)
