@@ -310,6 +310,36 @@ int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path,
 int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_edges,
                      int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats);
 
+/* Single-linkage merge table and multi-level cuts (this repository's; DESIGN.md section 9, "Merge table").  The graph is the
+ * one above.  Edge {a, b} (a < b) of weight w has the key (-w, a, b), weights compared as doubles with -0.0 = +0.0: a strict
+ * total order.  Kruskal over the edges in key order; an edge whose ends lie in different clusters is a merge, and there are
+ * n_objects - (number of components) of them: the maximum spanning forest, computed on the device.  Objects are nodes
+ * 0 .. n_objects - 1 and merge k (from 0) creates node n_objects + k.  The cut at level t joins the merges with w >= t; its
+ * labels and representatives follow the rule of vg_cluster_graph, and it equals `single` on the rows with w >= t. */
+typedef struct {
+    int64_t rounds;             /* Boruvka rounds launched (the last one finds no leaving edge) */
+    int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
+    int64_t n_merges;           /* forest edges = n_objects - components */
+} vg_linkage_stats;
+/* The merge table of the rows (validated as vg_cluster_graph validates them, before any device use).  Every output array is the
+ * caller's and has n_objects - 1 entries (they may be NULL when n_objects <= 1); *n_merges of them are written, in merge order:
+ * the edge (object_a < object_b, weight), the two nodes merged (node_a < node_b) and the members of the new node.  stats may be
+ * NULL.  No device is VG_ENODEV, n_objects >= 2^31 VG_EOVERFLOW. */
+int vg_cluster_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                             int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
+                             int64_t* size, int64_t* n_merges, vg_linkage_stats* stats);
+/* The cuts of ONE forest at levels[0 .. n_levels): label and representative hold n_levels rows of n_objects entries each, in the
+ * order of the levels (any order, repeats allowed; a NaN level is VG_EINVAL). */
+int vg_cluster_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                            const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats);
+/* File to file, with the host parse and the error messages of vg_cluster; p->algorithm must be VG_CLUSTER_SINGLE (else
+ * VG_EINVAL).  out_path: clusters.tsv of vg_cluster (the cut at the metric's floor) plus one column per level, headed
+ * `<metric>_<%g of the level>`, labels or -- with p->representatives -- representative ids; a level below the metric's minimum
+ * is VG_EINVAL.  linkage_path (may be NULL): header `node_a node_b similarity size object_a object_b` (tab-separated), one line
+ * per merge, similarity printed with %.6g. */
+int vg_cluster_linkage(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
+                       const char* linkage_path, const double* levels, int n_levels);
+
 /* ------------------------------------------------------------------ deduplicate ------- */
 /* The first stage: FASTA files -> one FASTA of the distinct sequences + a duplicates list, in place of mfasta-tool
  * (cmd_mfasta_deduplicate, vclust.py:810-866, run at vclust.py:1351); DESIGN.md section 10 is the contract.  A record's sequence is its lines

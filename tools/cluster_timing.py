@@ -1,11 +1,13 @@
 """Timing of the cluster stage (vg_cluster / vg_cluster_graph), per algorithm: host parse, GPU time per kernel (profile
 table), rounds, objects finished by the tail sweep, end-to-end wall time.
 
-  python tools/cluster_timing.py [--sizes 100000 1000000] [--ani ani.tsv --ids ani.ids.tsv] [--metric tani --min 0.95]
+  python tools/cluster_timing.py [--sizes 100000 1000000] [--ani ani.tsv --ids ani.ids.tsv] [--metric tani --min 0.95] [--linkage]
 
 Synthetic graphs: families of 20-200 objects in index order, ~50 rows per object (both directions, ~25 distinct
 neighbours), weights 0.80-1.00 inside families and a few weak rows between them.  With --ani, the file is also clustered
-through the whole-stage call (parse + GPU + write) for each algorithm.
+through the whole-stage call (parse + GPU + write) for each algorithm.  --linkage: the single-linkage merge table
+(vg_cluster_linkage_graph) on the same synthetic graphs instead of the four algorithms, with `single` timed on the same graph
+in the same process as the yardstick.
 """
 import argparse
 import json
@@ -56,14 +58,28 @@ def main():
     ap.add_argument('--ids', type=pathlib.Path)
     ap.add_argument('--metric', default='tani')
     ap.add_argument('--min', type=float, default=0.95)
+    ap.add_argument('--linkage', action='store_true')
     ap.add_argument('--json', type=pathlib.Path)
     a = ap.parse_args()
     api.set_device(0)
     api.profile_enable(True)
     api.cluster_graph(2, [0], [1], [1.0])          # context, code object
     res = []
+    if a.linkage:
+        api.cluster_linkage(2, [0], [1], [1.0])
     for n in a.sizes:
         q, r, w = family_graph(n)
+        if a.linkage:
+            (lab, rep, st), wall1, kern1 = timed(lambda: api.cluster_graph(n, q, r, w, 'single'))
+            (table, lst), wall, kern = timed(lambda: api.cluster_linkage(n, q, r, w))
+            row = dict(input=f'synthetic n={n} rows={len(q)}', algorithm='linkage', wall_ms=round(wall, 2), gpu_ms=round(sum(kern.values()), 2),
+                       kernels=kern, single_wall_ms=round(wall1, 2), single_gpu_ms=round(sum(kern1.values()), 2), single_kernels=kern1,
+                       gpu_ratio_to_single=round(sum(kern.values()) / max(sum(kern1.values()), 1e-9), 2),
+                       components=int(lab.max()) + 1, **lst)
+            assert lst['n_merges'] == n - row['components'], row
+            print(json.dumps(row), flush=True)
+            res.append(row)
+            continue
         for algo in ALGOS:
             (lab, rep, st), wall, kern = timed(lambda: api.cluster_graph(n, q, r, w, algo))
             row = dict(input=f'synthetic n={n} rows={len(q)}', algorithm=algo, wall_ms=round(wall, 2), gpu_ms=round(sum(kern.values()), 2),

@@ -68,6 +68,10 @@ class ClusterStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('sweep_objects', C.c_int64), ('n_edges', C.c_int64)]
 
 
+class LinkageStats(C.Structure):
+    _fields_ = [('rounds', C.c_int64), ('n_edges', C.c_int64), ('n_merges', C.c_int64)]
+
+
 # --algorithm values the library clusters itself (VG_CLUSTER_*); complete / leiden stay with Clusty
 CLUSTER_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2, 'set-cover': 3}
 
@@ -166,6 +170,11 @@ SYMBOLS = {
     'vg_cluster': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams)]),
     'vg_cluster_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_int,
                                    P(C.c_int32), P(C.c_int32), P(ClusterStats)]),
+    'vg_cluster_linkage_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_int32), P(C.c_int32),
+                                           P(C.c_double), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(LinkageStats)]),
+    'vg_cluster_levels_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_double), C.c_int,
+                                          P(C.c_int32), P(C.c_int32), P(LinkageStats)]),
+    'vg_cluster_linkage': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams), C.c_char_p, P(C.c_double), C.c_int]),
     'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),
     'vg_deduplicate_ex': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams), P(DedupOptions)]),

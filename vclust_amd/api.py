@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, AlignParams, ClusterStats, DedupStats, KernelTime, LzParams, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, AlignParams, ClusterStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -21,6 +21,8 @@ TASK_DTYPE = np.dtype([('q', '<u4'), ('r', '<u4')])
 STAT_DTYPE = np.dtype([('n_match', '<u4'), ('aln_len', '<u4'), ('n_regions', '<u4')])
 REGION_DTYPE = np.dtype([('task', '<u4'), ('qstart', '<i4'), ('qend', '<i4'), ('rstart', '<i4'),
                          ('rend', '<i4'), ('n_match', '<i4')])
+LINKAGE_DTYPE = np.dtype([('node_a', '<i8'), ('node_b', '<i8'), ('similarity', '<f8'), ('size', '<i8'), ('object_a', '<i4'),
+                          ('object_b', '<i4')])
 
 from .stages import DEFAULT_LZ  # noqa: E402
 
@@ -265,6 +267,56 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
                                        w.ctypes.data_as(P(C.c_double)), len(q), CLUSTER_ALGORITHMS[algorithm],
                                        label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
+
+
+def _rows(q, r, w):
+    q = np.ascontiguousarray(q, dtype=np.uint32)
+    r = np.ascontiguousarray(r, dtype=np.uint32)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not len(q) == len(r) == len(w):
+        raise ValueError('q, r and w must have the same length')
+    P = C.POINTER
+    return q, r, w, (q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)), w.ctypes.data_as(P(C.c_double)), len(q))
+
+
+def cluster_linkage(n_objects, q, r, w):
+    """The single-linkage merge table of the graph of cluster_graph (vg_cluster_linkage_graph): the maximum spanning forest in
+    the order (similarity descending, object_a, object_b).  -> (table, stats): table is a LINKAGE_DTYPE array with one record
+    per merge -- merge k creates node n_objects + k from node_a < node_b and has `size` members; (object_a, object_b,
+    similarity) is the edge -- and stats a dict(rounds, n_edges, n_merges)."""
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    cap = max(n - 1, 1) if n < 1 << 31 else 1          # (2^31 objects or more: the library refuses before it writes)
+    oa, ob = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    wt = np.zeros(cap, dtype=np.float64)
+    na, nb, sz = (np.zeros(cap, dtype=np.int64) for _ in range(3))
+    nm = C.c_int64(0)
+    st = LinkageStats()
+    P = C.POINTER
+    check(_lib.load().vg_cluster_linkage_graph(n, *rows, oa.ctypes.data_as(P(C.c_int32)), ob.ctypes.data_as(P(C.c_int32)),
+                                               wt.ctypes.data_as(P(C.c_double)), na.ctypes.data_as(P(C.c_int64)),
+                                               nb.ctypes.data_as(P(C.c_int64)), sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
+    table = np.zeros(nm.value, dtype=LINKAGE_DTYPE)
+    for name, arr in (('node_a', na), ('node_b', nb), ('similarity', wt), ('size', sz), ('object_a', oa), ('object_b', ob)):
+        table[name] = arr[:nm.value]
+    return table, dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+
+
+def cluster_levels(n_objects, q, r, w, levels):
+    """The cuts of one merge table at `levels` (vg_cluster_levels_graph): the cut at t joins the merges of similarity >= t and
+    equals cluster_graph(rows with w >= t, 'single').  -> (label int32[len(levels), n], representative int32[len(levels), n],
+    stats dict), rows in the order of the levels."""
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    width = n if 0 < n < 1 << 31 else 1                # (the library's row stride is n; it writes nothing otherwise)
+    label = np.zeros((len(lv), width), dtype=np.int32)
+    rep = np.zeros((len(lv), width), dtype=np.int32)
+    st = LinkageStats()
+    P = C.POINTER
+    check(_lib.load().vg_cluster_levels_graph(n, *rows, lv.ctypes.data_as(P(C.c_double)), len(lv), label.ctypes.data_as(P(C.c_int32)),
+                                              rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    return label[:, :n], rep[:, :n], dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
 
 
 def _seq_buffer(seqs):

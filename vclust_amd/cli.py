@@ -4,7 +4,8 @@
 output files (vclust.py:178-421, 1380-1521) but call libvclust_gpu.so (HIP, MI355X) through
 ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster` passes its
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
-single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster).  `deduplicate` does
+single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster); `--out-linkage` and
+`--levels` (the single-linkage merge table and its cuts) always run on the GPU.  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
 without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
 `--contained` always run on the GPU.  `info` reports the library and the optional CPU tools.
@@ -180,6 +181,11 @@ def get_parser() -> argparse.ArgumentParser:
                         help=f'Min. {name} (0-1) [%(default)s]')
     cl.add_argument('--num_alns', metavar='<int>', dest='num_alns', type=int, default=0,
                     help='Max. number of local alignments between two genomes; 0 = all [%(default)s]')
+    cl.add_argument('--out-linkage', metavar='<file>', type=pathlib.Path, dest='linkage_path',
+                    help='Write the single-linkage merge table (the dendrogram: one line per merge) to the tsv <file>')
+    cl.add_argument('--levels', metavar='<float>', type=_unit_float, nargs='+', dest='levels',
+                    help='Further thresholds of the metric (0-1, none below its minimum): one more column per level, the cut of '
+                         'the same single-linkage hierarchy there')
     cl.add_argument('--leiden-resolution', metavar='<float>', type=_unit_float, default=0.7)
     cl.add_argument('--leiden-beta', metavar='<float>', type=_unit_float, default=0.01)
     cl.add_argument('--leiden-iterations', metavar='<int>', type=int, default=2)
@@ -341,14 +347,29 @@ def cluster_call(args):
     """What the front-end hands to vg_cluster for validated cluster arguments -- the counterpart of cmd_clusty
     (vclust.py:1184-1278): a minimum only for values > 0, the num_alns maximum only for values > 0."""
     mins = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio') if getattr(args, k) > 0}
-    return dict(ani_path=args.input_path, ids_path=args.ids_path, out_path=args.output_path, algorithm=args.algorithm,
+    call = dict(ani_path=args.input_path, ids_path=args.ids_path, out_path=args.output_path, algorithm=args.algorithm,
                 metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives, **mins)
+    if getattr(args, 'linkage_path', None) is not None:
+        call['out_linkage'] = args.linkage_path
+    if getattr(args, 'levels', None):
+        call['levels'] = list(args.levels)
+    return call
 
 
 def handle_cluster(args, parser, logger):
     from ._lib import CLUSTER_ALGORITHMS
-    if not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS:
-        # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster, DESIGN.md section 9)
+    linkage_path, levels = getattr(args, 'linkage_path', None), getattr(args, 'levels', None)
+    hierarchy = linkage_path is not None or bool(levels)
+    if hierarchy:
+        if args.algorithm != 'single':
+            parser.error('--out-linkage and --levels are single linkage: they need --algorithm single.')
+        floor = vars(args).get(args.metric, 0)
+        for level in levels or ():
+            if floor and level < floor:
+                parser.error(f'--levels {level:g} is below --{args.metric} {floor:g}: rows below the threshold are not edges.')
+    if hierarchy or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
+        # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster, DESIGN.md section 9); the merge table and
+        # its cuts (which Clusty does not have) always do
         if not vars(args).get(args.metric, 0):
             parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
         from . import stages
@@ -356,6 +377,8 @@ def handle_cluster(args, parser, logger):
         desc = (f'libvclust_gpu cluster --algorithm {args.algorithm} --metric {args.metric}'
                 + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
                 + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
+                + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
+                + (f' --out-linkage {linkage_path}' if linkage_path is not None else '')
                 + f' [1 GPU] -> {args.output_path}')
         run_native(desc, lambda: stages.cluster(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
         return

@@ -2,9 +2,12 @@
 //   vg_prefilter  replaces kmer-db build + all2all + distance (vclust.py:1433-1471)
 //   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521)
 //   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557)
+//   vg_cluster_linkage   the same parse, then the single-linkage merge table and its cuts at several levels
 // Both are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
 #include "vg_common.h"
+#include <math.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <thread>
 #include <vector>
 
@@ -145,5 +148,53 @@ extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char
     if (p->verbosity >= 2)
         fprintf(stderr, "vg_cluster: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld objects by the tail sweep\n",
                 (long long)n, (long long)q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+    VG_API_END
+}
+
+extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
+                                  const char* linkage_path, const double* levels, int n_levels) {
+    VG_API_BEGIN
+    if (!ani_path || !ids_path || !out_path || !p || !p->metric || n_levels < 0 || (n_levels && !levels))
+        throw vg_error(VG_EINVAL, "vg_cluster_linkage: null argument");
+    if (p->algorithm != VG_CLUSTER_SINGLE) throw vg_error(VG_EINVAL, "vg_cluster_linkage: the merge table is single linkage (algorithm must be single)");
+    if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
+        throw vg_error(VG_EINVAL, std::string("vg_cluster_linkage: metric must be tani, gani or ani, not ") + p->metric);
+    const double floor = !strcmp(p->metric, "tani") ? p->min_tani : !strcmp(p->metric, "gani") ? p->min_gani : p->min_ani;
+    for (int l = 0; l < n_levels; ++l)
+        if (!(levels[l] >= floor))          // (also a NaN)
+            throw vg_error(VG_EINVAL, "vg_cluster_linkage: level " + std::to_string(levels[l]) + " is below the " + p->metric + " minimum (rows below it are not edges)");
+    vg_host_mark("vg_cluster_linkage: enter");
+    device_warmup warm(WARM_CLUSTER);         // (the HIP context is created beside the parse)
+    std::vector<std::string> ids;
+    vg_cluster_read_ids(ids_path, ids);
+    if ((int64_t)ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
+    std::vector<uint32_t> q, r; std::vector<double> w;
+    vg_cluster_read_rows(ani_path, (int64_t)ids.size(), p, q, r, w);
+    vg_host_mark("ani.tsv parsed");
+    warm.join();
+    const int64_t n = (int64_t)ids.size();
+    vg_forest f;
+    vg_cluster_forest("vg_cluster_linkage", n, q.data(), r.data(), w.data(), (int64_t)q.size(), f);
+    vg_host_mark("forest computed");
+    // column 0: every merge (the cut at the floor, i.e. `single` on the passing rows); then one cut per level
+    const size_t cols = (size_t)n_levels + 1, stride = (size_t)std::max<int64_t>(n, 1);
+    std::vector<int32_t> label(cols * stride), rep(cols * stride);
+    std::vector<std::string> names = { "cluster" };
+    std::vector<const int32_t*> lab_col, rep_col;
+    for (size_t c = 0; c < cols; ++c) {
+        vg_forest_cut(n, f, c ? levels[c - 1] : -HUGE_VAL, label.data() + c * stride, rep.data() + c * stride);
+        lab_col.push_back(label.data() + c * stride); rep_col.push_back(rep.data() + c * stride);
+        if (c) { char buf[64]; snprintf(buf, sizeof buf, "%g", levels[c - 1]); names.push_back(std::string(p->metric) + "_" + buf); }
+    }
+    if (linkage_path) {
+        const size_t nf = std::max<size_t>(f.a.size(), 1);
+        std::vector<int64_t> node_a(nf), node_b(nf), size(nf);
+        vg_forest_table(n, f, node_a.data(), node_b.data(), size.data());
+        vg_linkage_write(linkage_path, f, node_a.data(), node_b.data(), size.data());
+    }
+    vg_cluster_write_columns(out_path, ids, names, lab_col, rep_col, p->representatives != 0);
+    if (p->verbosity >= 2)
+        fprintf(stderr, "vg_cluster_linkage: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld merges, %d levels\n",
+                (long long)n, (long long)q.size(), (long long)f.stats.n_edges, (long long)f.stats.rounds, (long long)f.stats.n_merges, n_levels);
     VG_API_END
 }

@@ -6,6 +6,8 @@
 //   uclust    sweep in index order once a round decides too little
 //   set-cover rounds of 2-hop local maxima of (unassigned-neighbour count, -index), then a one-workgroup greedy sweep
 //   labels    min member per cluster, multi-member clusters numbered by earliest member, then singletons
+//   linkage   the single-linkage merge table: edges ranked by (w descending, a, b) with one more radix sort, Boruvka rounds on
+//             the ranks (find + hook + jump + relabel), the marked forest edges compacted in rank order; node numbering on the host
 // Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
 // only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
 // their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
@@ -287,6 +289,93 @@ __global__ void __launch_bounds__(SC_TPB) k_sc_sweep(int64_t n, int64_t nb, cons
     }
 }
 
+// ---------------------------------------------------------------- single-linkage merge table (maximum spanning forest)
+// Edge {a, b} (a < b) of weight w has the key (-w, a, b); its rank is its position in that order.  Ranks are unique, so the
+// forest and everything derived from it is, whatever ties the weights have.
+constexpr uint64_t NO_RANK = ~0ull;     // (rank arrays are cleared with 0xff bytes)
+constexpr int ROW_LANES = 16;           // lanes that scan one object's CSR row in k_bor_find
+// doubles as unsigned keys that sort ascending where the weights sort descending; -0.0 is +0.0 (NaN never gets here)
+__device__ __forceinline__ uint64_t desc_key(double w) {
+    uint64_t b = (uint64_t)__double_as_longlong(w + 0.0);
+    b = (b >> 63) ? ~b : b | (1ull << 63);      // ascending order of the doubles
+    return ~b;
+}
+struct forward_edge {                   // the directed edges a -> b with a < b: every undirected edge once, in (a, b) order
+    const uint64_t* keys;
+    __device__ bool operator()(int64_t k) const { const uint64_t x = keys[k]; return (uint32_t)(x >> 32) < (uint32_t)x; }
+};
+__global__ void k_rank_keys(const int64_t* pos, const double* vals, int64_t mu, uint64_t* wkey) {
+    GRID_STRIDE(j, mu) wkey[j] = desc_key(vals[pos[j]]);
+}
+// pos[p] = the directed position of the forward edge of rank p: both directions of the edge learn the rank (the reverse one
+// is found by bisection of the other end's row, which is ascending)
+__global__ void k_rank_scatter(const int64_t* pos, int64_t mu, const uint64_t* keys, const int64_t* off, const int32_t* adj,
+                               uint64_t* rank, int32_t* bad) {
+    GRID_STRIDE(p, mu) {
+        const int64_t k = pos[p];
+        const int32_t a = (int32_t)(keys[k] >> 32), b = (int32_t)(uint32_t)keys[k];
+        rank[k] = (uint64_t)p;
+        int64_t lo = off[b], hi = off[b + 1];
+        while (lo < hi) { const int64_t mid = lo + (hi - lo) / 2; if (adj[mid] < a) lo = mid + 1; else hi = mid; }
+        if (lo < off[b + 1] && adj[lo] == a) rank[lo] = (uint64_t)p; else st(bad, 1);
+    }
+}
+__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+// Boruvka, step 1: every object (ROW_LANES lanes each) looks for its lowest-rank edge that leaves its component and hands it to
+// the component's root.  comp[] is not written here.  An object without a leaving edge never gets one again (components only
+// grow): it is skipped from then on.
+__global__ void k_bor_find(int64_t n, const int64_t* off, const int32_t* adj, const uint64_t* rank, const int32_t* comp,
+                           uint8_t* inner, unsigned long long* cmin) {
+    const int lane = threadIdx.x % ROW_LANES;
+    const int64_t groups = (int64_t)gridDim.x * blockDim.x / ROW_LANES;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ROW_LANES; i < n; i += groups) {
+        if (inner[i]) continue;
+        const int32_t c = comp[i];
+        uint64_t best = NO_RANK;
+        for (int64_t k = off[i] + lane, e = off[i + 1]; k < e; k += ROW_LANES)
+            if (comp[adj[k]] != c) best = umin64(best, rank[k]);
+        for (int o = ROW_LANES / 2; o > 0; o >>= 1) best = umin64(best, (uint64_t)__shfl_xor((unsigned long long)best, o));
+        if (lane == 0) { if (best == NO_RANK) inner[i] = 1; else atomicMin(cmin + c, (unsigned long long)best); }
+    }
+}
+// step 2: every root with a leaving edge marks it as a forest edge and hooks under the root at its other end.  Along such hooks
+// the ranks of the chosen edges fall, except where two roots chose each other -- then they chose the same edge (ranks are
+// unique), and the larger root hooks under the smaller.  Reads comp[] and cmin[] (fixed in this kernel), writes parent[own].
+__global__ void k_bor_hook(int64_t n, const int32_t* comp, const unsigned long long* cmin, const int64_t* pos, const uint64_t* keys,
+                           uint8_t* forest, int32_t* parent, unsigned long long* active) {
+    int c = 0;
+    GRID_STRIDE(i64, n) {
+        const int32_t i = (int32_t)i64;
+        if (comp[i] != i) continue;
+        const uint64_t p = cmin[i];
+        if (p == NO_RANK) continue;
+        forest[p] = 1;
+        const uint64_t key = keys[pos[p]];
+        const int32_t ca = comp[(int32_t)(key >> 32)], o = ca == i ? comp[(int32_t)(uint32_t)key] : ca;
+        if (!(cmin[o] == p && i < o)) parent[i] = o;
+        ++c;
+    }
+    add_count(active, c);
+}
+// step 3: pointer jumping over the roots of this round (parent[] of a current root is itself; a stale read is an older ancestor)
+__global__ void k_bor_jump(int64_t n, const int32_t* comp, int32_t* parent) {
+    GRID_STRIDE(i, n) {
+        if (comp[i] != (int32_t)i) continue;
+        int32_t x = ld(parent + i);
+        for (;;) { const int32_t y = ld(parent + x); if (y == x) break; x = y; }
+        st(parent + i, x);
+    }
+}
+// step 4: every root of this round now points at its final root
+__global__ void k_bor_relabel(int64_t n, const int32_t* parent, int32_t* comp) { GRID_STRIDE(i, n) comp[i] = parent[comp[i]]; }
+__global__ void k_forest_gather(const int64_t* frank, int64_t nf, const int64_t* pos, const uint64_t* keys, const double* vals,
+                                int32_t* a, int32_t* b, double* w) {
+    GRID_STRIDE(j, nf) {
+        const int64_t k = pos[frank[j]];
+        a[j] = (int32_t)(keys[k] >> 32); b[j] = (int32_t)(uint32_t)keys[k]; w[j] = vals[k] + 0.0;
+    }
+}
+
 // ---------------------------------------------------------------- labels
 // every object must carry a cluster id in [0, n) before the label kernels index with it
 __global__ void k_check_roots(const int32_t* root, int64_t n, int32_t* bad) { GRID_STRIDE(i, n) if ((uint32_t)root[i] >= (uint64_t)n) st(bad, 1); }
@@ -321,36 +410,31 @@ void exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, hipStream_t 
     dbuf<char> tmp(std::max<size_t>(tb, 1));
     VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s));
 }
-}  // namespace
+// the argument checks of the array-level calls, before any device use
+void check_rows(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
+    const std::string name(fn);
+    if (n_objects < 0 || n_rows < 0) throw vg_error(VG_EINVAL, name + ": negative size");
+    if (n_objects >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, name + ": 2^31 or more objects (object indices are int32)");
+    if (n_rows && (!q || !r || !w)) throw vg_error(VG_EINVAL, name + ": null rows");
+}
+void check_row_values(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
+    std::vector<int64_t> bad((size_t)std::max(1, vg_host_threads()), -1);
+    vg_parallel_chunks(n_rows, vg_host_threads(), [&](int64_t lo, int64_t hi, int t) {
+        for (int64_t k = lo; k < hi; ++k)
+            if (q[k] >= (uint64_t)n_objects || r[k] >= (uint64_t)n_objects || std::isnan(w[k])) { bad[(size_t)t] = k; return; }
+    });
+    for (int64_t k : bad) if (k >= 0)
+        throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": " +
+                       (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
+}
 
-extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
-                                int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats) {
-    VG_API_BEGIN
-    if (n_objects < 0 || n_rows < 0) throw vg_error(VG_EINVAL, "vg_cluster_graph: negative size");
-    if (n_objects >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_cluster_graph: 2^31 or more objects (object indices are int32)");
-    if (n_rows && (!q || !r || !w)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null rows");
-    if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null output");
-    if (algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_SET_COVER) throw vg_error(VG_EINVAL, "vg_cluster_graph: unknown algorithm");
-    {
-        std::vector<int64_t> bad((size_t)std::max(1, vg_host_threads()), -1);
-        vg_parallel_chunks(n_rows, vg_host_threads(), [&](int64_t lo, int64_t hi, int t) {
-            for (int64_t k = lo; k < hi; ++k)
-                if (q[k] >= (uint64_t)n_objects || r[k] >= (uint64_t)n_objects || std::isnan(w[k])) { bad[(size_t)t] = k; return; }
-        });
-        for (int64_t k : bad) if (k >= 0)
-            throw vg_error(VG_EINVAL, "vg_cluster_graph: row " + std::to_string(k) + ": " +
-                           (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
-    }
-    vg_cluster_stats st_local{}; vg_cluster_stats& sts = stats ? *stats : st_local;
-    sts = vg_cluster_stats{};
-    if (n_objects == 0) return VG_OK;
-    vg_require_device();
-    hipStream_t s = vg_stream();
-    const int64_t n = n_objects;
+// the edge graph of the rows on the device: the m directed edges sorted by (src, dst) with their weights, and the CSR
+struct edge_graph { dbuf<uint64_t> ukeys; dbuf<double> uvals; int64_t m = 0; dbuf<int64_t> off; dbuf<int32_t> adj; };
+void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, hipStream_t s, edge_graph& g) {
+    dbuf<uint64_t>& ukeys = g.ukeys; dbuf<double>& uvals = g.uvals; int64_t& m = g.m;
     int bits = 1; while ((1LL << bits) <= n) ++bits;            // the sentinel source n must fit as well
 
     // ---- edges: sort both directions by (src, dst), merge duplicates to the max weight, CSR
-    dbuf<uint64_t> ukeys; dbuf<double> uvals; int64_t m = 0;
     if (n_rows) {
         const int64_t nd = 2 * n_rows;
         dbuf<uint64_t> keys((size_t)nd), keys2((size_t)nd); dbuf<double> vals((size_t)nd), vals2((size_t)nd);
@@ -387,12 +471,117 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
             if ((int64_t)(last >> 32) == n) --m;
         }
     }
-    sts.n_edges = m / 2;
-    dbuf<int64_t> off((size_t)n + 1); dbuf<int32_t> adj((size_t)std::max<int64_t>(m, 1));
+    g.off.alloc((size_t)n + 1); g.adj.alloc((size_t)std::max<int64_t>(m, 1));
     {
         vg_prof_scope ps("cluster_csr", (double)m * 12.0 + (double)n * 8.0);
-        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)ukeys.p, m, n, off.p, adj.p);
+        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)ukeys.p, m, n, g.off.p, g.adj.p);
     }
+}
+
+// The forest edges of the rows in merge order (ascending rank), computed on the device; only these records come back.
+void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f) {
+    hipStream_t s = vg_stream();
+    edge_graph eg;
+    build_edge_graph(n, q, r, w, n_rows, s, eg);
+    const int64_t m = eg.m, mu = m / 2;
+    f.stats.n_edges = mu;
+    if (mu == 0) return;
+    // ---- rank: forward edges in (a, b) order, then ONE stable sort by the weight key -> (w descending, a, b)
+    dbuf<int64_t> pos((size_t)mu); dbuf<uint64_t> rank((size_t)m);
+    {
+        vg_prof_scope ps("cluster_rank", (double)m * 8.0 + (double)mu * (16.0 + 32.0 * 2.0 + 40.0));
+        dbuf<int64_t> pos0((size_t)mu); dbuf<uint64_t> wkey((size_t)mu), wkey2((size_t)mu);
+        dbuf<unsigned long long> d_cnt(1);
+        rocprim::counting_iterator<int64_t> iota(0);
+        const forward_edge fwd{ eg.ukeys.p };
+        size_t tb = 0;
+        VG_HIP(rocprim::select(nullptr, tb, iota, pos0.p, d_cnt.p, (size_t)m, fwd, s));
+        {
+            dbuf<char> tmp(std::max<size_t>(tb, 1));
+            VG_HIP(rocprim::select((void*)tmp.p, tb, iota, pos0.p, d_cnt.p, (size_t)m, fwd, s));
+        }
+        if (read_counter(d_cnt, s) != mu) throw vg_error(VG_EHIP, "vg_cluster_linkage: the edge list is not symmetric (internal error)");
+        hipLaunchKernelGGL(k_rank_keys, dim3(grid_of(mu)), dim3(TPB), 0, s, (const int64_t*)pos0.p, (const double*)eg.uvals.p, mu, wkey.p);
+        tb = 0;
+        VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, wkey.p, wkey2.p, pos0.p, pos.p, (size_t)mu, 0u, 64u, s));
+        {
+            dbuf<char> tmp(std::max<size_t>(tb, 1));
+            VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, wkey.p, wkey2.p, pos0.p, pos.p, (size_t)mu, 0u, 64u, s));
+        }
+        dbuf<int32_t> bad(1); bad.zero(s);
+        hipLaunchKernelGGL(k_rank_scatter, dim3(grid_of(mu)), dim3(TPB), 0, s, (const int64_t*)pos.p, mu, (const uint64_t*)eg.ukeys.p,
+                           (const int64_t*)eg.off.p, (const int32_t*)eg.adj.p, rank.p, bad.p);
+        int32_t b = 0; bad.download(&b, 1, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (b) throw vg_error(VG_EHIP, "vg_cluster_linkage: an edge without its reverse (internal error)");
+    }
+    // ---- Boruvka rounds on the ranks: find, hook, jump, relabel; one counter read back per round
+    dbuf<uint8_t> forest((size_t)mu);
+    {
+        dbuf<int32_t> comp((size_t)n), parent((size_t)n); dbuf<uint8_t> inner((size_t)n); dbuf<unsigned long long> cmin((size_t)n), active(1);
+        forest.zero(s); inner.zero(s);
+        hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, comp.p, n);
+        hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, parent.p, n);
+        for (;;) {
+            {
+                vg_prof_scope ps("cluster_boruvka", (double)m * 16.0 + (double)n * 32.0);
+                VG_HIP(hipMemsetAsync(cmin.p, 0xff, cmin.bytes(), s));
+                active.zero(s);
+                hipLaunchKernelGGL(k_bor_find, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)eg.off.p, (const int32_t*)eg.adj.p,
+                                   (const uint64_t*)rank.p, (const int32_t*)comp.p, inner.p, cmin.p);
+                hipLaunchKernelGGL(k_bor_hook, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)comp.p, (const unsigned long long*)cmin.p,
+                                   (const int64_t*)pos.p, (const uint64_t*)eg.ukeys.p, forest.p, parent.p, active.p);
+                hipLaunchKernelGGL(k_bor_jump, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)comp.p, parent.p);
+                hipLaunchKernelGGL(k_bor_relabel, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)parent.p, comp.p);
+            }
+            ++f.stats.rounds;
+            if (read_counter(active, s) == 0) break;           // no component has a leaving edge
+            if (f.stats.rounds > 64) throw vg_error(VG_EHIP, "vg_cluster_linkage: the rounds do not end (internal error)");
+        }
+    }
+    VG_HIP(hipGetLastError());
+    // ---- forest: the marked ranks, ascending = merge order, with their ends and weights
+    vg_prof_scope ps("cluster_forest", (double)mu + (double)n * 40.0);
+    const int64_t cap = std::min<int64_t>(mu, n - 1);
+    dbuf<int64_t> frank((size_t)mu); dbuf<unsigned long long> d_cnt(1);
+    rocprim::counting_iterator<int64_t> iota(0);
+    size_t tb = 0;
+    VG_HIP(rocprim::select(nullptr, tb, iota, forest.p, frank.p, d_cnt.p, (size_t)mu, s));
+    {
+        dbuf<char> tmp(std::max<size_t>(tb, 1));
+        VG_HIP(rocprim::select((void*)tmp.p, tb, iota, forest.p, frank.p, d_cnt.p, (size_t)mu, s));
+    }
+    const int64_t nf = read_counter(d_cnt, s);
+    if (nf < 1 || nf > cap) throw vg_error(VG_EHIP, "vg_cluster_linkage: the marked edges are no forest (internal error)");
+    dbuf<int32_t> da((size_t)nf), db((size_t)nf); dbuf<double> dw((size_t)nf);
+    hipLaunchKernelGGL(k_forest_gather, dim3(grid_of(nf)), dim3(TPB), 0, s, (const int64_t*)frank.p, nf, (const int64_t*)pos.p,
+                       (const uint64_t*)eg.ukeys.p, (const double*)eg.uvals.p, da.p, db.p, dw.p);
+    VG_HIP(hipGetLastError());
+    f.a.resize((size_t)nf); f.b.resize((size_t)nf); f.w.resize((size_t)nf);
+    da.download(f.a.data(), (size_t)nf, s); db.download(f.b.data(), (size_t)nf, s); dw.download(f.w.data(), (size_t)nf, s);
+    VG_HIP(hipStreamSynchronize(s));
+    f.stats.n_merges = nf;
+}
+}  // namespace
+
+extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats) {
+    VG_API_BEGIN
+    check_rows("vg_cluster_graph", n_objects, q, r, w, n_rows);
+    if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null output");
+    if (algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_SET_COVER) throw vg_error(VG_EINVAL, "vg_cluster_graph: unknown algorithm");
+    check_row_values("vg_cluster_graph", n_objects, q, r, w, n_rows);
+    vg_cluster_stats st_local{}; vg_cluster_stats& sts = stats ? *stats : st_local;
+    sts = vg_cluster_stats{};
+    if (n_objects == 0) return VG_OK;
+    vg_require_device();
+    hipStream_t s = vg_stream();
+    const int64_t n = n_objects;
+    edge_graph eg;
+    build_edge_graph(n, q, r, w, n_rows, s, eg);
+    const int64_t m = eg.m;
+    dbuf<uint64_t>& ukeys = eg.ukeys; dbuf<double>& uvals = eg.uvals; dbuf<int64_t>& off = eg.off; dbuf<int32_t>& adj = eg.adj;
+    sts.n_edges = m / 2;
     dbuf<int32_t> root((size_t)n);
     dbuf<unsigned long long> d_dec(1);
 
@@ -493,5 +682,90 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
     minm.download(label, (size_t)n, s);
     rep.download(representative, (size_t)n, s);
     VG_HIP(hipStreamSynchronize(s));
+    VG_API_END
+}
+
+// ---------------------------------------------------------------- merge table and cuts (host numbering of <= n - 1 records)
+void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f) {
+    check_rows(fn, n_objects, q, r, w, n_rows);
+    check_row_values(fn, n_objects, q, r, w, n_rows);
+    f = vg_forest{};
+    if (n_objects == 0) return;
+    vg_require_device();
+    forest_on_device(n_objects, q, r, w, n_rows, f);
+}
+
+namespace {
+// union-find over the forest records; the root of a set is its minimum member
+struct min_sets {
+    std::vector<int32_t> up;
+    explicit min_sets(int64_t n) : up((size_t)n) { for (int64_t i = 0; i < n; ++i) up[(size_t)i] = (int32_t)i; }
+    int32_t find(int32_t x) { while (up[(size_t)x] != x) { up[(size_t)x] = up[(size_t)up[(size_t)x]]; x = up[(size_t)x]; } return x; }
+    int32_t join(int32_t a, int32_t b) { a = find(a); b = find(b); if (a > b) std::swap(a, b); up[(size_t)b] = a; return a; }
+};
+}  // namespace
+
+void vg_forest_table(int64_t n, const vg_forest& f, int64_t* node_a, int64_t* node_b, int64_t* size) {
+    min_sets sets(n);
+    std::vector<int64_t> node((size_t)n), members((size_t)n, 1);        // of a set's root: its current node and its size
+    for (int64_t i = 0; i < n; ++i) node[(size_t)i] = i;
+    for (size_t k = 0; k < f.a.size(); ++k) {
+        const int32_t ra = sets.find(f.a[k]), rb = sets.find(f.b[k]);
+        if (ra == rb) throw vg_error(VG_EHIP, "vg_cluster_linkage: a forest edge inside one cluster (internal error)");
+        node_a[k] = std::min(node[(size_t)ra], node[(size_t)rb]); node_b[k] = std::max(node[(size_t)ra], node[(size_t)rb]);
+        const int64_t sz = members[(size_t)ra] + members[(size_t)rb];
+        const int32_t root = sets.join(ra, rb);
+        node[(size_t)root] = n + (int64_t)k; members[(size_t)root] = sz; size[k] = sz;
+    }
+}
+
+void vg_forest_cut(int64_t n, const vg_forest& f, double level, int32_t* label, int32_t* rep) {
+    min_sets sets(n);
+    for (size_t k = 0; k < f.a.size() && f.w[k] >= level; ++k) sets.join(f.a[k], f.b[k]);       // (the weights are non-increasing)
+    std::vector<int32_t> members((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) { rep[i] = sets.find((int32_t)i); ++members[(size_t)rep[i]]; }
+    // multi-member clusters 0.. by earliest member, then singletons in object order (as k_head_labels)
+    std::vector<int32_t> head((size_t)n, 0);
+    int32_t next = 0;
+    for (int64_t i = 0; i < n; ++i) if (rep[i] == i && members[(size_t)i] >= 2) head[(size_t)i] = next++;
+    for (int64_t i = 0; i < n; ++i) if (rep[i] == i && members[(size_t)i] == 1) head[(size_t)i] = next++;
+    for (int64_t i = 0; i < n; ++i) label[i] = head[(size_t)rep[i]];
+}
+
+extern "C" int vg_cluster_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                        int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
+                                        int64_t* size, int64_t* n_merges, vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    check_rows("vg_cluster_linkage_graph", n_objects, q, r, w, n_rows);
+    if (!n_merges || (n_objects > 1 && (!object_a || !object_b || !weight || !node_a || !node_b || !size)))
+        throw vg_error(VG_EINVAL, "vg_cluster_linkage_graph: null output");
+    *n_merges = 0;
+    if (stats) *stats = vg_linkage_stats{};
+    vg_forest f;
+    vg_cluster_forest("vg_cluster_linkage_graph", n_objects, q, r, w, n_rows, f);
+    const size_t nf = f.a.size();
+    if (nf) {
+        memcpy(object_a, f.a.data(), nf * sizeof(int32_t)); memcpy(object_b, f.b.data(), nf * sizeof(int32_t));
+        memcpy(weight, f.w.data(), nf * sizeof(double));
+        vg_forest_table(n_objects, f, node_a, node_b, size);
+    }
+    *n_merges = (int64_t)nf;
+    if (stats) *stats = f.stats;
+    VG_API_END
+}
+
+extern "C" int vg_cluster_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                       const double* levels, int n_levels, int32_t* label, int32_t* representative,
+                                       vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    check_rows("vg_cluster_levels_graph", n_objects, q, r, w, n_rows);
+    if (n_levels < 0 || (n_levels && !levels)) throw vg_error(VG_EINVAL, "vg_cluster_levels_graph: null levels");
+    for (int l = 0; l < n_levels; ++l) if (std::isnan(levels[l])) throw vg_error(VG_EINVAL, "vg_cluster_levels_graph: a level is NaN");
+    if (n_objects && n_levels && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_levels_graph: null output");
+    if (stats) *stats = vg_linkage_stats{};
+    vg_forest f;
+    vg_cluster_forest("vg_cluster_levels_graph", n_objects, q, r, w, n_rows, f);
+    for (int l = 0; l < n_levels; ++l) vg_forest_cut(n_objects, f, levels[l], label + (int64_t)l * n_objects, representative + (int64_t)l * n_objects);
+    if (stats) *stats = f.stats;
     VG_API_END
 }

@@ -182,6 +182,16 @@ void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);
 void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
                           std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w);
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives);
+// merge table (vg_cluster.hip): the forest edges of the rows in merge order (a < b, weights non-increasing) -- checks the rows
+// (errors name fn), then the device; the node numbering of the table and the labels of a cut are host loops over those records
+struct vg_forest { std::vector<int32_t> a, b; std::vector<double> w; vg_linkage_stats stats{}; };
+void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f);
+void vg_forest_table(int64_t n, const vg_forest& f, int64_t* node_a, int64_t* node_b, int64_t* size);
+void vg_forest_cut(int64_t n, const vg_forest& f, double level, int32_t* label, int32_t* rep);
+// clusters.tsv with further columns (vg_io.cpp): column c has the header names[c] and the labels / representatives label[c], rep[c]
+void vg_cluster_write_columns(const char* path, const std::vector<std::string>& ids, const std::vector<std::string>& names,
+                              const std::vector<const int32_t*>& label, const std::vector<const int32_t*>& rep, bool representatives);
+void vg_linkage_write(const char* path, const vg_forest& f, const int64_t* node_a, const int64_t* node_b, const int64_t* size);
 
 // deduplicate stage (vg_genomes.cpp): the input files whole in memory (plain files mapped, gzip / BGZF inflated) and every
 // record in command-line and file order; a record is its header line [hdr, hdr_end) without '>' and its sequence lines [seq, end)

@@ -688,3 +688,41 @@ void vg_cluster_write(const char* path, const std::vector<std::string>& ids, con
     if (fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
     if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + path);
 }
+
+namespace {
+void write_text(const char* path, const std::string& o) {
+    FILE* f = fopen(path, "w");
+    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + path);
+    if (fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
+    if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + path);
+}
+}  // namespace
+
+void vg_cluster_write_columns(const char* path, const std::vector<std::string>& ids, const std::vector<std::string>& names,
+                              const std::vector<const int32_t*>& label, const std::vector<const int32_t*>& rep, bool representatives) {
+    std::string o = "object";
+    for (const std::string& nm : names) { o.push_back('\t'); o += nm; }
+    o.push_back('\n');
+    o.reserve(ids.size() * 24 * (names.size() + 1) + 64);
+    for (size_t i = 0; i < ids.size(); ++i) {
+        o += ids[i];
+        for (size_t c = 0; c < names.size(); ++c) {
+            o.push_back('\t');
+            if (representatives) o += ids[(size_t)rep[c][i]]; else o += std::to_string(label[c][i]);
+        }
+        o.push_back('\n');
+    }
+    write_text(path, o);
+}
+
+void vg_linkage_write(const char* path, const vg_forest& f, const int64_t* node_a, const int64_t* node_b, const int64_t* size) {
+    std::string o = "node_a\tnode_b\tsimilarity\tsize\tobject_a\tobject_b\n";
+    o.reserve(f.a.size() * 48 + 64);
+    char buf[160];
+    for (size_t k = 0; k < f.a.size(); ++k) {
+        snprintf(buf, sizeof buf, "%lld\t%lld\t%.6g\t%lld\t%d\t%d\n", (long long)node_a[k], (long long)node_b[k], f.w[k], (long long)size[k],
+                 (int)f.a[k], (int)f.b[k]);
+        o += buf;
+    }
+    write_text(path, o);
+}

@@ -52,9 +52,11 @@ CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
 
 
 def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num_alns=0, representatives=False,
-            num_threads=0, verbosity=0, **mins):
+            num_threads=0, verbosity=0, out_linkage=None, levels=None, **mins):
     """clusters.tsv from ani.tsv + its ids file (vg_cluster).  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio= (0 = off);
-    num_alns: max. number of local alignments of a passing row (0 = off)."""
+    num_alns: max. number of local alignments of a passing row (0 = off).  out_linkage: also the single-linkage merge table
+    -> that file; levels: one more column per level, the cut of the same forest there (vg_cluster_linkage; both need
+    algorithm='single' and no level below the metric's minimum)."""
     unknown = set(mins) - set(CLUSTER_FILTERS)
     if unknown:
         raise TypeError(f'unknown filter(s): {sorted(unknown)}')
@@ -64,7 +66,15 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
                       representatives=int(bool(representatives)), num_threads=int(num_threads), verbosity=int(verbosity))
     for name, val in mins.items():
         setattr(p, f'min_{name}', float(val))
-    check(_lib.load().vg_cluster(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)), C.byref(p)))
+    paths = (os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)))
+    if out_linkage is None and levels is None:
+        check(_lib.load().vg_cluster(*paths, C.byref(p)))
+        return
+    if algorithm != 'single':
+        raise ValueError('out_linkage and levels need algorithm=\'single\'')
+    lv = [float(x) for x in (levels or ())]
+    check(_lib.load().vg_cluster_linkage(*paths, C.byref(p), os.fsencode(str(out_linkage)) if out_linkage is not None else None,
+                                         (C.c_double * len(lv))(*lv) if lv else None, len(lv)))
 
 
 def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False, contained=False,
