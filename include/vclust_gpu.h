@@ -283,7 +283,7 @@ int vg_align_sharded(const char* const* fasta_paths, int n_paths, const char* ou
  * Objects are the rows of the ids file (index = row number from 0, i.e. the align stage's length order).  A row of ani.tsv
  * passes when every minimum > 0 holds (column >= value), num_alns <= max_num_alns when that is > 0, and qidx != ridx; it
  * links {qidx, ridx} with the metric value as weight (the maximum over duplicate and reverse rows). */
-enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3 };
+enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3, VG_CLUSTER_COMPLETE = 4 };
 typedef struct {            /* mirrors the cluster sub-parser, vclust.py:423 ff. */
     int algorithm;                                            /* VG_CLUSTER_* */
     const char* metric;                                       /* "tani" | "gani" | "ani": the edge weight */
@@ -293,7 +293,7 @@ typedef struct {            /* mirrors the cluster sub-parser, vclust.py:423 ff.
     int num_threads; int verbosity;
 } vg_cluster_params;
 typedef struct {
-    int64_t rounds;             /* parallel rounds launched (single: hooking rounds) */
+    int64_t rounds;             /* parallel rounds launched (single: hooking rounds; complete: merge rounds) */
     int64_t sweep_objects;      /* objects decided by the one-workgroup tail sweep */
     int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
 } vg_cluster_stats;
@@ -306,7 +306,8 @@ int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path,
 /* The array-level stage: rows (q[i], r[i], w[i]) over n_objects objects, read as above (self rows dropped, duplicates
  * merged to the maximum weight; NaN weights and indices >= n_objects are VG_EINVAL, n_objects >= 2^31 VG_EOVERFLOW).
  * label[n_objects]: the output file's numbering; representative[n_objects]: the index of the cluster's earliest member.
- * stats may be NULL. */
+ * stats may be NULL.  VG_CLUSTER_COMPLETE (here and in vg_cluster) is the cut of the complete-linkage hierarchy below at the
+ * floor, i.e. after every merge: each cluster is a clique of passing rows; sweep_objects is 0. */
 int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_edges,
                      int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats);
 
@@ -317,9 +318,9 @@ int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, co
  * 0 .. n_objects - 1 and merge k (from 0) creates node n_objects + k.  The cut at level t joins the merges with w >= t; its
  * labels and representatives follow the rule of vg_cluster_graph, and it equals `single` on the rows with w >= t. */
 typedef struct {
-    int64_t rounds;             /* Boruvka rounds launched (the last one finds no leaving edge) */
+    int64_t rounds;             /* single: Boruvka rounds launched (the last one finds no leaving edge); complete: merge rounds */
     int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
-    int64_t n_merges;           /* forest edges = n_objects - components */
+    int64_t n_merges;           /* single: forest edges = n_objects - components; complete: n_objects - clusters at the floor */
 } vg_linkage_stats;
 /* The merge table of the rows (validated as vg_cluster_graph validates them, before any device use).  Every output array is the
  * caller's and has n_objects - 1 entries (they may be NULL when n_objects <= 1); *n_merges of them are written, in merge order:
@@ -332,8 +333,22 @@ int vg_cluster_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_
  * order of the levels (any order, repeats allowed; a NaN level is VG_EINVAL). */
 int vg_cluster_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                             const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats);
-/* File to file, with the host parse and the error messages of vg_cluster; p->algorithm must be VG_CLUSTER_SINGLE (else
- * VG_EINVAL).  out_path: clusters.tsv of vg_cluster (the cut at the metric's floor) plus one column per level, headed
+/* Complete-linkage merge table and cuts (this repository's definition; DESIGN.md section 9, "Merge table: complete linkage").
+ * Same graph, same edge key (-w, a, b); a pair of objects without an edge has the key +infinity.  K(A, B) of two clusters is the
+ * LARGEST key over all pairs a in A, b in B (the worst pair; +infinity when any pair has no edge).  From singletons, the two
+ * clusters of smallest finite K merge, until no finite K is left; the merge record is that worst edge (object_a < object_b,
+ * weight).  Every cluster is a clique of passing rows, records come in increasing key order (weights never rise), and the table,
+ * node numbering, cuts, labels and representatives are exactly those of the single-linkage calls.  The cut at level t equals
+ * the run on the rows with w >= t after every merge.  On the device the merges of mutually nearest clusters happen in parallel
+ * rounds (the linkage is reducible, so these are the merges of the sequential rule); stats->rounds counts the merge rounds
+ * launched (the last one finds no merge).  Arguments, outputs and errors as vg_cluster_linkage_graph / vg_cluster_levels_graph. */
+int vg_cluster_complete_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                      int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
+                                      int64_t* size, int64_t* n_merges, vg_linkage_stats* stats);
+int vg_cluster_complete_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                     const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats);
+/* File to file, with the host parse and the error messages of vg_cluster; p->algorithm must be VG_CLUSTER_SINGLE or
+ * VG_CLUSTER_COMPLETE (else VG_EINVAL) and selects the hierarchy.  out_path: clusters.tsv of vg_cluster (the cut at the metric's floor) plus one column per level, headed
  * `<metric>_<%g of the level>`, labels or -- with p->representatives -- representative ids; a level below the metric's minimum
  * is VG_EINVAL.  linkage_path (may be NULL): header `node_a node_b similarity size object_a object_b` (tab-separated), one line
  * per merge, similarity printed with %.6g. */

@@ -2,16 +2,26 @@
 table), rounds, objects finished by the tail sweep, end-to-end wall time.
 
   python tools/cluster_timing.py [--sizes 100000 1000000] [--ani ani.tsv --ids ani.ids.tsv] [--metric tani --min 0.95] [--linkage]
+  python tools/cluster_timing.py --complete [--sizes 100000] [--clique-chain 200]
 
 Synthetic graphs: families of 20-200 objects in index order, ~50 rows per object (both directions, ~25 distinct
 neighbours), weights 0.80-1.00 inside families and a few weak rows between them.  With --ani, the file is also clustered
 through the whole-stage call (parse + GPU + write) for each algorithm.  --linkage: the single-linkage merge table
 (vg_cluster_linkage_graph) on the same synthetic graphs instead of the four algorithms, with `single` timed on the same graph
-in the same process as the yardstick.
+in the same process as the yardstick.  --complete: the complete-linkage merge table (vg_cluster_complete_linkage_graph) with
+`single` and the single-linkage table as yardsticks, all three on the same graph in the same process, each run once and
+discarded and then timed three times (the median is printed).  The graph is the synthetic one with every family made a full
+clique (the 50-rows-per-object families are no cliques and would merge almost nothing); the row prints the two profile groups
+`cluster_complete_best` / `cluster_complete_contract`, the rounds and the records of the cluster graph after each contraction
+(read from the library's VG_HOST_TRACE lines, which this mode switches on).  --clique-chain N adds the known worst case: one
+clique of N objects whose weights force one merge per round, with the time per round.
 """
 import argparse
 import json
+import os
 import pathlib
+import re
+import statistics
 import sys
 import tempfile
 import time
@@ -42,6 +52,66 @@ def family_graph(n, per_object=50, seed=0):
     return q.astype(np.uint32), r.astype(np.uint32), w
 
 
+def clique_family_graph(n, seed=0):
+    """the families of family_graph (20-200 objects in index order), every pair inside one a row of weight 0.80-1.00"""
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(20, 201, n // 20 + 2)
+    q, r, start = [], [], 0
+    for size in sizes:
+        size = min(int(size), n - start)
+        if size <= 0:
+            break
+        a, b = np.triu_indices(size, 1)
+        q.append(a + start); r.append(b + start)
+        start += size
+    q, r = np.concatenate(q), np.concatenate(r)
+    return q.astype(np.uint32), r.astype(np.uint32), rng.uniform(0.8, 1.0, len(q)).round(4)
+
+
+def clique_chain(n):
+    """one clique with w(i, j) = 1 - max(i, j) / (4 n): object k joins {0 .. k-1} in round k, one merge per round"""
+    q, r = np.triu_indices(n, 1)
+    return q.astype(np.uint32), r.astype(np.uint32), 1.0 - np.maximum(q, r) / (4.0 * n)
+
+
+def records_per_round(fn):
+    """run fn with the library's host trace on stderr captured -> its result, [records after each contraction]"""
+    sys.stderr.flush()
+    keep = os.dup(2)
+    with tempfile.TemporaryFile() as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            out = fn()
+        finally:
+            os.dup2(keep, 2); os.close(keep)
+        tmp.seek(0)
+        text = tmp.read().decode(errors='replace')
+    return out, [int(x) for x in re.findall(r'complete round \d+: \d+ merges, (\d+) records', text)][1:]
+
+
+def median_of_three(fn):
+    """discard one run, then the run of median wall time of three -> (result, wall ms, kernel groups)"""
+    fn()
+    runs = sorted((timed(fn) for _ in range(3)), key=lambda x: x[1])
+    return runs[1]
+
+
+def complete_row(name, n, q, r, w):
+    (lab, rep, st), wall1, kern1 = median_of_three(lambda: api.cluster_graph(n, q, r, w, 'single'))
+    (_, lst), wall2, kern2 = median_of_three(lambda: api.cluster_linkage(n, q, r, w))
+    (table, cst), wall, kern = median_of_three(lambda: api.cluster_complete_linkage_graph(n, q, r, w))
+    _, records = records_per_round(lambda: api.cluster_complete_linkage_graph(n, q, r, w))
+    gpu, rounds = sum(kern.values()), max(cst['rounds'], 1)
+    per_round = (kern.get('cluster_complete_best', 0) + kern.get('cluster_complete_contract', 0)) / rounds
+    return dict(input=f'{name} n={n} rows={len(q)}', algorithm='complete', wall_ms=round(wall, 2), gpu_ms=round(gpu, 2), kernels=kern,
+                best_ms=kern.get('cluster_complete_best', 0), contract_ms=kern.get('cluster_complete_contract', 0),
+                gpu_ms_per_round=round(per_round, 4), wall_ms_per_round=round(wall / rounds, 4), records_after_contraction=records,
+                single_wall_ms=round(wall1, 2), single_gpu_ms=round(sum(kern1.values()), 2),
+                linkage_wall_ms=round(wall2, 2), linkage_gpu_ms=round(sum(kern2.values()), 2), linkage_rounds=lst['rounds'],
+                gpu_ratio_to_single=round(gpu / max(sum(kern1.values()), 1e-9), 2),
+                gpu_ratio_to_linkage=round(gpu / max(sum(kern2.values()), 1e-9), 2), **cst)
+
+
 def timed(fn):
     api.profile_reset()
     t0 = time.perf_counter()
@@ -59,14 +129,30 @@ def main():
     ap.add_argument('--metric', default='tani')
     ap.add_argument('--min', type=float, default=0.95)
     ap.add_argument('--linkage', action='store_true')
+    ap.add_argument('--complete', action='store_true')
+    ap.add_argument('--clique-chain', type=int, default=0, metavar='N')
     ap.add_argument('--json', type=pathlib.Path)
     a = ap.parse_args()
+    if a.complete:
+        os.environ['VG_HOST_TRACE'] = '1'      # (read once, at the library's first trace point; only records_per_round shows it)
     api.set_device(0)
     api.profile_enable(True)
     api.cluster_graph(2, [0], [1], [1.0])          # context, code object
     res = []
     if a.linkage:
         api.cluster_linkage(2, [0], [1], [1.0])
+    if a.complete:
+        silent = lambda fn: records_per_round(fn)[0]            # noqa: E731  (the trace lines of the timed runs are dropped)
+        silent(lambda: api.cluster_complete_linkage_graph(2, [0], [1], [1.0]))
+        silent(lambda: api.cluster_linkage(2, [0], [1], [1.0]))
+        graphs = [('synthetic clique families', n, *clique_family_graph(n)) for n in a.sizes]
+        if a.clique_chain:
+            graphs.append(('one clique, one merge per round', a.clique_chain, *clique_chain(a.clique_chain)))
+        for name, n, q, r, w in graphs:
+            row = silent(lambda: complete_row(name, n, q, r, w))
+            print(json.dumps(row), flush=True)
+            res.append(row)
+        a.sizes = []
     for n in a.sizes:
         q, r, w = family_graph(n)
         if a.linkage:

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, AlignParams, ClusterStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, AlignParams, ClusterStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -250,9 +250,11 @@ from .stages import align, align_params, cluster, deduplicate as deduplicate_fil
 def cluster_graph(n_objects, q, r, w, algorithm='single'):
     """Cluster n_objects objects linked by the rows (q[i], r[i]) of weight w[i] (vg_cluster_graph): self rows are dropped,
     duplicate and reverse rows merged to the maximum weight.  -> (label int32[n], representative int32[n], stats dict):
-    label is the numbering of clusters.tsv, representative the index of each cluster's earliest member."""
-    if algorithm not in CLUSTER_ALGORITHMS:
-        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(CLUSTER_ALGORITHMS)})')
+    label is the numbering of clusters.tsv, representative the index of each cluster's earliest member.  algorithm: one of
+    CLUSTER_ALGORITHMS, or 'complete' -- the complete-linkage hierarchy after every merge (each cluster a clique of the rows)."""
+    known = {**CLUSTER_ALGORITHMS, **LINKAGE_ALGORITHMS}
+    if algorithm not in known:
+        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
     q = np.ascontiguousarray(q, dtype=np.uint32)
     r = np.ascontiguousarray(r, dtype=np.uint32)
     w = np.ascontiguousarray(w, dtype=np.float64)
@@ -264,7 +266,7 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     st = ClusterStats()
     P = C.POINTER
     check(_lib.load().vg_cluster_graph(n, q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)),
-                                       w.ctypes.data_as(P(C.c_double)), len(q), CLUSTER_ALGORITHMS[algorithm],
+                                       w.ctypes.data_as(P(C.c_double)), len(q), known[algorithm],
                                        label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
 
@@ -279,11 +281,8 @@ def _rows(q, r, w):
     return q, r, w, (q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)), w.ctypes.data_as(P(C.c_double)), len(q))
 
 
-def cluster_linkage(n_objects, q, r, w):
-    """The single-linkage merge table of the graph of cluster_graph (vg_cluster_linkage_graph): the maximum spanning forest in
-    the order (similarity descending, object_a, object_b).  -> (table, stats): table is a LINKAGE_DTYPE array with one record
-    per merge -- merge k creates node n_objects + k from node_a < node_b and has `size` members; (object_a, object_b,
-    similarity) is the edge -- and stats a dict(rounds, n_edges, n_merges)."""
+def _linkage_table(fn, n_objects, q, r, w):
+    """-> (table, stats) of the array-level merge-table call `fn`"""
     q, r, w, rows = _rows(q, r, w)
     n = int(n_objects)
     cap = max(n - 1, 1) if n < 1 << 31 else 1          # (2^31 objects or more: the library refuses before it writes)
@@ -293,19 +292,47 @@ def cluster_linkage(n_objects, q, r, w):
     nm = C.c_int64(0)
     st = LinkageStats()
     P = C.POINTER
-    check(_lib.load().vg_cluster_linkage_graph(n, *rows, oa.ctypes.data_as(P(C.c_int32)), ob.ctypes.data_as(P(C.c_int32)),
-                                               wt.ctypes.data_as(P(C.c_double)), na.ctypes.data_as(P(C.c_int64)),
-                                               nb.ctypes.data_as(P(C.c_int64)), sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
+    check(getattr(_lib.load(), fn)(n, *rows, oa.ctypes.data_as(P(C.c_int32)), ob.ctypes.data_as(P(C.c_int32)),
+                                   wt.ctypes.data_as(P(C.c_double)), na.ctypes.data_as(P(C.c_int64)),
+                                   nb.ctypes.data_as(P(C.c_int64)), sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
     table = np.zeros(nm.value, dtype=LINKAGE_DTYPE)
     for name, arr in (('node_a', na), ('node_b', nb), ('similarity', wt), ('size', sz), ('object_a', oa), ('object_b', ob)):
         table[name] = arr[:nm.value]
     return table, dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
 
 
+def cluster_linkage(n_objects, q, r, w):
+    """The single-linkage merge table of the graph of cluster_graph (vg_cluster_linkage_graph): the maximum spanning forest in
+    the order (similarity descending, object_a, object_b).  -> (table, stats): table is a LINKAGE_DTYPE array with one record
+    per merge -- merge k creates node n_objects + k from node_a < node_b and has `size` members; (object_a, object_b,
+    similarity) is the edge -- and stats a dict(rounds, n_edges, n_merges)."""
+    return _linkage_table('vg_cluster_linkage_graph', n_objects, q, r, w)
+
+
+def cluster_complete_linkage_graph(n_objects, q, r, w):
+    """The complete-linkage merge table of the graph of cluster_graph (vg_cluster_complete_linkage_graph).  K(A, B) of two clusters
+    is the worst edge between them in the order (similarity descending, object_a, object_b), infinite when any pair of their
+    members has no edge; from singletons, the two clusters of smallest finite K merge until none is left, so every cluster is a
+    clique of the rows.  -> (table, stats) as cluster_linkage: (object_a, object_b, similarity) is that worst edge, `similarity`
+    never rises down the table, and stats['rounds'] counts the parallel merge rounds."""
+    return _linkage_table('vg_cluster_complete_linkage_graph', n_objects, q, r, w)
+
+
+def cluster_complete_levels_graph(n_objects, q, r, w, levels):
+    """The cuts of one complete-linkage merge table at `levels` (vg_cluster_complete_levels_graph): the cut at t joins the merges
+    of similarity >= t and equals cluster_graph(rows with w >= t, 'complete'); every cluster of it is a clique of those rows and
+    lies inside one cluster of cluster_levels at t.  -> as cluster_levels."""
+    return _levels('vg_cluster_complete_levels_graph', n_objects, q, r, w, levels)
+
+
 def cluster_levels(n_objects, q, r, w, levels):
     """The cuts of one merge table at `levels` (vg_cluster_levels_graph): the cut at t joins the merges of similarity >= t and
     equals cluster_graph(rows with w >= t, 'single').  -> (label int32[len(levels), n], representative int32[len(levels), n],
     stats dict), rows in the order of the levels."""
+    return _levels('vg_cluster_levels_graph', n_objects, q, r, w, levels)
+
+
+def _levels(fn, n_objects, q, r, w, levels):
     q, r, w, rows = _rows(q, r, w)
     n = int(n_objects)
     lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
@@ -314,8 +341,8 @@ def cluster_levels(n_objects, q, r, w, levels):
     rep = np.zeros((len(lv), width), dtype=np.int32)
     st = LinkageStats()
     P = C.POINTER
-    check(_lib.load().vg_cluster_levels_graph(n, *rows, lv.ctypes.data_as(P(C.c_double)), len(lv), label.ctypes.data_as(P(C.c_int32)),
-                                              rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    check(getattr(_lib.load(), fn)(n, *rows, lv.ctypes.data_as(P(C.c_double)), len(lv), label.ctypes.data_as(P(C.c_int32)),
+                                   rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
     return label[:, :n], rep[:, :n], dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
 
 

@@ -8,6 +8,9 @@
 //   labels    min member per cluster, multi-member clusters numbered by earliest member, then singletons
 //   linkage   the single-linkage merge table: edges ranked by (w descending, a, b) with one more radix sort, Boruvka rounds on
 //             the ranks (find + hook + jump + relabel), the marked forest edges compacted in rank order; node numbering on the host
+//   complete  the complete-linkage merge table on the same ranks: rounds that merge every pair of mutually nearest clusters
+//             (find + match), then a contraction of the cluster graph (relabel, radix sort, reduce-by-key, select, CSR) that keeps
+//             a cluster pair only while every object pair between the two is an edge; the merge records go the forest's way
 // Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
 // only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
 // their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
@@ -376,6 +379,81 @@ __global__ void k_forest_gather(const int64_t* frank, int64_t nf, const int64_t*
     }
 }
 
+// ---------------------------------------------------------------- complete linkage
+// The cluster graph: directed records (src cluster << 32 | dst cluster, rank), sorted by key, with row offsets.  A cluster's id is
+// its minimum member.  The rank of a record is K of the cluster pair: the largest rank over the object edges between the two, and
+// there is a record only while EVERY object pair between them is an edge.  Initially these are the object graph and its ranks.
+constexpr int COUNT_BITS = 3;           // contraction: a record's value is rank << 3 | records merged into it (<= 4 per cluster pair)
+// round, step 1: every cluster (ROW_LANES lanes each) finds the smallest rank of its row and the cluster at that record's other
+// end.  The ranks of a row are distinct (each is another object edge), so one lane holds the minimum.  A cluster with an empty
+// row is final: it only gets "no rank".  mult[] (members of the matching merged into a cluster this round) starts at 1.
+__global__ void k_cl_find(int64_t n, const int64_t* off, const uint64_t* keys, const uint64_t* rank, unsigned long long* best,
+                          int32_t* bdst, int32_t* mult) {
+    const int lane = threadIdx.x % ROW_LANES;
+    const int64_t groups = (int64_t)gridDim.x * blockDim.x / ROW_LANES;
+    for (int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ROW_LANES; c < n; c += groups) {
+        const int64_t lo = off[c], hi = off[c + 1];
+        if (lo == hi) { if (lane == 0) { best[c] = NO_RANK; mult[c] = 1; } continue; }
+        uint64_t mine = NO_RANK; int64_t at = lo;
+        for (int64_t k = lo + lane; k < hi; k += ROW_LANES) { const uint64_t p = rank[k]; if (p < mine) { mine = p; at = k; } }
+        uint64_t low = mine;
+        for (int o = ROW_LANES / 2; o > 0; o >>= 1) low = umin64(low, (uint64_t)__shfl_xor((unsigned long long)low, o));
+        if (mine == low) { best[c] = low; bdst[c] = (int32_t)(uint32_t)keys[at]; mult[c] = 1; }
+    }
+}
+// step 2: the record (c, d), c < d, is a merge when its rank is the smallest of both rows.  Ranks are unique, so the merges of a
+// round are a matching, and the smallest rank of the whole graph is always one of them.  Reads only what k_cl_find wrote; the
+// merge list is filled in any order (it is sorted at the end), `total` counts the merges of all rounds so far.
+__global__ void k_cl_match(int64_t n, const unsigned long long* best, const int32_t* bdst, int32_t* parent, int32_t* mult,
+                           int64_t* merged, int64_t cap, unsigned long long* total) {
+    GRID_STRIDE(c, n) {
+        const uint64_t p = best[c];
+        if (p == NO_RANK) continue;
+        const int64_t d = bdst[c];
+        if (d <= c || d >= n || best[d] != p) continue;
+        const unsigned long long slot = atomicAdd(total, 1ull);
+        if (slot < (unsigned long long)cap) merged[slot] = (int64_t)p;
+        parent[d] = (int32_t)c; mult[c] = 2;
+    }
+}
+// contraction, step 1: every record under the new cluster ids, keyed on 2 * bits bits for the sort; the record of a merged pair
+// itself becomes the sentinel (src = n) that sorts last.  One hop of parent[] is enough: the merges are a matching.
+__global__ void k_cl_relabel(const uint64_t* keys, const uint64_t* rank, int64_t m, const int32_t* parent, int64_t n, int bits,
+                             uint64_t* okey, uint64_t* oval) {
+    GRID_STRIDE(e, m) {
+        const uint64_t s = (uint64_t)parent[keys[e] >> 32], d = (uint64_t)parent[(uint32_t)keys[e]];
+        okey[e] = s == d ? (uint64_t)n << bits : s << bits | d;
+        oval[e] = rank[e] << COUNT_BITS | 1;
+    }
+}
+struct max_rank_add_count {             // (rank, count) + (rank, count) of one cluster pair: the worst rank, the records seen
+    __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const {
+        const uint64_t ra = a >> COUNT_BITS, rb = b >> COUNT_BITS, lowbits = (1ull << COUNT_BITS) - 1;
+        return (ra > rb ? ra : rb) << COUNT_BITS | (((a & lowbits) + (b & lowbits)) & lowbits);
+    }
+};
+// step 2 (after sort and reduce-by-key): the pair (S, D) stays only if all mult(S) * mult(D) pairs of its constituents had a record
+struct surviving_pair {
+    const uint64_t* gkey; const uint64_t* gval; const unsigned long long* n_groups; const int32_t* mult; int64_t n; int bits;
+    __device__ bool operator()(int64_t k) const {
+        if ((unsigned long long)k >= *n_groups) return false;
+        const uint64_t s = gkey[k] >> bits, d = gkey[k] & ((1ull << bits) - 1);
+        return s < (uint64_t)n && d < (uint64_t)n && (gval[k] & ((1ull << COUNT_BITS) - 1)) == (uint64_t)(mult[s] * mult[d]);
+    }
+};
+// step 3: the survivors, in key order, are the new records; the tail of the old list is filled with the sentinel, so that k_csr
+// over the old length gives the new offsets (off[n] = the new length) without the host knowing it yet
+__global__ void k_cl_compact(const int64_t* idx, const unsigned long long* m_new, int64_t m_old, const uint64_t* gkey, const uint64_t* gval,
+                             int64_t n, int bits, uint64_t* keys, uint64_t* rank) {
+    const int64_t mn = (int64_t)*m_new < m_old ? (int64_t)*m_new : m_old;
+    GRID_STRIDE(e, m_old) {
+        if (e < mn) {
+            const uint64_t k = gkey[idx[e]];
+            keys[e] = (k >> bits) << 32 | (k & ((1ull << bits) - 1)); rank[e] = gval[idx[e]] >> COUNT_BITS;
+        } else keys[e] = (uint64_t)n << 32;
+    }
+}
+
 // ---------------------------------------------------------------- labels
 // every object must carry a cluster id in [0, n) before the label kernels index with it
 __global__ void k_check_roots(const int32_t* root, int64_t n, int32_t* bad) { GRID_STRIDE(i, n) if ((uint32_t)root[i] >= (uint64_t)n) st(bad, 1); }
@@ -478,16 +556,11 @@ void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const dou
     }
 }
 
-// The forest edges of the rows in merge order (ascending rank), computed on the device; only these records come back.
-void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f) {
-    hipStream_t s = vg_stream();
-    edge_graph eg;
-    build_edge_graph(n, q, r, w, n_rows, s, eg);
+// rank: forward edges in (a, b) order, then ONE stable sort by the weight key -> (w descending, a, b).  pos[p] = the directed
+// position of the forward edge of rank p (mu = m / 2 of them), rank[k] = the rank of the directed edge k
+void rank_edges(const edge_graph& eg, hipStream_t s, dbuf<int64_t>& pos, dbuf<uint64_t>& rank) {
     const int64_t m = eg.m, mu = m / 2;
-    f.stats.n_edges = mu;
-    if (mu == 0) return;
-    // ---- rank: forward edges in (a, b) order, then ONE stable sort by the weight key -> (w descending, a, b)
-    dbuf<int64_t> pos((size_t)mu); dbuf<uint64_t> rank((size_t)m);
+    pos.alloc((size_t)mu); rank.alloc((size_t)m);
     {
         vg_prof_scope ps("cluster_rank", (double)m * 8.0 + (double)mu * (16.0 + 32.0 * 2.0 + 40.0));
         dbuf<int64_t> pos0((size_t)mu); dbuf<uint64_t> wkey((size_t)mu), wkey2((size_t)mu);
@@ -515,6 +588,29 @@ void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const dou
         VG_HIP(hipStreamSynchronize(s));
         if (b) throw vg_error(VG_EHIP, "vg_cluster_linkage: an edge without its reverse (internal error)");
     }
+}
+// the merge records of the ranks frank[0 .. nf) (ascending = merge order): their ends and weights; only these leave the device
+void download_forest(const dbuf<int64_t>& frank, int64_t nf, const dbuf<int64_t>& pos, const edge_graph& eg, hipStream_t s, vg_forest& f) {
+    dbuf<int32_t> da((size_t)nf), db((size_t)nf); dbuf<double> dw((size_t)nf);
+    hipLaunchKernelGGL(k_forest_gather, dim3(grid_of(nf)), dim3(TPB), 0, s, (const int64_t*)frank.p, nf, (const int64_t*)pos.p,
+                       (const uint64_t*)eg.ukeys.p, (const double*)eg.uvals.p, da.p, db.p, dw.p);
+    VG_HIP(hipGetLastError());
+    f.a.resize((size_t)nf); f.b.resize((size_t)nf); f.w.resize((size_t)nf);
+    da.download(f.a.data(), (size_t)nf, s); db.download(f.b.data(), (size_t)nf, s); dw.download(f.w.data(), (size_t)nf, s);
+    VG_HIP(hipStreamSynchronize(s));
+    f.stats.n_merges = nf;
+}
+
+// The forest edges of the rows in merge order (ascending rank), computed on the device; only these records come back.
+void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f) {
+    hipStream_t s = vg_stream();
+    edge_graph eg;
+    build_edge_graph(n, q, r, w, n_rows, s, eg);
+    const int64_t m = eg.m, mu = m / 2;
+    f.stats.n_edges = mu;
+    if (mu == 0) return;
+    dbuf<int64_t> pos; dbuf<uint64_t> rank;
+    rank_edges(eg, s, pos, rank);
     // ---- Boruvka rounds on the ranks: find, hook, jump, relabel; one counter read back per round
     dbuf<uint8_t> forest((size_t)mu);
     {
@@ -553,14 +649,86 @@ void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const dou
     }
     const int64_t nf = read_counter(d_cnt, s);
     if (nf < 1 || nf > cap) throw vg_error(VG_EHIP, "vg_cluster_linkage: the marked edges are no forest (internal error)");
-    dbuf<int32_t> da((size_t)nf), db((size_t)nf); dbuf<double> dw((size_t)nf);
-    hipLaunchKernelGGL(k_forest_gather, dim3(grid_of(nf)), dim3(TPB), 0, s, (const int64_t*)frank.p, nf, (const int64_t*)pos.p,
-                       (const uint64_t*)eg.ukeys.p, (const double*)eg.uvals.p, da.p, db.p, dw.p);
+    download_forest(frank, nf, pos, eg, s, f);
+}
+
+// rocPRIM's two-call convention: the size query, then the call with that much temporary storage
+template <class F> void with_temp_storage(F call) {
+    size_t tb = 0;
+    VG_HIP(call((void*)nullptr, tb));
+    dbuf<char> tmp(std::max<size_t>(tb, 1));
+    VG_HIP(call((void*)tmp.p, tb));
+}
+
+// Complete linkage on the edge graph (which it consumes: the row offsets are rebuilt per contraction).  comp[i] = the cluster of
+// object i after every merge (its minimum member); f, if given, receives the merge records in merge order.  -> rounds launched
+int64_t complete_on_device(int64_t n, edge_graph& eg, hipStream_t s, dbuf<int32_t>& comp, vg_forest* f) {
+    const int64_t m0 = eg.m, mu = m0 / 2;
+    comp.alloc((size_t)n);
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, comp.p, n);
+    if (f) f->stats.n_edges = mu;
+    if (mu == 0) { VG_HIP(hipGetLastError()); return 0; }
+    dbuf<int64_t> pos; dbuf<uint64_t> rank;
+    rank_edges(eg, s, pos, rank);
+    int bits = 1; while ((1LL << bits) <= n) ++bits;            // cluster ids and the sentinel n: two of them are a sort key
+    const int64_t cap = std::min<int64_t>(mu, n - 1);
+    // the cluster graph (keys, rank, eg.off) starts as the object graph; t* / s* are the contraction's work arrays
+    dbuf<uint64_t> keys((size_t)m0), tkey((size_t)m0), tval((size_t)m0), skey((size_t)m0), sval((size_t)m0);
+    dbuf<int64_t> idx((size_t)m0), merged((size_t)cap);
+    dbuf<int32_t> parent((size_t)n), mult((size_t)n), bdst((size_t)n);
+    dbuf<unsigned long long> best((size_t)n), cnt(2), n_groups(1);     // cnt: merges of all rounds so far, records of the cluster graph
+    VG_HIP(hipMemcpyAsync(keys.p, eg.ukeys.p, (size_t)m0 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, parent.p, n);
+    const unsigned long long cnt0[2] = { 0, (unsigned long long)m0 };
+    cnt.upload(cnt0, 2, s);
+    int64_t rounds = 0, total = 0, m = m0;
+    char note[96];
+    for (;;) {
+        {
+            vg_prof_scope ps("cluster_complete_best", (double)m * 16.0 + (double)n * 40.0);
+            hipLaunchKernelGGL(k_cl_find, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)eg.off.p, (const uint64_t*)keys.p,
+                               (const uint64_t*)rank.p, best.p, bdst.p, mult.p);
+            hipLaunchKernelGGL(k_cl_match, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const unsigned long long*)best.p, (const int32_t*)bdst.p,
+                               parent.p, mult.p, merged.p, cap, cnt.p);
+        }
+        ++rounds;
+        unsigned long long now[2] = { 0, 0 };                   // the one read-back of the round: both counters
+        cnt.download(now, 2, s);
+        VG_HIP(hipStreamSynchronize(s));
+        const int64_t merges = (int64_t)now[0] - total;
+        total = (int64_t)now[0]; m = (int64_t)now[1];
+        if (total > cap || m < 0 || m > m0 || (m & 1)) throw vg_error(VG_EHIP, "vg_cluster_complete_linkage: the merges are no hierarchy (internal error)");
+        snprintf(note, sizeof note, "complete round %lld: %lld merges, %lld records", (long long)rounds, (long long)merges, (long long)m);
+        vg_host_mark(note);
+        if (merges == 0) break;                                 // no finite K is left
+        if (rounds > n) throw vg_error(VG_EHIP, "vg_cluster_complete_linkage: the rounds do not end (internal error)");
+        vg_prof_scope ps("cluster_complete_contract", (double)m * (32.0 + 32.0 * 2.0 + 32.0 + 24.0) + (double)n * 16.0);
+        hipLaunchKernelGGL(k_bor_relabel, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)parent.p, comp.p);
+        hipLaunchKernelGGL(k_cl_relabel, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)keys.p, (const uint64_t*)rank.p, m,
+                           (const int32_t*)parent.p, n, bits, tkey.p, tval.p);
+        with_temp_storage([&](void* tmp, size_t& tb) {
+            return rocprim::radix_sort_pairs(tmp, tb, tkey.p, skey.p, tval.p, sval.p, (size_t)m, 0u, 2u * (unsigned)bits, s); });
+        with_temp_storage([&](void* tmp, size_t& tb) {           // -> (cluster pair, worst rank << 3 | records) in tkey / tval
+            return rocprim::reduce_by_key(tmp, tb, skey.p, sval.p, (size_t)m, tkey.p, tval.p, n_groups.p, max_rank_add_count(),
+                                          rocprim::equal_to<uint64_t>(), s); });
+        const surviving_pair alive{ tkey.p, tval.p, n_groups.p, mult.p, n, bits };
+        rocprim::counting_iterator<int64_t> iota(0);
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::select(tmp, tb, iota, idx.p, cnt.p + 1, (size_t)m, alive, s); });
+        hipLaunchKernelGGL(k_cl_compact, dim3(grid_of(m)), dim3(TPB), 0, s, (const int64_t*)idx.p, (const unsigned long long*)(cnt.p + 1), m,
+                           (const uint64_t*)tkey.p, (const uint64_t*)tval.p, n, bits, keys.p, rank.p);
+        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)keys.p, m, n, eg.off.p, eg.adj.p);
+    }
     VG_HIP(hipGetLastError());
-    f.a.resize((size_t)nf); f.b.resize((size_t)nf); f.w.resize((size_t)nf);
-    da.download(f.a.data(), (size_t)nf, s); db.download(f.b.data(), (size_t)nf, s); dw.download(f.w.data(), (size_t)nf, s);
-    VG_HIP(hipStreamSynchronize(s));
-    f.stats.n_merges = nf;
+    if (f) {
+        f->stats.rounds = rounds;
+        if (total > 0) {                                        // the merge ranks, ascending = merge order
+            vg_prof_scope ps("cluster_forest", (double)total * 16.0 + (double)n * 40.0);
+            dbuf<int64_t> frank((size_t)total);
+            with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_keys(tmp, tb, merged.p, frank.p, (size_t)total, 0u, 64u, s); });
+            download_forest(frank, total, pos, eg, s, *f);
+        }
+    }
+    return rounds;
 }
 }  // namespace
 
@@ -569,7 +737,7 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
     VG_API_BEGIN
     check_rows("vg_cluster_graph", n_objects, q, r, w, n_rows);
     if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null output");
-    if (algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_SET_COVER) throw vg_error(VG_EINVAL, "vg_cluster_graph: unknown algorithm");
+    if (algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_COMPLETE) throw vg_error(VG_EINVAL, "vg_cluster_graph: unknown algorithm");
     check_row_values("vg_cluster_graph", n_objects, q, r, w, n_rows);
     vg_cluster_stats st_local{}; vg_cluster_stats& sts = stats ? *stats : st_local;
     sts = vg_cluster_stats{};
@@ -600,6 +768,8 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
             VG_HIP(hipStreamSynchronize(s));
             if (!c) break;
         }
+    } else if (algorithm == VG_CLUSTER_COMPLETE) {              // the floor cut of the complete-linkage hierarchy: every merge
+        sts.rounds = complete_on_device(n, eg, s, root, nullptr);
     } else if (algorithm == VG_CLUSTER_CDHIT || algorithm == VG_CLUSTER_UCLUST) {
         const bool uc = algorithm == VG_CLUSTER_UCLUST;
         VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
@@ -686,13 +856,20 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
 }
 
 // ---------------------------------------------------------------- merge table and cuts (host numbering of <= n - 1 records)
-void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f) {
+void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f,
+                       int algorithm) {
     check_rows(fn, n_objects, q, r, w, n_rows);
     check_row_values(fn, n_objects, q, r, w, n_rows);
+    if (algorithm != VG_CLUSTER_SINGLE && algorithm != VG_CLUSTER_COMPLETE) throw vg_error(VG_EINVAL, std::string(fn) + ": the merge table is single or complete linkage");
     f = vg_forest{};
     if (n_objects == 0) return;
     vg_require_device();
-    forest_on_device(n_objects, q, r, w, n_rows, f);
+    if (algorithm == VG_CLUSTER_SINGLE) { forest_on_device(n_objects, q, r, w, n_rows, f); return; }
+    hipStream_t s = vg_stream();
+    edge_graph eg;
+    build_edge_graph(n_objects, q, r, w, n_rows, s, eg);
+    dbuf<int32_t> comp;
+    complete_on_device(n_objects, eg, s, comp, &f);
 }
 
 namespace {
@@ -732,17 +909,17 @@ void vg_forest_cut(int64_t n, const vg_forest& f, double level, int32_t* label, 
     for (int64_t i = 0; i < n; ++i) label[i] = head[(size_t)rep[i]];
 }
 
-extern "C" int vg_cluster_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
-                                        int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
-                                        int64_t* size, int64_t* n_merges, vg_linkage_stats* stats) {
-    VG_API_BEGIN
-    check_rows("vg_cluster_linkage_graph", n_objects, q, r, w, n_rows);
+namespace {
+void linkage_graph(const char* fn, int algorithm, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                   int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
+                   int64_t* size, int64_t* n_merges, vg_linkage_stats* stats) {
+    check_rows(fn, n_objects, q, r, w, n_rows);
     if (!n_merges || (n_objects > 1 && (!object_a || !object_b || !weight || !node_a || !node_b || !size)))
-        throw vg_error(VG_EINVAL, "vg_cluster_linkage_graph: null output");
+        throw vg_error(VG_EINVAL, std::string(fn) + ": null output");
     *n_merges = 0;
     if (stats) *stats = vg_linkage_stats{};
     vg_forest f;
-    vg_cluster_forest("vg_cluster_linkage_graph", n_objects, q, r, w, n_rows, f);
+    vg_cluster_forest(fn, n_objects, q, r, w, n_rows, f, algorithm);
     const size_t nf = f.a.size();
     if (nf) {
         memcpy(object_a, f.a.data(), nf * sizeof(int32_t)); memcpy(object_b, f.b.data(), nf * sizeof(int32_t));
@@ -751,6 +928,34 @@ extern "C" int vg_cluster_linkage_graph(int64_t n_objects, const uint32_t* q, co
     }
     *n_merges = (int64_t)nf;
     if (stats) *stats = f.stats;
+}
+void levels_graph(const char* fn, int algorithm, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                  const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats) {
+    const std::string name(fn);
+    check_rows(fn, n_objects, q, r, w, n_rows);
+    if (n_levels < 0 || (n_levels && !levels)) throw vg_error(VG_EINVAL, name + ": null levels");
+    for (int l = 0; l < n_levels; ++l) if (std::isnan(levels[l])) throw vg_error(VG_EINVAL, name + ": a level is NaN");
+    if (n_objects && n_levels && (!label || !representative)) throw vg_error(VG_EINVAL, name + ": null output");
+    if (stats) *stats = vg_linkage_stats{};
+    vg_forest f;
+    vg_cluster_forest(fn, n_objects, q, r, w, n_rows, f, algorithm);
+    for (int l = 0; l < n_levels; ++l) vg_forest_cut(n_objects, f, levels[l], label + (int64_t)l * n_objects, representative + (int64_t)l * n_objects);
+    if (stats) *stats = f.stats;
+}
+}  // namespace
+
+extern "C" int vg_cluster_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                        int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
+                                        int64_t* size, int64_t* n_merges, vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    linkage_graph("vg_cluster_linkage_graph", VG_CLUSTER_SINGLE, n_objects, q, r, w, n_rows, object_a, object_b, weight, node_a, node_b, size, n_merges, stats);
+    VG_API_END
+}
+extern "C" int vg_cluster_complete_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                                 int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
+                                                 int64_t* size, int64_t* n_merges, vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    linkage_graph("vg_cluster_complete_linkage_graph", VG_CLUSTER_COMPLETE, n_objects, q, r, w, n_rows, object_a, object_b, weight, node_a, node_b, size, n_merges, stats);
     VG_API_END
 }
 
@@ -758,14 +963,13 @@ extern "C" int vg_cluster_levels_graph(int64_t n_objects, const uint32_t* q, con
                                        const double* levels, int n_levels, int32_t* label, int32_t* representative,
                                        vg_linkage_stats* stats) {
     VG_API_BEGIN
-    check_rows("vg_cluster_levels_graph", n_objects, q, r, w, n_rows);
-    if (n_levels < 0 || (n_levels && !levels)) throw vg_error(VG_EINVAL, "vg_cluster_levels_graph: null levels");
-    for (int l = 0; l < n_levels; ++l) if (std::isnan(levels[l])) throw vg_error(VG_EINVAL, "vg_cluster_levels_graph: a level is NaN");
-    if (n_objects && n_levels && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_levels_graph: null output");
-    if (stats) *stats = vg_linkage_stats{};
-    vg_forest f;
-    vg_cluster_forest("vg_cluster_levels_graph", n_objects, q, r, w, n_rows, f);
-    for (int l = 0; l < n_levels; ++l) vg_forest_cut(n_objects, f, levels[l], label + (int64_t)l * n_objects, representative + (int64_t)l * n_objects);
-    if (stats) *stats = f.stats;
+    levels_graph("vg_cluster_levels_graph", VG_CLUSTER_SINGLE, n_objects, q, r, w, n_rows, levels, n_levels, label, representative, stats);
+    VG_API_END
+}
+extern "C" int vg_cluster_complete_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                                const double* levels, int n_levels, int32_t* label, int32_t* representative,
+                                                vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    levels_graph("vg_cluster_complete_levels_graph", VG_CLUSTER_COMPLETE, n_objects, q, r, w, n_rows, levels, n_levels, label, representative, stats);
     VG_API_END
 }

@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import CLUSTER_ALGORITHMS, AlignParams, ClusterParams, DedupOptions, DedupParams, LzParams, PrefilterParams, check
+from ._lib import CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, AlignParams, ClusterParams, DedupOptions, DedupParams, LzParams, PrefilterParams, check
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -54,15 +54,17 @@ CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
 def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num_alns=0, representatives=False,
             num_threads=0, verbosity=0, out_linkage=None, levels=None, **mins):
     """clusters.tsv from ani.tsv + its ids file (vg_cluster).  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio= (0 = off);
-    num_alns: max. number of local alignments of a passing row (0 = off).  out_linkage: also the single-linkage merge table
+    num_alns: max. number of local alignments of a passing row (0 = off).  out_linkage: also the merge table
     -> that file; levels: one more column per level, the cut of the same forest there (vg_cluster_linkage; both need
-    algorithm='single' and no level below the metric's minimum)."""
+    algorithm='single' or 'complete' -- then the complete-linkage merge table and its cuts -- and no level below the metric's
+    minimum).  algorithm='complete' without either is the cut of that hierarchy at the floor (vg_cluster)."""
     unknown = set(mins) - set(CLUSTER_FILTERS)
     if unknown:
         raise TypeError(f'unknown filter(s): {sorted(unknown)}')
-    if algorithm not in CLUSTER_ALGORITHMS:
-        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(CLUSTER_ALGORITHMS)})')
-    p = ClusterParams(algorithm=CLUSTER_ALGORITHMS[algorithm], metric=metric.encode(), max_num_alns=int(num_alns),
+    known = {**CLUSTER_ALGORITHMS, **LINKAGE_ALGORITHMS}
+    if algorithm not in known:
+        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
+    p = ClusterParams(algorithm=known[algorithm], metric=metric.encode(), max_num_alns=int(num_alns),
                       representatives=int(bool(representatives)), num_threads=int(num_threads), verbosity=int(verbosity))
     for name, val in mins.items():
         setattr(p, f'min_{name}', float(val))
@@ -70,8 +72,8 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     if out_linkage is None and levels is None:
         check(_lib.load().vg_cluster(*paths, C.byref(p)))
         return
-    if algorithm != 'single':
-        raise ValueError('out_linkage and levels need algorithm=\'single\'')
+    if algorithm not in LINKAGE_ALGORITHMS:
+        raise ValueError('out_linkage and levels need algorithm=\'single\' or \'complete\'')
     lv = [float(x) for x in (levels or ())]
     check(_lib.load().vg_cluster_linkage(*paths, C.byref(p), os.fsencode(str(out_linkage)) if out_linkage is not None else None,
                                          (C.c_double * len(lv))(*lv) if lv else None, len(lv)))
