@@ -119,6 +119,19 @@ def test_periodic_and_low_complexity(api):
     assert st['collisions'] == 0
 
 
+def test_candidate_list_grows_and_takes_many_batches(api):
+    """The first 16 symbols recur 1 200 times in a set of 3 records: more candidates than the list's first 4 * 3 + 1 024
+    slots, so the candidate pass runs again on a grown list.  Only the rotation to the last occurrence is the record itself:
+    the equal candidate has rank 1 199, the 11th batch."""
+    rng = np.random.default_rng(5)
+    unit = rand(rng, 16)
+    rec = b''.join(unit + rand(rng, 5) for _ in range(1200))
+    last = 1199 * 21
+    assert len(rec) == 25200 and rec.count(unit) >= 1200 > 4 * 3 + 1024
+    erep, estrand, eoffset, _ = check_seqs(api, [rec, dcr.rot(rec, last), dr.revcomp(dcr.rot(rec, last))])
+    assert (erep, estrand, eoffset) == ([0, 0, 0], [0, 0, 1], [0, 25179, 21])
+
+
 def test_iupac(api):
     rng = np.random.default_rng(3)
     seqs = []

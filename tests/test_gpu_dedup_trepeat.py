@@ -138,6 +138,24 @@ def test_many_candidates_take_several_batches(api):
     assert check_repeats(api, [rec], 3) == [56]
 
 
+def test_candidate_list_grows_and_takes_many_batches(api):
+    """As above with 1 201 occurrences in a set of 2 records: more candidates than the list's first 2 * 2 + 1 024 slots, so
+    the candidate pass runs again on a grown list; the last occurrence has rank 1 200, the 11th batch.  Then poly-A with a
+    minimum of 1: 2 500 candidates per record, a grown list whose answer is the candidate of rank 0."""
+    rng = np.random.default_rng(3)
+    unit = rand(rng, 16)
+    head = unit + rand(rng, 40)
+    rec = head + rand(rng, 27000) + b''.join(unit + rand(rng, 5) for _ in range(1200)) + head
+    L = len(rec)
+    starts = [u for u in range(L - L // 2, L - 16 + 1) if rec.startswith(unit, u)]
+    assert L == 52312 and len(starts) == 1201 > 2 * 2 + 1024 and starts[-1] == L - 56
+    batches = len(starts).bit_length()                    # batch b holds the ranks 2^b - 1 .. 2^(b+1) - 2
+    _, _, _, erepeat, st = check_seqs(api, [rec, rand(rng, 500)], 16)
+    assert erepeat[0] == 56
+    assert st['batches'] == batches == 11 and st['equal'] == 1 and st['candidates'] == min(len(starts), 2 ** batches - 1), st
+    assert check_repeats(api, [b'A' * 5000, b'A' * 4999], 1) == [2500, 2499]
+
+
 def test_poly_a(api):
     """Every start is a candidate and the first one is equal: one batch."""
     seqs = [b'A' * 1000, b'A' * 999]

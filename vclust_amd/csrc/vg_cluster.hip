@@ -483,10 +483,7 @@ int64_t read_counter(dbuf<unsigned long long>& c, hipStream_t s) {
 }
 
 void exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, hipStream_t s) {
-    size_t tb = 0;
-    VG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s));
-    dbuf<char> tmp(std::max<size_t>(tb, 1));
-    VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s));
+    with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s); });
 }
 // the argument checks of the array-level calls, before any device use
 void check_rows(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
@@ -524,22 +521,17 @@ void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const dou
         }
         {
             vg_prof_scope ps("cluster_edges_sort", (double)nd * 32.0 * 2.0);
-            size_t tb = 0;
-            VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)nd, 0u, 32u + (unsigned)bits, s));
-            dbuf<char> tmp(std::max<size_t>(tb, 1));
-            VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)nd, 0u, 32u + (unsigned)bits, s));
+            with_temp_storage([&](void* tmp, size_t& tb) {
+                return rocprim::radix_sort_pairs(tmp, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)nd, 0u, 32u + (unsigned)bits, s); });
         }
         keys.release(); vals.release();
         ukeys.alloc((size_t)nd); uvals.alloc((size_t)nd);
         dbuf<unsigned long long> d_cnt(1);
         {
             vg_prof_scope ps("cluster_edges_merge", (double)nd * 32.0);
-            size_t tb = 0;
-            VG_HIP(rocprim::reduce_by_key(nullptr, tb, keys2.p, vals2.p, (size_t)nd, ukeys.p, uvals.p, d_cnt.p, rocprim::maximum<double>(),
-                                          rocprim::equal_to<uint64_t>(), s));
-            dbuf<char> tmp(std::max<size_t>(tb, 1));
-            VG_HIP(rocprim::reduce_by_key((void*)tmp.p, tb, keys2.p, vals2.p, (size_t)nd, ukeys.p, uvals.p, d_cnt.p, rocprim::maximum<double>(),
-                                          rocprim::equal_to<uint64_t>(), s));
+            with_temp_storage([&](void* tmp, size_t& tb) {
+                return rocprim::reduce_by_key(tmp, tb, keys2.p, vals2.p, (size_t)nd, ukeys.p, uvals.p, d_cnt.p, rocprim::maximum<double>(),
+                                              rocprim::equal_to<uint64_t>(), s); });
         }
         m = read_counter(d_cnt, s);
         if (m > 0) {                                             // the self-row sentinel, if any, is the last unique key
@@ -567,20 +559,11 @@ void rank_edges(const edge_graph& eg, hipStream_t s, dbuf<int64_t>& pos, dbuf<ui
         dbuf<unsigned long long> d_cnt(1);
         rocprim::counting_iterator<int64_t> iota(0);
         const forward_edge fwd{ eg.ukeys.p };
-        size_t tb = 0;
-        VG_HIP(rocprim::select(nullptr, tb, iota, pos0.p, d_cnt.p, (size_t)m, fwd, s));
-        {
-            dbuf<char> tmp(std::max<size_t>(tb, 1));
-            VG_HIP(rocprim::select((void*)tmp.p, tb, iota, pos0.p, d_cnt.p, (size_t)m, fwd, s));
-        }
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::select(tmp, tb, iota, pos0.p, d_cnt.p, (size_t)m, fwd, s); });
         if (read_counter(d_cnt, s) != mu) throw vg_error(VG_EHIP, "vg_cluster_linkage: the edge list is not symmetric (internal error)");
         hipLaunchKernelGGL(k_rank_keys, dim3(grid_of(mu)), dim3(TPB), 0, s, (const int64_t*)pos0.p, (const double*)eg.uvals.p, mu, wkey.p);
-        tb = 0;
-        VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, wkey.p, wkey2.p, pos0.p, pos.p, (size_t)mu, 0u, 64u, s));
-        {
-            dbuf<char> tmp(std::max<size_t>(tb, 1));
-            VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, wkey.p, wkey2.p, pos0.p, pos.p, (size_t)mu, 0u, 64u, s));
-        }
+        with_temp_storage([&](void* tmp, size_t& tb) {
+            return rocprim::radix_sort_pairs(tmp, tb, wkey.p, wkey2.p, pos0.p, pos.p, (size_t)mu, 0u, 64u, s); });
         dbuf<int32_t> bad(1); bad.zero(s);
         hipLaunchKernelGGL(k_rank_scatter, dim3(grid_of(mu)), dim3(TPB), 0, s, (const int64_t*)pos.p, mu, (const uint64_t*)eg.ukeys.p,
                            (const int64_t*)eg.off.p, (const int32_t*)eg.adj.p, rank.p, bad.p);
@@ -641,23 +624,10 @@ void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const dou
     const int64_t cap = std::min<int64_t>(mu, n - 1);
     dbuf<int64_t> frank((size_t)mu); dbuf<unsigned long long> d_cnt(1);
     rocprim::counting_iterator<int64_t> iota(0);
-    size_t tb = 0;
-    VG_HIP(rocprim::select(nullptr, tb, iota, forest.p, frank.p, d_cnt.p, (size_t)mu, s));
-    {
-        dbuf<char> tmp(std::max<size_t>(tb, 1));
-        VG_HIP(rocprim::select((void*)tmp.p, tb, iota, forest.p, frank.p, d_cnt.p, (size_t)mu, s));
-    }
+    with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::select(tmp, tb, iota, forest.p, frank.p, d_cnt.p, (size_t)mu, s); });
     const int64_t nf = read_counter(d_cnt, s);
     if (nf < 1 || nf > cap) throw vg_error(VG_EHIP, "vg_cluster_linkage: the marked edges are no forest (internal error)");
     download_forest(frank, nf, pos, eg, s, f);
-}
-
-// rocPRIM's two-call convention: the size query, then the call with that much temporary storage
-template <class F> void with_temp_storage(F call) {
-    size_t tb = 0;
-    VG_HIP(call((void*)nullptr, tb));
-    dbuf<char> tmp(std::max<size_t>(tb, 1));
-    VG_HIP(call((void*)tmp.p, tb));
 }
 
 // Complete linkage on the edge graph (which it consumes: the row offsets are rebuilt per contraction).  comp[i] = the cluster of

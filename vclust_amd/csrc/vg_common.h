@@ -85,6 +85,14 @@ template <class T> struct dbuf {
     void download(T* h, size_t count, hipStream_t s) const { vg_download_bytes(h, p, count * sizeof(T), s); }
 };
 
+// rocPRIM's two-call convention: call(nullptr, bytes) is the size query, then the call runs with that much temporary storage
+template <class F> void with_temp_storage(F call) {
+    size_t tb = 0;
+    VG_HIP(call((void*)nullptr, tb));
+    dbuf<char> tmp(tb ? tb : 1);
+    VG_HIP(call((void*)tmp.p, tb));
+}
+
 // ---------------------------------------------------------------- profiling (HIP events on vg_stream)
 struct vg_prof_scope {
     const char* name; double bytes; hipEvent_t e0 = nullptr, e1 = nullptr; bool on; hipStream_t stream;

@@ -18,17 +18,24 @@
 //             bit reversal of it; mixed terms of min(window, reverse complement) are summed, so the 128-bit sum depends
 //             neither on where the circle was opened nor on the strand
 //   ccand     per (member, chunk): the positions of the head's strands whose window equals the member's first window are
-//             the candidate offsets (ballots, a per-member counter, a list that grows when it overflows), sorted per member
-//   cverify   per (member, candidate, chunk): the member against the head rotated by the candidate (v_alignbit_b32 re-frames
-//             by offset mod 8, the word index wraps); candidates are tried in increasing order, in batches of 1, 2, 4, ...
-//             per member, and the smallest equal one is the answer
+//             the candidate offsets (code = strand, offset) of the candidate list below
+//   cverify   the list's compare with the functor rotation_words: the member against the head rotated by the candidate
+//             (v_alignbit_b32 re-frames by offset mod 8, the word index wraps); the smallest equal (strand, offset) is the answer
 // Terminal repeats (vg_deduplicate_circular_tr): an exact repeat of the record's first t >= m symbols at its end is taken off
 // before the circular mode runs.
 //   tcand     one wave per (record, chunk): the starts u in the record's second half whose min(16, m) symbols equal the
-//             record's first ones are the candidates (ballots, counters and a growing list as in ccand), sorted per record
-//   tcompare  per (record, candidate, chunk): the prefix against the symbols from u (v_alignbit_b32 re-frames by u mod 8),
-//             in batches of 1, 2, 4, ... candidates per record in increasing u; the smallest equal u is the largest repeat
+//             record's first ones are the candidates (code = u) of the candidate list below
+//   compare   the list's compare with the functor repeat_words: the prefix against the symbols from u (v_alignbit_b32
+//             re-frames by u mod 8); the smallest equal u is the largest repeat
 //   trim      the effective length L - t per record; the symbols behind it become zero in the device copy of the words
+// The candidate list, one engine for both: an owner (a member's sort position; a record) has candidates (owner, code).
+//   collect   the mode's candidate kernel hands out slots through put_candidates: a wave's ballot, one atomic on the list's
+//             total and one on the owner's counter; what lies past the list's end is counted and not written, and the host
+//             then grows the list to the count and runs the pass again
+//   order     two radix sorts: by code, then (stable) by owner; a scan of the counters gives every owner's segment
+//   verify    batches of 1, 2, 4, ... candidates per owner still without a result, in increasing code: k_batch counts the
+//             tasks, k_compare<functor> runs one wave per (owner, candidate, chunk) -- a mismatch sets the candidate's flag,
+//             a set flag ends its other chunks early -- and k_pick takes the atomicMin of the codes without a flag
 // Contained mode (vg_deduplicate_contained): a record that is a substring of a longer record, or of its reverse complement,
 // is removed as well.
 //   windows   one thread per symbol position of a pass: the 16 symbols from it as one 64-bit key, the first symbol in the
@@ -422,69 +429,115 @@ __global__ void k_ckeys(const unsigned long long* h, const int64_t* len, int64_t
 }
 static_assert(HASH_CHUNK == VERIFY_CHUNK, "the candidate pass cuts a record as for_windows does");
 __device__ __forceinline__ int64_t chunks_of(int64_t L) { return max((int64_t)1, (((L + 7) >> 3) + VERIFY_CHUNK - 1) / VERIFY_CHUNK); }
+
+// ---------------------------------------------------------------- device: the candidate engine
+// Circular mode and the terminal repeats share it.  An owner (a sort position p of a round; a record i of the repeat pass)
+// has nch[owner] compare chunks (0: it takes no part), candidates (owner, code) in one list, and a result res[owner]: the
+// smallest code whose compare finds no difference, NO_OFFSET while there is none.  A mode brings its candidate kernel
+// (which windows are candidates) and its compare functor (which two words a lane XORs); everything else is below.
 constexpr unsigned long long NO_OFFSET = ~0ull;
-// candidate tasks per position: the chunks of a member (one for an empty record), 0 for a head; res[p] = no offset yet
-__global__ void k_ctasks(const int32_t* A, int64_t na, const int64_t* hp, const int64_t* len, int64_t* cnt, unsigned long long* res) {
+struct cand_slots { unsigned long long cap; uint64_t* owner; uint64_t* code; unsigned long long* ccnt; unsigned long long* total; };
+// Slot hand-out, called by every lane of a wave with hits = __ballot(hit): lane 0 adds the hits to the list's total and to
+// the owner's counter, every hit takes the next slot in lane order.  What lies past `cap` is counted and not written (the
+// host grows the list and repeats the pass).
+__device__ __forceinline__ void put_candidates(const cand_slots& to, uint64_t hits, bool hit, int64_t owner, uint64_t code, int lane) {
+    if (!hits) return;
+    unsigned long long at = 0;
+    if (lane == 0) { at = atomicAdd(to.total, (unsigned long long)__popcll(hits)); atomicAdd(to.ccnt + owner, (unsigned long long)__popcll(hits)); }
+    const unsigned long long slot = __shfl(at, 0) + (unsigned long long)__popcll(hits & ((1ull << lane) - 1));
+    if (hit && slot < to.cap) { to.owner[slot] = (uint64_t)owner; to.code[slot] = code; }
+}
+// compare tasks of a batch per owner: (its candidates of rank lo .. hi - 1) x chunks; none for owners without chunks and for
+// those that have their result; cnt[n_own] = 0 (the total's slot)
+__global__ void k_batch(int64_t n_own, const int64_t* nch, const unsigned long long* res, const int64_t* ccnt, int64_t lo, int64_t hi,
+                        int64_t* cnt) {
+    for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o <= n_own; o += (int64_t)gridDim.x * blockDim.x) {
+        if (o == n_own) { cnt[o] = 0; continue; }
+        const bool open = nch[o] != 0 && res[o] == NO_OFFSET;
+        cnt[o] = open ? max((int64_t)0, min(ccnt[o], hi) - lo) * nch[o] : 0;
+    }
+}
+// the valid symbols of a compared word of which `left` symbols (>= 1) are left
+__device__ __forceinline__ uint32_t word_mask(int64_t left) { return left >= 8 ? ~0u : (1u << (4 * left)) - 1; }
+// One wave per (owner, candidate, chunk).  pair.of(owner, code) is the candidate's compare: nw words, and words(k, x, y,
+// mask) gives the two words at k and the mask of their valid symbols.  A mismatch sets the candidate's flag; a set flag ends
+// the other chunks of that candidate early.
+template <class Pair>
+__global__ void __launch_bounds__(TPB) k_compare(const Pair pair, const int64_t* __restrict__ nch, int64_t n_own, const int64_t* __restrict__ tbeg,
+                                                 int64_t n_tasks, const int64_t* __restrict__ cbeg, int64_t lo,
+                                                 const uint64_t* __restrict__ cand_code, uint8_t* bad) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
+        const int64_t o = owner_of(tbeg, n_own, t), local = t - tbeg[o];
+        const int64_t g = cbeg[o] + lo + local / nch[o], c = local % nch[o];
+        if (bad[g]) continue;
+        const auto cand = pair.of(o, cand_code[g]);
+        bool diff = false;
+        for (int64_t base = c * VERIFY_CHUNK, k1 = min(cand.nw, (c + 1) * VERIFY_CHUNK); base < k1; base += 64) {
+            const int64_t k = base + lane;
+            if (k < k1) {
+                uint32_t x, y, mask;
+                cand.words(k, x, y, mask);
+                diff = ((x ^ y) & mask) != 0;
+            }
+            if (__ballot(diff)) break;
+        }
+        if (__ballot(diff) && lane == 0) bad[g] = 1;
+    }
+}
+// the smallest code of the batch without a mismatch is the owner's result; count (may be null): count[0] += candidates of
+// the batch, count[1] += the equal ones
+__global__ void k_pick(const int64_t* nch, int64_t n_own, const int64_t* tbeg, int64_t n_tasks, const int64_t* cbeg, int64_t lo,
+                       const uint64_t* cand_code, const uint8_t* bad, unsigned long long* res, unsigned long long* count) {
+    int nc = 0, ne = 0;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tasks; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = owner_of(tbeg, n_own, t), local = t - tbeg[o];
+        if (local % nch[o]) continue;
+        const int64_t g = cbeg[o] + lo + local / nch[o];
+        ++nc;
+        if (!bad[g]) { atomicMin(res + o, (unsigned long long)cand_code[g]); ++ne; }
+    }
+    if (!count) return;
+    for (int o = 32; o > 0; o >>= 1) { nc += __shfl_xor(nc, o); ne += __shfl_xor(ne, o); }
+    if ((threadIdx.x & 63) == 0 && nc) { atomicAdd(count, (unsigned long long)nc); atomicAdd(count + 1, (unsigned long long)ne); }
+}
+
+// ---------------------------------------------------------------- device: circular mode's candidates and compare
+// owners of a round: nch[p] = the chunks of a member (one for an empty record), 0 for a head: its candidate tasks and the
+// chunks of each compare; nch[na] = 0 (the total's slot); res[p] = no offset yet
+__global__ void k_ctasks(const int32_t* A, int64_t na, const int64_t* hp, const int64_t* len, int64_t* nch, unsigned long long* res) {
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= na; p += (int64_t)gridDim.x * blockDim.x) {
-        if (p == na) { cnt[p] = 0; continue; }
-        cnt[p] = hp[p] == p ? 0 : chunks_of(len[A[p]]);
+        if (p == na) { nch[p] = 0; continue; }
+        nch[p] = hp[p] == p ? 0 : chunks_of(len[A[p]]);
         res[p] = NO_OFFSET;
     }
 }
 // One wave per (member, chunk of the head).  removed == rot(Y, s) needs Y's window at s to equal the member's window at 0.
 // Y = head: s = u for every u whose window equals it.  Y = revcomp(head): Y's window at s is the reverse complement of the
 // head's window at (L - 16 - s) mod L, so s = (L - 16 - u) mod L for every u whose window equals the reverse complement of
-// the member's.  Code of a candidate: strand << sbits | s.  Slots are handed out by a global counter; what lies past `cap` is
-// counted and not written (the caller grows the list and repeats).
+// the member's.  Code of a candidate: strand << sbits | s.
 __global__ void __launch_bounds__(TPB) k_ccand(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
                                                const int32_t* __restrict__ A, int64_t na, const int64_t* __restrict__ hp,
-                                               const int64_t* __restrict__ tbeg, int64_t n_tasks, int sbits, unsigned long long cap,
-                                               uint64_t* cand_p, uint64_t* cand_code, unsigned long long* ccnt, unsigned long long* total) {
+                                               const int64_t* __restrict__ tbeg, int64_t n_tasks, int sbits, const cand_slots to) {
     const int lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1;
     for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
         const int64_t p = owner_of(tbeg, na, t), c = t - tbeg[p];
         const int32_t m = A[p], hd = A[hp[p]];
         const int64_t L = len[m];
         const uint32_t* M = W + woff[m];
         if (L == 0) {          // (all empty records are equal: offset 0 on the forward strand)
-            if (lane == 0) {
-                const unsigned long long at = atomicAdd(total, 1ull);
-                atomicAdd(ccnt + p, 1ull);
-                if (at < cap) { cand_p[at] = (uint64_t)p; cand_code[at] = 0; }
-            }
+            put_candidates(to, 1ull, lane == 0, p, 0ull, lane);
             continue;
         }
         const uint64_t m0 = L < 16 ? gather(M, L, 0, 16) : ((uint64_t)M[0] | ((uint64_t)M[1] << 32)), r0 = rc_window(m0);
         for_windows(W + woff[hd], L, c, lane, [&](bool valid, int64_t u, uint64_t w) {
             const bool mf = valid && w == m0, mr = valid && w == r0;
             const uint64_t bf = __ballot(mf), br = __ballot(mr);
-            if (bf | br) {
-                const unsigned long long nf = (unsigned long long)__popcll(bf), nr = (unsigned long long)__popcll(br);
-                unsigned long long at = 0;
-                if (lane == 0) { at = atomicAdd(total, nf + nr); atomicAdd(ccnt + p, nf + nr); }
-                at = __shfl(at, 0);
-                if (mf) {
-                    const unsigned long long slot = at + (unsigned long long)__popcll(bf & below);
-                    if (slot < cap) { cand_p[slot] = (uint64_t)p; cand_code[slot] = (uint64_t)u; }
-                }
-                if (mr) {
-                    const unsigned long long slot = at + nf + (unsigned long long)__popcll(br & below);
-                    const int64_t s = (L - (16 + u) % L) % L;
-                    if (slot < cap) { cand_p[slot] = (uint64_t)p; cand_code[slot] = (1ull << sbits) | (uint64_t)s; }
-                }
+            if (bf | br) {     // (one branch per window without a hit; a hand-out per strand inside it)
+                put_candidates(to, bf, mf, p, (uint64_t)u, lane);
+                put_candidates(to, br, mr, p, mr ? (1ull << sbits) | (uint64_t)((L - (16 + u) % L) % L) : 0ull, lane);
             }
         });
-    }
-}
-// compare tasks of a batch per position: (the member's candidates of rank lo .. hi - 1) x chunks; none for heads and for
-// members that have their offset
-__global__ void k_cbatch(const int32_t* A, int64_t na, const int64_t* hp, const int64_t* len, const unsigned long long* res,
-                         const int64_t* ccnt, int64_t lo, int64_t hi, int64_t* cnt) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= na; p += (int64_t)gridDim.x * blockDim.x) {
-        if (p == na) { cnt[p] = 0; continue; }
-        const bool open = hp[p] != p && res[p] == NO_OFFSET;
-        cnt[p] = open ? max((int64_t)0, min(ccnt[p], hi) - lo) * chunks_of(len[A[p]]) : 0;
     }
 }
 // 8 cyclic symbols of a record from b < L: one re-framed pair of words, or symbol by symbol across the wrap point
@@ -492,51 +545,25 @@ __device__ __forceinline__ uint32_t cyc8(const uint32_t* R, int64_t L, int64_t b
     if (b + 8 <= L) { const int64_t w = b >> 3; return __builtin_amdgcn_alignbit(R[w + 1], R[w], (uint32_t)(4 * (b & 7))); }
     return (uint32_t)gather(R, L, b, 8);
 }
-// One wave per (member, candidate, chunk): member word k against the 8 symbols of Y from (8 k + s) mod L; for
-// Y = revcomp(head) these are the bit reversal of the head's 8 symbols from (L - 8 - pos) mod L.  A mismatch sets the
-// candidate's flag; a set flag ends the other chunks of that candidate early.
-__global__ void __launch_bounds__(TPB) k_ccompare(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
-                                                  const int32_t* __restrict__ A, int64_t na, const int64_t* __restrict__ hp,
-                                                  const int64_t* __restrict__ tbeg, int64_t n_tasks, const int64_t* __restrict__ cbeg, int64_t lo,
-                                                  const uint64_t* __restrict__ cand_code, int sbits, uint8_t* bad) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
-        const int64_t p = owner_of(tbeg, na, t), local = t - tbeg[p];
-        const int32_t m = A[p], hd = A[hp[p]];
-        const int64_t L = len[m], nw = (L + 7) >> 3, nch = chunks_of(L);
-        const int64_t g = cbeg[p] + lo + local / nch, c = local % nch;
-        if (bad[g]) continue;
-        const uint64_t code = cand_code[g];
-        const bool rcs = (code >> sbits) != 0;
-        const int64_t s = (int64_t)(code & ((1ull << sbits) - 1));
-        const uint32_t* M = W + woff[m]; const uint32_t* H = W + woff[hd];
-        bool diff = false;
-        for (int64_t base = c * VERIFY_CHUNK, k1 = min(nw, (c + 1) * VERIFY_CHUNK); base < k1; base += 64) {
-            const int64_t k = base + lane;
-            if (k < k1) {
-                int64_t pos = 8 * k + s; if (pos >= L) pos -= L;
-                uint32_t y;
-                if (rcs) { int64_t b = (L - 8 - pos) % L; if (b < 0) b += L; y = __builtin_bitreverse32(cyc8(H, L, b)); }
-                else y = cyc8(H, L, pos);
-                const int64_t nv = min((int64_t)8, L - 8 * k);
-                const uint32_t mask = nv == 8 ? ~0u : (1u << (4 * nv)) - 1;
-                diff = ((M[k] ^ y) & mask) != 0;
-            }
-            if (__ballot(diff)) break;
+// The compare of position p's member with Y rotated by s (code = strand << sbits | s): member word k against the 8 symbols
+// of Y from (8 k + s) mod L; for Y = revcomp(head) these are the bit reversal of the head's 8 symbols from (L - 8 - pos) mod L.
+struct rotation_words {
+    const uint32_t* W; const int64_t* woff; const int64_t* len; const int32_t* A; const int64_t* hp; int sbits;
+    struct cand {
+        const uint32_t* M; const uint32_t* H; int64_t L, s, nw; bool rcs;
+        __device__ __forceinline__ void words(int64_t k, uint32_t& x, uint32_t& y, uint32_t& mask) const {
+            int64_t pos = 8 * k + s; if (pos >= L) pos -= L;
+            if (rcs) { int64_t b = (L - 8 - pos) % L; if (b < 0) b += L; y = __builtin_bitreverse32(cyc8(H, L, b)); }
+            else y = cyc8(H, L, pos);
+            x = M[k]; mask = word_mask(L - 8 * k);
         }
-        if (__ballot(diff) && lane == 0) bad[g] = 1;
+    };
+    __device__ __forceinline__ cand of(int64_t p, uint64_t code) const {
+        const int32_t m = A[p];
+        const int64_t L = len[m];
+        return { W + woff[m], W + woff[A[hp[p]]], L, (int64_t)(code & ((1ull << sbits) - 1)), (L + 7) >> 3, (code >> sbits) != 0 };
     }
-}
-// the smallest candidate of the batch without a mismatch is the member's (strand, offset)
-__global__ void k_cpick(const int32_t* A, int64_t na, const int64_t* len, const int64_t* tbeg, int64_t n_tasks, const int64_t* cbeg, int64_t lo,
-                        const uint64_t* cand_code, const uint8_t* bad, unsigned long long* res) {
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tasks; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = owner_of(tbeg, na, t), local = t - tbeg[p], nch = chunks_of(len[A[p]]);
-        if (local % nch) continue;
-        const int64_t g = cbeg[p] + lo + local / nch;
-        if (!bad[g]) atomicMin(res + p, (unsigned long long)cand_code[g]);
-    }
-}
+};
 // heads keep themselves, members with an offset join their head, the others stay (keep[p] = 1)
 __global__ void k_cresolve(const int32_t* A, int64_t na, const int64_t* hp, const unsigned long long* res, int sbits,
                            int32_t* rep, int8_t* strand, int64_t* off, int32_t* keep, unsigned long long* n_diff) {
@@ -556,16 +583,18 @@ __global__ void k_cresolve(const int32_t* A, int64_t na, const int64_t* hp, cons
 // ---------------------------------------------------------------- device: terminal repeats
 // tr(X): the largest t in [m, L / 2] with X[0 : t) == X[u : L), u = L - t.  The starts u are ceil(L / 2) .. L - m.
 __device__ __forceinline__ int64_t tr_first_start(int64_t L) { return L - (L >> 1); }
-// compare chunks of a record's candidates: a repeat has at most L / 2 symbols
-__device__ __forceinline__ int64_t tr_chunks_of(int64_t L) { return chunks_of(L >> 1); }
+// owners of the pass: every record; a repeat has at most L / 2 symbols: the chunks of each compare; res[i] = no start yet
+__global__ void k_ttasks(int64_t n, const int64_t* len, int64_t* nch, unsigned long long* res) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        nch[i] = chunks_of(len[i] >> 1);
+        res[i] = NO_OFFSET;
+    }
+}
 // One wave per (record, chunk).  X[0 : t) == X[u : L) needs the w = min(16, m) symbols from u to equal the record's first w
-// symbols; u + w <= L, so the low w symbols of the window at u lie inside the record.  Every such u is a candidate.  Slots
-// are handed out by a global counter; what lies past `cap` is counted and not written (the caller grows the list and repeats).
+// symbols; u + w <= L, so the low w symbols of the window at u lie inside the record.  Every such u is a candidate; its code is u.
 __global__ void __launch_bounds__(TPB) k_tcand(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
-                                               const int64_t* __restrict__ cbeg, int64_t n, int64_t n_tasks, int64_t m, unsigned long long cap,
-                                               uint64_t* cand_rec, uint64_t* cand_u, unsigned long long* ccnt, unsigned long long* total) {
+                                               const int64_t* __restrict__ cbeg, int64_t n, int64_t n_tasks, int64_t m, const cand_slots to) {
     const int lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1;
     const int w = (int)min((int64_t)16, m);
     const uint64_t wmask = w == 16 ? ~0ull : (1ull << (4 * w)) - 1;
     for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
@@ -577,69 +606,27 @@ __global__ void __launch_bounds__(TPB) k_tcand(const uint32_t* __restrict__ W, c
         const uint64_t m0 = (L < 16 ? gather(R, L, 0, 16) : ((uint64_t)R[0] | ((uint64_t)R[1] << 32))) & wmask;
         for_windows(R, L, c, lane, [&](bool valid, int64_t u, uint64_t win) {
             const bool hit = valid && u >= u0 && u <= u1 && (win & wmask) == m0;
-            const uint64_t b = __ballot(hit);
-            if (b) {
-                unsigned long long at = 0;
-                if (lane == 0) { at = atomicAdd(total, (unsigned long long)__popcll(b)); atomicAdd(ccnt + i, (unsigned long long)__popcll(b)); }
-                at = __shfl(at, 0) + (unsigned long long)__popcll(b & below);
-                if (hit && at < cap) { cand_rec[at] = (uint64_t)i; cand_u[at] = (uint64_t)u; }
-            }
+            put_candidates(to, __ballot(hit), hit, i, (uint64_t)u, lane);
         });
     }
 }
-// compare tasks of a batch per record: (its candidates of rank lo .. hi - 1) x chunks; none once the record has its repeat
-__global__ void k_tbatch(int64_t n, const int64_t* len, const unsigned long long* res, const int64_t* ccnt, int64_t lo, int64_t hi,
-                         int64_t* cnt) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += (int64_t)gridDim.x * blockDim.x) {
-        if (i == n) { cnt[i] = 0; continue; }
-        cnt[i] = res[i] == NO_OFFSET ? max((int64_t)0, min(ccnt[i], hi) - lo) * tr_chunks_of(len[i]) : 0;
-    }
-}
-// One wave per (record, candidate, chunk): word k of the prefix against the 8 symbols from u + 8 k, two neighbouring words
-// re-framed by u mod 8 symbols (the word behind the record's last is read and shifted out or masked: the packed buffer ends
-// with zero words).  The last word is masked to t mod 8 symbols.  A mismatch sets the candidate's flag; a set flag ends the
-// candidate's other chunks early.
-__global__ void __launch_bounds__(TPB) k_tcompare(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
-                                                  int64_t n, const int64_t* __restrict__ tbeg, int64_t n_tasks, const int64_t* __restrict__ cbeg,
-                                                  int64_t lo, const uint64_t* __restrict__ cand_u, uint8_t* bad) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
-        const int64_t i = owner_of(tbeg, n, t), local = t - tbeg[i];
-        const int64_t L = len[i], nch = tr_chunks_of(L);
-        const int64_t g = cbeg[i] + lo + local / nch, c = local % nch;
-        if (bad[g]) continue;
-        const int64_t u = (int64_t)cand_u[g], tl = L - u, nw = (tl + 7) >> 3;
-        const uint32_t sh = (uint32_t)(4 * (u & 7));
-        const uint32_t* R = W + woff[i]; const uint32_t* S = R + (u >> 3);
-        bool diff = false;
-        for (int64_t base = c * VERIFY_CHUNK, k1 = min(nw, (c + 1) * VERIFY_CHUNK); base < k1; base += 64) {
-            const int64_t k = base + lane;
-            if (k < k1) {
-                const uint32_t y = __builtin_amdgcn_alignbit(S[k + 1], S[k], sh);
-                const int64_t nv = min((int64_t)8, tl - 8 * k);
-                const uint32_t mask = nv == 8 ? ~0u : (1u << (4 * nv)) - 1;
-                diff = ((R[k] ^ y) & mask) != 0;
-            }
-            if (__ballot(diff)) break;
+// The compare of record i's prefix with its symbols from u (code = u): word k of the prefix against the 8 symbols from
+// u + 8 k, two neighbouring words re-framed by u mod 8 symbols (the word behind the record's last is read and shifted out or
+// masked: the packed buffer ends with zero words).  The last word is masked to t mod 8 symbols.
+struct repeat_words {
+    const uint32_t* W; const int64_t* woff; const int64_t* len;
+    struct cand {
+        const uint32_t* R; const uint32_t* S; int64_t tl, nw; uint32_t sh;
+        __device__ __forceinline__ void words(int64_t k, uint32_t& x, uint32_t& y, uint32_t& mask) const {
+            x = R[k]; y = __builtin_amdgcn_alignbit(S[k + 1], S[k], sh); mask = word_mask(tl - 8 * k);
         }
-        if (__ballot(diff) && lane == 0) bad[g] = 1;
+    };
+    __device__ __forceinline__ cand of(int64_t i, uint64_t code) const {
+        const int64_t u = (int64_t)code, tl = len[i] - u;
+        const uint32_t* R = W + woff[i];
+        return { R, R + (u >> 3), tl, (tl + 7) >> 3, (uint32_t)(4 * (u & 7)) };
     }
-}
-// the smallest start of the batch without a mismatch is the record's (the largest repeat); count[0] += candidates of the
-// batch, count[1] += the equal ones
-__global__ void k_tpick(int64_t n, const int64_t* len, const int64_t* tbeg, int64_t n_tasks, const int64_t* cbeg, int64_t lo,
-                        const uint64_t* cand_u, const uint8_t* bad, unsigned long long* res, unsigned long long* count) {
-    int nc = 0, ne = 0;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tasks; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = owner_of(tbeg, n, t), local = t - tbeg[i], nch = tr_chunks_of(len[i]);
-        if (local % nch) continue;
-        const int64_t g = cbeg[i] + lo + local / nch;
-        ++nc;
-        if (!bad[g]) { atomicMin(res + i, (unsigned long long)cand_u[g]); ++ne; }
-    }
-    for (int o = 32; o > 0; o >>= 1) { nc += __shfl_xor(nc, o); ne += __shfl_xor(ne, o); }
-    if ((threadIdx.x & 63) == 0 && nc) { atomicAdd(count, (unsigned long long)nc); atomicAdd(count + 1, (unsigned long long)ne); }
-}
+};
 // repeat[i] = L - (the start found), 0 without one; eff[i] = L - repeat[i]
 __global__ void k_trepeat(int64_t n, const int64_t* len, const unsigned long long* res, int64_t* repeat, int64_t* eff) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -675,7 +662,7 @@ __device__ __forceinline__ uint64_t window_at(const uint32_t* R, int64_t L, int6
 // Index entry t of a pass: position pos0 + t of the concatenated records (pbeg = the records' first positions).  The key is
 // the bit reversal of the window: symbol k of the window sits in nibble 15 - k as its complement's code, so keys that share
 // their top 4 w bits are the windows that share their first w symbols.
-__global__ void k_cwindows(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+__global__ void k_sub_windows(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
                            const int64_t* __restrict__ pbeg, int64_t n, int64_t pos0, int64_t np, uint64_t* key, int64_t* val) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < np; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t g = pos0 + t, j = owner_of(pbeg, n, g);
@@ -686,7 +673,7 @@ __global__ void k_cwindows(const uint32_t* __restrict__ W, const int64_t* __rest
 // Query q = 2 i + strand: the sorted keys that start with the anchor, hlo[q] .. hlo[q] + hcnt[q] - 1.  Forward anchor: the
 // first w = min(anchor, L) symbols of X.  Reverse anchor: the first w symbols of revcomp(X), whose key is X's last w symbols
 // as they are packed, moved to the top bits (revcomp(X) lies in Y exactly when X lies in revcomp(Y)).  hcnt[2 n] = 0.
-__global__ void k_clookup(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len, int64_t n,
+__global__ void k_sub_lookup(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len, int64_t n,
                           int anchor, const uint64_t* __restrict__ key, int64_t np, int64_t* hlo, int64_t* hcnt) {
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q <= 2 * n; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = q >> 1, L = q < 2 * n ? len[i] : 0;
@@ -706,9 +693,9 @@ __global__ void k_clookup(const uint32_t* __restrict__ W, const int64_t* __restr
 // Hits h0 .. h1 - 1 of the pass (hoff = the queries' first hits): hit (i, strand) at position s of record j is a candidate
 // when j is longer and holds the whole record from s, or j is an earlier record of the same length and s = 0.  The queue has
 // room for every hit of the slice.
-__global__ void __launch_bounds__(TPB) k_ccands(const int64_t* __restrict__ len, const int64_t* __restrict__ pbeg, int64_t n,
-                                                const int64_t* __restrict__ hoff, const int64_t* __restrict__ hlo, const int64_t* __restrict__ val,
-                                                int64_t h0, int64_t h1, uint32_t* cq, int32_t* cj, int64_t* cs, unsigned long long* n_cand) {
+__global__ void __launch_bounds__(TPB) k_sub_cands(const int64_t* __restrict__ len, const int64_t* __restrict__ pbeg, int64_t n,
+                                                   const int64_t* __restrict__ hoff, const int64_t* __restrict__ hlo, const int64_t* __restrict__ val,
+                                                   int64_t h0, int64_t h1, uint32_t* cq, int32_t* cj, int64_t* cs, unsigned long long* n_cand) {
     const int lane = threadIdx.x & 63;
     const uint64_t below = (1ull << lane) - 1;
     for (int64_t h = h0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;; h += (int64_t)gridDim.x * blockDim.x) {
@@ -731,7 +718,7 @@ __global__ void __launch_bounds__(TPB) k_ccands(const int64_t* __restrict__ len,
     }
 }
 // verification tasks per candidate: the chunks of the record; bad[c] = 0; cnt[nc] = 0 (the total's slot)
-__global__ void k_cvtasks(const uint32_t* cq, int64_t nc, const int64_t* len, int64_t* cnt, uint32_t* bad) {
+__global__ void k_sub_tasks(const uint32_t* cq, int64_t nc, const int64_t* len, int64_t* cnt, uint32_t* bad) {
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= nc; c += (int64_t)gridDim.x * blockDim.x) {
         if (c == nc) { cnt[c] = 0; continue; }
         cnt[c] = chunks_of(len[cq[c] >> 1]);
@@ -741,9 +728,9 @@ __global__ void k_cvtasks(const uint32_t* cq, int64_t nc, const int64_t* len, in
 // One wave per (candidate, chunk): word k of X (forward) or of revcomp(X) (reverse: only the record is reversed) against
 // the 8 symbols of the container from s + 8 k, two neighbouring words re-framed by s mod 8 symbols.  The padding of the last
 // word is masked.  A mismatch sets the candidate's flag; a set flag ends the candidate's other chunks early.
-__global__ void __launch_bounds__(TPB) k_cverify(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
-                                                 const uint32_t* __restrict__ cq, const int32_t* __restrict__ cj, const int64_t* __restrict__ cs,
-                                                 int64_t nc, const int64_t* __restrict__ tbeg, int64_t n_tasks, uint32_t* bad) {
+__global__ void __launch_bounds__(TPB) k_sub_verify(const uint32_t* __restrict__ W, const int64_t* __restrict__ woff, const int64_t* __restrict__ len,
+                                                    const uint32_t* __restrict__ cq, const int32_t* __restrict__ cj, const int64_t* __restrict__ cs,
+                                                    int64_t nc, const int64_t* __restrict__ tbeg, int64_t n_tasks, uint32_t* bad) {
     const int lane = threadIdx.x & 63;
     for (int64_t t = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); t < n_tasks; t += (int64_t)gridDim.x * WAVES) {
         const int64_t c = owner_of(tbeg, nc, t), ch = t - tbeg[c];
@@ -775,7 +762,7 @@ __global__ void __launch_bounds__(TPB) k_cverify(const uint32_t* __restrict__ W,
 // best[i] = the largest key over the candidates without a flag: the container's rank from the end of the order (length
 // descending, index ascending), then '+' before '-', then the smallest offset.  The offset of a reverse hit is counted in
 // revcomp(container): revcomp(X) at s of Y is X at L_Y - L_X - s of revcomp(Y).  Keys are above 0 (an offset is below 2^sbits - 1).
-__global__ void k_cpick(const int64_t* len, const int32_t* rnk, int64_t n, const uint32_t* cq, const int32_t* cj, const int64_t* cs, int64_t nc,
+__global__ void k_sub_pick(const int64_t* len, const int32_t* rnk, int64_t n, const uint32_t* cq, const int32_t* cj, const int64_t* cs, int64_t nc,
                         const uint32_t* bad, int sbits, unsigned long long* best, unsigned long long* n_equal) {
     int e = 0;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += (int64_t)gridDim.x * blockDim.x) {
@@ -795,20 +782,35 @@ int grid_of(int64_t n, int per_block = TPB, int cap = 16384) {
 
 template <class K, class V>
 void sort_pairs(dbuf<K>& keys, dbuf<K>& keys2, dbuf<V>& vals, dbuf<V>& vals2, int64_t n, unsigned bits, hipStream_t s) {
-    size_t tb = 0;
-    VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)n, 0u, bits, s));
-    dbuf<char> tmp(std::max<size_t>(tb, 1));
-    VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)n, 0u, bits, s));
+    with_temp_storage([&](void* tmp, size_t& tb) {
+        return rocprim::radix_sort_pairs(tmp, tb, keys.p, keys2.p, vals.p, vals2.p, (size_t)n, 0u, bits, s); });
     std::swap(keys.p, keys2.p); std::swap(vals.p, vals2.p);
 }
 template <class T, class Op>
 void scan(const T* in, T* out, int64_t n, bool inclusive, Op op, hipStream_t s) {
-    size_t tb = 0;
-    if (inclusive) VG_HIP(rocprim::inclusive_scan(nullptr, tb, in, out, (size_t)n, op, s));
-    else VG_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, (T)0, (size_t)n, op, s));
-    dbuf<char> tmp(std::max<size_t>(tb, 1));
-    if (inclusive) VG_HIP(rocprim::inclusive_scan((void*)tmp.p, tb, in, out, (size_t)n, op, s));
-    else VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, in, out, (T)0, (size_t)n, op, s));
+    with_temp_storage([&](void* tmp, size_t& tb) {
+        return inclusive ? rocprim::inclusive_scan(tmp, tb, in, out, (size_t)n, op, s)
+                         : rocprim::exclusive_scan(tmp, tb, in, out, (T)0, (size_t)n, op, s); });
+}
+// the smallest b >= from (at most 64) with x < 2^b: the bits of a radix sort over keys up to x
+unsigned bit_width(uint64_t x, unsigned from) {
+    unsigned b = from;
+    while (b < 64 && (x >> b)) ++b;
+    return b;
+}
+// the (record, chunk of HASH_CHUNK words) tasks of records of len[i] symbols: cbeg[i] = record i's first task (an empty
+// record has one)
+struct chunk_tasks { std::vector<int64_t> cbeg; int64_t n_tasks = 0, max_len = 0, total_words = 0; };
+chunk_tasks chunk_tasks_of(const std::vector<int64_t>& len) {
+    chunk_tasks ct;
+    ct.cbeg.assign(len.size() + 1, 0);
+    for (size_t i = 0; i < len.size(); ++i) {
+        const int64_t nw = (len[i] + 7) >> 3;
+        ct.cbeg[i + 1] = ct.cbeg[i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
+        ct.max_len = std::max(ct.max_len, len[i]); ct.total_words += nw;
+    }
+    ct.n_tasks = ct.cbeg.back();
+    return ct;
 }
 
 // the three stable passes over the keys (low hash half, high half, length): equal keys end up adjacent, in index order
@@ -825,123 +827,111 @@ void sort_by_key(dbuf<uint64_t>& klo, dbuf<uint64_t>& khi, dbuf<uint64_t>& klen,
     }
 }
 
-// the candidate offsets of every member of a round, sorted by (position, strand, offset), and their flags
+// the candidate engine's list: the candidates (owner, code) of every owner, sorted by (owner, code) once order() has run,
+// and their flags
 struct cand_list {
-    dbuf<uint64_t> pos, code, pos2, code2;
+    dbuf<uint64_t> owner, code, owner2, code2;
     dbuf<uint8_t> bad;
-    dbuf<int64_t> cnt, beg;                  // per position (na + 1): the member's candidates and where they start
+    dbuf<int64_t> cnt, beg, nch;             // per owner (n + 1): its candidates, where they start, its compare chunks
     dbuf<unsigned long long> total;
+    void alloc_owners(int64_t n) { cnt.alloc((size_t)n + 1); beg.alloc((size_t)n + 1); nch.alloc((size_t)n + 1); total.alloc(1); }
 };
-
-// One round of the circular verification: res[p] = strand << sbits | offset of every member equal to its head in some
-// rotation of one of the head's strands, NO_OFFSET for the others.
-void circular_round(const packed_set& ps, const int64_t* d_woff, const int64_t* d_len, const int32_t* A, int64_t na, const int64_t* hp,
-                    dbuf<int64_t>& cnt, dbuf<int64_t>& tbeg, cand_list& cl, int sbits, unsigned long long* res, hipStream_t s) {
-    int64_t n_ct = 0;
+// Fills the list: produce(slots) launches the mode's candidate kernel over the n_own owners.  A list of cap0 slots (or the
+// one it has, if larger) is tried first; when more candidates were counted than it holds, nothing of it is used: it grows to
+// the count and the pass runs again.  -> the candidates
+template <class F>
+int64_t collect(cand_list& cl, int64_t n_own, size_t cap0, hipStream_t s, F produce) {
     unsigned long long n_cand = 0;
-    {
-        vg_prof_scope ps_("dedup_ccand", (double)na * 16.0);
-        hipLaunchKernelGGL(k_ctasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A, na, hp, d_len, cnt.p, res);
-        scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
-        vg_download_bytes(&n_ct, tbeg.p + na, sizeof n_ct, s);
+    for (size_t cap = cap0;; cap = (size_t)n_cand) {
+        if (cl.owner.n < cap) { cl.owner.alloc(cap); cl.code.alloc(cap); cl.owner2.alloc(cap); cl.code2.alloc(cap); cl.bad.alloc(cap); }
+        VG_HIP(hipMemsetAsync(cl.cnt.p, 0, (size_t)(n_own + 1) * sizeof(int64_t), s));
+        cl.total.zero(s);
+        produce(cand_slots{ (unsigned long long)cl.owner.n, cl.owner.p, cl.code.p, (unsigned long long*)cl.cnt.p, cl.total.p });
+        cl.total.download(&n_cand, 1, s);
         VG_HIP(hipStreamSynchronize(s));
-        if (n_ct == 0) return;               // (heads only)
-        for (size_t cap = std::max(cl.pos.n, (size_t)(4 * na + 1024));; cap = (size_t)n_cand) {
-            if (cl.pos.n < cap) { cl.pos.alloc(cap); cl.code.alloc(cap); cl.pos2.alloc(cap); cl.code2.alloc(cap); cl.bad.alloc(cap); }
-            VG_HIP(hipMemsetAsync(cl.cnt.p, 0, (size_t)(na + 1) * sizeof(int64_t), s));
-            cl.total.zero(s);
-            hipLaunchKernelGGL(k_ccand, dim3(grid_of(n_ct, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff, d_len, A, na, hp, tbeg.p, n_ct,
-                               sbits, (unsigned long long)cl.pos.n, cl.pos.p, cl.code.p, (unsigned long long*)cl.cnt.p, cl.total.p);
-            cl.total.download(&n_cand, 1, s);
-            VG_HIP(hipStreamSynchronize(s));
-            if (n_cand <= cl.pos.n) break;   // (else: the list was too short; nothing of it is used)
-        }
-        if (n_cand == 0) return;
-        unsigned pos_bits = 1; while (pos_bits < 64 && ((uint64_t)na >> pos_bits)) ++pos_bits;
-        sort_pairs(cl.code, cl.code2, cl.pos, cl.pos2, (int64_t)n_cand, (unsigned)sbits + 1, s);
-        sort_pairs(cl.pos, cl.pos2, cl.code, cl.code2, (int64_t)n_cand, pos_bits, s);
-        scan(cl.cnt.p, cl.beg.p, na + 1, false, rocprim::plus<int64_t>(), s);
-        VG_HIP(hipMemsetAsync(cl.bad.p, 0, (size_t)n_cand, s));
+        if (n_cand <= cl.owner.n) return (int64_t)n_cand;
     }
-    // candidates of rank [lo, lo + width) of every member still without an offset; the width doubles
-    for (int64_t lo = 0, width = 1;; lo += width, width *= 2) {
-        vg_prof_scope ps_("dedup_cverify", 0.0);
+}
+// sorts the n_cand candidates by (owner, code), gives every owner its segment and clears the flags
+void order(cand_list& cl, int64_t n_own, int64_t n_cand, unsigned code_bits, unsigned owner_bits, hipStream_t s) {
+    sort_pairs(cl.code, cl.code2, cl.owner, cl.owner2, n_cand, code_bits, s);
+    sort_pairs(cl.owner, cl.owner2, cl.code, cl.code2, n_cand, owner_bits, s);
+    scan(cl.cnt.p, cl.beg.p, n_own + 1, false, rocprim::plus<int64_t>(), s);
+    VG_HIP(hipMemsetAsync(cl.bad.p, 0, (size_t)n_cand, s));
+}
+// Compares the candidates of rank [lo, lo + width) of every owner still without a result; the width doubles, so the first
+// batch with an equal candidate holds the owner's smallest equal code.  One read-back per batch.  cnt, tbeg: n_own + 1
+// each; count: k_pick's counters, or null.  -> the batches launched
+template <class Pair>
+int64_t verify_batches(cand_list& cl, int64_t n_own, const Pair& pair, dbuf<int64_t>& cnt, dbuf<int64_t>& tbeg, unsigned long long* res,
+                       unsigned long long* count, hipStream_t s) {
+    for (int64_t batches = 0, lo = 0, width = 1;; ++batches, lo += width, width *= 2) {
         int64_t n_vt = 0;
-        hipLaunchKernelGGL(k_cbatch, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A, na, hp, d_len, res, cl.cnt.p, lo, lo + width, cnt.p);
-        scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
-        vg_download_bytes(&n_vt, tbeg.p + na, sizeof n_vt, s);
+        hipLaunchKernelGGL(k_batch, dim3(grid_of(n_own + 1)), dim3(TPB), 0, s, n_own, cl.nch.p, res, cl.cnt.p, lo, lo + width, cnt.p);
+        scan(cnt.p, tbeg.p, n_own + 1, false, rocprim::plus<int64_t>(), s);
+        vg_download_bytes(&n_vt, tbeg.p + n_own, sizeof n_vt, s);
         VG_HIP(hipStreamSynchronize(s));
-        if (n_vt == 0) break;
-        hipLaunchKernelGGL(k_ccompare, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff, d_len, A, na, hp, tbeg.p, n_vt,
-                           cl.beg.p, lo, cl.code.p, sbits, cl.bad.p);
-        hipLaunchKernelGGL(k_cpick, dim3(grid_of(n_vt)), dim3(TPB), 0, s, A, na, d_len, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res);
+        if (n_vt == 0) return batches;
+        hipLaunchKernelGGL(k_compare<Pair>, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, pair, cl.nch.p, n_own, tbeg.p, n_vt, cl.beg.p, lo,
+                           cl.code.p, cl.bad.p);
+        hipLaunchKernelGGL(k_pick, dim3(grid_of(n_vt)), dim3(TPB), 0, s, cl.nch.p, n_own, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res, count);
     }
 }
 
+// One round of the circular verification: res[p] = strand << sbits | offset of every member equal to its head in some
+// rotation of one of the head's strands, NO_OFFSET for the others.  Candidates sorted by (position, strand, offset).
+void circular_round(const packed_set& ps, const int64_t* d_woff, const int64_t* d_len, const int32_t* A, int64_t na, const int64_t* hp,
+                    dbuf<int64_t>& cnt, dbuf<int64_t>& tbeg, cand_list& cl, int sbits, unsigned long long* res, hipStream_t s) {
+    {
+        vg_prof_scope ps_("dedup_ccand", (double)na * 16.0);
+        int64_t n_ct = 0;
+        hipLaunchKernelGGL(k_ctasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A, na, hp, d_len, cl.nch.p, res);
+        scan(cl.nch.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+        vg_download_bytes(&n_ct, tbeg.p + na, sizeof n_ct, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (n_ct == 0) return;               // (heads only)
+        const int64_t n_cand = collect(cl, na, std::max(cl.owner.n, (size_t)(4 * na + 1024)), s, [&](const cand_slots& to) {
+            hipLaunchKernelGGL(k_ccand, dim3(grid_of(n_ct, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff, d_len, A, na, hp, tbeg.p, n_ct,
+                               sbits, to); });
+        if (n_cand == 0) return;
+        order(cl, na, n_cand, (unsigned)sbits + 1, bit_width((uint64_t)na, 1), s);
+    }
+    vg_prof_scope ps_("dedup_cverify", 0.0);
+    verify_batches(cl, na, rotation_words{ ps.d_words.p, d_woff, d_len, A, hp, sbits }, cnt, tbeg, res, nullptr, s);
+}
+
 // The terminal repeats of the packed records (resident): repeat_out[i] = tr(record i) for the minimum m >= 1.  Candidate
-// starts in increasing order per record, compared in batches of 1, 2, 4, ... per record; the first batch with an equal
-// candidate holds the smallest start, i.e. the largest repeat.  trim: the device copy of every record is cut to its circle
-// (symbols at or past L - tr become zero); the host copy stays.
+// starts in increasing order per record: the smallest equal start is the largest repeat.  trim: the device copy of every
+// record is cut to its circle (symbols at or past L - tr become zero); the host copy stays.
 void repeats_device(const packed_set& ps, int64_t m, int64_t* repeat_out, vg_dedup_repeat_stats& rst, bool trim) {
     const int64_t n = ps.n;
     if (n == 0) return;
     hipStream_t s = vg_stream();
-    int64_t max_len = 0, total_words = 0;
-    std::vector<int64_t> cbeg((size_t)n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t nw = (ps.len[(size_t)i] + 7) >> 3;
-        cbeg[(size_t)i + 1] = cbeg[(size_t)i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
-        max_len = std::max(max_len, ps.len[(size_t)i]); total_words += nw;
-    }
-    const int64_t n_tasks = cbeg[(size_t)n];
-    unsigned ubits = 1; while (ubits < 64 && (max_len >> ubits)) ++ubits;
-    unsigned rec_bits = 1; while (rec_bits < 64 && ((uint64_t)n >> rec_bits)) ++rec_bits;
+    const chunk_tasks ct = chunk_tasks_of(ps.len);
     dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1), d_rep((size_t)n), d_eff((size_t)n);
-    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
+    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(ct.cbeg.data(), (size_t)n + 1, s);
     dbuf<unsigned long long> res((size_t)n), d_count(2);
-    VG_HIP(hipMemsetAsync(res.p, 0xff, res.bytes(), s));          // (NO_OFFSET)
+    cand_list cl;
+    cl.alloc_owners(n);
+    hipLaunchKernelGGL(k_ttasks, dim3(grid_of(n)), dim3(TPB), 0, s, n, d_len.p, cl.nch.p, res.p);
     d_count.zero(s);
     {
-        vg_prof_scope ps_("dedup_trepeat", (double)total_words * 2.0);
-        cand_list cl;
-        cl.cnt.alloc((size_t)n + 1); cl.beg.alloc((size_t)n + 1); cl.total.alloc(1);
-        unsigned long long n_cand = 0;
-        for (size_t cap = (size_t)(2 * n + 1024);; cap = (size_t)n_cand) {
-            if (cl.pos.n < cap) { cl.pos.alloc(cap); cl.code.alloc(cap); cl.pos2.alloc(cap); cl.code2.alloc(cap); cl.bad.alloc(cap); }
-            VG_HIP(hipMemsetAsync(cl.cnt.p, 0, (size_t)(n + 1) * sizeof(int64_t), s));
-            cl.total.zero(s);
-            hipLaunchKernelGGL(k_tcand, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, m,
-                               (unsigned long long)cl.pos.n, cl.pos.p, cl.code.p, (unsigned long long*)cl.cnt.p, cl.total.p);
-            cl.total.download(&n_cand, 1, s);
-            VG_HIP(hipStreamSynchronize(s));
-            if (n_cand <= cl.pos.n) break;   // (else: the list was too short; nothing of it is used)
-        }
+        vg_prof_scope ps_("dedup_trepeat", (double)ct.total_words * 2.0);
+        const int64_t n_cand = collect(cl, n, (size_t)(2 * n + 1024), s, [&](const cand_slots& to) {
+            hipLaunchKernelGGL(k_tcand, dim3(grid_of(ct.n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n,
+                               ct.n_tasks, m, to); });
         if (n_cand > 0) {
             dbuf<int64_t> cnt((size_t)n + 1), tbeg((size_t)n + 1);
-            sort_pairs(cl.code, cl.code2, cl.pos, cl.pos2, (int64_t)n_cand, ubits, s);
-            sort_pairs(cl.pos, cl.pos2, cl.code, cl.code2, (int64_t)n_cand, rec_bits, s);
-            scan(cl.cnt.p, cl.beg.p, n + 1, false, rocprim::plus<int64_t>(), s);
-            VG_HIP(hipMemsetAsync(cl.bad.p, 0, (size_t)n_cand, s));
-            for (int64_t lo = 0, width = 1;; lo += width, width *= 2) {
-                int64_t n_vt = 0;
-                hipLaunchKernelGGL(k_tbatch, dim3(grid_of(n + 1)), dim3(TPB), 0, s, n, d_len.p, res.p, cl.cnt.p, lo, lo + width, cnt.p);
-                scan(cnt.p, tbeg.p, n + 1, false, rocprim::plus<int64_t>(), s);
-                vg_download_bytes(&n_vt, tbeg.p + n, sizeof n_vt, s);
-                VG_HIP(hipStreamSynchronize(s));
-                if (n_vt == 0) break;
-                ++rst.batches;
-                hipLaunchKernelGGL(k_tcompare, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, n, tbeg.p, n_vt,
-                                   cl.beg.p, lo, cl.code.p, cl.bad.p);
-                hipLaunchKernelGGL(k_tpick, dim3(grid_of(n_vt)), dim3(TPB), 0, s, n, d_len.p, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res.p,
-                                   d_count.p);
-            }
+            order(cl, n, n_cand, bit_width((uint64_t)ct.max_len, 1), bit_width((uint64_t)n, 1), s);
+            rst.batches += verify_batches(cl, n, repeat_words{ ps.d_words.p, d_woff.p, d_len.p }, cnt, tbeg, res.p, d_count.p, s);
         }
     }
     {
         vg_prof_scope ps_("dedup_trim", (double)n * 32.0);
         hipLaunchKernelGGL(k_trepeat, dim3(grid_of(n)), dim3(TPB), 0, s, n, d_len.p, res.p, d_rep.p, d_eff.p);
         if (trim)
-            hipLaunchKernelGGL(k_trim, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_eff.p, d_cbeg.p, n, n_tasks);
+            hipLaunchKernelGGL(k_trim, dim3(grid_of(ct.n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_eff.p, d_cbeg.p, n,
+                               ct.n_tasks);
     }
     unsigned long long count[2] = { 0, 0 };
     d_rep.download(repeat_out, (size_t)n, s);
@@ -960,18 +950,12 @@ void dedup_device(const packed_set& ps, const std::vector<int64_t>& len, int32_t
     const bool circular = off_out != nullptr;
     hipStream_t s = vg_stream();
     const int bits = g_hash_bits.load();
-    int64_t total_words = 0, max_len = 0;
-    std::vector<int64_t> cbeg((size_t)n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t nw = (len[(size_t)i] + 7) >> 3;
-        cbeg[(size_t)i + 1] = cbeg[(size_t)i] + std::max<int64_t>(1, (nw + HASH_CHUNK - 1) / HASH_CHUNK);
-        total_words += nw; max_len = std::max(max_len, len[(size_t)i]);
-    }
-    unsigned len_bits = 0; while (len_bits < 64 && (max_len >> len_bits)) ++len_bits;
+    const chunk_tasks ct = chunk_tasks_of(len);
+    const int64_t n_tasks = ct.n_tasks, total_words = ct.total_words;
+    const unsigned len_bits = bit_width((uint64_t)ct.max_len, 0);
     const int sbits = (int)std::max(1u, len_bits);       // circular mode: an offset is below the length
-    const int64_t n_tasks = cbeg[(size_t)n];
     dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1);
-    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(len.data(), (size_t)n, s); d_cbeg.upload(cbeg.data(), (size_t)n + 1, s);
+    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(len.data(), (size_t)n, s); d_cbeg.upload(ct.cbeg.data(), (size_t)n + 1, s);
     dbuf<unsigned long long> d_h((size_t)n * 4);
     d_h.zero(s);
     if (circular) {
@@ -1000,7 +984,7 @@ void dedup_device(const packed_set& ps, const std::vector<int64_t>& len, int32_t
     dbuf<int64_t> d_off;
     dbuf<unsigned long long> res;
     cand_list cl;
-    if (circular) { d_off.alloc((size_t)n); res.alloc((size_t)n); cl.cnt.alloc((size_t)n + 1); cl.beg.alloc((size_t)n + 1); cl.total.alloc(1); }
+    if (circular) { d_off.alloc((size_t)n); res.alloc((size_t)n); cl.alloc_owners(n); }
     int64_t na = n;
     while (na > 0) {
         ++st.rounds;
@@ -1098,7 +1082,7 @@ void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out
             dbuf<int64_t> val((size_t)np);
             {
                 vg_prof_scope ps_("dedupc_windows", (double)np * 16.5);
-                hipLaunchKernelGGL(k_cwindows, dim3(grid_of(np, TPB, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_pbeg.p, n, pos0, np,
+                hipLaunchKernelGGL(k_sub_windows, dim3(grid_of(np, TPB, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_pbeg.p, n, pos0, np,
                                    key.p, val.p);
             }
             {
@@ -1110,7 +1094,7 @@ void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out
             int64_t n_hits = 0;
             {
                 vg_prof_scope ps_("dedupc_lookup", (double)nq * 40.0);
-                hipLaunchKernelGGL(k_clookup, dim3(grid_of(nq + 1)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, n, anchor, key.p, np, hlo.p, hcnt.p);
+                hipLaunchKernelGGL(k_sub_lookup, dim3(grid_of(nq + 1)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, n, anchor, key.p, np, hlo.p, hcnt.p);
                 scan(hcnt.p, hoff.p, nq + 1, false, rocprim::plus<int64_t>(), s);
                 vg_download_bytes(&n_hits, hoff.p + nq, sizeof n_hits, s);
                 VG_HIP(hipStreamSynchronize(s));
@@ -1123,7 +1107,7 @@ void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out
                 {
                     vg_prof_scope ps_("dedupc_lookup", (double)(h1 - h0) * 32.0);
                     VG_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), s));
-                    hipLaunchKernelGGL(k_ccands, dim3(grid_of(h1 - h0)), dim3(TPB), 0, s, d_len.p, d_pbeg.p, n, hoff.p, hlo.p, val.p, h0, h1,
+                    hipLaunchKernelGGL(k_sub_cands, dim3(grid_of(h1 - h0)), dim3(TPB), 0, s, d_len.p, d_pbeg.p, n, hoff.p, hlo.p, val.p, h0, h1,
                                        cq.p, cj.p, cs.p, d_count.p);
                     d_count.download(&nc, 1, s);
                     VG_HIP(hipStreamSynchronize(s));
@@ -1133,15 +1117,15 @@ void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out
                 {
                     vg_prof_scope ps_("dedupc_verify", 0.0);
                     int64_t n_vt = 0;
-                    hipLaunchKernelGGL(k_cvtasks, dim3(grid_of((int64_t)nc + 1)), dim3(TPB), 0, s, cq.p, (int64_t)nc, d_len.p, cnt.p, bad.p);
+                    hipLaunchKernelGGL(k_sub_tasks, dim3(grid_of((int64_t)nc + 1)), dim3(TPB), 0, s, cq.p, (int64_t)nc, d_len.p, cnt.p, bad.p);
                     scan(cnt.p, tbeg.p, (int64_t)nc + 1, false, rocprim::plus<int64_t>(), s);
                     vg_download_bytes(&n_vt, tbeg.p + nc, sizeof n_vt, s);
                     VG_HIP(hipStreamSynchronize(s));
-                    hipLaunchKernelGGL(k_cverify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, cq.p, cj.p, cs.p,
+                    hipLaunchKernelGGL(k_sub_verify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, cq.p, cj.p, cs.p,
                                        (int64_t)nc, tbeg.p, n_vt, bad.p);
                 }
                 vg_prof_scope ps_("dedupc_pick", (double)nc * 24.0);
-                hipLaunchKernelGGL(k_cpick, dim3(grid_of((int64_t)nc)), dim3(TPB), 0, s, d_len.p, d_rnk.p, n, cq.p, cj.p, cs.p, (int64_t)nc, bad.p, sbits,
+                hipLaunchKernelGGL(k_sub_pick, dim3(grid_of((int64_t)nc)), dim3(TPB), 0, s, d_len.p, d_rnk.p, n, cq.p, cj.p, cs.p, (int64_t)nc, bad.p, sbits,
                                    d_best.p, d_count.p + 1);
             }
         }
