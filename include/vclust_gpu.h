@@ -283,7 +283,7 @@ int vg_align_sharded(const char* const* fasta_paths, int n_paths, const char* ou
  * Objects are the rows of the ids file (index = row number from 0, i.e. the align stage's length order).  A row of ani.tsv
  * passes when every minimum > 0 holds (column >= value), num_alns <= max_num_alns when that is > 0, and qidx != ridx; it
  * links {qidx, ridx} with the metric value as weight (the maximum over duplicate and reverse rows). */
-enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3, VG_CLUSTER_COMPLETE = 4 };
+enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3, VG_CLUSTER_COMPLETE = 4, VG_CLUSTER_AVERAGE = 5 };
 typedef struct {            /* mirrors the cluster sub-parser, vclust.py:423 ff. */
     int algorithm;                                            /* VG_CLUSTER_* */
     const char* metric;                                       /* "tani" | "gani" | "ani": the edge weight */
@@ -293,7 +293,7 @@ typedef struct {            /* mirrors the cluster sub-parser, vclust.py:423 ff.
     int num_threads; int verbosity;
 } vg_cluster_params;
 typedef struct {
-    int64_t rounds;             /* parallel rounds launched (single: hooking rounds; complete: merge rounds) */
+    int64_t rounds;             /* parallel rounds launched (single: hooking rounds; complete, average: merge rounds) */
     int64_t sweep_objects;      /* objects decided by the one-workgroup tail sweep */
     int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
 } vg_cluster_stats;
@@ -301,13 +301,15 @@ typedef struct {
  * ids file or a malformed number is VG_EINVAL naming the file and line, reported before any device use.  Output: header
  * `object<TAB>cluster`, one line per object in ids-file order; clusters of >= 2 members are numbered 0, 1, ... by their
  * earliest member, then singletons in ids-file order; with `representatives` the second column is the id of the cluster's
- * earliest member. */
+ * earliest member.  VG_CLUSTER_AVERAGE is the average-linkage hierarchy below, run down to the metric's minimum (its floor) with
+ * every merge joined; a weight outside [0, 1] is VG_EINVAL for it. */
 int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p);
 /* The array-level stage: rows (q[i], r[i], w[i]) over n_objects objects, read as above (self rows dropped, duplicates
  * merged to the maximum weight; NaN weights and indices >= n_objects are VG_EINVAL, n_objects >= 2^31 VG_EOVERFLOW).
  * label[n_objects]: the output file's numbering; representative[n_objects]: the index of the cluster's earliest member.
  * stats may be NULL.  VG_CLUSTER_COMPLETE (here and in vg_cluster) is the cut of the complete-linkage hierarchy below at the
- * floor, i.e. after every merge: each cluster is a clique of passing rows; sweep_objects is 0. */
+ * floor, i.e. after every merge: each cluster is a clique of passing rows; sweep_objects is 0.  VG_CLUSTER_AVERAGE needs a
+ * floor, which this call does not take: it is VG_EINVAL here (use the average-linkage calls below). */
 int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_edges,
                      int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats);
 
@@ -318,9 +320,9 @@ int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, co
  * 0 .. n_objects - 1 and merge k (from 0) creates node n_objects + k.  The cut at level t joins the merges with w >= t; its
  * labels and representatives follow the rule of vg_cluster_graph, and it equals `single` on the rows with w >= t. */
 typedef struct {
-    int64_t rounds;             /* single: Boruvka rounds launched (the last one finds no leaving edge); complete: merge rounds */
+    int64_t rounds;             /* single: Boruvka rounds launched (the last one finds no leaving edge); complete, average: merge rounds */
     int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
-    int64_t n_merges;           /* single: forest edges = n_objects - components; complete: n_objects - clusters at the floor */
+    int64_t n_merges;           /* single: forest edges = n_objects - components; complete, average: n_objects - clusters at the floor */
 } vg_linkage_stats;
 /* The merge table of the rows (validated as vg_cluster_graph validates them, before any device use).  Every output array is the
  * caller's and has n_objects - 1 entries (they may be NULL when n_objects <= 1); *n_merges of them are written, in merge order:
@@ -347,8 +349,36 @@ int vg_cluster_complete_linkage_graph(int64_t n_objects, const uint32_t* q, cons
                                       int64_t* size, int64_t* n_merges, vg_linkage_stats* stats);
 int vg_cluster_complete_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                                      const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats);
-/* File to file, with the host parse and the error messages of vg_cluster; p->algorithm must be VG_CLUSTER_SINGLE or
- * VG_CLUSTER_COMPLETE (else VG_EINVAL) and selects the hierarchy.  out_path: clusters.tsv of vg_cluster (the cut at the metric's floor) plus one column per level, headed
+/* Average-linkage (UPGMA) merge table and cuts (this repository's definition; DESIGN.md section 9, "Merge table: average linkage").
+ * Same graph; every weight must be finite and in [0, 1] (else VG_EINVAL, before any device use), and so must `floor`.  A weight w
+ * is the integer u = llrint(ldexp(w, 32)), and everything else is integer arithmetic on u: S(A, B) is the sum of u over the edges
+ * between two clusters, P(A, B) = |A| * |B|, sim(A, B) = S / (P * 2^32) -- a pair of objects without an edge adds 0 to S and 1 to P.
+ * A pair of clusters with at least one edge between them is a candidate with the key (-sim, c, d), c < d the cluster ids (minimum
+ * members), sim compared exactly (S1 * P2 against S2 * P1 in 128 bits).  From singletons, the candidate of smallest key merges,
+ * until none is left or the smallest key has sim < floor (S < F * P, F = llrint(ldexp(floor, 32))).  Record k: object_a < object_b
+ * are the two cluster ids merged, sum = S, pairs = P, similarity = the double nearest to S / (P * 2^32) (ties to even); similarity
+ * never rises down the table, and node numbering, labels and representatives are those of the calls above.  The cut at level t
+ * joins the merges with S >= T * P, T = llrint(ldexp(t, 32)); a level below the floor is VG_EINVAL.  Unlike the other two
+ * hierarchies, the cut at t is NOT the floor cut of a run with floor t: the rows between the floor and t still count in the
+ * averages.  2^32 or more edges are VG_EOVERFLOW.  stats->rounds counts the merge rounds launched (the last one finds no merge).
+ * sum and pairs have n_objects - 1 entries like the other outputs. */
+int vg_cluster_average_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                     double floor, int32_t* object_a, int32_t* object_b, double* similarity, uint64_t* sum,
+                                     uint64_t* pairs, int64_t* node_a, int64_t* node_b, int64_t* size, int64_t* n_merges,
+                                     vg_linkage_stats* stats);
+int vg_cluster_average_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                    double floor, const double* levels, int n_levels, int32_t* label, int32_t* representative,
+                                    vg_linkage_stats* stats);
+/* Test entries of that arithmetic.  The double nearest to sum / (pairs * 2^32), ties to even (host code; pairs == 0 gives NaN). */
+double vg_cluster_average_similarity(uint64_t sum, uint64_t pairs);
+/* out[i], i in 0 .. n - 2, is -1, 0 or 1 as entry i has the smaller, the same or the larger key than entry i + 1, where entry i is
+ * the candidate of similarity sum[i] / (size_c[i] * size_d[i]) between the clusters c[i] and d[i]: the comparator the kernels and the
+ * host share, run on the host or (on_device != 0; VG_ENODEV without one) in one kernel launch. */
+int vg_cluster_average_order_selftest(const uint64_t* sum, const uint32_t* size_c, const uint32_t* size_d, const uint32_t* c,
+                                      const uint32_t* d, int64_t n, int on_device, int8_t* out);
+/* File to file, with the host parse and the error messages of vg_cluster; p->algorithm must be VG_CLUSTER_SINGLE,
+ * VG_CLUSTER_COMPLETE or VG_CLUSTER_AVERAGE (else VG_EINVAL) and selects the hierarchy; the floor of VG_CLUSTER_AVERAGE is the
+ * metric's minimum.  out_path: clusters.tsv of vg_cluster (the cut at the metric's floor) plus one column per level, headed
  * `<metric>_<%g of the level>`, labels or -- with p->representatives -- representative ids; a level below the metric's minimum
  * is VG_EINVAL.  linkage_path (may be NULL): header `node_a node_b similarity size object_a object_b` (tab-separated), one line
  * per merge, similarity printed with %.6g. */

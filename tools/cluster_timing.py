@@ -3,6 +3,7 @@ table), rounds, objects finished by the tail sweep, end-to-end wall time.
 
   python tools/cluster_timing.py [--sizes 100000 1000000] [--ani ani.tsv --ids ani.ids.tsv] [--metric tani --min 0.95] [--linkage]
   python tools/cluster_timing.py --complete [--sizes 100000] [--clique-chain 200]
+  python tools/cluster_timing.py --average [--sizes 100000] [--floor 0.8]
 
 Synthetic graphs: families of 20-200 objects in index order, ~50 rows per object (both directions, ~25 distinct
 neighbours), weights 0.80-1.00 inside families and a few weak rows between them.  With --ani, the file is also clustered
@@ -14,7 +15,10 @@ discarded and then timed three times (the median is printed).  The graph is the 
 clique (the 50-rows-per-object families are no cliques and would merge almost nothing); the row prints the two profile groups
 `cluster_complete_best` / `cluster_complete_contract`, the rounds and the records of the cluster graph after each contraction
 (read from the library's VG_HOST_TRACE lines, which this mode switches on).  --clique-chain N adds the known worst case: one
-clique of N objects whose weights force one merge per round, with the time per round.
+clique of N objects whose weights force one merge per round, with the time per round.  --average: the average-linkage merge
+table (vg_cluster_average_linkage_graph, floor --floor) on the clique-family graph beside the complete-linkage table, both in the
+same process, each run once and discarded and then timed three times; the row prints the two profile groups
+`cluster_average_best` / `cluster_average_contract`, the rounds and the ratio of GPU time to `complete`.
 """
 import argparse
 import json
@@ -112,6 +116,16 @@ def complete_row(name, n, q, r, w):
                 gpu_ratio_to_linkage=round(gpu / max(sum(kern2.values()), 1e-9), 2), **cst)
 
 
+def average_row(name, n, q, r, w, floor):
+    (_, cst), wall1, kern1 = median_of_three(lambda: api.cluster_complete_linkage_graph(n, q, r, w))
+    (table, ast), wall, kern = median_of_three(lambda: api.cluster_average_linkage_graph(n, q, r, w, floor))
+    gpu, gpu1, rounds = sum(kern.values()), sum(kern1.values()), max(ast['rounds'], 1)
+    return dict(input=f'{name} n={n} rows={len(q)}', algorithm='average', floor=floor, wall_ms=round(wall, 2), gpu_ms=round(gpu, 2),
+                kernels=kern, best_ms=kern.get('cluster_average_best', 0), contract_ms=kern.get('cluster_average_contract', 0),
+                gpu_ms_per_round=round(gpu / rounds, 4), complete_wall_ms=round(wall1, 2), complete_gpu_ms=round(gpu1, 2),
+                complete_rounds=cst['rounds'], complete_merges=cst['n_merges'], gpu_ratio_to_complete=round(gpu / max(gpu1, 1e-9), 2), **ast)
+
+
 def timed(fn):
     api.profile_reset()
     t0 = time.perf_counter()
@@ -131,6 +145,8 @@ def main():
     ap.add_argument('--linkage', action='store_true')
     ap.add_argument('--complete', action='store_true')
     ap.add_argument('--clique-chain', type=int, default=0, metavar='N')
+    ap.add_argument('--average', action='store_true')
+    ap.add_argument('--floor', type=float, default=0.8)
     ap.add_argument('--json', type=pathlib.Path)
     a = ap.parse_args()
     if a.complete:
@@ -150,6 +166,14 @@ def main():
             graphs.append(('one clique, one merge per round', a.clique_chain, *clique_chain(a.clique_chain)))
         for name, n, q, r, w in graphs:
             row = silent(lambda: complete_row(name, n, q, r, w))
+            print(json.dumps(row), flush=True)
+            res.append(row)
+        a.sizes = []
+    if a.average:
+        api.cluster_complete_linkage_graph(2, [0], [1], [1.0])
+        api.cluster_average_linkage_graph(2, [0], [1], [1.0])
+        for n in a.sizes:
+            row = average_row('synthetic clique families', n, *clique_family_graph(n), a.floor)
             print(json.dumps(row), flush=True)
             res.append(row)
         a.sizes = []

@@ -77,6 +77,8 @@ CLUSTER_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2, 'set-cover': 3}
 # the hierarchies the library computes (merge table and cuts: --out-linkage / --levels); 'complete' is also an algorithm of
 # vg_cluster / vg_cluster_graph (the cut at the floor), but a plain `cluster --algorithm complete` still goes to Clusty
 LINKAGE_ALGORITHMS = {'single': 0, 'complete': 4}
+# ... and with average linkage (UPGMA), which Clusty does not have: it always runs in the library, with or without the merge table
+HIERARCHY_ALGORITHMS = {**LINKAGE_ALGORITHMS, 'average': 5}
 
 
 class DedupParams(C.Structure):
@@ -181,6 +183,14 @@ SYMBOLS = {
                                                     P(C.c_double), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(LinkageStats)]),
     'vg_cluster_complete_levels_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_double), C.c_int,
                                                    P(C.c_int32), P(C.c_int32), P(LinkageStats)]),
+    'vg_cluster_average_linkage_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_double, P(C.c_int32),
+                                                   P(C.c_int32), P(C.c_double), P(C.c_uint64), P(C.c_uint64), P(C.c_int64), P(C.c_int64),
+                                                   P(C.c_int64), P(C.c_int64), P(LinkageStats)]),
+    'vg_cluster_average_levels_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_double, P(C.c_double),
+                                                  C.c_int, P(C.c_int32), P(C.c_int32), P(LinkageStats)]),
+    'vg_cluster_average_similarity': (C.c_double, [C.c_uint64, C.c_uint64]),
+    'vg_cluster_average_order_selftest': (C.c_int, [P(C.c_uint64), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), C.c_int64,
+                                                    C.c_int, P(C.c_int8)]),
     'vg_cluster_linkage': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams), C.c_char_p, P(C.c_double), C.c_int]),
     'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),

@@ -325,6 +325,73 @@ def cluster_complete_levels_graph(n_objects, q, r, w, levels):
     return _levels('vg_cluster_complete_levels_graph', n_objects, q, r, w, levels)
 
 
+AVERAGE_LINKAGE_DTYPE = np.dtype(LINKAGE_DTYPE.descr + [('sum', '<u8'), ('pairs', '<u8')])
+
+
+def cluster_average_linkage_graph(n_objects, q, r, w, floor=0.0):
+    """The average-linkage (UPGMA) merge table of the graph of cluster_graph (vg_cluster_average_linkage_graph), in exact integer
+    arithmetic: a weight (in [0, 1]) is u = round(w * 2^32), sim(A, B) = S / (|A| |B| 2^32) with S the sum of u over the rows
+    between the two clusters (a pair without a row counts as 0; two clusters without any row between them never merge), and from
+    singletons the pair of smallest key (-sim, c, d) merges until none is left or sim < floor.  -> (table, stats): table is an
+    AVERAGE_LINKAGE_DTYPE array -- the fields of cluster_linkage with (object_a, object_b) the two cluster ids merged, plus the
+    exact `sum` S and `pairs` P = |A| |B| of each record; `similarity` is the double nearest to S / (P 2^32) and never rises."""
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    cap = max(n - 1, 1) if n < 1 << 31 else 1
+    oa, ob = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    wt = np.zeros(cap, dtype=np.float64)
+    sm, pr = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    na, nb, sz = (np.zeros(cap, dtype=np.int64) for _ in range(3))
+    nm = C.c_int64(0)
+    st = LinkageStats()
+    P = C.POINTER
+    check(_lib.load().vg_cluster_average_linkage_graph(
+        n, *rows, float(floor), oa.ctypes.data_as(P(C.c_int32)), ob.ctypes.data_as(P(C.c_int32)), wt.ctypes.data_as(P(C.c_double)),
+        sm.ctypes.data_as(P(C.c_uint64)), pr.ctypes.data_as(P(C.c_uint64)), na.ctypes.data_as(P(C.c_int64)), nb.ctypes.data_as(P(C.c_int64)),
+        sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
+    table = np.zeros(nm.value, dtype=AVERAGE_LINKAGE_DTYPE)
+    for name, arr in (('node_a', na), ('node_b', nb), ('similarity', wt), ('size', sz), ('object_a', oa), ('object_b', ob), ('sum', sm),
+                      ('pairs', pr)):
+        table[name] = arr[:nm.value]
+    return table, dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+
+
+def cluster_average_levels_graph(n_objects, q, r, w, levels, floor=0.0):
+    """The cuts of one average-linkage merge table at `levels` (vg_cluster_average_levels_graph): the cut at t joins the merges
+    with S >= round(t * 2^32) * P, compared exactly.  No level may lie below `floor`.  It is NOT cluster_average_linkage_graph
+    with floor t cut at its floor: the rows between floor and t still count in the averages.  -> as cluster_levels."""
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    width = n if 0 < n < 1 << 31 else 1
+    label = np.zeros((len(lv), width), dtype=np.int32)
+    rep = np.zeros((len(lv), width), dtype=np.int32)
+    st = LinkageStats()
+    P = C.POINTER
+    check(_lib.load().vg_cluster_average_levels_graph(n, *rows, float(floor), lv.ctypes.data_as(P(C.c_double)), len(lv),
+                                                      label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    return label[:, :n], rep[:, :n], dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+
+
+def cluster_average_similarity(s, p):
+    """Test entry (vg_cluster_average_similarity): the double nearest to s / (p * 2^32), ties to even."""
+    return float(_lib.load().vg_cluster_average_similarity(int(s), int(p)))
+
+
+def cluster_average_order_selftest(s, size_c, size_d, c, d, on_device=False):
+    """Test entry (vg_cluster_average_order_selftest): the shared comparator of average linkage over neighbouring entries ->
+    int8[n - 1] of -1 / 0 / 1, entry i against entry i + 1 (smaller key = larger s / (size_c * size_d), then smaller (c, d))."""
+    s = np.ascontiguousarray(s, dtype=np.uint64)
+    arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (size_c, size_d, c, d)]
+    if any(len(x) != len(s) for x in arrs):
+        raise ValueError('the five arrays must have the same length')
+    out = np.zeros(max(len(s) - 1, 1), dtype=np.int8)
+    P = C.POINTER
+    check(_lib.load().vg_cluster_average_order_selftest(s.ctypes.data_as(P(C.c_uint64)), *[x.ctypes.data_as(P(C.c_uint32)) for x in arrs],
+                                                        len(s), int(bool(on_device)), out.ctypes.data_as(P(C.c_int8))))
+    return out[:max(len(s) - 1, 0)]
+
+
 def cluster_levels(n_objects, q, r, w, levels):
     """The cuts of one merge table at `levels` (vg_cluster_levels_graph): the cut at t joins the merges of similarity >= t and
     equals cluster_graph(rows with w >= t, 'single').  -> (label int32[len(levels), n], representative int32[len(levels), n],

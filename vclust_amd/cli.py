@@ -5,7 +5,7 @@ output files (vclust.py:178-421, 1380-1521) but call libvclust_gpu.so (HIP, MI35
 ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster` passes its
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
 single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster); `--out-linkage` and
-`--levels` (the merge table of single or complete linkage and its cuts) always run on the GPU.  `deduplicate` does
+`--levels` (the merge table of single, complete or average linkage and its cuts) always run on the GPU, and so does `--algorithm average`.  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
 without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
 `--contained` always run on the GPU.  `info` reports the library and the optional CPU tools.
@@ -172,8 +172,9 @@ def get_parser() -> argparse.ArgumentParser:
     cl.add_argument('-r', '--out-repr', action='store_true', dest='representatives',
                     help='Output a representative genome for each cluster [%(default)s]')
     cl.add_argument('--algorithm', metavar='<str>', dest='algorithm', default='single',
-                    choices=['single', 'complete', 'uclust', 'cd-hit', 'set-cover', 'leiden'],
-                    help='Clustering algorithm [%(default)s]')
+                    choices=['single', 'complete', 'average', 'uclust', 'cd-hit', 'set-cover', 'leiden'],
+                    help='Clustering algorithm [%(default)s]; average (UPGMA: a pair without a row counts as 0) always runs on the GPU '
+                         'and merges down to the threshold of --metric')
     cl.add_argument('--metric', metavar='<str>', dest='metric', choices=['tani', 'gani', 'ani'], default='tani',
                     help='Similarity metric for clustering [%(default)s]')
     for name in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio'):
@@ -182,11 +183,12 @@ def get_parser() -> argparse.ArgumentParser:
     cl.add_argument('--num_alns', metavar='<int>', dest='num_alns', type=int, default=0,
                     help='Max. number of local alignments between two genomes; 0 = all [%(default)s]')
     cl.add_argument('--out-linkage', metavar='<file>', type=pathlib.Path, dest='linkage_path',
-                    help='Write the merge table of --algorithm single or complete (the dendrogram: one line per merge) '
+                    help='Write the merge table of --algorithm single, complete or average (the dendrogram: one line per merge) '
                          'to the tsv <file>')
     cl.add_argument('--levels', metavar='<float>', type=_unit_float, nargs='+', dest='levels',
                     help='Further thresholds of the metric (0-1, none below its minimum): one more column per level, the cut of '
-                         'the same hierarchy (single or complete linkage) there')
+                         'the same hierarchy (single, complete or average linkage) there; under average linkage the cut at a level '
+                         'is not a run at that threshold: the rows between the two still count in the averages')
     cl.add_argument('--leiden-resolution', metavar='<float>', type=_unit_float, default=0.7)
     cl.add_argument('--leiden-beta', metavar='<float>', type=_unit_float, default=0.01)
     cl.add_argument('--leiden-iterations', metavar='<int>', type=int, default=2)
@@ -358,20 +360,21 @@ def cluster_call(args):
 
 
 def handle_cluster(args, parser, logger):
-    from ._lib import CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS
+    from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS
     linkage_path, levels = getattr(args, 'linkage_path', None), getattr(args, 'levels', None)
     hierarchy = linkage_path is not None or bool(levels)
     if hierarchy:
-        if args.algorithm not in LINKAGE_ALGORITHMS:
-            parser.error('--out-linkage and --levels are a linkage hierarchy: they need --algorithm single or --algorithm complete.')
+        if args.algorithm not in HIERARCHY_ALGORITHMS:
+            parser.error('--out-linkage and --levels are a linkage hierarchy: they need --algorithm single, --algorithm complete '
+                         'or --algorithm average.')
         floor = vars(args).get(args.metric, 0)
         for level in levels or ():
             if floor and level < floor:
                 parser.error(f'--levels {level:g} is below --{args.metric} {floor:g}: rows below the threshold are not edges.')
-    if hierarchy or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
+    if hierarchy or args.algorithm == 'average' or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
         # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster); the merge table and
-        # its cuts (which Clusty does not have) always do, for single and for complete linkage.  A plain `--algorithm complete`
-        # is not in CLUSTER_ALGORITHMS and still goes to Clusty below.
+        # its cuts (which Clusty does not have) always do, for every hierarchy, and so does average linkage, which Clusty does
+        # not have either.  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and still goes to Clusty below.
         if not vars(args).get(args.metric, 0):
             parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
         from . import stages

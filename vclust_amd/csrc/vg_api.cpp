@@ -2,7 +2,7 @@
 //   vg_prefilter  replaces kmer-db build + all2all + distance (vclust.py:1433-1471)
 //   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521)
 //   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557)
-//   vg_cluster_linkage   the same parse, then the single- or complete-linkage merge table and its cuts at several levels
+//   vg_cluster_linkage   the same parse, then the single-, complete- or average-linkage merge table and its cuts at several levels
 // Both are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
 #include "vg_common.h"
 #include <math.h>
@@ -124,10 +124,15 @@ extern "C" int vg_align(const char* const* fasta_paths, int n_paths, const char*
     VG_API_END
 }
 
+// the minimum of the metric that is the edge weight: the floor of the average-linkage hierarchy and the lowest level of any
+static double metric_floor(const vg_cluster_params* p) {
+    return !strcmp(p->metric, "tani") ? p->min_tani : !strcmp(p->metric, "gani") ? p->min_gani : p->min_ani;
+}
+
 extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p) {
     VG_API_BEGIN
     if (!ani_path || !ids_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster: null argument");
-    if (p->algorithm < VG_CLUSTER_SINGLE || p->algorithm > VG_CLUSTER_COMPLETE) throw vg_error(VG_EINVAL, "vg_cluster: unknown algorithm");
+    if (p->algorithm < VG_CLUSTER_SINGLE || p->algorithm > VG_CLUSTER_AVERAGE) throw vg_error(VG_EINVAL, "vg_cluster: unknown algorithm");
     if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
         throw vg_error(VG_EINVAL, std::string("vg_cluster: metric must be tani, gani or ani, not ") + p->metric);
     vg_host_mark("vg_cluster: enter");
@@ -142,6 +147,12 @@ extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char
     const int64_t n = (int64_t)ids.size();
     std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
     vg_cluster_stats st{};
+    if (p->algorithm == VG_CLUSTER_AVERAGE) {                   // the average-linkage hierarchy down to the metric's minimum, every merge joined
+        vg_forest f;
+        vg_cluster_forest("vg_cluster", n, q.data(), r.data(), w.data(), (int64_t)q.size(), f, VG_CLUSTER_AVERAGE, metric_floor(p));
+        vg_forest_cut(n, f, -HUGE_VAL, label.data(), rep.data());
+        st.rounds = f.stats.rounds; st.n_edges = f.stats.n_edges;
+    } else
     check(vg_cluster_graph(n, q.data(), r.data(), w.data(), (int64_t)q.size(), p->algorithm, label.data(), rep.data(), &st));
     vg_host_mark("clusters computed");
     vg_cluster_write(out_path, ids, label.data(), rep.data(), p->representatives != 0);
@@ -156,11 +167,11 @@ extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, co
     VG_API_BEGIN
     if (!ani_path || !ids_path || !out_path || !p || !p->metric || n_levels < 0 || (n_levels && !levels))
         throw vg_error(VG_EINVAL, "vg_cluster_linkage: null argument");
-    if (p->algorithm != VG_CLUSTER_SINGLE && p->algorithm != VG_CLUSTER_COMPLETE)
-        throw vg_error(VG_EINVAL, "vg_cluster_linkage: the merge table is single or complete linkage (algorithm must be single or complete)");
+    if (p->algorithm != VG_CLUSTER_SINGLE && p->algorithm != VG_CLUSTER_COMPLETE && p->algorithm != VG_CLUSTER_AVERAGE)
+        throw vg_error(VG_EINVAL, "vg_cluster_linkage: the merge table is single, complete or average linkage (algorithm must be one of the three)");
     if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
         throw vg_error(VG_EINVAL, std::string("vg_cluster_linkage: metric must be tani, gani or ani, not ") + p->metric);
-    const double floor = !strcmp(p->metric, "tani") ? p->min_tani : !strcmp(p->metric, "gani") ? p->min_gani : p->min_ani;
+    const double floor = metric_floor(p);
     for (int l = 0; l < n_levels; ++l)
         if (!(levels[l] >= floor))          // (also a NaN)
             throw vg_error(VG_EINVAL, "vg_cluster_linkage: level " + std::to_string(levels[l]) + " is below the " + p->metric + " minimum (rows below it are not edges)");
@@ -175,7 +186,7 @@ extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, co
     warm.join();
     const int64_t n = (int64_t)ids.size();
     vg_forest f;
-    vg_cluster_forest("vg_cluster_linkage", n, q.data(), r.data(), w.data(), (int64_t)q.size(), f, p->algorithm);
+    vg_cluster_forest("vg_cluster_linkage", n, q.data(), r.data(), w.data(), (int64_t)q.size(), f, p->algorithm, floor);
     vg_host_mark("forest computed");
     // column 0: every merge (the cut at the floor, i.e. the algorithm on the passing rows); then one cut per level
     const size_t cols = (size_t)n_levels + 1, stride = (size_t)std::max<int64_t>(n, 1);

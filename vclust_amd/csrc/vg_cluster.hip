@@ -11,6 +11,8 @@
 //   complete  the complete-linkage merge table on the same ranks: rounds that merge every pair of mutually nearest clusters
 //             (find + match), then a contraction of the cluster graph (relabel, radix sort, reduce-by-key, select, CSR) that keeps
 //             a cluster pair only while every object pair between the two is an edge; the merge records go the forest's way
+//   average   the average-linkage (UPGMA) merge table in exact integer arithmetic: the same rounds on 64-bit sums of quantised
+//             weights, candidates compared as fractions (128-bit products), and a contraction that adds the sums of a cluster pair
 // Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
 // only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
 // their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
@@ -454,6 +456,112 @@ __global__ void k_cl_compact(const int64_t* idx, const unsigned long long* m_new
     }
 }
 
+// ---------------------------------------------------------------- average linkage (UPGMA)
+// A weight w is the integer u = llrint(ldexp(w, 32)).  The cluster graph: directed records (src cluster << 32 | dst cluster, S) with
+// S the sum of u over the object edges between the two clusters, sorted by key, with row offsets; size[c] = members of cluster c.
+// sim(A, B) = S / (|A| |B| 2^32): a pair of objects without an edge adds nothing to S, and a cluster pair without a record is no
+// candidate.  A candidate has the key (-sim, lo, hi), lo < hi the two cluster ids; no floating-point sum exists anywhere.
+struct av_cand { uint64_t S, P; uint32_t lo, hi; };         // P: the object pairs |A| |B| (inside one row: the other cluster's size)
+// < 0 when x has the smaller key (the larger similarity; ties: the smaller (lo, hi)), 0 for equal keys.  S1 / P1 against S2 / P2 is
+// S1 * P2 against S2 * P1 in 128 bits: S < 2^64 and P < 2^64, and a 64-bit product of the two would wrap.
+__host__ __device__ inline int av_compare(const av_cand& x, const av_cand& y) {
+    const unsigned __int128 l = (unsigned __int128)x.S * y.P, r = (unsigned __int128)y.S * x.P;
+    if (l != r) return l > r ? -1 : 1;
+    if (x.lo != y.lo) return x.lo < y.lo ? -1 : 1;
+    return x.hi < y.hi ? -1 : x.hi > y.hi ? 1 : 0;
+}
+// sim >= T / 2^32, exactly: S >= T * P (T <= 2^32 + 1 and P < 2^62: the product needs more than 64 bits)
+__host__ __device__ inline bool av_reaches(uint64_t S, uint64_t P, uint64_t T) { return (unsigned __int128)S >= (unsigned __int128)T * P; }
+
+__global__ void k_av_quantise(const double* vals, int64_t m, uint64_t* sum) { GRID_STRIDE(e, m) sum[e] = (uint64_t)llrint(ldexp(vals[e], 32)); }
+// round, step 1: every cluster (ROW_LANES lanes each) finds the record of its row with the smallest key.  Inside a row the
+// cluster's own size cancels: the candidates carry the other cluster's size as P.  The key order is total, so after the butterfly
+// every lane of the group holds the same candidate.  A cluster with an empty row is final: it gets no destination.
+__global__ void k_av_find(int64_t n, const int64_t* off, const uint64_t* keys, const uint64_t* sum, const int32_t* size,
+                          unsigned long long* bsum, int32_t* bdst) {
+    const int lane = threadIdx.x % ROW_LANES;
+    const int64_t groups = (int64_t)gridDim.x * blockDim.x / ROW_LANES;
+    for (int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ROW_LANES; c < n; c += groups) {
+        const int64_t lo = off[c], hi = off[c + 1];
+        if (lo == hi) { if (lane == 0) bdst[c] = UND; continue; }
+        // the candidate held by this lane: (S, P = the other cluster's size, d); d == UND: none yet.  Three scalars updated by
+        // selects, on purpose: as one av_cand assigned under a branch, the 64-bit P of the running best was left stale after a
+        // take by the compiler (seen in the ISA and as wrong merges on the device)
+        uint64_t bs = 0; uint32_t bp = 1; int32_t bd = UND;
+        const uint32_t uc = (uint32_t)c;
+        auto better = [&](uint64_t S2, uint32_t P2, int32_t d2) {   // is (S2, P2, d2) a candidate, with a smaller key than the lane's?
+            const uint32_t u1 = (uint32_t)bd, u2 = (uint32_t)d2;
+            const av_cand x{ S2, (uint64_t)P2, u2 < uc ? u2 : uc, u2 < uc ? uc : u2 }, y{ bs, (uint64_t)bp, u1 < uc ? u1 : uc, u1 < uc ? uc : u1 };
+            return d2 != UND && (bd == UND || av_compare(x, y) < 0);
+        };
+        for (int64_t k = lo + lane; k < hi; k += ROW_LANES) {
+            const int32_t d = (int32_t)(uint32_t)keys[k];
+            const uint64_t S = sum[k]; const uint32_t P = (uint32_t)size[d];
+            const bool take = better(S, P, d);
+            bs = take ? S : bs; bp = take ? P : bp; bd = take ? d : bd;
+        }
+        for (int o = ROW_LANES / 2; o > 0; o >>= 1) {           // the whole candidate travels: (S, P, d)
+            const uint64_t S2 = (uint64_t)__shfl_xor((unsigned long long)bs, o);
+            const uint32_t P2 = __shfl_xor(bp, o);
+            const int32_t d2 = __shfl_xor(bd, o);
+            const bool take = better(S2, P2, d2);
+            bs = take ? S2 : bs; bp = take ? P2 : bp; bd = take ? d2 : bd;
+        }
+        if (lane == 0) { bsum[c] = bs; bdst[c] = bd; }
+    }
+}
+// step 2: (c, d), c < d, is a merge when each is the other's choice and sim >= floor (S >= F * P); a record of S == 0 never merges
+// here (see the host loop).  The key order is total and symmetric, so the merges of a round are a matching.  Reads only what
+// k_av_find wrote, size[] (which grows in the contraction, after these reads) and, in the zero phase, the first record: then the
+// one merge of the round is the record of smallest (c, d), which is keys[0].  The merge list is filled in any order.
+__global__ void k_av_match(int64_t n, const unsigned long long* bsum, const int32_t* bdst, const int32_t* size, uint64_t F, int zero_phase,
+                           const uint64_t* keys, int32_t* parent, uint64_t* msum, uint64_t* mpairs, int32_t* mc, int32_t* md, int64_t cap,
+                           unsigned long long* total) {
+    GRID_STRIDE(c, n) {
+        const int64_t d = bdst[c];
+        if (d <= c || d >= n || bdst[d] != (int32_t)c) continue;            // (no destination is -1)
+        const uint64_t S = bsum[c], P = (uint64_t)size[c] * (uint64_t)size[d];
+        if (zero_phase ? keys[0] != ((uint64_t)c << 32 | (uint64_t)d) : (S == 0 || !av_reaches(S, P, F))) continue;
+        const unsigned long long slot = atomicAdd(total, 1ull);
+        if (slot < (unsigned long long)cap) { msum[slot] = S; mpairs[slot] = P; mc[slot] = (int32_t)c; md[slot] = (int32_t)d; }
+        parent[d] = (int32_t)c;
+    }
+}
+// contraction, step 1: the merges [from, to) of this round are a matching, so every size[] entry has one writer
+__global__ void k_av_grow(const int32_t* mc, const int32_t* md, int64_t from, int64_t to, int32_t* size) {
+    GRID_STRIDE(j, to - from) size[mc[from + j]] += size[md[from + j]];
+}
+// step 2: every record under the new cluster ids, keyed on 2 * bits bits for the sort; the record of a merged pair itself becomes
+// the sentinel (src = n) that sorts last.  One hop of parent[] is enough: the merges are a matching.
+__global__ void k_av_relabel(const uint64_t* keys, const uint64_t* sum, int64_t m, const int32_t* parent, int64_t n, int bits,
+                             uint64_t* okey, uint64_t* oval) {
+    GRID_STRIDE(e, m) {
+        const uint64_t s = (uint64_t)parent[keys[e] >> 32], d = (uint64_t)parent[(uint32_t)keys[e]];
+        okey[e] = s == d ? (uint64_t)n << bits : s << bits | d;
+        oval[e] = sum[e];
+    }
+}
+// step 3 (after sort and reduce-by-key with plus): the groups, in key order, are the new records -- all but the sentinel group,
+// which is the last one; the tail of the old list is filled with the sentinel, so that k_csr over the old length gives the new
+// offsets.  *m_new = the new length, for the round's read-back.
+__global__ void k_av_compact(const unsigned long long* n_groups, int64_t m_old, const uint64_t* gkey, const uint64_t* gsum, int64_t n, int bits,
+                             uint64_t* keys, uint64_t* sum, unsigned long long* m_new) {
+    const int64_t ng = (int64_t)*n_groups < m_old ? (int64_t)*n_groups : m_old;
+    GRID_STRIDE(e, m_old) {
+        const bool live = e < ng && (gkey[e] >> bits) < (uint64_t)n;
+        if (live) { keys[e] = (gkey[e] >> bits) << 32 | (gkey[e] & ((1ull << bits) - 1)); sum[e] = gsum[e]; }
+        else keys[e] = (uint64_t)n << 32;
+        if (e == 0) *m_new = (unsigned long long)(ng - (ng > 0 && (gkey[ng - 1] >> bits) >= (uint64_t)n ? 1 : 0));
+    }
+}
+__global__ void k_av_order(const uint64_t* S, const uint32_t* sc, const uint32_t* sd, const uint32_t* c, const uint32_t* d, int64_t n, int8_t* out) {
+    GRID_STRIDE(i, n - 1) {
+        const av_cand x{ S[i], (uint64_t)sc[i] * sd[i], c[i] < d[i] ? c[i] : d[i], c[i] < d[i] ? d[i] : c[i] };
+        const av_cand y{ S[i + 1], (uint64_t)sc[i + 1] * sd[i + 1], c[i + 1] < d[i + 1] ? c[i + 1] : d[i + 1], c[i + 1] < d[i + 1] ? d[i + 1] : c[i + 1] };
+        out[i] = (int8_t)av_compare(x, y);
+    }
+}
+
 // ---------------------------------------------------------------- labels
 // every object must carry a cluster id in [0, n) before the label kernels index with it
 __global__ void k_check_roots(const int32_t* root, int64_t n, int32_t* bad) { GRID_STRIDE(i, n) if ((uint32_t)root[i] >= (uint64_t)n) st(bad, 1); }
@@ -501,6 +609,16 @@ void check_row_values(const char* fn, int64_t n_objects, const uint32_t* q, cons
     for (int64_t k : bad) if (k >= 0)
         throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": " +
                        (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
+}
+// average linkage: the quantum 2^-32 and the 64-bit sums stand on weights (and a floor) in [0, 1]
+void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double floor) {
+    if (!(floor >= 0 && floor <= 1)) throw vg_error(VG_EINVAL, std::string(fn) + ": the floor must lie in [0, 1]");
+    std::vector<int64_t> bad((size_t)std::max(1, vg_host_threads()), -1);
+    vg_parallel_chunks(n_rows, vg_host_threads(), [&](int64_t lo, int64_t hi, int t) {
+        for (int64_t k = lo; k < hi; ++k) if (!(w[k] >= 0 && w[k] <= 1)) { bad[(size_t)t] = k; return; }
+    });
+    for (int64_t k : bad) if (k >= 0)
+        throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1] (average linkage)");
 }
 
 // the edge graph of the rows on the device: the m directed edges sorted by (src, dst) with their weights, and the CSR
@@ -700,6 +818,105 @@ int64_t complete_on_device(int64_t n, edge_graph& eg, hipStream_t s, dbuf<int32_
     }
     return rounds;
 }
+
+// the level t as a count of quanta: sim >= t is S >= T * P.  Below 0 every merge passes, above 1 none does (sim <= 1).
+uint64_t av_quanta(double t) { return t <= 0 ? 0 : t > 1 ? (1ull << 32) + 1 : (uint64_t)llrint(ldexp(t, 32)); }
+// the double nearest to S / (P * 2^32), ties to even: both operands shifted to 64 significant bits, one 128-by-64-bit division to a
+// 62- or 63-bit quotient whose lowest bit also takes the remainder (sticky), one conversion (which rounds once) and an exact ldexp
+double av_similarity(uint64_t S, uint64_t P) {
+    if (P == 0) return NAN;
+    if (S == 0) return 0.0;
+    const int zs = __builtin_clzll(S), zp = __builtin_clzll(P);
+    const unsigned __int128 num = (unsigned __int128)(S << zs) << 62;
+    const uint64_t den = P << zp;
+    const uint64_t quot = (uint64_t)(num / den) | (num % den ? 1u : 0u);
+    return ldexp((double)quot, zp - zs - 62 - 32);
+}
+
+// Average linkage on the edge graph (which it consumes: the row offsets are rebuilt per contraction); f receives the merge records
+// in merge order with their exact (S, P).  Rounds: find + match, one read-back of two counters, contraction.  With floor 0 a record
+// of S == 0 may merge too, but a cluster pair WITHOUT a record has the same similarity 0 and becomes a candidate when a merge gives
+// it a record: among such ties the parallel rounds are not the sequential rule.  So records of S == 0 wait until a round finds no
+// other merge (then every record left has S == 0) and merge one per round from there, the smallest (c, d) first -- the sequential
+// rule itself, whose order the host keeps for those records instead of sorting them.
+void average_on_device(int64_t n, edge_graph& eg, double floor, hipStream_t s, vg_forest& f) {
+    const int64_t m0 = eg.m, mu = m0 / 2;
+    f.stats.n_edges = mu;
+    if (mu == 0) return;
+    if (mu >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "vg_cluster_average_linkage: 2^32 or more edges (a sum of weights must fit 64 bits)");
+    const uint64_t F = av_quanta(floor);
+    int bits = 1; while ((1LL << bits) <= n) ++bits;            // cluster ids and the sentinel n: two of them are a sort key
+    const int64_t cap = std::min<int64_t>(mu, n - 1);
+    // the cluster graph (keys, sum, eg.off) starts as the object graph; t* / s* are the contraction's work arrays
+    dbuf<uint64_t> keys((size_t)m0), sum((size_t)m0), tkey((size_t)m0), tval((size_t)m0), skey((size_t)m0), sval((size_t)m0);
+    dbuf<uint64_t> msum((size_t)cap), mpairs((size_t)cap);
+    dbuf<int32_t> mc((size_t)cap), md((size_t)cap), parent((size_t)n), size((size_t)n), bdst((size_t)n);
+    dbuf<unsigned long long> bsum((size_t)n), cnt(2), n_groups(1);     // cnt: merges of all rounds so far, records of the cluster graph
+    VG_HIP(hipMemcpyAsync(keys.p, eg.ukeys.p, (size_t)m0 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(m0)), dim3(TPB), 0, s, (const double*)eg.uvals.p, m0, sum.p);
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, parent.p, n);
+    hipLaunchKernelGGL(k_fill, dim3(grid_of(n)), dim3(TPB), 0, s, size.p, n, 1);
+    const unsigned long long cnt0[2] = { 0, (unsigned long long)m0 };
+    cnt.upload(cnt0, 2, s);
+    int64_t rounds = 0, total = 0, m = m0, in_key_order = -1;  // in_key_order: the merges before the zero phase (-1: it never began)
+    char note[96];
+    for (;;) {
+        {
+            vg_prof_scope ps("cluster_average_best", (double)m * 20.0 + (double)n * 40.0);
+            hipLaunchKernelGGL(k_av_find, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)eg.off.p, (const uint64_t*)keys.p,
+                               (const uint64_t*)sum.p, (const int32_t*)size.p, bsum.p, bdst.p);
+            hipLaunchKernelGGL(k_av_match, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const unsigned long long*)bsum.p, (const int32_t*)bdst.p,
+                               (const int32_t*)size.p, F, in_key_order >= 0 ? 1 : 0, (const uint64_t*)keys.p, parent.p, msum.p, mpairs.p, mc.p,
+                               md.p, cap, cnt.p);
+        }
+        ++rounds;
+        unsigned long long now[2] = { 0, 0 };                   // the one read-back of the round: both counters
+        cnt.download(now, 2, s);
+        VG_HIP(hipStreamSynchronize(s));
+        const int64_t merges = (int64_t)now[0] - total;
+        total = (int64_t)now[0]; m = (int64_t)now[1];
+        if (total > cap || m < 0 || m > m0 || (m & 1)) throw vg_error(VG_EHIP, "vg_cluster_average_linkage: the merges are no hierarchy (internal error)");
+        snprintf(note, sizeof note, "average round %lld: %lld merges, %lld records", (long long)rounds, (long long)merges, (long long)m);
+        vg_host_mark(note);
+        if (rounds > 2 * n + 2) throw vg_error(VG_EHIP, "vg_cluster_average_linkage: the rounds do not end (internal error)");
+        if (merges == 0) {
+            if (F == 0 && m > 0 && in_key_order < 0) { in_key_order = total; continue; }     // only records of S == 0 are left
+            break;
+        }
+        vg_prof_scope ps("cluster_average_contract", (double)m * (32.0 + 32.0 * 2.0 + 32.0 + 24.0) + (double)n * 16.0);
+        hipLaunchKernelGGL(k_av_grow, dim3(grid_of(merges)), dim3(TPB), 0, s, (const int32_t*)mc.p, (const int32_t*)md.p, total - merges, total, size.p);
+        hipLaunchKernelGGL(k_av_relabel, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)keys.p, (const uint64_t*)sum.p, m,
+                           (const int32_t*)parent.p, n, bits, tkey.p, tval.p);
+        with_temp_storage([&](void* tmp, size_t& tb) {
+            return rocprim::radix_sort_pairs(tmp, tb, tkey.p, skey.p, tval.p, sval.p, (size_t)m, 0u, 2u * (unsigned)bits, s); });
+        with_temp_storage([&](void* tmp, size_t& tb) {           // -> (cluster pair, sum) in tkey / tval
+            return rocprim::reduce_by_key(tmp, tb, skey.p, sval.p, (size_t)m, tkey.p, tval.p, n_groups.p, rocprim::plus<uint64_t>(),
+                                          rocprim::equal_to<uint64_t>(), s); });
+        hipLaunchKernelGGL(k_av_compact, dim3(grid_of(m)), dim3(TPB), 0, s, (const unsigned long long*)n_groups.p, m, (const uint64_t*)tkey.p,
+                           (const uint64_t*)tval.p, n, bits, keys.p, sum.p, cnt.p + 1);
+        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)keys.p, m, n, eg.off.p, eg.adj.p);
+    }
+    VG_HIP(hipGetLastError());
+    f.stats.rounds = rounds;
+    f.stats.n_merges = total;
+    if (total == 0) return;
+    // the <= n - 1 merge records leave the device; their order is the key order (keys are distinct: d disappears when absorbed)
+    std::vector<uint64_t> hs((size_t)total), hp((size_t)total); std::vector<int32_t> hc((size_t)total), hd((size_t)total);
+    msum.download(hs.data(), (size_t)total, s); mpairs.download(hp.data(), (size_t)total, s);
+    mc.download(hc.data(), (size_t)total, s); md.download(hd.data(), (size_t)total, s);
+    VG_HIP(hipStreamSynchronize(s));
+    std::vector<int64_t> order((size_t)total);
+    for (int64_t k = 0; k < total; ++k) order[(size_t)k] = k;
+    std::stable_sort(order.begin(), order.begin() + (in_key_order >= 0 ? in_key_order : total), [&](int64_t x, int64_t y) {
+        return av_compare(av_cand{ hs[(size_t)x], hp[(size_t)x], (uint32_t)hc[(size_t)x], (uint32_t)hd[(size_t)x] },
+                          av_cand{ hs[(size_t)y], hp[(size_t)y], (uint32_t)hc[(size_t)y], (uint32_t)hd[(size_t)y] }) < 0; });
+    f.a.resize((size_t)total); f.b.resize((size_t)total); f.w.resize((size_t)total); f.sum.resize((size_t)total); f.pairs.resize((size_t)total);
+    for (int64_t k = 0; k < total; ++k) {
+        const size_t j = (size_t)order[(size_t)k];
+        f.a[(size_t)k] = hc[j]; f.b[(size_t)k] = hd[j]; f.sum[(size_t)k] = hs[j]; f.pairs[(size_t)k] = hp[j];
+        f.w[(size_t)k] = av_similarity(hs[j], hp[j]);
+    }
+}
 }  // namespace
 
 extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
@@ -827,10 +1044,12 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
 
 // ---------------------------------------------------------------- merge table and cuts (host numbering of <= n - 1 records)
 void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f,
-                       int algorithm) {
+                       int algorithm, double floor) {
     check_rows(fn, n_objects, q, r, w, n_rows);
     check_row_values(fn, n_objects, q, r, w, n_rows);
-    if (algorithm != VG_CLUSTER_SINGLE && algorithm != VG_CLUSTER_COMPLETE) throw vg_error(VG_EINVAL, std::string(fn) + ": the merge table is single or complete linkage");
+    if (algorithm != VG_CLUSTER_SINGLE && algorithm != VG_CLUSTER_COMPLETE && algorithm != VG_CLUSTER_AVERAGE)
+        throw vg_error(VG_EINVAL, std::string(fn) + ": the merge table is single, complete or average linkage");
+    if (algorithm == VG_CLUSTER_AVERAGE) check_unit_weights(fn, w, n_rows, floor);
     f = vg_forest{};
     if (n_objects == 0) return;
     vg_require_device();
@@ -838,6 +1057,7 @@ void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, con
     hipStream_t s = vg_stream();
     edge_graph eg;
     build_edge_graph(n_objects, q, r, w, n_rows, s, eg);
+    if (algorithm == VG_CLUSTER_AVERAGE) { average_on_device(n_objects, eg, floor, s, f); return; }
     dbuf<int32_t> comp;
     complete_on_device(n_objects, eg, s, comp, &f);
 }
@@ -868,7 +1088,11 @@ void vg_forest_table(int64_t n, const vg_forest& f, int64_t* node_a, int64_t* no
 
 void vg_forest_cut(int64_t n, const vg_forest& f, double level, int32_t* label, int32_t* rep) {
     min_sets sets(n);
-    for (size_t k = 0; k < f.a.size() && f.w[k] >= level; ++k) sets.join(f.a[k], f.b[k]);       // (the weights are non-increasing)
+    if (f.sum.empty()) { for (size_t k = 0; k < f.a.size() && f.w[k] >= level; ++k) sets.join(f.a[k], f.b[k]); }    // (the weights are non-increasing)
+    else {                                                      // average linkage: on the exact (S, P), not on the rounded double
+        const uint64_t T = av_quanta(level);
+        for (size_t k = 0; k < f.a.size(); ++k) if (av_reaches(f.sum[k], f.pairs[k], T)) sets.join(f.a[k], f.b[k]);
+    }
     std::vector<int32_t> members((size_t)n, 0);
     for (int64_t i = 0; i < n; ++i) { rep[i] = sets.find((int32_t)i); ++members[(size_t)rep[i]]; }
     // multi-member clusters 0.. by earliest member, then singletons in object order (as k_head_labels)
@@ -882,33 +1106,37 @@ void vg_forest_cut(int64_t n, const vg_forest& f, double level, int32_t* label, 
 namespace {
 void linkage_graph(const char* fn, int algorithm, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                    int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
-                   int64_t* size, int64_t* n_merges, vg_linkage_stats* stats) {
+                   int64_t* size, int64_t* n_merges, vg_linkage_stats* stats, double floor = 0.0, uint64_t* sum = nullptr, uint64_t* pairs = nullptr) {
     check_rows(fn, n_objects, q, r, w, n_rows);
-    if (!n_merges || (n_objects > 1 && (!object_a || !object_b || !weight || !node_a || !node_b || !size)))
+    const bool average = algorithm == VG_CLUSTER_AVERAGE;
+    if (!n_merges || (n_objects > 1 && (!object_a || !object_b || !weight || !node_a || !node_b || !size || (average && (!sum || !pairs)))))
         throw vg_error(VG_EINVAL, std::string(fn) + ": null output");
     *n_merges = 0;
     if (stats) *stats = vg_linkage_stats{};
     vg_forest f;
-    vg_cluster_forest(fn, n_objects, q, r, w, n_rows, f, algorithm);
+    vg_cluster_forest(fn, n_objects, q, r, w, n_rows, f, algorithm, floor);
     const size_t nf = f.a.size();
     if (nf) {
         memcpy(object_a, f.a.data(), nf * sizeof(int32_t)); memcpy(object_b, f.b.data(), nf * sizeof(int32_t));
         memcpy(weight, f.w.data(), nf * sizeof(double));
+        if (average) { memcpy(sum, f.sum.data(), nf * sizeof(uint64_t)); memcpy(pairs, f.pairs.data(), nf * sizeof(uint64_t)); }
         vg_forest_table(n_objects, f, node_a, node_b, size);
     }
     *n_merges = (int64_t)nf;
     if (stats) *stats = f.stats;
 }
 void levels_graph(const char* fn, int algorithm, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
-                  const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats) {
+                  const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats, double floor = 0.0) {
     const std::string name(fn);
     check_rows(fn, n_objects, q, r, w, n_rows);
     if (n_levels < 0 || (n_levels && !levels)) throw vg_error(VG_EINVAL, name + ": null levels");
     for (int l = 0; l < n_levels; ++l) if (std::isnan(levels[l])) throw vg_error(VG_EINVAL, name + ": a level is NaN");
+    if (algorithm == VG_CLUSTER_AVERAGE)                        // (the hierarchy stops at the floor: there is nothing to cut below it)
+        for (int l = 0; l < n_levels; ++l) if (levels[l] < floor) throw vg_error(VG_EINVAL, name + ": level " + std::to_string(levels[l]) + " is below the floor");
     if (n_objects && n_levels && (!label || !representative)) throw vg_error(VG_EINVAL, name + ": null output");
     if (stats) *stats = vg_linkage_stats{};
     vg_forest f;
-    vg_cluster_forest(fn, n_objects, q, r, w, n_rows, f, algorithm);
+    vg_cluster_forest(fn, n_objects, q, r, w, n_rows, f, algorithm, floor);
     for (int l = 0; l < n_levels; ++l) vg_forest_cut(n_objects, f, levels[l], label + (int64_t)l * n_objects, representative + (int64_t)l * n_objects);
     if (stats) *stats = f.stats;
 }
@@ -941,5 +1169,48 @@ extern "C" int vg_cluster_complete_levels_graph(int64_t n_objects, const uint32_
                                                 vg_linkage_stats* stats) {
     VG_API_BEGIN
     levels_graph("vg_cluster_complete_levels_graph", VG_CLUSTER_COMPLETE, n_objects, q, r, w, n_rows, levels, n_levels, label, representative, stats);
+    VG_API_END
+}
+
+extern "C" int vg_cluster_average_linkage_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                                double floor, int32_t* object_a, int32_t* object_b, double* similarity, uint64_t* sum,
+                                                uint64_t* pairs, int64_t* node_a, int64_t* node_b, int64_t* size, int64_t* n_merges,
+                                                vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    linkage_graph("vg_cluster_average_linkage_graph", VG_CLUSTER_AVERAGE, n_objects, q, r, w, n_rows, object_a, object_b, similarity, node_a, node_b, size,
+                  n_merges, stats, floor, sum, pairs);
+    VG_API_END
+}
+extern "C" int vg_cluster_average_levels_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                               double floor, const double* levels, int n_levels, int32_t* label, int32_t* representative,
+                                               vg_linkage_stats* stats) {
+    VG_API_BEGIN
+    levels_graph("vg_cluster_average_levels_graph", VG_CLUSTER_AVERAGE, n_objects, q, r, w, n_rows, levels, n_levels, label, representative, stats, floor);
+    VG_API_END
+}
+
+// ---------------------------------------------------------------- test entries of the average-linkage arithmetic
+extern "C" double vg_cluster_average_similarity(uint64_t sum, uint64_t pairs) { return av_similarity(sum, pairs); }
+
+extern "C" int vg_cluster_average_order_selftest(const uint64_t* sum, const uint32_t* size_c, const uint32_t* size_d, const uint32_t* c,
+                                                 const uint32_t* d, int64_t n, int on_device, int8_t* out) {
+    VG_API_BEGIN
+    if (n < 0 || (n > 0 && (!sum || !size_c || !size_d || !c || !d)) || (n > 1 && !out))
+        throw vg_error(VG_EINVAL, "vg_cluster_average_order_selftest: null argument");
+    if (n < 2) return VG_OK;
+    if (!on_device) {
+        auto cand = [&](int64_t i) { return av_cand{ sum[i], (uint64_t)size_c[i] * size_d[i], std::min(c[i], d[i]), std::max(c[i], d[i]) }; };
+        for (int64_t i = 0; i + 1 < n; ++i) out[i] = (int8_t)av_compare(cand(i), cand(i + 1));
+        return VG_OK;
+    }
+    vg_require_device();
+    hipStream_t s = vg_stream();
+    dbuf<uint64_t> ds((size_t)n); dbuf<uint32_t> dsc((size_t)n), dsd((size_t)n), dc((size_t)n), dd((size_t)n); dbuf<int8_t> dout((size_t)n - 1);
+    ds.upload(sum, (size_t)n, s); dsc.upload(size_c, (size_t)n, s); dsd.upload(size_d, (size_t)n, s); dc.upload(c, (size_t)n, s); dd.upload(d, (size_t)n, s);
+    hipLaunchKernelGGL(k_av_order, dim3(grid_of(n - 1)), dim3(TPB), 0, s, (const uint64_t*)ds.p, (const uint32_t*)dsc.p, (const uint32_t*)dsd.p,
+                       (const uint32_t*)dc.p, (const uint32_t*)dd.p, n, dout.p);
+    VG_HIP(hipGetLastError());
+    dout.download(out, (size_t)n - 1, s);
+    VG_HIP(hipStreamSynchronize(s));
     VG_API_END
 }

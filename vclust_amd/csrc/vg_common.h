@@ -192,10 +192,12 @@ void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives);
 // merge table (vg_cluster.hip): the forest edges of the rows in merge order (a < b, weights non-increasing) -- checks the rows
 // (errors name fn), then the device; the node numbering of the table and the labels of a cut are host loops over those records.
-// algorithm: VG_CLUSTER_SINGLE (the maximum spanning forest) or VG_CLUSTER_COMPLETE (the worst edge of every complete-linkage merge)
-struct vg_forest { std::vector<int32_t> a, b; std::vector<double> w; vg_linkage_stats stats{}; };
+// algorithm: VG_CLUSTER_SINGLE (the maximum spanning forest), VG_CLUSTER_COMPLETE (the worst edge of every complete-linkage merge)
+// or VG_CLUSTER_AVERAGE: (a, b) are the two cluster ids merged, w the rounded average, and sum / pairs hold the exact (S, P) of every
+// record (empty for the other two); floor is read by VG_CLUSTER_AVERAGE alone, which also wants every weight in [0, 1]
+struct vg_forest { std::vector<int32_t> a, b; std::vector<double> w; std::vector<uint64_t> sum, pairs; vg_linkage_stats stats{}; };
 void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f,
-                       int algorithm = VG_CLUSTER_SINGLE);
+                       int algorithm = VG_CLUSTER_SINGLE, double floor = 0.0);
 void vg_forest_table(int64_t n, const vg_forest& f, int64_t* node_a, int64_t* node_b, int64_t* size);
 void vg_forest_cut(int64_t n, const vg_forest& f, double level, int32_t* label, int32_t* rep);
 // clusters.tsv with further columns (vg_io.cpp): column c has the header names[c] and the labels / representatives label[c], rep[c]

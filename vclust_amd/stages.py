@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, AlignParams, ClusterParams, DedupOptions, DedupParams, LzParams, PrefilterParams, check
+from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, AlignParams, ClusterParams, DedupOptions, DedupParams, LzParams, PrefilterParams, check
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -56,12 +56,14 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     """clusters.tsv from ani.tsv + its ids file (vg_cluster).  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio= (0 = off);
     num_alns: max. number of local alignments of a passing row (0 = off).  out_linkage: also the merge table
     -> that file; levels: one more column per level, the cut of the same forest there (vg_cluster_linkage; both need
-    algorithm='single' or 'complete' -- then the complete-linkage merge table and its cuts -- and no level below the metric's
-    minimum).  algorithm='complete' without either is the cut of that hierarchy at the floor (vg_cluster)."""
+    algorithm='single', 'complete' or 'average' -- the merge table and the cuts of that hierarchy -- and no level below the metric's
+    minimum).  algorithm='complete' or 'average' without either is the cut of that hierarchy at the floor (vg_cluster).  'average'
+    (UPGMA in exact arithmetic; a pair without a row counts as 0) stops at the metric's minimum, and its cut at a level is not
+    a run at that minimum: the rows between the two still count in the averages."""
     unknown = set(mins) - set(CLUSTER_FILTERS)
     if unknown:
         raise TypeError(f'unknown filter(s): {sorted(unknown)}')
-    known = {**CLUSTER_ALGORITHMS, **LINKAGE_ALGORITHMS}
+    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS}
     if algorithm not in known:
         raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
     p = ClusterParams(algorithm=known[algorithm], metric=metric.encode(), max_num_alns=int(num_alns),
@@ -72,8 +74,8 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     if out_linkage is None and levels is None:
         check(_lib.load().vg_cluster(*paths, C.byref(p)))
         return
-    if algorithm not in LINKAGE_ALGORITHMS:
-        raise ValueError('out_linkage and levels need algorithm=\'single\' or \'complete\'')
+    if algorithm not in HIERARCHY_ALGORITHMS:
+        raise ValueError('out_linkage and levels need algorithm=\'single\', \'complete\' or \'average\'')
     lv = [float(x) for x in (levels or ())]
     check(_lib.load().vg_cluster_linkage(*paths, C.byref(p), os.fsencode(str(out_linkage)) if out_linkage is not None else None,
                                          (C.c_double * len(lv))(*lv) if lv else None, len(lv)))
