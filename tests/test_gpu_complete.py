@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import average_restatement as av
 import cluster_restatement as cr
 import complete_restatement as cl
 import linkage_restatement as lr
@@ -122,6 +123,33 @@ def test_clique_of_200_merges_once_per_round(api):
     table, stats = _check(api, n, q, r, w, [0.95, 0.9, 0.85])
     assert stats['n_merges'] == n - 1 and stats['rounds'] == n and table['size'][-1] == n
     assert table['object_a'].tolist() == list(range(n - 1)) and table['object_b'].tolist() == list(range(1, n))      # the worst pair: (k - 1, k)
+
+
+@pytest.mark.parametrize('degree', [1, 15, 16, 17, 33])
+def test_rows_around_the_lane_count(api, degree):
+    """a clique of `degree` + 1 objects with distinct weights plus random extra rows: rows of 1, 15, 16, 17 and 33 records
+    (ROW_LANES = 16) that shrink through the contractions; 4, 15, 17, 17 and 34 merges by the restatement"""
+    rng = np.random.default_rng(degree)
+    n = degree + 9
+    q, r = np.triu_indices(degree + 1, 1)
+    w = 0.5 + 1e-4 * rng.permutation(len(q))
+    q = np.concatenate([q, rng.integers(0, n, 12)]).astype(np.uint32)
+    r = np.concatenate([r, rng.integers(0, n, 12)]).astype(np.uint32)
+    w = np.concatenate([w, rng.choice([0.5, 0.75, 1.0], 12)])
+    _, stats = _check(api, n, q, r, w, [0.75, 0.5])
+    assert stats['n_merges'] >= degree
+
+
+def test_complete_then_average_then_complete(api, graph300):
+    """the loop the two linkages share carries no state from one to the next"""
+    q, r, w, _ = graph300
+    t0, s0 = api.cluster_complete_linkage_graph(300, q, r, w)
+    ta, _ = api.cluster_average_linkage_graph(300, q, r, w, 0.7)
+    t1, s1 = api.cluster_complete_linkage_graph(300, q, r, w)
+    assert t0.tobytes() == t1.tobytes() and s0 == s1
+    want = av.merges(300, cr.edges(zip(q.tolist(), r.tolist(), w.tolist())), 0.7)
+    assert [(int(t['object_a']), int(t['object_b']), int(t['sum']), int(t['pairs'])) for t in ta] == want
+    assert _as_rows(ta) == av.table(300, want)
 
 
 def test_planted_cliques_with_ties(api, graph300):

@@ -255,19 +255,14 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     known = {**CLUSTER_ALGORITHMS, **LINKAGE_ALGORITHMS}
     if algorithm not in known:
         raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
-    q = np.ascontiguousarray(q, dtype=np.uint32)
-    r = np.ascontiguousarray(r, dtype=np.uint32)
-    w = np.ascontiguousarray(w, dtype=np.float64)
-    if not len(q) == len(r) == len(w):
-        raise ValueError('q, r and w must have the same length')
+    q, r, w, rows = _rows(q, r, w)
     n = int(n_objects)
     label = np.zeros(max(n, 1), dtype=np.int32)
     rep = np.zeros(max(n, 1), dtype=np.int32)
     st = ClusterStats()
     P = C.POINTER
-    check(_lib.load().vg_cluster_graph(n, q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)),
-                                       w.ctypes.data_as(P(C.c_double)), len(q), known[algorithm],
-                                       label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    check(_lib.load().vg_cluster_graph(n, *rows, known[algorithm], label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
+                                       C.byref(st)))
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
 
 
@@ -281,22 +276,25 @@ def _rows(q, r, w):
     return q, r, w, (q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)), w.ctypes.data_as(P(C.c_double)), len(q))
 
 
-def _linkage_table(fn, n_objects, q, r, w):
-    """-> (table, stats) of the array-level merge-table call `fn`"""
+def _linkage_table(fn, n_objects, q, r, w, floor=None):
+    """-> (table, stats) of the array-level merge-table call `fn`.  With a floor, `fn` is the average-linkage entry: it takes the
+    floor after the rows and returns `sum` and `pairs` after the similarity, in an AVERAGE_LINKAGE_DTYPE table."""
     q, r, w, rows = _rows(q, r, w)
     n = int(n_objects)
     cap = max(n - 1, 1) if n < 1 << 31 else 1          # (2^31 objects or more: the library refuses before it writes)
     oa, ob = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
     wt = np.zeros(cap, dtype=np.float64)
+    exact = [] if floor is None else [np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)]       # sum, pairs
     na, nb, sz = (np.zeros(cap, dtype=np.int64) for _ in range(3))
     nm = C.c_int64(0)
     st = LinkageStats()
     P = C.POINTER
-    check(getattr(_lib.load(), fn)(n, *rows, oa.ctypes.data_as(P(C.c_int32)), ob.ctypes.data_as(P(C.c_int32)),
-                                   wt.ctypes.data_as(P(C.c_double)), na.ctypes.data_as(P(C.c_int64)),
+    check(getattr(_lib.load(), fn)(n, *rows, *([] if floor is None else [float(floor)]), oa.ctypes.data_as(P(C.c_int32)),
+                                   ob.ctypes.data_as(P(C.c_int32)), wt.ctypes.data_as(P(C.c_double)),
+                                   *(x.ctypes.data_as(P(C.c_uint64)) for x in exact), na.ctypes.data_as(P(C.c_int64)),
                                    nb.ctypes.data_as(P(C.c_int64)), sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
-    table = np.zeros(nm.value, dtype=LINKAGE_DTYPE)
-    for name, arr in (('node_a', na), ('node_b', nb), ('similarity', wt), ('size', sz), ('object_a', oa), ('object_b', ob)):
+    table = np.zeros(nm.value, dtype=LINKAGE_DTYPE if floor is None else AVERAGE_LINKAGE_DTYPE)
+    for name, arr in zip(table.dtype.names, (na, nb, wt, sz, oa, ob, *exact)):
         table[name] = arr[:nm.value]
     return table, dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
 
@@ -335,42 +333,14 @@ def cluster_average_linkage_graph(n_objects, q, r, w, floor=0.0):
     singletons the pair of smallest key (-sim, c, d) merges until none is left or sim < floor.  -> (table, stats): table is an
     AVERAGE_LINKAGE_DTYPE array -- the fields of cluster_linkage with (object_a, object_b) the two cluster ids merged, plus the
     exact `sum` S and `pairs` P = |A| |B| of each record; `similarity` is the double nearest to S / (P 2^32) and never rises."""
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
-    cap = max(n - 1, 1) if n < 1 << 31 else 1
-    oa, ob = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
-    wt = np.zeros(cap, dtype=np.float64)
-    sm, pr = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
-    na, nb, sz = (np.zeros(cap, dtype=np.int64) for _ in range(3))
-    nm = C.c_int64(0)
-    st = LinkageStats()
-    P = C.POINTER
-    check(_lib.load().vg_cluster_average_linkage_graph(
-        n, *rows, float(floor), oa.ctypes.data_as(P(C.c_int32)), ob.ctypes.data_as(P(C.c_int32)), wt.ctypes.data_as(P(C.c_double)),
-        sm.ctypes.data_as(P(C.c_uint64)), pr.ctypes.data_as(P(C.c_uint64)), na.ctypes.data_as(P(C.c_int64)), nb.ctypes.data_as(P(C.c_int64)),
-        sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
-    table = np.zeros(nm.value, dtype=AVERAGE_LINKAGE_DTYPE)
-    for name, arr in (('node_a', na), ('node_b', nb), ('similarity', wt), ('size', sz), ('object_a', oa), ('object_b', ob), ('sum', sm),
-                      ('pairs', pr)):
-        table[name] = arr[:nm.value]
-    return table, dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+    return _linkage_table('vg_cluster_average_linkage_graph', n_objects, q, r, w, floor)
 
 
 def cluster_average_levels_graph(n_objects, q, r, w, levels, floor=0.0):
     """The cuts of one average-linkage merge table at `levels` (vg_cluster_average_levels_graph): the cut at t joins the merges
     with S >= round(t * 2^32) * P, compared exactly.  No level may lie below `floor`.  It is NOT cluster_average_linkage_graph
     with floor t cut at its floor: the rows between floor and t still count in the averages.  -> as cluster_levels."""
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
-    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
-    width = n if 0 < n < 1 << 31 else 1
-    label = np.zeros((len(lv), width), dtype=np.int32)
-    rep = np.zeros((len(lv), width), dtype=np.int32)
-    st = LinkageStats()
-    P = C.POINTER
-    check(_lib.load().vg_cluster_average_levels_graph(n, *rows, float(floor), lv.ctypes.data_as(P(C.c_double)), len(lv),
-                                                      label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
-    return label[:, :n], rep[:, :n], dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+    return _levels('vg_cluster_average_levels_graph', n_objects, q, r, w, levels, floor)
 
 
 def cluster_average_similarity(s, p):
@@ -399,7 +369,8 @@ def cluster_levels(n_objects, q, r, w, levels):
     return _levels('vg_cluster_levels_graph', n_objects, q, r, w, levels)
 
 
-def _levels(fn, n_objects, q, r, w, levels):
+def _levels(fn, n_objects, q, r, w, levels, floor=None):
+    """-> (label, representative, stats) of the array-level cuts call `fn`; with a floor, of the average-linkage entry"""
     q, r, w, rows = _rows(q, r, w)
     n = int(n_objects)
     lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
@@ -408,8 +379,8 @@ def _levels(fn, n_objects, q, r, w, levels):
     rep = np.zeros((len(lv), width), dtype=np.int32)
     st = LinkageStats()
     P = C.POINTER
-    check(getattr(_lib.load(), fn)(n, *rows, lv.ctypes.data_as(P(C.c_double)), len(lv), label.ctypes.data_as(P(C.c_int32)),
-                                   rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    check(getattr(_lib.load(), fn)(n, *rows, *([] if floor is None else [float(floor)]), lv.ctypes.data_as(P(C.c_double)), len(lv),
+                                   label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
     return label[:, :n], rep[:, :n], dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
 
 

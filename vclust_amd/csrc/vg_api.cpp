@@ -129,36 +129,46 @@ static double metric_floor(const vg_cluster_params* p) {
     return !strcmp(p->metric, "tani") ? p->min_tani : !strcmp(p->metric, "gani") ? p->min_gani : p->min_ani;
 }
 
+// The opening of vg_cluster and vg_cluster_linkage (`fn` names the caller in the error texts): the metric, the levels if any (none
+// may lie below the metric's minimum), then both files parsed beside the creation of the HIP context.
+struct cluster_input { std::vector<std::string> ids; std::vector<uint32_t> q, r; std::vector<double> w; };
+static void read_cluster_input(const std::string& fn, const char* ani_path, const char* ids_path, const vg_cluster_params* p,
+                               const double* levels, int n_levels, cluster_input& in) {
+    if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
+        throw vg_error(VG_EINVAL, fn + ": metric must be tani, gani or ani, not " + p->metric);
+    for (int l = 0; l < n_levels; ++l)
+        if (!(levels[l] >= metric_floor(p)))          // (also a NaN)
+            throw vg_error(VG_EINVAL, fn + ": level " + std::to_string(levels[l]) + " is below the " + p->metric + " minimum (rows below it are not edges)");
+    vg_host_mark((fn + ": enter").c_str());
+    device_warmup warm(WARM_CLUSTER);         // (the HIP context is created beside the parse)
+    vg_cluster_read_ids(ids_path, in.ids);
+    if ((int64_t)in.ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
+    vg_cluster_read_rows(ani_path, (int64_t)in.ids.size(), p, in.q, in.r, in.w);
+    vg_host_mark("ani.tsv parsed");
+    warm.join();
+}
+
 extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p) {
     VG_API_BEGIN
     if (!ani_path || !ids_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster: null argument");
     if (p->algorithm < VG_CLUSTER_SINGLE || p->algorithm > VG_CLUSTER_AVERAGE) throw vg_error(VG_EINVAL, "vg_cluster: unknown algorithm");
-    if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
-        throw vg_error(VG_EINVAL, std::string("vg_cluster: metric must be tani, gani or ani, not ") + p->metric);
-    vg_host_mark("vg_cluster: enter");
-    device_warmup warm(WARM_CLUSTER);         // (the HIP context is created beside the parse)
-    std::vector<std::string> ids;
-    vg_cluster_read_ids(ids_path, ids);
-    if ((int64_t)ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
-    std::vector<uint32_t> q, r; std::vector<double> w;
-    vg_cluster_read_rows(ani_path, (int64_t)ids.size(), p, q, r, w);
-    vg_host_mark("ani.tsv parsed");
-    warm.join();
-    const int64_t n = (int64_t)ids.size();
+    cluster_input in;
+    read_cluster_input("vg_cluster", ani_path, ids_path, p, nullptr, 0, in);
+    const int64_t n = (int64_t)in.ids.size();
     std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
     vg_cluster_stats st{};
     if (p->algorithm == VG_CLUSTER_AVERAGE) {                   // the average-linkage hierarchy down to the metric's minimum, every merge joined
         vg_forest f;
-        vg_cluster_forest("vg_cluster", n, q.data(), r.data(), w.data(), (int64_t)q.size(), f, VG_CLUSTER_AVERAGE, metric_floor(p));
+        vg_cluster_forest("vg_cluster", n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), f, VG_CLUSTER_AVERAGE, metric_floor(p));
         vg_forest_cut(n, f, -HUGE_VAL, label.data(), rep.data());
         st.rounds = f.stats.rounds; st.n_edges = f.stats.n_edges;
     } else
-    check(vg_cluster_graph(n, q.data(), r.data(), w.data(), (int64_t)q.size(), p->algorithm, label.data(), rep.data(), &st));
+    check(vg_cluster_graph(n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), p->algorithm, label.data(), rep.data(), &st));
     vg_host_mark("clusters computed");
-    vg_cluster_write(out_path, ids, label.data(), rep.data(), p->representatives != 0);
+    vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0);
     if (p->verbosity >= 2)
         fprintf(stderr, "vg_cluster: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld objects by the tail sweep\n",
-                (long long)n, (long long)q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+                (long long)n, (long long)in.q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
     VG_API_END
 }
 
@@ -169,24 +179,11 @@ extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, co
         throw vg_error(VG_EINVAL, "vg_cluster_linkage: null argument");
     if (p->algorithm != VG_CLUSTER_SINGLE && p->algorithm != VG_CLUSTER_COMPLETE && p->algorithm != VG_CLUSTER_AVERAGE)
         throw vg_error(VG_EINVAL, "vg_cluster_linkage: the merge table is single, complete or average linkage (algorithm must be one of the three)");
-    if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
-        throw vg_error(VG_EINVAL, std::string("vg_cluster_linkage: metric must be tani, gani or ani, not ") + p->metric);
-    const double floor = metric_floor(p);
-    for (int l = 0; l < n_levels; ++l)
-        if (!(levels[l] >= floor))          // (also a NaN)
-            throw vg_error(VG_EINVAL, "vg_cluster_linkage: level " + std::to_string(levels[l]) + " is below the " + p->metric + " minimum (rows below it are not edges)");
-    vg_host_mark("vg_cluster_linkage: enter");
-    device_warmup warm(WARM_CLUSTER);         // (the HIP context is created beside the parse)
-    std::vector<std::string> ids;
-    vg_cluster_read_ids(ids_path, ids);
-    if ((int64_t)ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
-    std::vector<uint32_t> q, r; std::vector<double> w;
-    vg_cluster_read_rows(ani_path, (int64_t)ids.size(), p, q, r, w);
-    vg_host_mark("ani.tsv parsed");
-    warm.join();
-    const int64_t n = (int64_t)ids.size();
+    cluster_input in;
+    read_cluster_input("vg_cluster_linkage", ani_path, ids_path, p, levels, n_levels, in);
+    const int64_t n = (int64_t)in.ids.size();
     vg_forest f;
-    vg_cluster_forest("vg_cluster_linkage", n, q.data(), r.data(), w.data(), (int64_t)q.size(), f, p->algorithm, floor);
+    vg_cluster_forest("vg_cluster_linkage", n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), f, p->algorithm, metric_floor(p));
     vg_host_mark("forest computed");
     // column 0: every merge (the cut at the floor, i.e. the algorithm on the passing rows); then one cut per level
     const size_t cols = (size_t)n_levels + 1, stride = (size_t)std::max<int64_t>(n, 1);
@@ -204,9 +201,9 @@ extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, co
         vg_forest_table(n, f, node_a.data(), node_b.data(), size.data());
         vg_linkage_write(linkage_path, f, node_a.data(), node_b.data(), size.data());
     }
-    vg_cluster_write_columns(out_path, ids, names, lab_col, rep_col, p->representatives != 0);
+    vg_cluster_write_columns(out_path, in.ids, names, lab_col, rep_col, p->representatives != 0);
     if (p->verbosity >= 2)
         fprintf(stderr, "vg_cluster_linkage: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld merges, %d levels\n",
-                (long long)n, (long long)q.size(), (long long)f.stats.n_edges, (long long)f.stats.rounds, (long long)f.stats.n_merges, n_levels);
+                (long long)n, (long long)in.q.size(), (long long)f.stats.n_edges, (long long)f.stats.rounds, (long long)f.stats.n_merges, n_levels);
     VG_API_END
 }

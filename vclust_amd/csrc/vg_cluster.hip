@@ -8,11 +8,14 @@
 //   labels    min member per cluster, multi-member clusters numbered by earliest member, then singletons
 //   linkage   the single-linkage merge table: edges ranked by (w descending, a, b) with one more radix sort, Boruvka rounds on
 //             the ranks (find + hook + jump + relabel), the marked forest edges compacted in rank order; node numbering on the host
-//   complete  the complete-linkage merge table on the same ranks: rounds that merge every pair of mutually nearest clusters
-//             (find + match), then a contraction of the cluster graph (relabel, radix sort, reduce-by-key, select, CSR) that keeps
-//             a cluster pair only while every object pair between the two is an edge; the merge records go the forest's way
-//   average   the average-linkage (UPGMA) merge table in exact integer arithmetic: the same rounds on 64-bit sums of quantised
-//             weights, candidates compared as fractions (128-bit products), and a contraction that adds the sums of a cluster pair
+//   rounds    the loop of the two contraction-based hierarchies (agglomerate): rounds that merge every pair of mutually nearest
+//             clusters (find + match), one read-back, then a contraction of the cluster graph (relabel, radix sort, reduce-by-key,
+//             compaction, CSR).  A linkage is a small policy struct that supplies what differs:
+//   complete  the complete-linkage merge table on the ranks of the single-linkage table: the smallest rank of a row, a reduction to
+//             the worst rank that keeps a cluster pair only while every object pair between the two is an edge (select); the merge
+//             records go the forest's way
+//   average   the average-linkage (UPGMA) merge table in exact integer arithmetic: 64-bit sums of quantised weights, candidates
+//             compared as fractions (128-bit products), a reduction that adds the sums of a cluster pair
 // Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
 // only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
 // their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
@@ -21,6 +24,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <type_traits>
 
 namespace {
 constexpr int32_t UND = -1;             // an undecided / unassigned object (state arrays are cleared with 0xff bytes)
@@ -31,6 +35,8 @@ constexpr int SC_BLK = 1024;            // objects per block of the set-cover ar
 constexpr int SC_DIRTY_CAP = 2048;      // dirty blocks listed per pick (more: every block is recomputed)
 
 int grid_of(int64_t n, int cap = 8192) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, cap)); }
+// bits of an object or cluster id, the sentinel n included: the low half of an edge's sort key, both halves of a contraction's
+int id_bits(int64_t n) { int bits = 1; while ((1LL << bits) <= n) ++bits; return bits; }
 
 __device__ __forceinline__ int32_t ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -86,14 +92,13 @@ __global__ void k_hook(const uint64_t* keys, int64_t m, int32_t* parent, int32_t
     }
     if (c) st(changed, 1);
 }
-// pointer jumping to the root (roots do not move inside this kernel; a stale read is an older ancestor)
-__global__ void k_compress(int32_t* parent, int64_t n) {
-    GRID_STRIDE(i, n) {
-        int32_t x = ld(parent + i);
-        for (;;) { const int32_t y = ld(parent + x); if (y == x) break; x = y; }
-        st(parent + i, x);
-    }
+// pointer jumping to the root (roots do not move inside the kernel; a stale read is an older ancestor)
+__device__ __forceinline__ void jump_to_root(int32_t* parent, int64_t i) {
+    int32_t x = ld(parent + i);
+    for (;;) { const int32_t y = ld(parent + x); if (y == x) break; x = y; }
+    st(parent + i, x);
 }
+__global__ void k_compress(int32_t* parent, int64_t n) { GRID_STRIDE(i, n) jump_to_root(parent, i); }
 
 // ---------------------------------------------------------------- cd-hit / uclust
 // state[i]: UND, i (REP) or j < i (MEMBER of REP j).  Object i looks at its earlier neighbours only (the row prefix < i).
@@ -364,12 +369,7 @@ __global__ void k_bor_hook(int64_t n, const int32_t* comp, const unsigned long l
 }
 // step 3: pointer jumping over the roots of this round (parent[] of a current root is itself; a stale read is an older ancestor)
 __global__ void k_bor_jump(int64_t n, const int32_t* comp, int32_t* parent) {
-    GRID_STRIDE(i, n) {
-        if (comp[i] != (int32_t)i) continue;
-        int32_t x = ld(parent + i);
-        for (;;) { const int32_t y = ld(parent + x); if (y == x) break; x = y; }
-        st(parent + i, x);
-    }
+    GRID_STRIDE(i, n) if (comp[i] == (int32_t)i) jump_to_root(parent, i);
 }
 // step 4: every root of this round now points at its final root
 __global__ void k_bor_relabel(int64_t n, const int32_t* parent, int32_t* comp) { GRID_STRIDE(i, n) comp[i] = parent[comp[i]]; }
@@ -381,10 +381,26 @@ __global__ void k_forest_gather(const int64_t* frank, int64_t nf, const int64_t*
     }
 }
 
+// ---------------------------------------------------------------- cluster graph (complete and average linkage)
+// Both hierarchies run on a cluster graph: directed records (src cluster << 32 | dst cluster, value), sorted by key, with row
+// offsets; a cluster's id is its minimum member; initially these are the object graph.  A round is the linkage's find + match over
+// it, then a contraction whose first step is the same for both:
+// every record under the new cluster ids, keyed on 2 * bits bits for the sort, its value shifted up by count_bits with a count of 1
+// below it (complete linkage counts the records merged into one; average linkage has no count bits and keeps the value); the
+// record of a merged pair itself becomes the sentinel (src = n) that sorts last.  One hop of parent[] is enough: the merges are a
+// matching.
+__global__ void k_relabel(const uint64_t* keys, const uint64_t* val, int64_t m, const int32_t* parent, int64_t n, int bits, int count_bits,
+                          uint64_t* okey, uint64_t* oval) {
+    GRID_STRIDE(e, m) {
+        const uint64_t s = (uint64_t)parent[keys[e] >> 32], d = (uint64_t)parent[(uint32_t)keys[e]];
+        okey[e] = s == d ? (uint64_t)n << bits : s << bits | d;
+        oval[e] = val[e] << count_bits | (count_bits ? 1 : 0);
+    }
+}
+
 // ---------------------------------------------------------------- complete linkage
-// The cluster graph: directed records (src cluster << 32 | dst cluster, rank), sorted by key, with row offsets.  A cluster's id is
-// its minimum member.  The rank of a record is K of the cluster pair: the largest rank over the object edges between the two, and
-// there is a record only while EVERY object pair between them is an edge.  Initially these are the object graph and its ranks.
+// The value of a record is a rank: K of the cluster pair, the largest rank over the object edges between the two, and there is a
+// record only while EVERY object pair between them is an edge.  Initially these are the ranks of the object graph.
 constexpr int COUNT_BITS = 3;           // contraction: a record's value is rank << 3 | records merged into it (<= 4 per cluster pair)
 // round, step 1: every cluster (ROW_LANES lanes each) finds the smallest rank of its row and the cluster at that record's other
 // end.  The ranks of a row are distinct (each is another object edge), so one lane holds the minimum.  A cluster with an empty
@@ -418,16 +434,7 @@ __global__ void k_cl_match(int64_t n, const unsigned long long* best, const int3
         parent[d] = (int32_t)c; mult[c] = 2;
     }
 }
-// contraction, step 1: every record under the new cluster ids, keyed on 2 * bits bits for the sort; the record of a merged pair
-// itself becomes the sentinel (src = n) that sorts last.  One hop of parent[] is enough: the merges are a matching.
-__global__ void k_cl_relabel(const uint64_t* keys, const uint64_t* rank, int64_t m, const int32_t* parent, int64_t n, int bits,
-                             uint64_t* okey, uint64_t* oval) {
-    GRID_STRIDE(e, m) {
-        const uint64_t s = (uint64_t)parent[keys[e] >> 32], d = (uint64_t)parent[(uint32_t)keys[e]];
-        okey[e] = s == d ? (uint64_t)n << bits : s << bits | d;
-        oval[e] = rank[e] << COUNT_BITS | 1;
-    }
-}
+// contraction (after k_relabel with COUNT_BITS and the sort): the reduce-by-key operator
 struct max_rank_add_count {             // (rank, count) + (rank, count) of one cluster pair: the worst rank, the records seen
     __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const {
         const uint64_t ra = a >> COUNT_BITS, rb = b >> COUNT_BITS, lowbits = (1ull << COUNT_BITS) - 1;
@@ -511,7 +518,7 @@ __global__ void k_av_find(int64_t n, const int64_t* off, const uint64_t* keys, c
     }
 }
 // step 2: (c, d), c < d, is a merge when each is the other's choice and sim >= floor (S >= F * P); a record of S == 0 never merges
-// here (see the host loop).  The key order is total and symmetric, so the merges of a round are a matching.  Reads only what
+// here (see average_linkage).  The key order is total and symmetric, so the merges of a round are a matching.  Reads only what
 // k_av_find wrote, size[] (which grows in the contraction, after these reads) and, in the zero phase, the first record: then the
 // one merge of the round is the record of smallest (c, d), which is keys[0].  The merge list is filled in any order.
 __global__ void k_av_match(int64_t n, const unsigned long long* bsum, const int32_t* bdst, const int32_t* size, uint64_t F, int zero_phase,
@@ -527,23 +534,13 @@ __global__ void k_av_match(int64_t n, const unsigned long long* bsum, const int3
         parent[d] = (int32_t)c;
     }
 }
-// contraction, step 1: the merges [from, to) of this round are a matching, so every size[] entry has one writer
+// before the contraction: the merges [from, to) of this round are a matching, so every size[] entry has one writer
 __global__ void k_av_grow(const int32_t* mc, const int32_t* md, int64_t from, int64_t to, int32_t* size) {
     GRID_STRIDE(j, to - from) size[mc[from + j]] += size[md[from + j]];
 }
-// step 2: every record under the new cluster ids, keyed on 2 * bits bits for the sort; the record of a merged pair itself becomes
-// the sentinel (src = n) that sorts last.  One hop of parent[] is enough: the merges are a matching.
-__global__ void k_av_relabel(const uint64_t* keys, const uint64_t* sum, int64_t m, const int32_t* parent, int64_t n, int bits,
-                             uint64_t* okey, uint64_t* oval) {
-    GRID_STRIDE(e, m) {
-        const uint64_t s = (uint64_t)parent[keys[e] >> 32], d = (uint64_t)parent[(uint32_t)keys[e]];
-        okey[e] = s == d ? (uint64_t)n << bits : s << bits | d;
-        oval[e] = sum[e];
-    }
-}
-// step 3 (after sort and reduce-by-key with plus): the groups, in key order, are the new records -- all but the sentinel group,
-// which is the last one; the tail of the old list is filled with the sentinel, so that k_csr over the old length gives the new
-// offsets.  *m_new = the new length, for the round's read-back.
+// contraction (after k_relabel without count bits, the sort and reduce-by-key with plus): the groups, in key order, are the new
+// records -- all but the sentinel group, which is the last one; the tail of the old list is filled with the sentinel, so that
+// k_csr over the old length gives the new offsets.  *m_new = the new length, for the round's read-back.
 __global__ void k_av_compact(const unsigned long long* n_groups, int64_t m_old, const uint64_t* gkey, const uint64_t* gsum, int64_t n, int bits,
                              uint64_t* keys, uint64_t* sum, unsigned long long* m_new) {
     const int64_t ng = (int64_t)*n_groups < m_old ? (int64_t)*n_groups : m_old;
@@ -600,24 +597,26 @@ void check_rows(const char* fn, int64_t n_objects, const uint32_t* q, const uint
     if (n_objects >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, name + ": 2^31 or more objects (object indices are int32)");
     if (n_rows && (!q || !r || !w)) throw vg_error(VG_EINVAL, name + ": null rows");
 }
-void check_row_values(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
+// the first row for which is_bad(row) holds, or -1: a parallel scan, every thread stops at the first of its chunk
+template <class Bad> int64_t first_bad_row(int64_t n_rows, Bad is_bad) {
     std::vector<int64_t> bad((size_t)std::max(1, vg_host_threads()), -1);
     vg_parallel_chunks(n_rows, vg_host_threads(), [&](int64_t lo, int64_t hi, int t) {
-        for (int64_t k = lo; k < hi; ++k)
-            if (q[k] >= (uint64_t)n_objects || r[k] >= (uint64_t)n_objects || std::isnan(w[k])) { bad[(size_t)t] = k; return; }
+        for (int64_t k = lo; k < hi; ++k) if (is_bad(k)) { bad[(size_t)t] = k; return; }
     });
-    for (int64_t k : bad) if (k >= 0)
+    for (int64_t k : bad) if (k >= 0) return k;
+    return -1;
+}
+void check_row_values(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
+    const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return q[i] >= (uint64_t)n_objects || r[i] >= (uint64_t)n_objects || std::isnan(w[i]); });
+    if (k >= 0)
         throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": " +
                        (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
 }
 // average linkage: the quantum 2^-32 and the 64-bit sums stand on weights (and a floor) in [0, 1]
 void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double floor) {
     if (!(floor >= 0 && floor <= 1)) throw vg_error(VG_EINVAL, std::string(fn) + ": the floor must lie in [0, 1]");
-    std::vector<int64_t> bad((size_t)std::max(1, vg_host_threads()), -1);
-    vg_parallel_chunks(n_rows, vg_host_threads(), [&](int64_t lo, int64_t hi, int t) {
-        for (int64_t k = lo; k < hi; ++k) if (!(w[k] >= 0 && w[k] <= 1)) { bad[(size_t)t] = k; return; }
-    });
-    for (int64_t k : bad) if (k >= 0)
+    const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return !(w[i] >= 0 && w[i] <= 1); });
+    if (k >= 0)
         throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1] (average linkage)");
 }
 
@@ -625,7 +624,7 @@ void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double 
 struct edge_graph { dbuf<uint64_t> ukeys; dbuf<double> uvals; int64_t m = 0; dbuf<int64_t> off; dbuf<int32_t> adj; };
 void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, hipStream_t s, edge_graph& g) {
     dbuf<uint64_t>& ukeys = g.ukeys; dbuf<double>& uvals = g.uvals; int64_t& m = g.m;
-    int bits = 1; while ((1LL << bits) <= n) ++bits;            // the sentinel source n must fit as well
+    const int bits = id_bits(n);
 
     // ---- edges: sort both directions by (src, dst), merge duplicates to the max weight, CSR
     if (n_rows) {
@@ -748,75 +747,117 @@ void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const dou
     download_forest(frank, nf, pos, eg, s, f);
 }
 
-// Complete linkage on the edge graph (which it consumes: the row offsets are rebuilt per contraction).  comp[i] = the cluster of
-// object i after every merge (its minimum member); f, if given, receives the merge records in merge order.  -> rounds launched
-int64_t complete_on_device(int64_t n, edge_graph& eg, hipStream_t s, dbuf<int32_t>& comp, vg_forest* f) {
+// ---------------------------------------------------------------- agglomeration rounds (complete and average linkage)
+// The state of the loop.  The cluster graph (keys, val, eg.off) starts as the object graph; t* / s* are the contraction's work arrays.
+struct cluster_rounds {
+    const int64_t n, m0, cap; const int bits; const hipStream_t s; edge_graph& eg;     // m0 directed edges, at most cap merges
+    dbuf<uint64_t> keys, val, tkey, tval, skey, sval;
+    dbuf<int32_t> parent, bdst;
+    dbuf<unsigned long long> cnt, n_groups;                     // cnt: merges of all rounds so far, records of the cluster graph
+    int64_t rounds = 0, total = 0, m = 0;                       // total, m: the two counters as last read back
+};
+// The rounds of a hierarchy on the edge graph (which they consume: the row offsets are rebuilt per contraction): find + match, one
+// read-back of two counters, contraction; f receives the merge records in merge order.  The Linkage supplies only what differs:
+//   name, contract_scope, count_bits, reduce_op    the name in notes and error texts, the profile scope of the contraction, the
+//                             count bits k_relabel puts below a value, the reduce-by-key operator on such values
+//   begin(st)                 its checks, its own arrays, and st.val: the values of the object graph's records
+//   find_and_match(st)        the round's two launches under its scope name -> bdst, parent[d] = c, its merge list, cnt[0]
+//   round_limit(n), idle_round(st)    more rounds are an internal error; after a round without merges, true for another round
+//   before_contraction(st, merges)    what the round's merges change beside the cluster graph
+//   compact(st)               the reduced groups (tkey, tval, n_groups) -> the surviving records in keys / val, the tail of the old
+//                             list filled with the sentinel, cnt[1] = the new length
+//   finish(st, f)             the merge records leave the device
+template <class Linkage>
+void agglomerate(int64_t n, edge_graph& eg, hipStream_t s, Linkage& lk, vg_forest& f) {
     const int64_t m0 = eg.m, mu = m0 / 2;
-    comp.alloc((size_t)n);
-    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, comp.p, n);
-    if (f) f->stats.n_edges = mu;
-    if (mu == 0) { VG_HIP(hipGetLastError()); return 0; }
-    dbuf<int64_t> pos; dbuf<uint64_t> rank;
-    rank_edges(eg, s, pos, rank);
-    int bits = 1; while ((1LL << bits) <= n) ++bits;            // cluster ids and the sentinel n: two of them are a sort key
-    const int64_t cap = std::min<int64_t>(mu, n - 1);
-    // the cluster graph (keys, rank, eg.off) starts as the object graph; t* / s* are the contraction's work arrays
-    dbuf<uint64_t> keys((size_t)m0), tkey((size_t)m0), tval((size_t)m0), skey((size_t)m0), sval((size_t)m0);
-    dbuf<int64_t> idx((size_t)m0), merged((size_t)cap);
-    dbuf<int32_t> parent((size_t)n), mult((size_t)n), bdst((size_t)n);
-    dbuf<unsigned long long> best((size_t)n), cnt(2), n_groups(1);     // cnt: merges of all rounds so far, records of the cluster graph
-    VG_HIP(hipMemcpyAsync(keys.p, eg.ukeys.p, (size_t)m0 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, parent.p, n);
+    f.stats.n_edges = mu;
+    if (mu == 0) return;
+    const std::string fn = std::string("vg_cluster_") + Linkage::name + "_linkage";
+    cluster_rounds st{ n, m0, std::min<int64_t>(mu, n - 1), id_bits(n), s, eg };     // two ids are a sort key of the contraction
+    lk.begin(st);
+    for (dbuf<uint64_t>* b : { &st.keys, &st.tkey, &st.tval, &st.skey, &st.sval }) b->alloc((size_t)m0);
+    st.parent.alloc((size_t)n); st.bdst.alloc((size_t)n); st.cnt.alloc(2); st.n_groups.alloc(1);
+    VG_HIP(hipMemcpyAsync(st.keys.p, eg.ukeys.p, (size_t)m0 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, st.parent.p, n);
     const unsigned long long cnt0[2] = { 0, (unsigned long long)m0 };
-    cnt.upload(cnt0, 2, s);
-    int64_t rounds = 0, total = 0, m = m0;
+    st.cnt.upload(cnt0, 2, s);
+    st.m = m0;
     char note[96];
     for (;;) {
-        {
-            vg_prof_scope ps("cluster_complete_best", (double)m * 16.0 + (double)n * 40.0);
-            hipLaunchKernelGGL(k_cl_find, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)eg.off.p, (const uint64_t*)keys.p,
-                               (const uint64_t*)rank.p, best.p, bdst.p, mult.p);
-            hipLaunchKernelGGL(k_cl_match, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const unsigned long long*)best.p, (const int32_t*)bdst.p,
-                               parent.p, mult.p, merged.p, cap, cnt.p);
-        }
-        ++rounds;
+        lk.find_and_match(st);
+        ++st.rounds;
         unsigned long long now[2] = { 0, 0 };                   // the one read-back of the round: both counters
-        cnt.download(now, 2, s);
+        st.cnt.download(now, 2, s);
         VG_HIP(hipStreamSynchronize(s));
-        const int64_t merges = (int64_t)now[0] - total;
-        total = (int64_t)now[0]; m = (int64_t)now[1];
-        if (total > cap || m < 0 || m > m0 || (m & 1)) throw vg_error(VG_EHIP, "vg_cluster_complete_linkage: the merges are no hierarchy (internal error)");
-        snprintf(note, sizeof note, "complete round %lld: %lld merges, %lld records", (long long)rounds, (long long)merges, (long long)m);
+        const int64_t merges = (int64_t)now[0] - st.total, m = (int64_t)now[1];
+        st.total = (int64_t)now[0]; st.m = m;
+        if (st.total > st.cap || m < 0 || m > m0 || (m & 1)) throw vg_error(VG_EHIP, fn + ": the merges are no hierarchy (internal error)");
+        snprintf(note, sizeof note, "%s round %lld: %lld merges, %lld records", Linkage::name, (long long)st.rounds, (long long)merges, (long long)m);
         vg_host_mark(note);
-        if (merges == 0) break;                                 // no finite K is left
-        if (rounds > n) throw vg_error(VG_EHIP, "vg_cluster_complete_linkage: the rounds do not end (internal error)");
-        vg_prof_scope ps("cluster_complete_contract", (double)m * (32.0 + 32.0 * 2.0 + 32.0 + 24.0) + (double)n * 16.0);
-        hipLaunchKernelGGL(k_bor_relabel, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)parent.p, comp.p);
-        hipLaunchKernelGGL(k_cl_relabel, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)keys.p, (const uint64_t*)rank.p, m,
-                           (const int32_t*)parent.p, n, bits, tkey.p, tval.p);
+        // (a round without merges cannot be what passes the limit: every round before it merged, and total <= cap < n)
+        if (st.rounds > lk.round_limit(n)) throw vg_error(VG_EHIP, fn + ": the rounds do not end (internal error)");
+        if (merges == 0) { if (lk.idle_round(st)) continue; break; }
+        vg_prof_scope ps(Linkage::contract_scope, (double)m * (32.0 + 32.0 * 2.0 + 32.0 + 24.0) + (double)n * 16.0);
+        lk.before_contraction(st, merges);
+        hipLaunchKernelGGL(k_relabel, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)st.keys.p, (const uint64_t*)st.val.p, m,
+                           (const int32_t*)st.parent.p, n, st.bits, Linkage::count_bits, st.tkey.p, st.tval.p);
         with_temp_storage([&](void* tmp, size_t& tb) {
-            return rocprim::radix_sort_pairs(tmp, tb, tkey.p, skey.p, tval.p, sval.p, (size_t)m, 0u, 2u * (unsigned)bits, s); });
-        with_temp_storage([&](void* tmp, size_t& tb) {           // -> (cluster pair, worst rank << 3 | records) in tkey / tval
-            return rocprim::reduce_by_key(tmp, tb, skey.p, sval.p, (size_t)m, tkey.p, tval.p, n_groups.p, max_rank_add_count(),
-                                          rocprim::equal_to<uint64_t>(), s); });
-        const surviving_pair alive{ tkey.p, tval.p, n_groups.p, mult.p, n, bits };
-        rocprim::counting_iterator<int64_t> iota(0);
-        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::select(tmp, tb, iota, idx.p, cnt.p + 1, (size_t)m, alive, s); });
-        hipLaunchKernelGGL(k_cl_compact, dim3(grid_of(m)), dim3(TPB), 0, s, (const int64_t*)idx.p, (const unsigned long long*)(cnt.p + 1), m,
-                           (const uint64_t*)tkey.p, (const uint64_t*)tval.p, n, bits, keys.p, rank.p);
-        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)keys.p, m, n, eg.off.p, eg.adj.p);
+            return rocprim::radix_sort_pairs(tmp, tb, st.tkey.p, st.skey.p, st.tval.p, st.sval.p, (size_t)m, 0u, 2u * (unsigned)st.bits, s); });
+        with_temp_storage([&](void* tmp, size_t& tb) {           // -> (cluster pair, reduced value) in tkey / tval
+            return rocprim::reduce_by_key(tmp, tb, st.skey.p, st.sval.p, (size_t)m, st.tkey.p, st.tval.p, st.n_groups.p,
+                                          typename Linkage::reduce_op(), rocprim::equal_to<uint64_t>(), s); });
+        lk.compact(st);
+        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)st.keys.p, m, n, eg.off.p, eg.adj.p);
     }
     VG_HIP(hipGetLastError());
-    if (f) {
-        f->stats.rounds = rounds;
-        if (total > 0) {                                        // the merge ranks, ascending = merge order
-            vg_prof_scope ps("cluster_forest", (double)total * 16.0 + (double)n * 40.0);
-            dbuf<int64_t> frank((size_t)total);
-            with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_keys(tmp, tb, merged.p, frank.p, (size_t)total, 0u, 64u, s); });
-            download_forest(frank, total, pos, eg, s, *f);
-        }
+    f.stats.rounds = st.rounds;
+    lk.finish(st, f);
+}
+
+// Complete linkage: the values are the ranks of rank_edges.  comp[i] = the cluster of object i after every merge (its minimum
+// member); the merge records, if wanted, are the merge ranks sorted on the device and fetched the forest's way.
+struct complete_linkage {
+    static constexpr const char *name = "complete", *contract_scope = "cluster_complete_contract";
+    static constexpr int count_bits = COUNT_BITS; using reduce_op = max_rank_add_count;
+    dbuf<int32_t>& comp; const bool want_records;
+    dbuf<int64_t> pos, idx, merged; dbuf<int32_t> mult; dbuf<unsigned long long> best;
+    void begin(cluster_rounds& st) {
+        rank_edges(st.eg, st.s, pos, st.val);
+        idx.alloc((size_t)st.m0); merged.alloc((size_t)st.cap); mult.alloc((size_t)st.n); best.alloc((size_t)st.n);
     }
-    return rounds;
+    void find_and_match(cluster_rounds& st) {
+        vg_prof_scope ps("cluster_complete_best", (double)st.m * 16.0 + (double)st.n * 40.0);
+        hipLaunchKernelGGL(k_cl_find, dim3(grid_of(st.n * ROW_LANES)), dim3(TPB), 0, st.s, st.n, (const int64_t*)st.eg.off.p, (const uint64_t*)st.keys.p,
+                           (const uint64_t*)st.val.p, best.p, st.bdst.p, mult.p);
+        hipLaunchKernelGGL(k_cl_match, dim3(grid_of(st.n)), dim3(TPB), 0, st.s, st.n, (const unsigned long long*)best.p, (const int32_t*)st.bdst.p,
+                           st.parent.p, mult.p, merged.p, st.cap, st.cnt.p);
+    }
+    int64_t round_limit(int64_t n) const { return n; }
+    bool idle_round(const cluster_rounds&) { return false; }    // no finite K is left
+    void before_contraction(cluster_rounds& st, int64_t) {
+        hipLaunchKernelGGL(k_bor_relabel, dim3(grid_of(st.n)), dim3(TPB), 0, st.s, st.n, (const int32_t*)st.parent.p, comp.p);
+    }
+    void compact(cluster_rounds& st) {                          // (cluster pair, worst rank << 3 | records): select the full pairs
+        const surviving_pair alive{ st.tkey.p, st.tval.p, st.n_groups.p, mult.p, st.n, st.bits };
+        rocprim::counting_iterator<int64_t> iota(0);
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::select(tmp, tb, iota, idx.p, st.cnt.p + 1, (size_t)st.m, alive, st.s); });
+        hipLaunchKernelGGL(k_cl_compact, dim3(grid_of(st.m)), dim3(TPB), 0, st.s, (const int64_t*)idx.p, (const unsigned long long*)(st.cnt.p + 1), st.m,
+                           (const uint64_t*)st.tkey.p, (const uint64_t*)st.tval.p, st.n, st.bits, st.keys.p, st.val.p);
+    }
+    void finish(cluster_rounds& st, vg_forest& f) {             // the merge ranks, ascending = merge order
+        if (!want_records || st.total == 0) return;
+        vg_prof_scope ps("cluster_forest", (double)st.total * 16.0 + (double)st.n * 40.0);
+        dbuf<int64_t> frank((size_t)st.total);
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_keys(tmp, tb, merged.p, frank.p, (size_t)st.total, 0u, 64u, st.s); });
+        download_forest(frank, st.total, pos, st.eg, st.s, f);
+    }
+};
+void complete_on_device(int64_t n, edge_graph& eg, hipStream_t s, dbuf<int32_t>& comp, bool want_records, vg_forest& f) {
+    comp.alloc((size_t)n);
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, comp.p, n);
+    VG_HIP(hipGetLastError());
+    complete_linkage lk{ comp, want_records };
+    agglomerate(n, eg, s, lk, f);
 }
 
 // the level t as a count of quanta: sim >= t is S >= T * P.  Below 0 every merge passes, above 1 none does (sim <= 1).
@@ -833,89 +874,165 @@ double av_similarity(uint64_t S, uint64_t P) {
     return ldexp((double)quot, zp - zs - 62 - 32);
 }
 
-// Average linkage on the edge graph (which it consumes: the row offsets are rebuilt per contraction); f receives the merge records
-// in merge order with their exact (S, P).  Rounds: find + match, one read-back of two counters, contraction.  With floor 0 a record
-// of S == 0 may merge too, but a cluster pair WITHOUT a record has the same similarity 0 and becomes a candidate when a merge gives
-// it a record: among such ties the parallel rounds are not the sequential rule.  So records of S == 0 wait until a round finds no
-// other merge (then every record left has S == 0) and merge one per round from there, the smallest (c, d) first -- the sequential
-// rule itself, whose order the host keeps for those records instead of sorting them.
-void average_on_device(int64_t n, edge_graph& eg, double floor, hipStream_t s, vg_forest& f) {
-    const int64_t m0 = eg.m, mu = m0 / 2;
-    f.stats.n_edges = mu;
-    if (mu == 0) return;
-    if (mu >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "vg_cluster_average_linkage: 2^32 or more edges (a sum of weights must fit 64 bits)");
-    const uint64_t F = av_quanta(floor);
-    int bits = 1; while ((1LL << bits) <= n) ++bits;            // cluster ids and the sentinel n: two of them are a sort key
-    const int64_t cap = std::min<int64_t>(mu, n - 1);
-    // the cluster graph (keys, sum, eg.off) starts as the object graph; t* / s* are the contraction's work arrays
-    dbuf<uint64_t> keys((size_t)m0), sum((size_t)m0), tkey((size_t)m0), tval((size_t)m0), skey((size_t)m0), sval((size_t)m0);
-    dbuf<uint64_t> msum((size_t)cap), mpairs((size_t)cap);
-    dbuf<int32_t> mc((size_t)cap), md((size_t)cap), parent((size_t)n), size((size_t)n), bdst((size_t)n);
-    dbuf<unsigned long long> bsum((size_t)n), cnt(2), n_groups(1);     // cnt: merges of all rounds so far, records of the cluster graph
-    VG_HIP(hipMemcpyAsync(keys.p, eg.ukeys.p, (size_t)m0 * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(m0)), dim3(TPB), 0, s, (const double*)eg.uvals.p, m0, sum.p);
-    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, parent.p, n);
-    hipLaunchKernelGGL(k_fill, dim3(grid_of(n)), dim3(TPB), 0, s, size.p, n, 1);
-    const unsigned long long cnt0[2] = { 0, (unsigned long long)m0 };
-    cnt.upload(cnt0, 2, s);
-    int64_t rounds = 0, total = 0, m = m0, in_key_order = -1;  // in_key_order: the merges before the zero phase (-1: it never began)
-    char note[96];
-    for (;;) {
-        {
-            vg_prof_scope ps("cluster_average_best", (double)m * 20.0 + (double)n * 40.0);
-            hipLaunchKernelGGL(k_av_find, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)eg.off.p, (const uint64_t*)keys.p,
-                               (const uint64_t*)sum.p, (const int32_t*)size.p, bsum.p, bdst.p);
-            hipLaunchKernelGGL(k_av_match, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const unsigned long long*)bsum.p, (const int32_t*)bdst.p,
-                               (const int32_t*)size.p, F, in_key_order >= 0 ? 1 : 0, (const uint64_t*)keys.p, parent.p, msum.p, mpairs.p, mc.p,
-                               md.p, cap, cnt.p);
-        }
-        ++rounds;
-        unsigned long long now[2] = { 0, 0 };                   // the one read-back of the round: both counters
-        cnt.download(now, 2, s);
-        VG_HIP(hipStreamSynchronize(s));
-        const int64_t merges = (int64_t)now[0] - total;
-        total = (int64_t)now[0]; m = (int64_t)now[1];
-        if (total > cap || m < 0 || m > m0 || (m & 1)) throw vg_error(VG_EHIP, "vg_cluster_average_linkage: the merges are no hierarchy (internal error)");
-        snprintf(note, sizeof note, "average round %lld: %lld merges, %lld records", (long long)rounds, (long long)merges, (long long)m);
-        vg_host_mark(note);
-        if (rounds > 2 * n + 2) throw vg_error(VG_EHIP, "vg_cluster_average_linkage: the rounds do not end (internal error)");
-        if (merges == 0) {
-            if (F == 0 && m > 0 && in_key_order < 0) { in_key_order = total; continue; }     // only records of S == 0 are left
-            break;
-        }
-        vg_prof_scope ps("cluster_average_contract", (double)m * (32.0 + 32.0 * 2.0 + 32.0 + 24.0) + (double)n * 16.0);
-        hipLaunchKernelGGL(k_av_grow, dim3(grid_of(merges)), dim3(TPB), 0, s, (const int32_t*)mc.p, (const int32_t*)md.p, total - merges, total, size.p);
-        hipLaunchKernelGGL(k_av_relabel, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)keys.p, (const uint64_t*)sum.p, m,
-                           (const int32_t*)parent.p, n, bits, tkey.p, tval.p);
-        with_temp_storage([&](void* tmp, size_t& tb) {
-            return rocprim::radix_sort_pairs(tmp, tb, tkey.p, skey.p, tval.p, sval.p, (size_t)m, 0u, 2u * (unsigned)bits, s); });
-        with_temp_storage([&](void* tmp, size_t& tb) {           // -> (cluster pair, sum) in tkey / tval
-            return rocprim::reduce_by_key(tmp, tb, skey.p, sval.p, (size_t)m, tkey.p, tval.p, n_groups.p, rocprim::plus<uint64_t>(),
-                                          rocprim::equal_to<uint64_t>(), s); });
-        hipLaunchKernelGGL(k_av_compact, dim3(grid_of(m)), dim3(TPB), 0, s, (const unsigned long long*)n_groups.p, m, (const uint64_t*)tkey.p,
-                           (const uint64_t*)tval.p, n, bits, keys.p, sum.p, cnt.p + 1);
-        hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)keys.p, m, n, eg.off.p, eg.adj.p);
+// Average linkage: the values are the 64-bit sums; the merge records (c, d, S, P) leave the device and are sorted on the host.  With
+// floor 0 a record of S == 0 may merge too, but a cluster pair WITHOUT a record has the same similarity 0 and becomes a candidate
+// when a merge gives it a record: among such ties the parallel rounds are not the sequential rule.  So records of S == 0 wait until
+// a round finds no other merge (then every record left has S == 0) and merge one per round from there, the smallest (c, d) first --
+// the sequential rule itself, whose order the host keeps for those records instead of sorting them.
+struct average_linkage {
+    static constexpr const char *name = "average", *contract_scope = "cluster_average_contract";
+    static constexpr int count_bits = 0; using reduce_op = rocprim::plus<uint64_t>;
+    const uint64_t F;                                           // the floor in quanta
+    dbuf<uint64_t> msum, mpairs; dbuf<int32_t> mc, md, size; dbuf<unsigned long long> bsum;
+    int64_t in_key_order = -1;                                  // the merges before the zero phase (-1: it never began)
+    void begin(cluster_rounds& st) {
+        if (st.m0 / 2 >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "vg_cluster_average_linkage: 2^32 or more edges (a sum of weights must fit 64 bits)");
+        st.val.alloc((size_t)st.m0); msum.alloc((size_t)st.cap); mpairs.alloc((size_t)st.cap); mc.alloc((size_t)st.cap); md.alloc((size_t)st.cap);
+        size.alloc((size_t)st.n); bsum.alloc((size_t)st.n);
+        hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(st.m0)), dim3(TPB), 0, st.s, (const double*)st.eg.uvals.p, st.m0, st.val.p);
+        hipLaunchKernelGGL(k_fill, dim3(grid_of(st.n)), dim3(TPB), 0, st.s, size.p, st.n, 1);
     }
-    VG_HIP(hipGetLastError());
-    f.stats.rounds = rounds;
-    f.stats.n_merges = total;
-    if (total == 0) return;
+    void find_and_match(cluster_rounds& st) {
+        vg_prof_scope ps("cluster_average_best", (double)st.m * 20.0 + (double)st.n * 40.0);
+        hipLaunchKernelGGL(k_av_find, dim3(grid_of(st.n * ROW_LANES)), dim3(TPB), 0, st.s, st.n, (const int64_t*)st.eg.off.p, (const uint64_t*)st.keys.p,
+                           (const uint64_t*)st.val.p, (const int32_t*)size.p, bsum.p, st.bdst.p);
+        hipLaunchKernelGGL(k_av_match, dim3(grid_of(st.n)), dim3(TPB), 0, st.s, st.n, (const unsigned long long*)bsum.p, (const int32_t*)st.bdst.p,
+                           (const int32_t*)size.p, F, in_key_order >= 0 ? 1 : 0, (const uint64_t*)st.keys.p, st.parent.p, msum.p, mpairs.p, mc.p,
+                           md.p, st.cap, st.cnt.p);
+    }
+    int64_t round_limit(int64_t n) const { return 2 * n + 2; }    // (n - 1 merging rounds and two that find nothing, with room)
+    bool idle_round(const cluster_rounds& st) {                 // only records of S == 0 are left: the zero phase begins, once
+        if (!(F == 0 && st.m > 0 && in_key_order < 0)) return false;
+        in_key_order = st.total;
+        return true;
+    }
+    void before_contraction(cluster_rounds& st, int64_t merges) {
+        hipLaunchKernelGGL(k_av_grow, dim3(grid_of(merges)), dim3(TPB), 0, st.s, (const int32_t*)mc.p, (const int32_t*)md.p, st.total - merges, st.total, size.p);
+    }
+    void compact(cluster_rounds& st) {                          // (cluster pair, sum): every group but the sentinel's, no select pass
+        hipLaunchKernelGGL(k_av_compact, dim3(grid_of(st.m)), dim3(TPB), 0, st.s, (const unsigned long long*)st.n_groups.p, st.m, (const uint64_t*)st.tkey.p,
+                           (const uint64_t*)st.tval.p, st.n, st.bits, st.keys.p, st.val.p, st.cnt.p + 1);
+    }
     // the <= n - 1 merge records leave the device; their order is the key order (keys are distinct: d disappears when absorbed)
-    std::vector<uint64_t> hs((size_t)total), hp((size_t)total); std::vector<int32_t> hc((size_t)total), hd((size_t)total);
-    msum.download(hs.data(), (size_t)total, s); mpairs.download(hp.data(), (size_t)total, s);
-    mc.download(hc.data(), (size_t)total, s); md.download(hd.data(), (size_t)total, s);
-    VG_HIP(hipStreamSynchronize(s));
-    std::vector<int64_t> order((size_t)total);
-    for (int64_t k = 0; k < total; ++k) order[(size_t)k] = k;
-    std::stable_sort(order.begin(), order.begin() + (in_key_order >= 0 ? in_key_order : total), [&](int64_t x, int64_t y) {
-        return av_compare(av_cand{ hs[(size_t)x], hp[(size_t)x], (uint32_t)hc[(size_t)x], (uint32_t)hd[(size_t)x] },
-                          av_cand{ hs[(size_t)y], hp[(size_t)y], (uint32_t)hc[(size_t)y], (uint32_t)hd[(size_t)y] }) < 0; });
-    f.a.resize((size_t)total); f.b.resize((size_t)total); f.w.resize((size_t)total); f.sum.resize((size_t)total); f.pairs.resize((size_t)total);
-    for (int64_t k = 0; k < total; ++k) {
-        const size_t j = (size_t)order[(size_t)k];
-        f.a[(size_t)k] = hc[j]; f.b[(size_t)k] = hd[j]; f.sum[(size_t)k] = hs[j]; f.pairs[(size_t)k] = hp[j];
-        f.w[(size_t)k] = av_similarity(hs[j], hp[j]);
+    void finish(cluster_rounds& st, vg_forest& f) {
+        const int64_t total = st.total;
+        f.stats.n_merges = total;
+        if (total == 0) return;
+        std::vector<uint64_t> hs((size_t)total), hp((size_t)total); std::vector<int32_t> hc((size_t)total), hd((size_t)total);
+        msum.download(hs.data(), (size_t)total, st.s); mpairs.download(hp.data(), (size_t)total, st.s);
+        mc.download(hc.data(), (size_t)total, st.s); md.download(hd.data(), (size_t)total, st.s);
+        VG_HIP(hipStreamSynchronize(st.s));
+        std::vector<int64_t> order((size_t)total);
+        for (int64_t k = 0; k < total; ++k) order[(size_t)k] = k;
+        std::stable_sort(order.begin(), order.begin() + (in_key_order >= 0 ? in_key_order : total), [&](int64_t x, int64_t y) {
+            return av_compare(av_cand{ hs[(size_t)x], hp[(size_t)x], (uint32_t)hc[(size_t)x], (uint32_t)hd[(size_t)x] },
+                              av_cand{ hs[(size_t)y], hp[(size_t)y], (uint32_t)hc[(size_t)y], (uint32_t)hd[(size_t)y] }) < 0; });
+        f.a.resize((size_t)total); f.b.resize((size_t)total); f.w.resize((size_t)total); f.sum.resize((size_t)total); f.pairs.resize((size_t)total);
+        for (int64_t k = 0; k < total; ++k) {
+            const size_t j = (size_t)order[(size_t)k];
+            f.a[(size_t)k] = hc[j]; f.b[(size_t)k] = hd[j]; f.sum[(size_t)k] = hs[j]; f.pairs[(size_t)k] = hp[j];
+            f.w[(size_t)k] = av_similarity(hs[j], hp[j]);
+        }
     }
+};
+void average_on_device(int64_t n, edge_graph& eg, double floor, hipStream_t s, vg_forest& f) {
+    average_linkage lk{ av_quanta(floor) };
+    agglomerate(n, eg, s, lk, f);
+}
+
+// ---------------------------------------------------------------- the algorithms of vg_cluster_graph: root[i] = the cluster id of i
+// hook + compress, one launch each per round; the changed word is read back every 4 rounds (of the last)
+void single_on_device(int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n);
+    dbuf<int32_t> changed(1);
+    for (;;) {
+        for (int k = 0; k < 4; ++k) {
+            if (k == 3) changed.zero(s);
+            { vg_prof_scope ps("cluster_hook", (double)eg.m * 8.0); hipLaunchKernelGGL(k_hook, dim3(grid_of(eg.m)), dim3(TPB), 0, s, (const uint64_t*)eg.ukeys.p, eg.m, root.p, changed.p); }
+            { vg_prof_scope ps("cluster_compress", (double)n * 8.0); hipLaunchKernelGGL(k_compress, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n); }
+            ++sts.rounds;
+        }
+        int32_t c = 0;
+        changed.download(&c, 1, s);
+        VG_HIP(hipStreamSynchronize(s));
+        if (!c) break;
+    }
+}
+// f(std::true_type) for uclust, f(std::false_type) for cd-hit: a launch of either instantiation is written once
+template <class F> void with_uclust(bool uclust, F f) { if (uclust) f(std::true_type{}); else f(std::false_type{}); }
+// cd-hit, uclust and set cover: rounds that decide objects (round(counter) launches one, counting its decisions) until none is
+// left; a round of low progress hands the rest to the one-workgroup sweep()
+template <class Round, class Sweep>
+void decide_in_rounds(int64_t n, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts, Round round, Sweep sweep) {
+    dbuf<unsigned long long> d_dec(1);
+    VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
+    for (int64_t left = n; left > 0;) {
+        d_dec.zero(s);
+        round(d_dec.p);
+        ++sts.rounds;
+        const int64_t dec = read_counter(d_dec, s);
+        left -= dec;
+        if (left > 0 && low_progress(dec, left + dec)) { sweep(); sts.sweep_objects = left; left = 0; }
+    }
+}
+void greedy_on_device(bool uclust, int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
+    const int64_t* off = eg.off.p; const int32_t* adj = eg.adj.p; const double* wts = eg.uvals.p;
+    decide_in_rounds(n, s, root, sts, [&](unsigned long long* decided) {
+        vg_prof_scope ps(uclust ? "cluster_uclust_round" : "cluster_cdhit_round", (double)eg.m * 12.0 + (double)n * 12.0);
+        with_uclust(uclust, [&](auto uc) {
+            hipLaunchKernelGGL(k_greedy_round<decltype(uc)::value>, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, wts, root.p, decided); });
+    }, [&] {
+        // every object before the first undecided one is decided: the sweep may start at the lowest undecided index,
+        // which the host does not know -- it starts at 0 and skips decided chunks 256 at a time
+        vg_prof_scope ps(uclust ? "cluster_uclust_sweep" : "cluster_cdhit_sweep", (double)eg.m * 12.0);
+        with_uclust(uclust, [&](auto uc) {
+            hipLaunchKernelGGL(k_greedy_sweep<decltype(uc)::value>, dim3(1), dim3(SWEEP_TPB), 0, s, n, off, adj, wts, root.p, (int64_t)0); });
+    });
+}
+void set_cover_on_device(int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
+    const int64_t* off = eg.off.p; const int32_t* adj = eg.adj.p;
+    dbuf<uint64_t> key((size_t)n), m1((size_t)n);
+    decide_in_rounds(n, s, root, sts, [&](unsigned long long* decided) {
+        vg_prof_scope ps("cluster_setcover_round", (double)eg.m * 4.0 * 12.0);
+        hipLaunchKernelGGL(k_sc_key, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, (const int32_t*)root.p, key.p);
+        hipLaunchKernelGGL(k_sc_max, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, (const uint64_t*)key.p, m1.p);
+        hipLaunchKernelGGL(k_sc_pick, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, (const uint64_t*)key.p, (const uint64_t*)m1.p, root.p, decided);
+        hipLaunchKernelGGL(k_sc_claim, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, root.p, decided);
+    }, [&] {
+        const int64_t nb = (n + SC_BLK - 1) / SC_BLK;
+        dbuf<uint64_t> bmax((size_t)nb); dbuf<int32_t> dirty((size_t)nb);
+        dirty.zero(s);
+        vg_prof_scope ps("cluster_setcover_sweep", (double)eg.m * 12.0);
+        hipLaunchKernelGGL(k_sc_key, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, (const int32_t*)root.p, key.p);
+        hipLaunchKernelGGL(k_sc_block_max, dim3((unsigned)nb), dim3(SC_TPB), 0, s, n, (const uint64_t*)key.p, bmax.p);
+        hipLaunchKernelGGL(k_sc_sweep, dim3(1), dim3(SC_TPB), 0, s, n, nb, off, adj, root.p, key.p, bmax.p, dirty.p);
+    });
+}
+void check_roots(int64_t n, const dbuf<int32_t>& root, hipStream_t s) {
+    dbuf<int32_t> bad(1); bad.zero(s);
+    hipLaunchKernelGGL(k_check_roots, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, n, bad.p);
+    int32_t b = 0; bad.download(&b, 1, s);
+    VG_HIP(hipStreamSynchronize(s));
+    if (b) throw vg_error(VG_EHIP, "vg_cluster_graph: an object was left without a cluster (internal error)");
+}
+// labels: cluster id -> earliest member -> numbering.  by_min_member: a cluster id need not be its cluster's earliest member (a
+// set-cover pick; the other algorithms' ids are)
+void labels_on_device(int64_t n, const dbuf<int32_t>& root, bool by_min_member, hipStream_t s, dbuf<int32_t>& label, dbuf<int32_t>& rep) {
+    dbuf<int32_t> size((size_t)n), fm((size_t)n), fs((size_t)n), sm((size_t)n), ss((size_t)n), lab((size_t)n);
+    dbuf<int32_t>& minm = label;                                // (the earliest members, then the labels)
+    minm.alloc((size_t)n); rep.alloc((size_t)n);
+    vg_prof_scope ps("cluster_labels", (double)n * 4.0 * 14.0);
+    size.zero(s);
+    if (by_min_member) {
+        hipLaunchKernelGGL(k_fill, dim3(grid_of(n)), dim3(TPB), 0, s, minm.p, n, INT32_MAX);
+        hipLaunchKernelGGL(k_min_member, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, n, minm.p);
+    } else hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, minm.p, n);
+    hipLaunchKernelGGL(k_rep_size, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)minm.p, n, rep.p, size.p);
+    hipLaunchKernelGGL(k_flags, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)size.p, n, fm.p, fs.p);
+    exclusive_scan_i32(fm.p, sm.p, n, s);
+    exclusive_scan_i32(fs.p, ss.p, n, s);
+    hipLaunchKernelGGL(k_head_labels, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)fm.p, (const int32_t*)fs.p, (const int32_t*)sm.p, (const int32_t*)ss.p, n, lab.p);
+    hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)lab.p, n, minm.p);
 }
 }  // namespace
 
@@ -934,110 +1051,21 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
     const int64_t n = n_objects;
     edge_graph eg;
     build_edge_graph(n, q, r, w, n_rows, s, eg);
-    const int64_t m = eg.m;
-    dbuf<uint64_t>& ukeys = eg.ukeys; dbuf<double>& uvals = eg.uvals; dbuf<int64_t>& off = eg.off; dbuf<int32_t>& adj = eg.adj;
-    sts.n_edges = m / 2;
+    sts.n_edges = eg.m / 2;
     dbuf<int32_t> root((size_t)n);
-    dbuf<unsigned long long> d_dec(1);
-
-    if (algorithm == VG_CLUSTER_SINGLE) {
-        hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n);
-        dbuf<int32_t> changed(1);
-        for (;;) {
-            for (int k = 0; k < 4; ++k) {                         // the changed word is read back every 4 rounds (of the last)
-                if (k == 3) changed.zero(s);
-                { vg_prof_scope ps("cluster_hook", (double)m * 8.0); hipLaunchKernelGGL(k_hook, dim3(grid_of(m)), dim3(TPB), 0, s, (const uint64_t*)ukeys.p, m, root.p, changed.p); }
-                { vg_prof_scope ps("cluster_compress", (double)n * 8.0); hipLaunchKernelGGL(k_compress, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n); }
-                ++sts.rounds;
-            }
-            int32_t c = 0;
-            changed.download(&c, 1, s);
-            VG_HIP(hipStreamSynchronize(s));
-            if (!c) break;
-        }
-    } else if (algorithm == VG_CLUSTER_COMPLETE) {              // the floor cut of the complete-linkage hierarchy: every merge
-        sts.rounds = complete_on_device(n, eg, s, root, nullptr);
-    } else if (algorithm == VG_CLUSTER_CDHIT || algorithm == VG_CLUSTER_UCLUST) {
-        const bool uc = algorithm == VG_CLUSTER_UCLUST;
-        VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
-        int64_t left = n;
-        while (left > 0) {
-            d_dec.zero(s);
-            {
-                vg_prof_scope ps(uc ? "cluster_uclust_round" : "cluster_cdhit_round", (double)m * 12.0 + (double)n * 12.0);
-                if (uc) hipLaunchKernelGGL(k_greedy_round<true>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, d_dec.p);
-                else hipLaunchKernelGGL(k_greedy_round<false>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, d_dec.p);
-            }
-            ++sts.rounds;
-            const int64_t dec = read_counter(d_dec, s);
-            left -= dec;
-            if (left > 0 && low_progress(dec, left + dec)) {
-                // every object before the first undecided one is decided: the sweep may start at the lowest undecided index,
-                // which the host does not know -- it starts at 0 and skips decided chunks 256 at a time
-                vg_prof_scope ps(uc ? "cluster_uclust_sweep" : "cluster_cdhit_sweep", (double)m * 12.0);
-                if (uc) hipLaunchKernelGGL(k_greedy_sweep<true>, dim3(1), dim3(SWEEP_TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, (int64_t)0);
-                else hipLaunchKernelGGL(k_greedy_sweep<false>, dim3(1), dim3(SWEEP_TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const double*)uvals.p, root.p, (int64_t)0);
-                sts.sweep_objects = left;
-                left = 0;
-            }
-        }
-    } else {
-        VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
-        dbuf<uint64_t> key((size_t)n), m1((size_t)n);
-        int64_t left = n;
-        while (left > 0) {
-            d_dec.zero(s);
-            {
-                vg_prof_scope ps("cluster_setcover_round", (double)m * 4.0 * 12.0);
-                hipLaunchKernelGGL(k_sc_key, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const int32_t*)root.p, key.p);
-                hipLaunchKernelGGL(k_sc_max, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const uint64_t*)key.p, m1.p);
-                hipLaunchKernelGGL(k_sc_pick, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const uint64_t*)key.p, (const uint64_t*)m1.p, root.p, d_dec.p);
-                hipLaunchKernelGGL(k_sc_claim, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, root.p, d_dec.p);
-            }
-            ++sts.rounds;
-            const int64_t dec = read_counter(d_dec, s);
-            left -= dec;
-            if (left > 0 && low_progress(dec, left + dec)) {
-                const int64_t nb = (n + SC_BLK - 1) / SC_BLK;
-                dbuf<uint64_t> bmax((size_t)nb); dbuf<int32_t> dirty((size_t)nb);
-                dirty.zero(s);
-                vg_prof_scope ps("cluster_setcover_sweep", (double)m * 12.0);
-                hipLaunchKernelGGL(k_sc_key, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)off.p, (const int32_t*)adj.p, (const int32_t*)root.p, key.p);
-                hipLaunchKernelGGL(k_sc_block_max, dim3((unsigned)nb), dim3(SC_TPB), 0, s, n, (const uint64_t*)key.p, bmax.p);
-                hipLaunchKernelGGL(k_sc_sweep, dim3(1), dim3(SC_TPB), 0, s, n, nb, (const int64_t*)off.p, (const int32_t*)adj.p, root.p, key.p, bmax.p, dirty.p);
-                sts.sweep_objects = left;
-                left = 0;
-            }
-        }
+    switch (algorithm) {
+        case VG_CLUSTER_SINGLE: single_on_device(n, eg, s, root, sts); break;
+        case VG_CLUSTER_COMPLETE: { vg_forest f; complete_on_device(n, eg, s, root, false, f); sts.rounds = f.stats.rounds; } break;    // the floor cut: every merge
+        case VG_CLUSTER_SET_COVER: set_cover_on_device(n, eg, s, root, sts); break;
+        default: greedy_on_device(algorithm == VG_CLUSTER_UCLUST, n, eg, s, root, sts);
     }
     VG_HIP(hipGetLastError());
-    {
-        dbuf<int32_t> bad(1); bad.zero(s);
-        hipLaunchKernelGGL(k_check_roots, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, n, bad.p);
-        int32_t b = 0; bad.download(&b, 1, s);
-        VG_HIP(hipStreamSynchronize(s));
-        if (b) throw vg_error(VG_EHIP, "vg_cluster_graph: an object was left without a cluster (internal error)");
-    }
-
-    // ---- labels: cluster id -> earliest member -> numbering
-    dbuf<int32_t> minm((size_t)n), rep((size_t)n), size((size_t)n), fm((size_t)n), fs((size_t)n), sm((size_t)n), ss((size_t)n), lab((size_t)n);
-    {
-        vg_prof_scope ps("cluster_labels", (double)n * 4.0 * 14.0);
-        size.zero(s);
-        if (algorithm == VG_CLUSTER_SET_COVER) {       // (a pick need not be its cluster's earliest member; the other ids are)
-            hipLaunchKernelGGL(k_fill, dim3(grid_of(n)), dim3(TPB), 0, s, minm.p, n, INT32_MAX);
-            hipLaunchKernelGGL(k_min_member, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, n, minm.p);
-        } else hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, minm.p, n);
-        hipLaunchKernelGGL(k_rep_size, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)minm.p, n, rep.p, size.p);
-        hipLaunchKernelGGL(k_flags, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)size.p, n, fm.p, fs.p);
-        exclusive_scan_i32(fm.p, sm.p, n, s);
-        exclusive_scan_i32(fs.p, ss.p, n, s);
-        hipLaunchKernelGGL(k_head_labels, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)fm.p, (const int32_t*)fs.p, (const int32_t*)sm.p, (const int32_t*)ss.p, n, lab.p);
-        hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)lab.p, n, minm.p);
-    }
+    check_roots(n, root, s);
+    dbuf<int32_t> d_label, d_rep;
+    labels_on_device(n, root, algorithm == VG_CLUSTER_SET_COVER, s, d_label, d_rep);
     VG_HIP(hipGetLastError());
-    minm.download(label, (size_t)n, s);
-    rep.download(representative, (size_t)n, s);
+    d_label.download(label, (size_t)n, s);
+    d_rep.download(representative, (size_t)n, s);
     VG_HIP(hipStreamSynchronize(s));
     VG_API_END
 }
@@ -1059,7 +1087,7 @@ void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, con
     build_edge_graph(n_objects, q, r, w, n_rows, s, eg);
     if (algorithm == VG_CLUSTER_AVERAGE) { average_on_device(n_objects, eg, floor, s, f); return; }
     dbuf<int32_t> comp;
-    complete_on_device(n_objects, eg, s, comp, &f);
+    complete_on_device(n_objects, eg, s, comp, true, f);
 }
 
 namespace {
