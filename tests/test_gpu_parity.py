@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import lz_checks as lc
 import oracle_lib as orc
 from vclust_amd import api, synth
 
@@ -273,6 +274,44 @@ def test_index_budget_batches_do_not_change_results():
     assert sorted(map(key, regions)) == sorted(map(key, ref_regions))
 
 
+@pytest.mark.parametrize('families,batches', [(16, 1), (20, 2)])
+def test_index_budget_batches_with_every_regions_path(tmp_path, families, batches):
+    """Several batches crossed with each --out-aln path: under the 64 MiB budget, a child process each (developer switches
+    are read once) for the one-parse path, a first arena far too small (every batch repeats itself), the two-pass checker
+    (its arena and offsets in a later batch) and the general kernel.  Rows equal those of a child with the default budget,
+    regions equal them as sorted tuples, and the four budgeted children return the same region array.  16 families are the
+    set of the budget test above: 160 references x 415.6 kB (lz_ref_need) = 63.4 MiB, ONE batch under that budget; 20
+    families (79 MiB) are what it cuts in two."""
+    codes, offsets, names = synth.make_families(families, 10, length=40000, seed=9)
+    n_rr = 2 * np.diff(offsets) + 1
+    need = int((((n_rr + 128 + 31) // 32 + 2) * 12 + (4 ** 7 + n_rr) * 4).sum())         # lz_ref_need restated, every genome a reference
+    budget = (64 << 20) + 1
+    assert (batches - 1) * budget < need <= batches * budget and (batches == 1 or need < 1.5 * budget)
+    gs = api.GenomeSet.from_codes(codes, offsets, names)
+    tasks = gs.align_tasks(synth.family_pairs(families, 10))
+    from vclust_amd import _lib
+    _lib.load().vg_set_index_budget(budget)                  # what the library itself plans: one index build per batch
+    api.profile_enable(True); api.profile_reset()
+    try:
+        gs.lz_align(tasks)
+        builds = {e['name']: e['launches'] for e in api.profile_get()}.get('lz_build_index')
+    finally:
+        api.profile_enable(False)
+        _lib.load().vg_set_index_budget(24 << 30)
+    assert builds == batches
+    base = lc.run_child(tmp_path, 'base', codes, offsets, tasks)
+    key = lambda r: tuple(int(x) for x in r)
+    base_regions = sorted(map(key, base['regions']))
+    assert len(base_regions) == int(base['stats']['n_regions'].sum()) > 0
+    out = {name: lc.run_child(tmp_path, name, codes, offsets, tasks, env=env, budget=budget)
+           for name, env in (('one_parse', {}), ('tiny_arena', dict(VG_LZ_ARENA='64')), ('two_pass', dict(VG_LZ_REGIONS='two-pass')),
+                             ('general', dict(VG_LZ_KERNEL='general')))}
+    for name, o in out.items():
+        assert np.array_equal(o['stats'], base['stats']), name
+        assert sorted(map(key, o['regions'])) == base_regions, name
+        assert np.array_equal(o['regions'], out['one_parse']['regions']), name
+
+
 @pytest.mark.parametrize('mode', ['malloc'])
 def test_allocator_cycles_1_to_64_gib(mode):
     """The device allocator (hipMalloc blocks): three rounds of 1 + 4 + 17 + 64 GiB blocks -- a size that is not a
@@ -324,6 +363,33 @@ def test_prepared_indexes_do_not_change_the_rows():
     del gs                                                      # a pending plan goes with its set
     gs2 = api.GenomeSet.from_codes(codes, offsets, names)
     assert np.array_equal(gs2.lz_align(tasks), ref)
+
+
+def test_plan_survives_calls_with_different_task_lists():
+    """The plan of a call is kept (host side) for the next call on the same references and depends on the references only:
+    calls with different task lists over the same references, with and without regions and after vg_lz_prepare, return the
+    rows of the first call, and the regions of a fresh set."""
+    codes, offsets, names = synth.make_families(30, 6, length=20000, seed=17)
+    gs = api.GenomeSet.from_codes(codes, offsets, names)
+    pairs = synth.family_pairs(30, 6)
+    tasks = gs.align_tasks(pairs)
+    sub = tasks[np.arange(len(tasks)) % 3 != 2]
+    assert np.array_equal(np.unique(sub['r']), np.unique(tasks['r']))          # the same references, so the same plan
+    want = {(int(t['q']), int(t['r'])): tuple(int(x) for x in s) for t, s in zip(tasks, gs.lz_align(tasks))}
+    same = lambda tk, st: len(st) == len(tk) and all(want[(int(t['q']), int(t['r']))] == tuple(int(x) for x in s) for t, s in zip(tk, st))
+    assert same(sub, gs.lz_align(sub))
+    stats, regions = gs.lz_align(tasks, want_regions=True)
+    assert same(tasks, stats)
+    api.profile_enable(True); api.profile_reset()
+    try:
+        gs.lz_prepare(pairs)
+        prepared = gs.lz_align(sub)
+        builds = {e['name']: e['launches'] for e in api.profile_get()}.get('lz_build_index')
+    finally:
+        api.profile_enable(False)
+    assert same(sub, prepared) and builds == 1
+    fresh_stats, fresh_regions = api.GenomeSet.from_codes(codes, offsets, names).lz_align(tasks, want_regions=True)
+    assert np.array_equal(stats, fresh_stats) and np.array_equal(regions, fresh_regions) and len(regions) > 0
 
 
 def test_accuracy_against_known_truth():

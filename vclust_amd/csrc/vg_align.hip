@@ -1414,11 +1414,6 @@ k_regions_place(const region_rec* __restrict__ arena, unsigned long long n_slots
     }
 }
 
-inline int grid_for(int64_t n, int block = 256, int max_blocks = 256 * 16) {
-    int64_t b = (n + block - 1) / block; if (b < 1) b = 1;
-    return (int)std::min<int64_t>(b, max_blocks);
-}
-
 }  // namespace
 
 // The constants of the LZ restatement that <= 3 events of the reference's example decide (vg_lz_fit): process-wide, set
@@ -1489,17 +1484,16 @@ k_task_records(const vg_task* __restrict__ tasks, const uint32_t* __restrict__ s
 // ---- reference plan of a vg_lz_align call: which references are indexed in which batch, their descriptors, the lists
 // of the build kernels and one set of index pools sized for the largest batch.  It depends on the REFERENCES of the task
 // list only (not on the tasks), so vg_lz_prepare can make it -- and build the first batch's indexes -- from the candidate
-// pairs alone, while the caller still assembles the canonical task list on the host.
+// pairs alone, while the caller still assembles the canonical task list on the host.  Once planned it changes only through
+// batch0_built and its device pools: what a call knows about its TASKS (lz_range) stays with the call.
 namespace {
 struct lz_batch {
-    int64_t pos = 0, end = 0;            // sorted task range
     int first_ref = 0, n_refs = 0;       // reference ordinals [first_ref, first_ref + n_refs)
     std::vector<int64_t> chunk_off{ 0 };
     std::vector<int> reg_list, mid_list, small_list, large_list; std::vector<int64_t> large_chunks{ 0 };
     int reg_class_end[6] = {0, 0, 0, 0, 0, 0};      // reg_list is ordered by register class (24, 20, 16, 12, 8, 4 trips): end of each class
     int64_t rr_words = 0, mask_words = 0, stab_tot = 0, sent_n = 0, scratch_words = 0, stride = 0;
     int nblk_build = 0;
-    double bytes_alg = 0; int64_t q_max = 0, q_sum = 0;          // SURVEY 8(d) bytes of the batch; longest / total query
 };
 struct lz_slot { dbuf<uint32_t> rr_pool, mask_pool, stab_pool, sent_pool, scratch; dbuf<int> d_reg, d_mid, d_small, d_large; dbuf<int64_t> d_lchunk; };
 struct lz_plan {
@@ -1523,12 +1517,26 @@ std::unique_ptr<lz_plan> g_prepared;          // left by vg_lz_prepare for the n
 // reference ids) only; it is dropped with the set (vg_genomes_free), by vg_release_device_memory, and never kept by the
 // cold one-shot calls.  Results do not depend on it.
 std::unique_ptr<lz_plan> g_plan_cache;
-// (under g_prep_mu) the cached plan when it is the plan of exactly these references, with fresh pools; else nullptr
-std::unique_ptr<lz_plan> lz_take_cached_plan(const vg_genomes* g, const vg_lz_params* p, const std::vector<uint32_t>& ref_ids) {
-    if (!g_plan_cache) return nullptr;
-    lz_plan& Q = *g_plan_cache;
-    if (Q.g != g || Q.mal != p->mal || Q.msl != p->msl || Q.n_genomes != g->n || Q.ref_ids != ref_ids || Q.budget != lz_batch_budget(g, p, ref_ids)) { g_plan_cache.reset(); return nullptr; }
-    return std::move(g_plan_cache);
+// the plan kept in `kept` (g_prepared or g_plan_cache) when it is the plan of exactly these references: same set, same
+// parameters, same budget; one that is not is dropped (its pools go back to the allocator: one stream, in order).
+// g_prep_mu is held around the move only, never around planning or allocation.
+std::unique_ptr<lz_plan> lz_take_plan(std::unique_ptr<lz_plan>& kept, const vg_genomes* g, const vg_lz_params* p, const std::vector<uint32_t>& ref_ids) {
+    std::lock_guard<std::mutex> lk(g_prep_mu);
+    std::unique_ptr<lz_plan> Q = std::move(kept);
+    if (Q && (Q->g != g || Q->mal != p->mal || Q->msl != p->msl || Q->n_genomes != g->n || Q->ref_ids != ref_ids || Q->budget != lz_batch_budget(g, p, ref_ids))) Q.reset();
+    return Q;
+}
+// a ready plan for these references: the host side of the last call's plan with fresh pools (*taken_over = true), or a new one
+std::unique_ptr<lz_plan> lz_plan_for(const vg_genomes* g, const vg_lz_params* p, const std::vector<uint32_t>& ref_ids, bool* taken_over = nullptr) {
+    std::unique_ptr<lz_plan> plan = lz_take_plan(g_plan_cache, g, p, ref_ids);
+    if (taken_over) *taken_over = plan != nullptr;
+    if (plan) lz_plan_alloc(*plan);
+    else {
+        plan.reset(new lz_plan);
+        plan->g = g; plan->ref_ids = ref_ids;
+        lz_plan_references(g, p, *plan);
+    }
+    return plan;
 }
 void lz_keep_plan_host_side(std::unique_ptr<lz_plan>& plan) {
     if (!plan || vg_one_shot()) return;
@@ -1577,15 +1585,208 @@ const uint32_t* vg_genome_planes(const vg_genomes* g, hipStream_t s) {
     return g->d_planes.p;
 }
 
-static int64_t g_segment_task_limit = 32768;
-// VG_LZ_BUILD=lds: the scratch-based LDS build also for short references (tests compare the two)
-static const bool g_no_reg_build = [] { const char* e = vg_dev_getenv("VG_LZ_BUILD"); return e && strcmp(e, "lds") == 0; }();
+// ---- the host side of vg_lz_align, stage by stage
+namespace {
+constexpr int64_t SEGMENT_TASK_LIMIT = 32768;
+// The developer switches of this stage, read once per process, when the library is loaded
+bool lz_switch_is(const char* name, const char* value) { const char* e = vg_dev_getenv(name); return e && !strcmp(e, value); }
+const struct {
+    bool two_pass = lz_switch_is("VG_LZ_REGIONS", "two-pass");      // the checker of the one-parse --out-aln
+    bool general = lz_switch_is("VG_LZ_KERNEL", "general");         // never the kernel with the default parameters as constants
+    bool lds_build = lz_switch_is("VG_LZ_BUILD", "lds");            // the scratch-based LDS build also for short references (tests compare the two)
+    const char* segments = vg_dev_getenv("VG_LZ_SEGMENTS");         // > 1: four waves per pair, else one
+    const char* arena = vg_dev_getenv("VG_LZ_ARENA");               // tests: a first region arena of that many records
+} g_sw{};
+
+// what the three entry points check alike
+void lz_check_params(const vg_lz_params* p) {
+    if (p->mal < 8 || p->mal > 31 || p->msl < 4 || p->msl > 12 || p->msl > p->mal) throw vg_error(VG_EINVAL, "mal must be 8..31, msl 4..12 and <= mal");
+}
+void lz_check_lengths(const vg_genomes* g, int first, int end) {
+    for (int i = first; i < end; ++i) if (g->len[(size_t)i] > (1 << 29)) throw vg_error(VG_EOVERFLOW, "genome longer than 2^29 bases");
+}
+
+// group tasks by reference ON THE DEVICE (k_task_count, a stable radix sort on the reference id, k_task_records):
+// device task records (query, ordinal of the reference among the references that have tasks, position in
+// the caller's list); the host gets the per-reference counts back and plans the batches from them.
+struct lz_tasks {
+    dbuf<task_dev> d_tasks;                    // sorted on the reference
+    std::vector<int64_t> ref_first;            // first sorted task of reference r
+    std::vector<uint32_t> ref_ids;             // references that have tasks, ascending
+    int64_t q_max = 0; double q_sum = 0, bytes_alg_all = 0;      // longest / total query; SURVEY 8(d) bytes of the call
+    std::vector<task_dev> td;                  // host copy of d_tasks, fetched for the two-pass --out-aln only
+};
+lz_tasks lz_group_tasks(const vg_genomes* g, const vg_task* tasks, int64_t n_tasks, bool host_copy, hipStream_t s) {
+    lz_tasks T;
+    T.ref_first.assign((size_t)g->n + 1, 0);
+    T.d_tasks.alloc((size_t)n_tasks);
+    dbuf<vg_task> d_raw((size_t)n_tasks); d_raw.upload(tasks, (size_t)n_tasks, s);
+    dbuf<uint32_t> d_cnt((size_t)g->n), d_keys((size_t)n_tasks), d_vals((size_t)n_tasks), d_keys2((size_t)n_tasks), d_vals2((size_t)n_tasks);
+    dbuf<unsigned long long> d_sums(4);
+    d_cnt.zero(s); d_sums.zero(s);
+    hipLaunchKernelGGL(k_task_count, dim3(grid_for(n_tasks, 256, 512)), dim3(256), 0, s,   // (few workgroups: every wave ends in three atomics on the same words)
+                       (const vg_task*)d_raw.p, n_tasks, g->n, g->d_len.p, d_cnt.p, d_keys.p, d_vals.p, d_sums.p);
+    std::vector<uint32_t> cnt((size_t)g->n); unsigned long long sums[4];
+    d_cnt.download(cnt.data(), cnt.size(), s); d_sums.download(sums, 4, s);
+    const unsigned id_bits = bit_width((uint64_t)std::max(g->n, 1) - 1, 1);
+    with_temp_storage([&](void* tmp, size_t& tb) {
+        return rocprim::radix_sort_pairs(tmp, tb, d_keys.p, d_keys2.p, d_vals.p, d_vals2.p, (size_t)n_tasks, 0u, id_bits, s); });
+    VG_HIP(hipStreamSynchronize(s));
+    if (sums[3]) throw vg_error(VG_EINVAL, "task id out of range");
+    std::vector<uint32_t> ord((size_t)g->n, 0);
+    for (int i = 0; i < g->n; ++i) {
+        if (cnt[(size_t)i]) { ord[(size_t)i] = (uint32_t)T.ref_ids.size(); T.ref_ids.push_back((uint32_t)i); }
+        T.ref_first[(size_t)i + 1] = T.ref_first[(size_t)i] + cnt[(size_t)i];
+    }
+    T.q_max = (int64_t)sums[2]; T.q_sum = (double)sums[0];
+    T.bytes_alg_all = ((double)sums[0] + (double)sums[1]) / 4.0 + 20.0 * (double)n_tasks;
+    dbuf<uint32_t> d_ord((size_t)g->n); d_ord.upload(ord.data(), ord.size(), s);
+    hipLaunchKernelGGL(k_task_records, dim3(grid_for(n_tasks)), dim3(256), 0, s, (const vg_task*)d_raw.p, (const uint32_t*)d_vals2.p, n_tasks,
+                       (const uint32_t*)d_ord.p, T.d_tasks.p);
+    if (host_copy) { T.td.resize((size_t)n_tasks); T.d_tasks.download(T.td.data(), T.td.size(), s); }
+    VG_HIP(hipStreamSynchronize(s));                      // the scratch buffers go out of scope
+    return T;
+}
+
+// the parameters the kernels read, and whether the call takes the kernel that has the defaults as compile-time constants:
+// default parameters on a set without N (VG_LZ_KERNEL=general: never)
+struct lz_kernel_params { lz_dev_params P; bool fast; };
+lz_kernel_params lz_device_params(const vg_genomes* g, const vg_lz_params* p) {
+    // probe widths (speculation only: results do not depend on them): positions probed right after an event, and after a
+    // first miss, before the scan goes to 64 per trip
+    const int pw_after = PW_AFTER_EVENT, pw_miss = 64;
+    // R3's weak-seed ratio (a single-event fit, DESIGN section 2): 3 unless VG_LZ_WEAK_SEED says otherwise (0 = off)
+    const vg_lz_fit fit = lz_fit_now();
+    const int weak_ratio = std::max(0, std::min(fit.weak_seed_ratio, 1000));
+    const int margin = fit.anchor_margin >= 0 ? std::min(fit.anchor_margin, 1000) : p->msl - 1;
+    const int seed_choice = fit.seed_choice == 1 ? 1 : 3;
+    const lz_dev_params P{ p->mal, p->msl, p->mrd, p->mqd, p->reg, p->aw, p->am, p->ar, pw_after, pw_miss, weak_ratio, margin, seed_choice };
+    bool fast = !g_sw.general && weak_ratio == 3 && margin == 6 && seed_choice == 3 && p->mal == 11 && p->msl == 7 && p->mrd == 40 && p->mqd == 40 && p->reg == 35 && p->aw == 15 && p->am == 7 && p->ar == 3;
+    for (int i = 0; fast && i < g->n; ++i) if (g->has_n[(size_t)i] || g->len[(size_t)i] >= (1 << 22)) fast = false;   // (tag: 8 bits beside <= 24 position bits)
+    return { P, fast };
+}
+
+// the tasks of one batch in the call's sorted list (tasks of a reference are contiguous) and the batch's share of the
+// call's figures: SURVEY 8(d) bytes and total query by task share, the longest query of the call
+struct lz_range { int64_t pos, end; double bytes_alg; int64_t q_max, q_sum; };
+lz_range lz_task_range(const lz_batch& B, const lz_tasks& T, int64_t n_tasks) {
+    const size_t ri_end = (size_t)B.first_ref + (size_t)B.n_refs;
+    const int64_t pos = T.ref_first[T.ref_ids[(size_t)B.first_ref]], end = ri_end < T.ref_ids.size() ? T.ref_first[T.ref_ids[ri_end]] : n_tasks;
+    return { pos, end, T.bytes_alg_all * (double)(end - pos) / (double)n_tasks, T.q_max, (int64_t)(T.q_sum * (double)(end - pos) / (double)n_tasks) };
+}
+
+// ---- the parse launches.  What those of one call share:
+struct lz_call {
+    const vg_genomes* g; const uint32_t* d_planes; const task_dev* d_tasks; const lz_plan* plan; lz_dev_params P; bool fast;
+    vg_pair_stat* d_stats; int64_t n_tasks; hipStream_t s;
+};
+using parse_fn = void (*)(PARSE_ARGS);
+parse_fn lz_parse_kernel(bool segments, bool fast, bool regions) {
+    if (regions) return fast ? k_lz_parse_fast_regions : k_lz_parse_regions;         // (one wave per pair: regions leave in query order)
+    if (segments) return fast ? k_lz_parse_seg_fast : k_lz_parse_seg;
+    return fast ? k_lz_parse_fast : k_lz_parse;
+}
+// one parse of the batch's tasks against the indexes in the plan's pools; an arena = the regions variant, none = rows only
+void lz_launch_parse(const lz_call& c, const lz_range& R, bool segments, bool fast,
+                     region_rec* arena = nullptr, unsigned long long* cursor = nullptr, unsigned long long cap = 0) {
+    const int64_t nt = R.end - R.pos;
+    const int64_t nblk = segments ? (nt + 7) / 8 * 8 : ((nt + 3) / 4 + 7) / 8 * 8;
+    const parse_fn kern = lz_parse_kernel(segments, fast, arena != nullptr);
+    const vg_genomes* g = c.g; const lz_slot& L = c.plan->slot;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), 0, c.s, c.d_tasks + R.pos, nt, c.plan->d_refs.p, c.d_planes, g->d_nmask.p,
+                       g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
+                       L.sent_pool.p, c.P, c.d_stats, arena, cursor, cap);
+}
+// rows only
+void lz_batch_rows(const lz_call& c, const lz_range& R) {
+    const int64_t nt = R.end - R.pos;
+    vg_prof_scope ps("lz_parse", R.bytes_alg);
+    // Four waves per pair (segments) shorten the critical path: worth it when the launch would
+    // otherwise last as long as its slowest pair -- few tasks, or queries several times longer than
+    // the average one (mixed contig sets).  With many uniform tasks one wave per pair keeps every
+    // SIMD busy without the duplicated stretches.
+    const bool uneven = R.q_max * nt > 3 * R.q_sum;
+    const bool segments = g_sw.segments ? atoi(g_sw.segments) > 1 : ((c.n_tasks <= SEGMENT_TASK_LIMIT && nt <= SEGMENT_TASK_LIMIT) || uneven);
+    lz_launch_parse(c, R, segments && nt < (1LL << 31), c.fast);
+}
+
+// ---- --out-aln: rows and regions from ONE parse.  One attempt: a regions parse into an arena of cap records, the region
+// counts of the batch's rows scanned into every task's first slot, and the placing pass -- every record to slot first[t] + k
+// of the batch's regions, which go behind h_regions.  Returns the records the parse asked for (the cursor); more than cap:
+// those beyond the arena were not written and nothing is placed.  The arena and d_regions live for one attempt only.
+unsigned long long lz_parse_and_place(const lz_call& c, const lz_range& R, bool fast, unsigned long long cap, const char* misplaced, std::vector<vg_region>& h_regions) {
+    const int64_t nt = R.end - R.pos; hipStream_t s = c.s;
+    dbuf<unsigned long long> d_cur(1), d_first((size_t)nt + 1);
+    dbuf<unsigned int> d_bad(1);
+    dbuf<region_rec> d_arena((size_t)cap);
+    std::optional<vg_prof_scope> ps; ps.emplace("lz_parse", R.bytes_alg);
+    d_cur.zero(s); d_bad.zero(s);
+    lz_launch_parse(c, R, false, fast, d_arena.p, d_cur.p, cap);
+    ps.emplace("lz_regions_place", 0);                // (the scope above timed the parse; this one the kernels of the placing pass, not the downloads)
+    hipLaunchKernelGGL(k_region_counts, dim3(grid_for(nt + 1)), dim3(256), 0, s, c.d_tasks + R.pos, nt, (const vg_pair_stat*)c.d_stats, d_first.p);
+    with_temp_storage([&](void* tmp, size_t& tb) {
+        return rocprim::exclusive_scan(tmp, tb, d_first.p, d_first.p, 0ULL, (size_t)nt + 1, rocprim::plus<unsigned long long>(), s); });
+    ps.reset();
+    unsigned long long used = 0, nr = 0;
+    d_cur.download(&used, 1, s);
+    VG_HIP(hipMemcpyAsync(&nr, d_first.p + nt, sizeof nr, hipMemcpyDeviceToHost, s));
+    VG_HIP(hipStreamSynchronize(s));
+    if (used > cap || !nr) return used;
+    dbuf<vg_region> d_regions((size_t)nr);
+    ps.emplace("lz_regions_place", (double)used * 32.0 + (double)nr * 24.0);
+    hipLaunchKernelGGL(k_regions_place, dim3(grid_for((int64_t)used)), dim3(256), 0, s, (const region_rec*)d_arena.p, used,
+                       (const unsigned long long*)d_first.p, nr, d_regions.p, d_bad.p);
+    ps.reset();
+    unsigned int bad = 0; d_bad.download(&bad, 1, s);
+    const size_t at = h_regions.size();
+    h_regions.resize(at + (size_t)nr);
+    d_regions.download(h_regions.data() + at, (size_t)nr, s);
+    VG_HIP(hipStreamSynchronize(s));
+    if (bad) throw vg_error(VG_EHIP, misplaced);      // (rows and records of one parse cannot disagree)
+    return used;
+}
+// The arena is sized from the batch (a chunk per task + a region per 256 query symbols: four times what diverged phage
+// families produce); should a batch need more, the cursor says exactly how much and the batch is repeated.
+void lz_batch_regions(const lz_call& c, const lz_range& R, std::vector<vg_region>& h_regions) {
+    const int64_t nt = R.end - R.pos;
+    unsigned long long cap = (unsigned long long)nt * RCHUNK + (unsigned long long)(R.q_sum / 256) + 1024;
+    if (const long long first = g_sw.arena ? atoll(g_sw.arena) : 0LL; first > 0) cap = (unsigned long long)first;
+    // (a generous first arena must not be what makes a large call fail: at most an eighth of the free device memory;
+    // a batch that needs more says so through the cursor and is repeated with exactly what it needs)
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0)
+        cap = std::min(cap, std::max<unsigned long long>((unsigned long long)nt * RCHUNK / 4 + 1024, (unsigned long long)(fr / 8) / sizeof(region_rec)));
+    else (void)hipGetLastError();
+    const char* misplaced = "internal error: region records of the LZ parse disagree with its rows";
+    const unsigned long long used = lz_parse_and_place(c, R, c.fast, cap, misplaced, h_regions);
+    if (used > cap && lz_parse_and_place(c, R, c.fast, used, misplaced, h_regions) > used)       // (once more, with room for all)
+        throw vg_error(VG_EHIP, "internal error: the region arena of the LZ parse overflowed twice");
+}
+// VG_LZ_REGIONS=two-pass (developer switch, the checker of the one-parse path): a counting parse gives every task's region
+// count (its rows are kept in first_pass), the parse runs a SECOND time -- the general kernel, whatever the call takes
+// otherwise -- into an arena of exactly the chunks those counts need, and the same placing pass orders the records
+void lz_batch_two_pass(const lz_call& c, const lz_range& R, const std::vector<task_dev>& td, std::vector<vg_pair_stat>& first_pass, std::vector<vg_region>& h_regions) {
+    { vg_prof_scope ps("lz_parse", R.bytes_alg); lz_launch_parse(c, R, false, c.fast); }
+    std::vector<vg_pair_stat> h_stats((size_t)c.n_tasks);
+    vg_download_bytes(h_stats.data(), c.d_stats, h_stats.size() * sizeof(vg_pair_stat), c.s);
+    VG_HIP(hipStreamSynchronize(c.s));
+    if (first_pass.empty()) first_pass.resize((size_t)c.n_tasks);
+    unsigned long long chunks = 0;
+    for (int64_t t = R.pos; t < R.end; ++t) {
+        const uint32_t oi = td[(size_t)t].out_idx;
+        first_pass[oi] = h_stats[oi];
+        chunks += (h_stats[oi].n_regions + RCHUNK - 1) / RCHUNK;
+    }
+    if (chunks && lz_parse_and_place(c, R, false, chunks * RCHUNK, "internal error: the region pass and the counting pass of the LZ parse disagree", h_regions) > chunks * RCHUNK)
+        throw vg_error(VG_EHIP, "internal error: the region pass of the LZ parse overflowed the arena sized from the counting pass");
+}
+}  // namespace
 
 extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks, const vg_lz_params* p,
                            vg_pair_stat* stats, vg_region** regions, int64_t* n_regions) {
     VG_API_BEGIN
     if (!g || (!tasks && n_tasks) || !p || (!stats && n_tasks)) throw vg_error(VG_EINVAL, "vg_lz_align: null argument");
-    if (p->mal < 8 || p->mal > 31 || p->msl < 4 || p->msl > 12 || p->msl > p->mal) throw vg_error(VG_EINVAL, "mal must be 8..31, msl 4..12 and <= mal");
+    lz_check_params(p);
     if (p->aw < 1 || p->aw > 32 || p->ar < 1 || p->ar > 16 || p->am < 0 || p->mrd < 0 || p->mqd < 0 || p->reg < 0)
         throw vg_error(VG_EINVAL, "aw must be 1..32, ar 1..16");
     if (p->mqd > 2000) throw vg_error(VG_EINVAL, "mqd must be <= 2000 (one wave scores a literal run of at most 2 048 symbols)");
@@ -1597,239 +1798,34 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
 
     if (regions) { *regions = nullptr; if (n_regions) *n_regions = 0; }
     if (n_tasks == 0) return VG_OK;
-    for (int i = 0; i < g->n; ++i) if (g->len[i] > (1 << 29)) throw vg_error(VG_EOVERFLOW, "genome longer than 2^29 bases");
+    lz_check_lengths(g, 0, g->n);
     if (n_tasks >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "more than 2^32 - 1 ordered pairs in one call: split the task list");
+    const bool want_regions = regions != nullptr, two_pass = want_regions && g_sw.two_pass;
 
-    // group tasks by reference ON THE DEVICE (k_task_count, a stable radix sort on the reference id, k_task_records):
-    // device task records (query, ordinal of the reference among the references that have tasks, position in
-    // the caller's list); the host gets the per-reference counts back and plans the batches from them.
-    static const bool two_pass_regions = [] { const char* e = vg_dev_getenv("VG_LZ_REGIONS"); return e && !strcmp(e, "two-pass"); }();      // developer switch: the checker of the one-parse --out-aln
-    std::vector<task_dev> td;                                 // host copy, fetched for the two-pass --out-aln only
-    std::vector<int64_t> ref_first((size_t)g->n + 1, 0);     // first sorted task of reference r
-    std::vector<uint32_t> ref_ids;                            // references that have tasks, ascending
-    int64_t q_max = 0; double q_sum = 0, bytes_alg_all = 0;
-    dbuf<task_dev> d_tasks((size_t)n_tasks);
-    {
-        dbuf<vg_task> d_raw((size_t)n_tasks); d_raw.upload(tasks, (size_t)n_tasks, s);
-        dbuf<uint32_t> d_cnt((size_t)g->n), d_keys((size_t)n_tasks), d_vals((size_t)n_tasks), d_keys2((size_t)n_tasks), d_vals2((size_t)n_tasks);
-        dbuf<unsigned long long> d_sums(4);
-        d_cnt.zero(s); d_sums.zero(s);
-        hipLaunchKernelGGL(k_task_count, dim3(grid_for(n_tasks, 256, 512)), dim3(256), 0, s,   // (few workgroups: every wave ends in three atomics on the same words)
-                           (const vg_task*)d_raw.p, n_tasks, g->n, g->d_len.p, d_cnt.p,
-                           d_keys.p, d_vals.p, d_sums.p);
-        std::vector<uint32_t> cnt((size_t)g->n); unsigned long long sums[4];
-        d_cnt.download(cnt.data(), cnt.size(), s); d_sums.download(sums, 4, s);
-        int id_bits = 1; while ((1LL << id_bits) < g->n) ++id_bits;
-        size_t tmp_bytes = 0;
-        VG_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d_vals2.p, (size_t)n_tasks, 0u, (unsigned)id_bits, s));
-        dbuf<char> tmp(tmp_bytes);
-        VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, d_vals2.p, (size_t)n_tasks, 0u, (unsigned)id_bits, s));
-        VG_HIP(hipStreamSynchronize(s));
-        if (sums[3]) throw vg_error(VG_EINVAL, "task id out of range");
-        std::vector<uint32_t> ord((size_t)g->n, 0);
-        for (int i = 0; i < g->n; ++i) {
-            if (cnt[(size_t)i]) { ord[(size_t)i] = (uint32_t)ref_ids.size(); ref_ids.push_back((uint32_t)i); }
-            ref_first[(size_t)i + 1] = ref_first[(size_t)i] + cnt[(size_t)i];
-        }
-        q_max = (int64_t)sums[2]; q_sum = (double)sums[0];
-        bytes_alg_all = ((double)sums[0] + (double)sums[1]) / 4.0 + 20.0 * (double)n_tasks;
-        dbuf<uint32_t> d_ord((size_t)g->n); d_ord.upload(ord.data(), ord.size(), s);
-        hipLaunchKernelGGL(k_task_records, dim3(grid_for(n_tasks)), dim3(256), 0, s, (const vg_task*)d_raw.p, (const uint32_t*)d_vals2.p, n_tasks,
-                           (const uint32_t*)d_ord.p, d_tasks.p);
-        if (regions && two_pass_regions) { td.resize((size_t)n_tasks); d_tasks.download(td.data(), td.size(), s); }
-        VG_HIP(hipStreamSynchronize(s));                      // the scratch buffers go out of scope
-    }
+    const lz_tasks T = lz_group_tasks(g, tasks, n_tasks, two_pass, s);
     vg_host_mark("lz: tasks grouped");
-    // probe widths (speculation only: results do not depend on them): positions probed right after an event, and after a
-    // first miss, before the scan goes to 64 per trip
-    const int pw_after = PW_AFTER_EVENT, pw_miss = 64;
-    // R3's weak-seed ratio (a single-event fit, DESIGN section 2): 3 unless VG_LZ_WEAK_SEED says otherwise (0 = off)
-    const vg_lz_fit fit = lz_fit_now();
-    const int weak_ratio = std::max(0, std::min(fit.weak_seed_ratio, 1000));
-    const int margin = fit.anchor_margin >= 0 ? std::min(fit.anchor_margin, 1000) : p->msl - 1;
-    const int seed_choice = fit.seed_choice == 1 ? 1 : 3;
-    const lz_dev_params P{ p->mal, p->msl, p->mrd, p->mqd, p->reg, p->aw, p->am, p->ar, pw_after, pw_miss, weak_ratio, margin, seed_choice };
-    // default parameters on a set without N: the kernel with those as compile-time constants (VG_LZ_KERNEL=general: never)
-    static const bool no_fast = [] { const char* e = vg_dev_getenv("VG_LZ_KERNEL"); return e && !strcmp(e, "general"); }();
-    bool fast_params = !no_fast && weak_ratio == 3 && margin == 6 && seed_choice == 3 && p->mal == 11 && p->msl == 7 && p->mrd == 40 && p->mqd == 40 && p->reg == 35 && p->aw == 15 && p->am == 7 && p->ar == 3;
-    for (int i = 0; fast_params && i < g->n; ++i) if (g->has_n[(size_t)i] || g->len[(size_t)i] >= (1 << 22)) fast_params = false;   // (tag: 8 bits beside <= 24 position bits)
-
+    const lz_kernel_params K = lz_device_params(g, p);
     dbuf<vg_pair_stat> d_stats((size_t)n_tasks);
-    const bool want_regions = regions != nullptr;
-    std::vector<vg_region> h_regions;                 // all kept regions, batch after batch
-    std::vector<vg_pair_stat> h_stats;                // host copy of the rows (sizes the region buffer)
-    std::vector<vg_pair_stat> first_pass;             // --out-aln: the rows of the counting pass, batch after batch
-
     // ---- plan: references are taken in id order, batch after batch, each batch's indexes under the budget.
     // (Building batch b + 1 on a second stream while batch b is parsed was measured: the 160 KiB-LDS build
     // workgroups and the parse waves only split the CUs between them, 321 vs 319 ms at 100 k genomes -- so
     // the batches run back to back on the library stream, as few and as large as the budget allows.)
-    // A plan left by vg_lz_prepare for exactly these references (same set, same parameters, same budget) is taken over
-    // with its first batch already built (or being built: same stream).
-    std::unique_ptr<lz_plan> plan;
-    {
-        std::lock_guard<std::mutex> lk(g_prep_mu);
-        if (g_prepared) {
-            lz_plan& Q = *g_prepared;
-            if (Q.g == g && Q.mal == p->mal && Q.msl == p->msl && Q.ref_ids == ref_ids && Q.budget == lz_batch_budget(g, p, ref_ids)) plan = std::move(g_prepared);
-            else g_prepared.reset();                             // (its pools go back to the allocator: one stream, in order)
-        }
-    }
-    if (!plan) {
-        { std::lock_guard<std::mutex> lk(g_prep_mu); plan = lz_take_cached_plan(g, p, ref_ids); }
-        if (plan) lz_plan_alloc(*plan);
-        else {
-            plan.reset(new lz_plan);
-            plan->g = g; plan->ref_ids = ref_ids;
-            lz_plan_references(g, p, *plan);
-        }
-    }
-    std::vector<lz_batch>& batches = plan->batches;
-    dbuf<ref_desc>& d_refs = plan->d_refs;
-    lz_slot& slot = plan->slot;
-    // the task ranges of the batches (sorted task list: tasks of a reference are contiguous)
-    for (auto& B : batches) {
-        B.pos = ref_first[ref_ids[(size_t)B.first_ref]];
-        const size_t ri_end = (size_t)B.first_ref + (size_t)B.n_refs;
-        B.end = ri_end < ref_ids.size() ? ref_first[ref_ids[ri_end]] : n_tasks;
-        B.bytes_alg = bytes_alg_all * (double)(B.end - B.pos) / (double)n_tasks;       // the call's SURVEY 8(d) bytes, by task share
-        B.q_max = q_max; B.q_sum = (int64_t)(q_sum * (double)(B.end - B.pos) / (double)n_tasks);
-    }
+    // A plan left by vg_lz_prepare for exactly these references is taken over with its first batch already built (or being
+    // built: same stream).
+    std::unique_ptr<lz_plan> plan = lz_take_plan(g_prepared, g, p, T.ref_ids);
+    if (!plan) plan = lz_plan_for(g, p, T.ref_ids);
+    std::vector<lz_range> ranges;                     // per call: the plan holds nothing about tasks
+    for (const lz_batch& B : plan->batches) ranges.push_back(lz_task_range(B, T, n_tasks));
     vg_host_mark("lz: batches planned");
-    hipStream_t sb = s;
-    static const char* seg_env = vg_dev_getenv("VG_LZ_SEGMENTS");
-    for (size_t bi = 0; bi < batches.size(); ++bi) {
-        lz_batch& B = batches[bi];
-        lz_slot& L = slot;
-        if (!(bi == 0 && plan->batch0_built)) lz_build_batch(g, p, *plan, bi, sb);
-        {
-            const int64_t nt = B.end - B.pos;
-            std::optional<vg_prof_scope> ps; ps.emplace("lz_parse", B.bytes_alg);
-            // Four waves per pair (segments) shorten the critical path: worth it when the launch would
-            // otherwise last as long as its slowest pair -- few tasks, or queries several times longer than
-            // the average one (mixed contig sets).  With many uniform tasks one wave per pair keeps every
-            // SIMD busy without the duplicated stretches.
-            const bool uneven = B.q_max * nt > 3 * B.q_sum;
-            const bool segments = !want_regions && (seg_env ? atoi(seg_env) > 1 : ((n_tasks <= g_segment_task_limit && nt <= g_segment_task_limit) || uneven));
-            if (want_regions && !two_pass_regions) {
-                // --out-aln: rows and regions from ONE parse (one wave per pair: regions leave in query order).  The arena is
-                // sized from the batch (a chunk per task + a region per 256 query symbols: four times what diverged phage
-                // families produce); should a batch need more, the cursor says exactly how much and the batch is repeated.
-                const int64_t nblk = ((nt + 3) / 4 + 7) / 8 * 8;
-                unsigned long long cap = (unsigned long long)nt * RCHUNK + (unsigned long long)(B.q_sum / 256) + 1024;
-                static const long long cap_env = [] { const char* e = vg_dev_getenv("VG_LZ_ARENA"); return e ? atoll(e) : 0LL; }();      // developer switch (tests): a first arena of that many records
-                if (cap_env > 0) cap = (unsigned long long)cap_env;
-                {   // (a generous first arena must not be what makes a large call fail: at most an eighth of the free device memory;
-                    // a batch that needs more says so through the cursor and is repeated with exactly what it needs)
-                    size_t fr = 0, tot = 0;
-                    if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 0) {
-                        const unsigned long long most = std::max<unsigned long long>((unsigned long long)nt * RCHUNK / 4 + 1024, (unsigned long long)(fr / 8) / sizeof(region_rec));
-                        if (cap > most) cap = most;
-                    } else (void)hipGetLastError();
-                }
-                dbuf<unsigned long long> d_cur(1), d_first((size_t)nt + 1);
-                dbuf<unsigned int> d_bad(1);
-                for (int attempt = 0;; ++attempt) {
-                    dbuf<region_rec> d_arena((size_t)cap);
-                    d_cur.zero(s); d_bad.zero(s);
-                    if (!ps) ps.emplace("lz_parse", B.bytes_alg);
-                    if (fast_params) hipLaunchKernelGGL(k_lz_parse_fast_regions, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                       g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                       L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap);
-                    else hipLaunchKernelGGL(k_lz_parse_regions, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                       g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                       L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap);
-                    ps.reset();                                   // (the scope times the parse; what follows is the placing pass)
-                    std::optional<vg_prof_scope> ps2; ps2.emplace("lz_regions_place", 0);      // (its kernels, not the downloads)
-                    hipLaunchKernelGGL(k_region_counts, dim3(grid_for(nt + 1)), dim3(256), 0, s, (const task_dev*)(d_tasks.p + B.pos), nt, (const vg_pair_stat*)d_stats.p, d_first.p);
-                    size_t tb = 0;
-                    VG_HIP(rocprim::exclusive_scan(nullptr, tb, d_first.p, d_first.p, 0ULL, (size_t)nt + 1, rocprim::plus<unsigned long long>(), s));
-                    dbuf<char> tmp(tb);
-                    VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, d_first.p, d_first.p, 0ULL, (size_t)nt + 1, rocprim::plus<unsigned long long>(), s));
-                    ps2.reset();
-                    unsigned long long used = 0, nr = 0;
-                    d_cur.download(&used, 1, s);
-                    VG_HIP(hipMemcpyAsync(&nr, d_first.p + nt, sizeof nr, hipMemcpyDeviceToHost, s));
-                    VG_HIP(hipStreamSynchronize(s));
-                    if (used > cap) {
-                        if (attempt) throw vg_error(VG_EHIP, "internal error: the region arena of the LZ parse overflowed twice");
-                        cap = used; continue;                     // (records beyond the arena were not written: once more, with room for all)
-                    }
-                    if (nr) {
-                        dbuf<vg_region> d_regions((size_t)nr);
-                        ps2.emplace("lz_regions_place", (double)used * 32.0 + (double)nr * 24.0);
-                        hipLaunchKernelGGL(k_regions_place, dim3(grid_for((int64_t)used)), dim3(256), 0, s, (const region_rec*)d_arena.p, used,
-                                           (const unsigned long long*)d_first.p, nr, d_regions.p, d_bad.p);
-                        ps2.reset();
-                        unsigned int bad = 0; d_bad.download(&bad, 1, s);
-                        const size_t at = h_regions.size();
-                        h_regions.resize(at + (size_t)nr);
-                        d_regions.download(h_regions.data() + at, (size_t)nr, s);
-                        VG_HIP(hipStreamSynchronize(s));
-                        if (bad) throw vg_error(VG_EHIP, "internal error: region records of the LZ parse disagree with its rows");
-                    }
-                    break;
-                }
-                continue;
-            }
-            if (segments && nt < (1LL << 31)) {
-                const int64_t nblk = (nt + 7) / 8 * 8;
-                if (fast_params) hipLaunchKernelGGL(k_lz_parse_seg_fast, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
-                else hipLaunchKernelGGL(k_lz_parse_seg, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
-            } else {
-                const int64_t nblk = ((nt + 3) / 4 + 7) / 8 * 8;
-                if (fast_params) {
-                    hipLaunchKernelGGL(k_lz_parse_fast, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
-                } else {
-                    hipLaunchKernelGGL(k_lz_parse, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, (region_rec*)nullptr, (unsigned long long*)nullptr, 0ULL);
-                }
-            }
-            if (want_regions) {
-                // VG_LZ_REGIONS=two-pass (developer switch, the checker of the one-parse path): the rows just computed give
-                // every task's region count, the parse runs a SECOND time into an arena that is known to fit, and the same
-                // placing pass orders the records
-                h_stats.resize((size_t)n_tasks);
-                d_stats.download(h_stats.data(), (size_t)n_tasks, s);
-                VG_HIP(hipStreamSynchronize(s));
-                std::vector<unsigned long long> off((size_t)nt + 1, 0);
-                if (first_pass.empty()) first_pass.resize((size_t)n_tasks);
-                unsigned long long chunks = 0;
-                for (int64_t t = 0; t < nt; ++t) {
-                    const uint32_t oi = td[(size_t)(B.pos + t)].out_idx;
-                    first_pass[oi] = h_stats[oi];
-                    off[(size_t)t + 1] = off[(size_t)t] + h_stats[oi].n_regions;
-                    chunks += (h_stats[oi].n_regions + RCHUNK - 1) / RCHUNK;
-                }
-                const unsigned long long nr = off[(size_t)nt];
-                if (nr) {
-                    const unsigned long long cap = chunks * RCHUNK;
-                    dbuf<unsigned long long> d_off((size_t)nt + 1), d_cur(1); d_off.upload(off.data(), off.size(), s);
-                    dbuf<unsigned int> d_bad(1); d_cur.zero(s); d_bad.zero(s);
-                    dbuf<region_rec> d_arena((size_t)cap);
-                    dbuf<vg_region> d_regions((size_t)nr);
-                    const int64_t nblk = ((nt + 3) / 4 + 7) / 8 * 8;
-                    hipLaunchKernelGGL(k_lz_parse_regions, dim3((unsigned)nblk), dim3(256), 0, s, d_tasks.p + B.pos, nt, d_refs.p, d_planes, g->d_nmask.p,
-                                   g->d_base_off.p, g->d_len.p, g->d_has_n.p, L.rr_pool.p, L.mask_pool.p, L.stab_pool.p,
-                                   L.sent_pool.p, P, d_stats.p, d_arena.p, d_cur.p, cap);
-                    hipLaunchKernelGGL(k_regions_place, dim3(grid_for((int64_t)cap)), dim3(256), 0, s, (const region_rec*)d_arena.p, cap,
-                                       (const unsigned long long*)d_off.p, nr, d_regions.p, d_bad.p);
-                    unsigned int bad = 0; d_bad.download(&bad, 1, s);
-                    const size_t at = h_regions.size();
-                    h_regions.resize(at + (size_t)nr);
-                    d_regions.download(h_regions.data() + at, (size_t)nr, s);
-                    VG_HIP(hipStreamSynchronize(s));
-                    if (bad) throw vg_error(VG_EHIP, "internal error: the region pass and the counting pass of the LZ parse disagree");
-                }
-            }
-        }
+
+    const lz_call c{ g, d_planes, T.d_tasks.p, plan.get(), K.P, K.fast, d_stats.p, n_tasks, s };
+    std::vector<vg_region> h_regions;                 // all kept regions, batch after batch
+    std::vector<vg_pair_stat> first_pass;             // two-pass --out-aln: the rows of the counting pass
+    for (size_t bi = 0; bi < ranges.size(); ++bi) {
+        if (!(bi == 0 && plan->batch0_built)) lz_build_batch(g, p, *plan, bi, s);
+        if (!want_regions) lz_batch_rows(c, ranges[bi]);
+        else if (two_pass) lz_batch_two_pass(c, ranges[bi], T.td, first_pass, h_regions);
+        else lz_batch_regions(c, ranges[bi], h_regions);
     }
     vg_host_mark("lz: launched");
     vg_deferred_start();                                      // (the host now waits for the kernels: parked clean-up runs beside them)
@@ -1852,7 +1848,6 @@ extern "C" int vg_lz_align(vg_genomes* g, const vg_task* tasks, int64_t n_tasks,
     lz_keep_plan_host_side(plan);
     VG_API_END
 }
-
 
 // ------------------------------------------------------------------ reference plan (see lz_plan)
 namespace {
@@ -1915,8 +1910,8 @@ void lz_plan_references(const vg_genomes* g, const vg_lz_params* p, lz_plan& P) 
         for (int i = 0; i < n_refs; ++i) {
             const int gi = B.first_ref + i;                      // ordinal = index into all_refs / the device array
             const bool small = all_refs[(size_t)gi].n_rr <= (1 << 21) && p->msl <= 7;
-            if (small && all_refs[(size_t)gi].n_rr <= REG_MAX_RR && !g_no_reg_build) B.reg_list.push_back(gi);
-            else if (small && all_refs[(size_t)gi].n_rr <= MID_MAX_RR && !g_no_reg_build) B.mid_list.push_back(gi);
+            if (small && all_refs[(size_t)gi].n_rr <= REG_MAX_RR && !g_sw.lds_build) B.reg_list.push_back(gi);
+            else if (small && all_refs[(size_t)gi].n_rr <= MID_MAX_RR && !g_sw.lds_build) B.mid_list.push_back(gi);
             else if (small) B.small_list.push_back(gi);
             else { B.large_list.push_back(gi); B.large_chunks.push_back(B.large_chunks.back() + (B.chunk_off[(size_t)i + 1] - B.chunk_off[(size_t)i])); }
         }
@@ -2035,12 +2030,12 @@ void lz_build_batch(const vg_genomes* g, const vg_lz_params* p, lz_plan& P, size
 extern "C" int vg_lz_prepare(vg_genomes* g, const vg_pair_count* pairs, int64_t n_pairs, const vg_lz_params* p) {
     VG_API_BEGIN
     if (!g || (!pairs && n_pairs) || !p) throw vg_error(VG_EINVAL, "vg_lz_prepare: null argument");
-    if (p->mal < 8 || p->mal > 31 || p->msl < 4 || p->msl > 12 || p->msl > p->mal) throw vg_error(VG_EINVAL, "mal must be 8..31, msl 4..12 and <= mal");
+    lz_check_params(p);
     vg_require_device();
     int rc = vg_genomes_to_device(g); if (rc) return rc;
     vg_lz_drop_prepared(nullptr);
     if (n_pairs == 0) return VG_OK;
-    for (int i = 0; i < g->n; ++i) if (g->len[i] > (1 << 29)) throw vg_error(VG_EOVERFLOW, "genome longer than 2^29 bases");
+    lz_check_lengths(g, 0, g->n);
     std::vector<uint8_t> is_ref((size_t)g->n, 0);
     for (int64_t i = 0; i < n_pairs; ++i) {
         if (pairs[i].a >= (uint32_t)g->n || pairs[i].b >= (uint32_t)g->n) throw vg_error(VG_EINVAL, "pair id out of range");
@@ -2049,16 +2044,9 @@ extern "C" int vg_lz_prepare(vg_genomes* g, const vg_pair_count* pairs, int64_t 
     std::vector<uint32_t> ref_ids;
     for (int i = 0; i < g->n; ++i) if (is_ref[(size_t)i]) ref_ids.push_back((uint32_t)i);
     vg_host_mark("lz prepare: references listed");
-    std::unique_ptr<lz_plan> plan;
-    { std::lock_guard<std::mutex> lk(g_prep_mu); plan = lz_take_cached_plan(g, p, ref_ids); }
-    if (plan) { lz_plan_alloc(*plan); vg_host_mark("lz prepare: plan of the last call taken over"); }
-    else {
-        plan.reset(new lz_plan);
-        plan->ref_ids = std::move(ref_ids);
-        plan->g = g;
-        lz_plan_references(g, p, *plan);
-        vg_host_mark("lz prepare: planned");
-    }
+    bool taken_over = false;
+    std::unique_ptr<lz_plan> plan = lz_plan_for(g, p, ref_ids, &taken_over);
+    vg_host_mark(taken_over ? "lz prepare: plan of the last call taken over" : "lz prepare: planned");
     lz_build_batch(g, p, *plan, 0, vg_stream());
     plan->batch0_built = true;
     vg_host_mark("lz: first batch of indexes queued");
@@ -2074,11 +2062,11 @@ extern "C" int vg_lz_index_dump(vg_genomes* g, int idx, const vg_lz_params* p, u
     VG_API_BEGIN
     if (!g || !p || !bucket_end || !entries || !n_entries || !pos_bits || !tag_bits || !path) throw vg_error(VG_EINVAL, "vg_lz_index_dump: null argument");
     *bucket_end = nullptr; *entries = nullptr; *n_entries = 0;
-    if (p->mal < 8 || p->mal > 31 || p->msl < 4 || p->msl > 12 || p->msl > p->mal) throw vg_error(VG_EINVAL, "mal must be 8..31, msl 4..12 and <= mal");
+    lz_check_params(p);
     vg_require_device();
     int rc = vg_genomes_to_device(g); if (rc) return rc;
     if (idx < 0 || idx >= g->n) throw vg_error(VG_EINVAL, "genome id out of range");
-    if (g->len[idx] > (1 << 29)) throw vg_error(VG_EOVERFLOW, "genome longer than 2^29 bases");
+    lz_check_lengths(g, idx, idx + 1);
     hipStream_t s = vg_stream();
     lz_plan plan;
     plan.g = g; plan.ref_ids.assign(1, (uint32_t)idx);

@@ -92,6 +92,17 @@ template <class F> void with_temp_storage(F call) {
     dbuf<char> tmp(tb ? tb : 1);
     VG_HIP(call((void*)tmp.p, tb));
 }
+// blocks of a grid-stride launch over n items: one item per thread, at least one block and at most max_blocks
+inline int grid_for(int64_t n, int block = 256, int max_blocks = 256 * 16) {
+    int64_t b = (n + block - 1) / block; if (b < 1) b = 1;
+    return (int)(b < max_blocks ? b : max_blocks);
+}
+// the smallest b >= from (at most 64) with x < 2^b: the bits of a radix sort over keys up to x
+inline unsigned bit_width(uint64_t x, unsigned from) {
+    unsigned b = from;
+    while (b < 64 && (x >> b)) ++b;
+    return b;
+}
 
 // ---------------------------------------------------------------- profiling (HIP events on vg_stream)
 struct vg_prof_scope {

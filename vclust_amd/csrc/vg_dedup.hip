@@ -792,12 +792,6 @@ void scan(const T* in, T* out, int64_t n, bool inclusive, Op op, hipStream_t s) 
         return inclusive ? rocprim::inclusive_scan(tmp, tb, in, out, (size_t)n, op, s)
                          : rocprim::exclusive_scan(tmp, tb, in, out, (T)0, (size_t)n, op, s); });
 }
-// the smallest b >= from (at most 64) with x < 2^b: the bits of a radix sort over keys up to x
-unsigned bit_width(uint64_t x, unsigned from) {
-    unsigned b = from;
-    while (b < 64 && (x >> b)) ++b;
-    return b;
-}
 // the (record, chunk of HASH_CHUNK words) tasks of records of len[i] symbols: cbeg[i] = record i's first task (an empty
 // record has one)
 struct chunk_tasks { std::vector<int64_t> cbeg; int64_t n_tasks = 0, max_len = 0, total_words = 0; };

@@ -2047,12 +2047,6 @@ __global__ void k_bucket_sizes(const uint32_t* __restrict__ boff, const uint32_t
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) sizes[i] = boff[list[i] + 1] - boff[list[i]];
 }
 
-inline int grid_for(int64_t n, int block = 256, int max_blocks = 256 * 16) {
-    int64_t b = (n + block - 1) / block;
-    if (b < 1) b = 1;
-    return (int)std::min<int64_t>(b, max_blocks);
-}
-
 struct max_op { __device__ __host__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; } };
 
 }  // namespace
