@@ -520,3 +520,37 @@ def test_hash_subshards_from_one_scan(k, fraction, sub):
         assert list(tot) == list(osizes) and acc == opairs
     finally:
         api.profile_enable(False); _lib.load().vg_set_subshards(0)
+
+
+def test_hash_subshards_scan_ahead():
+    """HASH sub-shards beyond the one-scan masks (more than 32 of them, no fraction): every pass scans the bases for its own
+    k-mers, and the scan of sub-shard t + 1 runs ahead on the side queue while sub-shard t is indexed and multiplied.  Eight
+    outer shards of 33 sub-shards each (264 HASH passes): sizes and counts summed over the shards equal the oracle's.  No
+    pass takes its mask from `kmer_multi_mask`.  The `kmer_count` scope of one shard's call has 34 launches: the first pass
+    scans in line (1), the other 32 first scans arrive from the scan ahead, which has no scope, and every one of the 33 passes
+    -- 10^4 k-mers, too few for the bucket pipeline -- extracts once more in line for the general path (33).  Without the scan
+    ahead the scope would show 66."""
+    from vclust_amd import _lib
+    k = 25
+    codes, offsets, names = synth.make_families(60, 5, length=9000, seed=37)
+    gs = api.GenomeSet.from_codes(codes, offsets, names)
+    osizes, opairs = orc.shared_all(codes, offsets, k=k, fraction=1.0)
+    _lib.load().vg_set_subshards(33)
+    try:
+        tot = np.zeros(len(gs), dtype=np.int64); acc = {}
+        for sh in range(8):
+            if sh == 0:
+                api.profile_enable(True); api.profile_reset()
+            sz, pr = gs.kmer_shared(k=k, fraction=1.0, shard=sh, n_shards=8)
+            if sh == 0:
+                scopes = {e['name']: e for e in api.profile_get()}
+                api.profile_enable(False)
+                print('scan-ahead scopes:', {n: e['launches'] for n, e in scopes.items()})
+                assert 'kmer_multi_mask' not in scopes
+                assert scopes['kmer_count']['launches'] == 34
+            tot += sz
+            for p in pr:
+                acc[(int(p['a']), int(p['b']))] = acc.get((int(p['a']), int(p['b'])), 0) + int(p['shared'])
+        assert list(tot) == list(osizes) and acc == opairs
+    finally:
+        api.profile_enable(False); _lib.load().vg_set_subshards(0)

@@ -2052,6 +2052,21 @@ struct max_op { __device__ __host__ uint32_t operator()(uint32_t a, uint32_t b) 
 }  // namespace
 
 static int g_force_subshards = 0;
+// The developer switches of this stage and the user's workspace budget, read once per process, when the library is loaded
+static const char* pf_switch(const char* name) { const char* e = vg_dev_getenv(name); return e ? e : ""; }
+static const struct {
+    bool radix = !strcmp(pf_switch("VG_INDEX_PATH"), "radix");            // the general (rocPRIM) path instead of the bucket pipeline
+    bool long_rec = !strcmp(pf_switch("VG_LEVEL1_RECORDS"), "long");
+    bool old_scatter = !strcmp(pf_switch("VG_DENSE_SCATTER"), "staged");
+    bool range_dense = !strcmp(pf_switch("VG_RANGE_SCATTER"), "dense");   // developer A/B
+    bool staged2 = !strcmp(pf_switch("VG_LEVEL2_SCATTER"), "staged");
+    bool scan_each = !strcmp(pf_switch("VG_SUBSHARD_SCAN"), "each");      // HASH sub-shards: a scan per pass, never the one scan of all
+    int subshards = atoi(pf_switch("VG_SUBSHARDS"));                  // developer experiments
+    int placement_trials = atoi(pf_switch("VG_PLACEMENT_TRIALS"));
+    double workspace_gb = [] { const char* e = getenv("VG_WORKSPACE_GB"); const double v = e ? atof(e) : 0.0; return v > 0.01 ? v : 8.0; }();
+} g_sw{};
+// f(K) with K = 25 as a constant (the default k has kernels of its own) or 0 (k is read from the arguments)
+template <class F> static void with_k(bool k25, F f) { if (k25) f(std::integral_constant<int, 25>{}); else f(std::integral_constant<int, 0>{}); }
 // k-mers one pass is cut for: its row numbers are 32 bits (4.29e9) and sub-sharding starts at SUB_PASS_START expected
 // k-mers.  The expectation is an upper bound (every padded position counted) and HASH shards are even to a few 10^-5; a
 // pass that overflows all the same throws VG_EOVERFLOW and the loop is retried one cut finer.  (4.2e9 per pass would
@@ -2107,56 +2122,54 @@ static void finish_sort(sorted_index& si, int k) {
 // does not depend on anything the previous sub-shard computes: the sub-shard loop launches the scan of sub-shard t + 1
 // on the second queue when sub-shard t has finished its own scan, beside t's partition / bucket / SpGEMM kernels
 // (memory- and LDS-bound).  Safe with the single-queue caching allocator: the buffers are taken while the library
-// queue is idle (run_extract_sort has just synchronised), so no block they receive has work pending on it, and they
-// are handed on to run_extract_sort(t + 1), which waits for the scan's event before anything reads them.
+// queue is idle (kmer_shared_pass: the index stage has just synchronised), so no block they receive has work pending on it,
+// and they are handed on to run_extract_sort of pass t + 1, which waits for the scan's event before anything reads them.
 struct precount {
     dbuf<int> kept; dbuf<unsigned long long> wave_mask; dbuf<uint32_t> wave_cnt; dbuf<uint64_t> stage; dbuf<unsigned int> d_over;
-    const vg_genomes* g = nullptr; int k = 0, shard = -1, n_shards = 0, stage_cap = 0; hipEvent_t done = nullptr;
+    hipEvent_t done = nullptr;                    // recorded behind the scan; null = no scan is waiting to be taken
     void drop() {
         if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); done = nullptr; }     // nothing is freed under a running scan
-        kept.release(); wave_mask.release(); wave_cnt.release(); stage.release(); d_over.release(); shard = -1; g = nullptr;
+        kept.release(); wave_mask.release(); wave_cnt.release(); stage.release(); d_over.release();
     }
     ~precount() { drop(); }
 };
-static precount g_precount;
-// the index stage's milliseconds (level-1 count ... bucket kernels) of the last pass (placement trials of vg_kmer_shared; measured only while they run)
-static bool g_time_bucket_pass = false;
-static float g_last_bucket_ms = 0.f;
 struct pass_timer {
     float* out; hipStream_t s; hipEvent_t e0 = nullptr, e1 = nullptr;
     pass_timer(float* o, hipStream_t st) : out(o), s(st) { if (out && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, s); else out = nullptr; }
     ~pass_timer() { if (!out) return; (void)hipEventRecord(e1, s); (void)hipEventSynchronize(e1); float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) *out = ms; (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
 };
-// the kept mask of the pass that is about to run, left by the sub-shard loop's one scan of all sub-shards (k_multi_mask)
-struct pass_mask { const vg_genomes* g = nullptr; int k = 0, shard = -1, n_shards = 0; const unsigned long long* mask = nullptr; };
-static pass_mask g_pass_mask;
+// What the caller of a pass knows about it and the pass cannot see from its shard numbers.  All optional.
+struct pass_inputs {
+    const unsigned long long* mask = nullptr;     // the kept mask of this pass, left by the sub-shard loop's one scan of all sub-shards (k_multi_mask)
+    precount* pre = nullptr;                      // the sub-shard loop's scan ahead: holds this pass's scan if pre->done; refilled for next_shard
+    int next_shard = -1;                          // >= 0: once the index is built, start the scan of this shard (of the same cut) into *pre
+    float* index_ms = nullptr;                    // placement trials: receives the index stage's milliseconds
+    vg_slice_exchange* xs = nullptr;              // a RANGE shard counts by sliced scan + exchange
+};
 static int compact_stage_cap(double keep) { return (int)std::min<double>(256.0, std::ceil(1.5 * 256.0 * keep) + 24.0); }
 // to be called while the library queue is idle
-static void launch_precount(vg_genomes* g, int k, int shard, int n_shards) {
-    precount& pc = g_precount;
+static void launch_precount(precount& pc, vg_genomes* g, int k, int shard, int n_shards) {
     pc.drop();
     const int64_t P = g->padded_total(), W = P / 64, n_chunks = (W + 3) / 4;
-    pc.stage_cap = compact_stage_cap(1.0 / n_shards);
+    const int stage_cap = compact_stage_cap(1.0 / n_shards);
     pc.kept.alloc((size_t)std::max(1, g->n)); pc.wave_mask.alloc((size_t)W + 1); pc.wave_cnt.alloc((size_t)W + 1);
-    pc.stage.alloc((size_t)n_chunks * pc.stage_cap); pc.d_over.alloc(1);
+    pc.stage.alloc((size_t)n_chunks * stage_cap); pc.d_over.alloc(1);
     hipStream_t side = vg_side_stream();
     pc.kept.zero(side); pc.d_over.zero(side);
     VG_HIP(hipMemsetAsync(pc.wave_cnt.p + W, 0, sizeof(uint32_t), side));
     const kmer_args A = make_kmer_args(g, k, 1.0, shard, n_shards);
-    if (k == 25) hipLaunchKernelGGL(k_kmer_count<25>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, side, A, pc.wave_mask.p, pc.wave_cnt.p, pc.kept.p, pc.stage.p, pc.stage_cap, pc.d_over.p);
-    else hipLaunchKernelGGL(k_kmer_count<0>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, side, A, pc.wave_mask.p, pc.wave_cnt.p, pc.kept.p, pc.stage.p, pc.stage_cap, pc.d_over.p);
+    with_k(k == 25, [&](auto K) { hipLaunchKernelGGL(k_kmer_count<K()>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, side, A, pc.wave_mask.p, pc.wave_cnt.p, pc.kept.p, pc.stage.p, stage_cap, pc.d_over.p); });
     VG_HIP(hipEventCreateWithFlags(&pc.done, hipEventDisableTiming));
     VG_HIP(hipEventRecord(pc.done, side));
-    pc.g = g; pc.k = k; pc.shard = shard; pc.n_shards = n_shards;
 }
 
-static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, int n_shards, sorted_index& out, bool finish = true, bool do_sort = true) {
+static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, int n_shards, const pass_inputs& in, sorted_index& out, bool finish = true, bool do_sort = true) {
     hipStream_t s = vg_stream();
     const int64_t P = g->padded_total();
-    // the scan of this very sub-shard may already be running (or done) on the second queue
-    const bool pre = g_precount.g == g && g_precount.k == k && g_precount.shard == shard && g_precount.n_shards == n_shards && !(fraction < 1.0) && n_shards > 1;
-    const unsigned long long* premask = (g_pass_mask.g == g && g_pass_mask.k == k && g_pass_mask.shard == shard && g_pass_mask.n_shards == n_shards && !pre) ? g_pass_mask.mask : nullptr;
-    if (pre) { VG_HIP(hipStreamWaitEvent(s, g_precount.done, 0)); out.kept = std::move(g_precount.kept); }
+    // the scan of this very sub-shard may already be running (or done) on the second queue; the first extraction of the pass takes it
+    precount* const pc = in.pre && in.pre->done ? in.pre : nullptr; const bool pre = pc != nullptr;
+    const unsigned long long* premask = pre ? nullptr : in.mask;
+    if (pre) { VG_HIP(hipStreamWaitEvent(s, pc->done, 0)); out.kept = std::move(pc->kept); }
     else { out.kept.alloc((size_t)std::max(1, g->n)); out.kept.zero(s); }
     const int use_frac = fraction < 1.0;
     const kmer_args A = make_kmer_args(g, k, fraction, shard, n_shards);
@@ -2184,9 +2197,9 @@ static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, i
         dbuf<uint32_t> wave_cnt; dbuf<uint64_t> stage; dbuf<unsigned int> d_over;
         out.wave_base.alloc((size_t)W + 1);
         if (pre) {
-            out.wave_mask = std::move(g_precount.wave_mask); wave_cnt = std::move(g_precount.wave_cnt);
-            stage = std::move(g_precount.stage); d_over = std::move(g_precount.d_over);
-            (void)hipEventDestroy(g_precount.done); g_precount.done = nullptr; g_precount.shard = -1; g_precount.g = nullptr;
+            out.wave_mask = std::move(pc->wave_mask); wave_cnt = std::move(pc->wave_cnt);
+            stage = std::move(pc->stage); d_over = std::move(pc->d_over);
+            (void)hipEventDestroy(pc->done); pc->done = nullptr;
         } else if (premask) {
             // the pass's kept mask exists already (one scan served every sub-shard): count its words; the k-mers are computed
             // for the kept positions only by the emit pass below
@@ -2198,15 +2211,8 @@ static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, i
             VG_HIP(hipMemsetAsync(wave_cnt.p + W, 0, sizeof(uint32_t), s));
             stage.alloc((size_t)n_chunks * stage_cap);
             d_over.alloc(1); d_over.zero(s);
-        }
-        if (!pre && !premask) {
             vg_prof_scope ps("kmer_count", (double)P * (3.0 / 8.0 + 12.0 / 64.0));
-            if (A.k == 25 && !A.use_frac)
-                hipLaunchKernelGGL(k_kmer_count<25>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, s, A, out.wave_mask.p, wave_cnt.p, out.kept.p,
-                                   stage.p, stage_cap, d_over.p);
-            else
-                hipLaunchKernelGGL(k_kmer_count<0>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, s, A, out.wave_mask.p, wave_cnt.p, out.kept.p,
-                                   stage.p, stage_cap, d_over.p);
+            with_k(A.k == 25 && !A.use_frac, [&](auto K) { hipLaunchKernelGGL(k_kmer_count<K()>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, s, A, out.wave_mask.p, wave_cnt.p, out.kept.p, stage.p, stage_cap, d_over.p); });
         }
         size_t tb = 0;
         VG_HIP(rocprim::exclusive_scan(nullptr, tb, wave_cnt.p, out.wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
@@ -2295,11 +2301,6 @@ static bool bucket_digits(int64_t n_expect, int* total_bits_out, int* B1_out, in
     *total_bits_out = total_bits; *B2_out = B2; *B1_out = total_bits - B2;
     return true;
 }
-static int g_index_path = -1;      // -1 = not read yet; 0 = radix (rocPRIM) path forced; 1 = buckets
-static bool index_path_buckets() {
-    if (g_index_path < 0) { const char* e = vg_dev_getenv("VG_INDEX_PATH"); g_index_path = (e && !strcmp(e, "radix")) ? 0 : 1; }
-    return g_index_path != 0;
-}
 // 0 = every rank of a RANGE cut scans all bases (k_part_count<.., RANGE>); 1 = sliced scan, the peers emulated by this
 // process (vg_set_range_scan: tools/strong_scaling_sim.py, tests); the sharded entry points always exchange when it applies
 static int g_range_scan_mode = 0;
@@ -2307,7 +2308,7 @@ bool vg_slice_exchange_applies(const vg_genomes* g, int k, double fraction, int 
     (void)k;
     if (world < 2 || world > SX_MAX_WORLD || g_force_subshards > 1 || !range_shards(g, fraction, world)) return false;
     const int64_t P = g->padded_total();
-    if (!index_path_buckets() || P < (1 << 16) || P >= (1LL << 32)) return false;
+    if (g_sw.radix || P < (1 << 16) || P >= (1LL << 32)) return false;
     int total_bits = 0, B1 = 0, B2 = 0;
     return bucket_digits(P, &total_bits, &B1, &B2) && total_bits > 11 && B1 == DIG_BITS;      // the level-1 digit is the shard digit
 }
@@ -2338,8 +2339,7 @@ static void sliced_count(int k, const part_src& S, vg_slice_exchange* xs, int st
         if (rows <= 0) return;
         const size_t lds = (size_t)16 * (PT_PER / 4) * W * 8 * sizeof(uint32_t);
         const int grid = (int)std::min<int64_t>(rows, 512);
-        if (k == 25 && !S.A.use_frac) hipLaunchKernelGGL(k_slice_scan<25>, dim3(grid), dim3(PT_THREADS), lds, s, S, X, st_tiles, kept);
-        else hipLaunchKernelGGL(k_slice_scan<0>, dim3(grid), dim3(PT_THREADS), lds, s, S, X, st_tiles, kept);
+        with_k(k == 25 && !S.A.use_frac, [&](auto K) { hipLaunchKernelGGL(k_slice_scan<K()>, dim3(grid), dim3(PT_THREADS), lds, s, S, X, st_tiles, kept); });
     };
     sent mine; int status = VG_OK; std::string err;
     try { vg_prof_scope ps("kmer_slice_scan", (double)S.n / W * (3.0 / 8.0 + 1.0 / 8.0)); scan(me, mine, d_kept); }
@@ -2369,338 +2369,334 @@ static void sliced_count(int k, const part_src& S, vg_slice_exchange* xs, int st
     VG_HIP(hipStreamSynchronize(s));                                 // the send buffers go out of scope
 }
 
+// The index of one pass, as the SpGEMM reads it: a row per k-mer occurrence (per base position in a dense whole pass) with a pointer
+// into gen[], the ascending genome lists of the k-mers that occur more than once.  Members in the order a pass allocates them.
+struct kmer_index {
+    sorted_index si;                                 // compact rows: the row map (wave_base, goff, cblk); general path: the sorted keys too
+    dbuf<uint32_t> arena;                            // owner of rowinfo / gen when they are windows of one block
+    dbuf<uint32_t> rowinfo, gen; dbuf<int> d_dups;
+    std::vector<int> kept, dups;                     // per genome: k-mers the pass kept, duplicates among them
+    int64_t nv = 0, n_rows_info = 0;
+    bool compact_rows = false, rows_from_map = false;      // rows are kept k-mers, not positions; a sliced scan: a genome's rows are read off goff
+    const uint32_t* wbase = nullptr;                 // compact rows: rows before every 64-position word
+};
 // ---- the bucket pipeline (see the kernels above).  Source: the packed bases themselves (dense) or the kept
 // k-mers of a shard / fraction (keys, row numbers).  Fills gen[] and rowinfo[] like k_group_runs; false = the
 // input does not suit it (tiny, skewed, a bucket beyond the LDS): the caller takes the general path.
-// set by the sub-shard loop (kmer_shared_subshards): the k-mer scan of the NEXT sub-shard, started on the second queue at
-// a point where the library queue is idle
-static std::function<void()> g_after_extract;
-static void run_scan_hook() { if (g_after_extract) { auto hook = std::move(g_after_extract); g_after_extract = nullptr; hook(); } }
-// A RANGE shard of the dense source (A.dig_n < 2^11): `ri` receives the kept masks, the row bases and the row -> genome
-// map of the pass, n_rows_info becomes the number of kept k-mers, and the row pointers are indexed by row number.
-static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_args& A, const uint64_t* keys, const uint32_t* pos, int64_t n_src,
-                                const compact_map& cmap_in, int* d_kept, dbuf<uint32_t>& gen, dbuf<uint32_t>& rowinfo, dbuf<uint32_t>& arena,
-                                int64_t& n_rows_info, int* d_dups, int64_t* n_valid_out, sorted_index* ri = nullptr, vg_slice_exchange* xs = nullptr) {
-    compact_map cmap = cmap_in;
-    const bool range = dense && A.dig_n < (1u << DIG_BITS);
-    if (range && !ri) throw vg_error(VG_EINVAL, "internal error: a range shard needs its row map");
-    hipStream_t s = vg_stream();
-    vg_host_mark("buckets: enter");
-    pass_timer index_timer(g_time_bucket_pass ? &g_last_bucket_ms : nullptr, s);       // (placement trials: count ... bucket kernels of this pass)
-    if (!index_path_buckets() || n_src < (1 << 16) || n_src >= (1LL << 32)) return false;
+// The shape of a pass's partition, a function of the source size and the shard alone.
+struct bucket_geometry {
+    bool range, big_buckets, narrow, tile32k, short_rec;
+    int total_bits, B1, B2, levels, bin_lo, nb1g, nb1, nb2, st_tiles, n_slabs; int64_t n_st, nbk;
+    lvl2_tab L2;                                     // level-2 units and (dense source, k <= 25 at 2^11 buckets) short level-1 records; pointers set by the stages
+};
+static bool bucket_geometry_for(int k, bool dense, const kmer_args& A, int64_t n_src, bucket_geometry& G) {
+    G.range = dense && A.dig_n < (1u << DIG_BITS);
+    if (g_sw.radix || n_src < (1 << 16) || n_src >= (1LL << 32)) return false;
     // elements the partition will hold (a RANGE shard holds whole buckets of the set's own partition: the digits follow from n_src)
-    const int64_t n_expect = dense && !range ? n_src / std::max<uint32_t>(1u, A.n_shards) : n_src;
-    int total_bits = 0, B1 = 0, B2 = 0;
-    if (!bucket_digits(n_expect, &total_bits, &B1, &B2)) return false;
-    const bool big_buckets = (n_expect >> total_bits) > 1024;
-    const int levels = total_bits > 11 ? 2 : 1;
-    if (range && B1 > DIG_BITS) return false;
+    const int64_t n_expect = dense && !G.range ? n_src / std::max<uint32_t>(1u, A.n_shards) : n_src;
+    if (!bucket_digits(n_expect, &G.total_bits, &G.B1, &G.B2)) return false;
+    G.big_buckets = (n_expect >> G.total_bits) > 1024; G.levels = G.total_bits > 11 ? 2 : 1;
+    if (G.range && G.B1 > DIG_BITS) return false;
     // level-1 buckets of this pass: all 2^B1, or those the RANGE shard's digits fall into
-    const int bin_lo = range ? (int)(A.dig_lo >> (DIG_BITS - B1)) : 0;
-    const int nb1g = 1 << B1, nb1 = range ? (int)(((A.dig_lo + A.dig_n - 1) >> (DIG_BITS - B1)) - (uint32_t)bin_lo + 1) : nb1g, nb2 = 1 << B2;
-    const bool narrow = levels == 2 && 2 * k - total_bits <= 32;      // level-2 output: one key word instead of two
-    part_src S; memset(&S, 0, sizeof S);
-    S.A = A; S.keys = keys; S.pos = pos; S.n = n_src; S.k2 = 2 * k; S.bin_lo = bin_lo;
-    int st_tiles = (int)std::max<int64_t>(1, std::min<int64_t>(dense ? 16 : 8, n_src / ((int64_t)PT_TILE * 2048)));
-    if (dense && st_tiles >= 4) st_tiles &= ~3;             // whole 32 768-position tiles for k_part_scatter_dense
-    const int64_t n_st = (n_src + (int64_t)st_tiles * PT_TILE - 1) / ((int64_t)st_tiles * PT_TILE);
-    const size_t t1n = (size_t)nb1 * (size_t)n_st;
-    dbuf<uint32_t> T1s(t1n + 1);                              // counts [super-tile][bucket], scanned in place
-    const int n_slabs = (int)((n_st + SC_SLAB - 1) / SC_SLAB);
-    dbuf<uint32_t> slab((size_t)n_slabs * nb1), d_off1((size_t)nb1 + 1);
-    dbuf<uint32_t> a_rec, b_rec;
-    uint32_t n1 = 0; size_t n_cap = 0;                        // records of this pass; capacity its record buffers are sized for
-    // The row pointers start as zeros (only the later members of a run get one): 15 GB at 100 k genomes, 2.7 ms of
-    // fill.  With room to spare (they otherwise move into the level-1 record buffer once level 2 has read it) they get
-    // their own block, cleared on the side queue beside the k-mer kernels of level 1, which are bound by arithmetic.
-    hipEvent_t ev_rows_zero = nullptr;
-    // (whatever way the function is left: everything that touches the block later is queued on s behind the clear)
-    struct ev_guard { hipEvent_t& e; hipStream_t st; ~ev_guard() { if (e) { (void)hipStreamWaitEvent(st, e, 0); (void)hipEventDestroy(e); } } } ev_g{ ev_rows_zero, s };
-    // (dense single-pass sets only, whose whole workspace is a fraction of the HBM: with sub-shards of 10^6 contigs the
-    // extra 14 GB block pushed the caching allocator into trims and fresh hipMallocs -- 8.2 s per pass instead of 2.7)
-    if (levels == 2 && dense && !range) {
-        // (the device's total memory: asked once -- hipMemGetInfo is a driver round trip on every pass otherwise)
-        static const size_t tot = [] { size_t fr0 = 0, t0 = 0; return hipMemGetInfo(&fr0, &t0) == hipSuccess ? t0 : (size_t)0; }();
-        if (tot && (size_t)n_rows_info * 4 * 8 <= tot / 2) try {
-            { vg_dev_try_scope opportunistic; rowinfo.alloc((size_t)n_rows_info); }
-            hipStream_t side = vg_side_stream();
-            hipEvent_t ev_s = nullptr;
-            VG_HIP(hipEventCreateWithFlags(&ev_s, hipEventDisableTiming));
-            VG_HIP(hipEventRecord(ev_s, s));                   // (the block may have just been handed back by work still queued on s)
-            VG_HIP(hipStreamWaitEvent(side, ev_s, 0));
-            (void)hipEventDestroy(ev_s);
-            VG_HIP(hipMemsetAsync(rowinfo.p, 0, (size_t)n_rows_info * sizeof(uint32_t), side));
-            VG_HIP(hipEventCreateWithFlags(&ev_rows_zero, hipEventDisableTiming));
-            VG_HIP(hipEventRecord(ev_rows_zero, side));
-        } catch (...) {
-            // (an optimisation only: the row pointers then live in the level-1 record buffer and are cleared in line)
-            (void)hipGetLastError(); (void)hipDeviceSynchronize();
-            if (ev_rows_zero) { (void)hipEventDestroy(ev_rows_zero); ev_rows_zero = nullptr; }
-            rowinfo.release();
-        } else (void)hipGetLastError();
-    }
-    // level-2 units and (dense source, k <= 25 at 2^11 buckets) short level-1 records, see lvl2_tab
-    lvl2_tab L2; memset(&L2, 0, sizeof L2);
-    const int64_t st_pos = (int64_t)st_tiles * PT_TILE;
-    L2.T1s = T1s.p; L2.n_st = n_st; L2.off1 = d_off1.p; L2.nb1 = nb1;
-    L2.u_st = (int)std::max<int64_t>(1, std::min<int64_t>(n_st, (65536LL * nb1g) / st_pos));
-    L2.n_u = (int)((n_st + L2.u_st - 1) / L2.u_st);
-    L2.kr = 2 * k - B1;
+    G.bin_lo = G.range ? (int)(A.dig_lo >> (DIG_BITS - G.B1)) : 0;
+    G.nb1g = 1 << G.B1; G.nb2 = 1 << G.B2;
+    G.nb1 = G.range ? (int)(((A.dig_lo + A.dig_n - 1) >> (DIG_BITS - G.B1)) - (uint32_t)G.bin_lo + 1) : G.nb1g;
+    G.nbk = G.levels == 1 ? G.nb1 : (int64_t)G.nb1 * G.nb2;
+    G.narrow = G.levels == 2 && 2 * k - G.total_bits <= 32;      // level-2 output: one key word instead of two
+    G.st_tiles = (int)std::max<int64_t>(1, std::min<int64_t>(dense ? 16 : 8, n_src / ((int64_t)PT_TILE * 2048)));
+    if (dense && G.st_tiles >= 4) G.st_tiles &= ~3;             // whole 32 768-position tiles for k_part_scatter_dense
+    const int64_t st_pos = (int64_t)G.st_tiles * PT_TILE;
+    G.n_st = (n_src + st_pos - 1) / st_pos; G.n_slabs = (int)((G.n_st + SC_SLAB - 1) / SC_SLAB);
+    lvl2_tab& L2 = G.L2; memset(&L2, 0, sizeof L2);
+    L2.n_st = G.n_st; L2.nb1 = G.nb1; L2.kr = 2 * k - G.B1;
+    L2.u_st = (int)std::max<int64_t>(1, std::min<int64_t>(G.n_st, (65536LL * G.nb1g) / st_pos)); L2.n_u = (int)((G.n_st + L2.u_st - 1) / L2.u_st);
     { int sh = 0; while ((1LL << sh) < st_pos) ++sh; L2.st_shift = sh; }
-    static const bool long_rec = [] { const char* e = vg_dev_getenv("VG_LEVEL1_RECORDS"); return e && !strcmp(e, "long"); }();
-    static const bool old_scatter = [] { const char* e = vg_dev_getenv("VG_DENSE_SCATTER"); return e && !strcmp(e, "staged"); }();
-    const bool tile32k = dense && st_tiles % 4 == 0 && B1 <= 12 && !old_scatter;          // k_part_scatter_dense applies
-    bool short_rec = levels == 2 && tile32k && narrow && B2 <= 11 && L2.kr + SR_POS_BITS <= 64 && L2.kr - B2 >= 1 &&
-                     (st_pos & (st_pos - 1)) == 0 && st_pos <= (1LL << SR_POS_BITS) && !long_rec;
-    if (short_rec) {
+    G.tile32k = dense && G.st_tiles % 4 == 0 && G.B1 <= 12 && !g_sw.old_scatter;          // k_part_scatter_dense applies
+    G.short_rec = G.levels == 2 && G.tile32k && G.narrow && G.B2 <= 11 && L2.kr + SR_POS_BITS <= 64 && L2.kr - G.B2 >= 1 &&
+                  (st_pos & (st_pos - 1)) == 0 && st_pos <= (1LL << SR_POS_BITS) && !g_sw.long_rec;
+    if (G.short_rec) {
         const int64_t g_st = (1LL << SR_POS_BITS) / st_pos;                       // super-tiles per position group
         if (L2.u_st <= g_st) L2.g_st = (g_st % L2.u_st == 0) ? 0 : -1;            // a unit inside one group
         else L2.g_st = (L2.u_st % g_st == 0 && L2.u_st / g_st <= 4) ? (int)g_st : -1;
-        if (L2.g_st < 0) { short_rec = false; L2.g_st = 0; }
+        if (L2.g_st < 0) { G.short_rec = false; L2.g_st = 0; }
     }
+    return true;
+}
+// One run of the pipeline: what the stages below share.  The buffers are members in the order the stages allocate them.
+struct bucket_run {
+    vg_genomes* g; int k; bool dense; const pass_inputs& in; kmer_index& ix; int* d_kept; hipStream_t s;
+    bucket_geometry G; part_src S; compact_map cmap;
+    bool k25 = false; uint32_t n1 = 0; size_t n_cap = 0;      // the default (kernels with k as a constant); records of this pass; capacity its record buffers are sized for
+    const uint32_t* f_rec = nullptr; int f_stride = 3;        // the records the bucket kernels read
+    dbuf<uint32_t> T1s, slab, d_off1, a_rec, b_rec;           // T1s: counts [super-tile][bucket], scanned in place
+    // (whatever way the run is left: everything that touches the row pointers' own block later is queued on s behind its clear)
+    struct ev_guard { hipEvent_t e = nullptr; hipStream_t st; ~ev_guard() { if (e) { (void)hipStreamWaitEvent(st, e, 0); (void)hipEventDestroy(e); } } } rows_zero;
+    dbuf<uint32_t> boff;
+};
+struct level1_tmp { std::optional<vg_prof_scope> ps; dbuf<uint32_t> wave_cnt; dbuf<char> scan_tmp; };      // level 1, count to queued scatter: its scope, what the scan reads
+// The row pointers start as zeros (only the later members of a run get one): 15 GB at 100 k genomes, 2.7 ms of
+// fill.  With room to spare (they otherwise move into the level-1 record buffer once level 2 has read it) they get
+// their own block, cleared on the side queue beside the k-mer kernels of level 1, which are bound by arithmetic.
+// (dense single-pass sets only, whose whole workspace is a fraction of the HBM: with sub-shards of 10^6 contigs the
+// extra 14 GB block pushed the caching allocator into trims and fresh hipMallocs -- 8.2 s per pass instead of 2.7)
+static void clear_rows_aside(bucket_run& R) {
+    if (!(R.G.levels == 2 && R.dense && !R.G.range)) return;
+    dbuf<uint32_t>& rowinfo = R.ix.rowinfo; const int64_t n_rows_info = R.ix.n_rows_info; hipEvent_t& ev_rows_zero = R.rows_zero.e;
+    // (the device's total memory: asked once -- hipMemGetInfo is a driver round trip on every pass otherwise)
+    static const size_t tot = [] { size_t fr0 = 0, t0 = 0; return hipMemGetInfo(&fr0, &t0) == hipSuccess ? t0 : (size_t)0; }();
+    if (tot && (size_t)n_rows_info * 4 * 8 <= tot / 2) try {
+        { vg_dev_try_scope opportunistic; rowinfo.alloc((size_t)n_rows_info); }
+        hipStream_t side = vg_side_stream();
+        hipEvent_t ev_s = nullptr;
+        VG_HIP(hipEventCreateWithFlags(&ev_s, hipEventDisableTiming));
+        VG_HIP(hipEventRecord(ev_s, R.s));                 // (the block may have just been handed back by work still queued on s)
+        VG_HIP(hipStreamWaitEvent(side, ev_s, 0));
+        (void)hipEventDestroy(ev_s);
+        VG_HIP(hipMemsetAsync(rowinfo.p, 0, (size_t)n_rows_info * sizeof(uint32_t), side));
+        VG_HIP(hipEventCreateWithFlags(&ev_rows_zero, hipEventDisableTiming));
+        VG_HIP(hipEventRecord(ev_rows_zero, side));
+    } catch (...) {
+        // (an optimisation only: the row pointers then live in the level-1 record buffer and are cleared in line)
+        (void)hipGetLastError(); (void)hipDeviceSynchronize();
+        if (ev_rows_zero) { (void)hipEventDestroy(ev_rows_zero); ev_rows_zero = nullptr; }
+        rowinfo.release();
+    } else (void)hipGetLastError();
+}
+// Level-1 count (dense, RANGE, sliced or arrays), the column scan and the pass's record count.  A RANGE shard also gets its
+// row map here.  false = no valid k-mer at all: empty outputs are in place and the run is over.
+static bool level1_count(bucket_run& R, level1_tmp& t) {
+    const bucket_geometry& G = R.G; part_src& S = R.S; sorted_index& ri = R.ix.si; hipStream_t s = R.s;
+    vg_slice_exchange* xs = G.range ? R.in.xs : nullptr;
+    // (a sliced scan and its exchange have scopes of their own: kmer_slice_scan, exchange)
+    const double part_bytes = (double)S.n * (R.dense ? 2 * 3.0 / 8.0 : 8.0 + 12.0) + (double)S.n * (G.short_rec ? 8.0 : 12.0);
+    if (!xs) t.ps.emplace("kmer_partition", part_bytes);
+    const int grid_c = (int)std::min<int64_t>(G.n_st, 512); const int64_t W = S.n / 64;
+    if (G.range) {
+        ri.compact = true;
+        ri.wave_mask.alloc((size_t)W + 1); ri.wave_base.alloc((size_t)W + 1); t.wave_cnt.alloc((size_t)W + 1);
+        VG_HIP(hipMemsetAsync(t.wave_cnt.p + W, 0, sizeof(uint32_t), s));
+    }
+    if (xs) {
+        if (G.levels != 2 || G.B1 != DIG_BITS) throw vg_error(VG_EINVAL, "internal error: sliced scan without the shard digit as level-1 digit");
+        sliced_count(R.k, S, xs, G.st_tiles, G.n_st, G.nb1, R.T1s.p, ri.wave_mask.p, t.wave_cnt.p, R.d_kept, R.g->n, s);
+        t.ps.emplace("kmer_partition", part_bytes / xs->world);
+    }
+    else if (R.dense) with_k(R.k25, [&](auto K) {
+        if (G.range) hipLaunchKernelGGL((k_part_count<SRC_DENSE, K(), true>), dim3(grid_c), dim3(PT_THREADS), 0, s, S, G.B1, G.nb1, G.st_tiles, G.n_st, R.T1s.p, R.d_kept, ri.wave_mask.p, t.wave_cnt.p);
+        else hipLaunchKernelGGL((k_part_count<SRC_DENSE, K()>), dim3(grid_c), dim3(PT_THREADS), 0, s, S, G.B1, G.nb1, G.st_tiles, G.n_st, R.T1s.p, R.d_kept, nullptr, nullptr);
+    });
+    else hipLaunchKernelGGL(k_part_count<SRC_ARRAYS>, dim3(grid_c), dim3(PT_THREADS), 0, s, S, G.B1, G.nb1, G.st_tiles, G.n_st, R.T1s.p, nullptr, nullptr, nullptr);
+    if (G.range) {
+        // rows before every 64-position word (the payloads of the level-1 records and the SpGEMM's row ranges)
+        size_t tb = 0;
+        VG_HIP(rocprim::exclusive_scan(nullptr, tb, t.wave_cnt.p, ri.wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
+        t.scan_tmp.alloc(tb);
+        VG_HIP(rocprim::exclusive_scan((void*)t.scan_tmp.p, tb, t.wave_cnt.p, ri.wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
+        S.wmask = ri.wave_mask.p; S.wbase = ri.wave_base.p; R.G.L2.wbase = ri.wave_base.p; R.G.L2.W = W;
+    }
+    // counts -> write offsets, in place (see k_scan_columns_*)
+    hipLaunchKernelGGL(k_scan_columns_a, dim3(G.n_slabs), dim3(PT_THREADS), 0, s, (const uint32_t*)R.T1s.p, G.n_st, G.nb1, R.slab.p);
+    hipLaunchKernelGGL(k_scan_columns_b, dim3(1), dim3(PT_THREADS), 0, s, R.slab.p, G.n_slabs, G.nb1, R.d_off1.p);
+    hipLaunchKernelGGL(k_scan_columns_c, dim3(G.n_slabs), dim3(PT_THREADS), 0, s, R.T1s.p, G.n_st, G.nb1, (const uint32_t*)R.slab.p);
+    vg_host_mark("buckets: count+scan queued");
+    VG_HIP(hipMemcpyAsync(&R.n1, R.d_off1.p + G.nb1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VG_HIP(hipStreamSynchronize(s));
+    vg_host_mark("buckets: count+scan done");
+    const uint32_t n1 = R.n1; R.n_cap = (size_t)n1; if (R.dense) R.ix.nv = (int64_t)n1;
+    if (G.range) {
+        R.ix.n_rows_info = std::max<int64_t>((int64_t)n1, 1);
+        ri.n_valid = (int64_t)n1;
+        ri.cblk.alloc((size_t)(n1 >> CBLK_SHIFT) + 2); ri.cblk.zero(s);
+        ri.goff.alloc((size_t)R.g->n + 1);
+        hipLaunchKernelGGL(k_cblk, dim3(grid_for(R.g->n)), dim3(256), 0, s, (const uint32_t*)ri.wave_base.p, R.g->d_base_off.p, R.g->n, ri.cblk.p, ri.goff.p);
+        R.cmap = compact_map{ ri.goff.p, ri.cblk.p };
+    }
+    if (n1 > 0) return true;
+    // no valid k-mer at all (every record shorter than k, or all N): empty outputs the SpGEMM can read
+    if (!R.rows_zero.e) { R.ix.rowinfo.alloc((size_t)R.ix.n_rows_info); R.ix.rowinfo.zero(s); }
+    R.ix.gen.alloc(4); R.ix.gen.zero(s);
+    return false;
+}
+// Level-1 scatter into a_rec.  Two levels: the level-1 records are dead once level 2 has scattered them, and the genome
+// list + row descriptors are born after that: they take over the same block (48 GB less to allocate at 100 k genomes).
+static void level1_scatter(bucket_run& R) {
+    const bucket_geometry& G = R.G; const part_src& S = R.S; const kmer_args& A = S.A; hipStream_t s = R.s;
+    // (the passes of a RANGE sub-shard loop ask for the same sizes, so that each finds the previous pass's blocks in the
+    // allocator's cache: sized for the widest digit range of the loop plus a margin, not for this pass's exact count)
+    if (G.range) R.n_cap = std::max<size_t>((size_t)R.n1, (size_t)((double)S.n * A.dig_max / (double)(1u << DIG_BITS) * 1.01) + 65536);
+    const size_t n_cap = R.n_cap, rows_cap = G.range ? n_cap : (size_t)R.ix.n_rows_info;
+    R.a_rec.alloc(G.levels == 2 ? std::max((G.short_rec ? 2 : 3) * n_cap + 8, rows_cap + n_cap + 16) : 3 * n_cap + 8);
+    const int grid_s = (int)std::min<int64_t>(G.n_st, 256);
+    const uint32_t* T1s = R.T1s.p; uint32_t* a_rec = R.a_rec.p;
+    const int tsh = G.short_rec ? G.L2.kr : 0;
+    // (two tiles at a time when the shard keeps a sixth of the positions or less: their kept k-mers fit one list)
+    const bool tile64k = G.st_tiles % 8 == 0 && (uint64_t)A.dig_n * 6 <= (1u << DIG_BITS);
+    if (G.tile32k && G.range && G.nb1 <= RG_MAXBINS && !g_sw.range_dense) {
+        const bool kc = R.k == 25 && !A.use_frac;
+        if (tile64k) with_k(kc, [&](auto K) { hipLaunchKernelGGL((k_part_scatter_range<K(), 65536>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, G.B1, G.nb1, G.st_tiles / 8, G.n_st, T1s, a_rec, tsh); });
+        else with_k(kc, [&](auto K) { hipLaunchKernelGGL((k_part_scatter_range<K(), 32768>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, G.B1, G.nb1, G.st_tiles / 4, G.n_st, T1s, a_rec, tsh); });
+    }
+    else if (G.tile32k) with_k(R.k25 && !G.range, [&](auto K) { hipLaunchKernelGGL(k_part_scatter_dense<K()>, dim3(grid_s), dim3(PT_THREADS), 0, s, S, G.B1, G.nb1, G.st_tiles / 4, G.n_st, T1s, a_rec, tsh); });
+    else if (R.dense) hipLaunchKernelGGL((k_part_scatter<SRC_DENSE, 1>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, G.B1, 0, G.st_tiles, G.n_st, T1s, lvl2_tab{}, a_rec, -1, G.nb1);
+    else hipLaunchKernelGGL((k_part_scatter<SRC_ARRAYS, 1>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, G.B1, 0, G.st_tiles, G.n_st, T1s, lvl2_tab{}, a_rec, -1, G.nb1);
+}
+// Level 2 on units of u_st super-tiles of one level-1 bucket (see lvl2_tab): everything it needs is in the scanned level-1
+// table, so it is launched right behind level 1.  Leaves the final records in b_rec and hands a_rec on as the arena.
+static void level2(bucket_run& R) {
+    const bucket_geometry& G = R.G; const lvl2_tab& L2 = G.L2; hipStream_t s = R.s; kmer_index& ix = R.ix;
+    const int64_t n_units = (int64_t)G.nb1 * L2.n_u;
+    const size_t t2n = (size_t)G.nb1 * (size_t)G.nb2 * (size_t)L2.n_u;
+    dbuf<uint32_t> T2s(t2n);                              // counts [bucket][unit][b2], scanned in place
+    const uint32_t* a_rec = R.a_rec.p;
     {
-        // (a sliced scan and its exchange have scopes of their own: kmer_slice_scan, exchange)
-        const double part_bytes = (double)n_src * (dense ? 2 * 3.0 / 8.0 : 8.0 + 12.0) + (double)n_src * (short_rec ? 8.0 : 12.0);
-        std::optional<vg_prof_scope> ps;
-        if (!(range && xs)) ps.emplace("kmer_partition", part_bytes);
-        const int grid_c = (int)std::min<int64_t>(n_st, 512);
-        const bool k25 = dense && k == 25 && !A.use_frac && A.n_shards == 1;          // the default: kernels with k as a constant
-        unsigned long long* no_mask = nullptr; uint32_t* no_cnt = nullptr;
-        dbuf<uint32_t> wave_cnt;
-        const int64_t W = n_src / 64;
-        if (range) {
-            ri->compact = true;
-            ri->wave_mask.alloc((size_t)W + 1); ri->wave_base.alloc((size_t)W + 1); wave_cnt.alloc((size_t)W + 1);
-            VG_HIP(hipMemsetAsync(wave_cnt.p + W, 0, sizeof(uint32_t), s));
+        vg_prof_scope ps("kmer_partition2", (double)R.n1 * (4.0 + (G.short_rec ? 8.0 : 12.0) + (G.narrow ? 8.0 : 12.0)));
+        const int grid_c2 = (int)std::min<int64_t>(n_units, 512);
+        hipLaunchKernelGGL(G.short_rec ? k_part_count2<true> : k_part_count2<false>, dim3(grid_c2), dim3(PT_THREADS), 0, s, a_rec, G.B1, G.B2, n_units, L2, T2s.p);
+        hipLaunchKernelGGL(k_scan_units, dim3(G.nb1), dim3(PT_THREADS), 0, s, T2s.p, L2.n_u, G.nb2, (const uint32_t*)R.d_off1.p, G.nb1, R.boff.p);
+        R.b_rec.alloc((G.narrow ? 2 : 3) * R.n_cap + 8);
+        const int grid_s2 = (int)std::min<int64_t>(n_units, 256);
+        if (G.short_rec || (G.narrow && G.B2 <= 11 && !g_sw.staged2))
+            hipLaunchKernelGGL(G.short_rec ? k_part_scatter2_narrow<true> : k_part_scatter2_narrow<false>, dim3(grid_s2), dim3(PT_THREADS), 0, s, a_rec, G.B1, G.B2, n_units,
+                               (const uint32_t*)T2s.p, L2, R.b_rec.p, G.total_bits);
+        else {
+            part_src S2; memset(&S2, 0, sizeof S2);
+            S2.rec = a_rec; S2.n = (int64_t)R.n1; S2.k2 = 2 * R.k;
+            hipLaunchKernelGGL((k_part_scatter<SRC_PLANES, 2>), dim3(grid_s2), dim3(PT_THREADS), 0, s, S2, G.B1, G.B2, 0, n_units,
+                               (const uint32_t*)T2s.p, L2, R.b_rec.p, G.narrow ? G.total_bits : -1, 0);
         }
-        if (range && xs) {
-            if (levels != 2 || B1 != DIG_BITS) throw vg_error(VG_EINVAL, "internal error: sliced scan without the shard digit as level-1 digit");
-            sliced_count(k, S, xs, st_tiles, n_st, nb1, T1s.p, ri->wave_mask.p, wave_cnt.p, d_kept, g->n, s);
-            ps.emplace("kmer_partition", part_bytes / xs->world);
-        }
-        else if (k25 && range) hipLaunchKernelGGL((k_part_count<SRC_DENSE, 25, true>), dim3(grid_c), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles, n_st, T1s.p, d_kept, ri->wave_mask.p, wave_cnt.p);
-        else if (k25) hipLaunchKernelGGL((k_part_count<SRC_DENSE, 25>), dim3(grid_c), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles, n_st, T1s.p, d_kept, no_mask, no_cnt);
-        else if (dense && range) hipLaunchKernelGGL((k_part_count<SRC_DENSE, 0, true>), dim3(grid_c), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles, n_st, T1s.p, d_kept, ri->wave_mask.p, wave_cnt.p);
-        else if (dense) hipLaunchKernelGGL(k_part_count<SRC_DENSE>, dim3(grid_c), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles, n_st, T1s.p, d_kept, no_mask, no_cnt);
-        else hipLaunchKernelGGL(k_part_count<SRC_ARRAYS>, dim3(grid_c), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles, n_st, T1s.p, (int*)nullptr, no_mask, no_cnt);
-        dbuf<char> scan_tmp;
-        if (range) {
-            // rows before every 64-position word (the payloads of the level-1 records and the SpGEMM's row ranges)
-            size_t tb = 0;
-            VG_HIP(rocprim::exclusive_scan(nullptr, tb, wave_cnt.p, ri->wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
-            scan_tmp.alloc(tb);
-            VG_HIP(rocprim::exclusive_scan((void*)scan_tmp.p, tb, wave_cnt.p, ri->wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
-            S.wmask = ri->wave_mask.p; S.wbase = ri->wave_base.p; L2.wbase = ri->wave_base.p; L2.W = W;
-        }
-        // counts -> write offsets, in place (see k_scan_columns_*)
-        hipLaunchKernelGGL(k_scan_columns_a, dim3(n_slabs), dim3(PT_THREADS), 0, s, (const uint32_t*)T1s.p, n_st, nb1, slab.p);
-        hipLaunchKernelGGL(k_scan_columns_b, dim3(1), dim3(PT_THREADS), 0, s, slab.p, n_slabs, nb1, d_off1.p);
-        hipLaunchKernelGGL(k_scan_columns_c, dim3(n_slabs), dim3(PT_THREADS), 0, s, T1s.p, n_st, nb1, (const uint32_t*)slab.p);
-        vg_host_mark("buckets: count+scan queued");
-        VG_HIP(hipMemcpyAsync(&n1, d_off1.p + nb1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        VG_HIP(hipStreamSynchronize(s));
-        vg_host_mark("buckets: count+scan done");
-        *n_valid_out = (int64_t)n1; n_cap = (size_t)n1;
-        if (range) {
-            n_rows_info = std::max<int64_t>((int64_t)n1, 1);
-            ri->n_valid = (int64_t)n1;
-            ri->cblk.alloc((size_t)(n1 >> CBLK_SHIFT) + 2); ri->cblk.zero(s);
-            ri->goff.alloc((size_t)g->n + 1);
-            hipLaunchKernelGGL(k_cblk, dim3(grid_for(g->n)), dim3(256), 0, s, (const uint32_t*)ri->wave_base.p, g->d_base_off.p, g->n, ri->cblk.p, ri->goff.p);
-            cmap = compact_map{ ri->goff.p, ri->cblk.p };
-        }
-        if (n1 == 0) {
-            // no valid k-mer at all (every record shorter than k, or all N): empty outputs the SpGEMM can read
-            if (!ev_rows_zero) { rowinfo.alloc((size_t)n_rows_info); rowinfo.zero(s); }
-            gen.alloc(4); gen.zero(s);
-            return true;
-        }
-        // two levels: the level-1 records are dead once level 2 has scattered them, and the genome list + row
-        // descriptors are born after that: they take over the same block (48 GB less to allocate at 100 k genomes)
-        // (the passes of a RANGE sub-shard loop ask for the same sizes, so that each finds the previous pass's blocks in the
-        // allocator's cache: sized for the widest digit range of the loop plus a margin, not for this pass's exact count)
-        if (range) n_cap = std::max<size_t>((size_t)n1, (size_t)((double)n_src * A.dig_max / (double)(1u << DIG_BITS) * 1.01) + 65536);
-        const size_t rows_cap = range ? n_cap : (size_t)n_rows_info;
-        a_rec.alloc(levels == 2 ? std::max((short_rec ? 2 : 3) * n_cap + 8, rows_cap + n_cap + 16) : 3 * n_cap + 8);
-        const int grid_s = (int)std::min<int64_t>(n_st, 256);
-        static const bool range_dense = [] { const char* e = vg_dev_getenv("VG_RANGE_SCATTER"); return e && !strcmp(e, "dense"); }();      // developer A/B
-        // (two tiles at a time when the shard keeps a sixth of the positions or less: their kept k-mers fit one list)
-        const bool tile64k = st_tiles % 8 == 0 && (uint64_t)A.dig_n * 6 <= (1u << DIG_BITS);
-        if (tile32k && range && nb1 <= RG_MAXBINS && !range_dense) {
-            const int tsh = short_rec ? L2.kr : 0;
-            if (tile64k) {
-                if (k == 25 && !A.use_frac) hipLaunchKernelGGL((k_part_scatter_range<25, 65536>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles / 8, n_st, (const uint32_t*)T1s.p, a_rec.p, tsh);
-                else hipLaunchKernelGGL((k_part_scatter_range<0, 65536>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles / 8, n_st, (const uint32_t*)T1s.p, a_rec.p, tsh);
-            } else {
-                if (k == 25 && !A.use_frac) hipLaunchKernelGGL((k_part_scatter_range<25, 32768>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles / 4, n_st, (const uint32_t*)T1s.p, a_rec.p, tsh);
-                else hipLaunchKernelGGL((k_part_scatter_range<0, 32768>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles / 4, n_st, (const uint32_t*)T1s.p, a_rec.p, tsh);
-            }
-        }
-        else if (tile32k)
-            if (k25 && !range) hipLaunchKernelGGL(k_part_scatter_dense<25>, dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles / 4, n_st, (const uint32_t*)T1s.p, a_rec.p,
-                                        short_rec ? L2.kr : 0);
-            else hipLaunchKernelGGL(k_part_scatter_dense<0>, dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, nb1, st_tiles / 4, n_st, (const uint32_t*)T1s.p, a_rec.p,
-                                    short_rec ? L2.kr : 0);
-        else if (dense) hipLaunchKernelGGL((k_part_scatter<SRC_DENSE, 1>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, 0, st_tiles, n_st, (const uint32_t*)T1s.p,
-                                      lvl2_tab{}, a_rec.p, -1, nb1);
-        else hipLaunchKernelGGL((k_part_scatter<SRC_ARRAYS, 1>), dim3(grid_s), dim3(PT_THREADS), 0, s, S, B1, 0, st_tiles, n_st, (const uint32_t*)T1s.p,
-                                lvl2_tab{}, a_rec.p, -1, nb1);
     }
-    const int64_t nbk = levels == 1 ? nb1 : (int64_t)nb1 * nb2;
-    dbuf<uint32_t> boff((size_t)nbk + 1);
-    const uint32_t* f_rec = a_rec.p; int f_stride = 3;
-    if (levels == 1) {
-        VG_HIP(hipMemcpyAsync(boff.p, d_off1.p, ((size_t)nb1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));     // the level-1 buckets are the final ones
-    } else {
-        // level 2 on units of u_st super-tiles of one level-1 bucket (see lvl2_tab): everything it needs is in the
-        // scanned level-1 table, so it is launched right behind level 1
-        const int64_t n_units = (int64_t)nb1 * L2.n_u;
-        const size_t t2n = (size_t)nb1 * (size_t)nb2 * (size_t)L2.n_u;
-        dbuf<uint32_t> T2s(t2n);                              // counts [bucket][unit][b2], scanned in place
-        {
-            vg_prof_scope ps("kmer_partition2", (double)n1 * (4.0 + (short_rec ? 8.0 : 12.0) + (narrow ? 8.0 : 12.0)));
-            const int grid_c2 = (int)std::min<int64_t>(n_units, 512);
-            if (short_rec) hipLaunchKernelGGL(k_part_count2<true>, dim3(grid_c2), dim3(PT_THREADS), 0, s, (const uint32_t*)a_rec.p, B1, B2, n_units, L2, T2s.p);
-            else hipLaunchKernelGGL(k_part_count2<false>, dim3(grid_c2), dim3(PT_THREADS), 0, s, (const uint32_t*)a_rec.p, B1, B2, n_units, L2, T2s.p);
-            hipLaunchKernelGGL(k_scan_units, dim3(nb1), dim3(PT_THREADS), 0, s, T2s.p, L2.n_u, nb2, (const uint32_t*)d_off1.p, nb1, boff.p);
-            b_rec.alloc((narrow ? 2 : 3) * n_cap + 8);
-            static const bool staged2 = [] { const char* e = vg_dev_getenv("VG_LEVEL2_SCATTER"); return e && !strcmp(e, "staged"); }();
-            const int grid_s2 = (int)std::min<int64_t>(n_units, 256);
-            if (short_rec)
-                hipLaunchKernelGGL(k_part_scatter2_narrow<true>, dim3(grid_s2), dim3(PT_THREADS), 0, s, (const uint32_t*)a_rec.p, B1, B2, n_units,
-                                   (const uint32_t*)T2s.p, L2, b_rec.p, total_bits);
-            else if (narrow && B2 <= 11 && !staged2)
-                hipLaunchKernelGGL(k_part_scatter2_narrow<false>, dim3(grid_s2), dim3(PT_THREADS), 0, s, (const uint32_t*)a_rec.p, B1, B2, n_units,
-                                   (const uint32_t*)T2s.p, L2, b_rec.p, total_bits);
-            else {
-                part_src S2; memset(&S2, 0, sizeof S2);
-                S2.rec = a_rec.p; S2.n = (int64_t)n1; S2.k2 = 2 * k;
-                hipLaunchKernelGGL((k_part_scatter<SRC_PLANES, 2>), dim3(grid_s2), dim3(PT_THREADS), 0, s, S2, B1, B2, 0, n_units,
-                                   (const uint32_t*)T2s.p, L2, b_rec.p, narrow ? total_bits : -1, 0);
-            }
-        }
-        VG_HIP(hipStreamSynchronize(s));                       // the tables and level-1 records go out of scope below
-        vg_host_mark("buckets: level 2 done");
-        // (the library queue is idle here too.  Starting the scan of the next HASH sub-shard HERE, beside the bucket kernel,
-        // instead of in front of the SpGEMM was measured at 10^6 contigs once the SpGEMM had dropped to 16 ms and no longer
-        // covered the 52 ms scan: 2 502 against 2 458 ms per step -- the bucket kernel takes 86 ms instead of 55 beside it;
-        // the scan's arithmetic is additive wherever it runs: it starts in front of the SpGEMM.)
-        vg_deferred_start();                                  // (the bucket kernel and the SpGEMM are the long waits of the call)
-        f_rec = b_rec.p; f_stride = narrow ? 2 : 3;
-        arena = std::move(a_rec);
-        if (!ev_rows_zero) rowinfo.view(arena.p, (size_t)n_rows_info);
-        gen.view(arena.p + (((size_t)n_rows_info + 3) & ~(size_t)3), (size_t)n1 + 4);
-    }
-    if (gen.n < (size_t)n1 + 4) gen.alloc((size_t)n1 + 4);
-    if (rowinfo.n < (size_t)n_rows_info) rowinfo.alloc((size_t)n_rows_info);      // (one level: nothing to take over)
-    // ordinary buckets (mean <= 1 024): 256 threads, 9-bit sub-bins.  A bucket beyond the 1 536 entries that variant
-    // takes (k-mers shared by dozens of genomes) is queued for the 1 024-thread variant (6 144 entries, 11-bit
-    // sub-bins); what that one cannot take either (a k-mer occurring many hundreds of times) goes to k_bucket_big.
-    // Every bucket is finished by exactly one of the three: nothing is redone, nothing leaves the own pipeline.
+    VG_HIP(hipStreamSynchronize(s));                       // the tables and level-1 records go out of scope below
+    vg_host_mark("buckets: level 2 done");
+    vg_deferred_start();                                  // (the bucket kernel and the SpGEMM are the long waits of the call)
+    R.f_rec = R.b_rec.p; R.f_stride = G.narrow ? 2 : 3;
+    ix.arena = std::move(R.a_rec);
+    if (!R.rows_zero.e) ix.rowinfo.view(ix.arena.p, (size_t)ix.n_rows_info);
+    ix.gen.view(ix.arena.p + (((size_t)ix.n_rows_info + 3) & ~(size_t)3), (size_t)R.n1 + 4);
+}
+// ordinary buckets (mean <= 1 024): 256 threads, 9-bit sub-bins.  A bucket beyond the 1 536 entries that variant
+// takes (k-mers shared by dozens of genomes) is queued for the 1 024-thread variant (6 144 entries, 11-bit
+// sub-bins); what that one cannot take either (a k-mer occurring many hundreds of times) goes to k_bucket_big.
+// Every bucket is finished by exactly one of the three: nothing is redone, nothing leaves the own pipeline.
+static void bucket_kernels(bucket_run& R) {
+    const bucket_geometry& G = R.G; hipStream_t s = R.s; vg_genomes* g = R.g; kmer_index& ix = R.ix;
+    const uint32_t n1 = R.n1; const int64_t nbk = G.nbk;
+    if (ix.gen.n < (size_t)n1 + 4) ix.gen.alloc((size_t)n1 + 4);
+    if (ix.rowinfo.n < (size_t)ix.n_rows_info) ix.rowinfo.alloc((size_t)ix.n_rows_info);      // (one level: nothing to take over)
     dbuf<unsigned int> d_nover(2); d_nover.zero(s);
     dbuf<uint32_t> over1((size_t)nbk), over2;
-    if (ev_rows_zero) VG_HIP(hipStreamWaitEvent(s, ev_rows_zero, 0));
-    else VG_HIP(hipMemsetAsync(rowinfo.p, 0, (size_t)n_rows_info * sizeof(uint32_t), s));
-    const int pb = narrow ? 0 : total_bits;
+    if (R.rows_zero.e) VG_HIP(hipStreamWaitEvent(s, R.rows_zero.e, 0));
+    else VG_HIP(hipMemsetAsync(ix.rowinfo.p, 0, (size_t)ix.n_rows_info * sizeof(uint32_t), s));
+    const int pb = G.narrow ? 0 : G.total_bits;
+    const uint32_t* boff = R.boff.p; const uint32_t* blk2g = g->d_blk2g.p;
     unsigned int n_over[2] = {0, 0};
-#define VG_BUCKET_LAUNCH(NARROW_, THREADS_, SUBBITS_, GRID_, COUNT_, LIST_, OVER_, NOVER_) \
-    hipLaunchKernelGGL((k_bucket_runs<NARROW_, THREADS_, SUBBITS_>), dim3(GRID_), dim3(THREADS_), 0, s, f_rec, f_stride, (const uint32_t*)boff.p, (int64_t)(COUNT_), \
-                       pb, (const uint32_t*)g->d_blk2g.p, g->align_shift, gen.p, rowinfo.p, cmap, d_dups, (const uint32_t*)(LIST_), (OVER_), (NOVER_))
+    auto runs = [&](auto kern, int threads, int grid, int64_t count, const uint32_t* list, uint32_t* over, unsigned int* nover) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, R.f_rec, R.f_stride, boff, count, pb, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, list, over, nover);
+    };
+    const auto wide = G.narrow ? k_bucket_runs<true, 1024, 11> : k_bucket_runs<false, 1024, 11>;
     {
-        vg_prof_scope ps("bucket_sort_runs", (double)n1 * ((narrow ? 8 : 12) + 4 + 8));
+        vg_prof_scope ps("bucket_sort_runs", (double)n1 * ((G.narrow ? 8 : 12) + 4 + 8));
         const int grid_b = (int)std::min<int64_t>(nbk, 256 * 16);
-
-        if (big_buckets) { if (narrow) VG_BUCKET_LAUNCH(true, 1024, 11, grid_b, nbk, nullptr, over1.p, d_nover.p); else VG_BUCKET_LAUNCH(false, 1024, 11, grid_b, nbk, nullptr, over1.p, d_nover.p); }
-        else { if (narrow) VG_BUCKET_LAUNCH(true, BK_THREADS, 9, grid_b, nbk, nullptr, over1.p, d_nover.p); else VG_BUCKET_LAUNCH(false, BK_THREADS, 9, grid_b, nbk, nullptr, over1.p, d_nover.p); }
+        if (G.big_buckets) runs(wide, 1024, grid_b, nbk, nullptr, over1.p, d_nover.p);
+        else runs(G.narrow ? k_bucket_runs<true, BK_THREADS, 9> : k_bucket_runs<false, BK_THREADS, 9>, BK_THREADS, grid_b, nbk, nullptr, over1.p, d_nover.p);
         d_nover.download(n_over, 2, s);
         VG_HIP(hipStreamSynchronize(s));
     }
     const uint32_t* big_list = over1.p; unsigned int n_big = n_over[0];
-    if (n_big > 0 && !big_buckets) {
+    if (n_big > 0 && !G.big_buckets) {
         over2.alloc((size_t)n_big);
         vg_prof_scope ps("bucket_sort_runs_wide", 0);
-        const int grid_b = (int)std::min<int64_t>(n_big, 256 * 16);
-        if (narrow) VG_BUCKET_LAUNCH(true, 1024, 11, grid_b, n_big, over1.p, over2.p, d_nover.p + 1); else VG_BUCKET_LAUNCH(false, 1024, 11, grid_b, n_big, over1.p, over2.p, d_nover.p + 1);
+        runs(wide, 1024, (int)std::min<int64_t>(n_big, 256 * 16), n_big, over1.p, over2.p, d_nover.p + 1);
         d_nover.download(n_over, 2, s);
         VG_HIP(hipStreamSynchronize(s));
         big_list = over2.p; n_big = n_over[1];
     }
-#undef VG_BUCKET_LAUNCH
-    if (n_big > 0) {
-        // sizes of the queued buckets -> scratch offsets (the host adds them up)
-        dbuf<uint32_t> d_sz(n_big); std::vector<uint32_t> sz(n_big);
-        hipLaunchKernelGGL(k_bucket_sizes, dim3(grid_for(n_big)), dim3(256), 0, s, (const uint32_t*)boff.p, big_list, (int64_t)n_big, d_sz.p);
-        d_sz.download(sz.data(), n_big, s);
-        VG_HIP(hipStreamSynchronize(s));
-        std::vector<uint64_t> so(n_big); uint64_t tot = 0;
-        for (unsigned int i = 0; i < n_big; ++i) { so[i] = tot; tot += ((uint64_t)sz[i] + 3) & ~3ULL; }
-        dbuf<uint64_t> d_so(n_big);
-        d_so.upload(so.data(), n_big, s);
-        const uint32_t* d_lst_p = big_list;
-        dbuf<uint64_t> kA((size_t)tot + 4), kB((size_t)tot + 4); dbuf<uint32_t> pA((size_t)tot + 4), pB((size_t)tot + 4);
-        {
-            vg_prof_scope ps("bucket_big", (double)tot * 12.0 * 2.0);
-            hipLaunchKernelGGL(k_bucket_big, dim3(n_big), dim3(BB_THREADS), 0, s, f_rec, f_stride, (const uint32_t*)boff.p, d_lst_p,
-                               (const uint64_t*)d_so.p, pb, kA.p, pA.p, kB.p, pB.p, (const uint32_t*)g->d_blk2g.p, g->align_shift, gen.p, rowinfo.p, cmap, d_dups);
-        }
-        VG_HIP(hipStreamSynchronize(s));
+    if (n_big == 0) return;
+    // sizes of the queued buckets -> scratch offsets (the host adds them up)
+    dbuf<uint32_t> d_sz(n_big); std::vector<uint32_t> sz(n_big);
+    hipLaunchKernelGGL(k_bucket_sizes, dim3(grid_for(n_big)), dim3(256), 0, s, boff, big_list, (int64_t)n_big, d_sz.p);
+    d_sz.download(sz.data(), n_big, s);
+    VG_HIP(hipStreamSynchronize(s));
+    std::vector<uint64_t> so(n_big); uint64_t tot = 0;
+    for (unsigned int i = 0; i < n_big; ++i) { so[i] = tot; tot += ((uint64_t)sz[i] + 3) & ~3ULL; }
+    dbuf<uint64_t> d_so(n_big);
+    d_so.upload(so.data(), n_big, s);
+    dbuf<uint64_t> kA((size_t)tot + 4), kB((size_t)tot + 4); dbuf<uint32_t> pA((size_t)tot + 4), pB((size_t)tot + 4);
+    {
+        vg_prof_scope ps("bucket_big", (double)tot * 12.0 * 2.0);
+        hipLaunchKernelGGL(k_bucket_big, dim3(n_big), dim3(BB_THREADS), 0, s, R.f_rec, R.f_stride, boff, big_list,
+                           (const uint64_t*)d_so.p, pb, kA.p, pA.p, kB.p, pB.p, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p);
     }
+    VG_HIP(hipStreamSynchronize(s));
+}
+// The pipeline as a sequence.  The source is ix.si's kept k-mers (compact) or the bases (dense; ix.n_rows_info set by the
+// caller, d_kept receives the k-mers kept per genome).  A RANGE shard of the dense source (A.dig_n < 2^11): ix.si receives
+// the kept masks, the row bases and the row -> genome map of the pass, n_rows_info becomes the number of kept k-mers, and
+// the row pointers are indexed by row number.
+static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_args& A, int* d_kept, const pass_inputs& in, kmer_index& ix) {
+    hipStream_t s = vg_stream();
+    vg_host_mark("buckets: enter");
+    pass_timer index_timer(in.index_ms, s);                // (placement trials: count ... bucket kernels of this pass)
+    bucket_run R{ g, k, dense, in, ix, d_kept, s }; R.rows_zero.st = s;
+    const int64_t n_src = dense ? g->padded_total() : ix.nv;
+    if (!bucket_geometry_for(k, dense, A, n_src, R.G)) return false;
+    const bucket_geometry& G = R.G;
+    R.S.A = A; R.S.keys = dense ? nullptr : ix.si.keys.p; R.S.pos = dense ? nullptr : ix.si.pos.p; R.S.n = n_src; R.S.k2 = 2 * k; R.S.bin_lo = G.bin_lo;
+    R.cmap = dense ? compact_map{ nullptr, nullptr } : compact_map{ ix.si.goff.p, ix.si.cblk.p };
+    R.k25 = dense && k == 25 && !A.use_frac && A.n_shards == 1;
+    R.T1s.alloc((size_t)G.nb1 * (size_t)G.n_st + 1); R.slab.alloc((size_t)G.n_slabs * G.nb1); R.d_off1.alloc((size_t)G.nb1 + 1);
+    R.G.L2.T1s = R.T1s.p; R.G.L2.off1 = R.d_off1.p;
+    clear_rows_aside(R);
+    {
+        level1_tmp t;
+        if (!level1_count(R, t)) return true;
+        level1_scatter(R);
+    }
+    R.boff.alloc((size_t)G.nbk + 1);
+    if (G.levels == 2) level2(R);
+    else {
+        VG_HIP(hipMemcpyAsync(R.boff.p, R.d_off1.p, ((size_t)G.nb1 + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));     // the level-1 buckets are the final ones
+        R.f_rec = R.a_rec.p;
+    }
+    bucket_kernels(R);
     return true;
 }
-
-// one pass over the k-mers of one shard: per-genome set sizes and (a, b, shared) of every pair
-// dev_out != nullptr: the pairs stay in HBM (*dev_out, *dev_n of them) and host_pairs is left empty
-static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared,
-                             int64_t* set_sizes, std::vector<vg_pair_count>& host_pairs,
-                             dbuf<vg_pair_count>* dev_out = nullptr, unsigned long long* dev_n = nullptr, vg_slice_exchange* xs = nullptr) {
+// ---- the index by the bucket pipeline (own MSD partition + LDS sort); false = it declines, the general radix path takes over
+static bool index_by_buckets(vg_genomes* g, int k, double fraction, int shard, int n_shards, bool dense_src, const pass_inputs& in, kmer_index& ix) {
     hipStream_t s = vg_stream();
-    const int n = g->n;
-    sorted_index si;
-    const int64_t P = g->padded_total();
-    // RANGE shards (sets below 2^32 padded bases, no fraction) keep the dense source: the pass scans the bases, keeps the
-    // k-mers of its level-1 buckets and numbers them as rows; everything behind level 1 is a 1/n_shards slice of the whole
-    // pass, row pointers included.  HASH shards (larger sets, fractions) materialise their k-mers first (compact source).
-    const bool range = range_shards(g, fraction, n_shards);
-    const bool dense_src = !(fraction < 1.0) && (n_shards == 1 || range);
-    int64_t nv = 0, n_rows_info = 0;
-    dbuf<uint32_t> arena;                            // owner of rowinfo / gen when they are windows of one block
-    dbuf<uint32_t> rowinfo; dbuf<uint32_t> gen;
-    dbuf<int> d_dups((size_t)n); d_dups.zero(s);
-    std::vector<int> kept((size_t)n), dups((size_t)n);
-    // ---- the bucket pipeline first (own MSD partition + LDS sort); the general radix path when it declines
-    bool bucket_ok = false;
-    {
-        dbuf<int> kept_b((size_t)n); kept_b.zero(s);
-        kmer_args A = make_kmer_args(g, k, 1.0, dense_src ? shard : 0, dense_src ? n_shards : 1);      // (the compact source's keys are filtered already)
-        if (dense_src) {
-            if (P < (1LL << 32)) {
-                n_rows_info = P;
-                const compact_map none{ nullptr, nullptr };
-                bucket_ok = build_index_buckets(g, k, true, A, nullptr, nullptr, P, none, kept_b.p, gen, rowinfo, arena, n_rows_info, d_dups.p, &nv, range ? &si : nullptr, range ? xs : nullptr);
-                if (bucket_ok) kept_b.download(kept.data(), (size_t)n, s);
-            }
-        } else {
-            run_extract_sort(g, k, fraction, shard, n_shards, si, false, /*do_sort=*/false);
-            nv = si.n_valid; n_rows_info = std::max<int64_t>(nv, 1);
-            const compact_map cm{ si.goff.p, si.cblk.p };
-            int64_t nv2 = 0;
-            bucket_ok = build_index_buckets(g, k, false, A, si.keys.p, si.pos.p, nv, cm, nullptr, gen, rowinfo, arena, n_rows_info, d_dups.p, &nv2);
-            if (bucket_ok) si.kept.download(kept.data(), (size_t)n, s);
+    const int n = g->n; const int64_t P = g->padded_total(); bool ok = false;
+    dbuf<int> kept_b((size_t)n); kept_b.zero(s);
+    const kmer_args A = make_kmer_args(g, k, 1.0, dense_src ? shard : 0, dense_src ? n_shards : 1);      // (the compact source's keys are filtered already)
+    if (dense_src) {
+        if (P < (1LL << 32)) {
+            ix.n_rows_info = P;
+            ok = build_index_buckets(g, k, true, A, kept_b.p, in, ix);
+            if (ok) kept_b.download(ix.kept.data(), (size_t)n, s);
         }
-        if (bucket_ok) { d_dups.download(dups.data(), (size_t)n, s); VG_HIP(hipStreamSynchronize(s)); }
-        vg_host_mark("index built");
+    } else {
+        run_extract_sort(g, k, fraction, shard, n_shards, in, ix.si, false, /*do_sort=*/false);
+        ix.nv = ix.si.n_valid; ix.n_rows_info = std::max<int64_t>(ix.nv, 1);
+        ok = build_index_buckets(g, k, false, A, nullptr, in, ix);
+        if (ok) ix.si.kept.download(ix.kept.data(), (size_t)n, s);
     }
-    if (!bucket_ok) {
-    rowinfo.release(); gen.release(); arena.release();
+    if (ok) { ix.d_dups.download(ix.dups.data(), (size_t)n, s); VG_HIP(hipStreamSynchronize(s)); }
+    vg_host_mark("index built");
+    return ok;
+}
+// ---- the index by the general path: rocPRIM radix sort on the top key bits, runs ordered in the LDS (k_group_runs), the long
+// groups one by one, and a sort on all bits when several frequent k-mers share a prefix group
+static void index_by_radix(vg_genomes* g, int k, double fraction, int shard, int n_shards, const pass_inputs& in, kmer_index& ix) {
+    hipStream_t s = vg_stream(); const int n = g->n;
+    sorted_index& si = ix.si; dbuf<uint32_t>& rowinfo = ix.rowinfo; dbuf<uint32_t>& gen = ix.gen; dbuf<int>& d_dups = ix.d_dups;
+    rowinfo.release(); gen.release(); ix.arena.release();
     d_dups.zero(s);
     si = sorted_index();
-    run_extract_sort(g, k, fraction, shard, n_shards, si, false);
-    nv = si.n_valid;
-    n_rows_info = si.compact ? std::max<int64_t>(nv, 1) : P;      // row pointers: per kept k-mer or per base
+    run_extract_sort(g, k, fraction, shard, n_shards, in, si, false);
+    const int64_t nv = ix.nv = si.n_valid;
+    ix.n_rows_info = si.compact ? std::max<int64_t>(nv, 1) : g->padded_total();      // row pointers: per kept k-mer or per base
     // row pointers and genome list live in the sort's input buffers (16 + 16 GB less at 100 k genomes)
-    if (2 * si.spare64.n >= (size_t)n_rows_info) rowinfo.view(reinterpret_cast<uint32_t*>(si.spare64.p), (size_t)n_rows_info);
-    else rowinfo.alloc((size_t)n_rows_info);
-    VG_HIP(hipMemsetAsync(rowinfo.p, 0, (size_t)n_rows_info * sizeof(uint32_t), s));
+    if (2 * si.spare64.n >= (size_t)ix.n_rows_info) rowinfo.view(reinterpret_cast<uint32_t*>(si.spare64.p), (size_t)ix.n_rows_info);
+    else rowinfo.alloc((size_t)ix.n_rows_info);
+    VG_HIP(hipMemsetAsync(rowinfo.p, 0, (size_t)ix.n_rows_info * sizeof(uint32_t), s));
     const compact_map cmap{ si.compact ? si.goff.p : nullptr, si.compact ? si.cblk.p : nullptr };
     gen = si.spare32.n >= (size_t)std::max<int64_t>(nv, 1) + 4 ? std::move(si.spare32) : dbuf<uint32_t>((size_t)std::max<int64_t>(nv, 1) + 4);
     constexpr unsigned int LONG_CAP = 1u << 16;
@@ -2711,7 +2707,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
                            si.low_bit, gen.p, rowinfo.p, cmap, d_dups.p, long_list.p, d_nlong.p, LONG_CAP);
     }
     unsigned int n_long = 0, need_full = 0;
-    d_nlong.download(&n_long, 1, s); si.kept.download(kept.data(), (size_t)n, s); d_dups.download(dups.data(), (size_t)n, s);
+    d_nlong.download(&n_long, 1, s); si.kept.download(ix.kept.data(), (size_t)n, s); d_dups.download(ix.dups.data(), (size_t)n, s);
     VG_HIP(hipStreamSynchronize(s));
     if (n_long > 0 && n_long <= LONG_CAP) {
         {
@@ -2719,7 +2715,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
             hipLaunchKernelGGL(k_long_groups, dim3(n_long), dim3(256), 0, s, si.keys.p, si.pos.p, g->d_blk2g.p, g->align_shift, nv, si.low_bit,
                                long_list.p, gen.p, rowinfo.p, cmap, d_dups.p, d_full.p);
         }
-        d_full.download(&need_full, 1, s); d_dups.download(dups.data(), (size_t)n, s);
+        d_full.download(&need_full, 1, s); d_dups.download(ix.dups.data(), (size_t)n, s);
         VG_HIP(hipStreamSynchronize(s));
     }
     if (need_full || n_long > LONG_CAP) {
@@ -2731,19 +2727,14 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
             hipLaunchKernelGGL(k_runs, dim3(grid_for((nv + 3) / 4)), dim3(256), 0, s, si.keys.p, si.pos.p, g->d_blk2g.p, g->align_shift, nv,
                                gen.p, rowinfo.p, cmap, d_dups.p);
         }
-        d_dups.download(dups.data(), (size_t)n, s);
+        d_dups.download(ix.dups.data(), (size_t)n, s);
         VG_HIP(hipStreamSynchronize(s));
     }
-    }
-    const bool compact_rows = bucket_ok ? (!dense_src || range) : si.compact;
-    const uint32_t* wbase = compact_rows ? si.wave_base.p : nullptr;
-    for (int i = 0; i < n; ++i) set_sizes[i] = (int64_t)kept[i] - dups[i];
-    si.keys.release();
-    // (the library queue is idle here -- the index stage ended with a synchronisation --: the sub-shard loop starts the
-    // k-mer scan of the NEXT sub-shard on the second queue, beside this sub-shard's SpGEMM: arithmetic beside random
-    // reads.  Started earlier, beside the partition kernels, the scan only took their CUs: 2.70 against 2.74 s.)
-    run_scan_hook();
-    // SpGEMM with a growing output buffer
+}
+// ---- the SpGEMM over the index, with a growing output buffer.  dev_out != nullptr: the pairs stay in HBM (*dev_out, *dev_n of them) and host_pairs is left empty
+static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_shared, std::vector<vg_pair_count>& host_pairs,
+                         dbuf<vg_pair_count>* dev_out, unsigned long long* dev_n) {
+    hipStream_t s = vg_stream(); const int n = g->n;
     dbuf<unsigned long long> d_cursor(1);
     dbuf<uint32_t> d_over((size_t)n), d_nover(1);
     unsigned long long cap = std::max<unsigned long long>(1u << 20, (unsigned long long)n * 16);
@@ -2757,8 +2748,8 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
         // rows of a genome in this pass: its kept k-mers (a sliced scan counted the k-mers of its slice of the BASES instead:
         // the rows are then read off the row map)
         std::vector<uint32_t> goff_h;
-        if (xs && range && bucket_ok) { goff_h.resize((size_t)n + 1); si.goff.download(goff_h.data(), (size_t)n + 1, s); VG_HIP(hipStreamSynchronize(s)); }
-        auto rows_of = [&](int i) { return !goff_h.empty() ? (int64_t)(goff_h[(size_t)i + 1] - goff_h[(size_t)i]) : compact_rows ? (int64_t)kept[(size_t)i] : g->len[(size_t)i]; };
+        if (ix.rows_from_map) { goff_h.resize((size_t)n + 1); ix.si.goff.download(goff_h.data(), (size_t)n + 1, s); VG_HIP(hipStreamSynchronize(s)); }
+        auto rows_of = [&](int i) { return !goff_h.empty() ? (int64_t)(goff_h[(size_t)i + 1] - goff_h[(size_t)i]) : ix.compact_rows ? (int64_t)ix.kept[(size_t)i] : g->len[(size_t)i]; };
         for (int i = 0; i < n; ++i) (rows_of(i) <= SMALL_ROW ? small_rows : large_rows).push_back((uint32_t)i);
         if (small_rows.size() * 2 >= (size_t)n) {
             n_small = (int)small_rows.size(); n_large = (int)large_rows.size();
@@ -2769,16 +2760,17 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
     for (;;) {
         dbuf<vg_pair_count> d_out((size_t)cap);
         d_cursor.zero(s); d_nover.zero(s);
+        // one launch over n_rows rows (`rows` lists them, null = all genomes); rows whose table overflows are listed in `over`
+        auto launch = [&](auto kern, int threads, const uint32_t* rows, int n_rows, uint32_t* over) {
+            hipLaunchKernelGGL(kern, dim3((n_rows + 7) / 8 * 8), dim3(threads), 0, s, ix.rowinfo.p, ix.gen.p, (uint64_t)ix.gen.n, g->d_base_off.p, g->d_len.p, ix.wbase, n,
+                               min_shared, rows, n_rows, d_out.p, d_cursor.p, cap, over, d_nover.p);
+        };
         {
-            vg_prof_scope ps("spgemm_rows", (double)n_rows_info * 4.0);
+            vg_prof_scope ps("spgemm_rows", (double)ix.n_rows_info * 4.0);
             if (n_small) {
-                if (n_large) hipLaunchKernelGGL(k_spgemm<11>, dim3((n_large + 7) / 8 * 8), dim3(256), 0, s, rowinfo.p, gen.p, (uint64_t)gen.n, g->d_base_off.p, g->d_len.p, wbase, n,
-                                                min_shared, (const uint32_t*)d_large.p, n_large, d_out.p, d_cursor.p, cap, d_over.p, d_nover.p);
-                hipLaunchKernelGGL((k_spgemm<9, true>), dim3((n_small + 7) / 8 * 8), dim3(64), 0, s, rowinfo.p, gen.p, (uint64_t)gen.n, g->d_base_off.p, g->d_len.p, wbase, n,
-                                   min_shared, (const uint32_t*)d_small.p, n_small, d_out.p, d_cursor.p, cap, d_over.p, d_nover.p);
-            } else
-            hipLaunchKernelGGL(k_spgemm<11>, dim3((n + 7) / 8 * 8), dim3(256), 0, s, rowinfo.p, gen.p, (uint64_t)gen.n, g->d_base_off.p, g->d_len.p, wbase, n,
-                               min_shared, (const uint32_t*)nullptr, n, d_out.p, d_cursor.p, cap, d_over.p, d_nover.p);
+                if (n_large) launch(k_spgemm<11>, 256, d_large.p, n_large, d_over.p);
+                launch(k_spgemm<9, true>, 64, d_small.p, n_small, d_over.p);
+            } else launch(k_spgemm<11>, 256, nullptr, n, d_over.p);
         }
         // one round trip in the common case: overflow count, pair count and the first pairs together
         constexpr size_t EAGER = 1 << 16;
@@ -2788,8 +2780,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
         if (!dev_out) d_out.download(host_pairs.data(), host_pairs.size(), s);
         VG_HIP(hipStreamSynchronize(s));
         vg_host_mark("spgemm done");
-        if (dev_out && nover == 0 && produced <= cap) { *dev_out = std::move(d_out); *dev_n = produced; break; }
-        if (!dev_out && nover == 0 && produced <= host_pairs.size()) { host_pairs.resize((size_t)produced); break; }
+        if (nover == 0 && produced <= (dev_out ? cap : host_pairs.size())) { if (dev_out) { *dev_out = std::move(d_out); *dev_n = produced; } else host_pairs.resize((size_t)produced); break; }
         if (nover > 0) {
             // second try with the 64 KiB table for the rows that overflowed the small one
             dbuf<uint32_t> d_rows2(nover), d_over2(nover);
@@ -2797,8 +2788,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
             d_nover.zero(s);
             {
                 vg_prof_scope ps("spgemm_rows_wide", 0);
-                hipLaunchKernelGGL(k_spgemm<13>, dim3((nover + 7) / 8 * 8), dim3(256), 0, s, rowinfo.p, gen.p, (uint64_t)gen.n, g->d_base_off.p, g->d_len.p, wbase, n,
-                                   min_shared, (const uint32_t*)d_rows2.p, (int)nover, d_out.p, d_cursor.p, cap, d_over2.p, d_nover.p);
+                launch(k_spgemm<13>, 256, d_rows2.p, (int)nover, d_over2.p);
             }
             VG_HIP(hipMemcpyAsync(d_over.p, d_over2.p, sizeof(uint32_t) * nover, hipMemcpyDeviceToDevice, s));
             d_nover.download(&nover, 1, s);
@@ -2814,8 +2804,8 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
                 dense.zero(s);
                 d_rows.upload(rows.data() + o, nb, s);
                 vg_prof_scope ps("spgemm_dense_rows", 0);
-                hipLaunchKernelGGL(k_spgemm_dense, dim3(nb), dim3(256), 0, s, rowinfo.p, gen.p, (uint64_t)gen.n, g->d_base_off.p,
-                                   g->d_len.p, wbase, n, min_shared, d_rows.p, dense.p, d_out.p, d_cursor.p, cap);
+                hipLaunchKernelGGL(k_spgemm_dense, dim3(nb), dim3(256), 0, s, ix.rowinfo.p, ix.gen.p, (uint64_t)ix.gen.n, g->d_base_off.p,
+                                   g->d_len.p, ix.wbase, n, min_shared, d_rows.p, dense.p, d_out.p, d_cursor.p, cap);
                 VG_HIP(hipStreamSynchronize(s));
             }
         }
@@ -2830,6 +2820,33 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
         }
         cap = produced + produced / 8 + 1024;     // rerun with a buffer that fits
     }
+}
+// one pass over the k-mers of one shard: per-genome set sizes and (a, b, shared) of every pair (see spgemm_pairs for dev_out)
+static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared, int64_t* set_sizes, std::vector<vg_pair_count>& host_pairs,
+                             const pass_inputs& in = pass_inputs{}, dbuf<vg_pair_count>* dev_out = nullptr, unsigned long long* dev_n = nullptr) {
+    const int n = g->n;
+    kmer_index ix;
+    ix.d_dups.alloc((size_t)n); ix.d_dups.zero(vg_stream());
+    ix.kept.resize((size_t)n); ix.dups.resize((size_t)n);
+    // RANGE shards (sets below 2^32 padded bases, no fraction) keep the dense source: the pass scans the bases, keeps the
+    // k-mers of its level-1 buckets and numbers them as rows; everything behind level 1 is a 1/n_shards slice of the whole
+    // pass, row pointers included.  HASH shards (larger sets, fractions) materialise their k-mers first (compact source).
+    const bool range = range_shards(g, fraction, n_shards);
+    const bool dense_src = !(fraction < 1.0) && (n_shards == 1 || range);
+    const bool bucket_ok = index_by_buckets(g, k, fraction, shard, n_shards, dense_src, in, ix);      // 1. the index
+    if (!bucket_ok) index_by_radix(g, k, fraction, shard, n_shards, in, ix);
+    ix.compact_rows = bucket_ok ? (!dense_src || range) : ix.si.compact;
+    ix.rows_from_map = in.xs && range && bucket_ok;
+    ix.wbase = ix.compact_rows ? ix.si.wave_base.p : nullptr;
+    for (int i = 0; i < n; ++i) set_sizes[i] = (int64_t)ix.kept[i] - ix.dups[i];      // 2. set sizes, and the scan ahead
+    ix.si.keys.release();
+    // (the library queue is idle here -- the index stage ended with a synchronisation --: the sub-shard loop has the k-mer scan of
+    // the NEXT sub-shard started on the second queue, beside this sub-shard's SpGEMM: arithmetic beside random reads.  Started
+    // beside the partition kernels it only took their CUs, 2.70 against 2.74 s; beside the bucket kernel, behind level 2, that
+    // kernel takes 86 ms instead of 55 at 10^6 contigs.  An optimisation only: without room the next sub-shard scans in line.)
+    if (in.pre && in.next_shard >= 0)
+        try { vg_dev_try_scope opportunistic; launch_precount(*in.pre, g, k, in.next_shard, n_shards); } catch (...) { (void)hipGetLastError(); in.pre->drop(); }
+    spgemm_pairs(g, ix, min_shared, host_pairs, dev_out, dev_n);      // 3. the pairs
 }
 
 // sum of partial pair records (the sub-shards of one call): device radix sort on (a << 32 | b) + reduce by key
@@ -2901,14 +2918,13 @@ static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int sha
     for (int i = 0; i < n; ++i) set_sizes[i] = 0;
     std::vector<dbuf<vg_pair_count>> parts((size_t)sub); std::vector<unsigned long long> counts((size_t)sub, 0ULL);
     std::vector<vg_pair_count> none;
-    struct hook_guard { ~hook_guard() { g_after_extract = nullptr; g_precount.drop(); g_pass_mask = pass_mask(); } } hg;
+    precount ahead;                                   // the scan of the next sub-shard (whatever way the loop is left, it is waited for and dropped)
     // HASH sub-shards: ONE scan of the bases leaves the kept masks of all passes (k_multi_mask); a pass then computes the
     // k-mers of its kept positions only.  (sub x P / 8 bytes of masks -- 22 GB at 10^6 contigs -- replace two sets of
     // staging buffers of P / 256 x ~80 x 8 bytes each; VG_SUBSHARD_SCAN=each is the scan per pass of round 4)
-    static const bool scan_each = [] { const char* e = vg_dev_getenv("VG_SUBSHARD_SCAN"); return e && !strcmp(e, "each"); }();
     dbuf<unsigned long long> all_masks;
     const int64_t Wm = g->padded_total() / 64 + 1;
-    const bool multi = !scan_each && sub >= 2 && sub <= MM_MAX_SUB && !range_shards(g, fraction, n_shards * sub);
+    const bool multi = !g_sw.scan_each && sub >= 2 && sub <= MM_MAX_SUB && !range_shards(g, fraction, n_shards * sub);
     if (multi) {
         int rc = vg_genomes_to_device(g); if (rc) throw vg_error(rc, vg_last_error());
         hipStream_t s = vg_stream();
@@ -2917,23 +2933,44 @@ static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int sha
         const int64_t P = g->padded_total();
         const size_t lds = (size_t)4 * sub * 8 * sizeof(uint32_t);
         vg_prof_scope ps("kmer_multi_mask", (double)P * (3.0 / 8.0 + sub / 8.0));
-        if (k == 25 && !A.use_frac) hipLaunchKernelGGL(k_multi_mask<25>, dim3(grid_for((P + 255) / 4)), dim3(256), lds, s, A, (uint32_t)(shard * sub), (uint32_t)sub, (uint32_t)(n_shards * sub), all_masks.p, Wm);
-        else hipLaunchKernelGGL(k_multi_mask<0>, dim3(grid_for((P + 255) / 4)), dim3(256), lds, s, A, (uint32_t)(shard * sub), (uint32_t)sub, (uint32_t)(n_shards * sub), all_masks.p, Wm);
+        with_k(k == 25 && !A.use_frac, [&](auto K) { hipLaunchKernelGGL(k_multi_mask<K()>, dim3(grid_for((P + 255) / 4)), dim3(256), lds, s, A, (uint32_t)(shard * sub), (uint32_t)sub, (uint32_t)(n_shards * sub), all_masks.p, Wm); });
     }
+    // (HASH shards without the one scan: the compact source scans first, so the scan of sub-shard t + 1 can run ahead)
+    const bool scan_ahead = !multi && !(fraction < 1.0) && !range_shards(g, fraction, n_shards * sub);
     for (int t = 0; t < sub; ++t) {
-        g_after_extract = nullptr;
-        g_pass_mask = pass_mask();
-        if (multi) { g_pass_mask.g = g; g_pass_mask.k = k; g_pass_mask.shard = shard * sub + t; g_pass_mask.n_shards = n_shards * sub; g_pass_mask.mask = all_masks.p + (size_t)t * (size_t)Wm; }
-        if (!multi && t + 1 < sub && !(fraction < 1.0) && !range_shards(g, fraction, n_shards * sub))      // (HASH shards: the compact source scans first)
-            g_after_extract = [=] {
-                // (an optimisation only: without room for the second set of scan buffers the next sub-shard scans in line)
-                try { vg_dev_try_scope opportunistic; launch_precount(g, k, shard * sub + t + 1, n_shards * sub); } catch (...) { (void)hipGetLastError(); g_precount.drop(); }
-            };
-        kmer_shared_pass(g, k, fraction, shard * sub + t, n_shards * sub, 1u, part.data(), none, &parts[(size_t)t], &counts[(size_t)t]);
+        pass_inputs in; if (multi) in.mask = all_masks.p + (size_t)t * (size_t)Wm;
+        if (scan_ahead) { in.pre = &ahead; in.next_shard = t + 1 < sub ? shard * sub + t + 1 : -1; }
+        kmer_shared_pass(g, k, fraction, shard * sub + t, n_shards * sub, 1u, part.data(), none, in, &parts[(size_t)t], &counts[(size_t)t]);
         for (int i = 0; i < n; ++i) set_sizes[i] += part[i];
     }
     vg_host_mark("sub-shards done");
     sum_partial_pairs(parts, counts, min_shared, out, n_out);
+}
+
+// How a call over one shard of n_shards is cut into passes.  Sets beyond the 32-bit row numbering of one pass (2^32 padded bases
+// dense, ~2^31 kept k-mers per shard) are cut into sub-shards of this shard's k-mer range; partial counts of a pair add up.
+// A pure function of the set, the fraction and the process's knobs.  host_entry: vg_kmer_shared, whose rules differ in three places:
+//  - it alone honours VG_SUBSHARDS and, for a cold one-shot call (the CLI), the workspace budget;
+//  - vg_set_subshards(1) means "one pass" to it whatever the size (the device entry still cuts a set too large for one);
+//  - its overflow retry gives up under any vg_set_subshards(n > 0), the device entry's under n > 1.
+struct shard_plan { int sub; bool one_pass, range, retry_finer; };      // passes; sub == 1; RANGE (else HASH) shards; an overflowing loop may be cut finer
+static shard_plan plan_shards(const vg_genomes* g, double fraction, int n_shards, bool host_entry) {
+    const int64_t P = g->padded_total();
+    int64_t real_bases = 0; for (int i = 0; i < g->n; ++i) real_bases += g->len[(size_t)i];
+    const double expect = (double)real_bases * fraction / n_shards;        // k-mers kept by this shard, at most (padding positions hold none)
+    const bool dense = fraction >= 1.0 && n_shards == 1;
+    const bool too_large = dense ? P >= (1LL << 32) : expect >= SUB_PASS_START;      // row numbers of one pass are 32 bits
+    const int forced = g_force_subshards > (host_entry ? 0 : 1) ? g_force_subshards : 0;
+    int sub = 1;
+    if (forced) sub = forced;
+    else if (host_entry && g_sw.subshards > 0) sub = g_sw.subshards;
+    else if (too_large) sub = std::max(2, (int)std::ceil(expect / SUB_PASS_KMERS));
+    else if (host_entry && dense && vg_one_shot())
+        // a cold one-shot call (the CLI): RANGE sub-shards under a workspace budget (VG_WORKSPACE_GB) -- 16 bytes of records per kept
+        // k-mer and pass.  Eight passes over 100 k genomes cost tens of ms of scans and touch 8 GB of device memory instead of 66 GB:
+        // a cold process may wait 25-32 ms per GiB for the first use of memory the driver still has to wipe (vg_core.cpp).
+        sub = std::max(1, (int)std::min(64.0, std::ceil(16.0 * (double)P / (g_sw.workspace_gb * 1073741824.0))));
+    return { sub, sub == 1, range_shards(g, fraction, n_shards * sub), !forced };
 }
 
 // Placement trials (below): how many placements of the workspace the first dense pass of a long-lived process may try.
@@ -2942,9 +2979,8 @@ static std::mutex g_trials_mu;
 static int g_placement_trials = 1;
 static std::map<std::pair<int64_t, int>, int> g_trials_done;       // (padded bases, k) -> tried (under g_trials_mu)
 static int placement_trials_now() {
-    static const int env = [] { const char* e = vg_dev_getenv("VG_PLACEMENT_TRIALS"); return e && *e ? atoi(e) : 0; }();
     std::lock_guard<std::mutex> lk(g_trials_mu);
-    return env > 0 ? env : g_placement_trials;
+    return g_sw.placement_trials > 0 ? g_sw.placement_trials : g_placement_trials;
 }
 extern "C" void vg_set_placement_trials(int n) {
     std::lock_guard<std::mutex> lk(g_trials_mu);
@@ -2964,31 +3000,13 @@ extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, 
     *pairs = nullptr; *n_pairs = 0;
     const int n = g->n;
     if (n == 0) return VG_OK;
-    // Sets beyond the 32-bit row numbering of one pass (2^32 padded bases dense, ~2^31 kept k-mers per
-    // shard) are cut into sub-shards of this shard's k-mer range; partial counts of a pair add up.
-    const int64_t P = g->padded_total();
-    int64_t real_bases = 0; for (int i = 0; i < g->n; ++i) real_bases += g->len[(size_t)i];
-    const double expect = (double)real_bases * fraction / n_shards;        // k-mers kept by this shard, at most (padding positions hold none)
-    const bool dense = fraction >= 1.0 && n_shards == 1;
-    int sub = 1;
-    static const int env_sub = [] { const char* e = vg_dev_getenv("VG_SUBSHARDS"); return e ? atoi(e) : 0; }();      // developer experiments
-    if (g_force_subshards > 0) sub = g_force_subshards;
-    else if (env_sub > 0) sub = env_sub;
-    else if (dense ? P >= (1LL << 32) : expect >= SUB_PASS_START) sub = std::max(2, (int)std::ceil(expect / SUB_PASS_KMERS));      // row numbers of one pass are 32 bits
-    else if (dense && vg_one_shot()) {
-        // a cold one-shot call (the CLI): RANGE sub-shards under a workspace budget -- 16 bytes of records per kept k-mer
-        // and pass.  Eight passes over 100 k genomes cost eight scans of the bases more than one pass (tens of ms) and
-        // touch 8 GB of device memory instead of 66 GB: what a cold process may wait for is the first use of memory
-        // (25-32 ms per GiB when the driver still has to wipe it, vg_core.cpp).  VG_WORKSPACE_GB sets the budget.
-        static const double ws_gb = [] { const char* e = getenv("VG_WORKSPACE_GB"); const double v = e ? atof(e) : 0.0; return v > 0.01 ? v : 8.0; }();
-        sub = (int)std::min(64.0, std::ceil(16.0 * (double)P / (ws_gb * 1073741824.0)));
-    }
-    if (sub < 1) sub = 1;
+    const int64_t P = g->padded_total(); const bool dense = fraction >= 1.0 && n_shards == 1;
+    const shard_plan plan = plan_shards(g, fraction, n_shards, /*host_entry=*/true);
     std::vector<vg_pair_count> acc;
-    if (sub == 1) {
+    if (plan.one_pass) {
         vg_slice_exchange xs; xs.rank = shard; xs.world = n_shards; xs.emulate = true;
-        const bool sliced = g_range_scan_mode == 1 && vg_slice_exchange_applies(g, k, fraction, n_shards);
-        kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, set_sizes, acc, nullptr, nullptr, sliced ? &xs : nullptr);
+        pass_inputs in; if (g_range_scan_mode == 1 && vg_slice_exchange_applies(g, k, fraction, n_shards)) in.xs = &xs;
+        kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, set_sizes, acc, in);
         // Placement trials.  Where the driver puts the workspace decides between two states of the scattering kernels (the
         // bucket kernel 39 against 44 ms at 100 k genomes: same virtual addresses, same requests, same UTCL1 misses, 1.3-2 x
         // the translation-in-flight and DRAM-credit stalls -- profiles/r05_placement_states.md), and it stays for the
@@ -3006,23 +3024,23 @@ extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, 
             first_time = !g_trials_done[{ P, k }]++;
         }
         if (first_time && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 2 * vg_dev_cached_bytes() + (8ULL << 30)) {
-            struct timing_on { timing_on() { g_time_bucket_pass = true; } ~timing_on() { g_time_bucket_pass = false; } } on;
+            float index_ms = 0.f; pass_inputs timed; timed.index_ms = &index_ms;       // the index stage of the last timed pass
             std::vector<int64_t> sz2((size_t)n); std::vector<vg_pair_count> acc2;
             float best = 0.f;
             try {
-                kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2);       // (the first pass paid for the allocations: time this placement on a second one)
-                best = g_last_bucket_ms;
+                kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2, timed);       // (the first pass paid for the allocations: time this placement on a second one)
+                best = index_ms;
             } catch (...) { (void)hipGetLastError(); best = 0.f; }
             for (int trial = 1; trial < max_trials && best > 0.f; ++trial) {
                 const double w0 = vg_alloc_wait_ms();
                 vg_dev_park_cache();
                 bool keep_new = false;
                 try {
-                    kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2);
-                    kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2);
-                    keep_new = g_last_bucket_ms > 0.f && g_last_bucket_ms < 0.97f * best;
-                    if (getenv("VG_ALLOC_TRACE")) fprintf(stderr, "[vg placement] trial %d: index stage %.2f ms against %.2f ms -> %s\n", trial, g_last_bucket_ms, best, keep_new ? "kept" : "dropped");
-                    if (keep_new) best = g_last_bucket_ms;
+                    kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2, timed);
+                    kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2, timed);
+                    keep_new = index_ms > 0.f && index_ms < 0.97f * best;
+                    if (getenv("VG_ALLOC_TRACE")) fprintf(stderr, "[vg placement] trial %d: index stage %.2f ms against %.2f ms -> %s\n", trial, index_ms, best, keep_new ? "kept" : "dropped");
+                    if (keep_new) best = index_ms;
                 } catch (...) { (void)hipGetLastError(); keep_new = false; }
                 vg_dev_unpark(!keep_new);
                 if (vg_alloc_wait_ms() - w0 > 500.0) break;          // (memory the driver still has to wipe: a trial costs seconds here)
@@ -3034,9 +3052,9 @@ extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, 
         dbuf<vg_pair_count> d_sum; unsigned long long n_sum = 0;
         // (HASH sub-shards are sized on an expectation: a set whose repeated k-mers crowd one sub-shard beyond the 32-bit row
         // numbers of a pass is cut finer instead of failing)
-        for (int attempt = 0;; ++attempt) {
+        for (int attempt = 0, sub = plan.sub;; ++attempt) {
             try { kmer_shared_subshards(g, k, fraction, shard, n_shards, sub, min_shared, set_sizes, d_sum, &n_sum); break; }
-            catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || g_force_subshards > 0) throw; ++sub; d_sum.release(); }
+            catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; d_sum.release(); }
         }
         acc.resize((size_t)n_sum);
         if (n_sum) { d_sum.download(acc.data(), (size_t)n_sum, vg_stream()); VG_HIP(hipStreamSynchronize(vg_stream())); }
@@ -3050,18 +3068,9 @@ extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, 
     VG_API_END
 }
 
-// how a rank of an n_shards-way call cuts the k-mers (1 = RANGE, 2 = HASH): the two do not tile the key space together, so
-// the ranks of a sharded call compare notes BEFORE anything is exchanged (a per-process knob -- vg_set_subshards,
-// VG_INDEX_PATH -- can differ between processes).  A pure function of the set and the process's knobs.
-int vg_kmer_shard_mode(const vg_genomes* g, double fraction, int n_shards) {
-    const int64_t P = g->padded_total();
-    int64_t real_bases = 0; for (int i = 0; i < g->n; ++i) real_bases += g->len[(size_t)i];
-    const double expect = (double)real_bases * fraction / n_shards;
-    const bool dense = fraction >= 1.0 && n_shards == 1;
-    const bool one_pass = g_force_subshards <= 1 && !(dense ? P >= (1LL << 32) : expect >= SUB_PASS_START);
-    const int sub_planned = one_pass ? 1 : std::max(2, g_force_subshards > 1 ? g_force_subshards : (int)std::ceil(expect / SUB_PASS_KMERS));
-    return range_shards(g, fraction, n_shards * sub_planned) ? 1 : 2;
-}
+// how a rank of an n_shards-way call cuts the k-mers (1 = RANGE, 2 = HASH): the two do not tile the key space together, so the ranks of a sharded
+// call compare notes BEFORE anything is exchanged (a per-process knob -- vg_set_subshards, VG_INDEX_PATH -- can differ between processes)
+int vg_kmer_shard_mode(const vg_genomes* g, double fraction, int n_shards) { return plan_shards(g, fraction, n_shards, /*host_entry=*/false).range ? 1 : 2; }
 // internal (vg_dist.hip): one shard's pairs left in HBM (sub-shards included)
 void vg_kmer_shared_device(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared,
                            int64_t* set_sizes, dbuf<vg_pair_count>& pairs, int64_t* n_pairs, vg_slice_exchange* xs, int* mode_out) {
@@ -3070,27 +3079,17 @@ void vg_kmer_shared_device(vg_genomes* g, int k, double fraction, int shard, int
     int rc = vg_genomes_to_device(g); if (rc) throw vg_error(rc, vg_last_error());
     *n_pairs = 0;
     if (g->n == 0) return;
-    const int64_t P = g->padded_total();
-    int64_t real_bases = 0; for (int i = 0; i < g->n; ++i) real_bases += g->len[(size_t)i];
-    const double expect = (double)real_bases * fraction / n_shards;
-    const bool dense = fraction >= 1.0 && n_shards == 1;
-    const bool one_pass = g_force_subshards <= 1 && !(dense ? P >= (1LL << 32) : expect >= SUB_PASS_START);
-    if (mode_out) *mode_out = vg_kmer_shard_mode(g, fraction, n_shards);
-    hipStream_t s = vg_stream();
-    if (one_pass) {
-        std::vector<vg_pair_count> none; unsigned long long n = 0;
-        kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, set_sizes, none, &pairs, &n, xs);
-        *n_pairs = (int64_t)n;
-        return;
-    }
-    int sub = g_force_subshards > 1 ? g_force_subshards : (int)std::ceil(expect / SUB_PASS_KMERS);
-    if (sub < 2) sub = 2;
-    unsigned long long n = 0;
-    for (int attempt = 0;; ++attempt) {
+    const shard_plan plan = plan_shards(g, fraction, n_shards, /*host_entry=*/false);
+    if (mode_out) *mode_out = plan.range ? 1 : 2;
+    unsigned long long n = 0; int sub = plan.sub;
+    if (plan.one_pass) {
+        std::vector<vg_pair_count> none; pass_inputs in; in.xs = xs;
+        kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, set_sizes, none, in, &pairs, &n);
+    } else for (int attempt = 0;; ++attempt) {
         try { kmer_shared_subshards(g, k, fraction, shard, n_shards, sub, min_shared, set_sizes, pairs, &n); break; }
-        catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || g_force_subshards > 1) throw; ++sub; pairs.release(); }
+        catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; pairs.release(); }
     }
-    if (!pairs.p) pairs.alloc(1);
+    if (!plan.one_pass && !pairs.p) pairs.alloc(1);
     *n_pairs = (int64_t)n;
 }
 
@@ -3107,7 +3106,7 @@ extern "C" int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint6
     int rc = vg_genomes_to_device(g); if (rc) return rc;
     hipStream_t s = vg_stream();
     sorted_index si;
-    run_extract_sort(g, k, fraction, 0, 1, si);
+    run_extract_sort(g, k, fraction, 0, 1, pass_inputs{}, si);
     // host-side filter of one genome's keys out of the sorted index (test-only entry point)
     std::vector<uint64_t> keys((size_t)si.n_valid); std::vector<uint32_t> pos((size_t)si.n_valid);
     if (si.n_valid) { si.keys.download(keys.data(), keys.size(), s); si.pos.download(pos.data(), pos.size(), s); }
