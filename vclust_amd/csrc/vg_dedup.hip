@@ -47,6 +47,15 @@
 //   verify    one wave per (candidate, chunk): X, or revcomp(X) made by v_bfrev_b32, against the container re-framed by
 //             v_alignbit_b32; a mismatch sets the candidate's flag (32-bit atomic) and ends its other chunks early
 //   pick      64-bit atomicMax per record of (container's rank by length and index, strand, offset) over the equal candidates
+// The host side of a call, in call order: the entry point's own checks, check_seq_arrays and pack_seqs (array-level calls) or the
+// reader and pack_and_upload (files); run_mode, the one dispatch: contained_device, or repeats_device (with a minimum repeat) and
+// then dedup_device on the circles' lengths, then the counts.  dedup_device: record_table (first word, symbols, first task per
+// record), hash and keys by mode, sort_by_key, then the loop over the unresolved records -- the mode's round (plain_round or
+// circular_round: run_heads, the compare, the labels), the number of members that differ, the compaction -- and the download.
+// What both modes' rounds use is round_bufs; plain_state and circular_state are allocated by their mode alone.
+// contained_device: plan_contained (positions, key bits, length order, positions per pass: before anything is allocated), then a
+// contained_run: index_pass per pass, verify_slice per 2^20 hits, and contained_labels decodes the keys on the host.  A count
+// kernel, its exclusive scan and the read-back of the total are scan_total wherever they occur.
 #include "vg_common.h"
 #include <rocprim/rocprim.hpp>
 #include <zlib.h>
@@ -776,9 +785,11 @@ __global__ void k_sub_pick(const int64_t* len, const int32_t* rnk, int64_t n, co
     if ((threadIdx.x & 63) == 0 && e) atomicAdd(n_equal, (unsigned long long)e);
 }
 
-int grid_of(int64_t n, int per_block = TPB, int cap = 16384) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, cap));
-}
+// ---------------------------------------------------------------- host: the device side of a call
+enum dedup_mode { MODE_PLAIN, MODE_CIRCULAR, MODE_CONTAINED };
+// blocks of a grid-stride launch with one item per thread, and with one task per wave
+int blocks(int64_t n) { return grid_for(n, TPB, 16384); }
+int wave_blocks(int64_t n) { return grid_for(n, WAVES, 65536); }
 
 template <class K, class V>
 void sort_pairs(dbuf<K>& keys, dbuf<K>& keys2, dbuf<V>& vals, dbuf<V>& vals2, int64_t n, unsigned bits, hipStream_t s) {
@@ -792,8 +803,19 @@ void scan(const T* in, T* out, int64_t n, bool inclusive, Op op, hipStream_t s) 
         return inclusive ? rocprim::inclusive_scan(tmp, tb, in, out, (size_t)n, op, s)
                          : rocprim::exclusive_scan(tmp, tb, in, out, (T)0, (size_t)n, op, s); });
 }
-// the (record, chunk of HASH_CHUNK words) tasks of records of len[i] symbols: cbeg[i] = record i's first task (an empty
-// record has one)
+// one counter of the device on the host: a copy and a synchronise
+template <class T> T read_back(const T* at, hipStream_t s) {
+    T v = 0;
+    vg_download_bytes(&v, at, sizeof v, s);
+    VG_HIP(hipStreamSynchronize(s));
+    return v;
+}
+// beg[0 .. n] = the exclusive scan of the counts cnt[0 .. n) (slot n is only scanned over: beg[n] is the total) -> the total
+int64_t scan_total(const int64_t* cnt, int64_t* beg, int64_t n, hipStream_t s) {
+    scan(cnt, beg, n + 1, false, rocprim::plus<int64_t>(), s);
+    return read_back(beg + n, s);
+}
+// the (record, chunk of HASH_CHUNK words) tasks of records of len[i] symbols: cbeg[i] = record i's first task (an empty record has one)
 struct chunk_tasks { std::vector<int64_t> cbeg; int64_t n_tasks = 0, max_len = 0, total_words = 0; };
 chunk_tasks chunk_tasks_of(const std::vector<int64_t>& len) {
     chunk_tasks ct;
@@ -806,20 +828,15 @@ chunk_tasks chunk_tasks_of(const std::vector<int64_t>& len) {
     ct.n_tasks = ct.cbeg.back();
     return ct;
 }
-
-// the three stable passes over the keys (low hash half, high half, length): equal keys end up adjacent, in index order
-void sort_by_key(dbuf<uint64_t>& klo, dbuf<uint64_t>& khi, dbuf<uint64_t>& klen, dbuf<int32_t>& A, dbuf<int32_t>& A2, int64_t n, int bits,
-                 unsigned len_bits, hipStream_t s) {
-    vg_prof_scope ps_("dedup_sort", (double)n * 48.0);
-    dbuf<uint64_t> kg((size_t)n), ks((size_t)n);
-    const unsigned pass_bits[3] = { (unsigned)std::min(bits, 64), (unsigned)std::max(bits - 64, 0), len_bits };
-    const uint64_t* src[3] = { klo.p, khi.p, klen.p };
-    for (int pass = 0; pass < 3; ++pass) {
-        if (!pass_bits[pass]) continue;
-        hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, src[pass], A.p, n, kg.p);
-        sort_pairs(kg, ks, A, A2, n, pass_bits[pass], s);
+// the per-record arrays of the packed set on the device: record i's first word, its symbols (ps.len, or the circles' lengths
+// once the repeats are off) and beg[0 .. n]: its first hash task (cbeg) or its first index position (pbeg).  Three copies.
+struct record_table {
+    dbuf<int64_t> woff, len, beg;
+    record_table(const packed_set& ps, const std::vector<int64_t>& len_, const std::vector<int64_t>& beg_, hipStream_t s)
+        : woff((size_t)ps.n), len((size_t)ps.n), beg((size_t)ps.n + 1) {
+        woff.upload(ps.woff.data(), (size_t)ps.n, s); len.upload(len_.data(), (size_t)ps.n, s); beg.upload(beg_.data(), (size_t)ps.n + 1, s);
     }
-}
+};
 
 // the candidate engine's list: the candidates (owner, code) of every owner, sorted by (owner, code) once order() has run,
 // and their flags
@@ -841,8 +858,7 @@ int64_t collect(cand_list& cl, int64_t n_own, size_t cap0, hipStream_t s, F prod
         VG_HIP(hipMemsetAsync(cl.cnt.p, 0, (size_t)(n_own + 1) * sizeof(int64_t), s));
         cl.total.zero(s);
         produce(cand_slots{ (unsigned long long)cl.owner.n, cl.owner.p, cl.code.p, (unsigned long long*)cl.cnt.p, cl.total.p });
-        cl.total.download(&n_cand, 1, s);
-        VG_HIP(hipStreamSynchronize(s));
+        n_cand = read_back(cl.total.p, s);
         if (n_cand <= cl.owner.n) return (int64_t)n_cand;
     }
 }
@@ -860,38 +876,12 @@ template <class Pair>
 int64_t verify_batches(cand_list& cl, int64_t n_own, const Pair& pair, dbuf<int64_t>& cnt, dbuf<int64_t>& tbeg, unsigned long long* res,
                        unsigned long long* count, hipStream_t s) {
     for (int64_t batches = 0, lo = 0, width = 1;; ++batches, lo += width, width *= 2) {
-        int64_t n_vt = 0;
-        hipLaunchKernelGGL(k_batch, dim3(grid_of(n_own + 1)), dim3(TPB), 0, s, n_own, cl.nch.p, res, cl.cnt.p, lo, lo + width, cnt.p);
-        scan(cnt.p, tbeg.p, n_own + 1, false, rocprim::plus<int64_t>(), s);
-        vg_download_bytes(&n_vt, tbeg.p + n_own, sizeof n_vt, s);
-        VG_HIP(hipStreamSynchronize(s));
+        hipLaunchKernelGGL(k_batch, dim3(blocks(n_own + 1)), dim3(TPB), 0, s, n_own, cl.nch.p, res, cl.cnt.p, lo, lo + width, cnt.p);
+        const int64_t n_vt = scan_total(cnt.p, tbeg.p, n_own, s);
         if (n_vt == 0) return batches;
-        hipLaunchKernelGGL(k_compare<Pair>, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, pair, cl.nch.p, n_own, tbeg.p, n_vt, cl.beg.p, lo,
-                           cl.code.p, cl.bad.p);
-        hipLaunchKernelGGL(k_pick, dim3(grid_of(n_vt)), dim3(TPB), 0, s, cl.nch.p, n_own, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res, count);
+        hipLaunchKernelGGL(k_compare<Pair>, dim3(wave_blocks(n_vt)), dim3(TPB), 0, s, pair, cl.nch.p, n_own, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p);
+        hipLaunchKernelGGL(k_pick, dim3(blocks(n_vt)), dim3(TPB), 0, s, cl.nch.p, n_own, tbeg.p, n_vt, cl.beg.p, lo, cl.code.p, cl.bad.p, res, count);
     }
-}
-
-// One round of the circular verification: res[p] = strand << sbits | offset of every member equal to its head in some
-// rotation of one of the head's strands, NO_OFFSET for the others.  Candidates sorted by (position, strand, offset).
-void circular_round(const packed_set& ps, const int64_t* d_woff, const int64_t* d_len, const int32_t* A, int64_t na, const int64_t* hp,
-                    dbuf<int64_t>& cnt, dbuf<int64_t>& tbeg, cand_list& cl, int sbits, unsigned long long* res, hipStream_t s) {
-    {
-        vg_prof_scope ps_("dedup_ccand", (double)na * 16.0);
-        int64_t n_ct = 0;
-        hipLaunchKernelGGL(k_ctasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A, na, hp, d_len, cl.nch.p, res);
-        scan(cl.nch.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
-        vg_download_bytes(&n_ct, tbeg.p + na, sizeof n_ct, s);
-        VG_HIP(hipStreamSynchronize(s));
-        if (n_ct == 0) return;               // (heads only)
-        const int64_t n_cand = collect(cl, na, std::max(cl.owner.n, (size_t)(4 * na + 1024)), s, [&](const cand_slots& to) {
-            hipLaunchKernelGGL(k_ccand, dim3(grid_of(n_ct, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff, d_len, A, na, hp, tbeg.p, n_ct,
-                               sbits, to); });
-        if (n_cand == 0) return;
-        order(cl, na, n_cand, (unsigned)sbits + 1, bit_width((uint64_t)na, 1), s);
-    }
-    vg_prof_scope ps_("dedup_cverify", 0.0);
-    verify_batches(cl, na, rotation_words{ ps.d_words.p, d_woff, d_len, A, hp, sbits }, cnt, tbeg, res, nullptr, s);
 }
 
 // The terminal repeats of the packed records (resident): repeat_out[i] = tr(record i) for the minimum m >= 1.  Candidate
@@ -902,30 +892,28 @@ void repeats_device(const packed_set& ps, int64_t m, int64_t* repeat_out, vg_ded
     if (n == 0) return;
     hipStream_t s = vg_stream();
     const chunk_tasks ct = chunk_tasks_of(ps.len);
-    dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1), d_rep((size_t)n), d_eff((size_t)n);
-    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_cbeg.upload(ct.cbeg.data(), (size_t)n + 1, s);
+    record_table rt(ps, ps.len, ct.cbeg, s);
+    dbuf<int64_t> d_rep((size_t)n), d_eff((size_t)n);
     dbuf<unsigned long long> res((size_t)n), d_count(2);
     cand_list cl;
     cl.alloc_owners(n);
-    hipLaunchKernelGGL(k_ttasks, dim3(grid_of(n)), dim3(TPB), 0, s, n, d_len.p, cl.nch.p, res.p);
+    hipLaunchKernelGGL(k_ttasks, dim3(blocks(n)), dim3(TPB), 0, s, n, rt.len.p, cl.nch.p, res.p);
     d_count.zero(s);
     {
         vg_prof_scope ps_("dedup_trepeat", (double)ct.total_words * 2.0);
         const int64_t n_cand = collect(cl, n, (size_t)(2 * n + 1024), s, [&](const cand_slots& to) {
-            hipLaunchKernelGGL(k_tcand, dim3(grid_of(ct.n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n,
-                               ct.n_tasks, m, to); });
+            hipLaunchKernelGGL(k_tcand, dim3(wave_blocks(ct.n_tasks)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, rt.beg.p, n, ct.n_tasks, m, to); });
         if (n_cand > 0) {
             dbuf<int64_t> cnt((size_t)n + 1), tbeg((size_t)n + 1);
             order(cl, n, n_cand, bit_width((uint64_t)ct.max_len, 1), bit_width((uint64_t)n, 1), s);
-            rst.batches += verify_batches(cl, n, repeat_words{ ps.d_words.p, d_woff.p, d_len.p }, cnt, tbeg, res.p, d_count.p, s);
+            rst.batches += verify_batches(cl, n, repeat_words{ ps.d_words.p, rt.woff.p, rt.len.p }, cnt, tbeg, res.p, d_count.p, s);
         }
     }
     {
         vg_prof_scope ps_("dedup_trim", (double)n * 32.0);
-        hipLaunchKernelGGL(k_trepeat, dim3(grid_of(n)), dim3(TPB), 0, s, n, d_len.p, res.p, d_rep.p, d_eff.p);
+        hipLaunchKernelGGL(k_trepeat, dim3(blocks(n)), dim3(TPB), 0, s, n, rt.len.p, res.p, d_rep.p, d_eff.p);
         if (trim)
-            hipLaunchKernelGGL(k_trim, dim3(grid_of(ct.n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_eff.p, d_cbeg.p, n,
-                               ct.n_tasks);
+            hipLaunchKernelGGL(k_trim, dim3(wave_blocks(ct.n_tasks)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, d_eff.p, rt.beg.p, n, ct.n_tasks);
     }
     unsigned long long count[2] = { 0, 0 };
     d_rep.download(repeat_out, (size_t)n, s);
@@ -935,215 +923,279 @@ void repeats_device(const packed_set& ps, int64_t m, int64_t* repeat_out, vg_ded
     for (int64_t i = 0; i < n; ++i) { rst.with_repeat += repeat_out[i] > 0; rst.repeat_symbols += repeat_out[i]; }
 }
 
-// the device part: packed records (resident, of len[i] symbols each: the circles after repeats_device has trimmed them, else
-// ps.len) -> representative / strand on the host; off_out != nullptr: circular mode, which also fills the offsets
-void dedup_device(const packed_set& ps, const std::vector<int64_t>& len, int32_t* rep_out, int8_t* strand_out, int64_t* off_out,
-                  vg_dedup_stats& st) {
+// What the rounds of the plain and the circular mode share, in the order it is allocated: the keys per record, the unresolved
+// records A[0 .. na) in key order, the labels, the run heads hp per position, a count / scan pair, the members that differ.
+struct round_bufs {
+    dbuf<uint64_t> klo, khi, klen;
+    dbuf<int32_t> A, A2, d_rep, keep, at;
+    dbuf<int8_t> d_strand;
+    dbuf<int64_t> hp, hp2, cnt, tbeg;
+    dbuf<unsigned long long> d_ndiff;
+    void alloc_keys(size_t n) { klo.alloc(n); khi.alloc(n); klen.alloc(n); A.alloc(n); A2.alloc(n); }
+    void alloc_rounds(size_t n) {
+        d_rep.alloc(n); keep.alloc(n); at.alloc(n); d_strand.alloc(n); hp.alloc(n); hp2.alloc(n); cnt.alloc(n + 1); tbeg.alloc(n + 1); d_ndiff.alloc(1);
+    }
+};
+// each mode's own, allocated by that mode alone.  Plain: which strand gave a record's key; whether a member differs from its head.
+// Circular: the bits of an offset (it is below the length), the offsets, a member's smallest equal (strand << sbits | offset), the list.
+struct plain_state { dbuf<uint8_t> ori, diff; };
+struct circular_state { int sbits = 1; dbuf<int64_t> d_off; dbuf<unsigned long long> res; cand_list cl; };
+
+// the three stable passes over the keys (low hash half, high half, length): equal keys end up adjacent, in index order
+void sort_by_key(round_bufs& r, int64_t n, int bits, unsigned len_bits, hipStream_t s) {
+    vg_prof_scope ps_("dedup_sort", (double)n * 48.0);
+    dbuf<uint64_t> kg((size_t)n), ks((size_t)n);
+    const unsigned pass_bits[3] = { (unsigned)std::min(bits, 64), (unsigned)std::max(bits - 64, 0), len_bits };
+    const uint64_t* src[3] = { r.klo.p, r.khi.p, r.klen.p };
+    for (int pass = 0; pass < 3; ++pass) {
+        if (!pass_bits[pass]) continue;
+        hipLaunchKernelGGL(k_gather, dim3(blocks(n)), dim3(TPB), 0, s, src[pass], r.A.p, n, kg.p);
+        sort_pairs(kg, ks, r.A, r.A2, n, pass_bits[pass], s);
+    }
+}
+// hp[p] = the position of the head of p's run of equal keys among A[0 .. na): the start of either mode's dedup_runs scope
+void run_heads(round_bufs& r, int64_t na, hipStream_t s) {
+    hipLaunchKernelGGL(k_runs, dim3(blocks(na)), dim3(TPB), 0, s, r.A.p, na, r.klo.p, r.khi.p, r.klen.p, r.hp2.p);
+    scan(r.hp2.p, r.hp.p, na, true, rocprim::maximum<int64_t>(), s);
+}
+// One round of the plain mode: every member against its head in the orientation the two bits imply; the members that differ are kept.
+void plain_round(const packed_set& ps, const record_table& rt, round_bufs& r, plain_state& pl, int64_t na, hipStream_t s) {
+    {
+        vg_prof_scope ps_("dedup_runs", (double)na * 60.0);
+        run_heads(r, na, s);
+        hipLaunchKernelGGL(k_tasks, dim3(blocks(na + 1)), dim3(TPB), 0, s, r.A.p, na, r.hp.p, rt.len.p, r.cnt.p, pl.diff.p);
+        scan(r.cnt.p, r.tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
+    }
+    const int64_t n_vt = read_back(r.tbeg.p + na, s);        // (the element at na: the total; outside the scope, which times the group's kernels)
+    if (n_vt > 0) {
+        vg_prof_scope ps_("dedup_verify", (double)n_vt * VERIFY_CHUNK * 8.0);
+        hipLaunchKernelGGL(k_verify, dim3(wave_blocks(n_vt)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, pl.ori.p, r.A.p, na, r.hp.p, r.tbeg.p, n_vt, pl.diff.p);
+    }
+    vg_prof_scope ps_("dedup_labels", (double)na * 24.0);
+    hipLaunchKernelGGL(k_resolve, dim3(blocks(na)), dim3(TPB), 0, s, r.A.p, na, r.hp.p, pl.diff.p, pl.ori.p, r.d_rep.p, r.d_strand.p, r.keep.p, r.d_ndiff.p);
+}
+// One round of the circular mode: res[p] = strand << sbits | offset of every member equal to its head in some rotation of one of
+// the head's strands, NO_OFFSET for the others, which are kept for the next round.  Candidates sorted by (position, strand, offset).
+void circular_round(const packed_set& ps, const record_table& rt, round_bufs& r, circular_state& ci, int64_t na, hipStream_t s) {
+    {
+        vg_prof_scope ps_("dedup_runs", (double)na * 60.0);
+        run_heads(r, na, s);
+    }
+    int64_t n_cand = 0;
+    {
+        vg_prof_scope ps_("dedup_ccand", (double)na * 16.0);
+        hipLaunchKernelGGL(k_ctasks, dim3(blocks(na + 1)), dim3(TPB), 0, s, r.A.p, na, r.hp.p, rt.len.p, ci.cl.nch.p, ci.res.p);
+        const int64_t n_ct = scan_total(ci.cl.nch.p, r.tbeg.p, na, s);        // (0: heads only)
+        if (n_ct > 0) n_cand = collect(ci.cl, na, std::max(ci.cl.owner.n, (size_t)(4 * na + 1024)), s, [&](const cand_slots& to) {
+            hipLaunchKernelGGL(k_ccand, dim3(wave_blocks(n_ct)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, r.A.p, na, r.hp.p, r.tbeg.p, n_ct, ci.sbits, to); });
+        if (n_cand > 0) order(ci.cl, na, n_cand, (unsigned)ci.sbits + 1, bit_width((uint64_t)na, 1), s);
+    }
+    if (n_cand > 0) {
+        vg_prof_scope ps_("dedup_cverify", 0.0);
+        verify_batches(ci.cl, na, rotation_words{ ps.d_words.p, rt.woff.p, rt.len.p, r.A.p, r.hp.p, ci.sbits }, r.cnt, r.tbeg, ci.res.p, nullptr, s);
+    }
+    vg_prof_scope ps_("dedup_labels", (double)na * 32.0);
+    hipLaunchKernelGGL(k_cresolve, dim3(blocks(na)), dim3(TPB), 0, s, r.A.p, na, r.hp.p, ci.res.p, ci.sbits, r.d_rep.p, r.d_strand.p, ci.d_off.p, r.keep.p, r.d_ndiff.p);
+}
+
+// The plain and the circular mode on the device: packed records (resident, of len[i] symbols each: the circles after repeats_device has
+// trimmed them, else ps.len) -> representative / strand (circular: and offset) on the host.  Hash and keys by mode, one sort, the mode's rounds.
+void dedup_device(const packed_set& ps, const std::vector<int64_t>& len, dedup_mode mode, int32_t* rep_out, int8_t* strand_out, int64_t* off_out, vg_dedup_stats& st) {
     const int64_t n = ps.n;
     if (n == 0) return;
-    const bool circular = off_out != nullptr;
+    const bool circular = mode == MODE_CIRCULAR;
     hipStream_t s = vg_stream();
     const int bits = g_hash_bits.load();
     const chunk_tasks ct = chunk_tasks_of(len);
-    const int64_t n_tasks = ct.n_tasks, total_words = ct.total_words;
     const unsigned len_bits = bit_width((uint64_t)ct.max_len, 0);
-    const int sbits = (int)std::max(1u, len_bits);       // circular mode: an offset is below the length
-    dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_cbeg((size_t)n + 1);
-    d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(len.data(), (size_t)n, s); d_cbeg.upload(ct.cbeg.data(), (size_t)n + 1, s);
+    record_table rt(ps, len, ct.cbeg, s);
+    round_bufs r;
+    plain_state pl;                          // (each allocated by its mode alone)
+    circular_state ci;
     dbuf<unsigned long long> d_h((size_t)n * 4);
     d_h.zero(s);
-    if (circular) {
-        vg_prof_scope ps_("dedup_chash", (double)total_words * 4.0);
-        hipLaunchKernelGGL(k_chash, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, d_h.p);
-    } else {
-        vg_prof_scope ps_("dedup_hash", (double)total_words * 4.0);
-        hipLaunchKernelGGL(k_hash, dim3(grid_of(n_tasks, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_cbeg.p, n, n_tasks, d_h.p);
+    {
+        vg_prof_scope ps_(circular ? "dedup_chash" : "dedup_hash", (double)ct.total_words * 4.0);
+        hipLaunchKernelGGL((circular ? k_chash : k_hash), dim3(wave_blocks(ct.n_tasks)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, rt.beg.p, n, ct.n_tasks, d_h.p);
     }
-    d_cbeg.release();
-    dbuf<uint64_t> klo((size_t)n), khi((size_t)n), klen((size_t)n);
-    dbuf<uint8_t> ori((size_t)n);
-    dbuf<int32_t> A((size_t)n), A2((size_t)n);
+    rt.beg.release();
+    r.alloc_keys((size_t)n);
+    if (!circular) pl.ori.alloc((size_t)n);
     {
         vg_prof_scope ps_("dedup_keys", (double)n * 66.0);
-        if (circular) hipLaunchKernelGGL(k_ckeys, dim3(grid_of(n)), dim3(TPB), 0, s, d_h.p, d_len.p, n, bits, klo.p, khi.p, klen.p, A.p);
-        else hipLaunchKernelGGL(k_keys, dim3(grid_of(n)), dim3(TPB), 0, s, d_h.p, d_len.p, n, bits, klo.p, khi.p, klen.p, ori.p, A.p);
+        if (circular) hipLaunchKernelGGL(k_ckeys, dim3(blocks(n)), dim3(TPB), 0, s, d_h.p, rt.len.p, n, bits, r.klo.p, r.khi.p, r.klen.p, r.A.p);
+        else hipLaunchKernelGGL(k_keys, dim3(blocks(n)), dim3(TPB), 0, s, d_h.p, rt.len.p, n, bits, r.klo.p, r.khi.p, r.klen.p, pl.ori.p, r.A.p);
     }
     d_h.release();
-    sort_by_key(klo, khi, klen, A, A2, n, bits, len_bits, s);
-    dbuf<int32_t> d_rep((size_t)n), keep((size_t)n), at((size_t)n);
-    dbuf<int8_t> d_strand((size_t)n);
-    dbuf<int64_t> hp((size_t)n), hp2((size_t)n), cnt((size_t)n + 1), tbeg((size_t)n + 1);
-    dbuf<uint8_t> diff((size_t)n);
-    dbuf<unsigned long long> d_ndiff(1);
-    dbuf<int64_t> d_off;
-    dbuf<unsigned long long> res;
-    cand_list cl;
-    if (circular) { d_off.alloc((size_t)n); res.alloc((size_t)n); cl.alloc_owners(n); }
-    int64_t na = n;
-    while (na > 0) {
+    sort_by_key(r, n, bits, len_bits, s);
+    r.alloc_rounds((size_t)n);
+    if (circular) {
+        ci.sbits = (int)std::max(1u, len_bits);
+        ci.d_off.alloc((size_t)n); ci.res.alloc((size_t)n); ci.cl.alloc_owners(n);
+    }
+    else pl.diff.alloc((size_t)n);
+    for (int64_t na = n; na > 0;) {
         ++st.rounds;
-        d_ndiff.zero(s);
-        {
-            vg_prof_scope ps_("dedup_runs", (double)na * 60.0);
-            hipLaunchKernelGGL(k_runs, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, klo.p, khi.p, klen.p, hp2.p);
-            scan(hp2.p, hp.p, na, true, rocprim::maximum<int64_t>(), s);
-            if (!circular) {
-                hipLaunchKernelGGL(k_tasks, dim3(grid_of(na + 1)), dim3(TPB), 0, s, A.p, na, hp.p, d_len.p, cnt.p, diff.p);
-                scan(cnt.p, tbeg.p, na + 1, false, rocprim::plus<int64_t>(), s);
-            }
-        }
-        if (circular) {
-            circular_round(ps, d_woff.p, d_len.p, A.p, na, hp.p, cnt, tbeg, cl, sbits, res.p, s);
-            vg_prof_scope ps_("dedup_labels", (double)na * 32.0);
-            hipLaunchKernelGGL(k_cresolve, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, hp.p, res.p, sbits, d_rep.p, d_strand.p, d_off.p, keep.p, d_ndiff.p);
-        } else {
-            int64_t n_vt = 0;
-            vg_download_bytes(&n_vt, tbeg.p + na, sizeof n_vt, s);          // (the element at na: the total)
-            VG_HIP(hipStreamSynchronize(s));
-            if (n_vt > 0) {
-                vg_prof_scope ps_("dedup_verify", (double)n_vt * VERIFY_CHUNK * 8.0);
-                hipLaunchKernelGGL(k_verify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, ori.p, A.p, na,
-                                   hp.p, tbeg.p, n_vt, diff.p);
-            }
-            vg_prof_scope ps_("dedup_labels", (double)na * 24.0);
-            hipLaunchKernelGGL(k_resolve, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, hp.p, diff.p, ori.p, d_rep.p, d_strand.p, keep.p, d_ndiff.p);
-        }
-        unsigned long long nd = 0;
-        d_ndiff.download(&nd, 1, s);
-        VG_HIP(hipStreamSynchronize(s));
+        r.d_ndiff.zero(s);
+        circular ? circular_round(ps, rt, r, ci, na, s) : plain_round(ps, rt, r, pl, na, s);
+        const unsigned long long nd = read_back(r.d_ndiff.p, s);
         if (nd == 0) break;
         st.collisions += (int64_t)nd;
         {
             vg_prof_scope ps_("dedup_compact", (double)na * 12.0);
-            scan(keep.p, at.p, na, false, rocprim::plus<int32_t>(), s);
-            hipLaunchKernelGGL(k_compact, dim3(grid_of(na)), dim3(TPB), 0, s, A.p, na, keep.p, at.p, A2.p);
+            scan(r.keep.p, r.at.p, na, false, rocprim::plus<int32_t>(), s);
+            hipLaunchKernelGGL(k_compact, dim3(blocks(na)), dim3(TPB), 0, s, r.A.p, na, r.keep.p, r.at.p, r.A2.p);
         }
-        std::swap(A.p, A2.p);
+        std::swap(r.A.p, r.A2.p);
         na = (int64_t)nd;
     }
-    d_rep.download(rep_out, (size_t)n, s);
-    d_strand.download(strand_out, (size_t)n, s);
-    if (circular) d_off.download(off_out, (size_t)n, s);
+    r.d_rep.download(rep_out, (size_t)n, s);
+    r.d_strand.download(strand_out, (size_t)n, s);
+    if (circular) ci.d_off.download(off_out, (size_t)n, s);
     VG_HIP(hipStreamSynchronize(s));
+}
+
+// The contained mode's plan, computed before anything is allocated: the index positions (pbeg[i] = record i's first, one per
+// symbol), the bits of an offset and the order by (length descending, index ascending) of the result key, the positions per pass.
+struct contained_plan {
+    std::vector<int64_t> pbeg;
+    int64_t total_pos = 0, per_pass = 0;
+    int sbits = 1, anchor = 16;
+    std::vector<int32_t> order, rnk;         // order[rank] = record, rnk[record] = rank
+};
+contained_plan plan_contained(const packed_set& ps) {
+    const int64_t n = ps.n;
+    contained_plan pl;
+    pl.pbeg.assign((size_t)n + 1, 0);
+    int64_t max_len = 0;
+    for (int64_t i = 0; i < n; ++i) { pl.pbeg[(size_t)i + 1] = pl.pbeg[(size_t)i] + ps.len[(size_t)i]; max_len = std::max(max_len, ps.len[(size_t)i]); }
+    pl.total_pos = pl.pbeg[(size_t)n];
+    // (bit_width(x, 1) is what two hand-written loops gave here: their stops at 63 and 32 bits are out of reach of a length < 2^63 and of n - 1 < 2^31)
+    pl.sbits = (int)bit_width((uint64_t)max_len, 1);
+    if ((int)bit_width((uint64_t)(n - 1), 1) + 1 + pl.sbits > 64)
+        throw vg_error(VG_EOVERFLOW, "vg_deduplicate_contained: record count and longest record together exceed the 64-bit result key");
+    pl.order.resize((size_t)n); pl.rnk.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) pl.order[(size_t)i] = (int32_t)i;
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](int32_t a, int32_t b) { return ps.len[(size_t)a] > ps.len[(size_t)b]; });
+    for (int64_t r = 0; r < n; ++r) pl.rnk[(size_t)pl.order[(size_t)r]] = (int32_t)r;
+    if (pl.total_pos == 0) return pl;        // (nothing to index: no device call at all)
+    pl.anchor = g_anchor_symbols.load();
+    pl.per_pass = g_index_positions.load();
+    if (pl.per_pass <= 0) {
+        size_t fr = 0, tot = 0;
+        VG_HIP(hipMemGetInfo(&fr, &tot));
+        pl.per_pass = std::max<int64_t>(1 << 20, (int64_t)(fr / 2) / INDEX_BYTES);
+    }
+    pl.per_pass = std::min(std::min(pl.per_pass, pl.total_pos), MAX_PASS_POSITIONS);
+    return pl;
+}
+// The device side of a contained call: its buffers in the order they are allocated, one index pass, one slice of its hits.
+struct contained_run {
+    const packed_set& ps; const contained_plan& pl; vg_dedup_contained_stats& cst; hipStream_t s;
+    const int64_t n = ps.n, nq = 2 * ps.n;   // records; queries (record, strand)
+    record_table rt{ ps, ps.len, pl.pbeg, s };
+    dbuf<int32_t> d_rnk{ (size_t)n };
+    dbuf<unsigned long long> d_best{ (size_t)n }, d_count{ 2 };            // d_count: [0] candidates of a slice, [1] equal candidates
+    dbuf<int64_t> hlo{ (size_t)nq + 1 }, hcnt{ (size_t)nq + 1 }, hoff{ (size_t)nq + 1 };       // per query: first hit key, hits, first hit of the pass
+    dbuf<uint32_t> cq{ (size_t)CAND_SLICE }, bad{ (size_t)CAND_SLICE };    // the candidate queue of a slice: query, flag,
+    dbuf<int32_t> cj{ (size_t)CAND_SLICE };                                //   container,
+    dbuf<int64_t> cs{ (size_t)CAND_SLICE }, cnt{ (size_t)CAND_SLICE + 1 }, tbeg{ (size_t)CAND_SLICE + 1 };      //   position; tasks per candidate, their scan
+    dbuf<uint64_t> key; dbuf<int64_t> val;   // the sorted index of the pass
+    // the positions [pos0, pos0 + np): windows, sort, and the lookup of every query, which leaves the hit ranges -> the hits of the pass
+    int64_t index_pass(int64_t pos0, int64_t np) {
+        val.release(); key.release();        // (the pass before)
+        key.alloc((size_t)np); val.alloc((size_t)np);
+        {
+            vg_prof_scope ps_("dedupc_windows", (double)np * 16.5);
+            hipLaunchKernelGGL(k_sub_windows, dim3(grid_for(np, TPB, 65536)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, rt.beg.p, n, pos0, np, key.p, val.p);
+        }
+        {
+            vg_prof_scope ps_("dedupc_sort", (double)np * 64.0);
+            dbuf<uint64_t> key2((size_t)np);
+            dbuf<int64_t> val2((size_t)np);
+            sort_pairs(key, key2, val, val2, np, 64u, s);
+        }
+        vg_prof_scope ps_("dedupc_lookup", (double)nq * 40.0);
+        hipLaunchKernelGGL(k_sub_lookup, dim3(blocks(nq + 1)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, n, pl.anchor, key.p, np, hlo.p, hcnt.p);
+        return scan_total(hcnt.p, hoff.p, nq, s);
+    }
+    // the hits h0 .. h1 - 1 of the pass: candidates, verification tasks, verify, pick into d_best
+    void verify_slice(int64_t h0, int64_t h1) {
+        int64_t nc = 0;
+        {
+            vg_prof_scope ps_("dedupc_lookup", (double)(h1 - h0) * 32.0);
+            VG_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), s));
+            hipLaunchKernelGGL(k_sub_cands, dim3(blocks(h1 - h0)), dim3(TPB), 0, s, rt.len.p, rt.beg.p, n, hoff.p, hlo.p, val.p, h0, h1, cq.p, cj.p, cs.p, d_count.p);
+            nc = (int64_t)read_back(d_count.p, s);
+        }
+        if (nc == 0) return;
+        cst.candidates += nc;
+        {
+            vg_prof_scope ps_("dedupc_verify", 0.0);
+            hipLaunchKernelGGL(k_sub_tasks, dim3(blocks(nc + 1)), dim3(TPB), 0, s, cq.p, nc, rt.len.p, cnt.p, bad.p);
+            const int64_t n_vt = scan_total(cnt.p, tbeg.p, nc, s);
+            hipLaunchKernelGGL(k_sub_verify, dim3(wave_blocks(n_vt)), dim3(TPB), 0, s, ps.d_words.p, rt.woff.p, rt.len.p, cq.p, cj.p, cs.p, nc, tbeg.p, n_vt, bad.p);
+        }
+        vg_prof_scope ps_("dedupc_pick", (double)nc * 24.0);
+        hipLaunchKernelGGL(k_sub_pick, dim3(blocks(nc)), dim3(TPB), 0, s, rt.len.p, d_rnk.p, n, cq.p, cj.p, cs.p, nc, bad.p, pl.sbits, d_best.p, d_count.p + 1);
+    }
+};
+// the host decode of best[]: the container's rank, '+' before '-', the offset; the empty records form one group
+void contained_labels(const packed_set& ps, const contained_plan& pl, const std::vector<unsigned long long>& best, int32_t* rep_out, int8_t* strand_out, int64_t* off_out) {
+    const int64_t n = ps.n;
+    int64_t first_empty = -1;
+    const unsigned long long m = (1ull << pl.sbits) - 1;
+    for (int64_t i = 0; i < n; ++i) {
+        rep_out[i] = (int32_t)i; strand_out[i] = 0; off_out[i] = 0;
+        if (ps.len[(size_t)i] == 0) { if (first_empty < 0) first_empty = i; else rep_out[i] = (int32_t)first_empty; continue; }
+        const unsigned long long b = best[(size_t)i];
+        if (!b) continue;
+        rep_out[i] = pl.order[(size_t)(n - 1 - (int64_t)(b >> (pl.sbits + 1)))];
+        strand_out[i] = ((b >> pl.sbits) & 1ull) ? 0 : 1;
+        off_out[i] = (int64_t)(m - (b & m));
+    }
 }
 
 // Contained mode on the device: packed records (resident) -> representative / strand / offset on the host.  Every equal
 // candidate is a container of its record, and the largest key among them names a kept record: were the longest, earliest
 // container removed, its own container (longer, or equal and earlier) would contain the record too and have a larger key.
 // So one reduction over all candidates of all passes gives the representative; no second phase over the kept records.
-void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, int64_t* off_out, vg_dedup_stats& st,
-                      vg_dedup_contained_stats& cst) {
+void contained_device(const packed_set& ps, int32_t* rep_out, int8_t* strand_out, int64_t* off_out, vg_dedup_stats& st, vg_dedup_contained_stats& cst) {
     const int64_t n = ps.n;
     if (n == 0) return;
     hipStream_t s = vg_stream();
-    std::vector<int64_t> pbeg((size_t)n + 1, 0);
-    int64_t max_len = 0;
-    for (int64_t i = 0; i < n; ++i) { pbeg[(size_t)i + 1] = pbeg[(size_t)i] + ps.len[(size_t)i]; max_len = std::max(max_len, ps.len[(size_t)i]); }
-    const int64_t total_pos = pbeg[(size_t)n];
-    int sbits = 1; while (sbits < 63 && (max_len >> sbits)) ++sbits;
-    int rbits = 1; while (rbits < 32 && ((n - 1) >> rbits)) ++rbits;
-    if (rbits + 1 + sbits > 64)
-        throw vg_error(VG_EOVERFLOW, "vg_deduplicate_contained: record count and longest record together exceed the 64-bit result key");
-    std::vector<int32_t> order((size_t)n), rnk((size_t)n);      // by (length descending, index ascending)
-    for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (int32_t)i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ps.len[(size_t)a] > ps.len[(size_t)b]; });
-    for (int64_t r = 0; r < n; ++r) rnk[(size_t)order[(size_t)r]] = (int32_t)r;
+    const contained_plan pl = plan_contained(ps);
     std::vector<unsigned long long> best((size_t)n, 0ull);
-    if (total_pos > 0) {
-        const int anchor = g_anchor_symbols.load();
-        int64_t per_pass = g_index_positions.load();
-        if (per_pass <= 0) {
-            size_t fr = 0, tot = 0;
-            VG_HIP(hipMemGetInfo(&fr, &tot));
-            per_pass = std::max<int64_t>(1 << 20, (int64_t)(fr / 2) / INDEX_BYTES);
-        }
-        per_pass = std::min(std::min(per_pass, total_pos), MAX_PASS_POSITIONS);
-        dbuf<int64_t> d_woff((size_t)n), d_len((size_t)n), d_pbeg((size_t)n + 1);
-        dbuf<int32_t> d_rnk((size_t)n);
-        dbuf<unsigned long long> d_best((size_t)n), d_count(2);          // [0] candidates of a slice, [1] equal candidates
-        d_woff.upload(ps.woff.data(), (size_t)n, s); d_len.upload(ps.len.data(), (size_t)n, s); d_pbeg.upload(pbeg.data(), (size_t)n + 1, s);
-        d_rnk.upload(rnk.data(), (size_t)n, s);
-        d_best.zero(s); d_count.zero(s);
-        const int64_t nq = 2 * n;
-        dbuf<int64_t> hlo((size_t)nq + 1), hcnt((size_t)nq + 1), hoff((size_t)nq + 1);
-        dbuf<uint32_t> cq((size_t)CAND_SLICE), bad((size_t)CAND_SLICE);
-        dbuf<int32_t> cj((size_t)CAND_SLICE);
-        dbuf<int64_t> cs((size_t)CAND_SLICE), cnt((size_t)CAND_SLICE + 1), tbeg((size_t)CAND_SLICE + 1);
-        for (int64_t pos0 = 0; pos0 < total_pos; pos0 += per_pass) {
-            const int64_t np = std::min(per_pass, total_pos - pos0);
+    if (pl.total_pos > 0) {
+        contained_run run{ ps, pl, cst, s };
+        run.d_rnk.upload(pl.rnk.data(), (size_t)n, s);
+        run.d_best.zero(s); run.d_count.zero(s);
+        for (int64_t pos0 = 0; pos0 < pl.total_pos; pos0 += pl.per_pass) {
+            const int64_t np = std::min(pl.per_pass, pl.total_pos - pos0);
             ++cst.passes; cst.positions += np;
-            dbuf<uint64_t> key((size_t)np);
-            dbuf<int64_t> val((size_t)np);
-            {
-                vg_prof_scope ps_("dedupc_windows", (double)np * 16.5);
-                hipLaunchKernelGGL(k_sub_windows, dim3(grid_of(np, TPB, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, d_pbeg.p, n, pos0, np,
-                                   key.p, val.p);
-            }
-            {
-                vg_prof_scope ps_("dedupc_sort", (double)np * 64.0);
-                dbuf<uint64_t> key2((size_t)np);
-                dbuf<int64_t> val2((size_t)np);
-                sort_pairs(key, key2, val, val2, np, 64u, s);
-            }
-            int64_t n_hits = 0;
-            {
-                vg_prof_scope ps_("dedupc_lookup", (double)nq * 40.0);
-                hipLaunchKernelGGL(k_sub_lookup, dim3(grid_of(nq + 1)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, n, anchor, key.p, np, hlo.p, hcnt.p);
-                scan(hcnt.p, hoff.p, nq + 1, false, rocprim::plus<int64_t>(), s);
-                vg_download_bytes(&n_hits, hoff.p + nq, sizeof n_hits, s);
-                VG_HIP(hipStreamSynchronize(s));
-            }
+            const int64_t n_hits = run.index_pass(pos0, np);
             cst.hits += n_hits;
-            for (int64_t h0 = 0; h0 < n_hits; h0 += CAND_SLICE) {
-                const int64_t h1 = std::min(n_hits, h0 + CAND_SLICE);
-                unsigned long long nc = 0;
-                ++cst.slices;
-                {
-                    vg_prof_scope ps_("dedupc_lookup", (double)(h1 - h0) * 32.0);
-                    VG_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), s));
-                    hipLaunchKernelGGL(k_sub_cands, dim3(grid_of(h1 - h0)), dim3(TPB), 0, s, d_len.p, d_pbeg.p, n, hoff.p, hlo.p, val.p, h0, h1,
-                                       cq.p, cj.p, cs.p, d_count.p);
-                    d_count.download(&nc, 1, s);
-                    VG_HIP(hipStreamSynchronize(s));
-                }
-                if (nc == 0) continue;
-                cst.candidates += (int64_t)nc;
-                {
-                    vg_prof_scope ps_("dedupc_verify", 0.0);
-                    int64_t n_vt = 0;
-                    hipLaunchKernelGGL(k_sub_tasks, dim3(grid_of((int64_t)nc + 1)), dim3(TPB), 0, s, cq.p, (int64_t)nc, d_len.p, cnt.p, bad.p);
-                    scan(cnt.p, tbeg.p, (int64_t)nc + 1, false, rocprim::plus<int64_t>(), s);
-                    vg_download_bytes(&n_vt, tbeg.p + nc, sizeof n_vt, s);
-                    VG_HIP(hipStreamSynchronize(s));
-                    hipLaunchKernelGGL(k_sub_verify, dim3(grid_of(n_vt, WAVES, 65536)), dim3(TPB), 0, s, ps.d_words.p, d_woff.p, d_len.p, cq.p, cj.p, cs.p,
-                                       (int64_t)nc, tbeg.p, n_vt, bad.p);
-                }
-                vg_prof_scope ps_("dedupc_pick", (double)nc * 24.0);
-                hipLaunchKernelGGL(k_sub_pick, dim3(grid_of((int64_t)nc)), dim3(TPB), 0, s, d_len.p, d_rnk.p, n, cq.p, cj.p, cs.p, (int64_t)nc, bad.p, sbits,
-                                   d_best.p, d_count.p + 1);
-            }
+            for (int64_t h0 = 0; h0 < n_hits; h0 += CAND_SLICE, ++cst.slices) run.verify_slice(h0, std::min(n_hits, h0 + CAND_SLICE));
         }
-        unsigned long long n_equal = 0;
-        d_best.download(best.data(), (size_t)n, s);
-        vg_download_bytes(&n_equal, d_count.p + 1, sizeof n_equal, s);
-        VG_HIP(hipStreamSynchronize(s));
-        cst.verified = (int64_t)n_equal;
+        run.d_best.download(best.data(), (size_t)n, s);
+        cst.verified = (int64_t)read_back(run.d_count.p + 1, s);
     }
     st.rounds = cst.passes; st.collisions = cst.candidates - cst.verified;
-    int64_t first_empty = -1;
-    const unsigned long long m = (1ull << sbits) - 1;
-    for (int64_t i = 0; i < n; ++i) {
-        rep_out[i] = (int32_t)i; strand_out[i] = 0; off_out[i] = 0;
-        if (ps.len[(size_t)i] == 0) { if (first_empty < 0) first_empty = i; else rep_out[i] = (int32_t)first_empty; continue; }
-        const unsigned long long b = best[(size_t)i];
-        if (!b) continue;
-        rep_out[i] = order[(size_t)(n - 1 - (int64_t)(b >> (sbits + 1)))];
-        strand_out[i] = ((b >> sbits) & 1ull) ? 0 : 1;
-        off_out[i] = (int64_t)(m - (b & m));
-    }
+    contained_labels(ps, pl, best, rep_out, strand_out, off_out);
 }
 
-void finish_stats(int64_t n, const int32_t* rep, const int8_t* strand, vg_dedup_stats& st) {
+// a deduplicate call on the packed set, whatever the entry point: the mode's device part (min_repeat > 0: after the terminal repeats), the counts
+void run_mode(const packed_set& ps, dedup_mode mode, int64_t min_repeat, int32_t* rep, int8_t* strand, int64_t* offset, int64_t* repeat, vg_dedup_stats& st,
+              vg_dedup_contained_stats& cst, vg_dedup_repeat_stats& rst) {
+    const int64_t n = ps.n;
+    if (mode == MODE_CONTAINED) contained_device(ps, rep, strand, offset, st, cst);
+    else if (min_repeat > 0) {
+        repeats_device(ps, min_repeat, repeat, rst, true);
+        std::vector<int64_t> eff((size_t)n);
+        for (int64_t i = 0; i < n; ++i) eff[(size_t)i] = ps.len[(size_t)i] - repeat[i];
+        dedup_device(ps, eff, mode, rep, strand, offset, st);
+    }
+    else dedup_device(ps, ps.len, mode, rep, strand, offset, st);
     st.records = n; st.unique = 0; st.reverse = 0;
     for (int64_t i = 0; i < n; ++i) { st.unique += rep[i] == (int32_t)i; st.reverse += rep[i] != (int32_t)i && strand[i]; }
     st.removed = n - st.unique;
@@ -1219,8 +1271,29 @@ void write_duplicates(const char* path, const vg_fasta_text& in, const std::vect
     }
     write_all(path, { { out.data(), out.size() } });
 }
-enum dedup_mode { MODE_PLAIN, MODE_CIRCULAR, MODE_CONTAINED };
+// the array arguments of an array-level call, before anything is packed: fn names the call in the messages, outputs: its output arrays are all there
+void check_seq_arrays(const std::string& fn, const char* ascii, const int64_t* offsets, int64_t n, bool outputs) {
+    if (n < 0) throw vg_error(VG_EINVAL, fn + ": negative count");
+    if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, fn + ": 2^31 or more records (record indices are int32)");
+    if (n && (!offsets || !outputs)) throw vg_error(VG_EINVAL, fn + ": null argument");
+    if (n && offsets[n] > offsets[0] && !ascii) throw vg_error(VG_EINVAL, fn + ": null sequence buffer");
+    for (int64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) throw vg_error(VG_EINVAL, fn + ": offsets must not decrease");
+}
+// packs and uploads the n > 0 sequences of an array-level call; a byte outside the alphabet is the error, named by its record
+void pack_seqs(const char* ascii, const int64_t* offsets, int64_t n, packed_set& ps) {
+    std::vector<std::pair<const char*, const char*>> seq((size_t)n);
+    for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
+    pack_and_upload(seq, vg_host_threads(), ps);
+    if (ps.bad_rec >= 0)
+        throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
+}
 
+// the caller's stats struct, zeroed, or the local one where the caller passed none
+template <class T> T& cleared(T* p, T& local) {
+    if (p) *p = T{};
+    return p ? *p : local;
+}
 // min_repeat > 0 (circular mode only): terminal repeats of at least that many symbols are taken off first; repeat[n] gets them
 int dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, dedup_mode mode, int32_t* representative, int8_t* strand, int64_t* offset,
                vg_dedup_stats* stats, vg_dedup_contained_stats* cstats, int64_t min_repeat = 0, int64_t* repeat = nullptr,
@@ -1229,35 +1302,15 @@ int dedup_seqs(const char* ascii, const int64_t* offsets, int64_t n, dedup_mode 
     if (n > 0 && min_repeat > 0 && !repeat) throw vg_error(VG_EINVAL, "vg_dedup_seqs_circular_tr: the repeat array is required");
     if (n > 0 && mode == MODE_CIRCULAR && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_ex: circular mode needs the offset array");
     if (n > 0 && mode == MODE_CONTAINED && !offset) throw vg_error(VG_EINVAL, "vg_dedup_seqs_contained: the offset array is required");
-    if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_seqs: negative count");
-    if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_dedup_seqs: 2^31 or more records (record indices are int32)");
-    if (n && (!offsets || !representative || !strand)) throw vg_error(VG_EINVAL, "vg_dedup_seqs: null argument");
-    if (n && offsets[n] > offsets[0] && !ascii) throw vg_error(VG_EINVAL, "vg_dedup_seqs: null sequence buffer");
-    for (int64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) throw vg_error(VG_EINVAL, "vg_dedup_seqs: offsets must not decrease");
-    vg_dedup_stats st_local{}; vg_dedup_stats& st = stats ? *stats : st_local;
-    st = vg_dedup_stats{};
-    vg_dedup_contained_stats cst_local{}; vg_dedup_contained_stats& cst = cstats ? *cstats : cst_local;
-    cst = vg_dedup_contained_stats{};
-    vg_dedup_repeat_stats rst_local{}; vg_dedup_repeat_stats& rst = rstats ? *rstats : rst_local;
-    rst = vg_dedup_repeat_stats{};
+    check_seq_arrays("vg_dedup_seqs", ascii, offsets, n, representative && strand);
+    vg_dedup_stats st_local{}; vg_dedup_stats& st = cleared(stats, st_local);
+    vg_dedup_contained_stats cst_local{}; vg_dedup_contained_stats& cst = cleared(cstats, cst_local);
+    vg_dedup_repeat_stats rst_local{}; vg_dedup_repeat_stats& rst = cleared(rstats, rst_local);
     if (n == 0) return VG_OK;
-    std::vector<std::pair<const char*, const char*>> seq((size_t)n);
-    for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
     packed_set ps;
-    pack_and_upload(seq, vg_host_threads(), ps);
-    if (ps.bad_rec >= 0)
-        throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
+    pack_seqs(ascii, offsets, n, ps);
     if (offset) std::fill(offset, offset + n, (int64_t)0);
-    if (mode == MODE_CONTAINED) contained_device(ps, representative, strand, offset, st, cst);
-    else if (min_repeat > 0) {
-        repeats_device(ps, min_repeat, repeat, rst, true);
-        std::vector<int64_t> eff((size_t)n);
-        for (int64_t i = 0; i < n; ++i) eff[(size_t)i] = ps.len[(size_t)i] - repeat[i];
-        dedup_device(ps, eff, representative, strand, offset, st);
-    }
-    else dedup_device(ps, ps.len, representative, strand, mode == MODE_CIRCULAR ? offset : nullptr, st);
-    finish_stats(n, representative, strand, st);
+    run_mode(ps, mode, min_repeat, representative, strand, offset, repeat, st, cst, rst);
     VG_API_END
 }
 
@@ -1300,35 +1353,23 @@ int deduplicate_files(const char* const* paths, int n_paths, const char* const* 
     vg_dedup_contained_stats cst{};
     vg_dedup_repeat_stats rst{};
     std::vector<int64_t> repeat(min_repeat > 0 ? (size_t)std::max<int64_t>(n, 1) : 0);
-    if (mode == MODE_CONTAINED) contained_device(ps, rep.data(), strand.data(), offset.data(), st, cst);
-    else if (min_repeat > 0) {
-        repeats_device(ps, min_repeat, repeat.data(), rst, true);
-        std::vector<int64_t> eff((size_t)n);
-        for (int64_t i = 0; i < n; ++i) eff[(size_t)i] = ps.len[(size_t)i] - repeat[(size_t)i];
-        dedup_device(ps, eff, rep.data(), strand.data(), offset.data(), st);
-    }
-    else dedup_device(ps, ps.len, rep.data(), strand.data(), with_offset ? offset.data() : nullptr, st);
-    finish_stats(n, rep.data(), strand.data(), st);
+    run_mode(ps, mode, min_repeat, rep.data(), strand.data(), offset.data(), repeat.data(), st, cst, rst);
     ps.d_words.release();
     vg_host_mark("dedup: groups computed");
     write_fasta(out_path, in, prefix, rep.data(), p->gzip_level, T);
     write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), with_offset ? offset.data() : nullptr,
                      min_repeat > 0 ? repeat.data() : nullptr);
     vg_host_mark("dedup: written");
-    if (p->verbosity >= 1 && mode == MODE_CONTAINED)
-        fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld on the reverse strand), %lld anchor hits, %lld candidates, "
-                        "%lld of them equal, %lld index passes\n",
-                (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)cst.hits,
-                (long long)cst.candidates, (long long)cst.verified, (long long)cst.passes);
-    else if (p->verbosity >= 1 && min_repeat > 0)
-        fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds, "
-                        "%lld records with a terminal repeat (%lld symbols)\n",
-                (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
-                (long long)st.rounds, (long long)rst.with_repeat, (long long)rst.repeat_symbols);
-    else if (p->verbosity >= 1)
-        fprintf(stderr, "vg_deduplicate: %lld records, %lld unique, %lld removed (%lld as reverse complements), %lld hash collisions in %lld rounds\n",
-                (long long)st.records, (long long)st.unique, (long long)st.removed, (long long)st.reverse, (long long)st.collisions,
-                (long long)st.rounds);
+    if (p->verbosity >= 1) {
+        auto N = [](int64_t v) { return std::to_string(v); };
+        std::string line = "vg_deduplicate: " + N(st.records) + " records, " + N(st.unique) + " unique, " + N(st.removed) + " removed (" + N(st.reverse);
+        if (mode == MODE_CONTAINED)
+            line += " on the reverse strand), " + N(cst.hits) + " anchor hits, " + N(cst.candidates) + " candidates, " + N(cst.verified) +
+                    " of them equal, " + N(cst.passes) + " index passes";
+        else line += " as reverse complements), " + N(st.collisions) + " hash collisions in " + N(st.rounds) + " rounds";
+        if (mode != MODE_CONTAINED && min_repeat > 0) line += ", " + N(rst.with_repeat) + " records with a terminal repeat (" + N(rst.repeat_symbols) + " symbols)";
+        fprintf(stderr, "%s\n", line.c_str());
+    }
     VG_API_END
 }
 }  // namespace
@@ -1370,19 +1411,10 @@ extern "C" int vg_deduplicate_contained(const char* const* paths, int n_paths, c
 extern "C" int vg_dedup_terminal_repeats(const char* ascii, const int64_t* offsets, int64_t n, int64_t min_repeat, int64_t* repeat) {
     VG_API_BEGIN
     if (min_repeat < 1) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: min_repeat must be at least 1");
-    if (n < 0) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: negative count");
-    if (n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_dedup_terminal_repeats: 2^31 or more records (record indices are int32)");
-    if (n && (!offsets || !repeat)) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: null argument");
-    if (n && offsets[n] > offsets[0] && !ascii) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: null sequence buffer");
-    for (int64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) throw vg_error(VG_EINVAL, "vg_dedup_terminal_repeats: offsets must not decrease");
+    check_seq_arrays("vg_dedup_terminal_repeats", ascii, offsets, n, repeat != nullptr);
     if (n == 0) return VG_OK;
-    std::vector<std::pair<const char*, const char*>> seq((size_t)n);
-    for (int64_t i = 0; i < n; ++i) seq[(size_t)i] = { ascii + offsets[i], ascii + offsets[i + 1] };
     packed_set ps;
-    pack_and_upload(seq, vg_host_threads(), ps);
-    if (ps.bad_rec >= 0)
-        throw vg_error(VG_EINVAL, "record " + std::to_string(ps.bad_rec) + ": '" + quote_byte(*ps.bad_at) + "' is not an IUPAC nucleotide code");
+    pack_seqs(ascii, offsets, n, ps);
     vg_dedup_repeat_stats rst{};
     repeats_device(ps, min_repeat, repeat, rst, false);
     VG_API_END
