@@ -69,6 +69,14 @@ typedef struct vg_genomes vg_genomes;
  * Genome name = first header token (multisample) or file name (directory mode). */
 int vg_genomes_load(const char* const* paths, int n_paths, int multisample, int n_threads,
                     vg_genomes** out);
+/* A database and new genomes as ONE set: the genomes of db_paths, then those of new_paths; *n_db_genomes receives the number of
+ * database genomes (ids 0 .. n_db - 1; the new ones are n_db .. n - 1).  The set is what vg_genomes_load would make of the
+ * concatenated input.  multisample: exactly one file on each side, one genome per record, the records of the database file first
+ * (any other count is VG_EINVAL); otherwise one genome per file.  A name that occurs on both sides is VG_EINVAL naming it (the
+ * filter reader maps names to ids), and so is a combined set of fewer than two genomes; both are raised before anything is packed.  Stands in for the input of `kmer-db new2all`; vclust.py has
+ * no call site for it. */
+int vg_genomes_load_db_new(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
+                           int n_threads, vg_genomes** out, int* n_db_genomes);
 /* synthetic / in-memory input: codes 0..3 = ACGT, >3 = N; genome g = codes[offsets[g] ..
  * offsets[g+1]); names may be NULL ("g<idx>") */
 int vg_genomes_from_codes(const uint8_t* codes, const int64_t* offsets, int n_genomes,
@@ -99,6 +107,23 @@ typedef struct { uint32_t a, b, shared; } vg_pair_count;   /* a > b (input order
 int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, int n_shards,
                    uint32_t min_shared, int64_t* set_sizes, vg_pair_count** pairs,
                    int64_t* n_pairs);
+/* New genomes against a database (`kmer-db new2all`; vclust.py never exposed it, so there is no call site).  The set is the
+ * database genomes 0 .. n_db - 1 followed by the new genomes n_db .. n - 1 (vg_genomes_load_db_new, or any set and any n_db).
+ * pairs: the result of vg_kmer_shared(g, k, fraction, 0, 1, min_shared, ...) restricted to the pairs (a, b), a > b, with
+ * a >= n_db -- every pair that contains a new genome, same counts.  n_db = 0 is that call's result; n_db = n gives no pair.
+ * set_sizes (n entries): exact for every new genome and for every database genome that occurs in a returned pair, -1 for the other
+ * database genomes.  vg_filter_pairs and vg_write_fltr read the sizes of the two genomes of a pair and no others, so they take
+ * these arrays as they are; vg_write_fltr then writes the all-vs-all file of the set with the database rows empty.
+ * One device.  n_db < 0 or n_db > n is VG_EINVAL, raised before any device use.
+ * Two routes, same result: the passes of vg_kmer_shared (every option, sub-shards included) with the SpGEMM
+ * launched over the new genomes' rows only; and, for a dense single pass (no fraction, no sub-shards, below 2^32 padded positions)
+ * that the bucket pipeline accepts, the masked route, which indexes only the k-mers a new genome can share (profile scope
+ * `kmer_new_mask`) and restores the sizes of the database genomes in pairs by a second masked pass (`kmer_new_sizes`). */
+int vg_kmer_shared_new(vg_genomes* g, int n_db, int k, double fraction, uint32_t min_shared, int64_t* set_sizes,
+                       vg_pair_count** pairs, int64_t* n_pairs);
+/* route of vg_kmer_shared_new: 0 (default) = automatic, 1 = never the masked route, 2 = the masked route wherever it applies (tests,
+ * tools/new2all_timing.py); no reference call site */
+void vg_set_new_path(int mode);
 /* distinct canonical k-mers of one genome, ascending (parity tests) */
 int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint64_t** out, int64_t* n_out);
 
@@ -127,6 +152,12 @@ typedef struct {            /* mirrors the prefilter sub-parser, vclust.py:208-2
 } vg_prefilter_params;
 int vg_prefilter(const char* const* fasta_paths, int n_paths, const char* out_path,
                  const vg_prefilter_params* p);
+/* vg_prefilter for new genomes against a database: vg_genomes_load_db_new + vg_kmer_shared_new + vg_write_fltr.  fltr.txt has the
+ * header over all n names and one row per genome; the database rows are empty (`name,`) and a new genome's row holds its partners
+ * among the database and the earlier new genomes: the all-vs-all file of the concatenated input with the first n_db rows emptied.
+ * (`kmer-db new2all` + distance; no vclust.py call site.) */
+int vg_prefilter_new(const char* const* db_paths, int n_db_paths, const char* const* new_paths, int n_new_paths,
+                     const char* out_path, const vg_prefilter_params* p);
 /* on != 0: the process ends right after its vg_prefilter / vg_align call, so the call leaves the genome set (GBs of host
  * and device memory) to the process exit instead of releasing it piece by piece first (vclust.py's one-shot processes;
  * no reference call site).  Off by default: an embedding process keeps the normal ownership. */
@@ -218,6 +249,13 @@ int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_pair_stat* 
                  const char* out_path, const vg_align_params* p);
 int vg_align(const char* const* fasta_paths, int n_paths, const char* out_path,
              const vg_align_params* p);
+
+/* vg_align for new genomes against a database (no vclust.py call site; lz-ani itself aligns what its filter names).  With
+ * p->filter_path it is vg_align on the combined set -- a filter written by vg_prefilter_new names only pairs with a new genome;
+ * without one it aligns every pair that contains a new genome.  The ids file lists all n genomes; ani.tsv and the alignment
+ * table hold only those pairs.  Indexes are built for the genomes the tasks name and no others, as in vg_align. */
+int vg_align_new(const char* const* db_paths, int n_db_paths, const char* const* new_paths, int n_new_paths,
+                 const char* out_path, const vg_align_params* p);
 
 /* ------------------------------------------------------------------ one process per GPU - */
 /* The reference is single-node / thread-parallel (no distributed layer); these entry points

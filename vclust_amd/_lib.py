@@ -123,6 +123,7 @@ SYMBOLS = {
     'vg_copy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     'vg_alloc_selftest': (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int]),
     'vg_genomes_load': (C.c_int, [P(C.c_char_p), C.c_int, C.c_int, C.c_int, P(C.c_void_p)]),
+    'vg_genomes_load_db_new': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_int, C.c_int, C.c_int, P(C.c_void_p), P(C.c_int)]),
     'vg_genomes_from_codes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, P(C.c_char_p), P(C.c_void_p)]),
     'vg_genomes_free': (None, [C.c_void_p]),
     'vg_genomes_count': (C.c_int, [C.c_void_p]),
@@ -133,12 +134,14 @@ SYMBOLS = {
     'vg_genomes_to_device': (C.c_int, [C.c_void_p]),
     'vg_kmer_shared': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint32,
                                  P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
+    'vg_kmer_shared_new': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
     'vg_kmer_set': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, P(P(C.c_uint64)), P(C.c_int64)]),
     'vg_filter_pairs': (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.c_int64, C.POINTER(PairCount), C.c_int64,
                                   C.POINTER(C.POINTER(PairCount)), C.POINTER(C.c_int64)]),
     'vg_write_fltr': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
                                 P(C.c_int64), P(PairCount), C.c_int64, C.c_char_p]),
     'vg_prefilter': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(PrefilterParams)]),
+    'vg_prefilter_new': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_int, C.c_char_p, P(PrefilterParams)]),
     'vg_set_process_ends_after_call': (None, [C.c_int]),
     'vg_set_lz_fit': (None, [P(LzFit)]),
     'vg_lz_align': (C.c_int, [C.c_void_p, P(Task), C.c_int64, P(LzParams), P(PairStat),
@@ -152,10 +155,12 @@ SYMBOLS = {
     'vg_set_index_budget': (None, [C.c_int64]),
     'vg_set_subshards': (None, [C.c_int]),
     'vg_set_range_scan': (None, [C.c_int]),
+    'vg_set_new_path': (None, [C.c_int]),
     'vg_set_placement_trials': (None, [C.c_int]),
     'vg_write_ani': (C.c_int, [C.c_void_p, P(Task), P(PairStat), C.c_int64, P(Region), C.c_int64,
                                C.c_char_p, P(AlignParams)]),
     'vg_align': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(AlignParams)]),
+    'vg_align_new': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_int, C.c_char_p, P(AlignParams)]),
     'vg_comm_create': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, P(C.c_void_p)]),
     'vg_rccl_unique_id': (C.c_int, [C.c_void_p, C.c_int64]),
     'vg_comm_rccl_create': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int64, P(C.c_void_p)]),

@@ -82,6 +82,19 @@ class GenomeSet:
         return cls(h)
 
     @classmethod
+    def load_db_new(cls, db_paths, new_paths, multisample, n_threads=1):
+        """-> (set, n_db): the genomes of db_paths (ids 0 .. n_db - 1) followed by those of new_paths, as one set.  multisample:
+        one multi-FASTA on each side; otherwise one genome per file.  A name on both sides is an error."""
+        lib = _lib.load()
+        db = (C.c_char_p * len(db_paths))(*[os.fsencode(str(p)) for p in db_paths])
+        new = (C.c_char_p * len(new_paths))(*[os.fsencode(str(p)) for p in new_paths])
+        h = C.c_void_p()
+        n_db = C.c_int()
+        check(lib.vg_genomes_load_db_new(db, len(db_paths), new, len(new_paths), int(bool(multisample)), int(n_threads), C.byref(h),
+                                         C.byref(n_db)))
+        return cls(h), n_db.value
+
+    @classmethod
     def from_codes(cls, codes, offsets, names=None):
         """codes: uint8 array (0..3 ACGT, >3 N); offsets: int64 array of n+1 entries."""
         lib = _lib.load()
@@ -141,6 +154,17 @@ class GenomeSet:
         npairs = C.c_int64()
         check(self._lib.vg_kmer_shared(self._h, k, float(fraction), shard, n_shards, int(min_shared),
                                        sizes.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pp), C.byref(npairs)))
+        return sizes[:n], _take(pp, npairs.value, PAIR_DTYPE)
+
+    def kmer_shared_new(self, n_db, k=25, fraction=1.0, min_shared=1):
+        """New genomes (ids n_db .. n - 1) against a database (ids 0 .. n_db - 1): kmer_shared restricted to the pairs a > b with
+        a >= n_db.  set_sizes are -1 for the database genomes that no returned pair names."""
+        n = len(self)
+        sizes = np.zeros(max(n, 1), dtype=np.int64)
+        pp = C.POINTER(PairCount)()
+        npairs = C.c_int64()
+        check(self._lib.vg_kmer_shared_new(self._h, int(n_db), k, float(fraction), int(min_shared),
+                                           sizes.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pp), C.byref(npairs)))
         return sizes[:n], _take(pp, npairs.value, PAIR_DTYPE)
 
     def kmer_set(self, idx, k=25, fraction=1.0):
@@ -501,6 +525,12 @@ def set_range_scan(mode):
 def set_placement_trials(n):
     """Placements of the prefilter workspace the first dense pass of this process may try (vg_set_placement_trials; 1 = none, the default)."""
     _lib.load().vg_set_placement_trials(int(n))
+
+
+def set_new_path(mode):
+    """Route of GenomeSet.kmer_shared_new (vg_set_new_path): 0 = automatic, 1 = never the masked route, 2 = the masked route wherever
+    it applies."""
+    _lib.load().vg_set_new_path(int(mode))
 
 
 def release_device_memory():

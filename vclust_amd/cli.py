@@ -89,6 +89,12 @@ def get_parser() -> argparse.ArgumentParser:
                          help='Output filename', required=True)
         return req
 
+    def db_arg(p):
+        p.add_argument('--db', metavar='<file>', type=_existing_path, dest='db_path',
+                       help='Database of genomes already processed (a FASTA file, or a directory of files, like -i): the genomes '
+                            'of -i are new to it, the genome set is the database followed by them, and only pairs that contain a '
+                            'new genome are computed (rows of an earlier run are matched by name: ids are those of the combined set)')
+
     parser = argparse.ArgumentParser(
         description=f'%(prog)s v{__version__}: calculate ANI and cluster virus (meta)genome sequences '
                     '(MI355X-native prefilter/align)',
@@ -122,6 +128,7 @@ def get_parser() -> argparse.ArgumentParser:
     # prefilter
     pf = sub.add_parser('prefilter', help='Prefilter genome pairs for alignment', formatter_class=fmt, add_help=False)
     io_args(pf, 'Input FASTA file or directory of files (gzipped or uncompressed)')
+    db_arg(pf)
     pf.add_argument('-k', '--k', metavar='<int>', type=int, default=25, choices=range(15, 31),
                     help='Size of k-mer for Kmer-db [%(default)s]')
     pf.add_argument('--min-kmers', metavar='<int>', type=int, default=20,
@@ -143,6 +150,7 @@ def get_parser() -> argparse.ArgumentParser:
     al = sub.add_parser('align', help='Align genome sequence pairs and calculate ANI measures',
                         formatter_class=fmt, add_help=False)
     io_args(al, 'Input FASTA file or directory of files (gzipped or uncompressed)')
+    db_arg(al)
     al.add_argument('--filter', metavar='<file>', type=_existing_path, dest='filter_path',
                     help='Path to filter file (output of prefilter)')
     al.add_argument('--filter-threshold', metavar='<float>', dest='filter_threshold', type=_unit_float, default=0,
@@ -239,10 +247,31 @@ def validate_args_fasta_input(args, parser):
     if args.input_path.is_dir():
         args.is_multifasta = False
         args.fasta_paths = sorted(f for f in args.input_path.iterdir() if f.is_file())
-    if not args.is_multifasta and len(args.fasta_paths) < 2:
-        parser.error(f'Too few fasta files found in {args.input_path}. '
-                     f'Expected at least 2, found {len(args.fasta_paths)}.')
+    args.db_paths = None
+    db_path = getattr(args, 'db_path', None)
+    if db_path is None:
+        if not args.is_multifasta and len(args.fasta_paths) < 2:
+            parser.error(f'Too few fasta files found in {args.input_path}. '
+                         f'Expected at least 2, found {len(args.fasta_paths)}.')
+        return args
+    # --db: read by the rule of -i; the two are of one kind, and the combined set needs two genomes
+    if db_path.is_dir() != args.input_path.is_dir():
+        parser.error('-i and --db must both be FASTA files or both be directories.')
+    if _dist_env()[1] > 1:
+        parser.error('--db runs on one GPU: start it without a multi-process launcher (WORLD_SIZE must be 1).')
+    args.db_paths = sorted(f for f in db_path.iterdir() if f.is_file()) if db_path.is_dir() else [db_path]
+    if not args.is_multifasta:
+        for path, found in ((db_path, args.db_paths), (args.input_path, args.fasta_paths)):
+            if not found:
+                parser.error(f'No fasta files found in {path}.')
     return args
+
+
+def _db_description(args):
+    """The database and the file counts, for the 'Running:' line ('' without --db)."""
+    if args.db_paths is None:
+        return ''
+    return f' --db {args.db_path} [{len(args.db_paths)} database + {len(args.fasta_paths)} new file(s)]'
 
 
 def validate_args_prefilter(args, parser):
@@ -291,9 +320,12 @@ def _require_binary(path):
 def prefilter_call(args):
     """What the front-end hands to vg_prefilter for validated prefilter arguments -- the counterpart of the
     reference's three argv lists (cmd_kmerdb_build / _all2all / _distance, vclust.py:915-1055)."""
-    return dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta, k=args.k,
+    call = dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta, k=args.k,
                 min_kmers=args.min_kmers, min_ident=args.min_ident, kmers_fraction=args.kmers_fraction,
                 max_seqs=args.max_seqs, num_threads=args.num_threads)
+    if getattr(args, 'db_paths', None) is not None:       # --db: vg_prefilter_new (no reference counterpart)
+        call['db_paths'] = args.db_paths
+    return call
 
 
 def align_call(args):
@@ -302,9 +334,12 @@ def align_call(args):
     is exactly one input path (:1159-1160)."""
     lz = {k: getattr(args, k) for k in ('mal', 'msl', 'mrd', 'mqd', 'reg', 'aw', 'am', 'ar')}
     out_filters = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov') if getattr(args, k) > 0}
-    return dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta,
+    call = dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta,
                 columns=ALIGN_OUTFMT[args.outfmt], filter_path=args.filter_path, filter_threshold=args.filter_threshold,
                 out_aln=args.aln_path, lz=lz, out_filters=out_filters, num_threads=args.num_threads)
+    if getattr(args, 'db_paths', None) is not None:       # --db: vg_align_new (no reference counterpart)
+        call['db_paths'] = args.db_paths
+    return call
 
 
 def handle_prefilter(args, parser, logger):
@@ -313,7 +348,7 @@ def handle_prefilter(args, parser, logger):
     from . import stages
     rank, world, local_rank = _dist_env()
     desc = (f'libvclust_gpu prefilter -k {args.k} --min-kmers {args.min_kmers} --min-ident {args.min_ident} '
-            f'--kmers-fraction {args.kmers_fraction} --max-seqs {args.max_seqs} [{world} GPU] -> {args.output_path}')
+            f'--kmers-fraction {args.kmers_fraction} --max-seqs {args.max_seqs}{_db_description(args)} [{world} GPU] -> {args.output_path}')
 
     def work():
         kw = prefilter_call(args)
@@ -333,7 +368,7 @@ def handle_align(args, parser, logger):
     call = align_call(args)
     desc = ('libvclust_gpu align ' + ' '.join(f'--{k} {v}' for k, v in call['lz'].items())
             + (f' --filter {args.filter_path} {args.filter_threshold}' if args.filter_path else '')
-            + f' [{world} GPU] -> {args.output_path}')
+            + _db_description(args) + f' [{world} GPU] -> {args.output_path}')
 
     def work():
         kw = dict(call)

@@ -64,26 +64,37 @@ struct background_release {
 }
 extern "C" void vg_set_process_ends_after_call(int on) { g_leak_at_exit = on != 0; }
 
-extern "C" int vg_prefilter(const char* const* fasta_paths, int n_paths, const char* out_path,
-                            const vg_prefilter_params* p) {
-    VG_API_BEGIN
-    if (!fasta_paths || n_paths <= 0 || !out_path || !p) throw vg_error(VG_EINVAL, "vg_prefilter: null argument");
+// The genome set of a whole-stage call: one path list (vg_prefilter, vg_align), or the database's list in front of it (the _new
+// entries).  load() returns the resident set and n_db, the number of database genomes: -1 without a database.
+struct stage_input {
+    const char* const* paths; int n_paths; const char* const* db_paths; int n_db_paths;
+    bool ok() const { return paths && n_paths > 0 && (!db_paths ? n_db_paths == 0 : n_db_paths > 0); }
+    int load(int multisample, int n_threads, vg_genomes** g) const {
+        int n_db = -1;
+        if (!db_paths) check(vg_genomes_load_resident(paths, n_paths, multisample, n_threads, g));
+        else check(vg_genomes_load_db_new_resident(db_paths, n_db_paths, paths, n_paths, multisample, n_threads, g, &n_db));
+        return n_db;
+    }
+};
+
+static void prefilter_stage(const char* fn, const stage_input& in, const char* out_path, const vg_prefilter_params* p) {
+    if (!in.ok() || !out_path || !p) throw vg_error(VG_EINVAL, std::string(fn) + ": null argument");
     if (p->k < 15 || p->k > 30) throw vg_error(VG_EINVAL, "k must be in 15..30");
     if (!(p->kmers_fraction > 0.0) || p->kmers_fraction > 1.0) throw vg_error(VG_EINVAL, "kmers_fraction must be in (0,1]");
-    vg_host_mark("vg_prefilter: enter");
+    vg_host_mark((std::string(fn) + ": enter").c_str());
     vg_one_shot_scope one_shot;
     defer_scope parked;
     device_warmup warm(WARM_PREFILTER);
     genomes_guard gg;
-    check(vg_genomes_load_resident(fasta_paths, n_paths, p->is_multifasta, p->num_threads, &gg.g));
+    const int n_db = in.load(p->is_multifasta, p->num_threads, &gg.g);
     warm.join();
     vg_require_device();
     std::vector<int64_t> sizes((size_t)std::max(1, vg_genomes_count(gg.g)));
     free_guard pairs; int64_t np = 0;
     // on a single device the --min-kmers cut can be applied on the GPU already
     uint32_t min_emit = (uint32_t)std::max(1, p->min_kmers);
-    check(vg_kmer_shared(gg.g, p->k, p->kmers_fraction, 0, 1, min_emit, sizes.data(),
-                         (vg_pair_count**)&pairs.p, &np));
+    if (n_db < 0) check(vg_kmer_shared(gg.g, p->k, p->kmers_fraction, 0, 1, min_emit, sizes.data(), (vg_pair_count**)&pairs.p, &np));
+    else check(vg_kmer_shared_new(gg.g, n_db, p->k, p->kmers_fraction, min_emit, sizes.data(), (vg_pair_count**)&pairs.p, &np));
     // a one-shot process: the tens of GB of workspace go back to the driver NOW, so that the scrub of that memory
     // runs beside the writer and the start of the next process (`vclust.py align`) instead of in front of its
     // first allocation
@@ -94,21 +105,41 @@ extern "C" int vg_prefilter(const char* const* fasta_paths, int n_paths, const c
                             sizes.data(), (const vg_pair_count*)pairs.p, np, out_path));
     }
     vg_host_mark("fltr.txt written");
+}
+extern "C" int vg_prefilter(const char* const* fasta_paths, int n_paths, const char* out_path,
+                            const vg_prefilter_params* p) {
+    VG_API_BEGIN
+    prefilter_stage("vg_prefilter", { fasta_paths, n_paths, nullptr, 0 }, out_path, p);
+    VG_API_END
+}
+extern "C" int vg_prefilter_new(const char* const* db_paths, int n_db_paths, const char* const* new_paths, int n_new_paths,
+                                const char* out_path, const vg_prefilter_params* p) {
+    VG_API_BEGIN
+    if (!db_paths) throw vg_error(VG_EINVAL, "vg_prefilter_new: null argument");
+    prefilter_stage("vg_prefilter_new", { new_paths, n_new_paths, db_paths, n_db_paths }, out_path, p);
     VG_API_END
 }
 
-extern "C" int vg_align(const char* const* fasta_paths, int n_paths, const char* out_path, const vg_align_params* p) {
-    VG_API_BEGIN
-    if (!fasta_paths || n_paths <= 0 || !out_path || !p) throw vg_error(VG_EINVAL, "vg_align: null argument");
-    vg_host_mark("vg_align: enter");
+static void align_stage(const char* fn, const stage_input& in, const char* out_path, const vg_align_params* p) {
+    if (!in.ok() || !out_path || !p) throw vg_error(VG_EINVAL, std::string(fn) + ": null argument");
+    vg_host_mark((std::string(fn) + ": enter").c_str());
     vg_one_shot_scope one_shot;
     defer_scope parked;
     device_warmup warm(WARM_ALIGN);
     genomes_guard gg;
-    check(vg_genomes_load_resident(fasta_paths, n_paths, p->is_multifasta, p->num_threads, &gg.g));
+    const int n_db = in.load(p->is_multifasta, p->num_threads, &gg.g);
     warm.join();
     vg_require_device();
     free_guard pairs, tasks, regions; int64_t np = 0, nt = 0, nr = 0;
+    if (n_db > 0 && !p->filter_path) {
+        // no filter: every pair that contains a new genome (a filter written by vg_prefilter_new holds no other pair already)
+        const int64_t n = vg_genomes_count(gg.g);
+        np = n * (n - 1) / 2 - (int64_t)n_db * (n_db - 1) / 2;
+        vg_pair_count* v = (vg_pair_count*)malloc(sizeof(vg_pair_count) * (size_t)std::max<int64_t>(1, np));
+        if (!v) throw vg_error(VG_ENOMEM, "out of host memory");
+        pairs.p = v;
+        for (uint32_t a = (uint32_t)n_db; a < (uint32_t)n; ++a) for (uint32_t b = 0; b < a; ++b) *v++ = { a, b, 0 };
+    } else
     check(vg_read_filter(gg.g, p->filter_path, p->filter_threshold, (vg_pair_count**)&pairs.p, &np));
     vg_host_mark("filter read");
     check(vg_lz_prepare(gg.g, (const vg_pair_count*)pairs.p, np, &p->lz));          // (the first index batch is built beside the task list)
@@ -121,6 +152,17 @@ extern "C" int vg_align(const char* const* fasta_paths, int n_paths, const char*
         check(vg_write_ani(gg.g, (const vg_task*)tasks.p, stats.data(), nt, (const vg_region*)regions.p, nr, out_path, p));
     }
     vg_host_mark("ani.tsv written");
+}
+extern "C" int vg_align(const char* const* fasta_paths, int n_paths, const char* out_path, const vg_align_params* p) {
+    VG_API_BEGIN
+    align_stage("vg_align", { fasta_paths, n_paths, nullptr, 0 }, out_path, p);
+    VG_API_END
+}
+extern "C" int vg_align_new(const char* const* db_paths, int n_db_paths, const char* const* new_paths, int n_new_paths,
+                            const char* out_path, const vg_align_params* p) {
+    VG_API_BEGIN
+    if (!db_paths) throw vg_error(VG_EINVAL, "vg_align_new: null argument");
+    align_stage("vg_align_new", { new_paths, n_new_paths, db_paths, n_db_paths }, out_path, p);
     VG_API_END
 }
 

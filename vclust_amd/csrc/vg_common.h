@@ -156,6 +156,8 @@ void vg_lz_drop_prepared(const vg_genomes* g);    // forget the index plan vg_lz
 
 // vg_genomes_load with the upload to the library's device overlapped with the packing (vg_genomes.cpp; whole-stage calls)
 int vg_genomes_load_resident(const char* const* paths, int n_paths, int multisample, int n_threads, vg_genomes** out);
+int vg_genomes_load_db_new_resident(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
+                                    int n_threads, vg_genomes** out, int* n_db_genomes);      // (the same for vg_genomes_load_db_new)
 // RANGE shards held by several ranks (vg_prefilter.hip, k_slice_scan): every rank scans 1/world of the BASES and the kept
 // masks + level-1 counts of each rank's digit range travel to it.  The exchange is an all-to-all of device memory:
 // for every part, block d of `send` (bytes send_off[d] .. send_off[d + 1]) goes to rank d and block s of `recv` (bytes

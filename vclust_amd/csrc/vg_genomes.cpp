@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 #include <condition_variable>
+#include <unordered_set>
 
 static inline uint8_t code_of(unsigned char ch) {
     switch (ch) {
@@ -354,10 +355,14 @@ k_mask_of_lengths(uint32_t* __restrict__ nmask, int64_t n_words, const uint32_t*
 
 // to_device: the packed arrays travel to the HBM of the library's device WHILE the genomes are packed (a helper
 // thread uploads every stretch of genomes as soon as its last genome is done), and the set comes back resident
-static void genomes_load_impl(const char* const* paths, int n_paths, int multisample, int n_threads, bool to_device, vg_genomes** out) {
+// n_db_paths >= 0 (vg_genomes_load_db_new): the first n_db_paths files are the database, the others the new genomes; multisample
+// then means one genome per record of BOTH files, *n_db_genomes receives the database's genome count and a name that occurs on
+// both sides is VG_EINVAL, raised from the layout, before anything is packed or any device is asked for
+static void genomes_load_impl(const char* const* paths, int n_paths, int multisample, int n_threads, bool to_device, vg_genomes** out,
+                              int n_db_paths = -1, int* n_db_genomes = nullptr) {
     if (!paths || n_paths <= 0 || !out) throw vg_error(VG_EINVAL, "vg_genomes_load: bad arguments");
     const int T = std::max(1, n_threads);
-    const bool multi = multisample && n_paths == 1;
+    const bool multi = multisample && (n_db_paths >= 0 || n_paths == 1);
     vg_host_mark("ingest: enter");
     // 1. whole files into memory (gz inflated), files in parallel.  The mappings and the record lists are given to a
     // helper thread at the end: unmapping 4 GB of FASTA costs ~80 ms the caller need not wait for.
@@ -413,6 +418,16 @@ static void genomes_load_impl(const char* const* paths, int n_paths, int multisa
         if (multi) g->names.push_back(first_token(r0.hdr, r0.hdr_end));
         else { std::string pth = paths[d.file]; size_t sl = pth.find_last_of('/'); g->names.push_back(sl == std::string::npos ? pth : pth.substr(sl + 1)); }
         g->n++;
+    }
+    if (n_db_paths >= 0) {
+        int n_db = 0;
+        while (n_db < g->n && gd[(size_t)n_db].file < n_db_paths) ++n_db;
+        std::unordered_set<std::string> db_names(g->names.begin(), g->names.begin() + n_db);
+        for (int i = n_db; i < g->n; ++i)
+            if (db_names.count(g->names[(size_t)i]))
+                throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: the name " + g->names[(size_t)i] + " occurs in the database and in the new genomes");
+        *n_db_genomes = n_db;
+        if (g->n < 2) throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: the database and the new genomes together are " + std::to_string(g->n) + " genome(s); pairs need at least 2");
     }
     vg_host_mark("ingest: layout");
     // first touch in parallel: the arrays are written by the packing threads right below
@@ -501,7 +516,7 @@ static void genomes_load_impl(const char* const* paths, int n_paths, int multisa
             }
             if (multi) {
                 const gdesc& d0 = gd[(size_t)st_first[(size_t)c]]; const gdesc& d1 = gd[(size_t)st_first[(size_t)c + 1] - 1];
-                bufs[(size_t)d0.file].drop(recs[(size_t)d0.file][d0.r0].hdr - 1, recs[(size_t)d1.file][d1.r1 - 1].end);
+                if (d0.file == d1.file) bufs[(size_t)d0.file].drop(recs[(size_t)d0.file][d0.r0].hdr - 1, recs[(size_t)d1.file][d1.r1 - 1].end);
             }
         }
     });
@@ -540,6 +555,31 @@ extern "C" int vg_genomes_load(const char* const* paths, int n_paths, int multis
 int vg_genomes_load_resident(const char* const* paths, int n_paths, int multisample, int n_threads, vg_genomes** out) {
     VG_API_BEGIN
     genomes_load_impl(paths, n_paths, multisample, n_threads, true, out);
+    VG_API_END
+}
+
+// database files then new files as one path list for the loader; multi-FASTA mode wants exactly one file on each side
+static std::vector<const char*> db_new_paths(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
+                                             vg_genomes** out, int* n_db_genomes) {
+    if (!db_paths || !new_paths || n_db <= 0 || n_new <= 0 || !out || !n_db_genomes) throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: bad arguments");
+    if (multisample && (n_db != 1 || n_new != 1))
+        throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: multi-FASTA mode takes one database file and one file of new genomes");
+    std::vector<const char*> all(db_paths, db_paths + n_db);
+    all.insert(all.end(), new_paths, new_paths + n_new);
+    return all;
+}
+extern "C" int vg_genomes_load_db_new(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
+                                      int n_threads, vg_genomes** out, int* n_db_genomes) {
+    VG_API_BEGIN
+    const std::vector<const char*> all = db_new_paths(db_paths, n_db, new_paths, n_new, multisample, out, n_db_genomes);
+    genomes_load_impl(all.data(), (int)all.size(), multisample, n_threads, false, out, n_db, n_db_genomes);
+    VG_API_END
+}
+int vg_genomes_load_db_new_resident(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
+                                    int n_threads, vg_genomes** out, int* n_db_genomes) {
+    VG_API_BEGIN
+    const std::vector<const char*> all = db_new_paths(db_paths, n_db, new_paths, n_new, multisample, out, n_db_genomes);
+    genomes_load_impl(all.data(), (int)all.size(), multisample, n_threads, true, out, n_db, n_db_genomes);
     VG_API_END
 }
 

@@ -2145,6 +2145,7 @@ struct pass_inputs {
     int next_shard = -1;                          // >= 0: once the index is built, start the scan of this shard (of the same cut) into *pre
     float* index_ms = nullptr;                    // placement trials: receives the index stage's milliseconds
     vg_slice_exchange* xs = nullptr;              // a RANGE shard counts by sliced scan + exchange
+    int first_row = 0;                            // vg_kmer_shared_new: the SpGEMM runs over the rows of the genomes first_row .. n - 1 only
 };
 static int compact_stage_cap(double keep) { return (int)std::min<double>(256.0, std::ceil(1.5 * 256.0 * keep) + 24.0); }
 // to be called while the library queue is idle
@@ -2173,7 +2174,7 @@ static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, i
     else { out.kept.alloc((size_t)std::max(1, g->n)); out.kept.zero(s); }
     const int use_frac = fraction < 1.0;
     const kmer_args A = make_kmer_args(g, k, fraction, shard, n_shards);
-    out.compact = use_frac || n_shards > 1;
+    out.compact = use_frac || n_shards > 1 || premask != nullptr;       // (a given mask: the rows are its kept positions)
     if (!out.compact && P >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "dense k-mer pass needs < 2^32 padded bases");
     if (P >= (1LL << 37)) throw vg_error(VG_EOVERFLOW, "genome set exceeds 2^37 padded bases");
     dbuf<uint64_t> keys_a, keys_b; dbuf<uint32_t> pos_a, pos_b;
@@ -2632,12 +2633,11 @@ static void bucket_kernels(bucket_run& R) {
 // caller, d_kept receives the k-mers kept per genome).  A RANGE shard of the dense source (A.dig_n < 2^11): ix.si receives
 // the kept masks, the row bases and the row -> genome map of the pass, n_rows_info becomes the number of kept k-mers, and
 // the row pointers are indexed by row number.
-static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_args& A, int* d_kept, const pass_inputs& in, kmer_index& ix) {
-    hipStream_t s = vg_stream();
-    vg_host_mark("buckets: enter");
-    pass_timer index_timer(in.index_ms, s);                // (placement trials: count ... bucket kernels of this pass)
-    bucket_run R{ g, k, dense, in, ix, d_kept, s }; R.rows_zero.st = s;
-    const int64_t n_src = dense ? g->padded_total() : ix.nv;
+// geometry, source and level-1 tables of a run; false = the pipeline declines the input
+static bool start_bucket_run(bucket_run& R, const kmer_args& A) {
+    const bool dense = R.dense; const int k = R.k; kmer_index& ix = R.ix;
+    R.rows_zero.st = R.s;
+    const int64_t n_src = dense ? R.g->padded_total() : ix.nv;
     if (!bucket_geometry_for(k, dense, A, n_src, R.G)) return false;
     const bucket_geometry& G = R.G;
     R.S.A = A; R.S.keys = dense ? nullptr : ix.si.keys.p; R.S.pos = dense ? nullptr : ix.si.pos.p; R.S.n = n_src; R.S.k2 = 2 * k; R.S.bin_lo = G.bin_lo;
@@ -2645,6 +2645,15 @@ static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_arg
     R.k25 = dense && k == 25 && !A.use_frac && A.n_shards == 1;
     R.T1s.alloc((size_t)G.nb1 * (size_t)G.n_st + 1); R.slab.alloc((size_t)G.n_slabs * G.nb1); R.d_off1.alloc((size_t)G.nb1 + 1);
     R.G.L2.T1s = R.T1s.p; R.G.L2.off1 = R.d_off1.p;
+    return true;
+}
+static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_args& A, int* d_kept, const pass_inputs& in, kmer_index& ix) {
+    hipStream_t s = vg_stream();
+    vg_host_mark("buckets: enter");
+    pass_timer index_timer(in.index_ms, s);                // (placement trials: count ... bucket kernels of this pass)
+    bucket_run R{ g, k, dense, in, ix, d_kept, s };
+    if (!start_bucket_run(R, A)) return false;
+    const bucket_geometry& G = R.G;
     clear_rows_aside(R);
     {
         level1_tmp t;
@@ -2732,9 +2741,12 @@ static void index_by_radix(vg_genomes* g, int k, double fraction, int shard, int
     }
 }
 // ---- the SpGEMM over the index, with a growing output buffer.  dev_out != nullptr: the pairs stay in HBM (*dev_out, *dev_n of them) and host_pairs is left empty
+// first_row > 0 (vg_kmer_shared_new): only the rows of the genomes first_row .. n - 1 are launched.  A row a counts its partners
+// b < a, so what comes out is every pair (a, b), a > b, with a >= first_row, counted as the whole launch counts it.
 static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_shared, std::vector<vg_pair_count>& host_pairs,
-                         dbuf<vg_pair_count>* dev_out, unsigned long long* dev_n) {
+                         dbuf<vg_pair_count>* dev_out, unsigned long long* dev_n, int first_row = 0) {
     hipStream_t s = vg_stream(); const int n = g->n;
+    if (first_row >= n) { host_pairs.clear(); if (dev_out) { dev_out->alloc(1); *dev_n = 0; } return; }       // no row: no pair
     dbuf<unsigned long long> d_cursor(1);
     dbuf<uint32_t> d_over((size_t)n), d_nover(1);
     unsigned long long cap = std::max<unsigned long long>(1u << 20, (unsigned long long)n * 16);
@@ -2750,12 +2762,19 @@ static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_share
         std::vector<uint32_t> goff_h;
         if (ix.rows_from_map) { goff_h.resize((size_t)n + 1); ix.si.goff.download(goff_h.data(), (size_t)n + 1, s); VG_HIP(hipStreamSynchronize(s)); }
         auto rows_of = [&](int i) { return !goff_h.empty() ? (int64_t)(goff_h[(size_t)i + 1] - goff_h[(size_t)i]) : ix.compact_rows ? (int64_t)ix.kept[(size_t)i] : g->len[(size_t)i]; };
-        for (int i = 0; i < n; ++i) (rows_of(i) <= SMALL_ROW ? small_rows : large_rows).push_back((uint32_t)i);
-        if (small_rows.size() * 2 >= (size_t)n) {
+        for (int i = first_row; i < n; ++i) (rows_of(i) <= SMALL_ROW ? small_rows : large_rows).push_back((uint32_t)i);
+        if (small_rows.size() * 2 >= (size_t)(n - first_row)) {
             n_small = (int)small_rows.size(); n_large = (int)large_rows.size();
             d_small.alloc(small_rows.size()); d_small.upload(small_rows.data(), small_rows.size(), s);
             if (n_large) { d_large.alloc(large_rows.size()); d_large.upload(large_rows.data(), large_rows.size(), s); }
         }
+    }
+    dbuf<uint32_t> d_tail;                            // the rows first_row .. n - 1 as one list, where the two lists above were not made
+    if (first_row > 0 && !n_small) {
+        std::vector<uint32_t> tail((size_t)(n - first_row));
+        for (int i = first_row; i < n; ++i) tail[(size_t)(i - first_row)] = (uint32_t)i;
+        d_tail.alloc(tail.size()); d_tail.upload(tail.data(), tail.size(), s);
+        VG_HIP(hipStreamSynchronize(s));                 // (the host vector goes out of scope)
     }
     for (;;) {
         dbuf<vg_pair_count> d_out((size_t)cap);
@@ -2770,7 +2789,7 @@ static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_share
             if (n_small) {
                 if (n_large) launch(k_spgemm<11>, 256, d_large.p, n_large, d_over.p);
                 launch(k_spgemm<9, true>, 64, d_small.p, n_small, d_over.p);
-            } else launch(k_spgemm<11>, 256, nullptr, n, d_over.p);
+            } else launch(k_spgemm<11>, 256, d_tail.p, n - first_row, d_over.p);
         }
         // one round trip in the common case: overflow count, pair count and the first pairs together
         constexpr size_t EAGER = 1 << 16;
@@ -2832,7 +2851,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
     // k-mers of its level-1 buckets and numbers them as rows; everything behind level 1 is a 1/n_shards slice of the whole
     // pass, row pointers included.  HASH shards (larger sets, fractions) materialise their k-mers first (compact source).
     const bool range = range_shards(g, fraction, n_shards);
-    const bool dense_src = !(fraction < 1.0) && (n_shards == 1 || range);
+    const bool dense_src = !(fraction < 1.0) && (n_shards == 1 || range) && !in.mask;      // (a given mask is a compact source)
     const bool bucket_ok = index_by_buckets(g, k, fraction, shard, n_shards, dense_src, in, ix);      // 1. the index
     if (!bucket_ok) index_by_radix(g, k, fraction, shard, n_shards, in, ix);
     ix.compact_rows = bucket_ok ? (!dense_src || range) : ix.si.compact;
@@ -2846,7 +2865,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
     // kernel takes 86 ms instead of 55 at 10^6 contigs.  An optimisation only: without room the next sub-shard scans in line.)
     if (in.pre && in.next_shard >= 0)
         try { vg_dev_try_scope opportunistic; launch_precount(*in.pre, g, k, in.next_shard, n_shards); } catch (...) { (void)hipGetLastError(); in.pre->drop(); }
-    spgemm_pairs(g, ix, min_shared, host_pairs, dev_out, dev_n);      // 3. the pairs
+    spgemm_pairs(g, ix, min_shared, host_pairs, dev_out, dev_n, in.first_row);      // 3. the pairs
 }
 
 // sum of partial pair records (the sub-shards of one call): device radix sort on (a << 32 | b) + reduce by key
@@ -2912,7 +2931,7 @@ static void sum_partial_pairs(const std::vector<dbuf<vg_pair_count>>& parts, con
 }
 // the sub-shard loop of one call: every pass leaves its partial list in HBM
 static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int shard, int n_shards, int sub, uint32_t min_shared,
-                                  int64_t* set_sizes, dbuf<vg_pair_count>& out, unsigned long long* n_out) {
+                                  int64_t* set_sizes, dbuf<vg_pair_count>& out, unsigned long long* n_out, int first_row = 0) {
     const int n = g->n;
     std::vector<int64_t> part((size_t)n);
     for (int i = 0; i < n; ++i) set_sizes[i] = 0;
@@ -2939,6 +2958,7 @@ static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int sha
     const bool scan_ahead = !multi && !(fraction < 1.0) && !range_shards(g, fraction, n_shards * sub);
     for (int t = 0; t < sub; ++t) {
         pass_inputs in; if (multi) in.mask = all_masks.p + (size_t)t * (size_t)Wm;
+        in.first_row = first_row;
         if (scan_ahead) { in.pre = &ahead; in.next_shard = t + 1 < sub ? shard * sub + t + 1 : -1; }
         kmer_shared_pass(g, k, fraction, shard * sub + t, n_shards * sub, 1u, part.data(), none, in, &parts[(size_t)t], &counts[(size_t)t]);
         for (int i = 0; i < n; ++i) set_sizes[i] += part[i];
@@ -3065,6 +3085,199 @@ extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, 
     if (!acc.empty()) memcpy(outp, acc.data(), sizeof(vg_pair_count) * acc.size());
     *pairs = outp; *n_pairs = (int64_t)acc.size();
     vg_host_mark("vg_kmer_shared: return");
+    VG_API_END
+}
+
+// ---- vg_kmer_shared_new, the masked route: index only what a new genome can share.
+// Level 1 of the bucket pipeline runs as ever.  Inside a level-1 bucket the records lie in super-tile order, so the records of
+// the new genomes are its tail: from the bucket's segment of the super-tile that holds the first base of genome n_db on, and in
+// that one super-tile the position decides.  k_new_mask<false>: a workgroup sets an LDS bit field from the key bits of the bucket's
+// new records, then streams its share of the bucket's database records and, where the record's bit is set, sets the bit of its
+// position in the kept mask (64-bit atomicOr on the 64-position word; hits are a few per cent).  Every valid position of a new
+// genome is kept.  The field is a SUPERSET test: a false positive indexes a useless k-mer, a set bit is never missed.
+// Field: 2^19 bits = 64 KiB, so two 1 024-thread workgroups fit a CU (160 KiB) and fill its wave slots, which is what hides the
+// latency of the record stream; 2^20 bits would halve the false positives (new records of a bucket / 2^19: 4 % at 1 % new of
+// 100 000 genomes) but leave one workgroup per CU.  `chunks` workgroups share a bucket, each rebuilding the field from the tail; the
+// only hand-off is the kernel boundary behind it.  k_new_mask<true> is the same walk with another test: positions of the flagged
+// genomes (the second pass, for the set sizes of database genomes).
+namespace {
+constexpr int NM_BITS = 19;
+struct new_mask_args {
+    const uint32_t* rec; int short_kr;          // level-1 records; > 0: 8-byte short records with that many key bits, 0: (w0, w1, pay)
+    const uint32_t* T1s; const uint32_t* off1;  // scanned level-1 table [super-tile][bucket], bucket starts
+    int nb1; int64_t n_st, st_pos;              // buckets, super-tiles, positions per super-tile
+    int64_t p_new, st_new, P;                   // first position of genome n_db, its super-tile; padded positions of the set
+    int chunks;                                 // workgroups per bucket
+    const uint32_t* blk2g; int align_shift; const uint8_t* flag;      // BY_GENOME: position -> genome, genomes to keep
+};
+template <bool BY_GENOME>
+__global__ void __launch_bounds__(PT_THREADS)
+k_new_mask(new_mask_args a, unsigned long long* __restrict__ mask) {
+    __shared__ uint32_t bits[BY_GENOME ? 1 : 1 << (NM_BITS - 5)];
+    const int b = (int)(blockIdx.x / (unsigned)a.chunks), c = (int)(blockIdx.x % (unsigned)a.chunks);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n_waves = PT_THREADS / 64;
+    // the records of bucket b that came from super-tile st; key bits and position of record i of that segment (the two
+    // formats as k_part_count2<SHORT> reads them; a super-tile of short records lies inside one 2^25-position group)
+    auto segment = [&](int64_t st, uint32_t* r0, uint32_t* r1) {
+        *r0 = a.T1s[st * a.nb1 + b];
+        *r1 = st + 1 < a.n_st ? a.T1s[(st + 1) * a.nb1 + b] : a.off1[b + 1];
+    };
+    auto record = [&](uint32_t i, int64_t st, uint64_t* key, uint32_t* pos) {
+        if (a.short_kr > 0) {
+            uint64_t r; __builtin_memcpy(&r, a.rec + 2 * (size_t)i, 8);
+            *key = r >> SR_POS_BITS;
+            *pos = (uint32_t)((((uint64_t)st * (uint64_t)a.st_pos) >> SR_POS_BITS) << SR_POS_BITS) + (uint32_t)(r & ((1u << SR_POS_BITS) - 1u));
+        } else {
+            const uint32_t* r = a.rec + 3 * (size_t)i;
+            *key = ((uint64_t)r[0] << 32) | r[1]; *pos = r[2];
+        }
+    };
+    auto keep = [&](uint32_t pos) { atomicOr(&mask[pos >> 6], 1ULL << (pos & 63u)); };      // (callers have checked pos < P)
+    if (BY_GENOME) {
+        for (int64_t st = (int64_t)c * n_waves + wave; st < a.n_st; st += (int64_t)a.chunks * n_waves) {
+            uint32_t r0, r1; segment(st, &r0, &r1);
+            for (uint32_t i = r0 + lane; i < r1; i += 64) {
+                uint64_t key; uint32_t pos; record(i, st, &key, &pos);
+                if ((int64_t)pos < a.P && a.flag[a.blk2g[pos >> a.align_shift]]) keep(pos);
+            }
+        }
+        return;
+    }
+    for (int i = threadIdx.x; i < (1 << (NM_BITS - 5)); i += PT_THREADS) bits[i] = 0;
+    __syncthreads();
+    for (int64_t st = a.st_new + wave; st < a.n_st; st += n_waves) {              // the tail: the new genomes' records
+        uint32_t r0, r1; segment(st, &r0, &r1);
+        for (uint32_t i = r0 + lane; i < r1; i += 64) {
+            uint64_t key; uint32_t pos; record(i, st, &key, &pos);
+            if ((int64_t)pos < a.p_new || (int64_t)pos >= a.P) continue;          // (the one mixed super-tile)
+            const uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ULL) >> (64 - NM_BITS));
+            atomicOr(&bits[h >> 5], 1u << (h & 31u));
+            if (c == 0) keep(pos);
+        }
+    }
+    __syncthreads();
+    for (int64_t st = (int64_t)c * n_waves + wave; st <= a.st_new; st += (int64_t)a.chunks * n_waves) {      // this workgroup's share of the database records
+        uint32_t r0, r1; segment(st, &r0, &r1);
+        for (uint32_t i = r0 + lane; i < r1; i += 64) {
+            uint64_t key; uint32_t pos; record(i, st, &key, &pos);
+            if ((int64_t)pos >= a.p_new) continue;
+            const uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ULL) >> (64 - NM_BITS));
+            if ((bits[h >> 5] >> (h & 31u)) & 1u) keep(pos);
+        }
+    }
+}
+}
+static int g_new_path = 0;
+extern "C" void vg_set_new_path(int mode) { g_new_path = mode == 1 || mode == 2 ? mode : 0; }
+// automatic choice: the masked route up to this share of new padded bases in the set -- the largest measured share at which its
+// range lay below the unmasked route's (48.6-54.6 against 105-111 ms at 1 %, 133-138 against 105-112 ms at 10 %)
+constexpr double NEW_MASKED_UP_TO = 0.01;
+// the second pass is for FEW genomes: with more database genomes in pairs than this share of the database (and than a count that is
+// small on any device) the call falls back to the unmasked route, whose sizes come with its index
+constexpr double NEW_SIZES_SHARE = 0.25; constexpr int64_t NEW_SIZES_FEW = 4096;
+// true = pairs and set sizes are in place; false = the route does not apply to this set (or fell back): nothing has been written
+static bool kmer_shared_new_masked(vg_genomes* g, int n_db, int k, uint32_t min_shared, int64_t* set_sizes, std::vector<vg_pair_count>& acc) {
+    hipStream_t s = vg_stream(); const int n = g->n; const int64_t P = g->padded_total();
+    if (n_db <= 0 || n_db >= n || P >= (1LL << 32)) return false;
+    const kmer_args A = make_kmer_args(g, k, 1.0, 0, 1);
+    kmer_index ix1; pass_inputs none; dbuf<int> kept_b((size_t)n); kept_b.zero(s);
+    ix1.n_rows_info = P;
+    bucket_run R{ g, k, true, none, ix1, kept_b.p, s };
+    if (!start_bucket_run(R, A)) return false;
+    { level1_tmp t; if (!level1_count(R, t)) return false; level1_scatter(R); }
+    const bucket_geometry& G = R.G;
+    new_mask_args a{};
+    a.rec = R.a_rec.p; a.short_kr = G.short_rec ? G.L2.kr : 0; a.T1s = R.T1s.p; a.off1 = R.d_off1.p;
+    a.nb1 = G.nb1; a.n_st = G.n_st; a.st_pos = (int64_t)G.st_tiles * PT_TILE;
+    a.p_new = g->base_off[(size_t)n_db]; a.st_new = a.p_new / a.st_pos; a.P = P;
+    a.blk2g = g->d_blk2g.p; a.align_shift = g->align_shift;
+    // workgroups per bucket: as many as leave each at least eight database records per new record of the rebuilt field
+    const double new_share = (double)(P - a.p_new) / (double)P;
+    const int64_t groups = (a.st_new + PT_THREADS / 64) / (PT_THREADS / 64);
+    a.chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(groups, 64), (int64_t)((1.0 - new_share) / (8.0 * std::max(new_share, 1e-6)))));
+    const int64_t W = P / 64;
+    dbuf<unsigned long long> mask((size_t)W + 1); mask.zero(s);
+    {
+        vg_prof_scope ps("kmer_new_mask", (double)R.n1 * (G.short_rec ? 8.0 : 12.0));
+        hipLaunchKernelGGL(k_new_mask<false>, dim3((unsigned)(G.nb1 * a.chunks)), dim3(PT_THREADS), 0, s, a, mask.p);
+    }
+    // the masked pass: the new genomes' k-mers and the database's hits, SpGEMM over the new rows
+    pass_inputs in; in.mask = mask.p; in.first_row = n_db;
+    std::vector<int64_t> sizes((size_t)n); std::vector<vg_pair_count> pairs;
+    kmer_shared_pass(g, k, 1.0, 0, 1, min_shared, sizes.data(), pairs, in);
+    // set sizes of the database genomes in pairs: only their hits were indexed, so a second masked pass over ALL their positions
+    std::vector<uint8_t> flag((size_t)n, 0); int64_t n_flag = 0;
+    for (const vg_pair_count& pc : pairs) if ((int64_t)pc.b < n_db && !flag[pc.b]) { flag[pc.b] = 1; ++n_flag; }
+    if (n_flag > NEW_SIZES_FEW && (double)n_flag > NEW_SIZES_SHARE * n_db) return false;
+    if (n_flag) {
+        dbuf<uint8_t> d_flag((size_t)n); d_flag.upload(flag.data(), (size_t)n, s);
+        mask.zero(s);
+        a.flag = d_flag.p; a.chunks = (int)std::max<int64_t>(1, std::min<int64_t>(64, (a.n_st + PT_THREADS / 64 - 1) / (PT_THREADS / 64)));
+        {
+            vg_prof_scope ps("kmer_new_sizes", (double)R.n1 * (G.short_rec ? 8.0 : 12.0));
+            hipLaunchKernelGGL(k_new_mask<true>, dim3((unsigned)(G.nb1 * a.chunks)), dim3(PT_THREADS), 0, s, a, mask.p);
+        }
+        VG_HIP(hipStreamSynchronize(s));                   // (the flags' host copy and staging are done with)
+        kmer_index ix2;
+        ix2.d_dups.alloc((size_t)n); ix2.d_dups.zero(s); ix2.kept.resize((size_t)n); ix2.dups.resize((size_t)n);
+        pass_inputs in2; in2.mask = mask.p;
+        if (!index_by_buckets(g, k, 1.0, 0, 1, false, in2, ix2)) index_by_radix(g, k, 1.0, 0, 1, in2, ix2);
+        for (int i = 0; i < n_db; ++i) if (flag[(size_t)i]) sizes[(size_t)i] = (int64_t)ix2.kept[(size_t)i] - ix2.dups[(size_t)i];
+    }
+    for (int i = 0; i < n; ++i) set_sizes[i] = sizes[(size_t)i];
+    acc.swap(pairs);
+    return true;
+}
+
+// New genomes against a database (the header has the definition).  Two routes: the passes of vg_kmer_shared unchanged but for
+// their SpGEMM, which is launched over the new genomes' rows alone (every set, every option); and, for a dense single pass that the
+// bucket pipeline accepts, the masked route above.  vg_set_new_path chooses; both give the same result.
+extern "C" int vg_kmer_shared_new(vg_genomes* g, int n_db, int k, double fraction, uint32_t min_shared,
+                                  int64_t* set_sizes, vg_pair_count** pairs, int64_t* n_pairs) {
+    VG_API_BEGIN
+    if (!g || !set_sizes || !pairs || !n_pairs) throw vg_error(VG_EINVAL, "vg_kmer_shared_new: null argument");
+    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
+    if (!(fraction > 0.0) || fraction > 1.0) throw vg_error(VG_EINVAL, "fraction must be in (0,1]");
+    if (n_db < 0 || n_db > g->n)
+        throw vg_error(VG_EINVAL, "vg_kmer_shared_new: n_db = " + std::to_string(n_db) + " is outside 0.." + std::to_string(g->n) + " (the genomes of the set)");
+    vg_host_mark("vg_kmer_shared_new: enter");
+    vg_require_device();
+    int rc = vg_genomes_to_device(g); if (rc) return rc;
+    *pairs = nullptr; *n_pairs = 0;
+    const int n = g->n;
+    if (n == 0) return VG_OK;
+    const shard_plan plan = plan_shards(g, fraction, 1, /*host_entry=*/true);
+    std::vector<vg_pair_count> acc;
+    const int64_t P = g->padded_total();
+    const bool want_masked = g_new_path == 2 || (g_new_path == 0 && n_db < n && (double)(P - g->base_off[(size_t)n_db]) <= NEW_MASKED_UP_TO * (double)P);
+    // (a mask that keeps nearly everything of a set just under 2^32 positions overflows the row numbers of its compact pass: the
+    // unmasked route, whose rows are positions, takes the call like any other set the masked route does not suit)
+    bool masked_done = false;
+    if (plan.one_pass && fraction >= 1.0 && want_masked)
+        try { masked_done = kmer_shared_new_masked(g, n_db, k, min_shared, set_sizes, acc); }
+        catch (const vg_error& e) { if (e.code != VG_EOVERFLOW) throw; acc.clear(); }
+    if (masked_done) {
+    } else if (plan.one_pass) {
+        pass_inputs in; in.first_row = n_db;
+        kmer_shared_pass(g, k, fraction, 0, 1, min_shared, set_sizes, acc, in);
+    } else {
+        dbuf<vg_pair_count> d_sum; unsigned long long n_sum = 0;
+        for (int attempt = 0, sub = plan.sub;; ++attempt) {          // (cut finer on an overflowing sub-shard, as vg_kmer_shared does)
+            try { kmer_shared_subshards(g, k, fraction, 0, 1, sub, min_shared, set_sizes, d_sum, &n_sum, n_db); break; }
+            catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; d_sum.release(); }
+        }
+        acc.resize((size_t)n_sum);
+        if (n_sum) { d_sum.download(acc.data(), (size_t)n_sum, vg_stream()); VG_HIP(hipStreamSynchronize(vg_stream())); }
+    }
+    // the sizes of the database genomes that no pair names are not part of the result: -1
+    std::vector<char> named((size_t)n_db, 0);
+    for (const vg_pair_count& pc : acc) if ((int64_t)pc.b < n_db) named[(size_t)pc.b] = 1;
+    for (int i = 0; i < n_db; ++i) if (!named[(size_t)i]) set_sizes[i] = -1;
+    vg_pair_count* outp = (vg_pair_count*)malloc(sizeof(vg_pair_count) * std::max<size_t>(1, acc.size()));
+    if (!outp) throw vg_error(VG_ENOMEM, "out of host memory");
+    if (!acc.empty()) memcpy(outp, acc.data(), sizeof(vg_pair_count) * acc.size());
+    *pairs = outp; *n_pairs = (int64_t)acc.size();
+    vg_host_mark("vg_kmer_shared_new: return");
     VG_API_END
 }
 

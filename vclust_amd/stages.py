@@ -11,12 +11,21 @@ from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, AlignParams, Cluster
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
 
+def _path_array(paths):
+    return (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
+
+
 def prefilter(paths, out_path, is_multifasta, k=25, min_kmers=20, min_ident=0.7, batch_size=0,
-              kmers_fraction=1.0, max_seqs=0, num_threads=1, verbosity=0):
+              kmers_fraction=1.0, max_seqs=0, num_threads=1, verbosity=0, db_paths=None):
+    """fltr.txt of the genomes in `paths` (vg_prefilter).  db_paths: a database the genomes of `paths` are new to -- the set is
+    the database's genomes followed by them, and only the rows of the new genomes are filled (vg_prefilter_new)."""
     lib = _lib.load()
-    arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
+    arr = _path_array(paths)
     prm = PrefilterParams(k, min_kmers, min_ident, batch_size, kmers_fraction, max_seqs, num_threads,
                           verbosity, int(bool(is_multifasta)))
+    if db_paths is not None:
+        check(lib.vg_prefilter_new(_path_array(db_paths), len(db_paths), arr, len(paths), os.fsencode(str(out_path)), C.byref(prm)))
+        return
     check(lib.vg_prefilter(arr, len(paths), os.fsencode(str(out_path)), C.byref(prm)))
 
 
@@ -41,10 +50,15 @@ def align_params(columns, filter_path=None, filter_threshold=0.0, out_aln=None, 
 
 
 def align(paths, out_path, is_multifasta, columns, filter_path=None, filter_threshold=0.0, out_aln=None,
-          lz=None, out_filters=None, num_threads=1, verbosity=0):
+          lz=None, out_filters=None, num_threads=1, verbosity=0, db_paths=None):
+    """ani.tsv of the genomes in `paths` (vg_align).  db_paths: as in prefilter; only pairs that contain a genome of `paths` are
+    aligned -- the filter's, or all of them without a filter (vg_align_new)."""
     lib = _lib.load()
-    arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
+    arr = _path_array(paths)
     p = align_params(columns, filter_path, filter_threshold, out_aln, lz, out_filters, num_threads, verbosity, is_multifasta)
+    if db_paths is not None:
+        check(lib.vg_align_new(_path_array(db_paths), len(db_paths), arr, len(paths), os.fsencode(str(out_path)), C.byref(p)))
+        return
     check(lib.vg_align(arr, len(paths), os.fsencode(str(out_path)), C.byref(p)))
 
 
