@@ -124,6 +124,31 @@ int vg_kmer_shared_new(vg_genomes* g, int n_db, int k, double fraction, uint32_t
 /* route of vg_kmer_shared_new: 0 (default) = automatic, 1 = never the masked route, 2 = the masked route wherever it applies (tests,
  * tools/new2all_timing.py); no reference call site */
 void vg_set_new_path(int mode);
+/* Which index geometry a call will take (tests and tooling; no reference call site).  Host only: no device is needed or touched.
+ * vg_kmer_geometry reports what the bucket pipeline decides for the FIRST pass of vg_kmer_shared(g, k, fraction, shard, n_shards,
+ * ...), by calling the function that pass calls; vg_set_subshards and the developer switches apply to it as they do to the pass.
+ * vg_kmer_geometry_at is the same question for the dense single pass (no fraction, one shard, no sub-shards) over a set of
+ * `padded_positions` positions, without a set: the pass of vg_kmer_shared(g, k, 1.0, 0, 1, ...) and the level 1 of the masked
+ * route of vg_kmer_shared_new.
+ *   accepted    1 = the bucket pipeline takes the pass; 0 = it declines (the general path); -1 = the pass has a compact source
+ *               (a fraction, HASH shards): its geometry follows from the number of kept k-mers, which only the device knows.
+ *               Only P and n_passes are filled unless accepted == 1.
+ *   P           padded positions of the set;  n_passes: passes the call is cut into (1 = no sub-shards)
+ *   levels      partition levels (1 or 2);  total_bits = B1 + B2: key bits the two levels partition on
+ *   st_tiles    8 192-position tiles per level-1 super-tile;  n_st: super-tiles of the pass
+ *   u_st        super-tiles per level-2 unit
+ *   g_st        short records only: super-tiles per 2^25-position group where a unit spans several groups (u_st / g_st of them),
+ *               0 where a unit lies inside one group
+ *   tile32k     level 1 scatters whole 32 768-position tiles;  narrow: level-2 records carry one key word
+ *   short_rec   level-1 records are 8 bytes (key bits, position modulo 2^25) instead of 12 */
+typedef struct {
+    int accepted; int64_t P; int n_passes;
+    int levels, total_bits, B1, B2;
+    int st_tiles; int64_t n_st; int u_st, g_st;
+    int tile32k, narrow, short_rec;
+} vg_kmer_geometry_info;
+int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info);
+int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geometry_info* info);
 /* distinct canonical k-mers of one genome, ascending (parity tests) */
 int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint64_t** out, int64_t* n_out);
 

@@ -4,8 +4,10 @@ library's own all-vs-all kmer_shared on the same GenomeSet.  Pairs compare as a 
 every new genome and every genome of a returned pair and -1 elsewhere.
 
 Shapes are the smallest at which each index path exists: below 65 536 padded positions (the general radix path), one partition
-level (up to 2^21), two levels with 12-byte level-1 records, two levels with short records (from 4 x 8 192 x 2 048 positions at
-k <= 25).  Families straddle the database / new boundary, so every case has a pair of a new and a database genome and, with two
+level (up to 2^21), two levels with 12-byte level-1 records scattered tile by tile, and two levels with 12-byte records scattered
+in whole 32 768-position tiles (from 4 x 8 192 x 2 048 positions).  8-byte short records need a larger set than the oracle takes in
+a `Case` -- at k = 25 from 134 348 800 padded positions on, see test_geometry_cpu.py -- and have a file of their own,
+test_gpu_large_geometry.py.  Families straddle the database / new boundary, so every case has a pair of a new and a database genome and, with two
 or more new genomes, a pair of two new ones; both are asserted."""
 import numpy as np
 import pytest
@@ -167,13 +169,18 @@ def test_min_shared_on_the_masked_route(two_levels):
     two_levels.check(two_levels.n // 2 - 2, min_shared=500)            # (inside a family of five)
 
 
-# ---------------------------------------------------------------- 4. short level-1 records
-def test_short_records():
-    """1 700 genomes of 40 kb from the bench generator, the last 17 new: 67 108 864 padded positions and more.  Against the
-    library's own all-vs-all pass only (the oracle would take minutes)."""
+# ---------------------------------------------------------------- 4. whole 32 768-position tiles, 12-byte records
+def test_tiles_of_32768_positions():
+    """1 700 genomes of 40 kb from the bench generator, the last 17 new: 69 632 000 padded positions, super-tiles of four tiles
+    scattered as one 32 768-position tile.  At k = 25 the set partitions on 17 bits, 2k - 17 = 33 key bits do not fit one word,
+    and the level-1 records stay 12 bytes (short records: test_gpu_large_geometry.py).  Against the library's own all-vs-all
+    pass only (the single-threaded oracle of a Case would take minutes)."""
     codes, offsets, names = synth.make_families(170, 10, length=40000, seed=3)
     case = Case(codes, offsets, names, oracle=False)
     assert case.n == 1700 and case.offsets[-1] > 4 * 8192 * 2048
+    g = case.gs.kmer_geometry(k=25)
+    assert g['P'] == _padded(case.offsets)[0] == 69632000
+    assert (g['accepted'], g['levels'], g['tile32k'], g['st_tiles'], g['short_rec'], g['narrow']) == (1, 2, 1, 4, 0, 0)
     case.check(case.n - 17)
 
 

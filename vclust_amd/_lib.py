@@ -104,6 +104,13 @@ class DedupRepeatStats(C.Structure):
                 ('batches', C.c_int64)]
 
 
+class KmerGeometry(C.Structure):
+    _fields_ = [('accepted', C.c_int), ('P', C.c_int64), ('n_passes', C.c_int),
+                ('levels', C.c_int), ('total_bits', C.c_int), ('B1', C.c_int), ('B2', C.c_int),
+                ('st_tiles', C.c_int), ('n_st', C.c_int64), ('u_st', C.c_int), ('g_st', C.c_int),
+                ('tile32k', C.c_int), ('narrow', C.c_int), ('short_rec', C.c_int)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [('name', C.c_char * 48), ('total_ms', C.c_double), ('launches', C.c_int64),
                 ('bytes', C.c_double)]
@@ -135,6 +142,8 @@ SYMBOLS = {
     'vg_kmer_shared': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint32,
                                  P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
     'vg_kmer_shared_new': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
+    'vg_kmer_geometry': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, P(KmerGeometry)]),
+    'vg_kmer_geometry_at': (C.c_int, [C.c_int64, C.c_int, P(KmerGeometry)]),
     'vg_kmer_set': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, P(P(C.c_uint64)), P(C.c_int64)]),
     'vg_filter_pairs': (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.c_int64, C.POINTER(PairCount), C.c_int64,
                                   C.POINTER(C.POINTER(PairCount)), C.POINTER(C.c_int64)]),

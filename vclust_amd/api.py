@@ -167,6 +167,13 @@ class GenomeSet:
                                            sizes.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pp), C.byref(npairs)))
         return sizes[:n], _take(pp, npairs.value, PAIR_DTYPE)
 
+    def kmer_geometry(self, k=25, fraction=1.0, shard=0, n_shards=1):
+        """The index geometry of the first pass of kmer_shared with these arguments (vg_kmer_geometry; host only) -> dict of the
+        fields of vg_kmer_geometry_info.  Only accepted, P and n_passes mean anything unless accepted == 1."""
+        info = _lib.KmerGeometry()
+        check(self._lib.vg_kmer_geometry(self._h, int(k), float(fraction), int(shard), int(n_shards), C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in info._fields_}
+
     def kmer_set(self, idx, k=25, fraction=1.0):
         p = C.POINTER(C.c_uint64)()
         n = C.c_int64()
@@ -531,6 +538,14 @@ def set_new_path(mode):
     """Route of GenomeSet.kmer_shared_new (vg_set_new_path): 0 = automatic, 1 = never the masked route, 2 = the masked route wherever
     it applies."""
     _lib.load().vg_set_new_path(int(mode))
+
+
+def kmer_geometry_at(padded_positions, k=25):
+    """GenomeSet.kmer_geometry for the dense single pass over a set of that many padded positions, without a set
+    (vg_kmer_geometry_at)."""
+    info = _lib.KmerGeometry()
+    check(_lib.load().vg_kmer_geometry_at(int(padded_positions), int(k), C.byref(info)))
+    return {name: int(getattr(info, name)) for name, _ in info._fields_}
 
 
 def release_device_memory():

@@ -2075,18 +2075,25 @@ template <class F> static void with_k(bool k25, F f) { if (k25) f(std::integral_
 constexpr double SUB_PASS_KMERS = 3.6e9, SUB_PASS_START = 3.9e9;
 
 // RANGE or HASH shards (see kmer_args): a property of the set and the fraction, the same on every rank and in every pass
-static bool range_shards(const vg_genomes* g, double fraction, int n_shards) {
-    return n_shards > 1 && n_shards <= 256 && !(fraction < 1.0) && g->padded_total() < (1LL << 32);
+static bool range_shards(int64_t P, double fraction, int n_shards) {
+    return n_shards > 1 && n_shards <= 256 && !(fraction < 1.0) && P < (1LL << 32);
 }
-static kmer_args make_kmer_args(const vg_genomes* g, int k, double fraction, int shard, int n_shards) {
+static bool range_shards(const vg_genomes* g, double fraction, int n_shards) { return range_shards(g->padded_total(), fraction, n_shards); }
+// which keys a pass over P padded positions keeps: everything of kmer_args but the set's device pointers (vg_kmer_geometry asks without a device)
+static kmer_args shard_kmer_args(int64_t P, int align_shift, int k, double fraction, int shard, int n_shards) {
     const int use_frac = fraction < 1.0;
-    kmer_args A{ vg_genome_planes(g, vg_stream()), g->d_nmask.p, g->d_blk2g.p, g->d_base_off.p, g->d_len.p, g->padded_total(), k, use_frac,
-                 use_frac ? (uint64_t)std::ldexp(fraction, 64) : ~0ULL, (uint32_t)shard, (uint32_t)n_shards, g->align_shift, 0u, 1u << DIG_BITS, 1u << DIG_BITS };
-    if (range_shards(g, fraction, n_shards)) {
+    kmer_args A{ nullptr, nullptr, nullptr, nullptr, nullptr, P, k, use_frac,
+                 use_frac ? (uint64_t)std::ldexp(fraction, 64) : ~0ULL, (uint32_t)shard, (uint32_t)n_shards, align_shift, 0u, 1u << DIG_BITS, 1u << DIG_BITS };
+    if (range_shards(P, fraction, n_shards)) {
         A.dig_max = (uint32_t)(((1u << DIG_BITS) + (uint32_t)n_shards - 1u) / (uint32_t)n_shards);
         const uint32_t lo = (uint32_t)(((uint64_t)shard << DIG_BITS) / (uint64_t)n_shards), hi = (uint32_t)(((uint64_t)(shard + 1) << DIG_BITS) / (uint64_t)n_shards);
         A.shard = 0; A.n_shards = 1; A.dig_lo = lo; A.dig_n = hi - lo;
     }
+    return A;
+}
+static kmer_args make_kmer_args(const vg_genomes* g, int k, double fraction, int shard, int n_shards) {
+    kmer_args A = shard_kmer_args(g->padded_total(), g->align_shift, k, fraction, shard, n_shards);
+    A.planes = vg_genome_planes(g, vg_stream()); A.nmask = g->d_nmask.p; A.blk2g = g->d_blk2g.p; A.base_off = g->d_base_off.p; A.len = g->d_len.p;
     return A;
 }
 
@@ -2840,6 +2847,10 @@ static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_share
         cap = produced + produced / 8 + 1024;     // rerun with a buffer that fits
     }
 }
+// the source of a pass: the bases themselves (dense) or the kept k-mers, materialised first (compact; a given mask is a compact source)
+static bool pass_source_dense(int64_t P, double fraction, int n_shards, bool masked) {
+    return !(fraction < 1.0) && (n_shards == 1 || range_shards(P, fraction, n_shards)) && !masked;
+}
 // one pass over the k-mers of one shard: per-genome set sizes and (a, b, shared) of every pair (see spgemm_pairs for dev_out)
 static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared, int64_t* set_sizes, std::vector<vg_pair_count>& host_pairs,
                              const pass_inputs& in = pass_inputs{}, dbuf<vg_pair_count>* dev_out = nullptr, unsigned long long* dev_n = nullptr) {
@@ -2851,7 +2862,7 @@ static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, i
     // k-mers of its level-1 buckets and numbers them as rows; everything behind level 1 is a 1/n_shards slice of the whole
     // pass, row pointers included.  HASH shards (larger sets, fractions) materialise their k-mers first (compact source).
     const bool range = range_shards(g, fraction, n_shards);
-    const bool dense_src = !(fraction < 1.0) && (n_shards == 1 || range) && !in.mask;      // (a given mask is a compact source)
+    const bool dense_src = pass_source_dense(g->padded_total(), fraction, n_shards, in.mask != nullptr);
     const bool bucket_ok = index_by_buckets(g, k, fraction, shard, n_shards, dense_src, in, ix);      // 1. the index
     if (!bucket_ok) index_by_radix(g, k, fraction, shard, n_shards, in, ix);
     ix.compact_rows = bucket_ok ? (!dense_src || range) : ix.si.compact;
@@ -2929,6 +2940,10 @@ static void sum_partial_pairs(const std::vector<dbuf<vg_pair_count>>& parts, con
     VG_HIP(hipStreamSynchronize(s));                           // the scratch buffers go out of scope
     *n_out = no;
 }
+// HASH sub-shards share ONE scan of the bases (k_multi_mask): every pass of the loop is then handed a mask
+static bool subshards_share_scan(const vg_genomes* g, double fraction, int n_shards, int sub) {
+    return !g_sw.scan_each && sub >= 2 && sub <= MM_MAX_SUB && !range_shards(g, fraction, n_shards * sub);
+}
 // the sub-shard loop of one call: every pass leaves its partial list in HBM
 static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int shard, int n_shards, int sub, uint32_t min_shared,
                                   int64_t* set_sizes, dbuf<vg_pair_count>& out, unsigned long long* n_out, int first_row = 0) {
@@ -2943,7 +2958,7 @@ static void kmer_shared_subshards(vg_genomes* g, int k, double fraction, int sha
     // staging buffers of P / 256 x ~80 x 8 bytes each; VG_SUBSHARD_SCAN=each is the scan per pass of round 4)
     dbuf<unsigned long long> all_masks;
     const int64_t Wm = g->padded_total() / 64 + 1;
-    const bool multi = !g_sw.scan_each && sub >= 2 && sub <= MM_MAX_SUB && !range_shards(g, fraction, n_shards * sub);
+    const bool multi = subshards_share_scan(g, fraction, n_shards, sub);
     if (multi) {
         int rc = vg_genomes_to_device(g); if (rc) throw vg_error(rc, vg_last_error());
         hipStream_t s = vg_stream();
@@ -3310,6 +3325,47 @@ void vg_kmer_shared_device(vg_genomes* g, int k, double fraction, int shard, int
 static_assert(sizeof(vg_pair_count) == 12, "pair record layout");
 extern "C" void vg_set_subshards(int n) { g_force_subshards = n; }
 extern "C" void vg_set_range_scan(int mode) { g_range_scan_mode = mode == 1 ? 1 : 0; }
+
+
+// ---- vg_kmer_geometry: what bucket_geometry_for decides for a pass, asked on the host (tests, tooling)
+static void report_geometry(int k, bool dense, const kmer_args& A, int64_t P, vg_kmer_geometry_info* info) {
+    bucket_geometry G;
+    info->accepted = dense ? (bucket_geometry_for(k, true, A, P, G) ? 1 : 0) : -1;
+    if (info->accepted != 1) return;
+    info->levels = G.levels; info->total_bits = G.total_bits; info->B1 = G.B1; info->B2 = G.B2;
+    info->st_tiles = G.st_tiles; info->n_st = G.n_st; info->u_st = G.L2.u_st; info->g_st = G.L2.g_st;
+    info->tile32k = G.tile32k; info->narrow = G.narrow; info->short_rec = G.short_rec;
+}
+extern "C" int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info) {
+    VG_API_BEGIN
+    if (!g || !info) throw vg_error(VG_EINVAL, "vg_kmer_geometry: null argument");
+    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
+    if (n_shards < 1 || shard < 0 || shard >= n_shards) throw vg_error(VG_EINVAL, "bad shard");
+    if (!(fraction > 0.0) || fraction > 1.0) throw vg_error(VG_EINVAL, "fraction must be in (0,1]");
+    memset(info, 0, sizeof *info);
+    const int64_t P = g->padded_total();
+    info->P = P; info->n_passes = 1;
+    if (g->n == 0) return VG_OK;
+    // the first pass of the call, as vg_kmer_shared cuts it (kmer_shared_subshards: sub-shard 0 of shard * sub .. of n_shards * sub;
+    // the one scan of HASH sub-shards hands every pass a mask)
+    const shard_plan plan = plan_shards(g, fraction, n_shards, /*host_entry=*/true);
+    info->n_passes = plan.sub;
+    const int sh = shard * plan.sub, ns = n_shards * plan.sub;
+    const bool masked = subshards_share_scan(g, fraction, n_shards, plan.sub);
+    const bool dense = pass_source_dense(P, fraction, ns, masked);
+    report_geometry(k, dense, shard_kmer_args(P, g->align_shift, k, 1.0, sh, ns), P, info);
+    VG_API_END
+}
+extern "C" int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geometry_info* info) {
+    VG_API_BEGIN
+    if (!info) throw vg_error(VG_EINVAL, "vg_kmer_geometry_at: null argument");
+    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
+    if (padded_positions < 0) throw vg_error(VG_EINVAL, "vg_kmer_geometry_at: negative number of positions");
+    memset(info, 0, sizeof *info);
+    info->P = padded_positions; info->n_passes = 1;
+    report_geometry(k, true, shard_kmer_args(padded_positions, 0, k, 1.0, 0, 1), padded_positions, info);
+    VG_API_END
+}
 
 extern "C" int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint64_t** out, int64_t* n_out) {
     VG_API_BEGIN
