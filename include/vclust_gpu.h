@@ -149,6 +149,11 @@ typedef struct {
 } vg_kmer_geometry_info;
 int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info);
 int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geometry_info* info);
+/* The row-pointer rule of a prefilter pass (tests and tooling; no reference call site).  Host only: no device is needed or touched.
+ * A pass whose genome list holds `entries` slots over `n_genomes` genomes writes the row pointer of a k-mer with ONE smaller partner as
+ * 0xFFFFFFFF - partner where entries + n_genomes < 2^32; *inline_lo = 2^32 - n_genomes is then the smallest such value.  0 = the pass
+ * inlines nothing (no room beside the plain values 1 .. entries, or the developer switch VG_ROWPTR_INLINE=0). */
+int vg_rowptr_inline_lo(int64_t entries, int64_t n_genomes, uint32_t* inline_lo);
 /* distinct canonical k-mers of one genome, ascending (parity tests) */
 int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint64_t** out, int64_t* n_out);
 

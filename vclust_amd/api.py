@@ -548,6 +548,14 @@ def kmer_geometry_at(padded_positions, k=25):
     return {name: int(getattr(info, name)) for name, _ in info._fields_}
 
 
+def rowptr_inline_lo(entries, n_genomes):
+    """The smallest row-pointer value that carries a genome id in a prefilter pass of `entries` genome-list slots over `n_genomes`
+    genomes, or 0 where such a pass inlines nothing (vg_rowptr_inline_lo; host only)."""
+    lo = C.c_uint32(0)
+    check(_lib.load().vg_rowptr_inline_lo(int(entries), int(n_genomes), C.byref(lo)))
+    return int(lo.value)
+
+
 def release_device_memory():
     _lib.load().vg_release_device_memory()
 

@@ -6,9 +6,10 @@
 //
 // All kernels are HBM / latency bound integer kernels (no MFMA).  Per padded base position the pipeline reads 3 bits
 // of sequence (twice: histogram and scatter), writes and reads one 8-byte level-1 record and one 8-byte level-2
-// record, and writes one u32 of genome list (CSC side) and one u32 row pointer (CSR side: 0, or 1 + the start of
-// the k-mer's run in the genome list); the random traffic is the row-pointer scatter of the bucket kernel and the
-// reads of the short genome lists of shared k-mers in the SpGEMM.
+// record, and writes one u32 of genome list (CSC side) and one u32 row pointer (CSR side: 0, 1 + the start of
+// the k-mer's run in the genome list, or the k-mer's only smaller partner itself: "Row pointers" below); the random
+// traffic is the row-pointer scatter of the bucket kernel and the reads of the short genome lists of shared k-mers
+// in the SpGEMM.
 #include "vg_common.h"
 #include <functional>
 #include <map>
@@ -35,9 +36,19 @@ __host__ __device__ __forceinline__ uint64_t scramble_key(uint64_t cano, int k) 
 }
 __host__ __device__ __forceinline__ uint64_t unscramble_key(uint64_t key, int k) { return scramble_key(key, k); }   // an involution
 constexpr uint32_t DUP_BIT = 0x80000000u;
-// Row pointers: one u32 per base position (dense) or kept k-mer (compact): 0 = nothing to do, else 1 + the start
-// of the k-mer's run in gen[].  The run is ascending in genome id and contains the position's own genome, so a
-// walk from the start needs no length: it ends at the first genome >= a.
+// Row pointers: one u32 per base position (dense) or kept k-mer (compact):
+//   0                  nothing to do
+//   1 .. gen.n         1 + the start of the k-mer's run in gen[].  The run is ascending in genome id and contains the
+//                      position's own genome, so a walk from the start needs no length: it ends at the first genome >= a.
+//   >= inline_lo       the k-mer's ONLY smaller partner is genome 0xFFFFFFFF - value: no list to read (the entry at
+//                      rank 1 of its run, whose walk would fetch a line of gen[] to learn that one id)
+// inline_lo = 2^32 - n_genomes, valid for a pass only when gen.n < inline_lo (rowptr_inline_lo, decided per pass before
+// its writers run; 0 = off: no writer inlines, no reader decodes).  A pass may mix both forms: readers tell them apart by
+// value, so a writer that never inlines stays correct.
+// The readers test rs = value - 1 (the run start they need anyway) against inline_lo - 1, which is 0xFFFFFFFF when the
+// rule is off: no rs reaches it.
+__device__ __forceinline__ uint32_t rowptr_inline(uint32_t partner) { return 0xFFFFFFFFu - partner; }
+__device__ __forceinline__ uint32_t rowptr_partner_of_rs(uint32_t rs) { return 0xFFFFFFFEu - rs; }      // rs = value - 1
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33;
@@ -471,7 +482,7 @@ __global__ void __launch_bounds__(256)
 k_group_runs(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ blk2g, int blk_shift,
              int64_t n, int low_bit, uint32_t* __restrict__ gen, uint32_t* __restrict__ rowinfo,
              compact_map M, int* __restrict__ dup_per_genome, int64_t* __restrict__ long_list, unsigned int* __restrict__ n_long,
-             unsigned int long_cap) {
+             unsigned int long_cap, uint32_t inline_lo) {
     __shared__ uint64_t sk[GS_TILE + GS_HALO + 1];
     __shared__ uint32_t sp[GS_TILE + GS_HALO + 1];
     __shared__ unsigned long long sh[(GS_TILE + GS_HALO + 1) / 64 + 2];      // bit j: entry j starts an equal-prefix group
@@ -526,13 +537,14 @@ k_group_runs(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ pos
             // genomes are looked up here, not staged: 12 bytes of LDS per entry keep five workgroups on a CU
             const uint32_t pj = sp[j];
             const uint32_t g = M.cblk ? genome_of_compact(M, pj) : blk2g[pj >> blk_shift];
-            bool dup = false;
-            if (prev_eq >= 0) { const uint32_t pq = sp[prev_eq]; dup = (M.cblk ? genome_of_compact(M, pq) : blk2g[pq >> blk_shift]) == g; }
+            bool dup = false; uint32_t g_prev = 0;
+            if (prev_eq >= 0) { const uint32_t pq = sp[prev_eq]; g_prev = M.cblk ? genome_of_compact(M, pq) : blk2g[pq >> blk_shift]; dup = g_prev == g; }
             gen[rs + eq_before] = g | (dup ? DUP_BIT : 0u);
             if (dup) { atomicAdd(&dup_per_genome[g], 1); continue; }
             if (eq_before == 0) continue;                                // the run's smallest genome: no partner b < a
             const uint32_t p = sp[j];
-            rowinfo[p] = (uint32_t)rs + 1u;                             // p = base position (dense) or compact index
+            // p = base position (dense) or compact index.  One entry in front: it is the run's first, its genome the only partner
+            rowinfo[p] = (inline_lo && eq_before == 1) ? rowptr_inline(g_prev) : (uint32_t)rs + 1u;
         }
     }
 }
@@ -612,8 +624,9 @@ k_spgemm(const uint32_t* __restrict__ rowinfo, const uint32_t* __restrict__ gen,
          const int64_t* __restrict__ base_off, const int64_t* __restrict__ len, const uint32_t* __restrict__ wave_base,
          int n_genomes, uint32_t min_emit, const uint32_t* __restrict__ row_list, int n_rows,
          vg_pair_count* __restrict__ out, unsigned long long* __restrict__ out_cursor,
-         unsigned long long out_cap, uint32_t* __restrict__ overflow_rows, uint32_t* __restrict__ n_overflow) {
+         unsigned long long out_cap, uint32_t* __restrict__ overflow_rows, uint32_t* __restrict__ n_overflow, uint32_t inline_lo) {
     constexpr int HT_SIZE = 1 << HT_BITS;
+    const uint32_t inl = inline_lo - 1u;           // rs >= inl: an inline pointer (off: 0xFFFFFFFF, which no rs reaches)
     constexpr int ROWS_PER_TRIP = 16;             // independent row-pointer loads per thread and trip
     __shared__ uint32_t hk[HT_SIZE];
     __shared__ uint32_t hc[HT_SIZE];
@@ -640,20 +653,24 @@ k_spgemm(const uint32_t* __restrict__ rowinfo, const uint32_t* __restrict__ gen,
     const int64_t L = wave_base ? (int64_t)wave_base[base_off[a + 1] >> 6] - p0 : len[a];
     // one walk: the genome list of the run, four entries per memory round trip; ascending, and genome a itself is
     // in it: the first genome >= a ends the walk (entries past the run are never reached)
-    auto walk = [&](uint32_t rs) {
+    auto take4 = [&](const uint32_t* g4, bool& done) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (done) continue;
+            const uint32_t g = g4[j];
+            if (g & DUP_BIT) continue;
+            if (g >= a) { done = true; continue; }
+            if (!ht_add<HT_BITS>(hk, hc, g, &s_used)) s_fail = 1;
+        }
+    };
+    auto walk = [&](uint32_t rs, const uint32_t* first = nullptr /* the list's first four entries, where they are loaded already */) {
         bool done = false;
         uint32_t e = 0;
+        if (first) { take4(first, done); e = 4; }
         for (; e < (uint32_t)LONG_RUN && !done; e += 4) {
             uint32_t g4[4];
             __builtin_memcpy(g4, gen + (size_t)rs + e, 16);            // one 16-byte load (the list carries 4 slack entries)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (done) continue;
-                const uint32_t g = g4[j];
-                if (g & DUP_BIT) continue;
-                if (g >= a) { done = true; continue; }
-                if (!ht_add<HT_BITS>(hk, hc, g, &s_used)) s_fail = 1;
-            }
+            take4(g4, done);
         }
         if (!done) {
             // a long run: the rest is walked by the whole workgroup (queue full: this thread goes on alone)
@@ -679,18 +696,37 @@ k_spgemm(const uint32_t* __restrict__ rowinfo, const uint32_t* __restrict__ gen,
             uint32_t nq = 0;
 #pragma unroll
             for (int u = 0; u < ROWS_PER_TRIP; ++u) {
-                const bool nz = rr4[u] != 0u;
+                // inline pointers are counted where they lie; only the plain ones are queued
+                const bool il = rr4[u] != 0u && rr4[u] - 1u >= inl;
+                const bool nz = rr4[u] != 0u && !il;
                 const unsigned long long b = __ballot(nz);
                 if (nz) rq[nq + (uint32_t)__popcll(b & ((1ULL << lane) - 1ULL))] = rr4[u];
                 nq += (uint32_t)__popcll(b);
+                if (il && !ht_add<HT_BITS>(hk, hc, rowptr_partner_of_rs(rr4[u] - 1u), &s_used)) s_fail = 1;
             }
             __syncthreads();
             for (uint32_t qi = (uint32_t)lane; qi < nq; qi += 64u) walk(rq[qi] - 1u);
         } else {
+        // The first 16-byte list load of every plain pointer of half a trip is issued back to back, then the walks consume
+        // them: the pointers of a thread were walked one after the other, each a dependent round trip.  (Eight loads in
+        // flight: 72 VGPRs and the occupancy of the serial form; all sixteen take 104 and lose three waves per SIMD.)
+        constexpr int HB = 8;
 #pragma unroll
-        for (int u = 0; u < ROWS_PER_TRIP; ++u) {
-            if (!rr4[u]) continue;
-            walk(rr4[u] - 1u);
+        for (int h = 0; h < ROWS_PER_TRIP; h += HB) {
+            uint32_t f[HB][4];
+#pragma unroll
+            for (int u = 0; u < HB; ++u) {
+                f[u][0] = f[u][1] = f[u][2] = f[u][3] = 0u;
+                if (rr4[h + u] != 0u && rr4[h + u] - 1u < inl) __builtin_memcpy(f[u], gen + (size_t)(rr4[h + u] - 1u), 16);
+            }
+#pragma unroll
+            for (int u = 0; u < HB; ++u) {
+                if (!rr4[h + u]) continue;
+                const uint32_t rs = rr4[h + u] - 1u;
+                // the only partner, smaller than a by construction: no list, no bound test
+                if (rs >= inl) { if (!ht_add<HT_BITS>(hk, hc, rowptr_partner_of_rs(rs), &s_used)) s_fail = 1; continue; }
+                walk(rs, f[u]);
+            }
         }
         }
         // drain the long-run queue cooperatively when it fills up
@@ -751,14 +787,16 @@ __global__ void __launch_bounds__(256)
 k_spgemm_dense(const uint32_t* __restrict__ rowinfo, const uint32_t* __restrict__ gen, uint64_t n_gen,
                const int64_t* __restrict__ base_off, const int64_t* __restrict__ len, const uint32_t* __restrict__ wave_base,
                int n_genomes, uint32_t min_emit, const uint32_t* __restrict__ rows, uint32_t* __restrict__ dense /* gridDim.x * n_genomes, zeroed */,
-               vg_pair_count* __restrict__ out, unsigned long long* __restrict__ out_cursor, unsigned long long out_cap) {
+               vg_pair_count* __restrict__ out, unsigned long long* __restrict__ out_cursor, unsigned long long out_cap, uint32_t inline_lo) {
     const uint32_t a = rows[blockIdx.x];
+    const uint32_t inl = inline_lo - 1u;
     uint32_t* cnt = dense + (size_t)blockIdx.x * n_genomes;
     const int64_t p0 = wave_base ? (int64_t)wave_base[base_off[a] >> 6] : base_off[a];
     const int64_t L = wave_base ? (int64_t)wave_base[base_off[a + 1] >> 6] - p0 : len[a];
     for (int64_t i = threadIdx.x; i < L; i += blockDim.x) {
         const uint32_t r = rowinfo[p0 + i];
         if (!r) continue;
+        if (r - 1u >= inl) { atomicAdd(&cnt[rowptr_partner_of_rs(r - 1u)], 1u); continue; }
         for (uint64_t x = (uint64_t)r - 1; x < n_gen; ++x) {
             const uint32_t g = gen[x];
             if (g & DUP_BIT) continue;
@@ -1747,8 +1785,9 @@ k_bucket_runs(const uint32_t* __restrict__ rec, int stride /* 3: (w0, w1, pay); 
               const uint32_t* __restrict__ boff, int64_t n_buckets, int pbits, const uint32_t* __restrict__ blk2g, int blk_shift,
               uint32_t* __restrict__ gen, uint32_t* __restrict__ rowinfo, compact_map M, int* __restrict__ dup_per_genome,
               const uint32_t* __restrict__ bucket_list /* null: all buckets; else the n_buckets listed ones */,
-              uint32_t* __restrict__ over_list, unsigned int* __restrict__ n_over) {
+              uint32_t* __restrict__ over_list, unsigned int* __restrict__ n_over, uint32_t inline_lo) {
     constexpr int BK_SUB = 1 << SUBBITS, CAP = THREADS * BK_PER;
+    const uint32_t inline_rank = inline_lo ? 1u : 0u;      // entries in front of the one that inlines; 0 (off) is no entry's count: the first of a run writes no pointer
     static_assert(CAP <= 8192 && BK_MAXBIN <= 1024, "slot | rank << 13 of the run members");
     __shared__ uint32_t s_big;
     __shared__ uint64_t sk[CAP];                  // NARROW: key << 32 | pos; else (w0 << 32) | w1 -- in sub-bin order
@@ -1873,9 +1912,12 @@ k_bucket_runs(const uint32_t* __restrict__ rec, int stride /* 3: (w0, w1, pay); 
 #pragma unroll
         for (int q = 0; q < BK_PER; ++q) {
             if (at[q] == 0xffffffffu) continue;
-            const uint32_t slot = at[q] & 0x1fffu, g = gq[q];
-            if ((sgen[slot - 1] & ~DUP_BIT) == g) { sgen[slot] = g | DUP_BIT; atomicAdd(&dup_per_genome[g], 1); continue; }
-            rowinfo[pj[q]] = b0 + (slot - (at[q] >> 13)) + 1u;   // 1 + the first entry of this k-mer's run in the sorted list
+            const uint32_t slot = at[q] & 0x1fffu, g = gq[q], before = at[q] >> 13;
+            const uint32_t g_prev = sgen[slot - 1] & ~DUP_BIT;
+            if (g_prev == g) { sgen[slot] = g | DUP_BIT; atomicAdd(&dup_per_genome[g], 1); continue; }
+            // 1 + the first entry of this k-mer's run in the sorted list; one entry in front: the slot in front is the run's
+            // first (never a repeat, never rewritten here), and its genome travels in the pointer
+            rowinfo[pj[q]] = before == inline_rank ? rowptr_inline(g_prev) : b0 + (slot - before) + 1u;
         }
         lds_sync();
         // (the slots of singleton k-mers carry whatever the LDS held: nobody reads them)
@@ -1933,7 +1975,7 @@ k_bucket_big(const uint32_t* __restrict__ rec, int stride, const uint32_t* __res
              const uint64_t* __restrict__ soff /* scratch offset of every listed bucket, in entries */, int pbits,
              uint64_t* __restrict__ kA, uint32_t* __restrict__ pA, uint64_t* __restrict__ kB, uint32_t* __restrict__ pB,
              const uint32_t* __restrict__ blk2g, int blk_shift, uint32_t* __restrict__ gen, uint32_t* __restrict__ rowinfo,
-             compact_map M, int* __restrict__ dup_per_genome) {
+             compact_map M, int* __restrict__ dup_per_genome, uint32_t inline_lo) {
     __shared__ uint32_t hist[BB_DIGITS][256];
     __shared__ uint32_t gbase[256];
     __shared__ uint32_t wcnt[BB_THREADS / 64][256];
@@ -2039,7 +2081,14 @@ k_bucket_big(const uint32_t* __restrict__ rec, int stride, const uint32_t* __res
         const uint32_t rank = (sv & 0x7fffffffu) - 1u - base;       // among the run's non-duplicates
         // (a singleton k-mer writes its own slot: nobody reads it)
         gen[(uint64_t)b0 + rs + rank] = g;
-        if (rank > 0) rowinfo[pos] = b0 + rs + 1u;
+        if (rank == 0) continue;
+        uint32_t v = b0 + rs + 1u;
+        if (inline_lo && rank == 1u) {
+            // the run's first entry is no repeat: its genome (another thread writes that gen[] slot) is the only partner
+            const uint32_t pf = p0[rs];
+            v = rowptr_inline(M.cblk ? genome_of_compact(M, pf) : blk2g[pf >> blk_shift]);
+        }
+        rowinfo[pos] = v;
     }
 }
 
@@ -2061,10 +2110,18 @@ static const struct {
     bool range_dense = !strcmp(pf_switch("VG_RANGE_SCATTER"), "dense");   // developer A/B
     bool staged2 = !strcmp(pf_switch("VG_LEVEL2_SCATTER"), "staged");
     bool scan_each = !strcmp(pf_switch("VG_SUBSHARD_SCAN"), "each");      // HASH sub-shards: a scan per pass, never the one scan of all
+    bool no_inline = !strcmp(pf_switch("VG_ROWPTR_INLINE"), "0");         // every row pointer a plain one (see rowptr_inline_lo)
     int subshards = atoi(pf_switch("VG_SUBSHARDS"));                  // developer experiments
     int placement_trials = atoi(pf_switch("VG_PLACEMENT_TRIALS"));
     double workspace_gb = [] { const char* e = getenv("VG_WORKSPACE_GB"); const double v = e ? atof(e) : 0.0; return v > 0.01 ? v : 8.0; }();
 } g_sw{};
+// inline_lo of a pass whose genome list holds `entries` slots over n_genomes genomes (see "Row pointers" above), or 0 = off:
+// the plain values 1 .. entries and the n_genomes inline values must not meet
+static uint32_t rowptr_inline_lo(uint64_t entries, int64_t n_genomes) {
+    if (g_sw.no_inline || n_genomes < 1 || entries >= (1ULL << 32) || (uint64_t)n_genomes >= (1ULL << 32)) return 0u;
+    const uint64_t lo = (1ULL << 32) - (uint64_t)n_genomes;
+    return entries < lo ? (uint32_t)lo : 0u;
+}
 // f(K) with K = 25 as a constant (the default k has kernels of its own) or 0 (k is read from the arguments)
 template <class F> static void with_k(bool k25, F f) { if (k25) f(std::integral_constant<int, 25>{}); else f(std::integral_constant<int, 0>{}); }
 // k-mers one pass is cut for: its row numbers are 32 bits (4.29e9) and sub-sharding starts at SUB_PASS_START expected
@@ -2385,6 +2442,7 @@ struct kmer_index {
     dbuf<uint32_t> rowinfo, gen; dbuf<int> d_dups;
     std::vector<int> kept, dups;                     // per genome: k-mers the pass kept, duplicates among them
     int64_t nv = 0, n_rows_info = 0;
+    uint32_t inline_lo = 0;                          // row pointers from here on carry a genome (rowptr_inline_lo; 0 = none do)
     bool compact_rows = false, rows_from_map = false;      // rows are kept k-mers, not positions; a sliced scan: a genome's rows are read off goff
     const uint32_t* wbase = nullptr;                 // compact rows: rows before every 64-position word
 };
@@ -2590,6 +2648,7 @@ static void bucket_kernels(bucket_run& R) {
     const uint32_t n1 = R.n1; const int64_t nbk = G.nbk;
     if (ix.gen.n < (size_t)n1 + 4) ix.gen.alloc((size_t)n1 + 4);
     if (ix.rowinfo.n < (size_t)ix.n_rows_info) ix.rowinfo.alloc((size_t)ix.n_rows_info);      // (one level: nothing to take over)
+    ix.inline_lo = rowptr_inline_lo((uint64_t)ix.gen.n, g->n);
     dbuf<unsigned int> d_nover(2); d_nover.zero(s);
     dbuf<uint32_t> over1((size_t)nbk), over2;
     if (R.rows_zero.e) VG_HIP(hipStreamWaitEvent(s, R.rows_zero.e, 0));
@@ -2598,7 +2657,7 @@ static void bucket_kernels(bucket_run& R) {
     const uint32_t* boff = R.boff.p; const uint32_t* blk2g = g->d_blk2g.p;
     unsigned int n_over[2] = {0, 0};
     auto runs = [&](auto kern, int threads, int grid, int64_t count, const uint32_t* list, uint32_t* over, unsigned int* nover) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, R.f_rec, R.f_stride, boff, count, pb, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, list, over, nover);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, R.f_rec, R.f_stride, boff, count, pb, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, list, over, nover, ix.inline_lo);
     };
     const auto wide = G.narrow ? k_bucket_runs<true, 1024, 11> : k_bucket_runs<false, 1024, 11>;
     {
@@ -2632,7 +2691,7 @@ static void bucket_kernels(bucket_run& R) {
     {
         vg_prof_scope ps("bucket_big", (double)tot * 12.0 * 2.0);
         hipLaunchKernelGGL(k_bucket_big, dim3(n_big), dim3(BB_THREADS), 0, s, R.f_rec, R.f_stride, boff, big_list,
-                           (const uint64_t*)d_so.p, pb, kA.p, pA.p, kB.p, pB.p, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p);
+                           (const uint64_t*)d_so.p, pb, kA.p, pA.p, kB.p, pB.p, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, ix.inline_lo);
     }
     VG_HIP(hipStreamSynchronize(s));
 }
@@ -2715,12 +2774,13 @@ static void index_by_radix(vg_genomes* g, int k, double fraction, int shard, int
     VG_HIP(hipMemsetAsync(rowinfo.p, 0, (size_t)ix.n_rows_info * sizeof(uint32_t), s));
     const compact_map cmap{ si.compact ? si.goff.p : nullptr, si.compact ? si.cblk.p : nullptr };
     gen = si.spare32.n >= (size_t)std::max<int64_t>(nv, 1) + 4 ? std::move(si.spare32) : dbuf<uint32_t>((size_t)std::max<int64_t>(nv, 1) + 4);
+    ix.inline_lo = rowptr_inline_lo((uint64_t)gen.n, n);            // (k_group_runs inlines; the long groups and k_runs write plain pointers)
     constexpr unsigned int LONG_CAP = 1u << 16;
     dbuf<int64_t> long_list(LONG_CAP); dbuf<unsigned int> d_nlong(1), d_full(1); d_nlong.zero(s); d_full.zero(s);
     if (nv > 0) {
         vg_prof_scope ps("index_runs", (double)nv * (8 + 4 + 4 + 8));
         hipLaunchKernelGGL(k_group_runs, dim3(grid_for(nv, GS_TILE)), dim3(256), 0, s, si.keys.p, si.pos.p, g->d_blk2g.p, g->align_shift, nv,
-                           si.low_bit, gen.p, rowinfo.p, cmap, d_dups.p, long_list.p, d_nlong.p, LONG_CAP);
+                           si.low_bit, gen.p, rowinfo.p, cmap, d_dups.p, long_list.p, d_nlong.p, LONG_CAP, ix.inline_lo);
     }
     unsigned int n_long = 0, need_full = 0;
     d_nlong.download(&n_long, 1, s); si.kept.download(ix.kept.data(), (size_t)n, s); d_dups.download(ix.dups.data(), (size_t)n, s);
@@ -2789,7 +2849,7 @@ static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_share
         // one launch over n_rows rows (`rows` lists them, null = all genomes); rows whose table overflows are listed in `over`
         auto launch = [&](auto kern, int threads, const uint32_t* rows, int n_rows, uint32_t* over) {
             hipLaunchKernelGGL(kern, dim3((n_rows + 7) / 8 * 8), dim3(threads), 0, s, ix.rowinfo.p, ix.gen.p, (uint64_t)ix.gen.n, g->d_base_off.p, g->d_len.p, ix.wbase, n,
-                               min_shared, rows, n_rows, d_out.p, d_cursor.p, cap, over, d_nover.p);
+                               min_shared, rows, n_rows, d_out.p, d_cursor.p, cap, over, d_nover.p, ix.inline_lo);
         };
         {
             vg_prof_scope ps("spgemm_rows", (double)ix.n_rows_info * 4.0);
@@ -2831,7 +2891,7 @@ static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_share
                 d_rows.upload(rows.data() + o, nb, s);
                 vg_prof_scope ps("spgemm_dense_rows", 0);
                 hipLaunchKernelGGL(k_spgemm_dense, dim3(nb), dim3(256), 0, s, ix.rowinfo.p, ix.gen.p, (uint64_t)ix.gen.n, g->d_base_off.p,
-                                   g->d_len.p, ix.wbase, n, min_shared, d_rows.p, dense.p, d_out.p, d_cursor.p, cap);
+                                   g->d_len.p, ix.wbase, n, min_shared, d_rows.p, dense.p, d_out.p, d_cursor.p, cap, ix.inline_lo);
                 VG_HIP(hipStreamSynchronize(s));
             }
         }
@@ -3364,6 +3424,14 @@ extern "C" int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geom
     memset(info, 0, sizeof *info);
     info->P = padded_positions; info->n_passes = 1;
     report_geometry(k, true, shard_kmer_args(padded_positions, 0, k, 1.0, 0, 1), padded_positions, info);
+    VG_API_END
+}
+// the row-pointer rule of a pass (rowptr_inline_lo), asked on the host: *inline_lo = 0 where nothing is inlined
+extern "C" int vg_rowptr_inline_lo(int64_t entries, int64_t n_genomes, uint32_t* inline_lo) {
+    VG_API_BEGIN
+    if (!inline_lo) throw vg_error(VG_EINVAL, "vg_rowptr_inline_lo: null argument");
+    if (entries < 0 || n_genomes < 0) throw vg_error(VG_EINVAL, "vg_rowptr_inline_lo: negative count");
+    *inline_lo = rowptr_inline_lo((uint64_t)entries, n_genomes);
     VG_API_END
 }
 
