@@ -686,7 +686,8 @@ constexpr int REG_GEN_WORDS = 12288;                    // genome words + mask +
 constexpr int REG_LDS_WORDS = LDS_TAB + REG_GEN_WORDS + REG_RR_WORDS + REG_MK_WORDS;
 constexpr int REG_STAGE = REG_LDS_WORDS / 1024 * 1024;  // entries per staging window: the whole LDS block
 constexpr int REG_STAGE0 = (REG_LDS_WORDS - LDS_TAB) / 1024 * 1024;   // slots staged while the table is still live
-constexpr int REG_SLOT_BITS = 17;                       // slot < n_rr < 2^17; tag (<= 14 bits) above it
+constexpr int REG_TAG_SHIFT = 17;                       // pass 0 keeps (bucket << 2) | tag << 17: 4 * bucket < 2^16, tag <= 14 bits
+static_assert(2 * (4 * 1024 * REG_IT / 32) + 3 < REG_RR_WORDS && 4 * 1024 * REG_IT / 32 + 1 < REG_MK_WORDS, "pass 0 reads the words of every trip");
 
 // RR, bucket table and entries of ONE reference by the 1 024 threads of a workgroup (lds: REG_LDS_WORDS words).
 // IT: trips of 4 positions x 1 024 threads the registers hold -- 24 (references up to REG_MAX_RR symbols), 20 (the 40 kb
@@ -723,29 +724,54 @@ __device__ __forceinline__ void build_ref_reg(uint32_t* const lds, const ref_des
             s_rr[2 * ch] = lo; s_rr[2 * ch + 1] = hi; s_mk[ch] = m;
         }
         lds_sync();
-        // pass 0: bucket | tag << 18 of every position (4 consecutive positions out of one 128-bit window), bucket sizes
+        // pass 0: (bucket << 2) | tag << REG_TAG_SHIFT of every position (4 consecutive positions out of one 128-bit
+        // window), bucket sizes.  The low half of the word is the byte address of the bucket's counter.  A trip whose four
+        // positions are valid in every lane of the wave (all msl-mers inside RR, no masked symbol among the msl + 3 it
+        // reads: all but the trips at the separator, at the end of RR and at an N) runs without a test per position;
+        // `straight` remembers those trips for the slot pass.
         uint32_t reg[IT][4];
         const int n4 = (rd.n_rr + 3) & ~3;
+        const int tl = (rd.tag_bits + 1) >> 1, th = rd.tag_bits >> 1;
+        const uint32_t bm = (1u << msl) - 1u;
+        const uint32_t m_lo = bm << 2, m_hi = bm << (2 + msl);
+        const uint32_t m_tl = ((1u << tl) - 1u) << REG_TAG_SHIFT, m_th = ((1u << th) - 1u) << (REG_TAG_SHIFT + tl);
+        const uint32_t m_valid = (8u << msl) - 1u;                  // the msl + 3 mask bits the four positions read
+        const int last4 = rd.n_rr - msl - 3;                         // the last p0 whose four msl-mers lie inside RR
+        char* const tab_bytes = reinterpret_cast<char*>(tab);
+        uint32_t straight = 0;
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int p0 = 4 * (tid + 1024 * it);
-            reg[it][0] = reg[it][1] = reg[it][2] = reg[it][3] = 0xffffffffu;
-            if (p0 < n4) {
-                // the msl + tag bases of a position are <= 32 bits: one funnel shift over two words serves each of the
-                // four positions (p0 is a multiple of 4: their bit offsets 2 * (p0 & 15) + 2 j stay below 32)
-                const int wi = 2 * (p0 >> 5); const uint32_t sh = (uint32_t)(p0 & 31);
-                // (msl + tag bases of the four positions = bits 0 .. 3 + 7 + 7 of the planes from p0 on: one funnel shift per
-                // plane and one for the mask serve all four)
-                const uint32_t XL = __builtin_amdgcn_alignbit(s_rr[wi + 2], s_rr[wi], sh), XH = __builtin_amdgcn_alignbit(s_rr[wi + 3], s_rr[wi + 1], sh);
-                const uint32_t XM = __builtin_amdgcn_alignbit(s_mk[(p0 >> 5) + 1], s_mk[p0 >> 5], sh);
+            // the msl + tag bases of a position are <= 32 bits: one funnel shift over two words serves each of the
+            // four positions (p0 is a multiple of 4: their bit offsets 2 * (p0 & 15) + 2 j stay below 32).  The words
+            // of a trip behind RR are read too (they lie inside s_rr and s_mk; what they hold is not used).
+            const int wi = 2 * (p0 >> 5); const uint32_t sh = (uint32_t)(p0 & 31);
+            // (msl + tag bases of the four positions = bits 0 .. 3 + 7 + 7 of the planes from p0 on: one funnel shift per
+            // plane and one for the mask serve all four)
+            const uint32_t XL = __builtin_amdgcn_alignbit(s_rr[wi + 2], s_rr[wi], sh), XH = __builtin_amdgcn_alignbit(s_rr[wi + 3], s_rr[wi + 1], sh);
+            const uint32_t XM = __builtin_amdgcn_alignbit(s_mk[(p0 >> 5) + 1], s_mk[p0 >> 5], sh);
+            if (__builtin_amdgcn_ballot_w64(p0 <= last4 && (XM & m_valid) == 0) == __builtin_amdgcn_ballot_w64(true)) {
+                straight |= 1u << it;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int p = p0 + j;
-                    if (p + msl <= rd.n_rr && ((XM >> j) & ((1u << msl) - 1u)) == 0) {
-                        const uint32_t xl = XL >> j, xh = XH >> j;
-                        const uint32_t bt = bucket_of(xl, xh, msl) | (tag_of(xl, xh, msl, rd.tag_bits) << 18);
-                        atomicAdd(&tab[bt & 0x3ffffu], 1u);
-                        reg[it][j] = bt;
+                    // bucket: the msl low bits of each plane from bit j on, side by side from bit 2 on; tag: the next tl and
+                    // th bits, side by side from bit REG_TAG_SHIFT on (every shift count below is >= 0: msl <= 7, j <= 3)
+                    const uint32_t b4 = (((XL << 2) >> j) & m_lo) | (((XH << (2 + msl)) >> j) & m_hi);
+                    atomicAdd(reinterpret_cast<uint32_t*>(tab_bytes + b4), 1u);
+                    reg[it][j] = b4 | ((XL << (REG_TAG_SHIFT - msl - j)) & m_tl) | ((XH << (REG_TAG_SHIFT + tl - msl - j)) & m_th);
+                }
+            } else {
+                reg[it][0] = reg[it][1] = reg[it][2] = reg[it][3] = 0xffffffffu;
+                if (p0 < n4) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int p = p0 + j;
+                        if (p + msl <= rd.n_rr && ((XM >> j) & bm) == 0) {
+                            const uint32_t xl = XL >> j, xh = XH >> j;
+                            const uint32_t bt = (bucket_of(xl, xh, msl) << 2) | (tag_of(xl, xh, msl, rd.tag_bits) << REG_TAG_SHIFT);
+                            atomicAdd(reinterpret_cast<uint32_t*>(tab_bytes + (bt & 0xffffu)), 1u);
+                            reg[it][j] = bt;
+                        }
                     }
                 }
             }
@@ -753,23 +779,33 @@ __device__ __forceinline__ void build_ref_reg(uint32_t* const lds, const ref_des
         }
         lds_sync();
         const uint32_t total = lds_scan_exclusive_waves(tab, nb, wtot);     // tab[b] = first slot of bucket b
-        // every entry takes its slot (an invalid position keeps 0xffffffff: its slot field lies beyond every
-        // window); afterwards tab[b] = END of bucket b.  The entries of the first REG_STAGE0 slots are staged
-        // right away, in the LDS that the table does not occupy (one window sweep less).
+        // every entry takes its slot and becomes slot | tag << pos_bits (slot < n_rr <= 2^pos_bits; an invalid position
+        // keeps 0xffffffff: its slot field lies beyond every bucket, so what a window stages for it is never copied
+        // out); afterwards tab[b] = END of bucket b.  The entries of the first REG_STAGE0 slots are staged right away,
+        // in the LDS that the table does not occupy (one window sweep less).  An entry is the register with the
+        // position in place of the slot.
         uint32_t* const stage0 = lds + LDS_TAB;
+        const uint32_t pos_mask = (1u << rd.pos_bits) - 1u;
         {
             uint32_t t4 = 4u * (uint32_t)tid;
             asm volatile("" : "+v"(t4));
+            auto take_slot = [&](uint32_t r) { return atomicAdd(reinterpret_cast<uint32_t*>(tab_bytes + (r & 0xffffu)), 1u); };
+            auto place = [&](uint32_t& r, uint32_t slot, uint32_t pos) {
+                r = slot | ((r >> REG_TAG_SHIFT) << rd.pos_bits);
+                if (slot < (uint32_t)REG_STAGE0) stage0[slot] = (r & ~pos_mask) | pos;
+            };
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
+                if ((straight >> it) & 1u) {                     // (the four cursors are asked for before any entry is staged)
+                    uint32_t slot[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t bt = reg[it][j];
-                    if (bt != 0xffffffffu) {
-                        const uint32_t slot = atomicAdd(&tab[bt & 0x3ffffu], 1u);
-                        reg[it][j] = slot | ((bt >> 18) << REG_SLOT_BITS);
-                        if (slot < (uint32_t)REG_STAGE0) stage0[slot] = (t4 + (uint32_t)(4096 * it + j)) | ((bt >> 18) << rd.pos_bits);
-                    }
+                    for (int j = 0; j < 4; ++j) slot[j] = take_slot(reg[it][j]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) place(reg[it][j], slot[j], t4 + (uint32_t)(4096 * it + j));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (reg[it][j] != 0xffffffffu) place(reg[it][j], take_slot(reg[it][j]), t4 + (uint32_t)(4096 * it + j));
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -788,15 +824,17 @@ __device__ __forceinline__ void build_ref_reg(uint32_t* const lds, const ref_des
         for (uint32_t base = REG_STAGE0; base < total; base += REG_STAGE) {
             uint32_t t4 = 4u * (uint32_t)tid;
             asm volatile("" : "+v"(t4));                         // nothing below is hoisted out of the window loop (it would triple the live registers)
+            uint32_t minus_base4 = 0u - 4u * base;
+            asm volatile("" : "+s"(minus_base4));                // (kept apart from the shift: one v_lshl_add_u32 forms the byte offset)
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    uint32_t v = reg[it][j];
-                    asm volatile("" : "+v"(v));
-                    const uint32_t d = (v & ((1u << REG_SLOT_BITS) - 1u)) - base;
-                    if (d < (uint32_t)REG_STAGE)
-                        stage[d] = (t4 + (uint32_t)(4096 * it + j)) | ((v >> REG_SLOT_BITS) << rd.pos_bits);
+                    asm volatile("" : "+v"(reg[it][j]));
+                    const uint32_t v = reg[it][j];
+                    const uint32_t d4 = ((v & pos_mask) << 2) + minus_base4; // byte offset of the slot inside the window
+                    if (d4 < 4u * (uint32_t)REG_STAGE)
+                        *reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(stage) + d4) = (v & ~pos_mask) | (t4 + (uint32_t)(4096 * it + j));
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
