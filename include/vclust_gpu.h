@@ -381,6 +381,39 @@ int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path,
 int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_edges,
                      int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats);
 
+/* Update of a prior clustering (this repository's definition; DESIGN.md section 9, "Update of a prior clustering"): new objects
+ * are added to clusters that are taken as given.  Objects with a prior cluster are *prior*, the others *new*; the visit order is
+ * the prior objects in index order, then the new ones in index order.  Rows are read as above, and a row between two prior
+ * objects is ignored.  VG_CLUSTER_CDHIT / VG_CLUSTER_UCLUST: every prior object keeps its cluster and every prior cluster its
+ * representative; the new objects are visited in visit order and join the earliest (cd-hit) or heaviest (uclust; ties: earliest)
+ * representative, prior or new, they have an edge to, else found a cluster.  VG_CLUSTER_SINGLE: the connected components of the
+ * prior partition plus the kept edges (prior clusters may merge); the representative is the earliest member by index. */
+typedef struct {
+    int64_t rounds, sweep_objects, n_edges;     /* as vg_cluster_stats; n_edges counts the kept edges only */
+    int64_t n_prior, n_new;                     /* objects with / without a prior cluster */
+    int64_t joined_prior, joined_new, founded;  /* new objects by outcome: joined a prior representative, joined a new one, founded a
+                                                 * cluster (single: joined_new = 0, founded = new objects in components without a prior object) */
+    int64_t prior_merged;                       /* single: prior clusters minus components that contain a prior object; 0 otherwise */
+} vg_cluster_update_stats;
+/* The array-level update.  prior_rep[n_objects]: -1 for a new object, else the index of the representative of the object's prior
+ * cluster (prior_rep[prior_rep[i]] == prior_rep[i]; it need not be the cluster's earliest member).  A value outside [-1, n_objects)
+ * or a representative that is not its own representative is VG_EINVAL, as is an algorithm other than the three above; every
+ * argument check runs on the host before any device use.  label[n_objects]: the numbering of vg_cluster_graph applied to the
+ * final partition (by earliest member); representative[n_objects]: the frozen or founding representative (cd-hit, uclust) or the
+ * earliest member (single).  stats may be NULL.  No device is VG_ENODEV, n_objects >= 2^31 VG_EOVERFLOW. */
+int vg_cluster_update_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                            int algorithm, const int32_t* prior_rep, int32_t* label, int32_t* representative,
+                            vg_cluster_update_stats* stats);
+/* File to file, with the host parse and the error messages of vg_cluster.  prior_path: a clusters.tsv of this library (header
+ * `object<TAB>cluster`, one line per prior object), matched to the ids file by name.  Column 2 is a cluster number, and the
+ * representative of a prior cluster is then its earliest member in the ids file; with prior_is_repr it is the representative's id
+ * (as p->representatives writes it), which must be an object of the prior file and its own representative.  A name that is not
+ * in the ids file, a name listed twice, a malformed line or such a representative is VG_EINVAL naming the file and line, reported
+ * before any device use.  out_path: clusters.tsv of vg_cluster for the final partition; with p->representatives the second
+ * column is the representative above (a frozen one even where a new member comes earlier in the ids file). */
+int vg_cluster_update(const char* ani_path, const char* ids_path, const char* prior_path, int prior_is_repr,
+                      const char* out_path, const vg_cluster_params* p, vg_cluster_update_stats* stats);
+
 /* Single-linkage merge table and multi-level cuts (this repository's; DESIGN.md section 9, "Merge table").  The graph is the
  * one above.  Edge {a, b} (a < b) of weight w has the key (-w, a, b), weights compared as doubles with -0.0 = +0.0: a strict
  * total order.  Kruskal over the edges in key order; an edge whose ends lie in different clusters is a merge, and there are

@@ -4,6 +4,7 @@ table), rounds, objects finished by the tail sweep, end-to-end wall time.
   python tools/cluster_timing.py [--sizes 100000 1000000] [--ani ani.tsv --ids ani.ids.tsv] [--metric tani --min 0.95] [--linkage]
   python tools/cluster_timing.py --complete [--sizes 100000] [--clique-chain 200]
   python tools/cluster_timing.py --average [--sizes 100000] [--floor 0.8]
+  python tools/cluster_timing.py --update [--sizes 100000] [--new-fraction 0.01]
 
 Synthetic graphs: families of 20-200 objects in index order, ~50 rows per object (both directions, ~25 distinct
 neighbours), weights 0.80-1.00 inside families and a few weak rows between them.  With --ani, the file is also clustered
@@ -18,7 +19,11 @@ clique (the 50-rows-per-object families are no cliques and would merge almost no
 clique of N objects whose weights force one merge per round, with the time per round.  --average: the average-linkage merge
 table (vg_cluster_average_linkage_graph, floor --floor) on the clique-family graph beside the complete-linkage table, both in the
 same process, each run once and discarded and then timed three times; the row prints the two profile groups
-`cluster_average_best` / `cluster_average_contract`, the rounds and the ratio of GPU time to `complete`.
+`cluster_average_best` / `cluster_average_contract`, the rounds and the ratio of GPU time to `complete`.  --update: the update of a
+prior clustering (vg_cluster_update_graph) on the synthetic family graph with the last --new-fraction of the objects new: the
+prior is the plain run on the rows among the other objects, the update gets the rows with a new end (what `align --db` writes),
+and the plain run on the whole graph (vg_cluster_graph) is the yardstick, in the same process; each is run once and discarded and
+then timed three times.  The row also says whether the update's labels equal the plain run's (properties P1 and P2).
 """
 import argparse
 import json
@@ -126,6 +131,24 @@ def average_row(name, n, q, r, w, floor):
                 complete_rounds=cst['rounds'], complete_merges=cst['n_merges'], gpu_ratio_to_complete=round(gpu / max(gpu1, 1e-9), 2), **ast)
 
 
+def update_rows(n, q, r, w, new_fraction):
+    n_prior = n - max(1, int(round(n * new_fraction)))
+    inside = (q < n_prior) & (r < n_prior)
+    nq, nr, nw = (np.ascontiguousarray(x[~inside]) for x in (q, r, w))          # the rows with a new end
+    res = []
+    for algo in ('single', 'cd-hit', 'uclust'):
+        _, prep, _ = api.cluster_graph(n_prior, q[inside], r[inside], w[inside], algo)
+        prior = np.concatenate([prep, np.full(n - n_prior, -1, np.int32)])
+        (plab, prep_full, pst), pwall, pkern = median_of_three(lambda: api.cluster_graph(n, q, r, w, algo))
+        (lab, rep, st), wall, kern = median_of_three(lambda: api.cluster_update_graph(n, nq, nr, nw, prior, algo))
+        res.append(dict(input=f'synthetic n={n} rows={len(q)}, last {n - n_prior} objects new ({len(nq)} rows)', algorithm=algo,
+                        wall_ms=round(wall, 2), gpu_ms=round(sum(kern.values()), 2), kernels=kern,
+                        plain_wall_ms=round(pwall, 2), plain_gpu_ms=round(sum(pkern.values()), 2), plain_rounds=pst['rounds'],
+                        plain_sweep_objects=pst['sweep_objects'], plain_edges=pst['n_edges'],
+                        equals_plain=bool((lab == plab).all() and (rep == prep_full).all()), **st))
+    return res
+
+
 def timed(fn):
     api.profile_reset()
     t0 = time.perf_counter()
@@ -147,6 +170,8 @@ def main():
     ap.add_argument('--clique-chain', type=int, default=0, metavar='N')
     ap.add_argument('--average', action='store_true')
     ap.add_argument('--floor', type=float, default=0.8)
+    ap.add_argument('--update', action='store_true')
+    ap.add_argument('--new-fraction', type=float, default=0.01)
     ap.add_argument('--json', type=pathlib.Path)
     a = ap.parse_args()
     if a.complete:
@@ -176,6 +201,13 @@ def main():
             row = average_row('synthetic clique families', n, *clique_family_graph(n), a.floor)
             print(json.dumps(row), flush=True)
             res.append(row)
+        a.sizes = []
+    if a.update:
+        api.cluster_update_graph(2, [0], [1], [1.0], [0, -1])
+        for n in a.sizes:
+            for row in update_rows(n, *family_graph(n), a.new_fraction):
+                print(json.dumps(row), flush=True)
+                res.append(row)
         a.sizes = []
     for n in a.sizes:
         q, r, w = family_graph(n)

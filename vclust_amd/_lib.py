@@ -68,6 +68,11 @@ class ClusterStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('sweep_objects', C.c_int64), ('n_edges', C.c_int64)]
 
 
+class ClusterUpdateStats(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ('rounds', 'sweep_objects', 'n_edges', 'n_prior', 'n_new', 'joined_prior', 'joined_new',
+                                                'founded', 'prior_merged')]
+
+
 class LinkageStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('n_edges', C.c_int64), ('n_merges', C.c_int64)]
 
@@ -79,6 +84,8 @@ CLUSTER_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2, 'set-cover': 3}
 LINKAGE_ALGORITHMS = {'single': 0, 'complete': 4}
 # ... and with average linkage (UPGMA), which Clusty does not have: it always runs in the library, with or without the merge table
 HIERARCHY_ALGORITHMS = {**LINKAGE_ALGORITHMS, 'average': 5}
+# the algorithms under which new objects are added to a prior clustering (vg_cluster_update / vg_cluster_update_graph)
+UPDATE_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2}
 
 
 class DedupParams(C.Structure):
@@ -190,6 +197,9 @@ SYMBOLS = {
     'vg_cluster': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams)]),
     'vg_cluster_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_int,
                                    P(C.c_int32), P(C.c_int32), P(ClusterStats)]),
+    'vg_cluster_update_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_int, P(C.c_int32),
+                                          P(C.c_int32), P(C.c_int32), P(ClusterUpdateStats)]),
+    'vg_cluster_update': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, P(ClusterParams), P(ClusterUpdateStats)]),
     'vg_cluster_linkage_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_int32), P(C.c_int32),
                                            P(C.c_double), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(LinkageStats)]),
     'vg_cluster_levels_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_double), C.c_int,

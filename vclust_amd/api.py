@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, AlignParams, ClusterStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStats, ClusterUpdateStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -295,6 +295,37 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     check(_lib.load().vg_cluster_graph(n, *rows, known[algorithm], label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
                                        C.byref(st)))
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
+
+
+def cluster_update_graph(n_objects, q, r, w, prior_rep, algorithm='single'):
+    """Add new objects to a prior clustering (vg_cluster_update_graph; DESIGN.md section 9, "Update of a prior clustering").
+    prior_rep[i] is -1 for a new object, else the index of the representative of i's prior cluster (its own representative; it
+    need not be the cluster's earliest member).  Rows are read as by cluster_graph, and a row between two prior objects is
+    ignored.  'cd-hit' / 'uclust': prior clusters and their representatives are frozen, and the new objects are visited after
+    the prior ones; 'single': the components of the prior partition plus the kept rows.  -> (label int32[n], representative
+    int32[n], stats dict): label numbers the final partition by earliest member, representative is the frozen or founding
+    representative (single: the earliest member)."""
+    if algorithm not in UPDATE_ALGORITHMS:
+        raise ValueError(f'algorithm {algorithm!r} cannot update a prior clustering (choices: {", ".join(UPDATE_ALGORITHMS)})')
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    prior = np.ascontiguousarray(prior_rep, dtype=np.int32)
+    if n < 1 << 31 and len(prior) != n:
+        raise ValueError('prior_rep must have one entry per object')
+    label = np.zeros(max(n, 1) if n < 1 << 31 else 1, dtype=np.int32)
+    rep = np.zeros_like(label)
+    st = ClusterUpdateStats()
+    P = C.POINTER
+    check(_lib.load().vg_cluster_update_graph(n, *rows, UPDATE_ALGORITHMS[algorithm], prior.ctypes.data_as(P(C.c_int32)),
+                                              label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
+    return label[:n], rep[:n], {name: getattr(st, name) for name, _ in ClusterUpdateStats._fields_}
+
+
+def cluster_update(ani_path, ids_path, prior_path, out_path, algorithm='single', prior_repr=False, **options):
+    """clusters.tsv of the objects of the ids file, with the clusters of the clusters.tsv `prior_path` taken as given
+    (vg_cluster_update).  prior_repr: the second column of prior_path holds representative ids (as representatives=True writes
+    them).  options: those of cluster().  -> the update's counts as a dict."""
+    return cluster(ani_path, ids_path, out_path, algorithm=algorithm, prior_path=prior_path, prior_repr=prior_repr, **options)
 
 
 def _rows(q, r, w):

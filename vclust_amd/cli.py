@@ -5,7 +5,8 @@ output files (vclust.py:178-421, 1380-1521) but call libvclust_gpu.so (HIP, MI35
 ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster` passes its
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
 single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster); `--out-linkage` and
-`--levels` (the merge table of single, complete or average linkage and its cuts) always run on the GPU, and so does `--algorithm average`.  `deduplicate` does
+`--levels` (the merge table of single, complete or average linkage and its cuts) always run on the GPU, and so do `--algorithm average`
+and `--prior` (new genomes added to the clusters of an earlier clusters.tsv: vg_cluster_update).  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
 without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
 `--contained` always run on the GPU.  `info` reports the library and the optional CPU tools.
@@ -197,6 +198,12 @@ def get_parser() -> argparse.ArgumentParser:
                     help='Further thresholds of the metric (0-1, none below its minimum): one more column per level, the cut of '
                          'the same hierarchy (single, complete or average linkage) there; under average linkage the cut at a level '
                          'is not a run at that threshold: the rows between the two still count in the averages')
+    cl.add_argument('--prior', metavar='<file>', type=_existing_path, dest='prior_path',
+                    help='clusters.tsv of an earlier run: its clusters are taken as given and the other genomes of --ids are added '
+                         'to them (--algorithm single, cd-hit or uclust; always runs on the GPU).  Under cd-hit and uclust every '
+                         'earlier cluster keeps its members and its representative; under single, earlier clusters may merge')
+    cl.add_argument('--prior-repr', action='store_true', dest='prior_repr',
+                    help='The second column of --prior holds representative ids, as --out-repr writes them [%(default)s]')
     cl.add_argument('--leiden-resolution', metavar='<float>', type=_unit_float, default=0.7)
     cl.add_argument('--leiden-beta', metavar='<float>', type=_unit_float, default=0.01)
     cl.add_argument('--leiden-iterations', metavar='<int>', type=int, default=2)
@@ -383,7 +390,8 @@ def handle_align(args, parser, logger):
 
 def cluster_call(args):
     """What the front-end hands to vg_cluster for validated cluster arguments -- the counterpart of cmd_clusty
-    (vclust.py:1184-1278): a minimum only for values > 0, the num_alns maximum only for values > 0."""
+    (vclust.py:1184-1278): a minimum only for values > 0, the num_alns maximum only for values > 0.  With --prior the call
+    also carries prior_path and prior_repr, and goes to vg_cluster_update."""
     mins = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio') if getattr(args, k) > 0}
     call = dict(ani_path=args.input_path, ids_path=args.ids_path, out_path=args.output_path, algorithm=args.algorithm,
                 metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives, **mins)
@@ -391,13 +399,28 @@ def cluster_call(args):
         call['out_linkage'] = args.linkage_path
     if getattr(args, 'levels', None):
         call['levels'] = list(args.levels)
+    if getattr(args, 'prior_path', None) is not None:     # --prior: vg_cluster_update (no reference counterpart)
+        call['prior_path'] = args.prior_path
+        call['prior_repr'] = bool(args.prior_repr)
     return call
 
 
 def handle_cluster(args, parser, logger):
-    from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS
+    """`cluster`: bin/clusty where it exists and computes what is asked; the library otherwise, and always for the merge table,
+    its cuts, average linkage and --prior.  --prior adds the genomes of --ids that the earlier clusters.tsv does not list to its
+    clusters (the ids file and the rows are those of an `align --db` run; DESIGN.md section 9, "Update of a prior clustering")."""
+    from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS
     linkage_path, levels = getattr(args, 'linkage_path', None), getattr(args, 'levels', None)
     hierarchy = linkage_path is not None or bool(levels)
+    prior_path = getattr(args, 'prior_path', None)
+    if prior_path is None and getattr(args, 'prior_repr', False):
+        parser.error('--prior-repr describes the file of --prior: it needs --prior.')
+    if prior_path is not None:
+        if args.algorithm not in UPDATE_ALGORITHMS:
+            parser.error(f'--prior adds genomes to an earlier clustering under --algorithm {", ".join(UPDATE_ALGORITHMS)}, '
+                         f'not under {args.algorithm}.')
+        if hierarchy:
+            parser.error('--prior takes the earlier clusters as given: it excludes --out-linkage and --levels.')
     if hierarchy:
         if args.algorithm not in HIERARCHY_ALGORITHMS:
             parser.error('--out-linkage and --levels are a linkage hierarchy: they need --algorithm single, --algorithm complete '
@@ -406,10 +429,10 @@ def handle_cluster(args, parser, logger):
         for level in levels or ():
             if floor and level < floor:
                 parser.error(f'--levels {level:g} is below --{args.metric} {floor:g}: rows below the threshold are not edges.')
-    if hierarchy or args.algorithm == 'average' or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
+    if hierarchy or prior_path is not None or args.algorithm == 'average' or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
         # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster); the merge table and
         # its cuts (which Clusty does not have) always do, for every hierarchy, and so does average linkage, which Clusty does
-        # not have either.  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and still goes to Clusty below.
+        # not have either, and --prior.  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and still goes to Clusty below.
         if not vars(args).get(args.metric, 0):
             parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
         from . import stages
@@ -419,8 +442,15 @@ def handle_cluster(args, parser, logger):
                 + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
                 + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
                 + (f' --out-linkage {linkage_path}' if linkage_path is not None else '')
+                + (f' --prior {prior_path}' + (' --prior-repr' if args.prior_repr else '') if prior_path is not None else '')
                 + f' [1 GPU] -> {args.output_path}')
-        run_native(desc, lambda: stages.cluster(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
+        counts = []
+        run_native(desc, lambda: counts.append(stages.cluster(verbosity=args.verbosity_level, **call)), args.verbosity_level, logger)
+        if prior_path is not None:
+            c = counts[0]
+            logger.info(f'Prior clustering updated: {c["n_prior"]} prior + {c["n_new"]} new genomes, {c["n_edges"]} kept edges; new genomes: '
+                        f'{c["joined_prior"]} joined a prior cluster, {c["joined_new"]} joined a new one, {c["founded"]} founded a cluster; '
+                        f'{c["prior_merged"]} prior cluster(s) merged away')
         return
     _require_binary(BIN_CLUSTY)
     threshold = vars(args).get(args.metric, 0)

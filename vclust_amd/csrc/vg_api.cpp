@@ -214,6 +214,31 @@ extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char
     VG_API_END
 }
 
+extern "C" int vg_cluster_update(const char* ani_path, const char* ids_path, const char* prior_path, int prior_is_repr,
+                                 const char* out_path, const vg_cluster_params* p, vg_cluster_update_stats* stats) {
+    VG_API_BEGIN
+    if (!ani_path || !ids_path || !prior_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster_update: null argument");
+    if (p->algorithm != VG_CLUSTER_SINGLE && p->algorithm != VG_CLUSTER_CDHIT && p->algorithm != VG_CLUSTER_UCLUST)
+        throw vg_error(VG_EINVAL, "vg_cluster_update: the update of a prior clustering is single, cd-hit or uclust");
+    if (stats) *stats = vg_cluster_update_stats{};
+    cluster_input in;
+    read_cluster_input("vg_cluster_update", ani_path, ids_path, p, nullptr, 0, in);
+    std::vector<int32_t> prior;
+    vg_cluster_read_prior(prior_path, in.ids, prior_is_repr != 0, prior);
+    vg_host_mark("prior clusters parsed");
+    const int64_t n = (int64_t)in.ids.size();
+    std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
+    vg_cluster_update_stats st{};
+    check(vg_cluster_update_graph(n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), p->algorithm, prior.data(), label.data(), rep.data(), &st));
+    vg_host_mark("clusters computed");
+    vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0);
+    if (stats) *stats = st;
+    if (p->verbosity >= 2)
+        fprintf(stderr, "vg_cluster_update: %lld prior + %lld new objects, %lld rows passed, %lld kept edges, %lld rounds, %lld objects by the tail sweep\n",
+                (long long)st.n_prior, (long long)st.n_new, (long long)in.q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+    VG_API_END
+}
+
 extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
                                   const char* linkage_path, const double* levels, int n_levels) {
     VG_API_BEGIN

@@ -6,6 +6,9 @@
 //   uclust    sweep in index order once a round decides too little
 //   set-cover rounds of 2-hop local maxima of (unassigned-neighbour count, -index), then a one-workgroup greedy sweep
 //   labels    min member per cluster, multi-member clusters numbered by earliest member, then singletons
+//   update    a prior clustering taken as given (vg_cluster_update_graph): objects renumbered to visit ranks (prior first), rows
+//             between two prior objects dropped at the emit, the states / parents seeded from the prior clusters, then the rounds,
+//             the sweep and the hooking above unchanged, and the labels after mapping back
 //   linkage   the single-linkage merge table: edges ranked by (w descending, a, b) with one more radix sort, Boruvka rounds on
 //             the ranks (find + hook + jump + relabel), the marked forest edges compacted in rank order; node numbering on the host
 //   rounds    the loop of the two contraction-based hierarchies (agglomerate): rounds that merge every pair of mutually nearest
@@ -58,11 +61,16 @@ __device__ __forceinline__ void add_count(unsigned long long* counter, int c) {
 #define GRID_STRIDE(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 // ---------------------------------------------------------------- edge graph
-// both directions of every row; a self row becomes two sentinel keys (src = n) that sort behind every edge
-__global__ void k_emit(const uint32_t* q, const uint32_t* r, const double* w, int64_t rows, uint32_t n, uint64_t* keys, double* vals) {
+// both directions of every row; a self row becomes two sentinel keys (src = n) that sort behind every edge.  MAPPED (the update of
+// a prior clustering): both ends become visit ranks, and a row whose ends are both prior objects (rank < n_prior) is dropped the
+// same way
+template <bool MAPPED>
+__global__ void k_emit(const uint32_t* q, const uint32_t* r, const double* w, int64_t rows, uint32_t n, const int32_t* visit, uint32_t n_prior,
+                       uint64_t* keys, double* vals) {
     GRID_STRIDE(k, rows) {
-        const uint64_t a = q[k], b = r[k];
-        const bool self = a == b;
+        uint64_t a = q[k], b = r[k];
+        bool self = a == b;
+        if (MAPPED) { a = (uint64_t)visit[a]; b = (uint64_t)visit[b]; self = self || (a < n_prior && b < n_prior); }
         keys[2 * k] = self ? (uint64_t)n << 32 : a << 32 | b;
         keys[2 * k + 1] = self ? (uint64_t)n << 32 : b << 32 | a;
         vals[2 * k] = vals[2 * k + 1] = w[k];
@@ -576,6 +584,58 @@ __global__ void k_head_labels(const int32_t* fm, const int32_t* fs, const int32_
 }
 __global__ void k_gather(const int32_t* rep, const int32_t* lab, int64_t n, int32_t* label) { GRID_STRIDE(i, n) label[i] = lab[rep[i]]; }
 
+// ---------------------------------------------------------------- update of a prior clustering ("Update")
+// prior[i]: -1 for a new object, else the index of the representative of i's prior cluster.  Visit rank: the prior objects in
+// index order, then the new ones in index order; everything between the edge emit and the labels runs on visit ranks.
+__global__ void k_new_flags(const int32_t* prior, int64_t n, int32_t* flag) { GRID_STRIDE(i, n) flag[i] = prior[i] < 0; }
+// before[] = the exclusive scan of flag[]: the new objects ahead of i.  visit[] and its inverse, and the number of prior objects
+__global__ void k_visit_rank(const int32_t* flag, const int32_t* before, int64_t n, int32_t* visit, int32_t* inv, int32_t* n_prior_out) {
+    const int32_t n_prior = (int32_t)n - (before[n - 1] + flag[n - 1]);
+    GRID_STRIDE(i, n) {
+        const int32_t v = flag[i] ? n_prior + before[i] : (int32_t)i - before[i];
+        visit[i] = v; inv[v] = (int32_t)i;
+        if (i == 0) *n_prior_out = n_prior;
+    }
+}
+// cd-hit / uclust: a prior representative is REP, a prior member MEMBER(its representative), whichever of the two comes first
+__global__ void k_seed_greedy(const int32_t* prior, const int32_t* visit, int64_t n, int32_t* state) {
+    GRID_STRIDE(i, n) { const int32_t p = prior[i]; if (p >= 0) state[visit[i]] = visit[p]; }
+}
+// single: the parent of a prior object is the smallest visit rank of its prior cluster, so that parent[x] <= x holds whichever
+// member the prior file calls the representative.  minv[] is indexed by the representative's rank and starts as the identity (a
+// representative is a member of its cluster), so only a member that comes before its representative has anything to lower: none
+// does where the representative is the earliest member, and a large prior cluster does not serialise its members on one word
+__global__ void k_seed_min(const int32_t* prior, const int32_t* visit, int64_t n, int32_t* minv) {
+    GRID_STRIDE(i, n) {
+        const int32_t p = prior[i];
+        if (p < 0) continue;
+        const int32_t vp = visit[p], v = visit[i];
+        if (v < vp) atomicMin(minv + vp, v);
+    }
+}
+__global__ void k_seed_single(const int32_t* prior, const int32_t* visit, const int32_t* minv, int64_t n, int32_t* parent) {
+    GRID_STRIDE(i, n) { const int32_t p = prior[i], v = visit[i]; parent[v] = p >= 0 ? minv[visit[p]] : v; }
+}
+// back to object ids: the cluster id of object i as an object (greedy: its representative; single: some member of its component)
+__global__ void k_unmap(const int32_t* root, const int32_t* visit, const int32_t* inv, int64_t n, int32_t* out) {
+    GRID_STRIDE(i, n) out[i] = inv[root[visit[i]]];
+}
+// c[0..2]: new objects that joined a cluster with a prior object / joined a new representative / founded (single: lie in a
+// component without a prior object); c[3]: prior clusters; c[4]: prior objects that are still a cluster id (greedy: all the prior
+// representatives; single: one per component that holds a prior object)
+__global__ void k_update_counts(const int32_t* root, const int32_t* prior, const int32_t* visit, int64_t n, int32_t n_prior, bool single,
+                                unsigned long long* c) {
+    int jp = 0, jn = 0, fd = 0, pc = 0, pk = 0;
+    GRID_STRIDE(i, n) {
+        const int32_t v = visit[i], s = root[v];
+        if (prior[i] >= 0) { pc += prior[i] == (int32_t)i; pk += s == v; }
+        else if (s < n_prior) ++jp;
+        else if (single || s == v) ++fd;
+        else ++jn;
+    }
+    add_count(c + 0, jp); add_count(c + 1, jn); add_count(c + 2, fd); add_count(c + 3, pc); add_count(c + 4, pk);
+}
+
 // a round that decides fewer objects than this (and < 1 % of those left) hands the rest to the one-workgroup sweep
 constexpr int64_t LOW_PROGRESS = 4096;
 bool low_progress(int64_t decided, int64_t left) { return decided < LOW_PROGRESS && decided * 100 < left; }
@@ -620,9 +680,12 @@ void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double 
         throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1] (average linkage)");
 }
 
-// the edge graph of the rows on the device: the m directed edges sorted by (src, dst) with their weights, and the CSR
+// the edge graph of the rows on the device: the m directed edges sorted by (src, dst) with their weights, and the CSR.  With a
+// visit_map (the update of a prior clustering) the graph is over visit ranks and holds no edge between two prior objects.
 struct edge_graph { dbuf<uint64_t> ukeys; dbuf<double> uvals; int64_t m = 0; dbuf<int64_t> off; dbuf<int32_t> adj; };
-void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, hipStream_t s, edge_graph& g) {
+struct visit_map { const int32_t* visit = nullptr; int64_t n_prior = 0; };      // visit[object] = visit rank (device); ranks < n_prior are prior
+void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, hipStream_t s, edge_graph& g,
+                      visit_map vm = {}) {
     dbuf<uint64_t>& ukeys = g.ukeys; dbuf<double>& uvals = g.uvals; int64_t& m = g.m;
     const int bits = id_bits(n);
 
@@ -634,7 +697,10 @@ void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const dou
             dbuf<uint32_t> dq((size_t)n_rows), dr((size_t)n_rows); dbuf<double> dw((size_t)n_rows);
             dq.upload(q, (size_t)n_rows, s); dr.upload(r, (size_t)n_rows, s); dw.upload(w, (size_t)n_rows, s);
             vg_prof_scope ps("cluster_edges_emit", (double)n_rows * 48.0);
-            hipLaunchKernelGGL(k_emit, dim3(grid_of(n_rows)), dim3(TPB), 0, s, dq.p, dr.p, dw.p, n_rows, (uint32_t)n, keys.p, vals.p);
+            if (vm.visit)
+                hipLaunchKernelGGL(k_emit<true>, dim3(grid_of(n_rows)), dim3(TPB), 0, s, dq.p, dr.p, dw.p, n_rows, (uint32_t)n, vm.visit, (uint32_t)vm.n_prior, keys.p, vals.p);
+            else
+                hipLaunchKernelGGL(k_emit<false>, dim3(grid_of(n_rows)), dim3(TPB), 0, s, dq.p, dr.p, dw.p, n_rows, (uint32_t)n, (const int32_t*)nullptr, 0u, keys.p, vals.p);
         }
         {
             vg_prof_scope ps("cluster_edges_sort", (double)nd * 32.0 * 2.0);
@@ -942,8 +1008,9 @@ void average_on_device(int64_t n, edge_graph& eg, double floor, hipStream_t s, v
 
 // ---------------------------------------------------------------- the algorithms of vg_cluster_graph: root[i] = the cluster id of i
 // hook + compress, one launch each per round; the changed word is read back every 4 rounds (of the last)
-void single_on_device(int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
-    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n);
+// (seeded: root[] already holds a forest of depth one with parent[x] <= x -- the prior clusters of an update -- in place of k_iota)
+void single_on_device(int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts, bool seeded = false) {
+    if (!seeded) hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, root.p, n);
     dbuf<int32_t> changed(1);
     for (;;) {
         for (int k = 0; k < 4; ++k) {
@@ -961,12 +1028,14 @@ void single_on_device(int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32
 // f(std::true_type) for uclust, f(std::false_type) for cd-hit: a launch of either instantiation is written once
 template <class F> void with_uclust(bool uclust, F f) { if (uclust) f(std::true_type{}); else f(std::false_type{}); }
 // cd-hit, uclust and set cover: rounds that decide objects (round(counter) launches one, counting its decisions) until none is
-// left; a round of low progress hands the rest to the one-workgroup sweep()
-template <class Round, class Sweep>
-void decide_in_rounds(int64_t n, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts, Round round, Sweep sweep) {
+// left; a round of low progress hands the rest to the one-workgroup sweep().  seed() (the update of a prior clustering) writes the
+// final states of the n - undecided objects that are decided before the first round.
+template <class Round, class Sweep, class Seed>
+void decide_in_rounds(int64_t undecided, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts, Round round, Sweep sweep, Seed seed) {
     dbuf<unsigned long long> d_dec(1);
     VG_HIP(hipMemsetAsync(root.p, 0xff, root.bytes(), s));
-    for (int64_t left = n; left > 0;) {
+    seed();
+    for (int64_t left = undecided; left > 0;) {
         d_dec.zero(s);
         round(d_dec.p);
         ++sts.rounds;
@@ -975,19 +1044,29 @@ void decide_in_rounds(int64_t n, hipStream_t s, dbuf<int32_t>& root, vg_cluster_
         if (left > 0 && low_progress(dec, left + dec)) { sweep(); sts.sweep_objects = left; left = 0; }
     }
 }
-void greedy_on_device(bool uclust, int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
+template <class Round, class Sweep>
+void decide_in_rounds(int64_t n, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts, Round round, Sweep sweep) {
+    decide_in_rounds(n, s, root, sts, round, sweep, [] {});
+}
+// seed / n_prior (the update of a prior clustering): the first n_prior objects get their states from seed() and are never
+// undecided, so the rounds pass over them and the sweep starts behind them
+template <class Seed>
+void greedy_on_device(bool uclust, int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts, int64_t n_prior, Seed seed) {
     const int64_t* off = eg.off.p; const int32_t* adj = eg.adj.p; const double* wts = eg.uvals.p;
-    decide_in_rounds(n, s, root, sts, [&](unsigned long long* decided) {
+    decide_in_rounds(n - n_prior, s, root, sts, [&](unsigned long long* decided) {
         vg_prof_scope ps(uclust ? "cluster_uclust_round" : "cluster_cdhit_round", (double)eg.m * 12.0 + (double)n * 12.0);
         with_uclust(uclust, [&](auto uc) {
             hipLaunchKernelGGL(k_greedy_round<decltype(uc)::value>, dim3(grid_of(n)), dim3(TPB), 0, s, n, off, adj, wts, root.p, decided); });
     }, [&] {
         // every object before the first undecided one is decided: the sweep may start at the lowest undecided index,
-        // which the host does not know -- it starts at 0 and skips decided chunks 256 at a time
+        // which the host does not know -- it starts at 0 (behind the prior objects of an update) and skips decided chunks 256 at a time
         vg_prof_scope ps(uclust ? "cluster_uclust_sweep" : "cluster_cdhit_sweep", (double)eg.m * 12.0);
         with_uclust(uclust, [&](auto uc) {
-            hipLaunchKernelGGL(k_greedy_sweep<decltype(uc)::value>, dim3(1), dim3(SWEEP_TPB), 0, s, n, off, adj, wts, root.p, (int64_t)0); });
-    });
+            hipLaunchKernelGGL(k_greedy_sweep<decltype(uc)::value>, dim3(1), dim3(SWEEP_TPB), 0, s, n, off, adj, wts, root.p, n_prior); });
+    }, seed);
+}
+void greedy_on_device(bool uclust, int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
+    greedy_on_device(uclust, n, eg, s, root, sts, 0, [] {});
 }
 void set_cover_on_device(int64_t n, const edge_graph& eg, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& sts) {
     const int64_t* off = eg.off.p; const int32_t* adj = eg.adj.p;
@@ -1067,6 +1146,89 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
     d_label.download(label, (size_t)n, s);
     d_rep.download(representative, (size_t)n, s);
     VG_HIP(hipStreamSynchronize(s));
+    VG_API_END
+}
+
+// ---------------------------------------------------------------- update of a prior clustering
+extern "C" int vg_cluster_update_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                       int algorithm, const int32_t* prior_rep, int32_t* label, int32_t* representative,
+                                       vg_cluster_update_stats* stats) {
+    VG_API_BEGIN
+    const char* fn = "vg_cluster_update_graph";
+    check_rows(fn, n_objects, q, r, w, n_rows);
+    if (n_objects && (!prior_rep || !label || !representative)) throw vg_error(VG_EINVAL, std::string(fn) + ": null argument");
+    if (algorithm != VG_CLUSTER_SINGLE && algorithm != VG_CLUSTER_CDHIT && algorithm != VG_CLUSTER_UCLUST)
+        throw vg_error(VG_EINVAL, std::string(fn) + ": the update of a prior clustering is single, cd-hit or uclust");
+    check_row_values(fn, n_objects, q, r, w, n_rows);
+    const int64_t n = n_objects;
+    int64_t bad = first_bad_row(n, [&](int64_t i) { return prior_rep[i] < -1 || prior_rep[i] >= n; });
+    if (bad >= 0) throw vg_error(VG_EINVAL, std::string(fn) + ": prior_rep[" + std::to_string(bad) + "] = " + std::to_string(prior_rep[bad]) + " outside -1.." + std::to_string(n - 1));
+    bad = first_bad_row(n, [&](int64_t i) { return prior_rep[i] >= 0 && prior_rep[prior_rep[i]] != prior_rep[i]; });
+    if (bad >= 0) throw vg_error(VG_EINVAL, std::string(fn) + ": prior_rep[" + std::to_string(bad) + "] = " + std::to_string(prior_rep[bad]) + " is not its own representative");
+    vg_cluster_update_stats st_local{}; vg_cluster_update_stats& sts = stats ? *stats : st_local;
+    sts = vg_cluster_update_stats{};
+    if (n == 0) return VG_OK;
+    vg_require_device();
+    hipStream_t s = vg_stream();
+    const bool single = algorithm == VG_CLUSTER_SINGLE;
+
+    // ---- visit ranks
+    dbuf<int32_t> prior((size_t)n), visit((size_t)n), inv((size_t)n);
+    int32_t n_prior = 0;
+    {
+        dbuf<int32_t> flag((size_t)n), before((size_t)n), d_np(1);
+        prior.upload(prior_rep, (size_t)n, s);
+        vg_prof_scope ps("cluster_update_map", (double)n * 4.0 * 7.0);
+        hipLaunchKernelGGL(k_new_flags, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, n, flag.p);
+        exclusive_scan_i32(flag.p, before.p, n, s);
+        hipLaunchKernelGGL(k_visit_rank, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)flag.p, (const int32_t*)before.p, n, visit.p, inv.p, d_np.p);
+        d_np.download(&n_prior, 1, s);
+        VG_HIP(hipStreamSynchronize(s));
+    }
+    if (n_prior < 0 || n_prior > n) throw vg_error(VG_EHIP, std::string(fn) + ": the visit ranks are inconsistent (internal error)");
+    sts.n_prior = n_prior; sts.n_new = n - n_prior;
+
+    // ---- the kept edges on visit ranks, then the algorithm from the seeded state
+    edge_graph eg;
+    build_edge_graph(n, q, r, w, n_rows, s, eg, visit_map{ visit.p, n_prior });
+    sts.n_edges = eg.m / 2;
+    dbuf<int32_t> root((size_t)n);
+    vg_cluster_stats cs{};
+    if (single) {
+        {
+            dbuf<int32_t> minv((size_t)n);
+            vg_prof_scope ps("cluster_update_seed", (double)n * 4.0 * 8.0);
+            hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, minv.p, n);
+            hipLaunchKernelGGL(k_seed_min, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, (const int32_t*)visit.p, n, minv.p);
+            hipLaunchKernelGGL(k_seed_single, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, (const int32_t*)visit.p, (const int32_t*)minv.p, n, root.p);
+        }
+        single_on_device(n, eg, s, root, cs, true);
+    } else
+        greedy_on_device(algorithm == VG_CLUSTER_UCLUST, n, eg, s, root, cs, n_prior, [&] {
+            vg_prof_scope ps("cluster_update_seed", (double)n * 4.0 * 4.0);
+            hipLaunchKernelGGL(k_seed_greedy, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, (const int32_t*)visit.p, n, root.p);
+        });
+    VG_HIP(hipGetLastError());
+    sts.rounds = cs.rounds; sts.sweep_objects = cs.sweep_objects;
+    check_roots(n, root, s);
+
+    // ---- outcome counts, then labels on object ids: numbering by earliest member; the representative is the frozen or founding
+    // one (greedy: the cluster id itself) or the earliest member (single)
+    dbuf<unsigned long long> d_cnt(5);
+    dbuf<int32_t> cid((size_t)n), d_label, d_rep;
+    d_cnt.zero(s);
+    hipLaunchKernelGGL(k_update_counts, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)prior.p, (const int32_t*)visit.p, n, n_prior,
+                       single, d_cnt.p);
+    hipLaunchKernelGGL(k_unmap, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)visit.p, (const int32_t*)inv.p, n, cid.p);
+    labels_on_device(n, cid, true, s, d_label, d_rep);
+    VG_HIP(hipGetLastError());
+    unsigned long long cnt[5] = {};
+    d_cnt.download(cnt, 5, s);
+    d_label.download(label, (size_t)n, s);
+    (single ? d_rep : cid).download(representative, (size_t)n, s);
+    VG_HIP(hipStreamSynchronize(s));
+    sts.joined_prior = (int64_t)cnt[0]; sts.joined_new = (int64_t)cnt[1]; sts.founded = (int64_t)cnt[2];
+    sts.prior_merged = (int64_t)cnt[3] - (int64_t)cnt[4];
     VG_API_END
 }
 

@@ -203,6 +203,9 @@ void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);
 void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
                           std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w);
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives);
+// a prior clusters.tsv against the ids (vg_io.cpp): prior_rep[i] = -1 for an object without a line, else the index of its cluster's
+// representative -- the earliest member of the cluster number, or (is_repr) the object named in column 2; VG_EINVAL with file:line
+void vg_cluster_read_prior(const char* path, const std::vector<std::string>& ids, bool is_repr, std::vector<int32_t>& prior_rep);
 // merge table (vg_cluster.hip): the forest edges of the rows in merge order (a < b, weights non-increasing) -- checks the rows
 // (errors name fn), then the device; the node numbering of the table and the labels of a cut are host loops over those records.
 // algorithm: VG_CLUSTER_SINGLE (the maximum spanning forest), VG_CLUSTER_COMPLETE (the worst edge of every complete-linkage merge)

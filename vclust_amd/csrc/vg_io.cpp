@@ -18,6 +18,7 @@
 #include <atomic>
 #include <thread>
 #include <charconv>
+#include <string_view>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -673,6 +674,62 @@ void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_
     for (auto& pt : parts) {
         q.insert(q.end(), pt.q.begin(), pt.q.end()); r.insert(r.end(), pt.r.begin(), pt.r.end()); w.insert(w.end(), pt.w.begin(), pt.w.end());
     }
+}
+
+void vg_cluster_read_prior(const char* path, const std::vector<std::string>& ids, bool is_repr, std::vector<int32_t>& prior_rep) {
+    mapped_text f(path);
+    if (!f.n) row_error(path, 1, "empty file (no header)");
+    const char* end = f.p + f.n;
+    std::unordered_map<std::string_view, int32_t> index;
+    index.reserve(ids.size() * 2);
+    for (size_t i = 0; i < ids.size(); ++i) index.emplace(ids[i], (int32_t)i);
+    prior_rep.assign(ids.size(), -1);
+    // pass 1: every line names an object of the ids file once; its value is kept as (object, line, value text)
+    struct entry { int32_t obj; int64_t line; std::string_view value; uint64_t number; };
+    std::vector<entry> entries;
+    int64_t line = 0;
+    for (const char* a = f.p; a < end;) {
+        const char* e = f.line_end(a);
+        ++line;
+        const char* le = e > a && e[-1] == '\r' ? e - 1 : e;
+        const std::string_view text(a, (size_t)(le - a));
+        a = e + 1;
+        if (line == 1) { if (text != "object\tcluster") row_error(path, 1, "malformed header (expected object<TAB>cluster)"); continue; }
+        if (text.empty()) continue;
+        const size_t tab = text.find('\t');
+        if (tab == std::string_view::npos || tab == 0 || tab + 1 == text.size() || text.find('\t', tab + 1) != std::string_view::npos)
+            row_error(path, line, "malformed line (expected <object><TAB><cluster>)");
+        const std::string_view name = text.substr(0, tab);
+        const auto it = index.find(name);
+        if (it == index.end()) row_error(path, line, "object '" + std::string(name) + "' is not in the ids file");
+        if (prior_rep[(size_t)it->second] != -1) row_error(path, line, "object '" + std::string(name) + "' is listed twice");
+        prior_rep[(size_t)it->second] = -2;                      // (seen; the representative follows)
+        entries.push_back({ it->second, line, text.substr(tab + 1), 0 });
+    }
+    if (is_repr) {
+        // pass 2: the value names a prior object; pass 3: that object names itself
+        for (const entry& en : entries) {
+            const auto it = index.find(en.value);
+            if (it == index.end() || prior_rep[(size_t)it->second] == -1)
+                row_error(path, en.line, "representative '" + std::string(en.value) + "' is not an object of this file");
+            prior_rep[(size_t)en.obj] = it->second;
+        }
+        for (const entry& en : entries) {
+            const int32_t rep = prior_rep[(size_t)en.obj];
+            if (prior_rep[(size_t)rep] != rep) row_error(path, en.line, "representative '" + std::string(en.value) + "' is not its own representative");
+        }
+        return;
+    }
+    // cluster numbers: the representative is the earliest member in the ids file
+    std::unordered_map<uint64_t, int32_t> first;
+    for (entry& en : entries) {
+        const char* vb = en.value.data(); const char* ve = vb + en.value.size();
+        const auto rr = std::from_chars(vb, ve, en.number);
+        if (rr.ec != std::errc() || rr.ptr != ve) row_error(path, en.line, "malformed cluster number '" + std::string(en.value) + "'");
+        const auto ins = first.emplace(en.number, en.obj);
+        if (!ins.second && en.obj < ins.first->second) ins.first->second = en.obj;
+    }
+    for (const entry& en : entries) prior_rep[(size_t)en.obj] = first[en.number];
 }
 
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives) {

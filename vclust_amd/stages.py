@@ -6,7 +6,7 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, AlignParams, ClusterParams, DedupOptions, DedupParams, LzParams, PrefilterParams, check
+from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions, DedupParams, LzParams, PrefilterParams, check
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -66,18 +66,28 @@ CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
 
 
 def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num_alns=0, representatives=False,
-            num_threads=0, verbosity=0, out_linkage=None, levels=None, **mins):
+            num_threads=0, verbosity=0, out_linkage=None, levels=None, prior_path=None, prior_repr=False, **mins):
     """clusters.tsv from ani.tsv + its ids file (vg_cluster).  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio= (0 = off);
     num_alns: max. number of local alignments of a passing row (0 = off).  out_linkage: also the merge table
     -> that file; levels: one more column per level, the cut of the same forest there (vg_cluster_linkage; both need
     algorithm='single', 'complete' or 'average' -- the merge table and the cuts of that hierarchy -- and no level below the metric's
     minimum).  algorithm='complete' or 'average' without either is the cut of that hierarchy at the floor (vg_cluster).  'average'
     (UPGMA in exact arithmetic; a pair without a row counts as 0) stops at the metric's minimum, and its cut at a level is not
-    a run at that minimum: the rows between the two still count in the averages."""
+    a run at that minimum: the rows between the two still count in the averages.  prior_path: a clusters.tsv of an earlier run
+    whose clusters are taken as given and to which the other objects of the ids file are added (vg_cluster_update; algorithm
+    'single', 'cd-hit' or 'uclust', no out_linkage and no levels); prior_repr: its second column holds representative ids.  That
+    call returns the update's counts as a dict, every other one None."""
     unknown = set(mins) - set(CLUSTER_FILTERS)
     if unknown:
         raise TypeError(f'unknown filter(s): {sorted(unknown)}')
     known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS}
+    if prior_path is None and prior_repr:
+        raise ValueError('prior_repr needs prior_path')
+    if prior_path is not None:
+        if out_linkage is not None or levels is not None:
+            raise ValueError('prior_path excludes out_linkage and levels')
+        if algorithm not in UPDATE_ALGORITHMS:
+            raise ValueError(f'algorithm {algorithm!r} cannot update a prior clustering (choices: {", ".join(UPDATE_ALGORITHMS)})')
     if algorithm not in known:
         raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
     p = ClusterParams(algorithm=known[algorithm], metric=metric.encode(), max_num_alns=int(num_alns),
@@ -85,6 +95,11 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     for name, val in mins.items():
         setattr(p, f'min_{name}', float(val))
     paths = (os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)))
+    if prior_path is not None:
+        st = ClusterUpdateStats()
+        check(_lib.load().vg_cluster_update(paths[0], paths[1], os.fsencode(str(prior_path)), int(bool(prior_repr)), paths[2], C.byref(p),
+                                            C.byref(st)))
+        return {name: getattr(st, name) for name, _ in ClusterUpdateStats._fields_}
     if out_linkage is None and levels is None:
         check(_lib.load().vg_cluster(*paths, C.byref(p)))
         return
