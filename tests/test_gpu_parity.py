@@ -43,6 +43,18 @@ def test_kmer_sets_example(example):
         assert np.array_equal(mine, ref)
 
 
+@pytest.mark.parametrize('k,fraction', [(25, 0.5), (21, 0.3)])
+def test_kmer_sets_fraction_example(example, k, fraction):
+    """vg_kmer_set with a fraction: the compact extraction (scan, count, emit) followed by both sorts.  The oracle's set at these
+    fractions is a non-empty proper subset of the full one."""
+    codes, offsets, names, gs = example
+    for idx in (0, 5, 11):
+        seq = codes[offsets[idx]:offsets[idx + 1]]
+        ref = orc.kmer_set(seq, k, fraction)
+        assert 0 < len(ref) < len(orc.kmer_set(seq, k))
+        assert np.array_equal(gs.kmer_set(idx, k, fraction), ref)
+
+
 @pytest.mark.parametrize('k', [12, 28, 29, 30, 31])
 def test_kmer_sets_from_bit_planes(example, k):
     """The kernels read k-mers off the bit planes and keep (hi plane : lo plane) of the smaller strand as the key; what

@@ -2154,13 +2154,14 @@ static kmer_args make_kmer_args(const vg_genomes* g, int k, double fraction, int
     return A;
 }
 
-// shared pipeline: extract -> sort.  Returns sorted keys/pos of the n_valid real k-mers and the
-// per-genome number of k-mers kept by extraction.  compact = true: only kept k-mers were written
-// and the sort payload is the compact index itself (wave_base / cblk map it back to its genome).
+// shared pipeline: extract_kmers -> prefix_sort -> finish_sort.  Extraction leaves the keys of the n_valid real k-mers unsorted (no pos:
+// a key's row number is its index) and the per-genome number of k-mers it kept; the sorts leave keys/pos in order.  compact = true: only
+// kept k-mers were written and the sort payload is the compact index itself (wave_base / cblk map it back to its genome).
 struct sorted_index {
     dbuf<uint64_t> keys; dbuf<uint32_t> pos; dbuf<int> kept; int64_t n_valid = 0;
+    int64_t n_keys = 0;         // entries of keys: the kept k-mers (compact) or every padded position, sentinels included (dense)
     bool compact = false; dbuf<unsigned long long> wave_mask; dbuf<uint32_t> wave_base; dbuf<uint32_t> cblk, goff;
-    int low_bit = 0;            // keys are ordered on bits >= low_bit only (finish = false)
+    int low_bit = 0;            // keys are ordered on bits >= low_bit only (2k + 1: not at all; 0: finish_sort has run)
     dbuf<uint64_t> spare64; dbuf<uint32_t> spare32;     // buffers the sort no longer needs (reused by the caller)
 };
 
@@ -2171,29 +2172,33 @@ static void finish_sort(sorted_index& si, int k) {
         hipStream_t s = vg_stream();
         const size_t n = (size_t)si.n_valid;
         dbuf<uint64_t> k2(n); dbuf<uint32_t> p2(n);
-        size_t tmp_bytes = 0;
-        VG_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, si.keys.p, k2.p, si.pos.p, p2.p, n, 0u, (unsigned)(2 * k), s));
-        dbuf<char> tmp(tmp_bytes);
         vg_prof_scope ps("radix_sort_full", (double)n * 12.0 * 2.0 * ((2 * k + 7) / 8));
-        VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, si.keys.p, k2.p, si.pos.p, p2.p, n, 0u, (unsigned)(2 * k), s));
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, si.keys.p, k2.p, si.pos.p, p2.p, n, 0u, (unsigned)(2 * k), s); });
         VG_HIP(hipStreamSynchronize(s));
         si.keys = std::move(k2); si.pos = std::move(p2);
     }
     si.low_bit = 0;
 }
 
+// ---- extraction.  A compact extraction numbers the kept k-mers through their counts per 64-position word.  Three sources leave
+// the same thing -- out.kept and out.wave_mask, room for out.wave_base, a kept_counts --; extract_kmers chooses between them.
+struct kept_counts {
+    dbuf<uint32_t> wave_cnt;                                  // kept positions of every 64-position word (W + 1 entries, the last is 0)
+    dbuf<uint64_t> stage; dbuf<unsigned int> d_over;          // a scan: the kept k-mers staged per 256-position chunk; whether a chunk overflowed its slots
+    bool scanned = true;                                      // false = a given mask: no staged k-mers (the emit pass computes them), out.kept is filled behind it
+};
 // The k-mer scan of a sub-shard (k_kmer_count: arithmetic-bound, it reads the genomes and writes only its own buffers)
 // does not depend on anything the previous sub-shard computes: the sub-shard loop launches the scan of sub-shard t + 1
 // on the second queue when sub-shard t has finished its own scan, beside t's partition / bucket / SpGEMM kernels
 // (memory- and LDS-bound).  Safe with the single-queue caching allocator: the buffers are taken while the library
 // queue is idle (kmer_shared_pass: the index stage has just synchronised), so no block they receive has work pending on it,
-// and they are handed on to run_extract_sort of pass t + 1, which waits for the scan's event before anything reads them.
+// and they are handed on to extract_kmers of pass t + 1 (take_scan_ahead), which waits for the scan's event before anything reads them.
 struct precount {
-    dbuf<int> kept; dbuf<unsigned long long> wave_mask; dbuf<uint32_t> wave_cnt; dbuf<uint64_t> stage; dbuf<unsigned int> d_over;
+    dbuf<int> kept; dbuf<unsigned long long> wave_mask; kept_counts counts;
     hipEvent_t done = nullptr;                    // recorded behind the scan; null = no scan is waiting to be taken
     void drop() {
         if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); done = nullptr; }     // nothing is freed under a running scan
-        kept.release(); wave_mask.release(); wave_cnt.release(); stage.release(); d_over.release();
+        kept.release(); wave_mask.release(); counts = kept_counts();
     }
     ~precount() { drop(); }
 };
@@ -2212,149 +2217,141 @@ struct pass_inputs {
     int first_row = 0;                            // vg_kmer_shared_new: the SpGEMM runs over the rows of the genomes first_row .. n - 1 only
 };
 static int compact_stage_cap(double keep) { return (int)std::min<double>(256.0, std::ceil(1.5 * 256.0 * keep) + 24.0); }
+// k_kmer_count over the bases on queue st: the kept masks, their counts and the staged k-mers of the keys A keeps
+static void scan_bases(const kmer_args& A, int stage_cap, int* kept, dbuf<unsigned long long>& wave_mask, kept_counts& c, hipStream_t st) {
+    const int64_t W = A.P / 64;
+    wave_mask.alloc((size_t)W + 1); c.wave_cnt.alloc((size_t)W + 1);
+    VG_HIP(hipMemsetAsync(c.wave_cnt.p + W, 0, sizeof(uint32_t), st));
+    c.stage.alloc((size_t)((W + 3) / 4) * stage_cap);
+    c.d_over.alloc(1); c.d_over.zero(st);
+    with_k(A.k == 25 && !A.use_frac, [&](auto K) { hipLaunchKernelGGL(k_kmer_count<K()>, dim3(grid_for((A.P + 255) / 4)), dim3(256), 0, st, A, wave_mask.p, c.wave_cnt.p, kept, c.stage.p, stage_cap, c.d_over.p); });
+}
 // to be called while the library queue is idle
 static void launch_precount(precount& pc, vg_genomes* g, int k, int shard, int n_shards) {
     pc.drop();
-    const int64_t P = g->padded_total(), W = P / 64, n_chunks = (W + 3) / 4;
-    const int stage_cap = compact_stage_cap(1.0 / n_shards);
-    pc.kept.alloc((size_t)std::max(1, g->n)); pc.wave_mask.alloc((size_t)W + 1); pc.wave_cnt.alloc((size_t)W + 1);
-    pc.stage.alloc((size_t)n_chunks * stage_cap); pc.d_over.alloc(1);
     hipStream_t side = vg_side_stream();
-    pc.kept.zero(side); pc.d_over.zero(side);
-    VG_HIP(hipMemsetAsync(pc.wave_cnt.p + W, 0, sizeof(uint32_t), side));
-    const kmer_args A = make_kmer_args(g, k, 1.0, shard, n_shards);
-    with_k(k == 25, [&](auto K) { hipLaunchKernelGGL(k_kmer_count<K()>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, side, A, pc.wave_mask.p, pc.wave_cnt.p, pc.kept.p, pc.stage.p, stage_cap, pc.d_over.p); });
+    pc.kept.alloc((size_t)std::max(1, g->n)); pc.kept.zero(side);
+    scan_bases(make_kmer_args(g, k, 1.0, shard, n_shards), compact_stage_cap(1.0 / n_shards), pc.kept.p, pc.wave_mask, pc.counts, side);
     VG_HIP(hipEventCreateWithFlags(&pc.done, hipEventDisableTiming));
     VG_HIP(hipEventRecord(pc.done, side));
 }
-
-static void run_extract_sort(vg_genomes* g, int k, double fraction, int shard, int n_shards, const pass_inputs& in, sorted_index& out, bool finish = true, bool do_sort = true) {
+static void fresh_rows(sorted_index& out, const vg_genomes* g, int64_t W, hipStream_t s) { out.kept.alloc((size_t)std::max(1, g->n)); out.kept.zero(s); out.wave_base.alloc((size_t)W + 1); }
+// the sub-shard loop's scan ahead (launch_precount), running or done on the second queue
+static void take_scan_ahead(precount& pc, int64_t W, sorted_index& out, kept_counts& c, hipStream_t s) {
+    VG_HIP(hipStreamWaitEvent(s, pc.done, 0));
+    out.kept = std::move(pc.kept);
+    out.wave_base.alloc((size_t)W + 1);
+    out.wave_mask = std::move(pc.wave_mask); c = std::move(pc.counts);
+    (void)hipEventDestroy(pc.done); pc.done = nullptr;
+}
+// the pass's kept mask exists already (one scan served every sub-shard): count its words; the k-mers are computed for the kept
+// positions only, by the emit pass
+static void count_given_mask(const unsigned long long* mask, const vg_genomes* g, int64_t W, sorted_index& out, kept_counts& c, hipStream_t s) {
+    c.scanned = false;
+    fresh_rows(out, g, W, s);
+    out.wave_mask.view(const_cast<unsigned long long*>(mask), (size_t)W + 1); c.wave_cnt.alloc((size_t)W + 1);
+    VG_HIP(hipMemsetAsync(c.wave_cnt.p + W, 0, sizeof(uint32_t), s));
+    if (W > 0) hipLaunchKernelGGL(k_mask_popc, dim3(grid_for(W)), dim3(256), 0, s, mask, W, c.wave_cnt.p);
+}
+// the extraction's own scan of the bases
+static void scan_and_count(const vg_genomes* g, const kmer_args& A, int64_t W, int stage_cap, sorted_index& out, kept_counts& c, hipStream_t s) {
+    fresh_rows(out, g, W, s);
+    vg_prof_scope ps("kmer_count", (double)A.P * (3.0 / 8.0 + 12.0 / 64.0));
+    scan_bases(A, stage_cap, out.kept.p, out.wave_mask, c, s);
+}
+// The k-mers one pass keeps, unsorted, in out.keys (see sorted_index); the stream is idle when it returns.  The fourth source is the
+// dense extract (no fraction, no shards, no mask): a key per padded position, sentinels where there is no k-mer.
+static void extract_kmers(vg_genomes* g, int k, double fraction, int shard, int n_shards, const pass_inputs& in, sorted_index& out) {
     hipStream_t s = vg_stream();
     const int64_t P = g->padded_total();
     // the scan of this very sub-shard may already be running (or done) on the second queue; the first extraction of the pass takes it
-    precount* const pc = in.pre && in.pre->done ? in.pre : nullptr; const bool pre = pc != nullptr;
-    const unsigned long long* premask = pre ? nullptr : in.mask;
-    if (pre) { VG_HIP(hipStreamWaitEvent(s, pc->done, 0)); out.kept = std::move(pc->kept); }
-    else { out.kept.alloc((size_t)std::max(1, g->n)); out.kept.zero(s); }
-    const int use_frac = fraction < 1.0;
+    precount* const pc = in.pre && in.pre->done ? in.pre : nullptr;
+    const unsigned long long* premask = pc ? nullptr : in.mask;
     const kmer_args A = make_kmer_args(g, k, fraction, shard, n_shards);
-    out.compact = use_frac || n_shards > 1 || premask != nullptr;       // (a given mask: the rows are its kept positions)
+    out.compact = A.use_frac || n_shards > 1 || premask != nullptr;     // (a given mask: the rows are its kept positions)
     if (!out.compact && P >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "dense k-mer pass needs < 2^32 padded bases");
     if (P >= (1LL << 37)) throw vg_error(VG_EOVERFLOW, "genome set exceeds 2^37 padded bases");
-    dbuf<uint64_t> keys_a, keys_b; dbuf<uint32_t> pos_a, pos_b;
-    int64_t n_sort = P; unsigned long long nv = 0;
+    out.low_bit = 2 * k + 1;
     if (!out.compact) {
-        keys_a.alloc((size_t)P); keys_b.alloc((size_t)P); pos_a.alloc((size_t)P + 4); pos_b.alloc((size_t)P);
+        unsigned long long nv = 0;
+        out.kept.alloc((size_t)std::max(1, g->n)); out.kept.zero(s);
+        out.keys.alloc((size_t)P);
         dbuf<unsigned long long> d_nvalid(1); d_nvalid.zero(s);
         {
             vg_prof_scope ps("kmer_extract", (double)P * (3.0 / 8.0 + 8.0));
-            hipLaunchKernelGGL(k_kmer_extract, dim3(grid_for((P + 255) / 4)), dim3(256), 0, s, A, keys_a.p, d_nvalid.p, out.kept.p);
+            hipLaunchKernelGGL(k_kmer_extract, dim3(grid_for((P + 255) / 4)), dim3(256), 0, s, A, out.keys.p, d_nvalid.p, out.kept.p);
         }
-        hipLaunchKernelGGL(k_iota, dim3(grid_for(P)), dim3(256), 0, s, pos_a.p, P);
         d_nvalid.download(&nv, 1, s);
-    } else {
-        const int64_t W = P / 64;
-        // slots per 256-position chunk for the kept k-mers (1.5 x the expectation + slack; a chunk that
-        // overflows sends the call to the recomputing emit pass)
-        const double keep = (use_frac ? fraction : 1.0) / n_shards;
-        const int stage_cap = compact_stage_cap(keep);
-        const int64_t n_chunks = (W + 3) / 4;
-        dbuf<uint32_t> wave_cnt; dbuf<uint64_t> stage; dbuf<unsigned int> d_over;
-        out.wave_base.alloc((size_t)W + 1);
-        if (pre) {
-            out.wave_mask = std::move(pc->wave_mask); wave_cnt = std::move(pc->wave_cnt);
-            stage = std::move(pc->stage); d_over = std::move(pc->d_over);
-            (void)hipEventDestroy(pc->done); pc->done = nullptr;
-        } else if (premask) {
-            // the pass's kept mask exists already (one scan served every sub-shard): count its words; the k-mers are computed
-            // for the kept positions only by the emit pass below
-            out.wave_mask.view(const_cast<unsigned long long*>(premask), (size_t)W + 1); wave_cnt.alloc((size_t)W + 1);
-            VG_HIP(hipMemsetAsync(wave_cnt.p + W, 0, sizeof(uint32_t), s));
-            if (W > 0) hipLaunchKernelGGL(k_mask_popc, dim3(grid_for(W)), dim3(256), 0, s, premask, W, wave_cnt.p);
-        } else {
-            out.wave_mask.alloc((size_t)W + 1); wave_cnt.alloc((size_t)W + 1);
-            VG_HIP(hipMemsetAsync(wave_cnt.p + W, 0, sizeof(uint32_t), s));
-            stage.alloc((size_t)n_chunks * stage_cap);
-            d_over.alloc(1); d_over.zero(s);
-            vg_prof_scope ps("kmer_count", (double)P * (3.0 / 8.0 + 12.0 / 64.0));
-            with_k(A.k == 25 && !A.use_frac, [&](auto K) { hipLaunchKernelGGL(k_kmer_count<K()>, dim3(grid_for((P + 255) / 4)), dim3(256), 0, s, A, out.wave_mask.p, wave_cnt.p, out.kept.p, stage.p, stage_cap, d_over.p); });
-        }
-        size_t tb = 0;
-        VG_HIP(rocprim::exclusive_scan(nullptr, tb, wave_cnt.p, out.wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
-        dbuf<char> tmp(tb);
-        VG_HIP(rocprim::exclusive_scan((void*)tmp.p, tb, wave_cnt.p, out.wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s));
-        uint32_t total = 0; unsigned int over = premask ? 1u : 0u;          // (a given mask: no staged k-mers, the emit pass computes them)
-        int64_t total64 = 0;
-        if (premask) {
-            // the words' counts are 32 bits each, their sum may not be: add them up in 64 bits before trusting the scan
-            dbuf<unsigned long long> d_tot(1); size_t tb2 = 0;
-            VG_HIP(rocprim::reduce(nullptr, tb2, wave_cnt.p, d_tot.p, 0ULL, (size_t)W + 1, rocprim::plus<unsigned long long>(), s));
-            dbuf<char> tmp2(tb2);
-            VG_HIP(rocprim::reduce((void*)tmp2.p, tb2, wave_cnt.p, d_tot.p, 0ULL, (size_t)W + 1, rocprim::plus<unsigned long long>(), s));
-            unsigned long long t64 = 0; d_tot.download(&t64, 1, s);
-            VG_HIP(hipMemcpyAsync(&total, out.wave_base.p + W, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            VG_HIP(hipStreamSynchronize(s));
-            total64 = (int64_t)t64;
-        } else {
-            std::vector<int> kept_h((size_t)std::max(1, g->n));
-            VG_HIP(hipMemcpyAsync(&total, out.wave_base.p + W, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            d_over.download(&over, 1, s);
-            out.kept.download(kept_h.data(), (size_t)g->n, s);
-            VG_HIP(hipStreamSynchronize(s));
-            for (int i = 0; i < g->n; ++i) total64 += kept_h[i];
-        }
-        if (total64 >= (1LL << 32) - 1) throw vg_error(VG_EOVERFLOW, "more than 2^32 k-mers in one shard: use more shards");
-        nv = total; n_sort = (int64_t)total;
-        const size_t na = (size_t)std::max<int64_t>(n_sort, 1);
-        keys_a.alloc(na); if (do_sort) pos_a.alloc(na + 4);        // (unsorted, a k-mer's row number is its index: the bucket pipeline needs no array for it)
-        if (do_sort) { keys_b.alloc(na); pos_b.alloc(na); }         // the sort's outputs (the bucket pipeline sorts nothing)
-        vg_host_mark("extract: counted");
-        if (n_sort > 0 && !over) {
-            vg_prof_scope ps("kmer_emit", (double)n_sort * (8.0 + 12.0));
-            hipLaunchKernelGGL(k_kmer_gather, dim3(grid_for(n_chunks * 64)), dim3(256), 0, s, stage.p, stage_cap, out.wave_base.p, W, keys_a.p, pos_a.p);
-        } else if (n_sort > 0) {
-            vg_prof_scope ps("kmer_emit_recompute", (double)P * 3.0 / 8.0 + (double)n_sort * 12.0);
-            // (a wave lists the kept positions of nw words and gives every lane one: about 56 of them, so that a second trip
-            // of a few lanes is rare -- eight words at a seventh kept are 73 positions, two trips for every chunk)
-            const int nw = (int)std::max<int64_t>(1, std::min<int64_t>(8, 56 * P / (64 * std::max<int64_t>(n_sort, 1))));
-            if (n_sort * 4 <= P) hipLaunchKernelGGL(k_kmer_emit_sparse, dim3(grid_for(P / 8)), dim3(256), 0, s, A, out.wave_mask.p, out.wave_base.p, keys_a.p, pos_a.p, nw);
-            else hipLaunchKernelGGL(k_kmer_emit, dim3(grid_for(P)), dim3(256), 0, s, A, out.wave_mask.p, out.wave_base.p, keys_a.p, pos_a.p);
-        }
-        out.cblk.alloc((size_t)(n_sort >> CBLK_SHIFT) + 2); out.cblk.zero(s);
-        out.goff.alloc((size_t)g->n + 1);
-        hipLaunchKernelGGL(k_cblk, dim3(grid_for(g->n)), dim3(256), 0, s, out.wave_base.p, g->d_base_off.p, g->n, out.cblk.p, out.goff.p);
-        // (a given mask: the kept k-mers of a genome are its rows)
-        if (premask && g->n > 0) hipLaunchKernelGGL(k_kept_from_goff, dim3(grid_for(g->n)), dim3(256), 0, s, (const uint32_t*)out.goff.p, g->n, out.kept.p);
+        VG_HIP(hipStreamSynchronize(s));
+        out.n_valid = (int64_t)nv; out.n_keys = P;
+        return;
     }
-    // Stable LSD radix sort on the top key bits only (bit 2k is the sentinel flag, so sentinels end
-    // up behind every real k-mer); k_group_runs then orders the small equal-prefix groups.
+    const int64_t W = P / 64;
+    // slots per 256-position chunk for the kept k-mers (1.5 x the expectation + slack; a chunk that
+    // overflows sends the call to the recomputing emit pass)
+    const double keep = (A.use_frac ? fraction : 1.0) / n_shards;
+    const int stage_cap = compact_stage_cap(keep);
+    kept_counts c;
+    if (pc) take_scan_ahead(*pc, W, out, c, s); else if (premask) count_given_mask(premask, g, W, out, c, s); else scan_and_count(g, A, W, stage_cap, out, c, s);
+    with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, c.wave_cnt.p, out.wave_base.p, 0u, (size_t)W + 1, rocprim::plus<uint32_t>(), s); });
+    uint32_t total = 0; unsigned int over = c.scanned ? 0u : 1u;
+    unsigned long long total64 = 0;
+    std::vector<int> kept_h(c.scanned ? (size_t)g->n : 0);
+    VG_HIP(hipMemcpyAsync(&total, out.wave_base.p + W, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (c.scanned) { c.d_over.download(&over, 1, s); out.kept.download(kept_h.data(), kept_h.size(), s); }
+    else {
+        // the words' counts are 32 bits each, their sum may not be: add them up in 64 bits before trusting the scan
+        dbuf<unsigned long long> d_tot(1);
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::reduce(tmp, tb, c.wave_cnt.p, d_tot.p, 0ULL, (size_t)W + 1, rocprim::plus<unsigned long long>(), s); });
+        d_tot.download(&total64, 1, s);
+    }
+    VG_HIP(hipStreamSynchronize(s));
+    for (int x : kept_h) total64 += (unsigned long long)x;
+    if (total64 >= (1ULL << 32) - 1) throw vg_error(VG_EOVERFLOW, "more than 2^32 k-mers in one shard: use more shards");
+    const int64_t n_kept = (int64_t)total;
+    out.keys.alloc((size_t)std::max<int64_t>(n_kept, 1));        // (no pos array: unsorted, a k-mer's row number is its index)
+    vg_host_mark("extract: counted");
+    if (n_kept > 0 && !over) {
+        vg_prof_scope ps("kmer_emit", (double)n_kept * (8.0 + 12.0));
+        hipLaunchKernelGGL(k_kmer_gather, dim3(grid_for((W + 3) / 4 * 64)), dim3(256), 0, s, c.stage.p, stage_cap, out.wave_base.p, W, out.keys.p, (uint32_t*)nullptr);
+    } else if (n_kept > 0) {
+        vg_prof_scope ps("kmer_emit_recompute", (double)P * 3.0 / 8.0 + (double)n_kept * 12.0);
+        // (a wave lists the kept positions of nw words and gives every lane one: about 56 of them, so that a second trip
+        // of a few lanes is rare -- eight words at a seventh kept are 73 positions, two trips for every chunk)
+        const int nw = (int)std::max<int64_t>(1, std::min<int64_t>(8, 56 * P / (64 * std::max<int64_t>(n_kept, 1))));
+        if (n_kept * 4 <= P) hipLaunchKernelGGL(k_kmer_emit_sparse, dim3(grid_for(P / 8)), dim3(256), 0, s, A, out.wave_mask.p, out.wave_base.p, out.keys.p, (uint32_t*)nullptr, nw);
+        else hipLaunchKernelGGL(k_kmer_emit, dim3(grid_for(P)), dim3(256), 0, s, A, out.wave_mask.p, out.wave_base.p, out.keys.p, (uint32_t*)nullptr);
+    }
+    out.cblk.alloc((size_t)(n_kept >> CBLK_SHIFT) + 2); out.cblk.zero(s);
+    out.goff.alloc((size_t)g->n + 1);
+    hipLaunchKernelGGL(k_cblk, dim3(grid_for(g->n)), dim3(256), 0, s, out.wave_base.p, g->d_base_off.p, g->n, out.cblk.p, out.goff.p);
+    // (a given mask: the kept k-mers of a genome are its rows)
+    if (!c.scanned && g->n > 0) hipLaunchKernelGGL(k_kept_from_goff, dim3(grid_for(g->n)), dim3(256), 0, s, (const uint32_t*)out.goff.p, g->n, out.kept.p);
+    VG_HIP(hipStreamSynchronize(s));
+    vg_host_mark("extract: emitted");
+    out.n_valid = out.n_keys = n_kept;
+}
+// Stable LSD radix sort of extracted keys on the top key bits only (bit 2k is the sentinel flag, so sentinels end up behind every real k-mer);
+// k_group_runs then orders the small equal-prefix groups.  The payload is a key's index before the sort: its padded position or (compact) its row.
+static void prefix_sort(sorted_index& si, int k) {
+    hipStream_t s = vg_stream();
+    const int64_t n_sort = si.n_keys; const size_t na = (size_t)std::max<int64_t>(n_sort, 1);
+    dbuf<uint32_t> pos_a(na + 4); dbuf<uint64_t> keys_b(na); dbuf<uint32_t> pos_b(na);
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(n_sort)), dim3(256), 0, s, pos_a.p, n_sort);
     const unsigned int end_bit = (unsigned)(2 * k + 1);
     // a few entries per equal-prefix group on average: the run kernel finishes the order in the LDS,
     // at a cost that grows with the group size (measured break-even: ~2.5 entries per prefix)
     unsigned int sort_bits = n_sort <= (5LL << 23) ? 24u : (n_sort <= (5LL << 31) ? 32u : 40u);
     if (sort_bits > end_bit) sort_bits = end_bit;
     const unsigned int begin_bit = end_bit - sort_bits;
-    if (!do_sort) {
-        // the bucket pipeline takes the kept k-mers as they are (compact mode only: every entry is a real k-mer)
-        VG_HIP(hipStreamSynchronize(s));
-        vg_host_mark("extract: emitted");
-        out.keys = std::move(keys_a); out.pos = std::move(pos_a); out.n_valid = (int64_t)nv; out.low_bit = (int)end_bit;
-        return;
-    }
     if (n_sort > 0) {
-        size_t tmp_bytes = 0;
-        VG_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_a.p, keys_b.p, pos_a.p, pos_b.p, (size_t)n_sort, begin_bit, end_bit, s));
-        dbuf<char> tmp(tmp_bytes);
-        int passes = (int)(sort_bits + 7) / 8;
-        vg_prof_scope ps("radix_sort_pairs", (double)n_sort * 12.0 * 2.0 * passes);
-        VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, keys_a.p, keys_b.p, pos_a.p, pos_b.p, (size_t)n_sort, begin_bit, end_bit, s));
+        vg_prof_scope ps("radix_sort_pairs", (double)n_sort * 12.0 * 2.0 * ((sort_bits + 7) / 8));
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, si.keys.p, keys_b.p, pos_a.p, pos_b.p, (size_t)n_sort, begin_bit, end_bit, s); });
     }
     VG_HIP(hipStreamSynchronize(s));
-    out.keys = std::move(keys_b); out.pos = std::move(pos_b); out.n_valid = (int64_t)nv; out.low_bit = (int)begin_bit;
-    out.spare64 = std::move(keys_a); out.spare32 = std::move(pos_a);      // the sort's input: free again, same sizes as rowinfo / gen
-    if (finish) finish_sort(out, k);
+    si.spare64 = std::move(si.keys); si.spare32 = std::move(pos_a);      // the sort's input: free again, same sizes as rowinfo / gen
+    si.keys = std::move(keys_b); si.pos = std::move(pos_b); si.low_bit = (int)begin_bit;
 }
-
 
 // partition digits of the bucket pipeline for n_expect elements: false = the pipeline declines (buckets beyond the LDS sorts)
 static bool bucket_digits(int64_t n_expect, int* total_bits_out, int* B1_out, int* B2_out) {
@@ -2695,37 +2692,38 @@ static void bucket_kernels(bucket_run& R) {
     }
     VG_HIP(hipStreamSynchronize(s));
 }
-// The pipeline as a sequence.  The source is ix.si's kept k-mers (compact) or the bases (dense; ix.n_rows_info set by the
-// caller, d_kept receives the k-mers kept per genome).  A RANGE shard of the dense source (A.dig_n < 2^11): ix.si receives
-// the kept masks, the row bases and the row -> genome map of the pass, n_rows_info becomes the number of kept k-mers, and
-// the row pointers are indexed by row number.
-// geometry, source and level-1 tables of a run; false = the pipeline declines the input
-static bool start_bucket_run(bucket_run& R, const kmer_args& A) {
+// Geometry, source, level-1 tables, count and scatter of a run; beside(R) is called once the geometry stands (clear_rows_aside works beside
+// level 1).  declined = the pipeline does not take the input; empty = no valid k-mer (see level1_count); records = they lie in R.a_rec.
+enum class level1 { declined, empty, records };
+template <class F> static level1 open_bucket_run(bucket_run& R, const kmer_args& A, F beside) {
     const bool dense = R.dense; const int k = R.k; kmer_index& ix = R.ix;
     R.rows_zero.st = R.s;
     const int64_t n_src = dense ? R.g->padded_total() : ix.nv;
-    if (!bucket_geometry_for(k, dense, A, n_src, R.G)) return false;
+    if (!bucket_geometry_for(k, dense, A, n_src, R.G)) return level1::declined;
     const bucket_geometry& G = R.G;
-    R.S.A = A; R.S.keys = dense ? nullptr : ix.si.keys.p; R.S.pos = dense ? nullptr : ix.si.pos.p; R.S.n = n_src; R.S.k2 = 2 * k; R.S.bin_lo = G.bin_lo;
+    R.S.A = A; R.S.keys = dense ? nullptr : ix.si.keys.p; R.S.pos = nullptr; R.S.n = n_src; R.S.k2 = 2 * k; R.S.bin_lo = G.bin_lo;      // (no pos: a kept k-mer's row number is its index)
     R.cmap = dense ? compact_map{ nullptr, nullptr } : compact_map{ ix.si.goff.p, ix.si.cblk.p };
     R.k25 = dense && k == 25 && !A.use_frac && A.n_shards == 1;
     R.T1s.alloc((size_t)G.nb1 * (size_t)G.n_st + 1); R.slab.alloc((size_t)G.n_slabs * G.nb1); R.d_off1.alloc((size_t)G.nb1 + 1);
     R.G.L2.T1s = R.T1s.p; R.G.L2.off1 = R.d_off1.p;
-    return true;
+    beside(R);
+    level1_tmp t;
+    if (!level1_count(R, t)) return level1::empty;
+    level1_scatter(R);
+    return level1::records;
 }
+// The pipeline as a sequence.  The source is ix.si's kept k-mers (compact) or the bases (dense; ix.n_rows_info set by the
+// caller, d_kept receives the k-mers kept per genome).  A RANGE shard of the dense source (A.dig_n < 2^11): ix.si receives
+// the kept masks, the row bases and the row -> genome map of the pass, n_rows_info becomes the number of kept k-mers, and
+// the row pointers are indexed by row number.  false = the pipeline declines the input
 static bool build_index_buckets(vg_genomes* g, int k, bool dense, const kmer_args& A, int* d_kept, const pass_inputs& in, kmer_index& ix) {
     hipStream_t s = vg_stream();
     vg_host_mark("buckets: enter");
     pass_timer index_timer(in.index_ms, s);                // (placement trials: count ... bucket kernels of this pass)
     bucket_run R{ g, k, dense, in, ix, d_kept, s };
-    if (!start_bucket_run(R, A)) return false;
+    const level1 opened = open_bucket_run(R, A, clear_rows_aside);
+    if (opened != level1::records) return opened == level1::empty;
     const bucket_geometry& G = R.G;
-    clear_rows_aside(R);
-    {
-        level1_tmp t;
-        if (!level1_count(R, t)) return true;
-        level1_scatter(R);
-    }
     R.boff.alloc((size_t)G.nbk + 1);
     if (G.levels == 2) level2(R);
     else {
@@ -2748,7 +2746,7 @@ static bool index_by_buckets(vg_genomes* g, int k, double fraction, int shard, i
             if (ok) kept_b.download(ix.kept.data(), (size_t)n, s);
         }
     } else {
-        run_extract_sort(g, k, fraction, shard, n_shards, in, ix.si, false, /*do_sort=*/false);
+        extract_kmers(g, k, fraction, shard, n_shards, in, ix.si);       // (the pipeline takes the kept k-mers as they are: it sorts nothing)
         ix.nv = ix.si.n_valid; ix.n_rows_info = std::max<int64_t>(ix.nv, 1);
         ok = build_index_buckets(g, k, false, A, nullptr, in, ix);
         if (ok) ix.si.kept.download(ix.kept.data(), (size_t)n, s);
@@ -2765,7 +2763,8 @@ static void index_by_radix(vg_genomes* g, int k, double fraction, int shard, int
     rowinfo.release(); gen.release(); ix.arena.release();
     d_dups.zero(s);
     si = sorted_index();
-    run_extract_sort(g, k, fraction, shard, n_shards, in, si, false);
+    extract_kmers(g, k, fraction, shard, n_shards, in, si);
+    prefix_sort(si, k);
     const int64_t nv = ix.nv = si.n_valid;
     ix.n_rows_info = si.compact ? std::max<int64_t>(nv, 1) : g->padded_total();      // row pointers: per kept k-mer or per base
     // row pointers and genome list live in the sort's input buffers (16 + 16 GB less at 100 k genomes)
@@ -2911,23 +2910,27 @@ static void spgemm_pairs(vg_genomes* g, const kmer_index& ix, uint32_t min_share
 static bool pass_source_dense(int64_t P, double fraction, int n_shards, bool masked) {
     return !(fraction < 1.0) && (n_shards == 1 || range_shards(P, fraction, n_shards)) && !masked;
 }
-// one pass over the k-mers of one shard: per-genome set sizes and (a, b, shared) of every pair (see spgemm_pairs for dev_out)
-static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared, int64_t* set_sizes, std::vector<vg_pair_count>& host_pairs,
-                             const pass_inputs& in = pass_inputs{}, dbuf<vg_pair_count>* dev_out = nullptr, unsigned long long* dev_n = nullptr) {
-    const int n = g->n;
-    kmer_index ix;
-    ix.d_dups.alloc((size_t)n); ix.d_dups.zero(vg_stream());
-    ix.kept.resize((size_t)n); ix.dups.resize((size_t)n);
+// The index of one pass over the set's genomes, by the bucket pipeline or else the general path, and how the SpGEMM is to read its rows
+static void build_index(vg_genomes* g, int k, double fraction, int shard, int n_shards, const pass_inputs& in, kmer_index& ix) {
+    ix.d_dups.alloc((size_t)g->n); ix.d_dups.zero(vg_stream());
+    ix.kept.resize((size_t)g->n); ix.dups.resize((size_t)g->n);
     // RANGE shards (sets below 2^32 padded bases, no fraction) keep the dense source: the pass scans the bases, keeps the
     // k-mers of its level-1 buckets and numbers them as rows; everything behind level 1 is a 1/n_shards slice of the whole
     // pass, row pointers included.  HASH shards (larger sets, fractions) materialise their k-mers first (compact source).
     const bool range = range_shards(g, fraction, n_shards);
     const bool dense_src = pass_source_dense(g->padded_total(), fraction, n_shards, in.mask != nullptr);
-    const bool bucket_ok = index_by_buckets(g, k, fraction, shard, n_shards, dense_src, in, ix);      // 1. the index
+    const bool bucket_ok = index_by_buckets(g, k, fraction, shard, n_shards, dense_src, in, ix);
     if (!bucket_ok) index_by_radix(g, k, fraction, shard, n_shards, in, ix);
     ix.compact_rows = bucket_ok ? (!dense_src || range) : ix.si.compact;
     ix.rows_from_map = in.xs && range && bucket_ok;
     ix.wbase = ix.compact_rows ? ix.si.wave_base.p : nullptr;
+}
+// one pass over the k-mers of one shard: per-genome set sizes and (a, b, shared) of every pair (see spgemm_pairs for dev_out)
+static void kmer_shared_pass(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared, int64_t* set_sizes, std::vector<vg_pair_count>& host_pairs,
+                             const pass_inputs& in = pass_inputs{}, dbuf<vg_pair_count>* dev_out = nullptr, unsigned long long* dev_n = nullptr) {
+    const int n = g->n;
+    kmer_index ix;
+    build_index(g, k, fraction, shard, n_shards, in, ix);      // 1. the index
     for (int i = 0; i < n; ++i) set_sizes[i] = (int64_t)ix.kept[i] - ix.dups[i];      // 2. set sizes, and the scan ahead
     ix.si.keys.release();
     // (the library queue is idle here -- the index stage ended with a synchronisation --: the sub-shard loop has the k-mer scan of
@@ -3082,83 +3085,106 @@ extern "C" void vg_set_placement_trials(int n) {
     g_placement_trials = n < 1 ? 1 : (n > 8 ? 8 : n);
     g_trials_done.clear();                                          // (a caller who asks again gets trials again)
 }
+// the argument checks the k-mer entries share, in the order each makes them behind its own null check (one without shards or a fraction passes none)
+static void check_kmer_args(int k, double fraction = 1.0, int shard = 0, int n_shards = 1) {
+    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
+    if (n_shards < 1 || shard < 0 || shard >= n_shards) throw vg_error(VG_EINVAL, "bad shard");
+    if (!(fraction > 0.0) || fraction > 1.0) throw vg_error(VG_EINVAL, "fraction must be in (0,1]");
+}
+// a result as the C caller receives it: a malloc'ed copy (one element where there is nothing) that the caller frees
+template <class T> static T* to_caller(const std::vector<T>& v) {
+    T* out = (T*)malloc(sizeof(T) * std::max<size_t>(1, v.size()));
+    if (!out) throw vg_error(VG_ENOMEM, "out of host memory");
+    if (!v.empty()) memcpy(out, v.data(), sizeof(T) * v.size());
+    return out;
+}
+struct shard_call {                     // what a call over one shard of a set is: the entry points fill it in
+    vg_genomes* g; int k; double fraction; int shard, n_shards; uint32_t min_shared;
+    int first_row = 0;                  // vg_kmer_shared_new: pairs of the genomes first_row .. n - 1 only
+    vg_slice_exchange* xs = nullptr;    // a single RANGE pass counts by sliced scan + exchange
+};
+// The passes of a call as its plan cuts them: one pass, or the sub-shard loop, whose partial (a, b, count) records stay in HBM and are summed
+// ONCE there: sort on (a, b), reduce by key, threshold on the sum.  The pairs are left in host_pairs, or with dev_pairs in HBM (as spgemm_pairs).
+static void run_passes(const shard_call& c, const shard_plan& plan, int64_t* set_sizes, std::vector<vg_pair_count>& host_pairs,
+                       dbuf<vg_pair_count>* dev_pairs = nullptr, unsigned long long* dev_n = nullptr) {
+    if (plan.one_pass) {
+        pass_inputs in; in.xs = c.xs; in.first_row = c.first_row;
+        return kmer_shared_pass(c.g, c.k, c.fraction, c.shard, c.n_shards, c.min_shared, set_sizes, host_pairs, in, dev_pairs, dev_n);
+    }
+    dbuf<vg_pair_count> d_sum; unsigned long long n_sum = 0;
+    dbuf<vg_pair_count>& sum = dev_pairs ? *dev_pairs : d_sum;
+    // (HASH sub-shards are sized on an expectation: a set whose repeated k-mers crowd one sub-shard beyond the 32-bit row
+    // numbers of a pass is cut finer instead of failing)
+    for (int attempt = 0, sub = plan.sub;; ++attempt) {
+        try { kmer_shared_subshards(c.g, c.k, c.fraction, c.shard, c.n_shards, sub, c.min_shared, set_sizes, sum, &n_sum, c.first_row); break; }
+        catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; sum.release(); }
+    }
+    if (dev_pairs) { *dev_n = n_sum; return; }
+    host_pairs.resize((size_t)n_sum);
+    if (n_sum) { d_sum.download(host_pairs.data(), (size_t)n_sum, vg_stream()); VG_HIP(hipStreamSynchronize(vg_stream())); }
+}
+// Placement trials.  Where the driver puts the workspace decides between two states of the scattering kernels (the
+// bucket kernel 39 against 44 ms at 100 k genomes: same virtual addresses, same requests, same UTCL1 misses, 1.3-2 x
+// the translation-in-flight and DRAM-credit stalls -- profiles/r05_placement_states.md), and it stays for the
+// life of the blocks.  The FIRST whole pass of a long-lived process over a large set therefore tries up to three
+// placements -- the cached blocks of the previous one set aside, the pass repeated on fresh ones -- and keeps the
+// workspace whose index stage (level-1 count ... bucket kernel) was fastest; the results of the passes are the same, the caller gets the first's.
+// OPT-IN (vg_set_placement_trials; bench.py asks for 4 and says so in its line): an embedder's first call does no hidden
+// extra passes.  The caller's result is already in `acc`: whatever happens in a trial pass -- out of memory beside the
+// parked blocks, a HIP error -- is swallowed here, the parked workspace comes back and the call returns what it computed.
+static void placement_trials(const shard_call& c) {
+    vg_genomes* g = c.g; const int k = c.k, n = g->n;
+    const int64_t P = g->padded_total(); const bool dense = c.fraction >= 1.0 && c.n_shards == 1;
+    const int max_trials = placement_trials_now();
+    size_t fr = 0, tot = 0;
+    bool first_time = false;
+    if (dense && !vg_one_shot() && max_trials > 1 && P >= (1LL << 30)) {
+        std::lock_guard<std::mutex> lk(g_trials_mu);
+        first_time = !g_trials_done[{ P, k }]++;
+    }
+    if (!(first_time && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 2 * vg_dev_cached_bytes() + (8ULL << 30))) return;
+    float index_ms = 0.f; pass_inputs timed; timed.index_ms = &index_ms;       // the index stage of the last timed pass
+    std::vector<int64_t> sz2((size_t)n); std::vector<vg_pair_count> acc2;
+    auto pass = [&] { kmer_shared_pass(g, k, c.fraction, c.shard, c.n_shards, c.min_shared, sz2.data(), acc2, timed); };
+    float best = 0.f;
+    try {
+        pass();       // (the first pass paid for the allocations: time this placement on a second one)
+        best = index_ms;
+    } catch (...) { (void)hipGetLastError(); best = 0.f; }
+    for (int trial = 1; trial < max_trials && best > 0.f; ++trial) {
+        const double w0 = vg_alloc_wait_ms();
+        vg_dev_park_cache();
+        bool keep_new = false;
+        try {
+            pass();
+            pass();
+            keep_new = index_ms > 0.f && index_ms < 0.97f * best;
+            if (getenv("VG_ALLOC_TRACE")) fprintf(stderr, "[vg placement] trial %d: index stage %.2f ms against %.2f ms -> %s\n", trial, index_ms, best, keep_new ? "kept" : "dropped");
+            if (keep_new) best = index_ms;
+        } catch (...) { (void)hipGetLastError(); keep_new = false; }
+        vg_dev_unpark(!keep_new);
+        if (vg_alloc_wait_ms() - w0 > 500.0) break;          // (memory the driver still has to wipe: a trial costs seconds here)
+    }
+}
 extern "C" int vg_kmer_shared(vg_genomes* g, int k, double fraction, int shard, int n_shards, uint32_t min_shared,
                               int64_t* set_sizes, vg_pair_count** pairs, int64_t* n_pairs) {
     VG_API_BEGIN
     if (!g || !set_sizes || !pairs || !n_pairs) throw vg_error(VG_EINVAL, "vg_kmer_shared: null argument");
-    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
-    if (n_shards < 1 || shard < 0 || shard >= n_shards) throw vg_error(VG_EINVAL, "bad shard");
-    if (!(fraction > 0.0) || fraction > 1.0) throw vg_error(VG_EINVAL, "fraction must be in (0,1]");
+    check_kmer_args(k, fraction, shard, n_shards);
     vg_host_mark("vg_kmer_shared: enter");
     vg_require_device();
     int rc = vg_genomes_to_device(g); if (rc) return rc;
     *pairs = nullptr; *n_pairs = 0;
-    const int n = g->n;
-    if (n == 0) return VG_OK;
-    const int64_t P = g->padded_total(); const bool dense = fraction >= 1.0 && n_shards == 1;
+    if (g->n == 0) return VG_OK;
     const shard_plan plan = plan_shards(g, fraction, n_shards, /*host_entry=*/true);
+    shard_call call{ g, k, fraction, shard, n_shards, min_shared };
+    vg_slice_exchange xs; xs.rank = shard; xs.world = n_shards; xs.emulate = true;
+    if (plan.one_pass && g_range_scan_mode == 1 && vg_slice_exchange_applies(g, k, fraction, n_shards)) call.xs = &xs;
     std::vector<vg_pair_count> acc;
-    if (plan.one_pass) {
-        vg_slice_exchange xs; xs.rank = shard; xs.world = n_shards; xs.emulate = true;
-        pass_inputs in; if (g_range_scan_mode == 1 && vg_slice_exchange_applies(g, k, fraction, n_shards)) in.xs = &xs;
-        kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, set_sizes, acc, in);
-        // Placement trials.  Where the driver puts the workspace decides between two states of the scattering kernels (the
-        // bucket kernel 39 against 44 ms at 100 k genomes: same virtual addresses, same requests, same UTCL1 misses, 1.3-2 x
-        // the translation-in-flight and DRAM-credit stalls -- profiles/r05_placement_states.md), and it stays for the
-        // life of the blocks.  The FIRST whole pass of a long-lived process over a large set therefore tries up to three
-        // placements -- the cached blocks of the previous one set aside, the pass repeated on fresh ones -- and keeps the
-        // workspace whose index stage (level-1 count ... bucket kernel) was fastest; the results of the passes are the same, the caller gets the first's.
-        // OPT-IN (vg_set_placement_trials; bench.py asks for 4 and says so in its line): an embedder's first call does no hidden
-        // extra passes.  The caller's result is already in `acc`: whatever happens in a trial pass -- out of memory beside the
-        // parked blocks, a HIP error -- is swallowed here, the parked workspace comes back and the call returns what it computed.
-        const int max_trials = placement_trials_now();
-        size_t fr = 0, tot = 0;
-        bool first_time = false;
-        if (dense && !vg_one_shot() && max_trials > 1 && P >= (1LL << 30)) {
-            std::lock_guard<std::mutex> lk(g_trials_mu);
-            first_time = !g_trials_done[{ P, k }]++;
-        }
-        if (first_time && hipMemGetInfo(&fr, &tot) == hipSuccess && fr > 2 * vg_dev_cached_bytes() + (8ULL << 30)) {
-            float index_ms = 0.f; pass_inputs timed; timed.index_ms = &index_ms;       // the index stage of the last timed pass
-            std::vector<int64_t> sz2((size_t)n); std::vector<vg_pair_count> acc2;
-            float best = 0.f;
-            try {
-                kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2, timed);       // (the first pass paid for the allocations: time this placement on a second one)
-                best = index_ms;
-            } catch (...) { (void)hipGetLastError(); best = 0.f; }
-            for (int trial = 1; trial < max_trials && best > 0.f; ++trial) {
-                const double w0 = vg_alloc_wait_ms();
-                vg_dev_park_cache();
-                bool keep_new = false;
-                try {
-                    kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2, timed);
-                    kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, sz2.data(), acc2, timed);
-                    keep_new = index_ms > 0.f && index_ms < 0.97f * best;
-                    if (getenv("VG_ALLOC_TRACE")) fprintf(stderr, "[vg placement] trial %d: index stage %.2f ms against %.2f ms -> %s\n", trial, index_ms, best, keep_new ? "kept" : "dropped");
-                    if (keep_new) best = index_ms;
-                } catch (...) { (void)hipGetLastError(); keep_new = false; }
-                vg_dev_unpark(!keep_new);
-                if (vg_alloc_wait_ms() - w0 > 500.0) break;          // (memory the driver still has to wipe: a trial costs seconds here)
-            }
-        }
-    } else {
-        // partial (a, b, count) records of every sub-shard stay in HBM and are summed ONCE there: sort on (a, b), reduce
-        // by key, threshold on the sum
-        dbuf<vg_pair_count> d_sum; unsigned long long n_sum = 0;
-        // (HASH sub-shards are sized on an expectation: a set whose repeated k-mers crowd one sub-shard beyond the 32-bit row
-        // numbers of a pass is cut finer instead of failing)
-        for (int attempt = 0, sub = plan.sub;; ++attempt) {
-            try { kmer_shared_subshards(g, k, fraction, shard, n_shards, sub, min_shared, set_sizes, d_sum, &n_sum); break; }
-            catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; d_sum.release(); }
-        }
-        acc.resize((size_t)n_sum);
-        if (n_sum) { d_sum.download(acc.data(), (size_t)n_sum, vg_stream()); VG_HIP(hipStreamSynchronize(vg_stream())); }
-    }
+    run_passes(call, plan, set_sizes, acc);
+    if (plan.one_pass) placement_trials(call);
     vg_host_mark("pass done");
-    vg_pair_count* outp = (vg_pair_count*)malloc(sizeof(vg_pair_count) * std::max<size_t>(1, acc.size()));
-    if (!outp) throw vg_error(VG_ENOMEM, "out of host memory");
-    if (!acc.empty()) memcpy(outp, acc.data(), sizeof(vg_pair_count) * acc.size());
-    *pairs = outp; *n_pairs = (int64_t)acc.size();
+    *pairs = to_caller(acc); *n_pairs = (int64_t)acc.size();
     vg_host_mark("vg_kmer_shared: return");
     VG_API_END
 }
@@ -3258,8 +3284,7 @@ static bool kmer_shared_new_masked(vg_genomes* g, int n_db, int k, uint32_t min_
     kmer_index ix1; pass_inputs none; dbuf<int> kept_b((size_t)n); kept_b.zero(s);
     ix1.n_rows_info = P;
     bucket_run R{ g, k, true, none, ix1, kept_b.p, s };
-    if (!start_bucket_run(R, A)) return false;
-    { level1_tmp t; if (!level1_count(R, t)) return false; level1_scatter(R); }
+    if (open_bucket_run(R, A, [](bucket_run&) {}) != level1::records) return false;
     const bucket_geometry& G = R.G;
     new_mask_args a{};
     a.rec = R.a_rec.p; a.short_kr = G.short_rec ? G.L2.kr : 0; a.T1s = R.T1s.p; a.off1 = R.d_off1.p;
@@ -3293,10 +3318,8 @@ static bool kmer_shared_new_masked(vg_genomes* g, int n_db, int k, uint32_t min_
             hipLaunchKernelGGL(k_new_mask<true>, dim3((unsigned)(G.nb1 * a.chunks)), dim3(PT_THREADS), 0, s, a, mask.p);
         }
         VG_HIP(hipStreamSynchronize(s));                   // (the flags' host copy and staging are done with)
-        kmer_index ix2;
-        ix2.d_dups.alloc((size_t)n); ix2.d_dups.zero(s); ix2.kept.resize((size_t)n); ix2.dups.resize((size_t)n);
-        pass_inputs in2; in2.mask = mask.p;
-        if (!index_by_buckets(g, k, 1.0, 0, 1, false, in2, ix2)) index_by_radix(g, k, 1.0, 0, 1, in2, ix2);
+        kmer_index ix2; pass_inputs in2; in2.mask = mask.p;
+        build_index(g, k, 1.0, 0, 1, in2, ix2);
         for (int i = 0; i < n_db; ++i) if (flag[(size_t)i]) sizes[(size_t)i] = (int64_t)ix2.kept[(size_t)i] - ix2.dups[(size_t)i];
     }
     for (int i = 0; i < n; ++i) set_sizes[i] = sizes[(size_t)i];
@@ -3311,8 +3334,7 @@ extern "C" int vg_kmer_shared_new(vg_genomes* g, int n_db, int k, double fractio
                                   int64_t* set_sizes, vg_pair_count** pairs, int64_t* n_pairs) {
     VG_API_BEGIN
     if (!g || !set_sizes || !pairs || !n_pairs) throw vg_error(VG_EINVAL, "vg_kmer_shared_new: null argument");
-    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
-    if (!(fraction > 0.0) || fraction > 1.0) throw vg_error(VG_EINVAL, "fraction must be in (0,1]");
+    check_kmer_args(k, fraction);
     if (n_db < 0 || n_db > g->n)
         throw vg_error(VG_EINVAL, "vg_kmer_shared_new: n_db = " + std::to_string(n_db) + " is outside 0.." + std::to_string(g->n) + " (the genomes of the set)");
     vg_host_mark("vg_kmer_shared_new: enter");
@@ -3331,27 +3353,12 @@ extern "C" int vg_kmer_shared_new(vg_genomes* g, int n_db, int k, double fractio
     if (plan.one_pass && fraction >= 1.0 && want_masked)
         try { masked_done = kmer_shared_new_masked(g, n_db, k, min_shared, set_sizes, acc); }
         catch (const vg_error& e) { if (e.code != VG_EOVERFLOW) throw; acc.clear(); }
-    if (masked_done) {
-    } else if (plan.one_pass) {
-        pass_inputs in; in.first_row = n_db;
-        kmer_shared_pass(g, k, fraction, 0, 1, min_shared, set_sizes, acc, in);
-    } else {
-        dbuf<vg_pair_count> d_sum; unsigned long long n_sum = 0;
-        for (int attempt = 0, sub = plan.sub;; ++attempt) {          // (cut finer on an overflowing sub-shard, as vg_kmer_shared does)
-            try { kmer_shared_subshards(g, k, fraction, 0, 1, sub, min_shared, set_sizes, d_sum, &n_sum, n_db); break; }
-            catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; d_sum.release(); }
-        }
-        acc.resize((size_t)n_sum);
-        if (n_sum) { d_sum.download(acc.data(), (size_t)n_sum, vg_stream()); VG_HIP(hipStreamSynchronize(vg_stream())); }
-    }
+    if (!masked_done) run_passes(shard_call{ g, k, fraction, 0, 1, min_shared, /*first_row=*/n_db }, plan, set_sizes, acc);
     // the sizes of the database genomes that no pair names are not part of the result: -1
     std::vector<char> named((size_t)n_db, 0);
     for (const vg_pair_count& pc : acc) if ((int64_t)pc.b < n_db) named[(size_t)pc.b] = 1;
     for (int i = 0; i < n_db; ++i) if (!named[(size_t)i]) set_sizes[i] = -1;
-    vg_pair_count* outp = (vg_pair_count*)malloc(sizeof(vg_pair_count) * std::max<size_t>(1, acc.size()));
-    if (!outp) throw vg_error(VG_ENOMEM, "out of host memory");
-    if (!acc.empty()) memcpy(outp, acc.data(), sizeof(vg_pair_count) * acc.size());
-    *pairs = outp; *n_pairs = (int64_t)acc.size();
+    *pairs = to_caller(acc); *n_pairs = (int64_t)acc.size();
     vg_host_mark("vg_kmer_shared_new: return");
     VG_API_END
 }
@@ -3369,14 +3376,8 @@ void vg_kmer_shared_device(vg_genomes* g, int k, double fraction, int shard, int
     if (g->n == 0) return;
     const shard_plan plan = plan_shards(g, fraction, n_shards, /*host_entry=*/false);
     if (mode_out) *mode_out = plan.range ? 1 : 2;
-    unsigned long long n = 0; int sub = plan.sub;
-    if (plan.one_pass) {
-        std::vector<vg_pair_count> none; pass_inputs in; in.xs = xs;
-        kmer_shared_pass(g, k, fraction, shard, n_shards, min_shared, set_sizes, none, in, &pairs, &n);
-    } else for (int attempt = 0;; ++attempt) {
-        try { kmer_shared_subshards(g, k, fraction, shard, n_shards, sub, min_shared, set_sizes, pairs, &n); break; }
-        catch (const vg_error& e) { if (e.code != VG_EOVERFLOW || attempt >= 3 || !plan.retry_finer) throw; ++sub; pairs.release(); }
-    }
+    unsigned long long n = 0; std::vector<vg_pair_count> none;
+    run_passes(shard_call{ g, k, fraction, shard, n_shards, min_shared, /*first_row=*/0, xs }, plan, set_sizes, none, &pairs, &n);
     if (!plan.one_pass && !pairs.p) pairs.alloc(1);
     *n_pairs = (int64_t)n;
 }
@@ -3385,7 +3386,6 @@ void vg_kmer_shared_device(vg_genomes* g, int k, double fraction, int shard, int
 static_assert(sizeof(vg_pair_count) == 12, "pair record layout");
 extern "C" void vg_set_subshards(int n) { g_force_subshards = n; }
 extern "C" void vg_set_range_scan(int mode) { g_range_scan_mode = mode == 1 ? 1 : 0; }
-
 
 // ---- vg_kmer_geometry: what bucket_geometry_for decides for a pass, asked on the host (tests, tooling)
 static void report_geometry(int k, bool dense, const kmer_args& A, int64_t P, vg_kmer_geometry_info* info) {
@@ -3399,9 +3399,7 @@ static void report_geometry(int k, bool dense, const kmer_args& A, int64_t P, vg
 extern "C" int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info) {
     VG_API_BEGIN
     if (!g || !info) throw vg_error(VG_EINVAL, "vg_kmer_geometry: null argument");
-    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
-    if (n_shards < 1 || shard < 0 || shard >= n_shards) throw vg_error(VG_EINVAL, "bad shard");
-    if (!(fraction > 0.0) || fraction > 1.0) throw vg_error(VG_EINVAL, "fraction must be in (0,1]");
+    check_kmer_args(k, fraction, shard, n_shards);
     memset(info, 0, sizeof *info);
     const int64_t P = g->padded_total();
     info->P = P; info->n_passes = 1;
@@ -3419,7 +3417,7 @@ extern "C" int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int
 extern "C" int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geometry_info* info) {
     VG_API_BEGIN
     if (!info) throw vg_error(VG_EINVAL, "vg_kmer_geometry_at: null argument");
-    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
+    check_kmer_args(k);
     if (padded_positions < 0) throw vg_error(VG_EINVAL, "vg_kmer_geometry_at: negative number of positions");
     memset(info, 0, sizeof *info);
     info->P = padded_positions; info->n_passes = 1;
@@ -3438,12 +3436,14 @@ extern "C" int vg_rowptr_inline_lo(int64_t entries, int64_t n_genomes, uint32_t*
 extern "C" int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint64_t** out, int64_t* n_out) {
     VG_API_BEGIN
     if (!g || !out || !n_out || idx < 0 || idx >= g->n) throw vg_error(VG_EINVAL, "vg_kmer_set: bad argument");
-    if (k < 8 || k > 31) throw vg_error(VG_EINVAL, "k out of range (8..31)");
+    check_kmer_args(k, fraction);
     vg_require_device();
     int rc = vg_genomes_to_device(g); if (rc) return rc;
     hipStream_t s = vg_stream();
     sorted_index si;
-    run_extract_sort(g, k, fraction, 0, 1, pass_inputs{}, si);
+    extract_kmers(g, k, fraction, 0, 1, pass_inputs{}, si);
+    prefix_sort(si, k);
+    finish_sort(si, k);
     // host-side filter of one genome's keys out of the sorted index (test-only entry point)
     std::vector<uint64_t> keys((size_t)si.n_valid); std::vector<uint32_t> pos((size_t)si.n_valid);
     if (si.n_valid) { si.keys.download(keys.data(), keys.size(), s); si.pos.download(pos.data(), pos.size(), s); }
@@ -3468,10 +3468,7 @@ extern "C" int vg_kmer_set(vg_genomes* g, int idx, int k, double fraction, uint6
         }
     std::sort(mine.begin(), mine.end());
     mine.erase(std::unique(mine.begin(), mine.end()), mine.end());
-    uint64_t* o = (uint64_t*)malloc(sizeof(uint64_t) * std::max<size_t>(1, mine.size()));
-    if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
-    if (!mine.empty()) memcpy(o, mine.data(), sizeof(uint64_t) * mine.size());
-    *out = o; *n_out = (int64_t)mine.size();
+    *out = to_caller(mine); *n_out = (int64_t)mine.size();
     VG_API_END
 }
 
