@@ -182,6 +182,35 @@ def test_subshards(s8, ref25):
     assert got == ref25[1]
 
 
+EXTRACTED = {'kmer_count', 'kmer_emit', 'kmer_emit_recompute', 'kmer_extract', 'kmer_multi_mask'}      # scopes of the compact and HASH sources
+
+
+@pytest.mark.parametrize('n_shards', [2, 8])
+def test_range_scatter_half_tiles_and_64k_tiles(s8, ref25, n_shards):
+    """The two routes of the RANGE level-1 scatter that three shards do not take.  S8 is the smallest set that has them: 32 768-position
+    tiles need super-tiles of four tiles (P >= 2^26), the 65 536-position tile super-tiles of eight (P >= 2^27, S8) and a shard of a
+    sixth of the digits or less.
+
+    Eight shards: every pass is the 65 536-position kernel (accepted with more than one shard means RANGE; with 32 768-position
+    tiles, B1 = 11 and super-tiles of eight tiles a shard of an eighth of the digits takes two tiles at a time).  Two shards: the 32 768-position kernel, whose list holds 16 384 kept
+    k-mers, so a tile that keeps more is taken as two halves.  A genome of S8 occupies 40 960 positions, so every fifth tile lies
+    inside one genome and has 32 743 valid positions (one N costs 25); a shard keeps each with probability 1/2 -- 16 371 kept on
+    average, standard deviation 90 -- and 0.44 of these 825 tiles exceed the list in either shard.  The set is seeded: the tiles that
+    do are the same in every run."""
+    sizes, pairs = np.zeros(s8.n, dtype=np.int64), {}
+    for shard in range(n_shards):
+        g = s8.gs.kmer_geometry(k=25, shard=shard, n_shards=n_shards)
+        assert (g['accepted'], g['n_passes'], g['levels'], g['tile32k'], g['short_rec'], g['st_tiles'], g['B1']) == (1, 1, 2, 1, 1, 8, 11)
+        part_sizes, part, scopes = _profiled(lambda: s8.gs.kmer_shared(k=25, shard=shard, n_shards=n_shards))
+        assert {'kmer_partition', 'kmer_partition2', 'bucket_sort_runs'} <= scopes
+        assert not (scopes & EXTRACTED) and not any('radix' in s for s in scopes), scopes      # dense source cut by digit range: RANGE
+        sizes += np.array(part_sizes)
+        for key, v in part.items():
+            pairs[key] = pairs.get(key, 0) + v
+    assert [int(x) for x in sizes] == ref25[0]
+    assert pairs == ref25[1]
+
+
 # ---------------------------------------------------------------- 3. new genomes against a database
 def _check_new(big, ref, n_db, min_shared=1, paths=(1, 2)):
     """kmer_shared_new(n_db) under every route of `paths` against the restricted oracle result; the profile says which route ran

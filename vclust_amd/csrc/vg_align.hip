@@ -420,8 +420,7 @@ constexpr int LDS_TAB = 16384;      // bucket table: anchors use B <= 14 bits, s
 constexpr int LDS_STAGE = 22016;    // staged entries per window (tab + stage + scan scratch fill the 160 KiB of a CU)
 constexpr int TOP_BITS = 9;         // big references: entries are first dealt into 2^TOP_BITS bins
 constexpr int BIG_RR = 131072;      // RR symbols from which the linear (binned) build is used
-// workgroup barrier that waits for this wave's LDS traffic only: global stores stay in flight
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (barriers below are lds_sync() of vg_common.h: they wait for LDS traffic only, global stores stay in flight)
 
 // inclusive scan over the 64 lanes of a wave with DPP adds (row shifts, then the two row broadcasts): six
 // dependent VALU instructions instead of six LDS-crossbar round trips

@@ -103,6 +103,12 @@ inline unsigned bit_width(uint64_t x, unsigned from) {
     while (b < 64 && (x >> b)) ++b;
     return b;
 }
+#if defined(__HIPCC__) || defined(__HIP__)
+// workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the wave's global
+// stores (s_waitcnt vmcnt(0)), which serialises "store the tile" with "prepare the next one"; the kernels that use
+// it order nothing but LDS contents between their phases, so their stores stay in flight across the barrier.
+__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+#endif
 
 // ---------------------------------------------------------------- profiling (HIP events on vg_stream)
 struct vg_prof_scope {

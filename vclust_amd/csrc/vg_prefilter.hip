@@ -836,6 +836,27 @@ k_spgemm_dense(const uint32_t* __restrict__ rowinfo, const uint32_t* __restrict_
 //                                    gen[] and row pointers; 1 536-entry buckets, 6 144 on a second attempt
 // No global atomics, no host round trip between the levels, deterministic output.  A bucket that does not fit the
 // LDS (a k-mer present many hundreds of times) or an input too small sends the call to the general path.
+//
+// The partition kernels are variations on one tile loop -- load the cursors, zero the tile histogram, rank with LDS
+// atomics, scan the histogram, place, store, advance the cursors -- and every step they share is ONE function:
+//   bins_zero                           every histogram but the tile histogram of k_part_scatter2_narrow
+//   cursors_load, cursors_advance,
+//   tile_bin_starts<MAXBINS>            k_part_scatter, _dense, _range
+//   lvl1_bin / lvl1_bin_of_key          the level-1 bin rule on the top word (k_part_count, k_part_scatter, _dense, _range at
+//                                       output) and on the 64-bit key (_dense, _range when ranking)
+//   lvl2_bin                            k_part_scatter<., 2>, k_part_scatter2_narrow<false>
+//   short_rec_pack                      the SHORT record, written by _dense and _range ...
+//   short_rec_bin2 / _key32 / _low      ... and read by k_part_scatter2_narrow<true> (k_part_count2<true>: _bin2_shift; k_new_mask: _key, _low)
+//   short_group_word / _pos / _base     the 2^25-position groups of SHORT records: _dense, _range, lvl2_groups, k_part_scatter2_narrow<true>
+//   row_in_word, row_of_lds             row number of a kept position of a RANGE pass: k_part_scatter (the four positions of
+//                                       a global word), _dense (on the tile's LDS copies of the words)
+//   tile_words_fetch / _stage<NW>       a tile's words one tile ahead, registers -> LDS: _dense (planes, masks), _range (planes)
+//   fetch_tile / decode_tile<SRC>       the 8 192-element tile: k_part_count, k_slice_scan, k_part_scatter
+// Not shared because they are not the same step: the (mask, row base) copies of a tile (_dense: one word per thread,
+// guarded by S.wbase; _range: one more row base, which bounds the sub-tiles) and k_slice_scan's digit (no first bucket).
+// Spelled out where the call compiles to other code than the loop it replaces and the time moved with it (DESIGN.md
+// section 4): the genome prefetch and the kept-per-genome count in k_part_count and k_slice_scan; the bin of
+// k_part_count2; the cursor, zero and scan loops of k_part_scatter2_narrow.
 constexpr int PT_THREADS = 1024;
 constexpr int PT_TILE = 8192;            // elements staged per trip: 96 KiB of LDS + bins
 constexpr int PT_PER = PT_TILE / PT_THREADS;
@@ -855,9 +876,13 @@ struct part_src {                        // where the elements of a partition le
     int bin_lo;
     const unsigned long long* wmask; const uint32_t* wbase;
 };
-// row number of padded position p (a kept one) in a RANGE pass
-__device__ __forceinline__ uint32_t row_of(const unsigned long long* __restrict__ wmask, const uint32_t* __restrict__ wbase, int64_t p) {
-    return wbase[p >> 6] + (uint32_t)__popcll(wmask[p >> 6] & ((1ULL << (p & 63)) - 1ULL));
+// row number of a kept position in a RANGE pass: the rows before its 64-position word + the kept positions below its bit
+__device__ __forceinline__ uint32_t row_in_word(unsigned long long mask, uint32_t base, int64_t bit) {
+    return base + (uint32_t)__popcll(mask & ((1ULL << bit) - 1ULL));
+}
+// ... of local position lp of a tile, read off the tile's LDS copies of the words
+__device__ __forceinline__ uint32_t row_of_lds(const unsigned long long* s_wm, const uint32_t* s_wb, uint32_t lp) {
+    return row_in_word(s_wm[lp >> 6], s_wb[lp >> 6], lp & 63u);
 }
 enum { SRC_DENSE = 0, SRC_ARRAYS = 1, SRC_PLANES = 2 };
 
@@ -866,11 +891,6 @@ __device__ __forceinline__ void key_words(uint64_t key, int k2, uint32_t* w0, ui
     const uint64_t t = key << (64 - k2);
     *w0 = (uint32_t)(t >> 32); *w1 = (uint32_t)t;
 }
-
-// workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the wave's global
-// stores (s_waitcnt vmcnt(0)), which serialises "store the tile" with "prepare the next one"; the kernels below
-// order nothing but LDS contents between their phases, so their stores stay in flight across the barrier.
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // exclusive prefix sum over the 1 024 threads of a workgroup (scratch: 16 words of LDS)
 __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* s_wave, uint32_t* total) {
@@ -888,40 +908,42 @@ __device__ __forceinline__ uint32_t block_scan_1024(uint32_t v, uint32_t* s_wave
     return base + x - v;
 }
 
-// the PT_PER elements of thread t in a tile starting at source slot t0: slot = t0 + j * 1024 + t (planes,
-// arrays) or the four consecutive positions 4 * (...) (dense: one sequence window serves four k-mers)
-template <int SRC>
-__device__ __forceinline__ void load_tile(const part_src& S, int64_t t0, int64_t t_end, uint32_t w0[PT_PER], uint32_t w1[PT_PER],
-                                          uint32_t pay[PT_PER], bool ok[PT_PER], uint32_t* genome4 /* dense: genome of each group of 4 */) {
-    if (SRC == SRC_DENSE) {
+// ---- the steps of the tile loop, one definition each (who calls what: the table in the section header)
+// bin of a key.  Level 1: its top B1 bits, counted from the first bucket of the pass -- on the key's top word and, the
+// same rule, on the 64-bit key of k2 bits.  Level 2: the next B2 bits of the top word.
+__device__ __forceinline__ uint32_t lvl1_bin(uint32_t w0, int B1, int bin_lo) { return B1 ? (w0 >> (32 - B1)) - (uint32_t)bin_lo : 0u; }
+__device__ __forceinline__ uint32_t lvl1_bin_of_key(uint64_t key, int k2, int B1, int bin_lo) { return B1 ? (uint32_t)(key >> (k2 - B1)) - (uint32_t)bin_lo : 0u; }
+__device__ __forceinline__ uint32_t lvl2_bin(uint32_t w0, int B1, int B2, int nb2) { return (w0 >> (32 - B1 - B2)) & (uint32_t)(nb2 - 1); }
+// a table or tile histogram cleared; the cursors of a unit loaded from its row of write offsets; moved past a tile
+__device__ __forceinline__ void bins_zero(uint32_t* hist, int nbins) { for (int b = threadIdx.x; b < nbins; b += PT_THREADS) hist[b] = 0; }
+__device__ __forceinline__ void cursors_load(uint32_t* cursor, const uint32_t* __restrict__ row, int nbins) { for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = row[b]; }
+__device__ __forceinline__ void cursors_advance(uint32_t* cursor, const uint32_t* thist, int nbins) { for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] += thist[b]; }
+// exclusive scan of the tile histogram: tstart[b] = tile slots in front of bin b (nbins <= MAXBINS: MAXBINS / 1 024 bins per thread)
+template <int MAXBINS>
+__device__ __forceinline__ void tile_bin_starts(const uint32_t* thist, uint32_t* tstart, int nbins, uint32_t* s_wave) {
+    constexpr int BPT = MAXBINS / PT_THREADS;
+    uint32_t c[BPT], tot = 0;
 #pragma unroll
-        for (int q = 0; q < PT_PER / 4; ++q) {
-            const int64_t p0 = t0 + ((int64_t)q * PT_THREADS + threadIdx.x) * 4;
-            uint64_t kk[4] = {SENT, SENT, SENT, SENT}; uint32_t g = 0;
-            if (p0 < t_end) kmers4(S.A, p0, kk, &g);
-            genome4[q] = g;
+    for (int v = 0; v < BPT; ++v) { const int b = BPT * (int)threadIdx.x + v; c[v] = b < nbins ? thist[b] : 0u; tot += c[v]; }
+    uint32_t run = block_scan_1024(tot, s_wave, nullptr);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ok[4 * q + j] = kk[j] != SENT;
-                key_words(kk[j], S.k2, &w0[4 * q + j], &w1[4 * q + j]);
-                pay[4 * q + j] = (uint32_t)(p0 + j);
-            }
-        }
-    } else {
+    for (int v = 0; v < BPT; ++v) { const int b = BPT * (int)threadIdx.x + v; if (b < nbins) tstart[b] = run; run += c[v]; }
+}
+// NW words of a tile one tile ahead: from src[w0 ..) into registers (`fill` past the tile's NW words or the n_src the
+// array holds), and from the registers into the LDS once the tile is the current one
+constexpr int pf_words(int nw) { return (nw + PT_THREADS - 1) / PT_THREADS; }      // registers per thread that hold nw words
+template <int NW>
+__device__ __forceinline__ void tile_words_fetch(uint32_t (&pf)[pf_words(NW)], const uint32_t* __restrict__ src, int64_t w0, int64_t n_src, uint32_t fill) {
 #pragma unroll
-        for (int j = 0; j < PT_PER; ++j) {
-            const int64_t i = t0 + (int64_t)j * PT_THREADS + threadIdx.x;
-            ok[j] = i < t_end;
-            w0[j] = 0; w1[j] = 0; pay[j] = 0;
-            if (ok[j]) {
-                if (SRC == SRC_ARRAYS) { key_words(S.keys[i], S.k2, &w0[j], &w1[j]); pay[j] = S.pos ? S.pos[i] : (uint32_t)i; }
-                else { const uint32_t* r = S.rec + 3 * i; w0[j] = r[0]; w1[j] = r[1]; pay[j] = r[2]; }
-            }
-        }
-    }
+    for (int v = 0; v < pf_words(NW); ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; const int64_t w = w0 + i; pf[v] = (i < NW && w < n_src) ? src[w] : fill; }
+}
+template <int NW>
+__device__ __forceinline__ void tile_words_stage(uint32_t* s_dst, const uint32_t (&pf)[pf_words(NW)]) {
+#pragma unroll
+    for (int v = 0; v < pf_words(NW); ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; if (i < NW) s_dst[i] = pf[v]; }
 }
 
-// The same tile in two steps, for the scatter kernel: fetch_tile only issues the loads (the raw words of the
+// A tile of 8 192 elements in two steps: fetch_tile only issues the loads (the raw words of the
 // NEXT tile travel while the current one is sorted in the LDS), decode_tile turns them into (w0, w1, pay).
 constexpr int PT_RAW = 3 * PT_PER;
 template <int SRC>
@@ -991,7 +1013,7 @@ k_part_count(part_src S, int B1, int nb /* level-1 buckets of this pass */, int 
     __shared__ uint32_t hist[PT_MAXBINS];
     const int lane = threadIdx.x & 63;
     for (int64_t st = blockIdx.x; st < n_st; st += gridDim.x) {
-        for (int b = threadIdx.x; b < nb; b += PT_THREADS) hist[b] = 0;
+        bins_zero(hist, nb);
         __syncthreads();
         const int64_t s0 = st * st_tiles * PT_TILE, s1 = min(S.n, s0 + (int64_t)st_tiles * PT_TILE);
         uint32_t raw[PT_RAW], gq[PT_PER / 4];
@@ -1012,7 +1034,7 @@ k_part_count(part_src S, int B1, int nb /* level-1 buckets of this pass */, int 
             for (int q = 0; q < PT_PER / 4; ++q) g4[q] = gq[q];
             if (t0 + PT_TILE < s1) { fetch_tile<SRC>(S, t0 + PT_TILE, s1, raw); fetch_genomes(t0 + PT_TILE); }
 #pragma unroll
-            for (int j = 0; j < PT_PER; ++j) if (ok[j]) atomicAdd(&hist[B1 ? (w0[j] >> (32 - B1)) - (uint32_t)S.bin_lo : 0u], 1u);
+            for (int j = 0; j < PT_PER; ++j) if (ok[j]) atomicAdd(&hist[lvl1_bin(w0[j], B1, S.bin_lo)], 1u);
             if (SRC == SRC_DENSE && wave_mask) {
                 // the wave's 256 consecutive positions of every group q = four 64-position words: a lane's four flags are a
                 // nibble, eight lanes OR their nibbles into a 32-bit half-word (three cross-lane steps), two halves make a word
@@ -1086,7 +1108,7 @@ k_slice_scan(part_src S, slice_plan X, int st_tiles, int* __restrict__ kept_per_
     const int64_t W_total = S.n >> 6;
     for (int i = threadIdx.x; i < 16 * (PT_PER / 4) * (int)world * 8; i += PT_THREADS) s_m[i] = 0;
     for (int64_t st = X.st_lo + blockIdx.x; st < X.st_hi; st += gridDim.x) {
-        for (int b = threadIdx.x; b < (1 << DIG_BITS); b += PT_THREADS) hist[b] = 0;
+        bins_zero(hist, 1 << DIG_BITS);
         __syncthreads();
         const int64_t s0 = st * st_tiles * PT_TILE, s1 = min(S.n, s0 + (int64_t)st_tiles * PT_TILE);
         uint32_t raw[PT_RAW], gq[PT_PER / 4];
@@ -1164,10 +1186,24 @@ __global__ void k_mask_popc(const unsigned long long* __restrict__ m, int64_t n,
 // (b1 * n_u + U) * 2^B2 + b2 -- a unit's counters are one contiguous row; k_scan_units makes them write offsets.
 //
 // SHORT records (dense source, 2k - B1 + 25 <= 64): level 1 writes 8 bytes instead of 12,
-//   rec = (key bits below the level-1 digit) << 25 | (position mod 2^25);
+//   rec = (the kr = 2k - B1 key bits below the level-1 digit) << 25 | (position, or row number of a RANGE pass, inside its group);
 // the missing high position bits are those of the 2^25-position group the record came from, and a unit spans at
-// most four groups whose boundaries are again entries of the level-1 table.
+// most four groups whose boundaries are again entries of the level-1 table.  The format is these functions:
 constexpr int SR_POS_BITS = 25;
+__device__ __forceinline__ uint64_t short_rec_pack(uint64_t key, int kr, uint32_t low) {
+    return ((key & ((1ULL << kr) - 1)) << SR_POS_BITS) | (uint64_t)(low & ((1u << SR_POS_BITS) - 1u));
+}
+__device__ __forceinline__ uint32_t short_rec_low(uint64_t r) { return (uint32_t)r & ((1u << SR_POS_BITS) - 1u); }
+__device__ __forceinline__ uint64_t short_rec_key(uint64_t r) { return r >> SR_POS_BITS; }
+// the level-2 bin = the top B2 of its kr key bits; all key bits below the level-2 digit, top aligned in a word (kr - B2 <= 32)
+__device__ __forceinline__ int short_rec_bin2_shift(int kr, int B2) { return SR_POS_BITS + kr - B2; }
+__device__ __forceinline__ uint32_t short_rec_bin2(uint64_t r, int kr, int B2, int nb2) { return (uint32_t)(r >> short_rec_bin2_shift(kr, B2)) & (uint32_t)(nb2 - 1); }
+__device__ __forceinline__ uint32_t short_rec_key32(uint64_t r, int kr, int B2) { return (uint32_t)short_rec_key(r) << (32 - (kr - B2)); }
+// position groups: the first 64-position word of the group of position p, words per group, first position of a unit's group gsel
+__device__ __forceinline__ int64_t short_group_word(int64_t p) { return (p >> SR_POS_BITS) << (SR_POS_BITS - 6); }
+constexpr int64_t SR_GROUP_WORDS = 1LL << (SR_POS_BITS - 6);
+__device__ __forceinline__ uint32_t short_group_pos(uint32_t gsel) { return gsel << SR_POS_BITS; }
+__device__ __forceinline__ uint32_t short_group_base(uint64_t p) { return (uint32_t)(p >> SR_POS_BITS << SR_POS_BITS); }      // first position of the group of position p
 struct lvl2_tab {
     const uint32_t* T1s; int64_t n_st;      // level-1 write offsets [super-tile][bucket] (k_scan_columns)
     const uint32_t* off1; int nb1;          // start of every level-1 bucket (+ the total)
@@ -1186,7 +1222,7 @@ __device__ __forceinline__ void lvl2_unit(const lvl2_tab& L, int64_t u, uint32_t
 // SHORT: position base of the unit's first group and the record indices at which its 2nd..4th group start
 __device__ __forceinline__ void lvl2_groups(const lvl2_tab& L, uint32_t b1, uint32_t U, int64_t r1, uint32_t* base, uint32_t gb[3]) {
     const int64_t st0 = (int64_t)U * L.u_st;
-    *base = (uint32_t)(((uint64_t)st0 << L.st_shift) >> SR_POS_BITS << SR_POS_BITS);
+    *base = short_group_base((uint64_t)st0 << L.st_shift);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int64_t stg = st0 + (int64_t)(j + 1) * L.g_st;
@@ -1201,13 +1237,13 @@ k_part_count2(const uint32_t* __restrict__ rec, int B1, int B2, int64_t n_units,
     __shared__ uint32_t hist[PT_MAXBINS];
     const int nb2 = 1 << B2;
     for (int64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
-        for (int b = threadIdx.x; b < nb2; b += PT_THREADS) hist[b] = 0;
+        bins_zero(hist, nb2);
         __syncthreads();
         uint32_t b1, U; int64_t s0, s1;
         lvl2_unit(L, u, &b1, &U, &s0, &s1);
         if (SHORT) {
             // 8-byte records, two per 16-byte load (from an even record index), four loads per thread and trip
-            const int sh = SR_POS_BITS + L.kr - B2;
+            const int sh = short_rec_bin2_shift(L.kr, B2);      // short_rec_bin2 with the shift formed once: as calls the kernel is scheduled differently
             for (int64_t i0 = (s0 & ~(int64_t)1) + 2 * (int64_t)threadIdx.x; i0 < s1; i0 += 8 * PT_THREADS) {
                 uint4 r[4];
 #pragma unroll
@@ -1258,10 +1294,7 @@ k_part_scatter(part_src S, int B1, int B2, int unit_tiles, int64_t n_units, cons
         uint32_t b1 = 0, cl = 0;
         if (LEVEL == 2) lvl2_unit(L, u, &b1, &cl, &s0, &s1);
         lds_sync();
-        for (int b = threadIdx.x; b < nbins; b += PT_THREADS) {
-            const uint32_t off = LEVEL == 1 ? Ts[u * nbins + b] : Ts[((uint64_t)b1 * L.n_u + cl) * nbins + b];
-            cursor[b] = off;
-        }
+        cursors_load(cursor, Ts + (LEVEL == 1 ? (uint64_t)u : (uint64_t)b1 * L.n_u + cl) * nbins, nbins);
         // The raw words of tile t + 1 are requested while tile t is sorted; they (and, the memory pipeline being
         // in order, the stores of tile t - 1) must have landed before tile t's stores are issued -- so the stores
         // of one tile drain while the next is ranked and staged, instead of being waited for at its first load.
@@ -1270,7 +1303,7 @@ k_part_scatter(part_src S, int B1, int B2, int unit_tiles, int64_t n_units, cons
         for (int i = 0; i < PT_RAW; ++i) raw[i] = 0;
         fetch_tile<SRC>(S, s0, s1, raw);
         for (int64_t t0 = s0; t0 < s1; t0 += PT_TILE) {
-            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) thist[b] = 0;
+            bins_zero(thist, nbins);
             lds_sync();
             uint32_t w0[PT_PER], w1[PT_PER], pay[PT_PER], bin[PT_PER], rk[PT_PER]; bool ok[PT_PER];
             decode_tile<SRC>(S, t0, s1, raw, w0, w1, pay, ok);
@@ -1282,7 +1315,7 @@ k_part_scatter(part_src S, int B1, int B2, int unit_tiles, int64_t n_units, cons
                     if (p0 < s1) {
                         const unsigned long long m = S.wmask[p0 >> 6]; const uint32_t rb = S.wbase[p0 >> 6];
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) pay[4 * q + j] = rb + (uint32_t)__popcll(m & ((1ULL << ((p0 & 63) + j)) - 1ULL));
+                        for (int j = 0; j < 4; ++j) pay[4 * q + j] = row_in_word(m, rb, (p0 & 63) + j);
                     }
                 }
             }
@@ -1291,21 +1324,12 @@ k_part_scatter(part_src S, int B1, int B2, int unit_tiles, int64_t n_units, cons
             for (int j = 0; j < PT_PER; ++j) {
                 bin[j] = 0; rk[j] = 0;
                 if (ok[j]) {
-                    bin[j] = LEVEL == 1 ? (B1 ? (w0[j] >> (32 - B1)) - (uint32_t)S.bin_lo : 0u) : ((w0[j] >> (32 - B1 - B2)) & (uint32_t)(nbins - 1));
+                    bin[j] = LEVEL == 1 ? lvl1_bin(w0[j], B1, S.bin_lo) : lvl2_bin(w0[j], B1, B2, nbins);
                     rk[j] = atomicAdd(&thist[bin[j]], 1u);
                 }
             }
             lds_sync();
-            // exclusive scan of the tile histogram (nbins <= 4 096: four bins per thread)
-            {
-                constexpr int BPT = PT_MAXBINS / PT_THREADS;
-                uint32_t c[BPT], tot = 0;
-#pragma unroll
-                for (int u = 0; u < BPT; ++u) { const int b = BPT * (int)threadIdx.x + u; c[u] = b < nbins ? thist[b] : 0u; tot += c[u]; }
-                uint32_t run = block_scan_1024(tot, s_wave, nullptr);
-#pragma unroll
-                for (int u = 0; u < BPT; ++u) { const int b = BPT * (int)threadIdx.x + u; if (b < nbins) tstart[b] = run; run += c[u]; }
-            }
+            tile_bin_starts<PT_MAXBINS>(thist, tstart, nbins, s_wave);
             lds_sync();
 #pragma unroll
             for (int j = 0; j < PT_PER; ++j) if (ok[j]) {
@@ -1320,7 +1344,7 @@ k_part_scatter(part_src S, int B1, int B2, int unit_tiles, int64_t n_units, cons
             // hold consecutive slots, so a wave writes each bin's segment of the tile as one contiguous run
             for (uint32_t slot = threadIdx.x; slot < n_tile; slot += PT_THREADS) {
                 const uint32_t w = s_w0[slot];
-                const uint32_t b = LEVEL == 1 ? (B1 ? (w >> (32 - B1)) - (uint32_t)S.bin_lo : 0u) : ((w >> (32 - B1 - B2)) & (uint32_t)(nbins - 1));
+                const uint32_t b = LEVEL == 1 ? lvl1_bin(w, B1, S.bin_lo) : lvl2_bin(w, B1, B2, nbins);
                 const uint64_t dst = (uint64_t)cursor[b] + (slot - tstart[b]);
                 if (narrow_shift >= 0) {
                     // the bucket fixes the top narrow_shift key bits and at most 32 remain: one word carries them
@@ -1332,7 +1356,7 @@ k_part_scatter(part_src S, int B1, int B2, int unit_tiles, int64_t n_units, cons
                 }
             }
             lds_sync();
-            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] += thist[b];
+            cursors_advance(cursor, thist, nbins);
             lds_sync();
         }
     }
@@ -1369,24 +1393,20 @@ k_part_scatter_dense(part_src S, int B1, int nbins /* level-1 buckets of this pa
     for (int64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
         const int64_t s0 = u * unit_tiles * RT_TILE, s1 = min(S.n, s0 + (int64_t)unit_tiles * RT_TILE);
         lds_sync();
-        for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = Ts[u * nbins + b];
+        cursors_load(cursor, Ts + u * nbins, nbins);
         // the tile's packed bases and mask: three + two words per thread, requested one tile ahead (the barriers of
         // this kernel wait for LDS traffic only, so the loads travel while the current tile is sorted)
-        constexpr int NPK = (RT_TILE / 16 + 4 + PT_THREADS - 1) / PT_THREADS, NMK = (RT_TILE / 32 + 2 + PT_THREADS - 1) / PT_THREADS;
-        uint32_t pf_pk[NPK], pf_mk[NMK];
+        constexpr int NPK = RT_TILE / 16 + 4, NMK = RT_TILE / 32 + 2;      // (a k-mer window reaches into the next words)
+        uint32_t pf_pk[pf_words(NPK)], pf_mk[pf_words(NMK)];
         auto fetch_bases = [&](int64_t t0) {
-#pragma unroll
-            for (int v = 0; v < NPK; ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; const int64_t w = (t0 >> 4) + i; pf_pk[v] = (i < RT_TILE / 16 + 4 && w < n_pk) ? S.A.planes[w] : 0u; }
-#pragma unroll
-            for (int v = 0; v < NMK; ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; const int64_t w = (t0 >> 5) + i; pf_mk[v] = (i < RT_TILE / 32 + 2 && w < n_mk) ? S.A.nmask[w] : 0xffffffffu; }
+            tile_words_fetch<NPK>(pf_pk, S.A.planes, t0 >> 4, n_pk, 0u);
+            tile_words_fetch<NMK>(pf_mk, S.A.nmask, t0 >> 5, n_mk, 0xffffffffu);
         };
         fetch_bases(s0);
         for (int64_t t0 = s0; t0 < s1; t0 += RT_TILE) {
-#pragma unroll
-            for (int v = 0; v < NPK; ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; if (i < RT_TILE / 16 + 4) s_pk[i] = pf_pk[v]; }
-#pragma unroll
-            for (int v = 0; v < NMK; ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; if (i < RT_TILE / 32 + 2) s_mk[i] = pf_mk[v]; }
-            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) thist[b] = 0;
+            tile_words_stage<NPK>(s_pk, pf_pk);
+            tile_words_stage<NMK>(s_mk, pf_mk);
+            bins_zero(thist, nbins);
             uint32_t grp_row0 = 0;                                // RANGE: row number of the first kept k-mer of the tile's 2^25-position group
             if (S.wbase) {
                 const int64_t W = S.n >> 6;
@@ -1394,7 +1414,7 @@ k_part_scatter_dense(part_src S, int B1, int nbins /* level-1 buckets of this pa
                     const int64_t w = (t0 >> 6) + threadIdx.x;
                     s_wm[threadIdx.x] = w < W ? S.wmask[w] : 0ULL; s_wb[threadIdx.x] = S.wbase[w < W ? w : W];
                 }
-                grp_row0 = S.wbase[(t0 >> SR_POS_BITS) << (SR_POS_BITS - 6)];
+                grp_row0 = S.wbase[short_group_word(t0)];
             }
             lds_sync();
             if (t0 + RT_TILE < s1) fetch_bases(t0 + RT_TILE);
@@ -1411,21 +1431,13 @@ k_part_scatter_dense(part_src S, int B1, int nbins /* level-1 buckets of this pa
                 for (int j = 0; j < 4; ++j) {
                     br[4 * q + j] = 0xffffffffu;
                     if (kk[j] != SENT) {
-                        const uint32_t bin = B1 ? (uint32_t)(kk[j] >> (S.k2 - B1)) - (uint32_t)S.bin_lo : 0u;
+                        const uint32_t bin = lvl1_bin_of_key(kk[j], S.k2, B1, S.bin_lo);
                         br[4 * q + j] = bin | (atomicAdd(&thist[bin], 1u) << 12);
                     }
                 }
             }
             lds_sync();
-            {
-                constexpr int BPT = PT_MAXBINS / PT_THREADS;
-                uint32_t c[BPT], tot = 0;
-#pragma unroll
-                for (int v = 0; v < BPT; ++v) { const int b = BPT * (int)threadIdx.x + v; c[v] = b < nbins ? thist[b] : 0u; tot += c[v]; }
-                uint32_t run = block_scan_1024(tot, s_wave, nullptr);
-#pragma unroll
-                for (int v = 0; v < BPT; ++v) { const int b = BPT * (int)threadIdx.x + v; if (b < nbins) tstart[b] = run; run += c[v]; }
-            }
+            tile_bin_starts<PT_MAXBINS>(thist, tstart, nbins, s_wave);
             lds_sync();
 #pragma unroll
             for (int q = 0; q < RT_PER / 4; ++q) {
@@ -1446,18 +1458,18 @@ k_part_scatter_dense(part_src S, int B1, int nbins /* level-1 buckets of this pa
                 uint32_t low = v[2];                              // SHORT: the payload inside its 2^25-position group
                 if (S.wbase) {
                     // RANGE shard: row number instead of position; inside the group it is counted from the group's first row
-                    v[2] = s_wb[lp >> 6] + (uint32_t)__popcll(s_wm[lp >> 6] & ((1ULL << (lp & 63u)) - 1ULL));
+                    v[2] = row_of_lds(s_wm, s_wb, lp);
                     low = v[2] - grp_row0;
                 }
-                const uint32_t b = B1 ? (v[0] >> (32 - B1)) - (uint32_t)S.bin_lo : 0u;
+                const uint32_t b = lvl1_bin(v[0], B1, S.bin_lo);
                 const uint64_t dst = (uint64_t)cursor[b] + (slot - tstart[b]);
                 if (short_kr > 0) {
-                    const uint64_t r = ((key & ((1ULL << short_kr) - 1)) << SR_POS_BITS) | (uint64_t)(low & ((1u << SR_POS_BITS) - 1u));
+                    const uint64_t r = short_rec_pack(key, short_kr, low);
                     __builtin_memcpy(o_rec + 2 * dst, &r, 8);
                 } else __builtin_memcpy(o_rec + 3 * dst, v, 12);
             }
             lds_sync();
-            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] += thist[b];
+            cursors_advance(cursor, thist, nbins);
             lds_sync();
         }
     }
@@ -1491,25 +1503,20 @@ k_part_scatter_range(part_src S, int B1, int nbins /* <= 2048 */, int unit_tiles
     for (int64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
         const int64_t s0 = u * unit_tiles * TT, s1 = min(S.n, s0 + (int64_t)unit_tiles * TT);
         lds_sync();
-        for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = Ts[u * nbins + b];
-        constexpr int NPK = (TT / 16 + 4 + PT_THREADS - 1) / PT_THREADS;
-        uint32_t pf_pk[NPK];
-        auto fetch_bases = [&](int64_t t0) {
-#pragma unroll
-            for (int v = 0; v < NPK; ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; const int64_t w = (t0 >> 4) + i; pf_pk[v] = (i < TT / 16 + 4 && w < n_pk) ? S.A.planes[w] : 0u; }
-        };
-        fetch_bases(s0);
+        cursors_load(cursor, Ts + u * nbins, nbins);
+        constexpr int NPK = TT / 16 + 4;
+        uint32_t pf_pk[pf_words(NPK)];
+        tile_words_fetch<NPK>(pf_pk, S.A.planes, s0 >> 4, n_pk, 0u);
         for (int64_t t0 = s0; t0 < s1; t0 += TT) {
-#pragma unroll
-            for (int v = 0; v < NPK; ++v) { const int i = v * PT_THREADS + (int)threadIdx.x; if (i < TT / 16 + 4) s_pk[i] = pf_pk[v]; }
+            tile_words_stage<NPK>(s_pk, pf_pk);
             for (int i = (int)threadIdx.x; i <= TT / 64; i += PT_THREADS) {
                 const int64_t w = (t0 >> 6) + i;
                 if (i < TT / 64) s_wm[i] = w < W ? S.wmask[w] : 0ULL;
                 s_wb[i] = S.wbase[w < W ? w : W];
             }
-            const uint32_t grp_row0 = S.wbase[(t0 >> SR_POS_BITS) << (SR_POS_BITS - 6)];      // first row of the tile's 2^25-position group
+            const uint32_t grp_row0 = S.wbase[short_group_word(t0)];      // first row of the tile's 2^25-position group
             lds_sync();
-            if (t0 + TT < s1) fetch_bases(t0 + TT);
+            if (t0 + TT < s1) tile_words_fetch<NPK>(pf_pk, S.A.planes, (t0 + TT) >> 4, n_pk, 0u);
             // words per sub-tile: the whole tile if its kept k-mers fit the list, else halves, else quarters (16 384 positions always fit)
             int wn = TT / 64;
             if (s_wb[TT / 64] - s_wb[0] > (uint32_t)RG_LIST) {
@@ -1518,7 +1525,7 @@ k_part_scatter_range(part_src S, int B1, int nbins /* <= 2048 */, int unit_tiles
             }
             for (int w0 = 0; w0 < TT / 64; w0 += wn) {
                 const uint32_t row0 = s_wb[w0], n_sub = s_wb[w0 + wn] - row0;
-                for (int b = threadIdx.x; b < nbins; b += PT_THREADS) thist[b] = 0;
+                bins_zero(thist, nbins);
                 // list the kept positions: thread t takes the 32-position half-word t of the sub-tile
                 for (int hw = (int)threadIdx.x; hw < 2 * wn; hw += PT_THREADS) {
                     const int w = w0 + (hw >> 1);
@@ -1536,20 +1543,12 @@ k_part_scatter_range(part_src S, int B1, int nbins /* <= 2048 */, int unit_tiles
                     br[q] = 0xffffffffu;
                     if (i < n_sub) {
                         const uint64_t key = kmer_key_lds(S.A, s_pk, s_list[i]);
-                        const uint32_t bin = B1 ? (uint32_t)(key >> (S.k2 - B1)) - (uint32_t)S.bin_lo : 0u;
+                        const uint32_t bin = lvl1_bin_of_key(key, S.k2, B1, S.bin_lo);
                         br[q] = bin | (atomicAdd(&thist[bin], 1u) << 12);
                     }
                 }
                 lds_sync();
-                {
-                    constexpr int BPT = RG_MAXBINS / PT_THREADS;
-                    uint32_t c[BPT], tot = 0;
-#pragma unroll
-                    for (int v = 0; v < BPT; ++v) { const int b = BPT * (int)threadIdx.x + v; c[v] = b < nbins ? thist[b] : 0u; tot += c[v]; }
-                    uint32_t run = block_scan_1024(tot, s_wave, nullptr);
-#pragma unroll
-                    for (int v = 0; v < BPT; ++v) { const int b = BPT * (int)threadIdx.x + v; if (b < nbins) tstart[b] = run; run += c[v]; }
-                }
+                tile_bin_starts<RG_MAXBINS>(thist, tstart, nbins, s_wave);
                 lds_sync();
 #pragma unroll
                 for (int q = 0; q < RG_PER; ++q) {
@@ -1563,15 +1562,15 @@ k_part_scatter_range(part_src S, int B1, int nbins /* <= 2048 */, int unit_tiles
                     uint32_t v[3];
                     key_words(key, S.k2, &v[0], &v[1]);
                     v[2] = row0 + i;                              // the row number
-                    const uint32_t b = B1 ? (v[0] >> (32 - B1)) - (uint32_t)S.bin_lo : 0u;
+                    const uint32_t b = lvl1_bin(v[0], B1, S.bin_lo);
                     const uint64_t dst = (uint64_t)cursor[b] + (slot - tstart[b]);
                     if (short_kr > 0) {
-                        const uint64_t r = ((key & ((1ULL << short_kr) - 1)) << SR_POS_BITS) | (uint64_t)((v[2] - grp_row0) & ((1u << SR_POS_BITS) - 1u));
+                        const uint64_t r = short_rec_pack(key, short_kr, v[2] - grp_row0);
                         __builtin_memcpy(o_rec + 2 * dst, &r, 8);
                     } else __builtin_memcpy(o_rec + 3 * dst, v, 12);
                 }
                 lds_sync();
-                for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] += thist[b];
+                cursors_advance(cursor, thist, nbins);
                 lds_sync();
             }
         }
@@ -1602,7 +1601,7 @@ k_part_scatter2_narrow(const uint32_t* __restrict__ rec, int B1, int B2, int64_t
         if (SHORT) {
             lvl2_groups(L, b1, U, s1, &gbase, gb);
             if (L.wbase) {
-                const int64_t w0 = (int64_t)(gbase >> 6), gw = 1LL << (SR_POS_BITS - 6);
+                const int64_t w0 = (int64_t)(gbase >> 6), gw = SR_GROUP_WORDS;
                 grow0 = L.wbase[min(w0, L.W)]; grow1 = L.wbase[min(w0 + gw, L.W)]; grow2 = L.wbase[min(w0 + 2 * gw, L.W)]; grow3 = L.wbase[min(w0 + 3 * gw, L.W)];
             }
         }
@@ -1634,10 +1633,10 @@ k_part_scatter2_narrow(const uint32_t* __restrict__ rec, int B1, int B2, int64_t
                             const uint64_t r = h ? (((uint64_t)rr[p].w << 32) | rr[p].z) : (((uint64_t)rr[p].y << 32) | rr[p].x);
                             const uint32_t ui = (uint32_t)i;
                             const uint32_t gsel = (uint32_t)(ui >= gb[0]) + (uint32_t)(ui >= gb[1]) + (uint32_t)(ui >= gb[2]);
-                            key[j] = (uint32_t)(r >> SR_POS_BITS) << (32 - (L.kr - B2));
-                            const uint32_t low = (uint32_t)r & ((1u << SR_POS_BITS) - 1u);
-                            pay[j] = L.wbase ? (gsel == 0 ? grow0 : gsel == 1 ? grow1 : gsel == 2 ? grow2 : grow3) + low : gbase + (gsel << SR_POS_BITS) + low;
-                            br[j] = (uint32_t)(r >> (SR_POS_BITS + L.kr - B2)) & (uint32_t)(nbins - 1);
+                            key[j] = short_rec_key32(r, L.kr, B2);
+                            const uint32_t low = short_rec_low(r);
+                            pay[j] = L.wbase ? (gsel == 0 ? grow0 : gsel == 1 ? grow1 : gsel == 2 ? grow2 : grow3) + low : gbase + short_group_pos(gsel) + low;
+                            br[j] = short_rec_bin2(r, L.kr, B2, nbins);
                         }
                     }
                 }
@@ -1649,7 +1648,7 @@ k_part_scatter2_narrow(const uint32_t* __restrict__ rec, int B1, int B2, int64_t
                     if (i < s1) {
                         uint32_t r[3]; __builtin_memcpy(r, rec + 3 * i, 12);
                         key[j] = (uint32_t)(((((uint64_t)r[0] << 32) | r[1]) << narrow_shift) >> 32); pay[j] = r[2];
-                        br[j] = (r[0] >> (32 - B1 - B2)) & (uint32_t)(nbins - 1);
+                        br[j] = lvl2_bin(r[0], B1, B2, nbins);
                     }
                 }
             }
@@ -3226,8 +3225,8 @@ k_new_mask(new_mask_args a, unsigned long long* __restrict__ mask) {
     auto record = [&](uint32_t i, int64_t st, uint64_t* key, uint32_t* pos) {
         if (a.short_kr > 0) {
             uint64_t r; __builtin_memcpy(&r, a.rec + 2 * (size_t)i, 8);
-            *key = r >> SR_POS_BITS;
-            *pos = (uint32_t)((((uint64_t)st * (uint64_t)a.st_pos) >> SR_POS_BITS) << SR_POS_BITS) + (uint32_t)(r & ((1u << SR_POS_BITS) - 1u));
+            *key = short_rec_key(r);
+            *pos = short_group_base((uint64_t)st * (uint64_t)a.st_pos) + short_rec_low(r);
         } else {
             const uint32_t* r = a.rec + 3 * (size_t)i;
             *key = ((uint64_t)r[0] << 32) | r[1]; *pos = r[2];
