@@ -218,10 +218,11 @@ np.savez(sys.argv[1], stats=stats, regions=regions)
         assert np.array_equal(st, base[0]) and np.array_equal(rgs, base[1]), tag
 
 
-@pytest.mark.parametrize('k', [15, 30])
+@pytest.mark.parametrize('k', [15, 16, 30])
 def test_bucket_pipeline_key_widths(k):
     """The own index pipeline at the ends of the k range with two partition levels: k = 15 (30 key bits: the
-    narrow 8-byte level-2 records with few bits left) and k = 30 (60 key bits: the wide 12-byte records),
+    narrow 8-byte level-2 records with few bits left), k = 16 (the key is exactly one 32-bit word; 52 985 pairs, 9 000 of
+    them inside families, the others chance pairs) and k = 30 (60 key bits: the wide 12-byte records),
     2 000 genomes x 8 kb; sizes and counts equal the oracle's, dense and as four / eight shards (both shard sources)."""
     codes, offsets, names = synth.make_families(200, 10, length=8000, seed=23)
     gs = api.GenomeSet.from_codes(codes, offsets, names)
@@ -243,22 +244,26 @@ def test_bucket_pipeline_key_widths(k):
         assert list(tot) == list(osizes) and acc == opairs
 
 
-@pytest.mark.parametrize('world', [2, 3, 8])
-def test_sliced_scan_equals_the_replicated_scan(world):
+@pytest.mark.parametrize('k,world', [pytest.param(25, 2, id='2'), pytest.param(25, 3, id='3'), pytest.param(25, 8, id='8'),      # (the ids from before k was a parameter)
+                                     pytest.param(21, 3, id='k21-3'), pytest.param(30, 3, id='k30-3')])
+def test_sliced_scan_equals_the_replicated_scan(k, world):
     """The multi-GPU form of a RANGE shard (k_slice_scan: rank r scans 1/world of the BASES, the kept masks and level-1
     counts of every rank's k-mer range travel to it) with the peers' slices computed by this process: the pairs of every
     rank are exactly those of the replicated scan, and the ranks' partial set sizes and counts add up to the oracle's.
-    4.5 M bases: two partition levels, a last super-tile that is not full, digit ranges that do not divide 2 048 at 3."""
+    4.5 M bases: two partition levels, a last super-tile that is not full, digit ranges that do not divide 2 048 at 3.
+    k = 25 is `k_slice_scan<25>`; k = 21 and 30 read k from the arguments (`k_slice_scan<0>`)."""
     codes, offsets, names = synth.make_families(100, 5, length=9000, seed=31)
     gs = api.GenomeSet.from_codes(codes, offsets, names)
-    osizes, opairs = orc.shared_all(codes, offsets, k=25)
+    osizes, opairs = orc.shared_all(codes, offsets, k=k)
     tot = np.zeros(len(gs), dtype=np.int64); acc = {}
     for r in range(world):
-        sz0, pr0 = gs.kmer_shared(k=25, shard=r, n_shards=world)
+        g = gs.kmer_geometry(k=k, shard=r, n_shards=world)
+        assert (g['accepted'], g['n_passes'], g['levels'], g['B1']) == (1, 1, 2, 11)      # a RANGE shard cut on the level-1 digit
+        sz0, pr0 = gs.kmer_shared(k=k, shard=r, n_shards=world)
         api.set_range_scan(1)
         try:
             api.profile_enable(True); api.profile_reset()
-            sz1, pr1 = gs.kmer_shared(k=25, shard=r, n_shards=world)
+            sz1, pr1 = gs.kmer_shared(k=k, shard=r, n_shards=world)
             scopes = {e['name']: e for e in api.profile_get()}
         finally:
             api.profile_enable(False); api.set_range_scan(0)
@@ -518,6 +523,39 @@ def test_hash_subshards_from_one_scan(k, fraction, sub):
             for p in pr:
                 acc[(int(p['a']), int(p['b']))] = acc.get((int(p['a']), int(p['b'])), 0) + int(p['shared'])
         assert list(tot) == list(osizes) and acc == opairs
+    finally:
+        api.profile_enable(False); _lib.load().vg_set_subshards(0)
+
+
+def test_hash_subshards_from_one_scan_at_k25():
+    """The one-scan masks with k = 25 folded in (`k_multi_mask<25>`, what the million-contig workload runs): no fraction, so
+    only HASH passes take them, and shards are HASH only above 256 in total -- 65 outer shards of four sub-shards, 260 passes
+    (64 shards of four are RANGE; both asked of the host plan).  Sizes and counts summed over the 65 shards equal the oracle's."""
+    from vclust_amd import _lib
+    k = 25
+    codes, offsets, names = synth.make_families(60, 5, length=9000, seed=37)
+    gs = api.GenomeSet.from_codes(codes, offsets, names)
+    osizes, opairs = orc.shared_all(codes, offsets, k=k)
+    _lib.load().vg_set_subshards(4)
+    try:
+        for sh in (0, 64):
+            g = gs.kmer_geometry(k=k, shard=sh, n_shards=65)
+            assert (g['accepted'], g['n_passes']) == (-1, 4)
+        g = gs.kmer_geometry(k=k, shard=0, n_shards=64)
+        assert (g['accepted'], g['n_passes']) == (1, 4)
+        tot = np.zeros(len(gs), dtype=np.int64); acc = {}
+        for sh in range(65):
+            if sh == 0:
+                api.profile_enable(True); api.profile_reset()
+            sz, pr = gs.kmer_shared(k=k, shard=sh, n_shards=65)
+            if sh == 0:
+                scopes = {e['name']: e for e in api.profile_get()}
+                api.profile_enable(False)
+                assert scopes['kmer_multi_mask']['launches'] == 1 and 'kmer_count' not in scopes
+            tot += sz
+            for p in pr:
+                acc[(int(p['a']), int(p['b']))] = acc.get((int(p['a']), int(p['b'])), 0) + int(p['shared'])
+        assert len(opairs) > 0 and list(tot) == list(osizes) and acc == opairs
     finally:
         api.profile_enable(False); _lib.load().vg_set_subshards(0)
 
