@@ -486,6 +486,43 @@ int vg_cluster_average_order_selftest(const uint64_t* sum, const uint32_t* size_
 int vg_cluster_linkage(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
                        const char* linkage_path, const double* levels, int n_levels);
 
+/* Cluster report: cohesion and separation of a given clustering (this repository's definition; DESIGN.md section 9, "Cluster
+ * report").  The graph is the one above, every weight finite and in [0, 1] (else VG_EINVAL, before any device use) and taken as the
+ * integer u = llrint(ldexp(w, 32)) of average linkage; every figure is integer arithmetic on u.  label[i] in [0, n_clusters) is the
+ * cluster of object i -- any partition, computed by this library or not.  One record per label; a label without members has size 0,
+ * rep and nearest -1 and every other field 0. */
+typedef struct {
+    int64_t size;               /* members */
+    int64_t rep;                /* the earliest member (minimum index) */
+    uint64_t pairs;             /* size * (size - 1) / 2 */
+    uint64_t linked;            /* edges with both ends in the cluster */
+    uint64_t sum, min;          /* sum and minimum of u over those edges (min = 0 when linked == 0) */
+    uint64_t external;          /* edges with exactly one end in the cluster */
+    int64_t nearest;            /* the other label with the largest u on an edge between the two (ties: the smallest label); -1 when external == 0 */
+    uint64_t nearest_max;       /* that largest u */
+    uint64_t nearest_sum;       /* sum of u over all edges between the cluster and `nearest` */
+    int64_t misfits;            /* members with other_max > own_max (below) */
+} vg_cluster_stat;
+/* The array-level report: rows as passed to vg_cluster_graph (already-passing rows), out[n_clusters].  Per object, each array of
+ * n_objects entries or NULL: own_max[i] = the largest u to a member of its own cluster (0 without one), other_max[i] = the largest u
+ * to an object of another cluster (0 without one) and other[i] = that object's label (ties: the smallest label; -1 without one).
+ * n_objects == 0 and n_rows == 0 are valid.  A label outside [0, n_clusters) is VG_EINVAL (checked on the host before any device
+ * use), n_objects or n_clusters >= 2^31 and 2^32 or more undirected edges VG_EOVERFLOW, no device VG_ENODEV (no host fallback). */
+int vg_cluster_stats_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                           const int32_t* label, int64_t n_clusters, vg_cluster_stat* out, uint64_t* own_max, uint64_t* other_max,
+                           int32_t* other);
+/* File to file, made after clusters.tsv is written: the rows of ani.tsv that pass p's filters (the parse and the error messages
+ * of vg_cluster; p->algorithm and p->representatives are not read), then clusters_path -- header `object` and one or more label
+ * columns, objects matched to the ids file by name, every id exactly once; a label is a non-negative integer or, with
+ * clusters_is_repr, the id of a member of that cluster.  Anything else is VG_EINVAL naming the file and line, before any device
+ * use.  out_path: tab-separated, header `column cluster size representative pairs linked min_<metric> mean_linked mean_all external
+ * nearest nearest_<metric> nearest_mean misfits`; one block per label column in file order (`column` = its header), one line per
+ * cluster ordered by its earliest member; `cluster` and `nearest` are the label texts of clusters_path; the quotients
+ * (sum / (linked * 2^32), sum / (pairs * 2^32), nearest_sum / (size * size[nearest] * 2^32), min / 2^32, nearest_max / 2^32) are the
+ * doubles nearest the exact values, printed %.6g, and `-` where there is no denominator, no linked edge or no nearest cluster. */
+int vg_cluster_stats_file(const char* ani_path, const char* ids_path, const char* clusters_path, int clusters_is_repr,
+                          const vg_cluster_params* p, const char* out_path);
+
 /* ------------------------------------------------------------------ deduplicate ------- */
 /* The first stage: FASTA files -> one FASTA of the distinct sequences + a duplicates list, in place of mfasta-tool
  * (cmd_mfasta_deduplicate, vclust.py:810-866, run at vclust.py:1351); DESIGN.md section 10 is the contract.  A record's sequence is its lines

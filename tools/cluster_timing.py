@@ -5,6 +5,7 @@ table), rounds, objects finished by the tail sweep, end-to-end wall time.
   python tools/cluster_timing.py --complete [--sizes 100000] [--clique-chain 200]
   python tools/cluster_timing.py --average [--sizes 100000] [--floor 0.8]
   python tools/cluster_timing.py --update [--sizes 100000] [--new-fraction 0.01]
+  python tools/cluster_timing.py --stats [--sizes 100000 1000000]
 
 Synthetic graphs: families of 20-200 objects in index order, ~50 rows per object (both directions, ~25 distinct
 neighbours), weights 0.80-1.00 inside families and a few weak rows between them.  With --ani, the file is also clustered
@@ -23,7 +24,10 @@ same process, each run once and discarded and then timed three times; the row pr
 prior clustering (vg_cluster_update_graph) on the synthetic family graph with the last --new-fraction of the objects new: the
 prior is the plain run on the rows among the other objects, the update gets the rows with a new end (what `align --db` writes),
 and the plain run on the whole graph (vg_cluster_graph) is the yardstick, in the same process; each is run once and discarded and
-then timed three times.  The row also says whether the update's labels equal the plain run's (properties P1 and P2).
+then timed three times.  The row also says whether the update's labels equal the plain run's (properties P1 and P2).  --stats: the
+cluster report (vg_cluster_stats_graph) on the synthetic family graph, of the `cd-hit` labelling and of the labelling with every
+object in one cluster, beside the `single` run in the same process; each is run once and discarded and then timed three times, and
+the row prints the three profile groups `cluster_stats_rows` / `cluster_stats_reduce` / `cluster_stats_nearest`.
 """
 import argparse
 import json
@@ -149,6 +153,23 @@ def update_rows(n, q, r, w, new_fraction):
     return res
 
 
+def stats_rows(n, q, r, w):
+    """the cluster report of the `cd-hit` labelling (many clusters; `single` is one component on this graph), and of the labelling
+    that puts every object into one cluster (the hot record of the reduce pass), beside the `single` run itself"""
+    (lab, rep, st), wall1, kern1 = median_of_three(lambda: api.cluster_graph(n, q, r, w, 'single'))
+    res = []
+    for name, label in (('cd-hit', api.cluster_graph(n, q, r, w, 'cd-hit')[0]), ('one cluster', np.zeros(n, np.int32))):
+        k = int(label.max()) + 1
+        (rec, own, oth_max, oth), wall, kern = median_of_three(lambda: api.cluster_stats_graph(n, q, r, w, label, k))
+        groups = {g: kern.get(f'cluster_stats_{g}', 0) for g in ('rows', 'reduce', 'nearest')}
+        res.append(dict(input=f'synthetic n={n} rows={len(q)}', algorithm='stats', labelling=name, clusters=k, wall_ms=round(wall, 2),
+                        gpu_ms=round(sum(kern.values()), 2), kernels=kern, **{f'{g}_ms': v for g, v in groups.items()},
+                        single_wall_ms=round(wall1, 2), single_gpu_ms=round(sum(kern1.values()), 2), edges=st['n_edges'],
+                        linked=int(rec['linked'].sum()), external=int(rec['external'].sum()) // 2, misfits=int(rec['misfits'].sum())))
+        assert res[-1]['linked'] + res[-1]['external'] == st['n_edges'] and int(rec['size'].sum()) == n, res[-1]
+    return res
+
+
 def timed(fn):
     api.profile_reset()
     t0 = time.perf_counter()
@@ -172,6 +193,7 @@ def main():
     ap.add_argument('--floor', type=float, default=0.8)
     ap.add_argument('--update', action='store_true')
     ap.add_argument('--new-fraction', type=float, default=0.01)
+    ap.add_argument('--stats', action='store_true')
     ap.add_argument('--json', type=pathlib.Path)
     a = ap.parse_args()
     if a.complete:
@@ -206,6 +228,13 @@ def main():
         api.cluster_update_graph(2, [0], [1], [1.0], [0, -1])
         for n in a.sizes:
             for row in update_rows(n, *family_graph(n), a.new_fraction):
+                print(json.dumps(row), flush=True)
+                res.append(row)
+        a.sizes = []
+    if a.stats:
+        api.cluster_stats_graph(2, [0], [1], [1.0], [0, 0])
+        for n in a.sizes:
+            for row in stats_rows(n, *family_graph(n)):
                 print(json.dumps(row), flush=True)
                 res.append(row)
         a.sizes = []

@@ -73,6 +73,13 @@ class ClusterUpdateStats(C.Structure):
                                                 'founded', 'prior_merged')]
 
 
+class ClusterStat(C.Structure):
+    """vg_cluster_stat: the record of one cluster in the cluster report"""
+    _fields_ = [('size', C.c_int64), ('rep', C.c_int64), ('pairs', C.c_uint64), ('linked', C.c_uint64), ('sum', C.c_uint64),
+                ('min', C.c_uint64), ('external', C.c_uint64), ('nearest', C.c_int64), ('nearest_max', C.c_uint64),
+                ('nearest_sum', C.c_uint64), ('misfits', C.c_int64)]
+
+
 class LinkageStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('n_edges', C.c_int64), ('n_merges', C.c_int64)]
 
@@ -200,6 +207,9 @@ SYMBOLS = {
     'vg_cluster_update_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, C.c_int, P(C.c_int32),
                                           P(C.c_int32), P(C.c_int32), P(ClusterUpdateStats)]),
     'vg_cluster_update': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, P(ClusterParams), P(ClusterUpdateStats)]),
+    'vg_cluster_stats_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_int32), C.c_int64,
+                                         P(ClusterStat), P(C.c_uint64), P(C.c_uint64), P(C.c_int32)]),
+    'vg_cluster_stats_file': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, P(ClusterParams), C.c_char_p]),
     'vg_cluster_linkage_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_int32), P(C.c_int32),
                                            P(C.c_double), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64), P(LinkageStats)]),
     'vg_cluster_levels_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(C.c_double), C.c_int,

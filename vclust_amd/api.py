@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStats, ClusterUpdateStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -23,6 +23,7 @@ REGION_DTYPE = np.dtype([('task', '<u4'), ('qstart', '<i4'), ('qend', '<i4'), ('
                          ('rend', '<i4'), ('n_match', '<i4')])
 LINKAGE_DTYPE = np.dtype([('node_a', '<i8'), ('node_b', '<i8'), ('similarity', '<f8'), ('size', '<i8'), ('object_a', '<i4'),
                           ('object_b', '<i4')])
+CLUSTER_STAT_DTYPE = np.dtype([(name, '<u8' if t is C.c_uint64 else '<i8') for name, t in ClusterStat._fields_])
 
 from .stages import DEFAULT_LZ  # noqa: E402
 
@@ -275,7 +276,7 @@ class GenomeSet:
 
 
 # ---------------------------------------------------------------- whole-stage calls (vclust_amd/stages.py: no numpy)
-from .stages import align, align_params, cluster, deduplicate as deduplicate_files, prefilter  # noqa: E402,F401
+from .stages import align, align_params, cluster, cluster_stats, deduplicate as deduplicate_files, prefilter  # noqa: E402,F401
 
 
 def cluster_graph(n_objects, q, r, w, algorithm='single'):
@@ -326,6 +327,27 @@ def cluster_update(ani_path, ids_path, prior_path, out_path, algorithm='single',
     (vg_cluster_update).  prior_repr: the second column of prior_path holds representative ids (as representatives=True writes
     them).  options: those of cluster().  -> the update's counts as a dict."""
     return cluster(ani_path, ids_path, out_path, algorithm=algorithm, prior_path=prior_path, prior_repr=prior_repr, **options)
+
+
+def cluster_stats_graph(n_objects, q, r, w, label, n_clusters=None):
+    """The cluster report of the labelling label[i] in [0, n_clusters) on the graph of cluster_graph (vg_cluster_stats_graph; DESIGN.md
+    section 9, "Cluster report"): weights in [0, 1], taken as u = round(w * 2^32).  n_clusters: default max(label) + 1.  ->
+    (records CLUSTER_STAT_DTYPE[n_clusters], own_max uint64[n], other_max uint64[n], other int32[n]); every figure is an integer."""
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    label = np.ascontiguousarray(label, dtype=np.int32)
+    if n < 1 << 31 and len(label) != n:
+        raise ValueError('label must have one entry per object')
+    if n_clusters is None:
+        n_clusters = int(label.max()) + 1 if len(label) else 0
+    k = int(n_clusters)
+    out = np.zeros(max(k, 1) if 0 <= k < 1 << 31 else 1, dtype=CLUSTER_STAT_DTYPE)
+    size = max(n, 1) if n < 1 << 31 else 1
+    own, oth, lab = np.zeros(size, dtype=np.uint64), np.zeros(size, dtype=np.uint64), np.zeros(size, dtype=np.int32)
+    P = C.POINTER
+    check(_lib.load().vg_cluster_stats_graph(n, *rows, label.ctypes.data_as(P(C.c_int32)), k, out.ctypes.data_as(P(ClusterStat)),
+                                             own.ctypes.data_as(P(C.c_uint64)), oth.ctypes.data_as(P(C.c_uint64)), lab.ctypes.data_as(P(C.c_int32))))
+    return out[:k], own[:n], oth[:n], lab[:n]
 
 
 def _rows(q, r, w):

@@ -6,7 +6,8 @@ ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster`
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
 single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster); `--out-linkage` and
 `--levels` (the merge table of single, complete or average linkage and its cuts) always run on the GPU, and so do `--algorithm average`
-and `--prior` (new genomes added to the clusters of an earlier clusters.tsv: vg_cluster_update).  `deduplicate` does
+and `--prior` (new genomes added to the clusters of an earlier clusters.tsv: vg_cluster_update); `--out-stats` is a second call
+after clusters.tsv is written, whoever wrote it (the per-cluster report: vg_cluster_stats_file).  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
 without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
 `--contained` always run on the GPU.  `info` reports the library and the optional CPU tools.
@@ -204,7 +205,11 @@ def get_parser() -> argparse.ArgumentParser:
                          'earlier cluster keeps its members and its representative; under single, earlier clusters may merge')
     cl.add_argument('--prior-repr', action='store_true', dest='prior_repr',
                     help='The second column of --prior holds representative ids, as --out-repr writes them [%(default)s]')
-    cl.add_argument('--leiden-resolution', metavar='<float>', type=_unit_float, default=0.7)
+    cl.add_argument('--out-stats', metavar='<file>', type=pathlib.Path, dest='stats_path',
+                    help='After the clustering, write a per-cluster report to the tsv <file> (always on the GPU, for every '
+                         '--algorithm): members, pairs with a row in the input, weakest and mean similarity inside the cluster, '
+                         'the nearest other cluster, and members that are closer to another cluster than to their own')
+    cl.add_argument('--leiden-resolution',metavar='<float>', type=_unit_float, default=0.7)
     cl.add_argument('--leiden-beta', metavar='<float>', type=_unit_float, default=0.01)
     cl.add_argument('--leiden-iterations', metavar='<int>', type=int, default=2)
     common(cl, threads=False)
@@ -451,6 +456,7 @@ def handle_cluster(args, parser, logger):
             logger.info(f'Prior clustering updated: {c["n_prior"]} prior + {c["n_new"]} new genomes, {c["n_edges"]} kept edges; new genomes: '
                         f'{c["joined_prior"]} joined a prior cluster, {c["joined_new"]} joined a new one, {c["founded"]} founded a cluster; '
                         f'{c["prior_merged"]} prior cluster(s) merged away')
+        cluster_report(args, logger)
         return
     _require_binary(BIN_CLUSTY)
     threshold = vars(args).get(args.metric, 0)
@@ -470,6 +476,30 @@ def handle_cluster(args, parser, logger):
                 '--leiden-iterations', str(args.leiden_iterations)]
     cmd += [str(args.input_path), str(args.output_path)]
     run_subprocess(cmd, args.verbosity_level, logger)
+    cluster_report(args, logger)
+
+
+def cluster_stats_call(args):
+    """What the front-end hands to vg_cluster_stats_file for validated cluster arguments: the filters and the metric of the
+    clustering itself (cluster_call), the clusters.tsv just written, and whether it holds representative ids."""
+    mins = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio') if getattr(args, k) > 0}
+    return dict(ani_path=args.input_path, ids_path=args.ids_path, clusters_path=args.output_path, out_path=args.stats_path,
+                clusters_repr=bool(args.representatives), metric=args.metric, num_alns=max(args.num_alns, 0), **mins)
+
+
+def cluster_report(args, logger):
+    """--out-stats: the second call of `cluster`, made once clusters.tsv is complete -- whoever wrote it, the library or
+    bin/clusty ("Cluster report").  It always runs in the library, under a `Running:` / `Completed` pair of
+    its own."""
+    if getattr(args, 'stats_path', None) is None:
+        return
+    from . import stages
+    call = cluster_stats_call(args)
+    desc = (f'libvclust_gpu cluster-stats --metric {args.metric}'
+            + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
+            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
+            + f' --clusters {args.output_path} [1 GPU] -> {args.stats_path}')
+    run_native(desc, lambda: stages.cluster_stats(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
 
 
 def validate_args_deduplicate(args, parser):

@@ -3,6 +3,7 @@
 //   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521)
 //   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557)
 //   vg_cluster_linkage   the same parse, then the single-, complete- or average-linkage merge table and its cuts at several levels
+//   vg_cluster_stats_file   the same parse and a clusters.tsv read back, then the per-cluster report of every label column
 // Both are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
 #include "vg_common.h"
 #include <math.h>
@@ -236,6 +237,31 @@ extern "C" int vg_cluster_update(const char* ani_path, const char* ids_path, con
     if (p->verbosity >= 2)
         fprintf(stderr, "vg_cluster_update: %lld prior + %lld new objects, %lld rows passed, %lld kept edges, %lld rounds, %lld objects by the tail sweep\n",
                 (long long)st.n_prior, (long long)st.n_new, (long long)in.q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+    VG_API_END
+}
+
+extern "C" int vg_cluster_stats_file(const char* ani_path, const char* ids_path, const char* clusters_path, int clusters_is_repr,
+                                     const vg_cluster_params* p, const char* out_path) {
+    VG_API_BEGIN
+    if (!ani_path || !ids_path || !clusters_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster_stats_file: null argument");
+    cluster_input in;
+    read_cluster_input("vg_cluster_stats_file", ani_path, ids_path, p, nullptr, 0, in);
+    vg_label_columns cols;
+    vg_cluster_read_columns(clusters_path, in.ids, clusters_is_repr != 0, cols);
+    vg_host_mark("clusters.tsv parsed");
+    const size_t nc = cols.names.size();
+    std::vector<std::vector<vg_cluster_stat>> stats(nc);
+    std::vector<const int32_t*> label(nc); std::vector<int64_t> n_clusters(nc); std::vector<vg_cluster_stat*> out(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        stats[c].resize(cols.text[c].size());
+        label[c] = cols.label[c].data(); n_clusters[c] = (int64_t)cols.text[c].size(); out[c] = stats[c].data();
+    }
+    vg_cluster_stats_run("vg_cluster_stats_file", (int64_t)in.ids.size(), in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), (int)nc,
+                         label.data(), n_clusters.data(), out.data(), nullptr, nullptr, nullptr);
+    vg_host_mark("cluster report computed");
+    vg_cluster_stats_write(out_path, p->metric, in.ids, cols, stats);
+    if (p->verbosity >= 2)
+        fprintf(stderr, "vg_cluster_stats_file: %lld objects, %lld rows passed, %d label column(s)\n", (long long)in.ids.size(), (long long)in.q.size(), (int)nc);
     VG_API_END
 }
 

@@ -19,6 +19,8 @@
 //             records go the forest's way
 //   average   the average-linkage (UPGMA) merge table in exact integer arithmetic: 64-bit sums of quantised weights, candidates
 //             compared as fractions (128-bit products), a reduction that adds the sums of a cluster pair
+//   report    the cohesion / separation figures of a GIVEN labelling: a row pass per object, a reduction of the objects sorted by
+//             label (segments inside a wave by shuffles, one atomic group per segment piece), a second row pass for the nearest cluster
 // Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
 // only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
 // their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
@@ -636,6 +638,117 @@ __global__ void k_update_counts(const int32_t* root, const int32_t* prior, const
     add_count(c + 0, jp); add_count(c + 1, jn); add_count(c + 2, fd); add_count(c + 3, pc); add_count(c + 4, pk);
 }
 
+// ---------------------------------------------------------------- cohesion / separation report ("Cluster report")
+// A given labelling label[i] in [0, n_clusters) over the edge graph, every weight the integer u of average linkage.  Three passes:
+//   rows     every object (ROW_LANES lanes each, row-strided as k_cl_find) reduces its row: count / sum / minimum of its own-cluster
+//            edges (each undirected edge at its smaller end), count of its external edges, own_max, the best external (u, label)
+//   reduce   the objects sorted by label (one radix sort); a wave reduces 64 sorted positions by segment with shuffles and the
+//            first lane of every segment piece adds it to the cluster's record: one atomic group per cluster per 64 members
+//   nearest  the rows once more for the sum over the edges to each cluster's nearest one and the misfit flags, reduced the same way
+// Every sum is an integer sum and every choice the maximum / minimum of a total order: the result does not depend on launch order.
+// the best external neighbour as one key: u (<= 2^32: 33 bits) above the complement of the label (31 bits), so that the maximum is the
+// largest u and, among equals, the smallest label.  "None" is not a key value: the count of external edges says so.
+constexpr uint64_t ST_LABEL_MASK = 0x7fffffffull;
+__host__ __device__ inline uint64_t st_key(uint64_t u, int32_t label) { return u << 31 | (ST_LABEL_MASK - (uint64_t)label); }
+__host__ __device__ inline int32_t st_key_label(uint64_t key) { return (int32_t)(ST_LABEL_MASK - (key & ST_LABEL_MASK)); }
+__host__ __device__ inline uint64_t st_key_u(uint64_t key) { return key >> 31; }
+// what a row or a piece of a cluster adds to the cluster's record; the identity is { 0, 0, 0, ~0, 0 }
+struct st_part { uint64_t cnt, sum, ext, mn, key; };
+__device__ __forceinline__ void st_combine(st_part& x, const st_part& y) {
+    x.cnt += y.cnt; x.sum += y.sum; x.ext += y.ext; x.mn = umin64(x.mn, y.mn); x.key = umax64(x.key, y.key);
+}
+__device__ __forceinline__ st_part st_shfl(const st_part& x, int o, bool down) {
+    auto mv = [&](uint64_t v) { return (uint64_t)(down ? __shfl_down((unsigned long long)v, o) : __shfl_xor((unsigned long long)v, o)); };
+    return st_part{ mv(x.cnt), mv(x.sum), mv(x.ext), mv(x.mn), mv(x.key) };
+}
+// rows.  NEAR = false: the partials of the record and own_max; NEAR = true: part.sum = the sum of u over the edges into the nearest
+// cluster of the object's own (rec_ext / rec_key of its cluster say which), part.cnt = 1 for a misfit (other_max > own_max).
+template <bool NEAR>
+__global__ void k_st_rows(int64_t n, const int64_t* off, const int32_t* adj, const uint64_t* u, const int32_t* label,
+                          const uint64_t* rec_ext, const uint64_t* rec_key, uint64_t* p_cnt, uint64_t* p_sum, uint64_t* p_ext, uint64_t* p_mn,
+                          uint64_t* p_key, uint64_t* own_max) {
+    const int lane = threadIdx.x % ROW_LANES;
+    const int64_t groups = (int64_t)gridDim.x * blockDim.x / ROW_LANES;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ROW_LANES; i < n; i += groups) {
+        const int32_t c = label[i];
+        const int32_t near = NEAR && rec_ext[c] ? st_key_label(rec_key[c]) : -1;
+        st_part v{ 0, 0, 0, ~0ull, 0 }; uint64_t own = 0;
+        for (int64_t k = off[i] + lane, e = off[i + 1]; k < e; k += ROW_LANES) {
+            const int32_t j = adj[k], d = label[j]; const uint64_t x = u[k];
+            if (NEAR) { if (d == near) v.sum += x; continue; }
+            if (d == c) { own = umax64(own, x); if (j > i) { ++v.cnt; v.sum += x; v.mn = umin64(v.mn, x); } }
+            else { ++v.ext; v.key = umax64(v.key, st_key(x, d)); }
+        }
+        for (int o = ROW_LANES / 2; o > 0; o >>= 1) {
+            st_combine(v, st_shfl(v, o, false));
+            own = umax64(own, (uint64_t)__shfl_xor((unsigned long long)own, o));
+        }
+        if (lane) continue;
+        if (NEAR) { p_sum[i] = v.sum; p_cnt[i] = (p_ext[i] ? st_key_u(p_key[i]) : 0) > own_max[i]; }
+        else { p_cnt[i] = v.cnt; p_sum[i] = v.sum; p_ext[i] = v.ext; p_mn[i] = v.mn; p_key[i] = v.key; own_max[i] = own; }
+    }
+}
+// reduce.  slabel[p] / order[p]: the label and the object at sorted position p (ascending label, then index).  A wave takes 64
+// positions per trip; after the segmented butterfly the first lane of every run of equal labels holds the run's total and adds it to
+// the record.  NEAR = false also notes where a cluster begins and ends in the sorted order (its size and its earliest member, without
+// atomics); NEAR = true adds (misfits, nearest_sum) only.
+template <bool NEAR>
+__global__ void k_st_reduce(int64_t n, const int32_t* slabel, const int32_t* order, const uint64_t* p_cnt, const uint64_t* p_sum,
+                            const uint64_t* p_ext, const uint64_t* p_mn, const uint64_t* p_key, unsigned long long* r_cnt,
+                            unsigned long long* r_sum, unsigned long long* r_ext, unsigned long long* r_mn, unsigned long long* r_key,
+                            int64_t* r_begin, int64_t* r_end, int32_t* r_rep) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; base < n; base += stride) {      // (wave-uniform)
+        const int64_t p = base + lane;
+        const bool live = p < n;
+        const int32_t lb = live ? slabel[p] : -1;               // (no label is -1: a dead lane joins no run of a live one)
+        st_part v{ 0, 0, 0, ~0ull, 0 };
+        if (live) {
+            const int32_t i = order[p];
+            v.cnt = p_cnt[i]; v.sum = p_sum[i];
+            if (!NEAR) {
+                v.ext = p_ext[i]; v.mn = p_mn[i]; v.key = p_key[i];
+                if (p == 0 || slabel[p - 1] != lb) { r_begin[lb] = p; r_rep[lb] = i; }
+                if (p == n - 1 || slabel[p + 1] != lb) r_end[lb] = p + 1;
+            }
+        }
+        for (int o = 1; o < 64; o <<= 1) {                      // lane l: the total over [l, l + 2o) cut at the end of its run
+            const st_part w = st_shfl(v, o, true);
+            const int32_t lb2 = __shfl_down(lb, o);
+            const bool take = lane + o < 64 && lb2 == lb;       // (selects, not a branch around the struct: see k_av_find)
+            st_part t = v;
+            st_combine(t, w);
+            v.cnt = take ? t.cnt : v.cnt; v.sum = take ? t.sum : v.sum; v.ext = take ? t.ext : v.ext;
+            v.mn = take ? t.mn : v.mn; v.key = take ? t.key : v.key;
+        }
+        const int32_t before = __shfl_up(lb, 1);
+        if (!live || (lane && before == lb)) continue;
+        if (v.cnt) atomicAdd(r_cnt + lb, (unsigned long long)v.cnt);
+        if (v.sum) atomicAdd(r_sum + lb, (unsigned long long)v.sum);
+        if (NEAR) continue;
+        if (v.cnt) atomicMin(r_mn + lb, (unsigned long long)v.mn);
+        if (v.ext) { atomicAdd(r_ext + lb, (unsigned long long)v.ext); atomicMax(r_key + lb, (unsigned long long)v.key); }
+    }
+}
+// the records as the caller's structs; a label without members: size 0, rep and nearest -1, the rest 0
+__global__ void k_st_finish(int64_t n_clusters, const int64_t* r_begin, const int64_t* r_end, const int32_t* r_rep, const unsigned long long* r_cnt,
+                            const unsigned long long* r_sum, const unsigned long long* r_ext, const unsigned long long* r_mn,
+                            const unsigned long long* r_key, const unsigned long long* r_mis, const unsigned long long* r_nsum, vg_cluster_stat* out) {
+    GRID_STRIDE(c, n_clusters) {
+        vg_cluster_stat o{};
+        o.rep = -1; o.nearest = -1;
+        if (r_begin[c] >= 0) {
+            o.size = r_end[c] - r_begin[c]; o.rep = r_rep[c];
+            o.pairs = (uint64_t)o.size * (uint64_t)(o.size - 1) / 2;
+            o.linked = r_cnt[c]; o.sum = r_sum[c]; o.min = o.linked ? r_mn[c] : 0; o.external = r_ext[c];
+            if (o.external) { o.nearest = st_key_label(r_key[c]); o.nearest_max = st_key_u(r_key[c]); o.nearest_sum = r_nsum[c]; }
+            o.misfits = (int64_t)r_mis[c];
+        }
+        out[c] = o;
+    }
+}
+
 // a round that decides fewer objects than this (and < 1 % of those left) hands the rest to the one-workgroup sweep
 constexpr int64_t LOW_PROGRESS = 4096;
 bool low_progress(int64_t decided, int64_t left) { return decided < LOW_PROGRESS && decided * 100 < left; }
@@ -1113,7 +1226,112 @@ void labels_on_device(int64_t n, const dbuf<int32_t>& root, bool by_min_member, 
     hipLaunchKernelGGL(k_head_labels, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)fm.p, (const int32_t*)fs.p, (const int32_t*)sm.p, (const int32_t*)ss.p, n, lab.p);
     hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)lab.p, n, minm.p);
 }
+
+// The report of one labelling on the edge graph (u: its quantised weights): the three passes, then the records and, if wanted,
+// the per-object values leave the device.  label[] has been checked on the host.
+void stats_on_device(int64_t n, const edge_graph& eg, const dbuf<uint64_t>& u, hipStream_t s, const int32_t* label, int64_t n_clusters,
+                     vg_cluster_stat* out, uint64_t* own_max, uint64_t* other_max, int32_t* other) {
+    const int64_t* off = eg.off.p; const int32_t* adj = eg.adj.p;
+    const size_t nc = (size_t)n_clusters;
+    dbuf<int32_t> d_label((size_t)n), iota((size_t)n), slabel((size_t)n), order((size_t)n), r_rep(nc);
+    dbuf<uint64_t> p_cnt((size_t)n), p_sum((size_t)n), p_ext((size_t)n), p_mn((size_t)n), p_key((size_t)n), own((size_t)n), p_mis((size_t)n), p_nsum((size_t)n);
+    dbuf<unsigned long long> r_cnt(nc), r_sum(nc), r_ext(nc), r_mn(nc), r_key(nc), r_mis(nc), r_nsum(nc);
+    dbuf<int64_t> r_begin(nc), r_end(nc);
+    dbuf<vg_cluster_stat> d_out(nc);
+    d_label.upload(label, (size_t)n, s);
+    const int row_grid = grid_of(n * ROW_LANES);
+    {
+        vg_prof_scope ps("cluster_stats_rows", (double)eg.m * 16.0 + (double)n * 60.0);
+        hipLaunchKernelGGL(k_st_rows<false>, dim3(row_grid), dim3(TPB), 0, s, n, off, adj, (const uint64_t*)u.p, (const int32_t*)d_label.p,
+                           (const uint64_t*)nullptr, (const uint64_t*)nullptr, p_cnt.p, p_sum.p, p_ext.p, p_mn.p, p_key.p, own.p);
+    }
+    {
+        vg_prof_scope ps("cluster_stats_reduce", (double)n * (16.0 * 2.0 + 52.0) + (double)n_clusters * 64.0);
+        hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, iota.p, n);
+        with_temp_storage([&](void* tmp, size_t& tb) {
+            return rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)d_label.p, (uint32_t*)slabel.p, iota.p, order.p, (size_t)n, 0u,
+                                             (unsigned)id_bits(n_clusters), s); });
+        for (dbuf<unsigned long long>* b : { &r_cnt, &r_sum, &r_ext, &r_key, &r_mis, &r_nsum }) b->zero(s);
+        VG_HIP(hipMemsetAsync(r_mn.p, 0xff, r_mn.bytes(), s));
+        VG_HIP(hipMemsetAsync(r_begin.p, 0xff, r_begin.bytes(), s));
+        hipLaunchKernelGGL(k_st_reduce<false>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)slabel.p, (const int32_t*)order.p,
+                           (const uint64_t*)p_cnt.p, (const uint64_t*)p_sum.p, (const uint64_t*)p_ext.p, (const uint64_t*)p_mn.p,
+                           (const uint64_t*)p_key.p, r_cnt.p, r_sum.p, r_ext.p, r_mn.p, r_key.p, r_begin.p, r_end.p, r_rep.p);
+    }
+    {
+        vg_prof_scope ps("cluster_stats_nearest", (double)eg.m * 16.0 + (double)n * 72.0 + (double)n_clusters * 176.0);
+        hipLaunchKernelGGL(k_st_rows<true>, dim3(row_grid), dim3(TPB), 0, s, n, off, adj, (const uint64_t*)u.p, (const int32_t*)d_label.p,
+                           (const uint64_t*)r_ext.p, (const uint64_t*)r_key.p, p_mis.p, p_nsum.p, p_ext.p, p_mn.p, p_key.p, own.p);
+        hipLaunchKernelGGL(k_st_reduce<true>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)slabel.p, (const int32_t*)order.p,
+                           (const uint64_t*)p_mis.p, (const uint64_t*)p_nsum.p, (const uint64_t*)nullptr, (const uint64_t*)nullptr,
+                           (const uint64_t*)nullptr, r_mis.p, r_nsum.p, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                           (unsigned long long*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr, (int32_t*)nullptr);
+        hipLaunchKernelGGL(k_st_finish, dim3(grid_of(n_clusters)), dim3(TPB), 0, s, n_clusters, (const int64_t*)r_begin.p, (const int64_t*)r_end.p,
+                           (const int32_t*)r_rep.p, (const unsigned long long*)r_cnt.p, (const unsigned long long*)r_sum.p,
+                           (const unsigned long long*)r_ext.p, (const unsigned long long*)r_mn.p, (const unsigned long long*)r_key.p,
+                           (const unsigned long long*)r_mis.p, (const unsigned long long*)r_nsum.p, d_out.p);
+    }
+    VG_HIP(hipGetLastError());
+    d_out.download(out, nc, s);
+    if (own_max) own.download(own_max, (size_t)n, s);
+    if (other_max || other) {                                   // the best external key of every object, decoded here
+        std::vector<uint64_t> key((size_t)n), ext((size_t)n);
+        p_key.download(key.data(), (size_t)n, s); p_ext.download(ext.data(), (size_t)n, s);
+        VG_HIP(hipStreamSynchronize(s));
+        for (int64_t i = 0; i < n; ++i) {
+            if (other_max) other_max[i] = ext[(size_t)i] ? st_key_u(key[(size_t)i]) : 0;
+            if (other) other[i] = ext[(size_t)i] ? st_key_label(key[(size_t)i]) : -1;
+        }
+    }
+    VG_HIP(hipStreamSynchronize(s));
+}
 }  // namespace
+
+// The cluster report of n_cols labellings of one graph (vg_cluster_stats_graph: one; vg_cluster_stats_file: one per label column):
+// the checks on the host, one graph build, one quantisation, then the passes per labelling.  The per-object arrays belong to
+// labelling 0 and may be null.
+void vg_cluster_stats_run(const char* fn, int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, int n_cols,
+                          const int32_t* const* label, const int64_t* n_clusters, vg_cluster_stat* const* out, uint64_t* own_max,
+                          uint64_t* other_max, int32_t* other) {
+    const std::string name(fn);
+    check_rows(fn, n, q, r, w, n_rows);
+    for (int c = 0; c < n_cols; ++c) {
+        if (n_clusters[c] < 0) throw vg_error(VG_EINVAL, name + ": negative number of clusters");
+        if (n_clusters[c] >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, name + ": 2^31 or more clusters (labels are int32)");
+        if ((n && !label[c]) || (n_clusters[c] && !out[c])) throw vg_error(VG_EINVAL, name + ": null argument");
+    }
+    check_row_values(fn, n, q, r, w, n_rows);
+    const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return !(w[i] >= 0 && w[i] <= 1); });
+    if (k >= 0) throw vg_error(VG_EINVAL, name + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1]");
+    for (int c = 0; c < n_cols; ++c) {
+        const int64_t bad = first_bad_row(n, [&](int64_t i) { return label[c][i] < 0 || label[c][i] >= n_clusters[c]; });
+        if (bad >= 0)
+            throw vg_error(VG_EINVAL, name + ": label[" + std::to_string(bad) + "] = " + std::to_string(label[c][bad]) + " outside 0.." + std::to_string(n_clusters[c] - 1));
+    }
+    if (n == 0) {                                               // no member anywhere
+        for (int c = 0; c < n_cols; ++c)
+            for (int64_t x = 0; x < n_clusters[c]; ++x) { out[c][x] = vg_cluster_stat{}; out[c][x].rep = out[c][x].nearest = -1; }
+        return;
+    }
+    vg_require_device();
+    hipStream_t s = vg_stream();
+    edge_graph eg;
+    build_edge_graph(n, q, r, w, n_rows, s, eg);
+    if (eg.m / 2 >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, name + ": 2^32 or more edges (a sum of weights must fit 64 bits)");
+    dbuf<uint64_t> u((size_t)eg.m);
+    hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(eg.m)), dim3(TPB), 0, s, (const double*)eg.uvals.p, eg.m, u.p);
+    VG_HIP(hipGetLastError());
+    for (int c = 0; c < n_cols; ++c)
+        stats_on_device(n, eg, u, s, label[c], n_clusters[c], out[c], c ? nullptr : own_max, c ? nullptr : other_max, c ? nullptr : other);
+}
+
+extern "C" int vg_cluster_stats_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                      const int32_t* label, int64_t n_clusters, vg_cluster_stat* out, uint64_t* own_max,
+                                      uint64_t* other_max, int32_t* other) {
+    VG_API_BEGIN
+    vg_cluster_stats_run("vg_cluster_stats_graph", n_objects, q, r, w, n_rows, 1, &label, &n_clusters, &out, own_max, other_max, other);
+    VG_API_END
+}
 
 extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                                 int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats) {

@@ -212,6 +212,19 @@ void vg_cluster_write(const char* path, const std::vector<std::string>& ids, con
 // a prior clusters.tsv against the ids (vg_io.cpp): prior_rep[i] = -1 for an object without a line, else the index of its cluster's
 // representative -- the earliest member of the cluster number, or (is_repr) the object named in column 2; VG_EINVAL with file:line
 void vg_cluster_read_prior(const char* path, const std::vector<std::string>& ids, bool is_repr, std::vector<int32_t>& prior_rep);
+// cluster report.  The label columns of a clusters.tsv against the ids (vg_io.cpp): every id exactly once, a label a non-negative
+// integer or (is_repr) the id of a member of its cluster; VG_EINVAL with file:line.  The clusters of a column are numbered 0.. by
+// their earliest member: label[c][i] is that number, text[c][k] the label of cluster k as the file writes it.
+struct vg_label_columns { std::vector<std::string> names; std::vector<std::vector<int32_t>> label; std::vector<std::vector<std::string>> text; };
+void vg_cluster_read_columns(const char* path, const std::vector<std::string>& ids, bool is_repr, vg_label_columns& out);
+// the records of n_cols labellings of one graph (vg_cluster.hip): host checks (errors name fn), one graph build, three passes per
+// labelling; own_max / other_max / other (each may be null) are the per-object values of labelling 0
+void vg_cluster_stats_run(const char* fn, int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, int n_cols,
+                          const int32_t* const* label, const int64_t* n_clusters, vg_cluster_stat* const* out, uint64_t* own_max,
+                          uint64_t* other_max, int32_t* other);
+// the report file (vg_io.cpp): one block per column, one line per cluster in the order of the records (by earliest member)
+void vg_cluster_stats_write(const char* path, const char* metric, const std::vector<std::string>& ids, const vg_label_columns& cols,
+                            const std::vector<std::vector<vg_cluster_stat>>& stats);
 // merge table (vg_cluster.hip): the forest edges of the rows in merge order (a < b, weights non-increasing) -- checks the rows
 // (errors name fn), then the device; the node numbering of the table and the labels of a cut are host loops over those records.
 // algorithm: VG_CLUSTER_SINGLE (the maximum spanning forest), VG_CLUSTER_COMPLETE (the worst edge of every complete-linkage merge)

@@ -732,6 +732,128 @@ void vg_cluster_read_prior(const char* path, const std::vector<std::string>& ids
     for (const entry& en : entries) prior_rep[(size_t)en.obj] = first[en.number];
 }
 
+void vg_cluster_read_columns(const char* path, const std::vector<std::string>& ids, bool is_repr, vg_label_columns& out) {
+    mapped_text f(path);
+    if (!f.n) row_error(path, 1, "empty file (no header)");
+    const char* end = f.p + f.n;
+    std::unordered_map<std::string_view, int32_t> index;
+    index.reserve(ids.size() * 2);
+    for (size_t i = 0; i < ids.size(); ++i) index.emplace(ids[i], (int32_t)i);
+    auto split = [](std::string_view text, std::vector<std::string_view>& fields) {
+        fields.clear();
+        for (size_t a = 0;;) {
+            const size_t t = text.find('\t', a);
+            fields.push_back(text.substr(a, t == std::string_view::npos ? t : t - a));
+            if (t == std::string_view::npos) break;
+            a = t + 1;
+        }
+    };
+    // pass 1: the header, then every line names an object of the ids file once and carries one value per label column
+    std::vector<int64_t> line_of(ids.size(), 0);                // (0: not seen)
+    std::vector<std::string_view> value, fields;                // value[i * n_cols + c]
+    size_t n_cols = 0;
+    int64_t line = 0;
+    for (const char* a = f.p; a < end;) {
+        const char* e = f.line_end(a);
+        ++line;
+        const char* le = e > a && e[-1] == '\r' ? e - 1 : e;
+        const std::string_view text(a, (size_t)(le - a));
+        a = e + 1;
+        if (line == 1) {
+            split(text, fields);
+            bool ok = fields.size() >= 2 && fields[0] == "object";
+            for (const std::string_view& x : fields) ok = ok && !x.empty();
+            if (!ok) row_error(path, 1, "malformed header (expected object<TAB>cluster, then further label columns)");
+            n_cols = fields.size() - 1;
+            out.names.assign(fields.begin() + 1, fields.end());
+            value.assign(ids.size() * n_cols, std::string_view());
+            continue;
+        }
+        if (text.empty()) continue;
+        split(text, fields);
+        bool ok = fields.size() == n_cols + 1;
+        for (const std::string_view& x : fields) ok = ok && !x.empty();
+        if (!ok) row_error(path, line, "malformed line (expected " + std::to_string(n_cols + 1) + " fields)");
+        const auto it = index.find(fields[0]);
+        if (it == index.end()) row_error(path, line, "object '" + std::string(fields[0]) + "' is not in the ids file");
+        const size_t i = (size_t)it->second;
+        if (line_of[i]) row_error(path, line, "object '" + std::string(fields[0]) + "' is listed twice");
+        line_of[i] = line;
+        for (size_t c = 0; c < n_cols; ++c) {
+            const std::string_view v = fields[c + 1];
+            value[i * n_cols + c] = v;
+            if (is_repr) continue;
+            uint64_t number = 0;
+            const auto rr = std::from_chars(v.data(), v.data() + v.size(), number);
+            if (rr.ec != std::errc() || rr.ptr != v.data() + v.size() || number >= (1ull << 31))
+                row_error(path, line, "malformed cluster number '" + std::string(v) + "'");
+        }
+    }
+    for (size_t i = 0; i < ids.size(); ++i)
+        if (!line_of[i]) row_error(path, line, "object '" + ids[i] + "' of the ids file is missing");
+    // pass 2 (representative ids): the value names an object, and that object names itself in the same column
+    if (is_repr)
+        for (size_t i = 0; i < ids.size(); ++i)
+            for (size_t c = 0; c < n_cols; ++c) {
+                const std::string_view v = value[i * n_cols + c];
+                const auto it = index.find(v);
+                if (it == index.end()) row_error(path, line_of[i], "representative '" + std::string(v) + "' is not in the ids file");
+                if (value[(size_t)it->second * n_cols + c] != v)
+                    row_error(path, line_of[i], "representative '" + std::string(v) + "' is not a member of its cluster");
+            }
+    // the clusters of a column, numbered by their earliest member
+    out.label.assign(n_cols, std::vector<int32_t>(ids.size()));
+    out.text.assign(n_cols, {});
+    for (size_t c = 0; c < n_cols; ++c) {
+        std::unordered_map<std::string_view, int32_t> by_text; std::unordered_map<uint64_t, int32_t> by_number;
+        for (size_t i = 0; i < ids.size(); ++i) {
+            const std::string_view v = value[i * n_cols + c];
+            const int32_t next = (int32_t)out.text[c].size();
+            int32_t k;
+            if (is_repr) k = by_text.emplace(v, next).first->second;
+            else { uint64_t number = 0; std::from_chars(v.data(), v.data() + v.size(), number); k = by_number.emplace(number, next).first->second; }
+            if (k == next) out.text[c].emplace_back(v);
+            out.label[c][i] = k;
+        }
+    }
+}
+
+void vg_cluster_stats_write(const char* path, const char* metric, const std::vector<std::string>& ids, const vg_label_columns& cols,
+                            const std::vector<std::vector<vg_cluster_stat>>& stats) {
+    const std::string m(metric);
+    std::string o = "column\tcluster\tsize\trepresentative\tpairs\tlinked\tmin_" + m + "\tmean_linked\tmean_all\texternal\tnearest\tnearest_" + m +
+                    "\tnearest_mean\tmisfits\n";
+    char buf[64];
+    auto num = [&](uint64_t v) { o.push_back('\t'); o += std::to_string(v); };
+    // the double nearest S / (P * 2^32), by the exact division of the average-linkage table; no denominator (or no value): `-`
+    auto quotient = [&](bool have, uint64_t S, uint64_t P) {
+        o.push_back('\t');
+        if (!have || P == 0) { o.push_back('-'); return; }
+        snprintf(buf, sizeof buf, "%.6g", vg_cluster_average_similarity(S, P));
+        o += buf;
+    };
+    for (size_t c = 0; c < cols.names.size(); ++c)
+        for (size_t k = 0; k < stats[c].size(); ++k) {
+            const vg_cluster_stat& s = stats[c][k];
+            if (s.size == 0) continue;
+            const bool near = s.nearest >= 0;
+            o += cols.names[c]; o.push_back('\t'); o += cols.text[c][k];
+            num((uint64_t)s.size); o.push_back('\t'); o += ids[(size_t)s.rep];
+            num(s.pairs); num(s.linked);
+            quotient(s.linked != 0, s.min, 1); quotient(true, s.sum, s.linked); quotient(true, s.sum, s.pairs);
+            num(s.external);
+            o.push_back('\t'); o += near ? cols.text[c][(size_t)s.nearest] : std::string("-");
+            quotient(near, s.nearest_max, 1);
+            quotient(near, s.nearest_sum, near ? (uint64_t)s.size * (uint64_t)stats[c][(size_t)s.nearest].size : 0);
+            num((uint64_t)s.misfits);
+            o.push_back('\n');
+        }
+    FILE* fo = fopen(path, "w");
+    if (!fo) throw vg_error(VG_EIO, std::string("cannot write ") + path);
+    if (fwrite(o.data(), 1, o.size(), fo) != o.size()) { fclose(fo); throw vg_error(VG_EIO, std::string("write error on ") + path); }
+    if (fclose(fo)) throw vg_error(VG_EIO, std::string("write error on ") + path);
+}
+
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives) {
     std::string o = "object\tcluster\n";
     o.reserve(ids.size() * 24 + 16);

@@ -1,5 +1,5 @@
 """The whole-stage calls of the drop-in CLI (vg_prefilter, vg_align: FASTA on disk -> fltr.txt / ani.tsv on disk; vg_cluster:
-ani.tsv + ids file -> clusters.tsv; vg_deduplicate: FASTA files -> distinct records + duplicates list) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster|deduplicate` process is
+ani.tsv + ids file -> clusters.tsv, vg_cluster_stats_file: the per-cluster report of a clusters.tsv; vg_deduplicate: FASTA files -> distinct records + duplicates list) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster|deduplicate` process is
 one of these calls, and importing numpy costs it 60-180 ms of its ~1 s.  vclust_amd.api re-exports them beside the
 array-level API."""
 import ctypes as C
@@ -108,6 +108,23 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     lv = [float(x) for x in (levels or ())]
     check(_lib.load().vg_cluster_linkage(*paths, C.byref(p), os.fsencode(str(out_linkage)) if out_linkage is not None else None,
                                          (C.c_double * len(lv))(*lv) if lv else None, len(lv)))
+
+
+def cluster_stats(ani_path, ids_path, clusters_path, out_path, clusters_repr=False, metric='tani', num_alns=0, num_threads=0,
+                  verbosity=0, **mins):
+    """The cohesion / separation report of a clusters.tsv (vg_cluster_stats_file; DESIGN.md section 9, "Cluster report") -> out_path:
+    one block per label column, one line per cluster (members, pairs with a row, weakest and mean similarity inside, the nearest
+    other cluster, members closer to another cluster than to their own).  The rows are those of ani.tsv that pass the filters of
+    cluster() (metric, mins, num_alns: give the ones the clustering was made with); clusters_path may be any clustering of the
+    ids file, this library's or not; clusters_repr: its label columns hold representative ids."""
+    unknown = set(mins) - set(CLUSTER_FILTERS)
+    if unknown:
+        raise TypeError(f'unknown filter(s): {sorted(unknown)}')
+    p = ClusterParams(algorithm=0, metric=metric.encode(), max_num_alns=int(num_alns), num_threads=int(num_threads), verbosity=int(verbosity))
+    for name, val in mins.items():
+        setattr(p, f'min_{name}', float(val))
+    check(_lib.load().vg_cluster_stats_file(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(clusters_path)),
+                                            int(bool(clusters_repr)), C.byref(p), os.fsencode(str(out_path))))
 
 
 def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False, contained=False,
