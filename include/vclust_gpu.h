@@ -351,7 +351,8 @@ int vg_align_sharded(const char* const* fasta_paths, int n_paths, const char* ou
  * Objects are the rows of the ids file (index = row number from 0, i.e. the align stage's length order).  A row of ani.tsv
  * passes when every minimum > 0 holds (column >= value), num_alns <= max_num_alns when that is > 0, and qidx != ridx; it
  * links {qidx, ridx} with the metric value as weight (the maximum over duplicate and reverse rows). */
-enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3, VG_CLUSTER_COMPLETE = 4, VG_CLUSTER_AVERAGE = 5 };
+enum { VG_CLUSTER_SINGLE = 0, VG_CLUSTER_CDHIT = 1, VG_CLUSTER_UCLUST = 2, VG_CLUSTER_SET_COVER = 3, VG_CLUSTER_COMPLETE = 4, VG_CLUSTER_AVERAGE = 5,
+       VG_CLUSTER_MCL = 6 /* Markov clustering: its own calls below; vg_cluster and vg_cluster_graph refuse it */ };
 typedef struct {            /* mirrors the cluster sub-parser, vclust.py:423 ff. */
     int algorithm;                                            /* VG_CLUSTER_* */
     const char* metric;                                       /* "tani" | "gani" | "ani": the edge weight */
@@ -522,6 +523,46 @@ int vg_cluster_stats_graph(int64_t n_objects, const uint32_t* q, const uint32_t*
  * doubles nearest the exact values, printed %.6g, and `-` where there is no denominator, no linked edge or no nearest cluster. */
 int vg_cluster_stats_file(const char* ani_path, const char* ids_path, const char* clusters_path, int clusters_is_repr,
                           const vg_cluster_params* p, const char* out_path);
+
+/* Markov clustering (this repository's definition; DESIGN.md section 9, "Markov clustering"; tests/mcl_restatement.py is the
+ * sequential restatement).  The graph is the one above, every weight in [0, 1] (else VG_EINVAL).  The flow matrix is held in
+ * integers: an entry is a uint32 in units of 2^-30 (ONE = 2^30), row i the flow out of object i.  Start: the quantised weights
+ * llrint(w * 2^32), a loop as heavy as the row's heaviest edge (ONE without edges), the row normalised (p = floor(x * ONE / sum),
+ * zeros dropped).  One iteration, per row: expansion (the row times the matrix, exact 64-bit sums, >> 30), inflation by
+ * inflation = a / 2 (an exact integer square root when a is odd, then a >> 1 multiplications, each >> 30; zeros dropped; nothing left:
+ * the row is the loop alone), normalisation, pruning (entries >= floor(prune * ONE), else the largest; at most the max_row largest by
+ * (value descending, column ascending)), normalisation again; the row's chaos is max p - (sum p^2 >> 30).  The run stops after the
+ * first iteration whose largest chaos is <= floor(chaos_eps * ONE) (converged = 1) or after max_iterations (converged = 0: there
+ * is a result all the same).  Clusters: the connected components of {i, j : p_ij > 0, i != j} of the last matrix, labelled as
+ * VG_CLUSTER_SINGLE labels them.  Every sum is an integer sum: the result does not depend on the order of anything. */
+typedef struct {
+    double inflation;           /* a multiple of 0.5 in [1.5, 6] (pow() is not correctly rounded on the device; halves are exact) */
+    double prune;               /* [0, 0.1] */
+    double chaos_eps;           /* [0, 1) */
+    int max_row;                /* [2, 4096] */
+    int max_iterations;         /* [1, 1000] */
+} vg_mcl_params;
+typedef struct {
+    int64_t iterations, converged;
+    int64_t n_edges;            /* undirected edges after dropping self rows and merging duplicates */
+    int64_t nnz, max_row_seen;  /* entries and widest row of the last matrix */
+    int64_t lds_rows, spill_rows;   /* rows expanded in an LDS table / through the sorted spill records, over all iterations */
+    uint64_t chaos;             /* of the last iteration, in units of 2^-30 */
+} vg_mcl_stats;
+/* Rows as for vg_cluster_graph.  A parameter outside its range is VG_EINVAL naming it; every argument check runs on the host before
+ * any device use; n_objects == 0 is VG_OK without a device, n_objects >= 2^31 VG_EOVERFLOW, no device VG_ENODEV.  m_off, m_col and
+ * m_val may all be NULL; otherwise they receive the last matrix as CSR (m_off[n_objects + 1], columns ascending per row), each to be
+ * released with vg_free: with max_iterations = t that is the iterate after t steps.  stats may be NULL. */
+int vg_cluster_mcl_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                         const vg_mcl_params* params, int32_t* label, int32_t* representative, int64_t** m_off, int32_t** m_col,
+                         uint32_t** m_val, vg_mcl_stats* stats);
+/* File to file, with the host parse, the output and the error messages of vg_cluster; p->algorithm must be VG_CLUSTER_MCL. */
+int vg_cluster_mcl(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
+                   const vg_mcl_params* params, vg_mcl_stats* stats);
+/* Developer knob: the slots of the LDS table a row may use (a power of two in 16..4096; 0 = the default, 4096).  A row whose
+ * candidate bound exceeds it and whose distinct columns fill more than 3/4 of it takes the spill path, so a small value sends
+ * tiny graphs there. */
+void vg_cluster_mcl_set_table_slots(int slots);
 
 /* ------------------------------------------------------------------ deduplicate ------- */
 /* The first stage: FASTA files -> one FASTA of the distinct sequences + a duplicates list, in place of mfasta-tool

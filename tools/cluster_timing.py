@@ -6,6 +6,7 @@ table), rounds, objects finished by the tail sweep, end-to-end wall time.
   python tools/cluster_timing.py --average [--sizes 100000] [--floor 0.8]
   python tools/cluster_timing.py --update [--sizes 100000] [--new-fraction 0.01]
   python tools/cluster_timing.py --stats [--sizes 100000 1000000]
+  python tools/cluster_timing.py --mcl [--sizes 100000] [--rows-per-object 9 90]
 
 Synthetic graphs: families of 20-200 objects in index order, ~50 rows per object (both directions, ~25 distinct
 neighbours), weights 0.80-1.00 inside families and a few weak rows between them.  With --ani, the file is also clustered
@@ -27,7 +28,12 @@ and the plain run on the whole graph (vg_cluster_graph) is the yardstick, in the
 then timed three times.  The row also says whether the update's labels equal the plain run's (properties P1 and P2).  --stats: the
 cluster report (vg_cluster_stats_graph) on the synthetic family graph, of the `cd-hit` labelling and of the labelling with every
 object in one cluster, beside the `single` run in the same process; each is run once and discarded and then timed three times, and
-the row prints the three profile groups `cluster_stats_rows` / `cluster_stats_reduce` / `cluster_stats_nearest`.
+the row prints the three profile groups `cluster_stats_rows` / `cluster_stats_reduce` / `cluster_stats_nearest`.  --mcl: Markov
+clustering (vg_cluster_mcl_graph, default parameters) on the synthetic family graph at --rows-per-object rows per object (9: about
+4.5 edges per object, the shape of the benchmark's pair set; 90: ten times denser), beside `single` in the same process; each is run
+once and discarded and then timed three times, and the row prints all three wall times, the `cluster_mcl_*` and graph-build
+(`cluster_edges_*`, `cluster_csr`) profile groups of the median run with their spread over the three, the iterations and the
+LDS / spill row split.
 """
 import argparse
 import json
@@ -170,6 +176,21 @@ def stats_rows(n, q, r, w):
     return res
 
 
+def mcl_row(n, q, r, w, rows_per_object):
+    (lab1, _, st1), wall1, kern1 = median_of_three(lambda: api.cluster_graph(n, q, r, w, 'single'))
+    api.cluster_mcl_graph(n, q, r, w)
+    runs = sorted((timed(lambda: api.cluster_mcl_graph(n, q, r, w)) for _ in range(3)), key=lambda x: x[1])
+    (lab, rep, st), wall, kern = runs[1]
+    spread = {k: [round(min(x[2].get(k, 0) for x in runs), 3), round(max(x[2].get(k, 0) for x in runs), 3)] for k in kern}
+    mcl = {k: v for k, v in kern.items() if k.startswith('cluster_mcl_')}
+    build = {k: v for k, v in kern.items() if k.startswith('cluster_edges_') or k == 'cluster_csr'}
+    return dict(input=f'synthetic n={n} rows={len(q)} ({rows_per_object} per object)', algorithm='mcl', wall_ms=round(wall, 2),
+                wall_ms_all=[round(x[1], 2) for x in runs], gpu_ms=round(sum(kern.values()), 2), mcl_ms=round(sum(mcl.values()), 2),
+                build_ms=round(sum(build.values()), 2), kernels=kern, kernels_min_max=spread,
+                mcl_ms_per_iteration=round(sum(mcl.values()) / max(st['iterations'], 1), 3), clusters=int(lab.max()) + 1,
+                single_clusters=int(lab1.max()) + 1, single_wall_ms=round(wall1, 2), single_gpu_ms=round(sum(kern1.values()), 2), **st)
+
+
 def timed(fn):
     api.profile_reset()
     t0 = time.perf_counter()
@@ -194,6 +215,8 @@ def main():
     ap.add_argument('--update', action='store_true')
     ap.add_argument('--new-fraction', type=float, default=0.01)
     ap.add_argument('--stats', action='store_true')
+    ap.add_argument('--mcl', action='store_true')
+    ap.add_argument('--rows-per-object', type=int, nargs='*', default=[9, 90])
     ap.add_argument('--json', type=pathlib.Path)
     a = ap.parse_args()
     if a.complete:
@@ -235,6 +258,14 @@ def main():
         api.cluster_stats_graph(2, [0], [1], [1.0], [0, 0])
         for n in a.sizes:
             for row in stats_rows(n, *family_graph(n)):
+                print(json.dumps(row), flush=True)
+                res.append(row)
+        a.sizes = []
+    if a.mcl:
+        api.cluster_mcl_graph(2, [0], [1], [1.0])
+        for n in a.sizes:
+            for per_object in a.rows_per_object:
+                row = mcl_row(n, *family_graph(n, per_object), per_object)
                 print(json.dumps(row), flush=True)
                 res.append(row)
         a.sizes = []

@@ -93,6 +93,16 @@ LINKAGE_ALGORITHMS = {'single': 0, 'complete': 4}
 HIERARCHY_ALGORITHMS = {**LINKAGE_ALGORITHMS, 'average': 5}
 # the algorithms under which new objects are added to a prior clustering (vg_cluster_update / vg_cluster_update_graph)
 UPDATE_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2}
+# the flow algorithms: Markov clustering, with calls of its own (vg_cluster_mcl / vg_cluster_mcl_graph); always in the library
+FLOW_ALGORITHMS = {'mcl': 6}
+
+
+class MclParams(C.Structure):
+    _fields_ = [('inflation', C.c_double), ('prune', C.c_double), ('chaos_eps', C.c_double), ('max_row', C.c_int), ('max_iterations', C.c_int)]
+
+
+class MclStats(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ('iterations', 'converged', 'n_edges', 'nnz', 'max_row_seen', 'lds_rows', 'spill_rows')] + [('chaos', C.c_uint64)]
 
 
 class DedupParams(C.Structure):
@@ -227,6 +237,10 @@ SYMBOLS = {
     'vg_cluster_average_order_selftest': (C.c_int, [P(C.c_uint64), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), P(C.c_uint32), C.c_int64,
                                                     C.c_int, P(C.c_int8)]),
     'vg_cluster_linkage': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams), C.c_char_p, P(C.c_double), C.c_int]),
+    'vg_cluster_mcl_graph': (C.c_int, [C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_double), C.c_int64, P(MclParams), P(C.c_int32), P(C.c_int32),
+                                       P(P(C.c_int64)), P(P(C.c_int32)), P(P(C.c_uint32)), P(MclStats)]),
+    'vg_cluster_mcl': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams), P(MclParams), P(MclStats)]),
+    'vg_cluster_mcl_set_table_slots': (None, [C.c_int]),
     'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),
     'vg_deduplicate_ex': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams), P(DedupOptions)]),

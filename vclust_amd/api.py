@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, KernelTime, LinkageStats, LzParams, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, KernelTime, LinkageStats, LzParams, MclParams, MclStats, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -296,6 +296,37 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     check(_lib.load().vg_cluster_graph(n, *rows, known[algorithm], label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
                                        C.byref(st)))
     return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
+
+
+def cluster_mcl_graph(n_objects, q, r, w, inflation=2.0, prune=1e-4, max_row=128, chaos_eps=1e-3, max_iterations=100, matrix=False):
+    """Markov clustering of the graph of cluster_graph (vg_cluster_mcl_graph; DESIGN.md section 9, "Markov clustering"): weights in
+    [0, 1]; the flow matrix is held in integers of 2^-30, so the result is the same on every run.  inflation: a multiple of 0.5 in
+    [1.5, 6]; prune: entries below that share of a row are dropped; max_row: entries a row keeps at most; the run stops when the
+    chaos of an iteration is <= chaos_eps, or after max_iterations (stats['converged'] == 0: there is a result all the same).
+    -> (label int32[n], representative int32[n], stats dict), and with matrix=True also (offsets int64[n + 1], columns int32[nnz],
+    values uint32[nnz]): the last matrix as CSR, columns ascending per row -- with max_iterations=t the iterate after t steps."""
+    q, r, w, rows = _rows(q, r, w)
+    n = int(n_objects)
+    size = max(n, 1) if n < 1 << 31 else 1
+    label, rep = np.zeros(size, dtype=np.int32), np.zeros(size, dtype=np.int32)
+    prm = MclParams(float(inflation), float(prune), float(chaos_eps), int(max_row), int(max_iterations))
+    st = MclStats()
+    P = C.POINTER
+    off, col, val = P(C.c_int64)(), P(C.c_int32)(), P(C.c_uint32)()
+    check(_lib.load().vg_cluster_mcl_graph(n, *rows, C.byref(prm), label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
+                                           C.byref(off) if matrix else None, C.byref(col) if matrix else None,
+                                           C.byref(val) if matrix else None, C.byref(st)))
+    stats = {name: getattr(st, name) for name, _ in MclStats._fields_}
+    if not matrix:
+        return label[:n], rep[:n], stats
+    nnz = int(stats['nnz'])
+    return label[:n], rep[:n], stats, (_take(off, n + 1, np.dtype('<i8')), _take(col, nnz, np.dtype('<i4')), _take(val, nnz, np.dtype('<u4')))
+
+
+def cluster_mcl_set_table_slots(slots=0):
+    """Test knob (vg_cluster_mcl_set_table_slots): the LDS table slots a row of the Markov clustering may use; rows whose candidate
+    bound exceeds them, and whose distinct columns fill more than 3/4 of them, take the spill path.  0 = the default."""
+    _lib.load().vg_cluster_mcl_set_table_slots(int(slots))
 
 
 def cluster_update_graph(n_objects, q, r, w, prior_rep, algorithm='single'):

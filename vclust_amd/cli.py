@@ -5,7 +5,8 @@ output files (vclust.py:178-421, 1380-1521) but call libvclust_gpu.so (HIP, MI35
 ctypes instead of running bin/kmer-db and bin/lz-ani as subprocesses.  `cluster` passes its
 arguments on to bin/clusty where that binary exists, as the reference does; without it, the
 single, cd-hit, uclust and set-cover algorithms run on the GPU (vg_cluster); `--out-linkage` and
-`--levels` (the merge table of single, complete or average linkage and its cuts) always run on the GPU, and so do `--algorithm average`
+`--levels` (the merge table of single, complete or average linkage and its cuts) always run on the GPU, and so do `--algorithm average`,
+`--algorithm mcl` (Markov clustering in exact integer arithmetic: vg_cluster_mcl)
 and `--prior` (new genomes added to the clusters of an earlier clusters.tsv: vg_cluster_update); `--out-stats` is a second call
 after clusters.tsv is written, whoever wrote it (the per-cluster report: vg_cluster_stats_file).  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
@@ -182,9 +183,10 @@ def get_parser() -> argparse.ArgumentParser:
     cl.add_argument('-r', '--out-repr', action='store_true', dest='representatives',
                     help='Output a representative genome for each cluster [%(default)s]')
     cl.add_argument('--algorithm', metavar='<str>', dest='algorithm', default='single',
-                    choices=['single', 'complete', 'average', 'uclust', 'cd-hit', 'set-cover', 'leiden'],
+                    choices=['single', 'complete', 'average', 'uclust', 'cd-hit', 'set-cover', 'leiden', 'mcl'],
                     help='Clustering algorithm [%(default)s]; average (UPGMA: a pair without a row counts as 0) always runs on the GPU '
-                         'and merges down to the threshold of --metric')
+                         'and merges down to the threshold of --metric; mcl (Markov clustering: deterministic, separates dense groups '
+                         'joined by weak rows) always runs on the GPU too')
     cl.add_argument('--metric', metavar='<str>', dest='metric', choices=['tani', 'gani', 'ani'], default='tani',
                     help='Similarity metric for clustering [%(default)s]')
     for name in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio'):
@@ -209,6 +211,15 @@ def get_parser() -> argparse.ArgumentParser:
                     help='After the clustering, write a per-cluster report to the tsv <file> (always on the GPU, for every '
                          '--algorithm): members, pairs with a row in the input, weakest and mean similarity inside the cluster, '
                          'the nearest other cluster, and members that are closer to another cluster than to their own')
+    cl.add_argument('--mcl-inflation', metavar='<float>', type=float, dest='mcl_inflation', default=2.0,
+                    help='--algorithm mcl: the inflation exponent, a multiple of 0.5 in 1.5-6 (halves keep the integer arithmetic '
+                         'exact: pow() is not correctly rounded on the GPU); higher gives smaller clusters [%(default)s]')
+    cl.add_argument('--mcl-prune', metavar='<float>', type=float, dest='mcl_prune', default=1e-4,
+                    help='--algorithm mcl: drop flow below this share of a row (0-0.1) [%(default)s]')
+    cl.add_argument('--mcl-max-row', metavar='<int>', type=int, dest='mcl_max_row', default=128,
+                    help='--algorithm mcl: keep at most this many entries per row (2-4096) [%(default)s]')
+    cl.add_argument('--mcl-iterations', metavar='<int>', type=int, dest='mcl_iterations', default=100,
+                    help='--algorithm mcl: stop after this many iterations (1-1000) even if the flow still moves [%(default)s]')
     cl.add_argument('--leiden-resolution',metavar='<float>', type=_unit_float, default=0.7)
     cl.add_argument('--leiden-beta', metavar='<float>', type=_unit_float, default=0.01)
     cl.add_argument('--leiden-iterations', metavar='<int>', type=int, default=2)
@@ -407,12 +418,15 @@ def cluster_call(args):
     if getattr(args, 'prior_path', None) is not None:     # --prior: vg_cluster_update (no reference counterpart)
         call['prior_path'] = args.prior_path
         call['prior_repr'] = bool(args.prior_repr)
+    if args.algorithm == 'mcl':                           # Markov clustering: vg_cluster_mcl (no reference counterpart)
+        for key in ('mcl_inflation', 'mcl_prune', 'mcl_max_row', 'mcl_iterations'):
+            call[key] = getattr(args, key)
     return call
 
 
 def handle_cluster(args, parser, logger):
     """`cluster`: bin/clusty where it exists and computes what is asked; the library otherwise, and always for the merge table,
-    its cuts, average linkage and --prior.  --prior adds the genomes of --ids that the earlier clusters.tsv does not list to its
+    its cuts, average linkage, Markov clustering and --prior.  --prior adds the genomes of --ids that the earlier clusters.tsv does not list to its
     clusters (the ids file and the rows are those of an `align --db` run; DESIGN.md section 9, "Update of a prior clustering")."""
     from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS
     linkage_path, levels = getattr(args, 'linkage_path', None), getattr(args, 'levels', None)
@@ -434,15 +448,26 @@ def handle_cluster(args, parser, logger):
         for level in levels or ():
             if floor and level < floor:
                 parser.error(f'--levels {level:g} is below --{args.metric} {floor:g}: rows below the threshold are not edges.')
-    if hierarchy or prior_path is not None or args.algorithm == 'average' or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
+    mcl = args.algorithm == 'mcl'
+    if mcl:
+        if abs(2 * args.mcl_inflation - round(2 * args.mcl_inflation)) >= 1e-9 or not 1.5 <= args.mcl_inflation <= 6:
+            parser.error(f'--mcl-inflation {args.mcl_inflation:g} must be a multiple of 0.5 between 1.5 and 6.')
+        if not 0 <= args.mcl_prune <= 0.1:
+            parser.error(f'--mcl-prune {args.mcl_prune:g} must lie between 0 and 0.1.')
+        if not 2 <= args.mcl_max_row <= 4096:
+            parser.error(f'--mcl-max-row {args.mcl_max_row} must lie between 2 and 4096.')
+        if not 1 <= args.mcl_iterations <= 1000:
+            parser.error(f'--mcl-iterations {args.mcl_iterations} must lie between 1 and 1000.')
+    if hierarchy or prior_path is not None or args.algorithm == 'average' or mcl or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
         # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster); the merge table and
         # its cuts (which Clusty does not have) always do, for every hierarchy, and so does average linkage, which Clusty does
-        # not have either, and --prior.  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and still goes to Clusty below.
+        # not have either, --prior and Markov clustering.  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and still goes
+        # to Clusty below.
         if not vars(args).get(args.metric, 0):
             parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
         from . import stages
         call = cluster_call(args)
-        desc = (f'libvclust_gpu cluster --algorithm {args.algorithm} --metric {args.metric}'
+        desc = (f'libvclust_gpu cluster --algorithm {args.algorithm}' + (f' --mcl-inflation {args.mcl_inflation:g}' if mcl else '') + f' --metric {args.metric}'
                 + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
                 + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
                 + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
@@ -456,6 +481,13 @@ def handle_cluster(args, parser, logger):
             logger.info(f'Prior clustering updated: {c["n_prior"]} prior + {c["n_new"]} new genomes, {c["n_edges"]} kept edges; new genomes: '
                         f'{c["joined_prior"]} joined a prior cluster, {c["joined_new"]} joined a new one, {c["founded"]} founded a cluster; '
                         f'{c["prior_merged"]} prior cluster(s) merged away')
+        if mcl:
+            c = counts[0]
+            with open(args.output_path) as f:
+                labels = {line.split('\t')[1] for line in f.read().split('\n')[1:] if line}
+            logger.info(f'MCL: {c["iterations"]} iterations, chaos {c["chaos"] / (1 << 30):.3g}, {len(labels)} clusters')
+            if not c['converged']:
+                logger.warning(f'MCL did not converge within --mcl-iterations {args.mcl_iterations}: the clusters are those of the last iterate')
         cluster_report(args, logger)
         return
     _require_binary(BIN_CLUSTY)

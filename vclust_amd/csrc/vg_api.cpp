@@ -2,6 +2,7 @@
 //   vg_prefilter  replaces kmer-db build + all2all + distance (vclust.py:1433-1471)
 //   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521)
 //   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557)
+//   vg_cluster_mcl       the same parse, then Markov clustering (vg_cluster_mcl_graph)
 //   vg_cluster_linkage   the same parse, then the single-, complete- or average-linkage merge table and its cuts at several levels
 //   vg_cluster_stats_file   the same parse and a clusters.tsv read back, then the per-cluster report of every label column
 // Both are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
@@ -212,6 +213,29 @@ extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char
     if (p->verbosity >= 2)
         fprintf(stderr, "vg_cluster: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld objects by the tail sweep\n",
                 (long long)n, (long long)in.q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+    VG_API_END
+}
+
+extern "C" int vg_cluster_mcl(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
+                              const vg_mcl_params* params, vg_mcl_stats* stats) {
+    VG_API_BEGIN
+    if (!ani_path || !ids_path || !out_path || !p || !p->metric || !params) throw vg_error(VG_EINVAL, "vg_cluster_mcl: null argument");
+    if (p->algorithm != VG_CLUSTER_MCL) throw vg_error(VG_EINVAL, "vg_cluster_mcl: the algorithm must be VG_CLUSTER_MCL");
+    if (stats) *stats = vg_mcl_stats{};
+    cluster_input in;
+    read_cluster_input("vg_cluster_mcl", ani_path, ids_path, p, nullptr, 0, in);
+    const int64_t n = (int64_t)in.ids.size();
+    std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
+    vg_mcl_stats st{};
+    check(vg_cluster_mcl_graph(n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), params, label.data(), rep.data(), nullptr, nullptr,
+                               nullptr, &st));
+    vg_host_mark("clusters computed");
+    vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0);
+    if (stats) *stats = st;
+    if (p->verbosity >= 2)
+        fprintf(stderr, "vg_cluster_mcl: %lld objects, %lld rows passed, %lld edges, %lld iterations (%s), %lld entries, %lld LDS + %lld spill rows\n",
+                (long long)n, (long long)in.q.size(), (long long)st.n_edges, (long long)st.iterations, st.converged ? "converged" : "not converged",
+                (long long)st.nnz, (long long)st.lds_rows, (long long)st.spill_rows);
     VG_API_END
 }
 

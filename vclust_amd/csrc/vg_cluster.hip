@@ -1,4 +1,4 @@
-// vg_cluster.hip — the cluster stage on the GPU: single linkage, cd-hit, uclust and greedy set cover over the edge graph
+// vg_cluster.hip — the cluster stage on the GPU: single linkage, cd-hit, uclust, greedy set cover and Markov clustering over the edge graph
 // of ani.tsv (in place of Clusty, cmd_clusty, vclust.py:1184-1278).  DESIGN.md section 9 states the contract and the design.
 //   edges     rows -> both directions -> radix sort on (src, dst) -> duplicates merged to the max weight -> CSR (int64 offsets)
 //   single    hook (atomicMin on the parent array) + pointer jumping, one launch each per round: label = min member
@@ -21,12 +21,15 @@
 //             compared as fractions (128-bit products), a reduction that adds the sums of a cluster pair
 //   report    the cohesion / separation figures of a GIVEN labelling: a row pass per object, a reduction of the objects sorted by
 //             label (segments inside a wave by shuffles, one atomic group per segment piece), a second row pass for the nearest cluster
+//   mcl       Markov clustering in integers of 2^-30 (its own section at the end of the file): per iteration a plan pass, the row
+//             expansion in an LDS hash table (a wave or a workgroup per row) with a sorted spill path, one finish for both
 // Every cross-workgroup hand-off is a kernel boundary.  Inside a round, reads of other objects' state may be stale: states
 // only move from UNDECIDED to final, so a stale read delays a decision and never changes one.  The sweeps are one workgroup:
 // their stores are agent-scope (sc1) and drained before the barrier, their loads of state agent-scope (not L1-served).
 #include "vg_common.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <type_traits>
@@ -786,11 +789,11 @@ void check_row_values(const char* fn, int64_t n_objects, const uint32_t* q, cons
                        (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
 }
 // average linkage: the quantum 2^-32 and the 64-bit sums stand on weights (and a floor) in [0, 1]
-void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double floor) {
+void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double floor, const char* what = "average linkage") {
     if (!(floor >= 0 && floor <= 1)) throw vg_error(VG_EINVAL, std::string(fn) + ": the floor must lie in [0, 1]");
     const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return !(w[i] >= 0 && w[i] <= 1); });
     if (k >= 0)
-        throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1] (average linkage)");
+        throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1] (" + what + ")");
 }
 
 // the edge graph of the rows on the device: the m directed edges sorted by (src, dst) with their weights, and the CSR.  With a
@@ -1621,4 +1624,554 @@ extern "C" int vg_cluster_average_order_selftest(const uint64_t* sum, const uint
     dout.download(out, (size_t)n - 1, s);
     VG_HIP(hipStreamSynchronize(s));
     VG_API_END
+}
+
+// ---------------------------------------------------------------- Markov clustering ("Markov clustering")
+// The flow matrix in integers: an entry is col << 32 | p, p a uint32 in units of 2^-30; row i is ent[off[i] .. off[i] + cnt[i]) in
+// any order (every step below is a sum, a maximum or a choice by a unique key, so the order never shows).  One iteration:
+//   plan      the candidate bound of every row (the sum of nnz over the rows it names, and no more than n: its columns are
+//             objects), its kernel by that bound -- a wave or a workgroup --, the storage of the next matrix (min(max_row, bound)
+//             per row, one scan); one read-back
+//   expand    a row per wave / workgroup: (column, value) pairs of the named rows gathered 16 lanes a row, products added into an
+//             open-addressing hash table in LDS (column claimed by compare-and-swap, 64-bit sums by LDS atomics), then the finish
+//   spill     rows whose bound exceeds the table and whose distinct columns, tried in it, fill more than 3/4 of it: (row, column,
+//             product) records, one radix sort, reduce-by-key, the same finish over the row's segment of the reduced records, in
+//             place in global memory
+//   finish    inflation, normalisation, pruning (cut, then a radix select of the max_row largest keys p << 32 | ~column),
+//             normalisation, the row's chaos; it touches the candidate array a[0 .. L) (0 = no entry) only at a thread's own strided
+//             positions, so LDS table and global segment are the same code
+namespace {
+constexpr uint64_t MCL_ONE = 1ull << 30;
+constexpr uint32_t MCL_EMPTY = 0xffffffffu;        // (no column: columns are < 2^31)
+constexpr int MCL_WAVE_SLOTS = 512;                 // 6 KiB of table: a one-wave workgroup per row
+constexpr int MCL_GROUP_SLOTS = 4096;               // 48 KiB of table: three 256-thread workgroups on a CU's 160 KiB
+constexpr int MCL_SUB = 16;                         // lanes that read one named row: 16 pairs = 128 bytes
+constexpr int64_t MCL_SPILL_BATCH = 1ll << 25;      // spill records sorted at once (a row above it is a batch of its own)
+// the counters of one iteration: MC_WAVE .. MC_STORAGE are the plan's (MC_TRY: group rows whose bound exceeds the table), MC_SPILL
+// counts the rows the group kernel hands on
+enum { MC_CHAOS, MC_BAD, MC_WAVE, MC_GROUP, MC_TRY, MC_STORAGE, MC_SPILL, MC_N };
+std::atomic<int> g_mcl_slots{ 0 };
+
+struct mcl_matrix { dbuf<int64_t> off; dbuf<int32_t> cnt; dbuf<uint64_t> ent; };
+struct mcl_dev { int a; uint32_t cut; int max_row; };       // inflation = a / 2, cut = floor(prune * ONE)
+struct mcl_scratch { uint32_t hist[256]; uint64_t red[4]; uint32_t n_out, n_keys, full; };
+
+// floor(sqrt(x)), x <= 2^60: the double root is off by a few units at most, integer compares settle it
+__device__ __forceinline__ uint64_t mcl_isqrt(uint64_t x) {
+    uint64_t s = (uint64_t)sqrt((double)x);
+    while (s * s > x) --s;
+    while ((s + 1) * (s + 1) <= x) ++s;
+    return s;
+}
+// y^(a / 2), y <= ONE: every intermediate is <= ONE and every product <= 2^60
+__device__ __forceinline__ uint64_t mcl_power(uint64_t y, int a) {
+    uint64_t t = (a & 1) ? mcl_isqrt(y << 30) : MCL_ONE;
+    for (int k = a >> 1; k > 0; --k) t = (t * y) >> 30;
+    return t;
+}
+// the candidate of value p in column col: larger p first, then the smaller column; no entry is 0 (a key has p >= 1)
+__device__ __forceinline__ uint64_t mcl_key(uint64_t p, uint32_t col) { return p ? p << 32 | (uint32_t)~col : 0; }
+
+template <int T> __device__ __forceinline__ uint64_t mcl_sum(uint64_t v, mcl_scratch& sc) {
+    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
+    if (T == 64) return v;
+    if ((threadIdx.x & 63) == 0) sc.red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = 0;
+    for (int x = 0; x < T / 64; ++x) v += sc.red[x];
+    __syncthreads();
+    return v;
+}
+template <int T> __device__ __forceinline__ uint64_t mcl_max(uint64_t v, mcl_scratch& sc) {
+    for (int o = 32; o > 0; o >>= 1) v = umax64(v, (uint64_t)__shfl_xor((unsigned long long)v, o));
+    if (T == 64) return v;
+    if ((threadIdx.x & 63) == 0) sc.red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = 0;
+    for (int x = 0; x < T / 64; ++x) v = umax64(v, sc.red[x]);
+    __syncthreads();
+    return v;
+}
+
+// The finish of one row by a workgroup of T threads.  a[0 .. L), L >= 1: mcl_key(inflated value, column) or 0, in LDS or in global
+// memory; out[0 .. cap): the row's storage in the next matrix.  Steps 2 (its end) to 6 of the definition.
+template <int T>
+__device__ __forceinline__ void mcl_finish(uint64_t* a, int L, int32_t row, const mcl_dev P, mcl_scratch& sc, uint64_t* out, int64_t cap,
+                                           int32_t* out_cnt, unsigned long long* ctr) {
+    const int t = threadIdx.x;
+    uint64_t s = 0;
+    for (int x = t; x < L; x += T) s += a[x] >> 32;
+    uint64_t S = mcl_sum<T>(s, sc);
+    if (S == 0) { if (t == 0) a[0] = mcl_key(MCL_ONE, (uint32_t)row); S = MCL_ONE; }      // nothing survived inflation: the loop alone
+    // normalise, then the cut; `best` is the largest normalised candidate, kept if none passes
+    uint64_t best = 0, kept = 0;
+    for (int x = t; x < L; x += T) {
+        const uint64_t k = a[x];
+        if (!k) continue;
+        const uint64_t p = ((k >> 32) << 30) / S;
+        uint64_t nk = p ? p << 32 | (uint32_t)k : 0;
+        best = umax64(best, nk);
+        if (p < P.cut) nk = 0;
+        a[x] = nk; kept += nk != 0;
+    }
+    best = mcl_max<T>(best, sc); kept = mcl_sum<T>(kept, sc);
+    if (kept == 0) { if (t == 0) a[0] = best; kept = 1; }
+    if (kept > (uint64_t)P.max_row) {
+        // radix select, 8 bits a pass from the top: `prefix` becomes the max_row-th largest key (keys are unique)
+        uint64_t prefix = 0; uint32_t need = (uint32_t)P.max_row;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            for (int x = t; x < 256; x += T) sc.hist[x] = 0;
+            __syncthreads();
+            for (int x = t; x < L; x += T) {
+                const uint64_t k = a[x];
+                if (k && (shift == 56 || (k >> (shift + 8)) == (prefix >> (shift + 8)))) atomicAdd(&sc.hist[(k >> shift) & 255], 1u);
+            }
+            __syncthreads();
+            int d = 255; uint32_t above = 0;                    // every thread walks the histogram down (broadcast reads)
+            for (; d > 0; --d) { const uint32_t h = sc.hist[d]; if (above + h >= need) break; above += h; }
+            need -= above; prefix |= (uint64_t)d << shift;
+            __syncthreads();
+        }
+        for (int x = t; x < L; x += T) if (a[x] < prefix) a[x] = 0;
+    }
+    uint64_t s2 = 0;
+    for (int x = t; x < L; x += T) s2 += a[x] >> 32;
+    const uint64_t S2 = mcl_sum<T>(s2, sc);
+    if (t == 0) sc.n_out = 0;
+    __syncthreads();
+    uint64_t mx = 0, sq = 0; bool over = false;
+    for (int x = t; x < L; x += T) {
+        const uint64_t k = a[x];
+        if (!k) continue;
+        const uint64_t p = ((k >> 32) << 30) / S2;
+        if (!p) continue;
+        const uint32_t slot = atomicAdd(&sc.n_out, 1u);
+        if ((int64_t)slot < cap) out[slot] = (uint64_t)(~(uint32_t)k) << 32 | p; else over = true;
+        mx = umax64(mx, p); sq += p * p;
+    }
+    if (over) atomicMax(ctr + MC_BAD, 1ull);
+    mx = mcl_max<T>(mx, sc); sq = mcl_sum<T>(sq, sc);
+    __syncthreads();
+    if (t == 0) {
+        out_cnt[row] = (int32_t)((int64_t)sc.n_out < cap ? (int64_t)sc.n_out : cap);
+        atomicMax(ctr + MC_CHAOS, (unsigned long long)(mx - (sq >> 30)));
+    }
+    __syncthreads();
+}
+
+// start: one pass over the CSR and the quantised weights u; row i gets the deg(i) + 1 slots behind off[i] = eoff[i] + i.  (A row
+// whose weights all quantise to 0 gets the loop of an object without edges: there is nothing to normalise by otherwise.)
+__global__ void k_mcl_start(int64_t n, const int64_t* eoff, const int32_t* adj, const uint64_t* u, int64_t* off, int32_t* cnt, uint64_t* ent) {
+    GRID_STRIDE(i, n) {
+        const int64_t lo = eoff[i], hi = eoff[i + 1], base = lo + i;
+        uint64_t mx = 0, sum = 0;
+        for (int64_t k = lo; k < hi; ++k) { mx = umax64(mx, u[k]); sum += u[k]; }
+        const uint64_t loop = mx ? mx : MCL_ONE, S = sum + loop;
+        int32_t c = 0;
+        for (int64_t k = lo; k < hi; ++k) {
+            const uint64_t p = u[k] * MCL_ONE / S;
+            if (p) ent[base + c++] = (uint64_t)(uint32_t)adj[k] << 32 | p;
+        }
+        const uint64_t p = loop * MCL_ONE / S;
+        if (p) ent[base + c++] = (uint64_t)i << 32 | p;
+        off[i] = base; cnt[i] = c;
+    }
+}
+// plan, step 1: bound[i] = the sum of nnz over the rows that row i names (ROW_LANES lanes a row)
+__global__ void k_mcl_bound(int64_t n, const int64_t* off, const int32_t* cnt, const uint64_t* ent, int64_t* bound) {
+    const int lane = threadIdx.x % ROW_LANES;
+    const int64_t groups = (int64_t)gridDim.x * blockDim.x / ROW_LANES;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ROW_LANES; i < n; i += groups) {
+        const int64_t o = off[i];
+        uint64_t b = 0;
+        for (int32_t e = lane, c = cnt[i]; e < c; e += ROW_LANES) b += (uint64_t)cnt[ent[o + e] >> 32];
+        for (int x = ROW_LANES / 2; x > 0; x >>= 1) b += (uint64_t)__shfl_xor((unsigned long long)b, x);
+        if (lane == 0) bound[i] = (int64_t)b;
+    }
+}
+// plan, step 2: the row lists of the two kernels (one atomic per wave and class), the rows among the workgroup's whose bound exceeds
+// the table counted, and the storage bound of every row with its total
+__global__ void k_mcl_classify(int64_t n, const int64_t* bound, int64_t wave_cap, int64_t group_cap, int64_t max_row, int32_t* wave_rows,
+                               int32_t* group_rows, int64_t* store, unsigned long long* ctr) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n; base += stride) {      // (whole waves stay together for the ballots)
+        const int64_t i = base + threadIdx.x;
+        const bool live = i < n;
+        const int64_t b = live ? bound[i] : 0, distinct = b < n ? b : n;       // (a row has no more distinct columns than there are objects)
+        const int cls = !live ? -1 : distinct <= wave_cap ? 0 : 1;
+        for (int c = 0; c < 2; ++c) {
+            const uint64_t mask = __ballot(cls == c);
+            if (!mask) continue;
+            const int leader = __builtin_ctzll(mask);
+            unsigned long long at = 0;
+            if (lane == leader) at = atomicAdd(ctr + MC_WAVE + c, (unsigned long long)__builtin_popcountll(mask));
+            at = __shfl(at, leader);
+            if (cls != c) continue;
+            at += (unsigned long long)__builtin_popcountll(mask & ((1ull << lane) - 1));
+            if (c == 0) wave_rows[at] = (int32_t)i; else group_rows[at] = (int32_t)i;
+        }
+        const uint64_t above = __ballot(live && distinct > group_cap);
+        if (lane == 0 && above) atomicAdd(ctr + MC_TRY, (unsigned long long)__builtin_popcountll(above));
+        uint64_t keep = live ? (uint64_t)(distinct < max_row ? distinct : max_row) : 0;
+        if (live) store[i] = (int64_t)keep;
+        for (int o = 32; o > 0; o >>= 1) keep += (uint64_t)__shfl_xor((unsigned long long)keep, o);
+        if (lane == 0 && keep) atomicAdd(ctr + MC_STORAGE, (unsigned long long)keep);
+    }
+}
+// expand + finish in LDS, one row per workgroup of T threads (T = 64: a wave).  slots <= SLOTS is the table a row may use (the
+// developer knob lowers it); a row takes the power of two that holds twice its bound, so clearing and scanning follow the row's size.
+// min(bound, n) >= the distinct columns: a row with that <= slots always finds a slot (the probe count is a guard).  A row whose
+// bound EXCEEDS the table (only the workgroup kernel gets such rows) is tried all the same -- the bound counts every product, the
+// distinct columns of a row inside a family are far fewer -- with its claimed slots counted: once more than 3/4 of the table is
+// claimed the row is given up and appended to the spill list.  That happens iff the row has more distinct columns than that, whatever
+// the order of the claims, so which rows spill is as fixed as everything else.
+template <int T, int SLOTS>
+__global__ void __launch_bounds__(T) k_mcl_expand(int64_t n, const int32_t* rows, int64_t n_rows, const int64_t* off, const int32_t* cnt, const uint64_t* ent,
+                                                  const int64_t* bound, int slots, const mcl_dev P, const int64_t* off_next, const int64_t* store,
+                                                  int32_t* cnt_next, uint64_t* ent_next, int32_t* spill_rows, int64_t* spill_bound,
+                                                  unsigned long long* ctr) {
+    __shared__ uint32_t keys[SLOTS];
+    __shared__ uint64_t acc[SLOTS];
+    __shared__ mcl_scratch sc;
+    const int t = threadIdx.x, sub = t / MCL_SUB, sl = t % MCL_SUB;
+    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int32_t i = rows[r];
+        const int64_t distinct = bound[i] < n ? bound[i] : n;
+        int lg = 6;
+        while ((1 << lg) < slots && (int64_t)(1 << lg) < 2 * distinct) ++lg;
+        if ((1 << lg) > slots) lg = 31 - __builtin_clz((unsigned)slots);
+        const int ts = 1 << lg;
+        const bool tried = distinct > slots;                    // (then ts == slots)
+        const uint32_t limit = (uint32_t)(ts - ts / 4);
+        for (int x = t; x < ts; x += T) { keys[x] = MCL_EMPTY; acc[x] = 0; }
+        if (t == 0) { sc.n_keys = 0; sc.full = 0; }
+        __syncthreads();
+        const int64_t o = off[i];
+        bool lost = false;
+        for (int32_t e = sub, c = cnt[i]; e < c; e += T / MCL_SUB) {
+            if (tried && *(volatile uint32_t*)&sc.full) break;
+            const uint64_t ik = ent[o + e];
+            const uint32_t k = (uint32_t)(ik >> 32);
+            const uint64_t p = (uint32_t)ik;
+            const int64_t ok = off[k];
+            for (int32_t j = sl, ck = cnt[k]; j < ck; j += MCL_SUB) {
+                const uint64_t kj = ent[ok + j];
+                const uint32_t col = (uint32_t)(kj >> 32);
+                uint32_t h = (col * 2654435761u) >> (32 - lg);
+                int probe = 0;
+                for (; probe < ts; ++probe) {
+                    const uint32_t prev = atomicCAS(&keys[h], MCL_EMPTY, col);
+                    if (prev == MCL_EMPTY && tried && atomicAdd(&sc.n_keys, 1u) >= limit) *(volatile uint32_t*)&sc.full = 1;
+                    if (prev == MCL_EMPTY || prev == col) break;
+                    h = (h + 1) & (uint32_t)(ts - 1);
+                }
+                if (probe < ts) atomicAdd((unsigned long long*)&acc[h], (unsigned long long)(p * (uint32_t)kj));
+                else if (tried) *(volatile uint32_t*)&sc.full = 1;       // (claims in flight filled the rest: the count has passed the limit)
+                else lost = true;
+            }
+        }
+        if (lost) atomicMax(ctr + MC_BAD, 1ull);
+        __syncthreads();
+        if (tried && sc.full) {                                 // uniform: the row goes to the spill path
+            if (t == 0) { const unsigned long long at = atomicAdd(ctr + MC_SPILL, 1ull); spill_rows[at] = i; spill_bound[at] = bound[i]; }
+            __syncthreads();
+            continue;
+        }
+        for (int x = t; x < ts; x += T) {
+            const uint32_t col = keys[x];
+            acc[x] = col == MCL_EMPTY ? 0 : mcl_key(mcl_power(acc[x] >> 30, P.a), col);
+        }
+        mcl_finish<T>(acc, ts, i, P, sc, ent_next + off_next[i], store[i], cnt_next, ctr);
+    }
+}
+// spill, step 1: the records of one batch of rows, a workgroup per row; the row's bound records start where the batch's cursor stood
+__global__ void __launch_bounds__(TPB) k_mcl_spill_emit(const int32_t* rows, const int64_t* row_bound, int64_t n_rows, const int64_t* off,
+                                                        const int32_t* cnt, const uint64_t* ent, unsigned long long* cursor, int64_t rec_cap,
+                                                        uint64_t* rkey, uint64_t* rval, unsigned long long* ctr) {
+    __shared__ unsigned long long first;
+    const int t = threadIdx.x;
+    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int32_t i = rows[r];
+        const int64_t b = row_bound[r];
+        if (t == 0) first = atomicAdd(cursor, (unsigned long long)b);
+        __syncthreads();
+        int64_t pos = (int64_t)first;
+        __syncthreads();
+        if (pos + b > rec_cap) { if (t == 0) atomicMax(ctr + MC_BAD, 1ull); continue; }
+        const int64_t o = off[i], end = pos + b;
+        for (int32_t e = 0, c = cnt[i]; e < c; ++e) {
+            const uint64_t ik = ent[o + e];
+            const uint32_t k = (uint32_t)(ik >> 32);
+            const uint64_t p = (uint32_t)ik;
+            const int64_t ok = off[k];
+            const int32_t ck = cnt[k];
+            for (int32_t j = t; j < ck && pos + j < end; j += TPB) {
+                const uint64_t kj = ent[ok + j];
+                rkey[pos + j] = (uint64_t)(uint32_t)i << 32 | (kj >> 32);
+                rval[pos + j] = p * (uint32_t)kj;
+            }
+            pos += ck;
+        }
+    }
+}
+// spill, step 2 (after the sort and reduce-by-key): the row's segment of the reduced records becomes its candidate array, in place
+__global__ void __launch_bounds__(TPB) k_mcl_spill_finish(const int32_t* rows, int64_t n_rows, const uint64_t* gkey, uint64_t* gval,
+                                                          const unsigned long long* n_groups, const mcl_dev P, const int64_t* off_next,
+                                                          const int64_t* store, int32_t* cnt_next, uint64_t* ent_next, unsigned long long* ctr) {
+    __shared__ mcl_scratch sc;
+    const int t = threadIdx.x;
+    const int64_t ng = (int64_t)*n_groups;
+    auto lower = [&](uint64_t key) { int64_t lo = 0, hi = ng; while (lo < hi) { const int64_t mid = lo + (hi - lo) / 2; if (gkey[mid] < key) lo = mid + 1; else hi = mid; } return lo; };
+    for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const int32_t i = rows[r];
+        const int64_t lo = lower((uint64_t)(uint32_t)i << 32), hi = lower(((uint64_t)(uint32_t)i + 1) << 32);
+        if (hi <= lo) { if (t == 0) atomicMax(ctr + MC_BAD, 1ull); continue; }      // (a row always has candidates)
+        for (int64_t x = lo + t; x < hi; x += TPB) gval[x] = mcl_key(mcl_power(gval[x] >> 30, P.a), (uint32_t)gkey[x]);
+        mcl_finish<TPB>(gval + lo, (int)(hi - lo), i, P, sc, ent_next + off_next[i], store[i], cnt_next, ctr);
+    }
+}
+// the last matrix: an undirected edge per entry off the diagonal for the hooking (larger end first: k_hook reads those), the
+// (row, column) keys of the CSR output if it is wanted, entries and widest row.  Storage between the rows stays as it was filled.
+__global__ void k_mcl_last(int64_t n, const int64_t* off, const int32_t* cnt, const uint64_t* ent, uint64_t* hook, uint64_t* ckey, uint32_t* cval,
+                           unsigned long long* tally) {
+    int nnz = 0; unsigned long long widest = 0;
+    GRID_STRIDE(i, n) {
+        const int64_t o = off[i];
+        const int32_t c = cnt[i];
+        for (int32_t e = 0; e < c; ++e) {
+            const uint64_t x = ent[o + e], col = x >> 32, row = (uint64_t)i;
+            hook[o + e] = col == row ? 0 : (col > row ? col << 32 | row : row << 32 | col);
+            if (ckey) { ckey[o + e] = row << 32 | col; cval[o + e] = (uint32_t)x; }
+        }
+        nnz += c; widest = umax64(widest, (uint64_t)c);
+    }
+    add_count(tally, nnz);
+    if (widest) atomicMax(tally + 1, widest);
+}
+
+void check_mcl_params(const std::string& fn, const vg_mcl_params* p) {
+    if (!p) throw vg_error(VG_EINVAL, fn + ": null parameters");
+    const double twice = 2 * p->inflation;
+    if (!(p->inflation >= 1.5 && p->inflation <= 6) || !(std::fabs(twice - (double)llrint(twice)) < 1e-9))
+        throw vg_error(VG_EINVAL, fn + ": inflation " + std::to_string(p->inflation) + " must be a multiple of 0.5 in [1.5, 6]");
+    if (!(p->prune >= 0 && p->prune <= 0.1)) throw vg_error(VG_EINVAL, fn + ": prune " + std::to_string(p->prune) + " must lie in [0, 0.1]");
+    if (p->max_row < 2 || p->max_row > 4096) throw vg_error(VG_EINVAL, fn + ": max_row " + std::to_string(p->max_row) + " must lie in [2, 4096]");
+    if (!(p->chaos_eps >= 0 && p->chaos_eps < 1)) throw vg_error(VG_EINVAL, fn + ": chaos_eps " + std::to_string(p->chaos_eps) + " must lie in [0, 1)");
+    if (p->max_iterations < 1 || p->max_iterations > 1000)
+        throw vg_error(VG_EINVAL, fn + ": max_iterations " + std::to_string(p->max_iterations) + " must lie in [1, 1000]");
+}
+
+// The plan of one iteration over M: row lists, the offsets and the storage of the next matrix; h = the read-back (with the chaos of
+// the expansion that produced M)
+struct mcl_plan {
+    dbuf<int64_t> bound, spill_bound, store, off_next; dbuf<int32_t> wave_rows, group_rows, spill_rows;
+    unsigned long long h[MC_N] = {};
+};
+void mcl_make_plan(int64_t n, const mcl_matrix& M, int slots, int max_row, dbuf<unsigned long long>& ctr, hipStream_t s, mcl_plan& pl) {
+    vg_prof_scope ps("cluster_mcl_plan", (double)n * 60.0);
+    pl.off_next.alloc((size_t)n);
+    VG_HIP(hipMemsetAsync(ctr.p + MC_WAVE, 0, (MC_N - MC_WAVE) * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_mcl_bound, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)M.off.p, (const int32_t*)M.cnt.p,
+                       (const uint64_t*)M.ent.p, pl.bound.p);
+    hipLaunchKernelGGL(k_mcl_classify, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)pl.bound.p, (int64_t)std::min(MCL_WAVE_SLOTS, slots),
+                       (int64_t)std::min(MCL_GROUP_SLOTS, slots), (int64_t)max_row, pl.wave_rows.p, pl.group_rows.p, pl.store.p, ctr.p);
+    with_temp_storage([&](void* tmp, size_t& tb) {
+        return rocprim::exclusive_scan(tmp, tb, pl.store.p, pl.off_next.p, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), s); });
+    VG_HIP(hipGetLastError());
+    ctr.download(pl.h, MC_N, s);
+    VG_HIP(hipStreamSynchronize(s));
+    if (pl.h[MC_BAD]) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: a row lost candidates (internal error)");
+    if ((int64_t)(pl.h[MC_WAVE] + pl.h[MC_GROUP]) != n) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: the row classes do not add up (internal error)");
+}
+
+// the ns spill rows of one iteration (the list the group kernel filled), in batches of at most MCL_SPILL_BATCH records
+void mcl_spill(int64_t n, int64_t ns, const mcl_matrix& M, mcl_matrix& N, const mcl_plan& pl, const mcl_dev& P, dbuf<unsigned long long>& ctr,
+               hipStream_t s) {
+    std::vector<int64_t> hb((size_t)ns);
+    pl.spill_bound.download(hb.data(), (size_t)ns, s);
+    VG_HIP(hipStreamSynchronize(s));
+    dbuf<unsigned long long> cursor(1), n_groups(1);
+    const unsigned key_bits = 32u + (unsigned)id_bits(n);
+    for (int64_t from = 0; from < ns;) {
+        int64_t to = from, recs = 0;
+        while (to < ns && (to == from || recs + hb[(size_t)to] <= MCL_SPILL_BATCH)) recs += hb[(size_t)to++];
+        const int64_t rows = to - from;
+        if (recs >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "vg_cluster_mcl_graph: one row has 2^31 or more candidates");
+        dbuf<uint64_t> rkey((size_t)recs), rval((size_t)recs), skey((size_t)recs), sval((size_t)recs);
+        {
+            vg_prof_scope ps("cluster_mcl_spill_emit", (double)recs * 24.0);
+            cursor.zero(s);
+            hipLaunchKernelGGL(k_mcl_spill_emit, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(TPB), 0, s, (const int32_t*)pl.spill_rows.p + from,
+                               (const int64_t*)pl.spill_bound.p + from, rows, (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p,
+                               cursor.p, recs, rkey.p, rval.p, ctr.p);
+        }
+        {
+            vg_prof_scope ps("cluster_mcl_spill_sort", (double)recs * (32.0 * 2.0 + 32.0));
+            with_temp_storage([&](void* tmp, size_t& tb) {
+                return rocprim::radix_sort_pairs(tmp, tb, rkey.p, skey.p, rval.p, sval.p, (size_t)recs, 0u, key_bits, s); });
+            with_temp_storage([&](void* tmp, size_t& tb) {       // -> (row, column, sum of products) in rkey / rval
+                return rocprim::reduce_by_key(tmp, tb, skey.p, sval.p, (size_t)recs, rkey.p, rval.p, n_groups.p, rocprim::plus<uint64_t>(),
+                                              rocprim::equal_to<uint64_t>(), s); });
+        }
+        {
+            vg_prof_scope ps("cluster_mcl_spill_finish", (double)recs * 16.0);
+            hipLaunchKernelGGL(k_mcl_spill_finish, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(TPB), 0, s, (const int32_t*)pl.spill_rows.p + from,
+                               rows, (const uint64_t*)rkey.p, rval.p, (const unsigned long long*)n_groups.p, P, (const int64_t*)N.off.p,
+                               (const int64_t*)pl.store.p, N.cnt.p, N.ent.p, ctr.p);
+        }
+        VG_HIP(hipGetLastError());
+        from = to;
+    }
+}
+
+void mcl_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, const vg_mcl_params& prm, int32_t* label,
+                   int32_t* representative, int64_t** m_off, int32_t** m_col, uint32_t** m_val, vg_mcl_stats& sts) {
+    hipStream_t s = vg_stream();
+    const mcl_dev P{ (int)llrint(2 * prm.inflation), (uint32_t)(uint64_t)std::floor(prm.prune * (double)MCL_ONE), prm.max_row };
+    const uint64_t eps = (uint64_t)std::floor(prm.chaos_eps * (double)MCL_ONE);
+    const int slots = g_mcl_slots.load() ? g_mcl_slots.load() : MCL_GROUP_SLOTS;
+    mcl_matrix M;
+    {
+        edge_graph eg;
+        build_edge_graph(n, q, r, w, n_rows, s, eg);
+        sts.n_edges = eg.m / 2;
+        dbuf<uint64_t> u((size_t)std::max<int64_t>(eg.m, 1));
+        M.off.alloc((size_t)n); M.cnt.alloc((size_t)n); M.ent.alloc((size_t)(eg.m + n));
+        vg_prof_scope ps("cluster_mcl_start", (double)eg.m * 28.0 + (double)n * 28.0);
+        hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(eg.m)), dim3(TPB), 0, s, (const double*)eg.uvals.p, eg.m, u.p);
+        hipLaunchKernelGGL(k_mcl_start, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)eg.off.p, (const int32_t*)eg.adj.p, (const uint64_t*)u.p,
+                           M.off.p, M.cnt.p, M.ent.p);
+        VG_HIP(hipGetLastError());
+    }
+    dbuf<unsigned long long> ctr(MC_N);
+    ctr.zero(s);
+    mcl_plan pl;
+    pl.bound.alloc((size_t)n); pl.spill_bound.alloc((size_t)n); pl.store.alloc((size_t)n);
+    pl.wave_rows.alloc((size_t)n); pl.group_rows.alloc((size_t)n); pl.spill_rows.alloc((size_t)n);
+    mcl_make_plan(n, M, slots, P.max_row, ctr, s, pl);
+    char note[128];
+    for (;;) {
+        const int64_t nw = (int64_t)pl.h[MC_WAVE], ng = (int64_t)pl.h[MC_GROUP];
+        mcl_matrix N;
+        N.off = std::move(pl.off_next); N.cnt.alloc((size_t)n); N.ent.alloc((size_t)std::max<int64_t>((int64_t)pl.h[MC_STORAGE], 1));
+        VG_HIP(hipMemsetAsync(ctr.p, 0, MC_WAVE * sizeof(unsigned long long), s));       // chaos and the guard flag
+        if (nw) {
+            vg_prof_scope ps("cluster_mcl_expand_wave", (double)nw * 512.0);
+            hipLaunchKernelGGL((k_mcl_expand<64, MCL_WAVE_SLOTS>), dim3((unsigned)std::min<int64_t>(nw, 1 << 20)), dim3(64), 0, s, n, (const int32_t*)pl.wave_rows.p, nw,
+                               (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p, (const int64_t*)pl.bound.p,
+                               std::min(MCL_WAVE_SLOTS, slots), P, (const int64_t*)N.off.p, (const int64_t*)pl.store.p, N.cnt.p, N.ent.p,
+                               pl.spill_rows.p, pl.spill_bound.p, ctr.p);
+        }
+        if (ng) {
+            vg_prof_scope ps("cluster_mcl_expand_group", (double)ng * 16384.0);
+            hipLaunchKernelGGL((k_mcl_expand<TPB, MCL_GROUP_SLOTS>), dim3((unsigned)std::min<int64_t>(ng, 1 << 20)), dim3(TPB), 0, s, n, (const int32_t*)pl.group_rows.p, ng,
+                               (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p, (const int64_t*)pl.bound.p,
+                               std::min(MCL_GROUP_SLOTS, slots), P, (const int64_t*)N.off.p, (const int64_t*)pl.store.p, N.cnt.p, N.ent.p,
+                               pl.spill_rows.p, pl.spill_bound.p, ctr.p);
+        }
+        VG_HIP(hipGetLastError());
+        int64_t ns = 0;
+        if (pl.h[MC_TRY]) {                                     // rows were tried above their bound: how many did the table not hold?
+            unsigned long long given_up = 0;
+            vg_download_bytes(&given_up, ctr.p + MC_SPILL, sizeof given_up, s);
+            VG_HIP(hipStreamSynchronize(s));
+            ns = (int64_t)given_up;
+            if (ns > (int64_t)pl.h[MC_TRY]) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: more spill rows than rows above the table (internal error)");
+        }
+        if (ns) mcl_spill(n, ns, M, N, pl, P, ctr, s);
+        M = std::move(N);
+        ++sts.iterations; sts.lds_rows += n - ns; sts.spill_rows += ns;
+        mcl_make_plan(n, M, slots, P.max_row, ctr, s, pl);       // (also the read-back of this iteration's chaos)
+        sts.chaos = pl.h[MC_CHAOS];
+        snprintf(note, sizeof note, "mcl iteration %lld: chaos %llu, %lld + %lld LDS rows, %lld spill rows", (long long)sts.iterations,
+                 (unsigned long long)sts.chaos, (long long)nw, (long long)(ng - ns), (long long)ns);
+        vg_host_mark(note);
+        if (sts.chaos <= eps) { sts.converged = 1; break; }
+        if (sts.iterations >= prm.max_iterations) break;
+    }
+    // ---- clusters: the components of the last matrix, labelled as single linkage labels them; the matrix itself if it is wanted
+    const int64_t storage = (int64_t)M.ent.n;
+    const bool want = m_off != nullptr;
+    edge_graph hg;
+    hg.ukeys.alloc((size_t)storage); hg.m = storage;
+    dbuf<uint64_t> ckey, ckey2; dbuf<uint32_t> cval, cval2; dbuf<unsigned long long> tally(2);
+    unsigned long long ht[2] = {};
+    {
+        vg_prof_scope ps("cluster_mcl_last", (double)storage * 28.0);
+        hg.ukeys.zero(s); tally.zero(s);
+        if (want) {
+            ckey.alloc((size_t)storage); ckey2.alloc((size_t)storage); cval.alloc((size_t)storage); cval2.alloc((size_t)storage);
+            VG_HIP(hipMemsetAsync(ckey.p, 0xff, ckey.bytes(), s));
+            cval.zero(s);
+        }
+        hipLaunchKernelGGL(k_mcl_last, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p,
+                           hg.ukeys.p, ckey.p, cval.p, tally.p);
+        VG_HIP(hipGetLastError());
+        tally.download(ht, 2, s);
+        VG_HIP(hipStreamSynchronize(s));
+    }
+    sts.nnz = (int64_t)ht[0]; sts.max_row_seen = (int64_t)ht[1];
+    if (sts.nnz < n || sts.nnz > storage) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: the last matrix is inconsistent (internal error)");
+    dbuf<int32_t> root((size_t)n), d_label, d_rep;
+    vg_cluster_stats cs{};
+    single_on_device(n, hg, s, root, cs);
+    VG_HIP(hipGetLastError());
+    check_roots(n, root, s);
+    labels_on_device(n, root, false, s, d_label, d_rep);
+    VG_HIP(hipGetLastError());
+    d_label.download(label, (size_t)n, s);
+    d_rep.download(representative, (size_t)n, s);
+    VG_HIP(hipStreamSynchronize(s));
+    if (!want) return;
+    // the entries sorted by (row, column); the unused storage (keys of all ones) sorts behind them
+    vg_prof_scope ps("cluster_mcl_matrix", (double)storage * (12.0 * 2.0 * 2.0));
+    with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, ckey.p, ckey2.p, cval.p, cval2.p, (size_t)storage, 0u, 64u, s); });
+    dbuf<int64_t> d_off((size_t)n + 1); dbuf<int32_t> d_col((size_t)sts.nnz);
+    hipLaunchKernelGGL(k_csr, dim3(grid_of(sts.nnz + 1)), dim3(TPB), 0, s, (const uint64_t*)ckey2.p, sts.nnz, n, d_off.p, d_col.p);
+    VG_HIP(hipGetLastError());
+    *m_off = (int64_t*)malloc(sizeof(int64_t) * ((size_t)n + 1));
+    *m_col = (int32_t*)malloc(sizeof(int32_t) * (size_t)sts.nnz);
+    *m_val = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)sts.nnz);
+    if (!*m_off || !*m_col || !*m_val) throw vg_error(VG_ENOMEM, "out of host memory");
+    d_off.download(*m_off, (size_t)n + 1, s); d_col.download(*m_col, (size_t)sts.nnz, s); cval2.download(*m_val, (size_t)sts.nnz, s);
+    VG_HIP(hipStreamSynchronize(s));
+}
+}  // namespace
+
+extern "C" void vg_cluster_mcl_set_table_slots(int slots) {
+    int v = 0;
+    if (slots > 0) { v = 16; while (v < MCL_GROUP_SLOTS && v * 2 <= slots) v *= 2; }      // the power of two below, in 16..4096
+    g_mcl_slots.store(v);
+}
+
+extern "C" int vg_cluster_mcl_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
+                                    const vg_mcl_params* params, int32_t* label, int32_t* representative, int64_t** m_off, int32_t** m_col,
+                                    uint32_t** m_val, vg_mcl_stats* stats) {
+    const bool want = m_off || m_col || m_val;
+    if (m_off) *m_off = nullptr;
+    if (m_col) *m_col = nullptr;
+    if (m_val) *m_val = nullptr;
+    try {
+        const char* fn = "vg_cluster_mcl_graph";
+        check_rows(fn, n_objects, q, r, w, n_rows);
+        if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, std::string(fn) + ": null output");
+        if (want && (!m_off || !m_col || !m_val)) throw vg_error(VG_EINVAL, std::string(fn) + ": the matrix outputs are all three or none");
+        check_mcl_params(fn, params);
+        check_row_values(fn, n_objects, q, r, w, n_rows);
+        check_unit_weights(fn, w, n_rows, 0.0, "Markov clustering");
+        vg_mcl_stats st_local{}; vg_mcl_stats& sts = stats ? *stats : st_local;
+        sts = vg_mcl_stats{};
+        if (n_objects == 0) {
+            if (want && !(*m_off = (int64_t*)calloc(1, sizeof(int64_t)))) throw vg_error(VG_ENOMEM, "out of host memory");
+            return VG_OK;
+        }
+        vg_require_device();
+        mcl_on_device(n_objects, q, r, w, n_rows, *params, label, representative, want ? m_off : nullptr, m_col, m_val, sts);
+    } catch (...) {
+        // (nothing half-filled leaves the call; the error itself is reported below)
+        if (want && m_off && m_col && m_val) { free(*m_off); free(*m_col); free(*m_val); *m_off = nullptr; *m_col = nullptr; *m_val = nullptr; }
+        VG_API_BEGIN throw; VG_API_END
+    }
+    return VG_OK;
 }

@@ -6,7 +6,8 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions, DedupParams, LzParams, PrefilterParams, check
+from ._lib import (CLUSTER_ALGORITHMS, FLOW_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions,
+                   DedupParams, LzParams, MclParams, MclStats, PrefilterParams, check)
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -63,6 +64,8 @@ def align(paths, out_path, is_multifasta, columns, filter_path=None, filter_thre
 
 
 CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
+# the keywords of cluster() that belong to algorithm='mcl', with the library's defaults
+MCL_DEFAULTS = dict(mcl_inflation=2.0, mcl_prune=1e-4, mcl_max_row=128, mcl_chaos_eps=1e-3, mcl_iterations=100)
 
 
 def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num_alns=0, representatives=False,
@@ -76,11 +79,17 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     a run at that minimum: the rows between the two still count in the averages.  prior_path: a clusters.tsv of an earlier run
     whose clusters are taken as given and to which the other objects of the ids file are added (vg_cluster_update; algorithm
     'single', 'cd-hit' or 'uclust', no out_linkage and no levels); prior_repr: its second column holds representative ids.  That
-    call returns the update's counts as a dict, every other one None."""
+    call returns the update's counts as a dict.  algorithm='mcl': Markov clustering (vg_cluster_mcl; DESIGN.md section 9, "Markov
+    clustering"), deterministic, with the keywords mcl_inflation (a multiple of 0.5 in [1.5, 6]), mcl_prune, mcl_max_row,
+    mcl_chaos_eps and mcl_iterations; it excludes prior_path, out_linkage and levels and returns its stats as a dict (iterations,
+    converged, chaos, ...).  Every other call returns None."""
+    mcl = {k: mins.pop(k) for k in list(mins) if k in MCL_DEFAULTS}
     unknown = set(mins) - set(CLUSTER_FILTERS)
     if unknown:
         raise TypeError(f'unknown filter(s): {sorted(unknown)}')
-    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS}
+    if mcl and algorithm not in FLOW_ALGORITHMS:
+        raise ValueError(f'{", ".join(sorted(mcl))}: only with algorithm=\'mcl\'')
+    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
     if prior_path is None and prior_repr:
         raise ValueError('prior_repr needs prior_path')
     if prior_path is not None:
@@ -100,6 +109,12 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
         check(_lib.load().vg_cluster_update(paths[0], paths[1], os.fsencode(str(prior_path)), int(bool(prior_repr)), paths[2], C.byref(p),
                                             C.byref(st)))
         return {name: getattr(st, name) for name, _ in ClusterUpdateStats._fields_}
+    if algorithm in FLOW_ALGORITHMS and out_linkage is None and levels is None:
+        m = {**MCL_DEFAULTS, **mcl}
+        prm = MclParams(float(m['mcl_inflation']), float(m['mcl_prune']), float(m['mcl_chaos_eps']), int(m['mcl_max_row']), int(m['mcl_iterations']))
+        st = MclStats()
+        check(_lib.load().vg_cluster_mcl(*paths, C.byref(p), C.byref(prm), C.byref(st)))
+        return {name: getattr(st, name) for name, _ in MclStats._fields_}
     if out_linkage is None and levels is None:
         check(_lib.load().vg_cluster(*paths, C.byref(p)))
         return
