@@ -408,7 +408,8 @@ def cluster_call(args):
     """What the front-end hands to vg_cluster for validated cluster arguments -- the counterpart of cmd_clusty
     (vclust.py:1184-1278): a minimum only for values > 0, the num_alns maximum only for values > 0.  With --prior the call
     also carries prior_path and prior_repr, and goes to vg_cluster_update."""
-    mins = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio') if getattr(args, k) > 0}
+    from .stages import CLUSTER_FILTERS
+    mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
     call = dict(ani_path=args.input_path, ids_path=args.ids_path, out_path=args.output_path, algorithm=args.algorithm,
                 metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives, **mins)
     if getattr(args, 'linkage_path', None) is not None:
@@ -424,10 +425,11 @@ def cluster_call(args):
     return call
 
 
-def handle_cluster(args, parser, logger):
-    """`cluster`: bin/clusty where it exists and computes what is asked; the library otherwise, and always for the merge table,
-    its cuts, average linkage, Markov clustering and --prior.  --prior adds the genomes of --ids that the earlier clusters.tsv does not list to its
-    clusters (the ids file and the rows are those of an `align --db` run; DESIGN.md section 9, "Update of a prior clustering")."""
+def validate_args_cluster(args, parser):
+    """The checks of `cluster`, and who computes it: args.native is set where the library does -- always for the merge table, its
+    cuts, average linkage, Markov clustering and --prior, and for single / cd-hit / uclust / set-cover where there is no bin/clusty
+    (vg_cluster).  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and goes to Clusty, which must
+    then exist."""
     from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS
     linkage_path, levels = getattr(args, 'linkage_path', None), getattr(args, 'levels', None)
     hierarchy = linkage_path is not None or bool(levels)
@@ -458,30 +460,45 @@ def handle_cluster(args, parser, logger):
             parser.error(f'--mcl-max-row {args.mcl_max_row} must lie between 2 and 4096.')
         if not 1 <= args.mcl_iterations <= 1000:
             parser.error(f'--mcl-iterations {args.mcl_iterations} must lie between 1 and 1000.')
-    if hierarchy or prior_path is not None or args.algorithm == 'average' or mcl or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS):
-        # no Clusty: single / cd-hit / uclust / set-cover run on the GPU (vg_cluster); the merge table and
-        # its cuts (which Clusty does not have) always do, for every hierarchy, and so does average linkage, which Clusty does
-        # not have either, --prior and Markov clustering.  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and still goes
-        # to Clusty below.
-        if not vars(args).get(args.metric, 0):
-            parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+    args.native = (hierarchy or prior_path is not None or args.algorithm == 'average' or mcl
+                   or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS))
+    if not args.native:
+        _require_binary(BIN_CLUSTY)
+    if not vars(args).get(args.metric, 0):
+        parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+    return args
+
+
+def _cluster_description(args, call):
+    """The library's clustering for the 'Running:' line, in the words of the command line."""
+    from .stages import CLUSTER_FILTERS
+    levels, linkage_path, prior_path = getattr(args, 'levels', None), getattr(args, 'linkage_path', None), getattr(args, 'prior_path', None)
+    return (f'libvclust_gpu cluster --algorithm {args.algorithm}' + (f' --mcl-inflation {args.mcl_inflation:g}' if args.algorithm == 'mcl' else '')
+            + f' --metric {args.metric}' + ''.join(f' --{k} {v}' for k, v in call.items() if k in CLUSTER_FILTERS)
+            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
+            + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
+            + (f' --out-linkage {linkage_path}' if linkage_path is not None else '')
+            + (f' --prior {prior_path}' + (' --prior-repr' if args.prior_repr else '') if prior_path is not None else '')
+            + f' [1 GPU] -> {args.output_path}')
+
+
+def handle_cluster(args, parser, logger):
+    """`cluster`: bin/clusty where it exists and computes what is asked, the library otherwise (validate_args_cluster).  --prior adds
+    the genomes of --ids that the earlier clusters.tsv does not list to its clusters (the ids file and the rows are those of an
+    `align --db` run; DESIGN.md section 9, "Update of a prior clustering")."""
+    args = validate_args_cluster(args, parser)
+    if args.native:
         from . import stages
         call = cluster_call(args)
-        desc = (f'libvclust_gpu cluster --algorithm {args.algorithm}' + (f' --mcl-inflation {args.mcl_inflation:g}' if mcl else '') + f' --metric {args.metric}'
-                + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
-                + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
-                + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
-                + (f' --out-linkage {linkage_path}' if linkage_path is not None else '')
-                + (f' --prior {prior_path}' + (' --prior-repr' if args.prior_repr else '') if prior_path is not None else '')
-                + f' [1 GPU] -> {args.output_path}')
         counts = []
-        run_native(desc, lambda: counts.append(stages.cluster(verbosity=args.verbosity_level, **call)), args.verbosity_level, logger)
-        if prior_path is not None:
+        run_native(_cluster_description(args, call), lambda: counts.append(stages.cluster(verbosity=args.verbosity_level, **call)),
+                   args.verbosity_level, logger)
+        if getattr(args, 'prior_path', None) is not None:
             c = counts[0]
             logger.info(f'Prior clustering updated: {c["n_prior"]} prior + {c["n_new"]} new genomes, {c["n_edges"]} kept edges; new genomes: '
                         f'{c["joined_prior"]} joined a prior cluster, {c["joined_new"]} joined a new one, {c["founded"]} founded a cluster; '
                         f'{c["prior_merged"]} prior cluster(s) merged away')
-        if mcl:
+        if args.algorithm == 'mcl':
             c = counts[0]
             with open(args.output_path) as f:
                 labels = {line.split('\t')[1] for line in f.read().split('\n')[1:] if line}
@@ -490,13 +507,10 @@ def handle_cluster(args, parser, logger):
                 logger.warning(f'MCL did not converge within --mcl-iterations {args.mcl_iterations}: the clusters are those of the last iterate')
         cluster_report(args, logger)
         return
-    _require_binary(BIN_CLUSTY)
-    threshold = vars(args).get(args.metric, 0)
-    if not threshold:
-        parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+    from .stages import CLUSTER_FILTERS
     cmd = [str(BIN_CLUSTY), '--objects-file', str(args.ids_path), '--algo', args.algorithm, '--id-cols', 'qidx', 'ridx',
            '--distance-col', args.metric, '--similarity', '--numeric-ids']
-    for name in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio'):
+    for name in CLUSTER_FILTERS:
         if getattr(args, name) > 0:
             cmd += ['--min', name, str(getattr(args, name))]
     if args.num_alns > 0:
@@ -514,7 +528,8 @@ def handle_cluster(args, parser, logger):
 def cluster_stats_call(args):
     """What the front-end hands to vg_cluster_stats_file for validated cluster arguments: the filters and the metric of the
     clustering itself (cluster_call), the clusters.tsv just written, and whether it holds representative ids."""
-    mins = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio') if getattr(args, k) > 0}
+    from .stages import CLUSTER_FILTERS
+    mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
     return dict(ani_path=args.input_path, ids_path=args.ids_path, clusters_path=args.output_path, out_path=args.stats_path,
                 clusters_repr=bool(args.representatives), metric=args.metric, num_alns=max(args.num_alns, 0), **mins)
 

@@ -1,11 +1,14 @@
-// vg_api.cpp — the two whole-stage entry points the reference's front-end needs:
-//   vg_prefilter  replaces kmer-db build + all2all + distance (vclust.py:1433-1471)
-//   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521)
-//   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557)
-//   vg_cluster_mcl       the same parse, then Markov clustering (vg_cluster_mcl_graph)
-//   vg_cluster_linkage   the same parse, then the single-, complete- or average-linkage merge table and its cuts at several levels
-//   vg_cluster_stats_file   the same parse and a clusters.tsv read back, then the per-cluster report of every label column
-// Both are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
+// vg_api.cpp — the whole-stage entry points, files in and files out.  The three the reference's front-end needs:
+//   vg_prefilter  replaces kmer-db build + all2all + distance (vclust.py:1433-1471); vg_prefilter_new: new genomes against a database
+//   vg_align      replaces lz-ani all2all                    (vclust.py:1497-1521); vg_align_new: likewise
+//   vg_cluster    replaces clusty for single / cd-hit / uclust / set-cover (vclust.py:1539-1557), and the floor cut of complete and
+//                 average linkage
+// and four more on the parse of vg_cluster (cluster_stage):
+//   vg_cluster_mcl          Markov clustering (vg_cluster_mcl_graph)
+//   vg_cluster_update       a prior clusters.tsv read back, then its clusters extended by the new objects (vg_cluster_update_graph)
+//   vg_cluster_linkage      the single-, complete- or average-linkage merge table and its cuts at several levels
+//   vg_cluster_stats_file   a clusters.tsv read back, then the per-cluster report of every label column
+// All are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
 #include "vg_common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -173,46 +176,67 @@ static double metric_floor(const vg_cluster_params* p) {
     return !strcmp(p->metric, "tani") ? p->min_tani : !strcmp(p->metric, "gani") ? p->min_gani : p->min_ani;
 }
 
-// The opening of vg_cluster and vg_cluster_linkage (`fn` names the caller in the error texts): the metric, the levels if any (none
-// may lie below the metric's minimum), then both files parsed beside the creation of the HIP context.
-struct cluster_input { std::vector<std::string> ids; std::vector<uint32_t> q, r; std::vector<double> w; };
-static void read_cluster_input(const std::string& fn, const char* ani_path, const char* ids_path, const vg_cluster_params* p,
-                               const double* levels, int n_levels, cluster_input& in) {
+// The skeleton of the file-level cluster entries, each of which checks its own null arguments and its algorithm first (`fn` names
+// the entry in the error texts): the metric, the levels if any (none may lie below the metric's minimum), both files parsed beside
+// the creation of the HIP context, then the entry's parts --
+//   compute(in)    its further input (the prior clustering, the clusters file) and the array-level call, marked `computed`
+//   write(in)      the output files
+//   summary(in)    the line on stderr at verbosity 2
+struct cluster_input {
+    std::vector<std::string> ids; std::vector<uint32_t> q, r; std::vector<double> w;
+    int64_t n() const { return (int64_t)ids.size(); }
+    int64_t n_rows() const { return (int64_t)q.size(); }
+};
+template <class Compute, class Write, class Summary>
+static void cluster_stage(const std::string& fn, const char* ani_path, const char* ids_path, const vg_cluster_params* p, const double* levels,
+                          int n_levels, const char* computed, Compute compute, Write write, Summary summary) {
     if (strcmp(p->metric, "tani") && strcmp(p->metric, "gani") && strcmp(p->metric, "ani"))
         throw vg_error(VG_EINVAL, fn + ": metric must be tani, gani or ani, not " + p->metric);
     for (int l = 0; l < n_levels; ++l)
         if (!(levels[l] >= metric_floor(p)))          // (also a NaN)
             throw vg_error(VG_EINVAL, fn + ": level " + std::to_string(levels[l]) + " is below the " + p->metric + " minimum (rows below it are not edges)");
     vg_host_mark((fn + ": enter").c_str());
-    device_warmup warm(WARM_CLUSTER);         // (the HIP context is created beside the parse)
-    vg_cluster_read_ids(ids_path, in.ids);
-    if ((int64_t)in.ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
-    vg_cluster_read_rows(ani_path, (int64_t)in.ids.size(), p, in.q, in.r, in.w);
-    vg_host_mark("ani.tsv parsed");
-    warm.join();
+    cluster_input in;
+    {
+        device_warmup warm(WARM_CLUSTER);     // (the HIP context is created beside the parse)
+        vg_cluster_read_ids(ids_path, in.ids);
+        if (in.n() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
+        vg_cluster_read_rows(ani_path, in.n(), p, in.q, in.r, in.w);
+        vg_host_mark("ani.tsv parsed");
+    }
+    compute(in);
+    vg_host_mark(computed);
+    write(in);
+    if (p->verbosity >= 2) summary(in);
+}
+// ... of the three entries that write one partition: compute(in, label, rep) fills what vg_cluster_write puts out
+template <class Compute, class Summary>
+static void partition_stage(const char* fn, const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p,
+                            Compute compute, Summary summary) {
+    std::vector<int32_t> label, rep;
+    cluster_stage(fn, ani_path, ids_path, p, nullptr, 0, "clusters computed", [&](const cluster_input& in) {
+        label.resize((size_t)std::max<int64_t>(in.n(), 1)); rep.resize(label.size());
+        compute(in, label.data(), rep.data());
+    }, [&](const cluster_input& in) { vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0); }, summary);
 }
 
 extern "C" int vg_cluster(const char* ani_path, const char* ids_path, const char* out_path, const vg_cluster_params* p) {
     VG_API_BEGIN
     if (!ani_path || !ids_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster: null argument");
     if (p->algorithm < VG_CLUSTER_SINGLE || p->algorithm > VG_CLUSTER_AVERAGE) throw vg_error(VG_EINVAL, "vg_cluster: unknown algorithm");
-    cluster_input in;
-    read_cluster_input("vg_cluster", ani_path, ids_path, p, nullptr, 0, in);
-    const int64_t n = (int64_t)in.ids.size();
-    std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
     vg_cluster_stats st{};
-    if (p->algorithm == VG_CLUSTER_AVERAGE) {                   // the average-linkage hierarchy down to the metric's minimum, every merge joined
-        vg_forest f;
-        vg_cluster_forest("vg_cluster", n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), f, VG_CLUSTER_AVERAGE, metric_floor(p));
-        vg_forest_cut(n, f, -HUGE_VAL, label.data(), rep.data());
-        st.rounds = f.stats.rounds; st.n_edges = f.stats.n_edges;
-    } else
-    check(vg_cluster_graph(n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), p->algorithm, label.data(), rep.data(), &st));
-    vg_host_mark("clusters computed");
-    vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0);
-    if (p->verbosity >= 2)
+    partition_stage("vg_cluster", ani_path, ids_path, out_path, p, [&](const cluster_input& in, int32_t* label, int32_t* rep) {
+        if (p->algorithm == VG_CLUSTER_AVERAGE) {               // the average-linkage hierarchy down to the metric's minimum, every merge joined
+            vg_forest f;
+            vg_cluster_forest("vg_cluster", in.n(), in.q.data(), in.r.data(), in.w.data(), in.n_rows(), f, VG_CLUSTER_AVERAGE, metric_floor(p));
+            vg_forest_cut(in.n(), f, -HUGE_VAL, label, rep);
+            st.rounds = f.stats.rounds; st.n_edges = f.stats.n_edges;
+        } else
+            check(vg_cluster_graph(in.n(), in.q.data(), in.r.data(), in.w.data(), in.n_rows(), p->algorithm, label, rep, &st));
+    }, [&](const cluster_input& in) {
         fprintf(stderr, "vg_cluster: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld objects by the tail sweep\n",
-                (long long)n, (long long)in.q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+                (long long)in.n(), (long long)in.n_rows(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+    });
     VG_API_END
 }
 
@@ -222,20 +246,15 @@ extern "C" int vg_cluster_mcl(const char* ani_path, const char* ids_path, const 
     if (!ani_path || !ids_path || !out_path || !p || !p->metric || !params) throw vg_error(VG_EINVAL, "vg_cluster_mcl: null argument");
     if (p->algorithm != VG_CLUSTER_MCL) throw vg_error(VG_EINVAL, "vg_cluster_mcl: the algorithm must be VG_CLUSTER_MCL");
     if (stats) *stats = vg_mcl_stats{};
-    cluster_input in;
-    read_cluster_input("vg_cluster_mcl", ani_path, ids_path, p, nullptr, 0, in);
-    const int64_t n = (int64_t)in.ids.size();
-    std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
     vg_mcl_stats st{};
-    check(vg_cluster_mcl_graph(n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), params, label.data(), rep.data(), nullptr, nullptr,
-                               nullptr, &st));
-    vg_host_mark("clusters computed");
-    vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0);
-    if (stats) *stats = st;
-    if (p->verbosity >= 2)
+    partition_stage("vg_cluster_mcl", ani_path, ids_path, out_path, p, [&](const cluster_input& in, int32_t* label, int32_t* rep) {
+        check(vg_cluster_mcl_graph(in.n(), in.q.data(), in.r.data(), in.w.data(), in.n_rows(), params, label, rep, nullptr, nullptr, nullptr, &st));
+    }, [&](const cluster_input& in) {
         fprintf(stderr, "vg_cluster_mcl: %lld objects, %lld rows passed, %lld edges, %lld iterations (%s), %lld entries, %lld LDS + %lld spill rows\n",
-                (long long)n, (long long)in.q.size(), (long long)st.n_edges, (long long)st.iterations, st.converged ? "converged" : "not converged",
+                (long long)in.n(), (long long)in.n_rows(), (long long)st.n_edges, (long long)st.iterations, st.converged ? "converged" : "not converged",
                 (long long)st.nnz, (long long)st.lds_rows, (long long)st.spill_rows);
+    });
+    if (stats) *stats = st;
     VG_API_END
 }
 
@@ -246,21 +265,17 @@ extern "C" int vg_cluster_update(const char* ani_path, const char* ids_path, con
     if (p->algorithm != VG_CLUSTER_SINGLE && p->algorithm != VG_CLUSTER_CDHIT && p->algorithm != VG_CLUSTER_UCLUST)
         throw vg_error(VG_EINVAL, "vg_cluster_update: the update of a prior clustering is single, cd-hit or uclust");
     if (stats) *stats = vg_cluster_update_stats{};
-    cluster_input in;
-    read_cluster_input("vg_cluster_update", ani_path, ids_path, p, nullptr, 0, in);
     std::vector<int32_t> prior;
-    vg_cluster_read_prior(prior_path, in.ids, prior_is_repr != 0, prior);
-    vg_host_mark("prior clusters parsed");
-    const int64_t n = (int64_t)in.ids.size();
-    std::vector<int32_t> label((size_t)std::max<int64_t>(n, 1)), rep((size_t)std::max<int64_t>(n, 1));
     vg_cluster_update_stats st{};
-    check(vg_cluster_update_graph(n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), p->algorithm, prior.data(), label.data(), rep.data(), &st));
-    vg_host_mark("clusters computed");
-    vg_cluster_write(out_path, in.ids, label.data(), rep.data(), p->representatives != 0);
-    if (stats) *stats = st;
-    if (p->verbosity >= 2)
+    partition_stage("vg_cluster_update", ani_path, ids_path, out_path, p, [&](const cluster_input& in, int32_t* label, int32_t* rep) {
+        vg_cluster_read_prior(prior_path, in.ids, prior_is_repr != 0, prior);
+        vg_host_mark("prior clusters parsed");
+        check(vg_cluster_update_graph(in.n(), in.q.data(), in.r.data(), in.w.data(), in.n_rows(), p->algorithm, prior.data(), label, rep, &st));
+    }, [&](const cluster_input& in) {
         fprintf(stderr, "vg_cluster_update: %lld prior + %lld new objects, %lld rows passed, %lld kept edges, %lld rounds, %lld objects by the tail sweep\n",
-                (long long)st.n_prior, (long long)st.n_new, (long long)in.q.size(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+                (long long)st.n_prior, (long long)st.n_new, (long long)in.n_rows(), (long long)st.n_edges, (long long)st.rounds, (long long)st.sweep_objects);
+    });
+    if (stats) *stats = st;
     VG_API_END
 }
 
@@ -268,24 +283,24 @@ extern "C" int vg_cluster_stats_file(const char* ani_path, const char* ids_path,
                                      const vg_cluster_params* p, const char* out_path) {
     VG_API_BEGIN
     if (!ani_path || !ids_path || !clusters_path || !out_path || !p || !p->metric) throw vg_error(VG_EINVAL, "vg_cluster_stats_file: null argument");
-    cluster_input in;
-    read_cluster_input("vg_cluster_stats_file", ani_path, ids_path, p, nullptr, 0, in);
     vg_label_columns cols;
-    vg_cluster_read_columns(clusters_path, in.ids, clusters_is_repr != 0, cols);
-    vg_host_mark("clusters.tsv parsed");
-    const size_t nc = cols.names.size();
-    std::vector<std::vector<vg_cluster_stat>> stats(nc);
-    std::vector<const int32_t*> label(nc); std::vector<int64_t> n_clusters(nc); std::vector<vg_cluster_stat*> out(nc);
-    for (size_t c = 0; c < nc; ++c) {
-        stats[c].resize(cols.text[c].size());
-        label[c] = cols.label[c].data(); n_clusters[c] = (int64_t)cols.text[c].size(); out[c] = stats[c].data();
-    }
-    vg_cluster_stats_run("vg_cluster_stats_file", (int64_t)in.ids.size(), in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), (int)nc,
-                         label.data(), n_clusters.data(), out.data(), nullptr, nullptr, nullptr);
-    vg_host_mark("cluster report computed");
-    vg_cluster_stats_write(out_path, p->metric, in.ids, cols, stats);
-    if (p->verbosity >= 2)
-        fprintf(stderr, "vg_cluster_stats_file: %lld objects, %lld rows passed, %d label column(s)\n", (long long)in.ids.size(), (long long)in.q.size(), (int)nc);
+    std::vector<std::vector<vg_cluster_stat>> stats;
+    cluster_stage("vg_cluster_stats_file", ani_path, ids_path, p, nullptr, 0, "cluster report computed", [&](const cluster_input& in) {
+        vg_cluster_read_columns(clusters_path, in.ids, clusters_is_repr != 0, cols);
+        vg_host_mark("clusters.tsv parsed");
+        const size_t nc = cols.names.size();
+        stats.resize(nc);
+        std::vector<const int32_t*> label(nc); std::vector<int64_t> n_clusters(nc); std::vector<vg_cluster_stat*> out(nc);
+        for (size_t c = 0; c < nc; ++c) {
+            stats[c].resize(cols.text[c].size());
+            label[c] = cols.label[c].data(); n_clusters[c] = (int64_t)cols.text[c].size(); out[c] = stats[c].data();
+        }
+        vg_cluster_stats_run("vg_cluster_stats_file", in.n(), in.q.data(), in.r.data(), in.w.data(), in.n_rows(), (int)nc, label.data(),
+                             n_clusters.data(), out.data(), nullptr, nullptr, nullptr);
+    }, [&](const cluster_input& in) { vg_cluster_stats_write(out_path, p->metric, in.ids, cols, stats); },
+    [&](const cluster_input& in) {
+        fprintf(stderr, "vg_cluster_stats_file: %lld objects, %lld rows passed, %d label column(s)\n", (long long)in.n(), (long long)in.n_rows(), (int)cols.names.size());
+    });
     VG_API_END
 }
 
@@ -296,31 +311,31 @@ extern "C" int vg_cluster_linkage(const char* ani_path, const char* ids_path, co
         throw vg_error(VG_EINVAL, "vg_cluster_linkage: null argument");
     if (p->algorithm != VG_CLUSTER_SINGLE && p->algorithm != VG_CLUSTER_COMPLETE && p->algorithm != VG_CLUSTER_AVERAGE)
         throw vg_error(VG_EINVAL, "vg_cluster_linkage: the merge table is single, complete or average linkage (algorithm must be one of the three)");
-    cluster_input in;
-    read_cluster_input("vg_cluster_linkage", ani_path, ids_path, p, levels, n_levels, in);
-    const int64_t n = (int64_t)in.ids.size();
     vg_forest f;
-    vg_cluster_forest("vg_cluster_linkage", n, in.q.data(), in.r.data(), in.w.data(), (int64_t)in.q.size(), f, p->algorithm, metric_floor(p));
-    vg_host_mark("forest computed");
-    // column 0: every merge (the cut at the floor, i.e. the algorithm on the passing rows); then one cut per level
-    const size_t cols = (size_t)n_levels + 1, stride = (size_t)std::max<int64_t>(n, 1);
-    std::vector<int32_t> label(cols * stride), rep(cols * stride);
-    std::vector<std::string> names = { "cluster" };
-    std::vector<const int32_t*> lab_col, rep_col;
-    for (size_t c = 0; c < cols; ++c) {
-        vg_forest_cut(n, f, c ? levels[c - 1] : -HUGE_VAL, label.data() + c * stride, rep.data() + c * stride);
-        lab_col.push_back(label.data() + c * stride); rep_col.push_back(rep.data() + c * stride);
-        if (c) { char buf[64]; snprintf(buf, sizeof buf, "%g", levels[c - 1]); names.push_back(std::string(p->metric) + "_" + buf); }
-    }
-    if (linkage_path) {
-        const size_t nf = std::max<size_t>(f.a.size(), 1);
-        std::vector<int64_t> node_a(nf), node_b(nf), size(nf);
-        vg_forest_table(n, f, node_a.data(), node_b.data(), size.data());
-        vg_linkage_write(linkage_path, f, node_a.data(), node_b.data(), size.data());
-    }
-    vg_cluster_write_columns(out_path, in.ids, names, lab_col, rep_col, p->representatives != 0);
-    if (p->verbosity >= 2)
+    cluster_stage("vg_cluster_linkage", ani_path, ids_path, p, levels, n_levels, "forest computed", [&](const cluster_input& in) {
+        vg_cluster_forest("vg_cluster_linkage", in.n(), in.q.data(), in.r.data(), in.w.data(), in.n_rows(), f, p->algorithm, metric_floor(p));
+    }, [&](const cluster_input& in) {
+        // column 0: every merge (the cut at the floor, i.e. the algorithm on the passing rows); then one cut per level
+        const int64_t n = in.n();
+        const size_t cols = (size_t)n_levels + 1, stride = (size_t)std::max<int64_t>(n, 1);
+        std::vector<int32_t> label(cols * stride), rep(cols * stride);
+        std::vector<std::string> names = { "cluster" };
+        std::vector<const int32_t*> lab_col, rep_col;
+        for (size_t c = 0; c < cols; ++c) {
+            vg_forest_cut(n, f, c ? levels[c - 1] : -HUGE_VAL, label.data() + c * stride, rep.data() + c * stride);
+            lab_col.push_back(label.data() + c * stride); rep_col.push_back(rep.data() + c * stride);
+            if (c) { char buf[64]; snprintf(buf, sizeof buf, "%g", levels[c - 1]); names.push_back(std::string(p->metric) + "_" + buf); }
+        }
+        if (linkage_path) {
+            const size_t nf = std::max<size_t>(f.a.size(), 1);
+            std::vector<int64_t> node_a(nf), node_b(nf), size(nf);
+            vg_forest_table(n, f, node_a.data(), node_b.data(), size.data());
+            vg_linkage_write(linkage_path, f, node_a.data(), node_b.data(), size.data());
+        }
+        vg_cluster_write_columns(out_path, in.ids, names, lab_col, rep_col, p->representatives != 0);
+    }, [&](const cluster_input& in) {
         fprintf(stderr, "vg_cluster_linkage: %lld objects, %lld rows passed, %lld edges, %lld rounds, %lld merges, %d levels\n",
-                (long long)n, (long long)in.q.size(), (long long)f.stats.n_edges, (long long)f.stats.rounds, (long long)f.stats.n_merges, n_levels);
+                (long long)in.n(), (long long)in.n_rows(), (long long)f.stats.n_edges, (long long)f.stats.rounds, (long long)f.stats.n_merges, n_levels);
+    });
     VG_API_END
 }

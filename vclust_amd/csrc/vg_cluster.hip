@@ -766,12 +766,20 @@ int64_t read_counter(dbuf<unsigned long long>& c, hipStream_t s) {
 void exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, hipStream_t s) {
     with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), s); });
 }
-// the argument checks of the array-level calls, before any device use
-void check_rows(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
+// ---------------------------------------------------------------- the opening of the array-level entries
+struct row_list { int64_t n; const uint32_t *q, *r; const double* w; int64_t n_rows; };    // the rows of a call over n objects
+// The argument checks of every array-level entry, before any device use.  The order in which an entry raises its errors is part of
+// its behaviour, so the opening comes in steps an entry calls around its own checks: check_call, check_row_values and, where sums
+// of weights are taken, check_unit_weights.
+// check_call: the sizes and the row pointers, then the entry's own null condition and its algorithm set -- null_error and
+// algorithm_error are the texts behind "<fn>: " of the one that failed, nullptr where it holds
+void check_call(const char* fn, const row_list& in, const char* null_error = nullptr, const char* algorithm_error = nullptr) {
     const std::string name(fn);
-    if (n_objects < 0 || n_rows < 0) throw vg_error(VG_EINVAL, name + ": negative size");
-    if (n_objects >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, name + ": 2^31 or more objects (object indices are int32)");
-    if (n_rows && (!q || !r || !w)) throw vg_error(VG_EINVAL, name + ": null rows");
+    if (in.n < 0 || in.n_rows < 0) throw vg_error(VG_EINVAL, name + ": negative size");
+    if (in.n >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, name + ": 2^31 or more objects (object indices are int32)");
+    if (in.n_rows && (!in.q || !in.r || !in.w)) throw vg_error(VG_EINVAL, name + ": null rows");
+    if (null_error) throw vg_error(VG_EINVAL, name + ": " + null_error);
+    if (algorithm_error) throw vg_error(VG_EINVAL, name + ": " + algorithm_error);
 }
 // the first row for which is_bad(row) holds, or -1: a parallel scan, every thread stops at the first of its chunk
 template <class Bad> int64_t first_bad_row(int64_t n_rows, Bad is_bad) {
@@ -782,26 +790,32 @@ template <class Bad> int64_t first_bad_row(int64_t n_rows, Bad is_bad) {
     for (int64_t k : bad) if (k >= 0) return k;
     return -1;
 }
-void check_row_values(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows) {
-    const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return q[i] >= (uint64_t)n_objects || r[i] >= (uint64_t)n_objects || std::isnan(w[i]); });
+void check_row_values(const char* fn, const row_list& in) {
+    const int64_t k = first_bad_row(in.n_rows, [&](int64_t i) { return in.q[i] >= (uint64_t)in.n || in.r[i] >= (uint64_t)in.n || std::isnan(in.w[i]); });
     if (k >= 0)
         throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": " +
-                       (std::isnan(w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(n_objects - 1)));
+                       (std::isnan(in.w[k]) ? std::string("weight is NaN") : "object index outside 0.." + std::to_string(in.n - 1)));
 }
-// average linkage: the quantum 2^-32 and the 64-bit sums stand on weights (and a floor) in [0, 1]
-void check_unit_weights(const char* fn, const double* w, int64_t n_rows, double floor, const char* what = "average linkage") {
-    if (!(floor >= 0 && floor <= 1)) throw vg_error(VG_EINVAL, std::string(fn) + ": the floor must lie in [0, 1]");
-    const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return !(w[i] >= 0 && w[i] <= 1); });
+// the quantum 2^-32 and the 64-bit sums (average linkage, the report, Markov clustering) stand on weights in [0, 1] ...
+void check_unit_weights(const char* fn, const row_list& in, const char* what = nullptr) {      // what: named in parentheses behind the text
+    const int64_t k = first_bad_row(in.n_rows, [&](int64_t i) { return !(in.w[i] >= 0 && in.w[i] <= 1); });
     if (k >= 0)
-        throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1] (" + what + ")");
+        throw vg_error(VG_EINVAL, std::string(fn) + ": row " + std::to_string(k) + ": weight " + std::to_string(in.w[k]) + " outside [0, 1]" +
+                       (what ? " (" + std::string(what) + ")" : std::string()));
 }
+// ... and on fewer than 2^32 of them
+void check_edge_sums(const std::string& fn, int64_t n_edges) {
+    if (n_edges >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, fn + ": 2^32 or more edges (a sum of weights must fit 64 bits)");
+}
+// the stats of a call, cleared: the caller's, or a local one if it wants none
+template <class Stats> Stats& cleared(Stats* stats, Stats& local) { Stats& st = stats ? *stats : local; st = Stats{}; return st; }
 
 // the edge graph of the rows on the device: the m directed edges sorted by (src, dst) with their weights, and the CSR.  With a
 // visit_map (the update of a prior clustering) the graph is over visit ranks and holds no edge between two prior objects.
 struct edge_graph { dbuf<uint64_t> ukeys; dbuf<double> uvals; int64_t m = 0; dbuf<int64_t> off; dbuf<int32_t> adj; };
 struct visit_map { const int32_t* visit = nullptr; int64_t n_prior = 0; };      // visit[object] = visit rank (device); ranks < n_prior are prior
-void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, hipStream_t s, edge_graph& g,
-                      visit_map vm = {}) {
+void build_edge_graph(const row_list& in, hipStream_t s, edge_graph& g, visit_map vm) {
+    const int64_t n = in.n, n_rows = in.n_rows; const uint32_t *q = in.q, *r = in.r; const double* w = in.w;
     dbuf<uint64_t>& ukeys = g.ukeys; dbuf<double>& uvals = g.uvals; int64_t& m = g.m;
     const int bits = id_bits(n);
 
@@ -846,6 +860,14 @@ void build_edge_graph(int64_t n, const uint32_t* q, const uint32_t* r, const dou
         hipLaunchKernelGGL(k_csr, dim3(grid_of(m + 1)), dim3(TPB), 0, s, (const uint64_t*)ukeys.p, m, n, g.off.p, g.adj.p);
     }
 }
+// From checked rows to their graph on the device, the step behind the opening of every entry: nobody else builds a graph.
+// -> the library's stream, on which the graph is complete in stream order (eg.m / 2 = the undirected edges)
+hipStream_t graph_on_device(const row_list& in, edge_graph& eg, visit_map vm = {}) {
+    vg_require_device();
+    hipStream_t s = vg_stream();
+    build_edge_graph(in, s, eg, vm);
+    return s;
+}
 
 // rank: forward edges in (a, b) order, then ONE stable sort by the weight key -> (w descending, a, b).  pos[p] = the directed
 // position of the forward edge of rank p (mu = m / 2 of them), rank[k] = the rank of the directed edge k
@@ -883,11 +905,8 @@ void download_forest(const dbuf<int64_t>& frank, int64_t nf, const dbuf<int64_t>
     f.stats.n_merges = nf;
 }
 
-// The forest edges of the rows in merge order (ascending rank), computed on the device; only these records come back.
-void forest_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f) {
-    hipStream_t s = vg_stream();
-    edge_graph eg;
-    build_edge_graph(n, q, r, w, n_rows, s, eg);
+// The forest edges of the graph in merge order (ascending rank), computed on the device; only these records come back.
+void forest_on_device(int64_t n, const edge_graph& eg, hipStream_t s, vg_forest& f) {
     const int64_t m = eg.m, mu = m / 2;
     f.stats.n_edges = mu;
     if (mu == 0) return;
@@ -1068,7 +1087,7 @@ struct average_linkage {
     dbuf<uint64_t> msum, mpairs; dbuf<int32_t> mc, md, size; dbuf<unsigned long long> bsum;
     int64_t in_key_order = -1;                                  // the merges before the zero phase (-1: it never began)
     void begin(cluster_rounds& st) {
-        if (st.m0 / 2 >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, "vg_cluster_average_linkage: 2^32 or more edges (a sum of weights must fit 64 bits)");
+        check_edge_sums("vg_cluster_average_linkage", st.m0 / 2);
         st.val.alloc((size_t)st.m0); msum.alloc((size_t)st.cap); mpairs.alloc((size_t)st.cap); mc.alloc((size_t)st.cap); md.alloc((size_t)st.cap);
         size.alloc((size_t)st.n); bsum.alloc((size_t)st.n);
         hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(st.m0)), dim3(TPB), 0, st.s, (const double*)st.eg.uvals.p, st.m0, st.val.p);
@@ -1229,57 +1248,93 @@ void labels_on_device(int64_t n, const dbuf<int32_t>& root, bool by_min_member, 
     hipLaunchKernelGGL(k_head_labels, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)fm.p, (const int32_t*)fs.p, (const int32_t*)sm.p, (const int32_t*)ss.p, n, lab.p);
     hipLaunchKernelGGL(k_gather, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)rep.p, (const int32_t*)lab.p, n, minm.p);
 }
+// The labelling exit of every call that returns a partition: root[] is checked, ids(): the cluster ids to number -- root[] itself,
+// or what the update makes of the checked root[] -- go through labels_on_device, and label[] and representative[] (a cluster's
+// earliest member, or with rep_is_id its id) leave the device under one synchronise, behind what also() downloads with them.
+template <class Ids, class Also>
+void labels_to_host(int64_t n, const dbuf<int32_t>& root, bool by_min_member, bool rep_is_id, hipStream_t s, int32_t* label, int32_t* representative,
+                    Ids ids, Also also) {
+    VG_HIP(hipGetLastError());
+    check_roots(n, root, s);
+    const dbuf<int32_t>& id = ids();
+    dbuf<int32_t> d_label, d_rep;
+    labels_on_device(n, id, by_min_member, s, d_label, d_rep);
+    VG_HIP(hipGetLastError());
+    also();
+    d_label.download(label, (size_t)n, s);
+    (rep_is_id ? id : d_rep).download(representative, (size_t)n, s);
+    VG_HIP(hipStreamSynchronize(s));
+}
+void labels_to_host(int64_t n, const dbuf<int32_t>& root, bool by_min_member, hipStream_t s, int32_t* label, int32_t* representative) {
+    labels_to_host(n, root, by_min_member, false, s, label, representative, [&]() -> const dbuf<int32_t>& { return root; }, [] {});
+}
 
+// The report of one labelling: what the three passes share, the partial results per object (k_st_rows writes them: st_part's fields,
+// own_max, and from the nearest pass the misfit flags and the sums into the nearest cluster) and per cluster (k_st_reduce adds them
+// up over the objects sorted by label: slabel[p] = the label at sorted position p, order[p] = its object)
+struct st_labelling { int64_t n, n_clusters; const edge_graph& eg; const dbuf<uint64_t>& u; hipStream_t s; dbuf<int32_t> label, slabel, order; };
+struct st_object_parts {
+    dbuf<uint64_t> cnt, sum, ext, mn, key, own, mis, nsum;
+    explicit st_object_parts(size_t n) : cnt(n), sum(n), ext(n), mn(n), key(n), own(n), mis(n), nsum(n) {}
+};
+struct st_cluster_parts {
+    dbuf<unsigned long long> cnt, sum, ext, mn, key, mis, nsum; dbuf<int64_t> begin, end; dbuf<int32_t> rep;
+    explicit st_cluster_parts(size_t nc) : cnt(nc), sum(nc), ext(nc), mn(nc), key(nc), mis(nc), nsum(nc), begin(nc), end(nc), rep(nc) {}
+};
+void stats_rows_pass(const st_labelling& L, st_object_parts& p) {
+    vg_prof_scope ps("cluster_stats_rows", (double)L.eg.m * 16.0 + (double)L.n * 60.0);
+    hipLaunchKernelGGL(k_st_rows<false>, dim3(grid_of(L.n * ROW_LANES)), dim3(TPB), 0, L.s, L.n, (const int64_t*)L.eg.off.p, (const int32_t*)L.eg.adj.p,
+                       (const uint64_t*)L.u.p, (const int32_t*)L.label.p, (const uint64_t*)nullptr, (const uint64_t*)nullptr, p.cnt.p, p.sum.p, p.ext.p,
+                       p.mn.p, p.key.p, p.own.p);
+}
+void stats_reduce_pass(st_labelling& L, const st_object_parts& p, st_cluster_parts& r) {
+    const int64_t n = L.n; hipStream_t s = L.s;
+    dbuf<int32_t> iota((size_t)n);
+    vg_prof_scope ps("cluster_stats_reduce", (double)n * (16.0 * 2.0 + 52.0) + (double)L.n_clusters * 64.0);
+    hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, iota.p, n);
+    with_temp_storage([&](void* tmp, size_t& tb) {
+        return rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)L.label.p, (uint32_t*)L.slabel.p, iota.p, L.order.p, (size_t)n, 0u,
+                                         (unsigned)id_bits(L.n_clusters), s); });
+    for (dbuf<unsigned long long>* b : { &r.cnt, &r.sum, &r.ext, &r.key, &r.mis, &r.nsum }) b->zero(s);
+    VG_HIP(hipMemsetAsync(r.mn.p, 0xff, r.mn.bytes(), s));
+    VG_HIP(hipMemsetAsync(r.begin.p, 0xff, r.begin.bytes(), s));
+    hipLaunchKernelGGL(k_st_reduce<false>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)L.slabel.p, (const int32_t*)L.order.p,
+                       (const uint64_t*)p.cnt.p, (const uint64_t*)p.sum.p, (const uint64_t*)p.ext.p, (const uint64_t*)p.mn.p,
+                       (const uint64_t*)p.key.p, r.cnt.p, r.sum.p, r.ext.p, r.mn.p, r.key.p, r.begin.p, r.end.p, r.rep.p);
+}
+void stats_nearest_pass(const st_labelling& L, st_object_parts& p, st_cluster_parts& r, dbuf<vg_cluster_stat>& out) {
+    const int64_t n = L.n; hipStream_t s = L.s;
+    vg_prof_scope ps("cluster_stats_nearest", (double)L.eg.m * 16.0 + (double)n * 72.0 + (double)L.n_clusters * 176.0);
+    hipLaunchKernelGGL(k_st_rows<true>, dim3(grid_of(n * ROW_LANES)), dim3(TPB), 0, s, n, (const int64_t*)L.eg.off.p, (const int32_t*)L.eg.adj.p,
+                       (const uint64_t*)L.u.p, (const int32_t*)L.label.p, (const uint64_t*)r.ext.p, (const uint64_t*)r.key.p, p.mis.p, p.nsum.p, p.ext.p,
+                       p.mn.p, p.key.p, p.own.p);
+    hipLaunchKernelGGL(k_st_reduce<true>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)L.slabel.p, (const int32_t*)L.order.p,
+                       (const uint64_t*)p.mis.p, (const uint64_t*)p.nsum.p, (const uint64_t*)nullptr, (const uint64_t*)nullptr,
+                       (const uint64_t*)nullptr, r.mis.p, r.nsum.p, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                       (unsigned long long*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(k_st_finish, dim3(grid_of(L.n_clusters)), dim3(TPB), 0, s, L.n_clusters, (const int64_t*)r.begin.p, (const int64_t*)r.end.p,
+                       (const int32_t*)r.rep.p, (const unsigned long long*)r.cnt.p, (const unsigned long long*)r.sum.p,
+                       (const unsigned long long*)r.ext.p, (const unsigned long long*)r.mn.p, (const unsigned long long*)r.key.p,
+                       (const unsigned long long*)r.mis.p, (const unsigned long long*)r.nsum.p, out.p);
+}
 // The report of one labelling on the edge graph (u: its quantised weights): the three passes, then the records and, if wanted,
 // the per-object values leave the device.  label[] has been checked on the host.
 void stats_on_device(int64_t n, const edge_graph& eg, const dbuf<uint64_t>& u, hipStream_t s, const int32_t* label, int64_t n_clusters,
                      vg_cluster_stat* out, uint64_t* own_max, uint64_t* other_max, int32_t* other) {
-    const int64_t* off = eg.off.p; const int32_t* adj = eg.adj.p;
-    const size_t nc = (size_t)n_clusters;
-    dbuf<int32_t> d_label((size_t)n), iota((size_t)n), slabel((size_t)n), order((size_t)n), r_rep(nc);
-    dbuf<uint64_t> p_cnt((size_t)n), p_sum((size_t)n), p_ext((size_t)n), p_mn((size_t)n), p_key((size_t)n), own((size_t)n), p_mis((size_t)n), p_nsum((size_t)n);
-    dbuf<unsigned long long> r_cnt(nc), r_sum(nc), r_ext(nc), r_mn(nc), r_key(nc), r_mis(nc), r_nsum(nc);
-    dbuf<int64_t> r_begin(nc), r_end(nc);
-    dbuf<vg_cluster_stat> d_out(nc);
-    d_label.upload(label, (size_t)n, s);
-    const int row_grid = grid_of(n * ROW_LANES);
-    {
-        vg_prof_scope ps("cluster_stats_rows", (double)eg.m * 16.0 + (double)n * 60.0);
-        hipLaunchKernelGGL(k_st_rows<false>, dim3(row_grid), dim3(TPB), 0, s, n, off, adj, (const uint64_t*)u.p, (const int32_t*)d_label.p,
-                           (const uint64_t*)nullptr, (const uint64_t*)nullptr, p_cnt.p, p_sum.p, p_ext.p, p_mn.p, p_key.p, own.p);
-    }
-    {
-        vg_prof_scope ps("cluster_stats_reduce", (double)n * (16.0 * 2.0 + 52.0) + (double)n_clusters * 64.0);
-        hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, iota.p, n);
-        with_temp_storage([&](void* tmp, size_t& tb) {
-            return rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)d_label.p, (uint32_t*)slabel.p, iota.p, order.p, (size_t)n, 0u,
-                                             (unsigned)id_bits(n_clusters), s); });
-        for (dbuf<unsigned long long>* b : { &r_cnt, &r_sum, &r_ext, &r_key, &r_mis, &r_nsum }) b->zero(s);
-        VG_HIP(hipMemsetAsync(r_mn.p, 0xff, r_mn.bytes(), s));
-        VG_HIP(hipMemsetAsync(r_begin.p, 0xff, r_begin.bytes(), s));
-        hipLaunchKernelGGL(k_st_reduce<false>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)slabel.p, (const int32_t*)order.p,
-                           (const uint64_t*)p_cnt.p, (const uint64_t*)p_sum.p, (const uint64_t*)p_ext.p, (const uint64_t*)p_mn.p,
-                           (const uint64_t*)p_key.p, r_cnt.p, r_sum.p, r_ext.p, r_mn.p, r_key.p, r_begin.p, r_end.p, r_rep.p);
-    }
-    {
-        vg_prof_scope ps("cluster_stats_nearest", (double)eg.m * 16.0 + (double)n * 72.0 + (double)n_clusters * 176.0);
-        hipLaunchKernelGGL(k_st_rows<true>, dim3(row_grid), dim3(TPB), 0, s, n, off, adj, (const uint64_t*)u.p, (const int32_t*)d_label.p,
-                           (const uint64_t*)r_ext.p, (const uint64_t*)r_key.p, p_mis.p, p_nsum.p, p_ext.p, p_mn.p, p_key.p, own.p);
-        hipLaunchKernelGGL(k_st_reduce<true>, dim3(grid_of(n)), dim3(TPB), 0, s, n, (const int32_t*)slabel.p, (const int32_t*)order.p,
-                           (const uint64_t*)p_mis.p, (const uint64_t*)p_nsum.p, (const uint64_t*)nullptr, (const uint64_t*)nullptr,
-                           (const uint64_t*)nullptr, r_mis.p, r_nsum.p, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                           (unsigned long long*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr, (int32_t*)nullptr);
-        hipLaunchKernelGGL(k_st_finish, dim3(grid_of(n_clusters)), dim3(TPB), 0, s, n_clusters, (const int64_t*)r_begin.p, (const int64_t*)r_end.p,
-                           (const int32_t*)r_rep.p, (const unsigned long long*)r_cnt.p, (const unsigned long long*)r_sum.p,
-                           (const unsigned long long*)r_ext.p, (const unsigned long long*)r_mn.p, (const unsigned long long*)r_key.p,
-                           (const unsigned long long*)r_mis.p, (const unsigned long long*)r_nsum.p, d_out.p);
-    }
+    st_labelling L{ n, n_clusters, eg, u, s, dbuf<int32_t>((size_t)n), dbuf<int32_t>((size_t)n), dbuf<int32_t>((size_t)n) };
+    st_object_parts p((size_t)n);
+    st_cluster_parts r((size_t)n_clusters);
+    dbuf<vg_cluster_stat> d_out((size_t)n_clusters);
+    L.label.upload(label, (size_t)n, s);
+    stats_rows_pass(L, p);
+    stats_reduce_pass(L, p, r);
+    stats_nearest_pass(L, p, r, d_out);
     VG_HIP(hipGetLastError());
-    d_out.download(out, nc, s);
-    if (own_max) own.download(own_max, (size_t)n, s);
+    d_out.download(out, (size_t)n_clusters, s);
+    if (own_max) p.own.download(own_max, (size_t)n, s);
     if (other_max || other) {                                   // the best external key of every object, decoded here
         std::vector<uint64_t> key((size_t)n), ext((size_t)n);
-        p_key.download(key.data(), (size_t)n, s); p_ext.download(ext.data(), (size_t)n, s);
+        p.key.download(key.data(), (size_t)n, s); p.ext.download(ext.data(), (size_t)n, s);
         VG_HIP(hipStreamSynchronize(s));
         for (int64_t i = 0; i < n; ++i) {
             if (other_max) other_max[i] = ext[(size_t)i] ? st_key_u(key[(size_t)i]) : 0;
@@ -1297,15 +1352,15 @@ void vg_cluster_stats_run(const char* fn, int64_t n, const uint32_t* q, const ui
                           const int32_t* const* label, const int64_t* n_clusters, vg_cluster_stat* const* out, uint64_t* own_max,
                           uint64_t* other_max, int32_t* other) {
     const std::string name(fn);
-    check_rows(fn, n, q, r, w, n_rows);
+    const row_list in{ n, q, r, w, n_rows };
+    check_call(fn, in);
     for (int c = 0; c < n_cols; ++c) {
         if (n_clusters[c] < 0) throw vg_error(VG_EINVAL, name + ": negative number of clusters");
         if (n_clusters[c] >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, name + ": 2^31 or more clusters (labels are int32)");
         if ((n && !label[c]) || (n_clusters[c] && !out[c])) throw vg_error(VG_EINVAL, name + ": null argument");
     }
-    check_row_values(fn, n, q, r, w, n_rows);
-    const int64_t k = first_bad_row(n_rows, [&](int64_t i) { return !(w[i] >= 0 && w[i] <= 1); });
-    if (k >= 0) throw vg_error(VG_EINVAL, name + ": row " + std::to_string(k) + ": weight " + std::to_string(w[k]) + " outside [0, 1]");
+    check_row_values(fn, in);
+    check_unit_weights(fn, in);
     for (int c = 0; c < n_cols; ++c) {
         const int64_t bad = first_bad_row(n, [&](int64_t i) { return label[c][i] < 0 || label[c][i] >= n_clusters[c]; });
         if (bad >= 0)
@@ -1316,11 +1371,9 @@ void vg_cluster_stats_run(const char* fn, int64_t n, const uint32_t* q, const ui
             for (int64_t x = 0; x < n_clusters[c]; ++x) { out[c][x] = vg_cluster_stat{}; out[c][x].rep = out[c][x].nearest = -1; }
         return;
     }
-    vg_require_device();
-    hipStream_t s = vg_stream();
     edge_graph eg;
-    build_edge_graph(n, q, r, w, n_rows, s, eg);
-    if (eg.m / 2 >= (1LL << 32)) throw vg_error(VG_EOVERFLOW, name + ": 2^32 or more edges (a sum of weights must fit 64 bits)");
+    hipStream_t s = graph_on_device(in, eg);
+    check_edge_sums(name, eg.m / 2);
     dbuf<uint64_t> u((size_t)eg.m);
     hipLaunchKernelGGL(k_av_quantise, dim3(grid_of(eg.m)), dim3(TPB), 0, s, (const double*)eg.uvals.p, eg.m, u.p);
     VG_HIP(hipGetLastError());
@@ -1339,18 +1392,16 @@ extern "C" int vg_cluster_stats_graph(int64_t n_objects, const uint32_t* q, cons
 extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                                 int algorithm, int32_t* label, int32_t* representative, vg_cluster_stats* stats) {
     VG_API_BEGIN
-    check_rows("vg_cluster_graph", n_objects, q, r, w, n_rows);
-    if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, "vg_cluster_graph: null output");
-    if (algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_COMPLETE) throw vg_error(VG_EINVAL, "vg_cluster_graph: unknown algorithm");
-    check_row_values("vg_cluster_graph", n_objects, q, r, w, n_rows);
-    vg_cluster_stats st_local{}; vg_cluster_stats& sts = stats ? *stats : st_local;
-    sts = vg_cluster_stats{};
+    const char* fn = "vg_cluster_graph";
+    const row_list in{ n_objects, q, r, w, n_rows };
+    check_call(fn, in, n_objects && (!label || !representative) ? "null output" : nullptr,
+               algorithm < VG_CLUSTER_SINGLE || algorithm > VG_CLUSTER_COMPLETE ? "unknown algorithm" : nullptr);
+    check_row_values(fn, in);
+    vg_cluster_stats local; vg_cluster_stats& sts = cleared(stats, local);
     if (n_objects == 0) return VG_OK;
-    vg_require_device();
-    hipStream_t s = vg_stream();
     const int64_t n = n_objects;
     edge_graph eg;
-    build_edge_graph(n, q, r, w, n_rows, s, eg);
+    hipStream_t s = graph_on_device(in, eg);
     sts.n_edges = eg.m / 2;
     dbuf<int32_t> root((size_t)n);
     switch (algorithm) {
@@ -1359,95 +1410,90 @@ extern "C" int vg_cluster_graph(int64_t n_objects, const uint32_t* q, const uint
         case VG_CLUSTER_SET_COVER: set_cover_on_device(n, eg, s, root, sts); break;
         default: greedy_on_device(algorithm == VG_CLUSTER_UCLUST, n, eg, s, root, sts);
     }
-    VG_HIP(hipGetLastError());
-    check_roots(n, root, s);
-    dbuf<int32_t> d_label, d_rep;
-    labels_on_device(n, root, algorithm == VG_CLUSTER_SET_COVER, s, d_label, d_rep);
-    VG_HIP(hipGetLastError());
-    d_label.download(label, (size_t)n, s);
-    d_rep.download(representative, (size_t)n, s);
-    VG_HIP(hipStreamSynchronize(s));
+    labels_to_host(n, root, algorithm == VG_CLUSTER_SET_COVER, s, label, representative);
     VG_API_END
 }
 
 // ---------------------------------------------------------------- update of a prior clustering
+namespace {
+// the prior array on the device and the visit ranks made of it: visit[object], its inverse, the number of prior objects
+struct update_ranks { dbuf<int32_t> prior, visit, inv; int32_t n_prior = 0; };
+void visit_ranks(const char* fn, int64_t n, const int32_t* prior_rep, hipStream_t s, update_ranks& vr) {
+    for (dbuf<int32_t>* b : { &vr.prior, &vr.visit, &vr.inv }) b->alloc((size_t)n);
+    dbuf<int32_t> flag((size_t)n), before((size_t)n), d_np(1);
+    vr.prior.upload(prior_rep, (size_t)n, s);
+    {
+        vg_prof_scope ps("cluster_update_map", (double)n * 4.0 * 7.0);
+        hipLaunchKernelGGL(k_new_flags, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)vr.prior.p, n, flag.p);
+        exclusive_scan_i32(flag.p, before.p, n, s);
+        hipLaunchKernelGGL(k_visit_rank, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)flag.p, (const int32_t*)before.p, n, vr.visit.p, vr.inv.p, d_np.p);
+        d_np.download(&vr.n_prior, 1, s);
+        VG_HIP(hipStreamSynchronize(s));
+    }
+    if (vr.n_prior < 0 || vr.n_prior > n) throw vg_error(VG_EHIP, std::string(fn) + ": the visit ranks are inconsistent (internal error)");
+}
+// the algorithm on the kept edges from the seeded state -> root[] on visit ranks
+void seeded_on_device(int algorithm, int64_t n, const edge_graph& eg, const update_ranks& vr, hipStream_t s, dbuf<int32_t>& root, vg_cluster_stats& cs) {
+    const int32_t *prior = vr.prior.p, *visit = vr.visit.p;
+    if (algorithm == VG_CLUSTER_SINGLE) {
+        {
+            dbuf<int32_t> minv((size_t)n);
+            vg_prof_scope ps("cluster_update_seed", (double)n * 4.0 * 8.0);
+            hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, minv.p, n);
+            hipLaunchKernelGGL(k_seed_min, dim3(grid_of(n)), dim3(TPB), 0, s, prior, visit, n, minv.p);
+            hipLaunchKernelGGL(k_seed_single, dim3(grid_of(n)), dim3(TPB), 0, s, prior, visit, (const int32_t*)minv.p, n, root.p);
+        }
+        single_on_device(n, eg, s, root, cs, true);
+    } else
+        greedy_on_device(algorithm == VG_CLUSTER_UCLUST, n, eg, s, root, cs, vr.n_prior, [&] {
+            vg_prof_scope ps("cluster_update_seed", (double)n * 4.0 * 4.0);
+            hipLaunchKernelGGL(k_seed_greedy, dim3(grid_of(n)), dim3(TPB), 0, s, prior, visit, n, root.p);
+        });
+}
+// the outcome counts of the checked root[] -> d_cnt, and cid[] = the cluster ids back on object indices
+void update_outcome(int64_t n, const dbuf<int32_t>& root, const update_ranks& vr, bool single, hipStream_t s, dbuf<unsigned long long>& d_cnt,
+                    dbuf<int32_t>& cid) {
+    d_cnt.zero(s);
+    hipLaunchKernelGGL(k_update_counts, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)vr.prior.p, (const int32_t*)vr.visit.p, n,
+                       vr.n_prior, single, d_cnt.p);
+    hipLaunchKernelGGL(k_unmap, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)vr.visit.p, (const int32_t*)vr.inv.p, n, cid.p);
+}
+}  // namespace
+
 extern "C" int vg_cluster_update_graph(int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                                        int algorithm, const int32_t* prior_rep, int32_t* label, int32_t* representative,
                                        vg_cluster_update_stats* stats) {
     VG_API_BEGIN
     const char* fn = "vg_cluster_update_graph";
-    check_rows(fn, n_objects, q, r, w, n_rows);
-    if (n_objects && (!prior_rep || !label || !representative)) throw vg_error(VG_EINVAL, std::string(fn) + ": null argument");
-    if (algorithm != VG_CLUSTER_SINGLE && algorithm != VG_CLUSTER_CDHIT && algorithm != VG_CLUSTER_UCLUST)
-        throw vg_error(VG_EINVAL, std::string(fn) + ": the update of a prior clustering is single, cd-hit or uclust");
-    check_row_values(fn, n_objects, q, r, w, n_rows);
+    const row_list in{ n_objects, q, r, w, n_rows };
     const int64_t n = n_objects;
+    const bool single = algorithm == VG_CLUSTER_SINGLE;
+    check_call(fn, in, n && (!prior_rep || !label || !representative) ? "null argument" : nullptr,
+               !single && algorithm != VG_CLUSTER_CDHIT && algorithm != VG_CLUSTER_UCLUST ? "the update of a prior clustering is single, cd-hit or uclust" : nullptr);
+    check_row_values(fn, in);
     int64_t bad = first_bad_row(n, [&](int64_t i) { return prior_rep[i] < -1 || prior_rep[i] >= n; });
     if (bad >= 0) throw vg_error(VG_EINVAL, std::string(fn) + ": prior_rep[" + std::to_string(bad) + "] = " + std::to_string(prior_rep[bad]) + " outside -1.." + std::to_string(n - 1));
     bad = first_bad_row(n, [&](int64_t i) { return prior_rep[i] >= 0 && prior_rep[prior_rep[i]] != prior_rep[i]; });
     if (bad >= 0) throw vg_error(VG_EINVAL, std::string(fn) + ": prior_rep[" + std::to_string(bad) + "] = " + std::to_string(prior_rep[bad]) + " is not its own representative");
-    vg_cluster_update_stats st_local{}; vg_cluster_update_stats& sts = stats ? *stats : st_local;
-    sts = vg_cluster_update_stats{};
+    vg_cluster_update_stats local; vg_cluster_update_stats& sts = cleared(stats, local);
     if (n == 0) return VG_OK;
-    vg_require_device();
-    hipStream_t s = vg_stream();
-    const bool single = algorithm == VG_CLUSTER_SINGLE;
-
-    // ---- visit ranks
-    dbuf<int32_t> prior((size_t)n), visit((size_t)n), inv((size_t)n);
-    int32_t n_prior = 0;
-    {
-        dbuf<int32_t> flag((size_t)n), before((size_t)n), d_np(1);
-        prior.upload(prior_rep, (size_t)n, s);
-        vg_prof_scope ps("cluster_update_map", (double)n * 4.0 * 7.0);
-        hipLaunchKernelGGL(k_new_flags, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, n, flag.p);
-        exclusive_scan_i32(flag.p, before.p, n, s);
-        hipLaunchKernelGGL(k_visit_rank, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)flag.p, (const int32_t*)before.p, n, visit.p, inv.p, d_np.p);
-        d_np.download(&n_prior, 1, s);
-        VG_HIP(hipStreamSynchronize(s));
-    }
-    if (n_prior < 0 || n_prior > n) throw vg_error(VG_EHIP, std::string(fn) + ": the visit ranks are inconsistent (internal error)");
-    sts.n_prior = n_prior; sts.n_new = n - n_prior;
-
-    // ---- the kept edges on visit ranks, then the algorithm from the seeded state
+    // visit ranks, the kept edges on them, the algorithm from the seeded state
+    update_ranks vr;
+    visit_ranks(fn, n, prior_rep, vg_stream(), vr);
+    sts.n_prior = vr.n_prior; sts.n_new = n - vr.n_prior;
     edge_graph eg;
-    build_edge_graph(n, q, r, w, n_rows, s, eg, visit_map{ visit.p, n_prior });
+    hipStream_t s = graph_on_device(in, eg, visit_map{ vr.visit.p, vr.n_prior });
     sts.n_edges = eg.m / 2;
     dbuf<int32_t> root((size_t)n);
     vg_cluster_stats cs{};
-    if (single) {
-        {
-            dbuf<int32_t> minv((size_t)n);
-            vg_prof_scope ps("cluster_update_seed", (double)n * 4.0 * 8.0);
-            hipLaunchKernelGGL(k_iota, dim3(grid_of(n)), dim3(TPB), 0, s, minv.p, n);
-            hipLaunchKernelGGL(k_seed_min, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, (const int32_t*)visit.p, n, minv.p);
-            hipLaunchKernelGGL(k_seed_single, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, (const int32_t*)visit.p, (const int32_t*)minv.p, n, root.p);
-        }
-        single_on_device(n, eg, s, root, cs, true);
-    } else
-        greedy_on_device(algorithm == VG_CLUSTER_UCLUST, n, eg, s, root, cs, n_prior, [&] {
-            vg_prof_scope ps("cluster_update_seed", (double)n * 4.0 * 4.0);
-            hipLaunchKernelGGL(k_seed_greedy, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)prior.p, (const int32_t*)visit.p, n, root.p);
-        });
-    VG_HIP(hipGetLastError());
+    seeded_on_device(algorithm, n, eg, vr, s, root, cs);
     sts.rounds = cs.rounds; sts.sweep_objects = cs.sweep_objects;
-    check_roots(n, root, s);
-
-    // ---- outcome counts, then labels on object ids: numbering by earliest member; the representative is the frozen or founding
-    // one (greedy: the cluster id itself) or the earliest member (single)
-    dbuf<unsigned long long> d_cnt(5);
-    dbuf<int32_t> cid((size_t)n), d_label, d_rep;
-    d_cnt.zero(s);
-    hipLaunchKernelGGL(k_update_counts, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)prior.p, (const int32_t*)visit.p, n, n_prior,
-                       single, d_cnt.p);
-    hipLaunchKernelGGL(k_unmap, dim3(grid_of(n)), dim3(TPB), 0, s, (const int32_t*)root.p, (const int32_t*)visit.p, (const int32_t*)inv.p, n, cid.p);
-    labels_on_device(n, cid, true, s, d_label, d_rep);
-    VG_HIP(hipGetLastError());
+    // outcome counts, then labels on object ids: numbering by earliest member; the representative is the frozen or founding one
+    // (greedy: the cluster id itself) or the earliest member (single)
+    dbuf<unsigned long long> d_cnt(5); dbuf<int32_t> cid((size_t)n);
     unsigned long long cnt[5] = {};
-    d_cnt.download(cnt, 5, s);
-    d_label.download(label, (size_t)n, s);
-    (single ? d_rep : cid).download(representative, (size_t)n, s);
-    VG_HIP(hipStreamSynchronize(s));
+    labels_to_host(n, root, true, !single, s, label, representative,
+                   [&]() -> const dbuf<int32_t>& { update_outcome(n, root, vr, single, s, d_cnt, cid); return cid; }, [&] { d_cnt.download(cnt, 5, s); });
     sts.joined_prior = (int64_t)cnt[0]; sts.joined_new = (int64_t)cnt[1]; sts.founded = (int64_t)cnt[2];
     sts.prior_merged = (int64_t)cnt[3] - (int64_t)cnt[4];
     VG_API_END
@@ -1456,21 +1502,25 @@ extern "C" int vg_cluster_update_graph(int64_t n_objects, const uint32_t* q, con
 // ---------------------------------------------------------------- merge table and cuts (host numbering of <= n - 1 records)
 void vg_cluster_forest(const char* fn, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, vg_forest& f,
                        int algorithm, double floor) {
-    check_rows(fn, n_objects, q, r, w, n_rows);
-    check_row_values(fn, n_objects, q, r, w, n_rows);
+    const row_list in{ n_objects, q, r, w, n_rows };
+    check_call(fn, in);
+    check_row_values(fn, in);
     if (algorithm != VG_CLUSTER_SINGLE && algorithm != VG_CLUSTER_COMPLETE && algorithm != VG_CLUSTER_AVERAGE)
         throw vg_error(VG_EINVAL, std::string(fn) + ": the merge table is single, complete or average linkage");
-    if (algorithm == VG_CLUSTER_AVERAGE) check_unit_weights(fn, w, n_rows, floor);
+    if (algorithm == VG_CLUSTER_AVERAGE) {
+        if (!(floor >= 0 && floor <= 1)) throw vg_error(VG_EINVAL, std::string(fn) + ": the floor must lie in [0, 1]");
+        check_unit_weights(fn, in, "average linkage");
+    }
     f = vg_forest{};
     if (n_objects == 0) return;
-    vg_require_device();
-    if (algorithm == VG_CLUSTER_SINGLE) { forest_on_device(n_objects, q, r, w, n_rows, f); return; }
-    hipStream_t s = vg_stream();
     edge_graph eg;
-    build_edge_graph(n_objects, q, r, w, n_rows, s, eg);
-    if (algorithm == VG_CLUSTER_AVERAGE) { average_on_device(n_objects, eg, floor, s, f); return; }
+    hipStream_t s = graph_on_device(in, eg);
     dbuf<int32_t> comp;
-    complete_on_device(n_objects, eg, s, comp, true, f);
+    switch (algorithm) {
+        case VG_CLUSTER_SINGLE: forest_on_device(n_objects, eg, s, f); break;
+        case VG_CLUSTER_AVERAGE: average_on_device(n_objects, eg, floor, s, f); break;
+        default: complete_on_device(n_objects, eg, s, comp, true, f);
+    }
 }
 
 namespace {
@@ -1518,10 +1568,9 @@ namespace {
 void linkage_graph(const char* fn, int algorithm, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                    int32_t* object_a, int32_t* object_b, double* weight, int64_t* node_a, int64_t* node_b,
                    int64_t* size, int64_t* n_merges, vg_linkage_stats* stats, double floor = 0.0, uint64_t* sum = nullptr, uint64_t* pairs = nullptr) {
-    check_rows(fn, n_objects, q, r, w, n_rows);
     const bool average = algorithm == VG_CLUSTER_AVERAGE;
-    if (!n_merges || (n_objects > 1 && (!object_a || !object_b || !weight || !node_a || !node_b || !size || (average && (!sum || !pairs)))))
-        throw vg_error(VG_EINVAL, std::string(fn) + ": null output");
+    check_call(fn, { n_objects, q, r, w, n_rows },
+               !n_merges || (n_objects > 1 && (!object_a || !object_b || !weight || !node_a || !node_b || !size || (average && (!sum || !pairs)))) ? "null output" : nullptr);
     *n_merges = 0;
     if (stats) *stats = vg_linkage_stats{};
     vg_forest f;
@@ -1539,7 +1588,7 @@ void linkage_graph(const char* fn, int algorithm, int64_t n_objects, const uint3
 void levels_graph(const char* fn, int algorithm, int64_t n_objects, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows,
                   const double* levels, int n_levels, int32_t* label, int32_t* representative, vg_linkage_stats* stats, double floor = 0.0) {
     const std::string name(fn);
-    check_rows(fn, n_objects, q, r, w, n_rows);
+    check_call(fn, { n_objects, q, r, w, n_rows });
     if (n_levels < 0 || (n_levels && !levels)) throw vg_error(VG_EINVAL, name + ": null levels");
     for (int l = 0; l < n_levels; ++l) if (std::isnan(levels[l])) throw vg_error(VG_EINVAL, name + ": a level is NaN");
     if (algorithm == VG_CLUSTER_AVERAGE)                        // (the hierarchy stops at the floor: there is nothing to cut below it)
@@ -2025,17 +2074,13 @@ void mcl_spill(int64_t n, int64_t ns, const mcl_matrix& M, mcl_matrix& N, const 
     }
 }
 
-void mcl_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double* w, int64_t n_rows, const vg_mcl_params& prm, int32_t* label,
-                   int32_t* representative, int64_t** m_off, int32_t** m_col, uint32_t** m_val, vg_mcl_stats& sts) {
-    hipStream_t s = vg_stream();
-    const mcl_dev P{ (int)llrint(2 * prm.inflation), (uint32_t)(uint64_t)std::floor(prm.prune * (double)MCL_ONE), prm.max_row };
-    const uint64_t eps = (uint64_t)std::floor(prm.chaos_eps * (double)MCL_ONE);
-    const int slots = g_mcl_slots.load() ? g_mcl_slots.load() : MCL_GROUP_SLOTS;
-    mcl_matrix M;
+// what the stages of one run share: the device parameters, the table size, the counters
+struct mcl_run { const int64_t n; const hipStream_t s; const mcl_dev P; const int slots; dbuf<unsigned long long> ctr; };
+
+// the start matrix from the edge graph (released behind it), and the plan of the first iteration
+void mcl_start_matrix(mcl_run& R, edge_graph& eg, mcl_matrix& M, mcl_plan& pl) {
+    const int64_t n = R.n; hipStream_t s = R.s;
     {
-        edge_graph eg;
-        build_edge_graph(n, q, r, w, n_rows, s, eg);
-        sts.n_edges = eg.m / 2;
         dbuf<uint64_t> u((size_t)std::max<int64_t>(eg.m, 1));
         M.off.alloc((size_t)n); M.cnt.alloc((size_t)n); M.ent.alloc((size_t)(eg.m + n));
         vg_prof_scope ps("cluster_mcl_start", (double)eg.m * 28.0 + (double)n * 28.0);
@@ -2044,64 +2089,64 @@ void mcl_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double
                            M.off.p, M.cnt.p, M.ent.p);
         VG_HIP(hipGetLastError());
     }
-    dbuf<unsigned long long> ctr(MC_N);
-    ctr.zero(s);
-    mcl_plan pl;
+    eg = edge_graph{};
+    R.ctr.alloc(MC_N);
+    R.ctr.zero(s);
     pl.bound.alloc((size_t)n); pl.spill_bound.alloc((size_t)n); pl.store.alloc((size_t)n);
     pl.wave_rows.alloc((size_t)n); pl.group_rows.alloc((size_t)n); pl.spill_rows.alloc((size_t)n);
-    mcl_make_plan(n, M, slots, P.max_row, ctr, s, pl);
-    char note[128];
-    for (;;) {
-        const int64_t nw = (int64_t)pl.h[MC_WAVE], ng = (int64_t)pl.h[MC_GROUP];
-        mcl_matrix N;
-        N.off = std::move(pl.off_next); N.cnt.alloc((size_t)n); N.ent.alloc((size_t)std::max<int64_t>((int64_t)pl.h[MC_STORAGE], 1));
-        VG_HIP(hipMemsetAsync(ctr.p, 0, MC_WAVE * sizeof(unsigned long long), s));       // chaos and the guard flag
-        if (nw) {
-            vg_prof_scope ps("cluster_mcl_expand_wave", (double)nw * 512.0);
-            hipLaunchKernelGGL((k_mcl_expand<64, MCL_WAVE_SLOTS>), dim3((unsigned)std::min<int64_t>(nw, 1 << 20)), dim3(64), 0, s, n, (const int32_t*)pl.wave_rows.p, nw,
-                               (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p, (const int64_t*)pl.bound.p,
-                               std::min(MCL_WAVE_SLOTS, slots), P, (const int64_t*)N.off.p, (const int64_t*)pl.store.p, N.cnt.p, N.ent.p,
-                               pl.spill_rows.p, pl.spill_bound.p, ctr.p);
-        }
-        if (ng) {
-            vg_prof_scope ps("cluster_mcl_expand_group", (double)ng * 16384.0);
-            hipLaunchKernelGGL((k_mcl_expand<TPB, MCL_GROUP_SLOTS>), dim3((unsigned)std::min<int64_t>(ng, 1 << 20)), dim3(TPB), 0, s, n, (const int32_t*)pl.group_rows.p, ng,
-                               (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p, (const int64_t*)pl.bound.p,
-                               std::min(MCL_GROUP_SLOTS, slots), P, (const int64_t*)N.off.p, (const int64_t*)pl.store.p, N.cnt.p, N.ent.p,
-                               pl.spill_rows.p, pl.spill_bound.p, ctr.p);
-        }
-        VG_HIP(hipGetLastError());
-        int64_t ns = 0;
-        if (pl.h[MC_TRY]) {                                     // rows were tried above their bound: how many did the table not hold?
-            unsigned long long given_up = 0;
-            vg_download_bytes(&given_up, ctr.p + MC_SPILL, sizeof given_up, s);
-            VG_HIP(hipStreamSynchronize(s));
-            ns = (int64_t)given_up;
-            if (ns > (int64_t)pl.h[MC_TRY]) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: more spill rows than rows above the table (internal error)");
-        }
-        if (ns) mcl_spill(n, ns, M, N, pl, P, ctr, s);
-        M = std::move(N);
-        ++sts.iterations; sts.lds_rows += n - ns; sts.spill_rows += ns;
-        mcl_make_plan(n, M, slots, P.max_row, ctr, s, pl);       // (also the read-back of this iteration's chaos)
-        sts.chaos = pl.h[MC_CHAOS];
-        snprintf(note, sizeof note, "mcl iteration %lld: chaos %llu, %lld + %lld LDS rows, %lld spill rows", (long long)sts.iterations,
-                 (unsigned long long)sts.chaos, (long long)nw, (long long)(ng - ns), (long long)ns);
-        vg_host_mark(note);
-        if (sts.chaos <= eps) { sts.converged = 1; break; }
-        if (sts.iterations >= prm.max_iterations) break;
+    mcl_make_plan(n, M, R.slots, R.P.max_row, R.ctr, s, pl);
+}
+// the nr rows of one class expanded from M into N, a row per T-thread workgroup with a table of at most SLOTS slots
+template <int T, int SLOTS>
+void mcl_expand_rows(const char* scope, double bytes, mcl_run& R, const dbuf<int32_t>& rows, int64_t nr, const mcl_matrix& M, mcl_matrix& N, mcl_plan& pl) {
+    vg_prof_scope ps(scope, bytes);
+    hipLaunchKernelGGL((k_mcl_expand<T, SLOTS>), dim3((unsigned)std::min<int64_t>(nr, 1 << 20)), dim3(T), 0, R.s, R.n, (const int32_t*)rows.p, nr,
+                       (const int64_t*)M.off.p, (const int32_t*)M.cnt.p, (const uint64_t*)M.ent.p, (const int64_t*)pl.bound.p,
+                       std::min(SLOTS, R.slots), R.P, (const int64_t*)N.off.p, (const int64_t*)pl.store.p, N.cnt.p, N.ent.p,
+                       pl.spill_rows.p, pl.spill_bound.p, R.ctr.p);
+}
+// One iteration: M expanded by its plan (the two LDS kernels, then the rows the table did not hold), M replaced, the plan of the next
+// iteration -- whose read-back is also this iteration's chaos
+void mcl_iterate(mcl_run& R, mcl_matrix& M, mcl_plan& pl, vg_mcl_stats& sts) {
+    const int64_t n = R.n, nw = (int64_t)pl.h[MC_WAVE], ng = (int64_t)pl.h[MC_GROUP]; hipStream_t s = R.s;
+    mcl_matrix N;
+    N.off = std::move(pl.off_next); N.cnt.alloc((size_t)n); N.ent.alloc((size_t)std::max<int64_t>((int64_t)pl.h[MC_STORAGE], 1));
+    VG_HIP(hipMemsetAsync(R.ctr.p, 0, MC_WAVE * sizeof(unsigned long long), s));     // chaos and the guard flag
+    if (nw) mcl_expand_rows<64, MCL_WAVE_SLOTS>("cluster_mcl_expand_wave", (double)nw * 512.0, R, pl.wave_rows, nw, M, N, pl);
+    if (ng) mcl_expand_rows<TPB, MCL_GROUP_SLOTS>("cluster_mcl_expand_group", (double)ng * 16384.0, R, pl.group_rows, ng, M, N, pl);
+    VG_HIP(hipGetLastError());
+    int64_t ns = 0;
+    if (pl.h[MC_TRY]) {                                         // rows were tried above their bound: how many did the table not hold?
+        unsigned long long given_up = 0;
+        vg_download_bytes(&given_up, R.ctr.p + MC_SPILL, sizeof given_up, s);
+        VG_HIP(hipStreamSynchronize(s));
+        ns = (int64_t)given_up;
+        if (ns > (int64_t)pl.h[MC_TRY]) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: more spill rows than rows above the table (internal error)");
     }
-    // ---- clusters: the components of the last matrix, labelled as single linkage labels them; the matrix itself if it is wanted
-    const int64_t storage = (int64_t)M.ent.n;
-    const bool want = m_off != nullptr;
+    if (ns) mcl_spill(n, ns, M, N, pl, R.P, R.ctr, s);
+    M = std::move(N);
+    ++sts.iterations; sts.lds_rows += n - ns; sts.spill_rows += ns;
+    mcl_make_plan(n, M, R.slots, R.P.max_row, R.ctr, s, pl);
+    sts.chaos = pl.h[MC_CHAOS];
+    char note[128];
+    snprintf(note, sizeof note, "mcl iteration %lld: chaos %llu, %lld + %lld LDS rows, %lld spill rows", (long long)sts.iterations,
+             (unsigned long long)sts.chaos, (long long)nw, (long long)(ng - ns), (long long)ns);
+    vg_host_mark(note);
+}
+// the (row, column) keys and the values of the last matrix's entries, for the CSR output
+struct mcl_entries { dbuf<uint64_t> key; dbuf<uint32_t> val; };
+// The clusters: the components of the last matrix, labelled as single linkage labels them.  want: its entries -> ent too.
+void mcl_components(mcl_run& R, const mcl_matrix& M, bool want, int32_t* label, int32_t* representative, vg_mcl_stats& sts, mcl_entries& ent) {
+    const int64_t n = R.n, storage = (int64_t)M.ent.n; hipStream_t s = R.s;
     edge_graph hg;
     hg.ukeys.alloc((size_t)storage); hg.m = storage;
-    dbuf<uint64_t> ckey, ckey2; dbuf<uint32_t> cval, cval2; dbuf<unsigned long long> tally(2);
+    dbuf<uint64_t>& ckey = ent.key; dbuf<uint32_t>& cval = ent.val; dbuf<unsigned long long> tally(2);
     unsigned long long ht[2] = {};
     {
         vg_prof_scope ps("cluster_mcl_last", (double)storage * 28.0);
         hg.ukeys.zero(s); tally.zero(s);
         if (want) {
-            ckey.alloc((size_t)storage); ckey2.alloc((size_t)storage); cval.alloc((size_t)storage); cval2.alloc((size_t)storage);
+            ckey.alloc((size_t)storage); cval.alloc((size_t)storage);
             VG_HIP(hipMemsetAsync(ckey.p, 0xff, ckey.bytes(), s));
             cval.zero(s);
         }
@@ -2113,29 +2158,43 @@ void mcl_on_device(int64_t n, const uint32_t* q, const uint32_t* r, const double
     }
     sts.nnz = (int64_t)ht[0]; sts.max_row_seen = (int64_t)ht[1];
     if (sts.nnz < n || sts.nnz > storage) throw vg_error(VG_EHIP, "vg_cluster_mcl_graph: the last matrix is inconsistent (internal error)");
-    dbuf<int32_t> root((size_t)n), d_label, d_rep;
+    dbuf<int32_t> root((size_t)n);
     vg_cluster_stats cs{};
     single_on_device(n, hg, s, root, cs);
-    VG_HIP(hipGetLastError());
-    check_roots(n, root, s);
-    labels_on_device(n, root, false, s, d_label, d_rep);
-    VG_HIP(hipGetLastError());
-    d_label.download(label, (size_t)n, s);
-    d_rep.download(representative, (size_t)n, s);
-    VG_HIP(hipStreamSynchronize(s));
-    if (!want) return;
-    // the entries sorted by (row, column); the unused storage (keys of all ones) sorts behind them
+    labels_to_host(n, root, false, s, label, representative);
+}
+// The CSR output of the last matrix: its nnz entries sorted by (row, column) -- the unused storage (keys of all ones) sorts behind
+// them --, then the three arrays, allocated with malloc (the entry frees them if anything throws)
+void mcl_export(mcl_run& R, mcl_entries& ent, int64_t nnz, int64_t** m_off, int32_t** m_col, uint32_t** m_val) {
+    const int64_t n = R.n, storage = (int64_t)ent.key.n; hipStream_t s = R.s;
+    dbuf<uint64_t> key2((size_t)storage); dbuf<uint32_t> val2((size_t)storage);
     vg_prof_scope ps("cluster_mcl_matrix", (double)storage * (12.0 * 2.0 * 2.0));
-    with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, ckey.p, ckey2.p, cval.p, cval2.p, (size_t)storage, 0u, 64u, s); });
-    dbuf<int64_t> d_off((size_t)n + 1); dbuf<int32_t> d_col((size_t)sts.nnz);
-    hipLaunchKernelGGL(k_csr, dim3(grid_of(sts.nnz + 1)), dim3(TPB), 0, s, (const uint64_t*)ckey2.p, sts.nnz, n, d_off.p, d_col.p);
+    with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, ent.key.p, key2.p, ent.val.p, val2.p, (size_t)storage, 0u, 64u, s); });
+    dbuf<int64_t> d_off((size_t)n + 1); dbuf<int32_t> d_col((size_t)nnz);
+    hipLaunchKernelGGL(k_csr, dim3(grid_of(nnz + 1)), dim3(TPB), 0, s, (const uint64_t*)key2.p, nnz, n, d_off.p, d_col.p);
     VG_HIP(hipGetLastError());
     *m_off = (int64_t*)malloc(sizeof(int64_t) * ((size_t)n + 1));
-    *m_col = (int32_t*)malloc(sizeof(int32_t) * (size_t)sts.nnz);
-    *m_val = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)sts.nnz);
+    *m_col = (int32_t*)malloc(sizeof(int32_t) * (size_t)nnz);
+    *m_val = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)nnz);
     if (!*m_off || !*m_col || !*m_val) throw vg_error(VG_ENOMEM, "out of host memory");
-    d_off.download(*m_off, (size_t)n + 1, s); d_col.download(*m_col, (size_t)sts.nnz, s); cval2.download(*m_val, (size_t)sts.nnz, s);
+    d_off.download(*m_off, (size_t)n + 1, s); d_col.download(*m_col, (size_t)nnz, s); val2.download(*m_val, (size_t)nnz, s);
     VG_HIP(hipStreamSynchronize(s));
+}
+// Markov clustering of the edge graph, which is released once the start matrix stands; m_off null: no matrix output
+void mcl_on_device(int64_t n, edge_graph& eg, hipStream_t s, const vg_mcl_params& prm, int32_t* label, int32_t* representative, int64_t** m_off,
+                   int32_t** m_col, uint32_t** m_val, vg_mcl_stats& sts) {
+    mcl_run R{ n, s, mcl_dev{ (int)llrint(2 * prm.inflation), (uint32_t)(uint64_t)std::floor(prm.prune * (double)MCL_ONE), prm.max_row },
+               g_mcl_slots.load() ? g_mcl_slots.load() : MCL_GROUP_SLOTS, {} };
+    const uint64_t eps = (uint64_t)std::floor(prm.chaos_eps * (double)MCL_ONE);
+    mcl_matrix M; mcl_plan pl;
+    mcl_start_matrix(R, eg, M, pl);
+    do {
+        mcl_iterate(R, M, pl, sts);
+        if (sts.chaos <= eps) sts.converged = 1;
+    } while (!sts.converged && sts.iterations < prm.max_iterations);
+    mcl_entries ent;
+    mcl_components(R, M, m_off != nullptr, label, representative, sts, ent);
+    if (m_off) mcl_export(R, ent, sts.nnz, m_off, m_col, m_val);
 }
 }  // namespace
 
@@ -2154,20 +2213,21 @@ extern "C" int vg_cluster_mcl_graph(int64_t n_objects, const uint32_t* q, const 
     if (m_val) *m_val = nullptr;
     try {
         const char* fn = "vg_cluster_mcl_graph";
-        check_rows(fn, n_objects, q, r, w, n_rows);
-        if (n_objects && (!label || !representative)) throw vg_error(VG_EINVAL, std::string(fn) + ": null output");
+        const row_list in{ n_objects, q, r, w, n_rows };
+        check_call(fn, in, n_objects && (!label || !representative) ? "null output" : nullptr);
         if (want && (!m_off || !m_col || !m_val)) throw vg_error(VG_EINVAL, std::string(fn) + ": the matrix outputs are all three or none");
         check_mcl_params(fn, params);
-        check_row_values(fn, n_objects, q, r, w, n_rows);
-        check_unit_weights(fn, w, n_rows, 0.0, "Markov clustering");
-        vg_mcl_stats st_local{}; vg_mcl_stats& sts = stats ? *stats : st_local;
-        sts = vg_mcl_stats{};
+        check_row_values(fn, in);
+        check_unit_weights(fn, in, "Markov clustering");
+        vg_mcl_stats local; vg_mcl_stats& sts = cleared(stats, local);
         if (n_objects == 0) {
             if (want && !(*m_off = (int64_t*)calloc(1, sizeof(int64_t)))) throw vg_error(VG_ENOMEM, "out of host memory");
             return VG_OK;
         }
-        vg_require_device();
-        mcl_on_device(n_objects, q, r, w, n_rows, *params, label, representative, want ? m_off : nullptr, m_col, m_val, sts);
+        edge_graph eg;
+        hipStream_t s = graph_on_device(in, eg);
+        sts.n_edges = eg.m / 2;
+        mcl_on_device(n_objects, eg, s, *params, label, representative, want ? m_off : nullptr, m_col, m_val, sts);
     } catch (...) {
         // (nothing half-filled leaves the call; the error itself is reported below)
         if (want && m_off && m_col && m_val) { free(*m_off); free(*m_col); free(*m_val); *m_off = nullptr; *m_col = nullptr; *m_val = nullptr; }

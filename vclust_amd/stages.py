@@ -68,6 +68,18 @@ CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
 MCL_DEFAULTS = dict(mcl_inflation=2.0, mcl_prune=1e-4, mcl_max_row=128, mcl_chaos_eps=1e-3, mcl_iterations=100)
 
 
+def _cluster_params(algorithm_code, metric, num_alns, representatives, num_threads, verbosity, mins):
+    """vg_cluster_params of cluster() and cluster_stats(); mins: the minimum per filter of CLUSTER_FILTERS."""
+    unknown = set(mins) - set(CLUSTER_FILTERS)
+    if unknown:
+        raise TypeError(f'unknown filter(s): {sorted(unknown)}')
+    p = ClusterParams(algorithm=algorithm_code, metric=metric.encode(), max_num_alns=int(num_alns), representatives=int(bool(representatives)),
+                      num_threads=int(num_threads), verbosity=int(verbosity))
+    for name, val in mins.items():
+        setattr(p, f'min_{name}', float(val))
+    return p
+
+
 def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num_alns=0, representatives=False,
             num_threads=0, verbosity=0, out_linkage=None, levels=None, prior_path=None, prior_repr=False, **mins):
     """clusters.tsv from ani.tsv + its ids file (vg_cluster).  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio= (0 = off);
@@ -84,12 +96,11 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     mcl_chaos_eps and mcl_iterations; it excludes prior_path, out_linkage and levels and returns its stats as a dict (iterations,
     converged, chaos, ...).  Every other call returns None."""
     mcl = {k: mins.pop(k) for k in list(mins) if k in MCL_DEFAULTS}
-    unknown = set(mins) - set(CLUSTER_FILTERS)
-    if unknown:
-        raise TypeError(f'unknown filter(s): {sorted(unknown)}')
+    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
+    # (an unknown filter is the first error; an unknown algorithm is refused below, before p is used)
+    p = _cluster_params(known.get(algorithm, 0), metric, num_alns, representatives, num_threads, verbosity, mins)
     if mcl and algorithm not in FLOW_ALGORITHMS:
         raise ValueError(f'{", ".join(sorted(mcl))}: only with algorithm=\'mcl\'')
-    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
     if prior_path is None and prior_repr:
         raise ValueError('prior_repr needs prior_path')
     if prior_path is not None:
@@ -99,10 +110,6 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
             raise ValueError(f'algorithm {algorithm!r} cannot update a prior clustering (choices: {", ".join(UPDATE_ALGORITHMS)})')
     if algorithm not in known:
         raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
-    p = ClusterParams(algorithm=known[algorithm], metric=metric.encode(), max_num_alns=int(num_alns),
-                      representatives=int(bool(representatives)), num_threads=int(num_threads), verbosity=int(verbosity))
-    for name, val in mins.items():
-        setattr(p, f'min_{name}', float(val))
     paths = (os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)))
     if prior_path is not None:
         st = ClusterUpdateStats()
@@ -132,12 +139,7 @@ def cluster_stats(ani_path, ids_path, clusters_path, out_path, clusters_repr=Fal
     other cluster, members closer to another cluster than to their own).  The rows are those of ani.tsv that pass the filters of
     cluster() (metric, mins, num_alns: give the ones the clustering was made with); clusters_path may be any clustering of the
     ids file, this library's or not; clusters_repr: its label columns hold representative ids."""
-    unknown = set(mins) - set(CLUSTER_FILTERS)
-    if unknown:
-        raise TypeError(f'unknown filter(s): {sorted(unknown)}')
-    p = ClusterParams(algorithm=0, metric=metric.encode(), max_num_alns=int(num_alns), num_threads=int(num_threads), verbosity=int(verbosity))
-    for name, val in mins.items():
-        setattr(p, f'min_{name}', float(val))
+    p = _cluster_params(0, metric, num_alns, False, num_threads, verbosity, mins)
     check(_lib.load().vg_cluster_stats_file(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(clusters_path)),
                                             int(bool(clusters_repr)), C.byref(p), os.fsencode(str(out_path))))
 
