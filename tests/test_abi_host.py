@@ -385,3 +385,151 @@ def test_filter_pairs_equals_fltr_file(tmp_path, golden_dir):
                 printed.add((row, int(ent.split(':')[0]) - 1))
     assert {(int(p['a']), int(p['b'])) for p in kept} == printed and len(printed) == 13
     assert len(gs.filter_pairs(sizes, arr, k=25, min_kmers=20, min_ident=0.999)) < 13
+
+
+# ---------------------------------------------------------------- host text I/O: readers and writers against restatements
+def _pairs_of(arr):
+    return [(int(e['a']), int(e['b'])) for e in arr]
+
+
+@pytest.mark.parametrize('form', ['lf', 'crlf', 'no final newline'])
+def test_read_filter_corpus_in_three_line_forms(tmp_path, golden_dir, form):
+    """One corpus of awkward rows and cells against the golden set at threshold 0.1, with LF and CRLF line ends and without
+    a final newline: an empty row, a value on the threshold (kept), a 17-digit value (the general number parser), a
+    non-numeric column, a column beyond the header, the row's own column, a value without a leading zero, an unknown row."""
+    gs = api.GenomeSet.load([golden_dir / 'multifasta.fna'], multisample=True)
+    nm = gs.names()
+    lines = ['kmer-length: 25 fraction: 1,' + ','.join(nm) + ',',
+             '',
+             nm[1] + ',1:0.5,',
+             nm[2] + ',1:1e-1,2:0.12345678901234567,',
+             nm[3] + ',x:0.9,99:0.9,4:0.9,3:.5,',
+             'not_in_the_set,1:0.9,']
+    eol = '\r\n' if form == 'crlf' else '\n'
+    text = eol.join(lines) + ('' if form == 'no final newline' else eol)
+    (tmp_path / 'f.txt').write_bytes(text.encode())
+    assert _pairs_of(gs.read_filter(tmp_path / 'f.txt', 0.1)) == [(1, 0), (2, 0), (2, 1), (3, 2)]
+
+
+def test_read_filter_large_shuffled_file_equals_restatement(tmp_path):
+    """About 3 000 generated genomes, rows shuffled, a few thousand cells: large enough that the rows are parsed as several
+    byte ranges.  Against a restatement of the format: (a, b) ascending, unique, a > b."""
+    rng = np.random.default_rng(21)
+    n = 3000
+    names = ['gen%04d' % i for i in range(n)]
+    gs = api.GenomeSet.from_codes(np.zeros(4 * n, dtype=np.uint8), np.arange(n + 1, dtype=np.int64) * 4, names)
+    cols = rng.permutation(n)                                   # header position -> genome
+    lines = ['kmer-length: 25 fraction: 1,' + ','.join(names[c] for c in cols) + ',']
+    for r in rng.permutation(n):
+        k = int(rng.integers(0, 5))
+        cells = ['%d:%.6f' % (int(ci) + 1, rng.random()) for ci in sorted(rng.integers(0, n + 3, size=k))]
+        lines.append(names[r] + ',' + ''.join(c + ',' for c in cells))
+    text = '\n'.join(lines) + '\n'
+    assert len(text) - len(lines[0]) > 16 * 4096
+    (tmp_path / 'big.txt').write_text(text)
+    thr = 0.4
+    index = {nm: i for i, nm in enumerate(names)}
+    head = [index.get(x, -1) for x in lines[0].split(',')[1:-1]]
+    want = set()
+    for ln in lines[1:]:
+        f = ln.split(',')
+        row = index[f[0]]
+        for cell in f[1:]:
+            if ':' not in cell:
+                continue
+            ci, val = cell.split(':')
+            ci = int(ci) - 1
+            if 0 <= ci < len(head) and head[ci] >= 0 and head[ci] != row and float(val) >= thr:
+                want.add((max(row, head[ci]), min(row, head[ci])))
+    got = _pairs_of(gs.read_filter(tmp_path / 'big.txt', thr))
+    assert got == sorted(want) and 3000 < len(got) < 6000
+
+
+ANI_COLUMNS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov', 'num_alns', 'len_ratio', 'qlen', 'rlen',
+               'nt_match', 'nt_mismatch']
+
+
+def test_write_ani_bytes_do_not_depend_on_the_thread_count(tmp_path, golden_dir):
+    """40 000 tasks written by one thread and by five: the same bytes, and every cell of all 15 known columns equals the
+    restatement (qidx / ridx against align_order())."""
+    rng = np.random.default_rng(14)
+    gs = api.GenomeSet.load([golden_dir / 'multifasta.fna'], multisample=True)
+    tasks = np.tile(gs.align_tasks(gs.read_filter(None)), 304)[:40000]
+    stats = np.zeros(len(tasks), dtype=api.STAT_DTYPE)
+    stats['aln_len'] = rng.integers(0, 60000, size=len(tasks))
+    stats['n_match'] = (stats['aln_len'] * rng.random(len(tasks))).astype(np.uint32)
+    stats['n_regions'] = rng.integers(0, 40, size=len(tasks))
+    gs.write_ani(tmp_path / 'one.tsv', tasks, stats, columns=ANI_COLUMNS, num_threads=1)
+    gs.write_ani(tmp_path / 'five.tsv', tasks, stats, columns=ANI_COLUMNS, num_threads=5)
+    assert filecmp.cmp(tmp_path / 'one.tsv', tmp_path / 'five.tsv', shallow=False)
+    assert filecmp.cmp(tmp_path / 'one.ids.tsv', tmp_path / 'five.ids.tsv', shallow=False)
+    lens = [int(x) for x in gs.lengths()]; names = gs.names()
+    rank = {int(g): r for r, g in enumerate(gs.align_order())}
+    text = open(tmp_path / 'five.tsv').read().split('\n')
+    assert text[0].split('\t') == ANI_COLUMNS and text[-1] == '' and len(text) == len(tasks) + 2
+    fmt = {}
+    def num(a, b):
+        if (a, b) not in fmt:
+            fmt[(a, b)] = orc.fmt_num(a / b if b else 0.0)
+        return fmt[(a, b)]
+    bad = 0
+    for t, line in enumerate(text[1:-1]):
+        q, r = int(tasks[t]['q']), int(tasks[t]['r'])
+        m, a, nr = (int(x) for x in stats[t]); rm, ra, _ = (int(x) for x in stats[t ^ 1])
+        lq, lr = lens[q], lens[r]
+        want = [str(rank[q]), str(rank[r]), names[q], names[r], num(m + rm, lq + lr), num(m, lq), num(m, a), num(a, lq), num(ra, lr),
+                str(nr), '1' if lq == lr else '%.4f' % (min(lq, lr) / max(lq, lr)), str(lq), str(lr), str(m), str(a - m)]
+        bad += line.split('\t') != want
+    assert bad == 0
+
+
+@pytest.mark.parametrize('case', ['unknown column', 'odd task count', 'couple not mirrored'])
+def test_write_ani_argument_error_leaves_no_file(tmp_path, golden_dir, case):
+    gs = api.GenomeSet.load([golden_dir / 'multifasta.fna'], multisample=True)
+    tasks = gs.align_tasks(gs.read_filter(None))
+    if case == 'odd task count':
+        tasks = tasks[:-1]
+    if case == 'couple not mirrored':
+        tasks[5]['q'] = tasks[5]['r']
+    stats = np.zeros(len(tasks), dtype=api.STAT_DTYPE)
+    out = tmp_path / 'out'; out.mkdir()
+    with pytest.raises(_lib.VclustGpuError) as e:
+        gs.write_ani(out / 'ani.tsv', tasks, stats, columns=['qidx', 'bogus'] if case == 'unknown column' else ['qidx', 'ridx'])
+    assert e.value.code == -1
+    assert list(out.iterdir()) == []
+
+
+def test_write_fltr_bytes_do_not_depend_on_the_host_threads(tmp_path):
+    """A few thousand genomes written under VG_HOST_THREADS=1 and under the default (fresh processes: the count is read once)."""
+    import os
+    import pathlib
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np\n"
+            "from vclust_amd import api\n"
+            "rng = np.random.default_rng(4); n = 5000\n"
+            "gs = api.GenomeSet.from_codes(np.zeros(4 * n, dtype=np.uint8), np.arange(n + 1, dtype=np.int64) * 4, ['gen%%d' %% i for i in range(n)])\n"
+            "pairs = np.zeros(40000, dtype=api.PAIR_DTYPE)\n"
+            "pairs['a'] = rng.integers(0, n, size=len(pairs)); pairs['b'] = rng.integers(0, n, size=len(pairs)); pairs['shared'] = rng.integers(1, 400, size=len(pairs))\n"
+            "gs.write_fltr(sys.argv[1], rng.integers(300, 500, size=n), pairs, min_kmers=5, min_ident=0.9, max_seqs=3)\n"
+            % str(pathlib.Path(__file__).resolve().parent.parent))
+    env = {k: v for k, v in os.environ.items() if k != 'VG_HOST_THREADS'}
+    subprocess.run([sys.executable, '-c', code, str(tmp_path / 'one.txt')], env=dict(env, VG_HOST_THREADS='1'), check=True)
+    subprocess.run([sys.executable, '-c', code, str(tmp_path / 'default.txt')], env=env, check=True)
+    assert filecmp.cmp(tmp_path / 'one.txt', tmp_path / 'default.txt', shallow=False)
+    rows = (tmp_path / 'one.txt').read_text().split('\n')
+    assert len(rows) == 5002 and 3000 < sum(r.count(':') for r in rows[1:]) < 40000
+
+
+def test_filter_pairs_threaded_path_equals_the_small_path():
+    """2^17 + 777 pairs (the count-then-place over threads) against the same pairs sent in slices below 2^17."""
+    rng = np.random.default_rng(9)
+    n = 500; m = (1 << 17) + 777
+    gs = api.GenomeSet.from_codes(np.zeros(4 * n, dtype=np.uint8), np.arange(n + 1, dtype=np.int64) * 4)
+    sizes = rng.integers(100, 400, size=n)
+    pairs = np.zeros(m, dtype=api.PAIR_DTYPE)
+    pairs['a'] = rng.integers(0, n, size=m); pairs['b'] = rng.integers(0, n, size=m); pairs['shared'] = rng.integers(0, 120, size=m)
+    whole = gs.filter_pairs(sizes, pairs, k=25, min_kmers=20, min_ident=0.95)
+    sliced = np.concatenate([gs.filter_pairs(sizes, pairs[o:o + 50000], k=25, min_kmers=20, min_ident=0.95) for o in range(0, m, 50000)])
+    assert np.array_equal(whole, sliced) and m // 10 < len(whole) < m - m // 10

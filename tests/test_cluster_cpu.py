@@ -133,6 +133,42 @@ def test_host_side_validation_before_device_use(case, mutate, line, msg, tmp_pat
     assert e.value.code == -1
 
 
+def big_ani_file(tmp_path, n=3000, rows=60000, seed=17):
+    """An ids file and an ani.tsv above 2 MiB (so that four threads each parse a chunk of it): `rows` rows over n objects, a
+    blank line here and there.  -> (ani path, ids path, the lines of the ani file)"""
+    rng = np.random.default_rng(seed)
+    ids = tmp_path / 'big.ids.tsv'
+    ids.write_text('id\tseq_len\tno_parts\n' + ''.join('object_%06d\t1000\t1\n' % i for i in range(n)))
+    q = rng.integers(0, n, size=rows); r = (q + rng.integers(1, 4, size=rows) * rng.integers(0, 2, size=rows) * 7) % n
+    tani = rng.random(rows); ani = rng.random(rows)
+    lines = ['qidx\tridx\tquery\treference\ttani\tani']
+    for i in range(rows):
+        lines.append('%d\t%d\tobject_%06d\tobject_%06d\t%.6f\t%.6f' % (q[i], r[i], q[i], r[i], tani[i], ani[i]))
+        if i % 997 == 0:
+            lines.append('')
+    return tmp_path / 'big.tsv', ids, lines
+
+
+def test_row_error_names_the_same_line_for_every_thread_count(tmp_path):
+    """A malformed number deep in the last quarter of a file that four threads parse in chunks: the message, with its
+    file:line, is that of one thread, and the line is the right one."""
+    path, ids, lines = big_ani_file(tmp_path)
+    at = len(lines) - len(lines) // 7
+    while not lines[at]:
+        at += 1
+    f = lines[at].split('\t'); f[4] = '0.x5'; lines[at] = '\t'.join(f)
+    path.write_text('\n'.join(lines) + '\n')
+    assert path.stat().st_size > (2 << 20) + (1 << 19)
+    seen = []
+    for threads in (1, 4):
+        with pytest.raises(_lib.VclustGpuError) as e:
+            api.cluster(path, ids, tmp_path / 'c.tsv', tani=0.5, num_threads=threads)
+        assert e.value.code == -1
+        seen.append(str(e.value))
+    assert seen[0] == seen[1] and seen[0].endswith(f"{path}:{at + 1}: malformed tani '0.x5'"), seen
+    assert not (tmp_path / 'c.tsv').exists()
+
+
 def test_filter_columns_are_required_only_when_used(tmp_path, out_dir):
     """`lite` has no query/reference columns; len_ratio / num_alns are needed only when their filter is on."""
     lines = (out_dir / 'ani.tsv').read_text().split('\n')

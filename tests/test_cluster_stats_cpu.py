@@ -128,6 +128,19 @@ def _clusters_file(tmp_path, out_dir, representatives=False):
     return ids, lines
 
 
+# the library's full message of every case below, behind "<file>:<line>: " (recorded before the two label-file parsers became one)
+CLUSTERS_MESSAGES = {
+    'unknown id': "object 'no_such_genome' is not in the ids file",
+    'repeated id': "object 'NC_005091.alt2' is listed twice",
+    'missing id': "object 'NC_005091.alt1' of the ids file is missing",
+    'negative label': "malformed cluster number '-1'",
+    'representative is not a member': "representative 'NC_002486' is not a member of its cluster",
+    'representative outside the ids': "representative 'no_such_genome' is not in the ids file",
+    'bad header': 'malformed header (expected object<TAB>cluster, then further label columns)',
+    'a field too many': 'malformed line (expected 2 fields)',
+}
+
+
 @pytest.mark.parametrize('case,representatives,mutate,line,msg', [
     ('unknown id', False, lambda ls: ls.__setitem__(3, 'no_such_genome\t2'), 4, 'not in the ids file'),
     ('repeated id', False, lambda ls: ls.__setitem__(5, ls[2]), 6, 'listed twice'),
@@ -150,7 +163,7 @@ def test_clusters_file_errors_before_device_use(case, representatives, mutate, l
     assert f'{bad}:{line}: ' in str(ce.value) and msg in str(ce.value)
     with pytest.raises(_lib.VclustGpuError) as e:
         api.cluster_stats(out_dir / 'ani.tsv', out_dir / 'ani.ids.tsv', bad, tmp_path / 's.tsv', clusters_repr=representatives, tani=0.95)
-    assert e.value.code == -1 and f'{bad}:{line}: ' in str(e.value) and msg in str(e.value), str(e.value)
+    assert e.value.code == -1 and str(e.value) == f'libvclust_gpu error -1: {bad}:{line}: {CLUSTERS_MESSAGES[case]}', str(e.value)
     assert not (tmp_path / 's.tsv').exists()
 
 

@@ -222,6 +222,19 @@ def _mutated(tmp_path, out_dir, mutate, representatives):
     return path
 
 
+# the library's full message of every case below, behind "<file>:<line>: " (recorded before the two label-file parsers became one)
+PRIOR_MESSAGES = {
+    'unknown name': "object 'no_such_genome' is not in the ids file",
+    'listed twice': "object 'NC_005091.alt2' is listed twice",
+    'no tab': 'malformed line (expected <object><TAB><cluster>)',
+    'three fields': 'malformed line (expected <object><TAB><cluster>)',
+    'not a number': "malformed cluster number 'x7'",
+    'bad header': 'malformed header (expected object<TAB>cluster)',
+    'representative outside the file': "representative 'no_such_genome' is not an object of this file",
+    'representative is a member': "representative 'NC_005091' is not its own representative",
+}
+
+
 @pytest.mark.parametrize('case,representatives,mutate,line,msg', [
     ('unknown name', False, lambda ls: ls.__setitem__(3, 'no_such_genome\t2'), 4, 'not in the ids file'),
     ('listed twice', False, lambda ls: ls.__setitem__(5, ls[2]), 6, 'listed twice'),
@@ -248,7 +261,7 @@ def test_prior_file_errors_before_device_use(case, representatives, mutate, line
     assert not (tmp_path / 'c.tsv').exists()
     with pytest.raises(_lib.VclustGpuError) as e:
         api.cluster_update(out_dir / 'ani.tsv', out_dir / 'ani.ids.tsv', bad, tmp_path / 'c.tsv', prior_repr=representatives, tani=0.95)
-    assert e.value.code == -1 and f'{bad}:{line}: ' in str(e.value)
+    assert e.value.code == -1 and str(e.value) == f'libvclust_gpu error -1: {bad}:{line}: {PRIOR_MESSAGES[case]}'
 
 
 def test_restatement_reads_both_forms_of_the_prior_file(tmp_path, out_dir):

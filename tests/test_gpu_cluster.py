@@ -64,6 +64,17 @@ def test_golden_files_equal_restatement(api, out_dir, tmp_path, algo, repr_, met
     assert out.read_bytes() == cr.run(out_dir / 'ani.tsv', out_dir / 'ani.ids.tsv', algo, metric, representatives=repr_, **{metric: thr})
 
 
+def test_large_file_parsed_by_four_threads_equals_restatement(api, tmp_path):
+    """About 3 000 objects and 60 000 rows in a file above 2 MiB (every one of four threads parses a chunk), blank lines, rows
+    below an active minimum: the clusters of the restatement on the same file."""
+    from test_cluster_cpu import big_ani_file
+    path, ids, lines = big_ani_file(tmp_path)
+    path.write_text('\n'.join(lines) + '\n')
+    assert path.stat().st_size > (2 << 20) + (1 << 19)
+    api.cluster(path, ids, tmp_path / 'c.tsv', algorithm='single', tani=0.97, ani=0.3, num_threads=4)
+    assert (tmp_path / 'c.tsv').read_bytes() == cr.run(path, ids, 'single', 'tani', tani=0.97, ani=0.3)
+
+
 def _check(api, n, q, r, w, algo):
     label, rep, stats = api.cluster_graph(n, q, r, w, algo)
     want_label, want_rep = cr.cluster_graph(n, list(zip(map(int, q), map(int, r), map(float, w))), algo)

@@ -254,7 +254,7 @@ class GenomeSet:
                     pos_bits=pb.value, tag_bits=tg.value, path=path.value)
 
     def write_ani(self, out_path, tasks, stats, regions=None, columns=None, out_aln=None, lz=None,
-                  out_filters=None):
+                  out_filters=None, num_threads=0):
         tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
         stats = np.ascontiguousarray(stats, dtype=STAT_DTYPE)
         columns = list(columns or ALIGN_FIELDS[:11])
@@ -266,6 +266,7 @@ class GenomeSet:
         p.out_aln_path = os.fsencode(str(out_aln)) if out_aln else None
         p.out_columns = cols
         p.n_out_columns = len(columns)
+        p.num_threads = int(num_threads)
         reg_ptr, nreg = None, 0
         if regions is not None:
             regions = np.ascontiguousarray(regions, dtype=REGION_DTYPE)

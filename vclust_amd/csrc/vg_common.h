@@ -5,6 +5,9 @@
 #include <cstdlib>
 #include <stdint.h>
 #include <string>
+#include <string_view>
+#include <atomic>
+#include <algorithm>
 #include <functional>
 #include <vector>
 #include <stdexcept>
@@ -193,6 +196,12 @@ const char* vg_dev_getenv(const char* name);      // a developer switch: read on
 void vg_host_mark(const char* what);
 double vg_alloc_wait_ms();            // wall time this process has spent inside the driver's device-allocation calls
 template <class F> void vg_parallel_chunks(int64_t n, int n_thr, F fn);
+// fn(i) for every i in [0, n): the items are handed out by a shared counter to n_threads threads, the caller one of them (work
+// items of uneven cost; at most n threads).  Every thread is joined; an exception ends the hand-out, and the first one (by
+// thread index) is rethrown on the caller.
+template <class F> void vg_parallel_for(int64_t n, int n_threads, F fn);
+// the file `path` made of `parts` in order; closed on every way out, VG_EIO "cannot write <path>" / "write error on <path>" (vg_io.cpp)
+void vg_write_file(const char* path, const std::vector<std::string_view>& parts);
 // append one genome given codes (0..3, >3 = N); used by the FASTA reader and vg_genomes_from_codes
 void vg_genomes_append(vg_genomes* g, const std::string& name, const uint8_t* codes, int64_t len, int n_parts);
 void vg_genomes_finish(vg_genomes* g);
@@ -257,5 +266,21 @@ template <class F> void vg_parallel_chunks(int64_t n, int n_thr, F fn) {
     for (int t = 0; t < n_thr; ++t) th.emplace_back([&, t]() {
         try { fn(n * t / n_thr, n * (t + 1) / n_thr, t); } catch (...) { err[(size_t)t] = std::current_exception(); } });
     for (auto& x : th) x.join();
+    for (auto& e : err) if (e) std::rethrow_exception(e);
+}
+template <class F> void vg_parallel_for(int64_t n, int n_threads, F fn) {
+    std::atomic<int64_t> next(0);
+    std::vector<std::exception_ptr> err((size_t)std::max(1, n_threads));
+    auto work = [&](int t) {
+        try { for (;;) { const int64_t i = next.fetch_add(1); if (i >= n) break; fn(i); } }
+        catch (...) { err[(size_t)t] = std::current_exception(); next.store(n); }
+    };
+    std::vector<std::thread> th;
+    struct joiner { std::vector<std::thread>& th; ~joiner() { for (auto& x : th) x.join(); } };
+    {
+        joiner j{ th };                  // (a thread that cannot be started leaves the started ones joined)
+        for (int t = 1; t < std::min<int64_t>(n_threads, n); ++t) th.emplace_back(work, t);
+        work(0);
+    }
     for (auto& e : err) if (e) std::rethrow_exception(e);
 }

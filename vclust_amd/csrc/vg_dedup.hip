@@ -118,20 +118,6 @@ const char* pack_nibbles(const char* q, const char* end, uint32_t* out, uint32_t
     return nullptr;
 }
 
-template <class F> void parallel_for(int64_t n, int n_threads, F fn) {
-    std::atomic<int64_t> next(0);
-    std::vector<std::exception_ptr> err((size_t)std::max(1, n_threads));
-    auto work = [&](int t) {
-        try { for (;;) { const int64_t i = next.fetch_add(1); if (i >= n) break; fn(i); } }
-        catch (...) { err[(size_t)t] = std::current_exception(); next.store(n); }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < std::min<int64_t>(n_threads, n); ++t) th.emplace_back(work, t);
-    work(0);
-    for (auto& x : th) x.join();
-    for (auto& e : err) if (e) std::rethrow_exception(e);
-}
-
 // the packed records, host and device
 struct packed_set {
     int64_t n = 0;
@@ -190,7 +176,7 @@ void pack_and_upload(const std::vector<std::pair<const char*, const char*>>& seq
     struct join_guard { std::thread& t; std::mutex& m; std::condition_variable& cv; bool& done;
                         ~join_guard() { { std::lock_guard<std::mutex> lk(m); done = true; } cv.notify_all(); if (t.joinable()) t.join(); } } jg{ uploader, mu, cv, done };
     std::vector<const char*> bad((size_t)n, nullptr);
-    parallel_for(n, n_threads, [&](int64_t i) {
+    vg_parallel_for(n, n_threads, [&](int64_t i) {
         int64_t ns = 0;
         uint32_t* o = ps.words.data() + ps.woff[(size_t)i];
         bad[(size_t)i] = pack_nibbles(seq[(size_t)i].first, seq[(size_t)i].second, o, ps.words.data() + ps.woff[(size_t)i + 1], &ns);
@@ -1206,12 +1192,6 @@ std::string first_token(const char* b, const char* e) {
     const char* q = b; while (q < e && *q != ' ' && *q != '\t' && *q != '\r') ++q;
     return std::string(b, q);
 }
-void write_all(const char* path, const std::vector<std::pair<const char*, size_t>>& parts) {
-    FILE* f = fopen(path, "wb");
-    if (!f) throw vg_error(VG_EIO, std::string("cannot create ") + path);
-    for (auto& p : parts) if (p.second && fwrite(p.first, 1, p.second, f) != p.second) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
-    if (fclose(f) != 0) throw vg_error(VG_EIO, std::string("write error on ") + path);
-}
 // the output FASTA: the kept records in input order, assembled in memory by all threads, then written plain or as gzip members
 // of GZ_BLOCK uncompressed bytes each (compressed in parallel: the bytes do not depend on the thread count)
 void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, int level, int T) {
@@ -1225,7 +1205,7 @@ void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<st
     std::vector<int64_t> at(kept.size() + 1, 0);
     for (size_t k = 0; k < kept.size(); ++k) at[k + 1] = at[k] + size_of(in.recs[(size_t)kept[k]]);
     std::vector<char, no_init_alloc<char>> buf((size_t)at.back());
-    parallel_for((int64_t)kept.size(), T, [&](int64_t k) {
+    vg_parallel_for((int64_t)kept.size(), T, [&](int64_t k) {
         const vg_fasta_rec& r = in.recs[(size_t)kept[(size_t)k]];
         char* o = buf.data() + at[(size_t)k];
         const std::string& pf = prefix[(size_t)r.file];
@@ -1234,10 +1214,10 @@ void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<st
         memcpy(o, r.seq, (size_t)(r.end - r.seq)); o += r.end - r.seq;
         if (r.end > r.seq && r.end[-1] != '\n') *o++ = '\n';
     });
-    if (level <= 0) { write_all(path, { { buf.data(), buf.size() } }); return; }
+    if (level <= 0) { vg_write_file(path, { { buf.data(), buf.size() } }); return; }
     const int64_t nb = std::max<int64_t>(1, ((int64_t)buf.size() + (int64_t)GZ_BLOCK - 1) / (int64_t)GZ_BLOCK);
     std::vector<std::vector<unsigned char>> member((size_t)nb);
-    parallel_for(nb, T, [&](int64_t b) {
+    vg_parallel_for(nb, T, [&](int64_t b) {
         const size_t lo = (size_t)b * GZ_BLOCK, len = std::min(GZ_BLOCK, buf.size() - std::min(buf.size(), lo));
         z_stream zs; memset(&zs, 0, sizeof zs);
         if (deflateInit2(&zs, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw vg_error(VG_ENOMEM, "deflateInit2 failed");
@@ -1250,9 +1230,9 @@ void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<st
         deflateEnd(&zs);
         if (rc != Z_STREAM_END) throw vg_error(VG_EIO, "gzip compression failed");
     });
-    std::vector<std::pair<const char*, size_t>> parts;
+    std::vector<std::string_view> parts;
     for (auto& m : member) parts.emplace_back((const char*)m.data(), m.size());
-    write_all(path, parts);
+    vg_write_file(path, parts);
 }
 // offset: nullptr, or (circular and contained mode) the fourth column; repeat: nullptr, or (terminal repeats) the fifth and
 // sixth: the removed record's and the kept record's
@@ -1269,7 +1249,7 @@ void write_duplicates(const char* path, const vg_fasta_text& in, const std::vect
         if (repeat) { out += '\t'; out += std::to_string(repeat[i]); out += '\t'; out += std::to_string(repeat[rep[i]]); }
         out += '\n';
     }
-    write_all(path, { { out.data(), out.size() } });
+    vg_write_file(path, { out });
 }
 // the array arguments of an array-level call, before anything is packed: fn names the call in the messages, outputs: its output arrays are all there
 void check_seq_arrays(const std::string& fn, const char* ascii, const int64_t* offsets, int64_t n, bool outputs) {

@@ -130,14 +130,6 @@ bool bgzf_blocks(const unsigned char* p, size_t n, std::vector<bgzf_block>& bloc
     *total = out;
     return !blocks.empty();
 }
-template <class F> void parallel_for(int64_t n, int n_threads, F fn) {
-    std::atomic<int64_t> next(0);
-    auto work = [&]() { for (;;) { int64_t i = next.fetch_add(1); if (i >= n) break; fn(i); } };
-    std::vector<std::thread> th;
-    for (int t = 1; t < std::min<int64_t>(n_threads, n); ++t) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
-}
 
 bool slurp_bgzf(const std::string& path, FILE* f, filebuf& fb, int n_threads) {
     fseek(f, 0, SEEK_END); const long long sz = ftell(f);
@@ -157,7 +149,7 @@ bool slurp_bgzf(const std::string& path, FILE* f, filebuf& fb, int n_threads) {
     std::atomic<bool> bad(false);
     // runs of 64 blocks (<= 4 MiB of text) per work item
     const int64_t n_items = ((int64_t)blocks.size() + 63) / 64;
-    parallel_for(n_items, n_threads, [&](int64_t it) {
+    vg_parallel_for(n_items, n_threads, [&](int64_t it) {
         z_stream zs; memset(&zs, 0, sizeof zs);
         if (inflateInit2(&zs, -15) != Z_OK) { bad = true; return; }
         for (size_t b = (size_t)it * 64; b < std::min(blocks.size(), (size_t)(it + 1) * 64) && !bad.load(std::memory_order_relaxed); ++b) {
@@ -253,7 +245,7 @@ void find_records(const filebuf& fb, std::vector<record>& out, int n_threads) {
     // record starts: '>' at the beginning of a line, found chunk-parallel with memchr
     const int T = std::max(1, n_threads);
     std::vector<std::vector<const char*>> starts(T);
-    auto scan = [&](int t) {
+    vg_parallel_for(T, T, [&](int64_t t) {
         const char* lo = p + fb.size() * t / T; const char* hi = p + fb.size() * (t + 1) / T;
         // piece by piece: the pages of a piece are mapped in one call (instead of one minor fault per 64 KB) and scanned
         // while they are hot.  Small pieces on purpose: a populate call holds the address-space lock shared, and the
@@ -275,16 +267,12 @@ void find_records(const filebuf& fb, std::vector<record>& out, int n_threads) {
                 q = g + 1;
             }
         }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < T; ++t) th.emplace_back(scan, t);
-    scan(0);
-    for (auto& x : th) x.join();
+    });
     std::vector<const char*> all;
     for (auto& v : starts) all.insert(all.end(), v.begin(), v.end());
     out.resize(all.size());
     // (the header line of every record is touched here: 10^5 cache misses when done by one thread)
-    parallel_for(((int64_t)all.size() + 1023) / 1024, T, [&](int64_t c) {
+    vg_parallel_for(((int64_t)all.size() + 1023) / 1024, T, [&](int64_t c) {
         for (size_t i = (size_t)c * 1024; i < std::min(all.size(), (size_t)(c + 1) * 1024); ++i) {
             record& r = out[i];
             r.hdr = all[i] + 1;
@@ -373,7 +361,7 @@ static void genomes_load_impl(const char* const* paths, int n_paths, int multisa
     std::vector<filebuf>& bufs = in_state->bufs;
     {
         std::string first_err; std::atomic<bool> failed(false);
-        parallel_for(n_paths, T, [&](int64_t i) {
+        vg_parallel_for(n_paths, T, [&](int64_t i) {
             if (failed.load()) return;
             try { slurp(paths[i], bufs[(size_t)i], std::max(1, T / (int)std::min<int64_t>(n_paths, T))); }
             catch (const std::exception& e) { if (!failed.exchange(true)) first_err = e.what(); }
@@ -435,7 +423,7 @@ static void genomes_load_impl(const char* const* paths, int n_paths, int multisa
     g->packed.resize((size_t)(g->padded_total() / 16)); g->nmask.resize((size_t)(g->padded_total() / 32));
     {
         const int64_t chunk = 1 << 20, np = ((int64_t)g->packed.size() + chunk - 1) / chunk, nm = ((int64_t)g->nmask.size() + chunk - 1) / chunk;
-        parallel_for(np + nm, T, [&](int64_t c) {
+        vg_parallel_for(np + nm, T, [&](int64_t c) {
             std::vector<uint32_t, no_init_alloc<uint32_t>>& v = c < np ? g->packed : g->nmask;
             const int64_t lo = (c < np ? c : c - np) * chunk, hi = std::min<int64_t>(lo + chunk, (int64_t)v.size());
 #ifdef MADV_POPULATE_WRITE
@@ -489,7 +477,7 @@ static void genomes_load_impl(const char* const* paths, int n_paths, int multisa
     }
     struct join_guard { std::thread& t; std::mutex& m; std::condition_variable& cv; bool& done;
                         ~join_guard() { { std::lock_guard<std::mutex> lk(m); done = true; } cv.notify_all(); if (t.joinable()) t.join(); } } jg{ uploader, up_mu, up_cv, up_done };
-    parallel_for(n_g, T, [&](int64_t gi) {
+    vg_parallel_for(n_g, T, [&](int64_t gi) {
         const gdesc& d = gd[(size_t)gi];
         int64_t at = g->base_off[(size_t)gi]; bool any_n = false;
         for (size_t r = d.r0; r < d.r1; ++r) {
@@ -656,7 +644,7 @@ void vg_fasta_read(const char* const* paths, int n_paths, int n_threads, vg_fast
     out.bufs = std::shared_ptr<void>(bufs, [](void* p) { delete (std::vector<filebuf>*)p; });
     {
         std::string first_err; std::atomic<bool> failed(false);
-        parallel_for(n_paths, T, [&](int64_t i) {
+        vg_parallel_for(n_paths, T, [&](int64_t i) {
             if (failed.load()) return;
             try { slurp(paths[i], (*bufs)[(size_t)i], std::max(1, T / (int)std::min<int64_t>(n_paths, T))); }
             catch (const std::exception& e) { if (!failed.exchange(true)) first_err = e.what(); }

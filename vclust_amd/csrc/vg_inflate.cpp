@@ -6,14 +6,13 @@
 // the CRC-32 of the members to worker threads (chunks + crc32_combine).  It is a FAST PATH WITH A VERDICT: every
 // member's CRC-32 and length are checked, and on anything it does not like (a damaged or unusual stream, a mismatch) it
 // returns false and the caller inflates the file with zlib as before -- a wrong byte cannot get through unnoticed.
+#include "vg_common.h"
 #include <zlib.h>
 #include <stdint.h>
 #include <stddef.h>
 #include <algorithm>
-#include <atomic>
 #include <string.h>
 #include <stdlib.h>
-#include <thread>
 #include <vector>
 
 namespace {
@@ -300,10 +299,8 @@ bool vg_fast_gunzip(const unsigned char* in, size_t n, int n_threads, char** out
         struct piece { size_t a, b; uint32_t crc; };
         std::vector<piece> pieces;
         for (const member& m : members) { if (m.o1 == m.o0) continue; for (size_t a = m.o0; a < m.o1; a += chunk) pieces.push_back({ a, std::min(m.o1, a + chunk), 0 }); }
-        std::atomic<size_t> next(0);
-        auto work = [&] { for (;;) { const size_t i = next.fetch_add(1); if (i >= pieces.size()) break; pieces[i].crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)out.p + pieces[i].a, (uInt)(pieces[i].b - pieces[i].a)); } };
-        std::vector<std::thread> th; for (int t = 1; t < std::max(1, std::min(n_threads, 32)); ++t) th.emplace_back(work);
-        work(); for (auto& x : th) x.join();
+        vg_parallel_for((int64_t)pieces.size(), std::min(n_threads, 32), [&](int64_t i) {
+            pieces[(size_t)i].crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef*)out.p + pieces[(size_t)i].a, (uInt)(pieces[(size_t)i].b - pieces[(size_t)i].a)); });
         size_t pi = 0;
         for (const member& m : members) {
             uLong c = crc32(0L, Z_NULL, 0);

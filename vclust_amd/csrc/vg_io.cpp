@@ -15,8 +15,6 @@
 #include <unordered_map>
 #include <mutex>
 #include <numeric>
-#include <atomic>
-#include <thread>
 #include <charconv>
 #include <string_view>
 #include <fcntl.h>
@@ -95,6 +93,83 @@ int vg_fmt_len_ratio(int64_t a, int64_t b, char* buf) {
     return snprintf(buf, 32, "%.4f", (double)std::min(a, b) / (double)std::max(a, b));
 }
 
+// ---------------------------------------------------------------- files: the three shared pieces
+void vg_write_file(const char* path, const std::vector<std::string_view>& parts) {
+    struct closer { void operator()(FILE* f) const { fclose(f); } };
+    std::unique_ptr<FILE, closer> f(fopen(path, "w"));
+    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + path);
+    bool ok = true;
+    for (const std::string_view& p : parts) ok = ok && (p.empty() || fwrite(p.data(), 1, p.size(), f.get()) == p.size());
+    ok = fclose(f.release()) == 0 && ok;
+    if (!ok) throw vg_error(VG_EIO, std::string("write error on ") + path);
+}
+
+namespace {
+// head, then the rows [0, n) formatted in pieces of `piece` rows by n_threads threads (fn(lo, hi, out) appends the rows
+// lo .. hi - 1 to out) and written in order: the pieces are cut by row number alone, so the bytes do not depend on n_threads
+template <class F> void write_rows(const char* path, const std::string& head, int64_t n, int64_t piece, int n_threads, F fn) {
+    std::vector<std::string> text((size_t)((n + piece - 1) / piece));
+    vg_parallel_for((int64_t)text.size(), n_threads, [&](int64_t c) { fn(c * piece, std::min(n, (c + 1) * piece), text[(size_t)c]); });
+    std::vector<std::string_view> parts{ head };
+    parts.insert(parts.end(), text.begin(), text.end());
+    vg_write_file(path, parts);
+}
+
+// a whole text file, read-only: a regular non-empty file is mapped, anything else (a pipe, a file without a size) is read into
+// memory; an empty file has n == 0.  `what` goes into the one error, "cannot open <what><path>"
+struct text_file {
+    const char* p = nullptr; size_t n = 0;
+    explicit text_file(const char* path, const char* what = "") {
+        const int fd = open(path, O_RDONLY);
+        if (fd < 0) throw vg_error(VG_EIO, std::string("cannot open ") + what + path);
+        struct closer { int fd; ~closer() { close(fd); } } cl{ fd };
+        struct stat sb;
+        if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
+            m = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m != MAP_FAILED) { n = (size_t)sb.st_size; (void)madvise(m, n, MADV_WILLNEED); p = (const char*)m; return; }
+        }
+        char buf[1 << 16];
+        for (ssize_t r; (r = read(fd, buf, sizeof buf)) > 0;) own.append(buf, (size_t)r);
+        p = own.data(); n = own.size();
+    }
+    ~text_file() { if (m != MAP_FAILED) munmap(m, n); }
+    text_file(const text_file&) = delete; text_file& operator=(const text_file&) = delete;
+    const char* end() const { return p + n; }
+    const char* line_end(const char* a) const { const char* e = (const char*)memchr(a, '\n', (size_t)(end() - a)); return e ? e : end(); }
+    int64_t line_of(const char* at) const {          // 1-based line number of a position (errors only)
+        int64_t l = 1;
+        for (const char* x = p; (x = (const char*)memchr(x, '\n', (size_t)(at - x))) != nullptr; ++x) ++l;
+        return l;
+    }
+private:
+    void* m = MAP_FAILED; std::string own;
+};
+// fn(line number from 1, the line without its '\n' and without a '\r' in front of that) for every line; nothing is skipped
+template <class F> void for_each_line(const text_file& f, F fn) {
+    int64_t line = 0;
+    for (const char* a = f.p; a < f.end();) {
+        const char* e = f.line_end(a);
+        fn(++line, std::string_view(a, (size_t)((e > a && e[-1] == '\r' ? e - 1 : e) - a)));
+        a = e + 1;
+    }
+}
+void split_fields(std::string_view text, char sep, std::vector<std::string_view>& fields) {
+    fields.clear();
+    for (size_t a = 0;;) {
+        const size_t t = text.find(sep, a);
+        fields.push_back(text.substr(a, t == std::string_view::npos ? t : t - a));
+        if (t == std::string_view::npos) break;
+        a = t + 1;
+    }
+}
+// an array the C ABI hands to its caller (vg_free): never of size 0
+template <class T> std::unique_ptr<T, decltype(&free)> host_array(size_t n) {
+    std::unique_ptr<T, decltype(&free)> o((T*)malloc(sizeof(T) * std::max<size_t>(1, n)), &free);
+    if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
+    return o;
+}
+}  // namespace
+
 // ---------------------------------------------------------------- fltr.txt
 extern "C" int vg_filter_pairs(int k, int min_kmers, double min_ident, const int64_t* set_sizes, int64_t n_genomes,
                                const vg_pair_count* pairs, int64_t n_pairs, vg_pair_count** out, int64_t* n_out) {
@@ -106,9 +181,9 @@ extern "C" int vg_filter_pairs(int k, int min_kmers, double min_ident, const int
     vg_host_mark("filter_pairs: enter");
     const double E = std::exp((min_ident - 1.0) * (double)k);
     const double Jstar = E < 2.0 ? E / (2.0 - E) : INFINITY;
-    vg_pair_count* o = (vg_pair_count*)malloc(sizeof(vg_pair_count) * std::max<size_t>(1, (size_t)n_pairs));
-    if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
-    size_t total = 0;
+    auto kept_pairs = host_array<vg_pair_count>((size_t)n_pairs);
+    vg_pair_count* const o = kept_pairs.get();
+    int64_t total = 0;
     auto keeps = [&](const vg_pair_count& p) {
         if ((int64_t)p.a >= n_genomes || (int64_t)p.b >= n_genomes) throw vg_error(VG_EINVAL, "pair id out of range");
         if ((int64_t)p.shared < min_kmers) return false;
@@ -118,22 +193,19 @@ extern "C" int vg_filter_pairs(int k, int min_kmers, double min_ident, const int
         if (std::isfinite(Jstar) && std::fabs(j - Jstar) > 1e-9 * Jstar) return j > Jstar;
         return vg_ani_shorter(p.shared, set_sizes[p.a], set_sizes[p.b], k) >= min_ident;
     };
-    try {
-        // (10^5 .. 10^6 pairs -- every rank of a sharded call does this between the stages --: chunks over a few threads, kept pairs counted, then written in order)
-        const int T = n_pairs >= (1 << 17) ? std::max(1, std::min(vg_host_threads(), 8)) : 1;
-        if (T == 1) { for (int64_t i = 0; i < n_pairs; ++i) if (keeps(pairs[i])) o[total++] = pairs[i]; }
-        else {
-            std::vector<int64_t> kept((size_t)T + 1, 0);
-            std::vector<uint8_t> flag((size_t)n_pairs);
-            vg_parallel_chunks(n_pairs, T, [&](int64_t a, int64_t b, int t) { int64_t c = 0; for (int64_t i = a; i < b; ++i) { flag[(size_t)i] = keeps(pairs[i]); c += flag[(size_t)i]; } kept[(size_t)t + 1] = c; });
-            for (int t = 0; t < T; ++t) kept[(size_t)t + 1] += kept[(size_t)t];
-            vg_parallel_chunks(n_pairs, T, [&](int64_t a, int64_t b, int t) { int64_t at = kept[(size_t)t]; for (int64_t i = a; i < b; ++i) if (flag[(size_t)i]) o[at++] = pairs[i]; });
-            total = (size_t)kept[(size_t)T];
-        }
-    } catch (...) { free(o); throw; }
+    // (10^5 .. 10^6 pairs -- every rank of a sharded call does this between the stages --: chunks over a few threads, kept pairs counted, then written in order)
+    const int T = n_pairs >= (1 << 17) ? std::max(1, std::min(vg_host_threads(), 8)) : 1;
+    if (T == 1) { for (int64_t i = 0; i < n_pairs; ++i) if (keeps(pairs[i])) o[total++] = pairs[i]; }
+    else {
+        std::vector<int64_t> kept((size_t)T + 1, 0);
+        std::vector<uint8_t> flag((size_t)n_pairs);
+        vg_parallel_chunks(n_pairs, T, [&](int64_t a, int64_t b, int t) { int64_t c = 0; for (int64_t i = a; i < b; ++i) { flag[(size_t)i] = keeps(pairs[i]); c += flag[(size_t)i]; } kept[(size_t)t + 1] = c; });
+        for (int t = 0; t < T; ++t) kept[(size_t)t + 1] += kept[(size_t)t];
+        vg_parallel_chunks(n_pairs, T, [&](int64_t a, int64_t b, int t) { int64_t at = kept[(size_t)t]; for (int64_t i = a; i < b; ++i) if (flag[(size_t)i]) o[at++] = pairs[i]; });
+        total = kept[(size_t)T];
+    }
     vg_host_mark("filter_pairs: done");
-    struct { size_t n; size_t size() const { return n; } } keep{ total };
-    *out = o; *n_out = (int64_t)keep.size();
+    *out = kept_pairs.release(); *n_out = total;
     VG_API_END
 }
 
@@ -156,16 +228,11 @@ extern "C" int vg_write_fltr(const vg_genomes* g, int k, double fraction, int mi
             if (a < ng) cells[cur[a]++] = { bb, pairs[i].shared };
         }
     }
-    FILE* f = fopen(out_path, "w");
-    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + out_path);
-    fprintf(f, "kmer-length: %d fraction: %g ,", k, fraction);
-    for (int i = 0; i < g->n; ++i) fprintf(f, "%s,", g->names[i].c_str());
-    fputc('\n', f);
-    // rows are formatted by several threads, each its own contiguous range, and written in order
-    const int n_thr = std::max(1, std::min(vg_host_threads(), 16));
-    std::vector<std::string> text((size_t)n_thr);
-    vg_parallel_chunks((int64_t)ng, n_thr, [&](int64_t lo, int64_t hi, int t) {
-        std::string& o = text[(size_t)t];
+    char buf[64];
+    std::string head(buf, (size_t)snprintf(buf, sizeof buf, "kmer-length: %d fraction: %g ,", k, fraction));
+    for (int i = 0; i < g->n; ++i) { head += g->names[i]; head += ','; }
+    head += '\n';
+    write_rows(out_path, head, (int64_t)ng, 512, std::max(1, std::min(vg_host_threads(), 16)), [&](int64_t lo, int64_t hi, std::string& o) {
         struct ent { uint32_t col; double ani; };
         std::vector<ent> row; char buf[64];
         for (int64_t a = lo; a < hi; ++a) {
@@ -189,8 +256,6 @@ extern "C" int vg_write_fltr(const vg_genomes* g, int k, double fraction, int mi
             o += '\n';
         }
     });
-    for (auto& o : text) if (!o.empty() && fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + out_path); }
-    if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + out_path);
     VG_API_END
 }
 
@@ -212,6 +277,106 @@ extern "C" int vg_align_order(const vg_genomes* g, int32_t* order) {
     VG_API_END
 }
 
+// the filter file, in stages: header columns, one cell, a byte range of whole rows, the order of the couples
+namespace {
+// names -> genome ids.  A filter written from the same FASTA lists the genomes in the set's own order: a name is first compared
+// with the name the order predicts (one string compare); the hash map over all names is only built when a name turns up
+// somewhere else.
+struct name_lookup {
+    const vg_genomes* g;
+    std::unordered_map<std::string_view, uint32_t> by_name; std::once_flag by_name_once;
+    bool is(int64_t id, std::string_view name) const { return id >= 0 && id < (int64_t)g->n && g->names[(size_t)id] == name; }
+    int64_t operator()(std::string_view name, int64_t guess) {
+        if (is(guess, name)) return guess;
+        std::call_once(by_name_once, [&] { by_name.reserve((size_t)g->n * 2); for (int i = 0; i < g->n; ++i) by_name.emplace(g->names[i], (uint32_t)i); });
+        auto it = by_name.find(name);
+        return it == by_name.end() ? -1 : (int64_t)it->second;
+    }
+};
+// header: the genome id of every column (-1: a name the set does not have)
+std::vector<int64_t> filter_columns(std::string_view header, name_lookup& lookup) {
+    std::vector<std::string_view> fields;
+    split_fields(header, ',', fields);
+    std::vector<int64_t> col_id;
+    for (size_t c = 1; c + 1 < fields.size(); ++c) col_id.push_back(lookup(fields[c], (int64_t)c - 1));     // (behind the last ',': nothing)
+    return col_id;
+}
+// one cell "column:value" -> the 0-based column (anything but digits: what atol makes of it) and the value
+bool filter_cell(const char* q, const char* fe, long& ci, double& val) {
+    const char* colon = (const char*)memchr(q, ':', (size_t)(fe - q));
+    if (!colon) return false;
+    ci = 0;
+    const char* d = q; bool ok = d < colon;
+    for (; d < colon; ++d) { if (*d < '0' || *d > '9') { ok = false; break; } ci = ci * 10 + (*d - '0'); }
+    if (!ok) ci = atol(std::string(q, colon).c_str());
+    ci -= 1;
+    // value: digits '.' digits with <= 15 digits is exact as mantissa / 10^k; anything else goes to strtod
+    static const double p10[16] = { 1, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15 };
+    uint64_t m = 0; int nd = 0, frac = -1; bool plain = colon + 1 < fe;
+    for (const char* x = colon + 1; x < fe && plain; ++x) {
+        if (*x >= '0' && *x <= '9') { m = m * 10 + (uint64_t)(*x - '0'); ++nd; if (frac >= 0) ++frac; }
+        else if (*x == '.' && frac < 0) frac = 0; else plain = false;
+    }
+    val = plain && nd <= 15 ? (double)m / p10[frac < 0 ? 0 : frac] : atof(std::string(colon + 1, fe).c_str());
+    return true;
+}
+// the rows of the byte range [lo, hi) of the body, cut to whole lines (a line belongs to the range its first byte is in),
+// parsed in place (no per-field strings)
+void filter_rows(const text_file& f, const char* body, size_t lo, size_t hi, const std::vector<int64_t>& col_id, name_lookup& lookup,
+                 double thr, std::vector<vg_pair_count>& out) {
+    const vg_genomes* g = lookup.g;
+    auto behind = [&](const char* nl) { return nl < f.end() ? nl + 1 : nl; };               // (the start of the line behind a line end)
+    auto line_start = [&](size_t at) { return at == 0 ? body : behind(f.line_end(body + at - 1)); };
+    const char* a = line_start(lo); const char* const stop = body + hi < f.end() ? line_start(hi) : f.end();
+    // the row in front of this one, + 1.  The first row of a range has no row in front of it: the first range starts at
+    // genome 0, the others look around the genome their byte offset suggests (rows of similar length: a few thousand name
+    // compares at most) before the hash map over all names is built for them
+    int64_t guess = lo == 0 ? 0 : -1;
+    bool first_row = lo > 0;
+    while (a < stop) {
+        const char* nl = f.line_end(a);
+        const char* q = a; const char* const e = nl > a && nl[-1] == '\r' ? nl - 1 : nl;
+        a = behind(nl);
+        const char* c = (const char*)memchr(q, ',', (size_t)(e - q)); if (!c) continue;
+        const std::string_view name(q, (size_t)(c - q));
+        if (first_row) {
+            first_row = false;
+            const int64_t est = (int64_t)((double)g->n * (double)(a - body) / (double)std::max<size_t>(1, (size_t)(f.end() - body)));
+            for (int64_t d = 0; d <= 4096 && guess < 0; ++d)
+                for (int64_t cand : { est + d, est - d }) if (lookup.is(cand, name)) { guess = cand; break; }
+        }
+        const int64_t row = lookup(name, guess);
+        if (row >= 0) guess = row + 1;
+        for (q = c + 1; q < e;) {
+            const char* n2 = (const char*)memchr(q, ',', (size_t)(e - q)); const char* fe = n2 ? n2 : e;
+            long ci; double val;
+            if (filter_cell(q, fe, ci, val) && row >= 0 && ci >= 0 && ci < (long)col_id.size() && col_id[(size_t)ci] >= 0 && col_id[(size_t)ci] != row && val >= thr) {
+                const uint32_t x = (uint32_t)row, y = (uint32_t)col_id[(size_t)ci];
+                out.push_back({ std::max(x, y), std::min(x, y), 0 });
+            }
+            if (!n2) break;
+            q = n2 + 1;
+        }
+    }
+}
+// ascending (a, b), every couple once: long lists by two stable counting passes over the genome ids (b, then a), short ones
+// by a comparison sort
+void order_couples(std::vector<vg_pair_count>& v, int n) {
+    if ((int64_t)v.size() > 4 * (int64_t)n) {
+        std::vector<vg_pair_count> tmp(v.size()); std::vector<int64_t> at((size_t)n + 1);
+        for (int pass = 0; pass < 2; ++pass) {
+            std::fill(at.begin(), at.end(), 0);
+            for (const auto& e : v) at[(size_t)(pass ? e.a : e.b) + 1]++;
+            for (int i = 0; i < n; ++i) at[(size_t)i + 1] += at[(size_t)i];
+            for (const auto& e : v) tmp[(size_t)at[(size_t)(pass ? e.a : e.b)]++] = e;
+            v.swap(tmp);
+        }
+    } else
+        std::sort(v.begin(), v.end(), [](const vg_pair_count& x, const vg_pair_count& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    v.erase(std::unique(v.begin(), v.end(), [](const vg_pair_count& x, const vg_pair_count& y) { return x.a == y.a && x.b == y.b; }), v.end());
+}
+}  // namespace
+
 extern "C" int vg_read_filter(const vg_genomes* g, const char* path, double thr, vg_pair_count** pairs, int64_t* n_pairs) {
     VG_API_BEGIN
     if (!g || !pairs || !n_pairs) throw vg_error(VG_EINVAL, "vg_read_filter: null argument");
@@ -219,117 +384,21 @@ extern "C" int vg_read_filter(const vg_genomes* g, const char* path, double thr,
     if (!path) {
         for (uint32_t a = 1; a < (uint32_t)g->n; ++a) for (uint32_t b = 0; b < a; ++b) v.push_back({ a, b, 0 });
     } else {
-        FILE* f = fopen(path, "r");
-        if (!f) throw vg_error(VG_EIO, std::string("cannot open filter ") + path);
-        // names -> genome ids.  A filter written from the same FASTA lists the genomes in the set's own order: a name is
-        // first compared with the name the order predicts (one string compare); the hash map over all names is only
-        // built when a name turns up somewhere else.
-        std::unordered_map<std::string, uint32_t> by_name; std::once_flag by_name_once;
-        auto lookup = [&](const char* b, size_t len, int64_t guess) -> int64_t {
-            if (guess >= 0 && guess < (int64_t)g->n) { const std::string& nm = g->names[(size_t)guess]; if (nm.size() == len && memcmp(nm.data(), b, len) == 0) return guess; }
-            std::call_once(by_name_once, [&] { by_name.reserve((size_t)g->n * 2); for (int i = 0; i < g->n; ++i) by_name.emplace(g->names[i], (uint32_t)i); });
-            auto it = by_name.find(std::string(b, len));
-            return it == by_name.end() ? -1 : (int64_t)it->second;
-        };
-        std::string data;
-        { fseek(f, 0, SEEK_END); const long long sz = ftell(f); fseek(f, 0, SEEK_SET);
-          if (sz > 0) { data.resize((size_t)sz); const size_t r = fread(&data[0], 1, (size_t)sz, f); data.resize(r); } }
-        { char buf[1 << 16]; size_t r; while ((r = fread(buf, 1, sizeof buf, f)) > 0) data.append(buf, r); }    // (a file that grew, or no size: the rest)
-        fclose(f);
-        // header: column names -> genome ids
-        std::vector<int64_t> col_id;
-        size_t body = data.find('\n'); if (body == std::string::npos) body = data.size();
-        {
-            size_t he = body; if (he > 0 && data[he - 1] == '\r') --he;
-            size_t c = data.find(',');
-            while (c != std::string::npos && c + 1 < he) {
-                size_t n2 = data.find(',', c + 1); if (n2 == std::string::npos || n2 > he) break;
-                col_id.push_back(lookup(data.data() + c + 1, n2 - c - 1, (int64_t)col_id.size()));
-                c = n2;
-            }
-        }
-        // rows: parsed by several threads, each a range of whole lines, in place (no per-field strings)
-        const char* base = data.data(); const size_t n_data = data.size();
-        const size_t b0 = std::min(body + 1, n_data);
+        const text_file f(path, "filter ");
+        name_lookup lookup{ g };
+        const char* hdr_end = f.line_end(f.p);
+        const std::vector<int64_t> col_id = filter_columns(std::string_view(f.p, (size_t)((hdr_end > f.p && hdr_end[-1] == '\r' ? hdr_end - 1 : hdr_end) - f.p)), lookup);
+        // rows: parsed by several threads, each a range of whole lines
+        const char* body = hdr_end < f.end() ? hdr_end + 1 : hdr_end;
         const int n_thr = std::max(1, std::min(vg_host_threads(), 16));
         std::vector<std::vector<vg_pair_count>> part((size_t)n_thr);
-        vg_parallel_chunks((int64_t)(n_data - b0), n_thr, [&](int64_t lo, int64_t hi, int t) {
-            size_t p0 = b0 + (size_t)lo, p1 = b0 + (size_t)hi;
-            if (lo > 0) { const char* nl = (const char*)memchr(base + p0 - 1, '\n', n_data - (p0 - 1)); p0 = nl ? (size_t)(nl - base) + 1 : n_data; }   // first whole line
-            if ((size_t)hi < n_data - b0) { const char* nl = (const char*)memchr(base + p1 - 1, '\n', n_data - (p1 - 1)); p1 = nl ? (size_t)(nl - base) + 1 : n_data; }
-            std::vector<vg_pair_count>& out = part[(size_t)t];
-            // the row in front of this one, + 1.  The first row of a chunk has no row in front of it: the first chunk starts
-            // at genome 0, the others look around the genome their byte offset suggests (rows of similar length: a few
-            // thousand name compares at most) before the hash map over all names is built for them
-            int64_t guess = lo == 0 ? 0 : -1;
-            bool first_row = lo > 0;
-            while (p0 < p1) {
-                const char* nl = (const char*)memchr(base + p0, '\n', n_data - p0);
-                size_t le = nl ? (size_t)(nl - base) : n_data; const size_t next = le + 1;
-                if (le > p0 && base[le - 1] == '\r') --le;
-                const char* q = base + p0; const char* const e = base + le;
-                p0 = next;
-                const char* c = (const char*)memchr(q, ',', (size_t)(e - q)); if (!c) continue;
-                if (first_row) {
-                    first_row = false;
-                    const size_t len = (size_t)(c - q);
-                    const int64_t est = (int64_t)((double)g->n * (double)(p0 - b0) / (double)std::max<size_t>(1, n_data - b0));
-                    for (int64_t d = 0; d <= 4096 && guess < 0; ++d)
-                        for (int64_t cand : { est + d, est - d }) {
-                            if (cand < 0 || cand >= (int64_t)g->n) continue;
-                            const std::string& nm = g->names[(size_t)cand];
-                            if (nm.size() == len && memcmp(nm.data(), q, len) == 0) { guess = cand; break; }
-                        }
-                }
-                const int64_t row = lookup(q, (size_t)(c - q), guess);
-                if (row >= 0) guess = row + 1;
-                q = c + 1;
-                while (q < e) {
-                    const char* n2 = (const char*)memchr(q, ',', (size_t)(e - q)); const char* fe = n2 ? n2 : e;
-                    const char* colon = (const char*)memchr(q, ':', (size_t)(fe - q));
-                    if (colon) {
-                        long ci = 0; const char* d = q; bool ok = d < colon;
-                        for (; d < colon; ++d) { if (*d < '0' || *d > '9') { ok = false; break; } ci = ci * 10 + (*d - '0'); }
-                        if (!ok) ci = atol(std::string(q, colon).c_str());
-                        ci -= 1;
-                        // value: digits '.' digits with <= 15 digits is exact as mantissa / 10^k; anything else goes to strtod
-                        double val; { uint64_t m = 0; int nd = 0, frac = -1; bool plain = colon + 1 < fe;
-                            for (const char* x = colon + 1; x < fe && plain; ++x) {
-                                if (*x >= '0' && *x <= '9') { m = m * 10 + (uint64_t)(*x - '0'); ++nd; if (frac >= 0) ++frac; }
-                                else if (*x == '.' && frac < 0) frac = 0; else plain = false;
-                            }
-                            if (plain && nd <= 15) { static const double p10[16] = { 1, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15 };
-                                val = (double)m / p10[frac < 0 ? 0 : frac]; }
-                            else val = atof(std::string(colon + 1, fe).c_str()); }
-                        if (row >= 0 && ci >= 0 && ci < (long)col_id.size() && col_id[(size_t)ci] >= 0 && col_id[(size_t)ci] != row && val >= thr) {
-                            const uint32_t x = (uint32_t)row, y = (uint32_t)col_id[(size_t)ci];
-                            out.push_back({ std::max(x, y), std::min(x, y), 0 });
-                        }
-                    }
-                    if (!n2) break;
-                    q = n2 + 1;
-                }
-            }
-        });
+        vg_parallel_chunks((int64_t)(f.end() - body), n_thr, [&](int64_t lo, int64_t hi, int t) { filter_rows(f, body, (size_t)lo, (size_t)hi, col_id, lookup, thr, part[(size_t)t]); });
         for (auto& pv : part) v.insert(v.end(), pv.begin(), pv.end());
-        // ascending (a, b): two stable counting passes over the genome ids (b, then a) instead of a comparison sort
-        if ((int64_t)v.size() > 4 * (int64_t)g->n) {
-            std::vector<vg_pair_count> tmp(v.size()); std::vector<int64_t> at((size_t)g->n + 1);
-            for (int pass = 0; pass < 2; ++pass) {
-                std::fill(at.begin(), at.end(), 0);
-                for (const auto& e : v) at[(size_t)(pass ? e.a : e.b) + 1]++;
-                for (int i = 0; i < g->n; ++i) at[(size_t)i + 1] += at[(size_t)i];
-                for (const auto& e : v) tmp[(size_t)at[(size_t)(pass ? e.a : e.b)]++] = e;
-                v.swap(tmp);
-            }
-        } else
-        std::sort(v.begin(), v.end(), [](const vg_pair_count& x, const vg_pair_count& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
-        v.erase(std::unique(v.begin(), v.end(), [](const vg_pair_count& x, const vg_pair_count& y) { return x.a == y.a && x.b == y.b; }), v.end());
+        order_couples(v, g->n);
     }
-    vg_pair_count* o = (vg_pair_count*)malloc(sizeof(vg_pair_count) * std::max<size_t>(1, v.size()));
-    if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
-    if (!v.empty()) memcpy(o, v.data(), sizeof(vg_pair_count) * v.size());
-    *pairs = o; *n_pairs = (int64_t)v.size();
+    auto o = host_array<vg_pair_count>(v.size());
+    if (!v.empty()) memcpy(o.get(), v.data(), sizeof(vg_pair_count) * v.size());
+    *pairs = o.release(); *n_pairs = (int64_t)v.size();
     VG_API_END
 }
 
@@ -348,9 +417,20 @@ int vg_align_tasks_perm(const vg_genomes* g, const vg_pair_count* pairs, int64_t
     vg_length_order(g);
     vg_host_mark("align_tasks: length order");
     const std::vector<int32_t>& order = g->len_order; const std::vector<int32_t>& rank = g->len_rank;
-    // couples sorted by (lo, hi) of the length ranks: two stable counting passes, on hi and then on lo (LSD order).
-    // One thread: 10^5..10^6 couples are a few milliseconds of cache-resident work, less than starting helpers costs.
+    // couples sorted by (lo, hi) of the length ranks; couple i of the sorted list becomes the task rows 2i and 2i + 1
     struct rp { int32_t lo, hi; uint32_t idx; };
+    auto couple = [&](int64_t i) {
+        if (pairs[i].a >= (uint32_t)g->n || pairs[i].b >= (uint32_t)g->n) throw vg_error(VG_EINVAL, "pair id out of range");
+        const int32_t x = rank[pairs[i].a], y = rank[pairs[i].b];
+        return rp{ std::min(x, y), std::max(x, y), (uint32_t)i };
+    };
+    auto o = host_array<vg_task>(2 * (size_t)n_pairs);
+    vg_task* const row = o.get();
+    auto emit = [&](int64_t i, const rp& c) {
+        row[2 * i] = { (uint32_t)order[(size_t)c.hi], (uint32_t)order[(size_t)c.lo] };        // row (q = b, r = a)
+        row[2 * i + 1] = { (uint32_t)order[(size_t)c.lo], (uint32_t)order[(size_t)c.hi] };    // row (q = a, r = b)
+        if (perm) perm[i] = c.idx;
+    };
     if (n_pairs >= (1 << 21) && vg_host_threads() > 1) {
         // millions of couples (contigs-1M: 3.5 M, 75 ms on one thread): range partition on lo over the threads (counts,
         // offsets, scatter), every range sorted on its own, the task couples written in parallel
@@ -358,59 +438,32 @@ int vg_align_tasks_perm(const vg_genomes* g, const vg_pair_count* pairs, int64_t
         const int64_t ng = std::max<int64_t>(1, g->n);
         std::vector<rp, no_init_alloc<rp>> v, tmp; v.resize((size_t)n_pairs); tmp.resize((size_t)n_pairs);      // (84 MB at 3.5 M couples: not cleared by one thread first)
         std::vector<std::vector<int64_t>> cnt((size_t)T, std::vector<int64_t>((size_t)T + 1, 0));
-        std::atomic<bool> bad(false);
         auto bucket_of = [&](int32_t lo) { return (int)((int64_t)lo * T / ng); };
         vg_parallel_chunks(n_pairs, T, [&](int64_t a, int64_t b, int t) {
-            for (int64_t i = a; i < b; ++i) {
-                if (pairs[i].a >= (uint32_t)g->n || pairs[i].b >= (uint32_t)g->n) { bad = true; return; }
-                const int32_t x = rank[pairs[i].a], y = rank[pairs[i].b];
-                v[(size_t)i] = { std::min(x, y), std::max(x, y), (uint32_t)i };
-                cnt[(size_t)t][(size_t)bucket_of(v[(size_t)i].lo)]++;
-            }
+            for (int64_t i = a; i < b; ++i) { v[(size_t)i] = couple(i); cnt[(size_t)t][(size_t)bucket_of(v[(size_t)i].lo)]++; }
         });
-        if (bad.load()) throw vg_error(VG_EINVAL, "pair id out of range");
         std::vector<int64_t> b_first((size_t)T + 1, 0);
         { int64_t run = 0; for (int bk = 0; bk < T; ++bk) { b_first[(size_t)bk] = run; for (int t = 0; t < T; ++t) { const int64_t c = cnt[(size_t)t][(size_t)bk]; cnt[(size_t)t][(size_t)bk] = run; run += c; } } b_first[(size_t)T] = run; }
         vg_parallel_chunks(n_pairs, T, [&](int64_t a, int64_t b, int t) {
             for (int64_t i = a; i < b; ++i) tmp[(size_t)cnt[(size_t)t][(size_t)bucket_of(v[(size_t)i].lo)]++] = v[(size_t)i];
         });
-        vg_task* o = (vg_task*)malloc(sizeof(vg_task) * std::max<size_t>(1, 2 * tmp.size()));
-        if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
-        auto finish = [&](int64_t a, int64_t b) {
-            for (int64_t bk = a; bk < b; ++bk) {
-                std::sort(tmp.begin() + b_first[(size_t)bk], tmp.begin() + b_first[(size_t)bk + 1], [](const rp& x, const rp& y) { return x.lo != y.lo ? x.lo < y.lo : (x.hi != y.hi ? x.hi < y.hi : x.idx < y.idx); });
-                for (int64_t i = b_first[(size_t)bk]; i < b_first[(size_t)bk + 1]; ++i) {
-                    o[2 * i] = { (uint32_t)order[(size_t)tmp[(size_t)i].hi], (uint32_t)order[(size_t)tmp[(size_t)i].lo] };
-                    o[2 * i + 1] = { (uint32_t)order[(size_t)tmp[(size_t)i].lo], (uint32_t)order[(size_t)tmp[(size_t)i].hi] };
-                    if (perm) perm[i] = tmp[(size_t)i].idx;
-                }
-            }
-        };
-        { std::vector<std::thread> th; for (int t = 1; t < T; ++t) th.emplace_back(finish, (int64_t)t, (int64_t)t + 1); finish(0, 1); for (auto& x : th) x.join(); }
-        vg_host_mark("align_tasks: done");
-        *tasks = o; *n_tasks = (int64_t)(2 * tmp.size());
-        return VG_OK;
-    }
-    std::vector<rp> v((size_t)n_pairs), tmp((size_t)n_pairs);
-    std::vector<int64_t> at_lo((size_t)g->n + 1, 0), at_hi((size_t)g->n + 1, 0);
-    for (int64_t i = 0; i < n_pairs; ++i) {
-        if (pairs[i].a >= (uint32_t)g->n || pairs[i].b >= (uint32_t)g->n) throw vg_error(VG_EINVAL, "pair id out of range");
-        const int32_t x = rank[pairs[i].a], y = rank[pairs[i].b];
-        v[(size_t)i] = { std::min(x, y), std::max(x, y), (uint32_t)i };
-        at_lo[(size_t)v[(size_t)i].lo + 1]++; at_hi[(size_t)v[(size_t)i].hi + 1]++;
-    }
-    for (int key = 0; key < g->n; ++key) { at_lo[(size_t)key + 1] += at_lo[(size_t)key]; at_hi[(size_t)key + 1] += at_hi[(size_t)key]; }
-    for (int64_t i = 0; i < n_pairs; ++i) tmp[(size_t)at_hi[(size_t)v[(size_t)i].hi]++] = v[(size_t)i];
-    for (int64_t i = 0; i < n_pairs; ++i) v[(size_t)at_lo[(size_t)tmp[(size_t)i].lo]++] = tmp[(size_t)i];
-    vg_task* o = (vg_task*)malloc(sizeof(vg_task) * std::max<size_t>(1, 2 * v.size()));
-    if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
-    for (size_t i = 0; i < v.size(); ++i) {
-        o[2 * i] = { (uint32_t)order[(size_t)v[i].hi], (uint32_t)order[(size_t)v[i].lo] };       // row (q = b, r = a)
-        o[2 * i + 1] = { (uint32_t)order[(size_t)v[i].lo], (uint32_t)order[(size_t)v[i].hi] };   // row (q = a, r = b)
-        if (perm) perm[i] = v[i].idx;
+        vg_parallel_for(T, T, [&](int64_t bk) {
+            std::sort(tmp.begin() + b_first[(size_t)bk], tmp.begin() + b_first[(size_t)bk + 1], [](const rp& x, const rp& y) { return x.lo != y.lo ? x.lo < y.lo : (x.hi != y.hi ? x.hi < y.hi : x.idx < y.idx); });
+            for (int64_t i = b_first[(size_t)bk]; i < b_first[(size_t)bk + 1]; ++i) emit(i, tmp[(size_t)i]);
+        });
+    } else {
+        // two stable counting passes, on hi and then on lo (LSD order).  One thread: 10^5..10^6 couples are a few
+        // milliseconds of cache-resident work, less than starting helpers costs.
+        std::vector<rp> v((size_t)n_pairs), tmp((size_t)n_pairs);
+        std::vector<int64_t> at_lo((size_t)g->n + 1, 0), at_hi((size_t)g->n + 1, 0);
+        for (int64_t i = 0; i < n_pairs; ++i) { v[(size_t)i] = couple(i); at_lo[(size_t)v[(size_t)i].lo + 1]++; at_hi[(size_t)v[(size_t)i].hi + 1]++; }
+        for (int key = 0; key < g->n; ++key) { at_lo[(size_t)key + 1] += at_lo[(size_t)key]; at_hi[(size_t)key + 1] += at_hi[(size_t)key]; }
+        for (int64_t i = 0; i < n_pairs; ++i) tmp[(size_t)at_hi[(size_t)v[(size_t)i].hi]++] = v[(size_t)i];
+        for (int64_t i = 0; i < n_pairs; ++i) v[(size_t)at_lo[(size_t)tmp[(size_t)i].lo]++] = tmp[(size_t)i];
+        for (int64_t i = 0; i < n_pairs; ++i) emit(i, v[(size_t)i]);
     }
     vg_host_mark("align_tasks: done");
-    *tasks = o; *n_tasks = (int64_t)(2 * v.size());
+    *tasks = o.release(); *n_tasks = 2 * n_pairs;
     VG_API_END
 }
 
@@ -419,43 +472,40 @@ extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_
                             const vg_region* regions, int64_t n_regions, const char* out_path, const vg_align_params* p) {
     VG_API_BEGIN
     if (!g || (!tasks && n_tasks) || (!stats && n_tasks) || !out_path || !p) throw vg_error(VG_EINVAL, "vg_write_ani: null argument");
+    // the arguments first: an error leaves no file behind
     if (n_tasks & 1) throw vg_error(VG_EINVAL, "vg_write_ani: tasks must come in (q,r),(r,q) couples");
-    std::vector<int32_t> order(g->n), rank(g->n);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return g->len[x] > g->len[y]; });
-    for (int i = 0; i < g->n; ++i) rank[order[i]] = i;
+    enum column { QIDX, RIDX, QUERY, REFERENCE, TANI, GANI, ANI, QCOV, RCOV, NUM_ALNS, LEN_RATIO, QLEN, RLEN, NT_MATCH, NT_MISMATCH };
+    constexpr int N_COLUMNS = NT_MISMATCH + 1;
+    static const char* const known[N_COLUMNS] = { "qidx", "ridx", "query", "reference", "tani", "gani", "ani", "qcov", "rcov", "num_alns",
+                                                  "len_ratio", "qlen", "rlen", "nt_match", "nt_mismatch" };
+    std::vector<column> columns;
+    std::string head;
+    for (int c = 0; c < p->n_out_columns; ++c) {
+        const char* const* kn = std::find_if(known, known + N_COLUMNS, [&](const char* x) { return !strcmp(x, p->out_columns[c]); });
+        if (kn == known + N_COLUMNS) throw vg_error(VG_EINVAL, std::string("unknown output column ") + p->out_columns[c]);
+        columns.push_back((column)(kn - known));
+        if (c) head += '\t';
+        head += *kn;
+    }
+    head += '\n';
+    for (int64_t t = 0; t < n_tasks; ++t)
+        if (tasks[t ^ 1].q != tasks[t].r || tasks[t ^ 1].r != tasks[t].q) throw vg_error(VG_EINVAL, "vg_write_ani: task couple mismatch");
+    vg_length_order(g);
+    const std::vector<int32_t>& order = g->len_order; const std::vector<int32_t>& rank = g->len_rank;
     {
         std::string ids(out_path);
         if (ids.size() > 4 && ids.compare(ids.size() - 4, 4, ".tsv") == 0) ids.resize(ids.size() - 4);
         ids += ".ids.tsv";
-        FILE* f = fopen(ids.c_str(), "w");
-        if (!f) throw vg_error(VG_EIO, "cannot write " + ids);
-        fprintf(f, "id\tseq_len\tno_parts\n");
-        for (int i = 0; i < g->n; ++i) fprintf(f, "%s\t%lld\t%d\n", g->names[order[i]].c_str(), (long long)g->len[order[i]], g->n_parts[order[i]]);
-        if (fclose(f)) throw vg_error(VG_EIO, "write error on " + ids);
+        std::string o = "id\tseq_len\tno_parts\n";
+        for (int32_t i : order) { o += g->names[(size_t)i]; o += '\t'; o += std::to_string(g->len[(size_t)i]); o += '\t'; o += std::to_string(g->n_parts[(size_t)i]); o += '\n'; }
+        vg_write_file(ids.c_str(), { o });
     }
-    FILE* f = fopen(out_path, "w");
-    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + out_path);
-    for (int c = 0; c < p->n_out_columns; ++c) fprintf(f, "%s%s", c ? "\t" : "", p->out_columns[c]);
-    fputc('\n', f);
-    // rows are formatted in parallel into per-chunk buffers and written in order
-    for (int c = 0; c < p->n_out_columns; ++c) {
-        static const char* known[] = { "qidx", "ridx", "query", "reference", "tani", "gani", "ani", "qcov", "rcov", "num_alns",
-                                       "len_ratio", "qlen", "rlen", "nt_match", "nt_mismatch" };
-        bool ok = false; for (const char* kn : known) ok |= !strcmp(kn, p->out_columns[c]);
-        if (!ok) { fclose(f); throw vg_error(VG_EINVAL, std::string("unknown output column ") + p->out_columns[c]); }
-    }
-    for (int64_t t = 0; t < n_tasks; ++t)
-        if (tasks[t ^ 1].q != tasks[t].r || tasks[t ^ 1].r != tasks[t].q) { fclose(f); throw vg_error(VG_EINVAL, "vg_write_ani: task couple mismatch"); }
     const int nthreads = std::max(1, std::min(p->num_threads > 0 ? p->num_threads : 8, 64));
     const int64_t chunk = 1 << 14;
-    const int64_t n_chunks = (n_tasks + chunk - 1) / chunk;
-    std::vector<std::string> out_chunks((size_t)n_chunks);
-    auto format_chunk = [&](int64_t ci) {
-        std::string& o = out_chunks[(size_t)ci];
+    write_rows(out_path, head, n_tasks, chunk, nthreads, [&](int64_t lo, int64_t hi, std::string& o) {
         o.reserve((size_t)chunk * 96);
         char buf[64];
-        for (int64_t t = ci * chunk; t < std::min(n_tasks, (ci + 1) * chunk); ++t) {
+        for (int64_t t = lo; t < hi; ++t) {
             const vg_task& tk = tasks[t]; const vg_pair_stat& x = stats[t]; const vg_pair_stat& rev = stats[t ^ 1];
             int64_t lq = g->len[tk.q], lr = g->len[tk.r];
             double ani = x.aln_len ? (double)x.n_match / (double)x.aln_len : 0.0;
@@ -468,38 +518,30 @@ extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_
             if (p->out_ani > 0 && ani < p->out_ani) continue;
             if (p->out_qcov > 0 && qcov < p->out_qcov) continue;
             if (p->out_rcov > 0 && rcov < p->out_rcov) continue;
-            for (int c = 0; c < p->n_out_columns; ++c) {
-                const char* col = p->out_columns[c];
+            auto num = [&](double v) { o.append(buf, (size_t)vg_fmt_num(v, buf)); };
+            for (size_t c = 0; c < columns.size(); ++c) {
                 if (c) o.push_back('\t');
-                if (!strcmp(col, "qidx")) o += std::to_string(rank[tk.q]);
-                else if (!strcmp(col, "ridx")) o += std::to_string(rank[tk.r]);
-                else if (!strcmp(col, "query")) o += g->names[tk.q];
-                else if (!strcmp(col, "reference")) o += g->names[tk.r];
-                else if (!strcmp(col, "tani")) { vg_fmt_num(tani, buf); o += buf; }
-                else if (!strcmp(col, "gani")) { vg_fmt_num(gani, buf); o += buf; }
-                else if (!strcmp(col, "ani")) { vg_fmt_num(ani, buf); o += buf; }
-                else if (!strcmp(col, "qcov")) { vg_fmt_num(qcov, buf); o += buf; }
-                else if (!strcmp(col, "rcov")) { vg_fmt_num(rcov, buf); o += buf; }
-                else if (!strcmp(col, "num_alns")) o += std::to_string(x.n_regions);
-                else if (!strcmp(col, "len_ratio")) { vg_fmt_len_ratio(lq, lr, buf); o += buf; }
-                else if (!strcmp(col, "qlen")) o += std::to_string(lq);
-                else if (!strcmp(col, "rlen")) o += std::to_string(lr);
-                else if (!strcmp(col, "nt_match")) o += std::to_string(x.n_match);
-                else if (!strcmp(col, "nt_mismatch")) o += std::to_string(x.aln_len - x.n_match);
+                switch (columns[c]) {
+                case QIDX: o += std::to_string(rank[tk.q]); break;
+                case RIDX: o += std::to_string(rank[tk.r]); break;
+                case QUERY: o += g->names[tk.q]; break;
+                case REFERENCE: o += g->names[tk.r]; break;
+                case TANI: num(tani); break;
+                case GANI: num(gani); break;
+                case ANI: num(ani); break;
+                case QCOV: num(qcov); break;
+                case RCOV: num(rcov); break;
+                case NUM_ALNS: o += std::to_string(x.n_regions); break;
+                case LEN_RATIO: o.append(buf, (size_t)vg_fmt_len_ratio(lq, lr, buf)); break;
+                case QLEN: o += std::to_string(lq); break;
+                case RLEN: o += std::to_string(lr); break;
+                case NT_MATCH: o += std::to_string(x.n_match); break;
+                case NT_MISMATCH: o += std::to_string(x.aln_len - x.n_match); break;
+                }
             }
             o.push_back('\n');
         }
-    };
-    {
-        std::atomic<int64_t> next(0);
-        auto work = [&]() { for (;;) { int64_t ci = next.fetch_add(1); if (ci >= n_chunks) break; format_chunk(ci); } };
-        std::vector<std::thread> th;
-        for (int t = 1; t < std::min<int64_t>(nthreads, n_chunks); ++t) th.emplace_back(work);
-        work();
-        for (auto& x : th) x.join();
-    }
-    for (auto& o : out_chunks) if (!o.empty() && fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + out_path); }
-    if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + out_path);
+    });
 
     if (p->out_aln_path && regions) {
         std::vector<vg_region> v(regions, regions + n_regions);
@@ -509,9 +551,7 @@ extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_
             if (lx != ly) return lx > ly;
             return x.qstart < y.qstart;
         });
-        FILE* fa = fopen(p->out_aln_path, "w");
-        if (!fa) throw vg_error(VG_EIO, std::string("cannot write ") + p->out_aln_path);
-        fprintf(fa, "query\treference\tpident\talnlen\tqstart\tqend\trstart\trend\tnt_match\tnt_mismatch\n");
+        std::string o = "query\treference\tpident\talnlen\tqstart\tqend\trstart\trend\tnt_match\tnt_mismatch\n";
         for (auto& r : v) {
             if ((int64_t)r.task >= n_tasks) continue;
             const vg_task& tk = tasks[r.task];
@@ -520,43 +560,19 @@ extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_
             // virtual end and may lie past the end of the strand)
             const bool rev = r.rstart > L;
             auto fwd1 = [&](int64_t rr) { return rev ? L - (rr - (L + 1)) : rr + 1; };
-            int alnlen = r.qend - r.qstart + 1; char buf[64];
+            int alnlen = r.qend - r.qstart + 1; char buf[64], row[160];
             vg_fmt_num(100.0 * r.n_match / alnlen, buf);
-            fprintf(fa, "%s\t%s\t%s\t%d\t%d\t%d\t%lld\t%lld\t%d\t%d\n", g->names[tk.q].c_str(), g->names[tk.r].c_str(), buf, alnlen,
-                    r.qstart + 1, r.qend + 1, (long long)fwd1(r.rstart), (long long)fwd1(r.rend), r.n_match, alnlen - r.n_match);
+            o += g->names[tk.q]; o += '\t'; o += g->names[tk.r];
+            o.append(row, (size_t)snprintf(row, sizeof row, "\t%s\t%d\t%d\t%d\t%lld\t%lld\t%d\t%d\n", buf, alnlen,
+                                           r.qstart + 1, r.qend + 1, (long long)fwd1(r.rstart), (long long)fwd1(r.rend), r.n_match, alnlen - r.n_match));
         }
-        if (fclose(fa)) throw vg_error(VG_EIO, std::string("write error on ") + p->out_aln_path);
+        vg_write_file(p->out_aln_path, { o });
     }
     VG_API_END
 }
 
 // ---------------------------------------------------------------- cluster stage: ids file, ani.tsv rows, clusters.tsv
 namespace {
-struct mapped_text {            // a whole text file, read-only mapped (empty file: n == 0)
-    const char* p = nullptr; size_t n = 0; void* m = MAP_FAILED;
-    explicit mapped_text(const char* path) {
-        const int fd = open(path, O_RDONLY);
-        if (fd < 0) throw vg_error(VG_EIO, std::string("cannot open ") + path);
-        struct stat sb;
-        if (fstat(fd, &sb) != 0) { close(fd); throw vg_error(VG_EIO, std::string("cannot stat ") + path); }
-        n = (size_t)sb.st_size;
-        if (n) {
-            m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { close(fd); throw vg_error(VG_EIO, std::string("cannot map ") + path); }
-            (void)madvise(m, n, MADV_WILLNEED);
-            p = (const char*)m;
-        }
-        close(fd);
-    }
-    ~mapped_text() { if (m != MAP_FAILED) munmap(m, n); }
-    mapped_text(const mapped_text&) = delete; mapped_text& operator=(const mapped_text&) = delete;
-    const char* line_end(const char* a) const { const char* e = (const char*)memchr(a, '\n', (size_t)(p + n - a)); return e ? e : p + n; }
-    int64_t line_of(const char* at) const {          // 1-based line number of a position (errors only)
-        int64_t l = 1;
-        for (const char* x = p; (x = (const char*)memchr(x, '\n', (size_t)(at - x))) != nullptr; ++x) ++l;
-        return l;
-    }
-};
 [[noreturn]] void row_error(const char* path, int64_t line, const std::string& what) {
     throw vg_error(VG_EINVAL, std::string(path) + ":" + std::to_string(line) + ": " + what);
 }
@@ -567,35 +583,22 @@ bool parse_double(const char* a, const char* b, double& v) {
 }  // namespace
 
 void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids) {
-    mapped_text f(path);
+    const text_file f(path);
     ids.clear();
-    const char* end = f.p + f.n;
-    const char* a = f.n ? f.line_end(f.p) : end;         // (the header line)
-    while (a < end) {
-        ++a;
-        if (a >= end) break;
-        const char* e = f.line_end(a);
-        if (e > a) {
-            const char* t = (const char*)memchr(a, '\t', (size_t)(e - a));
-            ids.emplace_back(a, t ? t : e);
-        }
-        a = e;
-    }
+    for_each_line(f, [&](int64_t line, std::string_view text) {
+        if (line > 1 && !text.empty()) ids.emplace_back(text.substr(0, text.find('\t')));       // (line 1: the header)
+    });
 }
 
 void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
                           std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w) {
-    mapped_text f(path);
+    const text_file f(path);
     if (!f.n) row_error(path, 1, "empty file (no header)");
-    const char* end = f.p + f.n;
+    const char* end = f.end();
     const char* hdr_end = f.line_end(f.p);
-    std::vector<std::string> names;
-    for (const char* a = f.p; a <= hdr_end;) {
-        const char* t = (const char*)memchr(a, '\t', (size_t)(hdr_end - a));
-        const char* e = t ? t : hdr_end;
-        names.emplace_back(a, e);
-        a = e + 1;
-    }
+    std::vector<std::string_view> fields;
+    split_fields(std::string_view(f.p, (size_t)(hdr_end - f.p)), '\t', fields);
+    const std::vector<std::string> names(fields.begin(), fields.end());
     auto col_of = [&](const char* name) {
         for (size_t c = 0; c < names.size(); ++c) if (names[c] == name) return (int)c;
         row_error(path, 1, std::string("missing column ") + name);
@@ -623,7 +626,7 @@ void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_
     }
     struct part { std::vector<uint32_t> q, r; std::vector<double> w; const char* err_at = nullptr; std::string err; };
     std::vector<part> parts((size_t)nthr);
-    auto work = [&](int t) {
+    vg_parallel_for(nthr, nthr, [&](int64_t t) {
         part& pt = parts[(size_t)t];
         std::vector<const char*> fb((size_t)max_col + 1), fe((size_t)max_col + 1);
         std::vector<double> v(cols.size());
@@ -657,13 +660,7 @@ void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_
             if (pass) { pt.q.push_back((uint32_t)idx[0]); pt.r.push_back((uint32_t)idx[1]); pt.w.push_back(v[2]); }
             a = e + 1;
         }
-    };
-    {
-        std::vector<std::thread> th;
-        for (int t = 1; t < nthr; ++t) th.emplace_back(work, t);
-        work(0);
-        for (auto& x : th) x.join();
-    }
+    });
     size_t total = 0;
     for (auto& pt : parts) {
         if (pt.err_at) row_error(path, f.line_of(pt.err_at), pt.err);
@@ -676,130 +673,108 @@ void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_
     }
 }
 
-void vg_cluster_read_prior(const char* path, const std::vector<std::string>& ids, bool is_repr, std::vector<int32_t>& prior_rep) {
-    mapped_text f(path);
+namespace {
+// an "object, then label column(s)" file against the ids: line 1 is the header, every other line that is not empty names an
+// object of the ids file once and carries one value per label column.  The views point into the file.
+struct label_file {
+    std::unordered_map<std::string_view, int32_t> index;       // id -> object
+    std::vector<std::string_view> names;                        // the header behind "object"
+    std::vector<int32_t> listed;                                // the objects in the order of their lines
+    std::vector<int64_t> line_of;                               // per object: its line (0: it has none)
+    std::vector<std::string_view> value;                        // value[i * n_cols + c]
+    size_t n_cols = 0;
+    int64_t n_lines = 0;
+};
+// prior: the header is exactly object<TAB>cluster (and the texts of the two "malformed" errors are those of the prior file)
+void read_label_file(const text_file& f, const char* path, const std::vector<std::string>& ids, bool prior, label_file& lf) {
     if (!f.n) row_error(path, 1, "empty file (no header)");
-    const char* end = f.p + f.n;
-    std::unordered_map<std::string_view, int32_t> index;
-    index.reserve(ids.size() * 2);
-    for (size_t i = 0; i < ids.size(); ++i) index.emplace(ids[i], (int32_t)i);
+    lf.index.reserve(ids.size() * 2);
+    for (size_t i = 0; i < ids.size(); ++i) lf.index.emplace(ids[i], (int32_t)i);
+    lf.line_of.assign(ids.size(), 0);
+    std::vector<std::string_view> fields;
+    for_each_line(f, [&](int64_t line, std::string_view text) {
+        lf.n_lines = line;
+        if (line > 1 && text.empty()) return;
+        split_fields(text, '\t', fields);
+        bool ok = line == 1 ? fields.size() >= 2 && fields[0] == "object" : fields.size() == lf.n_cols + 1;
+        for (const std::string_view& x : fields) ok = ok && !x.empty();
+        if (line == 1) {
+            if (prior ? text != "object\tcluster" : !ok)
+                row_error(path, 1, prior ? "malformed header (expected object<TAB>cluster)" : "malformed header (expected object<TAB>cluster, then further label columns)");
+            lf.names.assign(fields.begin() + 1, fields.end());
+            lf.n_cols = lf.names.size();
+            lf.value.assign(ids.size() * lf.n_cols, std::string_view());
+            return;
+        }
+        if (!ok) row_error(path, line, prior ? "malformed line (expected <object><TAB><cluster>)" : "malformed line (expected " + std::to_string(lf.n_cols + 1) + " fields)");
+        const auto it = lf.index.find(fields[0]);
+        if (it == lf.index.end()) row_error(path, line, "object '" + std::string(fields[0]) + "' is not in the ids file");
+        const size_t i = (size_t)it->second;
+        if (lf.line_of[i]) row_error(path, line, "object '" + std::string(fields[0]) + "' is listed twice");
+        lf.line_of[i] = line;
+        lf.listed.push_back(it->second);
+        std::copy(fields.begin() + 1, fields.end(), lf.value.begin() + (std::ptrdiff_t)(i * lf.n_cols));
+    });
+}
+// a cluster number up to `max`; the whole value must be one
+uint64_t cluster_number(const char* path, int64_t line, std::string_view v, uint64_t max) {
+    uint64_t number = 0;
+    const auto rr = std::from_chars(v.data(), v.data() + v.size(), number);
+    if (rr.ec != std::errc() || rr.ptr != v.data() + v.size() || number > max) row_error(path, line, "malformed cluster number '" + std::string(v) + "'");
+    return number;
+}
+}  // namespace
+
+void vg_cluster_read_prior(const char* path, const std::vector<std::string>& ids, bool is_repr, std::vector<int32_t>& prior_rep) {
+    const text_file f(path);
+    label_file lf;
+    read_label_file(f, path, ids, true, lf);
     prior_rep.assign(ids.size(), -1);
-    // pass 1: every line names an object of the ids file once; its value is kept as (object, line, value text)
-    struct entry { int32_t obj; int64_t line; std::string_view value; uint64_t number; };
-    std::vector<entry> entries;
-    int64_t line = 0;
-    for (const char* a = f.p; a < end;) {
-        const char* e = f.line_end(a);
-        ++line;
-        const char* le = e > a && e[-1] == '\r' ? e - 1 : e;
-        const std::string_view text(a, (size_t)(le - a));
-        a = e + 1;
-        if (line == 1) { if (text != "object\tcluster") row_error(path, 1, "malformed header (expected object<TAB>cluster)"); continue; }
-        if (text.empty()) continue;
-        const size_t tab = text.find('\t');
-        if (tab == std::string_view::npos || tab == 0 || tab + 1 == text.size() || text.find('\t', tab + 1) != std::string_view::npos)
-            row_error(path, line, "malformed line (expected <object><TAB><cluster>)");
-        const std::string_view name = text.substr(0, tab);
-        const auto it = index.find(name);
-        if (it == index.end()) row_error(path, line, "object '" + std::string(name) + "' is not in the ids file");
-        if (prior_rep[(size_t)it->second] != -1) row_error(path, line, "object '" + std::string(name) + "' is listed twice");
-        prior_rep[(size_t)it->second] = -2;                      // (seen; the representative follows)
-        entries.push_back({ it->second, line, text.substr(tab + 1), 0 });
-    }
     if (is_repr) {
-        // pass 2: the value names a prior object; pass 3: that object names itself
-        for (const entry& en : entries) {
-            const auto it = index.find(en.value);
-            if (it == index.end() || prior_rep[(size_t)it->second] == -1)
-                row_error(path, en.line, "representative '" + std::string(en.value) + "' is not an object of this file");
-            prior_rep[(size_t)en.obj] = it->second;
+        // the value names an object of this file; then: that object names itself
+        for (const int32_t obj : lf.listed) {
+            const auto it = lf.index.find(lf.value[(size_t)obj]);
+            if (it == lf.index.end() || !lf.line_of[(size_t)it->second])
+                row_error(path, lf.line_of[(size_t)obj], "representative '" + std::string(lf.value[(size_t)obj]) + "' is not an object of this file");
+            prior_rep[(size_t)obj] = it->second;
         }
-        for (const entry& en : entries) {
-            const int32_t rep = prior_rep[(size_t)en.obj];
-            if (prior_rep[(size_t)rep] != rep) row_error(path, en.line, "representative '" + std::string(en.value) + "' is not its own representative");
-        }
+        for (const int32_t obj : lf.listed)
+            if (prior_rep[(size_t)prior_rep[(size_t)obj]] != prior_rep[(size_t)obj])
+                row_error(path, lf.line_of[(size_t)obj], "representative '" + std::string(lf.value[(size_t)obj]) + "' is not its own representative");
         return;
     }
-    // cluster numbers: the representative is the earliest member in the ids file
+    // cluster numbers (any 64-bit one): the representative is the earliest member in the ids file
     std::unordered_map<uint64_t, int32_t> first;
-    for (entry& en : entries) {
-        const char* vb = en.value.data(); const char* ve = vb + en.value.size();
-        const auto rr = std::from_chars(vb, ve, en.number);
-        if (rr.ec != std::errc() || rr.ptr != ve) row_error(path, en.line, "malformed cluster number '" + std::string(en.value) + "'");
-        const auto ins = first.emplace(en.number, en.obj);
-        if (!ins.second && en.obj < ins.first->second) ins.first->second = en.obj;
+    std::vector<uint64_t> number(ids.size());
+    for (const int32_t obj : lf.listed) {
+        number[(size_t)obj] = cluster_number(path, lf.line_of[(size_t)obj], lf.value[(size_t)obj], UINT64_MAX);
+        const auto ins = first.emplace(number[(size_t)obj], obj);
+        if (!ins.second && obj < ins.first->second) ins.first->second = obj;
     }
-    for (const entry& en : entries) prior_rep[(size_t)en.obj] = first[en.number];
+    for (const int32_t obj : lf.listed) prior_rep[(size_t)obj] = first[number[(size_t)obj]];
 }
 
 void vg_cluster_read_columns(const char* path, const std::vector<std::string>& ids, bool is_repr, vg_label_columns& out) {
-    mapped_text f(path);
-    if (!f.n) row_error(path, 1, "empty file (no header)");
-    const char* end = f.p + f.n;
-    std::unordered_map<std::string_view, int32_t> index;
-    index.reserve(ids.size() * 2);
-    for (size_t i = 0; i < ids.size(); ++i) index.emplace(ids[i], (int32_t)i);
-    auto split = [](std::string_view text, std::vector<std::string_view>& fields) {
-        fields.clear();
-        for (size_t a = 0;;) {
-            const size_t t = text.find('\t', a);
-            fields.push_back(text.substr(a, t == std::string_view::npos ? t : t - a));
-            if (t == std::string_view::npos) break;
-            a = t + 1;
-        }
-    };
-    // pass 1: the header, then every line names an object of the ids file once and carries one value per label column
-    std::vector<int64_t> line_of(ids.size(), 0);                // (0: not seen)
-    std::vector<std::string_view> value, fields;                // value[i * n_cols + c]
-    size_t n_cols = 0;
-    int64_t line = 0;
-    for (const char* a = f.p; a < end;) {
-        const char* e = f.line_end(a);
-        ++line;
-        const char* le = e > a && e[-1] == '\r' ? e - 1 : e;
-        const std::string_view text(a, (size_t)(le - a));
-        a = e + 1;
-        if (line == 1) {
-            split(text, fields);
-            bool ok = fields.size() >= 2 && fields[0] == "object";
-            for (const std::string_view& x : fields) ok = ok && !x.empty();
-            if (!ok) row_error(path, 1, "malformed header (expected object<TAB>cluster, then further label columns)");
-            n_cols = fields.size() - 1;
-            out.names.assign(fields.begin() + 1, fields.end());
-            value.assign(ids.size() * n_cols, std::string_view());
-            continue;
-        }
-        if (text.empty()) continue;
-        split(text, fields);
-        bool ok = fields.size() == n_cols + 1;
-        for (const std::string_view& x : fields) ok = ok && !x.empty();
-        if (!ok) row_error(path, line, "malformed line (expected " + std::to_string(n_cols + 1) + " fields)");
-        const auto it = index.find(fields[0]);
-        if (it == index.end()) row_error(path, line, "object '" + std::string(fields[0]) + "' is not in the ids file");
-        const size_t i = (size_t)it->second;
-        if (line_of[i]) row_error(path, line, "object '" + std::string(fields[0]) + "' is listed twice");
-        line_of[i] = line;
-        for (size_t c = 0; c < n_cols; ++c) {
-            const std::string_view v = fields[c + 1];
-            value[i * n_cols + c] = v;
-            if (is_repr) continue;
-            uint64_t number = 0;
-            const auto rr = std::from_chars(v.data(), v.data() + v.size(), number);
-            if (rr.ec != std::errc() || rr.ptr != v.data() + v.size() || number >= (1ull << 31))
-                row_error(path, line, "malformed cluster number '" + std::string(v) + "'");
-        }
-    }
+    const text_file f(path);
+    label_file lf;
+    read_label_file(f, path, ids, false, lf);
+    const size_t n_cols = lf.n_cols;
+    const std::vector<std::string_view>& value = lf.value;
+    out.names.assign(lf.names.begin(), lf.names.end());
+    if (!is_repr)
+        for (const int32_t obj : lf.listed)
+            for (size_t c = 0; c < n_cols; ++c) cluster_number(path, lf.line_of[(size_t)obj], value[(size_t)obj * n_cols + c], (1ull << 31) - 1);
     for (size_t i = 0; i < ids.size(); ++i)
-        if (!line_of[i]) row_error(path, line, "object '" + ids[i] + "' of the ids file is missing");
-    // pass 2 (representative ids): the value names an object, and that object names itself in the same column
+        if (!lf.line_of[i]) row_error(path, lf.n_lines, "object '" + ids[i] + "' of the ids file is missing");
+    // representative ids: the value names an object, and that object names itself in the same column
     if (is_repr)
         for (size_t i = 0; i < ids.size(); ++i)
             for (size_t c = 0; c < n_cols; ++c) {
                 const std::string_view v = value[i * n_cols + c];
-                const auto it = index.find(v);
-                if (it == index.end()) row_error(path, line_of[i], "representative '" + std::string(v) + "' is not in the ids file");
+                const auto it = lf.index.find(v);
+                if (it == lf.index.end()) row_error(path, lf.line_of[i], "representative '" + std::string(v) + "' is not in the ids file");
                 if (value[(size_t)it->second * n_cols + c] != v)
-                    row_error(path, line_of[i], "representative '" + std::string(v) + "' is not a member of its cluster");
+                    row_error(path, lf.line_of[i], "representative '" + std::string(v) + "' is not a member of its cluster");
             }
     // the clusters of a column, numbered by their earliest member
     out.label.assign(n_cols, std::vector<int32_t>(ids.size()));
@@ -848,10 +823,7 @@ void vg_cluster_stats_write(const char* path, const char* metric, const std::vec
             num((uint64_t)s.misfits);
             o.push_back('\n');
         }
-    FILE* fo = fopen(path, "w");
-    if (!fo) throw vg_error(VG_EIO, std::string("cannot write ") + path);
-    if (fwrite(o.data(), 1, o.size(), fo) != o.size()) { fclose(fo); throw vg_error(VG_EIO, std::string("write error on ") + path); }
-    if (fclose(fo)) throw vg_error(VG_EIO, std::string("write error on ") + path);
+    vg_write_file(path, { o });
 }
 
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives) {
@@ -862,20 +834,8 @@ void vg_cluster_write(const char* path, const std::vector<std::string>& ids, con
         if (representatives) o += ids[(size_t)rep[i]]; else o += std::to_string(label[i]);
         o.push_back('\n');
     }
-    FILE* f = fopen(path, "w");
-    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + path);
-    if (fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
-    if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + path);
+    vg_write_file(path, { o });
 }
-
-namespace {
-void write_text(const char* path, const std::string& o) {
-    FILE* f = fopen(path, "w");
-    if (!f) throw vg_error(VG_EIO, std::string("cannot write ") + path);
-    if (fwrite(o.data(), 1, o.size(), f) != o.size()) { fclose(f); throw vg_error(VG_EIO, std::string("write error on ") + path); }
-    if (fclose(f)) throw vg_error(VG_EIO, std::string("write error on ") + path);
-}
-}  // namespace
 
 void vg_cluster_write_columns(const char* path, const std::vector<std::string>& ids, const std::vector<std::string>& names,
                               const std::vector<const int32_t*>& label, const std::vector<const int32_t*>& rep, bool representatives) {
@@ -891,7 +851,7 @@ void vg_cluster_write_columns(const char* path, const std::vector<std::string>& 
         }
         o.push_back('\n');
     }
-    write_text(path, o);
+    vg_write_file(path, { o });
 }
 
 void vg_linkage_write(const char* path, const vg_forest& f, const int64_t* node_a, const int64_t* node_b, const int64_t* size) {
@@ -903,5 +863,5 @@ void vg_linkage_write(const char* path, const vg_forest& f, const int64_t* node_
                  (int)f.a[k], (int)f.b[k]);
         o += buf;
     }
-    write_text(path, o);
+    vg_write_file(path, { o });
 }

@@ -77,41 +77,24 @@ extern "C" int vg_synth_plan(const int64_t* fam_idx, const int32_t* members, con
     for (int64_t f = 0; f < n_fam; ++f) first[(size_t)f + 1] = first[(size_t)f] + members[f];
     const int64_t ng = first[(size_t)n_fam];
     std::vector<std::vector<uint8_t>> seqs((size_t)ng);
-    std::atomic<int64_t> next{0};
     const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(), 256));
-    auto work = [&]() {
-        std::vector<uint8_t> anc;
-        for (;;) {
-            const int64_t f = next.fetch_add(1);
-            if (f >= n_fam) break;
-            anc.resize((size_t)lengths[f]);
-            const uint64_t sa = stream_id(seed, (uint64_t)fam_idx[f], 0, 0);
-            for (size_t i = 0; i < anc.size(); ++i) anc[i] = (uint8_t)(draw(sa, i) >> 62);
-            for (int m = 0; m < members[f]; ++m)
-                mutate(seed, (uint64_t)fam_idx[f], (uint64_t)m + 1, anc, p_lo, p_hi, n_indels, seqs[(size_t)(first[(size_t)f] + m)]);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < nt; ++t) th.emplace_back(work);
-    for (auto& x : th) x.join();
+    vg_parallel_for(n_fam, nt, [&](int64_t f) {
+        std::vector<uint8_t> anc((size_t)lengths[f]);
+        const uint64_t sa = stream_id(seed, (uint64_t)fam_idx[f], 0, 0);
+        for (size_t i = 0; i < anc.size(); ++i) anc[i] = (uint8_t)(draw(sa, i) >> 62);
+        for (int m = 0; m < members[f]; ++m)
+            mutate(seed, (uint64_t)fam_idx[f], (uint64_t)m + 1, anc, p_lo, p_hi, n_indels, seqs[(size_t)(first[(size_t)f] + m)]);
+    });
     int64_t* off = (int64_t*)malloc(sizeof(int64_t) * ((size_t)ng + 1));
     if (!off) throw vg_error(VG_ENOMEM, "out of host memory");
     off[0] = 0;
     for (int64_t i = 0; i < ng; ++i) off[i + 1] = off[i] + (int64_t)seqs[(size_t)i].size();
     uint8_t* codes = (uint8_t*)malloc((size_t)std::max<int64_t>(off[ng], 1));
     if (!codes) { free(off); throw vg_error(VG_ENOMEM, "out of host memory"); }
-    std::atomic<int64_t> nx2{0};
-    auto copy = [&]() {
-        for (;;) {
-            const int64_t i = nx2.fetch_add(64);
-            if (i >= ng) break;
-            for (int64_t j = i; j < std::min(ng, i + 64); ++j)
-                if (!seqs[(size_t)j].empty()) memcpy(codes + off[j], seqs[(size_t)j].data(), seqs[(size_t)j].size());
-        }
-    };
-    th.clear();
-    for (int t = 0; t < nt; ++t) th.emplace_back(copy);
-    for (auto& x : th) x.join();
+    vg_parallel_for((ng + 63) / 64, nt, [&](int64_t c) {
+        for (int64_t j = 64 * c; j < std::min(ng, 64 * c + 64); ++j)
+            if (!seqs[(size_t)j].empty()) memcpy(codes + off[j], seqs[(size_t)j].data(), seqs[(size_t)j].size());
+    });
     *codes_out = codes; *offsets_out = off; *n_genomes = ng;
     VG_API_END
 }
