@@ -92,6 +92,15 @@ int         vg_genomes_codes(const vg_genomes* g, int idx, uint8_t* out);
 /* 2-bit packed bases + N mask -> HBM of the current device (idempotent); the kernels' own copy of the bases -- bit planes,
  * DESIGN.md section 3 -- is made from them on the device at the first prefilter / align call */
 int vg_genomes_to_device(vg_genomes* g);
+/* A subset of a resident set (this repository's call; no reference call site): *out is a new set holding the genomes ids[0 .. n_ids)
+ * of g, in that order, with their names, lengths and part counts.  It is built on the device from g's resident 2-bit codes and N mask
+ * by one gather kernel (profile scope `derep_subset`); no base travels from the host.  The subset keeps g's block size, lays its
+ * genomes out by the loader's padding rule (at least one masked padding base behind every genome) and is resident on g's device; g is
+ * not changed and need not outlive it.  Its host copy of the bases stays empty: vg_genomes_codes downloads the genome it is asked
+ * for, and the sharded entry points (vg_kmer_shared_sharded, vg_lz_align_sharded, vg_lz_align_pairs_sharded) refuse such a set with
+ * VG_EINVAL.  An id outside [0, n) or listed twice is VG_EINVAL naming it, and so is a set that is not resident
+ * (vg_genomes_to_device); all three are raised before any device use.  n_ids = 0 gives a valid empty set. */
+int vg_genomes_subset(const vg_genomes* g, const int32_t* ids, int n_ids, vg_genomes** out);
 
 /* ------------------------------------------------------------------ prefilter --------- */
 typedef struct { uint32_t a, b, shared; } vg_pair_count;   /* a > b (input order ids) */
@@ -563,6 +572,55 @@ int vg_cluster_mcl(const char* ani_path, const char* ids_path, const char* out_p
  * candidate bound exceeds it and whose distinct columns fill more than 3/4 of it takes the spill path, so a small value sends
  * tiny graphs there. */
 void vg_cluster_mcl_set_table_slots(int slots);
+
+/* ------------------------------------------------------------------ dereplicate ------- */
+/* Greedy incremental clustering against representatives only (this repository's command; no reference call site; DESIGN.md
+ * section 13 is the contract).  Objects are the genomes in align order (vg_align_order; rank = object index, as in ani.ids.tsv).
+ * The result is the one of vg_kmer_shared + vg_filter_pairs -> vg_lz_align of every kept pair -> vg_cluster_graph(VG_CLUSTER_CDHIT) on
+ * the rows that pass the cluster filters AS ani.tsv PRINTS THEM, but a genome is only ever compared with the representatives found
+ * so far and with the batch-mates that joined none of them: per batch of `batch_genomes` consecutive ranks, a subset
+ * [representatives | batch] (vg_genomes_subset), vg_kmer_shared_new with the representatives as the database, the pairs (batch
+ * genome, representative) aligned first, then the pairs among the batch genomes still without a representative, and
+ * vg_cluster_update_graph(VG_CLUSTER_CDHIT) with the representatives as the prior clustering.  The representatives stay in HBM. */
+typedef struct {
+    int    k;                   /* -k, 15..30 */
+    double kmers_fraction;      /* --kmers-fraction, (0, 1] */
+    int    min_kmers;           /* --min-kmers */
+    double min_ident;           /* --min-ident */
+    vg_lz_params lz;
+    vg_cluster_params cluster;  /* metric and filters as for vg_cluster; algorithm must be VG_CLUSTER_CDHIT and the metric's minimum > 0 */
+    int    batch_genomes;       /* genomes per batch, >= 1; results never depend on it */
+} vg_derep_params;
+typedef struct {                /* pair counts are unordered pairs */
+    int64_t batches;
+    int64_t representatives;
+    int64_t pairs_candidate;    /* pairs kept by the prefilter, over all batches */
+    int64_t pairs_aligned;      /* of those, aligned (both directions) */
+    int64_t pairs_skipped;      /* of those, never aligned: a batch genome that joined an earlier representative against its batch-mates */
+    int64_t joined_prior;       /* genomes that joined a representative of an earlier batch */
+    int64_t joined_new;         /* genomes that joined a representative of their own batch */
+    int64_t founded;            /* = representatives */
+} vg_derep_stats;
+/* The array-level call.  label[n], representative[n]: indexed by object (rank), exactly what vg_cluster_graph(VG_CLUSTER_CDHIT) returns
+ * for the passing rows of the whole pair list.  tasks / stats_rows / n_tasks (all three or none; vg_free): every aligned ordered pair
+ * in input-order ids with its integers, couples in the order of vg_align_tasks, ready for vg_write_ani.  st may be NULL.  Refused with
+ * VG_EINVAL before any device use: batch_genomes < 1, an algorithm other than VG_CLUSTER_CDHIT, an unknown metric, a metric minimum
+ * of 0, k outside 15..30, kmers_fraction outside (0, 1].  The representatives the batches found are compared with those of the final
+ * vg_cluster_graph over all rows; a difference is an internal error (VG_EHIP) naming the object. */
+int vg_dereplicate_set(vg_genomes* g, const vg_derep_params* p, int32_t* label, int32_t* representative, vg_task** tasks,
+                       vg_pair_stat** stats_rows, int64_t* n_tasks, vg_derep_stats* st);
+typedef struct {
+    vg_derep_params derep;
+    int representatives;                                      /* clusters.tsv: second column = the representative's id */
+    const char* out_table_path;                               /* NULL = none; else ani.tsv of the computed rows + its .ids.tsv (all n genomes) */
+    const char* const* out_columns; int n_out_columns;        /* columns of that table (ALIGN_OUTFMT[fmt]) */
+    const char* out_repr_fasta_path;                          /* NULL = none; one multi-FASTA input only: the representatives' records, verbatim, input order */
+    int num_threads; int verbosity; int is_multifasta;
+    vg_derep_stats* stats;                                    /* NULL, or where the counts go */
+} vg_derep_file_params;
+/* File to file: FASTA in, clusters.tsv (the file vg_cluster writes) out.  verbosity >= 1: one summary line on stderr,
+ * `Dereplicate: <n> genomes, <r> representatives, <b> batches, <p> pairs aligned (<c> candidates skipped)`. */
+int vg_dereplicate(const char* const* fasta_paths, int n_paths, const char* out_path, const vg_derep_file_params* p);
 
 /* ------------------------------------------------------------------ deduplicate ------- */
 /* The first stage: FASTA files -> one FASTA of the distinct sequences + a duplicates list, in place of mfasta-tool

@@ -64,6 +64,23 @@ class ClusterParams(C.Structure):
                 ('max_num_alns', C.c_int), ('representatives', C.c_int), ('num_threads', C.c_int), ('verbosity', C.c_int)]
 
 
+class DerepParams(C.Structure):
+    """vg_derep_params: prefilter, align and cluster options of dereplicate, and its batch size"""
+    _fields_ = [('k', C.c_int), ('kmers_fraction', C.c_double), ('min_kmers', C.c_int), ('min_ident', C.c_double), ('lz', LzParams),
+                ('cluster', ClusterParams), ('batch_genomes', C.c_int)]
+
+
+class DerepStats(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ('batches', 'representatives', 'pairs_candidate', 'pairs_aligned', 'pairs_skipped',
+                                                'joined_prior', 'joined_new', 'founded')]
+
+
+class DerepFileParams(C.Structure):
+    _fields_ = [('derep', DerepParams), ('representatives', C.c_int), ('out_table_path', C.c_char_p),
+                ('out_columns', C.POINTER(C.c_char_p)), ('n_out_columns', C.c_int), ('out_repr_fasta_path', C.c_char_p),
+                ('num_threads', C.c_int), ('verbosity', C.c_int), ('is_multifasta', C.c_int), ('stats', C.POINTER(DerepStats))]
+
+
 class ClusterStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('sweep_objects', C.c_int64), ('n_edges', C.c_int64)]
 
@@ -95,6 +112,10 @@ HIERARCHY_ALGORITHMS = {**LINKAGE_ALGORITHMS, 'average': 5}
 UPDATE_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2}
 # the flow algorithms: Markov clustering, with calls of its own (vg_cluster_mcl / vg_cluster_mcl_graph); always in the library
 FLOW_ALGORITHMS = {'mcl': 6}
+# the algorithm of dereplicate (vg_dereplicate / vg_dereplicate_set): a genome is compared with representatives only, which is cd-hit
+DEREP_ALGORITHMS = {'cd-hit': 1}
+# genomes per batch of dereplicate ("Batch size")
+DEREP_BATCH_GENOMES = 4096
 
 
 class MclParams(C.Structure):
@@ -163,6 +184,7 @@ SYMBOLS = {
     'vg_genomes_name': (C.c_char_p, [C.c_void_p, C.c_int]),
     'vg_genomes_codes': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'vg_genomes_to_device': (C.c_int, [C.c_void_p]),
+    'vg_genomes_subset': (C.c_int, [C.c_void_p, P(C.c_int32), C.c_int, P(C.c_void_p)]),
     'vg_kmer_shared': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint32,
                                  P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
     'vg_kmer_shared_new': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
@@ -241,6 +263,9 @@ SYMBOLS = {
                                        P(P(C.c_int64)), P(P(C.c_int32)), P(P(C.c_uint32)), P(MclStats)]),
     'vg_cluster_mcl': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams), P(MclParams), P(MclStats)]),
     'vg_cluster_mcl_set_table_slots': (None, [C.c_int]),
+    'vg_dereplicate_set': (C.c_int, [C.c_void_p, P(DerepParams), P(C.c_int32), P(C.c_int32), P(P(Task)), P(P(PairStat)), P(C.c_int64),
+                                     P(DerepStats)]),
+    'vg_dereplicate': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(DerepFileParams)]),
     'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),
     'vg_deduplicate_ex': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams), P(DedupOptions)]),

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, KernelTime, LinkageStats, LzParams, MclParams, MclStats, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, DerepStats, KernelTime, LinkageStats, LzParams, MclParams, MclStats, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -146,6 +146,36 @@ class GenomeSet:
     def to_device(self):
         check(self._lib.vg_genomes_to_device(self._h))
 
+    def subset(self, ids):
+        """The genomes `ids` of this resident set, in that order, as a new set gathered on the device (vg_genomes_subset): no base
+        travels from the host.  An id outside the set or listed twice, and a set that is not resident, are errors."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        h = C.c_void_p()
+        check(self._lib.vg_genomes_subset(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(h)))
+        return GenomeSet(h)
+
+    def dereplicate_set(self, batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min_ident=0.7, lz=None, algorithm='cd-hit',
+                        metric='tani', num_alns=0, want_rows=False, **mins):
+        """Greedy clustering against representatives only (vg_dereplicate_set): the result of kmer_shared ->
+        filter_pairs -> lz_align -> cluster_graph('cd-hit') on the rows that pass the filters as ani.tsv prints them, computed batch
+        by batch against the representatives found so far.  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio=; the metric's must be
+        above 0.  -> (label int32[n], representative int32[n], stats dict), indexed by rank (align_order); with want_rows=True also
+        (tasks, stats rows) of every aligned ordered pair, in input-order ids, as write_ani takes them."""
+        from .stages import derep_params
+        prm = derep_params(batch_genomes, k, kmers_fraction, min_kmers, min_ident, lz, algorithm, metric, num_alns, mins)
+        n = len(self)
+        label, rep = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        st = DerepStats()
+        P = C.POINTER
+        tp, sp, nt = P(Task)(), P(PairStat)(), C.c_int64()
+        check(self._lib.vg_dereplicate_set(self._h, C.byref(prm), label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
+                                           C.byref(tp) if want_rows else None, C.byref(sp) if want_rows else None,
+                                           C.byref(nt) if want_rows else None, C.byref(st)))
+        stats = {name: getattr(st, name) for name, _ in DerepStats._fields_}
+        if not want_rows:
+            return label[:n], rep[:n], stats
+        return label[:n], rep[:n], stats, (_take(tp, nt.value, TASK_DTYPE), _take(sp, nt.value, STAT_DTYPE))
+
     # ---------------------------------------------------------------- prefilter
     def kmer_shared(self, k=25, fraction=1.0, shard=0, n_shards=1, min_shared=1):
         """-> (set_sizes int64[n], pairs structured array a>b with shared counts)."""
@@ -277,7 +307,7 @@ class GenomeSet:
 
 
 # ---------------------------------------------------------------- whole-stage calls (vclust_amd/stages.py: no numpy)
-from .stages import align, align_params, cluster, cluster_stats, deduplicate as deduplicate_files, prefilter  # noqa: E402,F401
+from .stages import align, align_params, cluster, cluster_stats, deduplicate as deduplicate_files, dereplicate, prefilter  # noqa: E402,F401
 
 
 def cluster_graph(n_objects, q, r, w, algorithm='single'):

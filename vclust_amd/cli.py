@@ -11,7 +11,8 @@ and `--prior` (new genomes added to the clusters of an earlier clusters.tsv: vg_
 after clusters.tsv is written, whoever wrote it (the per-cluster report: vg_cluster_stats_file).  `deduplicate` does
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
 without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
-`--contained` always run on the GPU.  `info` reports the library and the optional CPU tools.
+`--contained` always run on the GPU.  `dereplicate` (this repository's command: prefilter, align and cd-hit clustering in one
+process, every genome compared with the representatives only; vg_dereplicate) always runs on the GPU.  `info` reports the library and the optional CPU tools.
 
 Multi-GPU: start one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 vclust.py align -i x.fna -o ani.tsv ...
@@ -225,6 +226,46 @@ def get_parser() -> argparse.ArgumentParser:
     cl.add_argument('--leiden-iterations', metavar='<int>', type=int, default=2)
     common(cl, threads=False)
 
+    # dereplicate (always vg_dereplicate: this repository's command)
+    dr = sub.add_parser('dereplicate', help='Cluster genomes into representatives (greedy, cd-hit): prefilter, align and cluster in one '
+                                            'process, comparing every genome with the representatives only',
+                        formatter_class=fmt, add_help=False)
+    io_args(dr, 'Input FASTA file or directory of files (gzipped or uncompressed)')
+    dr.add_argument('-k', '--k', metavar='<int>', type=int, default=25, choices=range(15, 31), help='Size of k-mer for the prefilter [%(default)s]')
+    dr.add_argument('--min-kmers', metavar='<int>', type=int, default=20,
+                    help='Minimum number of shared k-mers between two genomes [%(default)s]')
+    dr.add_argument('--min-ident', metavar='<float>', type=_unit_float, default=0.7,
+                    help='Minimum sequence identity (0-1) between two genomes, relative to the shorter one [%(default)s]')
+    dr.add_argument('--kmers-fraction', metavar='<float>', type=_unit_float, default=1.0,
+                    help='Fraction of k-mers to analyze in each genome (0-1) [%(default)s]')
+    for name, default, text in (('mal', 11, 'Min. anchor length'), ('msl', 7, 'Min. seed length'),
+                                ('mrd', 40, 'Max. dist. between approx. matches in reference'),
+                                ('mqd', 40, 'Max. dist. between approx. matches in query'),
+                                ('reg', 35, 'Min. considered region length'), ('aw', 15, 'Approx. window length'),
+                                ('am', 7, 'Max. no. of mismatches in approx. window'),
+                                ('ar', 3, 'Min. length of run ending approx. extension')):
+        dr.add_argument(f'--{name}', metavar='<int>', type=int, default=default, help=f'{text} [%(default)s]')
+    dr.add_argument('-r', '--out-repr', action='store_true', dest='representatives',
+                    help='Output a representative genome for each cluster [%(default)s]')
+    dr.add_argument('--algorithm', metavar='<str>', dest='algorithm', default='cd-hit', choices=['cd-hit'],
+                    help='Clustering algorithm [%(default)s]: a genome joins the earliest (longest) representative it has a passing '
+                         'row to, else it becomes one')
+    dr.add_argument('--metric', metavar='<str>', dest='metric', choices=['tani', 'gani', 'ani'], default='tani',
+                    help='Similarity metric for clustering [%(default)s]')
+    for name in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio'):
+        dr.add_argument(f'--{name}', metavar='<float>', dest=name, type=_unit_float, default=0, help=f'Min. {name} (0-1) [%(default)s]')
+    dr.add_argument('--num_alns', metavar='<int>', dest='num_alns', type=int, default=0,
+                    help='Max. number of local alignments between two genomes; 0 = all [%(default)s]')
+    dr.add_argument('--batch-genomes', metavar='<int>', type=int, dest='batch_genomes', default=None,
+                    help='Genomes compared with the representatives at a time; results do not depend on it [4096]')
+    dr.add_argument('--out-table', metavar='<file>', type=pathlib.Path, dest='table_path',
+                    help='Write the ANI rows that were computed (a subset of the rows of `align`) to the tsv <file>, with its .ids.tsv')
+    dr.add_argument('--outfmt', metavar='<str>', choices=ALIGN_OUTFMT.keys(), dest='outfmt', default='standard',
+                    help='Format of --out-table [%(default)s]\nchoices: ' + ','.join(ALIGN_OUTFMT.keys()))
+    dr.add_argument('--out-repr-fasta', metavar='<file>', type=pathlib.Path, dest='repr_fasta_path',
+                    help='Write the records of the representative genomes to the FASTA <file> (a single multi-FASTA input only)')
+    common(dr)
+
     sub.add_parser('info', help='Show information about the tool and its dependencies', formatter_class=fmt,
                    add_help=False)
 
@@ -232,7 +273,7 @@ def get_parser() -> argparse.ArgumentParser:
     if len(sys.argv[1:]) == 0:
         parser.print_help()
         parser.exit()
-    for name, sp in (('prefilter', pf), ('align', al), ('cluster', cl), ('deduplicate', dd)):
+    for name, sp in (('prefilter', pf), ('align', al), ('cluster', cl), ('deduplicate', dd), ('dereplicate', dr)):
         if sys.argv[-1] == name:
             sp.print_help()
             parser.exit()
@@ -623,6 +664,44 @@ def handle_deduplicate(args, parser, logger):
     run_subprocess(cmd, args.verbosity_level, logger)
 
 
+def dereplicate_call(args):
+    """What the front-end hands to vg_dereplicate for validated dereplicate arguments: the prefilter, align and cluster options as
+    prefilter_call, align_call and cluster_call pass them."""
+    from .stages import CLUSTER_FILTERS
+    mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
+    lz = {k: getattr(args, k) for k in ('mal', 'msl', 'mrd', 'mqd', 'reg', 'aw', 'am', 'ar')}
+    return dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta, batch_genomes=args.batch_genomes,
+                k=args.k, kmers_fraction=args.kmers_fraction, min_kmers=args.min_kmers, min_ident=args.min_ident, lz=lz,
+                algorithm=args.algorithm, metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives,
+                out_table=args.table_path, columns=ALIGN_OUTFMT[args.outfmt], out_repr_fasta=args.repr_fasta_path,
+                num_threads=args.num_threads, **mins)
+
+
+def handle_dereplicate(args, parser, logger):
+    """`dereplicate`: prefilter -> align -> cluster --algorithm cd-hit in one process, batch by batch against the representatives
+    (vg_dereplicate).  Always in the library; one GPU."""
+    args = validate_args_fasta_input(args, parser)
+    if _dist_env()[1] > 1:
+        parser.error('dereplicate runs on one GPU: start it without a multi-process launcher (WORLD_SIZE must be 1).')
+    if not vars(args).get(args.metric, 0):
+        parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+    if args.batch_genomes is not None and args.batch_genomes < 1:
+        parser.error('--batch-genomes must be at least 1.')
+    if args.repr_fasta_path is not None and not args.is_multifasta:
+        parser.error('--out-repr-fasta copies the records of one multi-FASTA file: it does not take a directory input.')
+    from . import stages
+    call = dereplicate_call(args)
+    desc = (f'libvclust_gpu dereplicate -k {args.k} --min-kmers {args.min_kmers} --min-ident {args.min_ident} --kmers-fraction {args.kmers_fraction} '
+            + ' '.join(f'--{k} {v}' for k, v in call['lz'].items()) + f' --algorithm {args.algorithm} --metric {args.metric}'
+            + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
+            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
+            + (f' --batch-genomes {args.batch_genomes}' if args.batch_genomes is not None else '')
+            + (f' --out-table {args.table_path}' if args.table_path is not None else '')
+            + (f' --out-repr-fasta {args.repr_fasta_path}' if args.repr_fasta_path is not None else '')
+            + f' [1 GPU] -> {args.output_path}')
+    run_native(desc, lambda: stages.dereplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
+
+
 def handle_info(args, parser, logger):
     lines = [f'Vclust (MI355X-native prefilter/align) version {__version__}', '', 'GPU path:']
     ok = True
@@ -654,7 +733,7 @@ def main():
     rank, world, _ = _dist_env()
     logger = create_logger('Vclust', getattr(args, 'verbosity_level', 0) if rank == 0 else 0)
     handlers = {'info': handle_info, 'deduplicate': handle_deduplicate, 'prefilter': handle_prefilter,
-                'align': handle_align, 'cluster': handle_cluster}
+                'align': handle_align, 'cluster': handle_cluster, 'dereplicate': handle_dereplicate}
     if args.command in handlers:
         handlers[args.command](args, parser, logger)
 

@@ -149,6 +149,7 @@ struct vg_genomes {
     std::vector<uint32_t, no_init_alloc<uint32_t>> nmask;     // base_off[n]/32 words (+ slack)
     // device residency
     int device = -1;
+    bool device_only = false;            // a subset gathered on the device (vg_subset.hip): packed / nmask above stay empty
     dbuf<uint32_t> d_packed, d_nmask;
     mutable dbuf<uint32_t> d_planes;     // the bases once more as bit planes ((lo, hi) word pair per 32 bases): what the LZ parse reads; made on first use (vg_align.hip)
     dbuf<int64_t> d_base_off, d_len;
@@ -212,6 +213,17 @@ int vg_choose_align_shift(int64_t total_len, int64_t n);
 int  vg_fmt_num(double x, char* buf);                 // LZ-ANI number format
 int  vg_fmt_len_ratio(int64_t a, int64_t b, char* buf);
 double vg_ani_shorter(int64_t shared, int64_t na, int64_t nb, int k);
+// One row of ani.tsv as numbers (vg_io.cpp).  vg_ani_row_values: what vg_write_ani computes for the task (q, r) from the integers of
+// the task (x) and of its reverse (rev) and the two lengths.  vg_ani_row_printed: those values as a reader of the file gets them --
+// each through the writer's formatter and the cluster parser's from_chars.  vg_cluster_row_passes: the filters of
+// vg_cluster_read_rows on such a row (minimums > 0 hold with >=, num_alns <= the maximum when that is > 0); *w = the metric's value.
+struct vg_ani_row { double tani, gani, ani, qcov, rcov, len_ratio; uint32_t num_alns; };
+void vg_ani_row_values(int64_t lq, int64_t lr, const vg_pair_stat& x, const vg_pair_stat& rev, vg_ani_row& row);
+void vg_ani_row_printed(int64_t lq, int64_t lr, const vg_ani_row& row, vg_ani_row& printed);
+bool vg_cluster_row_passes(const vg_cluster_params* p, const vg_ani_row& printed, double* w);
+// the records of FASTA files as the deduplicate stage reads them, and `which` of them written verbatim, in that order (vg_io.cpp)
+struct vg_fasta_text;
+void vg_fasta_write_records(const char* path, const vg_fasta_text& text, const std::vector<int64_t>& which);
 // cluster stage (vg_io.cpp): the first column of the ids file; the passing rows of ani.tsv (VG_EINVAL with file:line on a
 // missing column, an index outside the ids file or a malformed number); clusters.tsv
 void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);

@@ -405,6 +405,7 @@ extern "C" int vg_kmer_shared_sharded(vg_genomes* g, int k, double fraction, uin
                                       int64_t* set_sizes, vg_pair_count** pairs, int64_t* n_pairs) {
     VG_API_BEGIN
     if (!g || !c || !set_sizes || !pairs || !n_pairs) throw vg_error(VG_EINVAL, "vg_kmer_shared_sharded: null argument");
+    if (g->device_only) throw vg_error(VG_EINVAL, "vg_kmer_shared_sharded: a subset (vg_genomes_subset) has no host copy; the sharded calls take a loaded set");
     *pairs = nullptr; *n_pairs = 0;
     const int n = vg_genomes_count(g);
     if (!c->exchanges()) { check(vg_kmer_shared(g, k, fraction, 0, 1, min_shared, set_sizes, pairs, n_pairs)); return VG_OK; }
@@ -523,6 +524,7 @@ extern "C" int vg_lz_align_sharded(vg_genomes* g, const vg_task* tasks, int64_t 
                                    vg_pair_stat* stats, vg_region** regions, int64_t* n_regions) {
     VG_API_BEGIN
     if (!g || !c || (!tasks && n_tasks) || !p || (!stats && n_tasks)) throw vg_error(VG_EINVAL, "vg_lz_align_sharded: null argument");
+    if (g->device_only) throw vg_error(VG_EINVAL, "vg_lz_align_sharded: a subset (vg_genomes_subset) has no host copy; the sharded calls take a loaded set");
     if (!c->exchanges()) { check(vg_lz_align(g, tasks, n_tasks, p, stats, regions, n_regions)); return VG_OK; }
     if (regions) { *regions = nullptr; if (n_regions) *n_regions = 0; }
     const int W = c->world;
@@ -660,6 +662,7 @@ extern "C" int vg_lz_align_pairs_sharded(vg_genomes* g, const vg_pair_count* can
                                          vg_task** tasks_out, int64_t* n_tasks_out, vg_pair_stat** stats_out) {
     VG_API_BEGIN
     if (!g || !c || (!cand && n_cand) || !p || !tasks_out || !n_tasks_out || !stats_out) throw vg_error(VG_EINVAL, "vg_lz_align_pairs_sharded: null argument");
+    if (g->device_only) throw vg_error(VG_EINVAL, "vg_lz_align_pairs_sharded: a subset (vg_genomes_subset) has no host copy; the sharded calls take a loaded set");
     *tasks_out = nullptr; *n_tasks_out = 0; *stats_out = nullptr;
     const int n = vg_genomes_count(g);
     const int64_t n_tasks = 2 * n_cand;

@@ -603,13 +603,24 @@ extern "C" const char* vg_genomes_name(const vg_genomes* g, int idx) {
 
 extern "C" int vg_genomes_codes(const vg_genomes* g, int idx, uint8_t* out) {
     if (!g || !out || idx < 0 || idx >= g->n) return VG_EINVAL;
-    const int64_t p0 = g->base_off[(size_t)idx];
-    for (int64_t j = 0; j < g->len[(size_t)idx]; ++j) {
-        const int64_t p = p0 + j;
-        const bool n = (g->nmask[(size_t)(p >> 5)] >> (p & 31)) & 1u;
-        out[j] = n ? 4 : (uint8_t)((g->packed[(size_t)(p >> 4)] >> (2 * (p & 15))) & 3u);
+    VG_API_BEGIN
+    const int64_t p0 = g->base_off[(size_t)idx], len = g->len[(size_t)idx];
+    // a subset gathered on the device has no host copy: the words of this genome are downloaded (genomes start at multiples of 64 bases)
+    std::vector<uint32_t> pk, mk;
+    if (g->device_only && len > 0) {
+        vg_require_device();
+        pk.resize((size_t)((len + 15) / 16)); mk.resize((size_t)((len + 31) / 32));
+        VG_HIP(hipMemcpy(pk.data(), g->d_packed.p + p0 / 16, pk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        VG_HIP(hipMemcpy(mk.data(), g->d_nmask.p + p0 / 32, mk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
-    return VG_OK;
+    const uint32_t* packed = g->device_only ? pk.data() : g->packed.data();
+    const uint32_t* nmask = g->device_only ? mk.data() : g->nmask.data();
+    for (int64_t j = 0; j < len; ++j) {
+        const int64_t p = g->device_only ? j : p0 + j;
+        const bool n = (nmask[(size_t)(p >> 5)] >> (p & 31)) & 1u;
+        out[j] = n ? 4 : (uint8_t)((packed[(size_t)(p >> 4)] >> (2 * (p & 15))) & 3u);
+    }
+    VG_API_END
 }
 
 extern "C" int vg_genomes_to_device(vg_genomes* g) {
@@ -618,6 +629,7 @@ extern "C" int vg_genomes_to_device(vg_genomes* g) {
     vg_require_device();
     int dev = 0; VG_HIP(hipGetDevice(&dev));
     if (g->device == dev) return VG_OK;
+    if (g->device_only) throw vg_error(VG_EINVAL, "a subset lives on the device it was gathered on (device " + std::to_string(g->device) + "): it has no host copy to upload to another");
     if (g->device >= 0) {
         // resident on another device: the allocator knows every block's device and returns these to THAT device's
         // driver instead of caching them here (vg_dev_free)

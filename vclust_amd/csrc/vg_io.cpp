@@ -468,6 +468,46 @@ int vg_align_tasks_perm(const vg_genomes* g, const vg_pair_count* pairs, int64_t
 }
 
 // ---------------------------------------------------------------- ani.tsv / ids.tsv / aln.tsv
+void vg_ani_row_values(int64_t lq, int64_t lr, const vg_pair_stat& x, const vg_pair_stat& rev, vg_ani_row& row) {
+    row.ani = x.aln_len ? (double)x.n_match / (double)x.aln_len : 0.0;
+    row.gani = lq ? (double)x.n_match / (double)lq : 0.0;
+    row.qcov = lq ? (double)x.aln_len / (double)lq : 0.0;
+    row.rcov = lr ? (double)rev.aln_len / (double)lr : 0.0;
+    row.tani = (lq + lr) ? (double)((uint64_t)x.n_match + rev.n_match) / (double)(lq + lr) : 0.0;
+    row.len_ratio = lq == lr ? 1.0 : (double)std::min(lq, lr) / (double)std::max(lq, lr);
+    row.num_alns = x.n_regions;
+}
+void vg_ani_row_printed(int64_t lq, int64_t lr, const vg_ani_row& row, vg_ani_row& printed) {
+    char buf[64];
+    auto reread = [&](int n) {
+        double v = 0;
+        const auto r = std::from_chars(buf, buf + n, v);
+        if (r.ec != std::errc() || r.ptr != buf + n) throw vg_error(VG_EHIP, std::string("a printed number does not read back: ") + buf);
+        return v;
+    };
+    printed.tani = reread(vg_fmt_num(row.tani, buf)); printed.gani = reread(vg_fmt_num(row.gani, buf));
+    printed.ani = reread(vg_fmt_num(row.ani, buf)); printed.qcov = reread(vg_fmt_num(row.qcov, buf));
+    printed.rcov = reread(vg_fmt_num(row.rcov, buf));
+    printed.len_ratio = reread(vg_fmt_len_ratio(lq, lr, buf));
+    printed.num_alns = row.num_alns;
+}
+bool vg_cluster_row_passes(const vg_cluster_params* p, const vg_ani_row& v, double* w) {
+    *w = !strcmp(p->metric, "tani") ? v.tani : !strcmp(p->metric, "gani") ? v.gani : v.ani;
+    const std::pair<double, double> filters[] = { { v.tani, p->min_tani }, { v.gani, p->min_gani }, { v.ani, p->min_ani },
+                                                  { v.qcov, p->min_qcov }, { v.rcov, p->min_rcov }, { v.len_ratio, p->min_len_ratio } };
+    for (auto& fl : filters) if (fl.second > 0 && !(fl.first >= fl.second)) return false;
+    return !(p->max_num_alns > 0) || (double)v.num_alns <= (double)p->max_num_alns;
+}
+void vg_fasta_write_records(const char* path, const vg_fasta_text& text, const std::vector<int64_t>& which) {
+    std::vector<std::string_view> parts;
+    for (const int64_t i : which) {
+        const vg_fasta_rec& r = text.recs[(size_t)i];
+        parts.emplace_back(r.hdr - 1, (size_t)(r.end - (r.hdr - 1)));       // from the '>' to the start of the next record
+        if (r.end[-1] != '\n') parts.emplace_back("\n");                      // (the last record of a file without a final line end)
+    }
+    vg_write_file(path, parts);
+}
+
 extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_pair_stat* stats, int64_t n_tasks,
                             const vg_region* regions, int64_t n_regions, const char* out_path, const vg_align_params* p) {
     VG_API_BEGIN
@@ -508,11 +548,8 @@ extern "C" int vg_write_ani(const vg_genomes* g, const vg_task* tasks, const vg_
         for (int64_t t = lo; t < hi; ++t) {
             const vg_task& tk = tasks[t]; const vg_pair_stat& x = stats[t]; const vg_pair_stat& rev = stats[t ^ 1];
             int64_t lq = g->len[tk.q], lr = g->len[tk.r];
-            double ani = x.aln_len ? (double)x.n_match / (double)x.aln_len : 0.0;
-            double gani = lq ? (double)x.n_match / (double)lq : 0.0;
-            double qcov = lq ? (double)x.aln_len / (double)lq : 0.0;
-            double rcov = lr ? (double)rev.aln_len / (double)lr : 0.0;
-            double tani = (lq + lr) ? (double)((uint64_t)x.n_match + rev.n_match) / (double)(lq + lr) : 0.0;
+            vg_ani_row row; vg_ani_row_values(lq, lr, x, rev, row);
+            const double ani = row.ani, gani = row.gani, qcov = row.qcov, rcov = row.rcov, tani = row.tani;
             if (p->out_tani > 0 && tani < p->out_tani) continue;
             if (p->out_gani > 0 && gani < p->out_gani) continue;
             if (p->out_ani > 0 && ani < p->out_ani) continue;

@@ -6,8 +6,8 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, FLOW_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions,
-                   DedupParams, LzParams, MclParams, MclStats, PrefilterParams, check)
+from ._lib import (CLUSTER_ALGORITHMS, DEREP_ALGORITHMS, DEREP_BATCH_GENOMES, FLOW_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions,
+                   DedupParams, DerepFileParams, DerepParams, DerepStats, LzParams, MclParams, MclStats, PrefilterParams, check)
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -175,3 +175,40 @@ def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_thre
                                             C.byref(opt)))
         return
     check(_lib.load().vg_deduplicate(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm)))
+
+
+def derep_params(batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min_ident=0.7, lz=None, algorithm='cd-hit', metric='tani',
+                 num_alns=0, mins=None):
+    """vg_derep_params of dereplicate() and GenomeSet.dereplicate_set().  An algorithm the library does not know at all is refused
+    here; one it knows but dereplicate cannot run (anything but cd-hit) is refused by the library, before any device use."""
+    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
+    if algorithm not in known:
+        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices of dereplicate: {", ".join(DEREP_ALGORITHMS)})')
+    p = DerepParams()
+    p.k, p.kmers_fraction, p.min_kmers, p.min_ident = int(k), float(kmers_fraction), int(min_kmers), float(min_ident)
+    p.lz = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+    p.cluster = _cluster_params(known[algorithm], metric, num_alns, False, 0, 0, mins or {})
+    p.batch_genomes = DEREP_BATCH_GENOMES if batch_genomes is None else int(batch_genomes)
+    return p
+
+
+def dereplicate(paths, out_path, is_multifasta, batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min_ident=0.7, lz=None,
+                algorithm='cd-hit', metric='tani', num_alns=0, representatives=False, out_table=None, columns=None, out_repr_fasta=None,
+                num_threads=1, verbosity=0, **mins):
+    """clusters.tsv of the genomes in `paths` by greedy clustering against representatives only (vg_dereplicate; DESIGN.md section
+    13): the file that prefilter -> align with that filter -> cluster(algorithm='cd-hit') writes for the same options, for every
+    batch_genomes.  out_table: also an ani.tsv of the rows that were computed (columns: default the standard format) and its
+    .ids.tsv; out_repr_fasta: the records of the representatives, verbatim (one multi-FASTA input only).  -> the counts as a dict."""
+    st = DerepStats()
+    p = DerepFileParams()
+    p.derep = derep_params(batch_genomes, k, kmers_fraction, min_kmers, min_ident, lz, algorithm, metric, num_alns, mins)
+    p.representatives = int(bool(representatives))
+    columns = list(columns or ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov', 'num_alns', 'len_ratio'])
+    cols = (C.c_char_p * len(columns))(*[c.encode() for c in columns])
+    p.out_table_path = os.fsencode(str(out_table)) if out_table is not None else None
+    p.out_columns, p.n_out_columns = cols, len(columns)
+    p.out_repr_fasta_path = os.fsencode(str(out_repr_fasta)) if out_repr_fasta is not None else None
+    p.num_threads, p.verbosity, p.is_multifasta = int(num_threads), int(verbosity), int(bool(is_multifasta))
+    p.stats = C.pointer(st)
+    check(_lib.load().vg_dereplicate(_path_array(paths), len(paths), os.fsencode(str(out_path)), C.byref(p)))
+    return {name: getattr(st, name) for name, _ in DerepStats._fields_}
