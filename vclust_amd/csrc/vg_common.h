@@ -224,6 +224,9 @@ bool vg_cluster_row_passes(const vg_cluster_params* p, const vg_ani_row& printed
 // the records of FASTA files as the deduplicate stage reads them, and `which` of them written verbatim, in that order (vg_io.cpp)
 struct vg_fasta_text;
 void vg_fasta_write_records(const char* path, const vg_fasta_text& text, const std::vector<int64_t>& which);
+// the deduplicate stage's output (vg_io.cpp): the records with rep[i] == i, each header behind its file's prefix, in input order; level 0
+// = plain, 1..9 = gzip members of 4 MiB of text compressed on n_threads threads (the bytes do not depend on n_threads)
+void vg_fasta_write_kept(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, int level, int n_threads);
 // cluster stage (vg_io.cpp): the first column of the ids file; the passing rows of ani.tsv (VG_EINVAL with file:line on a
 // missing column, an index outside the ids file or a malformed number); clusters.tsv
 void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);

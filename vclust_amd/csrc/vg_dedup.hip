@@ -58,7 +58,6 @@
 // kernel, its exclusive scan and the read-back of the total are scan_total wherever they occur.
 #include "vg_common.h"
 #include <rocprim/rocprim.hpp>
-#include <zlib.h>
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -72,7 +71,6 @@ constexpr int WAVES = TPB / 64;
 constexpr int64_t HASH_CHUNK = 2048;        // words (16 Ki symbols) per hash task: 8 trips of 64 lanes x 16 bytes
 constexpr int64_t VERIFY_CHUNK = 2048;      // words per verification task
 constexpr int64_t STRETCH_WORDS = 8 << 20;  // 32 MiB of packed symbols: the unit of the overlapped upload
-constexpr size_t GZ_BLOCK = 4u << 20;       // uncompressed bytes per gzip member of the output
 
 std::atomic<int> g_hash_bits(128);
 std::atomic<int> g_anchor_symbols(16);      // contained mode: symbols of an anchor (test knob)
@@ -1192,48 +1190,6 @@ std::string first_token(const char* b, const char* e) {
     const char* q = b; while (q < e && *q != ' ' && *q != '\t' && *q != '\r') ++q;
     return std::string(b, q);
 }
-// the output FASTA: the kept records in input order, assembled in memory by all threads, then written plain or as gzip members
-// of GZ_BLOCK uncompressed bytes each (compressed in parallel: the bytes do not depend on the thread count)
-void write_fasta(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, int level, int T) {
-    const int64_t n = (int64_t)in.recs.size();
-    std::vector<int64_t> kept;
-    for (int64_t i = 0; i < n; ++i) if (rep[i] == (int32_t)i) kept.push_back(i);
-    auto size_of = [&](const vg_fasta_rec& r) {
-        const int64_t sl = r.end - r.seq;
-        return (int64_t)(1 + prefix[(size_t)r.file].size() + (r.hdr_end - r.hdr) + 1 + sl + (sl > 0 && r.end[-1] != '\n'));
-    };
-    std::vector<int64_t> at(kept.size() + 1, 0);
-    for (size_t k = 0; k < kept.size(); ++k) at[k + 1] = at[k] + size_of(in.recs[(size_t)kept[k]]);
-    std::vector<char, no_init_alloc<char>> buf((size_t)at.back());
-    vg_parallel_for((int64_t)kept.size(), T, [&](int64_t k) {
-        const vg_fasta_rec& r = in.recs[(size_t)kept[(size_t)k]];
-        char* o = buf.data() + at[(size_t)k];
-        const std::string& pf = prefix[(size_t)r.file];
-        *o++ = '>'; memcpy(o, pf.data(), pf.size()); o += pf.size();
-        memcpy(o, r.hdr, (size_t)(r.hdr_end - r.hdr)); o += r.hdr_end - r.hdr; *o++ = '\n';
-        memcpy(o, r.seq, (size_t)(r.end - r.seq)); o += r.end - r.seq;
-        if (r.end > r.seq && r.end[-1] != '\n') *o++ = '\n';
-    });
-    if (level <= 0) { vg_write_file(path, { { buf.data(), buf.size() } }); return; }
-    const int64_t nb = std::max<int64_t>(1, ((int64_t)buf.size() + (int64_t)GZ_BLOCK - 1) / (int64_t)GZ_BLOCK);
-    std::vector<std::vector<unsigned char>> member((size_t)nb);
-    vg_parallel_for(nb, T, [&](int64_t b) {
-        const size_t lo = (size_t)b * GZ_BLOCK, len = std::min(GZ_BLOCK, buf.size() - std::min(buf.size(), lo));
-        z_stream zs; memset(&zs, 0, sizeof zs);
-        if (deflateInit2(&zs, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw vg_error(VG_ENOMEM, "deflateInit2 failed");
-        std::vector<unsigned char>& out = member[(size_t)b];
-        out.resize(deflateBound(&zs, (uLong)len) + 32);
-        zs.next_in = (Bytef*)(buf.data() + lo); zs.avail_in = (uInt)len;
-        zs.next_out = out.data(); zs.avail_out = (uInt)out.size();
-        const int rc = deflate(&zs, Z_FINISH);
-        out.resize(out.size() - zs.avail_out);
-        deflateEnd(&zs);
-        if (rc != Z_STREAM_END) throw vg_error(VG_EIO, "gzip compression failed");
-    });
-    std::vector<std::string_view> parts;
-    for (auto& m : member) parts.emplace_back((const char*)m.data(), m.size());
-    vg_write_file(path, parts);
-}
 // offset: nullptr, or (circular and contained mode) the fourth column; repeat: nullptr, or (terminal repeats) the fifth and
 // sixth: the removed record's and the kept record's
 void write_duplicates(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, const int8_t* strand,
@@ -1336,7 +1292,7 @@ int deduplicate_files(const char* const* paths, int n_paths, const char* const* 
     run_mode(ps, mode, min_repeat, rep.data(), strand.data(), offset.data(), repeat.data(), st, cst, rst);
     ps.d_words.release();
     vg_host_mark("dedup: groups computed");
-    write_fasta(out_path, in, prefix, rep.data(), p->gzip_level, T);
+    vg_fasta_write_kept(out_path, in, prefix, rep.data(), p->gzip_level, T);
     write_duplicates(dup_path, in, prefix, rep.data(), strand.data(), with_offset ? offset.data() : nullptr,
                      min_repeat > 0 ? repeat.data() : nullptr);
     vg_host_mark("dedup: written");

@@ -193,12 +193,14 @@ bool inflate_stream(bitreader& br, outbuf& out, size_t member_start) {
                 // Fast loop: the bit buffer lives in locals; one refill per symbol group (a literal/length code, its extra
                 // bits, a distance code and its extra bits need <= 48 of the >= 56 bits a refill leaves); the table entry
                 // of the NEXT symbol is loaded before the match is copied, so that load and copy overlap.
-                const size_t stop = out.cap - 600;
+                // (the end of the input ends it too: stop drops to 0 when a refill runs dry, so a cut stream is not decoded on,
+                // zeros for bits, until the output chunk is full)
+                size_t stop = out.cap - 600;
                 bool end_of_block = false;
                 uint64_t buf = br.buf; int cnt = br.cnt; size_t pos = br.pos; bool over = br.over;
                 char* const base = out.p; size_t op = out.n;
 #define VG_REFILL() do { if (pos + 8 <= n_in) { uint64_t w_; memcpy(&w_, in + pos, 8); buf |= w_ << cnt; pos += (size_t)((63 - cnt) >> 3); cnt |= 56; } \
-                         else { while (cnt <= 56) { if (pos < n_in) buf |= (uint64_t)in[pos++] << cnt; else over = true; cnt += 8; } } } while (0)
+                         else { while (cnt <= 56) { if (pos < n_in) buf |= (uint64_t)in[pos++] << cnt; else { over = true; stop = 0; } cnt += 8; } } } while (0)
 #define VG_SUB(T, e_, mb) do { if (kind_of(e_) == 4) e_ = (T)[((e_) >> 16) + ((uint32_t)(buf >> (mb)) & ((1u << ((e_) & 0xff)) - 1u))]; } while (0)
                 VG_REFILL();
                 uint32_t e = TL[buf & ((1u << LL_MAIN) - 1)];
@@ -265,8 +267,10 @@ bool inflate_stream(bitreader& br, outbuf& out, size_t member_start) {
 // The whole file: gzip members one after the other.  On success *out_p / *out_n hold the text (malloc'd: the caller frees it).
 bool vg_fast_gunzip(const unsigned char* in, size_t n, int n_threads, char** out_p, size_t* out_n) {
     outbuf out;
-    // the last member's ISIZE is the length of its text modulo 2^32: the size of the whole for the usual one-member file
-    if (n >= 18) { uint32_t isz; memcpy(&isz, in + n - 4, 4); if (!out.room((size_t)isz + (1u << 16))) return false; }
+    // the last member's ISIZE is the length of its text modulo 2^32: the size of the whole for the usual one-member file.
+    // It is read before anything is verified, so it only counts as far as n bytes of deflate can reach (1032:1 at most, a
+    // 258-byte match out of two bits); a trailer that asks for more is damaged and nothing is reserved for it
+    if (n >= 18) { uint32_t isz; memcpy(&isz, in + n - 4, 4); if ((size_t)isz <= 1032 * n && !out.room((size_t)isz + (1u << 16))) return false; }
     struct member { size_t o0, o1; uint32_t crc; };
     std::vector<member> members;
     size_t at = 0;

@@ -6,6 +6,7 @@
 //   ani.aln.tsv         layout of example/output/ani.aln.tsv     
 //   cluster stage       ids file + ani.tsv rows in, clusters.tsv out
 #include "vg_common.h"
+#include <climits>
 #include <cmath>
 #include <math.h>
 #include <stdio.h>
@@ -21,6 +22,7 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <zlib.h>
 
 // ---------------------------------------------------------------- numbers
 double vg_ani_shorter(int64_t shared, int64_t na, int64_t nb, int k) {
@@ -307,9 +309,10 @@ bool filter_cell(const char* q, const char* fe, long& ci, double& val) {
     if (!colon) return false;
     ci = 0;
     const char* d = q; bool ok = d < colon;
-    for (; d < colon; ++d) { if (*d < '0' || *d > '9') { ok = false; break; } ci = ci * 10 + (*d - '0'); }
+    // (a column number too long for a long saturates, as atol's does: such a column does not exist)
+    for (; d < colon; ++d) { if (*d < '0' || *d > '9') { ok = false; break; } ci = ci > (LONG_MAX - 9) / 10 ? LONG_MAX : ci * 10 + (*d - '0'); }
     if (!ok) ci = atol(std::string(q, colon).c_str());
-    ci -= 1;
+    if (ci > LONG_MIN) ci -= 1;
     // value: digits '.' digits with <= 15 digits is exact as mantissa / 10^k; anything else goes to strtod
     static const double p10[16] = { 1, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15 };
     uint64_t m = 0; int nd = 0, frac = -1; bool plain = colon + 1 < fe;
@@ -505,6 +508,50 @@ void vg_fasta_write_records(const char* path, const vg_fasta_text& text, const s
         parts.emplace_back(r.hdr - 1, (size_t)(r.end - (r.hdr - 1)));       // from the '>' to the start of the next record
         if (r.end[-1] != '\n') parts.emplace_back("\n");                      // (the last record of a file without a final line end)
     }
+    vg_write_file(path, parts);
+}
+
+// the deduplicate stage's output FASTA: the kept records (rep[i] == i) in input order, assembled in memory by all threads, then
+// written plain or as gzip members of GZ_BLOCK uncompressed bytes each (compressed in parallel: the bytes do not depend on the thread count)
+constexpr size_t GZ_BLOCK = 4u << 20;
+void vg_fasta_write_kept(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, int level, int T) {
+    const int64_t n = (int64_t)in.recs.size();
+    std::vector<int64_t> kept;
+    for (int64_t i = 0; i < n; ++i) if (rep[i] == (int32_t)i) kept.push_back(i);
+    auto size_of = [&](const vg_fasta_rec& r) {
+        const int64_t sl = r.end - r.seq;
+        return (int64_t)(1 + prefix[(size_t)r.file].size() + (r.hdr_end - r.hdr) + 1 + sl + (sl > 0 && r.end[-1] != '\n'));
+    };
+    std::vector<int64_t> at(kept.size() + 1, 0);
+    for (size_t k = 0; k < kept.size(); ++k) at[k + 1] = at[k] + size_of(in.recs[(size_t)kept[k]]);
+    std::vector<char, no_init_alloc<char>> buf((size_t)at.back());
+    vg_parallel_for((int64_t)kept.size(), T, [&](int64_t k) {
+        const vg_fasta_rec& r = in.recs[(size_t)kept[(size_t)k]];
+        char* o = buf.data() + at[(size_t)k];
+        const std::string& pf = prefix[(size_t)r.file];
+        *o++ = '>'; memcpy(o, pf.data(), pf.size()); o += pf.size();
+        memcpy(o, r.hdr, (size_t)(r.hdr_end - r.hdr)); o += r.hdr_end - r.hdr; *o++ = '\n';
+        memcpy(o, r.seq, (size_t)(r.end - r.seq)); o += r.end - r.seq;
+        if (r.end > r.seq && r.end[-1] != '\n') *o++ = '\n';
+    });
+    if (level <= 0) { vg_write_file(path, { { buf.data(), buf.size() } }); return; }
+    const int64_t nb = std::max<int64_t>(1, ((int64_t)buf.size() + (int64_t)GZ_BLOCK - 1) / (int64_t)GZ_BLOCK);
+    std::vector<std::vector<unsigned char>> member((size_t)nb);
+    vg_parallel_for(nb, T, [&](int64_t b) {
+        const size_t lo = (size_t)b * GZ_BLOCK, len = std::min(GZ_BLOCK, buf.size() - std::min(buf.size(), lo));
+        z_stream zs; memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw vg_error(VG_ENOMEM, "deflateInit2 failed");
+        std::vector<unsigned char>& out = member[(size_t)b];
+        out.resize(deflateBound(&zs, (uLong)len) + 32);
+        zs.next_in = (Bytef*)(buf.data() + lo); zs.avail_in = (uInt)len;
+        zs.next_out = out.data(); zs.avail_out = (uInt)out.size();
+        const int rc = deflate(&zs, Z_FINISH);
+        out.resize(out.size() - zs.avail_out);
+        deflateEnd(&zs);
+        if (rc != Z_STREAM_END) throw vg_error(VG_EIO, "gzip compression failed");
+    });
+    std::vector<std::string_view> parts;
+    for (auto& m : member) parts.emplace_back((const char*)m.data(), m.size());
     vg_write_file(path, parts);
 }
 
