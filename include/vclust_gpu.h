@@ -101,6 +101,25 @@ int vg_genomes_to_device(vg_genomes* g);
  * VG_EINVAL.  An id outside [0, n) or listed twice is VG_EINVAL naming it, and so is a set that is not resident
  * (vg_genomes_to_device); all three are raised before any device use.  n_ids = 0 gives a valid empty set. */
 int vg_genomes_subset(const vg_genomes* g, const int32_t* ids, int n_ids, vg_genomes** out);
+/* A subset extended in place (this repository's call; no reference call site): the genomes ids[0 .. n_ids) of `parent` are appended
+ * behind the last genome of `sub`, in that order, by the layout rules of vg_genomes_subset and by one gather kernel (profile scope
+ * `derep_extend`) that writes the appended genomes and the slack behind them and neither reads nor copies the genomes already there.
+ * sub must be a set vg_genomes_subset made from this very parent (it may be empty); afterwards it is, to every kernel, the set
+ * vg_genomes_subset would make of all its genomes.  When the appended bases do not fit, the buffers grow to at least 1.5 times their
+ * size, which costs one copy device to device of the resident part (vg_genomes_reserve avoids it).  Everything the set keeps of its
+ * contents (bit planes, align order, the index plans of vg_lz_prepare) is dropped and remade lazily.  VG_EINVAL, before any device
+ * use: a null argument, an id outside the parent, listed twice or in sub already, a sub that vg_genomes_subset did not make or made
+ * from another parent, a parent that is not resident or on another device than sub.  n_ids = 0 is valid. */
+int vg_genomes_extend(vg_genomes* sub, const vg_genomes* parent, const int32_t* ids, int n_ids);
+/* The inverse: every genome of `sub` from n_keep on is dropped, and the slack behind the new last genome is written afresh, so that
+ * a kernel that reads past the end sees what it sees in the set vg_genomes_subset makes of the kept genomes.  The capacity stays;
+ * the caches are dropped as by vg_genomes_extend.  VG_EINVAL, before any device use: null, n_keep outside 0..n, a set that
+ * vg_genomes_subset did not make. */
+int vg_genomes_truncate(vg_genomes* sub, int n_keep);
+/* Room for `genomes` genomes of `bases` bases in all (padding is added by the call: a whole block per genome, the worst case of the
+ * loader's rule), so that extending `sub` up to there never moves it.  Never shrinks.  VG_EINVAL, before any device use: null, a
+ * negative count, a set that vg_genomes_subset did not make. */
+int vg_genomes_reserve(vg_genomes* sub, int64_t bases, int64_t genomes);
 
 /* ------------------------------------------------------------------ prefilter --------- */
 typedef struct { uint32_t a, b, shared; } vg_pair_count;   /* a > b (input order ids) */
@@ -578,8 +597,9 @@ void vg_cluster_mcl_set_table_slots(int slots);
  * section 13 is the contract).  Objects are the genomes in align order (vg_align_order; rank = object index, as in ani.ids.tsv).
  * The result is the one of vg_kmer_shared + vg_filter_pairs -> vg_lz_align of every kept pair -> vg_cluster_graph(VG_CLUSTER_CDHIT) on
  * the rows that pass the cluster filters AS ani.tsv PRINTS THEM, but a genome is only ever compared with the representatives found
- * so far and with the batch-mates that joined none of them: per batch of `batch_genomes` consecutive ranks, a subset
- * [representatives | batch] (vg_genomes_subset), vg_kmer_shared_new with the representatives as the database, the pairs (batch
+ * so far and with the batch-mates that joined none of them: per batch of `batch_genomes` consecutive ranks, the working set
+ * [representatives | batch] (the batch appended by vg_genomes_extend, dropped again by vg_genomes_truncate, its founders appended for
+ * good), vg_kmer_shared_new with the representatives as the database, the pairs (batch
  * genome, representative) aligned first, then the pairs among the batch genomes still without a representative, and
  * vg_cluster_update_graph(VG_CLUSTER_CDHIT) with the representatives as the prior clustering.  The representatives stay in HBM. */
 typedef struct {
@@ -621,6 +641,34 @@ typedef struct {
 /* File to file: FASTA in, clusters.tsv (the file vg_cluster writes) out.  verbosity >= 1: one summary line on stderr,
  * `Dereplicate: <n> genomes, <r> representatives, <b> batches, <p> pairs aligned (<c> candidates skipped)`. */
 int vg_dereplicate(const char* const* fasta_paths, int n_paths, const char* out_path, const vg_derep_file_params* p);
+
+/* New genomes added to an earlier run ("Update"): the clusters and representatives of a prior clustering are
+ * kept as they are, and every other object is dereplicated on top of them.  The result is vg_cluster_update_graph(VG_CLUSTER_CDHIT)
+ * over the whole edge graph of vg_dereplicate_set with that prior: new objects are visited in index order and join the earliest
+ * representative in visit order (the prior representatives in index order, then the founders), else found a cluster.  Only the prior
+ * REPRESENTATIVES are ever gathered, indexed or aligned: a row to a prior member joins nothing.  vg_dereplicate_set is this call
+ * with no prior object.  In vg_derep_stats, `representatives` then counts the prior ones too, `founded` the new ones only, and
+ * `joined_prior` the new genomes that joined a representative older than their batch, prior or not. */
+typedef struct {
+    int64_t prior_objects;          /* objects with a prior cluster */
+    int64_t prior_representatives;  /* = prior clusters */
+    int64_t joined_prior_cluster;   /* new genomes that joined a representative the prior named (the rest of joined_prior + joined_new joined a founder) */
+} vg_derep_update_stats;
+/* The array-level call.  g: any set; n_db: the number of database genomes in it (input ids 0 .. n_db - 1, as vg_genomes_load_db_new
+ * returns it) -- checked against the set and otherwise not read: a database genome without a prior cluster is a new object like any
+ * other.  prior_rep[n], indexed by object (rank): the object index of the representative of its prior cluster, or -1 = new, by the
+ * rules of vg_cluster_update_graph.  Everything else as vg_dereplicate_set; ust may be NULL.  Refused with VG_EINVAL before any
+ * device use: what vg_dereplicate_set refuses, n_db outside 0..n, a prior_rep value outside -1..n-1 or not its own representative. */
+int vg_dereplicate_update_set(vg_genomes* g, int n_db, const vg_derep_params* p, const int32_t* prior_rep, int32_t* label, int32_t* representative,
+                              vg_task** tasks, vg_pair_stat** stats_rows, int64_t* n_tasks, vg_derep_stats* st, vg_derep_update_stats* ust);
+/* File to file: the genome set is the one of vg_genomes_load_db_new (the database, then the new genomes), and prior_path is a
+ * clusters.tsv read against its ids exactly as vg_cluster_update reads one (by name; prior_is_repr: column 2 holds representative
+ * ids; same VG_EINVAL messages).  clusters.tsv is byte for byte the file of vg_prefilter_new -> vg_align_new with that filter ->
+ * vg_cluster_update(VG_CLUSTER_CDHIT) for a prior that covers the database.  p as for vg_dereplicate; the table's .ids.tsv is the
+ * combined set's, and the representatives' FASTA needs one multi-FASTA file on each side (the database's records first).
+ * verbosity >= 1 adds a second line, `Dereplicate update: ...`, with the counts of ust. */
+int vg_dereplicate_update(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, const char* prior_path, int prior_is_repr,
+                          const char* out_path, const vg_derep_file_params* p, vg_derep_update_stats* ust);
 
 /* ------------------------------------------------------------------ deduplicate ------- */
 /* The first stage: FASTA files -> one FASTA of the distinct sequences + a duplicates list, in place of mfasta-tool

@@ -75,6 +75,11 @@ class DerepStats(C.Structure):
                                                 'joined_prior', 'joined_new', 'founded')]
 
 
+class DerepUpdateStats(C.Structure):
+    """vg_derep_update_stats: what dereplicate counts beside DerepStats when it adds genomes to an earlier run"""
+    _fields_ = [(name, C.c_int64) for name in ('prior_objects', 'prior_representatives', 'joined_prior_cluster')]
+
+
 class DerepFileParams(C.Structure):
     _fields_ = [('derep', DerepParams), ('representatives', C.c_int), ('out_table_path', C.c_char_p),
                 ('out_columns', C.POINTER(C.c_char_p)), ('n_out_columns', C.c_int), ('out_repr_fasta_path', C.c_char_p),
@@ -185,6 +190,9 @@ SYMBOLS = {
     'vg_genomes_codes': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'vg_genomes_to_device': (C.c_int, [C.c_void_p]),
     'vg_genomes_subset': (C.c_int, [C.c_void_p, P(C.c_int32), C.c_int, P(C.c_void_p)]),
+    'vg_genomes_extend': (C.c_int, [C.c_void_p, C.c_void_p, P(C.c_int32), C.c_int]),
+    'vg_genomes_truncate': (C.c_int, [C.c_void_p, C.c_int]),
+    'vg_genomes_reserve': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     'vg_kmer_shared': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint32,
                                  P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
     'vg_kmer_shared_new': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
@@ -266,6 +274,10 @@ SYMBOLS = {
     'vg_dereplicate_set': (C.c_int, [C.c_void_p, P(DerepParams), P(C.c_int32), P(C.c_int32), P(P(Task)), P(P(PairStat)), P(C.c_int64),
                                      P(DerepStats)]),
     'vg_dereplicate': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(DerepFileParams)]),
+    'vg_dereplicate_update_set': (C.c_int, [C.c_void_p, C.c_int, P(DerepParams), P(C.c_int32), P(C.c_int32), P(C.c_int32), P(P(Task)), P(P(PairStat)),
+                                            P(C.c_int64), P(DerepStats), P(DerepUpdateStats)]),
+    'vg_dereplicate_update': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_int, C.c_char_p, C.c_int, C.c_char_p, P(DerepFileParams),
+                                        P(DerepUpdateStats)]),
     'vg_deduplicate': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams)]),
     'vg_dedup_seqs': (C.c_int, [C.c_char_p, P(C.c_int64), C.c_int64, P(C.c_int32), P(C.c_int8), P(DedupStats)]),
     'vg_deduplicate_ex': (C.c_int, [P(C.c_char_p), C.c_int, P(C.c_char_p), C.c_char_p, C.c_char_p, P(DedupParams), P(DedupOptions)]),

@@ -10,7 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, DerepStats, KernelTime, LinkageStats, LzParams, MclParams, MclStats, PairCount, PairStat,
+from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, DerepStats, DerepUpdateStats, KernelTime, LinkageStats, LzParams, MclParams, MclStats, PairCount, PairStat,
                    PrefilterParams, Region, Task, check)
 
 ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
@@ -154,24 +154,56 @@ class GenomeSet:
         check(self._lib.vg_genomes_subset(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(h)))
         return GenomeSet(h)
 
+    def extend(self, parent, ids):
+        """Append the genomes `ids` of `parent`, in that order, behind the last genome of this set, in place (vg_genomes_extend).  This
+        set must be a subset() of that very parent (it may be empty).  Only the appended genomes are written; the genomes already
+        here are neither read nor copied, unless the buffers have to grow (reserve() avoids that).  An id outside the parent, listed
+        twice or in this set already is an error."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        check(self._lib.vg_genomes_extend(self._h, parent._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids)))
+
+    def truncate(self, n):
+        """Drop every genome from n on, in place (vg_genomes_truncate): what is left is, to every kernel, the subset() of the kept
+        genomes.  The capacity stays."""
+        check(self._lib.vg_genomes_truncate(self._h, int(n)))
+
+    def reserve(self, bases, genomes):
+        """Room for `genomes` genomes of `bases` bases in all (vg_genomes_reserve; padding is added by the call), so that extend()
+        up to there never moves the set."""
+        check(self._lib.vg_genomes_reserve(self._h, int(bases), int(genomes)))
+
     def dereplicate_set(self, batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min_ident=0.7, lz=None, algorithm='cd-hit',
-                        metric='tani', num_alns=0, want_rows=False, **mins):
+                        metric='tani', num_alns=0, want_rows=False, n_db=0, prior_rep=None, **mins):
         """Greedy clustering against representatives only (vg_dereplicate_set): the result of kmer_shared ->
         filter_pairs -> lz_align -> cluster_graph('cd-hit') on the rows that pass the filters as ani.tsv prints them, computed batch
         by batch against the representatives found so far.  mins: tani=, gani=, ani=, qcov=, rcov=, len_ratio=; the metric's must be
         above 0.  -> (label int32[n], representative int32[n], stats dict), indexed by rank (align_order); with want_rows=True also
-        (tasks, stats rows) of every aligned ordered pair, in input-order ids, as write_ani takes them."""
+        (tasks, stats rows) of every aligned ordered pair, in input-order ids, as write_ani takes them.
+        prior_rep (one entry per rank: the rank of the representative of its prior cluster, -1 = new) adds the other genomes to
+        that clustering (vg_dereplicate_update_set): the result of cluster_update_graph('cd-hit') with that prior, with only the
+        prior representatives ever compared; n_db is the number of database genomes of a load_db_new set.  The stats then also
+        hold prior_objects, prior_representatives and joined_prior_cluster."""
         from .stages import derep_params
         prm = derep_params(batch_genomes, k, kmers_fraction, min_kmers, min_ident, lz, algorithm, metric, num_alns, mins)
         n = len(self)
         label, rep = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
-        st = DerepStats()
+        st, ust = DerepStats(), DerepUpdateStats()
         P = C.POINTER
         tp, sp, nt = P(Task)(), P(PairStat)(), C.c_int64()
-        check(self._lib.vg_dereplicate_set(self._h, C.byref(prm), label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
-                                           C.byref(tp) if want_rows else None, C.byref(sp) if want_rows else None,
-                                           C.byref(nt) if want_rows else None, C.byref(st)))
+        rows = (C.byref(tp) if want_rows else None, C.byref(sp) if want_rows else None, C.byref(nt) if want_rows else None)
+        if prior_rep is None and not n_db:
+            check(self._lib.vg_dereplicate_set(self._h, C.byref(prm), label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), *rows,
+                                               C.byref(st)))
+        else:
+            prior = np.full(n, -1, dtype=np.int32) if prior_rep is None else np.ascontiguousarray(prior_rep, dtype=np.int32)
+            if len(prior) != n:
+                raise ValueError('prior_rep must have one entry per genome')
+            check(self._lib.vg_dereplicate_update_set(self._h, int(n_db), C.byref(prm), prior.ctypes.data_as(P(C.c_int32)),
+                                                      label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), *rows, C.byref(st),
+                                                      C.byref(ust)))
         stats = {name: getattr(st, name) for name, _ in DerepStats._fields_}
+        if prior_rep is not None or n_db:
+            stats.update({name: getattr(ust, name) for name, _ in DerepUpdateStats._fields_})
         if not want_rows:
             return label[:n], rep[:n], stats
         return label[:n], rep[:n], stats, (_take(tp, nt.value, TASK_DTYPE), _take(sp, nt.value, STAT_DTYPE))

@@ -12,7 +12,8 @@ after clusters.tsv is written, whoever wrote it (the per-cluster report: vg_clus
 the same with bin/mfasta-tool: the pass-through where that binary exists, the GPU (vg_deduplicate)
 without it; `--circular` (with `--terminal-repeat <int>`: assembler overlaps taken off first) and
 `--contained` always run on the GPU.  `dereplicate` (this repository's command: prefilter, align and cd-hit clustering in one
-process, every genome compared with the representatives only; vg_dereplicate) always runs on the GPU.  `info` reports the library and the optional CPU tools.
+process, every genome compared with the representatives only; vg_dereplicate; with `--db` and `--prior` new genomes added to the
+clusters of an earlier run, vg_dereplicate_update) always runs on the GPU.  `info` reports the library and the optional CPU tools.
 
 Multi-GPU: start one process per GPU, e.g.
     python -m torch.distributed.run --nproc-per-node 8 vclust.py align -i x.fna -o ani.tsv ...
@@ -231,6 +232,12 @@ def get_parser() -> argparse.ArgumentParser:
                                             'process, comparing every genome with the representatives only',
                         formatter_class=fmt, add_help=False)
     io_args(dr, 'Input FASTA file or directory of files (gzipped or uncompressed)')
+    db_arg(dr)
+    dr.add_argument('--prior', metavar='<file>', type=_existing_path, dest='prior_path',
+                    help='clusters.tsv of an earlier run over the genomes of --db: its clusters and representatives are kept as they '
+                         'are, the genomes of -i are added to them, and only its representatives are ever compared (needs --db)')
+    dr.add_argument('--prior-repr', action='store_true', dest='prior_repr',
+                    help='The second column of --prior holds representative ids, as --out-repr writes them [%(default)s]')
     dr.add_argument('-k', '--k', metavar='<int>', type=int, default=25, choices=range(15, 31), help='Size of k-mer for the prefilter [%(default)s]')
     dr.add_argument('--min-kmers', metavar='<int>', type=int, default=20,
                     help='Minimum number of shared k-mers between two genomes [%(default)s]')
@@ -263,7 +270,8 @@ def get_parser() -> argparse.ArgumentParser:
     dr.add_argument('--outfmt', metavar='<str>', choices=ALIGN_OUTFMT.keys(), dest='outfmt', default='standard',
                     help='Format of --out-table [%(default)s]\nchoices: ' + ','.join(ALIGN_OUTFMT.keys()))
     dr.add_argument('--out-repr-fasta', metavar='<file>', type=pathlib.Path, dest='repr_fasta_path',
-                    help='Write the records of the representative genomes to the FASTA <file> (a single multi-FASTA input only)')
+                    help='Write the records of the representative genomes to the FASTA <file> (a single multi-FASTA input only; '
+                         'with --db, one on each side: the records of --db first)')
     common(dr)
 
     sub.add_parser('info', help='Show information about the tool and its dependencies', formatter_class=fmt,
@@ -670,16 +678,27 @@ def dereplicate_call(args):
     from .stages import CLUSTER_FILTERS
     mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
     lz = {k: getattr(args, k) for k in ('mal', 'msl', 'mrd', 'mqd', 'reg', 'aw', 'am', 'ar')}
-    return dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta, batch_genomes=args.batch_genomes,
+    call = dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta, batch_genomes=args.batch_genomes,
                 k=args.k, kmers_fraction=args.kmers_fraction, min_kmers=args.min_kmers, min_ident=args.min_ident, lz=lz,
                 algorithm=args.algorithm, metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives,
                 out_table=args.table_path, columns=ALIGN_OUTFMT[args.outfmt], out_repr_fasta=args.repr_fasta_path,
                 num_threads=args.num_threads, **mins)
+    if getattr(args, 'db_paths', None) is not None:       # --db --prior: vg_dereplicate_update
+        call.update(db_paths=args.db_paths, prior_path=args.prior_path, prior_repr=bool(args.prior_repr))
+    return call
 
 
 def handle_dereplicate(args, parser, logger):
     """`dereplicate`: prefilter -> align -> cluster --algorithm cd-hit in one process, batch by batch against the representatives
-    (vg_dereplicate).  Always in the library; one GPU."""
+    (vg_dereplicate).  With --db and --prior the genomes of -i are added to the clusters of an earlier run
+    over --db (vg_dereplicate_update).  Always in the library; one GPU."""
+    prior_path, db_path = getattr(args, 'prior_path', None), getattr(args, 'db_path', None)
+    if prior_path is None and getattr(args, 'prior_repr', False):
+        parser.error('--prior-repr describes the file of --prior: it needs --prior.')
+    if prior_path is not None and db_path is None:
+        parser.error('--prior names the clusters of the genomes of --db: it needs --db.')
+    if db_path is not None and prior_path is None:
+        parser.error('--db holds the genomes of an earlier run: it needs the clusters.tsv of that run as --prior.')
     args = validate_args_fasta_input(args, parser)
     if _dist_env()[1] > 1:
         parser.error('dereplicate runs on one GPU: start it without a multi-process launcher (WORLD_SIZE must be 1).')
@@ -698,6 +717,7 @@ def handle_dereplicate(args, parser, logger):
             + (f' --batch-genomes {args.batch_genomes}' if args.batch_genomes is not None else '')
             + (f' --out-table {args.table_path}' if args.table_path is not None else '')
             + (f' --out-repr-fasta {args.repr_fasta_path}' if args.repr_fasta_path is not None else '')
+            + _db_description(args) + (f' --prior {args.prior_path}' + (' --prior-repr' if args.prior_repr else '') if args.db_paths is not None else '')
             + f' [1 GPU] -> {args.output_path}')
     run_native(desc, lambda: stages.dereplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
 

@@ -136,6 +136,7 @@ template <class T> struct no_init_alloc : std::allocator<T> {
     template <class U, class... A> void construct(U* p, A&&... a) { ::new ((void*)p) U(std::forward<A>(a)...); }
 };
 
+inline uint64_t vg_genomes_next_uid() { static std::atomic<uint64_t> last{0}; return ++last; }
 struct vg_genomes {
     int n = 0;
     int align_shift = 6;                 // genomes start at multiples of (1 << align_shift) bases
@@ -155,6 +156,14 @@ struct vg_genomes {
     dbuf<int64_t> d_base_off, d_len;
     dbuf<uint8_t> d_has_n;
     dbuf<uint32_t> d_blk2g;
+    // a device-only set is extended and truncated in place (vg_genomes_extend / vg_genomes_truncate, vg_subset.hip): its memory belongs
+    // to the cap_* buffers, which may be larger than what is used, and the d_* arrays above are windows of exactly the used part
+    dbuf<uint32_t> cap_packed, cap_nmask, cap_blk2g;
+    dbuf<int64_t> cap_base_off, cap_len;
+    dbuf<uint8_t> cap_has_n;
+    uint64_t uid = vg_genomes_next_uid();       // this set among all sets the process ever made (an address comes back after a free)
+    uint64_t parent_uid = 0;                    // device-only: the set it was gathered from ...
+    std::vector<int32_t> parent_id;             // ... and, per genome, the id there
     int64_t padded_total() const { return base_off.empty() ? 0 : base_off.back(); }
     // L1 order (stable sort by length, descending), computed once: order[rank] = input id, rank[id]
     mutable std::vector<int32_t> len_order, len_rank;

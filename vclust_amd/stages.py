@@ -7,7 +7,7 @@ import os
 
 from . import _lib
 from ._lib import (CLUSTER_ALGORITHMS, DEREP_ALGORITHMS, DEREP_BATCH_GENOMES, FLOW_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions,
-                   DedupParams, DerepFileParams, DerepParams, DerepStats, LzParams, MclParams, MclStats, PrefilterParams, check)
+                   DedupParams, DerepFileParams, DerepParams, DerepStats, DerepUpdateStats, LzParams, MclParams, MclStats, PrefilterParams, check)
 
 DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
 
@@ -194,12 +194,20 @@ def derep_params(batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min
 
 def dereplicate(paths, out_path, is_multifasta, batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min_ident=0.7, lz=None,
                 algorithm='cd-hit', metric='tani', num_alns=0, representatives=False, out_table=None, columns=None, out_repr_fasta=None,
-                num_threads=1, verbosity=0, **mins):
+                num_threads=1, verbosity=0, db_paths=None, prior_path=None, prior_repr=False, **mins):
     """clusters.tsv of the genomes in `paths` by greedy clustering against representatives only (vg_dereplicate; DESIGN.md section
     13): the file that prefilter -> align with that filter -> cluster(algorithm='cd-hit') writes for the same options, for every
     batch_genomes.  out_table: also an ani.tsv of the rows that were computed (columns: default the standard format) and its
-    .ids.tsv; out_repr_fasta: the records of the representatives, verbatim (one multi-FASTA input only).  -> the counts as a dict."""
-    st = DerepStats()
+    .ids.tsv; out_repr_fasta: the records of the representatives, verbatim (one multi-FASTA input only).  db_paths and prior_path
+    (both or neither): the genomes of `paths` are new to the database db_paths, whose clusters -- the clusters.tsv prior_path of
+    an earlier run, prior_repr: with representative ids in its second column -- are kept as they are (vg_dereplicate_update): the
+    file that prefilter, align and cluster(prior_path=...) write with db_paths, with only the prior representatives ever compared.
+    -> the counts as a dict."""
+    if (db_paths is None) != (prior_path is None):
+        raise ValueError('db_paths and prior_path go together: the database is the genome set of the prior clustering')
+    if prior_path is None and prior_repr:
+        raise ValueError('prior_repr needs prior_path')
+    st, ust = DerepStats(), DerepUpdateStats()
     p = DerepFileParams()
     p.derep = derep_params(batch_genomes, k, kmers_fraction, min_kmers, min_ident, lz, algorithm, metric, num_alns, mins)
     p.representatives = int(bool(representatives))
@@ -210,5 +218,9 @@ def dereplicate(paths, out_path, is_multifasta, batch_genomes=None, k=25, kmers_
     p.out_repr_fasta_path = os.fsencode(str(out_repr_fasta)) if out_repr_fasta is not None else None
     p.num_threads, p.verbosity, p.is_multifasta = int(num_threads), int(verbosity), int(bool(is_multifasta))
     p.stats = C.pointer(st)
-    check(_lib.load().vg_dereplicate(_path_array(paths), len(paths), os.fsencode(str(out_path)), C.byref(p)))
-    return {name: getattr(st, name) for name, _ in DerepStats._fields_}
+    if db_paths is None:
+        check(_lib.load().vg_dereplicate(_path_array(paths), len(paths), os.fsencode(str(out_path)), C.byref(p)))
+        return {name: getattr(st, name) for name, _ in DerepStats._fields_}
+    check(_lib.load().vg_dereplicate_update(_path_array(db_paths), len(db_paths), _path_array(paths), len(paths), os.fsencode(str(prior_path)),
+                                            int(bool(prior_repr)), os.fsencode(str(out_path)), C.byref(p), C.byref(ust)))
+    return {name: getattr(x, name) for x in (st, ust) for name, _ in type(x)._fields_}
