@@ -3,7 +3,9 @@
 The library is the product: there is no Python or CPU fallback.  If the shared object is
 missing the import fails loudly and tells how to build it.
 """
+import collections
 import ctypes as C
+import os
 import pathlib
 
 PKG_DIR = pathlib.Path(__file__).resolve().parent
@@ -37,6 +39,14 @@ class LzParams(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('mal', 'msl', 'mrd', 'mqd', 'reg', 'aw', 'am', 'ar')]
 
 
+DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
+
+
+def lz_params(lz=None):
+    """vg_lz_params: DEFAULT_LZ, overridden by the entries of the dict `lz`."""
+    return LzParams(**{**DEFAULT_LZ, **(lz or {})})
+
+
 class LzFit(C.Structure):
     _fields_ = [('weak_seed_ratio', C.c_int), ('anchor_margin', C.c_int), ('seed_choice', C.c_int)]
 
@@ -45,6 +55,16 @@ class PrefilterParams(C.Structure):
     _fields_ = [('k', C.c_int), ('min_kmers', C.c_int), ('min_ident', C.c_double),
                 ('batch_size', C.c_int), ('kmers_fraction', C.c_double), ('max_seqs', C.c_int),
                 ('num_threads', C.c_int), ('verbosity', C.c_int), ('is_multifasta', C.c_int)]
+
+
+# LZ-ANI output columns and the three output formats (same sets as the reference, vclust.py:38-47)
+ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
+                'num_alns', 'len_ratio', 'qlen', 'rlen', 'nt_match', 'nt_mismatch']
+ALIGN_OUTFMT = {
+    'lite': ALIGN_FIELDS[:2] + ALIGN_FIELDS[4:11],
+    'standard': ALIGN_FIELDS[:11],
+    'complete': ALIGN_FIELDS[:],
+}
 
 
 class AlignParams(C.Structure):
@@ -117,6 +137,8 @@ HIERARCHY_ALGORITHMS = {**LINKAGE_ALGORITHMS, 'average': 5}
 UPDATE_ALGORITHMS = {'single': 0, 'cd-hit': 1, 'uclust': 2}
 # the flow algorithms: Markov clustering, with calls of its own (vg_cluster_mcl / vg_cluster_mcl_graph); always in the library
 FLOW_ALGORITHMS = {'mcl': 6}
+# every algorithm the library knows
+LIBRARY_ALGORITHMS = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
 # the algorithm of dereplicate (vg_dereplicate / vg_dereplicate_set): a genome is compared with representatives only, which is cd-hit
 DEREP_ALGORITHMS = {'cd-hit': 1}
 # genomes per batch of dereplicate ("Batch size")
@@ -152,6 +174,27 @@ class DedupContainedStats(C.Structure):
 class DedupRepeatStats(C.Structure):
     _fields_ = [('with_repeat', C.c_int64), ('repeat_symbols', C.c_int64), ('candidates', C.c_int64), ('equal', C.c_int64),
                 ('batches', C.c_int64)]
+
+
+# The modes of deduplicate, keyed by (circular, contained, terminal repeat given): the C entry for files and the one for sequences;
+# `extra`: the arguments that these two take beside the ones every mode has, from the terminal repeat; `n_arrays`: the int64 arrays
+# the sequence entry fills beside representative and strand (the offsets, the repeats); `more_stats`: its second stats struct.
+DedupMode = collections.namedtuple('DedupMode', 'files seqs extra n_arrays more_stats')
+DEDUP_MODES = {
+    (False, False, False): DedupMode('vg_deduplicate', 'vg_dedup_seqs', lambda tr: [], 0, None),
+    (True, False, False): DedupMode('vg_deduplicate_ex', 'vg_dedup_seqs_ex', lambda tr: [C.byref(DedupOptions(circular=1))], 1, None),
+    (True, False, True): DedupMode('vg_deduplicate_circular_tr', 'vg_dedup_seqs_circular_tr', lambda tr: [int(tr)], 2, DedupRepeatStats),
+    (False, True, False): DedupMode('vg_deduplicate_contained', 'vg_dedup_seqs_contained', lambda tr: [], 1, DedupContainedStats),
+}
+
+
+def dedup_mode(circular, contained, repeat_given, needs='circular'):
+    """The mode of deduplicate for these options, and its argument check; `needs`: how the caller spells the circular option."""
+    if circular and contained:
+        raise ValueError('circular and contained exclude each other')
+    if repeat_given and not circular:
+        raise ValueError(f'terminal_repeat needs {needs}')
+    return DEDUP_MODES[bool(circular), bool(contained), bool(repeat_given)]
 
 
 class KmerGeometry(C.Structure):
@@ -324,6 +367,30 @@ def load():
 def check(rc):
     if rc != 0:
         raise VclustGpuError(rc, load().vg_last_error().decode('utf-8', 'replace'))
+
+
+# ---------------------------------------------------------------- marshalling (numpy-free: an array is anything with .ctypes)
+def ptr(arr, ctype=None):
+    """A pointer to the memory of an array: to `ctype` elements, or void*."""
+    return arr.ctypes.data_as(C.POINTER(ctype) if ctype is not None else C.c_void_p)
+
+
+def path(p):
+    """A path as the bytes of a char* argument; None stays None (NULL)."""
+    return None if p is None else os.fsencode(str(p))
+
+
+def path_array(paths):
+    return (C.c_char_p * len(paths))(*[path(p) for p in paths])
+
+
+def string_array(strings):
+    return (C.c_char_p * len(strings))(*[str(s).encode() for s in strings])
+
+
+def as_dict(*structs):
+    """The fields of the structs, in order, as one dict."""
+    return {name: getattr(st, name) for st in structs for name, _ in st._fields_}
 
 
 def hip_copy(dst, src, nbytes, to_host):

@@ -5,27 +5,44 @@ Everything computational happens inside libvclust_gpu.so.
 """
 import ctypes as C
 import inspect
-import os
 
 import numpy as np
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterStat, ClusterStats, ClusterUpdateStats, DedupStats, DerepStats, DerepUpdateStats, KernelTime, LinkageStats, LzParams, MclParams, MclStats, PairCount, PairStat,
-                   PrefilterParams, Region, Task, check)
+from ._lib import (ALIGN_FIELDS, ALIGN_OUTFMT, CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, ClusterStat, ClusterStats,  # noqa: F401
+                   ClusterUpdateStats, DedupStats, DerepStats, DerepUpdateStats, KernelTime, LinkageStats, MclParams, MclStats, PairCount,
+                   PairStat, Region, Task, as_dict, check, lz_params, path, path_array, ptr)
+# the whole-stage calls (vclust_amd/stages.py: no numpy)
+from .stages import (DEFAULT_LZ, align, align_params, cluster, cluster_stats, deduplicate as deduplicate_files, derep_params, dereplicate,  # noqa: F401
+                     prefilter)
 
-ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
-                'num_alns', 'len_ratio', 'qlen', 'rlen', 'nt_match', 'nt_mismatch']
 
-PAIR_DTYPE = np.dtype([('a', '<u4'), ('b', '<u4'), ('shared', '<u4')])
-TASK_DTYPE = np.dtype([('q', '<u4'), ('r', '<u4')])
-STAT_DTYPE = np.dtype([('n_match', '<u4'), ('aln_len', '<u4'), ('n_regions', '<u4')])
-REGION_DTYPE = np.dtype([('task', '<u4'), ('qstart', '<i4'), ('qend', '<i4'), ('rstart', '<i4'),
-                         ('rend', '<i4'), ('n_match', '<i4')])
+def _dtype(ctype):
+    """numpy's dtype for a ctypes scalar or struct (the library's record structs have no padding, and neither has the dtype)."""
+    d = np.dtype(ctype)
+    return np.dtype(d.descr) if d.names else d
+
+
+PAIR_DTYPE, TASK_DTYPE, STAT_DTYPE, REGION_DTYPE, CLUSTER_STAT_DTYPE = (_dtype(t) for t in (PairCount, Task, PairStat, Region, ClusterStat))
 LINKAGE_DTYPE = np.dtype([('node_a', '<i8'), ('node_b', '<i8'), ('similarity', '<f8'), ('size', '<i8'), ('object_a', '<i4'),
                           ('object_b', '<i4')])
-CLUSTER_STAT_DTYPE = np.dtype([(name, '<u8' if t is C.c_uint64 else '<i8') for name, t in ClusterStat._fields_])
+AVERAGE_LINKAGE_DTYPE = np.dtype(LINKAGE_DTYPE.descr + [('sum', '<u8'), ('pairs', '<u8')])
 
-from .stages import DEFAULT_LZ  # noqa: E402
+
+def _input(x, ctype):
+    """x as a contiguous array of `ctype` elements -> (pointer, length); the pointer keeps the array alive."""
+    arr = np.ascontiguousarray(x, dtype=_dtype(ctype))
+    return ptr(arr, ctype), len(arr)
+
+
+def _filled(n, ctypes, call, guard=False):
+    """The frame of a call that fills one entry per object: a zeroed array of n entries for each of `ctypes` -- of one entry for
+    n = 0, so that the pointer is valid, and under `guard` for n >= 2^31, which the library refuses before it writes -- handed to
+    `call` as pointers -> the first n entries of each."""
+    size = 1 if guard and n >= 1 << 31 else max(n, 1)
+    arrays = [np.zeros(size, dtype=_dtype(t)) for t in ctypes]
+    call(*[ptr(a, t) for a, t in zip(arrays, ctypes)])
+    return [a[:n] for a in arrays]
 
 
 def version():
@@ -76,29 +93,22 @@ class GenomeSet:
 
     @classmethod
     def load(cls, paths, multisample, n_threads=1):
-        lib = _lib.load()
-        arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
         h = C.c_void_p()
-        check(lib.vg_genomes_load(arr, len(paths), int(bool(multisample)), int(n_threads), C.byref(h)))
+        check(_lib.load().vg_genomes_load(path_array(paths), len(paths), int(bool(multisample)), int(n_threads), C.byref(h)))
         return cls(h)
 
     @classmethod
     def load_db_new(cls, db_paths, new_paths, multisample, n_threads=1):
         """-> (set, n_db): the genomes of db_paths (ids 0 .. n_db - 1) followed by those of new_paths, as one set.  multisample:
         one multi-FASTA on each side; otherwise one genome per file.  A name on both sides is an error."""
-        lib = _lib.load()
-        db = (C.c_char_p * len(db_paths))(*[os.fsencode(str(p)) for p in db_paths])
-        new = (C.c_char_p * len(new_paths))(*[os.fsencode(str(p)) for p in new_paths])
-        h = C.c_void_p()
-        n_db = C.c_int()
-        check(lib.vg_genomes_load_db_new(db, len(db_paths), new, len(new_paths), int(bool(multisample)), int(n_threads), C.byref(h),
-                                         C.byref(n_db)))
+        h, n_db = C.c_void_p(), C.c_int()
+        check(_lib.load().vg_genomes_load_db_new(path_array(db_paths), len(db_paths), path_array(new_paths), len(new_paths),
+                                                 int(bool(multisample)), int(n_threads), C.byref(h), C.byref(n_db)))
         return cls(h), n_db.value
 
     @classmethod
     def from_codes(cls, codes, offsets, names=None):
         """codes: uint8 array (0..3 ACGT, >3 N); offsets: int64 array of n+1 entries."""
-        lib = _lib.load()
         codes = np.ascontiguousarray(codes, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         n = len(offsets) - 1
@@ -106,8 +116,7 @@ class GenomeSet:
         if names is not None:
             nm = (C.c_char_p * n)(*[s.encode() for s in names])
         h = C.c_void_p()
-        check(lib.vg_genomes_from_codes(codes.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
-                                        n, nm, C.byref(h)))
+        check(_lib.load().vg_genomes_from_codes(ptr(codes), ptr(offsets), n, nm, C.byref(h)))
         return cls(h)
 
     def close(self):
@@ -131,7 +140,7 @@ class GenomeSet:
     def lengths(self):
         out = np.zeros(len(self), dtype=np.int64)
         if len(self):
-            check(self._lib.vg_genomes_lengths(self._h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+            check(self._lib.vg_genomes_lengths(self._h, ptr(out, C.c_int64)))
         return out
 
     def names(self):
@@ -140,7 +149,7 @@ class GenomeSet:
     def codes(self, idx):
         """Bases of genome idx as held on the host (0..3 = ACGT, 4 = N)."""
         out = np.empty(int(self.lengths()[idx]), dtype=np.uint8)
-        _lib.check(_lib.load().vg_genomes_codes(self._h, int(idx), out.ctypes.data_as(C.c_void_p)))
+        check(self._lib.vg_genomes_codes(self._h, int(idx), ptr(out)))
         return out
 
     def to_device(self):
@@ -149,9 +158,8 @@ class GenomeSet:
     def subset(self, ids):
         """The genomes `ids` of this resident set, in that order, as a new set gathered on the device (vg_genomes_subset): no base
         travels from the host.  An id outside the set or listed twice, and a set that is not resident, are errors."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
         h = C.c_void_p()
-        check(self._lib.vg_genomes_subset(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), C.byref(h)))
+        check(self._lib.vg_genomes_subset(self._h, *_input(ids, C.c_int32), C.byref(h)))
         return GenomeSet(h)
 
     def extend(self, parent, ids):
@@ -159,8 +167,7 @@ class GenomeSet:
         set must be a subset() of that very parent (it may be empty).  Only the appended genomes are written; the genomes already
         here are neither read nor copied, unless the buffers have to grow (reserve() avoids that).  An id outside the parent, listed
         twice or in this set already is an error."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
-        check(self._lib.vg_genomes_extend(self._h, parent._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids)))
+        check(self._lib.vg_genomes_extend(self._h, parent._h, *_input(ids, C.c_int32)))
 
     def truncate(self, n):
         """Drop every genome from n on, in place (vg_genomes_truncate): what is left is, to every kernel, the subset() of the kept
@@ -183,59 +190,50 @@ class GenomeSet:
         that clustering (vg_dereplicate_update_set): the result of cluster_update_graph('cd-hit') with that prior, with only the
         prior representatives ever compared; n_db is the number of database genomes of a load_db_new set.  The stats then also
         hold prior_objects, prior_representatives and joined_prior_cluster."""
-        from .stages import derep_params
         prm = derep_params(batch_genomes, k, kmers_fraction, min_kmers, min_ident, lz, algorithm, metric, num_alns, mins)
         n = len(self)
-        label, rep = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        update = prior_rep is not None or bool(n_db)
         st, ust = DerepStats(), DerepUpdateStats()
-        P = C.POINTER
-        tp, sp, nt = P(Task)(), P(PairStat)(), C.c_int64()
-        rows = (C.byref(tp) if want_rows else None, C.byref(sp) if want_rows else None, C.byref(nt) if want_rows else None)
-        if prior_rep is None and not n_db:
-            check(self._lib.vg_dereplicate_set(self._h, C.byref(prm), label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), *rows,
-                                               C.byref(st)))
-        else:
-            prior = np.full(n, -1, dtype=np.int32) if prior_rep is None else np.ascontiguousarray(prior_rep, dtype=np.int32)
-            if len(prior) != n:
+        tp, sp, nt = C.POINTER(Task)(), C.POINTER(PairStat)(), C.c_int64()
+        rows = [C.byref(x) if want_rows else None for x in (tp, sp, nt)]
+        if update:
+            prior, n_prior = _input(np.full(n, -1) if prior_rep is None else prior_rep, C.c_int32)
+            if n_prior != n:
                 raise ValueError('prior_rep must have one entry per genome')
-            check(self._lib.vg_dereplicate_update_set(self._h, int(n_db), C.byref(prm), prior.ctypes.data_as(P(C.c_int32)),
-                                                      label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), *rows, C.byref(st),
-                                                      C.byref(ust)))
-        stats = {name: getattr(st, name) for name, _ in DerepStats._fields_}
-        if prior_rep is not None or n_db:
-            stats.update({name: getattr(ust, name) for name, _ in DerepUpdateStats._fields_})
+
+        def call(lp, rp):
+            if update:
+                check(self._lib.vg_dereplicate_update_set(self._h, int(n_db), C.byref(prm), prior, lp, rp, *rows, C.byref(st), C.byref(ust)))
+            else:
+                check(self._lib.vg_dereplicate_set(self._h, C.byref(prm), lp, rp, *rows, C.byref(st)))
+        label, rep = _filled(n, (C.c_int32, C.c_int32), call)
+        stats = as_dict(st, ust) if update else as_dict(st)
         if not want_rows:
-            return label[:n], rep[:n], stats
-        return label[:n], rep[:n], stats, (_take(tp, nt.value, TASK_DTYPE), _take(sp, nt.value, STAT_DTYPE))
+            return label, rep, stats
+        return label, rep, stats, (_take(tp, nt.value, TASK_DTYPE), _take(sp, nt.value, STAT_DTYPE))
 
     # ---------------------------------------------------------------- prefilter
     def kmer_shared(self, k=25, fraction=1.0, shard=0, n_shards=1, min_shared=1):
         """-> (set_sizes int64[n], pairs structured array a>b with shared counts)."""
-        n = len(self)
-        sizes = np.zeros(max(n, 1), dtype=np.int64)
-        pp = C.POINTER(PairCount)()
-        npairs = C.c_int64()
-        check(self._lib.vg_kmer_shared(self._h, k, float(fraction), shard, n_shards, int(min_shared),
-                                       sizes.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pp), C.byref(npairs)))
-        return sizes[:n], _take(pp, npairs.value, PAIR_DTYPE)
+        pp, npairs = C.POINTER(PairCount)(), C.c_int64()
+        sizes, = _filled(len(self), (C.c_int64,), lambda sp: check(self._lib.vg_kmer_shared(
+            self._h, k, float(fraction), shard, n_shards, int(min_shared), sp, C.byref(pp), C.byref(npairs))))
+        return sizes, _take(pp, npairs.value, PAIR_DTYPE)
 
     def kmer_shared_new(self, n_db, k=25, fraction=1.0, min_shared=1):
         """New genomes (ids n_db .. n - 1) against a database (ids 0 .. n_db - 1): kmer_shared restricted to the pairs a > b with
         a >= n_db.  set_sizes are -1 for the database genomes that no returned pair names."""
-        n = len(self)
-        sizes = np.zeros(max(n, 1), dtype=np.int64)
-        pp = C.POINTER(PairCount)()
-        npairs = C.c_int64()
-        check(self._lib.vg_kmer_shared_new(self._h, int(n_db), k, float(fraction), int(min_shared),
-                                           sizes.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pp), C.byref(npairs)))
-        return sizes[:n], _take(pp, npairs.value, PAIR_DTYPE)
+        pp, npairs = C.POINTER(PairCount)(), C.c_int64()
+        sizes, = _filled(len(self), (C.c_int64,), lambda sp: check(self._lib.vg_kmer_shared_new(
+            self._h, int(n_db), k, float(fraction), int(min_shared), sp, C.byref(pp), C.byref(npairs))))
+        return sizes, _take(pp, npairs.value, PAIR_DTYPE)
 
     def kmer_geometry(self, k=25, fraction=1.0, shard=0, n_shards=1):
         """The index geometry of the first pass of kmer_shared with these arguments (vg_kmer_geometry; host only) -> dict of the
         fields of vg_kmer_geometry_info.  Only accepted, P and n_passes mean anything unless accepted == 1."""
         info = _lib.KmerGeometry()
         check(self._lib.vg_kmer_geometry(self._h, int(k), float(fraction), int(shard), int(n_shards), C.byref(info)))
-        return {name: int(getattr(info, name)) for name, _ in info._fields_}
+        return as_dict(info)
 
     def kmer_set(self, idx, k=25, fraction=1.0):
         p = C.POINTER(C.c_uint64)()
@@ -245,60 +243,42 @@ class GenomeSet:
 
     def filter_pairs(self, set_sizes, pairs, k=25, min_kmers=20, min_ident=0.7):
         """The pairs write_fltr would print (thresholds on shared count and ani-shorter), in memory."""
-        sizes = np.ascontiguousarray(set_sizes, dtype=np.int64)
-        pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
-        out = C.POINTER(PairCount)(); n = C.c_int64()
-        check(self._lib.vg_filter_pairs(int(k), int(min_kmers), float(min_ident), sizes.ctypes.data_as(C.POINTER(C.c_int64)), len(sizes),
-                                        pairs.ctypes.data_as(C.POINTER(PairCount)), len(pairs), C.byref(out), C.byref(n)))
+        out, n = C.POINTER(PairCount)(), C.c_int64()
+        check(self._lib.vg_filter_pairs(int(k), int(min_kmers), float(min_ident), *_input(set_sizes, C.c_int64), *_input(pairs, PairCount),
+                                        C.byref(out), C.byref(n)))
         return _take(out, n.value, PAIR_DTYPE)
 
     def write_fltr(self, out_path, set_sizes, pairs, k=25, fraction=1.0, min_kmers=20, min_ident=0.7, max_seqs=0):
-        sizes = np.ascontiguousarray(set_sizes, dtype=np.int64)
-        pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
         check(self._lib.vg_write_fltr(self._h, k, float(fraction), int(min_kmers), float(min_ident), int(max_seqs),
-                                      sizes.ctypes.data_as(C.POINTER(C.c_int64)),
-                                      pairs.ctypes.data_as(C.POINTER(PairCount)), len(pairs),
-                                      os.fsencode(str(out_path))))
+                                      _input(set_sizes, C.c_int64)[0], *_input(pairs, PairCount), path(out_path)))
 
     # ---------------------------------------------------------------- align
     def align_order(self):
-        out = np.zeros(max(len(self), 1), dtype=np.int32)
-        check(self._lib.vg_align_order(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
-        return out[:len(self)]
+        order, = _filled(len(self), (C.c_int32,), lambda p: check(self._lib.vg_align_order(self._h, p)))
+        return order
 
     def read_filter(self, path=None, threshold=0.0):
         pp = C.POINTER(PairCount)()
         n = C.c_int64()
-        check(self._lib.vg_read_filter(self._h, os.fsencode(str(path)) if path else None, float(threshold),
-                                       C.byref(pp), C.byref(n)))
+        check(self._lib.vg_read_filter(self._h, _lib.path(path or None), float(threshold), C.byref(pp), C.byref(n)))
         return _take(pp, n.value, PAIR_DTYPE)
 
     def align_tasks(self, pairs):
-        pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
-        tp = C.POINTER(Task)()
-        n = C.c_int64()
-        check(self._lib.vg_align_tasks(self._h, pairs.ctypes.data_as(C.POINTER(PairCount)), len(pairs),
-                                       C.byref(tp), C.byref(n)))
+        tp, n = C.POINTER(Task)(), C.c_int64()
+        check(self._lib.vg_align_tasks(self._h, *_input(pairs, PairCount), C.byref(tp), C.byref(n)))
         return _take(tp, n.value, TASK_DTYPE)
 
     def lz_prepare(self, pairs, lz=None):
         """Optional head start of lz_align: the indexes of the pairs' genomes are queued on the device now (they are built
         while align_tasks runs on the host); lz_align takes them over when its tasks name the same references."""
-        pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
-        prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
-        check(self._lib.vg_lz_prepare(self._h, pairs.ctypes.data_as(C.POINTER(PairCount)), len(pairs), C.byref(prm)))
+        check(self._lib.vg_lz_prepare(self._h, *_input(pairs, PairCount), C.byref(lz_params(lz))))
 
     def lz_align(self, tasks, lz=None, want_regions=False):
         """LZ parse of the ordered pairs -> stats (and regions)."""
-        tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
-        prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
-        stats = np.zeros(max(len(tasks), 1), dtype=STAT_DTYPE)
-        rp = C.POINTER(Region)()
-        nr = C.c_int64()
-        check(self._lib.vg_lz_align(self._h, tasks.ctypes.data_as(C.POINTER(Task)), len(tasks), C.byref(prm),
-                                    stats.ctypes.data_as(C.POINTER(PairStat)),
-                                    C.byref(rp) if want_regions else None, C.byref(nr)))
-        stats = stats[:len(tasks)]
+        tp, n = _input(tasks, Task)
+        rp, nr = C.POINTER(Region)(), C.c_int64()
+        stats, = _filled(n, (PairStat,), lambda sp: check(self._lib.vg_lz_align(
+            self._h, tp, n, C.byref(lz_params(lz)), sp, C.byref(rp) if want_regions else None, C.byref(nr))))
         if want_regions:
             return stats, _take(rp, nr.value, REGION_DTYPE)
         return stats
@@ -306,7 +286,7 @@ class GenomeSet:
     def lz_index_dump(self, idx, lz=None):
         """The index lz_align would build for genome idx (parity tests) -> dict(bucket_end uint32[4^msl], entries uint32[n],
         pos_bits, tag_bits, path: 0..5 register build of 24..4 trips, 6 mid, 7 lds, 8 global)."""
-        prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+        prm = lz_params(lz)
         tb, en = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
         n, pb, tg, path = C.c_int64(), C.c_int(), C.c_int(), C.c_int()
         check(self._lib.vg_lz_index_dump(self._h, int(idx), C.byref(prm), C.byref(tb), C.byref(en), C.byref(n),
@@ -317,29 +297,12 @@ class GenomeSet:
 
     def write_ani(self, out_path, tasks, stats, regions=None, columns=None, out_aln=None, lz=None,
                   out_filters=None, num_threads=0):
-        tasks = np.ascontiguousarray(tasks, dtype=TASK_DTYPE)
-        stats = np.ascontiguousarray(stats, dtype=STAT_DTYPE)
-        columns = list(columns or ALIGN_FIELDS[:11])
-        cols = (C.c_char_p * len(columns))(*[c.encode() for c in columns])
-        p = AlignParams()
-        p.lz = LzParams(**{**DEFAULT_LZ, **(lz or {})})
-        for name, val in (out_filters or {}).items():
-            setattr(p, f'out_{name}', float(val))
-        p.out_aln_path = os.fsencode(str(out_aln)) if out_aln else None
-        p.out_columns = cols
-        p.n_out_columns = len(columns)
-        p.num_threads = int(num_threads)
-        reg_ptr, nreg = None, 0
-        if regions is not None:
-            regions = np.ascontiguousarray(regions, dtype=REGION_DTYPE)
-            reg_ptr, nreg = regions.ctypes.data_as(C.POINTER(Region)), len(regions)
-        check(self._lib.vg_write_ani(self._h, tasks.ctypes.data_as(C.POINTER(Task)),
-                                     stats.ctypes.data_as(C.POINTER(PairStat)), len(tasks), reg_ptr, nreg,
-                                     os.fsencode(str(out_path)), C.byref(p)))
-
-
-# ---------------------------------------------------------------- whole-stage calls (vclust_amd/stages.py: no numpy)
-from .stages import align, align_params, cluster, cluster_stats, deduplicate as deduplicate_files, dereplicate, prefilter  # noqa: E402,F401
+        tp, n = _input(tasks, Task)
+        # (is_multifasta=False: this call has always left that field of vg_align_params 0)
+        p = align_params(list(columns or ALIGN_OUTFMT['standard']), out_aln=out_aln, lz=lz, out_filters=out_filters, num_threads=int(num_threads),
+                         is_multifasta=False)
+        reg_ptr, nreg = _input(regions, Region) if regions is not None else (None, 0)
+        check(self._lib.vg_write_ani(self._h, tp, _input(stats, PairStat)[0], n, reg_ptr, nreg, path(out_path), C.byref(p)))
 
 
 def cluster_graph(n_objects, q, r, w, algorithm='single'):
@@ -350,15 +313,10 @@ def cluster_graph(n_objects, q, r, w, algorithm='single'):
     known = {**CLUSTER_ALGORITHMS, **LINKAGE_ALGORITHMS}
     if algorithm not in known:
         raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
-    label = np.zeros(max(n, 1), dtype=np.int32)
-    rep = np.zeros(max(n, 1), dtype=np.int32)
-    st = ClusterStats()
-    P = C.POINTER
-    check(_lib.load().vg_cluster_graph(n, *rows, known[algorithm], label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
-                                       C.byref(st)))
-    return label[:n], rep[:n], dict(rounds=st.rounds, sweep_objects=st.sweep_objects, n_edges=st.n_edges)
+    rows, n, st = _rows(q, r, w), int(n_objects), ClusterStats()
+    label, rep = _filled(n, (C.c_int32, C.c_int32), lambda lp, rp: check(_lib.load().vg_cluster_graph(
+        n, *rows, known[algorithm], lp, rp, C.byref(st))))
+    return label, rep, as_dict(st)
 
 
 def cluster_mcl_graph(n_objects, q, r, w, inflation=2.0, prune=1e-4, max_row=128, chaos_eps=1e-3, max_iterations=100, matrix=False):
@@ -368,22 +326,17 @@ def cluster_mcl_graph(n_objects, q, r, w, inflation=2.0, prune=1e-4, max_row=128
     chaos of an iteration is <= chaos_eps, or after max_iterations (stats['converged'] == 0: there is a result all the same).
     -> (label int32[n], representative int32[n], stats dict), and with matrix=True also (offsets int64[n + 1], columns int32[nnz],
     values uint32[nnz]): the last matrix as CSR, columns ascending per row -- with max_iterations=t the iterate after t steps."""
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
-    size = max(n, 1) if n < 1 << 31 else 1
-    label, rep = np.zeros(size, dtype=np.int32), np.zeros(size, dtype=np.int32)
+    rows, n, st = _rows(q, r, w), int(n_objects), MclStats()
     prm = MclParams(float(inflation), float(prune), float(chaos_eps), int(max_row), int(max_iterations))
-    st = MclStats()
-    P = C.POINTER
-    off, col, val = P(C.c_int64)(), P(C.c_int32)(), P(C.c_uint32)()
-    check(_lib.load().vg_cluster_mcl_graph(n, *rows, C.byref(prm), label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)),
-                                           C.byref(off) if matrix else None, C.byref(col) if matrix else None,
-                                           C.byref(val) if matrix else None, C.byref(st)))
-    stats = {name: getattr(st, name) for name, _ in MclStats._fields_}
+    off, col, val = C.POINTER(C.c_int64)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_uint32)()
+    csr = [C.byref(x) if matrix else None for x in (off, col, val)]
+    label, rep = _filled(n, (C.c_int32, C.c_int32), lambda lp, rp: check(_lib.load().vg_cluster_mcl_graph(
+        n, *rows, C.byref(prm), lp, rp, *csr, C.byref(st))), guard=True)
+    stats = as_dict(st)
     if not matrix:
-        return label[:n], rep[:n], stats
+        return label, rep, stats
     nnz = int(stats['nnz'])
-    return label[:n], rep[:n], stats, (_take(off, n + 1, np.dtype('<i8')), _take(col, nnz, np.dtype('<i4')), _take(val, nnz, np.dtype('<u4')))
+    return label, rep, stats, (_take(off, n + 1, np.dtype('<i8')), _take(col, nnz, np.dtype('<i4')), _take(val, nnz, np.dtype('<u4')))
 
 
 def cluster_mcl_set_table_slots(slots=0):
@@ -402,18 +355,13 @@ def cluster_update_graph(n_objects, q, r, w, prior_rep, algorithm='single'):
     representative (single: the earliest member)."""
     if algorithm not in UPDATE_ALGORITHMS:
         raise ValueError(f'algorithm {algorithm!r} cannot update a prior clustering (choices: {", ".join(UPDATE_ALGORITHMS)})')
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
-    prior = np.ascontiguousarray(prior_rep, dtype=np.int32)
-    if n < 1 << 31 and len(prior) != n:
+    rows, n, st = _rows(q, r, w), int(n_objects), ClusterUpdateStats()
+    prior, n_prior = _input(prior_rep, C.c_int32)
+    if n < 1 << 31 and n_prior != n:
         raise ValueError('prior_rep must have one entry per object')
-    label = np.zeros(max(n, 1) if n < 1 << 31 else 1, dtype=np.int32)
-    rep = np.zeros_like(label)
-    st = ClusterUpdateStats()
-    P = C.POINTER
-    check(_lib.load().vg_cluster_update_graph(n, *rows, UPDATE_ALGORITHMS[algorithm], prior.ctypes.data_as(P(C.c_int32)),
-                                              label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
-    return label[:n], rep[:n], {name: getattr(st, name) for name, _ in ClusterUpdateStats._fields_}
+    label, rep = _filled(n, (C.c_int32, C.c_int32), lambda lp, rp: check(_lib.load().vg_cluster_update_graph(
+        n, *rows, UPDATE_ALGORITHMS[algorithm], prior, lp, rp, C.byref(st))), guard=True)
+    return label, rep, as_dict(st)
 
 
 def cluster_update(ani_path, ids_path, prior_path, out_path, algorithm='single', prior_repr=False, **options):
@@ -427,8 +375,7 @@ def cluster_stats_graph(n_objects, q, r, w, label, n_clusters=None):
     """The cluster report of the labelling label[i] in [0, n_clusters) on the graph of cluster_graph (vg_cluster_stats_graph; DESIGN.md
     section 9, "Cluster report"): weights in [0, 1], taken as u = round(w * 2^32).  n_clusters: default max(label) + 1.  ->
     (records CLUSTER_STAT_DTYPE[n_clusters], own_max uint64[n], other_max uint64[n], other int32[n]); every figure is an integer."""
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
+    rows, n = _rows(q, r, w), int(n_objects)
     label = np.ascontiguousarray(label, dtype=np.int32)
     if n < 1 << 31 and len(label) != n:
         raise ValueError('label must have one entry per object')
@@ -436,45 +383,35 @@ def cluster_stats_graph(n_objects, q, r, w, label, n_clusters=None):
         n_clusters = int(label.max()) + 1 if len(label) else 0
     k = int(n_clusters)
     out = np.zeros(max(k, 1) if 0 <= k < 1 << 31 else 1, dtype=CLUSTER_STAT_DTYPE)
-    size = max(n, 1) if n < 1 << 31 else 1
-    own, oth, lab = np.zeros(size, dtype=np.uint64), np.zeros(size, dtype=np.uint64), np.zeros(size, dtype=np.int32)
-    P = C.POINTER
-    check(_lib.load().vg_cluster_stats_graph(n, *rows, label.ctypes.data_as(P(C.c_int32)), k, out.ctypes.data_as(P(ClusterStat)),
-                                             own.ctypes.data_as(P(C.c_uint64)), oth.ctypes.data_as(P(C.c_uint64)), lab.ctypes.data_as(P(C.c_int32))))
-    return out[:k], own[:n], oth[:n], lab[:n]
+    own, oth, lab = _filled(n, (C.c_uint64, C.c_uint64, C.c_int32), lambda *per_object: check(_lib.load().vg_cluster_stats_graph(
+        n, *rows, ptr(label, C.c_int32), k, ptr(out, ClusterStat), *per_object)), guard=True)
+    return out[:k], own, oth, lab
 
 
 def _rows(q, r, w):
-    q = np.ascontiguousarray(q, dtype=np.uint32)
-    r = np.ascontiguousarray(r, dtype=np.uint32)
-    w = np.ascontiguousarray(w, dtype=np.float64)
-    if not len(q) == len(r) == len(w):
+    """The rows of a graph as the array-level calls take them -> (q pointer, r pointer, w pointer, number of rows)."""
+    (q, n), (r, nr), (w, nw) = _input(q, C.c_uint32), _input(r, C.c_uint32), _input(w, C.c_double)
+    if not n == nr == nw:
         raise ValueError('q, r and w must have the same length')
-    P = C.POINTER
-    return q, r, w, (q.ctypes.data_as(P(C.c_uint32)), r.ctypes.data_as(P(C.c_uint32)), w.ctypes.data_as(P(C.c_double)), len(q))
+    return q, r, w, n
 
 
 def _linkage_table(fn, n_objects, q, r, w, floor=None):
     """-> (table, stats) of the array-level merge-table call `fn`.  With a floor, `fn` is the average-linkage entry: it takes the
     floor after the rows and returns `sum` and `pairs` after the similarity, in an AVERAGE_LINKAGE_DTYPE table."""
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
+    rows, n = _rows(q, r, w), int(n_objects)
     cap = max(n - 1, 1) if n < 1 << 31 else 1          # (2^31 objects or more: the library refuses before it writes)
-    oa, ob = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
-    wt = np.zeros(cap, dtype=np.float64)
-    exact = [] if floor is None else [np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)]       # sum, pairs
-    na, nb, sz = (np.zeros(cap, dtype=np.int64) for _ in range(3))
-    nm = C.c_int64(0)
-    st = LinkageStats()
-    P = C.POINTER
-    check(getattr(_lib.load(), fn)(n, *rows, *([] if floor is None else [float(floor)]), oa.ctypes.data_as(P(C.c_int32)),
-                                   ob.ctypes.data_as(P(C.c_int32)), wt.ctypes.data_as(P(C.c_double)),
-                                   *(x.ctypes.data_as(P(C.c_uint64)) for x in exact), na.ctypes.data_as(P(C.c_int64)),
-                                   nb.ctypes.data_as(P(C.c_int64)), sz.ctypes.data_as(P(C.c_int64)), C.byref(nm), C.byref(st)))
+    # object_a, object_b, similarity, (sum, pairs,) node_a, node_b, size: one entry per merge, in the order of the C arguments
+    ctypes = (C.c_int32, C.c_int32, C.c_double) + (() if floor is None else (C.c_uint64, C.c_uint64)) + (C.c_int64,) * 3
+    arrays = [np.zeros(cap, dtype=t) for t in ctypes]
+    nm, st = C.c_int64(0), LinkageStats()
+    check(getattr(_lib.load(), fn)(n, *rows, *([] if floor is None else [float(floor)]), *[ptr(a, t) for a, t in zip(arrays, ctypes)],
+                                   C.byref(nm), C.byref(st)))
+    oa, ob, wt, *exact, na, nb, sz = arrays
     table = np.zeros(nm.value, dtype=LINKAGE_DTYPE if floor is None else AVERAGE_LINKAGE_DTYPE)
     for name, arr in zip(table.dtype.names, (na, nb, wt, sz, oa, ob, *exact)):
         table[name] = arr[:nm.value]
-    return table, dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+    return table, as_dict(st)
 
 
 def cluster_linkage(n_objects, q, r, w):
@@ -499,9 +436,6 @@ def cluster_complete_levels_graph(n_objects, q, r, w, levels):
     of similarity >= t and equals cluster_graph(rows with w >= t, 'complete'); every cluster of it is a clique of those rows and
     lies inside one cluster of cluster_levels at t.  -> as cluster_levels."""
     return _levels('vg_cluster_complete_levels_graph', n_objects, q, r, w, levels)
-
-
-AVERAGE_LINKAGE_DTYPE = np.dtype(LINKAGE_DTYPE.descr + [('sum', '<u8'), ('pairs', '<u8')])
 
 
 def cluster_average_linkage_graph(n_objects, q, r, w, floor=0.0):
@@ -529,15 +463,12 @@ def cluster_average_similarity(s, p):
 def cluster_average_order_selftest(s, size_c, size_d, c, d, on_device=False):
     """Test entry (vg_cluster_average_order_selftest): the shared comparator of average linkage over neighbouring entries ->
     int8[n - 1] of -1 / 0 / 1, entry i against entry i + 1 (smaller key = larger s / (size_c * size_d), then smaller (c, d))."""
-    s = np.ascontiguousarray(s, dtype=np.uint64)
-    arrs = [np.ascontiguousarray(x, dtype=np.uint32) for x in (size_c, size_d, c, d)]
-    if any(len(x) != len(s) for x in arrs):
+    (s, n), arrs = _input(s, C.c_uint64), [_input(x, C.c_uint32) for x in (size_c, size_d, c, d)]
+    if any(nx != n for _, nx in arrs):
         raise ValueError('the five arrays must have the same length')
-    out = np.zeros(max(len(s) - 1, 1), dtype=np.int8)
-    P = C.POINTER
-    check(_lib.load().vg_cluster_average_order_selftest(s.ctypes.data_as(P(C.c_uint64)), *[x.ctypes.data_as(P(C.c_uint32)) for x in arrs],
-                                                        len(s), int(bool(on_device)), out.ctypes.data_as(P(C.c_int8))))
-    return out[:max(len(s) - 1, 0)]
+    out, = _filled(n - 1, (C.c_int8,), lambda op: check(_lib.load().vg_cluster_average_order_selftest(
+        s, *[x for x, _ in arrs], n, int(bool(on_device)), op)))
+    return out
 
 
 def cluster_levels(n_objects, q, r, w, levels):
@@ -549,17 +480,15 @@ def cluster_levels(n_objects, q, r, w, levels):
 
 def _levels(fn, n_objects, q, r, w, levels, floor=None):
     """-> (label, representative, stats) of the array-level cuts call `fn`; with a floor, of the average-linkage entry"""
-    q, r, w, rows = _rows(q, r, w)
-    n = int(n_objects)
-    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    rows, n = _rows(q, r, w), int(n_objects)
+    lv, n_levels = _input(np.reshape(levels, -1), C.c_double)
     width = n if 0 < n < 1 << 31 else 1                # (the library's row stride is n; it writes nothing otherwise)
-    label = np.zeros((len(lv), width), dtype=np.int32)
-    rep = np.zeros((len(lv), width), dtype=np.int32)
+    label = np.zeros((n_levels, width), dtype=np.int32)
+    rep = np.zeros((n_levels, width), dtype=np.int32)
     st = LinkageStats()
-    P = C.POINTER
-    check(getattr(_lib.load(), fn)(n, *rows, *([] if floor is None else [float(floor)]), lv.ctypes.data_as(P(C.c_double)), len(lv),
-                                   label.ctypes.data_as(P(C.c_int32)), rep.ctypes.data_as(P(C.c_int32)), C.byref(st)))
-    return label[:, :n], rep[:, :n], dict(rounds=st.rounds, n_edges=st.n_edges, n_merges=st.n_merges)
+    check(getattr(_lib.load(), fn)(n, *rows, *([] if floor is None else [float(floor)]), lv, n_levels, ptr(label, C.c_int32), ptr(rep, C.c_int32),
+                                   C.byref(st)))
+    return label[:, :n], rep[:, :n], as_dict(st)
 
 
 def _seq_buffer(seqs):
@@ -576,11 +505,9 @@ def terminal_repeats(seqs, min_repeat):
     """The terminal repeat of every sequence (vg_dedup_terminal_repeats) -> int64[n]: the largest t with
     min_repeat <= t <= len // 2 whose first t symbols equal its last t symbols (literally, case ignored), 0 without one."""
     ascii, offsets, n = _seq_buffer(seqs)
-    repeat = np.zeros(max(n, 1), dtype=np.int64)
-    P = C.POINTER
-    check(_lib.load().vg_dedup_terminal_repeats(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, int(min_repeat),
-                                                repeat.ctypes.data_as(P(C.c_int64))))
-    return repeat[:n]
+    repeat, = _filled(n, (C.c_int64,), lambda rp: check(_lib.load().vg_dedup_terminal_repeats(
+        ascii, ptr(offsets, C.c_int64), n, int(min_repeat), rp)))
+    return repeat
 
 
 def deduplicate(seqs, circular=False, contained=False, **options):
@@ -603,44 +530,16 @@ def deduplicate(seqs, circular=False, contained=False, **options):
     if unknown:
         raise TypeError(f'deduplicate() got an unexpected keyword argument {sorted(unknown)[0]!r}')
     terminal_repeat = options.get('terminal_repeat')
-    if circular and contained:
-        raise ValueError('circular and contained exclude each other')
-    if terminal_repeat is not None and not circular:
-        raise ValueError('terminal_repeat needs circular=True')
+    mode = _lib.dedup_mode(circular, contained, terminal_repeat is not None, needs='circular=True')
     ascii, offsets, n = _seq_buffer(seqs)
-    rep = np.zeros(max(n, 1), dtype=np.int32)
-    strand = np.zeros(max(n, 1), dtype=np.int8)
-    st = DedupStats()
-    P = C.POINTER
-    if contained:
-        off = np.zeros(max(n, 1), dtype=np.int64)
-        cst = _lib.DedupContainedStats()
-        check(_lib.load().vg_dedup_seqs_contained(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, rep.ctypes.data_as(P(C.c_int32)),
-                                                  strand.ctypes.data_as(P(C.c_int8)), off.ctypes.data_as(P(C.c_int64)), C.byref(st), C.byref(cst)))
-        stats = {k: getattr(st, k) for k, _ in DedupStats._fields_}
-        stats.update({k: getattr(cst, k) for k, _ in _lib.DedupContainedStats._fields_})
-        return rep[:n], strand[:n], off[:n], stats
-    if circular and terminal_repeat is not None:
-        off = np.zeros(max(n, 1), dtype=np.int64)
-        repeat = np.zeros(max(n, 1), dtype=np.int64)
-        rst = _lib.DedupRepeatStats()
-        check(_lib.load().vg_dedup_seqs_circular_tr(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, int(terminal_repeat),
-                                                    rep.ctypes.data_as(P(C.c_int32)), strand.ctypes.data_as(P(C.c_int8)),
-                                                    off.ctypes.data_as(P(C.c_int64)), repeat.ctypes.data_as(P(C.c_int64)), C.byref(st),
-                                                    C.byref(rst)))
-        stats = {k: getattr(st, k) for k, _ in DedupStats._fields_}
-        stats.update({k: getattr(rst, k) for k, _ in _lib.DedupRepeatStats._fields_})
-        stats['repeat'] = repeat[:n]
-        return rep[:n], strand[:n], off[:n], stats
-    if circular:
-        off = np.zeros(max(n, 1), dtype=np.int64)
-        opt = _lib.DedupOptions(circular=1)
-        check(_lib.load().vg_dedup_seqs_ex(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, C.byref(opt), rep.ctypes.data_as(P(C.c_int32)),
-                                           strand.ctypes.data_as(P(C.c_int8)), off.ctypes.data_as(P(C.c_int64)), C.byref(st)))
-        return rep[:n], strand[:n], off[:n], {k: getattr(st, k) for k, _ in DedupStats._fields_}
-    check(_lib.load().vg_dedup_seqs(ascii, offsets.ctypes.data_as(P(C.c_int64)), n, rep.ctypes.data_as(P(C.c_int32)),
-                                    strand.ctypes.data_as(P(C.c_int8)), C.byref(st)))
-    return rep[:n], strand[:n], {k: getattr(st, k) for k, _ in DedupStats._fields_}
+    st, more = DedupStats(), [mode.more_stats()] if mode.more_stats else []
+    # representative, strand, and the mode's offsets and repeats
+    arrays = _filled(n, (C.c_int32, C.c_int8) + (C.c_int64,) * mode.n_arrays, lambda *per_sequence: check(getattr(_lib.load(), mode.seqs)(
+        ascii, ptr(offsets, C.c_int64), n, *mode.extra(terminal_repeat), *per_sequence, C.byref(st), *map(C.byref, more))))
+    stats = as_dict(st, *more)
+    if mode.n_arrays == 2:
+        stats['repeat'] = arrays.pop()
+    return (*arrays, stats)
 
 
 # The introspected signature stays the three parameters of the plain, circular and contained modes, which
@@ -692,7 +591,7 @@ def kmer_geometry_at(padded_positions, k=25):
     (vg_kmer_geometry_at)."""
     info = _lib.KmerGeometry()
     check(_lib.load().vg_kmer_geometry_at(int(padded_positions), int(k), C.byref(info)))
-    return {name: int(getattr(info, name)) for name, _ in info._fields_}
+    return as_dict(info)
 
 
 def rowptr_inline_lo(entries, n_genomes):

@@ -27,6 +27,10 @@ import pathlib
 import subprocess
 import sys
 
+from . import stages
+from ._lib import ALIGN_FIELDS, ALIGN_OUTFMT, CLUSTER_ALGORITHMS, DEFAULT_LZ, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS  # noqa: F401
+from .stages import CLUSTER_FILTERS, dist_env
+
 __version__ = '1.3.1'
 
 DEFAULT_THREAD_COUNT = min(multiprocessing.cpu_count(), 64)
@@ -35,16 +39,6 @@ SCRIPT_DIR = pathlib.Path(__file__).resolve().parent.parent
 BIN_DIR = SCRIPT_DIR / 'bin'
 BIN_CLUSTY = BIN_DIR / 'clusty'
 BIN_MFASTA = BIN_DIR / 'mfasta-tool'
-
-# LZ-ANI output columns and the three output formats (same sets as the reference, vclust.py:38-47)
-ALIGN_FIELDS = ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov',
-                'num_alns', 'len_ratio', 'qlen', 'rlen', 'nt_match', 'nt_mismatch']
-ALIGN_OUTFMT = {
-    'lite': ALIGN_FIELDS[:2] + ALIGN_FIELDS[4:11],
-    'standard': ALIGN_FIELDS[:11],
-    'complete': ALIGN_FIELDS[:],
-}
-
 
 # ------------------------------------------------------------------ argument parsing
 class _HelpFormatter(argparse.RawDescriptionHelpFormatter):
@@ -75,6 +69,90 @@ def _unit_float(value):
     return f
 
 
+# ------------------------------------------------------------------ option groups: each declared once, for every subcommand that takes it
+LZ_HELP = dict(mal='Min. anchor length', msl='Min. seed length', mrd='Max. dist. between approx. matches in reference',
+               mqd='Max. dist. between approx. matches in query', reg='Min. considered region length', aw='Approx. window length',
+               am='Max. no. of mismatches in approx. window', ar='Min. length of run ending approx. extension')
+
+
+def lz_options(p):
+    for name, default in DEFAULT_LZ.items():
+        p.add_argument(f'--{name}', metavar='<int>', type=int, default=default, help=f'{LZ_HELP[name]} [%(default)s]')
+
+
+def prefilter_options(p, k_for, own=False):
+    """-k, --min-kmers, --min-ident and --kmers-fraction; own: with the two options that only `prefilter` has, in its order."""
+    p.add_argument('-k', '--k', metavar='<int>', type=int, default=25, choices=range(15, 31), help=f'Size of k-mer for {k_for} [%(default)s]')
+    p.add_argument('--min-kmers', metavar='<int>', type=int, default=20,
+                   help='Minimum number of shared k-mers between two genomes [%(default)s]')
+    p.add_argument('--min-ident', metavar='<float>', type=_unit_float, default=0.7,
+                   help='Minimum sequence identity (0-1) between two genomes, relative to the shorter one [%(default)s]')
+    if own:
+        p.add_argument('--batch-size', metavar='<int>', type=int, default=0,
+                       help='Process a multifasta file in batches of <int> sequences (accepted for '
+                            'compatibility; the GPU path produces identical results) [%(default)s]')
+    p.add_argument('--kmers-fraction', metavar='<float>', type=_unit_float, default=1.0,
+                   help='Fraction of k-mers to analyze in each genome (0-1) [%(default)s]')
+    if own:
+        p.add_argument('--max-seqs', metavar='<int>', type=int, default=0,
+                       help='Maximum number of sequences allowed to pass the prefilter per query; 0 = all [%(default)s]')
+
+
+def cluster_filter_options(p, **algorithm):
+    """-r, --algorithm (default, choices and help are the subcommand's), --metric, the six minimums and --num_alns."""
+    p.add_argument('-r', '--out-repr', action='store_true', dest='representatives',
+                   help='Output a representative genome for each cluster [%(default)s]')
+    p.add_argument('--algorithm', metavar='<str>', dest='algorithm', **algorithm)
+    p.add_argument('--metric', metavar='<str>', dest='metric', choices=['tani', 'gani', 'ani'], default='tani',
+                   help='Similarity metric for clustering [%(default)s]')
+    for name in CLUSTER_FILTERS:
+        p.add_argument(f'--{name}', metavar='<float>', dest=name, type=_unit_float, default=0, help=f'Min. {name} (0-1) [%(default)s]')
+    p.add_argument('--num_alns', metavar='<int>', dest='num_alns', type=int, default=0,
+                   help='Max. number of local alignments between two genomes; 0 = all [%(default)s]')
+
+
+def prior_options(p, prior_help):
+    p.add_argument('--prior', metavar='<file>', type=_existing_path, dest='prior_path', help=prior_help)
+    p.add_argument('--prior-repr', action='store_true', dest='prior_repr',
+                   help='The second column of --prior holds representative ids, as --out-repr writes them [%(default)s]')
+
+
+def db_option(p):
+    p.add_argument('--db', metavar='<file>', type=_existing_path, dest='db_path',
+                   help='Database of genomes already processed (a FASTA file, or a directory of files, like -i): the genomes '
+                        'of -i are new to it, the genome set is the database followed by them, and only pairs that contain a '
+                        'new genome are computed (rows of an earlier run are matched by name: ids are those of the combined set)')
+
+
+def lz_of(args):
+    return {k: getattr(args, k) for k in DEFAULT_LZ}
+
+
+def minimums_of(args):
+    """The minimums that are set: as the reference, a filter is passed on only for a value > 0."""
+    return {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
+
+
+# the groups as the 'Running:' line shows them
+def _lz_text(args):
+    return ' '.join(f'--{k} {v}' for k, v in lz_of(args).items())
+
+
+def _prefilter_text(args):
+    return f'-k {args.k} --min-kmers {args.min_kmers} --min-ident {args.min_ident} --kmers-fraction {args.kmers_fraction}'
+
+
+def _filters_text(args):
+    return (f' --metric {args.metric}' + ''.join(f' --{k} {v}' for k, v in minimums_of(args).items())
+            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else ''))
+
+
+def _prior_text(args):
+    if getattr(args, 'prior_path', None) is None:
+        return ''
+    return f' --prior {args.prior_path}' + (' --prior-repr' if args.prior_repr else '')
+
+
 def get_parser() -> argparse.ArgumentParser:
     fmt = lambda prog: _HelpFormatter(prog, max_help_position=32, width=100)  # noqa: E731
 
@@ -93,12 +171,6 @@ def get_parser() -> argparse.ArgumentParser:
         req.add_argument('-o', '--out', metavar='<file>', type=pathlib.Path, dest='output_path',
                          help='Output filename', required=True)
         return req
-
-    def db_arg(p):
-        p.add_argument('--db', metavar='<file>', type=_existing_path, dest='db_path',
-                       help='Database of genomes already processed (a FASTA file, or a directory of files, like -i): the genomes '
-                            'of -i are new to it, the genome set is the database followed by them, and only pairs that contain a '
-                            'new genome are computed (rows of an earlier run are matched by name: ids are those of the combined set)')
 
     parser = argparse.ArgumentParser(
         description=f'%(prog)s v{__version__}: calculate ANI and cluster virus (meta)genome sequences '
@@ -133,29 +205,15 @@ def get_parser() -> argparse.ArgumentParser:
     # prefilter
     pf = sub.add_parser('prefilter', help='Prefilter genome pairs for alignment', formatter_class=fmt, add_help=False)
     io_args(pf, 'Input FASTA file or directory of files (gzipped or uncompressed)')
-    db_arg(pf)
-    pf.add_argument('-k', '--k', metavar='<int>', type=int, default=25, choices=range(15, 31),
-                    help='Size of k-mer for Kmer-db [%(default)s]')
-    pf.add_argument('--min-kmers', metavar='<int>', type=int, default=20,
-                    help='Minimum number of shared k-mers between two genomes [%(default)s]')
-    pf.add_argument('--min-ident', metavar='<float>', type=_unit_float, default=0.7,
-                    help='Minimum sequence identity (0-1) between two genomes, relative to the shorter one '
-                         '[%(default)s]')
-    pf.add_argument('--batch-size', metavar='<int>', type=int, default=0,
-                    help='Process a multifasta file in batches of <int> sequences (accepted for '
-                         'compatibility; the GPU path produces identical results) [%(default)s]')
-    pf.add_argument('--kmers-fraction', metavar='<float>', type=_unit_float, default=1.0,
-                    help='Fraction of k-mers to analyze in each genome (0-1) [%(default)s]')
-    pf.add_argument('--max-seqs', metavar='<int>', type=int, default=0,
-                    help='Maximum number of sequences allowed to pass the prefilter per query; 0 = all '
-                         '[%(default)s]')
+    db_option(pf)
+    prefilter_options(pf, 'Kmer-db', own=True)
     common(pf)
 
     # align
     al = sub.add_parser('align', help='Align genome sequence pairs and calculate ANI measures',
                         formatter_class=fmt, add_help=False)
     io_args(al, 'Input FASTA file or directory of files (gzipped or uncompressed)')
-    db_arg(al)
+    db_option(al)
     al.add_argument('--filter', metavar='<file>', type=_existing_path, dest='filter_path',
                     help='Path to filter file (output of prefilter)')
     al.add_argument('--filter-threshold', metavar='<float>', dest='filter_threshold', type=_unit_float, default=0,
@@ -168,13 +226,7 @@ def get_parser() -> argparse.ArgumentParser:
                         ('qcov', 'query coverage (aligned fraction)'), ('rcov', 'reference coverage (aligned fraction)')):
         al.add_argument(f'--out-{name}', dest=name, metavar='<float>', type=_unit_float, default=0,
                         help=f'Min. {label} to output (0-1) [%(default)s]')
-    for name, default, text in (('mal', 11, 'Min. anchor length'), ('msl', 7, 'Min. seed length'),
-                                ('mrd', 40, 'Max. dist. between approx. matches in reference'),
-                                ('mqd', 40, 'Max. dist. between approx. matches in query'),
-                                ('reg', 35, 'Min. considered region length'), ('aw', 15, 'Approx. window length'),
-                                ('am', 7, 'Max. no. of mismatches in approx. window'),
-                                ('ar', 3, 'Min. length of run ending approx. extension')):
-        al.add_argument(f'--{name}', metavar='<int>', type=int, default=default, help=f'{text} [%(default)s]')
+    lz_options(al)
     common(al)
 
     # cluster (bin/clusty if present, else vg_cluster for single / cd-hit / uclust / set-cover)
@@ -182,20 +234,11 @@ def get_parser() -> argparse.ArgumentParser:
     clr = io_args(cl, 'Input file with ANI metrics (tsv)')
     clr.add_argument('--ids', metavar='<file>', type=_existing_path, dest='ids_path', required=True,
                      help='Input file with sequence identifiers (tsv)')
-    cl.add_argument('-r', '--out-repr', action='store_true', dest='representatives',
-                    help='Output a representative genome for each cluster [%(default)s]')
-    cl.add_argument('--algorithm', metavar='<str>', dest='algorithm', default='single',
-                    choices=['single', 'complete', 'average', 'uclust', 'cd-hit', 'set-cover', 'leiden', 'mcl'],
-                    help='Clustering algorithm [%(default)s]; average (UPGMA: a pair without a row counts as 0) always runs on the GPU '
-                         'and merges down to the threshold of --metric; mcl (Markov clustering: deterministic, separates dense groups '
-                         'joined by weak rows) always runs on the GPU too')
-    cl.add_argument('--metric', metavar='<str>', dest='metric', choices=['tani', 'gani', 'ani'], default='tani',
-                    help='Similarity metric for clustering [%(default)s]')
-    for name in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio'):
-        cl.add_argument(f'--{name}', metavar='<float>', dest=name, type=_unit_float, default=0,
-                        help=f'Min. {name} (0-1) [%(default)s]')
-    cl.add_argument('--num_alns', metavar='<int>', dest='num_alns', type=int, default=0,
-                    help='Max. number of local alignments between two genomes; 0 = all [%(default)s]')
+    cluster_filter_options(
+        cl, default='single', choices=['single', 'complete', 'average', 'uclust', 'cd-hit', 'set-cover', 'leiden', 'mcl'],
+        help='Clustering algorithm [%(default)s]; average (UPGMA: a pair without a row counts as 0) always runs on the GPU '
+             'and merges down to the threshold of --metric; mcl (Markov clustering: deterministic, separates dense groups '
+             'joined by weak rows) always runs on the GPU too')
     cl.add_argument('--out-linkage', metavar='<file>', type=pathlib.Path, dest='linkage_path',
                     help='Write the merge table of --algorithm single, complete or average (the dendrogram: one line per merge) '
                          'to the tsv <file>')
@@ -203,12 +246,9 @@ def get_parser() -> argparse.ArgumentParser:
                     help='Further thresholds of the metric (0-1, none below its minimum): one more column per level, the cut of '
                          'the same hierarchy (single, complete or average linkage) there; under average linkage the cut at a level '
                          'is not a run at that threshold: the rows between the two still count in the averages')
-    cl.add_argument('--prior', metavar='<file>', type=_existing_path, dest='prior_path',
-                    help='clusters.tsv of an earlier run: its clusters are taken as given and the other genomes of --ids are added '
-                         'to them (--algorithm single, cd-hit or uclust; always runs on the GPU).  Under cd-hit and uclust every '
-                         'earlier cluster keeps its members and its representative; under single, earlier clusters may merge')
-    cl.add_argument('--prior-repr', action='store_true', dest='prior_repr',
-                    help='The second column of --prior holds representative ids, as --out-repr writes them [%(default)s]')
+    prior_options(cl, 'clusters.tsv of an earlier run: its clusters are taken as given and the other genomes of --ids are added '
+                      'to them (--algorithm single, cd-hit or uclust; always runs on the GPU).  Under cd-hit and uclust every '
+                      'earlier cluster keeps its members and its representative; under single, earlier clusters may merge')
     cl.add_argument('--out-stats', metavar='<file>', type=pathlib.Path, dest='stats_path',
                     help='After the clustering, write a per-cluster report to the tsv <file> (always on the GPU, for every '
                          '--algorithm): members, pairs with a row in the input, weakest and mean similarity inside the cluster, '
@@ -232,37 +272,14 @@ def get_parser() -> argparse.ArgumentParser:
                                             'process, comparing every genome with the representatives only',
                         formatter_class=fmt, add_help=False)
     io_args(dr, 'Input FASTA file or directory of files (gzipped or uncompressed)')
-    db_arg(dr)
-    dr.add_argument('--prior', metavar='<file>', type=_existing_path, dest='prior_path',
-                    help='clusters.tsv of an earlier run over the genomes of --db: its clusters and representatives are kept as they '
-                         'are, the genomes of -i are added to them, and only its representatives are ever compared (needs --db)')
-    dr.add_argument('--prior-repr', action='store_true', dest='prior_repr',
-                    help='The second column of --prior holds representative ids, as --out-repr writes them [%(default)s]')
-    dr.add_argument('-k', '--k', metavar='<int>', type=int, default=25, choices=range(15, 31), help='Size of k-mer for the prefilter [%(default)s]')
-    dr.add_argument('--min-kmers', metavar='<int>', type=int, default=20,
-                    help='Minimum number of shared k-mers between two genomes [%(default)s]')
-    dr.add_argument('--min-ident', metavar='<float>', type=_unit_float, default=0.7,
-                    help='Minimum sequence identity (0-1) between two genomes, relative to the shorter one [%(default)s]')
-    dr.add_argument('--kmers-fraction', metavar='<float>', type=_unit_float, default=1.0,
-                    help='Fraction of k-mers to analyze in each genome (0-1) [%(default)s]')
-    for name, default, text in (('mal', 11, 'Min. anchor length'), ('msl', 7, 'Min. seed length'),
-                                ('mrd', 40, 'Max. dist. between approx. matches in reference'),
-                                ('mqd', 40, 'Max. dist. between approx. matches in query'),
-                                ('reg', 35, 'Min. considered region length'), ('aw', 15, 'Approx. window length'),
-                                ('am', 7, 'Max. no. of mismatches in approx. window'),
-                                ('ar', 3, 'Min. length of run ending approx. extension')):
-        dr.add_argument(f'--{name}', metavar='<int>', type=int, default=default, help=f'{text} [%(default)s]')
-    dr.add_argument('-r', '--out-repr', action='store_true', dest='representatives',
-                    help='Output a representative genome for each cluster [%(default)s]')
-    dr.add_argument('--algorithm', metavar='<str>', dest='algorithm', default='cd-hit', choices=['cd-hit'],
-                    help='Clustering algorithm [%(default)s]: a genome joins the earliest (longest) representative it has a passing '
-                         'row to, else it becomes one')
-    dr.add_argument('--metric', metavar='<str>', dest='metric', choices=['tani', 'gani', 'ani'], default='tani',
-                    help='Similarity metric for clustering [%(default)s]')
-    for name in ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio'):
-        dr.add_argument(f'--{name}', metavar='<float>', dest=name, type=_unit_float, default=0, help=f'Min. {name} (0-1) [%(default)s]')
-    dr.add_argument('--num_alns', metavar='<int>', dest='num_alns', type=int, default=0,
-                    help='Max. number of local alignments between two genomes; 0 = all [%(default)s]')
+    db_option(dr)
+    prior_options(dr, 'clusters.tsv of an earlier run over the genomes of --db: its clusters and representatives are kept as they '
+                      'are, the genomes of -i are added to them, and only its representatives are ever compared (needs --db)')
+    prefilter_options(dr, 'the prefilter')
+    lz_options(dr)
+    cluster_filter_options(dr, default='cd-hit', choices=['cd-hit'],
+                           help='Clustering algorithm [%(default)s]: a genome joins the earliest (longest) representative it has a passing '
+                                'row to, else it becomes one')
     dr.add_argument('--batch-genomes', metavar='<int>', type=int, dest='batch_genomes', default=None,
                     help='Genomes compared with the representatives at a time; results do not depend on it [4096]')
     dr.add_argument('--out-table', metavar='<file>', type=pathlib.Path, dest='table_path',
@@ -329,7 +346,7 @@ def validate_args_fasta_input(args, parser):
     # --db: read by the rule of -i; the two are of one kind, and the combined set needs two genomes
     if db_path.is_dir() != args.input_path.is_dir():
         parser.error('-i and --db must both be FASTA files or both be directories.')
-    if _dist_env()[1] > 1:
+    if dist_env()[1] > 1:
         parser.error('--db runs on one GPU: start it without a multi-process launcher (WORLD_SIZE must be 1).')
     args.db_paths = sorted(f for f in db_path.iterdir() if f.is_file()) if db_path.is_dir() else [db_path]
     if not args.is_multifasta:
@@ -352,9 +369,14 @@ def validate_args_prefilter(args, parser):
     return args
 
 
-def _dist_env():
-    """(rank, world, local_rank) of a torchrun launch, (0, 1, 0) otherwise."""
-    return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
+def _check_prior_pair(args, parser):
+    if getattr(args, 'prior_path', None) is None and getattr(args, 'prior_repr', False):
+        parser.error('--prior-repr describes the file of --prior: it needs --prior.')
+
+
+def _check_metric_threshold(args, parser):
+    if not vars(args).get(args.metric, 0):
+        parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
 
 
 def run_native(description, fn, verbosity_level, logger):
@@ -404,11 +426,10 @@ def align_call(args):
     """What the front-end hands to vg_align for validated align arguments -- the counterpart of cmd_lzani
     (vclust.py:1058-1181): `--out-filter` only for values > 0 (:1170-1176), `--multisample-fasta true` iff there
     is exactly one input path (:1159-1160)."""
-    lz = {k: getattr(args, k) for k in ('mal', 'msl', 'mrd', 'mqd', 'reg', 'aw', 'am', 'ar')}
     out_filters = {k: getattr(args, k) for k in ('tani', 'gani', 'ani', 'qcov', 'rcov') if getattr(args, k) > 0}
     call = dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta,
                 columns=ALIGN_OUTFMT[args.outfmt], filter_path=args.filter_path, filter_threshold=args.filter_threshold,
-                out_aln=args.aln_path, lz=lz, out_filters=out_filters, num_threads=args.num_threads)
+                out_aln=args.aln_path, lz=lz_of(args), out_filters=out_filters, num_threads=args.num_threads)
     if getattr(args, 'db_paths', None) is not None:       # --db: vg_align_new (no reference counterpart)
         call['db_paths'] = args.db_paths
     return call
@@ -417,10 +438,8 @@ def align_call(args):
 def handle_prefilter(args, parser, logger):
     args = validate_args_prefilter(args, parser)
     args = validate_args_fasta_input(args, parser)
-    from . import stages
-    rank, world, local_rank = _dist_env()
-    desc = (f'libvclust_gpu prefilter -k {args.k} --min-kmers {args.min_kmers} --min-ident {args.min_ident} '
-            f'--kmers-fraction {args.kmers_fraction} --max-seqs {args.max_seqs}{_db_description(args)} [{world} GPU] -> {args.output_path}')
+    world = dist_env()[1]
+    desc = f'libvclust_gpu prefilter {_prefilter_text(args)} --max-seqs {args.max_seqs}{_db_description(args)} [{world} GPU] -> {args.output_path}'
 
     def work():
         kw = prefilter_call(args)
@@ -435,10 +454,9 @@ def handle_prefilter(args, parser, logger):
 
 def handle_align(args, parser, logger):
     args = validate_args_fasta_input(args, parser)
-    from . import stages
-    rank, world, local_rank = _dist_env()
+    world = dist_env()[1]
     call = align_call(args)
-    desc = ('libvclust_gpu align ' + ' '.join(f'--{k} {v}' for k, v in call['lz'].items())
+    desc = ('libvclust_gpu align ' + _lz_text(args)
             + (f' --filter {args.filter_path} {args.filter_threshold}' if args.filter_path else '')
             + _db_description(args) + f' [{world} GPU] -> {args.output_path}')
 
@@ -457,10 +475,8 @@ def cluster_call(args):
     """What the front-end hands to vg_cluster for validated cluster arguments -- the counterpart of cmd_clusty
     (vclust.py:1184-1278): a minimum only for values > 0, the num_alns maximum only for values > 0.  With --prior the call
     also carries prior_path and prior_repr, and goes to vg_cluster_update."""
-    from .stages import CLUSTER_FILTERS
-    mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
     call = dict(ani_path=args.input_path, ids_path=args.ids_path, out_path=args.output_path, algorithm=args.algorithm,
-                metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives, **mins)
+                metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives, **minimums_of(args))
     if getattr(args, 'linkage_path', None) is not None:
         call['out_linkage'] = args.linkage_path
     if getattr(args, 'levels', None):
@@ -479,12 +495,10 @@ def validate_args_cluster(args, parser):
     cuts, average linkage, Markov clustering and --prior, and for single / cd-hit / uclust / set-cover where there is no bin/clusty
     (vg_cluster).  A plain `--algorithm complete` is not in CLUSTER_ALGORITHMS and goes to Clusty, which must
     then exist."""
-    from ._lib import CLUSTER_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS
     linkage_path, levels = getattr(args, 'linkage_path', None), getattr(args, 'levels', None)
     hierarchy = linkage_path is not None or bool(levels)
     prior_path = getattr(args, 'prior_path', None)
-    if prior_path is None and getattr(args, 'prior_repr', False):
-        parser.error('--prior-repr describes the file of --prior: it needs --prior.')
+    _check_prior_pair(args, parser)
     if prior_path is not None:
         if args.algorithm not in UPDATE_ALGORITHMS:
             parser.error(f'--prior adds genomes to an earlier clustering under --algorithm {", ".join(UPDATE_ALGORITHMS)}, '
@@ -513,22 +527,16 @@ def validate_args_cluster(args, parser):
                    or (not BIN_CLUSTY.exists() and args.algorithm in CLUSTER_ALGORITHMS))
     if not args.native:
         _require_binary(BIN_CLUSTY)
-    if not vars(args).get(args.metric, 0):
-        parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+    _check_metric_threshold(args, parser)
     return args
 
 
-def _cluster_description(args, call):
+def _cluster_description(args):
     """The library's clustering for the 'Running:' line, in the words of the command line."""
-    from .stages import CLUSTER_FILTERS
-    levels, linkage_path, prior_path = getattr(args, 'levels', None), getattr(args, 'linkage_path', None), getattr(args, 'prior_path', None)
+    levels, linkage_path = getattr(args, 'levels', None), getattr(args, 'linkage_path', None)
     return (f'libvclust_gpu cluster --algorithm {args.algorithm}' + (f' --mcl-inflation {args.mcl_inflation:g}' if args.algorithm == 'mcl' else '')
-            + f' --metric {args.metric}' + ''.join(f' --{k} {v}' for k, v in call.items() if k in CLUSTER_FILTERS)
-            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
-            + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
-            + (f' --out-linkage {linkage_path}' if linkage_path is not None else '')
-            + (f' --prior {prior_path}' + (' --prior-repr' if args.prior_repr else '') if prior_path is not None else '')
-            + f' [1 GPU] -> {args.output_path}')
+            + _filters_text(args) + (f' --levels {" ".join(f"{x:g}" for x in levels)}' if levels else '')
+            + (f' --out-linkage {linkage_path}' if linkage_path is not None else '') + _prior_text(args) + f' [1 GPU] -> {args.output_path}')
 
 
 def handle_cluster(args, parser, logger):
@@ -537,10 +545,9 @@ def handle_cluster(args, parser, logger):
     `align --db` run; DESIGN.md section 9, "Update of a prior clustering")."""
     args = validate_args_cluster(args, parser)
     if args.native:
-        from . import stages
         call = cluster_call(args)
         counts = []
-        run_native(_cluster_description(args, call), lambda: counts.append(stages.cluster(verbosity=args.verbosity_level, **call)),
+        run_native(_cluster_description(args), lambda: counts.append(stages.cluster(verbosity=args.verbosity_level, **call)),
                    args.verbosity_level, logger)
         if getattr(args, 'prior_path', None) is not None:
             c = counts[0]
@@ -556,12 +563,10 @@ def handle_cluster(args, parser, logger):
                 logger.warning(f'MCL did not converge within --mcl-iterations {args.mcl_iterations}: the clusters are those of the last iterate')
         cluster_report(args, logger)
         return
-    from .stages import CLUSTER_FILTERS
     cmd = [str(BIN_CLUSTY), '--objects-file', str(args.ids_path), '--algo', args.algorithm, '--id-cols', 'qidx', 'ridx',
            '--distance-col', args.metric, '--similarity', '--numeric-ids']
-    for name in CLUSTER_FILTERS:
-        if getattr(args, name) > 0:
-            cmd += ['--min', name, str(getattr(args, name))]
+    for name, value in minimums_of(args).items():
+        cmd += ['--min', name, str(value)]
     if args.num_alns > 0:
         cmd += ['--max', 'num_alns', str(args.num_alns)]
     if args.representatives:
@@ -577,10 +582,8 @@ def handle_cluster(args, parser, logger):
 def cluster_stats_call(args):
     """What the front-end hands to vg_cluster_stats_file for validated cluster arguments: the filters and the metric of the
     clustering itself (cluster_call), the clusters.tsv just written, and whether it holds representative ids."""
-    from .stages import CLUSTER_FILTERS
-    mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
     return dict(ani_path=args.input_path, ids_path=args.ids_path, clusters_path=args.output_path, out_path=args.stats_path,
-                clusters_repr=bool(args.representatives), metric=args.metric, num_alns=max(args.num_alns, 0), **mins)
+                clusters_repr=bool(args.representatives), metric=args.metric, num_alns=max(args.num_alns, 0), **minimums_of(args))
 
 
 def cluster_report(args, logger):
@@ -589,12 +592,8 @@ def cluster_report(args, logger):
     its own."""
     if getattr(args, 'stats_path', None) is None:
         return
-    from . import stages
     call = cluster_stats_call(args)
-    desc = (f'libvclust_gpu cluster-stats --metric {args.metric}'
-            + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
-            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
-            + f' --clusters {args.output_path} [1 GPU] -> {args.stats_path}')
+    desc = f'libvclust_gpu cluster-stats{_filters_text(args)} --clusters {args.output_path} [1 GPU] -> {args.stats_path}'
     run_native(desc, lambda: stages.cluster_stats(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
 
 
@@ -641,7 +640,6 @@ def handle_deduplicate(args, parser, logger):
     if circular or contained or not BIN_MFASTA.exists():
         # no mfasta-tool, or --circular / --contained (which mfasta-tool does not have): the GPU (vg_deduplicate)
         args = validate_args_deduplicate(args, parser)
-        from . import stages
         call = deduplicate_call(args)
         desc = (f'libvclust_gpu deduplicate -i {" ".join(str(f) for f in args.input_path)}'
                 + (f' --add-prefixes {" ".join(args.add_prefixes)}' if args.add_prefixes else '')
@@ -675,14 +673,11 @@ def handle_deduplicate(args, parser, logger):
 def dereplicate_call(args):
     """What the front-end hands to vg_dereplicate for validated dereplicate arguments: the prefilter, align and cluster options as
     prefilter_call, align_call and cluster_call pass them."""
-    from .stages import CLUSTER_FILTERS
-    mins = {k: getattr(args, k) for k in CLUSTER_FILTERS if getattr(args, k) > 0}
-    lz = {k: getattr(args, k) for k in ('mal', 'msl', 'mrd', 'mqd', 'reg', 'aw', 'am', 'ar')}
     call = dict(paths=args.fasta_paths, out_path=args.output_path, is_multifasta=args.is_multifasta, batch_genomes=args.batch_genomes,
-                k=args.k, kmers_fraction=args.kmers_fraction, min_kmers=args.min_kmers, min_ident=args.min_ident, lz=lz,
+                k=args.k, kmers_fraction=args.kmers_fraction, min_kmers=args.min_kmers, min_ident=args.min_ident, lz=lz_of(args),
                 algorithm=args.algorithm, metric=args.metric, num_alns=max(args.num_alns, 0), representatives=args.representatives,
                 out_table=args.table_path, columns=ALIGN_OUTFMT[args.outfmt], out_repr_fasta=args.repr_fasta_path,
-                num_threads=args.num_threads, **mins)
+                num_threads=args.num_threads, **minimums_of(args))
     if getattr(args, 'db_paths', None) is not None:       # --db --prior: vg_dereplicate_update
         call.update(db_paths=args.db_paths, prior_path=args.prior_path, prior_repr=bool(args.prior_repr))
     return call
@@ -693,32 +688,25 @@ def handle_dereplicate(args, parser, logger):
     (vg_dereplicate).  With --db and --prior the genomes of -i are added to the clusters of an earlier run
     over --db (vg_dereplicate_update).  Always in the library; one GPU."""
     prior_path, db_path = getattr(args, 'prior_path', None), getattr(args, 'db_path', None)
-    if prior_path is None and getattr(args, 'prior_repr', False):
-        parser.error('--prior-repr describes the file of --prior: it needs --prior.')
+    _check_prior_pair(args, parser)
     if prior_path is not None and db_path is None:
         parser.error('--prior names the clusters of the genomes of --db: it needs --db.')
     if db_path is not None and prior_path is None:
         parser.error('--db holds the genomes of an earlier run: it needs the clusters.tsv of that run as --prior.')
     args = validate_args_fasta_input(args, parser)
-    if _dist_env()[1] > 1:
+    if dist_env()[1] > 1:
         parser.error('dereplicate runs on one GPU: start it without a multi-process launcher (WORLD_SIZE must be 1).')
-    if not vars(args).get(args.metric, 0):
-        parser.error(f'{args.metric} threshold must be above 0. Specify the option: --{args.metric}')
+    _check_metric_threshold(args, parser)
     if args.batch_genomes is not None and args.batch_genomes < 1:
         parser.error('--batch-genomes must be at least 1.')
     if args.repr_fasta_path is not None and not args.is_multifasta:
         parser.error('--out-repr-fasta copies the records of one multi-FASTA file: it does not take a directory input.')
-    from . import stages
     call = dereplicate_call(args)
-    desc = (f'libvclust_gpu dereplicate -k {args.k} --min-kmers {args.min_kmers} --min-ident {args.min_ident} --kmers-fraction {args.kmers_fraction} '
-            + ' '.join(f'--{k} {v}' for k, v in call['lz'].items()) + f' --algorithm {args.algorithm} --metric {args.metric}'
-            + ''.join(f' --{k} {v}' for k, v in call.items() if k in stages.CLUSTER_FILTERS)
-            + (f' --num_alns {args.num_alns}' if args.num_alns > 0 else '') + (' --out-repr' if args.representatives else '')
+    desc = (f'libvclust_gpu dereplicate {_prefilter_text(args)} {_lz_text(args)} --algorithm {args.algorithm}{_filters_text(args)}'
             + (f' --batch-genomes {args.batch_genomes}' if args.batch_genomes is not None else '')
             + (f' --out-table {args.table_path}' if args.table_path is not None else '')
             + (f' --out-repr-fasta {args.repr_fasta_path}' if args.repr_fasta_path is not None else '')
-            + _db_description(args) + (f' --prior {args.prior_path}' + (' --prior-repr' if args.prior_repr else '') if args.db_paths is not None else '')
-            + f' [1 GPU] -> {args.output_path}')
+            + _db_description(args) + _prior_text(args) + f' [1 GPU] -> {args.output_path}')
     run_native(desc, lambda: stages.dereplicate(verbosity=args.verbosity_level, **call), args.verbosity_level, logger)
 
 
@@ -750,7 +738,7 @@ def handle_info(args, parser, logger):
 def main():
     parser = get_parser()
     args = parser.parse_args()
-    rank, world, _ = _dist_env()
+    rank = dist_env()[0]
     logger = create_logger('Vclust', getattr(args, 'verbosity_level', 0) if rank == 0 else 0)
     handlers = {'info': handle_info, 'deduplicate': handle_deduplicate, 'prefilter': handle_prefilter,
                 'align': handle_align, 'cluster': handle_cluster, 'dereplicate': handle_dereplicate}

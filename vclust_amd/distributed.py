@@ -14,12 +14,14 @@ vg_lz_align_sharded, vg_prefilter_sharded, vg_align_sharded); this module only b
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
-
-def dist_env():
-    return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
+from . import _lib, api
+from ._lib import PairCount, PairStat, Region, Task, check, lz_params, path, path_array
+from .api import _filled, _input, _take
+from .stages import dist_env
 
 
 def init_process_group(backend=None):
@@ -71,8 +73,7 @@ class Comm:
         return self._lib.vg_comm_world(self.h)
 
     def selftest(self, nbytes=1000):
-        from . import _lib
-        _lib.check(self._lib.vg_comm_selftest(self.h, nbytes))
+        check(self._lib.vg_comm_selftest(self.h, nbytes))
 
     def close(self):
         if self.h:
@@ -97,12 +98,11 @@ def make_comm(dist=None, device=None, kind=None):
     "callback" (all-gather through torch.distributed); default: $VCLUST_COMM, else rccl on the nccl backend, callback
     otherwise."""
     import torch
-    from . import _lib
     lib = _lib.load()
     rank, world, _ = dist_env()
     h = C.c_void_p()
     if dist is None or world == 1:
-        _lib.check(lib.vg_comm_create(0, 1, None, None, C.byref(h)))
+        check(lib.vg_comm_create(0, 1, None, None, C.byref(h)))
         return Comm(h, lib)
     backend = dist.get_backend()
     if kind is None:
@@ -113,8 +113,6 @@ def make_comm(dist=None, device=None, kind=None):
         # has raised.  Rank 0's id travels with a flag; creation and a first real exchange (vg_comm_selftest) are each
         # agreed on by all ranks before the next collective; any failure sends EVERY rank to the callback communicator
         # (all-gathers through torch.distributed) with a line on stderr.
-        import sys
-
         def agree(ok):
             t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=device if backend == 'nccl' else 'cpu')
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
@@ -173,104 +171,74 @@ def make_comm(dist=None, device=None, kind=None):
                 _host_view(recv, world * int(nbytes))[:] = res
             return 0
         except Exception as exc:          # never let an exception cross the C boundary
-            import sys
             print(f'vclust_amd.distributed: all-gather callback failed: {exc}', file=sys.stderr)
             return 1
 
     cb = _lib.ALLGATHER_FN(allgather)
-    _lib.check(lib.vg_comm_create(rank, world, C.cast(cb, C.c_void_p), None, C.byref(h)))
+    check(lib.vg_comm_create(rank, world, C.cast(cb, C.c_void_p), None, C.byref(h)))
     return Comm(h, lib, keep=cb)
 
 
 # ------------------------------------------------------------------ sharded stages (in-memory)
 def prefilter_counts(gs, comm, k, fraction, min_shared=1):
     """Global set sizes and (a, b, shared) triples on every rank (vg_kmer_shared_sharded)."""
-    from . import _lib, api
-    lib = _lib.load()
-    sizes = np.zeros(max(len(gs), 1), dtype=np.int64)
-    pp = C.POINTER(_lib.PairCount)(); n = C.c_int64()
-    _lib.check(lib.vg_kmer_shared_sharded(gs._h, k, float(fraction), int(min_shared), comm.h,
-                                          sizes.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pp), C.byref(n)))
-    pairs = api._take(pp, n.value, api.PAIR_DTYPE)
-    return sizes[:len(gs)], pairs
+    pp, n = C.POINTER(PairCount)(), C.c_int64()
+    sizes, = _filled(len(gs), (C.c_int64,), lambda sp: check(_lib.load().vg_kmer_shared_sharded(
+        gs._h, k, float(fraction), int(min_shared), comm.h, sp, C.byref(pp), C.byref(n))))
+    return sizes, _take(pp, n.value, api.PAIR_DTYPE)
 
 
 def align_pairs_share(gs, cand, world, rank):
     """Rank `rank`'s tasks of the candidate pairs under the reference-range partition (vg_align_pairs_share)."""
-    from . import _lib, api
-    lib = _lib.load()
-    cand = np.ascontiguousarray(cand, dtype=api.PAIR_DTYPE)
-    tp = C.POINTER(_lib.Task)(); nt = C.c_int64()
-    _lib.check(lib.vg_align_pairs_share(gs._h, cand.ctypes.data_as(C.POINTER(_lib.PairCount)), len(cand), int(world), int(rank), C.byref(tp), C.byref(nt)))
-    return api._take(tp, nt.value, api.TASK_DTYPE)
+    tp, nt = C.POINTER(Task)(), C.c_int64()
+    check(_lib.load().vg_align_pairs_share(gs._h, *_input(cand, PairCount), int(world), int(rank), C.byref(tp), C.byref(nt)))
+    return _take(tp, nt.value, api.TASK_DTYPE)
 
 
 def align_pairs(gs, cand, comm, lz=None):
     """Canonical task list and rows of the candidate pairs on every rank (vg_lz_align_pairs_sharded): a rank starts its
     kernels from the pairs alone, the task list of the whole set is assembled beside them."""
-    from . import _lib, api
-    lib = _lib.load()
-    cand = np.ascontiguousarray(cand, dtype=api.PAIR_DTYPE)
-    prm = _lib.LzParams(**{**api.DEFAULT_LZ, **(lz or {})})
-    tp = C.POINTER(_lib.Task)(); nt = C.c_int64(); sp = C.POINTER(_lib.PairStat)()
-    _lib.check(lib.vg_lz_align_pairs_sharded(gs._h, cand.ctypes.data_as(C.POINTER(_lib.PairCount)), len(cand), C.byref(prm), comm.h,
-                                             C.byref(tp), C.byref(nt), C.byref(sp)))
-    return api._take(tp, nt.value, api.TASK_DTYPE), api._take(sp, nt.value, api.STAT_DTYPE)
+    tp, nt, sp = C.POINTER(Task)(), C.c_int64(), C.POINTER(PairStat)()
+    check(_lib.load().vg_lz_align_pairs_sharded(gs._h, *_input(cand, PairCount), C.byref(lz_params(lz)), comm.h, C.byref(tp), C.byref(nt),
+                                                C.byref(sp)))
+    return _take(tp, nt.value, api.TASK_DTYPE), _take(sp, nt.value, api.STAT_DTYPE)
 
 
 def align_rows(gs, tasks, comm, lz=None, want_regions=False):
     """Rows (and regions) of every task on every rank (vg_lz_align_sharded)."""
-    from . import _lib, api
-    lib = _lib.load()
-    tasks = np.ascontiguousarray(tasks, dtype=api.TASK_DTYPE)
-    stats = np.zeros(len(tasks), dtype=api.STAT_DTYPE)
-    prm = _lib.LzParams(**{**api.DEFAULT_LZ, **(lz or {})})
-    rp = C.POINTER(_lib.Region)(); nr = C.c_int64()
-    _lib.check(lib.vg_lz_align_sharded(gs._h, tasks.ctypes.data_as(C.POINTER(_lib.Task)), len(tasks), C.byref(prm), comm.h,
-                                       stats.ctypes.data_as(C.POINTER(_lib.PairStat)),
-                                       C.byref(rp) if want_regions else None, C.byref(nr)))
-    regions = api._take(rp, nr.value, api.REGION_DTYPE) if want_regions else None
-    return stats, regions
+    tp, n = _input(tasks, Task)
+    stats = np.zeros(n, dtype=api.STAT_DTYPE)
+    rp, nr = C.POINTER(Region)(), C.c_int64()
+    check(_lib.load().vg_lz_align_sharded(gs._h, tp, n, C.byref(lz_params(lz)), comm.h, _lib.ptr(stats, PairStat),
+                                          C.byref(rp) if want_regions else None, C.byref(nr)))
+    return stats, _take(rp, nr.value, api.REGION_DTYPE) if want_regions else None
 
 
 def align_owner(tasks, n_genomes, world):
-    from . import _lib, api
-    lib = _lib.load()
-    tasks = np.ascontiguousarray(tasks, dtype=api.TASK_DTYPE)
-    owner = np.zeros(max(len(tasks), 1), dtype=np.int32)
-    _lib.check(lib.vg_align_owner(tasks.ctypes.data_as(C.POINTER(_lib.Task)), len(tasks), int(n_genomes), int(world),
-                                  owner.ctypes.data_as(C.POINTER(C.c_int32))))
-    return owner[:len(tasks)]
+    tp, n = _input(tasks, Task)
+    owner, = _filled(n, (C.c_int32,), lambda op: check(_lib.load().vg_align_owner(tp, n, int(n_genomes), int(world), op)))
+    return owner
 
 
 # ------------------------------------------------------------------ whole stages (files)
-def prefilter(paths, out_path, is_multifasta, k=25, min_kmers=20, min_ident=0.7, kmers_fraction=1.0, max_seqs=0,
-              num_threads=1):
-    from . import _lib, api
-    lib = _lib.load()
+def _sharded_stage(call):
+    """A whole stage on this rank's device: `call` gets the communicator of the process group."""
     dist, device = init_process_group()
-    rank, world, local_rank = dist_env()
-    api.set_device(local_rank % max(api.device_count(), 1))
+    api.set_device(dist_env()[2] % max(api.device_count(), 1))
     comm = make_comm(dist, device)
     try:
-        arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
-        prm = _lib.PrefilterParams(k, min_kmers, min_ident, 0, kmers_fraction, max_seqs, num_threads, 0, int(bool(is_multifasta)))
-        _lib.check(lib.vg_prefilter_sharded(arr, len(paths), os.fsencode(str(out_path)), C.byref(prm), comm.h))
+        call(comm)
     finally:
         comm.close()
+
+
+def prefilter(paths, out_path, is_multifasta, k=25, min_kmers=20, min_ident=0.7, kmers_fraction=1.0, max_seqs=0,
+              num_threads=1):
+    prm = _lib.PrefilterParams(k, min_kmers, min_ident, 0, kmers_fraction, max_seqs, num_threads, 0, int(bool(is_multifasta)))
+    _sharded_stage(lambda comm: check(_lib.load().vg_prefilter_sharded(path_array(paths), len(paths), path(out_path), C.byref(prm), comm.h)))
 
 
 def align(paths, out_path, is_multifasta, columns, filter_path=None, filter_threshold=0.0, out_aln=None, lz=None,
           out_filters=None, num_threads=1):
-    from . import _lib, api
-    lib = _lib.load()
-    dist, device = init_process_group()
-    rank, world, local_rank = dist_env()
-    api.set_device(local_rank % max(api.device_count(), 1))
-    comm = make_comm(dist, device)
-    try:
-        arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
-        p = api.align_params(columns, filter_path, filter_threshold, out_aln, lz, out_filters, num_threads, 0, is_multifasta)
-        _lib.check(lib.vg_align_sharded(arr, len(paths), os.fsencode(str(out_path)), C.byref(p), comm.h))
-    finally:
-        comm.close()
+    p = api.align_params(columns, filter_path, filter_threshold, out_aln, lz, out_filters, num_threads, 0, is_multifasta)
+    _sharded_stage(lambda comm: check(_lib.load().vg_align_sharded(path_array(paths), len(paths), path(out_path), C.byref(p), comm.h)))

@@ -6,14 +6,19 @@ import ctypes as C
 import os
 
 from . import _lib
-from ._lib import (CLUSTER_ALGORITHMS, DEREP_ALGORITHMS, DEREP_BATCH_GENOMES, FLOW_ALGORITHMS, HIERARCHY_ALGORITHMS, UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupOptions,
-                   DedupParams, DerepFileParams, DerepParams, DerepStats, DerepUpdateStats, LzParams, MclParams, MclStats, PrefilterParams, check)
+from ._lib import (ALIGN_OUTFMT, DEFAULT_LZ, DEREP_ALGORITHMS, DEREP_BATCH_GENOMES, FLOW_ALGORITHMS, HIERARCHY_ALGORITHMS, LIBRARY_ALGORITHMS,  # noqa: F401
+                   UPDATE_ALGORITHMS, AlignParams, ClusterParams, ClusterUpdateStats, DedupParams, DerepFileParams, DerepParams,
+                   DerepStats, DerepUpdateStats, MclParams, MclStats, PrefilterParams, as_dict, check, lz_params, path, path_array, string_array)
 
-DEFAULT_LZ = dict(mal=11, msl=7, mrd=40, mqd=40, reg=35, aw=15, am=7, ar=3)
+
+def dist_env():
+    """(rank, world, local_rank) of a torchrun launch, (0, 1, 0) otherwise."""
+    return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
 
 
-def _path_array(paths):
-    return (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
+def _check_prior(prior_path, prior_repr):
+    if prior_path is None and prior_repr:
+        raise ValueError('prior_repr needs prior_path')
 
 
 def prefilter(paths, out_path, is_multifasta, k=25, min_kmers=20, min_ident=0.7, batch_size=0,
@@ -21,26 +26,25 @@ def prefilter(paths, out_path, is_multifasta, k=25, min_kmers=20, min_ident=0.7,
     """fltr.txt of the genomes in `paths` (vg_prefilter).  db_paths: a database the genomes of `paths` are new to -- the set is
     the database's genomes followed by them, and only the rows of the new genomes are filled (vg_prefilter_new)."""
     lib = _lib.load()
-    arr = _path_array(paths)
     prm = PrefilterParams(k, min_kmers, min_ident, batch_size, kmers_fraction, max_seqs, num_threads,
                           verbosity, int(bool(is_multifasta)))
     if db_paths is not None:
-        check(lib.vg_prefilter_new(_path_array(db_paths), len(db_paths), arr, len(paths), os.fsencode(str(out_path)), C.byref(prm)))
+        check(lib.vg_prefilter_new(path_array(db_paths), len(db_paths), path_array(paths), len(paths), path(out_path), C.byref(prm)))
         return
-    check(lib.vg_prefilter(arr, len(paths), os.fsencode(str(out_path)), C.byref(prm)))
+    check(lib.vg_prefilter(path_array(paths), len(paths), path(out_path), C.byref(prm)))
 
 
 def align_params(columns, filter_path=None, filter_threshold=0.0, out_aln=None, lz=None, out_filters=None, num_threads=1,
                  verbosity=0, is_multifasta=True):
     """vg_align_params for the given options (the struct keeps its strings alive through attributes)."""
-    cols = (C.c_char_p * len(columns))(*[c.encode() for c in columns])
+    cols = string_array(columns)
     p = AlignParams()
-    p.lz = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+    p.lz = lz_params(lz)
     for name, val in (out_filters or {}).items():
         setattr(p, f'out_{name}', float(val))
-    p.filter_path = os.fsencode(str(filter_path)) if filter_path else None
+    p.filter_path = path(filter_path or None)
     p.filter_threshold = float(filter_threshold)
-    p.out_aln_path = os.fsencode(str(out_aln)) if out_aln else None
+    p.out_aln_path = path(out_aln or None)
     p.out_columns = cols
     p.n_out_columns = len(columns)
     p.num_threads = num_threads
@@ -55,12 +59,11 @@ def align(paths, out_path, is_multifasta, columns, filter_path=None, filter_thre
     """ani.tsv of the genomes in `paths` (vg_align).  db_paths: as in prefilter; only pairs that contain a genome of `paths` are
     aligned -- the filter's, or all of them without a filter (vg_align_new)."""
     lib = _lib.load()
-    arr = _path_array(paths)
     p = align_params(columns, filter_path, filter_threshold, out_aln, lz, out_filters, num_threads, verbosity, is_multifasta)
     if db_paths is not None:
-        check(lib.vg_align_new(_path_array(db_paths), len(db_paths), arr, len(paths), os.fsencode(str(out_path)), C.byref(p)))
+        check(lib.vg_align_new(path_array(db_paths), len(db_paths), path_array(paths), len(paths), path(out_path), C.byref(p)))
         return
-    check(lib.vg_align(arr, len(paths), os.fsencode(str(out_path)), C.byref(p)))
+    check(lib.vg_align(path_array(paths), len(paths), path(out_path), C.byref(p)))
 
 
 CLUSTER_FILTERS = ('tani', 'gani', 'ani', 'qcov', 'rcov', 'len_ratio')
@@ -96,40 +99,37 @@ def cluster(ani_path, ids_path, out_path, algorithm='single', metric='tani', num
     mcl_chaos_eps and mcl_iterations; it excludes prior_path, out_linkage and levels and returns its stats as a dict (iterations,
     converged, chaos, ...).  Every other call returns None."""
     mcl = {k: mins.pop(k) for k in list(mins) if k in MCL_DEFAULTS}
-    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
     # (an unknown filter is the first error; an unknown algorithm is refused below, before p is used)
-    p = _cluster_params(known.get(algorithm, 0), metric, num_alns, representatives, num_threads, verbosity, mins)
+    p = _cluster_params(LIBRARY_ALGORITHMS.get(algorithm, 0), metric, num_alns, representatives, num_threads, verbosity, mins)
     if mcl and algorithm not in FLOW_ALGORITHMS:
         raise ValueError(f'{", ".join(sorted(mcl))}: only with algorithm=\'mcl\'')
-    if prior_path is None and prior_repr:
-        raise ValueError('prior_repr needs prior_path')
+    _check_prior(prior_path, prior_repr)
+    hierarchy = out_linkage is not None or levels is not None
     if prior_path is not None:
-        if out_linkage is not None or levels is not None:
+        if hierarchy:
             raise ValueError('prior_path excludes out_linkage and levels')
         if algorithm not in UPDATE_ALGORITHMS:
             raise ValueError(f'algorithm {algorithm!r} cannot update a prior clustering (choices: {", ".join(UPDATE_ALGORITHMS)})')
-    if algorithm not in known:
-        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(known)})')
-    paths = (os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(out_path)))
+    if algorithm not in LIBRARY_ALGORITHMS:
+        raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices: {", ".join(LIBRARY_ALGORITHMS)})')
+    paths = (path(ani_path), path(ids_path), path(out_path))
     if prior_path is not None:
         st = ClusterUpdateStats()
-        check(_lib.load().vg_cluster_update(paths[0], paths[1], os.fsencode(str(prior_path)), int(bool(prior_repr)), paths[2], C.byref(p),
-                                            C.byref(st)))
-        return {name: getattr(st, name) for name, _ in ClusterUpdateStats._fields_}
-    if algorithm in FLOW_ALGORITHMS and out_linkage is None and levels is None:
+        check(_lib.load().vg_cluster_update(paths[0], paths[1], path(prior_path), int(bool(prior_repr)), paths[2], C.byref(p), C.byref(st)))
+        return as_dict(st)
+    if algorithm in FLOW_ALGORITHMS and not hierarchy:
         m = {**MCL_DEFAULTS, **mcl}
         prm = MclParams(float(m['mcl_inflation']), float(m['mcl_prune']), float(m['mcl_chaos_eps']), int(m['mcl_max_row']), int(m['mcl_iterations']))
         st = MclStats()
         check(_lib.load().vg_cluster_mcl(*paths, C.byref(p), C.byref(prm), C.byref(st)))
-        return {name: getattr(st, name) for name, _ in MclStats._fields_}
-    if out_linkage is None and levels is None:
+        return as_dict(st)
+    if not hierarchy:
         check(_lib.load().vg_cluster(*paths, C.byref(p)))
         return
     if algorithm not in HIERARCHY_ALGORITHMS:
         raise ValueError('out_linkage and levels need algorithm=\'single\', \'complete\' or \'average\'')
     lv = [float(x) for x in (levels or ())]
-    check(_lib.load().vg_cluster_linkage(*paths, C.byref(p), os.fsencode(str(out_linkage)) if out_linkage is not None else None,
-                                         (C.c_double * len(lv))(*lv) if lv else None, len(lv)))
+    check(_lib.load().vg_cluster_linkage(*paths, C.byref(p), path(out_linkage), (C.c_double * len(lv))(*lv) if lv else None, len(lv)))
 
 
 def cluster_stats(ani_path, ids_path, clusters_path, out_path, clusters_repr=False, metric='tani', num_alns=0, num_threads=0,
@@ -140,8 +140,8 @@ def cluster_stats(ani_path, ids_path, clusters_path, out_path, clusters_repr=Fal
     cluster() (metric, mins, num_alns: give the ones the clustering was made with); clusters_path may be any clustering of the
     ids file, this library's or not; clusters_repr: its label columns hold representative ids."""
     p = _cluster_params(0, metric, num_alns, False, num_threads, verbosity, mins)
-    check(_lib.load().vg_cluster_stats_file(os.fsencode(str(ani_path)), os.fsencode(str(ids_path)), os.fsencode(str(clusters_path)),
-                                            int(bool(clusters_repr)), C.byref(p), os.fsencode(str(out_path))))
+    check(_lib.load().vg_cluster_stats_file(path(ani_path), path(ids_path), path(clusters_path), int(bool(clusters_repr)), C.byref(p),
+                                            path(out_path)))
 
 
 def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False, contained=False,
@@ -153,41 +153,24 @@ def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_thre
     too, with the same offset column (vg_deduplicate_contained); it excludes circular.  terminal_repeat (with circular only):
     an exact repeat of a record's first symbols at its end, of at least that many symbols, is taken off before rotations are
     compared, and dup_path gets the two repeat columns (vg_deduplicate_circular_tr); 0 = off."""
-    if circular and contained:
-        raise ValueError('circular and contained exclude each other')
-    if terminal_repeat and not circular:
-        raise ValueError('terminal_repeat needs circular')
+    mode = _lib.dedup_mode(circular, contained, terminal_repeat)
     if prefixes is not None and len(prefixes) != len(paths):
         raise ValueError('one prefix per input file')
-    arr = (C.c_char_p * len(paths))(*[os.fsencode(str(p)) for p in paths])
-    pre = (C.c_char_p * len(paths))(*[str(x).encode() for x in prefixes]) if prefixes is not None else None
     prm = DedupParams(gzip_level=int(gzip_level), num_threads=int(num_threads), verbosity=int(verbosity))
-    if contained:
-        check(_lib.load().vg_deduplicate_contained(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm)))
-        return
-    if circular and terminal_repeat:
-        check(_lib.load().vg_deduplicate_circular_tr(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)),
-                                                     C.byref(prm), int(terminal_repeat)))
-        return
-    if circular:
-        opt = DedupOptions(circular=1)
-        check(_lib.load().vg_deduplicate_ex(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm),
-                                            C.byref(opt)))
-        return
-    check(_lib.load().vg_deduplicate(arr, len(paths), pre, os.fsencode(str(out_path)), os.fsencode(str(dup_path)), C.byref(prm)))
+    check(getattr(_lib.load(), mode.files)(path_array(paths), len(paths), string_array(prefixes) if prefixes is not None else None,
+                                           path(out_path), path(dup_path), C.byref(prm), *mode.extra(terminal_repeat)))
 
 
 def derep_params(batch_genomes=None, k=25, kmers_fraction=1.0, min_kmers=20, min_ident=0.7, lz=None, algorithm='cd-hit', metric='tani',
                  num_alns=0, mins=None):
     """vg_derep_params of dereplicate() and GenomeSet.dereplicate_set().  An algorithm the library does not know at all is refused
     here; one it knows but dereplicate cannot run (anything but cd-hit) is refused by the library, before any device use."""
-    known = {**CLUSTER_ALGORITHMS, **HIERARCHY_ALGORITHMS, **FLOW_ALGORITHMS}
-    if algorithm not in known:
+    if algorithm not in LIBRARY_ALGORITHMS:
         raise ValueError(f'algorithm {algorithm!r} is not computed by the library (choices of dereplicate: {", ".join(DEREP_ALGORITHMS)})')
     p = DerepParams()
     p.k, p.kmers_fraction, p.min_kmers, p.min_ident = int(k), float(kmers_fraction), int(min_kmers), float(min_ident)
-    p.lz = LzParams(**{**DEFAULT_LZ, **(lz or {})})
-    p.cluster = _cluster_params(known[algorithm], metric, num_alns, False, 0, 0, mins or {})
+    p.lz = lz_params(lz)
+    p.cluster = _cluster_params(LIBRARY_ALGORITHMS[algorithm], metric, num_alns, False, 0, 0, mins or {})
     p.batch_genomes = DEREP_BATCH_GENOMES if batch_genomes is None else int(batch_genomes)
     return p
 
@@ -205,22 +188,21 @@ def dereplicate(paths, out_path, is_multifasta, batch_genomes=None, k=25, kmers_
     -> the counts as a dict."""
     if (db_paths is None) != (prior_path is None):
         raise ValueError('db_paths and prior_path go together: the database is the genome set of the prior clustering')
-    if prior_path is None and prior_repr:
-        raise ValueError('prior_repr needs prior_path')
+    _check_prior(prior_path, prior_repr)
     st, ust = DerepStats(), DerepUpdateStats()
     p = DerepFileParams()
     p.derep = derep_params(batch_genomes, k, kmers_fraction, min_kmers, min_ident, lz, algorithm, metric, num_alns, mins)
     p.representatives = int(bool(representatives))
-    columns = list(columns or ['qidx', 'ridx', 'query', 'reference', 'tani', 'gani', 'ani', 'qcov', 'rcov', 'num_alns', 'len_ratio'])
-    cols = (C.c_char_p * len(columns))(*[c.encode() for c in columns])
-    p.out_table_path = os.fsencode(str(out_table)) if out_table is not None else None
+    columns = list(columns or ALIGN_OUTFMT['standard'])
+    cols = string_array(columns)
+    p.out_table_path = path(out_table)
     p.out_columns, p.n_out_columns = cols, len(columns)
-    p.out_repr_fasta_path = os.fsencode(str(out_repr_fasta)) if out_repr_fasta is not None else None
+    p.out_repr_fasta_path = path(out_repr_fasta)
     p.num_threads, p.verbosity, p.is_multifasta = int(num_threads), int(verbosity), int(bool(is_multifasta))
     p.stats = C.pointer(st)
     if db_paths is None:
-        check(_lib.load().vg_dereplicate(_path_array(paths), len(paths), os.fsencode(str(out_path)), C.byref(p)))
-        return {name: getattr(st, name) for name, _ in DerepStats._fields_}
-    check(_lib.load().vg_dereplicate_update(_path_array(db_paths), len(db_paths), _path_array(paths), len(paths), os.fsencode(str(prior_path)),
-                                            int(bool(prior_repr)), os.fsencode(str(out_path)), C.byref(p), C.byref(ust)))
-    return {name: getattr(x, name) for x in (st, ust) for name, _ in type(x)._fields_}
+        check(_lib.load().vg_dereplicate(path_array(paths), len(paths), path(out_path), C.byref(p)))
+        return as_dict(st)
+    check(_lib.load().vg_dereplicate_update(path_array(db_paths), len(db_paths), path_array(paths), len(paths), path(prior_path),
+                                            int(bool(prior_repr)), path(out_path), C.byref(p), C.byref(ust)))
+    return as_dict(st, ust)
