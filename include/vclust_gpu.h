@@ -168,7 +168,10 @@ void vg_set_new_path(int mode);
  *   g_st        short records only: super-tiles per 2^25-position group where a unit spans several groups (u_st / g_st of them),
  *               0 where a unit lies inside one group
  *   tile32k     level 1 scatters whole 32 768-position tiles;  narrow: level-2 records carry one key word
- *   short_rec   level-1 records are 8 bytes (key bits, position modulo 2^25) instead of 12 */
+ *   short_rec   level-1 records are 8 bytes (key bits, position modulo 2^25) instead of 12
+ * vg_kmer_level2_slots answers, for the same pass and by the same function, how its level 2 runs: *slots > 0 = in one pass, without
+ * a count, every final bucket owning that many record slots; 0 = the counted level 2 (RANGE and HASH shards, sub-shards, one
+ * level, the wide scatter, fewer than 256 level-1 buckets) or a pass the bucket pipeline does not take as a dense one. */
 typedef struct {
     int accepted; int64_t P; int n_passes;
     int levels, total_bits, B1, B2;
@@ -176,6 +179,7 @@ typedef struct {
     int tile32k, narrow, short_rec;
 } vg_kmer_geometry_info;
 int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info);
+int vg_kmer_level2_slots(const vg_genomes* g, int k, double fraction, int shard, int n_shards, int* slots);
 int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geometry_info* info);
 /* The row-pointer rule of a prefilter pass (tests and tooling; no reference call site).  Host only: no device is needed or touched.
  * A pass whose genome list holds `entries` slots over `n_genomes` genomes writes the row pointer of a k-mer with ONE smaller partner as

@@ -241,6 +241,7 @@ SYMBOLS = {
     'vg_kmer_shared_new': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, P(C.c_int64), P(P(PairCount)), P(C.c_int64)]),
     'vg_kmer_geometry': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, P(KmerGeometry)]),
     'vg_kmer_geometry_at': (C.c_int, [C.c_int64, C.c_int, P(KmerGeometry)]),
+    'vg_kmer_level2_slots': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, P(C.c_int)]),
     'vg_rowptr_inline_lo': (C.c_int, [C.c_int64, C.c_int64, P(C.c_uint32)]),
     'vg_kmer_set': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, P(P(C.c_uint64)), P(C.c_int64)]),
     'vg_filter_pairs': (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), C.c_int64, C.POINTER(PairCount), C.c_int64,

@@ -235,6 +235,13 @@ class GenomeSet:
         check(self._lib.vg_kmer_geometry(self._h, int(k), float(fraction), int(shard), int(n_shards), C.byref(info)))
         return as_dict(info)
 
+    def kmer_level2_slots(self, k=25, fraction=1.0, shard=0, n_shards=1):
+        """How level 2 of the first pass of kmer_shared with these arguments runs (vg_kmer_level2_slots; host only): record slots per
+        final bucket of the one-pass form, or 0 = the counted level 2."""
+        slots = C.c_int(0)
+        check(self._lib.vg_kmer_level2_slots(self._h, int(k), float(fraction), int(shard), int(n_shards), C.byref(slots)))
+        return int(slots.value)
+
     def kmer_set(self, idx, k=25, fraction=1.0):
         p = C.POINTER(C.c_uint64)()
         n = C.c_int64()

@@ -832,9 +832,12 @@ k_spgemm_dense(const uint32_t* __restrict__ rowinfo, const uint32_t* __restrict_
 //             k_scan_units           per level-1 bucket: T2 -> write offsets in place + the final bucket starts
 //             k_part_scatter2_narrow tiles of 16 384 records narrowed to 8 bytes (<= 32 key bits left), bin-major
 //                                    output; k_part_scatter<SRC_PLANES,2> for wider keys
-//   buckets   k_bucket_runs          LDS counting sort on the next 9 (11) bits, in-bin ranking, runs, duplicates,
+//             the dense pass over all buckets (level2_capacity) runs k_part_scatter2_narrow<., true> ALONE: fixed slots per final
+//             bucket, one workgroup per level-1 bucket, sizes counted while writing and scanned into the bucket starts
+//   buckets  k_bucket_runs          LDS counting sort on the next 9 (11) bits, in-bin ranking, runs, duplicates,
 //                                    gen[] and row pointers; 1 536-entry buckets, 6 144 on a second attempt
-// No global atomics, no host round trip between the levels, deterministic output.  A bucket that does not fit the
+// No global atomics on the records' way (the one-pass level 2 keeps an overflow flag and the largest bucket size in two words), no
+// host round trip between the levels, deterministic output.  A bucket that does not fit the
 // LDS (a k-mer present many hundreds of times) or an input too small sends the call to the general path.
 //
 // The partition kernels are variations on one tile loop -- load the cursors, zero the tile histogram, rank with LDS
@@ -1581,21 +1584,39 @@ k_part_scatter_range(part_src S, int B1, int nbins /* <= 2048 */, int unit_tiles
 // tiles of 16 384 records, staged in the LDS already narrowed.  The staged record no longer holds its bin, so
 // the output runs bin-major: eight lanes take one bin's slots (a bin's segment of the tile: 8 records = 64 bytes
 // on average), eight bins per wave and trip.
+//
+// ONEPASS: no count pass in front of it.  One workgroup takes ALL units of a level-1 bucket, in order, and keeps its 2^B2 cursors
+// in the LDS from the first tile to the last; final bucket bk owns the fixed slots [bk * cap, (bk + 1) * cap) of o_rec, so the
+// cursors start at b * cap (relative to the level-1 bucket's first slot) and need no table.  Inside a final bucket the records lie in
+// unit order, then tile order: the order of the counted layout.  The sizes go to cnt2[b1][b2] (the host scans them into boff), the
+// largest one to stat[1].  A tile that would take a bucket past its capacity stores only what fits and sets stat[0]: the host then
+// runs the counted level 2 (the level-1 records are untouched); workgroups that start a bucket after that leave at once.
 constexpr int NT_TILE = 16384;
 constexpr int NT_PER = NT_TILE / PT_THREADS;
 constexpr int NT_MAXBINS = 2048;
-template <bool SHORT>
+template <bool SHORT, bool ONEPASS>
 __global__ void __launch_bounds__(PT_THREADS)
 k_part_scatter2_narrow(const uint32_t* __restrict__ rec, int B1, int B2, int64_t n_units, const uint32_t* __restrict__ Ts, lvl2_tab L,
-                       uint32_t* __restrict__ o_rec, int narrow_shift) {
+                       uint32_t* __restrict__ o_rec, int narrow_shift, uint32_t cap, uint32_t* __restrict__ cnt2, uint32_t* __restrict__ stat) {
     __shared__ uint2 s_rec[NT_TILE];
     __shared__ uint32_t thist[NT_MAXBINS], tstart[NT_MAXBINS], cursor[NT_MAXBINS];
     __shared__ uint32_t s_wave[16];
+    __shared__ uint32_t s_stop;
     const int nbins = 1 << B2;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+    // the units of a workgroup: every gridDim.x-th one, or (ONEPASS) all n_u of every gridDim.x-th level-1 bucket, one after the other
+    const int64_t bucket_step = ((int64_t)gridDim.x - 1) * L.n_u;
+    for (int64_t u = ONEPASS ? (int64_t)blockIdx.x * L.n_u : (int64_t)blockIdx.x; u < n_units; u += ONEPASS ? 1 + ((u + 1) % L.n_u ? 0 : bucket_step) : (int64_t)gridDim.x) {
         uint32_t b1, U; int64_t s0, s1;
         lvl2_unit(L, u, &b1, &U, &s0, &s1);
+        const uint64_t obase = ONEPASS ? (uint64_t)b1 * (uint64_t)nbins * cap : 0ull;      // first slot of the level-1 bucket's block
+        if (ONEPASS && U == 0) {
+            lds_sync();
+            if (threadIdx.x == 0) s_stop = __hip_atomic_load(stat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = (uint32_t)b * cap;
+            lds_sync();
+            if (s_stop) break;                                 // (one value for the whole workgroup: read once, handed on through the LDS)
+        }
         uint32_t gbase = 0, gb[3] = {0, 0, 0};
         uint32_t grow0 = 0, grow1 = 0, grow2 = 0, grow3 = 0;      // RANGE shard: first row of each of the unit's (up to four) position groups
         if (SHORT) {
@@ -1606,7 +1627,7 @@ k_part_scatter2_narrow(const uint32_t* __restrict__ rec, int B1, int B2, int64_t
             }
         }
         lds_sync();
-        for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = Ts[((uint64_t)b1 * L.n_u + U) * nbins + b];
+        if (!ONEPASS) for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = Ts[((uint64_t)b1 * L.n_u + U) * nbins + b];
         for (int64_t t0 = s0; t0 < s1; t0 += NT_TILE) {
             for (int b = threadIdx.x; b < nbins; b += PT_THREADS) thist[b] = 0;
             lds_sync();
@@ -1673,15 +1694,28 @@ k_part_scatter2_narrow(const uint32_t* __restrict__ rec, int B1, int B2, int64_t
             for (int bb = wv * per_wave; bb < min(nbins, (wv + 1) * per_wave); bb += 8) {
                 const int b = bb + (lane >> 3);
                 const bool live = b < min(nbins, (wv + 1) * per_wave);
-                const uint32_t st = live ? tstart[b] : 0u, cnt = live ? thist[b] : 0u;
-                const uint64_t cur = live ? cursor[b] : 0ull;
+                const uint32_t st = live ? tstart[b] : 0u; uint32_t cnt = live ? thist[b] : 0u;
+                const uint64_t cur = obase + (live ? cursor[b] : 0u);
+                if (ONEPASS && live) {
+                    const uint32_t room = (uint32_t)(b + 1) * cap - cursor[b];      // nothing is stored beyond the bucket's slots
+                    if (cnt > room) { cnt = room; if ((lane & 7) == 0) stat[0] = 1u; }
+                }
                 for (uint32_t i = (uint32_t)(lane & 7); __any(i < cnt); i += 8) {
                     if (i < cnt) { const uint2 v = s_rec[st + i]; __builtin_memcpy(o_rec + 2 * (cur + i), &v, 8); }
                 }
             }
             lds_sync();
-            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] += thist[b];
+            if (ONEPASS) for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] = min(cursor[b] + thist[b], (uint32_t)(b + 1) * cap);
+            else for (int b = threadIdx.x; b < nbins; b += PT_THREADS) cursor[b] += thist[b];
             lds_sync();
+        }
+        if (ONEPASS && U + 1 == (uint32_t)L.n_u) {
+            // the sizes of the bucket's final buckets, and the largest of them (cursor[] is stable: the tile loop ends on a barrier)
+            uint32_t mx = 0;
+            for (int b = threadIdx.x; b < nbins; b += PT_THREADS) { const uint32_t c = cursor[b] - (uint32_t)b * cap; cnt2[(uint64_t)b1 * nbins + b] = c; mx = max(mx, c); }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+            if (lane == 0 && mx > 0) atomicMax(&stat[1], mx);
         }
     }
 }
@@ -1784,7 +1818,8 @@ k_bucket_runs(const uint32_t* __restrict__ rec, int stride /* 3: (w0, w1, pay); 
               const uint32_t* __restrict__ boff, int64_t n_buckets, int pbits, const uint32_t* __restrict__ blk2g, int blk_shift,
               uint32_t* __restrict__ gen, uint32_t* __restrict__ rowinfo, compact_map M, int* __restrict__ dup_per_genome,
               const uint32_t* __restrict__ bucket_list /* null: all buckets; else the n_buckets listed ones */,
-              uint32_t* __restrict__ over_list, unsigned int* __restrict__ n_over, uint32_t inline_lo) {
+              uint32_t* __restrict__ over_list, unsigned int* __restrict__ n_over, uint32_t inline_lo,
+              uint32_t cap /* 0: the records of bucket bk start at boff[bk]; else at bk * cap (one-pass level 2) */) {
     constexpr int BK_SUB = 1 << SUBBITS, CAP = THREADS * BK_PER;
     const uint32_t inline_rank = inline_lo ? 1u : 0u;      // entries in front of the one that inlines; 0 (off) is no entry's count: the first of a run writes no pointer
     static_assert(CAP <= 8192 && BK_MAXBIN <= 1024, "slot | rank << 13 of the run members");
@@ -1804,6 +1839,7 @@ k_bucket_runs(const uint32_t* __restrict__ rec, int stride /* 3: (w0, w1, pay); 
         // of it has been written when it is handed on
         if (n_u > (uint32_t)CAP) { if (threadIdx.x == 0) over_list[atomicAdd(n_over, 1u)] = (uint32_t)bk; continue; }
         const int n = (int)n_u;
+        const uint64_t r0 = cap ? (uint64_t)bk * cap : (uint64_t)b0;      // the bucket's first record (gen[] and the pointers are numbered by boff either way)
         lds_sync();
         for (int b = threadIdx.x; b <= BK_SUB; b += THREADS) cnt[b] = 0;
         if (threadIdx.x == 0) s_big = 0;
@@ -1816,8 +1852,8 @@ k_bucket_runs(const uint32_t* __restrict__ rec, int stride /* 3: (w0, w1, pay); 
             for (int p = 0; p < BK_PER / 2; ++p) {
                 const int j = 2 * (p * THREADS + (int)threadIdx.x);
                 uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-                if (j + 1 < n) __builtin_memcpy(&rr, rec + 2 * (uint64_t)(b0 + j), 16);
-                else if (j < n) __builtin_memcpy(&rr.x, rec + 2 * (uint64_t)(b0 + j), 8);
+                if (j + 1 < n) __builtin_memcpy(&rr, rec + 2 * (r0 + j), 16);
+                else if (j < n) __builtin_memcpy(&rr.x, rec + 2 * (r0 + j), 8);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int q = 2 * p + h;
@@ -1832,7 +1868,7 @@ k_bucket_runs(const uint32_t* __restrict__ rec, int stride /* 3: (w0, w1, pay); 
                 const int j = q * THREADS + threadIdx.x;
                 sb[q] = 0; ar[q] = 0; key[q] = 0; pj[q] = 0;
                 if (j < n) {
-                    const uint32_t* r = rec + (uint64_t)(b0 + j) * stride;
+                    const uint32_t* r = rec + (r0 + j) * stride;
                     const uint32_t a = r[0], c = stride == 3 ? r[1] : 0u;
                     pj[q] = r[stride - 1];
                     key[q] = ((uint64_t)a << 32) | c;
@@ -1974,7 +2010,7 @@ k_bucket_big(const uint32_t* __restrict__ rec, int stride, const uint32_t* __res
              const uint64_t* __restrict__ soff /* scratch offset of every listed bucket, in entries */, int pbits,
              uint64_t* __restrict__ kA, uint32_t* __restrict__ pA, uint64_t* __restrict__ kB, uint32_t* __restrict__ pB,
              const uint32_t* __restrict__ blk2g, int blk_shift, uint32_t* __restrict__ gen, uint32_t* __restrict__ rowinfo,
-             compact_map M, int* __restrict__ dup_per_genome, uint32_t inline_lo) {
+             compact_map M, int* __restrict__ dup_per_genome, uint32_t inline_lo, uint32_t cap /* as k_bucket_runs */) {
     __shared__ uint32_t hist[BB_DIGITS][256];
     __shared__ uint32_t gbase[256];
     __shared__ uint32_t wcnt[BB_THREADS / 64][256];
@@ -1984,13 +2020,14 @@ k_bucket_big(const uint32_t* __restrict__ rec, int stride, const uint32_t* __res
     const uint32_t bk = list[blockIdx.x];
     const uint32_t b0 = boff[bk];
     const uint32_t n = boff[bk + 1] - b0;
+    const uint64_t r0 = cap ? (uint64_t)bk * cap : (uint64_t)b0;
     uint64_t* k0 = kA + soff[blockIdx.x]; uint32_t* p0 = pA + soff[blockIdx.x];
     uint64_t* k1 = kB + soff[blockIdx.x]; uint32_t* p1 = pB + soff[blockIdx.x];
     for (int i = threadIdx.x; i < BB_DIGITS * 256; i += BB_THREADS) (&hist[0][0])[i] = 0;
     __syncthreads();
     // copy in + all twelve digit histograms (a histogram does not depend on the order of the entries)
     for (uint32_t i = threadIdx.x; i < n; i += BB_THREADS) {
-        const uint32_t* r = rec + (uint64_t)(b0 + i) * stride;
+        const uint32_t* r = rec + (r0 + i) * stride;
         uint64_t key; uint32_t pos;
         if (stride == 2) { key = r[0]; pos = r[1]; }
         else { key = ((((uint64_t)r[0] << 32) | r[1]) << pbits) >> pbits; pos = r[2]; }
@@ -2110,6 +2147,9 @@ static const struct {
     bool staged2 = !strcmp(pf_switch("VG_LEVEL2_SCATTER"), "staged");
     bool scan_each = !strcmp(pf_switch("VG_SUBSHARD_SCAN"), "each");      // HASH sub-shards: a scan per pass, never the one scan of all
     bool no_inline = !strcmp(pf_switch("VG_ROWPTR_INLINE"), "0");         // every row pointer a plain one (see rowptr_inline_lo)
+    // VG_LEVEL2=counted: never the one-pass level 2; onepass: the default rule; onepass:N: the default rule with N slots per final bucket
+    bool l2_counted = !strcmp(pf_switch("VG_LEVEL2"), "counted");
+    int l2_cap = !strncmp(pf_switch("VG_LEVEL2"), "onepass:", 8) ? atoi(pf_switch("VG_LEVEL2") + 8) : 0;
     int subshards = atoi(pf_switch("VG_SUBSHARDS"));                  // developer experiments
     int placement_trials = atoi(pf_switch("VG_PLACEMENT_TRIALS"));
     double workspace_gb = [] { const char* e = getenv("VG_WORKSPACE_GB"); const double v = e ? atof(e) : 0.0; return v > 0.01 ? v : 8.0; }();
@@ -2446,8 +2486,11 @@ struct kmer_index {
 // k-mers of a shard / fraction (keys, row numbers).  Fills gen[] and rowinfo[] like k_group_runs; false = the
 // input does not suit it (tiny, skewed, a bucket beyond the LDS): the caller takes the general path.
 // The shape of a pass's partition, a function of the source size and the shard alone.
+struct bucket_geometry;
+static uint32_t level2_capacity(const bucket_geometry& G, bool dense, const kmer_args& A, int64_t n_src);
 struct bucket_geometry {
     bool range, big_buckets, narrow, tile32k, short_rec;
+    uint32_t cap2;                                   // > 0: level 2 in one pass, every final bucket with this many slots (level2_capacity)
     int total_bits, B1, B2, levels, bin_lo, nb1g, nb1, nb2, st_tiles, n_slabs; int64_t n_st, nbk;
     lvl2_tab L2;                                     // level-2 units and (dense source, k <= 25 at 2^11 buckets) short level-1 records; pointers set by the stages
 };
@@ -2482,14 +2525,29 @@ static bool bucket_geometry_for(int k, bool dense, const kmer_args& A, int64_t n
         else L2.g_st = (L2.u_st % g_st == 0 && L2.u_st / g_st <= 4) ? (int)g_st : -1;
         if (L2.g_st < 0) { G.short_rec = false; L2.g_st = 0; }
     }
+    G.cap2 = level2_capacity(G, dense, A, n_src);
     return true;
+}
+// Level 2 in one pass (k_part_scatter2_narrow<., true>): slots per final bucket, or 0 = the counted level 2.  The Feistel round
+// makes the keys uniform, so a final bucket of a set without repeats holds m = records / buckets entries with Poisson spread
+// sqrt(m): m + 7 sqrt(m) slots, a multiple of 8 records (64 bytes), are exceeded by one bucket in 10^12.  (m is taken from the
+// positions, the upper bound of the records: the host decides before the device has counted.)  Only for the dense pass over all
+// level-1 buckets of one shard, with both levels, the narrow scatter, at least 256 level-1 buckets (a workgroup per bucket: one
+// round of the CUs) and a grown level-2 block within the budget of a pass: 1.5 records' worth of slots per position.
+static uint32_t level2_capacity(const bucket_geometry& G, bool dense, const kmer_args& A, int64_t n_src) {
+    const bool narrow_scatter = G.short_rec || (G.narrow && G.B2 <= 11 && !g_sw.staged2);
+    if (!dense || G.range || A.n_shards != 1 || G.levels != 2 || G.nb1 < 256 || !narrow_scatter || g_sw.l2_counted) return 0u;
+    const double m = (double)n_src / (double)G.nbk;
+    const uint64_t cap = g_sw.l2_cap > 0 ? (uint64_t)g_sw.l2_cap : ((uint64_t)std::ceil(m + 7.0 * std::sqrt(m)) + 7) & ~7ULL;
+    const bool fits = (uint64_t)G.nbk * cap <= (uint64_t)n_src + (uint64_t)n_src / 2 && (uint64_t)G.nb2 * cap < (1ULL << 31);
+    return fits ? (uint32_t)cap : 0u;
 }
 // One run of the pipeline: what the stages below share.  The buffers are members in the order the stages allocate them.
 struct bucket_run {
     vg_genomes* g; int k; bool dense; const pass_inputs& in; kmer_index& ix; int* d_kept; hipStream_t s;
     bucket_geometry G; part_src S; compact_map cmap;
     bool k25 = false; uint32_t n1 = 0; size_t n_cap = 0;      // the default (kernels with k as a constant); records of this pass; capacity its record buffers are sized for
-    const uint32_t* f_rec = nullptr; int f_stride = 3;        // the records the bucket kernels read
+    const uint32_t* f_rec = nullptr; int f_stride = 3; uint32_t f_cap = 0;      // the records the bucket kernels read; > 0: bucket bk's start at bk * f_cap, not at boff[bk]
     dbuf<uint32_t> T1s, slab, d_off1, a_rec, b_rec;           // T1s: counts [super-tile][bucket], scanned in place
     // (whatever way the run is left: everything that touches the row pointers' own block later is queued on s behind its clear)
     struct ev_guard { hipEvent_t e = nullptr; hipStream_t st; ~ev_guard() { if (e) { (void)hipStreamWaitEvent(st, e, 0); (void)hipEventDestroy(e); } } } rows_zero;
@@ -2604,8 +2662,8 @@ static void level1_scatter(bucket_run& R) {
 }
 // Level 2 on units of u_st super-tiles of one level-1 bucket (see lvl2_tab): everything it needs is in the scanned level-1
 // table, so it is launched right behind level 1.  Leaves the final records in b_rec and hands a_rec on as the arena.
-static void level2(bucket_run& R) {
-    const bucket_geometry& G = R.G; const lvl2_tab& L2 = G.L2; hipStream_t s = R.s; kmer_index& ix = R.ix;
+static void level2_counted(bucket_run& R) {
+    const bucket_geometry& G = R.G; const lvl2_tab& L2 = G.L2; hipStream_t s = R.s;
     const int64_t n_units = (int64_t)G.nb1 * L2.n_u;
     const size_t t2n = (size_t)G.nb1 * (size_t)G.nb2 * (size_t)L2.n_u;
     dbuf<uint32_t> T2s(t2n);                              // counts [bucket][unit][b2], scanned in place
@@ -2615,11 +2673,11 @@ static void level2(bucket_run& R) {
         const int grid_c2 = (int)std::min<int64_t>(n_units, 512);
         hipLaunchKernelGGL(G.short_rec ? k_part_count2<true> : k_part_count2<false>, dim3(grid_c2), dim3(PT_THREADS), 0, s, a_rec, G.B1, G.B2, n_units, L2, T2s.p);
         hipLaunchKernelGGL(k_scan_units, dim3(G.nb1), dim3(PT_THREADS), 0, s, T2s.p, L2.n_u, G.nb2, (const uint32_t*)R.d_off1.p, G.nb1, R.boff.p);
-        R.b_rec.alloc((G.narrow ? 2 : 3) * R.n_cap + 8);
+        if (!R.b_rec.p) R.b_rec.alloc((G.narrow ? 2 : 3) * R.n_cap + 8);
         const int grid_s2 = (int)std::min<int64_t>(n_units, 256);
         if (G.short_rec || (G.narrow && G.B2 <= 11 && !g_sw.staged2))
-            hipLaunchKernelGGL(G.short_rec ? k_part_scatter2_narrow<true> : k_part_scatter2_narrow<false>, dim3(grid_s2), dim3(PT_THREADS), 0, s, a_rec, G.B1, G.B2, n_units,
-                               (const uint32_t*)T2s.p, L2, R.b_rec.p, G.total_bits);
+            hipLaunchKernelGGL((G.short_rec ? k_part_scatter2_narrow<true, false> : k_part_scatter2_narrow<false, false>), dim3(grid_s2), dim3(PT_THREADS), 0, s, a_rec, G.B1, G.B2, n_units,
+                               (const uint32_t*)T2s.p, L2, R.b_rec.p, G.total_bits, 0u, nullptr, nullptr);
         else {
             part_src S2; memset(&S2, 0, sizeof S2);
             S2.rec = a_rec; S2.n = (int64_t)R.n1; S2.k2 = 2 * R.k;
@@ -2627,10 +2685,40 @@ static void level2(bucket_run& R) {
                                (const uint32_t*)T2s.p, L2, R.b_rec.p, G.narrow ? G.total_bits : -1, 0);
         }
     }
-    VG_HIP(hipStreamSynchronize(s));                       // the tables and level-1 records go out of scope below
+    VG_HIP(hipStreamSynchronize(s));                       // the tables go out of scope
+}
+// Level 2 without a count pass (bucket_geometry::cap2): the scatter counts as it writes, a scan of its 2^(B1 + B2) sizes gives boff.
+// false = a final bucket outgrew its slots (a k-mer in more genomes than the slack): nothing of the result is used.
+static bool level2_one_pass(bucket_run& R) {
+    const bucket_geometry& G = R.G; const lvl2_tab& L2 = G.L2; hipStream_t s = R.s;
+    const int64_t n_units = (int64_t)G.nb1 * L2.n_u;
+    // (large enough for the counted layout too: an overflowing pass scatters again into the same block)
+    R.b_rec.alloc(2 * std::max((size_t)G.nbk * G.cap2, R.n_cap) + 8);
+    dbuf<uint32_t> stat(2); stat.zero(s);                 // [0] a bucket overflowed, [1] the largest final bucket
+    uint32_t h_stat[2] = {0, 0};
+    {
+        vg_prof_scope ps("kmer_partition2", (double)R.n1 * ((G.short_rec ? 8.0 : 12.0) + 8.0));
+        hipLaunchKernelGGL((G.short_rec ? k_part_scatter2_narrow<true, true> : k_part_scatter2_narrow<false, true>), dim3((unsigned)std::min(G.nb1, 256)), dim3(PT_THREADS), 0, s,
+                           (const uint32_t*)R.a_rec.p, G.B1, G.B2, n_units, nullptr, L2, R.b_rec.p, G.total_bits, G.cap2, R.boff.p, stat.p);
+        // sizes -> starts, in place, with the end behind the last bucket
+        VG_HIP(hipMemsetAsync(R.boff.p + G.nbk, 0, sizeof(uint32_t), s));
+        with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, R.boff.p, R.boff.p, 0u, (size_t)G.nbk + 1, rocprim::plus<uint32_t>(), s); });
+    }
+    stat.download(h_stat, 2, s);
+    VG_HIP(hipStreamSynchronize(s));
+    char mark[96];
+    snprintf(mark, sizeof mark, h_stat[0] ? "level2: one pass overflowed, counted (%u slots)" : "level2: one pass (largest bucket %u of %u slots)", h_stat[0] ? G.cap2 : h_stat[1], G.cap2);
+    vg_host_mark(mark);
+    return h_stat[0] == 0;
+}
+static void level2(bucket_run& R) {
+    const bucket_geometry& G = R.G; kmer_index& ix = R.ix;
+    uint32_t cap = G.cap2;
+    if (cap && !level2_one_pass(R)) cap = 0;
+    if (!cap) level2_counted(R);
     vg_host_mark("buckets: level 2 done");
     vg_deferred_start();                                  // (the bucket kernel and the SpGEMM are the long waits of the call)
-    R.f_rec = R.b_rec.p; R.f_stride = G.narrow ? 2 : 3;
+    R.f_rec = R.b_rec.p; R.f_stride = G.narrow ? 2 : 3; R.f_cap = cap;
     ix.arena = std::move(R.a_rec);
     if (!R.rows_zero.e) ix.rowinfo.view(ix.arena.p, (size_t)ix.n_rows_info);
     ix.gen.view(ix.arena.p + (((size_t)ix.n_rows_info + 3) & ~(size_t)3), (size_t)R.n1 + 4);
@@ -2653,7 +2741,7 @@ static void bucket_kernels(bucket_run& R) {
     const uint32_t* boff = R.boff.p; const uint32_t* blk2g = g->d_blk2g.p;
     unsigned int n_over[2] = {0, 0};
     auto runs = [&](auto kern, int threads, int grid, int64_t count, const uint32_t* list, uint32_t* over, unsigned int* nover) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, R.f_rec, R.f_stride, boff, count, pb, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, list, over, nover, ix.inline_lo);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, R.f_rec, R.f_stride, boff, count, pb, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, list, over, nover, ix.inline_lo, R.f_cap);
     };
     const auto wide = G.narrow ? k_bucket_runs<true, 1024, 11> : k_bucket_runs<false, 1024, 11>;
     {
@@ -2687,7 +2775,7 @@ static void bucket_kernels(bucket_run& R) {
     {
         vg_prof_scope ps("bucket_big", (double)tot * 12.0 * 2.0);
         hipLaunchKernelGGL(k_bucket_big, dim3(n_big), dim3(BB_THREADS), 0, s, R.f_rec, R.f_stride, boff, big_list,
-                           (const uint64_t*)d_so.p, pb, kA.p, pA.p, kB.p, pB.p, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, ix.inline_lo);
+                           (const uint64_t*)d_so.p, pb, kA.p, pA.p, kB.p, pB.p, blk2g, g->align_shift, ix.gen.p, ix.rowinfo.p, R.cmap, ix.d_dups.p, ix.inline_lo, R.f_cap);
     }
     VG_HIP(hipStreamSynchronize(s));
 }
@@ -3387,22 +3475,23 @@ extern "C" void vg_set_subshards(int n) { g_force_subshards = n; }
 extern "C" void vg_set_range_scan(int mode) { g_range_scan_mode = mode == 1 ? 1 : 0; }
 
 // ---- vg_kmer_geometry: what bucket_geometry_for decides for a pass, asked on the host (tests, tooling)
-static void report_geometry(int k, bool dense, const kmer_args& A, int64_t P, vg_kmer_geometry_info* info) {
+static void report_geometry(int k, bool dense, const kmer_args& A, int64_t P, vg_kmer_geometry_info* info, int* level2_slots = nullptr) {
     bucket_geometry G;
+    if (level2_slots) *level2_slots = 0;
     info->accepted = dense ? (bucket_geometry_for(k, true, A, P, G) ? 1 : 0) : -1;
     if (info->accepted != 1) return;
     info->levels = G.levels; info->total_bits = G.total_bits; info->B1 = G.B1; info->B2 = G.B2;
     info->st_tiles = G.st_tiles; info->n_st = G.n_st; info->u_st = G.L2.u_st; info->g_st = G.L2.g_st;
+    if (level2_slots) *level2_slots = (int)G.cap2;
     info->tile32k = G.tile32k; info->narrow = G.narrow; info->short_rec = G.short_rec;
 }
-extern "C" int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info) {
-    VG_API_BEGIN
-    if (!g || !info) throw vg_error(VG_EINVAL, "vg_kmer_geometry: null argument");
-    check_kmer_args(k, fraction, shard, n_shards);
+// the geometry of the first pass of vg_kmer_shared(g, k, fraction, shard, n_shards, ...) and the slots of its level 2 (0: counted)
+static void first_pass_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info, int* level2_slots) {
     memset(info, 0, sizeof *info);
+    if (level2_slots) *level2_slots = 0;
     const int64_t P = g->padded_total();
     info->P = P; info->n_passes = 1;
-    if (g->n == 0) return VG_OK;
+    if (g->n == 0) return;
     // the first pass of the call, as vg_kmer_shared cuts it (kmer_shared_subshards: sub-shard 0 of shard * sub .. of n_shards * sub;
     // the one scan of HASH sub-shards hands every pass a mask)
     const shard_plan plan = plan_shards(g, fraction, n_shards, /*host_entry=*/true);
@@ -3410,7 +3499,21 @@ extern "C" int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int
     const int sh = shard * plan.sub, ns = n_shards * plan.sub;
     const bool masked = subshards_share_scan(g, fraction, n_shards, plan.sub);
     const bool dense = pass_source_dense(P, fraction, ns, masked);
-    report_geometry(k, dense, shard_kmer_args(P, g->align_shift, k, 1.0, sh, ns), P, info);
+    report_geometry(k, dense, shard_kmer_args(P, g->align_shift, k, 1.0, sh, ns), P, info, level2_slots);
+}
+extern "C" int vg_kmer_geometry(const vg_genomes* g, int k, double fraction, int shard, int n_shards, vg_kmer_geometry_info* info) {
+    VG_API_BEGIN
+    if (!g || !info) throw vg_error(VG_EINVAL, "vg_kmer_geometry: null argument");
+    check_kmer_args(k, fraction, shard, n_shards);
+    first_pass_geometry(g, k, fraction, shard, n_shards, info, nullptr);
+    VG_API_END
+}
+extern "C" int vg_kmer_level2_slots(const vg_genomes* g, int k, double fraction, int shard, int n_shards, int* slots) {
+    VG_API_BEGIN
+    if (!g || !slots) throw vg_error(VG_EINVAL, "vg_kmer_level2_slots: null argument");
+    check_kmer_args(k, fraction, shard, n_shards);
+    vg_kmer_geometry_info info;
+    first_pass_geometry(g, k, fraction, shard, n_shards, &info, slots);
     VG_API_END
 }
 extern "C" int vg_kmer_geometry_at(int64_t padded_positions, int k, vg_kmer_geometry_info* info) {
