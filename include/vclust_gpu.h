@@ -596,6 +596,51 @@ int vg_cluster_mcl(const char* ani_path, const char* ids_path, const char* out_p
  * tiny graphs there. */
 void vg_cluster_mcl_set_table_slots(int slots);
 
+/* ------------------------------------------------------------------ coverage ---------- */
+/* Coverage map (this repository's definition; DESIGN.md section 14 is the contract, tests/cover_restatement.py its sequential
+ * statement).  n objects with lengths len[i]; optionally a group label[i] in [0, n_groups) per object (NULL: one group).  A row
+ * (q, r, qstart, qend) says that the positions qstart..qend (0-based, inclusive) of object q are aligned to partner r; only the
+ * query side counts and a row with q == r is ignored.  C(i, r) is the union of the rows (i, r, ..); depth_in(x) / depth_out(x) of
+ * object i count the partners r of i's group / of another group with x in C(i, r).  The segments of an object with len > 0 are the
+ * maximal runs on which (depth_in, depth_out) is constant: disjoint, covering 0..len-1, ordered by (object, start); an object
+ * without rows has the one segment (0, len-1, 0, 0).  The result depends on the set of rows only. */
+typedef struct {
+    int64_t len;
+    int64_t partners_in, partners_out;              /* distinct partners with a row, of the object's group / of another */
+    int64_t covered, covered_in, covered_out;       /* positions with depth_in + depth_out >= 1, depth_in >= 1, depth_out >= 1 */
+    int64_t core;               /* positions with depth_in == (members of the group) - 1; 0 for a group of one */
+    int64_t sum_in, sum_out;    /* the depths summed over the positions = |C(i, r)| summed over the partners */
+    int64_t max_depth;          /* the largest depth_in + depth_out */
+    int64_t segments;           /* the object's segments */
+} vg_cover_stat;
+typedef struct { int32_t object, start, end, depth_in, depth_out; } vg_cover_segment;   /* 0-based inclusive */
+typedef struct {
+    int64_t rows_kept;          /* rows with q != r */
+    int64_t intervals;          /* maximal intervals of all C(i, r) (rows that overlap or touch are one) */
+    int64_t breakpoints;        /* distinct (object, position) at which an interval starts or has just ended */
+    int64_t segments;
+} vg_cover_run_stats;
+/* out[n_objects].  segments / n_segments: both NULL (no profile) or both given; *segments is released with vg_free.  Checked on
+ * the host before any device use, VG_EINVAL naming the row or object: an index >= n_objects, qstart < 0, qstart > qend,
+ * qend >= len[q], a negative length or one >= 2^31, a label outside [0, n_groups), only one of segments / n_segments.
+ * n_objects >= 2^31 or n_rows >= 2^32 is VG_EOVERFLOW; n_objects == 0 is VG_OK without a device; no device VG_ENODEV (no host
+ * fallback).  st may be NULL. */
+int vg_cover_rows(int64_t n_objects, const int64_t* len, const int32_t* label, int64_t n_groups,
+                  const uint32_t* q, const uint32_t* r, const int32_t* qstart, const int32_t* qend, int64_t n_rows,
+                  vg_cover_stat* out, vg_cover_segment** segments, int64_t* n_segments, vg_cover_run_stats* st);
+/* File to file.  ids_path: the ids file of vg_align (columns `id` first and `seq_len`, found by header name).  aln_path: the table
+ * vg_align writes with out_aln_path; the columns query, reference, qstart, qend are found by header name and hold 1-based inclusive
+ * positions; names are matched to the ids file.  clusters_path (may be NULL: one group): read as by vg_cluster_stats_file; column
+ * (NULL: the first) names the label column that gives the groups.  An unknown name, a missing column, a malformed number, a range
+ * outside 1..seq_len or an unknown label column is VG_EINVAL `<file>:<line>: ...`, before any device use.  out_path: tab-separated,
+ * one line per object in ids-file order, header `id len group group_size partners_in partners_out covered covered_in covered_out
+ * core max_depth mean_depth covered_frac core_frac`; group is the label text of clusters_path (`-` without one); the quotients
+ * (sum_in + sum_out) / len, covered / len and core / len are printed %.6g, `-` when len == 0, and core_frac also when
+ * group_size < 2.  segments_path (may be NULL): header `id start end depth_in depth_out`, positions 1-based inclusive, in segment
+ * order.  The bytes do not depend on num_threads.  verbosity >= 1: one summary line on stderr. */
+int vg_cover_file(const char* aln_path, const char* ids_path, const char* clusters_path, int clusters_is_repr,
+                  const char* column, const char* out_path, const char* segments_path, int num_threads, int verbosity);
+
 /* ------------------------------------------------------------------ dereplicate ------- */
 /* Greedy incremental clustering against representatives only (this repository's command; no reference call site; DESIGN.md
  * section 13 is the contract).  Objects are the genomes in align order (vg_align_order; rank = object index, as in ani.ids.tsv).

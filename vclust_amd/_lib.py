@@ -122,6 +122,21 @@ class ClusterStat(C.Structure):
                 ('nearest_sum', C.c_uint64), ('misfits', C.c_int64)]
 
 
+class CoverStat(C.Structure):
+    """vg_cover_stat: the record of one object in the coverage map"""
+    _fields_ = [(name, C.c_int64) for name in ('len', 'partners_in', 'partners_out', 'covered', 'covered_in', 'covered_out', 'core',
+                                                'sum_in', 'sum_out', 'max_depth', 'segments')]
+
+
+class CoverSegment(C.Structure):
+    """vg_cover_segment: a maximal run of constant (depth_in, depth_out), positions 0-based inclusive"""
+    _fields_ = [(name, C.c_int32) for name in ('object', 'start', 'end', 'depth_in', 'depth_out')]
+
+
+class CoverRunStats(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ('rows_kept', 'intervals', 'breakpoints', 'segments')]
+
+
 class LinkageStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('n_edges', C.c_int64), ('n_merges', C.c_int64)]
 
@@ -315,6 +330,9 @@ SYMBOLS = {
                                        P(P(C.c_int64)), P(P(C.c_int32)), P(P(C.c_uint32)), P(MclStats)]),
     'vg_cluster_mcl': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, P(ClusterParams), P(MclParams), P(MclStats)]),
     'vg_cluster_mcl_set_table_slots': (None, [C.c_int]),
+    'vg_cover_rows': (C.c_int, [C.c_int64, P(C.c_int64), P(C.c_int32), C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_int32), P(C.c_int32), C.c_int64,
+                                P(CoverStat), P(P(CoverSegment)), P(C.c_int64), P(CoverRunStats)]),
+    'vg_cover_file': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     'vg_dereplicate_set': (C.c_int, [C.c_void_p, P(DerepParams), P(C.c_int32), P(C.c_int32), P(P(Task)), P(P(PairStat)), P(C.c_int64),
                                      P(DerepStats)]),
     'vg_dereplicate': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(DerepFileParams)]),

@@ -10,10 +10,10 @@ import numpy as np
 
 from . import _lib
 from ._lib import (ALIGN_FIELDS, ALIGN_OUTFMT, CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, ClusterStat, ClusterStats,  # noqa: F401
-                   ClusterUpdateStats, DedupStats, DerepStats, DerepUpdateStats, KernelTime, LinkageStats, MclParams, MclStats, PairCount,
+                   ClusterUpdateStats, CoverRunStats, CoverSegment, CoverStat, DedupStats, DerepStats, DerepUpdateStats, KernelTime, LinkageStats, MclParams, MclStats, PairCount,
                    PairStat, Region, Task, as_dict, check, lz_params, path, path_array, ptr)
 # the whole-stage calls (vclust_amd/stages.py: no numpy)
-from .stages import (DEFAULT_LZ, align, align_params, cluster, cluster_stats, deduplicate as deduplicate_files, derep_params, dereplicate,  # noqa: F401
+from .stages import (DEFAULT_LZ, align, align_params, cluster, cluster_stats, cover, deduplicate as deduplicate_files, derep_params, dereplicate,  # noqa: F401
                      prefilter)
 
 
@@ -24,6 +24,7 @@ def _dtype(ctype):
 
 
 PAIR_DTYPE, TASK_DTYPE, STAT_DTYPE, REGION_DTYPE, CLUSTER_STAT_DTYPE = (_dtype(t) for t in (PairCount, Task, PairStat, Region, ClusterStat))
+COVER_STAT_DTYPE, COVER_SEGMENT_DTYPE = _dtype(CoverStat), _dtype(CoverSegment)
 LINKAGE_DTYPE = np.dtype([('node_a', '<i8'), ('node_b', '<i8'), ('similarity', '<f8'), ('size', '<i8'), ('object_a', '<i4'),
                           ('object_b', '<i4')])
 AVERAGE_LINKAGE_DTYPE = np.dtype(LINKAGE_DTYPE.descr + [('sum', '<u8'), ('pairs', '<u8')])
@@ -393,6 +394,37 @@ def cluster_stats_graph(n_objects, q, r, w, label, n_clusters=None):
     own, oth, lab = _filled(n, (C.c_uint64, C.c_uint64, C.c_int32), lambda *per_object: check(_lib.load().vg_cluster_stats_graph(
         n, *rows, ptr(label, C.c_int32), k, ptr(out, ClusterStat), *per_object)), guard=True)
     return out[:k], own, oth, lab
+
+
+def cover_rows(lengths, q, r, qstart, qend, label=None, n_groups=None, segments=True):
+    """The coverage map of the rows (q[i], r[i], qstart[i], qend[i]) -- positions qstart..qend (0-based, inclusive) of object q are
+    aligned to partner r -- over objects of the given lengths (vg_cover_rows).  label[i] in [0, n_groups):
+    the groups that split the depth into `in` and `out` (default: one group; n_groups: default max(label) + 1).  ->
+    (records COVER_STAT_DTYPE[n], segments COVER_SEGMENT_DTYPE[...] or None with segments=False, run_stats dict)."""
+    lp, n = _input(lengths, C.c_int64)
+    (qp, nq), (rp, nr), (sp, ns), (ep, ne) = _input(q, C.c_uint32), _input(r, C.c_uint32), _input(qstart, C.c_int32), _input(qend, C.c_int32)
+    if not nq == nr == ns == ne:
+        raise ValueError('q, r, qstart and qend must have the same length')
+    gp, k = None, 0
+    if label is not None:
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if len(label) != n:
+            raise ValueError('label must have one entry per object')
+        gp, k = ptr(label, C.c_int32), int(n_groups) if n_groups is not None else (int(label.max()) + 1 if n else 1)
+    elif n_groups is not None:
+        raise ValueError('n_groups needs label')
+    seg, n_seg, st = C.POINTER(CoverSegment)(), C.c_int64(), CoverRunStats()
+    records, = _filled(n, (CoverStat,), lambda out: check(_lib.load().vg_cover_rows(
+        n, lp, gp, k, qp, rp, sp, ep, nq, out, C.byref(seg) if segments else None, C.byref(n_seg) if segments else None, C.byref(st))))
+    return records, _take(seg, n_seg.value, COVER_SEGMENT_DTYPE) if segments else None, as_dict(st)
+
+
+def cover_regions(genomes, tasks, regions, label=None):
+    """The coverage map of a run without any file: `tasks` (TASK_DTYPE) and `regions` (REGION_DTYPE) as GenomeSet.lz_align takes
+    and returns them over the GenomeSet `genomes`; a region is a row (q, r) of its task with its qstart, qend.  -> as cover_rows."""
+    tasks, regions = np.asarray(tasks), np.asarray(regions)
+    t = regions['task']
+    return cover_rows(genomes.lengths(), tasks['q'][t], tasks['r'][t], regions['qstart'], regions['qend'], label=label)
 
 
 def _rows(q, r, w):

@@ -238,7 +238,8 @@ void vg_fasta_write_records(const char* path, const vg_fasta_text& text, const s
 void vg_fasta_write_kept(const char* path, const vg_fasta_text& in, const std::vector<std::string>& prefix, const int32_t* rep, int level, int n_threads);
 // cluster stage (vg_io.cpp): the first column of the ids file; the passing rows of ani.tsv (VG_EINVAL with file:line on a
 // missing column, an index outside the ids file or a malformed number); clusters.tsv
-void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids);
+// (seq_len, if given: also the column of that header name, one non-negative integer below 2^31 per id; VG_EINVAL with file:line)
+void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids, std::vector<int64_t>* seq_len = nullptr);
 void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
                           std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<double>& w);
 void vg_cluster_write(const char* path, const std::vector<std::string>& ids, const int32_t* label, const int32_t* rep, bool representatives);
@@ -258,6 +259,15 @@ void vg_cluster_stats_run(const char* fn, int64_t n, const uint32_t* q, const ui
 // the report file (vg_io.cpp): one block per column, one line per cluster in the order of the records (by earliest member)
 void vg_cluster_stats_write(const char* path, const char* metric, const std::vector<std::string>& ids, const vg_label_columns& cols,
                             const std::vector<std::vector<vg_cluster_stat>>& stats);
+// coverage stage (vg_io.cpp).  The alignment table against the ids: the columns query, reference, qstart, qend by header name, names
+// matched to ids, positions 1-based inclusive in the file and 0-based in the arrays; VG_EINVAL with file:line on a missing column,
+// an unknown name, a malformed number or a range outside 1..len.  The rows are in file order whatever n_threads is.
+void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, const std::vector<int64_t>& len, int n_threads,
+                        std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<int32_t>& qs, std::vector<int32_t>& qe);
+// the per-object summary (group / group_text null: one group, printed `-`; group_size per group) and the depth profile
+void vg_cover_write(const char* path, const std::vector<std::string>& ids, const int32_t* group, const std::vector<std::string>* group_text,
+                    const std::vector<int64_t>& group_size, const vg_cover_stat* stats, int n_threads);
+void vg_cover_write_segments(const char* path, const std::vector<std::string>& ids, const vg_cover_segment* seg, int64_t n_segments, int n_threads);
 // merge table (vg_cluster.hip): the forest edges of the rows in merge order (a < b, weights non-increasing) -- checks the rows
 // (errors name fn), then the device; the node numbering of the table and the labels of a cut are host loops over those records.
 // algorithm: VG_CLUSTER_SINGLE (the maximum spanning forest), VG_CLUSTER_COMPLETE (the worst edge of every complete-linkage merge)

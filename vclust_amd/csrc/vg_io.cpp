@@ -666,12 +666,29 @@ bool parse_double(const char* a, const char* b, double& v) {
 }
 }  // namespace
 
-void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids) {
+void vg_cluster_read_ids(const char* path, std::vector<std::string>& ids, std::vector<int64_t>* seq_len) {
     const text_file f(path);
     ids.clear();
+    if (seq_len) seq_len->clear();
+    std::vector<std::string_view> fields;
+    size_t len_col = 0;
     for_each_line(f, [&](int64_t line, std::string_view text) {
         if (line > 1 && !text.empty()) ids.emplace_back(text.substr(0, text.find('\t')));       // (line 1: the header)
+        if (!seq_len || (line > 1 && text.empty())) return;
+        split_fields(text, '\t', fields);
+        if (line == 1) {
+            len_col = (size_t)(std::find(fields.begin(), fields.end(), std::string_view("seq_len")) - fields.begin());
+            if (len_col == fields.size()) row_error(path, 1, "missing column seq_len");
+            return;
+        }
+        if (fields.size() <= len_col) row_error(path, line, "expected at least " + std::to_string(len_col + 1) + " columns, found " + std::to_string(fields.size()));
+        const std::string_view v = fields[len_col];
+        uint64_t x = 0;
+        const auto rr = std::from_chars(v.data(), v.data() + v.size(), x);
+        if (rr.ec != std::errc() || rr.ptr != v.data() + v.size() || x >= (1ull << 31)) row_error(path, line, "malformed seq_len '" + std::string(v) + "'");
+        seq_len->push_back((int64_t)x);
     });
+    if (seq_len && !f.n) row_error(path, 1, "empty file (no header)");
 }
 
 void vg_cluster_read_rows(const char* path, int64_t n_objects, const vg_cluster_params* p,
@@ -948,4 +965,110 @@ void vg_linkage_write(const char* path, const vg_forest& f, const int64_t* node_
         o += buf;
     }
     vg_write_file(path, { o });
+}
+
+// ---------------------------------------------------------------- coverage stage: the alignment table, the two output files
+void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, const std::vector<int64_t>& len, int n_threads,
+                        std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<int32_t>& qs, std::vector<int32_t>& qe) {
+    const text_file f(path);
+    if (!f.n) row_error(path, 1, "empty file (no header)");
+    const char* end = f.end();
+    const char* hdr_end = f.line_end(f.p);
+    std::vector<std::string_view> names;
+    split_fields(std::string_view(f.p, (size_t)((hdr_end > f.p && hdr_end[-1] == '\r' ? hdr_end - 1 : hdr_end) - f.p)), '\t', names);
+    // columns: 0 query, 1 reference, 2 qstart, 3 qend
+    const char* const wanted[4] = { "query", "reference", "qstart", "qend" };
+    size_t col[4];
+    for (int k = 0; k < 4; ++k) {
+        col[k] = (size_t)(std::find(names.begin(), names.end(), std::string_view(wanted[k])) - names.begin());
+        if (col[k] == names.size()) row_error(path, 1, std::string("missing column ") + wanted[k]);
+    }
+    const size_t max_col = *std::max_element(col, col + 4);
+    std::unordered_map<std::string_view, uint32_t> index;
+    index.reserve(ids.size() * 2);
+    for (size_t i = 0; i < ids.size(); ++i) index.emplace(ids[i], (uint32_t)i);
+
+    // the body cut into chunks at line starts, one per thread; each chunk keeps its rows and its first error
+    const char* body = hdr_end < end ? hdr_end + 1 : end;
+    const int nthr = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads > 0 ? n_threads : vg_host_threads(), (int64_t)((end - body) >> 20) + 1));
+    std::vector<const char*> cut((size_t)nthr + 1, end);
+    cut[0] = body;
+    for (int t = 1; t < nthr; ++t) {
+        const char* x = std::max(body + (end - body) * t / nthr, cut[(size_t)t - 1]);
+        cut[(size_t)t] = x < end ? std::min(end, f.line_end(x) + 1) : end;
+    }
+    struct part { std::vector<uint32_t> q, r; std::vector<int32_t> qs, qe; const char* err_at = nullptr; std::string err; };
+    std::vector<part> parts((size_t)nthr);
+    vg_parallel_for(nthr, nthr, [&](int64_t t) {
+        part& pt = parts[(size_t)t];
+        std::vector<std::string_view> fields;
+        for (const char* a = cut[(size_t)t]; a < cut[(size_t)t + 1];) {
+            const char* e = f.line_end(a);
+            const std::string_view text(a, (size_t)((e > a && e[-1] == '\r' ? e - 1 : e) - a));
+            if (text.empty()) { a = e + 1; continue; }          // (blank line)
+            split_fields(text, '\t', fields);
+            if (fields.size() <= max_col) { pt.err_at = a; pt.err = "expected " + std::to_string(names.size()) + " columns, found " + std::to_string(fields.size()); return; }
+            uint32_t obj[2];
+            for (int k = 0; k < 2; ++k) {
+                const auto it = index.find(fields[col[k]]);
+                if (it == index.end()) { pt.err_at = a; pt.err = std::string(wanted[k]) + " '" + std::string(fields[col[k]]) + "' is not in the ids file"; return; }
+                obj[k] = it->second;
+            }
+            uint64_t pos[2];
+            for (int k = 0; k < 2; ++k) {
+                const std::string_view v = fields[col[2 + k]];
+                const auto rr = std::from_chars(v.data(), v.data() + v.size(), pos[k]);
+                if (rr.ec != std::errc() || rr.ptr != v.data() + v.size()) { pt.err_at = a; pt.err = std::string("malformed ") + wanted[2 + k] + " '" + std::string(v) + "'"; return; }
+            }
+            if (pos[0] < 1 || pos[0] > pos[1] || pos[1] > (uint64_t)len[obj[0]]) {
+                pt.err_at = a;
+                pt.err = "qstart..qend " + std::to_string(pos[0]) + ".." + std::to_string(pos[1]) + " is not a range inside 1.." + std::to_string(len[obj[0]]);
+                return;
+            }
+            pt.q.push_back(obj[0]); pt.r.push_back(obj[1]); pt.qs.push_back((int32_t)(pos[0] - 1)); pt.qe.push_back((int32_t)(pos[1] - 1));
+            a = e + 1;
+        }
+    });
+    for (auto& pt : parts) if (pt.err_at) row_error(path, f.line_of(pt.err_at), pt.err);
+    q.clear(); r.clear(); qs.clear(); qe.clear();
+    for (auto& pt : parts) {
+        q.insert(q.end(), pt.q.begin(), pt.q.end()); r.insert(r.end(), pt.r.begin(), pt.r.end());
+        qs.insert(qs.end(), pt.qs.begin(), pt.qs.end()); qe.insert(qe.end(), pt.qe.begin(), pt.qe.end());
+    }
+}
+
+void vg_cover_write(const char* path, const std::vector<std::string>& ids, const int32_t* group, const std::vector<std::string>* group_text,
+                    const std::vector<int64_t>& group_size, const vg_cover_stat* stats, int n_threads) {
+    const std::string head = "id\tlen\tgroup\tgroup_size\tpartners_in\tpartners_out\tcovered\tcovered_in\tcovered_out\tcore\tmax_depth\tmean_depth\tcovered_frac\tcore_frac\n";
+    write_rows(path, head, (int64_t)ids.size(), 1 << 14, n_threads, [&](int64_t lo, int64_t hi, std::string& o) {
+        char buf[64];
+        auto num = [&](int64_t v) { o.push_back('\t'); o += std::to_string(v); };
+        auto quotient = [&](bool have, int64_t a, int64_t b) {
+            o.push_back('\t');
+            if (!have) { o.push_back('-'); return; }
+            snprintf(buf, sizeof buf, "%.6g", (double)a / (double)b);
+            o += buf;
+        };
+        for (int64_t i = lo; i < hi; ++i) {
+            const vg_cover_stat& s = stats[i];
+            const int64_t members = group_size[(size_t)(group ? group[i] : 0)];
+            o += ids[(size_t)i];
+            num(s.len);
+            o.push_back('\t'); o += group_text ? (*group_text)[(size_t)group[i]] : std::string("-");
+            num(members); num(s.partners_in); num(s.partners_out); num(s.covered); num(s.covered_in); num(s.covered_out); num(s.core); num(s.max_depth);
+            quotient(s.len > 0, s.sum_in + s.sum_out, s.len); quotient(s.len > 0, s.covered, s.len); quotient(s.len > 0 && members >= 2, s.core, s.len);
+            o.push_back('\n');
+        }
+    });
+}
+
+void vg_cover_write_segments(const char* path, const std::vector<std::string>& ids, const vg_cover_segment* seg, int64_t n_segments, int n_threads) {
+    write_rows(path, "id\tstart\tend\tdepth_in\tdepth_out\n", n_segments, 1 << 16, n_threads, [&](int64_t lo, int64_t hi, std::string& o) {
+        char buf[64];
+        for (int64_t k = lo; k < hi; ++k) {
+            o += ids[(size_t)seg[k].object];
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%d\t%d\n", (long long)seg[k].start + 1, (long long)seg[k].end + 1, (int)seg[k].depth_in, (int)seg[k].depth_out);
+            o += buf;
+        }
+    });
 }
