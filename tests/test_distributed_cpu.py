@@ -49,6 +49,14 @@ try:
     D.prefilter_counts(gs, comm, 25, 1.0, min_shared=20); res["sliced_rc"] = 0
 except _lib.VclustGpuError as e:
     res["sliced_rc"] = e.code; res["sliced_msg"] = str(e)
+# the align stage from made-up candidate pairs (it is never reached: no device): EVERY rank that failed says why, not
+# only the first failed one
+small = api.GenomeSet.from_codes(rng.integers(0, 4, 40 * 500).astype(np.uint8), np.arange(41, dtype=np.int64) * 500, None)
+cand = np.zeros(30, dtype=api.PAIR_DTYPE); cand["a"] = np.arange(1, 31); cand["b"] = np.arange(30) // 2; cand["shared"] = 100
+try:
+    D.align_pairs(small, cand, comm); res["pairs_rc"] = 0
+except _lib.VclustGpuError as e:
+    res["pairs_rc"] = e.code; res["pairs_msg"] = str(e)
 res["comm"] = comm.describe()
 # the strict form of the built-in RCCL communicator: no device here, so creation fails on every rank and every rank raises
 try:
@@ -80,6 +88,10 @@ def test_two_ranks_comm_and_failure_agreement(tmp_path, golden_dir):
         assert got[r]['selftest']
         assert got[r]['ingest_rc'] != 0 and 'rank 1 failed' in got[r]['ingest_msg']     # the same verdict on both ranks
         assert got[r]['nodev_rc'] == -3 and 'no HIP device' in got[r]['nodev_msg'] or got[r]['nodev_rc'] != 0
+        # one rule for the text of every agreement: the first failed rank is named, and a rank that failed itself says why
+        assert 'rank 0 failed' in got[r]['nodev_msg'] and 'no HIP device' in got[r]['nodev_msg'], got[r]
+        assert got[r]['pairs_rc'] == -3, got[r]
+        assert 'rank 0 failed' in got[r]['pairs_msg'] and 'no HIP device' in got[r]['pairs_msg'], got[r]
         assert got[r]['align_rc'] != 0
         assert got[r]['sliced_rc'] == -3, got[r]
         assert got[r]['comm'] == dict(comm='callback', rccl_ranks=None, rank=r, world=2)
@@ -141,6 +153,7 @@ def test_align_pairs_share_is_the_owner_partition_of_the_task_list():
             got_all += len(mine)
         assert got_all == len(tasks)
     assert len(D.align_pairs_share(gs, cand[:0], 4, 1)) == 0
+    assert len(D.align_pairs_share(gs, cand[:0], 1, 0)) == 0              # world = 1, n_tasks = 0
     # more than 2^17 pairs: the listing runs on several threads (per-chunk owner counts become starting positions) and must
     # give the same tasks IN THE SAME ORDER as one thread would (pair order, r = a before r = b)
     a = rng.integers(1, n, 400000); b = (rng.integers(0, n, 400000) ** 2 // n) % a

@@ -187,7 +187,6 @@ struct vg_slice_exchange {
     int rank = 0, world = 1;
     bool emulate = false;       // developer / tests: no peers -- their slices are scanned by this process (one GPU stands in for `world`)
     std::function<void(int status, const vg_xpart* parts, int n_parts)> alltoallv;
-    bool agreed = false;        // the agreement in front of the exchange has taken place (the failure handling of the caller pairs it otherwise)
 };
 // whether a shard pass of (g, k, fraction) over `world` ranks takes the sliced scan: a pure function of its arguments
 bool vg_slice_exchange_applies(const vg_genomes* g, int k, double fraction, int world);

@@ -111,59 +111,50 @@ void gather_device(const vg_comm* c, const void* send, void* recv, int64_t bytes
     vg_prof_scope ps("exchange", (double)bytes * c->world);
     if (c->p_allgather(send, recv, (size_t)bytes, ncclChar, c->nccl_comm, s) != ncclSuccess) throw vg_error(VG_EIO, "ncclAllGather failed");
 }
-// every rank learns whether any rank failed: throws the first failure on all of them
-void agree(const vg_comm* c, int my_rc, const char* what) {
-    std::vector<int32_t> all((size_t)c->world, 0); int32_t mine = my_rc;
-    gather_host(c, &mine, all.data(), sizeof(int32_t));
-    // (the first failed rank names the error code; a rank that failed itself -- whether or not it is that first one -- says why)
-    for (int r = 0; r < c->world; ++r) if (all[(size_t)r] != 0)
-        throw vg_error(all[(size_t)r], std::string(what) + ": rank " + std::to_string(r) + " failed" + (my_rc != 0 ? std::string(": ") + vg_last_error() : std::string()));
-}
-// the same agreement carrying a checksum every rank must hold alike (e.g. of an input list all ranks are to pass identically)
-void agree_same(const vg_comm* c, int my_rc, uint32_t checksum, const char* what, const char* mismatch) {
-    std::vector<uint32_t> all((size_t)c->world * 2, 0); const uint32_t mine[2] = { (uint32_t)my_rc, checksum };
-    gather_host(c, mine, all.data(), sizeof mine);
-    for (int r = 0; r < c->world; ++r) if ((int32_t)all[(size_t)2 * r] != 0)
-        throw vg_error((int32_t)all[(size_t)2 * r], std::string(what) + ": rank " + std::to_string(r) + " failed" + (r == c->rank ? std::string(": ") + vg_last_error() : std::string()));
-    for (int r = 1; r < c->world; ++r) if (all[(size_t)2 * r + 1] != all[1])
+// THE agreement, in front of every exchange: each rank contributes {status, payload words} and every rank holds all of them
+// afterwards (returned: world blocks of 1 + payload.size() words, rank r's status first).  Throws on every rank alike:
+// the first failed rank names the error code, and a rank that failed itself -- whether or not it is that first one -- says
+// why; then the first n_same payload words, which every rank must hold as rank 0 does (a checksum of an input all ranks
+// are to pass identically, a plan decided from process-local knobs), else `mismatch`.
+std::vector<int64_t> agree(const vg_comm* c, int my_rc, const char* what, std::vector<int64_t> payload = {}, size_t n_same = 0, const char* mismatch = "") {
+    const size_t nw = 1 + payload.size();
+    payload.insert(payload.begin(), (int64_t)my_rc);
+    std::vector<int64_t> all(nw * (size_t)c->world, 0);
+    gather_host(c, payload.data(), all.data(), (int64_t)(nw * sizeof(int64_t)));
+    for (int r = 0; r < c->world; ++r) if (all[(size_t)r * nw] != 0)
+        throw vg_error((int)all[(size_t)r * nw], std::string(what) + ": rank " + std::to_string(r) + " failed" + (my_rc != 0 ? std::string(": ") + vg_last_error() : std::string()));
+    for (int r = 1; r < c->world; ++r) for (size_t i = 1; i <= n_same; ++i) if (all[(size_t)r * nw + i] != all[i])
         throw vg_error(VG_EINVAL, std::string(what) + ": rank " + std::to_string(r) + " and rank 0 " + mismatch);
+    return all;
 }
-// the agreement in front of an all-to-all: status and plan word as in agree_same, plus every rank's block sizes in both
-// directions -- each rank holds the whole (sender, receiver) matrix afterwards and all reach the same verdict: a layout two
+// the agreement in front of an all-to-all: status and plan word, plus every rank's block sizes in both directions -- each
+// rank holds the whole (sender, receiver) matrix afterwards and all reach the same verdict: a layout two
 // ranks computed differently (word_of / st_of from different tile counts) stops every rank HERE instead of hanging or
 // writing past a block inside grouped ncclSend / ncclRecv
 void agree_exchange(const vg_comm* c, int my_rc, uint32_t plan, const vg_xpart* parts, int n_parts, const char* what, const char* mismatch) {
     // (the message has ONE size whatever the rank has to say -- a rank that failed before it knew its blocks, or that does
-    // not slice at all, pairs the collective with n_parts = 0)
+    // not slice at all, pairs the collective with n_parts = 0; so does one with more parts than the message carries, as a failure)
     constexpr int MAX_XPARTS = 4;
-    if (n_parts > MAX_XPARTS) throw vg_error(VG_EINVAL, "internal error: more exchange parts than the agreement carries");
+    if (n_parts > MAX_XPARTS) { vg_set_error("internal error: more exchange parts than the agreement carries"); my_rc = VG_EINVAL; n_parts = 0; }
     const int W = c->world;
-    const size_t nw = 3 + (size_t)MAX_XPARTS * 2 * (size_t)W;
-    std::vector<int64_t> mine(nw, 0), all(nw * (size_t)W, 0);
-    mine[0] = my_rc; mine[1] = plan; mine[2] = n_parts;
+    const size_t nw = 3 + (size_t)MAX_XPARTS * 2 * (size_t)W;              // (status, plan, n_parts, sizes)
+    std::vector<int64_t> mine(nw - 1, 0);
+    mine[0] = plan; mine[1] = n_parts;
+    auto at = [&](int i, int dir, int r) { return 3 + ((size_t)i * 2 + (size_t)dir) * W + (size_t)r; };       // in a rank's block of nw words
     for (int i = 0; i < n_parts; ++i) for (int r = 0; r < W; ++r) {
-        mine[3 + ((size_t)i * 2 + 0) * W + r] = parts[i].send_off[r + 1] - parts[i].send_off[r];
-        mine[3 + ((size_t)i * 2 + 1) * W + r] = parts[i].recv_off[r + 1] - parts[i].recv_off[r];
+        mine[at(i, 0, r) - 1] = parts[i].send_off[r + 1] - parts[i].send_off[r];
+        mine[at(i, 1, r) - 1] = parts[i].recv_off[r + 1] - parts[i].recv_off[r];
     }
-    gather_host(c, mine.data(), all.data(), (int64_t)(nw * sizeof(int64_t)));
-    for (int r = 0; r < W; ++r) if (all[(size_t)r * nw] != 0)
-        throw vg_error((int)all[(size_t)r * nw], std::string(what) + ": rank " + std::to_string(r) + " failed" + (r == c->rank ? std::string(": ") + vg_last_error() : std::string()));
-    for (int r = 1; r < W; ++r) if (all[(size_t)r * nw + 1] != all[1] || all[(size_t)r * nw + 2] != all[2])
-        throw vg_error(VG_EINVAL, std::string(what) + ": rank " + std::to_string(r) + " and rank 0 " + mismatch);
+    const std::vector<int64_t> all = agree(c, my_rc, what, std::move(mine), 2, mismatch);
     for (int i = 0; i < n_parts; ++i) for (int a = 0; a < W; ++a) for (int b = 0; b < W; ++b)
-        if (all[(size_t)a * nw + 3 + ((size_t)i * 2 + 0) * W + b] != all[(size_t)b * nw + 3 + ((size_t)i * 2 + 1) * W + a])
+        if (all[(size_t)a * nw + at(i, 0, b)] != all[(size_t)b * nw + at(i, 1, a)])
             throw vg_error(VG_EINVAL, std::string(what) + ": rank " + std::to_string(a) + " sends a block of part " + std::to_string(i) + " to rank " + std::to_string(b) +
                            " whose size the receiver computed differently (the ranks disagree on the exchange layout)");
 }
-// a compute section between two exchanges: its failure becomes this rank's status word of the next agreement
-template <class F> void guarded(const vg_comm* c, const char* what, F fn) {
-    int rc = VG_OK;
-    try { fn(); }
-    catch (const vg_error& e) { vg_set_error("%s", e.what()); rc = e.code; }
-    catch (const std::bad_alloc&) { vg_set_error("out of host memory"); rc = VG_ENOMEM; }
-    catch (const std::exception& e) { vg_set_error("%s", e.what()); rc = VG_EINVAL; }
-    agree(c, rc, what);
-}
+// a compute section between two exchanges: its failure becomes this rank's status word of the next agreement (what it
+// threw is kept as the rank's last error, exactly as at the C ABI)
+template <class F> int run_guarded(F fn) { VG_API_BEGIN fn(); VG_API_END }
+template <class F> void guarded(const vg_comm* c, const char* what, F fn) { agree(c, run_guarded(fn), what); }
 
 // all-to-all of DEVICE memory (vg_xpart: block d of send -> rank d, block s of recv <- rank s), after the agreement on
 // `status`.  RCCL: one group of ncclSend / ncclRecv per peer; a callback communicator has only its all-gather, so every
@@ -222,7 +213,37 @@ void alltoallv_device(const vg_comm* c, const vg_xpart* parts, int n_parts, bool
     }
 }
 
-inline int dgrid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096)); }
+// every rank contributes cnt[rank] records of R (HOST memory) and receives all of them in rank order: one all-gather of
+// blocks padded to the largest count; every rank knows all counts beforehand (from the input, or they travel first)
+template <class R> struct padded_gather {
+    std::vector<int64_t> cnt; int64_t pad = 1;
+    std::vector<R> send, all;
+    // inside a guarded section (everything that allocates): the zero-filled send block holding this rank's records, the
+    // receive block, the staging of the exchange
+    void stage(const vg_comm* c, std::vector<int64_t> counts, const R* mine) {
+        cnt = std::move(counts);
+        for (int64_t n : cnt) pad = std::max(pad, n);
+        send.assign((size_t)pad, R{}); all.resize((size_t)pad * cnt.size());
+        if (cnt[(size_t)c->rank]) memcpy(send.data(), mine, sizeof(R) * (size_t)cnt[(size_t)c->rank]);
+        reserve_staging(c, pad * (int64_t)sizeof(R));
+    }
+    // outside it, behind the section's agreement
+    void exchange(const vg_comm* c) { gather_host(c, send.data(), all.data(), pad * (int64_t)sizeof(R)); }
+    const R* block(int r) const { return all.data() + (size_t)r * (size_t)pad; }     // rank r's records: the first cnt[r]
+};
+
+// malloc'ed memory handed over by (or to be handed out through) the C ABI: vg_free, unless released to the caller
+template <class T> struct free_guard {
+    T* p = nullptr;
+    ~free_guard() { if (p) vg_free(p); }
+    T* release() { T* q = p; p = nullptr; return q; }
+};
+template <class T> T* host_alloc(int64_t n) {
+    T* p = (T*)malloc(sizeof(T) * (size_t)std::max<int64_t>(1, n));
+    if (!p) throw vg_error(VG_ENOMEM, "out of host memory");
+    return p;
+}
+
 // output slot of a kept element behind a global cursor, ONE atomic per wave (a global atomic per element on one word
 // costs ~10 ns each: 4.5 ms per 450 000 records); to be called by all active lanes of the wave
 __device__ __forceinline__ unsigned long long wave_slot(unsigned long long* cursor, bool keep) {
@@ -362,8 +383,7 @@ extern "C" int vg_comm_selftest(const vg_comm* c, int64_t bytes) {
         for (int r = 0; r < W; ++r) { soff[(size_t)r + 1] = soff[(size_t)r] + blk(c->rank, r); roff[(size_t)r + 1] = roff[(size_t)r] + blk(r, c->rank); }
         std::vector<uint8_t> hs((size_t)soff[(size_t)W]), hr((size_t)roff[(size_t)W]);
         for (int r = 0; r < W; ++r) for (int64_t i = 0; i < blk(c->rank, r); ++i) hs[(size_t)(soff[(size_t)r] + i)] = (uint8_t)(i * 7 + c->rank * 29 + r * 3 + 1);
-        int rc = VG_OK;
-        try {
+        guarded(c, "vg_comm_selftest all-to-all", [&] {
             dbuf<uint8_t> ds(hs.size()), dr(hr.size());
             hipStream_t s = vg_stream();
             ds.upload(hs.data(), hs.size(), s);
@@ -372,35 +392,62 @@ extern "C" int vg_comm_selftest(const vg_comm* c, int64_t bytes) {
             dr.download(hr.data(), hr.size(), s); VG_HIP(hipStreamSynchronize(s));
             for (int r = 0; r < W; ++r) for (int64_t i = 0; i < blk(r, c->rank); ++i)
                 if (hr[(size_t)(roff[(size_t)r] + i)] != (uint8_t)(i * 7 + r * 29 + c->rank * 3 + 1)) throw vg_error(VG_EIO, "vg_comm_selftest: wrong all-to-all block from rank " + std::to_string(r));
-        } catch (const vg_error& e) { vg_set_error("%s", e.what()); rc = e.code; }
-        agree(c, rc, "vg_comm_selftest all-to-all");
+        });
     }
     VG_API_END
 }
 
-// owner rank of every task (reference-range partition): references are cut into `world` contiguous id ranges
-// holding about the same number of tasks; a pure function of the task list
-extern "C" int vg_align_owner(const vg_task* tasks, int64_t n_tasks, int n_genomes, int world, int32_t* owner) {
-    VG_API_BEGIN
-    if ((!tasks && n_tasks) || (!owner && n_tasks) || world < 1 || n_genomes < 0) throw vg_error(VG_EINVAL, "vg_align_owner: bad arguments");
-    // (every rank of a sharded run does this for the whole list: a few threads, per-thread counters)
-    const int n_thr = n_tasks >= (1 << 18) ? std::min(vg_host_threads(), 8) : 1;
-    std::vector<std::vector<int64_t>> part((size_t)n_thr, std::vector<int64_t>((size_t)n_genomes + 1, 0));
-    vg_parallel_chunks(n_tasks, n_thr, [&](int64_t lo, int64_t hi, int t) {
-        auto& pr = part[(size_t)t];
-        for (int64_t i = lo; i < hi; ++i) { if (tasks[i].r >= (uint32_t)n_genomes) throw vg_error(VG_EINVAL, "task id out of range"); pr[tasks[i].r]++; }
+// ------------------------------------------------------------------ the reference-range partition of the align tasks
+namespace {
+// (every rank of a sharded run walks the whole task / pair list: a few threads from 2^18 tasks on)
+int list_threads(int64_t n_tasks) { return n_tasks >= (1 << 18) ? std::max(1, std::min(vg_host_threads(), 8)) : 1; }
+// THE owner rule: references are cut into `world` contiguous id ranges holding about the same number of tasks -- the
+// owner of reference r is min(world - 1, before * world / n_tasks), `before` the tasks of the references below r.  A
+// pure function of the task list; the list comes as n_items items, refs(i, count) calls count(r) for the reference of
+// every task of item i (a task: its own; a candidate pair: a and b).  Counted on T threads with per-thread counters.
+template <class Refs> std::vector<int32_t> ref_owners(int64_t n_items, int T, int64_t n_tasks, int n_genomes, int world, const char* bad_id, Refs refs) {
+    std::vector<std::vector<int64_t>> part((size_t)T, std::vector<int64_t>((size_t)n_genomes + 1, 0));
+    vg_parallel_chunks(n_items, T, [&](int64_t lo, int64_t hi, int t) {
+        auto count = [&, &pr = part[(size_t)t]](uint32_t r) { if (r >= (uint32_t)n_genomes) throw vg_error(VG_EINVAL, bad_id); pr[r]++; };
+        for (int64_t i = lo; i < hi; ++i) refs(i, count);
     });
     std::vector<int32_t> own_ref((size_t)n_genomes + 1, 0);
     int64_t before = 0;
     for (int r = 0; r < n_genomes; ++r) {
         own_ref[(size_t)r] = n_tasks ? (int32_t)std::min<int64_t>(world - 1, before * world / n_tasks) : 0;
-        for (int t = 0; t < n_thr; ++t) before += part[(size_t)t][(size_t)r];
+        for (int t = 0; t < T; ++t) before += part[(size_t)t][(size_t)r];
     }
-    vg_parallel_chunks(n_tasks, n_thr, [&](int64_t lo, int64_t hi, int) { for (int64_t i = lo; i < hi; ++i) owner[i] = own_ref[tasks[i].r]; });
+    return own_ref;
+}
+}  // namespace
+
+// owner rank of every task: the owner of its reference
+extern "C" int vg_align_owner(const vg_task* tasks, int64_t n_tasks, int n_genomes, int world, int32_t* owner) {
+    VG_API_BEGIN
+    if ((!tasks && n_tasks) || (!owner && n_tasks) || world < 1 || n_genomes < 0) throw vg_error(VG_EINVAL, "vg_align_owner: bad arguments");
+    const int T = list_threads(n_tasks);
+    const std::vector<int32_t> own_ref = ref_owners(n_tasks, T, n_tasks, n_genomes, world, "task id out of range", [&](int64_t i, auto& count) { count(tasks[i].r); });
+    vg_parallel_chunks(n_tasks, T, [&](int64_t lo, int64_t hi, int) { for (int64_t i = lo; i < hi; ++i) owner[i] = own_ref[tasks[i].r]; });
     VG_API_END
 }
 
 // ------------------------------------------------------------------ prefilter, sharded
+// The collectives a rank enters, in order, by its path through the shard.  A "x" is the agreement of that name (one
+// all-gather of status words); every rank of a run is in the same column at the same time, whichever its row.
+//
+//   path of the rank             | A "prefilter scan"          | all-to-all | A "prefilter shard" | sizes .. A "union" | counts | A "sums"
+//   -----------------------------+-----------------------------+------------+---------------------+--------------------+--------+---------
+//   sliced scan                  | in the pass, block sizes    | yes        | yes                 | yes                | if any | yes
+//   not sliced, world > 1        | in front of the pass, 0     | --         | yes                 | yes                | if any | yes
+//   failed before the exchange   | from the catch, 0, status   | --         | yes: throws on all  | --                 | --     | --
+//   world of one (VG_DIST_FORCE) | --                          | --         | yes                 | yes                | if any | yes
+//
+// "block sizes" / "0": what the rank's message says of its all-to-all blocks.  A sliced rank whose own scan failed enters
+// the agreement in the pass all the same, with its status; one whose pass returns without reaching the exchange enters it
+// right behind the pass, with 0.  A failure status makes "prefilter scan" throw on every rank: none enters the all-to-all
+// (over a callback communicator: two all-gathers per part), all meet again in "prefilter shard", which throws on all.
+// "sizes .. union": the all-gathers of the set sizes and of the nomination counts, A "prefilter nominations", the all-gather
+// of the nominated keys, A "prefilter union".  "counts": of the union, skipped by every rank alike when it is empty.
 extern "C" int vg_kmer_shared_sharded(vg_genomes* g, int k, double fraction, uint32_t min_shared, const vg_comm* c,
                                       int64_t* set_sizes, vg_pair_count** pairs, int64_t* n_pairs) {
     VG_API_BEGIN
@@ -411,48 +458,50 @@ extern "C" int vg_kmer_shared_sharded(vg_genomes* g, int k, double fraction, uin
     if (!c->exchanges()) { check(vg_kmer_shared(g, k, fraction, 0, 1, min_shared, set_sizes, pairs, n_pairs)); return VG_OK; }
     const int W = c->world;
     if (min_shared < 1) min_shared = 1;
-    hipStream_t s = vg_stream();
+    hipStream_t s = nullptr;      // (set in the first guarded section: a rank without a usable device fails THROUGH the agreements)
     // ---- this rank's shard of the k-mer range: partial sizes (host) and partial counts (left in HBM)
     std::vector<int64_t> part_sizes((size_t)std::max(n, 1) + 1, 0);           // (+ 1: how this rank cut the k-mers, compared below)
     int my_mode = 0;
     dbuf<vg_pair_count> d_loc; int64_t n_loc = 0;
-    dbuf<uint64_t> d_nom, lk, lk2; dbuf<uint32_t> lv, lv2; dbuf<unsigned long long> d_cur(1);
+    dbuf<uint64_t> d_nom, lk, lk2; dbuf<uint32_t> lv, lv2; dbuf<unsigned long long> d_cur;
     unsigned long long n_nom = 0;
     const uint32_t thr = (min_shared + (uint32_t)W - 1) / (uint32_t)W;        // pigeonhole: some rank holds >= ceil(T / W) of a pair that reaches T
-    // RANGE shards: every rank scans 1/W of the bases, kept masks and level-1 counts travel (k_slice_scan); the agreement
-    // in front of that exchange is paired below by a rank that never reaches it
+    // RANGE shards: every rank scans 1/W of the bases, kept masks and level-1 counts travel (k_slice_scan)
     vg_slice_exchange xs; xs.rank = c->rank; xs.world = W;
     const bool sliced = W > 1 && vg_slice_exchange_applies(g, k, fraction, W);
     // EVERY rank of a world > 1 goes through ONE "prefilter scan" agreement in front of its shard's exchanges, sliced or
     // not, and the agreement carries how the rank is about to work: (sliced scan?, RANGE / HASH cut).  Both are decided from
     // process-local knobs (vg_set_subshards, VG_INDEX_PATH); a rank that decided differently would otherwise
     // skip or add a collective and leave its peers inside grouped ncclSend / ncclRecv.  A mismatch throws on every rank.
+    // pair_scan is the only way into that agreement, and scan_paired says whether this rank has been through (a world of
+    // one has none): a rank that never reaches the exchange pairs it below.
     const uint32_t my_plan = W > 1 ? (uint32_t)(sliced ? 1 : 0) | ((uint32_t)vg_kmer_shard_mode(g, fraction, W) << 1) : 0u;
     const char* plan_mismatch = "plan the prefilter shard differently (sliced scan / RANGE against HASH shards: do the ranks differ in vg_set_subshards or VG_INDEX_PATH?)";
-    xs.alltoallv = [&](int status, const vg_xpart* parts, int n_parts) {
-        xs.agreed = true;
+    bool scan_paired = W == 1;
+    auto pair_scan = [&](int status, const vg_xpart* parts, int n_parts) {
+        scan_paired = true;
         agree_exchange(c, status, my_plan, parts, n_parts, "prefilter scan", plan_mismatch);
-        alltoallv_device(c, parts, n_parts);
     };
+    xs.alltoallv = [&](int status, const vg_xpart* parts, int n_parts) { pair_scan(status, parts, n_parts); alltoallv_device(c, parts, n_parts); };
     guarded(c, "prefilter shard", [&] {
-        // (a rank that does not slice pairs the agreement here, in front of its pass)
-        if (W > 1 && !sliced) { xs.agreed = true; agree_exchange(c, VG_OK, my_plan, nullptr, 0, "prefilter scan", plan_mismatch); }
-        try { vg_kmer_shared_device(g, k, fraction, c->rank, W, 1u, part_sizes.data(), d_loc, &n_loc, sliced ? &xs : nullptr, &my_mode); }
-        catch (...) {
-            if (W > 1 && !xs.agreed) { xs.agreed = true; try { agree_exchange(c, VG_EINVAL, my_plan, nullptr, 0, "prefilter scan", plan_mismatch); } catch (...) {} }
+        try {
+            s = vg_stream(); d_cur.alloc(1);
+            if (!sliced && !scan_paired) pair_scan(VG_OK, nullptr, 0);        // not sliced: in front of the pass
+            vg_kmer_shared_device(g, k, fraction, c->rank, W, 1u, part_sizes.data(), d_loc, &n_loc, sliced ? &xs : nullptr, &my_mode);      // sliced: through xs.alltoallv
+            if (!scan_paired) pair_scan(VG_OK, nullptr, 0);                   // sliced, and the pass ended without an exchange
+        } catch (...) {
+            // failed before the exchange: the peers are on their way into the agreement, so this rank enters it too, with a
+            // failure status -- the agreement then throws here as on every rank, which is dropped for the cause already held
+            if (!scan_paired) try { pair_scan(VG_EINVAL, nullptr, 0); } catch (...) {}
             throw;
         }
-        if (W > 1 && !xs.agreed) { xs.agreed = true; agree_exchange(c, VG_OK, my_plan, nullptr, 0, "prefilter scan", plan_mismatch); }
         // nominations, and this rank's records sorted by key for the lookups of step 3
         d_nom.alloc((size_t)std::max<int64_t>(n_loc, 1)); d_cur.zero(s);
         lk.alloc((size_t)std::max<int64_t>(n_loc, 1)); lk2.alloc(lk.n); lv.alloc(lk.n); lv2.alloc(lk.n);
         if (n_loc) {
-            hipLaunchKernelGGL(k_nominate, dim3(dgrid(n_loc)), dim3(256), 0, s, (const vg_pair_count*)d_loc.p, n_loc, thr, d_nom.p, d_cur.p);
-            hipLaunchKernelGGL(k_local_keys, dim3(dgrid(n_loc)), dim3(256), 0, s, (const vg_pair_count*)d_loc.p, n_loc, lk.p, lv.p);
-            size_t tb = 0;
-            VG_HIP(rocprim::radix_sort_pairs(nullptr, tb, lk.p, lk2.p, lv.p, lv2.p, (size_t)n_loc, 0u, 64u, s));
-            dbuf<char> tmp(tb);
-            VG_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tb, lk.p, lk2.p, lv.p, lv2.p, (size_t)n_loc, 0u, 64u, s));
+            hipLaunchKernelGGL(k_nominate, dim3(grid_for(n_loc)), dim3(256), 0, s, (const vg_pair_count*)d_loc.p, n_loc, thr, d_nom.p, d_cur.p);
+            hipLaunchKernelGGL(k_local_keys, dim3(grid_for(n_loc)), dim3(256), 0, s, (const vg_pair_count*)d_loc.p, n_loc, lk.p, lv.p);
+            with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, lk.p, lk2.p, lv.p, lv2.p, (size_t)n_loc, 0u, 64u, s); });
         }
         d_cur.download(&n_nom, 1, s);
         VG_HIP(hipStreamSynchronize(s));
@@ -471,6 +520,8 @@ extern "C" int vg_kmer_shared_sharded(vg_genomes* g, int k, double fraction, uin
         for (int i = 0; i < n; ++i) { int64_t t = 0; for (int r = 0; r < W; ++r) t += all_sizes[(size_t)r * nw + i]; set_sizes[i] = t; }
     }
     // ---- 1: nominations travel (keys only), 2: their union
+    // (the padded gather of DEVICE memory: zeroed and filled on the stream, squeezed by a kernel -- not padded_gather, which
+    // would have to branch on where its blocks live at every step)
     std::vector<int64_t> cnt((size_t)W, 0), prefix((size_t)W + 1, 0);
     const int64_t my_nom = (int64_t)n_nom;
     gather_host(c, &my_nom, cnt.data(), sizeof(int64_t));
@@ -488,34 +539,29 @@ extern "C" int vg_kmer_shared_sharded(vg_genomes* g, int k, double fraction, uin
         d_prefix.upload(prefix.data(), prefix.size(), s);
         d_uni.alloc(nt);
         if (total) {
-            hipLaunchKernelGGL(k_squeeze_keys, dim3(dgrid(pad * W)), dim3(256), 0, s, (const uint64_t*)d_all.p, (const int64_t*)d_prefix.p, W, pad, keys.p);
-            size_t tb = 0, tb2 = 0;
-            VG_HIP(rocprim::radix_sort_keys(nullptr, tb, keys.p, keys2.p, (size_t)total, 0u, 64u, s));
-            VG_HIP(rocprim::unique(nullptr, tb2, keys2.p, d_uni.p, d_nu.p, (size_t)total, rocprim::equal_to<uint64_t>(), s));
-            dbuf<char> tmp(std::max(tb, tb2));
-            VG_HIP(rocprim::radix_sort_keys((void*)tmp.p, tb, keys.p, keys2.p, (size_t)total, 0u, 64u, s));
-            VG_HIP(rocprim::unique((void*)tmp.p, tb2, keys2.p, d_uni.p, d_nu.p, (size_t)total, rocprim::equal_to<uint64_t>(), s));
+            hipLaunchKernelGGL(k_squeeze_keys, dim3(grid_for(pad * W)), dim3(256), 0, s, (const uint64_t*)d_all.p, (const int64_t*)d_prefix.p, W, pad, keys.p);
+            with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::radix_sort_keys(tmp, tb, keys.p, keys2.p, (size_t)total, 0u, 64u, s); });
+            with_temp_storage([&](void* tmp, size_t& tb) { return rocprim::unique(tmp, tb, keys2.p, d_uni.p, d_nu.p, (size_t)total, rocprim::equal_to<uint64_t>(), s); });
             d_nu.download(&nu, 1, s); VG_HIP(hipStreamSynchronize(s));
         }
         // ---- 3: this rank's count of every pair of the union (the union is the same on every rank)
         d_cnt.alloc((size_t)std::max<unsigned long long>(nu, 1)); d_cnt_all.alloc(d_cnt.n * W);
-        if (nu) hipLaunchKernelGGL(k_lookup_counts, dim3(dgrid((int64_t)nu)), dim3(256), 0, s, (const uint64_t*)d_uni.p, (int64_t)nu, (const uint64_t*)lk2.p,
+        if (nu) hipLaunchKernelGGL(k_lookup_counts, dim3(grid_for((int64_t)nu)), dim3(256), 0, s, (const uint64_t*)d_uni.p, (int64_t)nu, (const uint64_t*)lk2.p,
                                    (const uint32_t*)lv2.p, n_loc, d_cnt.p);
     });
     if (nu) gather_device(c, d_cnt.p, d_cnt_all.p, (int64_t)nu * (int64_t)sizeof(uint32_t));
-    vg_pair_count* out = nullptr; unsigned long long n_out = 0;
+    free_guard<vg_pair_count> out_g; unsigned long long n_out = 0;
     guarded(c, "prefilter sums", [&] {
         dbuf<vg_pair_count> d_out((size_t)std::max<unsigned long long>(nu, 1));
         d_cur.zero(s);
-        if (nu) hipLaunchKernelGGL(k_sum_counts, dim3(dgrid((int64_t)nu)), dim3(256), 0, s, (const uint64_t*)d_uni.p, (int64_t)nu, (const uint32_t*)d_cnt_all.p, W, min_shared, d_out.p, d_cur.p);
+        if (nu) hipLaunchKernelGGL(k_sum_counts, dim3(grid_for((int64_t)nu)), dim3(256), 0, s, (const uint64_t*)d_uni.p, (int64_t)nu, (const uint32_t*)d_cnt_all.p, W, min_shared, d_out.p, d_cur.p);
         d_cur.download(&n_out, 1, s); VG_HIP(hipStreamSynchronize(s));
-        out = (vg_pair_count*)malloc(sizeof(vg_pair_count) * std::max<size_t>(1, (size_t)n_out));
-        if (!out) throw vg_error(VG_ENOMEM, "out of host memory");
+        vg_pair_count* out = out_g.p = host_alloc<vg_pair_count>((int64_t)n_out);
         if (n_out) { d_out.download(out, (size_t)n_out, s); VG_HIP(hipStreamSynchronize(s)); }
         // the cursor order depends on scheduling; every rank returns the same list
         std::sort(out, out + n_out, [](const vg_pair_count& x, const vg_pair_count& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
     });
-    *pairs = out; *n_pairs = (int64_t)n_out;
+    *pairs = out_g.release(); *n_pairs = (int64_t)n_out;
     VG_API_END
 }
 
@@ -529,9 +575,8 @@ extern "C" int vg_lz_align_sharded(vg_genomes* g, const vg_task* tasks, int64_t 
     if (regions) { *regions = nullptr; if (n_regions) *n_regions = 0; }
     const int W = c->world;
     std::vector<int32_t> owner; std::vector<int64_t> mine, per_rank((size_t)W, 0);
-    std::vector<vg_pair_stat> my_stats, send, all;
-    vg_region* my_reg = nullptr; int64_t my_nreg = 0, pad = 1;
-    struct guard { vg_region** q; ~guard() { if (*q) vg_free(*q); } } gr{ &my_reg };
+    std::vector<vg_pair_stat> my_stats; padded_gather<vg_pair_stat> rows;
+    free_guard<vg_region> my_reg; int64_t my_nreg = 0;
     guarded(c, "align shard", [&] {
         owner.resize((size_t)std::max<int64_t>(n_tasks, 1));
         check(vg_align_owner(tasks, n_tasks, vg_genomes_count(g), W, owner.data()));
@@ -539,77 +584,40 @@ extern "C" int vg_lz_align_sharded(vg_genomes* g, const vg_task* tasks, int64_t 
         std::vector<vg_task> my_tasks(mine.size());
         for (size_t i = 0; i < mine.size(); ++i) my_tasks[i] = tasks[mine[i]];
         my_stats.resize(std::max<size_t>(1, mine.size()));
-        check(vg_lz_align(g, my_tasks.data(), (int64_t)my_tasks.size(), p, my_stats.data(), regions ? &my_reg : nullptr, regions ? &my_nreg : nullptr));
-        // rows: sizes are known to every rank (per_rank), one padded all-gather
-        for (int r = 0; r < W; ++r) pad = std::max(pad, per_rank[(size_t)r]);
-        send.assign((size_t)pad, vg_pair_stat{}); all.resize((size_t)pad * W);
-        if (!mine.empty()) memcpy(send.data(), my_stats.data(), sizeof(vg_pair_stat) * mine.size());
-        reserve_staging(c, pad * (int64_t)sizeof(vg_pair_stat));
+        check(vg_lz_align(g, my_tasks.data(), (int64_t)my_tasks.size(), p, my_stats.data(), regions ? &my_reg.p : nullptr, regions ? &my_nreg : nullptr));
+        rows.stage(c, per_rank, my_stats.data());                    // (the counts are known to every rank)
     });
-    gather_host(c, send.data(), all.data(), pad * (int64_t)sizeof(vg_pair_stat));
+    rows.exchange(c);
     std::vector<int64_t> cursor((size_t)W, 0);
-    for (int64_t t = 0; t < n_tasks; ++t) { const int r = owner[(size_t)t]; stats[t] = all[(size_t)(r * pad + cursor[(size_t)r]++)]; }
+    for (int64_t t = 0; t < n_tasks; ++t) { const int r = owner[(size_t)t]; stats[t] = rows.block(r)[cursor[(size_t)r]++]; }
     if (regions) {
         // regions: variable length, task ids translated to the global list
-        for (int64_t i = 0; i < my_nreg; ++i) my_reg[i].task = (uint32_t)mine[my_reg[i].task];
+        for (int64_t i = 0; i < my_nreg; ++i) my_reg.p[i].task = (uint32_t)mine[my_reg.p[i].task];
         std::vector<int64_t> cnt((size_t)W, 0);
         gather_host(c, &my_nreg, cnt.data(), sizeof(int64_t));
-        int64_t rpad = 1, tot = 0; for (int r = 0; r < W; ++r) { rpad = std::max(rpad, cnt[(size_t)r]); tot += cnt[(size_t)r]; }
-        std::vector<vg_region> rs, ra; vg_region* o = nullptr;
+        int64_t tot = 0; for (int64_t n : cnt) tot += n;
+        padded_gather<vg_region> regs; free_guard<vg_region> o;
         guarded(c, "align regions", [&] {
-            rs.assign((size_t)rpad, vg_region{}); ra.resize((size_t)rpad * W);
-            if (my_nreg) memcpy(rs.data(), my_reg, sizeof(vg_region) * (size_t)my_nreg);
-            o = (vg_region*)malloc(sizeof(vg_region) * std::max<size_t>(1, (size_t)tot));
-            if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
-            reserve_staging(c, rpad * (int64_t)sizeof(vg_region));
+            o.p = host_alloc<vg_region>(tot);
+            regs.stage(c, std::move(cnt), my_reg.p);
         });
-        gather_host(c, rs.data(), ra.data(), rpad * (int64_t)sizeof(vg_region));
+        regs.exchange(c);
         int64_t w = 0;
-        for (int r = 0; r < W; ++r) { memcpy(o + w, ra.data() + (size_t)r * rpad, sizeof(vg_region) * (size_t)cnt[(size_t)r]); w += cnt[(size_t)r]; }
-        *regions = o; if (n_regions) *n_regions = tot;
+        for (int r = 0; r < W; ++r) { memcpy(o.p + w, regs.block(r), sizeof(vg_region) * (size_t)regs.cnt[(size_t)r]); w += regs.cnt[(size_t)r]; }
+        *regions = o.release(); if (n_regions) *n_regions = tot;
     }
     VG_API_END
 }
 
-// reference ranges of `world` ranks from the candidate pairs (every pair is one task with r = a and one with r = b: the
-// rule of vg_align_owner without the task list), the position of both tasks of every pair in their owners' lists (tasks
+// reference ranges of `world` ranks from the candidate pairs (every pair is one task with r = a and one with r = b:
+// ref_owners without the task list), the position of both tasks of every pair in their owners' lists (tasks
 // listed in pair order: r = a first), and rank `me`'s own list
 namespace {
 void pairs_share(int n, const vg_pair_count* cand, int64_t n_cand, int W, int me, std::vector<int32_t>& own_ref,
                  std::vector<uint32_t>* la, std::vector<uint32_t>* lb, std::vector<int64_t>& per_rank, std::vector<vg_task>& mine) {
-    const int64_t n_tasks = 2 * n_cand;
-    own_ref.assign((size_t)n + 1, 0); per_rank.assign((size_t)W, 0); mine.clear();
-    // (every rank of a sharded call does this for the whole pair list between the stages: a few threads from 10^5 pairs on)
-    const int T = n_cand >= (1 << 17) ? std::max(1, std::min(vg_host_threads(), 8)) : 1;
-    std::vector<int64_t> per_ref((size_t)n + 1, 0);
-    if (T == 1) {
-        for (int64_t i = 0; i < n_cand; ++i) {
-            if (cand[i].a >= (uint32_t)n || cand[i].b >= (uint32_t)n) throw vg_error(VG_EINVAL, "pair id out of range");
-            per_ref[cand[i].a]++; per_ref[cand[i].b]++;
-        }
-    } else {
-        vg_parallel_chunks(n_cand, T, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t i = lo; i < hi; ++i) {
-                if (cand[i].a >= (uint32_t)n || cand[i].b >= (uint32_t)n) throw vg_error(VG_EINVAL, "pair id out of range");
-                __atomic_fetch_add(&per_ref[cand[i].a], 1, __ATOMIC_RELAXED); __atomic_fetch_add(&per_ref[cand[i].b], 1, __ATOMIC_RELAXED);
-            }
-        });
-    }
-    int64_t before = 0;
-    for (int r = 0; r < n; ++r) { own_ref[(size_t)r] = n_tasks ? (int32_t)std::min<int64_t>(W - 1, before * W / n_tasks) : 0; before += per_ref[(size_t)r]; }
-    if (T == 1) {
-        for (int64_t i = 0; i < n_cand; ++i) {
-            const uint32_t a = cand[i].a, b = cand[i].b;
-            const int ra = own_ref[a], rb = own_ref[b];
-            const int64_t ia = per_rank[(size_t)ra]++;
-            if (la) (*la)[(size_t)i] = (uint32_t)ia;
-            if (ra == me) mine.push_back({ b, a });
-            const int64_t ib = per_rank[(size_t)rb]++;
-            if (lb) (*lb)[(size_t)i] = (uint32_t)ib;
-            if (rb == me) mine.push_back({ a, b });
-        }
-        return;
-    }
+    const int T = list_threads(2 * n_cand);
+    own_ref = ref_owners(n_cand, T, 2 * n_cand, n, W, "pair id out of range", [&](int64_t i, auto& count) { count(cand[i].a); count(cand[i].b); });
+    per_rank.assign((size_t)W, 0);
     // positions in the owners' lists are running counts in pair order: per chunk the tasks of every owner are counted,
     // the chunks' counts become their starting positions, and every chunk then numbers its own pairs
     std::vector<std::vector<int64_t>> cnt((size_t)T, std::vector<int64_t>((size_t)W, 0));
@@ -644,8 +652,7 @@ extern "C" int vg_align_pairs_share(const vg_genomes* g, const vg_pair_count* ca
     if (!g || (!cand && n_cand) || !tasks_out || !n_tasks_out || world < 1 || rank < 0 || rank >= world) throw vg_error(VG_EINVAL, "vg_align_pairs_share: bad arguments");
     std::vector<int32_t> own_ref; std::vector<int64_t> per_rank; std::vector<vg_task> mine;
     pairs_share(vg_genomes_count(g), cand, n_cand, world, rank, own_ref, nullptr, nullptr, per_rank, mine);
-    vg_task* o = (vg_task*)malloc(sizeof(vg_task) * std::max<size_t>(1, mine.size()));
-    if (!o) throw vg_error(VG_ENOMEM, "out of host memory");
+    vg_task* o = host_alloc<vg_task>((int64_t)mine.size());
     if (!mine.empty()) memcpy(o, mine.data(), sizeof(vg_task) * mine.size());
     *tasks_out = o; *n_tasks_out = (int64_t)mine.size();
     VG_API_END
@@ -664,31 +671,27 @@ extern "C" int vg_lz_align_pairs_sharded(vg_genomes* g, const vg_pair_count* can
     if (!g || !c || (!cand && n_cand) || !p || !tasks_out || !n_tasks_out || !stats_out) throw vg_error(VG_EINVAL, "vg_lz_align_pairs_sharded: null argument");
     if (g->device_only) throw vg_error(VG_EINVAL, "vg_lz_align_pairs_sharded: a subset (vg_genomes_subset) has no host copy; the sharded calls take a loaded set");
     *tasks_out = nullptr; *n_tasks_out = 0; *stats_out = nullptr;
-    const int n = vg_genomes_count(g);
     const int64_t n_tasks = 2 * n_cand;
-    struct free_guard2 { void* p = nullptr; ~free_guard2() { if (p) free(p); } } tasks_g, stats_g;
+    free_guard<vg_task> tasks_g; free_guard<vg_pair_stat> stats_g;
+    int64_t nt = 0;
     if (!c->exchanges()) {
         check(vg_lz_prepare(g, cand, n_cand, p));
-        int64_t nt = 0;
-        check(vg_align_tasks(g, cand, n_cand, (vg_task**)&tasks_g.p, &nt));
-        stats_g.p = malloc(sizeof(vg_pair_stat) * (size_t)std::max<int64_t>(1, nt));
-        if (!stats_g.p) throw vg_error(VG_ENOMEM, "out of host memory");
-        check(vg_lz_align(g, (const vg_task*)tasks_g.p, nt, p, (vg_pair_stat*)stats_g.p, nullptr, nullptr));
-        *tasks_out = (vg_task*)tasks_g.p; *n_tasks_out = nt; *stats_out = (vg_pair_stat*)stats_g.p; tasks_g.p = nullptr; stats_g.p = nullptr;
+        check(vg_align_tasks(g, cand, n_cand, &tasks_g.p, &nt));
+        stats_g.p = host_alloc<vg_pair_stat>(nt);
+        check(vg_lz_align(g, tasks_g.p, nt, p, stats_g.p, nullptr, nullptr));
+        *tasks_out = tasks_g.release(); *n_tasks_out = nt; *stats_out = stats_g.release();
         return VG_OK;
     }
     const int W = c->world;
     std::vector<int32_t> own_ref;
     std::vector<uint32_t> la((size_t)std::max<int64_t>(n_cand, 1)), lb((size_t)std::max<int64_t>(n_cand, 1)), perm((size_t)std::max<int64_t>(n_cand, 1));
-    std::vector<int64_t> per_rank;
-    std::vector<vg_pair_stat> send, all;
-    int64_t pad = 1, nt = 0;
+    padded_gather<vg_pair_stat> rows;
     vg_host_mark("align pairs: enter");
     // every rank must pass the SAME pairs in the SAME order (the positions of a rank's rows in the gathered blocks follow
     // from the order): an order-sensitive checksum of the list travels with the section's status word
     uint32_t cand_ck = 0;
     {
-        const int T = n_cand >= (1 << 17) ? std::max(1, std::min(vg_host_threads(), 8)) : 1;
+        const int T = list_threads(n_tasks);
         std::vector<uint64_t> part((size_t)T, 0);
         vg_parallel_chunks(n_cand, T, [&](int64_t lo, int64_t hi, int t) {
             uint64_t h = 0;
@@ -698,56 +701,51 @@ extern "C" int vg_lz_align_pairs_sharded(vg_genomes* g, const vg_pair_count* can
         uint64_t h = (uint64_t)n_cand; for (uint64_t v : part) h += v;
         cand_ck = (uint32_t)(h ^ (h >> 32));
     }
-    int rc_shard = VG_OK;
-    try { [&] {
+    const int rc_shard = run_guarded([&] {
         if (n_cand >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, "more than 2^31 candidate pairs in one call");
         // the canonical list of the whole set: a helper thread, beside everything below
         int rc_list = VG_OK; std::string err_list;
-        std::thread th([&] { rc_list = vg_align_tasks_perm(g, cand, n_cand, (vg_task**)&tasks_g.p, &nt, perm.data()); if (rc_list != VG_OK) err_list = vg_last_error(); });
+        std::thread th([&] { rc_list = vg_align_tasks_perm(g, cand, n_cand, &tasks_g.p, &nt, perm.data()); if (rc_list != VG_OK) err_list = vg_last_error(); });
         struct joiner { std::thread& t; ~joiner() { if (t.joinable()) t.join(); } } jn{ th };
-        std::vector<vg_task> mine;
-        pairs_share(n, cand, n_cand, W, c->rank, own_ref, &la, &lb, per_rank, mine);
+        std::vector<vg_task> mine; std::vector<int64_t> per_rank;
+        pairs_share(vg_genomes_count(g), cand, n_cand, W, c->rank, own_ref, &la, &lb, per_rank, mine);
         vg_host_mark("align pairs: own tasks listed");
         std::vector<vg_pair_stat> my_stats(std::max<size_t>(1, mine.size()));
         check(vg_lz_align(g, mine.data(), (int64_t)mine.size(), p, my_stats.data(), nullptr, nullptr));
         th.join();
         vg_host_mark("align pairs: canonical list joined");
         if (rc_list != VG_OK) throw vg_error(rc_list, err_list);
-        for (int r = 0; r < W; ++r) pad = std::max(pad, per_rank[(size_t)r]);
-        send.assign((size_t)pad, vg_pair_stat{}); all.resize((size_t)pad * W);
-        if (!mine.empty()) memcpy(send.data(), my_stats.data(), sizeof(vg_pair_stat) * mine.size());
-        stats_g.p = malloc(sizeof(vg_pair_stat) * (size_t)std::max<int64_t>(1, n_tasks));
-        if (!stats_g.p) throw vg_error(VG_ENOMEM, "out of host memory");
-        reserve_staging(c, pad * (int64_t)sizeof(vg_pair_stat));
-    }(); }
-    catch (const vg_error& e) { vg_set_error("%s", e.what()); rc_shard = e.code; }
-    catch (const std::bad_alloc&) { vg_set_error("out of host memory"); rc_shard = VG_ENOMEM; }
-    catch (const std::exception& e) { vg_set_error("%s", e.what()); rc_shard = VG_EINVAL; }
-    agree_same(c, rc_shard, cand_ck, "align shard", "were given different candidate pair lists (the same pairs in the same order are required: vg_kmer_shared_sharded returns them sorted)");
-    gather_host(c, send.data(), all.data(), pad * (int64_t)sizeof(vg_pair_stat));
+        stats_g.p = host_alloc<vg_pair_stat>(n_tasks);
+        rows.stage(c, std::move(per_rank), my_stats.data());
+    });
+    agree(c, rc_shard, "align shard", { (int64_t)cand_ck }, 1, "were given different candidate pair lists (the same pairs in the same order are required: vg_kmer_shared_sharded returns them sorted)");
+    rows.exchange(c);
     // rows into the canonical order: couple cidx came from pair perm[cidx]; its two tasks are that pair's (r = a) and (r = b) tasks
     {
-        const vg_task* tk = (const vg_task*)tasks_g.p; vg_pair_stat* st = (vg_pair_stat*)stats_g.p;
+        const vg_task* tk = tasks_g.p; vg_pair_stat* st = stats_g.p;
         vg_parallel_chunks(n_cand, n_cand >= (1 << 18) ? std::min(vg_host_threads(), 8) : 1, [&](int64_t lo, int64_t hi, int) {
             for (int64_t cidx = lo; cidx < hi; ++cidx) {
                 const uint32_t pi = perm[(size_t)cidx]; const uint32_t a = cand[pi].a, b = cand[pi].b;
                 for (int d = 0; d < 2; ++d) {
                     const uint32_t r = tk[2 * cidx + d].r;
                     const bool is_a = r == a;
-                    st[2 * cidx + d] = all[(size_t)own_ref[is_a ? a : b] * (size_t)pad + (is_a ? la[pi] : lb[pi])];
+                    st[2 * cidx + d] = rows.block(own_ref[is_a ? a : b])[is_a ? la[pi] : lb[pi]];
                 }
             }
         });
     }
     vg_host_mark("align pairs: rows placed");
-    *tasks_out = (vg_task*)tasks_g.p; *n_tasks_out = nt; *stats_out = (vg_pair_stat*)stats_g.p; tasks_g.p = nullptr; stats_g.p = nullptr;
+    *tasks_out = tasks_g.release(); *n_tasks_out = nt; *stats_out = stats_g.release();
     VG_API_END
 }
 
 // ------------------------------------------------------------------ whole stages, sharded (rank 0 writes the files)
 namespace {
 struct genomes_guard { vg_genomes* g = nullptr; ~genomes_guard() { if (g) vg_genomes_free(g); } };
-struct free_guard { void* p = nullptr; ~free_guard() { if (p) vg_free(p); } };
+// (every rank reads the whole input on the same host: the ranks share its cores instead of each taking `num_threads`)
+int ingest_threads(int num_threads, const vg_comm* c) {
+    return std::max(1, std::min(num_threads, (int)std::max(1u, std::thread::hardware_concurrency() / (unsigned)std::max(1, c->world))));
+}
 }
 
 extern "C" int vg_prefilter_sharded(const char* const* fasta_paths, int n_paths, const char* out_path, const vg_prefilter_params* p, const vg_comm* c) {
@@ -756,15 +754,13 @@ extern "C" int vg_prefilter_sharded(const char* const* fasta_paths, int n_paths,
     if (p->k < 15 || p->k > 30) throw vg_error(VG_EINVAL, "k must be in 15..30");
     if (!(p->kmers_fraction > 0.0) || p->kmers_fraction > 1.0) throw vg_error(VG_EINVAL, "kmers_fraction must be in (0,1]");
     genomes_guard gg;
-    // (every rank reads the whole input on the same host: the ranks share its cores instead of each taking `num_threads`)
-    const int ingest_threads = std::max(1, std::min(p->num_threads, (int)std::max(1u, std::thread::hardware_concurrency() / (unsigned)std::max(1, c->world))));
-    int rc = vg_genomes_load(fasta_paths, n_paths, p->is_multifasta, ingest_threads, &gg.g);
+    int rc = vg_genomes_load(fasta_paths, n_paths, p->is_multifasta, ingest_threads(p->num_threads, c), &gg.g);
     agree(c, rc, "ingest");
     std::vector<int64_t> sizes((size_t)std::max(1, vg_genomes_count(gg.g)));
-    free_guard pairs; int64_t np = 0;
-    check(vg_kmer_shared_sharded(gg.g, p->k, p->kmers_fraction, (uint32_t)std::max(1, p->min_kmers), c, sizes.data(), (vg_pair_count**)&pairs.p, &np));
+    free_guard<vg_pair_count> pairs; int64_t np = 0;
+    check(vg_kmer_shared_sharded(gg.g, p->k, p->kmers_fraction, (uint32_t)std::max(1, p->min_kmers), c, sizes.data(), &pairs.p, &np));
     rc = VG_OK;
-    if (c->rank == 0) rc = vg_write_fltr(gg.g, p->k, p->kmers_fraction, p->min_kmers, p->min_ident, p->max_seqs, sizes.data(), (const vg_pair_count*)pairs.p, np, out_path);
+    if (c->rank == 0) rc = vg_write_fltr(gg.g, p->k, p->kmers_fraction, p->min_kmers, p->min_ident, p->max_seqs, sizes.data(), pairs.p, np, out_path);
     agree(c, rc, "fltr.txt writer");
     VG_API_END
 }
@@ -773,26 +769,26 @@ extern "C" int vg_align_sharded(const char* const* fasta_paths, int n_paths, con
     VG_API_BEGIN
     if (!fasta_paths || n_paths <= 0 || !out_path || !p || !c) throw vg_error(VG_EINVAL, "vg_align_sharded: null argument");
     genomes_guard gg;
-    const int ingest_threads = std::max(1, std::min(p->num_threads, (int)std::max(1u, std::thread::hardware_concurrency() / (unsigned)std::max(1, c->world))));
-    int rc = vg_genomes_load(fasta_paths, n_paths, p->is_multifasta, ingest_threads, &gg.g);
-    free_guard pairs, tasks, regions, rows; int64_t np = 0, nt = 0, nr = 0;
+    int rc = vg_genomes_load(fasta_paths, n_paths, p->is_multifasta, ingest_threads(p->num_threads, c), &gg.g);
+    free_guard<vg_pair_count> pairs; free_guard<vg_task> tasks; free_guard<vg_region> regions; free_guard<vg_pair_stat> rows;
+    int64_t np = 0, nt = 0, nr = 0;
     const bool want_aln = p->out_aln_path != nullptr;
-    if (rc == VG_OK) rc = vg_read_filter(gg.g, p->filter_path, p->filter_threshold, (vg_pair_count**)&pairs.p, &np);
+    if (rc == VG_OK) rc = vg_read_filter(gg.g, p->filter_path, p->filter_threshold, &pairs.p, &np);
     // without an alignment table the ranks start from the pairs (the canonical list is assembled beside the kernels)
-    if (rc == VG_OK && want_aln) rc = vg_align_tasks(gg.g, (const vg_pair_count*)pairs.p, np, (vg_task**)&tasks.p, &nt);
+    if (rc == VG_OK && want_aln) rc = vg_align_tasks(gg.g, pairs.p, np, &tasks.p, &nt);
     agree(c, rc, "ingest / filter");
     std::vector<vg_pair_stat> stats_v;
     const vg_pair_stat* stats = nullptr;
     if (want_aln) {
         stats_v.resize((size_t)std::max<int64_t>(1, nt));
-        check(vg_lz_align_sharded(gg.g, (const vg_task*)tasks.p, nt, &p->lz, c, stats_v.data(), (vg_region**)&regions.p, &nr));
+        check(vg_lz_align_sharded(gg.g, tasks.p, nt, &p->lz, c, stats_v.data(), &regions.p, &nr));
         stats = stats_v.data();
     } else {
-        check(vg_lz_align_pairs_sharded(gg.g, (const vg_pair_count*)pairs.p, np, &p->lz, c, (vg_task**)&tasks.p, &nt, (vg_pair_stat**)&rows.p));
-        stats = (const vg_pair_stat*)rows.p;
+        check(vg_lz_align_pairs_sharded(gg.g, pairs.p, np, &p->lz, c, &tasks.p, &nt, &rows.p));
+        stats = rows.p;
     }
     rc = VG_OK;
-    if (c->rank == 0) rc = vg_write_ani(gg.g, (const vg_task*)tasks.p, stats, nt, (const vg_region*)regions.p, nr, out_path, p);
+    if (c->rank == 0) rc = vg_write_ani(gg.g, tasks.p, stats, nt, regions.p, nr, out_path, p);
     agree(c, rc, "ani.tsv writer");
     VG_API_END
 }

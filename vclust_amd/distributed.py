@@ -91,61 +91,54 @@ def _host_view(ptr, nbytes):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(max(int(nbytes), 1),))[:int(nbytes)]
 
 
-def make_comm(dist=None, device=None, kind=None):
-    """vg_comm for the current process group.  kind: "rccl" (built-in RCCL communicator; any failure to create or
-    self-test it sends every rank to the callback communicator with a line on stderr), "rccl-strict" (the same, but a
-    failure raises on every rank instead: what a measurement of the RCCL path must use -- `bench.py --gpus N`),
-    "callback" (all-gather through torch.distributed); default: $VCLUST_COMM, else rccl on the nccl backend, callback
-    otherwise."""
+def _rccl_comm(lib, dist, device, rank, world, strict):
+    """The built-in RCCL communicator, made fail-soft: no step may leave some ranks inside a collective while another
+    has raised.  Rank 0's id travels with a flag; creation and a first real exchange (vg_comm_selftest) are each
+    agreed on by all ranks before the next collective.  Returns the Comm, or None on EVERY rank after any failure on
+    one of them (a line on stderr; `strict`: raises on every rank instead)."""
     import torch
-    lib = _lib.load()
-    rank, world, _ = dist_env()
+    on_nccl = dist.get_backend() == 'nccl'
     h = C.c_void_p()
-    if dist is None or world == 1:
-        check(lib.vg_comm_create(0, 1, None, None, C.byref(h)))
-        return Comm(h, lib)
-    backend = dist.get_backend()
-    if kind is None:
-        kind = os.environ.get('VCLUST_COMM') or ('rccl' if backend == 'nccl' else 'callback')
-    strict = kind == 'rccl-strict'
-    if kind in ('rccl', 'rccl-strict'):
-        # The built-in RCCL communicator, made fail-soft: no step may leave some ranks inside a collective while another
-        # has raised.  Rank 0's id travels with a flag; creation and a first real exchange (vg_comm_selftest) are each
-        # agreed on by all ranks before the next collective; any failure sends EVERY rank to the callback communicator
-        # (all-gathers through torch.distributed) with a line on stderr.
-        def agree(ok):
-            t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=device if backend == 'nccl' else 'cpu')
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            return int(t.item()) == 1
-        uid = torch.zeros(129, dtype=torch.uint8)
-        if rank == 0:
-            buf = (C.c_uint8 * 128)()
-            if lib.vg_rccl_unique_id(buf, 128) == 0:
-                uid = torch.from_numpy(np.frombuffer(bytes(buf) + b'\x01', dtype=np.uint8).copy())
-            else:
-                print(f'vclust_amd.distributed: no RCCL unique id ({lib.vg_last_error().decode()}): callback communicator', file=sys.stderr)
-        if backend == 'nccl':
-            uid = uid.to(device)
-        dist.broadcast(uid, src=0)
-        raw = bytes(uid.cpu().numpy().tobytes())
-        made = raw[128] == 1 and lib.vg_comm_rccl_create(rank, world, raw[:128], 128, C.byref(h)) == 0
-        if raw[128] == 1 and not made:
-            print(f'vclust_amd.distributed: rank {rank}: vg_comm_rccl_create failed ({lib.vg_last_error().decode()})', file=sys.stderr)
-        if agree(made):
-            tested = lib.vg_comm_selftest(h, 1 << 16) == 0
-            if not tested:
-                print(f'vclust_amd.distributed: rank {rank}: RCCL exchange self-test failed ({lib.vg_last_error().decode()})', file=sys.stderr)
-            if agree(tested):
-                return Comm(h, lib)
-        if made:
-            lib.vg_comm_free(h)
-        h = C.c_void_p()
-        if strict:
-            # (every rank is here: the failure was agreed on)
-            raise RuntimeError('vclust_amd.distributed: VCLUST_COMM=rccl-strict and the built-in RCCL communicator could not be '
-                               'created or failed its self-test on some rank (see stderr): not falling back')
-        if rank == 0:
-            print('vclust_amd.distributed: falling back to the callback communicator (torch.distributed all-gathers)', file=sys.stderr)
+
+    def agree(ok):
+        t = torch.tensor([1 if ok else 0], dtype=torch.int32, device=device if on_nccl else 'cpu')
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        return int(t.item()) == 1
+    uid = torch.zeros(129, dtype=torch.uint8)
+    if rank == 0:
+        buf = (C.c_uint8 * 128)()
+        if lib.vg_rccl_unique_id(buf, 128) == 0:
+            uid = torch.from_numpy(np.frombuffer(bytes(buf) + b'\x01', dtype=np.uint8).copy())
+        else:
+            print(f'vclust_amd.distributed: no RCCL unique id ({lib.vg_last_error().decode()}): callback communicator', file=sys.stderr)
+    if on_nccl:
+        uid = uid.to(device)
+    dist.broadcast(uid, src=0)
+    raw = bytes(uid.cpu().numpy().tobytes())
+    made = raw[128] == 1 and lib.vg_comm_rccl_create(rank, world, raw[:128], 128, C.byref(h)) == 0
+    if raw[128] == 1 and not made:
+        print(f'vclust_amd.distributed: rank {rank}: vg_comm_rccl_create failed ({lib.vg_last_error().decode()})', file=sys.stderr)
+    if agree(made):
+        tested = lib.vg_comm_selftest(h, 1 << 16) == 0
+        if not tested:
+            print(f'vclust_amd.distributed: rank {rank}: RCCL exchange self-test failed ({lib.vg_last_error().decode()})', file=sys.stderr)
+        if agree(tested):
+            return Comm(h, lib)
+    if made:
+        lib.vg_comm_free(h)
+    if strict:
+        # (every rank is here: the failure was agreed on)
+        raise RuntimeError('vclust_amd.distributed: VCLUST_COMM=rccl-strict and the built-in RCCL communicator could not be '
+                           'created or failed its self-test on some rank (see stderr): not falling back')
+    if rank == 0:
+        print('vclust_amd.distributed: falling back to the callback communicator (torch.distributed all-gathers)', file=sys.stderr)
+    return None
+
+
+def _callback_comm(lib, dist, device, rank, world):
+    """The callback communicator: the library's all-gathers (host or device memory) go through torch.distributed."""
+    import torch
+    on_nccl = dist.get_backend() == 'nccl'
 
     def allgather(ctx, send, recv, nbytes, on_device):
         try:
@@ -155,7 +148,7 @@ def make_comm(dist=None, device=None, kind=None):
             else:
                 host_send = _host_view(send, nbytes)
             t = torch.from_numpy(np.ascontiguousarray(host_send).copy())
-            if backend == 'nccl':
+            if on_nccl:
                 t = t.to(device)
             out = torch.empty(world * int(nbytes), dtype=torch.uint8, device=t.device)
             try:
@@ -175,8 +168,27 @@ def make_comm(dist=None, device=None, kind=None):
             return 1
 
     cb = _lib.ALLGATHER_FN(allgather)
+    h = C.c_void_p()
     check(lib.vg_comm_create(rank, world, C.cast(cb, C.c_void_p), None, C.byref(h)))
     return Comm(h, lib, keep=cb)
+
+
+def make_comm(dist=None, device=None, kind=None):
+    """vg_comm for the current process group.  kind: "rccl" (built-in RCCL communicator; any failure to create or
+    self-test it sends every rank to the callback communicator with a line on stderr), "rccl-strict" (the same, but a
+    failure raises on every rank instead: what a measurement of the RCCL path must use -- `bench.py --gpus N`),
+    "callback" (all-gather through torch.distributed); default: $VCLUST_COMM, else rccl on the nccl backend, callback
+    otherwise."""
+    lib = _lib.load()
+    rank, world, _ = dist_env()
+    if dist is None or world == 1:
+        h = C.c_void_p()
+        check(lib.vg_comm_create(0, 1, None, None, C.byref(h)))
+        return Comm(h, lib)
+    if kind is None:
+        kind = os.environ.get('VCLUST_COMM') or ('rccl' if dist.get_backend() == 'nccl' else 'callback')
+    comm = _rccl_comm(lib, dist, device, rank, world, strict=kind == 'rccl-strict') if kind in ('rccl', 'rccl-strict') else None
+    return comm if comm is not None else _callback_comm(lib, dist, device, rank, world)
 
 
 # ------------------------------------------------------------------ sharded stages (in-memory)
