@@ -212,9 +212,17 @@ static void rpush(rvec* v, vo_region x) {
     v->r[v->n++] = x;
 }
 
-int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
-                const vo_lz_params* p, const vo_lz_variant* v,
-                vo_region** out, int* n_out) {
+typedef struct { vo_lz_event* e; int64_t n, cap; } evec;
+static void epush(evec* v, vo_lz_event x) {
+    if (v->n == v->cap) { v->cap = v->cap ? v->cap * 2 : 256; v->e = (vo_lz_event*)realloc(v->e, sizeof(vo_lz_event) * v->cap); }
+    v->e[v->n++] = x;
+}
+
+/* The parse from query position `start` with the state a fresh parse has there (no prediction, no open region,
+ * kept_end = start); evs != NULL: one record per match placed. */
+static int lz_parse_from(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
+                         const vo_lz_params* p, const vo_lz_variant* v, int64_t start,
+                         vo_region** out, int* n_out, evec* evs) {
     pctx c = { ix, NULL, qn, p, v };
     uint8_t* q = (uint8_t*)malloc(qn > 0 ? qn : 1);
     for (int64_t i = 0; i < qn; ++i) q[i] = qry[i] > 3 ? VO_NQRY : qry[i];
@@ -230,8 +238,9 @@ int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
 
     int64_t pred = -1;        /* predicted RR position for q[i]; <0: none */
     int64_t lit = 0;          /* literals since the last match */
-    int64_t i = 0;
-    int64_t kept_end = 0;     /* query end (exclusive) of the last kept region */
+    int64_t i = start;
+    int64_t kept_end = start; /* query end (exclusive) of the last kept region */
+    uint32_t sum_m = 0, sum_a = 0, sum_n = 0;      /* kept matches, kept length, kept regions (the events' virtual sums) */
     int64_t vend = 0;         /* virtual reference end of the open region (rend rule) */
     int64_t lim = v->loop_le ? qn - p->mal + 1 : qn - p->mal;
     const int64_t seed_fwd = v->seed_fwd >= 0 ? v->seed_fwd : p->mrd - 1;
@@ -241,7 +250,8 @@ int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
         cur.n_mismatch = (cur.qend - cur.qstart + 1) - cur.n_match; \
         int keep = v->reg_on_span ? (cur.qend - cur.qstart + 1 >= p->reg) : (cur.n_match >= p->reg); \
         if (v->trace) fprintf(stderr, "REGION %s qs=%d qe=%d nm=%d\n", keep ? "KEPT" : "DROP", cur.qstart + 1, cur.qend + 1, cur.n_match); \
-        if (keep) { rpush(&regs, cur); kept_end = cur.qend + 1; } in_region = 0; } } while (0)
+        if (keep) { rpush(&regs, cur); kept_end = cur.qend + 1; \
+                    sum_m += (uint32_t)cur.n_match; sum_a += (uint32_t)(cur.qend - cur.qstart + 1); sum_n += 1; } in_region = 0; } } while (0)
 
     while (i < lim) {
         int64_t best_pos = 0, best_len = 0;
@@ -305,6 +315,7 @@ int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
         }
 
         if (best_len > 0) {
+            const int64_t ev_i = i;
             if (v->trace && s_len > 0 && a_len > 0) fprintf(stderr, "BOTH i=%lld s_len=%lld s_pos=%lld a_len=%lld a_pos=%lld pred=%lld lit=%lld\n", (long long)i + 1, (long long)s_len, (long long)s_pos, (long long)a_len, (long long)a_pos, (long long)pred, (long long)lit);
             if (v->trace) fprintf(stderr, "i=%lld %s pos=%lld len=%lld pred=%lld lit=%lld\n", (long long)i + 1,
                                   is_close ? "CLOSE" : "DIST", (long long)best_pos, (long long)best_len,
@@ -390,6 +401,15 @@ int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
                 if (pred - 1 > cur.rend) cur.rend = (int32_t)(pred - 1);
                 if (v->rend_mode == 2 && gap_end_ref > cur.rend) cur.rend = (int32_t)gap_end_ref;
             } else { cur.rend = (int32_t)(pred - 1); vend = pred; }
+            if (evs) {
+                /* the sums count the open region up to here, as 32-bit modular values */
+                vo_lz_event ev;
+                ev.ev_i = (int32_t)ev_i;
+                ev.ev_pos = (int32_t)(best_pos >= ix->rc_off ? best_pos - (ix->rc_off - ix->len - 1) : best_pos);
+                ev.ev_end = (int32_t)i; ev.span_ok = (i - cur.qstart >= p->reg);
+                ev.VM = sum_m + (uint32_t)cur.n_match; ev.VA = sum_a - (uint32_t)cur.qstart; ev.VN = sum_n;
+                epush(evs, ev);
+            }
         } else {
             ++i; ++lit;
             if (pred >= 0) ++pred;
@@ -403,4 +423,20 @@ int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
     free(q); free(ql); free(qs);
     *out = regs.r; *n_out = regs.n;
     return 0;
+}
+
+int vo_lz_parse(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
+                const vo_lz_params* p, const vo_lz_variant* v,
+                vo_region** out, int* n_out) {
+    return lz_parse_from(ix, qry, qn, p, v, 0, out, n_out, NULL);
+}
+
+int vo_lz_parse_events(const vo_ref_index* ix, const uint8_t* qry, int64_t qn,
+                       const vo_lz_params* p, const vo_lz_variant* v, int64_t start,
+                       vo_lz_event** events, int64_t* n_events, vo_region** out, int* n_out) {
+    evec evs = { NULL, 0, 0 };
+    if (start < 0) start = 0;
+    int rc = lz_parse_from(ix, qry, qn, p, v, start, out, n_out, &evs);
+    *events = evs.e; *n_events = evs.n;
+    return rc;
 }

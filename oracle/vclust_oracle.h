@@ -118,6 +118,16 @@ void vo_lz_free_index(vo_ref_index* idx);
 int  vo_lz_parse(const vo_ref_index* idx, const uint8_t* qry, int64_t qlen,
                  const vo_lz_params* p, const vo_lz_variant* v,
                  vo_region** out, int* n_out);
+/* The same parse started at query position `start` with the state a fresh parse has there (i = kept_end = start, no
+ * literals, no prediction, no open region; start = 0 is vo_lz_parse), and one record per EVENT, a match the parse places:
+ * where it starts in the query and in the canonical space fwd | N | rc, the query position behind its extension, whether the open region spans >= reg once the
+ * match and its extension are placed (i_after_event - region.qstart >= reg), and the sums at that point as 32-bit modular
+ * values: VM = kept matches + the open region's, VA = kept length - the open region's qstart, VN = kept regions.
+ * *events and *out are malloc'd. */
+typedef struct { int32_t ev_i, ev_pos, ev_end, span_ok; uint32_t VM, VA, VN; } vo_lz_event;
+int  vo_lz_parse_events(const vo_ref_index* idx, const uint8_t* qry, int64_t qlen,
+                        const vo_lz_params* p, const vo_lz_variant* v, int64_t start,
+                        vo_lz_event** events, int64_t* n_events, vo_region** out, int* n_out);
 /* regions are reported in the canonical space fwd | N | rc; 1-based forward coordinates of a position
  * on a given strand (a region's strand is that of its rstart; rend may lie past the strand's end) */
 int64_t vo_rr_to_fwd1(const vo_ref_index* idx, int64_t rr_pos);

@@ -108,6 +108,14 @@ def _tuples(a):
     return list(zip(a['qstart'].tolist(), a['qend'].tolist(), a['rstart'].tolist(), a['rend'].tolist(), a['n_match'].tolist()))
 
 
+def one_run_per_task(region_task, n_regions):
+    """A task's regions are contiguous in the output: the task ids form exactly one run per task that has regions (the
+    number of run starts equals the number of tasks with n_regions > 0)"""
+    tk = np.asarray(region_task)
+    runs = (1 + int(np.count_nonzero(tk[1:] != tk[:-1]))) if len(tk) else 0
+    return runs == int(np.count_nonzero(np.asarray(n_regions) > 0))
+
+
 def assert_rows_and_regions(orc, codes, offsets, tasks, stats, regions, lz=None, cache=None, what=''):
     """Every task: its row equals orc.lz_pair_stat, and (regions is not None) its regions equal orc.lz_regions as an
     ordered list of (qstart, qend, rstart, rend, n_match).  No task is sampled away; every region belongs to a task."""
@@ -116,7 +124,8 @@ def assert_rows_and_regions(orc, codes, offsets, tasks, stats, regions, lz=None,
     by_task = None
     if regions is not None:
         assert len(regions) == 0 or int(regions['task'].max()) < len(tasks), (what, 'a region names no task')
-        order = np.argsort(regions['task'], kind='stable')          # a task's regions are contiguous and in query order
+        assert one_run_per_task(regions['task'], stats['n_regions']), (what, "a task's regions are not contiguous in the output")
+        order = np.argsort(regions['task'], kind='stable')          # (a no-op after the line above: kept so that a failure names tasks)
         sorted_regions = regions[order]
         first = np.searchsorted(sorted_regions['task'], np.arange(len(tasks) + 1))
         by_task = (sorted_regions, first)

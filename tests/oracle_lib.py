@@ -59,7 +59,7 @@ def lib():
         if not LIB.exists():
             build()
         L = C.CDLL(str(LIB))
-        if not hasattr(L, 'vo_last_stage_cpu'):          # a library built from older sources
+        if not (hasattr(L, 'vo_last_stage_cpu') and hasattr(L, 'vo_lz_parse_events')):          # a library built from older sources
             build()
             L = C.CDLL(str(LIB))
         L.vo_read_fasta.argtypes = [C.c_char_p, C.c_int, C.POINTER(GenomeSet)]
@@ -82,6 +82,10 @@ def lib():
         L.vo_lz_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LzParams), C.POINTER(LzVariant),
                                   C.POINTER(C.POINTER(OracleRegion)), C.POINTER(C.c_int)]
         L.vo_lz_parse.restype = C.c_int
+        L.vo_lz_parse_events.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(LzParams), C.POINTER(LzVariant), C.c_int64,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                         C.POINTER(C.POINTER(OracleRegion)), C.POINTER(C.c_int)]
+        L.vo_lz_parse_events.restype = C.c_int
         L.vo_path_rows.argtypes = [C.POINTER(GenomeSet), C.c_int, C.c_int, C.c_double, C.POINTER(LzParams),
                                    C.POINTER(C.POINTER(PairStat)), C.POINTER(C.c_int64)]
         L.vo_path_rows.restype = C.c_int
@@ -206,6 +210,74 @@ def lz_regions(q, r, lz=None):
             L.free(C.cast(regs, C.c_void_p))
         L.vo_lz_free_index(ix)
     return out
+
+
+EVENT_DTYPE = np.dtype([('ev_i', '<i4'), ('ev_pos', '<i4'), ('ev_end', '<i4'), ('span_ok', '<i4'), ('VM', '<u4'), ('VA', '<u4'), ('VN', '<u4')])
+
+
+def lz_events(q, r, start=0, lz=None, with_row=False):
+    """The events (every match placed) of the oracle's parse of q against r from query position `start` with the state a
+    fresh parse has there (start = 0: the ordinary parse): a record array (ev_i, ev_pos in fwd | N | rc, ev_end = the
+    query position behind the match and its extension, span_ok, and the
+    virtual sums VM, VA, VN as 32-bit modular values -- vo_lz_parse_events).  with_row: -> (events, (n_match, aln_len,
+    n_regions) of the regions that parse keeps)."""
+    prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    r = np.ascontiguousarray(r, dtype=np.uint8)
+    L = lib()
+    v = LzVariant()
+    L.vo_lz_default_variant(C.byref(v))
+    ix = L.vo_lz_build_index(r.ctypes.data_as(C.c_void_p), len(r), C.byref(prm), C.byref(v))
+    if not ix:
+        raise MemoryError('vo_lz_build_index')
+    try:
+        return lz_events_ix(ix, prm, v, q, start, with_row)
+    finally:
+        L.vo_lz_free_index(ix)
+
+
+class LzIndex:
+    """The oracle's index of one reference, kept for several lz_events calls (`with LzIndex(r, lz) as ix: ix.events(q, start)`)"""
+
+    def __init__(self, r, lz=None):
+        self.prm = LzParams(**{**DEFAULT_LZ, **(lz or {})})
+        self.r = np.ascontiguousarray(r, dtype=np.uint8)
+        self.v = LzVariant()
+        lib().vo_lz_default_variant(C.byref(self.v))
+        self.ix = lib().vo_lz_build_index(self.r.ctypes.data_as(C.c_void_p), len(self.r), C.byref(self.prm), C.byref(self.v))
+        if not self.ix:
+            raise MemoryError('vo_lz_build_index')
+
+    def events(self, q, start=0, with_row=False):
+        return lz_events_ix(self.ix, self.prm, self.v, np.ascontiguousarray(q, dtype=np.uint8), start, with_row)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        lib().vo_lz_free_index(self.ix)
+        self.ix = None
+
+
+def lz_events_ix(ix, prm, v, q, start, with_row):
+    L = lib()
+    ev = C.c_void_p(); n_ev = C.c_int64(); regs = C.POINTER(OracleRegion)(); n = C.c_int()
+    try:
+        L.vo_lz_parse_events(ix, q.ctypes.data_as(C.c_void_p), len(q), C.byref(prm), C.byref(v), int(start),
+                             C.byref(ev), C.byref(n_ev), C.byref(regs), C.byref(n))
+        out = np.zeros(n_ev.value, dtype=EVENT_DTYPE)
+        if n_ev.value:
+            C.memmove(out.ctypes.data, ev, n_ev.value * EVENT_DTYPE.itemsize)
+        row = (0, 0, 0)
+        if n.value:
+            raw = np.ctypeslib.as_array(C.cast(regs, C.POINTER(C.c_int32)), shape=(n.value, 6)).astype(np.int64)
+            row = (int(raw[:, 4].sum()) & 0xffffffff, int((raw[:, 1] - raw[:, 0] + 1).sum()) & 0xffffffff, int(n.value))
+    finally:
+        if regs:
+            L.free(C.cast(regs, C.c_void_p))
+        if ev:
+            L.free(ev)
+    return (out, row) if with_row else out
 
 
 def path_rows(codes, offsets, k=25, min_kmers=20, min_ident=0.7, lz=None, threads=None):

@@ -9,7 +9,12 @@ branch-free window rule ((aw, am) = (15, 7)).
 Every ordered pair of the set is parsed in separate processes (developer switches are read once per process): the
 one-wave FAST kernel, the four-wave one, the one that also writes regions, the general kernel and the general kernel
 that writes regions.  The region-writing variants hand their regions back: every task's regions equal orc.lz_regions as
-an ordered list (lz_checks.assert_rows_and_regions)."""
+an ordered list (lz_checks.assert_rows_and_regions).
+The four-wave kernel splits a query among its waves only from qlen - mal >= 8 192 on, i.e. from 8 203 bases: of this set
+only three sequences reach that -- `ref` (13 001 bases), the tandem repeat `rep` and its mutated copy (9 200 bases
+each); on every other query wave 0 parses alone, so
+`fast_segments` checks these edges in the four-wave kernel's code, not the hand-over between segments.  The hand-over has
+its own inputs and its own file: test_gpu_parse_handover.py."""
 import os
 import pathlib
 import subprocess

@@ -8,6 +8,7 @@ import numpy as np
 root = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(root)); sys.path.insert(0, str(root / 'tests'))
 import oracle_lib as orc
+import lz_checks as lc
 from vclust_amd import api, synth
 api.set_device(0)
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
@@ -100,7 +101,7 @@ for case in range(n_cases):
               np.array_equal(np.bincount(tk, weights=span, minlength=len(tasks)).astype(np.int64), stats['aln_len'].astype(np.int64)) and
               bool(np.all(span >= (lz or {}).get('reg', 35))))
         same = tk[1:] == tk[:-1]
-        ok = ok and bool(np.all(tk[1:] >= tk[:-1]) or True) and bool(np.all(rg['qstart'][1:][same] > rg['qend'][:-1][same]))
+        ok = ok and lc.one_run_per_task(tk, stats['n_regions']) and bool(np.all(rg['qstart'][1:][same] > rg['qend'][:-1][same]))
     if not ok:
         bad += 1; print('REGIONS MISMATCH case', case, 'seed', seed0 + case, lz, fit, flush=True)
     # ... and equal the oracle's, task by task, as ordered lists of (qstart, qend, rstart, rend, n_match)
