@@ -56,49 +56,75 @@ def _check(api, lengths, rows, label=None, n_groups=None):
     return got[0].tobytes() + got[1].tobytes()
 
 
-def test_pair_unions(api):
-    """One object, three partners: rows that overlap, nest, touch (end + 1 == next start), repeat, and come unsorted."""
+def pair_unions_input():
     rows = [(0, 1, 40, 59), (0, 1, 10, 19), (0, 1, 15, 30), (0, 1, 31, 35),      # overlap, then touch: 10..35
             (0, 2, 5, 90), (0, 2, 20, 30), (0, 2, 20, 30), (0, 2, 5, 5),          # nested and repeated
             (0, 3, 70, 79), (0, 3, 60, 69), (0, 3, 80, 80), (0, 3, 0, 0),         # three that touch, unsorted
             (0, 1, 40, 59), (0, 0, 0, 99)]                                        # a repeat, a self row
-    _check(api, [100, 7, 7, 7], rows)
-    got = _library(api, [100, 7, 7, 7], rows)
+    return [100, 7, 7, 7], rows
+
+
+def test_pair_unions(api):
+    """One object, three partners: rows that overlap, nest, touch (end + 1 == next start), repeat, and come unsorted."""
+    lengths, rows = pair_unions_input()
+    _check(api, lengths, rows)
+    got = _library(api, lengths, rows)
     # (60 is the end + 1 of partner 1 and the start of partner 3: one breakpoint, and no segment starts there)
     assert got[2] == dict(rows_kept=13, intervals=5, breakpoints=9, segments=8 + 3)
     assert got[0]['sum_in'][0] == 26 + 20 + 86 + 1 + 21
 
 
+ENDS_INPUT = ([50, 1, 0, 9, 30, 12], [(0, 5, 0, 9), (0, 5, 40, 49), (0, 4, 0, 49), (1, 0, 0, 0), (4, 0, 29, 29), (4, 1, 0, 0), (4, 5, 0, 29)])
+ENDS_MORE = [([0, 0, 0], []), ([5], []), ([5, 5], [(0, 0, 0, 4), (1, 1, 2, 3)])]      # no rows; the last: self rows only
+
+
 def test_ends(api):
     """Position 0, a row that ends at len - 1 (a breakpoint at len), lengths 1 and 0, no rows at all, a partner that is never a query."""
-    lengths = [50, 1, 0, 9, 30, 12]
-    rows = [(0, 5, 0, 9), (0, 5, 40, 49), (0, 4, 0, 49), (1, 0, 0, 0), (4, 0, 29, 29), (4, 1, 0, 0), (4, 5, 0, 29)]
+    lengths, rows = ENDS_INPUT
     _check(api, lengths, rows)
     records, segments, run = _library(api, lengths, rows)
     assert [tuple(t) for t in segments.tolist() if t[0] in (1, 3, 5)] == [(1, 0, 0, 1, 0), (3, 0, 8, 0, 0), (5, 0, 11, 0, 0)]
     assert records['segments'].tolist() == [3, 1, 0, 1, 3, 1]
-    _check(api, [0, 0, 0], [])
-    _check(api, [5], [])
-    _check(api, [5, 5], [(0, 0, 0, 4), (1, 1, 2, 3)])          # self rows only
+    for more in ENDS_MORE:
+        _check(api, *more)
+
+
+NET_ZERO_INPUT = ([60, 5, 5, 5], [(0, 1, 10, 29), (0, 2, 30, 49)])
+NET_ZERO_LABEL = [0, 0, 1, 1]
+NET_ZERO_ENDS = [([40, 5, 5], [(0, 1, 0, 19), (0, 2, 20, 39)], [0, 0, 0], 1), ([40, 5, 5], [(0, 1, 0, 19), (0, 2, 20, 39)], [0, 0, 1], 2)]
 
 
 def test_net_zero_breakpoints(api):
     """Partner A ends at x and partner B starts at x + 1: one segment inside one channel, two across the channels (same total depth)."""
-    lengths, rows = [60, 5, 5, 5], [(0, 1, 10, 29), (0, 2, 30, 49)]
+    lengths, rows = NET_ZERO_INPUT
     _check(api, lengths, rows)
     records, segments, run = _library(api, lengths, rows)
     assert [tuple(t) for t in segments.tolist() if t[0] == 0] == [(0, 0, 9, 0, 0), (0, 10, 49, 1, 0), (0, 50, 59, 0, 0)] and run['breakpoints'] == 3
-    label = [0, 0, 1, 1]
+    label = NET_ZERO_LABEL
     _check(api, lengths, rows, label, 2)
     records, segments, run = _library(api, lengths, rows, label, 2)
     assert [tuple(t) for t in segments.tolist() if t[0] == 0] == [(0, 0, 9, 0, 0), (0, 10, 29, 1, 0), (0, 30, 49, 0, 1), (0, 50, 59, 0, 0)]
     assert records['max_depth'][0] == 1
     # the same at the two ends of the object
-    _check(api, [40, 5, 5], [(0, 1, 0, 19), (0, 2, 20, 39)], [0, 0, 0], 1)
-    _check(api, [40, 5, 5], [(0, 1, 0, 19), (0, 2, 20, 39)], [0, 0, 1], 2)
+    for case in NET_ZERO_ENDS:
+        _check(api, *case)
 
 
 TILE_OBJECTS = 307
+
+
+def tile_edges_input():
+    m = TILE_OBJECTS
+    rng = np.random.default_rng(5)
+    lengths = [int(x) for x in rng.integers(6, 20, m + 1)]
+    rows = []
+    for k in range(1, m + 1):
+        partners = [p for p in rng.permutation(m + 1).tolist() if p != k][:k]
+        for p in partners:
+            s = int(rng.integers(0, lengths[k]))
+            rows.append((k, p, s, int(rng.integers(s, lengths[k]))))
+    rows = [rows[i] for i in rng.permutation(len(rows))]
+    return lengths, rows, [int(x) for x in rng.integers(0, 3, m + 1)], 3
 
 
 def test_tile_edges(api):
@@ -109,21 +135,10 @@ def test_tile_edges(api):
     m = 307: 47 278 rows and 94 556 events, four times that chunk."""
     m = TILE_OBJECTS
     assert 2 * (m * (m + 1) // 2) >= 4 * 23552 and m * (m + 1) // 2 >= 4 * 1024
-    rng = np.random.default_rng(5)
-    lengths = [int(x) for x in rng.integers(6, 20, m + 1)]
-    rows = []
-    for k in range(1, m + 1):
-        partners = [p for p in rng.permutation(m + 1).tolist() if p != k][:k]
-        for p in partners:
-            s = int(rng.integers(0, lengths[k]))
-            rows.append((k, p, s, int(rng.integers(s, lengths[k]))))
-    rows = [rows[i] for i in rng.permutation(len(rows))]
-    _check(api, lengths, rows, [int(x) for x in rng.integers(0, 3, m + 1)], 3)
+    _check(api, *tile_edges_input())
 
 
-def test_hot_object(api):
-    """One object with 5 000 rows from 300 partners (several workgroups of rows, events and segments in one object) beside 2 000
-    objects with one row each."""
+def hot_object_input():
     rng = np.random.default_rng(6)
     n = 2301
     lengths = [40000] + [int(x) for x in rng.integers(1, 50, n - 1)]
@@ -134,13 +149,26 @@ def test_hot_object(api):
     for k in range(301, n):
         s = int(rng.integers(0, lengths[k]))
         rows.append((k, int(rng.integers(0, n)), s, int(rng.integers(s, lengths[k]))))
-    label = [int(x) for x in rng.integers(0, 4, n)]
+    return lengths, rows, [int(x) for x in rng.integers(0, 4, n)], 4
+
+
+def test_hot_object(api):
+    """One object with 5 000 rows from 300 partners (several workgroups of rows, events and segments in one object) beside 2 000
+    objects with one row each."""
+    lengths, rows, label, _ = hot_object_input()
     _check(api, lengths, rows, label, 4)
     records, segments, run = _library(api, lengths, rows, label, 4)
     assert records['segments'][0] > 4 * 1024 and records['partners_in'][0] + records['partners_out'][0] == 300
 
 
-def test_groups(api):
+GROUPS_FULL_LABEL, GROUPS_SPARSE_LABEL = [0, 1, 0, 2, 1, 2, 1, 0, 2], [5, 1, 5, 7, 1, 7, 1, 5, 7]
+
+
+def groups_full(lengths, rows):
+    return rows + [(q, r, 0, lengths[q] - 1) for q in (1, 4, 6) for r in (1, 4, 6)]
+
+
+def groups_input():
     rng = np.random.default_rng(7)
     n = 9
     lengths = [int(x) for x in rng.integers(20, 60, n)]
@@ -150,19 +178,24 @@ def test_groups(api):
             for _ in range(2):
                 s = int(rng.integers(0, lengths[q]))
                 rows.append((q, r, s, int(rng.integers(s, lengths[q]))))
+    return lengths, rows
+
+
+def test_groups(api):
+    lengths, rows = groups_input()
+    n = len(lengths)
     plain = _check(api, lengths, rows)                                     # no labels
     assert plain == _check(api, lengths, rows, [0] * n, 1)
     records = _library(api, lengths, rows, list(range(n)), n)[0]           # every object its own group
     _check(api, lengths, rows, list(range(n)), n)
     assert not records['core'].any() and not records['sum_in'].any() and not records['partners_in'].any()
     # a group in which every other member covers everything: core == len
-    full = rows + [(q, r, 0, lengths[q] - 1) for q in (1, 4, 6) for r in (1, 4, 6)]
-    label = [0, 1, 0, 2, 1, 2, 1, 0, 2]
+    full, label = groups_full(lengths, rows), GROUPS_FULL_LABEL
     _check(api, lengths, full, label, 3)
     records = _library(api, lengths, full, label, 3)[0]
     assert all(records['core'][q] == lengths[q] for q in (1, 4, 6))
     # more groups than labels used
-    _check(api, lengths, rows, [5, 1, 5, 7, 1, 7, 1, 5, 7], 12)
+    _check(api, lengths, rows, GROUPS_SPARSE_LABEL, 12)
 
 
 def test_order_and_threads(api, golden, tmp_path):
@@ -183,8 +216,7 @@ def test_order_and_threads(api, golden, tmp_path):
     assert files[0] == files[1]
 
 
-def test_random(api):
-    """200 objects, lengths 1..3 000, 20 000 rows, labels in 12 groups."""
+def random_input():
     rng = np.random.default_rng(9)
     n = 200
     lengths = [int(x) for x in rng.integers(1, 3001, n)]
@@ -193,7 +225,25 @@ def test_random(api):
         q = int(rng.integers(0, n))
         s = int(rng.integers(0, lengths[q]))
         rows.append((q, int(rng.integers(0, n)), s, min(lengths[q] - 1, s + int(rng.integers(0, 200)))))
-    _check(api, lengths, rows, [int(x) for x in rng.integers(0, 12, n)], 12)
+    return lengths, rows, [int(x) for x in rng.integers(0, 12, n)], 12
+
+
+def test_random(api):
+    """200 objects, lengths 1..3 000, 20 000 rows, labels in 12 groups."""
+    _check(api, *random_input())
+
+
+def constructed_inputs():
+    """every (lengths, rows, label, n_groups) this file builds by hand or by seed (the golden table apart), for the tests that hold
+    the two references to each other"""
+    out = [pair_unions_input() + (None, None), ENDS_INPUT + (None, None)] + [m + (None, None) for m in ENDS_MORE]
+    out += [NET_ZERO_INPUT + (None, None), NET_ZERO_INPUT + (NET_ZERO_LABEL, 2)] + NET_ZERO_ENDS
+    out += [tile_edges_input(), hot_object_input(), random_input()]
+    lengths, rows = groups_input()
+    n = len(lengths)
+    out += [(lengths, rows, None, None), (lengths, rows, [0] * n, 1), (lengths, rows, list(range(n)), n),
+            (lengths, groups_full(lengths, rows), GROUPS_FULL_LABEL, 3), (lengths, rows, GROUPS_SPARSE_LABEL, 12)]
+    return out
 
 
 def _expected_files(g, clusters):

@@ -1,7 +1,8 @@
 """Markov clustering on the MI355X (vg_cluster_mcl_graph, vg_cluster_mcl, `cluster --algorithm mcl`) against the sequential restatement
 (tests/mcl_restatement.py).  The definition is integer arithmetic throughout, so everything must be EQUAL: labels, representatives,
 the iteration count, the convergence flag, the chaos of the last iteration and the matrix itself after 1, 2 and 3 iterations and at
-the stop -- on the LDS path and, with the table shrunk to 64 slots, on the spill path."""
+the stop -- on the LDS path and, with the table shrunk to 64 slots, on the spill path; and at the default table of 4 096 slots
+on graphs whose rows exceed it (mcl_cases.table_size_cases)."""
 import pathlib
 import subprocess
 import sys
@@ -18,7 +19,8 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 VCLUST = ROOT / 'vclust.py'
 CASES = mcl_cases.all_cases()
 DEFAULT_SLOTS, SMALL_SLOTS = 4096, 64
-_TRACES = {}
+_TRACES, _FIGURES = {}, {}
+TABLE_CASES = mcl_cases.table_size_cases()
 
 
 def run(*args, timeout=300):
@@ -47,15 +49,13 @@ def _trace(name, n, rows, params):
     return _TRACES[name]
 
 
-def _spill_rows(start, trace, iterations, slots):
+def _spill_rows(name, start, trace, iterations, slots):
     """rows whose candidate bound (the sum of nnz over the rows they name, at most the number of objects) exceeds the table AND whose
-    distinct candidate columns fill more than 3/4 of it, over the matrices that were expanded"""
-    total = 0
-    for m in [start] + [t['matrix'] for t in trace[:iterations - 1]]:
-        for row in m:
-            if min(sum(len(m[k]) for k in row), len(m)) > slots and len(set().union(*(m[k] for k in row))) > slots - slots // 4:
-                total += 1
-    return total
+    distinct candidate columns fill more than 3/4 of it, over the matrices that were expanded (mcl_cases.predict, once per case
+    and table)"""
+    if (name, slots) not in _FIGURES:
+        _FIGURES[name, slots] = mcl_cases.predict(start, trace, len(trace), slots)
+    return sum(f['spilled'] for f in _FIGURES[name, slots][:iterations])
 
 
 def _check(api, name, n, rows, params, slots=DEFAULT_SLOTS, limits=(1, 2, 3, None)):
@@ -73,7 +73,7 @@ def _check(api, name, n, rows, params, slots=DEFAULT_SLOTS, limits=(1, 2, 3, Non
         want_label, want_rep = cr.labels(mr.components(n, want['matrix']))
         assert label.tolist() == want_label and rep.tolist() == want_rep, what
         assert stats['n_edges'] == len(e) and stats['nnz'] == len(col) and stats['max_row_seen'] == max(len(x) for x in want['matrix']), what
-        spill = _spill_rows(start, trace, want['iterations'], slots)
+        spill = _spill_rows(name, start, trace, want['iterations'], slots)
         assert stats['spill_rows'] == spill and stats['lds_rows'] == n * want['iterations'] - spill, what
         # without the matrix outputs the call gives the same clusters
         label2, rep2, stats2 = api.cluster_mcl_graph(n, q, r, w, **kw)
@@ -118,6 +118,37 @@ def test_the_spill_path_gives_the_same(api):
     assert spilled > 0
     name, n, rows, params = next(c for c in CASES if c[0] == 'widths')
     assert _check(api, name, n, rows, params, limits=(None,))['spill_rows'] == 0         # (the default is back)
+
+
+@pytest.mark.parametrize('case', [c for c in TABLE_CASES if c[4] == DEFAULT_SLOTS], ids=[c[0] for c in TABLE_CASES if c[4] == DEFAULT_SLOTS])
+def test_rows_above_the_real_table(api, case):
+    """The default table of 4 096 slots: rows whose bound exceeds it are tried in it and kept up to 3 072 distinct columns, given to
+    the spill path from 3 073; the select of the finish over thousands of candidates, in LDS and in a spill row's global segment.
+    That the case does so is read off the restatement first (mcl_cases.reaches_its_path)."""
+    name, n, rows, params, slots, expected = case
+    e, start, trace = _trace(name, n, rows, params)
+    figures = mcl_cases.reaches_its_path(case, start, trace)
+    stats = _check(api, name, n, rows, params, limits=(None,))
+    assert stats['spill_rows'] == sum(f['spilled'] for f in figures) and stats['iterations'] == len(figures)
+    if 'widest' in expected:
+        assert stats['max_row_seen'] == expected['widest']
+
+
+def test_two_spill_batches(api):
+    """One iteration whose spill rows need more records than are sorted at once (2^25): the batch loop takes a second trip.  The
+    table is shrunk to 64 slots, or no graph of seconds would spill that much; the restatement does the same 5 x 10^7 products,
+    which is what this test costs."""
+    case = next(c for c in TABLE_CASES if c[4] == SMALL_SLOTS)
+    name, n, rows, params, slots, expected = case
+    e, start, trace = _trace(name, n, rows, params)
+    figures = mcl_cases.reaches_its_path(case, start, trace)
+    assert max(f['records'] for f in figures) > 1 << 25 and max(f['records'] for f in figures) < 1 << 26
+    api.cluster_mcl_set_table_slots(SMALL_SLOTS)
+    try:
+        stats = _check(api, name, n, rows, params, slots=SMALL_SLOTS, limits=(None,))
+    finally:
+        api.cluster_mcl_set_table_slots(0)
+    assert stats['spill_rows'] == sum(f['spilled'] for f in figures) == 2 * n and stats['converged'] == 1
 
 
 def test_not_converged_is_still_a_result(api):

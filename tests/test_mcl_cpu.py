@@ -88,6 +88,23 @@ def test_the_cases_of_the_gpu_test_converge():
         assert sorted(first) == list(range(8)), distinct
 
 
+def test_the_table_size_cases_reach_their_paths():
+    """the cases of the GPU test at the real table: what the predictor says of each (rows tried, distinct columns of the named row,
+    rows and records spilled, per iteration) is what the case states, so a changed case cannot stop reaching its path unnoticed"""
+    cases = mcl_cases.table_size_cases()
+    assert [c[4] for c in cases].count(64) == 1 and len({c[0] for c in cases}) == len(cases) == 8
+    for case in cases:
+        name, n, rows, params, slots, expected = case
+        e = cr.edges(rows)
+        trace = mr.trace(n, e, **params)
+        figures = mcl_cases.reaches_its_path(case, mr.start(n, e), trace)
+        assert 'max_iterations' in params or trace[-1]['converged'] == 1, name
+        if slots == 64:
+            assert figures[1]['records'] > 1 << 25, name
+    # the crowns differ by one leaf, the limit by one column: 3/4 of 4 096
+    assert cases[0][5]['figures'][0]['distinct'] == 4096 - 4096 // 4 == cases[1][5]['figures'][0]['distinct'] - 1
+
+
 def test_symbols_exported_declared_and_listed():
     lib = _lib.load()
     header = (ROOT / 'include' / 'vclust_gpu.h').read_text()
