@@ -1,6 +1,7 @@
 // fasta_ingest — the FASTA readers of the library on plain, gzip and BGZF files, well-formed and damaged:
 //   vg_genomes_load (host part: no upload)      names, lengths and vg_genomes_codes against a restatement of the format
-//   vg_fasta_read / vg_fasta_write_records      the records of the deduplicate stage, read and written back byte for byte
+//   ... in directory mode, vg_genomes_load_db_new   one genome per file (records joined by N), database + new genomes and its refusals
+//   vg_fasta_read / vg_fasta_write_records     the records of the deduplicate stage, read and written back byte for byte
 //   vg_fasta_write_kept                         the deduplicate stage's output, plain and as gzip members at levels 1, 5 and 9
 //
 //   fasta_ingest <tests/golden/example> [threads ...]        (default: 1 3 16)
@@ -78,10 +79,14 @@ std::string bgzf(const std::string& text, size_t block, std::vector<size_t>* sta
 }
 
 // ---- the calls
-struct loaded { int status = 0; std::string message; std::vector<record> recs; };
-loaded load(const std::string& path, int threads) {
-    loaded l; vg_genomes* g = nullptr; const char* paths[1] = { path.c_str() };
-    l.status = vg_genomes_load(paths, 1, 1, threads, &g);
+struct loaded { int status = 0; std::string message; std::vector<record> recs; std::vector<int> n_parts; int n_db = -1; };
+// vg_genomes_load of `paths`, or (db not empty) vg_genomes_load_db_new of the database files `db` and the new files `paths`
+loaded load_set(const std::vector<std::string>& db, const std::vector<std::string>& paths, int multisample, int threads) {
+    loaded l; vg_genomes* g = nullptr; std::vector<const char*> d, p;
+    for (const std::string& s : db) d.push_back(s.c_str());
+    for (const std::string& s : paths) p.push_back(s.c_str());
+    l.status = db.empty() ? vg_genomes_load(p.data(), (int)p.size(), multisample, threads, &g)
+                          : vg_genomes_load_db_new(d.data(), (int)d.size(), p.data(), (int)p.size(), multisample, threads, &g, &l.n_db);
     if (l.status != VG_OK) { l.message = vg_last_error(); return l; }
     std::vector<int64_t> len((size_t)vg_genomes_count(g));
     if (!len.empty()) vg_genomes_lengths(g, len.data());
@@ -89,11 +94,12 @@ loaded load(const std::string& path, int threads) {
         record r; r.name = vg_genomes_name(g, i); r.codes.resize((size_t)len[(size_t)i] + 1, 0xee);     // one byte more: nothing is written behind the length
         if (vg_genomes_codes(g, i, r.codes.data()) != VG_OK || r.codes.back() != 0xee) l.message = "vg_genomes_codes failed";
         r.codes.pop_back();
-        l.recs.push_back(r);
+        l.recs.push_back(r); l.n_parts.push_back(g->n_parts[(size_t)i]);
     }
     delete g;
     return l;
 }
+loaded load(const std::string& path, int threads) { return load_set({}, { path }, 1, threads); }
 bool same(const std::vector<record>& a, const std::vector<record>& b) {
     if (a.size() != b.size()) return false;
     for (size_t i = 0; i < a.size(); ++i) if (a[i].name != b[i].name || a[i].codes != b[i].codes) return false;
@@ -202,6 +208,61 @@ void damaged(const std::string& tag, const std::string& bytes, const std::string
     } catch (const vg_error& e) { line("read  " + tag + ": status " + std::to_string(e.code) + " " + scrub(e.what())); if (!*e.what()) fail("vg_fasta_read " + tag + ": an error without a message"); }
 }
 
+// ---- the loader's other two modes
+// directory mode: a file is one genome, its records joined by one N (code 4) each and named by the file; a file without a record is none
+void file_genome(const std::string& path, const std::string& text, std::vector<record>& out) {
+    const std::vector<record> parts = restate(text);
+    if (parts.empty()) return;
+    record r; r.name = path.substr(path.find_last_of('/') + 1);
+    for (size_t k = 0; k < parts.size(); ++k) { if (k) r.codes.push_back(4); r.codes.insert(r.codes.end(), parts[k].codes.begin(), parts[k].codes.end()); }
+    out.push_back(r);
+}
+void report(const std::string& tag, const loaded& l) {
+    std::string s = "load  " + tag + ": status " + std::to_string(l.status) + " " + (l.status ? scrub(l.message) : digest(l.recs));
+    if (l.status == VG_OK) { s += ", parts"; for (const int n : l.n_parts) s += " " + std::to_string(n); if (l.n_db >= 0) s += ", n_db " + std::to_string(l.n_db); }
+    line(s);
+}
+void refused(const std::string& tag, const loaded& l, int status, const std::string& message) {
+    report(tag, l);
+    if (l.status != status || scrub(l.message) != message) fail("load " + tag + ": expected status " + std::to_string(status) + " " + message);
+}
+void loader_modes(int threads) {
+    const std::string one = ">solo one record\nACGTNACGTTGCA\nGGA\n", three = ">p1 x\nACGT\n>p2\nGG\nCC\n>p3\nTTNA\n", two = ">t1\nACGTACGTAC\n>t2\nGGGGCCCCNN\nTT\n";
+    const std::string none = "no record in this file\nACGT\n", crlf = ">c x\r\nACGT\r\nNNAC\r\n>d\r\nTT\r\n";
+    {   // directory mode over five files
+        const std::vector<std::string> paths = { fresh(one, ".fna"), fresh(three, ".fna"), fresh(gz(two, 6), ".fna.gz"), fresh(none, ".fna"), fresh(crlf, ".fna") };
+        const std::string* texts[] = { &one, &three, &two, &none, &crlf };
+        std::vector<record> want;
+        for (size_t i = 0; i < paths.size(); ++i) file_genome(paths[i], *texts[i], want);
+        const loaded l = load_set({}, paths, 0, threads);
+        report("directory, five files", l);
+        if (l.status != VG_OK || !l.message.empty() || !same(l.recs, want) || l.n_parts != std::vector<int>({ 1, 3, 2, 2 })) { fail("load directory: not one genome per file with a record, named by the file, in path order"); return; }
+        const std::vector<uint8_t>& c = l.recs[1].codes;      // p1 (4 bases) N p2 (4) N p3 (4)
+        if (c.size() != 4 + 4 + 4 + 2 || c[4] != 4 || c[9] != 4) fail("load directory: the three records are not joined by one N each");
+    }
+    const std::string db = ">d1 the database\nACGTACGT\n>d2\nGGNCC\n", fresh_ones = ">n1\nTTTT\nAC\n>n2 x\r\nACGU\r\n";
+    {   // database + new, multi-FASTA: the genomes of the two files behind one another
+        const loaded l = load_set({ fresh(db, ".fna") }, { fresh(fresh_ones, ".fna") }, 1, threads), whole = load(fresh(db + fresh_ones, ".fna"), threads);
+        report("db + new, multi-FASTA", l);
+        if (l.status != VG_OK || whole.status != VG_OK || !same(l.recs, whole.recs) || !same(l.recs, restate(db + fresh_ones)) || l.n_db != 2) fail("load db + new, multi-FASTA: not vg_genomes_load of the concatenation with 2 database genomes");
+    }
+    {   // database + new, directory mode
+        const std::vector<std::string> d = { fresh(one, ".fna"), fresh(three, ".fna") }, n = { fresh(gz(two, 6), ".fna.gz") };
+        std::vector<record> want;
+        file_genome(d[0], one, want); file_genome(d[1], three, want); file_genome(n[0], two, want);
+        const loaded l = load_set(d, n, 0, threads);
+        report("db + new, directory", l);
+        if (l.status != VG_OK || !same(l.recs, want) || l.n_db != 2 || l.n_parts != std::vector<int>({ 1, 3, 2 })) fail("load db + new, directory: not the three files' genomes with 2 database genomes");
+    }
+    refused("db + new, a name on both sides", load_set({ fresh(db, ".fna") }, { fresh(">n1\nTT\n>d2 again\nCC\n", ".fna") }, 1, threads), VG_EINVAL,
+            "vg_genomes_load_db_new: the name d2 occurs in the database and in the new genomes");
+    refused("db + new, one genome in all", load_set({ fresh(">d1\nACGT\n", ".fna") }, { fresh(none, ".fna") }, 1, threads), VG_EINVAL,
+            "vg_genomes_load_db_new: the database and the new genomes together are 1 genome(s); pairs need at least 2");
+    refused("db + new, two database files in multi-FASTA mode", load_set({ fresh(db, ".fna"), fresh(one, ".fna") }, { fresh(fresh_ones, ".fna") }, 1, threads), VG_EINVAL,
+            "vg_genomes_load_db_new: multi-FASTA mode takes one database file and one file of new genomes");
+    refused("db + new, a missing new file", load_set({ fresh(db, ".fna") }, { g_dir->path + "/missing.fna" }, 1, threads), VG_EIO, "cannot open <dir>/missing.fna");
+}
+
 std::string sized(const std::string& unit, size_t size, char last) {
     std::string t; while (t.size() < size) t += unit;
     t.resize(size); t.back() = last;
@@ -254,6 +315,7 @@ int main(int argc, char** argv) {
             damaged("golden bgzf, cut to exactly 8192", blocks.substr(0, 8192), golden, threads, true);
             if (!golden_gz.empty()) { const std::string p = fresh(golden_gz, ".fna.gz"); if (!same(load(p, threads).recs, restate(golden))) fail("the golden multifasta.fna.gz does not give the genomes of multifasta.fna"); }
         }
+        loader_modes(threads);
         g_first = false;
     }
     return hp::finish();

@@ -18,7 +18,8 @@ run is ten times its value):
                                           for the 41-byte named case, this one for 1.1 MB)
     gunzip_corpus --big         7 s      (tsan 13 s)
     text_readers               11 s
-    fasta_ingest               11 s      (tsan, 3 and 16 threads: 13 s)
+    fasta_ingest               11 s      (tsan, 3 and 16 threads: 13 s; measured again with the directory and database + new
+                                          cases in: 10.3 s and 12.3 s, so both values stay)
     writers_and_lists           3 s      (tsan 9 s)
 
 The valid streams that vg_fast_gunzip declines and leaves to zlib are pinned below (FELL_BACK): measured, none -- every class

@@ -168,6 +168,19 @@ struct vg_genomes {
     // L1 order (stable sort by length, descending), computed once: order[rank] = input id, rank[id]
     mutable std::vector<int32_t> len_order, len_rank;
 };
+// The layout rule, stated once (the loaders of vg_genomes.cpp, the device-only sets of vg_subset.hip).  A genome of len bases takes
+// its length rounded up to the set's block with at least one masked base behind it: no k-mer window reaches the next genome.
+inline int64_t vg_padded_len(int64_t len, int align_shift) { const int64_t al = 1LL << align_shift; return (len / al + 1) * al; }
+// genome g->n (the caller counts it) of len bases appended to the layout: its blk2g run and the next base_off; returns its offset
+inline int64_t vg_layout_append(vg_genomes* g, int64_t len) {
+    if (g->base_off.empty()) g->base_off.push_back(0);
+    const int64_t off = g->base_off.back(), padded = vg_padded_len(len, g->align_shift);
+    g->blk2g.insert(g->blk2g.end(), (size_t)(padded >> g->align_shift), (uint32_t)g->n);
+    g->base_off.push_back(off + padded);
+    return off;
+}
+// the layout closed: the entry behind the last block, which a kernel that reads a few words past the last genome looks up
+inline void vg_layout_close(vg_genomes* g) { g->blk2g.push_back(g->n > 0 ? (uint32_t)(g->n - 1) : 0u); }
 void vg_length_order(const vg_genomes* g);        // fills g->len_order / g->len_rank on first use
 int  vg_align_tasks_perm(const vg_genomes* g, const vg_pair_count* pairs, int64_t n_pairs, vg_task** tasks, int64_t* n_tasks, uint32_t* perm /* n_pairs entries, or null */);
 const uint32_t* vg_genome_planes(const vg_genomes* g, hipStream_t s);   // g->d_planes, made from the resident 2-bit codes on first use (queued on s; vg_align.hip)

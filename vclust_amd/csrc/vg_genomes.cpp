@@ -25,10 +25,7 @@ static inline uint8_t code_of(unsigned char ch) {
 }
 
 void vg_genomes_append(vg_genomes* g, const std::string& name, const uint8_t* codes, int64_t len, int n_parts) {
-    if (g->base_off.empty()) g->base_off.push_back(0);
-    int64_t off = g->base_off.back();
-    const int64_t al = 1LL << g->align_shift;
-    const int64_t padded = (len / al + 1) * al;      // at least one masked base behind every genome: no k-mer window reaches the next one
+    const int64_t off = vg_layout_append(g, len), padded = g->base_off.back() - off;
     g->packed.resize((off + padded) / 16, 0u);
     g->nmask.resize((off + padded) / 32, 0u);
     uint32_t* pk = g->packed.data() + off / 16;
@@ -44,8 +41,6 @@ void vg_genomes_append(vg_genomes* g, const std::string& name, const uint8_t* co
     g->len.push_back(len);
     g->n_parts.push_back(n_parts);
     g->has_n.push_back(any_n ? 1 : 0);
-    g->base_off.push_back(off + padded);
-    for (int64_t b = off >> g->align_shift; b < (off + padded) >> g->align_shift; ++b) g->blk2g.push_back((uint32_t)g->n);
     g->n++;
 }
 
@@ -61,7 +56,7 @@ void vg_genomes_finish(vg_genomes* g) {
     // slack so that kernels may read a few words past the last genome
     g->packed.resize(g->padded_total() / 16 + 16, 0u);
     g->nmask.resize(g->padded_total() / 32 + 16, 0xffffffffu);
-    g->blk2g.push_back(g->n > 0 ? (uint32_t)(g->n - 1) : 0u);
+    vg_layout_close(g);
 }
 
 bool vg_fast_gunzip(const unsigned char* in, size_t n, int n_threads, char** out_p, size_t* out_n);      // vg_inflate.cpp
@@ -131,17 +126,25 @@ bool bgzf_blocks(const unsigned char* p, size_t n, std::vector<bgzf_block>& bloc
     return !blocks.empty();
 }
 
+// an open file mapped whole and read-only (no mapping: empty or not mappable), given back on the way out unless handed over
+struct mapped_file {
+    long long size; void* p = MAP_FAILED;
+    explicit mapped_file(FILE* f) { fseek(f, 0, SEEK_END); size = ftell(f); if (size > 0) p = mmap(nullptr, (size_t)size, PROT_READ, MAP_PRIVATE, fileno(f), 0); }
+    mapped_file(const mapped_file&) = delete; mapped_file& operator=(const mapped_file&) = delete;
+    ~mapped_file() { if (p != MAP_FAILED) munmap(p, (size_t)size); }
+    explicit operator bool() const { return p != MAP_FAILED; }
+    void advise(int advice) const { (void)madvise(p, (size_t)size, advice); }
+    void hand_over(filebuf& fb) { fb.map = p; fb.map_len = (size_t)size; fb.ptr = (const char*)p; fb.len = (size_t)size; p = MAP_FAILED; }
+};
+
 bool slurp_bgzf(const std::string& path, FILE* f, filebuf& fb, int n_threads) {
-    fseek(f, 0, SEEK_END); const long long sz = ftell(f);
-    if (sz < 28) return false;
-    void* m = mmap(nullptr, (size_t)sz, PROT_READ, MAP_PRIVATE, fileno(f), 0);
-    if (m == MAP_FAILED) return false;
-    struct unmap { void* m; size_t n; ~unmap() { munmap(m, n); } } um{ m, (size_t)sz };
-    const unsigned char* p = (const unsigned char*)m;
+    const mapped_file m(f);
+    if (m.size < 28 || !m) return false;
+    const unsigned char* p = (const unsigned char*)m.p;
     std::vector<bgzf_block> blocks; size_t total = 0;
-    if (!bgzf_blocks(p, (size_t)sz, blocks, &total)) return false;
+    if (!bgzf_blocks(p, (size_t)m.size, blocks, &total)) return false;
     vg_host_mark("ingest: bgzf members found");
-    (void)madvise(m, (size_t)sz, MADV_WILLNEED);
+    m.advise(MADV_WILLNEED);
     // (not a std::vector: its resize would clear 800 MB on one thread before the workers overwrite them)
     fb.own_raw = (char*)malloc(std::max<size_t>(total, 1));
     if (!fb.own_raw) throw vg_error(VG_ENOMEM, "out of host memory");
@@ -178,18 +181,10 @@ void slurp(const std::string& path, filebuf& fb, int n_threads) {
     size_t got = fread(magic, 1, 2, f);
     const bool gz = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
     if (!gz) {
-        fseek(f, 0, SEEK_END); const long long sz = ftell(f);
-        if (sz > 0) {
-            void* m = mmap(nullptr, (size_t)sz, PROT_READ, MAP_PRIVATE, fileno(f), 0);
-            if (m != MAP_FAILED) {
-                (void)madvise(m, (size_t)sz, MADV_WILLNEED);
-                fb.map = m; fb.map_len = (size_t)sz; fb.ptr = (const char*)m; fb.len = (size_t)sz;
-                fclose(f);
-                return;
-            }
-        }
+        mapped_file m(f);
+        if (m) { m.advise(MADV_WILLNEED); m.hand_over(fb); fclose(f); return; }
         fseek(f, 0, SEEK_SET);                           // not mappable (pipe, special file): read it
-        fb.own.resize((size_t)std::max<long long>(sz, 0));
+        fb.own.resize((size_t)std::max<long long>(m.size, 0));
         size_t off = 0;
         while (off < fb.own.size()) { size_t r = fread(fb.own.data() + off, 1, fb.own.size() - off, f); if (!r) break; off += r; }
         fclose(f);
@@ -204,13 +199,11 @@ void slurp(const std::string& path, filebuf& fb, int n_threads) {
     try { done = slurp_bgzf(path, f, fb, n_threads); } catch (...) { fclose(f); throw; }
     static const bool zlib_only = [] { const char* e = vg_dev_getenv("VG_GZ"); return e && !strcmp(e, "zlib"); }();
     if (!done && !zlib_only) {
-        fseek(f, 0, SEEK_END); const long long sz = ftell(f);
-        void* m = sz > 0 ? mmap(nullptr, (size_t)sz, PROT_READ, MAP_PRIVATE, fileno(f), 0) : MAP_FAILED;
-        if (m != MAP_FAILED) {
-            (void)madvise(m, (size_t)sz, MADV_SEQUENTIAL);
+        const mapped_file m(f);
+        if (m) {
+            m.advise(MADV_SEQUENTIAL);
             char* o = nullptr; size_t on = 0;
-            if (vg_fast_gunzip((const unsigned char*)m, (size_t)sz, n_threads, &o, &on)) { fb.own_raw = o; fb.ptr = o; fb.len = on; done = true; vg_host_mark("ingest: gzip inflated by the own decoder"); }
-            munmap(m, (size_t)sz);
+            if (vg_fast_gunzip((const unsigned char*)m.p, (size_t)m.size, n_threads, &o, &on)) { fb.own_raw = o; fb.ptr = o; fb.len = on; done = true; vg_host_mark("ingest: gzip inflated by the own decoder"); }
         }
     }
     fclose(f);
@@ -231,6 +224,19 @@ void slurp(const std::string& path, filebuf& fb, int n_threads) {
     if (zerr != Z_OK && zerr != Z_STREAM_END) throw vg_error(VG_EIO, "read error in " + path);
     fb.own.resize(off);
     fb.ptr = fb.own.data(); fb.len = off;
+}
+
+// every file whole in memory (gz inflated), files in parallel.  The first failure ends the reading and comes out as VG_EIO
+// with that file's message, whatever its own code was (an allocation that failed in the BGZF path included).
+void read_files(const char* const* paths, int n_paths, int T, std::vector<filebuf>& bufs) {
+    bufs = std::vector<filebuf>((size_t)std::max(n_paths, 0));
+    std::string first_err; std::atomic<bool> failed(false);
+    vg_parallel_for(n_paths, T, [&](int64_t i) {
+        if (failed.load()) return;
+        try { slurp(paths[i], bufs[(size_t)i], std::max(1, T / (int)std::min<int64_t>(n_paths, T))); }
+        catch (const std::exception& e) { if (!failed.exchange(true)) first_err = e.what(); }
+    });
+    if (failed.load()) throw vg_error(VG_EIO, first_err);
 }
 
 // one FASTA record inside a buffer: [hdr, hdr_end) header line without '>', [seq, end) sequence lines
@@ -341,143 +347,148 @@ k_mask_of_lengths(uint32_t* __restrict__ nmask, int64_t n_words, const uint32_t*
     }
 }
 
-// to_device: the packed arrays travel to the HBM of the library's device WHILE the genomes are packed (a helper
-// thread uploads every stretch of genomes as soon as its last genome is done), and the set comes back resident
+// the small arrays of a set on the device (stream s): offsets, lengths, N flags, block -> genome
+static void upload_tables(vg_genomes* g, hipStream_t s) {
+    g->d_base_off.alloc(g->base_off.size()); g->d_base_off.upload(g->base_off.data(), g->base_off.size(), s);
+    g->d_len.alloc(std::max<size_t>(1, g->len.size())); if (g->n) g->d_len.upload(g->len.data(), g->len.size(), s);
+    g->d_has_n.alloc(std::max<size_t>(1, g->has_n.size())); if (g->n) g->d_has_n.upload(g->has_n.data(), g->has_n.size(), s);
+    g->d_blk2g.alloc(g->blk2g.size()); g->d_blk2g.upload(g->blk2g.data(), g->blk2g.size(), s);
+}
+
+namespace {      // ---- the loader: stages over one state (Ingest)
 // n_db_paths >= 0 (vg_genomes_load_db_new): the first n_db_paths files are the database, the others the new genomes; multisample
-// then means one genome per record of BOTH files, *n_db_genomes receives the database's genome count and a name that occurs on
-// both sides is VG_EINVAL, raised from the layout, before anything is packed or any device is asked for
-static void genomes_load_impl(const char* const* paths, int n_paths, int multisample, int n_threads, bool to_device, vg_genomes** out,
-                              int n_db_paths = -1, int* n_db_genomes = nullptr) {
-    if (!paths || n_paths <= 0 || !out) throw vg_error(VG_EINVAL, "vg_genomes_load: bad arguments");
-    const int T = std::max(1, n_threads);
-    const bool multi = multisample && (n_db_paths >= 0 || n_paths == 1);
-    vg_host_mark("ingest: enter");
-    // 1. whole files into memory (gz inflated), files in parallel.  The mappings and the record lists are given to a
-    // helper thread at the end: unmapping 4 GB of FASTA costs ~80 ms the caller need not wait for.
-    struct input_state { std::vector<filebuf> bufs; std::vector<std::vector<record>> recs; };
-    auto* in_state = new input_state();
-    struct in_guard { input_state* p; ~in_guard() { if (p) { input_state* q = p; try { vg_defer([q] { delete q; }); } catch (...) { delete q; } } } } in_g{ in_state };
-    in_state->bufs = std::vector<filebuf>((size_t)n_paths);
-    std::vector<filebuf>& bufs = in_state->bufs;
-    {
-        std::string first_err; std::atomic<bool> failed(false);
-        vg_parallel_for(n_paths, T, [&](int64_t i) {
-            if (failed.load()) return;
-            try { slurp(paths[i], bufs[(size_t)i], std::max(1, T / (int)std::min<int64_t>(n_paths, T))); }
-            catch (const std::exception& e) { if (!failed.exchange(true)) first_err = e.what(); }
-        });
-        if (failed.load()) throw vg_error(VG_EIO, first_err);
-    }
-    vg_host_mark("ingest: files mapped");
-    // 2. records and their lengths
-    in_state->recs = std::vector<std::vector<record>>((size_t)n_paths);
-    std::vector<std::vector<record>>& recs = in_state->recs;
-    for (int i = 0; i < n_paths; ++i) find_records(bufs[(size_t)i], recs[(size_t)i], multi ? T : 1);
-    struct gdesc { int file; size_t r0, r1; int64_t len; };
-    std::vector<gdesc> gd;
-    for (int i = 0; i < n_paths; ++i) {
-        auto& v = recs[(size_t)i];
-        if (multi) for (size_t r = 0; r < v.size(); ++r) gd.push_back({ i, r, r + 1, 0 });
-        else if (!v.empty()) gd.push_back({ i, 0, v.size(), 0 });
+// then means one genome per record of BOTH files.  resident: the set comes back on the library's device (upload_pipe).
+struct load_request { const char* const* paths; int n_paths; int multisample; int n_threads; bool resident; int n_db_paths; };
+// The text and its records.  They go to a helper thread at the end: unmapping 4 GB of FASTA costs ~80 ms the caller need not wait for.
+struct ingest_input { std::vector<filebuf> bufs; std::vector<std::vector<record>> recs; };
+struct deferred_delete { void operator()(ingest_input* p) const { try { vg_defer([p] { delete p; }); } catch (...) { delete p; } } };
+struct gdesc { int file; size_t r0, r1; int64_t len; };      // a genome: records [r0, r1) of a file, its length (an upper bound until packed)
+struct ingest {
+    const load_request& rq; const int T; const bool multi;
+    std::unique_ptr<ingest_input, deferred_delete> in{ new ingest_input() };
+    std::vector<gdesc> gd; int64_t total = 0;
+    std::unique_ptr<vg_genomes> g{ new vg_genomes() };
+    explicit ingest(const load_request& r) : rq(r), T(std::max(1, r.n_threads)), multi(r.multisample && (r.n_db_paths >= 0 || r.n_paths == 1)) {}
+};
+
+// records -> genomes and their lengths
+void plan_genomes(ingest& s) {
+    std::vector<std::vector<record>>& recs = s.in->recs = std::vector<std::vector<record>>((size_t)s.rq.n_paths);
+    for (int i = 0; i < s.rq.n_paths; ++i) {
+        find_records(s.in->bufs[(size_t)i], recs[(size_t)i], s.multi ? s.T : 1);
+        if (s.multi) for (size_t r = 0; r < recs[(size_t)i].size(); ++r) s.gd.push_back({ i, r, r + 1, 0 });
+        else if (!recs[(size_t)i].empty()) s.gd.push_back({ i, 0, recs[(size_t)i].size(), 0 });
     }
     // No counting pass over the text: the layout is made from an UPPER BOUND of every genome's length -- the bytes of its
     // sequence lines, line ends included (1/60 more than the truth for 60-column FASTA) --, the true length is what the
     // packer has written when it reaches the end of the record, and the difference is padding (masked like the padding
     // that aligns the next genome anyway).  One pass over 4 GB of text less per process.
-    int64_t total = 0;
-    for (auto& d : gd) {
+    for (auto& d : s.gd) {
         for (size_t r = d.r0; r < d.r1; ++r) d.len += (int64_t)(recs[(size_t)d.file][r].end - recs[(size_t)d.file][r].seq);
         d.len += (int64_t)(d.r1 - d.r0) - 1;                 // records of one genome are joined by one N
-        total += d.len;
+        s.total += d.len;
     }
-    vg_host_mark("ingest: records found");
-    // 3. layout, then parallel packing straight into the 2-bit arrays
-    vg_genomes* g = new vg_genomes();
-    std::unique_ptr<vg_genomes> guard(g);
-    g->align_shift = vg_choose_align_shift(total, (int64_t)gd.size());
-    const int64_t al = 1LL << g->align_shift;
-    g->base_off.push_back(0);
-    for (auto& d : gd) {
-        const int64_t padded = (d.len / al + 1) * al;          // >= 1 masked base behind the genome (see vg_genomes_append)
-        for (int64_t b = g->base_off.back() >> g->align_shift; b < (g->base_off.back() + padded) >> g->align_shift; ++b) g->blk2g.push_back((uint32_t)g->n);
-        g->base_off.push_back(g->base_off.back() + padded);
+}
+
+// the layout rule over the upper bounds, and the names.  A database/new load is checked here, before anything is packed or any
+// device is asked for: *n_db_genomes receives the database's genome count, a name on both sides is VG_EINVAL
+void lay_out(ingest& s, int* n_db_genomes) {
+    vg_genomes* g = s.g.get();
+    g->align_shift = vg_choose_align_shift(s.total, (int64_t)s.gd.size()); g->base_off.push_back(0);
+    for (auto& d : s.gd) {
+        vg_layout_append(g, d.len);
         g->len.push_back(0); g->n_parts.push_back((int32_t)(d.r1 - d.r0)); g->has_n.push_back(0);      // (the length: set by the packer)
-        const record& r0 = recs[(size_t)d.file][d.r0];
-        if (multi) g->names.push_back(first_token(r0.hdr, r0.hdr_end));
-        else { std::string pth = paths[d.file]; size_t sl = pth.find_last_of('/'); g->names.push_back(sl == std::string::npos ? pth : pth.substr(sl + 1)); }
+        const record& r0 = s.in->recs[(size_t)d.file][d.r0];
+        if (s.multi) g->names.push_back(first_token(r0.hdr, r0.hdr_end));
+        else { std::string pth = s.rq.paths[d.file]; size_t sl = pth.find_last_of('/'); g->names.push_back(sl == std::string::npos ? pth : pth.substr(sl + 1)); }
         g->n++;
     }
-    if (n_db_paths >= 0) {
-        int n_db = 0;
-        while (n_db < g->n && gd[(size_t)n_db].file < n_db_paths) ++n_db;
-        std::unordered_set<std::string> db_names(g->names.begin(), g->names.begin() + n_db);
-        for (int i = n_db; i < g->n; ++i)
-            if (db_names.count(g->names[(size_t)i]))
-                throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: the name " + g->names[(size_t)i] + " occurs in the database and in the new genomes");
-        *n_db_genomes = n_db;
-        if (g->n < 2) throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: the database and the new genomes together are " + std::to_string(g->n) + " genome(s); pairs need at least 2");
-    }
-    vg_host_mark("ingest: layout");
-    // first touch in parallel: the arrays are written by the packing threads right below
+    if (s.rq.n_db_paths < 0) return;
+    int n_db = 0; while (n_db < g->n && s.gd[(size_t)n_db].file < s.rq.n_db_paths) ++n_db;
+    std::unordered_set<std::string> db_names(g->names.begin(), g->names.begin() + n_db);
+    for (int i = n_db; i < g->n; ++i)
+        if (db_names.count(g->names[(size_t)i]))
+            throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: the name " + g->names[(size_t)i] + " occurs in the database and in the new genomes");
+    *n_db_genomes = n_db;
+    if (g->n < 2) throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: the database and the new genomes together are " + std::to_string(g->n) + " genome(s); pairs need at least 2");
+}
+
+// first touch in parallel: the arrays are written by the packing threads right after
+void clear_arrays(ingest& s) {
+    vg_genomes* g = s.g.get();
     g->packed.reserve((size_t)(g->padded_total() / 16) + 16); g->nmask.reserve((size_t)(g->padded_total() / 32) + 16);   // + the slack vg_genomes_finish adds
     g->packed.resize((size_t)(g->padded_total() / 16)); g->nmask.resize((size_t)(g->padded_total() / 32));
-    {
-        const int64_t chunk = 1 << 20, np = ((int64_t)g->packed.size() + chunk - 1) / chunk, nm = ((int64_t)g->nmask.size() + chunk - 1) / chunk;
-        vg_parallel_for(np + nm, T, [&](int64_t c) {
-            std::vector<uint32_t, no_init_alloc<uint32_t>>& v = c < np ? g->packed : g->nmask;
-            const int64_t lo = (c < np ? c : c - np) * chunk, hi = std::min<int64_t>(lo + chunk, (int64_t)v.size());
+    const int64_t chunk = 1 << 20, np = ((int64_t)g->packed.size() + chunk - 1) / chunk, nm = ((int64_t)g->nmask.size() + chunk - 1) / chunk;
+    vg_parallel_for(np + nm, s.T, [&](int64_t c) {
+        std::vector<uint32_t, no_init_alloc<uint32_t>>& v = c < np ? g->packed : g->nmask;
+        const int64_t lo = (c < np ? c : c - np) * chunk, hi = std::min<int64_t>(lo + chunk, (int64_t)v.size());
 #ifdef MADV_POPULATE_WRITE
-            {   // fresh anonymous memory: populate the chunk's whole pages in one call (they come zeroed) instead of faulting page by page
-                const uintptr_t a = ((uintptr_t)(v.data() + lo) + 4095) & ~(uintptr_t)4095, b = (uintptr_t)(v.data() + hi) & ~(uintptr_t)4095;
-                if (b > a) (void)madvise((void*)a, (size_t)(b - a), MADV_POPULATE_WRITE);
-            }
+        {   // fresh anonymous memory: populate the chunk's whole pages in one call (they come zeroed) instead of faulting page by page
+            const uintptr_t a = ((uintptr_t)(v.data() + lo) + 4095) & ~(uintptr_t)4095, b = (uintptr_t)(v.data() + hi) & ~(uintptr_t)4095;
+            if (b > a) (void)madvise((void*)a, (size_t)(b - a), MADV_POPULATE_WRITE);
+        }
 #endif
-            memset(v.data() + lo, 0, (size_t)(hi - lo) * sizeof(uint32_t));
-        });
+        memset(v.data() + lo, 0, (size_t)(hi - lo) * sizeof(uint32_t));
+    });
+}
+
+// Stretches of genomes, the unit of the overlapped upload: the first genome of every stretch, then the genome count.  A stretch is
+// closed by the genome that fills it, and never starts behind the last genome.
+int64_t stretch_bases() {      // 128 M bases (= 32 MB packed + 16 MB mask); developer switch VG_INGEST_STRETCH_BASES, at least 64
+    static const int64_t bases = [] { const char* e = vg_dev_getenv("VG_INGEST_STRETCH_BASES"); const long long v = e ? atoll(e) : 0; return v >= 64 ? (int64_t)v : (int64_t)(128LL << 20); }();
+    return bases;
+}
+std::vector<int64_t> cut_stretches(const std::vector<int64_t>& base_off, int64_t want) {
+    const int64_t n_g = (int64_t)base_off.size() - 1;
+    std::vector<int64_t> first{ 0 };
+    for (int64_t gi = 0; gi + 1 < n_g; ++gi) if (base_off[(size_t)gi + 1] - base_off[(size_t)first.back()] >= want) first.push_back(gi + 1);
+    first.push_back(n_g); return first;
+}
+// The upload pipe: the packed arrays travel to the HBM of the library's device WHILE the genomes are packed.  A helper thread with a
+// stream of its own uploads every stretch of genomes as soon as its last genome is done.  The pipe owns that thread and everything
+// it shares with the packing threads, which only push; the thread reads the set's host arrays and layout and writes d_packed / d_nmask.
+class upload_pipe {
+    struct item { int64_t stretch; bool with_mask; };
+    std::thread th; std::mutex mu; std::condition_variable cv; std::vector<item> queue; bool closed = false; std::string err;
+    void run(vg_genomes* g, const std::vector<int64_t>& first) {
+        try {
+            vg_require_device();
+            hipStream_t st; VG_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+            for (;;) {
+                item it;
+                { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !queue.empty() || closed; }); if (queue.empty()) break; it = queue.back(); queue.pop_back(); }      // (the newest first)
+                const int64_t b0 = g->base_off[(size_t)first[(size_t)it.stretch]], b1 = g->base_off[(size_t)first[(size_t)it.stretch + 1]];      // multiples of 64 bases
+                VG_HIP(hipMemcpyAsync(g->d_packed.p + b0 / 16, g->packed.data() + b0 / 16, (size_t)(b1 - b0) / 16 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                if (it.with_mask) VG_HIP(hipMemcpyAsync(g->d_nmask.p + b0 / 32, g->nmask.data() + b0 / 32, (size_t)(b1 - b0) / 32 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                VG_HIP(hipStreamSynchronize(st));
+            }
+            (void)hipStreamDestroy(st);
+        } catch (const std::exception& e) { std::lock_guard<std::mutex> lk(mu); err = e.what(); }
     }
-    vg_host_mark("ingest: arrays cleared");
-    // stretches of genomes of ~32 MB of packed bases: the unit of the overlapped upload
-    const int64_t n_g = (int64_t)gd.size();
-    std::vector<int64_t> st_first;                          // first genome of every stretch (+ n_g)
-    {
-        const int64_t want = 128LL << 20;                   // bases per stretch (= 32 MB packed + 16 MB mask)
-        int64_t last = 0; st_first.push_back(0);
-        for (int64_t gi = 0; gi < n_g; ++gi) if (g->base_off[(size_t)gi + 1] - g->base_off[(size_t)last] >= want && gi + 1 < n_g) { st_first.push_back(gi + 1); last = gi + 1; }
-        st_first.push_back(n_g);
-    }
-    const int64_t n_st = (int64_t)st_first.size() - 1;
-    std::vector<int> st_of((size_t)n_g);
-    for (int64_t c = 0; c < n_st; ++c) for (int64_t gi = st_first[(size_t)c]; gi < st_first[(size_t)c + 1]; ++gi) st_of[(size_t)gi] = (int)c;
-    std::unique_ptr<std::atomic<int64_t>[]> st_left(new std::atomic<int64_t>[(size_t)std::max<int64_t>(n_st, 1)]);
-    for (int64_t c = 0; c < n_st; ++c) st_left[(size_t)c].store(st_first[(size_t)c + 1] - st_first[(size_t)c]);
-    std::unique_ptr<std::atomic<int>[]> st_has_n(new std::atomic<int>[(size_t)std::max<int64_t>(n_st, 1)]);      // a genome of the stretch holds an N: its mask travels
-    for (int64_t c = 0; c < n_st; ++c) st_has_n[(size_t)c].store(0);
-    std::mutex up_mu; std::condition_variable up_cv; std::vector<int64_t> up_queue; bool up_done = false; std::string up_err;
-    std::thread uploader; int dev = 0;
-    const size_t pk_words = (size_t)(g->padded_total() / 16) + 16, mk_words = (size_t)(g->padded_total() / 32) + 16;   // with the slack vg_genomes_finish adds
-    if (to_device && n_g > 0) {
+    void shut() { if (!th.joinable()) return; { std::lock_guard<std::mutex> lk(mu); closed = true; } cv.notify_all(); th.join(); }
+public:
+    // the device arrays of g (with the slack vg_genomes_finish adds) and the thread; `stretches` (cut_stretches) outlives the pipe
+    void open(vg_genomes* g, const std::vector<int64_t>& stretches) {
         vg_require_device();
-        VG_HIP(hipGetDevice(&dev));
-        g->d_packed.alloc(pk_words); g->d_nmask.alloc(mk_words);
-        uploader = std::thread([&]() {
-            try {
-                vg_require_device();
-                hipStream_t st; VG_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-                for (;;) {
-                    int64_t c;
-                    { std::unique_lock<std::mutex> lk(up_mu); up_cv.wait(lk, [&] { return !up_queue.empty() || up_done; }); if (up_queue.empty()) break; c = up_queue.back(); up_queue.pop_back(); }
-                    const int64_t b0 = g->base_off[(size_t)st_first[(size_t)c]], b1 = g->base_off[(size_t)st_first[(size_t)c + 1]];      // multiples of 64 bases
-                    VG_HIP(hipMemcpyAsync(g->d_packed.p + b0 / 16, g->packed.data() + b0 / 16, (size_t)(b1 - b0) / 16 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    if (st_has_n[(size_t)c].load()) VG_HIP(hipMemcpyAsync(g->d_nmask.p + b0 / 32, g->nmask.data() + b0 / 32, (size_t)(b1 - b0) / 32 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    VG_HIP(hipStreamSynchronize(st));
-                }
-                (void)hipStreamDestroy(st);
-            } catch (const std::exception& e) { std::lock_guard<std::mutex> lk(up_mu); up_err = e.what(); }
-        });
+        g->d_packed.alloc((size_t)(g->padded_total() / 16) + 16); g->d_nmask.alloc((size_t)(g->padded_total() / 32) + 16);
+        th = std::thread([this, g, &stretches] { run(g, stretches); });
     }
-    struct join_guard { std::thread& t; std::mutex& m; std::condition_variable& cv; bool& done;
-                        ~join_guard() { { std::lock_guard<std::mutex> lk(m); done = true; } cv.notify_all(); if (t.joinable()) t.join(); } } jg{ uploader, up_mu, up_cv, up_done };
-    vg_parallel_for(n_g, T, [&](int64_t gi) {
+    // a stretch whose genomes are all packed; with_mask: one of them holds an N, so its mask travels too
+    void push(int64_t stretch, bool with_mask) { { std::lock_guard<std::mutex> lk(mu); queue.push_back({ stretch, with_mask }); } cv.notify_one(); }
+    // every pushed stretch is on the device (the thread's stream has been drained), or the thread's error is thrown
+    void close() { shut(); if (!err.empty()) throw vg_error(VG_EHIP, "upload of the genome arrays failed: " + err); }
+    ~upload_pipe() { shut(); }
+};
+
+// parallel packing straight into the 2-bit arrays; the thread that completes a stretch hands it to the pipe (if any) and drops its text
+void pack_genomes(ingest& s, const std::vector<int64_t>& st_first, upload_pipe* pipe) {
+    vg_genomes* g = s.g.get(); const std::vector<gdesc>& gd = s.gd; std::vector<filebuf>& bufs = s.in->bufs; const std::vector<std::vector<record>>& recs = s.in->recs;
+    // per stretch: the genomes still to pack, and whether one of them holds an N (its mask travels)
+    struct stretch_state { std::atomic<int64_t> left; std::atomic<int> has_n; };
+    const int64_t n_st = (int64_t)st_first.size() - 1;
+    std::unique_ptr<stretch_state[]> st(new stretch_state[(size_t)n_st]);
+    for (int64_t c = 0; c < n_st; ++c) { st[(size_t)c].left.store(st_first[(size_t)c + 1] - st_first[(size_t)c]); st[(size_t)c].has_n.store(0); }
+    vg_parallel_for((int64_t)gd.size(), s.T, [&](int64_t gi) {
         const gdesc& d = gd[(size_t)gi];
         int64_t at = g->base_off[(size_t)gi]; bool any_n = false;
         for (size_t r = d.r0; r < d.r1; ++r) {
@@ -494,81 +505,79 @@ static void genomes_load_impl(const char* const* paths, int n_paths, int multisa
             for (; i < e; ++i) g->nmask[(size_t)(i >> 5)] |= 1u << (i & 31);
         }
         g->has_n[(size_t)gi] = any_n ? 1 : 0;
-        if (any_n) st_has_n[(size_t)st_of[(size_t)gi]].store(1);
-        if (st_left[(size_t)st_of[(size_t)gi]].fetch_sub(1) == 1) {
-            // the last genome of its stretch: the stretch can travel, and nobody reads its text again
-            const int64_t c = st_of[(size_t)gi];
-            if (uploader.joinable()) {
-                { std::lock_guard<std::mutex> lk(up_mu); up_queue.push_back(c); }
-                up_cv.notify_one();
-            }
-            if (multi) {
-                const gdesc& d0 = gd[(size_t)st_first[(size_t)c]]; const gdesc& d1 = gd[(size_t)st_first[(size_t)c + 1] - 1];
-                if (d0.file == d1.file) bufs[(size_t)d0.file].drop(recs[(size_t)d0.file][d0.r0].hdr - 1, recs[(size_t)d1.file][d1.r1 - 1].end);
-            }
+        const int64_t c = std::upper_bound(st_first.begin(), st_first.end(), gi) - st_first.begin() - 1;      // the genome's stretch
+        if (any_n) st[(size_t)c].has_n.store(1);
+        if (st[(size_t)c].left.fetch_sub(1) != 1) return;
+        // the last genome of its stretch: the stretch can travel, and nobody reads its text again
+        if (pipe) pipe->push(c, st[(size_t)c].has_n.load() != 0);
+        if (s.multi) {
+            const gdesc& d0 = gd[(size_t)st_first[(size_t)c]]; const gdesc& d1 = gd[(size_t)st_first[(size_t)c + 1] - 1];
+            if (d0.file == d1.file) bufs[(size_t)d0.file].drop(recs[(size_t)d0.file][d0.r0].hdr - 1, recs[(size_t)d1.file][d1.r1 - 1].end);
         }
     });
-    vg_genomes_finish(g);
-    vg_host_mark("ingest: packed");
-    if (uploader.joinable()) {
-        { std::lock_guard<std::mutex> lk(up_mu); up_done = true; }
-        up_cv.notify_all(); uploader.join();
-        if (!up_err.empty()) throw vg_error(VG_EHIP, "upload of the genome arrays failed: " + up_err);
-        // the slack words behind the last genome and the small arrays
-        hipStream_t s = vg_stream();
-        const size_t pk_tail = (size_t)(g->padded_total() / 16), mk_tail = (size_t)(g->padded_total() / 32);
-        VG_HIP(hipMemcpyAsync(g->d_packed.p + pk_tail, g->packed.data() + pk_tail, (g->packed.size() - pk_tail) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        VG_HIP(hipMemcpyAsync(g->d_nmask.p + mk_tail, g->nmask.data() + mk_tail, (g->nmask.size() - mk_tail) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        g->d_base_off.alloc(g->base_off.size()); g->d_base_off.upload(g->base_off.data(), g->base_off.size(), s);
-        g->d_len.alloc(std::max<size_t>(1, g->len.size())); g->d_len.upload(g->len.data(), g->len.size(), s);
-        g->d_has_n.alloc(std::max<size_t>(1, g->has_n.size())); g->d_has_n.upload(g->has_n.data(), g->has_n.size(), s);
-        g->d_blk2g.alloc(g->blk2g.size()); g->d_blk2g.upload(g->blk2g.data(), g->blk2g.size(), s);
-        // the masks that did not travel (the uploader's stream has been drained: its copies are in place)
-        hipLaunchKernelGGL(k_mask_of_lengths, dim3(4096), dim3(256), 0, s, g->d_nmask.p, (int64_t)mk_tail, (const uint32_t*)g->d_blk2g.p, g->align_shift,
-                           (const int64_t*)g->d_base_off.p, (const int64_t*)g->d_len.p, (const uint8_t*)g->d_has_n.p);
-        VG_HIP(hipStreamSynchronize(s));
-        g->device = dev;
-        vg_host_mark("ingest: resident");
-    }
-    *out = guard.release();
 }
 
-extern "C" int vg_genomes_load(const char* const* paths, int n_paths, int multisample, int n_threads,
-                               vg_genomes** out) {
-    VG_API_BEGIN
-    genomes_load_impl(paths, n_paths, multisample, n_threads, false, out);
-    VG_API_END
+// what the pipe did not carry: the slack words behind the last genome, the small arrays, the masks of the genomes without N
+void finish_resident(vg_genomes* g) {
+    int dev = 0; VG_HIP(hipGetDevice(&dev)); hipStream_t s = vg_stream();
+    const size_t pk_tail = (size_t)(g->padded_total() / 16), mk_tail = (size_t)(g->padded_total() / 32);
+    VG_HIP(hipMemcpyAsync(g->d_packed.p + pk_tail, g->packed.data() + pk_tail, (g->packed.size() - pk_tail) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    VG_HIP(hipMemcpyAsync(g->d_nmask.p + mk_tail, g->nmask.data() + mk_tail, (g->nmask.size() - mk_tail) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    upload_tables(g, s);
+    // the masks that did not travel (the pipe's stream has been drained: its copies are in place)
+    hipLaunchKernelGGL(k_mask_of_lengths, dim3(4096), dim3(256), 0, s, g->d_nmask.p, (int64_t)mk_tail, (const uint32_t*)g->d_blk2g.p, g->align_shift,
+                       (const int64_t*)g->d_base_off.p, (const int64_t*)g->d_len.p, (const uint8_t*)g->d_has_n.p);
+    VG_HIP(hipStreamSynchronize(s));
+    g->device = dev;
 }
-// internal (vg_api.cpp): ingest with the upload overlapped
-int vg_genomes_load_resident(const char* const* paths, int n_paths, int multisample, int n_threads, vg_genomes** out) {
-    VG_API_BEGIN
-    genomes_load_impl(paths, n_paths, multisample, n_threads, true, out);
-    VG_API_END
+
+void load_genomes(const load_request& rq, vg_genomes** out, int* n_db_genomes = nullptr) {
+    if (!rq.paths || rq.n_paths <= 0 || !out) throw vg_error(VG_EINVAL, "vg_genomes_load: bad arguments");
+    ingest s(rq);
+    vg_host_mark("ingest: enter");
+    read_files(rq.paths, rq.n_paths, s.T, s.in->bufs);
+    vg_host_mark("ingest: files mapped");
+    plan_genomes(s);
+    vg_host_mark("ingest: records found");
+    lay_out(s, n_db_genomes);
+    vg_host_mark("ingest: layout");
+    clear_arrays(s);
+    vg_host_mark("ingest: arrays cleared");
+    const std::vector<int64_t> stretches = cut_stretches(s.g->base_off, stretch_bases());
+    const bool resident = rq.resident && s.g->n > 0;
+    upload_pipe pipe;                                       // (behind s: the thread is joined before the set and the text can go)
+    if (resident) pipe.open(s.g.get(), stretches);
+    pack_genomes(s, stretches, resident ? &pipe : nullptr);
+    vg_genomes_finish(s.g.get());
+    vg_host_mark("ingest: packed");
+    if (resident) { pipe.close(); finish_resident(s.g.get()); vg_host_mark("ingest: resident"); }
+    *out = s.g.release();
 }
 
 // database files then new files as one path list for the loader; multi-FASTA mode wants exactly one file on each side
-static std::vector<const char*> db_new_paths(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
-                                             vg_genomes** out, int* n_db_genomes) {
+void load_db_new(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample, int n_threads, bool resident,
+                 vg_genomes** out, int* n_db_genomes) {
     if (!db_paths || !new_paths || n_db <= 0 || n_new <= 0 || !out || !n_db_genomes) throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: bad arguments");
-    if (multisample && (n_db != 1 || n_new != 1))
-        throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: multi-FASTA mode takes one database file and one file of new genomes");
-    std::vector<const char*> all(db_paths, db_paths + n_db);
-    all.insert(all.end(), new_paths, new_paths + n_new);
-    return all;
+    if (multisample && (n_db != 1 || n_new != 1)) throw vg_error(VG_EINVAL, "vg_genomes_load_db_new: multi-FASTA mode takes one database file and one file of new genomes");
+    std::vector<const char*> all(db_paths, db_paths + n_db); all.insert(all.end(), new_paths, new_paths + n_new);
+    load_genomes({ all.data(), (int)all.size(), multisample, n_threads, resident, n_db }, out, n_db_genomes);
+}
+}  // namespace
+
+// the four entries: host set or resident set (internal, vg_api.cpp: the upload overlapped), one list of files or database + new
+extern "C" int vg_genomes_load(const char* const* paths, int n_paths, int multisample, int n_threads, vg_genomes** out) {
+    VG_API_BEGIN load_genomes({ paths, n_paths, multisample, n_threads, false, -1 }, out); VG_API_END
+}
+int vg_genomes_load_resident(const char* const* paths, int n_paths, int multisample, int n_threads, vg_genomes** out) {
+    VG_API_BEGIN load_genomes({ paths, n_paths, multisample, n_threads, true, -1 }, out); VG_API_END
 }
 extern "C" int vg_genomes_load_db_new(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
                                       int n_threads, vg_genomes** out, int* n_db_genomes) {
-    VG_API_BEGIN
-    const std::vector<const char*> all = db_new_paths(db_paths, n_db, new_paths, n_new, multisample, out, n_db_genomes);
-    genomes_load_impl(all.data(), (int)all.size(), multisample, n_threads, false, out, n_db, n_db_genomes);
-    VG_API_END
+    VG_API_BEGIN load_db_new(db_paths, n_db, new_paths, n_new, multisample, n_threads, false, out, n_db_genomes); VG_API_END
 }
 int vg_genomes_load_db_new_resident(const char* const* db_paths, int n_db, const char* const* new_paths, int n_new, int multisample,
                                     int n_threads, vg_genomes** out, int* n_db_genomes) {
-    VG_API_BEGIN
-    const std::vector<const char*> all = db_new_paths(db_paths, n_db, new_paths, n_new, multisample, out, n_db_genomes);
-    genomes_load_impl(all.data(), (int)all.size(), multisample, n_threads, true, out, n_db, n_db_genomes);
-    VG_API_END
+    VG_API_BEGIN load_db_new(db_paths, n_db, new_paths, n_new, multisample, n_threads, true, out, n_db_genomes); VG_API_END
 }
 
 extern "C" int vg_genomes_from_codes(const uint8_t* codes, const int64_t* offsets, int n_genomes,
@@ -639,10 +648,7 @@ extern "C" int vg_genomes_to_device(vg_genomes* g) {
     hipStream_t s = vg_stream();
     g->d_packed.alloc(g->packed.size()); g->d_packed.upload(g->packed.data(), g->packed.size(), s);
     g->d_nmask.alloc(g->nmask.size());   g->d_nmask.upload(g->nmask.data(), g->nmask.size(), s);
-    g->d_base_off.alloc(g->base_off.size()); g->d_base_off.upload(g->base_off.data(), g->base_off.size(), s);
-    g->d_len.alloc(std::max<size_t>(1, g->len.size())); if (g->n) g->d_len.upload(g->len.data(), g->len.size(), s);
-    g->d_has_n.alloc(std::max<size_t>(1, g->has_n.size())); if (g->n) g->d_has_n.upload(g->has_n.data(), g->has_n.size(), s);
-    g->d_blk2g.alloc(g->blk2g.size()); g->d_blk2g.upload(g->blk2g.data(), g->blk2g.size(), s);
+    upload_tables(g, s);
     VG_HIP(hipStreamSynchronize(s));
     g->device = dev;
     vg_host_mark("genomes uploaded");
@@ -652,17 +658,8 @@ extern "C" int vg_genomes_to_device(vg_genomes* g) {
 // the deduplicate stage's input (vg_dedup.hip): every file whole in memory, every record in file order
 void vg_fasta_read(const char* const* paths, int n_paths, int n_threads, vg_fasta_text& out) {
     const int T = std::max(1, n_threads);
-    auto* bufs = new std::vector<filebuf>((size_t)std::max(n_paths, 0));
-    out.bufs = std::shared_ptr<void>(bufs, [](void* p) { delete (std::vector<filebuf>*)p; });
-    {
-        std::string first_err; std::atomic<bool> failed(false);
-        vg_parallel_for(n_paths, T, [&](int64_t i) {
-            if (failed.load()) return;
-            try { slurp(paths[i], (*bufs)[(size_t)i], std::max(1, T / (int)std::min<int64_t>(n_paths, T))); }
-            catch (const std::exception& e) { if (!failed.exchange(true)) first_err = e.what(); }
-        });
-        if (failed.load()) throw vg_error(VG_EIO, first_err);
-    }
+    auto bufs = std::make_shared<std::vector<filebuf>>();
+    out.bufs = bufs; read_files(paths, n_paths, T, *bufs);
     out.file_data.clear(); out.file_len.clear(); out.recs.clear();
     std::vector<record> rv;
     for (int i = 0; i < n_paths; ++i) {

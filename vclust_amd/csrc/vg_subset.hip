@@ -91,9 +91,9 @@ void check_ids(const char* fn, const vg_genomes* g, const int32_t* ids, int n_id
 void check_extendable(const char* fn, const vg_genomes* sub) {
     if (!sub->device_only) throw vg_error(VG_EINVAL, std::string(fn) + ": the set was not made by vg_genomes_subset (a loaded set has a host copy, which would not follow)");
 }
-// the padded bases of genome id of g by the loader's rule (vg_genomes_append), which g's own layout must cover
+// the padded bases of genome id of g by the layout rule (vg_padded_len), which g's own layout must cover
 int64_t padded_len(const char* fn, const vg_genomes* g, int32_t id) {
-    const int64_t al = 1LL << g->align_shift, padded = (g->len[(size_t)id] / al + 1) * al;
+    const int64_t padded = vg_padded_len(g->len[(size_t)id], g->align_shift);
     if (padded > g->base_off[(size_t)id + 1] - g->base_off[(size_t)id])
         throw vg_error(VG_EHIP, std::string(fn) + ": genome " + std::to_string(id) + " has less padding than the loader's rule gives it");
     return padded;
@@ -111,18 +111,16 @@ void append(const char* fn, const char* scope, const char* parent_is, vg_genomes
     hipStream_t s = vg_stream();
     grow_all(sub, set_sizes(total, (int64_t)n0 + n_ids, shift), s);
     drop_caches(sub);
-    // layout: the parent's block size, the loader's padding rule
+    // layout: the parent's block size, the layout rule
     sub->blk2g.pop_back();                                   // (the entry behind the last block)
     for (int i = 0; i < n_ids; ++i) {
         const size_t id = (size_t)ids[i];
-        const int64_t off = sub->base_off.back(), padded = (g->len[id] / (1LL << shift) + 1) << shift;
         sub->names.push_back(g->names[id]); sub->len.push_back(g->len[id]); sub->n_parts.push_back(g->n_parts[id]); sub->has_n.push_back(g->has_n[id]);
         sub->parent_id.push_back(ids[i]);
-        sub->base_off.push_back(off + padded);
-        sub->blk2g.insert(sub->blk2g.end(), (size_t)(padded >> shift), (uint32_t)(n0 + i));
+        vg_layout_append(sub, g->len[id]);
         sub->n++;
     }
-    sub->blk2g.push_back(sub->n > 0 ? (uint32_t)(sub->n - 1) : 0u);       // (as vg_genomes_finish leaves it)
+    vg_layout_close(sub);                                    // (as vg_genomes_finish leaves it)
     window(sub);
     // the device: the new tails of the small arrays, then the bases
     const size_t b0 = (size_t)(total0 >> shift);
@@ -160,7 +158,7 @@ extern "C" int vg_genomes_subset(const vg_genomes* g, const int32_t* ids, int n_
     // an empty set of g's layout on g's device, then its genomes
     std::unique_ptr<vg_genomes> sub(new vg_genomes());
     sub->align_shift = g->align_shift; sub->device_only = true; sub->parent_uid = g->uid; sub->device = g->device;
-    sub->base_off.push_back(0); sub->blk2g.push_back(0u);
+    sub->base_off.push_back(0); vg_layout_close(sub.get());
     append(fn, "derep_subset", "the set", sub.get(), g, ids, n_ids);
     *out = sub.release();
     VG_API_END
@@ -200,7 +198,7 @@ extern "C" int vg_genomes_truncate(vg_genomes* sub, int n_keep) {
     sub->names.resize(k); sub->len.resize(k); sub->n_parts.resize(k); sub->has_n.resize(k); sub->parent_id.resize(k); sub->base_off.resize(k + 1);
     const int64_t total = sub->padded_total();
     sub->blk2g.resize((size_t)(total >> sub->align_shift));
-    sub->blk2g.push_back(n_keep > 0 ? (uint32_t)(n_keep - 1) : 0u);
+    vg_layout_close(sub);
     window(sub);                                             // (the capacity stays)
     // what a kernel that reads past the end sees: the entry behind the last block, and the slack behind the last genome written afresh
     vg_upload_bytes(sub->d_blk2g.p + (sub->blk2g.size() - 1), &sub->blk2g.back(), sizeof(uint32_t), s);
