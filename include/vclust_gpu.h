@@ -641,6 +641,53 @@ int vg_cover_rows(int64_t n_objects, const int64_t* len, const int32_t* label, i
 int vg_cover_file(const char* aln_path, const char* ids_path, const char* clusters_path, int clusters_is_repr,
                   const char* column, const char* out_path, const char* segments_path, int num_threads, int verbosity);
 
+/* ------------------------------------------------------------------ painting ---------- */
+/* Mosaic painting (this repository's definition; DESIGN.md section 15 is the contract, tests/paint_restatement.py its sequential
+ * statement).  Objects, lengths and groups as in the coverage map.  A row (q, r, qstart, qend, n_match) says that the positions
+ * qstart..qend (0-based, inclusive) of object q are aligned to partner r with n_match matching positions, 0 <= n_match <= span =
+ * qend - qstart + 1; only the query side counts and a row with q == r is ignored.  A row outranks another row of the same object by
+ * larger I = floor(n_match * 2^32 / span), then larger span, then smaller r, then smaller qstart (rows equal on all four are the same
+ * row).  The winner at a position is the best-ranked row that covers it; a position no row covers is unpainted.  The segments of an
+ * object with len > 0 are the maximal runs of one winning row, or of no winner: disjoint, covering 0..len-1, ordered by (object,
+ * start).  The result depends on the set of rows only. */
+typedef struct {
+    int64_t len;
+    int64_t painted;                    /* positions with a winner */
+    int64_t painted_in, painted_out;    /* ... whose partner is of the object's group / of another group */
+    int64_t donors;                     /* distinct winning partners */
+    int64_t top_partner, top_painted;   /* the donor with the most positions (ties: the smallest index; -1 without one), and how many */
+    int64_t switches;                   /* pairs of neighbouring segments, both painted, with different partners */
+    int64_t segments;
+} vg_paint_stat;
+/* 0-based inclusive; an unpainted segment has partner = row_qstart = row_qend = -1 and n_match = 0 */
+typedef struct { int32_t object, start, end, partner, row_qstart, row_qend, n_match; } vg_paint_segment;
+typedef struct { int32_t object, partner; int64_t painted, segments; } vg_paint_donor;   /* by (object, partner) */
+typedef struct {
+    int64_t rows_kept;          /* rows with q != r */
+    int64_t breakpoints;        /* distinct (object, position) over qstart and qend + 1 of the kept rows, and 0 and len of every object with len > 0 */
+    int64_t segments;
+    int64_t donor_records;
+    int64_t levels;             /* levels of the maximum structure: floor(log2(the longest row in elementary segments)) + 1; 0 without rows */
+} vg_paint_run_stats;
+/* out[n_objects].  segments / n_segments and donors / n_donors: each pair both NULL or both given; *segments and *donors are
+ * released with vg_free.  Checks, limits and codes are those of vg_cover_rows, on the host before any device use, and also
+ * VG_EINVAL for n_match < 0 or n_match > span.  n_objects == 0 is VG_OK without a device; no device VG_ENODEV (no host fallback).
+ * st may be NULL. */
+int vg_paint_rows(int64_t n_objects, const int64_t* len, const int32_t* label, int64_t n_groups,
+                  const uint32_t* q, const uint32_t* r, const int32_t* qstart, const int32_t* qend, const int32_t* n_match, int64_t n_rows,
+                  vg_paint_stat* out, vg_paint_segment** segments, int64_t* n_segments, vg_paint_donor** donors, int64_t* n_donors,
+                  vg_paint_run_stats* st);
+/* File to file.  The files are read as by vg_cover_file; the table's columns alnlen and nt_match are taken as well, by header name,
+ * and `<file>:<line>: ...` VG_EINVAL also when alnlen != qend - qstart + 1, nt_match > alnlen, or (with a column nt_mismatch)
+ * nt_match + nt_mismatch != alnlen.  out_path: one line per object in ids-file order, header `id len group painted painted_in
+ * painted_out donors top_partner top_painted switches segments painted_frac top_frac`; top_partner is the partner's id (`-` without
+ * one); painted / len and top_painted / len are printed %.6g, `-` when len == 0.  segments_path (may be NULL): header `id start end
+ * partner pident row_qstart row_qend`, positions 1-based inclusive, pident = 100 * n_match / span of the winning row in the digits
+ * of vg_align's alignment table; the last four are `-` on an unpainted segment.  donors_path (may be NULL): header `id partner
+ * painted segments painted_frac`.  The bytes do not depend on num_threads.  verbosity >= 1: one summary line on stderr. */
+int vg_paint_file(const char* aln_path, const char* ids_path, const char* clusters_path, int clusters_is_repr, const char* column,
+                  const char* out_path, const char* segments_path, const char* donors_path, int num_threads, int verbosity);
+
 /* ------------------------------------------------------------------ dereplicate ------- */
 /* Greedy incremental clustering against representatives only (this repository's command; no reference call site; DESIGN.md
  * section 13 is the contract).  Objects are the genomes in align order (vg_align_order; rank = object index, as in ani.ids.tsv).

@@ -137,6 +137,26 @@ class CoverRunStats(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ('rows_kept', 'intervals', 'breakpoints', 'segments')]
 
 
+class PaintStat(C.Structure):
+    """vg_paint_stat: the record of one object in the mosaic painting"""
+    _fields_ = [(name, C.c_int64) for name in ('len', 'painted', 'painted_in', 'painted_out', 'donors', 'top_partner', 'top_painted', 'switches',
+                                                'segments')]
+
+
+class PaintSegment(C.Structure):
+    """vg_paint_segment: a maximal run of one winning row (partner -1: of no winner), positions 0-based inclusive"""
+    _fields_ = [(name, C.c_int32) for name in ('object', 'start', 'end', 'partner', 'row_qstart', 'row_qend', 'n_match')]
+
+
+class PaintDonor(C.Structure):
+    """vg_paint_donor: what one winning partner paints of one object"""
+    _fields_ = [('object', C.c_int32), ('partner', C.c_int32), ('painted', C.c_int64), ('segments', C.c_int64)]
+
+
+class PaintRunStats(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in ('rows_kept', 'breakpoints', 'segments', 'donor_records', 'levels')]
+
+
 class LinkageStats(C.Structure):
     _fields_ = [('rounds', C.c_int64), ('n_edges', C.c_int64), ('n_merges', C.c_int64)]
 
@@ -333,6 +353,9 @@ SYMBOLS = {
     'vg_cover_rows': (C.c_int, [C.c_int64, P(C.c_int64), P(C.c_int32), C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_int32), P(C.c_int32), C.c_int64,
                                 P(CoverStat), P(P(CoverSegment)), P(C.c_int64), P(CoverRunStats)]),
     'vg_cover_file': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
+    'vg_paint_rows': (C.c_int, [C.c_int64, P(C.c_int64), P(C.c_int32), C.c_int64, P(C.c_uint32), P(C.c_uint32), P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                C.c_int64, P(PaintStat), P(P(PaintSegment)), P(C.c_int64), P(P(PaintDonor)), P(C.c_int64), P(PaintRunStats)]),
+    'vg_paint_file': (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     'vg_dereplicate_set': (C.c_int, [C.c_void_p, P(DerepParams), P(C.c_int32), P(C.c_int32), P(P(Task)), P(P(PairStat)), P(C.c_int64),
                                      P(DerepStats)]),
     'vg_dereplicate': (C.c_int, [P(C.c_char_p), C.c_int, C.c_char_p, P(DerepFileParams)]),

@@ -11,10 +11,10 @@ import numpy as np
 from . import _lib
 from ._lib import (ALIGN_FIELDS, ALIGN_OUTFMT, CLUSTER_ALGORITHMS, LINKAGE_ALGORITHMS, UPDATE_ALGORITHMS, ClusterStat, ClusterStats,  # noqa: F401
                    ClusterUpdateStats, CoverRunStats, CoverSegment, CoverStat, DedupStats, DerepStats, DerepUpdateStats, KernelTime, LinkageStats, MclParams, MclStats, PairCount,
-                   PairStat, Region, Task, as_dict, check, lz_params, path, path_array, ptr)
+                   PaintDonor, PaintRunStats, PaintSegment, PaintStat, PairStat, Region, Task, as_dict, check, lz_params, path, path_array, ptr)
 # the whole-stage calls (vclust_amd/stages.py: no numpy)
 from .stages import (DEFAULT_LZ, align, align_params, cluster, cluster_stats, cover, deduplicate as deduplicate_files, derep_params, dereplicate,  # noqa: F401
-                     prefilter)
+                     paint, prefilter)
 
 
 def _dtype(ctype):
@@ -25,6 +25,7 @@ def _dtype(ctype):
 
 PAIR_DTYPE, TASK_DTYPE, STAT_DTYPE, REGION_DTYPE, CLUSTER_STAT_DTYPE = (_dtype(t) for t in (PairCount, Task, PairStat, Region, ClusterStat))
 COVER_STAT_DTYPE, COVER_SEGMENT_DTYPE = _dtype(CoverStat), _dtype(CoverSegment)
+PAINT_STAT_DTYPE, PAINT_SEGMENT_DTYPE, PAINT_DONOR_DTYPE = _dtype(PaintStat), _dtype(PaintSegment), _dtype(PaintDonor)
 LINKAGE_DTYPE = np.dtype([('node_a', '<i8'), ('node_b', '<i8'), ('similarity', '<f8'), ('size', '<i8'), ('object_a', '<i4'),
                           ('object_b', '<i4')])
 AVERAGE_LINKAGE_DTYPE = np.dtype(LINKAGE_DTYPE.descr + [('sum', '<u8'), ('pairs', '<u8')])
@@ -425,6 +426,41 @@ def cover_regions(genomes, tasks, regions, label=None):
     tasks, regions = np.asarray(tasks), np.asarray(regions)
     t = regions['task']
     return cover_rows(genomes.lengths(), tasks['q'][t], tasks['r'][t], regions['qstart'], regions['qend'], label=label)
+
+
+def paint_rows(lengths, q, r, qstart, qend, n_match, label=None, n_groups=None, segments=True, donors=True):
+    """The mosaic painting of the rows (q[i], r[i], qstart[i], qend[i], n_match[i]) -- positions qstart..qend (0-based, inclusive) of
+    object q are aligned to partner r with n_match matching positions -- over objects of the given lengths (vg_paint_rows; DESIGN.md
+    section 15): at every position the covering row of the highest identity wins.  label, n_groups: as in cover_rows; they split the
+    painted positions into `in` and `out`.  -> (records PAINT_STAT_DTYPE[n], segments PAINT_SEGMENT_DTYPE[...] or None with
+    segments=False, donor records PAINT_DONOR_DTYPE[...] or None with donors=False, run_stats dict)."""
+    lp, n = _input(lengths, C.c_int64)
+    (qp, nq), (rp, nr), (sp, ns), (ep, ne), (mp, nm) = (_input(q, C.c_uint32), _input(r, C.c_uint32), _input(qstart, C.c_int32), _input(qend, C.c_int32),
+                                                        _input(n_match, C.c_int32))
+    if not nq == nr == ns == ne == nm:
+        raise ValueError('q, r, qstart, qend and n_match must have the same length')
+    gp, k = None, 0
+    if label is not None:
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if len(label) != n:
+            raise ValueError('label must have one entry per object')
+        gp, k = ptr(label, C.c_int32), int(n_groups) if n_groups is not None else (int(label.max()) + 1 if n else 1)
+    elif n_groups is not None:
+        raise ValueError('n_groups needs label')
+    seg, n_seg, don, n_don, st = C.POINTER(PaintSegment)(), C.c_int64(), C.POINTER(PaintDonor)(), C.c_int64(), PaintRunStats()
+    records, = _filled(n, (PaintStat,), lambda out: check(_lib.load().vg_paint_rows(
+        n, lp, gp, k, qp, rp, sp, ep, mp, nq, out, C.byref(seg) if segments else None, C.byref(n_seg) if segments else None,
+        C.byref(don) if donors else None, C.byref(n_don) if donors else None, C.byref(st))))
+    return (records, _take(seg, n_seg.value, PAINT_SEGMENT_DTYPE) if segments else None,
+            _take(don, n_don.value, PAINT_DONOR_DTYPE) if donors else None, as_dict(st))
+
+
+def paint_regions(genomes, tasks, regions, label=None):
+    """The mosaic painting of a run without any file: tasks and regions as in cover_regions; a region is a row (q, r) of its task with
+    its qstart, qend and n_match.  -> as paint_rows."""
+    tasks, regions = np.asarray(tasks), np.asarray(regions)
+    t = regions['task']
+    return paint_rows(genomes.lengths(), tasks['q'][t], tasks['r'][t], regions['qstart'], regions['qend'], regions['n_match'], label=label)
 
 
 def _rows(q, r, w):

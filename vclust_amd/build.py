@@ -16,7 +16,7 @@ CSRC = PKG_DIR / 'csrc'
 LIB_PATH = PKG_DIR / 'libvclust_gpu.so'
 ORACLE_DIR = ROOT / 'oracle'
 
-SOURCES = ['vg_core.cpp', 'vg_genomes.cpp', 'vg_inflate.cpp', 'vg_io.cpp', 'vg_api.cpp', 'vg_synth.cpp', 'vg_prefilter.hip', 'vg_align.hip', 'vg_dist.hip', 'vg_cluster.hip', 'vg_dedup.hip', 'vg_subset.hip', 'vg_derep.cpp', 'vg_cover.hip']
+SOURCES = ['vg_core.cpp', 'vg_genomes.cpp', 'vg_inflate.cpp', 'vg_io.cpp', 'vg_api.cpp', 'vg_synth.cpp', 'vg_prefilter.hip', 'vg_align.hip', 'vg_dist.hip', 'vg_cluster.hip', 'vg_dedup.hip', 'vg_subset.hip', 'vg_derep.cpp', 'vg_cover.hip', 'vg_paint.hip']
 
 
 def _hipcc() -> str:
@@ -36,7 +36,8 @@ def _stale(target: pathlib.Path, deps) -> bool:
 def build_lib(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """Compile every HIP/C++ source into vclust_amd/libvclust_gpu.so for gfx950."""
     srcs = [CSRC / s for s in SOURCES]
-    deps = srcs + [CSRC / 'vg_common.h', CSRC / 'vg_window.h', ROOT / 'include' / 'vclust_gpu.h']
+    headers = [CSRC / 'vg_common.h', CSRC / 'vg_window.h', CSRC / 'vg_scan.h', ROOT / 'include' / 'vclust_gpu.h']
+    deps = srcs + headers
     if not force and not _stale(LIB_PATH, deps):
         return LIB_PATH
     obj_dir = PKG_DIR / '_obj'
@@ -51,7 +52,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> pathlib.Path:
     for s in srcs:
         o = obj_dir / (s.name + '.o')
         objs.append(o)
-        if force or _stale(o, [s, CSRC / 'vg_common.h', CSRC / 'vg_window.h', ROOT / 'include' / 'vclust_gpu.h']):
+        if force or _stale(o, [s] + headers):
             cmd = [hipcc, *flags, '-x', 'hip', '-c', str(s), '-o', str(o)]
             if verbose:
                 print(' '.join(cmd), file=sys.stderr)

@@ -10,6 +10,7 @@
 //   vg_cluster_stats_file   a clusters.tsv read back, then the per-cluster report of every label column
 // and one on the alignment table of vg_align:
 //   vg_cover_file           the coverage map of every genome (vg_cover_rows)
+//   vg_paint_file           the closest partner of every genome at every position (vg_paint_rows)
 // All are compositions of the finer C-ABI calls (ingest -> HBM -> integer kernels -> writers).
 #include "vg_common.h"
 #include <math.h>
@@ -348,6 +349,50 @@ extern "C" int vg_cover_file(const char* aln_path, const char* ids_path, const c
     if (verbosity >= 1)
         fprintf(stderr, "vg_cover_file: %lld objects, %lld rows (%lld kept), %lld intervals, %lld breakpoints, %lld segments\n", (long long)n,
                 (long long)q.size(), (long long)st.rows_kept, (long long)st.intervals, (long long)st.breakpoints, (long long)st.segments);
+    VG_API_END
+}
+
+// The painting of an alignment table: read as vg_cover_file reads, one array-level call, three writers.
+extern "C" int vg_paint_file(const char* aln_path, const char* ids_path, const char* clusters_path, int clusters_is_repr, const char* column,
+                             const char* out_path, const char* segments_path, const char* donors_path, int num_threads, int verbosity) {
+    VG_API_BEGIN
+    if (!aln_path || !ids_path || !out_path) throw vg_error(VG_EINVAL, "vg_paint_file: null argument");
+    if (column && !clusters_path) throw vg_error(VG_EINVAL, "vg_paint_file: a label column needs a clusters file");
+    vg_host_mark("vg_paint_file: enter");
+    const int n_threads = num_threads > 0 ? num_threads : vg_host_threads();
+    std::vector<std::string> ids; std::vector<int64_t> len;
+    std::vector<uint32_t> q, r; std::vector<int32_t> qs, qe, nm;
+    vg_label_columns cols; size_t c = 0;
+    {
+        device_warmup warm(WARM_CLUSTER);
+        vg_cluster_read_ids(ids_path, ids, &len);
+        if ((int64_t)ids.size() >= (1LL << 31)) throw vg_error(VG_EOVERFLOW, std::string(ids_path) + ": 2^31 or more objects");
+        vg_cover_read_rows(aln_path, ids, len, n_threads, q, r, qs, qe, &nm);
+        vg_host_mark("alignment table parsed");
+        if (clusters_path) {
+            vg_cluster_read_columns(clusters_path, ids, clusters_is_repr != 0, cols);
+            if (column) {
+                c = (size_t)(std::find(cols.names.begin(), cols.names.end(), std::string(column)) - cols.names.begin());
+                if (c == cols.names.size()) throw vg_error(VG_EINVAL, std::string(clusters_path) + ":1: no label column '" + column + "'");
+            }
+            vg_host_mark("clusters.tsv parsed");
+        }
+    }
+    const int64_t n = (int64_t)ids.size();
+    const int32_t* group = clusters_path ? cols.label[c].data() : nullptr;
+    std::vector<vg_paint_stat> stats((size_t)std::max<int64_t>(n, 1));
+    free_guard seg, donor; int64_t n_seg = 0, n_donor = 0;
+    vg_paint_run_stats st{};
+    check(vg_paint_rows(n, len.data(), group, clusters_path ? (int64_t)cols.text[c].size() : 1, q.data(), r.data(), qs.data(), qe.data(), nm.data(),
+                        (int64_t)q.size(), stats.data(), segments_path ? (vg_paint_segment**)&seg.p : nullptr, segments_path ? &n_seg : nullptr,
+                        donors_path ? (vg_paint_donor**)&donor.p : nullptr, donors_path ? &n_donor : nullptr, &st));
+    vg_host_mark("painting computed");
+    vg_paint_write(out_path, ids, group, clusters_path ? &cols.text[c] : nullptr, stats.data(), n_threads);
+    if (segments_path) vg_paint_write_segments(segments_path, ids, (const vg_paint_segment*)seg.p, n_seg, n_threads);
+    if (donors_path) vg_paint_write_donors(donors_path, ids, len, (const vg_paint_donor*)donor.p, n_donor, n_threads);
+    if (verbosity >= 1)
+        fprintf(stderr, "vg_paint_file: %lld objects, %lld rows (%lld kept), %lld breakpoints, %lld levels, %lld segments, %lld donor records\n", (long long)n,
+                (long long)q.size(), (long long)st.rows_kept, (long long)st.breakpoints, (long long)st.levels, (long long)st.segments, (long long)st.donor_records);
     VG_API_END
 }
 

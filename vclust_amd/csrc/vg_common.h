@@ -273,13 +273,23 @@ void vg_cluster_stats_write(const char* path, const char* metric, const std::vec
                             const std::vector<std::vector<vg_cluster_stat>>& stats);
 // coverage stage (vg_io.cpp).  The alignment table against the ids: the columns query, reference, qstart, qend by header name, names
 // matched to ids, positions 1-based inclusive in the file and 0-based in the arrays; VG_EINVAL with file:line on a missing column,
-// an unknown name, a malformed number or a range outside 1..len.  The rows are in file order whatever n_threads is.
+// an unknown name, a malformed number or a range outside 1..len.  The rows are in file order whatever n_threads is.  nm (the painting
+// stage): also the column nt_match into *nm, after the checks alnlen == qend - qstart + 1, nt_match <= alnlen and, if the table has
+// the column, nt_match + nt_mismatch == alnlen.
 void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, const std::vector<int64_t>& len, int n_threads,
-                        std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<int32_t>& qs, std::vector<int32_t>& qe);
+                        std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<int32_t>& qs, std::vector<int32_t>& qe,
+                        std::vector<int32_t>* nm = nullptr);
 // the per-object summary (group / group_text null: one group, printed `-`; group_size per group) and the depth profile
 void vg_cover_write(const char* path, const std::vector<std::string>& ids, const int32_t* group, const std::vector<std::string>* group_text,
                     const std::vector<int64_t>& group_size, const vg_cover_stat* stats, int n_threads);
 void vg_cover_write_segments(const char* path, const std::vector<std::string>& ids, const vg_cover_segment* seg, int64_t n_segments, int n_threads);
+// painting stage (vg_io.cpp): the per-object summary (group / group_text null: printed `-`), the segments with the pident of their
+// winning row, and the donor table with painted / len[object]
+void vg_paint_write(const char* path, const std::vector<std::string>& ids, const int32_t* group, const std::vector<std::string>* group_text,
+                    const vg_paint_stat* stats, int n_threads);
+void vg_paint_write_segments(const char* path, const std::vector<std::string>& ids, const vg_paint_segment* seg, int64_t n_segments, int n_threads);
+void vg_paint_write_donors(const char* path, const std::vector<std::string>& ids, const std::vector<int64_t>& len, const vg_paint_donor* donor, int64_t n_donors,
+                           int n_threads);
 // merge table (vg_cluster.hip): the forest edges of the rows in merge order (a < b, weights non-increasing) -- checks the rows
 // (errors name fn), then the device; the node numbering of the table and the labels of a cut are host loops over those records.
 // algorithm: VG_CLUSTER_SINGLE (the maximum spanning forest), VG_CLUSTER_COMPLETE (the worst edge of every complete-linkage merge)

@@ -969,7 +969,7 @@ void vg_linkage_write(const char* path, const vg_forest& f, const int64_t* node_
 
 // ---------------------------------------------------------------- coverage stage: the alignment table, the two output files
 void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, const std::vector<int64_t>& len, int n_threads,
-                        std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<int32_t>& qs, std::vector<int32_t>& qe) {
+                        std::vector<uint32_t>& q, std::vector<uint32_t>& r, std::vector<int32_t>& qs, std::vector<int32_t>& qe, std::vector<int32_t>* nm) {
     const text_file f(path);
     if (!f.n) row_error(path, 1, "empty file (no header)");
     const char* end = f.end();
@@ -983,7 +983,19 @@ void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, c
         col[k] = (size_t)(std::find(names.begin(), names.end(), std::string_view(wanted[k])) - names.begin());
         if (col[k] == names.size()) row_error(path, 1, std::string("missing column ") + wanted[k]);
     }
-    const size_t max_col = *std::max_element(col, col + 4);
+    size_t max_col = *std::max_element(col, col + 4);
+    // with nm also: 0 alnlen, 1 nt_match, and 2 nt_mismatch if the table has it
+    const char* const counted[3] = { "alnlen", "nt_match", "nt_mismatch" };
+    size_t ccol[3] = { 0, 0, 0 };
+    int n_counted = 0;
+    if (nm) {
+        for (int k = 0; k < 3; ++k) {
+            ccol[k] = (size_t)(std::find(names.begin(), names.end(), std::string_view(counted[k])) - names.begin());
+            if (ccol[k] == names.size()) { if (k < 2) row_error(path, 1, std::string("missing column ") + counted[k]); break; }
+            max_col = std::max(max_col, ccol[k]);
+            n_counted = k + 1;
+        }
+    }
     std::unordered_map<std::string_view, uint32_t> index;
     index.reserve(ids.size() * 2);
     for (size_t i = 0; i < ids.size(); ++i) index.emplace(ids[i], (uint32_t)i);
@@ -997,7 +1009,7 @@ void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, c
         const char* x = std::max(body + (end - body) * t / nthr, cut[(size_t)t - 1]);
         cut[(size_t)t] = x < end ? std::min(end, f.line_end(x) + 1) : end;
     }
-    struct part { std::vector<uint32_t> q, r; std::vector<int32_t> qs, qe; const char* err_at = nullptr; std::string err; };
+    struct part { std::vector<uint32_t> q, r; std::vector<int32_t> qs, qe, nm; const char* err_at = nullptr; std::string err; };
     std::vector<part> parts((size_t)nthr);
     vg_parallel_for(nthr, nthr, [&](int64_t t) {
         part& pt = parts[(size_t)t];
@@ -1025,6 +1037,23 @@ void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, c
                 pt.err = "qstart..qend " + std::to_string(pos[0]) + ".." + std::to_string(pos[1]) + " is not a range inside 1.." + std::to_string(len[obj[0]]);
                 return;
             }
+            if (nm) {
+                uint64_t cnt[3] = { 0, 0, 0 };
+                for (int k = 0; k < n_counted; ++k) {
+                    const std::string_view v = fields[ccol[k]];
+                    const auto rr = std::from_chars(v.data(), v.data() + v.size(), cnt[k]);
+                    if (rr.ec != std::errc() || rr.ptr != v.data() + v.size()) { pt.err_at = a; pt.err = std::string("malformed ") + counted[k] + " '" + std::string(v) + "'"; return; }
+                }
+                const uint64_t span = pos[1] - pos[0] + 1;
+                if (cnt[0] != span) { pt.err_at = a; pt.err = "alnlen " + std::to_string(cnt[0]) + " is not qend - qstart + 1 = " + std::to_string(span); return; }
+                if (cnt[1] > cnt[0]) { pt.err_at = a; pt.err = "nt_match " + std::to_string(cnt[1]) + " > alnlen " + std::to_string(cnt[0]); return; }
+                if (n_counted == 3 && cnt[1] + cnt[2] != cnt[0]) {
+                    pt.err_at = a;
+                    pt.err = "nt_match + nt_mismatch = " + std::to_string(cnt[1] + cnt[2]) + " is not alnlen " + std::to_string(cnt[0]);
+                    return;
+                }
+                pt.nm.push_back((int32_t)cnt[1]);
+            }
             pt.q.push_back(obj[0]); pt.r.push_back(obj[1]); pt.qs.push_back((int32_t)(pos[0] - 1)); pt.qe.push_back((int32_t)(pos[1] - 1));
             a = e + 1;
         }
@@ -1034,6 +1063,10 @@ void vg_cover_read_rows(const char* path, const std::vector<std::string>& ids, c
     for (auto& pt : parts) {
         q.insert(q.end(), pt.q.begin(), pt.q.end()); r.insert(r.end(), pt.r.begin(), pt.r.end());
         qs.insert(qs.end(), pt.qs.begin(), pt.qs.end()); qe.insert(qe.end(), pt.qe.begin(), pt.qe.end());
+    }
+    if (nm) {
+        nm->clear();
+        for (auto& pt : parts) nm->insert(nm->end(), pt.nm.begin(), pt.nm.end());
     }
 }
 
@@ -1069,6 +1102,61 @@ void vg_cover_write_segments(const char* path, const std::vector<std::string>& i
             o += ids[(size_t)seg[k].object];
             snprintf(buf, sizeof buf, "\t%lld\t%lld\t%d\t%d\n", (long long)seg[k].start + 1, (long long)seg[k].end + 1, (int)seg[k].depth_in, (int)seg[k].depth_out);
             o += buf;
+        }
+    });
+}
+
+// ---------------------------------------------------------------- painting stage: the three output files
+void vg_paint_write(const char* path, const std::vector<std::string>& ids, const int32_t* group, const std::vector<std::string>* group_text,
+                    const vg_paint_stat* stats, int n_threads) {
+    const std::string head = "id\tlen\tgroup\tpainted\tpainted_in\tpainted_out\tdonors\ttop_partner\ttop_painted\tswitches\tsegments\tpainted_frac\ttop_frac\n";
+    write_rows(path, head, (int64_t)ids.size(), 1 << 14, n_threads, [&](int64_t lo, int64_t hi, std::string& o) {
+        char buf[64];
+        auto num = [&](int64_t v) { o.push_back('\t'); o += std::to_string(v); };
+        auto quotient = [&](bool have, int64_t a, int64_t b) {
+            o.push_back('\t');
+            if (!have) { o.push_back('-'); return; }
+            snprintf(buf, sizeof buf, "%.6g", (double)a / (double)b);
+            o += buf;
+        };
+        for (int64_t i = lo; i < hi; ++i) {
+            const vg_paint_stat& s = stats[i];
+            o += ids[(size_t)i];
+            num(s.len);
+            o.push_back('\t'); o += group_text ? (*group_text)[(size_t)group[i]] : std::string("-");
+            num(s.painted); num(s.painted_in); num(s.painted_out); num(s.donors);
+            o.push_back('\t'); o += s.top_partner >= 0 ? ids[(size_t)s.top_partner] : std::string("-");
+            num(s.top_painted); num(s.switches); num(s.segments);
+            quotient(s.len > 0, s.painted, s.len); quotient(s.len > 0, s.top_painted, s.len);
+            o.push_back('\n');
+        }
+    });
+}
+
+void vg_paint_write_segments(const char* path, const std::vector<std::string>& ids, const vg_paint_segment* seg, int64_t n_segments, int n_threads) {
+    write_rows(path, "id\tstart\tend\tpartner\tpident\trow_qstart\trow_qend\n", n_segments, 1 << 16, n_threads, [&](int64_t lo, int64_t hi, std::string& o) {
+        char buf[96], pident[64];
+        for (int64_t k = lo; k < hi; ++k) {
+            const vg_paint_segment& g = seg[k];
+            o += ids[(size_t)g.object];
+            o.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%lld\t%lld\t", (long long)g.start + 1, (long long)g.end + 1));
+            if (g.partner < 0) { o += "-\t-\t-\t-\n"; continue; }
+            vg_fmt_num(100.0 * g.n_match / (g.row_qend - g.row_qstart + 1), pident);       // (the expression of the alignment table's pident)
+            o += ids[(size_t)g.partner];
+            o.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%s\t%lld\t%lld\n", pident, (long long)g.row_qstart + 1, (long long)g.row_qend + 1));
+        }
+    });
+}
+
+void vg_paint_write_donors(const char* path, const std::vector<std::string>& ids, const std::vector<int64_t>& len, const vg_paint_donor* donor, int64_t n_donors,
+                           int n_threads) {
+    write_rows(path, "id\tpartner\tpainted\tsegments\tpainted_frac\n", n_donors, 1 << 16, n_threads, [&](int64_t lo, int64_t hi, std::string& o) {
+        char buf[96];
+        for (int64_t k = lo; k < hi; ++k) {
+            const vg_paint_donor& d = donor[k];
+            o += ids[(size_t)d.object]; o.push_back('\t'); o += ids[(size_t)d.partner];
+            o.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%lld\t%lld\t%.6g\n", (long long)d.painted, (long long)d.segments,
+                                           (double)d.painted / (double)len[(size_t)d.object]));
         }
     });
 }

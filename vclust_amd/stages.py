@@ -1,5 +1,5 @@
 """The whole-stage calls of the drop-in CLI (vg_prefilter, vg_align: FASTA on disk -> fltr.txt / ani.tsv on disk; vg_cluster:
-ani.tsv + ids file -> clusters.tsv, vg_cluster_stats_file: the per-cluster report of a clusters.tsv; vg_cover_file: the alignment table of align -> the coverage map; vg_deduplicate: FASTA files -> distinct records + duplicates list) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster|deduplicate` process is
+ani.tsv + ids file -> clusters.tsv, vg_cluster_stats_file: the per-cluster report of a clusters.tsv; vg_cover_file: the alignment table of align -> the coverage map; vg_paint_file: the same table -> the closest partner at every position; vg_deduplicate: FASTA files -> distinct records + duplicates list) as thin ctypes wrappers WITHOUT numpy: a `vclust.py prefilter|align|cluster|deduplicate` process is
 one of these calls, and importing numpy costs it 60-180 ms of its ~1 s.  vclust_amd.api re-exports them beside the
 array-level API."""
 import ctypes as C
@@ -156,6 +156,20 @@ def cover(aln_path, ids_path, out_path, clusters_path=None, clusters_repr=False,
     check(_lib.load().vg_cover_file(path(aln_path), path(ids_path), path(clusters_path), int(bool(clusters_repr)),
                                     None if column is None else str(column).encode(), path(out_path), path(segments_path), int(num_threads),
                                     int(verbosity)))
+
+
+def paint(aln_path, ids_path, out_path, clusters_path=None, clusters_repr=False, column=None, segments_path=None, donors_path=None,
+          num_threads=0, verbosity=0):
+    """The mosaic painting of an alignment table (vg_paint_file): aln_path is the file `align --out-aln` writes,
+    ids_path its ids file.  At every position of a genome the row of the highest identity that covers it wins.  -> out_path: one
+    line per genome (painted positions, donors, the top partner, switches, segments); segments_path: also one line per maximal run
+    of one winning row, with its partner and pident; donors_path: also one line per (genome, winning partner).  clusters_path,
+    clusters_repr and column as in cover(): the groups that split the painted positions into `in` and `out`."""
+    if clusters_path is None and (clusters_repr or column is not None):
+        raise ValueError('clusters_repr and column describe the file of clusters_path: they need clusters_path')
+    check(_lib.load().vg_paint_file(path(aln_path), path(ids_path), path(clusters_path), int(bool(clusters_repr)),
+                                    None if column is None else str(column).encode(), path(out_path), path(segments_path), path(donors_path),
+                                    int(num_threads), int(verbosity)))
 
 
 def deduplicate(paths, out_path, dup_path, prefixes=None, gzip_level=0, num_threads=0, verbosity=0, circular=False, contained=False,
